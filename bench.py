@@ -11,10 +11,15 @@ resident in HBM when the timed region starts.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0) with the driver's fields plus `roofline`, `cpu_baseline` (at every N) and `extra`:
-at N=1 the single-substep kernel, BASELINE config 3, a steady-state figure (960 substeps after 64) and one GPU's share of
-configs 4 and 5; at N>1 configs 4 (N slabs of 500 x 4000) and 5 (N slabs of 1000 x 8000, mixed stiffness, dt 1/128)
-measured in the same run.  `--config4` / `--config5` make those shapes the main workload.
+Prints ONE JSON line (rank 0) with the driver's fields plus `roofline` (from the timed region itself) and `extra` (upload
+time).  A plain run does only that: set up, warm up, time --steps substeps, print.  `--full` adds everything else the
+benchmark measures: `cpu_baseline` (at every N), the read-back and re-upload times, and in `extra` at N=1 the single-substep
+kernel, BASELINE config 3, a steady-state figure (960 substeps after 64) and one GPU's share of configs 4 and 5; at N>1
+configs 4 (N slabs of 500 x 4000) and 5 (N slabs of 1000 x 8000, mixed stiffness, dt 1/128) measured in the same run.
+Without --full `cpu_baseline` is null.  `--config4` / `--config5` make those shapes the main workload.
+
+`--dump-outputs DIR` writes the state the timed path left after its last step, as sb_load_buffers hands it to a caller, to
+DIR/*.npy (see dump_outputs); the scenes are seeded, so two builds given the same arguments can be compared file for file.
 
 N>1: every rank times its own substep launches and ghost refreshes with HIP events on its engine's stream (sb_mark), the
 timed region starts on a refresh boundary and holds at least one refresh whatever --steps is (the ghost depth is lowered to
@@ -78,8 +83,13 @@ def parse():
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="N>1 on a single-GPU box: every rank uses cuda:0 and the process group is gloo (control "
                          "plane only), so the multi-rank code path and the peer exchange can be exercised; not a measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the records of `extra`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline, read-back / re-upload times and the "
+                         "records of `extra` (steady state, single-substep kernel, default collision mode, configs 3, 4 and 5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they computed (particles, beams, counts) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the records of `extra`")
     ap.add_argument("--config4", action="store_true",
                     help="BASELINE config 4 as the main workload: one 500 x 4000 slab per GPU (8 GPUs: the 4000 x 4000 lattice, "
                          "16 M particles), ghost-halo exchange between neighbours")
@@ -520,14 +530,54 @@ def effective_depth(want, steps, width):
     return 1
 
 
+DUMP_PARTICLE_BYTES = 24 << 20    # --dump-outputs: at most 24 MiB of particle rows and 34 MiB of beam rows (< 64 MB in all)
+DUMP_BEAM_BYTES = 34 << 20
+
+
+def dump_sample(n, row_bytes, budget, seed):
+    """Rows 0..n-1 when they fit `budget` bytes, else a fixed seeded sample of as many as fit, in ascending order."""
+    import numpy as np
+    k = budget // row_bytes
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(dirname, out, particles=None, beams=None):
+    """--dump-outputs: what a caller of the timed path receives after its last step (the Buffers that sb_load_buffers filled),
+    in list order: particles.npy float32 (n, 6) = px, py, vx, vy, ax, ay; beams.npy float32 (n, 11) = a, b and the nine floats
+    of layout.BEAM_FLOATS (float64 when a particle index does not fit float32 exactly); counts.npy float64 = the lengths of
+    the two lists before any sampling.  `particles` / `beams` are the data indices to write (default: the live lists of the
+    mapping); more rows than the budget holds are replaced by a fixed seeded sample of them, the same for the same lengths."""
+    import numpy as np
+    from softbody_webgpu_amd.layout import BEAM_FLOATS
+    P, B, maxP = out.particle_count, out.beam_count, out.max_particles
+    if particles is None:
+        particles = out.mapping[:P].astype(np.int64)
+    if beams is None:
+        beams = out.mapping[maxP:maxP + B].astype(np.int64)
+    particles = np.asarray(particles, np.int64)
+    beams = np.asarray(beams, np.int64)
+    os.makedirs(dirname, exist_ok=True)
+    pv = out.particles[particles[dump_sample(particles.size, 6 * 4, DUMP_PARTICLE_BYTES, 1)]].astype(np.float32)
+    wide = maxP >= (1 << 24)
+    bt = np.float64 if wide else np.float32
+    rec = out.beams[beams[dump_sample(beams.size, 11 * np.dtype(bt).itemsize, DUMP_BEAM_BYTES, 2)]]
+    bv = np.stack([rec["a"].astype(bt), rec["b"].astype(bt)] + [rec[f].astype(bt) for f in BEAM_FLOATS], axis=1)
+    np.save(os.path.join(dirname, "particles.npy"), pv)
+    np.save(os.path.join(dirname, "beams.npy"), bv.reshape(-1, 11))
+    np.save(os.path.join(dirname, "counts.npy"), np.array([particles.size, beams.size], np.float64))
+
+
 class Ctx:
     pass
 
 
 def run_workload(ctx, a, W, H, subticks, mixed, mode, steps, warmup, named=None, want_cpu=True, cpu_seconds=None,
-                 readback=False):
+                 readback=False, dump=False):
     """One lattice workload on every rank: scene -> engine -> exchanger -> warm-up -> timed region -> verify.  All ranks
-    call it together; returns the record (rank 0 fills it in, the others get the shared numbers too)."""
+    call it together; returns the record (rank 0 fills it in, the others get the shared numbers too).  `dump`: rank 0 writes
+    --dump-outputs (at N > 1 its own slab's owned particles and beams)."""
     sb, halo, torch, dist = ctx.sb, ctx.halo, ctx.torch, ctx.dist
     rank, world, local, ctl = ctx.rank, ctx.world, ctx.local, ctx.ctl
     d = a.spacing
@@ -645,12 +695,16 @@ def run_workload(ctx, a, W, H, subticks, mixed, mode, steps, warmup, named=None,
                            "note": "device time of sb_peer_exchange (pack into the neighbours' mailboxes, flag handshake, unpack) "
                                    "or of pack + RCCL send/recv + unpack, HIP events on each rank's engine stream, max over ranks; "
                                    "the timed region starts on a refresh boundary"}
-    if readback and world == 1:
+    if dump and a.dump_outputs and world > 1 and rank == 0:
+        dump_outputs(a.dump_outputs, eng.load_buffers(buf.copy()), plan.owned_particles, plan.owned_beams)
+    if (readback or dump and a.dump_outputs) and world == 1:
         out = buf.copy()                       # (the destination; its allocation is not the engine's time)
         t0 = time.perf_counter()
         eng.load_buffers(out)
         rec["readback_ms"] = (time.perf_counter() - t0) * 1e3
-        if not a.no_extra:   # uploads that keep the plan: the state just read back (same topology), and that state with 1 % of the beams cut
+        if dump and a.dump_outputs:
+            dump_outputs(a.dump_outputs, out)
+        if readback and not a.no_extra:   # uploads that keep the plan: the state just read back (same topology), and that state with 1 % of the beams cut
             import numpy as np
             t0 = time.perf_counter()
             eng.write_buffers(out)
@@ -672,7 +726,7 @@ def run_workload(ctx, a, W, H, subticks, mixed, mode, steps, warmup, named=None,
                                        "die on the device); plan_kept = [uploads that kept the plan, of them uploads that removed beams]"}
     eng.destroy()
     rec["cpu_baseline"] = None
-    if want_cpu and rank == 0 and not a.no_cpu_baseline:
+    if want_cpu and a.full and rank == 0 and not a.no_cpu_baseline:
         cb = cpu_baseline(buf, bounds, mode, cpu_seconds or a.cpu_seconds, subticks)
         if world > 1:
             cb["sample"] = ("rank 0's slab only -- ONE GPU's share of the scene, its %d ghost columns included (%d particles); "
@@ -741,7 +795,7 @@ def main():
         line = special_scene(ctx, a, mode)
     else:
         rec = run_workload(ctx, a, a.width, a.height, a.subticks, a.mixed_stiffness, mode, a.steps, a.warmup, named=named,
-                           readback=True)
+                           readback=a.full, dump=True)
         buf, bounds = rec.pop("_buf"), rec.pop("_bounds")
         line = {
             "metric": "particle-steps/sec", "value": rec["value"], "unit": "particle-steps/s",
@@ -762,7 +816,7 @@ def main():
             extra.update({"upload_ms": rec["upload_ms"], "readback_ms": rec.get("readback_ms"),
                           "upload_note": "sb_write_buffers / sb_load_buffers of the whole scene, host buffers <-> HBM, "
                                          "tiling and AoS<->SoA transposes included; never part of `value`"})
-        if not a.no_extra:
+        if a.full and not a.no_extra:
             plain = not (named or shaped or a.mixed_stiffness or a.lattice_on_floor or a.rest_lengths != "lattice")
             if world == 1 and rank == 0:
                 if mode == 0 and line["roofline"] and line["roofline"]["substeps_per_launch"] > 1:
@@ -841,12 +895,18 @@ def special_scene(ctx, a, mode):
                    "tiles": eng.info("tiles"), "grid_builds": eng.info("grid_builds"), "parallelism": "single GPU"},
         "roofline": roofline(eng, kernel_ms, a.steps, P, B, workload),
     }
-    out = buf.copy()
-    t0 = time.perf_counter()
-    eng.load_buffers(out)
-    line["extra"] = {"upload_ms": upload_ms, "readback_ms": (time.perf_counter() - t0) * 1e3}
+    line["extra"] = {"upload_ms": upload_ms, "readback_ms": None}
+    if a.full or a.dump_outputs:
+        out = buf.copy()
+        t0 = time.perf_counter()
+        eng.load_buffers(out)
+        line["extra"]["readback_ms"] = (time.perf_counter() - t0) * 1e3
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, out)
     eng.destroy()
-    line["cpu_baseline"] = None if a.no_cpu_baseline else cpu_baseline(buf, bounds, mode, a.cpu_seconds, a.subticks)
+    line["cpu_baseline"] = None
+    if a.full and not a.no_cpu_baseline:
+        line["cpu_baseline"] = cpu_baseline(buf, bounds, mode, a.cpu_seconds, a.subticks)
     return line
 
 

@@ -1,5 +1,6 @@
 """bench.py's one JSON line (the driver's contract): the keys it must carry, the two extra objects, sane values -- on the real
-workload with few steps, and the N = 2 form started bare on one GPU (the ranks are child processes bench.py starts itself)."""
+workload with few steps, and the N = 2 form started bare on one GPU (the ranks are child processes bench.py starts itself).
+The records beside the headline come with --full; a plain run carries the headline alone and can dump what it computed."""
 import json
 import os
 import subprocess
@@ -39,7 +40,7 @@ def check_roofline(r, blocked, lists=False):
 
 
 def test_default_line_carries_the_contract():
-    d = run_bench("--steps", "60", "--warmup", "12", "--cpu-seconds", "2")
+    d = run_bench("--full", "--steps", "60", "--warmup", "12", "--cpu-seconds", "2")
     for k in KEYS:
         assert k in d, k
     assert d["metric"] == "particle-steps/sec" and d["unit"] == "particle-steps/s" and d["n_gpus"] == 1 and d["steps"] == 60
@@ -73,7 +74,7 @@ def test_default_line_carries_the_contract():
 def test_two_ranks_with_the_drivers_arguments():
     """`--steps 20 --warmup 5` is what the driver runs: the timed region must hold a ghost refresh (at a fixed depth of 30 it
     used to hold none), and the N > 1 line carries `roofline` and `cpu_baseline` like the N = 1 line."""
-    d = run_bench("--gpus", "2", "--rehearse-one-gpu", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2", timeout=1200)
+    d = run_bench("--full", "--gpus", "2", "--rehearse-one-gpu", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2", timeout=1200)
     assert d["n_gpus"] == 2 and d["value"] > 1.0e10 and "REHEARSAL" in d["data"]
     x = d["config"]["exchange"]
     assert x["exchanges_in_timed_region"] >= 1 and x["ghost_depth"] == 20 and x["exchange_us_avg"] > 0 and x["transport"] == "peer"
@@ -90,7 +91,68 @@ def test_two_ranks_with_the_drivers_arguments():
     assert dm["n_gpus"] == 2 and dm["value"] > 1.0e10 and dm["hybrid"]["substeps_in_blocked_launches"] > 0
 
 
-def test_two_ranks_long_region_keeps_the_depth_asked_for():
-    d = run_bench("--gpus", "2", "--rehearse-one-gpu", "--steps", "120", "--warmup", "30", "--no-extra", "--no-cpu-baseline")
+def test_two_ranks_long_region_keeps_the_depth_asked_for(tmp_path):
+    """... and rank 0 dumps its own slab: the 1000 x 1000 particles it owns, none of its ghosts."""
+    import numpy as np
+    out = str(tmp_path / "ranks")
+    d = run_bench("--gpus", "2", "--rehearse-one-gpu", "--steps", "120", "--warmup", "30", "--no-extra", "--no-cpu-baseline",
+                  "--dump-outputs", out)
     assert d["n_gpus"] == 2 and d["value"] > 1.0e10 and "REHEARSAL" in d["data"]
     assert d["config"]["exchange"]["ghost_depth"] == 24 and d["config"]["exchange"]["exchanges_in_timed_region"] == 5
+    got = load_dump(out)
+    assert got["counts"][0] == 1_000_000 and got["particles"].shape == (1_000_000, 6) and np.isfinite(got["particles"]).all()
+    assert got["beams"].shape[1] == 11 and got["counts"][1] > got["beams"].shape[0] > 500_000
+
+
+def load_dump(d):
+    import numpy as np
+    names = sorted(os.listdir(d))
+    assert names == ["beams.npy", "counts.npy", "particles.npy"], names
+    assert sum(os.path.getsize(os.path.join(d, n)) for n in names) <= 64_000_000
+    return {n[:-4]: np.load(os.path.join(d, n)) for n in names}
+
+
+def test_plain_line_is_the_headline_and_its_dump_repeats(tmp_path):
+    """Without --full: the driver's keys, --steps timed steps, no CPU baseline and none of the records of `extra` that take runs
+    of their own; --dump-outputs writes the default scene's state after the last step (all 1 M particles, a fixed sample of the
+    3 M beams), and a second run with the same arguments writes the same bits."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        out = str(tmp_path / ("run%d" % k))
+        d = run_bench("--steps", "20", "--warmup", "5", "--dump-outputs", out)
+        for key in KEYS:
+            assert key in d, key
+        assert d["steps"] == 20 and d["warmup"] == 5 and d["n_gpus"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert d["metric"] == "particle-steps/sec" and d["unit"] == "particle-steps/s" and d["value"] > 1.0e10
+        assert abs(d["value"] - 1_000_000 * 20 / (d["ms_per_step"] * 20 * 1e-3)) / d["value"] < 1e-6
+        assert d["cpu_baseline"] is None and set(d["extra"]) == {"upload_ms", "readback_ms", "upload_note"}
+        check_roofline(d["roofline"], blocked=True)
+        runs.append(load_dump(out))
+    a, b = runs
+    assert a["counts"].tolist() == [1_000_000, 2_996_001]
+    assert a["particles"].dtype == np.float32 and a["particles"].shape == (1_000_000, 6) and np.isfinite(a["particles"]).all()
+    assert a["beams"].dtype == np.float32 and a["beams"].shape[1] == 11 and 500_000 < a["beams"].shape[0] < 2_996_001
+    for n in a:
+        assert a[n].tobytes() == b[n].tobytes(), n
+
+
+def test_dump_is_what_the_timed_path_computed(sb, oracle, tmp_path):
+    """A small lattice through the plain run (5 + 20 substeps) dumps the oracle's state after 25 substeps of the same scene, bit for bit."""
+    import numpy as np
+    out = str(tmp_path / "small")
+    d = run_bench("--width", "40", "--height", "30", "--steps", "20", "--warmup", "5", "--dump-outputs", out)
+    assert d["steps"] == 20 and d["cpu_baseline"] is None
+    got = load_dump(out)
+    buf = sb.scenes.lattice_buffers(40, 30, d=30.0, origin=(1000.0, 1000.0), jitter=1.0, layout=2)
+    ref = oracle.OracleEngine(max(40, 30) * 30.0 + 2000.0, 10.0, 64, 2, oracle.COLLIDE_OFF, threads=4)
+    ref.write_buffers(buf)
+    ref.step(25)
+    exp = ref.load_buffers(buf.copy())
+    P, B, maxP = exp.particle_count, exp.beam_count, exp.max_particles
+    assert got["counts"].tolist() == [P, B] and got["particles"].shape == (P, 6) and got["beams"].shape == (B, 11)
+    assert np.array_equal(got["particles"].view("u4"), exp.particles[exp.mapping[:P].astype(np.int64)].view("u4"))
+    rec = exp.beams[exp.mapping[maxP:maxP + B].astype(np.int64)]
+    assert np.array_equal(got["beams"][:, 0], rec["a"].astype(np.float32)) and np.array_equal(got["beams"][:, 1], rec["b"].astype(np.float32))
+    for i, f in enumerate(sb.layout.BEAM_FLOATS):
+        assert np.array_equal(got["beams"][:, 2 + i].view("u4"), rec[f].view("u4")), f

@@ -15,7 +15,7 @@ python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"
 tail -3 $OUT/pytest_gpu.log
 fi
 if [ $PART = prof ] || [ $PART = all ]; then
-python bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; tail -5 $OUT/bench.err; exit 1; }
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; tail -5 $OUT/bench.err; exit 1; }
 cut -c1-300 $OUT/bench.json
 BENCH="python3 $ROOT/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extra"
 CFG3="python3 $ROOT/bench.py --config3 --steps 200 --warmup 20 --no-cpu-baseline --no-extra"
@@ -43,14 +43,14 @@ prof pmc_write_cfg3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/
 cd $ROOT
 fi
 if [ $PART = bench ] || [ $PART = all ]; then
-python3 bench.py --config3 --no-cpu-baseline > $OUT/bench_config3.json 2>/dev/null || echo "config3 bench failed"
+python3 bench.py --full --config3 --no-cpu-baseline > $OUT/bench_config3.json 2>/dev/null || echo "config3 bench failed"
 python3 bench.py --block-substeps 1 --no-cpu-baseline --no-extra > $OUT/bench_single_substep.json 2>/dev/null || echo "k=1 bench failed"
 python3 bench.py --collisions grid --no-cpu-baseline --no-extra > $OUT/bench_grid.json 2>/dev/null || echo "grid bench failed"
 SB_HYBRID=0 python3 bench.py --collisions grid --no-cpu-baseline --no-extra > $OUT/bench_grid_no_hybrid.json 2>/dev/null || echo "grid bench (no hybrid) failed"
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver_protocol.json 2>/dev/null || echo "driver-protocol bench failed"
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_protocol.json 2>/dev/null || echo "driver-protocol bench failed"
 python3 bench.py --rest-lengths current --no-cpu-baseline --no-extra > $OUT/bench_rest_lengths.json 2>/dev/null || echo "mode-1 bench failed"
 python3 bench.py --lattice-on-floor --no-cpu-baseline --no-extra > $OUT/bench_config3_contacts.json 2>/dev/null || echo "lattice-on-floor bench failed"
-python3 bench.py --soup --no-cpu-baseline > $OUT/bench_soup.json 2>/dev/null || echo "soup bench failed"
+python3 bench.py --full --soup --no-cpu-baseline > $OUT/bench_soup.json 2>/dev/null || echo "soup bench failed"
 python3 tools/config3_contacts_check.py 2>/dev/null | grep -v "amdgpu.ids" > $OUT/config3_contacts_check.txt || echo "config3 check failed"
 # one GPU's share of BASELINE configs 4 (500 x 4000 columns x rows) and 5 (1000 x 8000, mixed springs, dt = 1/128), and 4 M / 16 M particles
 python3 bench.py --no-cpu-baseline --no-extra --width 500 --height 4000 --steps 500 > $OUT/cfg4_share.json 2>/dev/null || echo "cfg4 share failed"
@@ -60,8 +60,8 @@ python3 bench.py --no-cpu-baseline --no-extra --width 4000 --height 4000 --steps
 # multi-GPU pieces that one card can show: cost of one ghost refresh (RCCL vs direct peer stores, loopback)
 # and the whole N=2 bench code path with both ranks on this card, started bare (rehearsal, not a measurement)
 python3 tools/exchange_cost.py 2>/dev/null | grep "^depth" > $OUT/exchange_cost.txt || echo "exchange cost probe failed"
-python3 bench.py --gpus 2 --rehearse-one-gpu --steps 480 --warmup 48 2>/dev/null > $OUT/rehearse_2ranks.json || echo "rehearsal failed"
-python3 bench.py --gpus 2 --rehearse-one-gpu --steps 20 --warmup 5 2>/dev/null > $OUT/rehearse_2ranks_driver_protocol.json || echo "rehearsal (driver protocol) failed"
+python3 bench.py --full --gpus 2 --rehearse-one-gpu --steps 480 --warmup 48 2>/dev/null > $OUT/rehearse_2ranks.json || echo "rehearsal failed"
+python3 bench.py --full --gpus 2 --rehearse-one-gpu --steps 20 --warmup 5 2>/dev/null > $OUT/rehearse_2ranks_driver_protocol.json || echo "rehearsal (driver protocol) failed"
 # ... the same two ranks with the engine's default collision mode (hash on: blocked launches between the ghost refreshes since r04)
 python3 bench.py --gpus 2 --rehearse-one-gpu --collisions grid --steps 480 --warmup 48 --no-cpu-baseline --no-extra 2>/dev/null > $OUT/rehearse_2ranks_grid.json || echo "rehearsal (grid) failed"
 # the spatial hash's two schedules on the config-3 scenes (lagged by default, classic forced)
