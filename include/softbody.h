@@ -19,7 +19,7 @@
  *     (src/lock.ts:4-19; engineWorker.ts:553,584,632).  When do calls return?
  *       SB_COLLIDE_OFF / SB_COLLIDE_ALLPAIRS, and SB_PATH_ATOMIC with any collision mode:
  *         sb_step / sb_frame / sb_delete_pass only ENQUEUE work on the engine's HIP stream;
- *         sb_sync, sb_load_buffers and sb_step_timed wait for it.
+ *         sb_sync, sb_load_buffers, sb_step_timed and sb_render wait for it.
  *       SB_COLLIDE_GRID on the tiled path (the default of sb_default_options): sb_step and
  *         sb_frame MAY WAIT for the stream, like every call of the reference does
  *         (engineWorker.ts:632-633,686-688: `await queue.onSubmittedWorkDone()` on both
@@ -34,6 +34,7 @@
  *         2.4 ms of its 2.4 ms (a Node host should call from a worker thread, as the
  *         reference itself does: engine.ts:138).  sb_delete_pass, sb_write_user_input
  *         and the sb_halo_* / sb_peer_* calls still only enqueue.
+ *       Any collision mode and path: sb_render waits for the stream, sb_render_device only enqueues.
  *       A wait POLLS the stream for as long as the work in flight should take (busily for
  *         the first 8 ms, then every ~50 us between short sleeps; 0.2 s at most) before it
  *         parks the thread: being woken costs 0.2 - 0.5 ms on some hosts, more than many
@@ -199,7 +200,8 @@ sb_status sb_get_counts(sb_engine *e, uint32_t *particles, uint32_t *beams);
 /* introspection for benches/tests: key = "path", "tiles", "beam_copies", "halo_particles",
  * "device_bytes", "substeps_done", "kernels_per_substep", "substep_hbm_bytes" (the HBM bytes one substep
  * launch has to move with the data layout the engine holds: the launched kernel's own compulsory traffic),
- * "grid_cells", "grid_builds", "grid_wide", "grid_skin_x1000", "material_mode", "materials", "local_index_bits". */
+ * "grid_cells", "grid_builds", "grid_wide", "grid_skin_x1000", "material_mode", "materials", "local_index_bits",
+ * "render_table_build_us" (host time of sb_render's last draw-table build: the first render after an upload). */
 sb_status sb_get_info(sb_engine *e, const char *key, uint64_t *value);
 
 /* ---- multi-GPU halo exchange; one engine per rank/GPU, each holding its
@@ -293,6 +295,32 @@ sb_status sb_partition_peer_counts(const sb_partition *p, uint32_t rank, uint32_
 /* ... and the lists themselves, LOCAL data indices in the order sb_halo_configure expects (any pointer may be NULL) */
 sb_status sb_partition_peer_lists(const sb_partition *p, uint32_t rank, uint32_t j, uint32_t *ghost_particles, uint32_t *send_particles,
                                   uint32_t *ghost_beams, uint32_t *send_beams);
+
+/* ---- pictures of the state (the reference's render pass, engineWorker.ts:666-683) ----
+ * The picture is that of the headless renderer host/render.js, renderPPM(mapper, {resolution, boundsSize, particleRadius})
+ * with `mapper` holding what sb_load_buffers would return at this point of the stream, BYTE FOR BYTE: the PPM body, RGB8,
+ * resolution^2 * 3 bytes, rows top to bottom, no "P6" header.  One disc per particle slot (inner (0,89,128) within 0.8 r,
+ * white ring up to r), then one line per live beam slot coloured by its stress / strain, later slots over earlier ones.
+ * The engine evaluates render.js's double arithmetic step for step and resolves "last writer wins" by an integer max over
+ * per-pixel keys, so the bytes do not depend on the schedule.  Where render.js does not terminate (a particle with an
+ * infinite coordinate, a beam with a non-finite endpoint coordinate, or pixel coordinates of 2^53 and beyond) the engine
+ * draws nothing for that primitive; a particle with a NaN coordinate draws nothing in both.
+ * Zero fields mean: resolution 512 (render.js's default); bounds_size and particle_radius those of sb_options.
+ * Errors: SB_ERR_STATE before an upload; SB_ERR_INVALID for a resolution above 16384 or a buffer smaller than
+ * resolution^2 * 3 bytes; SB_ERR_UNSUPPORTED on an engine with ghost zones configured (ranks are not composited).
+ * A render only reads the state: it changes nothing a later step, frame or read-back computes.
+ * sb_render WAITS for the stream and copies into host memory; sb_render_device only ENQUEUES on the engine's stream
+ * and writes into device memory (a torch tensor, say), which must stay valid until that work has run. */
+#define SB_RENDER_MAX_RESOLUTION 16384
+typedef struct sb_render_options {
+    uint32_t struct_size;    /* = sizeof(sb_render_options); 0 or a NULL pointer = all defaults */
+    uint32_t resolution;     /* picture is resolution x resolution pixels; 0 = 512 */
+    double bounds_size;      /* world units across the picture; 0 = sb_options.bounds_size */
+    double particle_radius;  /* disc radius in world units; 0 = sb_options.particle_radius */
+    uint32_t reserved[4];
+} sb_render_options;
+sb_status sb_render(sb_engine *e, const sb_render_options *opts, void *rgb, size_t rgb_bytes);
+sb_status sb_render_device(sb_engine *e, const sb_render_options *opts, void *device_rgb);
 
 /* the engine's hipStream_t, so a caller can order its own work (RCCL send/recv) after it. */
 sb_status sb_get_stream(sb_engine *e, void **hip_stream);

@@ -671,6 +671,7 @@ sb_status sb_destroy(sb_engine *e)
     (void)hipStreamSynchronize(e->stream);
     reap_join(e);
     free_scene(e);
+    sbr_release(e);
     for (const auto &b : e->pool_free) (void)hipFree(b.first);
     e->pool_free.clear();
     if (e->dev_err) (void)hipHostFree(e->dev_err);
@@ -2040,6 +2041,7 @@ sb_status sb_get_info(sb_engine *e, const char *key, uint64_t *value)
     else if (k == "substeps_done") *value = e->substeps_done;
     else if (k == "lds_bytes") *value = e->lds_bytes;
     else if (k == "uploads_kept") *value = e->uploads_kept;
+    else if (k == "render_table_build_us") *value = (uint64_t)(sbr_last_build_ms(e) * 1000.0 + 0.5); // sb_render's last draw-table build (host time)
     else if (k == "kernels_per_substep") // (the hash's helper launch runs in the classic schedule only: sb_physics.h SbGridCtl)
         *value = (e->path == SB_PATH_TILED ? 1 : 2) + (e->opt.collision_mode == SB_COLLIDE_GRID && sbk_grid_mode(e) == SB_GRID_CLASSIC ? 1 : 0);
     else if (k == "grid_aborts") *value = e->grid_aborts;                   // lagged launches whose tail found the lists not known to be valid any more (host recovery)
@@ -2365,6 +2367,7 @@ sb_status sb_write_buffers(sb_engine *e, const void *metadata, size_t metadata_b
                            size_t mapping_bytes, const void *particles, size_t particles_bytes,
                            const void *beams, size_t beams_bytes)
 {
+    sbr_invalidate(e);
     SB_GUARDED(e, sb_write_buffers_impl(e, metadata, metadata_bytes, mapping, mapping_bytes, particles, particles_bytes,
                                         beams, beams_bytes))
 }

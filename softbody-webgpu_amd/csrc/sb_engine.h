@@ -220,6 +220,8 @@ struct sb_engine {
     int stage_cur = 0;
     std::thread reaper;               // frees the host arrays of the last upload (sb_api.hip: SbUploadTrash)
 
+    struct SbRenderState *rs = nullptr; // sb_render.hip: draw tables (rebuilt at the first render after an upload) + key image
+
     size_t device_bytes = 0;
     std::vector<void *> allocs;                             // freed with the scene (not pooled)
     std::vector<std::pair<void *, size_t>> pool_used, pool_free; // device blocks of the scene / kept for the next upload (sb_api.hip dev_alloc)
@@ -243,3 +245,7 @@ void sbk_launch_delete_blocked(sb_engine *e);
 void sbk_hybrid_to_blocked(sb_engine *e);
 void sbk_hybrid_to_tiled(sb_engine *e, bool aux);
 void sbk_hybrid_launch(sb_engine *e, const uint32_t *ks, uint32_t count, bool aux_last);
+// sb_render.hip
+void sbr_invalidate(sb_engine *e);      // an upload replaced the scene: the next render builds its draw tables again
+void sbr_release(sb_engine *e);         // everything sb_render allocated (sb_destroy)
+double sbr_last_build_ms(const sb_engine *e);

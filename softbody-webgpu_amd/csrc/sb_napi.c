@@ -74,6 +74,7 @@ static struct {
                               const uint32_t *, const uint32_t *, uint32_t);
     sb_status (*peer_exchange)(sb_engine *);
     sb_status (*get_stream)(sb_engine *, void **);
+    sb_status (*render)(sb_engine *, const sb_render_options *, void *, size_t);
     sb_status (*partition_create)(uint32_t, uint32_t, uint32_t, const void *, const void *, const void *, const void *, uint32_t,
                                   uint32_t, float, sb_partition **);
     sb_status (*partition_destroy)(sb_partition *);
@@ -169,6 +170,7 @@ static napi_value js_load(napi_env env, napi_callback_info info)
     SYM(peer_connect, "sb_peer_connect");
     SYM(peer_exchange, "sb_peer_exchange");
     SYM(get_stream, "sb_get_stream");
+    SYM(render, "sb_render");
     SYM(partition_create, "sb_partition_create");
     SYM(partition_destroy, "sb_partition_destroy");
     SYM(partition_rank_counts, "sb_partition_rank_counts");
@@ -873,6 +875,47 @@ static napi_value js_partition_peer(napi_env env, napi_callback_info info)
     return obj;
 }
 
+/* render(handle, {resolution, boundsSize, particleRadius}) -> Buffer: the binary PPM host/render.js renderPPM returns for the
+ * state sb_load_buffers would read back ("P6" header included), drawn on the GPU by sb_render.  Absent / 0 fields: 512 and the
+ * engine's own bounds / radius. */
+static napi_value js_render(napi_env env, napi_callback_info info)
+{
+    if (!need_lib(env)) return NULL;
+    size_t argc = 2;
+    napi_value argv[2];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    sb_engine *e = argc >= 1 ? get_engine(env, argv[0]) : NULL;
+    if (!e) return NULL;
+    sb_render_options o;
+    memset(&o, 0, sizeof o);
+    o.struct_size = sizeof o;
+    double res = 512.0;
+    if (argc >= 2) {
+        napi_valuetype t;
+        CHECK_NAPI(napi_typeof(env, argv[1], &t));
+        if (t == napi_object) {
+            (void)opt_number(env, argv[1], "resolution", &res);
+            (void)opt_number(env, argv[1], "boundsSize", &o.bounds_size);
+            (void)opt_number(env, argv[1], "particleRadius", &o.particle_radius);
+        }
+    }
+    if (!(res >= 1.0 && res <= SB_RENDER_MAX_RESOLUTION) || res != (double)(uint32_t)res) {
+        napi_throw_range_error(env, NULL, "render: resolution must be an integer in 1 .. 16384");
+        return NULL;
+    }
+    o.resolution = (uint32_t)res;
+    char head[48];
+    const int hl = snprintf(head, sizeof head, "P6\n%u %u\n255\n", o.resolution, o.resolution);
+    const size_t body = (size_t)o.resolution * o.resolution * 3;
+    void *data = NULL;
+    napi_value out;
+    CHECK_NAPI(napi_create_buffer(env, (size_t)hl + body, &data, &out));
+    memcpy(data, head, (size_t)hl);
+    sb_status st = sb.render(e, &o, (uint8_t *)data + hl, body);
+    if (st != SB_OK) return throw_status(env, e, st, "sb_render");
+    return out;
+}
+
 static napi_value init(napi_env env, napi_value exports)
 {
     static const struct { const char *name; napi_callback fn; } fns[] = {
@@ -888,7 +931,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"peerConnect", js_peer_connect}, {"peerExchange", js_peer_exchange}, {"haloDeleteGhosts", js_halo_delete_ghosts},
         {"partitionCreate", js_partition_create}, {"partitionDestroy", js_partition_destroy},
         {"partitionRankCounts", js_partition_rank_counts}, {"partitionRankScene", js_partition_rank_scene},
-        {"partitionRankIds", js_partition_rank_ids}, {"partitionPeer", js_partition_peer},
+        {"partitionRankIds", js_partition_rank_ids}, {"partitionPeer", js_partition_peer}, {"render", js_render},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

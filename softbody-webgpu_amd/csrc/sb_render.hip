@@ -1,0 +1,492 @@
+// sb_render.hip -- pictures of the state (sb_render / sb_render_device of include/softbody.h) for gfx950 (CDNA4, wave64).
+//
+// The picture is host/render.js's renderPPM of what sb_load_buffers would return, byte for byte.  render.js
+// draws particle slots 0 .. P-1, then beam slots 0 .. B-1 over them, and a pixel shows the last primitive that `put` it.
+// Here every put is an atomicMax of a 64-bit key that orders the primitives as render.js draws them:
+//     0                                   black
+//     1 << 62 | particle slot << 1 | ring  (ring = 1: white, 0: inner colour; a slot puts a pixel at most once)
+//     2 << 62 | engine beam slot          (strictly increasing in the caller's slot, sb_engine.h h_user_slot)
+// so the result is that of render.js's order for any schedule, and a resolve pass turns keys into RGB8.
+// Every double operation of render.js is restated in the same order in double (the library builds with -ffp-contract=off):
+// toPx(v) = v / S * res, the box floor / ceil, the pixel centre (p + 0.5) / res * S, V8's Math.hypot (scaled, Kahan-summed),
+// the line points floor(a + (b - a) * k / n).  Beams are clipped exactly: every point coordinate is monotone in k (each rounded
+// operation is), so the k whose points land in the image form an interval, found by bisection.
+//
+// Where render.js does not terminate the engine draws nothing: a particle with an infinite coordinate (or a box bound of
+// magnitude 2^53 or more: `p++` stops counting there), a beam with a non-finite endpoint coordinate or with n >= 2^53 points;
+// a NaN centre draws nothing in both.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <stdexcept>
+#include <vector>
+
+#include "sb_engine.h"
+
+#define SBR_BLOCK 256
+#define SBR_INLINE_PIXELS 64u // a particle's clipped box up to this many pixels is drawn by its own thread, larger ones by a wave
+#define SBR_INLINE_POINTS 32u // the same for a beam's clipped points
+#define SBR_WIDE_BLOCKS 2048u // workgroups of the wave-per-primitive kernels (they stride over the list)
+
+static const double kTwo53 = 9007199254740992.0;
+static const uint64_t kKeyParticle = 1ull << 62, kKeyBeam = 2ull << 62;
+
+struct SbrArgs {
+    double S, r, r08, res; // bounds, radius, radius * 0.8, resolution (render.js numbers)
+    uint32_t nres;         // resolution as an integer
+};
+
+// what sb_render keeps between calls (sb_engine.h rs): the draw tables of the scene of the latest upload (built at the first
+// render after it) and the key image (kept until sb_destroy or a larger resolution; not in the scene pool)
+struct SbRenderState {
+    bool valid = false;             // the tables belong to the scene on the device (sb_write_buffers clears this)
+    uint32_t nbeam_slots = 0;       // engine beam slots the tables cover
+    uint2 *d_ends = nullptr;        // per engine beam slot: internal particle indices of A and B; x = 0xFFFFFFFF: not drawn
+    uint32_t *d_copy = nullptr;     // per engine beam slot: the copy whose strain / stress is read back for it
+    size_t cap_ends = 0, cap_copy = 0;
+    uint32_t *d_wide_p = nullptr;   // particles whose clipped box is drawn by a wave
+    uint4 *d_wide_b = nullptr;      // beams whose clipped range is drawn by a wave: slot, count, first k (u64)
+    size_t cap_wide_p = 0, cap_wide_b = 0;
+    uint32_t *d_count = nullptr;    // [2] lengths of the two lists
+    unsigned long long *d_keys = nullptr;
+    size_t cap_keys = 0;            // pixels
+    uint8_t *d_rgb = nullptr;       // sb_render's picture on its way to the host
+    size_t cap_rgb = 0;
+    double build_ms = 0.0;          // host time of the last table build
+};
+
+// ---------------------------------------------------------------- device arithmetic (render.js, in its order)
+
+// V8's Math.hypot for two finite arguments: both scaled by the larger magnitude, squares summed with Kahan compensation
+__device__ __forceinline__ double sbr_hypot(double a, double b)
+{
+    const double x = fabs(a), y = fabs(b);
+    double mx = 0.0;
+    if (x > mx) mx = x;
+    if (y > mx) mx = y;
+    if (mx == 0.0) return 0.0;
+    double sum = 0.0, comp = 0.0;
+    {
+        const double n = x / mx;
+        const double summand = n * n - comp;
+        const double pre = sum + summand;
+        comp = (pre - sum) - summand;
+        sum = pre;
+    }
+    {
+        const double n = y / mx;
+        const double summand = n * n - comp;
+        const double pre = sum + summand;
+        comp = (pre - sum) - summand;
+        sum = pre;
+    }
+    return sqrt(sum) * mx;
+}
+
+__device__ __forceinline__ double sbr_to_px(double v, const SbrArgs &a) { return v / a.S * a.res; }
+
+__device__ __forceinline__ void sbr_put(unsigned long long *keys, uint32_t res, uint32_t px, uint32_t py, unsigned long long key)
+{
+    if (px < res && py < res) atomicMax(keys + (size_t)(res - 1 - py) * res + px, key); // row res-1-py: render.js's y flip
+}
+
+// one pixel of a particle's box
+__device__ __forceinline__ void sbr_disc_pixel(unsigned long long *keys, const SbrArgs &a, double cx, double cy, uint32_t px,
+                                               uint32_t py, unsigned long long base)
+{
+    const double wx = ((double)px + 0.5) / a.res * a.S, wy = ((double)py + 0.5) / a.res * a.S;
+    const double d = sbr_hypot(wx - cx, wy - cy);
+    if (d < a.r08) sbr_put(keys, a.nres, px, py, base);
+    else if (d < a.r) sbr_put(keys, a.nres, px, py, base | 1ull);
+}
+
+// the particle's box clipped to the image; false: nothing to draw (including where render.js does not terminate)
+__device__ __forceinline__ bool sbr_box(const SbrArgs &a, float2 p, uint32_t &x0, uint32_t &x1, uint32_t &y0, uint32_t &y1)
+{
+    const double cx = p.x, cy = p.y;
+    if (!(isfinite(cx) && isfinite(cy))) return false;
+    const double X0 = floor(sbr_to_px(cx - a.r, a)), X1 = ceil(sbr_to_px(cx + a.r, a));
+    const double Y0 = floor(sbr_to_px(cy - a.r, a)), Y1 = ceil(sbr_to_px(cy + a.r, a));
+    if (!(Y0 <= Y1)) return false; // no row (NaN bounds included)
+    if (!(fabs(Y0) < kTwo53 && fabs(Y1) < kTwo53)) return false;
+    if (!(X0 <= X1)) return false;
+    if (!(fabs(X0) < kTwo53 && fabs(X1) < kTwo53)) return false;
+    const double hi = a.res - 1.0;
+    const double cx0 = fmax(X0, 0.0), cx1 = fmin(X1, hi), cy0 = fmax(Y0, 0.0), cy1 = fmin(Y1, hi);
+    if (cx0 > cx1 || cy0 > cy1) return false;
+    x0 = (uint32_t)cx0, x1 = (uint32_t)cx1, y0 = (uint32_t)cy0, y1 = (uint32_t)cy1;
+    return true;
+}
+
+// ---------------------------------------------------------------- kernels
+
+// a thread per particle: small boxes in place, large ones onto the wave list
+__global__ __launch_bounds__(SBR_BLOCK) void k_render_particles(const float2 *__restrict__ pos, const uint32_t *__restrict__ pslot,
+                                                                uint32_t P, SbrArgs a, unsigned long long *keys, uint32_t *wide,
+                                                                uint32_t *count)
+{
+    const uint32_t j = blockIdx.x * SBR_BLOCK + threadIdx.x;
+    if (j >= P) return;
+    const float2 p = pos[j];
+    uint32_t x0, x1, y0, y1;
+    if (!sbr_box(a, p, x0, x1, y0, y1)) return;
+    if ((uint64_t)(x1 - x0 + 1) * (y1 - y0 + 1) > SBR_INLINE_PIXELS) {
+        wide[atomicAdd(count, 1u)] = j;
+        return;
+    }
+    const unsigned long long base = kKeyParticle | ((unsigned long long)pslot[j] << 1);
+    for (uint32_t py = y0; py <= y1; py++)
+        for (uint32_t px = x0; px <= x1; px++) sbr_disc_pixel(keys, a, p.x, p.y, px, py, base);
+}
+
+// a wave per listed particle, its lanes over the clipped box
+__global__ __launch_bounds__(SBR_BLOCK) void k_render_particles_wide(const float2 *__restrict__ pos, const uint32_t *__restrict__ pslot,
+                                                                     SbrArgs a, unsigned long long *keys, const uint32_t *wide,
+                                                                     const uint32_t *count)
+{
+    const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (SBR_BLOCK / 64);
+    const uint32_t n = *count;
+    for (uint32_t i = blockIdx.x * (SBR_BLOCK / 64) + threadIdx.x / 64u; i < n; i += waves) {
+        const uint32_t j = wide[i];
+        const float2 p = pos[j];
+        uint32_t x0, x1, y0, y1;
+        if (!sbr_box(a, p, x0, x1, y0, y1)) continue; // (true: it was listed)
+        const uint32_t w = x1 - x0 + 1, h = y1 - y0 + 1;
+        const unsigned long long base = kKeyParticle | ((unsigned long long)pslot[j] << 1);
+        for (uint64_t q = lane; q < (uint64_t)w * h; q += 64u)
+            sbr_disc_pixel(keys, a, p.x, p.y, x0 + (uint32_t)(q % w), y0 + (uint32_t)(q / w), base);
+    }
+}
+
+// a point of a beam: floor(a + (b - a) * k / n)
+__device__ __forceinline__ double sbr_point(double a0, double d, double k, double n) { return floor(a0 + d * k / n); }
+
+// smallest k in [lo, hi] with pred(k) (pred false ... true over k), hi + 1 if none
+template <typename F>
+__device__ __forceinline__ uint64_t sbr_first(uint64_t lo, uint64_t hi, F pred)
+{
+    uint64_t l = lo, h = hi + 1; // answer in [l, h]
+    while (l < h) {
+        const uint64_t m = l + (h - l) / 2;
+        if (pred(m)) h = m;
+        else l = m + 1;
+    }
+    return l;
+}
+
+// the k range [k0, k0 + cnt) of one coordinate's points inside [0, res-1]; the coordinate is monotone in k
+__device__ __forceinline__ void sbr_clip_axis(double a0, double d, double n, uint64_t N, double hi, uint64_t &klo, uint64_t &khi)
+{
+    if (d >= 0.0) { // non-decreasing (d = 0: constant)
+        klo = sbr_first(0, N, [&](uint64_t k) { return sbr_point(a0, d, (double)k, n) >= 0.0; });
+        const uint64_t past = sbr_first(0, N, [&](uint64_t k) { return sbr_point(a0, d, (double)k, n) > hi; });
+        khi = past; // exclusive
+    } else {        // non-increasing
+        klo = sbr_first(0, N, [&](uint64_t k) { return sbr_point(a0, d, (double)k, n) <= hi; });
+        khi = sbr_first(0, N, [&](uint64_t k) { return sbr_point(a0, d, (double)k, n) < 0.0; });
+    }
+}
+
+struct SbrLine {
+    double ax, ay, dx, dy, n;
+};
+
+// the beam's line; false: nothing to draw
+__device__ __forceinline__ bool sbr_line(const SbrArgs &a, float2 A, float2 B, SbrLine &l)
+{
+    l.ax = sbr_to_px(A.x, a);
+    l.ay = sbr_to_px(A.y, a);
+    const double bx = sbr_to_px(B.x, a), by = sbr_to_px(B.y, a);
+    if (!(isfinite(l.ax) && isfinite(l.ay) && isfinite(bx) && isfinite(by))) return false;
+    l.dx = bx - l.ax;
+    l.dy = by - l.ay;
+    const double m = ceil(fmax(fabs(l.dx), fabs(l.dy))); // (finite operands: fmax = Math.max)
+    l.n = m > 1.0 ? m : 1.0;
+    return l.n < kTwo53;
+}
+
+// a thread per engine beam slot: the clipped k range, short ranges in place, long ones onto the wave list
+__global__ __launch_bounds__(SBR_BLOCK) void k_render_beams(const float2 *__restrict__ pos, const uint2 *__restrict__ ends,
+                                                            const uint32_t *__restrict__ dead, uint32_t B, SbrArgs a,
+                                                            unsigned long long *keys, uint4 *wide, uint32_t *count)
+{
+    const uint32_t s = blockIdx.x * SBR_BLOCK + threadIdx.x;
+    if (s >= B) return;
+    const uint2 en = ends[s];
+    if (en.x == 0xFFFFFFFFu || (dead && dead[s])) return;
+    SbrLine l;
+    if (!sbr_line(a, pos[en.x], pos[en.y], l)) return;
+    const uint64_t N = (uint64_t)l.n;
+    const double hi = a.res - 1.0;
+    uint64_t k0 = 0, k1 = N + 1; // [k0, k1)
+    const double x0 = sbr_point(l.ax, l.dx, 0.0, l.n), xN = sbr_point(l.ax, l.dx, l.n, l.n);
+    const double y0 = sbr_point(l.ay, l.dy, 0.0, l.n), yN = sbr_point(l.ay, l.dy, l.n, l.n);
+    if (!(x0 >= 0.0 && x0 <= hi && xN >= 0.0 && xN <= hi && y0 >= 0.0 && y0 <= hi && yN >= 0.0 && yN <= hi)) {
+        uint64_t xl, xh, yl, yh;
+        sbr_clip_axis(l.ax, l.dx, l.n, N, hi, xl, xh);
+        sbr_clip_axis(l.ay, l.dy, l.n, N, hi, yl, yh);
+        k0 = xl > yl ? xl : yl;
+        k1 = xh < yh ? xh : yh;
+        if (k0 >= k1) return;
+    }
+    const uint64_t cnt = k1 - k0;
+    if (cnt > SBR_INLINE_POINTS) {
+        wide[atomicAdd(count, 1u)] = make_uint4(s, (uint32_t)cnt, (uint32_t)k0, (uint32_t)(k0 >> 32));
+        return;
+    }
+    const unsigned long long key = kKeyBeam | s;
+    for (uint64_t k = k0; k < k1; k++)
+        sbr_put(keys, a.nres, (uint32_t)sbr_point(l.ax, l.dx, (double)k, l.n), (uint32_t)sbr_point(l.ay, l.dy, (double)k, l.n), key);
+}
+
+// a wave per listed beam, its lanes over the clipped points (at most ~2 per pixel along the major axis: cnt < 2^32)
+__global__ __launch_bounds__(SBR_BLOCK) void k_render_beams_wide(const float2 *__restrict__ pos, const uint2 *__restrict__ ends,
+                                                                 SbrArgs a, unsigned long long *keys, const uint4 *wide,
+                                                                 const uint32_t *count)
+{
+    const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (SBR_BLOCK / 64);
+    const uint32_t n = *count;
+    for (uint32_t i = blockIdx.x * (SBR_BLOCK / 64) + threadIdx.x / 64u; i < n; i += waves) {
+        const uint4 w = wide[i];
+        const uint2 en = ends[w.x];
+        SbrLine l;
+        if (!sbr_line(a, pos[en.x], pos[en.y], l)) continue; // (true: it was listed)
+        const uint64_t k0 = (uint64_t)w.z | ((uint64_t)w.w << 32);
+        const unsigned long long key = kKeyBeam | w.x;
+        for (uint32_t q = lane; q < w.y; q += 64u) {
+            const double k = (double)(k0 + q);
+            sbr_put(keys, a.nres, (uint32_t)sbr_point(l.ax, l.dx, k, l.n), (uint32_t)sbr_point(l.ay, l.dy, k, l.n), key);
+        }
+    }
+}
+
+// render.js's byte of a Float32Array component: Math.round(clamp01(c) * 255), NaN -> 0 (Buffer stores ToUint8(NaN) = 0)
+__device__ __forceinline__ uint32_t sbr_byte(float c)
+{
+    const double v = c;
+    if (v != v) return 0u;
+    const double cl = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
+    return (uint32_t)floor(cl * 255.0 + 0.5); // exact: a float times 255 has at most 32 significant bits
+}
+
+// JS Math.max(0, Math.min(1, v)) (NaN stays NaN), then the Float32Array store
+__device__ __forceinline__ float sbr_clamp01_f32(double v)
+{
+    if (v != v) return __builtin_nan("");
+    return (float)(v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v));
+}
+
+// key -> RGB8, one pixel per thread (keys are stored in output row order already)
+__global__ __launch_bounds__(SBR_BLOCK) void k_render_resolve(const unsigned long long *__restrict__ keys, size_t npix,
+                                                              const uint32_t *__restrict__ copy, const float *__restrict__ strain,
+                                                              const float *__restrict__ stress, uint8_t *rgb)
+{
+    const size_t i = (size_t)blockIdx.x * SBR_BLOCK + threadIdx.x;
+    if (i >= npix) return;
+    const unsigned long long key = keys[i];
+    uint32_t r = 0, g = 0, b = 0;
+    if ((key >> 62) == 1u) {
+        if (key & 1ull) r = g = b = 255u;          // ring (1, 1, 1)
+        else r = 0u, g = 89u, b = 128u;            // inner (0, 0.35, 0.5): f32(0.35) * 255 = 89.25, 0.5 * 255 = 127.5
+    } else if ((key >> 62) == 2u) {
+        const uint32_t c = copy[(uint32_t)key];
+        const double sn = strain[c], ss = stress[c];
+        r = sbr_byte(sbr_clamp01_f32(ss + 1.0));
+        g = sbr_byte(sbr_clamp01_f32(1.0 - ss));
+        const double bb = 1.0 - fabs(sn);
+        b = sbr_byte(bb != bb ? __builtin_nanf("") : (float)(bb < 0.0 ? 0.0 : bb)); // Math.max(0, .) keeps NaN
+    }
+    rgb[i * 3 + 0] = (uint8_t)r;
+    rgb[i * 3 + 1] = (uint8_t)g;
+    rgb[i * 3 + 2] = (uint8_t)b;
+}
+
+// ---------------------------------------------------------------- host side
+
+#define SBR_FAIL(e, code, ...)                            \
+    do {                                                  \
+        char _buf[512];                                   \
+        snprintf(_buf, sizeof _buf, __VA_ARGS__);         \
+        (e)->err = _buf;                                  \
+        return (code);                                    \
+    } while (0)
+#define SBR_HIP(e, call)                                                                                       \
+    do {                                                                                                       \
+        hipError_t _r = (call);                                                                                \
+        if (_r != hipSuccess) {                                                                                \
+            (void)hipGetLastError();                                                                           \
+            SBR_FAIL(e, _r == hipErrorOutOfMemory ? SB_ERR_OOM : SB_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(_r)); \
+        }                                                                                                      \
+    } while (0)
+
+#define SB_TRYR(x)                   \
+    do {                             \
+        sb_status _s = (x);          \
+        if (_s != SB_OK) return _s;  \
+    } while (0)
+
+template <typename T>
+static sb_status sbr_grow(sb_engine *e, T **p, size_t &cap, size_t n)
+{
+    n = std::max<size_t>(n, 1);
+    if (*p && cap >= n) return SB_OK;
+    if (*p) {
+        SBR_HIP(e, hipStreamSynchronize(e->stream)); // a render in flight may still read it
+        SBR_HIP(e, hipFree(*p));
+        *p = nullptr;
+        cap = 0;
+    }
+    SBR_HIP(e, hipMalloc((void **)p, n * sizeof(T)));
+    cap = n;
+    return SB_OK;
+}
+
+void sbr_invalidate(sb_engine *e)
+{
+    if (e && e->rs) e->rs->valid = false;
+}
+
+void sbr_release(sb_engine *e)
+{
+    if (!e || !e->rs) return;
+    SbRenderState *r = e->rs;
+    void *ps[] = {r->d_ends, r->d_copy, r->d_wide_p, r->d_wide_b, r->d_count, r->d_keys, r->d_rgb};
+    for (void *p : ps)
+        if (p) (void)hipFree(p);
+    delete r;
+    e->rs = nullptr;
+}
+
+double sbr_last_build_ms(const sb_engine *e) { return e && e->rs ? e->rs->build_ms : 0.0; }
+
+// per engine beam slot: endpoints as internal particle indices and the copy read back for it (the caller's slots of the latest
+// upload only; the engine's slots an upload cut are not drawn)
+static sb_status sbr_build_tables(sb_engine *e)
+{
+    SbRenderState &r = *e->rs;
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t P = e->P, B = e->B, maxP = e->opt.max_particles;
+    if (e->h_pidx.size() != P || e->h_beams.size() != B || e->h_copy_of_slot.size() < B)
+        SBR_FAIL(e, SB_ERR_STATE, "sb_render: host shadows of the scene are inconsistent");
+    std::vector<uint32_t> internal_of_index(maxP, 0xFFFFFFFFu);
+    for (uint32_t i = 0; i < P; i++) internal_of_index[e->h_pidx[i]] = i;
+    std::vector<uint2> ends(std::max<uint32_t>(B, 1), make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu));
+    const size_t Bu = e->h_user_slot.empty() ? B : e->h_user_slot.size();
+    sbt::parallel_ranges(Bu, 1 << 16, [&](size_t u0, size_t u1) {
+        for (size_t u = u0; u < u1; u++) {
+            const uint32_t s = e->h_user_slot.empty() ? (uint32_t)u : e->h_user_slot[u];
+            const SbHostBeam &h = e->h_beams[s];
+            ends[s] = make_uint2(internal_of_index[h.da], internal_of_index[h.db]);
+        }
+    });
+    for (const uint2 &v : ends)
+        if (v.x != 0xFFFFFFFFu && (v.x >= P || v.y >= P)) SBR_FAIL(e, SB_ERR_STATE, "sb_render: beam endpoint outside the scene");
+    SB_TRYR(sbr_grow(e, &r.d_ends, r.cap_ends, B));
+    SB_TRYR(sbr_grow(e, &r.d_copy, r.cap_copy, B));
+    SBR_HIP(e, hipMemcpyAsync(r.d_ends, ends.data(), (size_t)std::max<uint32_t>(B, 1) * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+    if (B) SBR_HIP(e, hipMemcpyAsync(r.d_copy, e->h_copy_of_slot.data(), (size_t)B * 4, hipMemcpyHostToDevice, e->stream));
+    SB_TRYR(sbr_grow(e, &r.d_wide_p, r.cap_wide_p, P));
+    SB_TRYR(sbr_grow(e, &r.d_wide_b, r.cap_wide_b, B));
+    SBR_HIP(e, hipStreamSynchronize(e->stream)); // (the host vectors go out of scope)
+    r.nbeam_slots = B;
+    r.valid = true;
+    r.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SB_OK;
+}
+
+static sb_status sbr_enqueue(sb_engine *e, const sb_render_options *o, uint8_t *d_rgb, size_t bytes_avail, bool host_bytes,
+                             uint32_t *res_out)
+{
+    if (!e) return SB_ERR_INVALID;
+    if (o && o->struct_size != 0 && o->struct_size != sizeof(sb_render_options))
+        SBR_FAIL(e, SB_ERR_INVALID, "sb_render: sb_render_options.struct_size %u != %zu", o->struct_size, sizeof(sb_render_options));
+    const bool given = o && o->struct_size;
+    const uint32_t res = given && o->resolution ? o->resolution : 512u;
+    if (res > SB_RENDER_MAX_RESOLUTION) SBR_FAIL(e, SB_ERR_INVALID, "sb_render: resolution %u above %u", res, SB_RENDER_MAX_RESOLUTION);
+    if (!e->loaded) SBR_FAIL(e, SB_ERR_STATE, "sb_render before sb_write_buffers");
+    if (e->n_ghost_p || e->n_send_p || e->n_ghost_b || e->n_send_b)
+        SBR_FAIL(e, SB_ERR_UNSUPPORTED, "sb_render: the engine has ghost zones configured (ranks are not composited)");
+    const size_t npix = (size_t)res * res;
+    if (host_bytes && bytes_avail < npix * 3)
+        SBR_FAIL(e, SB_ERR_INVALID, "sb_render: buffer of %zu bytes, the picture needs %zu", bytes_avail, npix * 3);
+    if (!d_rgb && !host_bytes) SBR_FAIL(e, SB_ERR_INVALID, "sb_render_device: null destination");
+    SbrArgs a;
+    a.S = given && o->bounds_size != 0.0 ? o->bounds_size : (double)e->opt.bounds_size;
+    a.r = given && o->particle_radius != 0.0 ? o->particle_radius : (double)e->opt.particle_radius;
+    a.r08 = a.r * 0.8;
+    a.res = (double)res;
+    a.nres = res;
+    SBR_HIP(e, hipSetDevice(e->device));
+    if (!e->rs) e->rs = new SbRenderState();
+    SbRenderState &r = *e->rs;
+    if (!r.valid) SB_TRYR(sbr_build_tables(e));
+    if (!r.d_count) SBR_HIP(e, hipMalloc((void **)&r.d_count, 2 * sizeof(uint32_t)));
+    SB_TRYR(sbr_grow(e, &r.d_keys, r.cap_keys, npix));
+    SBR_HIP(e, hipMemsetAsync(r.d_keys, 0, npix * sizeof(unsigned long long), e->stream));
+    SBR_HIP(e, hipMemsetAsync(r.d_count, 0, 2 * sizeof(uint32_t), e->stream));
+    const float2 *pos = e->part[e->cur].pos;
+    const uint32_t *dead = e->B && e->delete_gen ? e->d_dead_gen : nullptr; // as sb_load_buffers (fetch_dead) sees it
+    const uint32_t P = e->P, B = e->B;
+    if (P) {
+        k_render_particles<<<(P + SBR_BLOCK - 1) / SBR_BLOCK, SBR_BLOCK, 0, e->stream>>>(pos, e->d_pslot, P, a, r.d_keys, r.d_wide_p,
+                                                                                        r.d_count);
+        k_render_particles_wide<<<SBR_WIDE_BLOCKS, SBR_BLOCK, 0, e->stream>>>(pos, e->d_pslot, a, r.d_keys, r.d_wide_p, r.d_count);
+    }
+    if (B) {
+        k_render_beams<<<(B + SBR_BLOCK - 1) / SBR_BLOCK, SBR_BLOCK, 0, e->stream>>>(pos, r.d_ends, dead, B, a, r.d_keys, r.d_wide_b,
+                                                                                    r.d_count + 1);
+        k_render_beams_wide<<<SBR_WIDE_BLOCKS, SBR_BLOCK, 0, e->stream>>>(pos, r.d_ends, a, r.d_keys, r.d_wide_b, r.d_count + 1);
+    }
+    k_render_resolve<<<(unsigned)((npix + SBR_BLOCK - 1) / SBR_BLOCK), SBR_BLOCK, 0, e->stream>>>(
+        r.d_keys, npix, r.d_copy, e->beams.strain, e->beams.stress, d_rgb);
+    SBR_HIP(e, hipGetLastError());
+    *res_out = res;
+    return SB_OK;
+}
+
+extern "C" {
+
+sb_status sb_render_device(sb_engine *e, const sb_render_options *opts, void *device_rgb)
+{
+    try {
+        uint32_t res = 0;
+        return sbr_enqueue(e, opts, (uint8_t *)device_rgb, 0, false, &res);
+    } catch (const std::bad_alloc &) {
+        if (e) e->err = "out of host memory";
+        return SB_ERR_OOM;
+    } catch (const std::exception &ex) {
+        if (e) e->err = std::string("internal error: ") + ex.what();
+        return SB_ERR_INVALID;
+    }
+}
+
+sb_status sb_render(sb_engine *e, const sb_render_options *opts, void *rgb, size_t rgb_bytes)
+{
+    try {
+        if (!e) return SB_ERR_INVALID;
+        if (!rgb) SBR_FAIL(e, SB_ERR_INVALID, "sb_render: null destination");
+        // the size check needs the resolution before anything is enqueued: sbr_enqueue checks it against rgb_bytes
+        const bool given = opts && opts->struct_size;
+        const size_t res = given && opts->resolution ? opts->resolution : 512u;
+        if (res <= SB_RENDER_MAX_RESOLUTION && e->loaded) {
+            if (!e->rs) e->rs = new SbRenderState();
+            if (rgb_bytes >= res * res * 3) SB_TRYR(sbr_grow(e, &e->rs->d_rgb, e->rs->cap_rgb, res * res * 3));
+        }
+        uint32_t got = 0;
+        SB_TRYR(sbr_enqueue(e, opts, e->rs ? e->rs->d_rgb : nullptr, rgb_bytes, true, &got));
+        SBR_HIP(e, hipMemcpyAsync(rgb, e->rs->d_rgb, (size_t)got * got * 3, hipMemcpyDeviceToHost, e->stream));
+        SBR_HIP(e, hipStreamSynchronize(e->stream));
+        return SB_OK;
+    } catch (const std::bad_alloc &) {
+        if (e) e->err = "out of host memory";
+        return SB_ERR_OOM;
+    } catch (const std::exception &ex) {
+        if (e) e->err = std::string("internal error: ") + ex.what();
+        return SB_ERR_INVALID;
+    }
+}
+
+} // extern "C"

@@ -39,6 +39,13 @@ class SbOptions(ctypes.Structure):
                 ("block_substeps", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
 
 
+class SbRenderOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("resolution", ctypes.c_uint32), ("bounds_size", ctypes.c_double),
+                ("particle_radius", ctypes.c_double), ("reserved", ctypes.c_uint32 * 4)]
+
+
+RENDER_MAX_RESOLUTION = 16384
+
 _lib = None
 
 
@@ -100,6 +107,8 @@ def load_library():
     L.sb_peer_exchange.argtypes = [vp]
     L.sb_halo_unpack.argtypes = [vp, vp]
     L.sb_get_stream.argtypes = [vp, ctypes.POINTER(vp)]
+    L.sb_render.argtypes = [vp, ctypes.POINTER(SbRenderOptions), vp, sz]
+    L.sb_render_device.argtypes = [vp, ctypes.POINTER(SbRenderOptions), vp]
     f32 = ctypes.c_float
     L.sb_partition_create.argtypes = [u32, u32, u32, vp, vp, vp, vp, u32, u32, f32, ctypes.POINTER(vp)]
     L.sb_partition_destroy.argtypes = [vp]
@@ -285,3 +294,35 @@ class Engine:
         s = ctypes.c_void_p()
         self._check(load_library().sb_get_stream(self._h, ctypes.byref(s)))
         return s.value
+
+    @staticmethod
+    def _render_options(resolution, bounds_size, particle_radius):
+        o = SbRenderOptions()
+        o.struct_size = ctypes.sizeof(SbRenderOptions)
+        o.resolution = int(resolution)
+        o.bounds_size = 0.0 if bounds_size is None else float(bounds_size)
+        o.particle_radius = 0.0 if particle_radius is None else float(particle_radius)
+        return o
+
+    def render(self, resolution=512, bounds_size=None, particle_radius=None):
+        """The picture of host/render.js renderPPM (its body: RGB8, rows top to bottom) of the current state, drawn on the
+        GPU: a (resolution, resolution, 3) uint8 array.  None = the engine's own bounds / radius.  Waits for the stream."""
+        res = int(resolution)
+        out = np.empty((res, res, 3), dtype=np.uint8)
+        o = self._render_options(res, bounds_size, particle_radius)
+        self._check(load_library().sb_render(self._h, ctypes.byref(o), _ptr(out), out.nbytes))
+        return out
+
+    def render_device(self, dst, resolution=512, bounds_size=None, particle_radius=None):
+        """The same picture into device memory: `dst` is a device pointer (int) or a contiguous uint8 torch tensor of at least
+        resolution^2 * 3 bytes on the engine's device.  Only enqueues on the engine's stream (sync() or the tensor's
+        consumer ordered after stream() waits for it)."""
+        res = int(resolution)
+        if isinstance(dst, int):
+            ptr = dst
+        else:
+            if not dst.is_contiguous() or dst.element_size() * dst.numel() < res * res * 3:
+                raise ValueError("render_device: a contiguous tensor of at least %d bytes is needed" % (res * res * 3))
+            ptr = dst.data_ptr()
+        o = self._render_options(res, bounds_size, particle_radius)
+        self._check(load_library().sb_render_device(self._h, ctypes.byref(o), ctypes.c_void_p(ptr)))

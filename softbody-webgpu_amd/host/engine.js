@@ -69,6 +69,8 @@ class WGPUSoftbodyEngine {
 
     /** one simulated frame (the rAF callback of engineWorker.ts:699-709) */
     async frame() { await this.worker.frame(); }
+    /** the picture of the current state: the PPM Buffer renderPPM returns, drawn on the GPU (engineWorker.js render) */
+    async render(opts) { return this.worker.render(opts); }
     /** n frames back to back */
     async run(frames) { for (let i = 0; i < frames && this.running; i++) await this.frame(); }
 

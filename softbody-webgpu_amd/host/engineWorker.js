@@ -6,6 +6,8 @@
  *   writeBuffers()  engineWorker.ts:580-597  ->  sb_write_buffers
  *   loadBuffers()   engineWorker.ts:548-579  ->  sb_load_buffers
  *   frame()         engineWorker.ts:626-695  ->  sb_write_user_input + sb_frame
+ * and the picture of the render pass (engineWorker.ts:666-683) headless:
+ *   render()        renderPPM of the state loadBuffers() would read  ->  sb_render (on the GPU, no read-back)
  */
 const { WGPUSoftbodyEngineMessageTypes: MSG } = require('./messages');
 const { BufferMapper, Vector2D } = require('./engineMapping');
@@ -95,6 +97,24 @@ class WGPUSoftbodyEngineWorker {
         this.frameTimes.push(t);
         while (this.frameTimes[0] + 1000 < t) this.frameTimes.shift();
         this.post({ type: MSG.FRAMERATE, data: this.currentFps });
+    }
+
+    /**
+     * The picture host/render.js renderPPM(mapper, opts) returns for the state loadBuffers() would read back, byte for byte
+     * ("P6" header included), drawn on the GPU (sb_render): no state travels to the host.
+     * @param opts {resolution (512), boundsSize, particleRadius} -- the engine's own bounds / radius unless given
+     * @returns Buffer
+     */
+    async render(opts) {
+        const o = opts || {};
+        return this.lock.run(() => {
+            if (!this.uploaded) throw new Error('render before writeBuffers');
+            return this.addon.render(this.handle, {
+                resolution: o.resolution || 512,
+                boundsSize: o.boundsSize !== undefined ? o.boundsSize : this.boundsSize,
+                particleRadius: o.particleRadius !== undefined ? o.particleRadius : this.particleRadius
+            });
+        });
     }
 
     /** benchmark granularity: n substeps, no delete pass; returns device milliseconds */

@@ -154,6 +154,12 @@ export type NativeEngineOptions = Partial<WGPUSoftbodyEngineOptions> & {
     readonly blockSubsteps?: number     // collisions off: substeps per launch (0/undefined = 6, 1 = one launch per substep)
 };
 
+export interface RenderOptions {
+    readonly resolution?: number       // pixels across (square picture); default 512, at most 16384
+    readonly boundsSize?: number
+    readonly particleRadius?: number
+}
+
 export class WGPUSoftbodyEngine {
     readonly resolution: number;
     readonly canvas: unknown | null;
@@ -167,6 +173,8 @@ export class WGPUSoftbodyEngine {
     corruptBuffers(): Promise<void>;
     setInput(appliedForce: Vector2D, rawMousePos: Vector2D, mouseActive: boolean): Promise<void>;
     frame(): Promise<void>;
+    /** renderPPM's picture of the current state ("P6" header included), drawn on the GPU (sb_render) */
+    render(opts?: RenderOptions): Promise<Buffer>;
     run(frames: number): Promise<void>;
     destroy(): Promise<void>;
     readonly destroyed: boolean;
@@ -184,6 +192,9 @@ export class WGPUSoftbodyEngineWorker {
     writeBuffers(): Promise<void>;
     frame(): Promise<void>;
     step(nSubsteps: number): Promise<number>;
+    /** renderPPM(bufferMapper after loadBuffers(), opts) byte for byte, drawn on the GPU without a read-back; the engine's own
+     *  boundsSize / particleRadius unless given */
+    render(opts?: RenderOptions): Promise<Buffer>;
     onMessage(msg: { type: WGPUSoftbodyEngineMessageTypes, data?: unknown }): Promise<void>;
     destroy(): Promise<void>;
 }
