@@ -201,7 +201,8 @@ sb_status sb_get_counts(sb_engine *e, uint32_t *particles, uint32_t *beams);
  * "device_bytes", "substeps_done", "kernels_per_substep", "substep_hbm_bytes" (the HBM bytes one substep
  * launch has to move with the data layout the engine holds: the launched kernel's own compulsory traffic),
  * "grid_cells", "grid_builds", "grid_wide", "grid_skin_x1000", "material_mode", "materials", "local_index_bits",
- * "render_table_build_us" (host time of sb_render's last draw-table build: the first render after an upload). */
+ * "render_table_build_us" (host time of sb_render's last draw-table build: the first render after an upload),
+ * "halo_guard" (1 while a halo guard is set, sb_halo_guard). */
 sb_status sb_get_info(sb_engine *e, const char *key, uint64_t *value);
 
 /* ---- multi-GPU halo exchange; one engine per rank/GPU, each holding its
@@ -273,7 +274,7 @@ sb_status sb_peer_exchange(sb_engine *e);
  * `depth` substeps (sb_halo_* / sb_peer_*): both sides list the traded records in ascending GLOBAL data index.
  * Errors are reported through sb_last_error(NULL).  Limits: ghost zones are redundant computation, valid while
  * information travels at most one hop per substep -- contacts between particles of slabs that are not neighbours
- * in x are missed, and break flags do not cross ranks. */
+ * in x are missed, and break flags do not cross ranks.  Ownership never migrates: sb_halo_guard says when to partition again. */
 typedef struct sb_partition sb_partition;
 sb_status sb_partition_create(uint32_t layout, uint32_t max_particles, uint32_t max_beams, const void *metadata, const void *mapping,
                               const void *particles, const void *beams, uint32_t world, uint32_t depth, float contact_reach,
@@ -295,6 +296,69 @@ sb_status sb_partition_peer_counts(const sb_partition *p, uint32_t rank, uint32_
 /* ... and the lists themselves, LOCAL data indices in the order sb_halo_configure expects (any pointer may be NULL) */
 sb_status sb_partition_peer_lists(const sb_partition *p, uint32_t rank, uint32_t j, uint32_t *ghost_particles, uint32_t *send_particles,
                                   uint32_t *ghost_beams, uint32_t *send_beams);
+
+/* halo guard data of one rank (world <= 64, else SB_ERR_UNSUPPORTED; see sb_halo_guard), as fixed at partition time:
+ * lo[world], hi[world] = the x-extent of every rank's own particles (+inf / -inf for a rank that owns none);
+ * geometry = { R: the contact reach (0 for world 1), H: the hop length SB_GUARD_HOP_HEADROOM * max(2 * particle_radius,
+ * longest live beam) }; held[local particles] = per LOCAL data index, bit t set when rank t holds the particle (own or ghost).
+ * Any output pointer may be NULL. */
+#define SB_GUARD_HOP_HEADROOM 1.5f
+sb_status sb_partition_rank_guard(const sb_partition *p, uint32_t rank, float particle_radius, float *lo, float *hi, float geometry[2],
+                                  uint64_t *held);
+
+/* ---- halo guard: the device notices when a partition has gone stale ----
+ * Ghost zones are fixed when the scene is partitioned and ownership never migrates, so once particles move far enough a rank
+ * misses contacts it should compute and its owned state silently stops matching the single engine.  An engine with a guard
+ * runs one more kernel at the end of every ghost refresh (behind the unpack of sb_halo_unpack and of sb_peer_exchange), on the
+ * engine's stream, that checks the rule below on the refreshed state -- the ghost endpoint of a beam that crosses ranks is then
+ * its owner's copy; sb_halo_guard_status reads the verdict.  NOTE: a rank without neighbours must still call sb_halo_unpack
+ * (NULL buffer, empty lists) or sb_peer_exchange at each of its refreshes: those calls are where the check runs.  The guard only reads state.
+ *   Fixed at partition time (sb_partition_rank_guard): lo_t, hi_t per rank t, R, H; the caller adds depth D (substeps between
+ *   refreshes, at most) and s, the motion allowance per substep (0 = default H / (16 D)).  C = D * (H + s), the chain reach.
+ *   At every refresh, on the refreshed state (float32 arithmetic in exactly this order; a check FAILS when its comparison is false,
+ *   so NaN fails (A), (C), (D)):
+ *     (A) own particle:  lo_r - (R - 3C) <= x <= hi_r + (R - 3C)
+ *     (B) own particle, every rank t != r that does not hold it:  NOT (lo_t - (R - C) <= x <= hi_t + (R - C))
+ *     (C) own beam (endpoint A owned) that no delete pass has removed:  sqrt(dx*dx + dy*dy) <= H - (2D) * s
+ *     (D) own particle:  |x - x at the previous refresh| <= n * s, n = substeps since then
+ *   With SB_COLLIDE_OFF, or world 1, only (C) and (D) are checked.  If every check passes at every refresh and no particle moves more than s
+ *   in x within one substep, every owned state equals the single engine's bit for bit.  Blind spot: (D) sees the
+ *   displacement between refreshes only, so a particle that leaves and returns within one refresh window goes unnoticed.
+ * Call order: sb_halo_configure [+ sb_halo_set_layout] -> sb_halo_guard -> refreshes -> sb_halo_guard_status.  Errors:
+ * SB_ERR_STATE before sb_halo_configure; SB_ERR_UNSUPPORTED for world > 64; SB_ERR_INVALID for a bad rank or index, depth 0,
+ * H or s not finite, s > H / 2, H - 2Ds <= 0, or (collisions on) R < 3C, with a message.  A NULL desc turns the guard off; so
+ * do a new upload and a new sb_halo_configure.  sb_get_info "halo_guard" = 1 while a guard is set. */
+#define SB_GUARD_SLAB 1u   /* (A) an own particle left its slab */
+#define SB_GUARD_BAND 2u   /* (B) a particle entered the band of a rank that does not hold it */
+#define SB_GUARD_BEAM 4u   /* (C) an own beam is longer than H allows */
+#define SB_GUARD_MOTION 8u /* (D) an own particle moved more than the allowance */
+typedef struct sb_halo_guard_desc {
+    uint32_t struct_size;          /* = sizeof(sb_halo_guard_desc) */
+    uint32_t rank, world, depth;
+    float contact_reach;           /* R */
+    float hop;                     /* H */
+    float motion;                  /* s per substep; 0 = H / (16 depth) */
+    uint32_t n_own_particles;
+    const uint32_t *own_particles; /* local particle data indices */
+    const uint64_t *held;          /* per own particle (same order): bit t = rank t holds it */
+    uint32_t n_own_beams;
+    const uint32_t *own_beams;     /* local beam data indices */
+    const float *lo, *hi;          /* [world] */
+    uint32_t reserved[4];
+} sb_halo_guard_desc;
+typedef struct sb_halo_guard_report {
+    uint32_t kinds;         /* SB_GUARD_* bits of every failed check since sb_halo_guard */
+    uint32_t violations;    /* (refresh, item) pairs that failed at least one check */
+    uint32_t refreshes;     /* refreshes checked */
+    uint32_t first_refresh; /* index of the first refresh that failed (0 = the first refresh after sb_halo_guard); ~0 = none */
+    uint32_t first_is_beam; /* the first failed item at that refresh (particles before beams, lowest data index first): */
+    uint32_t first_index;   /* its LOCAL data index */
+    float motion;           /* the s in use */
+    uint32_t reserved;
+} sb_halo_guard_report;
+sb_status sb_halo_guard(sb_engine *e, const sb_halo_guard_desc *desc);
+/* waits for the engine's stream, then reads the verdict */
+sb_status sb_halo_guard_status(sb_engine *e, sb_halo_guard_report *report);
 
 /* ---- pictures of the state (the reference's render pass, engineWorker.ts:666-683) ----
  * The picture is that of the headless renderer host/render.js, renderPPM(mapper, {resolution, boundsSize, particleRadius})

@@ -197,6 +197,14 @@ static void free_scene(sb_engine *e)
     e->bk = SbBlockedDev{};
     e->hy = SbBlockedDev{};
     e->n_peers = e->peer_seq = e->send_floats = e->recv_floats = 0;
+    e->halo_configured = e->guard_on = false; // (the guard's arrays were pool blocks of the scene)
+    e->d_guard_p = nullptr;
+    e->d_guard_held = nullptr;
+    e->d_guard_xprev = nullptr;
+    e->d_guard_b = nullptr;
+    e->d_guard_bslot = nullptr;
+    e->d_guard_pdata = e->d_guard_bdata = nullptr;
+    e->d_guard_status = nullptr;
     if (e->dev_err) *e->dev_err = 0;
 }
 
@@ -2112,6 +2120,8 @@ sb_status sb_get_info(sb_engine *e, const char *key, uint64_t *value)
     else if (k == "hybrid_launches") *value = e->hy.launches_ok;      // tracked launches that were validated
     else if (k == "hybrid_failed") *value = e->hy.launches_failed;    // tracked launches that went over the skin and were redone
     else if (k == "hybrid_validate_launches") *value = e->hy.validate_launches; // k_hybrid_validate launches: one per run (a launch is validated by its successor's prologue)
+    else if (k == "halo_guard") *value = e->guard_on ? 1 : 0; // sb_halo_guard is set
+    else if (k == "halo_guard_refreshes") *value = e->guard_on ? e->guard_refreshes : 0; // refreshes it has checked
     else if (k == "material_mode") *value = e->mat_mode;
     else if (k == "materials") *value = e->nmat;
     else if (k == "local_index_bits") *value = e->lbits;
@@ -2186,6 +2196,8 @@ static sb_status sb_halo_configure_impl(sb_engine *e, const uint32_t *ghost_part
     e->n_ghost_b = n_gb;
     e->n_send_b = n_sb;
     e->n_ghost_b_copies = (uint32_t)ghost_copies.size();
+    e->halo_configured = true;
+    e->guard_on = false; // new lists: a guard has to be set again (sb_halo_guard)
     SB_TRY(dev_alloc(e, &e->d_send_p_off, n_sp));
     SB_TRY(dev_alloc(e, &e->d_send_b_off, n_sb));
     SB_TRY(dev_alloc(e, &e->d_ghost_p_off, n_gp));
@@ -2310,13 +2322,172 @@ sb_status sb_peer_connect(sb_engine *e, uint32_t n_peers, void *const *mailboxes
     return SB_OK;
 }
 
+// ---- halo guard (include/softbody.h sb_halo_guard) ----------------------------
+static void pool_release(sb_engine *e, void *p)
+{
+    if (!p) return;
+    auto it = std::find_if(e->pool_used.begin(), e->pool_used.end(), [p](const std::pair<void *, size_t> &b) { return b.first == p; });
+    if (it != e->pool_used.end()) {
+        e->pool_free.push_back(*it);
+        e->pool_used.erase(it);
+    }
+}
+
+// one refresh ended (behind its unpack): check it
+static void guard_refresh(sb_engine *e)
+{
+    if (!e->guard_on) return;
+    e->guard.refresh = e->guard_refreshes++;
+    e->guard.allow = (float)(e->substeps_done - e->guard_substeps) * e->guard.s;
+    e->guard_substeps = e->substeps_done;
+    sbk_launch_halo_guard(e, false);
+}
+
+static sb_status sb_halo_guard_impl(sb_engine *e, const sb_halo_guard_desc *d)
+{
+    if (!e) return SB_ERR_INVALID;
+    if (!e->loaded) SB_FAIL(e, SB_ERR_STATE, "sb_halo_guard before sb_write_buffers");
+    if (!e->halo_configured) SB_FAIL(e, SB_ERR_STATE, "sb_halo_guard before sb_halo_configure");
+    SB_HIP(e, hipSetDevice(e->device));
+    SB_HIP(e, hipStreamSynchronize(e->stream));
+    e->guard_on = false;
+    if (!d) return SB_OK;
+    if (d->struct_size != sizeof *d) SB_FAIL(e, SB_ERR_INVALID, "sb_halo_guard: struct_size %u (expected %zu)", d->struct_size, sizeof *d);
+    if (d->world > SB_GUARD_MAX_WORLD) SB_FAIL(e, SB_ERR_UNSUPPORTED, "sb_halo_guard: world %u (the guard supports at most %d ranks)", d->world, SB_GUARD_MAX_WORLD);
+    if (!d->world || d->rank >= d->world) SB_FAIL(e, SB_ERR_INVALID, "sb_halo_guard: rank %u of world %u", d->rank, d->world);
+    if (!d->depth) SB_FAIL(e, SB_ERR_INVALID, "sb_halo_guard: depth 0");
+    if (!d->lo || !d->hi || (d->n_own_particles && (!d->own_particles || !d->held)) || (d->n_own_beams && !d->own_beams))
+        SB_FAIL(e, SB_ERR_INVALID, "sb_halo_guard: null list");
+    const float H = d->hop, R = d->contact_reach, D = (float)d->depth;
+    if (!(H > 0.0f) || !std::isfinite(H)) SB_FAIL(e, SB_ERR_INVALID, "sb_halo_guard: hop length H = %g must be positive and finite", H);
+    const float s = d->motion == 0.0f ? H / (16.0f * D) : d->motion;
+    if (!(s >= 0.0f) || !(s <= 0.5f * H)) SB_FAIL(e, SB_ERR_INVALID, "sb_halo_guard: motion allowance s = %g must lie in [0, H/2 = %g]", s, 0.5f * H);
+    const float C = D * (H + s), lmax = H - (2.0f * D) * s;
+    if (!(lmax > 0.0f)) SB_FAIL(e, SB_ERR_INVALID, "sb_halo_guard: H - 2 depth s = %g leaves no room for a beam: a smaller s", lmax);
+    const bool collide = e->opt.collision_mode != SB_COLLIDE_OFF && d->world > 1; // (one rank holds everything: (A), (B) are moot)
+    const float a = R - 3.0f * C, b = R - C; // (A) and (B) widen the slabs by these: b - a = 2C
+    if (collide && !(a >= 0.0f && std::isfinite(R)))
+        SB_FAIL(e, SB_ERR_INVALID, "sb_halo_guard: contact reach R = %g < 3C = %g (C = depth * (H + s)): the rule cannot hold; "
+                "partition with a wider reach, or use a smaller depth or s", R, 3.0f * C);
+    // own particles and beams -> internal indices
+    const uint32_t maxP = e->opt.max_particles, maxB = e->opt.max_beams;
+    std::vector<uint32_t> internal_of_index(maxP, 0xFFFFFFFFu), slot_of_beam(maxB, 0xFFFFFFFFu);
+    for (uint32_t i = 0; i < e->P; i++) internal_of_index[e->h_pidx[i]] = i;
+    for (uint32_t u = 0; u < sb_user_beams(e); u++) slot_of_beam[map_get(e, e->h_mapping.data(), (size_t)maxP + u)] = sb_user_slot(e, u);
+    // both lists in ascending INTERNAL order (the kernel's position reads then stream); checked here, sorted below
+    for (uint32_t k = 0; k < d->n_own_particles; k++)
+        if (d->own_particles[k] >= maxP || internal_of_index[d->own_particles[k]] == 0xFFFFFFFFu)
+            SB_FAIL(e, SB_ERR_INVALID, "sb_halo_guard: own particle %u is not an active data index", d->own_particles[k]);
+    for (uint32_t k = 0; k < d->n_own_beams; k++)
+        if (d->own_beams[k] >= maxB || slot_of_beam[d->own_beams[k]] == 0xFFFFFFFFu)
+            SB_FAIL(e, SB_ERR_INVALID, "sb_halo_guard: own beam %u is not an active data index", d->own_beams[k]);
+    auto ia = [&](uint32_t u) { return internal_of_index[e->h_beams[slot_of_beam[d->own_beams[u]]].da]; };
+    std::vector<uint32_t> order_p(d->n_own_particles), order_b(d->n_own_beams);
+    std::iota(order_p.begin(), order_p.end(), 0u);
+    std::iota(order_b.begin(), order_b.end(), 0u);
+    std::stable_sort(order_p.begin(), order_p.end(),
+                     [&](uint32_t u, uint32_t v) { return internal_of_index[d->own_particles[u]] < internal_of_index[d->own_particles[v]]; });
+    std::stable_sort(order_b.begin(), order_b.end(), [&](uint32_t u, uint32_t v) { return ia(u) < ia(v); });
+    std::vector<uint32_t> own_p(d->n_own_particles), p_data(d->n_own_particles), b_data(d->n_own_beams);
+    std::vector<uint64_t> held(d->n_own_particles);
+    for (uint32_t k = 0; k < d->n_own_particles; k++) {
+        const uint32_t di = d->own_particles[order_p[k]];
+        if (di >= maxP || internal_of_index[di] == 0xFFFFFFFFu)
+            SB_FAIL(e, SB_ERR_INVALID, "sb_halo_guard: own particle %u is not an active data index", di);
+        own_p[k] = internal_of_index[di];
+        p_data[k] = di;
+        held[k] = d->held[order_p[k]];
+    }
+    std::vector<uint2> own_b(d->n_own_beams);
+    std::vector<uint32_t> own_bslot(d->n_own_beams);
+    for (uint32_t k = 0; k < d->n_own_beams; k++) {
+        const uint32_t di = d->own_beams[order_b[k]];
+        if (di >= maxB || slot_of_beam[di] == 0xFFFFFFFFu)
+            SB_FAIL(e, SB_ERR_INVALID, "sb_halo_guard: own beam %u is not an active data index", di);
+        const SbHostBeam &h = e->h_beams[slot_of_beam[di]];
+        own_b[k] = make_uint2(internal_of_index[h.da], internal_of_index[h.db]);
+        own_bslot[k] = slot_of_beam[di];
+        b_data[k] = di;
+    }
+    SbGuardArgs g{};
+    g.world = d->world;
+    g.rank = d->rank;
+    g.s = s;
+    g.lmax = lmax;
+    g.a_lo = d->lo[d->rank] - a;
+    g.a_hi = d->hi[d->rank] + a;
+    for (uint32_t t = 0; t < d->world; t++) {
+        g.b_lo[t] = d->lo[t] - b;
+        g.b_hi[t] = d->hi[t] + b;
+    }
+    g.np = d->n_own_particles;
+    g.nb = d->n_own_beams;
+    g.checks = SB_GUARD_BEAM | SB_GUARD_MOTION | (collide ? SB_GUARD_SLAB | SB_GUARD_BAND : 0u);
+    for (void *old : {(void *)e->d_guard_p, (void *)e->d_guard_held, (void *)e->d_guard_xprev, (void *)e->d_guard_b, (void *)e->d_guard_bslot,
+                      (void *)e->d_guard_pdata, (void *)e->d_guard_bdata, (void *)e->d_guard_status})
+        pool_release(e, old);
+    e->d_guard_p = nullptr;
+    e->d_guard_held = nullptr;
+    e->d_guard_xprev = nullptr;
+    e->d_guard_b = nullptr;
+    e->d_guard_bslot = nullptr;
+    e->d_guard_pdata = e->d_guard_bdata = nullptr;
+    e->d_guard_status = nullptr;
+    SB_TRY(dev_alloc(e, &e->d_guard_p, g.np));
+    SB_TRY(dev_alloc(e, &e->d_guard_held, g.np));
+    SB_TRY(dev_alloc(e, &e->d_guard_xprev, g.np));
+    SB_TRY(dev_alloc(e, &e->d_guard_b, g.nb));
+    SB_TRY(dev_alloc(e, &e->d_guard_bslot, g.nb));
+    SB_TRY(dev_alloc(e, &e->d_guard_pdata, g.np));
+    SB_TRY(dev_alloc(e, &e->d_guard_bdata, g.nb));
+    SB_TRY(dev_alloc(e, &e->d_guard_status, 8));
+    if (g.np) {
+        SB_HIP(e, hipMemcpy(e->d_guard_p, own_p.data(), (size_t)g.np * 4, hipMemcpyHostToDevice));
+        SB_HIP(e, hipMemcpy(e->d_guard_held, held.data(), (size_t)g.np * 8, hipMemcpyHostToDevice));
+        SB_HIP(e, hipMemcpy(e->d_guard_pdata, p_data.data(), (size_t)g.np * 4, hipMemcpyHostToDevice));
+    }
+    if (g.nb) {
+        SB_HIP(e, hipMemcpy(e->d_guard_b, own_b.data(), (size_t)g.nb * sizeof(uint2), hipMemcpyHostToDevice));
+        SB_HIP(e, hipMemcpy(e->d_guard_bslot, own_bslot.data(), (size_t)g.nb * 4, hipMemcpyHostToDevice));
+        SB_HIP(e, hipMemcpy(e->d_guard_bdata, b_data.data(), (size_t)g.nb * 4, hipMemcpyHostToDevice));
+    }
+    const uint32_t status0[8] = {0u, 0u, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u};
+    SB_HIP(e, hipMemcpy(e->d_guard_status, status0, sizeof status0, hipMemcpyHostToDevice));
+    e->guard = g;
+    e->guard_refreshes = 0;
+    e->guard_substeps = e->substeps_done;
+    e->guard_on = true;
+    sbk_launch_halo_guard(e, true); // x of the own particles now: the first refresh's (D) measures from here
+    SB_HIP(e, hipGetLastError());
+    return SB_OK;
+}
+
+sb_status sb_halo_guard_status(sb_engine *e, sb_halo_guard_report *r)
+{
+    if (!e || !r) return SB_ERR_INVALID;
+    if (!e->guard_on) SB_FAIL(e, SB_ERR_STATE, "sb_halo_guard_status without a guard (sb_halo_guard)");
+    SB_TRY(sb_sync(e));
+    uint32_t st[8];
+    SB_HIP(e, hipMemcpy(st, e->d_guard_status, sizeof st, hipMemcpyDeviceToHost));
+    memset(r, 0, sizeof *r);
+    r->kinds = st[0];
+    r->violations = st[1];
+    r->refreshes = e->guard_refreshes;
+    r->first_refresh = st[2];
+    r->first_is_beam = st[2] == 0xFFFFFFFFu ? 0u : st[4] >> 31;
+    r->first_index = st[2] == 0xFFFFFFFFu ? 0xFFFFFFFFu : st[4] & 0x7FFFFFFFu;
+    r->motion = e->guard.s;
+    return SB_OK;
+}
+
 sb_status sb_peer_exchange(sb_engine *e)
 {
     if (!e) return SB_ERR_INVALID;
     if (!e->loaded || !e->mailbox) SB_FAIL(e, SB_ERR_STATE, "sb_peer_exchange before sb_peer_connect");
-    if (!e->n_peers) return SB_OK;
+    if (!e->n_peers && !e->guard_on) return SB_OK;
     SB_HIP(e, hipSetDevice(e->device));
-    sbk_launch_peer_exchange(e);
+    if (e->n_peers) sbk_launch_peer_exchange(e);
+    guard_refresh(e);
     SB_HIP(e, hipGetLastError());
     return SB_OK;
 }
@@ -2339,6 +2510,7 @@ sb_status sb_halo_unpack(sb_engine *e, const void *device_src)
     if ((e->n_ghost_p || e->n_ghost_b) && !device_src) SB_FAIL(e, SB_ERR_INVALID, "null device buffer");
     SB_HIP(e, hipSetDevice(e->device));
     sbk_launch_halo_unpack(e, (const float *)device_src);
+    guard_refresh(e);
     SB_HIP(e, hipGetLastError());
     return SB_OK;
 }
@@ -2368,6 +2540,7 @@ sb_status sb_write_buffers(sb_engine *e, const void *metadata, size_t metadata_b
                            const void *beams, size_t beams_bytes)
 {
     sbr_invalidate(e);
+    if (e) e->halo_configured = e->guard_on = false; // (also when the upload keeps the plan: a new scene has no halo, no guard)
     SB_GUARDED(e, sb_write_buffers_impl(e, metadata, metadata_bytes, mapping, mapping_bytes, particles, particles_bytes,
                                         beams, beams_bytes))
 }
@@ -2385,5 +2558,11 @@ sb_status sb_halo_configure(sb_engine *e, const uint32_t *ghost_particles, uint3
 {
     SB_GUARDED(e, sb_halo_configure_impl(e, ghost_particles, n_gp, send_particles, n_sp, ghost_beams, n_gb, send_beams, n_sb))
 }
+
+sb_status sb_halo_guard(sb_engine *e, const sb_halo_guard_desc *desc)
+{
+    SB_GUARDED(e, sb_halo_guard_impl(e, desc))
+}
+
 
 } // extern "C"

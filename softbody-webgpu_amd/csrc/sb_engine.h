@@ -104,6 +104,17 @@ struct SbBlockedDev {
     uint64_t entries_at[SB_BK_KMAX + 1] = {}, region_at[SB_BK_KMAX + 1] = {}; // totals over the tiles of what a launch of depth k loads
 };
 
+// k_halo_guard's thresholds (include/softbody.h sb_halo_guard; float32, computed once on the host)
+#define SB_GUARD_MAX_WORLD 64
+struct SbGuardArgs {
+    float a_lo, a_hi;                    // (A) own particles stay within
+    float lmax;                          // (C) own beams at most this long
+    float allow;                         // (D) x displacement since the previous refresh: n * s (set per refresh)
+    float s;                             // motion allowance per substep
+    uint32_t world, rank, refresh, np, nb, checks, init;
+    float b_lo[SB_GUARD_MAX_WORLD], b_hi[SB_GUARD_MAX_WORLD]; // (B) per rank: a particle it does not hold stays outside
+};
+
 struct sb_engine {
     sb_options opt{};
     SbParams prm{};
@@ -164,6 +175,19 @@ struct sb_engine {
     uint32_t *d_send_p_off = nullptr, *d_send_b_off = nullptr;   // float offsets into the packed send buffer
     uint32_t *d_ghost_p_off = nullptr, *d_ghost_b_off = nullptr; // float offsets into the packed recv buffer
     uint32_t send_floats = 0, recv_floats = 0;                   // extents of the two packed layouts
+    bool halo_configured = false;      // sb_halo_configure ran since the upload
+    // halo guard (sb_halo_guard): a check of the partition behind every refresh (sb_kernels.hip k_halo_guard)
+    bool guard_on = false;
+    uint32_t guard_np = 0, guard_nb = 0, guard_checks = 0, guard_refreshes = 0;
+    uint64_t guard_substeps = 0;       // substeps_done at the last refresh checked
+    SbGuardArgs guard{};               // thresholds (kernarg)
+    uint32_t *d_guard_p = nullptr;     // per own particle: internal index (ascending)
+    uint64_t *d_guard_held = nullptr;  // per own particle: bit t = rank t holds it
+    float *d_guard_xprev = nullptr;    // per own particle: x at the previous refresh
+    uint2 *d_guard_b = nullptr;        // per own beam: internal index of A, of B (ascending)
+    uint32_t *d_guard_bslot = nullptr; // per own beam: its engine slot (d_dead_gen: removed by a delete pass)
+    uint32_t *d_guard_pdata = nullptr, *d_guard_bdata = nullptr; // data index per position of the two lists (read on failure)
+    uint32_t *d_guard_status = nullptr; // [8]: kinds, violations, first refresh, 0, first key (u64, 8-byte aligned)
     // direct peer exchange (sb_peer_*): own mailbox, neighbours' mailboxes, per-neighbour routing
     void *mailbox = nullptr;
     std::vector<void *> mapped;        // opened IPC mappings (closed with the scene)
@@ -237,6 +261,7 @@ void sbk_launch_halo_clear_ghost_flags(sb_engine *e);
 void sbk_launch_halo_pack(sb_engine *e, float *dst);
 void sbk_launch_halo_unpack(sb_engine *e, const float *src);
 void sbk_launch_peer_exchange(sb_engine *e);
+void sbk_launch_halo_guard(sb_engine *e, bool init); // init: record x only (sb_halo_guard)
 // sb_blocked.hip
 void sbk_launch_blocked(sb_engine *e, uint32_t n, bool write_aux);
 void sbk_preload_blocked(const SbBlockedDev &bk, bool tracked); // resolve every kernel variant a call on this plan may launch (upload time)

@@ -982,6 +982,73 @@ void sbk_launch_halo_clear_ghost_flags(sb_engine *e)
     k_halo_clear_ghost_flags<<<cdiv(e->n_ghost_b_copies, SB_BLOCK), SB_BLOCK, 0, e->stream>>>(e->d_ghost_b, e->n_ghost_b_copies, e->d_broken);
 }
 
+// Halo guard (include/softbody.h sb_halo_guard): one lane per own particle, then one per own beam, on the
+// refreshed state.  It writes nothing but x of the own particles (for the next refresh's (D)) and the status block, with
+// vector atomics: the OR of the kinds, a count, the smallest refresh index and the smallest key (refresh << 32 | beam << 31 |
+// local data index), so the verdict does not depend on the schedule.  A wave that finds anything reduces it first and one
+// lane reports, so a run that fires stays cheap.  The lists hold internal indices only (4 bytes per particle, 8 per beam) in
+// ascending internal order, so that the position reads stream; data indices, a beam's slot and its delete-pass word are read
+// only for an item that fails (a beam a delete pass removed carries no force: its endpoints may part).  Every comparison
+// fails on NaN.
+__global__ __launch_bounds__(SB_BLOCK) void k_halo_guard(const float2 *__restrict__ pos, const uint32_t *__restrict__ own_p,
+                                                         const uint64_t *__restrict__ held, float *__restrict__ xprev,
+                                                         const uint2 *__restrict__ own_b, const uint32_t *__restrict__ bslot,
+                                                         const uint32_t *__restrict__ dead_gen, const uint32_t *__restrict__ pdata,
+                                                         const uint32_t *__restrict__ bdata, uint32_t *__restrict__ status,
+                                                         SbGuardArgs g)
+{
+    const uint32_t k = blockIdx.x * SB_BLOCK + threadIdx.x;
+    uint32_t kinds = 0, key = 0xFFFFFFFFu;
+    if (k < g.np) {
+        const float x = pos[own_p[k]].x;
+        if (!g.init) {
+            if ((g.checks & SB_GUARD_SLAB) && !(x >= g.a_lo && x <= g.a_hi)) kinds |= SB_GUARD_SLAB;
+            if (g.checks & SB_GUARD_BAND) {
+                const uint64_t h = held[k];
+                for (uint32_t t = 0; t < g.world; t++)
+                    if (t != g.rank && !((h >> t) & 1ull) && x >= g.b_lo[t] && x <= g.b_hi[t]) kinds |= SB_GUARD_BAND;
+            }
+            if ((g.checks & SB_GUARD_MOTION) && !(fabsf(x - xprev[k]) <= g.allow)) kinds |= SB_GUARD_MOTION;
+        }
+        xprev[k] = x;
+        if (kinds) key = pdata[k];
+    } else if (k < g.np + g.nb && !g.init) {
+        const uint32_t j = k - g.np;
+        const uint2 b = own_b[j];
+        const float2 pa = pos[b.x], pb = pos[b.y];
+        const float dx = pb.x - pa.x, dy = pb.y - pa.y;
+        if ((g.checks & SB_GUARD_BEAM) && !(sqrtf(dx * dx + dy * dy) <= g.lmax) && dead_gen[bslot[j]] == 0u) {
+            kinds |= SB_GUARD_BEAM;
+            key = 0x80000000u | bdata[j];
+        }
+    }
+    const unsigned long long bad = __ballot(kinds != 0u);
+    if (!bad) return;
+    uint32_t kor = kinds, kmin = key;
+    for (int off = warpSize / 2; off > 0; off >>= 1) {
+        kor |= __shfl_xor(kor, off);
+        kmin = min(kmin, __shfl_xor(kmin, off));
+    }
+    if (__lane_id() == (unsigned)(__ffsll(bad) - 1)) {
+        atomicOr(status + 0, kor);
+        atomicAdd(status + 1, (uint32_t)__popcll(bad));
+        atomicMin(status + 2, g.refresh);
+        atomicMin((unsigned long long *)(status + 4), ((unsigned long long)g.refresh << 32) | kmin);
+    }
+}
+
+void sbk_launch_halo_guard(sb_engine *e, bool init)
+{
+    SbGuardArgs g = e->guard;
+    g.init = init ? 1u : 0u;
+    if (init) g.nb = 0;
+    const uint32_t n = g.np + g.nb;
+    if (!n) return;
+    k_halo_guard<<<cdiv(n, SB_BLOCK), SB_BLOCK, 0, e->stream>>>(e->part[e->cur].pos, e->d_guard_p, e->d_guard_held,
+                                                               e->d_guard_xprev, e->d_guard_b, e->d_guard_bslot, e->d_dead_gen,
+                                                               e->d_guard_pdata, e->d_guard_bdata, e->d_guard_status, g);
+}
+
 void sbk_launch_halo_pack(sb_engine *e, float *dst)
 {
     uint32_t n = e->n_send_p + e->n_send_b;

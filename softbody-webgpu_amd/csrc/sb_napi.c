@@ -29,6 +29,8 @@
  *   partitionRankCounts(p, rank) -> Uint32Array(8) / partitionRankScene(p, rank, maxP, maxB, metadata, mapping, particles, beams)
  *   partitionRankIds(p, rank) -> {particleGlobal, particleOwned, beamGlobal, beamOwned}
  *   partitionPeer(p, rank, j) -> {rank, ghostP, sendP, ghostB, sendB} / partitionDestroy(p)
+ *   partitionRankGuard(p, rank, particleRadius) -> {lo, hi, reach, hop, held}   (halo guard data; sb_partition_rank_guard)
+ *   haloGuard(h, desc | null) / haloGuardStatus(h) -> {kinds, violations, refreshes, firstRefresh, firstIsBeam, firstIndex, motion}
  * Device pointers travel as JS numbers (they are < 2^53).  An engine handle is a small box around the sb_engine
  * pointer: destroy() empties the box, every later call with that handle throws instead of touching freed memory, and an
  * engine whose handle is garbage-collected without destroy() is destroyed by the finalizer.
@@ -84,6 +86,9 @@ static struct {
     sb_status (*partition_rank_ids)(const sb_partition *, uint32_t, uint32_t *, uint8_t *, uint32_t *, uint8_t *);
     sb_status (*partition_peer_counts)(const sb_partition *, uint32_t, uint32_t, uint32_t *, uint32_t *);
     sb_status (*partition_peer_lists)(const sb_partition *, uint32_t, uint32_t, uint32_t *, uint32_t *, uint32_t *, uint32_t *);
+    sb_status (*partition_rank_guard)(const sb_partition *, uint32_t, float, float *, float *, float *, uint64_t *);
+    sb_status (*halo_guard)(sb_engine *, const sb_halo_guard_desc *);
+    sb_status (*halo_guard_status)(sb_engine *, sb_halo_guard_report *);
     const char *(*last_error)(const sb_engine *);
     uint32_t (*abi_version)(void);
 } sb;
@@ -179,6 +184,9 @@ static napi_value js_load(napi_env env, napi_callback_info info)
     SYM(partition_rank_ids, "sb_partition_rank_ids");
     SYM(partition_peer_counts, "sb_partition_peer_counts");
     SYM(partition_peer_lists, "sb_partition_peer_lists");
+    SYM(partition_rank_guard, "sb_partition_rank_guard");
+    SYM(halo_guard, "sb_halo_guard");
+    SYM(halo_guard_status, "sb_halo_guard_status");
     SYM(last_error, "sb_last_error");
     SYM(abi_version, "sb_abi_version");
 #undef SYM
@@ -875,6 +883,162 @@ static napi_value js_partition_peer(napi_env env, napi_callback_info info)
     return obj;
 }
 
+/* ---------------------------------------------------------------- halo guard (include/softbody.h sb_halo_guard) */
+
+/* partitionRankGuard(partition, rank, particleRadius) -> {lo: Float32Array(world), hi, reach, hop, held: BigUint64Array(local particles)}
+ * (bit t of held[i]: rank t holds local particle i) */
+static napi_value js_partition_rank_guard(napi_env env, napi_callback_info info)
+{
+    size_t argc = 3;
+    napi_value argv[3];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    sb_partition *pt = argc >= 1 ? get_partition(env, argv[0], NULL) : NULL;
+    if (!pt) return NULL;
+    uint32_t rank = 0, c[8];
+    double radius = 0.0;
+    if (argc < 3 || napi_get_value_uint32(env, argv[1], &rank) != napi_ok || napi_get_value_double(env, argv[2], &radius) != napi_ok ||
+        sb.partition_rank_counts(pt, rank, c) != SB_OK) {
+        napi_throw_type_error(env, NULL, "partitionRankGuard(partition, rank, particleRadius)");
+        return NULL;
+    }
+    /* world: the ranks of the partition (counts of the first rank that does not exist) */
+    uint32_t world = rank + 1, tmp[8];
+    while (sb.partition_rank_counts(pt, world, tmp) == SB_OK) world++;
+    void *lo, *hi, *held;
+    float geo[2] = {0.0f, 0.0f};
+    napi_value obj, tlo = make_typed(env, napi_float32_array, world, 4, &lo), thi = make_typed(env, napi_float32_array, world, 4, &hi),
+                    th = make_typed(env, napi_biguint64_array, c[0], 8, &held), vr, vh;
+    if (!tlo || !thi || !th) return NULL;
+    sb_status st = sb.partition_rank_guard(pt, rank, (float)radius, (float *)lo, (float *)hi, geo, (uint64_t *)held);
+    if (st != SB_OK) return throw_status(env, NULL, st, "sb_partition_rank_guard");
+    CHECK_NAPI(napi_create_object(env, &obj));
+    CHECK_NAPI(napi_create_double(env, geo[0], &vr));
+    CHECK_NAPI(napi_create_double(env, geo[1], &vh));
+    CHECK_NAPI(napi_set_named_property(env, obj, "lo", tlo));
+    CHECK_NAPI(napi_set_named_property(env, obj, "hi", thi));
+    CHECK_NAPI(napi_set_named_property(env, obj, "reach", vr));
+    CHECK_NAPI(napi_set_named_property(env, obj, "hop", vh));
+    CHECK_NAPI(napi_set_named_property(env, obj, "held", th));
+    return obj;
+}
+
+/* typed array of one element type (or undefined / null) -> pointer + element count */
+static int get_typed(napi_env env, napi_value v, napi_typedarray_type want, const void **data, uint32_t *n)
+{
+    napi_valuetype t;
+    bool is = false;
+    napi_typedarray_type tt;
+    size_t len, off;
+    void *p;
+    napi_value ab;
+    *data = NULL;
+    *n = 0;
+    if (napi_typeof(env, v, &t) != napi_ok) return 0;
+    if (t == napi_undefined || t == napi_null) return 1;
+    if (napi_is_typedarray(env, v, &is) != napi_ok || !is) return 0;
+    if (napi_get_typedarray_info(env, v, &tt, &len, &p, &ab, &off) != napi_ok || tt != want) return 0;
+    *data = p;
+    *n = (uint32_t)len;
+    return 1;
+}
+
+static int get_field(napi_env env, napi_value obj, const char *name, napi_value *v)
+{
+    bool has = false;
+    if (napi_has_named_property(env, obj, name, &has) != napi_ok || !has) return 0;
+    return napi_get_named_property(env, obj, name, v) == napi_ok;
+}
+
+/* haloGuard(handle, {rank, world, depth, contactReach, hop, motion, ownParticles: Uint32Array, held: BigUint64Array,
+ * ownBeams: Uint32Array, lo: Float32Array, hi: Float32Array}) sets the guard; haloGuard(handle, null) turns it off */
+static napi_value js_halo_guard(napi_env env, napi_callback_info info)
+{
+    if (!need_lib(env)) return NULL;
+    size_t argc = 2;
+    napi_value argv[2];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    sb_engine *e = argc >= 1 ? get_engine(env, argv[0]) : NULL;
+    if (!e) return NULL;
+    napi_valuetype t = napi_undefined;
+    if (argc >= 2) CHECK_NAPI(napi_typeof(env, argv[1], &t));
+    if (t == napi_null || t == napi_undefined) {
+        sb_status st = sb.halo_guard(e, NULL);
+        if (st != SB_OK) return throw_status(env, e, st, "sb_halo_guard");
+        return NULL;
+    }
+    sb_halo_guard_desc d;
+    memset(&d, 0, sizeof d);
+    d.struct_size = sizeof d;
+    double rank = -1, world = -1, depth = -1, reach = 0, hop = 0, motion = 0;
+    int ok = t == napi_object && opt_number(env, argv[1], "rank", &rank) && opt_number(env, argv[1], "world", &world) &&
+             opt_number(env, argv[1], "depth", &depth) && opt_number(env, argv[1], "hop", &hop);
+    (void)opt_number(env, argv[1], "contactReach", &reach);
+    (void)opt_number(env, argv[1], "motion", &motion);
+    const void *own = NULL, *held = NULL, *ownb = NULL, *lo = NULL, *hi = NULL;
+    uint32_t n_own = 0, n_held = 0, n_ownb = 0, n_lo = 0, n_hi = 0;
+    napi_value v;
+    ok = ok && get_field(env, argv[1], "ownParticles", &v) && get_typed(env, v, napi_uint32_array, &own, &n_own) &&
+         get_field(env, argv[1], "held", &v) && get_typed(env, v, napi_biguint64_array, &held, &n_held) &&
+         get_field(env, argv[1], "lo", &v) && get_typed(env, v, napi_float32_array, &lo, &n_lo) &&
+         get_field(env, argv[1], "hi", &v) && get_typed(env, v, napi_float32_array, &hi, &n_hi) &&
+         (!get_field(env, argv[1], "ownBeams", &v) || get_typed(env, v, napi_uint32_array, &ownb, &n_ownb));
+    if (!ok || rank < 0 || world < 1 || depth < 0 || n_held != n_own || n_lo != (uint32_t)world || n_hi != (uint32_t)world) {
+        napi_throw_type_error(env, NULL, "haloGuard(handle, {rank, world, depth, contactReach, hop, motion, ownParticles: Uint32Array, "
+                                         "held: BigUint64Array (one per own particle), ownBeams: Uint32Array, lo, hi: Float32Array(world)})");
+        return NULL;
+    }
+    d.rank = (uint32_t)rank;
+    d.world = (uint32_t)world;
+    d.depth = (uint32_t)depth;
+    d.contact_reach = (float)reach;
+    d.hop = (float)hop;
+    d.motion = (float)motion;
+    d.n_own_particles = n_own;
+    d.own_particles = (const uint32_t *)own;
+    d.held = (const uint64_t *)held;
+    d.n_own_beams = n_ownb;
+    d.own_beams = (const uint32_t *)ownb;
+    d.lo = (const float *)lo;
+    d.hi = (const float *)hi;
+    sb_status st = sb.halo_guard(e, &d);
+    if (st != SB_OK) return throw_status(env, e, st, "sb_halo_guard");
+    return NULL;
+}
+
+/* haloGuardStatus(handle) -> {kinds, violations, refreshes, firstRefresh, firstIsBeam, firstIndex, motion} (waits for the stream;
+ * firstRefresh / firstIsBeam / firstIndex are null while nothing has fired) */
+static napi_value js_halo_guard_status(napi_env env, napi_callback_info info)
+{
+    if (!need_lib(env)) return NULL;
+    size_t argc = 1;
+    napi_value argv[1];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    sb_engine *e = argc >= 1 ? get_engine(env, argv[0]) : NULL;
+    if (!e) return NULL;
+    sb_halo_guard_report r;
+    sb_status st = sb.halo_guard_status(e, &r);
+    if (st != SB_OK) return throw_status(env, e, st, "sb_halo_guard_status");
+    const int fired = r.first_refresh != 0xFFFFFFFFu;
+    napi_value obj, v, nul;
+    CHECK_NAPI(napi_get_null(env, &nul));
+    CHECK_NAPI(napi_create_object(env, &obj));
+    CHECK_NAPI(napi_create_uint32(env, r.kinds, &v));
+    CHECK_NAPI(napi_set_named_property(env, obj, "kinds", v));
+    CHECK_NAPI(napi_create_uint32(env, r.violations, &v));
+    CHECK_NAPI(napi_set_named_property(env, obj, "violations", v));
+    CHECK_NAPI(napi_create_uint32(env, r.refreshes, &v));
+    CHECK_NAPI(napi_set_named_property(env, obj, "refreshes", v));
+    CHECK_NAPI(napi_create_uint32(env, r.first_refresh, &v));
+    CHECK_NAPI(napi_set_named_property(env, obj, "firstRefresh", fired ? v : nul));
+    CHECK_NAPI(napi_get_boolean(env, r.first_is_beam != 0, &v));
+    CHECK_NAPI(napi_set_named_property(env, obj, "firstIsBeam", fired ? v : nul));
+    CHECK_NAPI(napi_create_uint32(env, r.first_index, &v));
+    CHECK_NAPI(napi_set_named_property(env, obj, "firstIndex", fired ? v : nul));
+    CHECK_NAPI(napi_create_double(env, r.motion, &v));
+    CHECK_NAPI(napi_set_named_property(env, obj, "motion", v));
+    return obj;
+}
+
 /* render(handle, {resolution, boundsSize, particleRadius}) -> Buffer: the binary PPM host/render.js renderPPM returns for the
  * state sb_load_buffers would read back ("P6" header included), drawn on the GPU by sb_render.  Absent / 0 fields: 512 and the
  * engine's own bounds / radius. */
@@ -932,6 +1096,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"partitionCreate", js_partition_create}, {"partitionDestroy", js_partition_destroy},
         {"partitionRankCounts", js_partition_rank_counts}, {"partitionRankScene", js_partition_rank_scene},
         {"partitionRankIds", js_partition_rank_ids}, {"partitionPeer", js_partition_peer}, {"render", js_render},
+        {"partitionRankGuard", js_partition_rank_guard}, {"haloGuard", js_halo_guard}, {"haloGuardStatus", js_halo_guard_status},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

@@ -51,6 +51,10 @@ struct sb_partition {
     std::vector<uint8_t> metadata, particles, beams;  // copies of the caller's records (active ones are read)
     std::vector<uint32_t> p_data_of_slot, b_data_of_slot;
     std::vector<Rank> ranks;
+    // halo guard (world <= 64): what sb_partition_rank_guard hands out
+    std::vector<float> lo, hi;           // per rank: x-extent of its own particles (+inf / -inf: owns none)
+    std::vector<uint64_t> held_of_slot;  // per global particle slot: bit r = rank r holds it (own or ghost)
+    float reach = 0.0f, longest_beam = 0.0f;
 };
 
 static inline uint32_t rd32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
@@ -81,6 +85,7 @@ static sb_status partition_create_impl(uint32_t layout, uint32_t maxP, uint32_t 
     std::unique_ptr<sb_partition> holder(new sb_partition()); // released to the caller on success only: an exception or an
     sb_partition *pt = holder.get();                          // early return below frees it
     pt->layout = layout; pt->world = world; pt->depth = depth; pt->P = P; pt->B = B; pt->maxP = maxP; pt->maxB = maxB;
+    pt->reach = reach;
     pt->metadata.assign(md, md + SB_METADATA_BYTES);
     pt->particles.assign(pd, pd + (size_t)maxP * SB_PARTICLE_STRIDE);
     pt->beams.assign(bd, bd + (size_t)maxB * bstride);
@@ -128,6 +133,19 @@ static sb_status partition_create_impl(uint32_t layout, uint32_t maxP, uint32_t 
     { std::vector<uint32_t> cur(adj0.begin(), adj0.end() - 1);
       for (uint32_t s = 0; s < B; s++) { adj[cur[ba[s]]++] = bb[s]; if (bb[s] != ba[s]) adj[cur[bb[s]]++] = ba[s]; } }
 
+    // longest live beam at partition time (the halo guard's hop length H)
+    for (uint32_t s = 0; s < B; s++) {
+        const uint8_t *pa = pt->particles.data() + (size_t)pt->p_data_of_slot[ba[s]] * SB_PARTICLE_STRIDE;
+        const uint8_t *pb = pt->particles.data() + (size_t)pt->p_data_of_slot[bb[s]] * SB_PARTICLE_STRIDE;
+        const float dx = rdf(pb) - rdf(pa), dy = rdf(pb + 4) - rdf(pa + 4), len = std::sqrt(dx * dx + dy * dy);
+        if (std::isfinite(len)) pt->longest_beam = std::max(pt->longest_beam, len);
+    }
+    const bool guard = world <= 64;
+    if (guard) {
+        pt->lo.assign(world, INFINITY);
+        pt->hi.assign(world, -INFINITY);
+        pt->held_of_slot.assign(P, 0);
+    }
     pt->ranks.resize(world);
     std::vector<uint32_t> stamp(P, 0xFFFFFFFFu), local_of_slot(P, 0), frontier, next;
     std::vector<std::vector<uint32_t>> local_p_of_slot(world); // per rank: local DATA index per global slot (or ~0)
@@ -150,6 +168,11 @@ static sb_status partition_create_impl(uint32_t layout, uint32_t maxP, uint32_t 
             frontier.swap(next);
         }
         for (uint32_t s = 0; s < P; s++) if (stamp[s] == r) R.particles.push_back(s); // ascending slot
+        if (guard) {
+            pt->lo[r] = xmin;
+            pt->hi[r] = xmax;
+            for (uint32_t s : R.particles) pt->held_of_slot[s] |= 1ull << r;
+        }
         // local data index = rank of the global data index among the local particles (monotone)
         std::vector<uint32_t> by_data(R.particles);
         std::sort(by_data.begin(), by_data.end(), [&](uint32_t p, uint32_t q) { return pt->p_data_of_slot[p] < pt->p_data_of_slot[q]; });
@@ -346,6 +369,30 @@ sb_status sb_partition_rank_ids(const sb_partition *p, uint32_t rank, uint32_t *
     if (particle_owned) std::copy(R.p_owned.begin(), R.p_owned.end(), particle_owned);
     if (beam_global) std::copy(R.b_global_data.begin(), R.b_global_data.end(), beam_global);
     if (beam_owned) std::copy(R.b_owned.begin(), R.b_owned.end(), beam_owned);
+    return SB_OK;
+}
+
+sb_status sb_partition_rank_guard(const sb_partition *p, uint32_t rank, float particle_radius, float *lo, float *hi, float geometry[2],
+                                  uint64_t *held)
+{
+    if (!p || rank >= p->world) { sb_set_create_error("sb_partition_rank_guard: no such rank"); return SB_ERR_INVALID; }
+    if (p->world > 64) { sb_set_create_error("sb_partition_rank_guard: the halo guard supports at most 64 ranks"); return SB_ERR_UNSUPPORTED; }
+    if (!(particle_radius > 0.0f) || !std::isfinite(particle_radius)) {
+        sb_set_create_error("sb_partition_rank_guard: particle_radius must be positive and finite");
+        return SB_ERR_INVALID;
+    }
+    if (lo) std::copy(p->lo.begin(), p->lo.end(), lo);
+    if (hi) std::copy(p->hi.begin(), p->hi.end(), hi);
+    if (geometry) {
+        geometry[0] = p->reach > 0.0f && p->world > 1 ? p->reach : 0.0f;
+        geometry[1] = SB_GUARD_HOP_HEADROOM * std::max(2.0f * particle_radius, p->longest_beam);
+    }
+    if (held) {
+        const Rank &R = p->ranks[rank];
+        std::vector<uint32_t> slot_of_local(R.p_global_data.size());
+        for (uint32_t k = 0; k < R.particles.size(); k++) slot_of_local[R.p_local_of_data[k]] = R.particles[k];
+        for (size_t i = 0; i < slot_of_local.size(); i++) held[i] = p->held_of_slot[slot_of_local[i]];
+    }
     return SB_OK;
 }
 

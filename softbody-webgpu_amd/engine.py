@@ -46,6 +46,43 @@ class SbRenderOptions(ctypes.Structure):
 
 RENDER_MAX_RESOLUTION = 16384
 
+GUARD_SLAB, GUARD_BAND, GUARD_BEAM, GUARD_MOTION = 1, 2, 4, 8     # SB_GUARD_* (include/softbody.h sb_halo_guard)
+GUARD_KIND_NAMES = {GUARD_SLAB: "A", GUARD_BAND: "B", GUARD_BEAM: "C", GUARD_MOTION: "D"}
+
+
+class SbHaloGuardDesc(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("rank", ctypes.c_uint32), ("world", ctypes.c_uint32),
+                ("depth", ctypes.c_uint32), ("contact_reach", ctypes.c_float), ("hop", ctypes.c_float),
+                ("motion", ctypes.c_float), ("n_own_particles", ctypes.c_uint32), ("own_particles", ctypes.c_void_p),
+                ("held", ctypes.c_void_p), ("n_own_beams", ctypes.c_uint32), ("own_beams", ctypes.c_void_p),
+                ("lo", ctypes.c_void_p), ("hi", ctypes.c_void_p), ("reserved", ctypes.c_uint32 * 4)]
+
+
+class SbHaloGuardReport(ctypes.Structure):
+    _fields_ = [("kinds", ctypes.c_uint32), ("violations", ctypes.c_uint32), ("refreshes", ctypes.c_uint32),
+                ("first_refresh", ctypes.c_uint32), ("first_is_beam", ctypes.c_uint32), ("first_index", ctypes.c_uint32),
+                ("motion", ctypes.c_float), ("reserved", ctypes.c_uint32)]
+
+
+class GuardStatus:
+    """sb_halo_guard_report: the verdict of an engine's halo guard.  `kinds` = SB_GUARD_* bits (0: nothing fired);
+    `first_refresh` / `first_is_beam` / `first_index` (LOCAL data index) name the first offending item, or are None."""
+
+    def __init__(self, r):
+        self.kinds, self.violations, self.refreshes, self.motion = r.kinds, r.violations, r.refreshes, r.motion
+        fired = r.first_refresh != 0xFFFFFFFF
+        self.first_refresh = r.first_refresh if fired else None
+        self.first_is_beam = bool(r.first_is_beam) if fired else None
+        self.first_index = r.first_index if fired else None
+
+    @property
+    def kind_names(self):
+        return "".join(n for bit, n in sorted(GUARD_KIND_NAMES.items()) if self.kinds & bit)
+
+    def __repr__(self):
+        return ("GuardStatus(kinds=%r, violations=%d, refreshes=%d, first_refresh=%r, first_is_beam=%r, first_index=%r)"
+                % (self.kind_names, self.violations, self.refreshes, self.first_refresh, self.first_is_beam, self.first_index))
+
 _lib = None
 
 
@@ -106,6 +143,8 @@ def load_library():
     L.sb_peer_connect.argtypes = [vp, u32, ctypes.POINTER(vp), vp, vp, vp, vp, vp, u32]
     L.sb_peer_exchange.argtypes = [vp]
     L.sb_halo_unpack.argtypes = [vp, vp]
+    L.sb_halo_guard.argtypes = [vp, ctypes.POINTER(SbHaloGuardDesc)]
+    L.sb_halo_guard_status.argtypes = [vp, ctypes.POINTER(SbHaloGuardReport)]
     L.sb_get_stream.argtypes = [vp, ctypes.POINTER(vp)]
     L.sb_render.argtypes = [vp, ctypes.POINTER(SbRenderOptions), vp, sz]
     L.sb_render_device.argtypes = [vp, ctypes.POINTER(SbRenderOptions), vp]
@@ -118,6 +157,7 @@ def load_library():
     L.sb_partition_rank_ids.argtypes = [vp, u32, vp, vp, vp, vp]
     L.sb_partition_peer_counts.argtypes = [vp, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32 * 4)]
     L.sb_partition_peer_lists.argtypes = [vp, u32, u32, vp, vp, vp, vp]
+    L.sb_partition_rank_guard.argtypes = [vp, u32, f32, vp, vp, vp, vp]
     L.sb_last_error.argtypes = [vp]
     L.sb_last_error.restype = ctypes.c_char_p
     L.sb_abi_version.restype = u32
@@ -289,6 +329,34 @@ class Engine:
 
     def halo_unpack(self, device_ptr):
         self._check(load_library().sb_halo_unpack(self._h, ctypes.c_void_p(device_ptr)))
+
+    def halo_guard(self, rank, world, depth, contact_reach, hop, lo, hi, own_particles, held, own_beams=(), motion=0.0):
+        """sb_halo_guard: check the partition behind every ghost refresh from now on (include/softbody.h states the rule).
+        own_particles / own_beams are LOCAL data indices, `held` the per-own-particle rank masks, lo / hi every rank's
+        x-extent at partition time; motion = s per substep (0: the default H / (16 depth)).  Call after halo_configure."""
+        op = np.ascontiguousarray(own_particles, dtype="<u4")
+        hd = np.ascontiguousarray(held, dtype="<u8")
+        ob = np.ascontiguousarray(own_beams, dtype="<u4")
+        lo_, hi_ = np.ascontiguousarray(lo, dtype="<f4"), np.ascontiguousarray(hi, dtype="<f4")
+        if hd.size != op.size or lo_.size != world or hi_.size != world:
+            raise ValueError("halo_guard: held needs one mask per own particle, lo / hi one value per rank")
+        d = SbHaloGuardDesc()
+        d.struct_size = ctypes.sizeof(SbHaloGuardDesc)
+        d.rank, d.world, d.depth = rank, world, depth
+        d.contact_reach, d.hop, d.motion = contact_reach, hop, motion
+        d.n_own_particles, d.own_particles, d.held = op.size, _ptr(op), _ptr(hd)
+        d.n_own_beams, d.own_beams = ob.size, _ptr(ob)
+        d.lo, d.hi = _ptr(lo_), _ptr(hi_)
+        self._check(load_library().sb_halo_guard(self._h, ctypes.byref(d)))
+
+    def halo_guard_off(self):
+        self._check(load_library().sb_halo_guard(self._h, None))
+
+    def halo_guard_status(self):
+        """The guard's verdict so far (waits for the engine's stream): a GuardStatus."""
+        r = SbHaloGuardReport()
+        self._check(load_library().sb_halo_guard_status(self._h, ctypes.byref(r)))
+        return GuardStatus(r)
 
     def stream(self):
         s = ctypes.c_void_p()

@@ -32,6 +32,31 @@ def hash_at(seed, idx):
     return (x >> np.uint64(11)).astype(np.float64) / float(1 << 52) - 1.0
 
 
+class HaloGuardData:
+    """What the halo guard needs of a partition (sb_partition_rank_guard): every rank's x-extent of own particles, the
+    contact reach R, the hop length H, and per LOCAL particle the mask of the ranks that hold it (bit t: rank t)."""
+
+    def __init__(self, lo, hi, reach, hop, held):
+        self.lo, self.hi = np.asarray(lo, "<f4"), np.asarray(hi, "<f4")
+        self.reach, self.hop = float(reach), float(hop)
+        self.held = np.asarray(held, "<u8")
+
+
+class RepartitionDue(RuntimeError):
+    """The halo guard of a rank fired: its partition has gone stale, and from the next refresh on its owned state may differ
+    from the single engine's.  Raised at the end of the frame in which it fired; the remedy is halo.repartition().
+    Fields: rank, kinds (SB_GUARD_* bits), kind_names ("A".."D", include/softbody.h), refresh (index of the first refresh that
+    failed), violations, and the first offending item: is_beam and global_id (a global particle data index, or a global beam
+    key of the plan)."""
+
+    def __init__(self, rank, status, global_id):
+        self.rank, self.kinds, self.kind_names = rank, status.kinds, status.kind_names
+        self.refresh, self.violations = status.first_refresh, status.violations
+        self.is_beam, self.global_id = status.first_is_beam, global_id
+        super().__init__("repartition due: rank %d, checks %s failed from refresh %d on (%d violations; first: %s %d)"
+                         % (rank, self.kind_names, self.refresh, self.violations, "beam" if self.is_beam else "particle", global_id))
+
+
 class Peer:
     def __init__(self, rank, ghost_p, send_p, ghost_b, send_b):
         self.rank = rank
@@ -51,6 +76,7 @@ class HaloPlan:
         self.peers = peers
         self.global_particle_id = global_particle_id    # per local particle
         self.global_beam_key = global_beam_key          # per local beam: (global id of A) * 4 + kind
+        self.guard = None                               # HaloGuardData (partition_scene plans of world <= 64)
 
     def lists(self):
         cat = lambda xs: np.concatenate(xs).astype("<u4") if xs else np.zeros(0, "<u4")  # noqa: E731
@@ -134,12 +160,13 @@ def slab_scene(sb, rank, world, W, H, d=30.0, origin=(1000.0, 1000.0), jitter=0.
     return buf, plan
 
 
-def partition_scene(buf, world, depth, contact_reach=0.0, ranks=None):
+def partition_scene(buf, world, depth, contact_reach=0.0, ranks=None, particle_radius=10.0):
     """Split ANY scene (a layout.Buffers: the default scene, a loaded snapshot, something a BufferMapper built) into
     x-slabs with ghost zones `depth` beam hops deep: the C library's sb_partition_* (csrc/sb_partition.cpp), shared
     with the Node host.  contact_reach > 0 also makes every particle within that distance (in x) of a rank's own
     particles a ghost, so that contacts across slab faces are computed on both sides.  Returns [(Buffers, HaloPlan)]
-    for `ranks` (default: all).  global_particle_id / global_beam_key of the plans are GLOBAL DATA INDICES."""
+    for `ranks` (default: all).  global_particle_id / global_beam_key of the plans are GLOBAL DATA INDICES.  With world <= 64 the
+    plans also carry what the halo guard needs (plan.guard, HaloGuardData; its hop length follows `particle_radius`)."""
     import ctypes
     from .engine import EngineError, _ptr, load_library
     L = load_library()
@@ -172,6 +199,10 @@ def partition_scene(buf, world, depth, contact_reach=0.0, ranks=None):
                 peers.append(Peer(pr.value, *lists))
             plan = HaloPlan(r, world, depth if world > 1 else 0, nP, np.nonzero(po)[0].astype("<u4"),
                             np.nonzero(bo)[0].astype("<u4"), peers, pg.astype(np.int64), bg.astype(np.int64))
+            if world <= 64:
+                lo, hi, geo, held = np.zeros(world, "<f4"), np.zeros(world, "<f4"), np.zeros(2, "<f4"), np.zeros(nP, "<u8")
+                check(L.sb_partition_rank_guard(h, r, float(particle_radius), _ptr(lo), _ptr(hi), _ptr(geo), _ptr(held)))
+                plan.guard = HaloGuardData(lo, hi, geo[0], geo[1], held)
             out.append((local, plan))
         return out
     finally:
@@ -231,19 +262,62 @@ class Exchanger:
 
     `engine` needs step(n), halo_pack(ptr), halo_unpack(ptr); `transport` moves the packed
     buffers: TorchTransport for real ranks (torch.distributed P2P, nccl=RCCL on GPU tensors, gloo on
-    CPU tensors), or a test double."""
+    CPU tensors), or a test double.
 
-    def __init__(self, engine, plan, transport):
+    guard=True sets the engine's halo guard (include/softbody.h sb_halo_guard; plans of partition_scene / repartition
+    only) with motion allowance `motion` per substep (0: the default): every refresh is then checked on the device, a
+    rank without neighbours refreshes (with empty lists) only to be checked, and frame() raises RepartitionDue at the
+    end of the frame in which the guard fired."""
+
+    def __init__(self, engine, plan, transport, guard=False, motion=0.0):
         self.engine, self.plan, self.transport = engine, plan, transport
         self.since = 0
         self.timer = None            # a StepTimer while somebody wants the device times of step() (bench.py)
         self.exchanges = 0
         self.beams_after_frames = engine.counts()[1]
+        self._check_guard_plan(guard)
         gp, sp, gb, sb_ = plan.lists()
         engine.halo_configure(gp, sp, gb, sb_)
         self.segs, n_send, n_recv, offsets = plan.segments()
         engine.halo_set_layout(*offsets)
         self.send, self.recv = transport.allocate(n_send, n_recv)
+        self._set_guard(guard, motion)
+
+    def _check_guard_plan(self, guard):
+        self.guarded = bool(guard)
+        if guard and getattr(self.plan, "guard", None) is None:
+            raise ValueError("guard=True needs a plan of partition_scene() / repartition() with world <= 64 (slab_scene plans "
+                             "carry no guard data)")
+        if guard and self.plan.world > 1 and self.plan.depth <= 0:
+            raise ValueError("guard=True needs a ghost depth of at least 1")
+
+    def _set_guard(self, guard, motion):
+        if not guard:
+            return
+        p, g = self.plan, self.plan.guard
+        own = p.owned_particles
+        self.engine.halo_guard(p.rank, p.world, max(p.depth, 1), g.reach, g.hop, g.lo, g.hi, own, g.held[own],
+                               p.owned_beams, motion)
+
+    def _refreshes(self):
+        """does this rank run the refresh schedule? (always with a guard: a rank without neighbours is still checked)"""
+        return bool(self.plan.peers) or self.guarded
+
+    def guard_status(self):
+        """The guard's verdict so far, without raising: an engine.GuardStatus (None without a guard).  Waits for the
+        engine's stream."""
+        return self.engine.halo_guard_status() if self.guarded else None
+
+    def check_guard(self):
+        """Raise RepartitionDue if the guard has fired (frame() calls it after its own wait; drivers that run ranks in
+        lock step call it after theirs)."""
+        if not self.guarded:
+            return
+        st = self.engine.halo_guard_status()
+        if st.kinds:
+            p = self.plan
+            gid = p.global_beam_key[st.first_index] if st.first_is_beam else p.global_particle_id[st.first_index]
+            raise RepartitionDue(p.rank, st, int(gid))
 
     def verify(self):
         """What a halo run must not have done (call after stepping; it drains the engine's stream): removed beams by any
@@ -273,9 +347,13 @@ class Exchanger:
             self.since = 0
             self.engine.halo_delete_ghosts()
         self.beams_after_frames = self.engine.counts()[1]
+        self.check_guard()           # (counts() has drained the stream: the status read finds it idle, one short copy)
 
     def exchange(self):
         if not self.plan.peers:
+            if self.guarded:         # nothing to trade; the guard runs behind the (empty) unpack
+                self.engine.halo_pack(None)
+                self.engine.halo_unpack(None)
             return
         self.engine.halo_pack(self.transport.pointer(self.send))
         self.transport.exchange(self.send, self.recv, self.segs, self.engine)
@@ -291,7 +369,7 @@ class Exchanger:
     def step(self, n):
         k = self.plan.depth
         t = self.timer
-        if not self.plan.peers or k <= 0:
+        if not self._refreshes() or k <= 0:
             if t is not None:
                 t.run("step", self.engine.step, n)
             else:
@@ -324,17 +402,19 @@ class PeerExchanger(Exchanger):
         ex = PeerExchanger(engine, plan);  cards = all_gather(ex.card);  ex.connect(cards)
     `cards` is indexable by rank."""
 
-    def __init__(self, engine, plan, timeout_ms=10000):
+    def __init__(self, engine, plan, timeout_ms=10000, guard=False, motion=0.0):
         self.engine, self.plan, self.transport = engine, plan, None
         self.since = 0
         self.timer = None
         self.exchanges = 0
         self.timeout_ms = timeout_ms
         self.beams_after_frames = engine.counts()[1]
+        self._check_guard_plan(guard)
         gp, sp, gb, sb_ = plan.lists()
         engine.halo_configure(gp, sp, gb, sb_)
         self.segs, n_send, n_recv, offsets = plan.segments()
         engine.halo_set_layout(*offsets)
+        self._set_guard(guard, motion)
         ptr, handle, _ = engine.peer_mailbox()
         import os
         self.card = dict(rank=plan.rank, pid=os.getpid(), pointer=ptr, handle=handle, recv_floats=n_recv,
@@ -370,7 +450,7 @@ class PeerExchanger(Exchanger):
         self.connected = True
 
     def exchange(self):
-        if self.plan.peers:
+        if self.plan.peers or self.guarded:    # (without neighbours: the guard's check only)
             self.engine.peer_exchange()
 
 
@@ -479,7 +559,7 @@ def owned_state(plan, buf):
     return (plan.global_particle_id[op], buf.particles[op].copy(), plan.global_beam_key[ob], dyn, live[ob])
 
 
-def repartition(gbuf, states, world, depth, contact_reach=0.0, ranks=None):
+def repartition(gbuf, states, world, depth, contact_reach=0.0, ranks=None, particle_radius=10.0):
     """Ownership does not migrate by itself: the slabs and ghost zones are those of the partition, so free particles that
     wander into another rank's territory stop being seen by that rank's owners.  The remedy is to partition
     again from the current state: `gbuf` is the global scene the run was partitioned from (layout.Buffers; brought up to
@@ -502,5 +582,5 @@ def repartition(gbuf, states, world, depth, contact_reach=0.0, ranks=None):
     keep = slots[~dead[slots.astype(np.int64)]]
     gbuf.mapping[P0:P0 + keep.size] = keep
     gbuf.beam_count = int(keep.size)
-    return partition_scene(gbuf, world, depth, contact_reach, ranks)
+    return partition_scene(gbuf, world, depth, contact_reach, ranks, particle_radius)
 

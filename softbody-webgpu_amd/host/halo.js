@@ -10,6 +10,7 @@
  *   HaloPlan                                                       who owns what on a rank, what it trades with whom
  *   PeerExchanger                                                  mailbox set-up, connect, step(n) with a refresh every depth substeps, frame()
  *   ownedState / repartition                                       ownership follows the particles: partition again from the gathered state
+ *   RepartitionDueError                                            what a guarded PeerExchanger throws when the partition has gone stale
  * The same three pieces exist for the Python harness in softbody-webgpu_amd/halo.py; both call the same C code.
  */
 const { native } = require('./native');
@@ -62,7 +63,7 @@ class HaloPlan {
  * depth * max(2r + motion per substep, longest beam)).  Returns [{rank, maxParticles, maxBeams, metadata, mapping,
  * particleData, beamData, plan}], the buffers in the scene's layout, sized to the rank's share.
  */
-function partitionScene(scene, world, depth, contactReach, ranks) {
+function partitionScene(scene, world, depth, contactReach, ranks, particleRadius) {
     const addon = native();
     const layout = typeof scene.layout === 'object' ? scene.layout.id : scene.layout;
     const part = addon.partitionCreate(layout, scene.maxParticles, scene.maxBeams, scene.metadata, scene.mapping,
@@ -86,11 +87,29 @@ function partitionScene(scene, world, depth, contactReach, ranks) {
             for (let j = 0; j < c[4]; j++) peers.push(addon.partitionPeer(part, r, j));
             local.plan = new HaloPlan(r, world, world > 1 ? depth : 0, c[0], owned(ids.particleOwned), owned(ids.beamOwned), peers,
                 ids.particleGlobal, ids.beamGlobal);
+            // what the halo guard needs (world <= 64): every rank's own x-extent, R, H, the held masks of the local particles
+            local.plan.guard = world <= 64 ? addon.partitionRankGuard(part, r, particleRadius || 10) : null;
             out.push(local);
         }
         return out;
     } finally {
         addon.partitionDestroy(part);
+    }
+}
+
+/**
+ * A guarded PeerExchanger's frame() found that the halo guard fired (include/softbody.h sb_halo_guard): from the refresh
+ * `refresh` on, this rank's partition was stale.  kinds: SB_GUARD_* bits (kindNames "A".."D"); globalId: the global particle
+ * data index (or, isBeam, the global beam data index) of the first offending item.  The remedy is repartition().
+ */
+class RepartitionDueError extends Error {
+    constructor(rank, st, globalId) {
+        const names = ['A', 'B', 'C', 'D'].filter((_, k) => st.kinds & (1 << k)).join('');
+        super('repartition due: rank ' + rank + ', checks ' + names + ' failed from refresh ' + st.firstRefresh + ' on (' + st.violations +
+            ' violations; first: ' + (st.firstIsBeam ? 'beam ' : 'particle ') + globalId + ')');
+        this.name = 'RepartitionDueError';
+        Object.assign(this, { rank, kinds: st.kinds, kindNames: names, refresh: st.firstRefresh, violations: st.violations,
+            isBeam: st.firstIsBeam, globalId });
     }
 }
 
@@ -103,11 +122,17 @@ function partitionScene(scene, world, depth, contactReach, ranks) {
  * A card is plain data (the 64-byte IPC handle as an array of bytes), so it survives JSON / process.send.
  */
 class PeerExchanger {
-    constructor(handle, plan, timeoutMs) {
+    /** opts: {guard: true, motion: s per substep (0: default)} sets the halo guard (plans of partitionScene / repartition only);
+     *  may stand in the place of timeoutMs */
+    constructor(handle, plan, timeoutMs, opts) {
+        if (typeof timeoutMs === 'object' && timeoutMs !== null) { opts = timeoutMs; timeoutMs = undefined; }
+        opts = opts || {};
         this.addon = native();
         this.handle = handle;
         this.plan = plan;
-        this.timeoutMs = timeoutMs || 10000;
+        this.timeoutMs = timeoutMs || opts.timeoutMs || 10000;
+        this.guarded = !!opts.guard;
+        if (this.guarded && !plan.guard) throw new TypeError('guard: true needs a plan of partitionScene() / repartition() with world <= 64');
         this.since = 0;
         this.connected = false;
         this.beamsAfterFrames = this.addon.getCounts(handle).beams;
@@ -115,6 +140,12 @@ class PeerExchanger {
         const lay = plan.segments();
         this.segs = lay.segments;
         this.addon.haloSetLayout(handle, ...lay.offsets);
+        if (this.guarded) {
+            const g = plan.guard, own = plan.ownedParticles;
+            this.addon.haloGuard(handle, { rank: plan.rank, world: plan.world, depth: Math.max(plan.depth, 1), contactReach: g.reach,
+                hop: g.hop, motion: opts.motion || 0, ownParticles: own, held: BigUint64Array.from(own, (i) => g.held[i]),
+                ownBeams: plan.ownedBeams, lo: g.lo, hi: g.hi });
+        }
         const box = this.addon.peerMailbox(handle);
         this.card = {
             rank: plan.rank, pid: process.pid, pointer: box.pointer, handle: Array.from(new Uint8Array(box.handle)),
@@ -146,13 +177,28 @@ class PeerExchanger {
     }
 
     exchange() {
-        if (this.plan.peers.length) this.addon.peerExchange(this.handle);
+        if (this.plan.peers.length || this.guarded) this.addon.peerExchange(this.handle); // (no neighbours: the guard's check only)
+    }
+
+    /** the guard's verdict so far (waits for the engine's stream), or null without a guard */
+    guardStatus() {
+        return this.guarded ? this.addon.haloGuardStatus(this.handle) : null;
+    }
+
+    /** throws RepartitionDueError if the guard has fired */
+    checkGuard() {
+        if (!this.guarded) return;
+        const st = this.addon.haloGuardStatus(this.handle);
+        if (st.kinds) {
+            const p = this.plan;
+            throw new RepartitionDueError(p.rank, st, st.firstIsBeam ? p.globalBeamKey[st.firstIndex] : p.globalParticleId[st.firstIndex]);
+        }
     }
 
     /** n substeps, with a ghost refresh after every plan.depth of them (counted across calls) */
     step(n) {
         const k = this.plan.depth;
-        if (!this.plan.peers.length || k <= 0) { this.addon.step(this.handle, n); return; }
+        if ((!this.plan.peers.length && !this.guarded) || k <= 0) { this.addon.step(this.handle, n); return; }
         while (n > 0) {
             const m = Math.min(n, k - this.since);
             this.addon.step(this.handle, m);
@@ -176,6 +222,7 @@ class PeerExchanger {
             this.addon.haloDeleteGhosts(this.handle);
         }
         this.beamsAfterFrames = this.addon.getCounts(this.handle).beams;
+        this.checkGuard();  // (getCounts has drained the stream: the status read finds it idle)
     }
 
     /** beams may only disappear through frame() above: a plain deletePass()/frame() of one rank's engine makes the ranks diverge */
@@ -223,7 +270,7 @@ function ownedState(plan, local) {
  * of the mapping by stable compaction, as compute_delete does); `states` = ownedState() of EVERY rank.  Call it between
  * frames; every rank then uploads its new scene and builds a new PeerExchanger.  (halo.py repartition.)
  */
-function repartition(scene, states, world, depth, contactReach, ranks) {
+function repartition(scene, states, world, depth, contactReach, ranks, particleRadius) {
     const L = layoutOf(scene), f = new Float32Array(scene.particleData), bv = new DataView(scene.beamData), md = new DataView(scene.metadata);
     const dead = new Uint8Array(scene.maxBeams), seen = new Uint8Array(scene.maxParticles);
     for (const st of states) {
@@ -245,7 +292,7 @@ function repartition(scene, states, world, depth, contactReach, ranks) {
         if (!dead[idx]) map[scene.maxParticles + w++] = idx;
     }
     md.setUint32(24, w, true);
-    return partitionScene(scene, world, depth, contactReach, ranks);
+    return partitionScene(scene, world, depth, contactReach, ranks, particleRadius);
 }
 
-module.exports = { HaloPlan, PeerExchanger, partitionScene, ownedState, repartition };
+module.exports = { HaloPlan, PeerExchanger, RepartitionDueError, partitionScene, ownedState, repartition };

@@ -230,28 +230,46 @@ export class HaloPlan {
     readonly ownedParticles: Uint32Array; readonly ownedBeams: Uint32Array;
     readonly peers: HaloPeer[];
     readonly globalParticleId: Uint32Array; readonly globalBeamKey: Uint32Array;
+    /** halo guard data (partitionScene / repartition with world <= 64; null otherwise) */
+    readonly guard: HaloGuardData | null;
     lists(): [Uint32Array, Uint32Array, Uint32Array, Uint32Array];
     segments(): { segments: { rank: number, send: [number, number], recv: [number, number] }[], sendFloats: number,
         recvFloats: number, offsets: [Uint32Array, Uint32Array, Uint32Array, Uint32Array] };
 }
+/** sb_partition_rank_guard: every rank's own x-extent, the contact reach R, the hop length H, and per LOCAL particle the mask
+ *  of the ranks that hold it (bit t: rank t) */
+export type HaloGuardData = { readonly lo: Float32Array, readonly hi: Float32Array, readonly reach: number, readonly hop: number,
+    readonly held: BigUint64Array };
 export type RankScene = { readonly rank: number, readonly layout: 1 | 2, readonly maxParticles: number, readonly maxBeams: number,
     readonly metadata: ArrayBuffer, readonly mapping: ArrayBuffer, readonly particleData: ArrayBuffer, readonly beamData: ArrayBuffer,
     readonly plan: HaloPlan };
 /** any scene (a BufferMapper after writeState(), or its four buffers) -> x-slabs with ghost zones `depth` beam hops deep */
 export function partitionScene(scene: BufferMapper | { layout: 1 | 2, maxParticles: number, maxBeams: number, metadata: ArrayBuffer,
     mapping: ArrayBuffer, particleData: ArrayBuffer, beamData: ArrayBuffer }, world: number, depth: number, contactReach?: number,
-    ranks?: number[]): RankScene[];
+    ranks?: number[], particleRadius?: number): RankScene[];
 /** a rank's share of the gathered scene: rows of its own particles, dynamic fields of its own beams, which of them are left */
 export type OwnedState = { readonly particleIds: Uint32Array, readonly particleRows: Float32Array, readonly beamKeys: Uint32Array,
     readonly beamDyn: Float32Array, readonly live: Uint8Array };
 export function ownedState(plan: HaloPlan, local: RankScene): OwnedState;
 /** partition again from the current state (between frames): updates `scene` in place from every rank's ownedState(), then partitionScene() */
 export function repartition(scene: Parameters<typeof partitionScene>[0], states: OwnedState[], world: number, depth: number,
-    contactReach?: number, ranks?: number[]): RankScene[];
+    contactReach?: number, ranks?: number[], particleRadius?: number): RankScene[];
 export type PeerCard = { readonly rank: number, readonly pid: number, readonly pointer: number, readonly handle: number[],
     readonly recvFloats: number, readonly recv: [number, number, number][] };
+/** the halo guard's verdict (sb_halo_guard_report); the first* fields are null while nothing has fired */
+export type HaloGuardStatus = { readonly kinds: number, readonly violations: number, readonly refreshes: number,
+    readonly firstRefresh: number | null, readonly firstIsBeam: boolean | null, readonly firstIndex: number | null, readonly motion: number };
+/** thrown by a guarded PeerExchanger's frame(): the partition has gone stale; repartition() */
+export class RepartitionDueError extends Error {
+    readonly rank: number; readonly kinds: number; readonly kindNames: string; readonly refresh: number;
+    readonly violations: number; readonly isBeam: boolean; readonly globalId: number;
+}
+export type PeerExchangerOptions = { guard?: boolean, motion?: number, timeoutMs?: number };
 export class PeerExchanger {
-    constructor(handle: unknown, plan: HaloPlan, timeoutMs?: number);
+    constructor(handle: unknown, plan: HaloPlan, timeoutMs?: number | PeerExchangerOptions, opts?: PeerExchangerOptions);
+    guardStatus(): HaloGuardStatus | null;
+    /** throws RepartitionDueError if the guard has fired (frame() calls it at its end) */
+    checkGuard(): void;
     readonly card: PeerCard;
     readonly connected: boolean;
     connect(cardsByRank: (PeerCard | undefined)[]): void;
