@@ -35,6 +35,9 @@
  *         reference itself does: engine.ts:138).  sb_delete_pass, sb_write_user_input
  *         and the sb_halo_* / sb_peer_* calls still only enqueue.
  *       Any collision mode and path: sb_render waits for the stream, sb_render_device only enqueues.
+ *       sb_read_state_device and sb_write_particles_device only enqueue (the first export after an upload builds its tables
+ *         and waits for the stream once, as the first render does; with SB_COLLIDE_GRID the import's reset of the spatial
+ *         hash copies its start state from host memory, which the runtime may do behind the work in flight).
  *       A wait POLLS the stream for as long as the work in flight should take (busily for
  *         the first 8 ms, then every ~50 us between short sleeps; 0.2 s at most) before it
  *         parks the thread: being woken costs 0.2 - 0.5 ms on some hosts, more than many
@@ -385,6 +388,32 @@ typedef struct sb_render_options {
 } sb_render_options;
 sb_status sb_render(sb_engine *e, const sb_render_options *opts, void *rgb, size_t rgb_bytes);
 sb_status sb_render_device(sb_engine *e, const sb_render_options *opts, void *device_rgb);
+
+/* ---- the state in device memory (no host round trip) ----
+ * Both calls only ENQUEUE on the engine's stream; the device buffers must stay valid until that work has run.  The first export
+ * after an upload builds its beam tables and waits for the stream once, as the first render does; later calls only enqueue.
+ * Errors: SB_ERR_STATE before an upload; SB_ERR_UNSUPPORTED on an engine with ghost zones or peers configured (ranks are not
+ * handled here); SB_ERR_INVALID for a NULL source to sb_write_particles_device, or a particle buffer that is not 8-byte / a beam
+ * buffer that is not 16-byte aligned.
+ *
+ * sb_read_state_device -- any pointer may be NULL:
+ *   particles:  max_particles * 24 B, the particle record (6 f32: p.xy, v.xy, a.xy) at each particle's DATA index: exactly the
+ *               bytes sb_load_buffers would write into its particle buffer at this point of the stream.
+ *   beams:      max_beams * 16 B, 4 f32 { target_length, last_length, strain, stress } at each beam's data index (the data indices
+ *               of the latest upload's mapping; a beam a delete pass removed keeps its last state, as in sb_load_buffers).
+ *   beam_alive: max_beams bytes, 1 = live, 0 = removed by a delete pass (or by a plan-keeping upload), per data index.
+ *   Data indices that hold no particle / beam of the latest upload are NOT written.  Reading only reads: the state, the spatial
+ *   hash, the per-tile flags and the schedule stay as they were, and every later result is the one without the call. */
+sb_status sb_read_state_device(sb_engine *e, void *device_particles, void *device_beams, void *device_beam_alive);
+
+/* sb_write_particles_device -- overwrites p, v, a of every particle from a device buffer in the particle layout above (only the
+ * records at the data indices of the scene's particles are read).  Beams, counts, pending break flags, the mapping and the substep
+ * count are untouched.  Every later result is the one the engine would compute had its particle state been these bytes all along.
+ * The spatial hash starts again (as after an upload that keeps the plan) and the hybrid schedule looks at the scene afresh.  An
+ * import that moves particles far from where the last planning upload saw them stays correct but may run slower until the next
+ * planning upload: the hash keeps the frame fitted at that upload (particles outside are clamped into its edge cells), and the
+ * tiles stay those bisected from the upload's positions. */
+sb_status sb_write_particles_device(sb_engine *e, const void *device_particles);
 
 /* the engine's hipStream_t, so a caller can order its own work (RCCL send/recv) after it. */
 sb_status sb_get_stream(sb_engine *e, void **hip_stream);

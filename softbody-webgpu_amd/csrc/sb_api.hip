@@ -212,18 +212,6 @@ static inline uint32_t beam_stride(const sb_engine *e)
 {
     return e->opt.layout == SB_LAYOUT_V1 ? SB_BEAM_STRIDE_V1 : SB_BEAM_STRIDE_V2;
 }
-static inline uint32_t map_isz(const sb_engine *e) { return e->opt.layout == SB_LAYOUT_V1 ? 2 : 4; }
-static inline uint32_t map_get(const sb_engine *e, const uint8_t *m, size_t id)
-{
-    if (e->opt.layout == SB_LAYOUT_V1) {
-        uint16_t v;
-        memcpy(&v, m + 2 * id, 2);
-        return v;
-    }
-    uint32_t v;
-    memcpy(&v, m + 4 * id, 4);
-    return v;
-}
 static inline void map_set(const sb_engine *e, uint8_t *m, size_t id, uint32_t val)
 {
     if (e->opt.layout == SB_LAYOUT_V1) {
@@ -680,6 +668,7 @@ sb_status sb_destroy(sb_engine *e)
     reap_join(e);
     free_scene(e);
     sbr_release(e);
+    sbs_release(e);
     for (const auto &b : e->pool_free) (void)hipFree(b.first);
     e->pool_free.clear();
     if (e->dev_err) (void)hipHostFree(e->dev_err);
@@ -704,9 +693,26 @@ static inline uint32_t sb_grid_executed0()
     return v;
 }
 
-// the caller's beam slots (those of the latest upload) -> the engine's own (sb_engine.h h_user_slot)
-static inline uint32_t sb_user_beams(const sb_engine *e) { return e->h_user_slot.empty() ? e->B : (uint32_t)e->h_user_slot.size(); }
-static inline uint32_t sb_user_slot(const sb_engine *e, size_t u) { return e->h_user_slot.empty() ? (uint32_t)u : e->h_user_slot[u]; }
+} // extern "C"
+
+// The spatial hash forgets every particle position it holds: no build yet, same frame (an upload that keeps the plan; a particle
+// import, sb_state_io.hip).  Enqueued on the engine's stream; the first substep after it starts with a forced helper launch.
+sb_status sb_grid_reset_hash(sb_engine *e)
+{
+    if (!(e->opt.collision_mode == SB_COLLIDE_GRID && e->d_grid_ctl)) return SB_OK;
+    for (int k = 0; k < 2; k++) SB_HIP(e, hipMemsetAsync(e->d_head[k], 0, e->grid_heads * 8, e->stream));
+    SB_HIP(e, hipMemsetAsync(e->d_blk_max, 0, e->grid_slots * 4, e->stream));
+    SB_HIP(e, hipMemsetAsync(e->d_grid_outside, 0, 16, e->stream));
+    SB_HIP(e, hipMemsetAsync(e->d_nl_count, 0, std::max<size_t>(e->P, 1) * 4, e->stream));
+    SB_HIP(e, hipMemcpyAsync(e->d_grid_ctl, e->grid_ctl0, sizeof e->grid_ctl0, hipMemcpyHostToDevice, e->stream));
+    e->grid_par = 0;
+    e->grid_force = true;
+    e->grid_classic_left = e->grid_classic_chunk = e->grid_calm = 0;
+    e->grid_executed = sb_grid_executed0();
+    return SB_OK;
+}
+
+extern "C" {
 
 // An upload of the SAME topology (same counts, same mapping, every beam between the same two particles with the same rest
 // length and material) as the scene on the device -- the editor moved or nudged something, or a caller steps from a saved
@@ -914,17 +920,7 @@ static sb_status rewrite_scene_state(sb_engine *e, const uint8_t *md, const uint
         e->uploads_edited += B != Bu ? 1u : 0u;
     }
     e->h_user_slot.swap(user_slot);
-    if (e->opt.collision_mode == SB_COLLIDE_GRID && e->d_grid_ctl) { // the hash: no build yet, same frame
-        for (int k = 0; k < 2; k++) SB_HIP(e, hipMemsetAsync(e->d_head[k], 0, e->grid_heads * 8, e->stream));
-        SB_HIP(e, hipMemsetAsync(e->d_blk_max, 0, e->grid_slots * 4, e->stream));
-        SB_HIP(e, hipMemsetAsync(e->d_grid_outside, 0, 16, e->stream));
-        SB_HIP(e, hipMemsetAsync(e->d_nl_count, 0, std::max<size_t>(P, 1) * 4, e->stream));
-        SB_HIP(e, hipMemcpyAsync(e->d_grid_ctl, e->grid_ctl0, sizeof e->grid_ctl0, hipMemcpyHostToDevice, e->stream));
-        e->grid_par = 0;
-        e->grid_force = true;
-        e->grid_classic_left = e->grid_classic_chunk = e->grid_calm = 0;
-        e->grid_executed = sb_grid_executed0();
-    }
+    SB_TRY(sb_grid_reset_hash(e));
     memcpy(&e->consts, md + 48, sizeof(SbConsts));
     SB_HIP(e, hipStreamSynchronize(e->stream));
     e->uploads_kept++;
@@ -2540,6 +2536,7 @@ sb_status sb_write_buffers(sb_engine *e, const void *metadata, size_t metadata_b
                            const void *beams, size_t beams_bytes)
 {
     sbr_invalidate(e);
+    sbs_invalidate(e);
     if (e) e->halo_configured = e->guard_on = false; // (also when the upload keeps the plan: a new scene has no halo, no guard)
     SB_GUARDED(e, sb_write_buffers_impl(e, metadata, metadata_bytes, mapping, mapping_bytes, particles, particles_bytes,
                                         beams, beams_bytes))

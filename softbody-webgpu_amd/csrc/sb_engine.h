@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstring>
 #include <string>
 #include <thread>
 #include <vector>
@@ -245,11 +246,29 @@ struct sb_engine {
     std::thread reaper;               // frees the host arrays of the last upload (sb_api.hip: SbUploadTrash)
 
     struct SbRenderState *rs = nullptr; // sb_render.hip: draw tables (rebuilt at the first render after an upload) + key image
+    struct SbStateIoState *sio = nullptr; // sb_state_io.hip: export tables (rebuilt at the first export after an upload)
 
     size_t device_bytes = 0;
     std::vector<void *> allocs;                             // freed with the scene (not pooled)
     std::vector<std::pair<void *, size_t>> pool_used, pool_free; // device blocks of the scene / kept for the next upload (sb_api.hip dev_alloc)
 };
+
+// mapping entries of the caller's layout (u16 in v1, u32 in v2)
+static inline uint32_t map_isz(const sb_engine *e) { return e->opt.layout == SB_LAYOUT_V1 ? 2 : 4; }
+static inline uint32_t map_get(const sb_engine *e, const uint8_t *m, size_t id)
+{
+    if (e->opt.layout == SB_LAYOUT_V1) {
+        uint16_t v;
+        memcpy(&v, m + 2 * id, 2);
+        return v;
+    }
+    uint32_t v;
+    memcpy(&v, m + 4 * id, 4);
+    return v;
+}
+// the caller's beam slots (those of the latest upload) -> the engine's own (h_user_slot above)
+static inline uint32_t sb_user_beams(const sb_engine *e) { return e->h_user_slot.empty() ? e->B : (uint32_t)e->h_user_slot.size(); }
+static inline uint32_t sb_user_slot(const sb_engine *e, size_t u) { return e->h_user_slot.empty() ? (uint32_t)u : e->h_user_slot[u]; }
 
 // sb_kernels.hip
 void sbk_launch_substep(sb_engine *e, bool write_aux);
@@ -274,3 +293,9 @@ void sbk_hybrid_launch(sb_engine *e, const uint32_t *ks, uint32_t count, bool au
 void sbr_invalidate(sb_engine *e);      // an upload replaced the scene: the next render builds its draw tables again
 void sbr_release(sb_engine *e);         // everything sb_render allocated (sb_destroy)
 double sbr_last_build_ms(const sb_engine *e);
+sb_status sbr_copy_table(sb_engine *e, const uint32_t **copy); // per engine beam slot: the copy read back for it (device; built on first use)
+// sb_state_io.hip
+void sbs_invalidate(sb_engine *e);      // an upload replaced the scene: the next export builds its tables again
+void sbs_release(sb_engine *e);         // everything sb_state_io allocated (sb_destroy)
+// sb_api.hip
+sb_status sb_grid_reset_hash(sb_engine *e); // the spatial hash forgets every position it holds (plan-keeping upload, particle import)

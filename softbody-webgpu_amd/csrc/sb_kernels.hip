@@ -681,16 +681,6 @@ struct SbHaloFlags {
     uint32_t *plastic0, *plastic1; // blocked layout only (else nullptr), with
     const uint32_t *tile_b0;     // its beams per tile
 };
-SB_DEV uint32_t sb_range_of(const uint32_t *__restrict__ first, uint32_t n, uint32_t i) // largest t < n with first[t] <= i
-{
-    uint32_t lo = 0u, hi = n;
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (first[mid] <= i) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // packed float buffer -> ghost lists (every device copy of a ghost beam is refreshed)
 __global__ __launch_bounds__(SB_BLOCK) void k_halo_unpack(SbParticleArrays c, SbBeamArrays b,

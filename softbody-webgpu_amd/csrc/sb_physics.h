@@ -550,6 +550,17 @@ static_assert(sizeof(SbGridCtl) % 16 == 0, "SbGridCtl is moved in 16-byte chunks
 // load per word and per particle was a trip past the L2 each
 #define SB_CTL_LOAD(p) (*(p))
 #define SB_AGENT_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+// the tile (range) of item i: largest t < n with first[t] <= i (halo unpack, particle import)
+SB_DEV uint32_t sb_range_of(const uint32_t *__restrict__ first, uint32_t n, uint32_t i)
+{
+    uint32_t lo = 0u, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (first[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
 
 SB_DEV SbGridGeom sb_grid_geom_load(const SbGridGeom *c)
 {

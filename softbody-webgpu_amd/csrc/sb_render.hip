@@ -43,6 +43,7 @@ struct SbrArgs {
 // render after it) and the key image (kept until sb_destroy or a larger resolution; not in the scene pool)
 struct SbRenderState {
     bool valid = false;             // the tables belong to the scene on the device (sb_write_buffers clears this)
+    bool copy_valid = false;        // ... d_copy alone (sbr_copy_table: shared with sb_state_io.hip's beam export)
     uint32_t nbeam_slots = 0;       // engine beam slots the tables cover
     uint2 *d_ends = nullptr;        // per engine beam slot: internal particle indices of A and B; x = 0xFFFFFFFF: not drawn
     uint32_t *d_copy = nullptr;     // per engine beam slot: the copy whose strain / stress is read back for it
@@ -346,7 +347,7 @@ static sb_status sbr_grow(sb_engine *e, T **p, size_t &cap, size_t n)
 
 void sbr_invalidate(sb_engine *e)
 {
-    if (e && e->rs) e->rs->valid = false;
+    if (e && e->rs) e->rs->valid = e->rs->copy_valid = false;
 }
 
 void sbr_release(sb_engine *e)
@@ -361,6 +362,24 @@ void sbr_release(sb_engine *e)
 }
 
 double sbr_last_build_ms(const sb_engine *e) { return e && e->rs ? e->rs->build_ms : 0.0; }
+
+// per engine beam slot: the copy whose state sb_load_buffers reads back for it (h_copy_of_slot on the device), built at the first
+// use after an upload; the draw tables and sb_state_io.hip's beam export share it (copy may be NULL: build only)
+sb_status sbr_copy_table(sb_engine *e, const uint32_t **copy)
+{
+    if (!e->rs) e->rs = new SbRenderState();
+    SbRenderState &r = *e->rs;
+    if (!r.copy_valid) {
+        const uint32_t B = e->B;
+        if (e->h_copy_of_slot.size() < B) SBR_FAIL(e, SB_ERR_STATE, "host shadows of the scene are inconsistent");
+        SB_TRYR(sbr_grow(e, &r.d_copy, r.cap_copy, B));
+        if (B) SBR_HIP(e, hipMemcpyAsync(r.d_copy, e->h_copy_of_slot.data(), (size_t)B * 4, hipMemcpyHostToDevice, e->stream));
+        SBR_HIP(e, hipStreamSynchronize(e->stream)); // (an upload may rewrite the host array)
+        r.copy_valid = true;
+    }
+    if (copy) *copy = r.d_copy;
+    return SB_OK;
+}
 
 // per engine beam slot: endpoints as internal particle indices and the copy read back for it (the caller's slots of the latest
 // upload only; the engine's slots an upload cut are not drawn)
@@ -385,9 +404,8 @@ static sb_status sbr_build_tables(sb_engine *e)
     for (const uint2 &v : ends)
         if (v.x != 0xFFFFFFFFu && (v.x >= P || v.y >= P)) SBR_FAIL(e, SB_ERR_STATE, "sb_render: beam endpoint outside the scene");
     SB_TRYR(sbr_grow(e, &r.d_ends, r.cap_ends, B));
-    SB_TRYR(sbr_grow(e, &r.d_copy, r.cap_copy, B));
+    SB_TRYR(sbr_copy_table(e, nullptr));
     SBR_HIP(e, hipMemcpyAsync(r.d_ends, ends.data(), (size_t)std::max<uint32_t>(B, 1) * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
-    if (B) SBR_HIP(e, hipMemcpyAsync(r.d_copy, e->h_copy_of_slot.data(), (size_t)B * 4, hipMemcpyHostToDevice, e->stream));
     SB_TRYR(sbr_grow(e, &r.d_wide_p, r.cap_wide_p, P));
     SB_TRYR(sbr_grow(e, &r.d_wide_b, r.cap_wide_b, B));
     SBR_HIP(e, hipStreamSynchronize(e->stream)); // (the host vectors go out of scope)

@@ -148,6 +148,8 @@ def load_library():
     L.sb_get_stream.argtypes = [vp, ctypes.POINTER(vp)]
     L.sb_render.argtypes = [vp, ctypes.POINTER(SbRenderOptions), vp, sz]
     L.sb_render_device.argtypes = [vp, ctypes.POINTER(SbRenderOptions), vp]
+    L.sb_read_state_device.argtypes = [vp, vp, vp, vp]
+    L.sb_write_particles_device.argtypes = [vp, vp]
     f32 = ctypes.c_float
     L.sb_partition_create.argtypes = [u32, u32, u32, vp, vp, vp, vp, u32, u32, f32, ctypes.POINTER(vp)]
     L.sb_partition_destroy.argtypes = [vp]
@@ -194,6 +196,8 @@ class Engine:
             self._h = None
             raise EngineError(st, L.sb_last_error(None).decode())
         self.layout, self.max_particles, self.max_beams = layout, max_particles, max_beams
+        self.device = device
+        self._ext_stream = None
         self.collision_mode = collision_mode
         self.subticks = (subticks + 1) // 2 * 2
 
@@ -394,3 +398,79 @@ class Engine:
             ptr = dst.data_ptr()
         o = self._render_options(res, bounds_size, particle_radius)
         self._check(load_library().sb_render_device(self._h, ctypes.byref(o), ctypes.c_void_p(ptr)))
+
+    # ---- the state in device memory (sb_read_state_device / sb_write_particles_device)
+
+    def _device_buffer(self, what, x, dtype, nbytes):
+        """A device pointer (int, passed as is) or a contiguous torch tensor on the engine's device with dtype `dtype` and at
+        least `nbytes` bytes: (pointer, is_tensor).  ValueError otherwise."""
+        if isinstance(x, int):
+            return x, False
+        import torch
+        if not isinstance(x, torch.Tensor):
+            raise ValueError("%s: a device pointer (int) or a torch tensor is needed, not %s" % (what, type(x).__name__))
+        dev = torch.device("cuda", self.device)
+        if x.device.type != "cuda" or (x.device.index if x.device.index is not None else torch.cuda.current_device()) != self.device:
+            raise ValueError("%s: the tensor is on %s, the engine on %s" % (what, x.device, dev))
+        if x.dtype != getattr(torch, dtype):
+            raise ValueError("%s: a %s tensor is needed, not %s" % (what, dtype, x.dtype))
+        if not x.is_contiguous():
+            raise ValueError("%s: the tensor must be contiguous" % what)
+        if x.element_size() * x.numel() < nbytes:
+            raise ValueError("%s: a tensor of at least %d bytes is needed, this one has %d" % (what, nbytes, x.element_size() * x.numel()))
+        return x.data_ptr(), True
+
+    def _streams(self):
+        """(torch's current stream, the engine's stream as a torch stream) on the engine's device."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if self._ext_stream is None:
+            self._ext_stream = torch.cuda.ExternalStream(self.stream(), device=dev)
+        return torch.cuda.current_stream(dev), self._ext_stream
+
+    def _ordered(self, tensors, call):
+        """call() enqueues on the engine's stream; with tensors, that work is ordered behind torch's current stream and torch's
+        current stream behind it (no explicit sync needed on either side)."""
+        if not tensors:
+            return self._check(call())
+        cur, eng = self._streams()
+        eng.wait_stream(cur)
+        self._check(call())
+        cur.wait_stream(eng)
+
+    def read_state_device(self, particles=None, beams=None, beam_alive=None):
+        """The state sb_load_buffers would read back now, gathered on the GPU: particle records (6 f32: p.xy, v.xy, a.xy) at each
+        particle's data index into `particles` (float32, max_particles * 24 bytes), {target_length, last_length, strain, stress}
+        at each beam's data index into `beams` (float32, max_beams * 16 bytes), 1 / 0 (live / removed) into `beam_alive` (uint8,
+        max_beams bytes).  Each is None, a device pointer (int) or a contiguous torch tensor on the engine's device; rows of no
+        particle / beam are not written.  Only enqueues; with tensors, torch's current stream is ordered after the export."""
+        args, tensors = [], False
+        for what, x, dtype, n in (("particles", particles, "float32", self.max_particles * PARTICLE_STRIDE),
+                                  ("beams", beams, "float32", self.max_beams * 16),
+                                  ("beam_alive", beam_alive, "uint8", self.max_beams)):
+            if x is None:
+                args.append(None)
+                continue
+            ptr, t = self._device_buffer("read_state_device: " + what, x, dtype, n)
+            args.append(ptr)
+            tensors |= t
+        vp = ctypes.c_void_p
+        self._ordered(tensors, lambda: load_library().sb_read_state_device(self._h, vp(args[0]), vp(args[1]), vp(args[2])))
+
+    def write_particles_device(self, src):
+        """Overwrite p, v, a of every particle from particle records on the GPU (the layout of read_state_device's `particles`):
+        a device pointer (int) or a contiguous float32 torch tensor of at least max_particles * 24 bytes on the engine's device.
+        Only enqueues; with a tensor, the import waits for torch's current stream and torch's current stream for the import."""
+        ptr, t = self._device_buffer("write_particles_device", src, "float32", self.max_particles * PARTICLE_STRIDE)
+        self._ordered(t, lambda: load_library().sb_write_particles_device(self._h, ctypes.c_void_p(ptr)))
+
+    def state_tensors(self):
+        """New torch tensors of the current state: {"particles": (max_particles, 6) float32, "beams": (max_beams, 4) float32,
+        "beam_alive": (max_beams,) uint8}; rows of no particle / beam are NaN (0 in beam_alive)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        out = {"particles": torch.full((self.max_particles, 6), float("nan"), dtype=torch.float32, device=dev),
+               "beams": torch.full((self.max_beams, 4), float("nan"), dtype=torch.float32, device=dev),
+               "beam_alive": torch.zeros(self.max_beams, dtype=torch.uint8, device=dev)}
+        self.read_state_device(out["particles"], out["beams"], out["beam_alive"])
+        return out
