@@ -38,6 +38,8 @@
  *       sb_read_state_device and sb_write_particles_device only enqueue (the first export after an upload builds its tables
  *         and waits for the stream once, as the first render does; with SB_COLLIDE_GRID the import's reset of the spatial
  *         hash copies its start state from host memory, which the runtime may do behind the work in flight).
+ *       The sb_batch_* group (many small scenes, below): everything only enqueues on the batch's own stream except
+ *         sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync, which wait for it.
  *       A wait POLLS the stream for as long as the work in flight should take (busily for
  *         the first 8 ms, then every ~50 us between short sleeps; 0.2 s at most) before it
  *         parks the thread: being woken costs 0.2 - 0.5 ms on some hosts, more than many
@@ -414,6 +416,85 @@ sb_status sb_read_state_device(sb_engine *e, void *device_particles, void *devic
  * planning upload: the hash keeps the frame fitted at that upload (particles outside are clamped into its edge cells), and the
  * tiles stay those bisected from the upload's positions. */
 sb_status sb_write_particles_device(sb_engine *e, const void *device_particles);
+
+/* ---- batched small scenes: N independent scenes, one workgroup per scene, one launch per frame ----
+ * A second object beside sb_engine, for the user who steps thousands of copies of a SMALL scene (a controller, an RL loop):
+ * every scene is a full scene of the reference -- its own particles, beams, mapping, counts, physics constants and user input --
+ * and all of them advance in ONE launch per frame, each in the LDS of its own workgroup.  The arithmetic is sb_engine's
+ * (the same device functions), so every scene's bytes are those of an sb_engine / of the reference's all-pairs loop.
+ * An sb_batch never touches an sb_engine.
+ *   Limits: per scene at most SB_BATCH_MAX_PARTICLES particles and SB_BATCH_MAX_BEAMS beams (what one workgroup holds).
+ *   When do calls return?  sb_batch_frame / _step / _delete_pass / _reset_device / _write_user_input[_device] /
+ *     _set_physics_constants / _read_state_device / _write_particles_device only ENQUEUE on the batch's stream (device buffers
+ *     must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
+ *   Errors: every call returns an sb_status; sb_batch_last_error(b) gives the message (b == NULL: the last failed
+ *     sb_batch_create of the calling thread).  Options are checked BEFORE a device is looked for. */
+#define SB_BATCH_MAX_PARTICLES 1024
+#define SB_BATCH_MAX_BEAMS 4096
+typedef struct sb_batch sb_batch;
+typedef struct sb_batch_options {
+    uint32_t struct_size;    /* = sizeof(sb_batch_options) */
+    uint32_t n_scenes;       /* >= 1 */
+    float bounds_size;       /* as sb_options */
+    float particle_radius;
+    uint32_t subticks;       /* rounded UP to even; time_step = 1/subticks */
+    uint32_t max_particles;  /* capacity PER SCENE, 1 .. SB_BATCH_MAX_PARTICLES */
+    uint32_t max_beams;      /* capacity PER SCENE, 0 .. SB_BATCH_MAX_BEAMS */
+    uint32_t layout;         /* SB_LAYOUT_* of the host buffers of sb_batch_write_scene / sb_batch_load_scene */
+    uint32_t collision_mode; /* SB_COLLIDE_OFF, or on: SB_COLLIDE_ALLPAIRS and SB_COLLIDE_GRID both mean the reference's loop
+                              * over all slots in ascending order (compute.wgsl:144-170) and give the same bits */
+    int32_t device_ordinal;
+    uint32_t reserved[6];
+} sb_batch_options;
+
+/* reference defaults (bounds 1000, radius 10, subticks 64, v1, collisions on, device 0), one scene at the capacity limit */
+void sb_batch_default_options(sb_batch_options *opts);
+sb_status sb_batch_create(const sb_batch_options *opts, sb_batch **out);
+sb_status sb_batch_destroy(sb_batch *b);
+
+/* ONE scene in the four host buffers of sb_write_buffers (full per-scene capacity, the same validation) into scenes
+ * first .. first+count-1; count = n_scenes replicates it over the batch.  The upload also becomes those scenes' RESET state.
+ * Scenes never uploaded hold zero particles and step as no-ops. */
+sb_status sb_batch_write_scene(sb_batch *b, uint32_t first, uint32_t count, const void *metadata, size_t metadata_bytes,
+                               const void *mapping, size_t mapping_bytes, const void *particles, size_t particles_bytes,
+                               const void *beams, size_t beams_bytes);
+/* the 32 bytes at metadata offset 80 of EVERY scene from host memory ... */
+sb_status sb_batch_write_user_input(sb_batch *b, const void *bytes32);
+/* ... or n_scenes x 32 bytes from device memory, scene after scene (per-scene actions straight from a tensor) */
+sb_status sb_batch_write_user_input_device(sb_batch *b, const void *device_bytes);
+/* the 8 floats at metadata offset 48 of scenes first .. first+count-1 */
+sb_status sb_batch_set_physics_constants(sb_batch *b, uint32_t first, uint32_t count, const float constants8[8]);
+
+/* every scene: n_frames x (subticks substeps, then one delete pass), the user input held constant; one launch per frame */
+sb_status sb_batch_frame(sb_batch *b, uint32_t n_frames);
+/* n substeps without a delete pass (any n; one launch), and the delete pass on its own */
+sb_status sb_batch_step(sb_batch *b, uint32_t n_substeps);
+sb_status sb_batch_delete_pass(sb_batch *b);
+
+/* scenes whose byte in device_mask_u8[n_scenes] is nonzero go back to the state of their latest upload (particles, beam state,
+ * beam mapping, counts, pending break flags); user input and physics constants stay.  NULL = all scenes. */
+sb_status sb_batch_reset_device(sb_batch *b, const void *device_mask_u8);
+
+/* the layouts of sb_read_state_device / sb_write_particles_device with a leading scene dimension: particles
+ * [n_scenes][max_particles] x 24 B at each particle's DATA index, beams [n_scenes][max_beams] x 16 B {target_length,
+ * last_length, strain, stress}, beam_alive [n_scenes][max_beams] bytes.  Rows of no particle / beam of a scene's latest upload
+ * are not written (not read).  Any pointer of the export may be NULL.  Pointers must be 4-byte aligned. */
+sb_status sb_batch_read_state_device(sb_batch *b, void *device_particles, void *device_beams, void *device_beam_alive);
+sb_status sb_batch_write_particles_device(sb_batch *b, const void *device_particles);
+
+/* scene i back into host buffers exactly as sb_load_buffers returns a single engine in the same state (counts in the metadata,
+ * the mapping after the delete passes' stable in-place compactions, beam records with strain / stress; only records reachable
+ * through the uploaded mapping are written; any pointer may be NULL).  SB_ERR_STATE for a scene never uploaded. */
+sb_status sb_batch_load_scene(sb_batch *b, uint32_t scene, void *metadata, size_t metadata_bytes, void *mapping, size_t mapping_bytes,
+                              void *particles, size_t particles_bytes, void *beams, size_t beams_bytes);
+
+sb_status sb_batch_sync(sb_batch *b);
+sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream);
+/* key = "n_scenes", "scene_max_particles", "scene_max_beams" (the limits), "max_particles", "max_beams" (this batch's capacity),
+ * "threads_per_scene", "lds_bytes_per_scene", "materials_in_lds", "scenes_per_cu", "frame_kernel_vgprs",
+ * "frame_kernel_scratch_bytes", "frames_done", "substeps_done" */
+sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value);
+const char *sb_batch_last_error(const sb_batch *b);
 
 /* the engine's hipStream_t, so a caller can order its own work (RCCL send/recv) after it. */
 sb_status sb_get_stream(sb_engine *e, void **hip_stream);

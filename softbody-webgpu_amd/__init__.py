@@ -6,6 +6,7 @@ The directory name carries a hyphen (it is the reference's name), so load it wit
   layout.py   host-visible byte layouts (mirror of src/engineMapping.ts)
   scenes.py   synthetic scene generators (generalised main.ts:addRectangle)
   engine.py   ctypes binding of the C ABI in include/softbody.h (libsoftbody_hip.so)
+  batch.py    BatchEngine: the sb_batch_* group (N small scenes, one workgroup each, one launch per frame)
   csrc/       HIP kernels + the C ABI + the N-API addon
   host/       JavaScript/TypeScript host mirror of engine.ts / engineMapping.ts / engineWorker.ts
 """
@@ -14,8 +15,8 @@ from .layout import LAYOUT_V1, LAYOUT_V2, Buffers  # noqa: F401
 
 
 def __getattr__(name):
-    if name in ("engine", "Engine", "EngineError", "halo"):
+    if name in ("engine", "Engine", "EngineError", "halo", "batch", "BatchEngine"):
         import importlib
-        mod = importlib.import_module(".engine" if name != "halo" else ".halo", __name__)
-        return mod if name in ("engine", "halo") else getattr(mod, name)
+        mod = importlib.import_module({"halo": ".halo", "batch": ".batch", "BatchEngine": ".batch"}.get(name, ".engine"), __name__)
+        return mod if name in ("engine", "halo", "batch") else getattr(mod, name)
     raise AttributeError(name)

@@ -1,0 +1,229 @@
+"""ctypes binding of the sb_batch_* group of include/softbody.h: N independent small scenes, one workgroup per scene,
+one launch per frame.  Like engine.py this only marshals buffers; there is no CPU fallback."""
+import ctypes
+
+import numpy as np
+
+from . import engine as _engine
+from .engine import COLLIDE_GRID, EngineError, _ptr
+from .layout import LAYOUT_V1, PARTICLE_STRIDE, Buffers
+
+BATCH_MAX_PARTICLES, BATCH_MAX_BEAMS = 1024, 4096     # SB_BATCH_MAX_* (include/softbody.h)
+
+
+class SbBatchOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_scenes", ctypes.c_uint32), ("bounds_size", ctypes.c_float),
+                ("particle_radius", ctypes.c_float), ("subticks", ctypes.c_uint32), ("max_particles", ctypes.c_uint32),
+                ("max_beams", ctypes.c_uint32), ("layout", ctypes.c_uint32), ("collision_mode", ctypes.c_uint32),
+                ("device_ordinal", ctypes.c_int32), ("reserved", ctypes.c_uint32 * 6)]
+
+
+_bound = None
+
+
+def load_library():
+    """engine.load_library() (which checks that every declared symbol is exported) plus the prototypes of sb_batch_*."""
+    global _bound
+    if _bound is not None:
+        return _bound
+    L = _engine.load_library()
+    vp, sz, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32
+    L.sb_batch_default_options.argtypes = [ctypes.POINTER(SbBatchOptions)]
+    L.sb_batch_default_options.restype = None
+    L.sb_batch_create.argtypes = [ctypes.POINTER(SbBatchOptions), ctypes.POINTER(vp)]
+    L.sb_batch_destroy.argtypes = [vp]
+    L.sb_batch_write_scene.argtypes = [vp, u32, u32, vp, sz, vp, sz, vp, sz, vp, sz]
+    L.sb_batch_write_user_input.argtypes = [vp, vp]
+    L.sb_batch_write_user_input_device.argtypes = [vp, vp]
+    L.sb_batch_set_physics_constants.argtypes = [vp, u32, u32, vp]
+    L.sb_batch_frame.argtypes = [vp, u32]
+    L.sb_batch_step.argtypes = [vp, u32]
+    L.sb_batch_delete_pass.argtypes = [vp]
+    L.sb_batch_reset_device.argtypes = [vp, vp]
+    L.sb_batch_read_state_device.argtypes = [vp, vp, vp, vp]
+    L.sb_batch_write_particles_device.argtypes = [vp, vp]
+    L.sb_batch_load_scene.argtypes = [vp, u32, vp, sz, vp, sz, vp, sz, vp, sz]
+    L.sb_batch_sync.argtypes = [vp]
+    L.sb_batch_get_stream.argtypes = [vp, ctypes.POINTER(vp)]
+    L.sb_batch_get_info.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)]
+    L.sb_batch_last_error.argtypes = [vp]
+    L.sb_batch_last_error.restype = ctypes.c_char_p
+    for name in _engine.declared_symbols():
+        if name.startswith("sb_batch_") and name not in ("sb_batch_default_options", "sb_batch_last_error"):
+            getattr(L, name).restype = ctypes.c_int
+    _bound = L
+    return L
+
+
+class BatchEngine:
+    """N independent scenes of at most BATCH_MAX_PARTICLES particles / BATCH_MAX_BEAMS beams each, stepped together.
+    max_particles / max_beams are the capacity PER SCENE (the sizes of the layout.Buffers that write_scene / load_scene take)."""
+
+    def __init__(self, n_scenes=1, bounds_size=1000.0, particle_radius=10.0, subticks=64, layout=LAYOUT_V1,
+                 max_particles=BATCH_MAX_PARTICLES, max_beams=BATCH_MAX_BEAMS, collision_mode=COLLIDE_GRID, device=0):
+        L = load_library()
+        o = SbBatchOptions()
+        L.sb_batch_default_options(ctypes.byref(o))
+        o.n_scenes, o.bounds_size, o.particle_radius, o.subticks = n_scenes, bounds_size, particle_radius, subticks
+        o.max_particles, o.max_beams, o.layout = max_particles, max_beams, layout
+        o.collision_mode, o.device_ordinal = collision_mode, device
+        self._h = ctypes.c_void_p()
+        st = L.sb_batch_create(ctypes.byref(o), ctypes.byref(self._h))
+        if st != 0:
+            self._h = None
+            raise EngineError(st, L.sb_batch_last_error(None).decode())
+        self.n_scenes, self.layout, self.max_particles, self.max_beams = n_scenes, layout, max_particles, max_beams
+        self.device, self.collision_mode = device, collision_mode
+        self.subticks = (subticks + 1) // 2 * 2
+        self._ext_stream = None
+
+    def _check(self, st):
+        if st != 0:
+            raise EngineError(st, load_library().sb_batch_last_error(self._h).decode())
+
+    def destroy(self):
+        if self._h:
+            load_library().sb_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    # ---- scenes in and out (host buffers)
+    def write_scene(self, buf: Buffers, first=0, count=None):
+        """Upload ONE scene into scenes first .. first+count-1 (count=None: all scenes from `first` on); it also becomes
+        their reset state.  Waits for the stream."""
+        count = self.n_scenes - first if count is None else count
+        self._check(load_library().sb_batch_write_scene(
+            self._h, first, count, _ptr(buf.metadata), buf.metadata.nbytes, _ptr(buf.mapping), buf.mapping.nbytes,
+            _ptr(buf.particles), buf.particles.nbytes, _ptr(buf.beams), buf.beams.nbytes))
+
+    def load_scene(self, i, buf: Buffers):
+        """Scene i into `buf` exactly as Engine.load_buffers returns a single engine in the same state.  Waits."""
+        self._check(load_library().sb_batch_load_scene(
+            self._h, i, _ptr(buf.metadata), buf.metadata.nbytes, _ptr(buf.mapping), buf.mapping.nbytes,
+            _ptr(buf.particles), buf.particles.nbytes, _ptr(buf.beams), buf.beams.nbytes))
+        return buf
+
+    # ---- inputs
+    def write_user_input(self, x):
+        """32 bytes (bytes / bytearray / numpy): every scene gets them; or a contiguous torch tensor of n_scenes x 32 bytes on
+        the batch's device (any dtype, e.g. float32 [n_scenes, 8] with mouse_active's bits in column 1): scene i gets row i."""
+        if isinstance(x, (bytes, bytearray, memoryview, np.ndarray)):
+            raw = bytes(x.tobytes() if isinstance(x, np.ndarray) else x)
+            if len(raw) != 32:
+                raise ValueError("write_user_input: 32 bytes are needed, not %d" % len(raw))
+            b = (ctypes.c_ubyte * 32).from_buffer_copy(raw)
+            return self._check(load_library().sb_batch_write_user_input(self._h, ctypes.cast(b, ctypes.c_void_p)))
+        ptr, t = self._device_buffer("write_user_input", x, None, self.n_scenes * 32)
+        self._ordered(t, lambda: load_library().sb_batch_write_user_input_device(self._h, ctypes.c_void_p(ptr)))
+
+    def set_physics_constants(self, consts8, first=0, count=None):
+        a = np.ascontiguousarray(consts8, dtype="<f4")
+        if a.shape != (8,):
+            raise ValueError("set_physics_constants: 8 floats are needed")
+        count = self.n_scenes - first if count is None else count
+        self._check(load_library().sb_batch_set_physics_constants(self._h, first, count, _ptr(a)))
+
+    # ---- stepping (only enqueues)
+    def frame(self, n=1):
+        self._check(load_library().sb_batch_frame(self._h, n))
+
+    def step(self, n):
+        self._check(load_library().sb_batch_step(self._h, n))
+
+    def delete_pass(self):
+        self._check(load_library().sb_batch_delete_pass(self._h))
+
+    def reset(self, mask=None):
+        """Scenes whose mask entry is nonzero (a uint8 / bool torch tensor of n_scenes entries on the device, or a device
+        pointer) go back to their latest upload; None = all."""
+        if mask is None:
+            return self._check(load_library().sb_batch_reset_device(self._h, None))
+        ptr, t = self._device_buffer("reset", mask, ("uint8", "bool"), self.n_scenes)
+        self._ordered(t, lambda: load_library().sb_batch_reset_device(self._h, ctypes.c_void_p(ptr)))
+
+    def sync(self):
+        self._check(load_library().sb_batch_sync(self._h))
+
+    def info(self, key):
+        v = ctypes.c_uint64()
+        self._check(load_library().sb_batch_get_info(self._h, key.encode(), ctypes.byref(v)))
+        return v.value
+
+    def stream(self):
+        s = ctypes.c_void_p()
+        self._check(load_library().sb_batch_get_stream(self._h, ctypes.byref(s)))
+        return s.value
+
+    # ---- the state in device memory
+    def _device_buffer(self, what, x, dtypes, nbytes):
+        """A device pointer (int, passed as is) or a contiguous torch tensor on the batch's device, of one of `dtypes` (None:
+        any) and at least `nbytes` bytes: (pointer, is_tensor).  ValueError otherwise."""
+        if isinstance(x, int) and not isinstance(x, bool):
+            return x, False
+        import torch
+        if not isinstance(x, torch.Tensor):
+            raise ValueError("%s: a device pointer (int) or a torch tensor is needed, not %s" % (what, type(x).__name__))
+        if x.device.type != "cuda" or (x.device.index if x.device.index is not None else torch.cuda.current_device()) != self.device:
+            raise ValueError("%s: the tensor is on %s, the batch on cuda:%d" % (what, x.device, self.device))
+        if dtypes is not None:
+            dtypes = (dtypes,) if isinstance(dtypes, str) else dtypes
+            if x.dtype not in [getattr(torch, d) for d in dtypes]:
+                raise ValueError("%s: a %s tensor is needed, not %s" % (what, " / ".join(dtypes), x.dtype))
+        if not x.is_contiguous():
+            raise ValueError("%s: the tensor must be contiguous" % what)
+        if x.element_size() * x.numel() < nbytes:
+            raise ValueError("%s: a tensor of at least %d bytes is needed, this one has %d" % (what, nbytes, x.element_size() * x.numel()))
+        return x.data_ptr(), True
+
+    def _ordered(self, tensors, call):
+        """call() enqueues on the batch's stream; with tensors, that work is ordered behind torch's current stream and torch's
+        current stream behind it (as Engine._ordered does for one engine)."""
+        if not tensors:
+            return self._check(call())
+        import torch
+        dev = torch.device("cuda", self.device)
+        if self._ext_stream is None:
+            self._ext_stream = torch.cuda.ExternalStream(self.stream(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        self._ext_stream.wait_stream(cur)
+        self._check(call())
+        cur.wait_stream(self._ext_stream)
+
+    def read_state_device(self, particles=None, beams=None, beam_alive=None):
+        """Engine.read_state_device with a leading scene dimension: particles float32 [n_scenes, max_particles, 6], beams
+        float32 [n_scenes, max_beams, 4] {target_length, last_length, strain, stress}, beam_alive uint8 / bool
+        [n_scenes, max_beams], each at DATA indices; rows of no particle / beam are not written.  Only enqueues."""
+        n, args, tensors = self.n_scenes, [], False
+        for what, x, dtype, nb in (("particles", particles, "float32", n * self.max_particles * PARTICLE_STRIDE),
+                                   ("beams", beams, "float32", n * self.max_beams * 16),
+                                   ("beam_alive", beam_alive, ("uint8", "bool"), n * self.max_beams)):
+            if x is None:
+                args.append(None)
+                continue
+            ptr, t = self._device_buffer("read_state_device: " + what, x, dtype, nb)
+            args.append(ptr)
+            tensors |= t
+        vp = ctypes.c_void_p
+        self._ordered(tensors, lambda: load_library().sb_batch_read_state_device(self._h, vp(args[0]), vp(args[1]), vp(args[2])))
+
+    def write_particles_device(self, src):
+        """Overwrite p, v, a of every particle of every scene from float32 [n_scenes, max_particles, 6] on the device (only
+        rows of a scene's particles are read).  Beams, counts, mappings and pending break flags are untouched."""
+        ptr, t = self._device_buffer("write_particles_device", src, "float32", self.n_scenes * self.max_particles * PARTICLE_STRIDE)
+        self._ordered(t, lambda: load_library().sb_batch_write_particles_device(self._h, ctypes.c_void_p(ptr)))
+
+    def state_tensors(self):
+        """(particles [N, maxP, 6] float32, beams [N, maxB, 4] float32, alive [N, maxB] bool) of the current state as new torch
+        tensors; rows of no particle / beam are NaN (False in alive)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        p = torch.full((self.n_scenes, self.max_particles, 6), float("nan"), dtype=torch.float32, device=dev)
+        b = torch.full((self.n_scenes, self.max_beams, 4), float("nan"), dtype=torch.float32, device=dev)
+        a = torch.zeros((self.n_scenes, self.max_beams), dtype=torch.bool, device=dev)
+        self.read_state_device(p, b, a)
+        return p, b, a

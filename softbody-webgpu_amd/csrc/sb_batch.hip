@@ -1,0 +1,822 @@
+// sb_batch.hip -- N independent SMALL scenes, one workgroup per scene, one launch per frame (gfx950, wave64).
+//
+// sb_engine spreads ONE scene over the chip and pays a launch per substep (or per few): a scene of the reference's own size
+// (119 particles / 299 beams by default, 2 500 at most in its box) uses a fraction of one CU and its frame costs what 64
+// dependent launches cost.  Here a scene lives in the LDS and registers of ONE workgroup for a whole frame:
+//
+//   load    particles in SLOT order (internal index == slot, as on the atomic path), the data index per slot (the tie-break of
+//           compute.wgsl:153 compares DATA indices), beams in beam-slot order, material rows
+//   substep beam phase: every live beam slot from the READ positions through sb_beam_eval, ds_add of the i32 forces, break
+//           flags as bits per beam slot; barrier; particle phase: the reference's loop over slots 0 .. P-1 in ascending order
+//           against the frozen positions / velocities (every lane reads the same LDS word: a broadcast), sb_collide_pair_at,
+//           sb_particle_finish with the consumed and cleared sum, new state into the WRITE half of the ping-pong; barrier
+//   delete  flagged beams leave the slot list by forward stable compaction (sbo_delete / SURVEY A7), counts updated, flags cleared
+//   store   once per launch
+//
+// The arithmetic is sb_physics.h's, called, not restated: the bits are those of k_beams_atomic + k_particles<ALLPAIRS>.
+// Forces are integer sums (order-free), so nothing here depends on how beams are dealt to lanes.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/softbody.h"
+#include "sb_physics.h"
+
+// ---------------------------------------------------------------- device memory of a batch
+// Per scene: 32 metadata words (the 112 bytes of the reference's metadata buffer, then SB_BM_B0 / SB_BM_LOADED), a CONSTANT blob
+// (what only an upload writes) and a STATE blob (what stepping changes), the latter twice: current and reset.  Everything a
+// beam or a particle owns is stored at its DATA index, so the state export / import are plain row copies.
+#define SB_BM_WORDS 32u
+#define SB_BM_P 1u       // metadata.particle_i_c
+#define SB_BM_B 6u       // metadata.beam_i_c (live beam slots)
+#define SB_BM_CONSTS 12u // 8 physics constants, 8 user input words
+#define SB_BM_B0 28u     // beam slots at the latest upload
+#define SB_BM_LOADED 29u // 1 once uploaded
+#define SB_BATCH_MAT_ROW 6u // length, spring, damp, yield, limit, 1/length
+
+struct SbBatchView {
+    uint32_t *meta;     // [n_scenes][SB_BM_WORDS]
+    unsigned char *cst; // [n_scenes][cst_bytes]
+    unsigned char *st;  // [n_scenes][st_bytes]  current
+    unsigned char *rst; // [n_scenes][st_bytes]  reset
+    uint32_t cst_bytes, st_bytes; // multiples of 16
+    // constant blob: slot -> data index of every particle slot (all max_particles entries of the uploaded mapping, verbatim),
+    // per beam DATA index (slot of endpoint A) | (slot of endpoint B) << 16 and the material row, per data index "holds a
+    // particle / beam of the upload"
+    uint32_t o_pmap, o_bword, o_bmat, o_pex, o_bex;
+    // state blob: particle records (6 f32) and beam state {target, last, strain, stress} at their data indices, slot -> data
+    // index of every beam slot (verbatim; the delete pass compacts its head in place), pending break flags (one bit per beam
+    // SLOT), per beam data index "not removed by a delete pass"
+    uint32_t o_part, o_bstate, o_bmap, o_bflags, o_balive;
+    uint32_t maxP, maxB, nflagw, n_scenes;
+};
+
+SB_DEV uint32_t sbb_uniform(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
+SB_DEV float sbb_uniform(float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); }
+
+// ---------------------------------------------------------------- the frame kernel
+// One thread per particle slot (blockDim.x >= max_particles: chosen at create), beams dealt round-robin.
+// COLLIDE: the collision loop is compiled in.  MAT_LDS: the material rows fit the LDS beside the rest (else they are read from
+// the constant blob every substep: L2 hits).
+template <bool COLLIDE, bool MAT_LDS>
+__global__ __launch_bounds__(1024) void k_batch_frame(SbBatchView V, SbParams prm, uint32_t n_sub, uint32_t do_delete)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char sbb_lds[];
+    const uint32_t scene = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+    uint32_t *meta = V.meta + (size_t)scene * SB_BM_WORDS;
+    // (metadata words are rewritten between launches by other kernels: read at agent scope, never through the scalar cache)
+    const uint32_t P = sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_P])), Bc = sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_B]));
+    if (P == 0u || P > V.maxP || Bc > V.maxB) return; // an empty (or never uploaded) scene; counts are validated at upload
+    const uint32_t maxP = V.maxP, maxB = V.maxB;
+
+    // LDS map (sb_batch_lds_bytes mirrors it)
+    float2 *s_pos = (float2 *)sbb_lds;       // [2][maxP] ping-pong
+    float2 *s_vel = s_pos + 2u * maxP;       // [2][maxP]
+    float2 *s_tl = s_vel + 2u * maxP;        // [maxB] {target_length, last_length} per beam slot
+    int *s_f = (int *)(s_tl + maxB);         // [maxP][2] fixed-point force sums (compute.wgsl:68-69)
+    uint32_t *s_pidx = (uint32_t *)(s_f + 2u * maxP); // [maxP] data index per slot
+    uint32_t *s_w = s_pidx + maxP;           // [maxB] endpoint slots
+    uint32_t *s_bd = s_w + maxB;             // [maxB] data index per beam slot
+    uint32_t *s_flags = s_bd + maxB;         // [nflagw] break flags
+    uint32_t *s_off = s_flags + V.nflagw;    // [nflagw + 1] delete pass: live beams in front of each flag word
+    float *s_mat = (float *)(s_off + V.nflagw + 1u); // [maxB][6] (MAT_LDS)
+
+    const unsigned char *cst = V.cst + (size_t)scene * V.cst_bytes;
+    unsigned char *st = V.st + (size_t)scene * V.st_bytes;
+    const uint32_t *g_pmap = (const uint32_t *)(cst + V.o_pmap);
+    const uint32_t *g_bword = (const uint32_t *)(cst + V.o_bword);
+    const float *g_bmat = (const float *)(cst + V.o_bmat);
+    float2 *g_part = (float2 *)(st + V.o_part);
+    float4 *g_bstate = (float4 *)(st + V.o_bstate);
+    uint32_t *g_bmap = (uint32_t *)(st + V.o_bmap);
+    uint32_t *g_bflags = (uint32_t *)(st + V.o_bflags);
+    unsigned char *g_balive = st + V.o_balive;
+
+    // the scene's constants: uniform, kept in scalar registers
+    SbConsts c;
+    {
+        uint32_t w[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) w[k] = sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_CONSTS + k]));
+        memcpy(&c, w, sizeof c);
+    }
+    const bool plain = c.drag_exp == 2.0f && c.mouse_active == 0u; // sb_particle_finish<PLAIN>: same bits, fewer branches
+
+    // ---- load
+    const bool active = tid < P;
+    SbParticle q;
+    q.p = q.v = q.a = make_float2(0.f, 0.f);
+    uint32_t my_idx = 0u;
+    if (active) {
+        my_idx = g_pmap[tid];
+        q.p = g_part[3u * my_idx];
+        q.v = g_part[3u * my_idx + 1u];
+        q.a = g_part[3u * my_idx + 2u];
+        s_pos[tid] = q.p;
+        s_vel[tid] = q.v;
+        s_f[2u * tid] = 0;
+        s_f[2u * tid + 1u] = 0;
+        s_pidx[tid] = my_idx;
+    }
+    for (uint32_t j = tid; j < Bc; j += T) {
+        const uint32_t d = g_bmap[j];
+        const float4 bs = g_bstate[d];
+        s_bd[j] = d;
+        s_w[j] = g_bword[d];
+        s_tl[j] = make_float2(bs.x, bs.y);
+        if (MAT_LDS) {
+#pragma unroll
+            for (uint32_t k = 0; k < SB_BATCH_MAT_ROW; k++) s_mat[SB_BATCH_MAT_ROW * j + k] = g_bmat[SB_BATCH_MAT_ROW * d + k];
+        }
+    }
+    for (uint32_t w = tid; w < V.nflagw; w += T) s_flags[w] = g_bflags[w];
+    __syncthreads();
+
+    const float elasticity_coeff = sb_div(c.elasticity + 1.0f, 2.0f); // :143
+    // Contact test of k_particles<SB_COLLIDE_ALLPAIRS>: dist = sqrt(d2) (IEEE), contact when dist == 0 or dist < 2r.  The root is
+    // only taken where d2 <= thr = (2r)^2 * 1.001: beyond it sqrt(d2) > 2r * 1.0004, which no rounding brings back under 2r
+    // (and d2 > 0).  A threshold that is not an ordinary number (tiny, huge or NaN radius) turns the shortcut off; a NaN d2
+    // fails `d2 > thr` and takes the exact test.
+    const float two_r = prm.particle_radius * 2.0f;
+    const float thr0 = two_r * two_r * 1.001f;
+    const float thr = (thr0 >= 0x1p-100f && thr0 <= 0x1p100f) ? thr0 : __uint_as_float(0x7f800000u);
+
+    // ---- substeps
+    uint32_t cur = 0u;
+    for (uint32_t k = 0; k < n_sub; k++) {
+        const bool aux = k + 1u == n_sub; // strain / stress are outputs only (:122-123): stored by the last substep of a launch
+        const float2 *rp = s_pos + cur * maxP, *rv = s_vel + cur * maxP;
+        float2 *wp = s_pos + (cur ^ 1u) * maxP, *wv = s_vel + (cur ^ 1u) * maxP;
+        // beam phase (compute.wgsl:96-131)
+        for (uint32_t j = tid; j < Bc; j += T) {
+            const uint32_t word = s_w[j], ia = word & 0xffffu, ib = word >> 16;
+            const float2 tl = s_tl[j];
+            const float *m = MAT_LDS ? &s_mat[SB_BATCH_MAT_ROW * j] : &g_bmat[SB_BATCH_MAT_ROW * s_bd[j]];
+            const float length = m[0], spring = m[1], damp = m[2], yield = m[3], limit = m[4], inv_length = m[5];
+            SbBeamResult r;
+            if (aux) {
+                r = sb_beam_eval<true>(rp[ia], rp[ib], length, inv_length, tl.x, tl.y, spring, damp, yield, limit);
+                g_bstate[s_bd[j]] = make_float4(r.target_length, r.last_length, r.strain, r.stress);
+            } else {
+                r = sb_beam_eval<false>(rp[ia], rp[ib], length, inv_length, tl.x, tl.y, spring, damp, yield, limit);
+            }
+            s_tl[j] = make_float2(r.target_length, r.last_length);
+            atomicAdd(&s_f[2u * ia], r.ax);
+            atomicAdd(&s_f[2u * ia + 1u], r.ay);
+            atomicAdd(&s_f[2u * ib], r.bx);
+            atomicAdd(&s_f[2u * ib + 1u], r.by);
+            if (r.broken) atomicOr(&s_flags[j >> 5], 1u << (j & 31u)); // mark_beam_deleted, :86-88,117
+        }
+        __syncthreads();
+        // particle phase (compute.wgsl:134-202)
+        if (active) {
+            SbParticle particle = q;
+            const SbParticle self = q; // :141
+            if (COLLIDE) {
+                for (uint32_t o = 0; o < P; o++) { // :144-170, ascending slot order
+                    const float2 op = rp[o];
+                    const float dx = op.x - self.p.x, dy = op.y - self.p.y;
+                    const float d2 = dx * dx + dy * dy;
+                    if (d2 > thr) continue;
+                    const float dist = sb_sqrt(d2); // sb_length(dx, dy)
+                    if (o != tid && (dist == 0.0f || dist < two_r))
+                        sb_collide_pair_at(prm, c.friction, elasticity_coeff, particle, self, my_idx, s_pidx[o], dx, dy, dist, rv[o]);
+                }
+            }
+            const int fx = s_f[2u * tid], fy = s_f[2u * tid + 1u];
+            s_f[2u * tid] = 0; // atomicExchange(..., 0), :184-185
+            s_f[2u * tid + 1u] = 0;
+            if (plain) sb_particle_finish<true>(prm, c, particle, fx, fy);
+            else sb_particle_finish<false>(prm, c, particle, fx, fy);
+            q = particle;
+            wp[tid] = q.p;
+            wv[tid] = q.v;
+        }
+        __syncthreads();
+        cur ^= 1u;
+    }
+
+    // ---- store (beam state went out with the last substep)
+    if (n_sub != 0u && active) {
+        g_part[3u * my_idx] = q.p;
+        g_part[3u * my_idx + 1u] = q.v;
+        g_part[3u * my_idx + 2u] = q.a;
+    }
+    if (!do_delete) {
+        if (n_sub != 0u)
+            for (uint32_t w = tid; w < V.nflagw; w += T) g_bflags[w] = s_flags[w];
+        return;
+    }
+    // ---- delete pass (compute.wgsl:205-246, canonical semantics: in-place forward stable compaction of the beam slots;
+    // slots past the new count keep their stale entries, as the oracle's do)
+    const uint32_t nw = (Bc + 31u) >> 5;
+    if (tid == 0u) {
+        uint32_t run = 0u;
+        for (uint32_t w = 0; w < nw; w++) {
+            const uint32_t valid = (w == nw - 1u && (Bc & 31u) != 0u) ? (1u << (Bc & 31u)) - 1u : 0xFFFFFFFFu;
+            s_off[w] = run;
+            run += __popc(~s_flags[w] & valid);
+        }
+        s_off[nw] = run;
+    }
+    __syncthreads();
+    const uint32_t newc = s_off[nw];
+    if (newc != Bc) {
+        for (uint32_t j = tid; j < Bc; j += T) {
+            const uint32_t w = j >> 5, bit = 1u << (j & 31u), fl = s_flags[w], d = s_bd[j];
+            if (fl & bit) {
+                g_balive[d] = 0;
+            } else {
+                const uint32_t np = s_off[w] + __popc(~fl & (bit - 1u));
+                if (np != j) g_bmap[np] = d;
+            }
+        }
+        if (tid == 0u) meta[SB_BM_B] = newc; // :238
+    }
+    for (uint32_t w = tid; w < V.nflagw; w += T) g_bflags[w] = 0u; // :241-244
+}
+
+// ---------------------------------------------------------------- helper kernels: plain copies
+#define SBB_BLOCK 256
+
+// one uploaded scene (staged in device memory) into scenes first .. first + count - 1: constant blob, state blob, reset blob, metadata
+__global__ __launch_bounds__(SBB_BLOCK) void k_batch_replicate(SbBatchView V, const uint4 *__restrict__ stage_cst, const uint4 *__restrict__ stage_st,
+                                                                const uint32_t *__restrict__ stage_meta, uint32_t first, uint32_t count)
+{
+    const uint32_t scene = first + blockIdx.x;
+    if (blockIdx.x >= count || scene >= V.n_scenes) return;
+    uint4 *c = (uint4 *)(V.cst + (size_t)scene * V.cst_bytes), *s = (uint4 *)(V.st + (size_t)scene * V.st_bytes);
+    uint4 *r = (uint4 *)(V.rst + (size_t)scene * V.st_bytes);
+    for (uint32_t i = threadIdx.x; i < V.cst_bytes / 16u; i += SBB_BLOCK) c[i] = stage_cst[i];
+    for (uint32_t i = threadIdx.x; i < V.st_bytes / 16u; i += SBB_BLOCK) {
+        const uint4 v = stage_st[i];
+        s[i] = v;
+        r[i] = v;
+    }
+    if (threadIdx.x < SB_BM_WORDS) V.meta[(size_t)scene * SB_BM_WORDS + threadIdx.x] = stage_meta[threadIdx.x];
+}
+
+__global__ __launch_bounds__(SBB_BLOCK) void k_batch_reset(SbBatchView V, const unsigned char *__restrict__ mask)
+{
+    const uint32_t scene = blockIdx.x;
+    if (scene >= V.n_scenes) return;
+    if (mask && mask[scene] == 0) return;
+    uint32_t *meta = V.meta + (size_t)scene * SB_BM_WORDS;
+    if (meta[SB_BM_LOADED] == 0u) return;
+    uint4 *s = (uint4 *)(V.st + (size_t)scene * V.st_bytes);
+    const uint4 *r = (const uint4 *)(V.rst + (size_t)scene * V.st_bytes);
+    for (uint32_t i = threadIdx.x; i < V.st_bytes / 16u; i += SBB_BLOCK) s[i] = r[i];
+    if (threadIdx.x == 0u) meta[SB_BM_B] = meta[SB_BM_B0];
+}
+
+struct SbBatchWords8 {
+    uint32_t w[8];
+};
+// words [word0, word0 + 8) of the metadata of scenes first .. first + count - 1: from `src` (per scene, 8 words each) or `same`
+__global__ __launch_bounds__(SBB_BLOCK) void k_batch_meta8(SbBatchView V, uint32_t first, uint32_t count, uint32_t word0,
+                                                            const uint32_t *__restrict__ src, SbBatchWords8 same)
+{
+    const uint32_t t = blockIdx.x * SBB_BLOCK + threadIdx.x, s = t >> 3, k = t & 7u;
+    if (s >= count || first + s >= V.n_scenes) return;
+    V.meta[(size_t)(first + s) * SB_BM_WORDS + word0 + k] = src ? src[(size_t)(first + s) * 8u + k] : same.w[k];
+}
+
+__global__ __launch_bounds__(SBB_BLOCK) void k_batch_export(SbBatchView V, float *particles, float *beams, unsigned char *alive)
+{
+    const uint32_t scene = blockIdx.x;
+    if (scene >= V.n_scenes) return;
+    const unsigned char *cst = V.cst + (size_t)scene * V.cst_bytes, *st = V.st + (size_t)scene * V.st_bytes;
+    const unsigned char *pex = cst + V.o_pex, *bex = cst + V.o_bex, *bal = st + V.o_balive;
+    const float *part = (const float *)(st + V.o_part), *bstate = (const float *)(st + V.o_bstate);
+    if (particles)
+        for (uint32_t i = threadIdx.x; i < V.maxP * 6u; i += SBB_BLOCK)
+            if (pex[i / 6u]) particles[(size_t)scene * V.maxP * 6u + i] = part[i];
+    if (beams)
+        for (uint32_t i = threadIdx.x; i < V.maxB * 4u; i += SBB_BLOCK)
+            if (bex[i >> 2]) beams[(size_t)scene * V.maxB * 4u + i] = bstate[i];
+    if (alive)
+        for (uint32_t i = threadIdx.x; i < V.maxB; i += SBB_BLOCK)
+            if (bex[i]) alive[(size_t)scene * V.maxB + i] = bal[i];
+}
+
+__global__ __launch_bounds__(SBB_BLOCK) void k_batch_import(SbBatchView V, const float *__restrict__ particles)
+{
+    const uint32_t scene = blockIdx.x;
+    if (scene >= V.n_scenes) return;
+    const unsigned char *pex = V.cst + (size_t)scene * V.cst_bytes + V.o_pex;
+    float *part = (float *)(V.st + (size_t)scene * V.st_bytes + V.o_part);
+    for (uint32_t i = threadIdx.x; i < V.maxP * 6u; i += SBB_BLOCK)
+        if (pex[i / 6u]) part[i] = particles[(size_t)scene * V.maxP * 6u + i];
+}
+
+// ---------------------------------------------------------------- host
+struct sb_batch {
+    sb_batch_options opt{};
+    std::string err;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    SbBatchView V{};
+    SbParams prm{};
+    uint32_t subticks = 0, threads = 0, lds_bytes = 0;
+    bool mat_lds = false, collide = false;
+    unsigned char *stage = nullptr; // device staging of one upload: meta words, constant blob, state blob
+    uint64_t frames_done = 0, substeps_done = 0;
+    int scenes_per_cu = 0, vgprs = 0, scratch = 0;
+};
+
+static thread_local std::string g_batch_create_error;
+
+#define SBB_FAIL(b, code, ...)                                         \
+    do {                                                               \
+        char _buf[512];                                                \
+        snprintf(_buf, sizeof _buf, __VA_ARGS__);                      \
+        if (b) (b)->err = _buf; else g_batch_create_error = _buf;      \
+        return (code);                                                 \
+    } while (0)
+#define SBB_HIP(b, call)                                                                                   \
+    do {                                                                                                   \
+        hipError_t _r = (call);                                                                            \
+        if (_r != hipSuccess) {                                                                            \
+            (void)hipGetLastError();                                                                       \
+            SBB_FAIL(b, _r == hipErrorOutOfMemory ? SB_ERR_OOM : SB_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(_r)); \
+        }                                                                                                  \
+    } while (0)
+
+static inline uint32_t up16(uint32_t x) { return (x + 15u) & ~15u; }
+static inline uint32_t cdivb(uint32_t a, uint32_t b) { return (a + b - 1u) / b; }
+
+// threads of a scene's workgroup: one per particle slot of the capacity, and enough that a lane evaluates at most four beams
+// per substep; whole waves, 64 .. 1024
+static uint32_t sb_batch_threads(uint32_t maxP, uint32_t maxB)
+{
+    const uint32_t t = std::max((maxP + 63u) / 64u * 64u, (cdivb(maxB, 4u) + 63u) / 64u * 64u);
+    return std::min(std::max(t, 64u), 1024u);
+}
+// the LDS map of k_batch_frame
+static uint32_t sb_batch_lds_bytes(uint32_t maxP, uint32_t maxB, bool mats)
+{
+    const uint32_t nflagw = cdivb(std::max(maxB, 1u), 32u);
+    return up16(maxP * (16u + 16u + 8u + 4u) + maxB * (8u + 4u + 4u) + (2u * nflagw + 1u) * 4u + (mats ? maxB * SB_BATCH_MAT_ROW * 4u : 0u));
+}
+#define SB_BATCH_LDS_LIMIT (160u * 1024u) // one CU of gfx950
+
+const char *sb_batch_last_error(const sb_batch *b) { return b ? b->err.c_str() : g_batch_create_error.c_str(); }
+
+void sb_batch_default_options(sb_batch_options *o)
+{
+    memset(o, 0, sizeof *o);
+    o->struct_size = sizeof *o;
+    o->n_scenes = 1;
+    o->bounds_size = 1000.0f;   // engineWorker.ts:39
+    o->particle_radius = 10.0f; // engineWorker.ts:40
+    o->subticks = 64;           // engineWorker.ts:41
+    o->max_particles = SB_BATCH_MAX_PARTICLES;
+    o->max_beams = SB_BATCH_MAX_BEAMS;
+    o->layout = SB_LAYOUT_V1;
+    o->collision_mode = SB_COLLIDE_GRID;
+    o->device_ordinal = 0;
+}
+
+typedef void (*sb_batch_kernel)(SbBatchView, SbParams, uint32_t, uint32_t);
+static sb_batch_kernel sb_batch_frame_kernel(const sb_batch *b)
+{
+    if (b->collide) return b->mat_lds ? k_batch_frame<true, true> : k_batch_frame<true, false>;
+    return b->mat_lds ? k_batch_frame<false, true> : k_batch_frame<false, false>;
+}
+
+sb_status sb_batch_destroy(sb_batch *b)
+{
+    if (!b) return SB_ERR_INVALID;
+    (void)hipSetDevice(b->device);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    if (b->V.meta) (void)hipFree(b->V.meta);
+    if (b->V.cst) (void)hipFree(b->V.cst);
+    if (b->V.st) (void)hipFree(b->V.st);
+    if (b->V.rst) (void)hipFree(b->V.rst);
+    if (b->stage) (void)hipFree(b->stage);
+    if (b->stream) (void)hipStreamDestroy(b->stream);
+    delete b;
+    return SB_OK;
+}
+
+sb_status sb_batch_create(const sb_batch_options *opts, sb_batch **out)
+{
+    sb_batch *none = nullptr;
+    if (!opts || !out) SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: null argument");
+    *out = nullptr;
+    if (opts->struct_size != sizeof(sb_batch_options))
+        SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: sb_batch_options.struct_size %u != %zu", opts->struct_size, sizeof(sb_batch_options));
+    if (opts->n_scenes == 0) SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: n_scenes is 0");
+    if (opts->layout != SB_LAYOUT_V1 && opts->layout != SB_LAYOUT_V2) SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: unknown layout %u", opts->layout);
+    if (opts->layout == SB_LAYOUT_V1 && (opts->max_particles > 65536 || opts->max_beams > 65536))
+        SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: v1 layout holds at most 65536 particles/beams (u16 indices)");
+    if (opts->max_particles == 0) SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: max_particles is 0");
+    if (opts->max_particles > SB_BATCH_MAX_PARTICLES)
+        SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: max_particles %u per scene is above the limit of %u (what one workgroup holds)",
+                 opts->max_particles, (unsigned)SB_BATCH_MAX_PARTICLES);
+    if (opts->max_beams > SB_BATCH_MAX_BEAMS)
+        SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: max_beams %u per scene is above the limit of %u (what one workgroup holds)",
+                 opts->max_beams, (unsigned)SB_BATCH_MAX_BEAMS);
+    if (opts->collision_mode > SB_COLLIDE_GRID) SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: unknown collision_mode %u", opts->collision_mode);
+    if (!(opts->particle_radius > 0.f) || !(opts->bounds_size > 0.f) || opts->subticks == 0)
+        SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: radius, bounds and subticks must be positive");
+    int ndev = 0;
+    hipError_t r = hipGetDeviceCount(&ndev);
+    if (r != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        SBB_FAIL(none, SB_ERR_NO_DEVICE, "no HIP device available (%s); a batch has no CPU fallback",
+                 r == hipSuccess ? "device count 0" : hipGetErrorString(r));
+    }
+    if (opts->device_ordinal < 0 || opts->device_ordinal >= ndev)
+        SBB_FAIL(none, SB_ERR_NO_DEVICE, "device_ordinal %d out of range (%d devices)", opts->device_ordinal, ndev);
+
+    sb_batch *b = new sb_batch();
+    b->opt = *opts;
+    b->device = opts->device_ordinal;
+    b->subticks = (opts->subticks + 1) / 2 * 2; // engineWorker.ts:90
+    b->prm.bounds_size = opts->bounds_size;
+    b->prm.particle_radius = opts->particle_radius;
+    b->prm.time_step = 1.0f / (float)b->subticks; // engineWorker.ts:331
+    {
+        // time_step^2 a power of two (any power-of-two subticks): x / dt^2 is the exact multiplication by its reciprocal,
+        // resolved here once (SbParams::inv_dt2, as sb_create does)
+        const float dt2 = b->prm.time_step * b->prm.time_step;
+        uint32_t bits;
+        memcpy(&bits, &dt2, 4);
+        const bool pow2 = (bits & 0x007fffffu) == 0u && (bits >> 23) > 1u && (bits >> 23) < 253u;
+        b->prm.inv_dt2 = pow2 ? 1.0f / dt2 : 0.0f;
+    }
+    b->collide = opts->collision_mode != SB_COLLIDE_OFF;
+    const uint32_t maxP = opts->max_particles, maxB = opts->max_beams, n = opts->n_scenes;
+    b->threads = sb_batch_threads(maxP, maxB);
+    b->mat_lds = sb_batch_lds_bytes(maxP, maxB, true) <= SB_BATCH_LDS_LIMIT;
+    b->lds_bytes = sb_batch_lds_bytes(maxP, maxB, b->mat_lds);
+
+    SbBatchView &V = b->V;
+    V.maxP = maxP;
+    V.maxB = maxB;
+    V.n_scenes = n;
+    V.nflagw = cdivb(std::max(maxB, 1u), 32u);
+    uint32_t o = 0;
+    V.o_pmap = o, o += up16(maxP * 4u);
+    V.o_bword = o, o += up16(maxB * 4u);
+    V.o_bmat = o, o += up16(maxB * SB_BATCH_MAT_ROW * 4u);
+    V.o_pex = o, o += up16(maxP);
+    V.o_bex = o, o += up16(maxB);
+    V.cst_bytes = std::max(o, 16u);
+    o = 0;
+    V.o_part = o, o += up16(maxP * 24u);
+    V.o_bstate = o, o += up16(maxB * 16u);
+    V.o_bmap = o, o += up16(maxB * 4u);
+    V.o_bflags = o, o += up16(V.nflagw * 4u);
+    V.o_balive = o, o += up16(maxB);
+    V.st_bytes = std::max(o, 16u);
+
+#define SBB_CREATE_HIP(call)                                                                              \
+    do {                                                                                                  \
+        hipError_t _r = (call);                                                                           \
+        if (_r != hipSuccess) {                                                                           \
+            (void)hipGetLastError();                                                                      \
+            g_batch_create_error = std::string(#call " failed: ") + hipGetErrorString(_r);                \
+            (void)sb_batch_destroy(b);                                                                    \
+            return _r == hipErrorOutOfMemory ? SB_ERR_OOM : SB_ERR_HIP;                                   \
+        }                                                                                                 \
+    } while (0)
+    SBB_CREATE_HIP(hipSetDevice(b->device));
+    SBB_CREATE_HIP(hipStreamCreate(&b->stream));
+    SBB_CREATE_HIP(hipMalloc((void **)&V.meta, (size_t)n * SB_BM_WORDS * 4u));
+    SBB_CREATE_HIP(hipMalloc((void **)&V.cst, (size_t)n * V.cst_bytes));
+    SBB_CREATE_HIP(hipMalloc((void **)&V.st, (size_t)n * V.st_bytes));
+    SBB_CREATE_HIP(hipMalloc((void **)&V.rst, (size_t)n * V.st_bytes));
+    SBB_CREATE_HIP(hipMalloc((void **)&b->stage, (size_t)SB_BM_WORDS * 4u + V.cst_bytes + V.st_bytes));
+    SBB_CREATE_HIP(hipMemsetAsync(V.meta, 0, (size_t)n * SB_BM_WORDS * 4u, b->stream));
+    SBB_CREATE_HIP(hipMemsetAsync(V.cst, 0, (size_t)n * V.cst_bytes, b->stream));
+    SBB_CREATE_HIP(hipMemsetAsync(V.st, 0, (size_t)n * V.st_bytes, b->stream));
+    SBB_CREATE_HIP(hipMemsetAsync(V.rst, 0, (size_t)n * V.st_bytes, b->stream));
+    const void *fn = (const void *)sb_batch_frame_kernel(b);
+    SBB_CREATE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes));
+    hipFuncAttributes fa{};
+    SBB_CREATE_HIP(hipFuncGetAttributes(&fa, fn));
+    b->vgprs = fa.numRegs;
+    b->scratch = (int)fa.localSizeBytes;
+    SBB_CREATE_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b->scenes_per_cu, fn, (int)b->threads, b->lds_bytes));
+    SBB_CREATE_HIP(hipStreamSynchronize(b->stream));
+#undef SBB_CREATE_HIP
+    *out = b;
+    return SB_OK;
+}
+
+static inline uint32_t rd32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
+static inline uint32_t map_isz(const sb_batch *b) { return b->opt.layout == SB_LAYOUT_V1 ? 2u : 4u; }
+static inline uint32_t bstride(const sb_batch *b) { return b->opt.layout == SB_LAYOUT_V1 ? SB_BEAM_STRIDE_V1 : SB_BEAM_STRIDE_V2; }
+static inline uint32_t map_get(const sb_batch *b, const uint8_t *m, size_t id)
+{
+    if (b->opt.layout == SB_LAYOUT_V1) {
+        uint16_t v;
+        memcpy(&v, m + 2 * id, 2);
+        return v;
+    }
+    return rd32(m + 4 * id);
+}
+static inline void map_set(const sb_batch *b, uint8_t *m, size_t id, uint32_t val)
+{
+    if (b->opt.layout == SB_LAYOUT_V1) {
+        const uint16_t v = (uint16_t)val;
+        memcpy(m + 2 * id, &v, 2);
+    } else {
+        memcpy(m + 4 * id, &val, 4);
+    }
+}
+
+static sb_status check_sizes(sb_batch *b, const char *who, bool need_all, const void *metadata, size_t metadata_bytes, const void *mapping,
+                             size_t mapping_bytes, const void *particles, size_t particles_bytes, const void *beams, size_t beams_bytes)
+{
+    const uint32_t maxP = b->opt.max_particles, maxB = b->opt.max_beams;
+    if (need_all && (!metadata || !mapping || !particles || (!beams && maxB))) SBB_FAIL(b, SB_ERR_INVALID, "%s: null buffer", who);
+    if (metadata && metadata_bytes < SB_METADATA_BYTES) SBB_FAIL(b, SB_ERR_INVALID, "%s: metadata buffer is %zu bytes, need 112", who, metadata_bytes);
+    if (mapping && mapping_bytes < (size_t)(maxP + (size_t)maxB) * map_isz(b))
+        SBB_FAIL(b, SB_ERR_INVALID, "%s: mapping buffer is %zu bytes, need %zu", who, mapping_bytes, (size_t)(maxP + (size_t)maxB) * map_isz(b));
+    if (particles && particles_bytes < (size_t)maxP * SB_PARTICLE_STRIDE)
+        SBB_FAIL(b, SB_ERR_INVALID, "%s: particle buffer is %zu bytes, need %zu", who, particles_bytes, (size_t)maxP * SB_PARTICLE_STRIDE);
+    if (beams && beams_bytes < (size_t)maxB * bstride(b))
+        SBB_FAIL(b, SB_ERR_INVALID, "%s: beam buffer is %zu bytes, need %zu", who, beams_bytes, (size_t)maxB * bstride(b));
+    return SB_OK;
+}
+
+static sb_status check_launch(sb_batch *b, const char *what)
+{
+    const hipError_t r = hipGetLastError();
+    if (r != hipSuccess) SBB_FAIL(b, SB_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(r));
+    return SB_OK;
+}
+
+sb_status sb_batch_write_scene(sb_batch *b, uint32_t first, uint32_t count, const void *metadata, size_t metadata_bytes, const void *mapping,
+                               size_t mapping_bytes, const void *particles, size_t particles_bytes, const void *beams, size_t beams_bytes)
+{
+    if (!b) return SB_ERR_INVALID;
+    const uint32_t maxP = b->opt.max_particles, maxB = b->opt.max_beams;
+    if (count == 0 || first >= b->opt.n_scenes || count > b->opt.n_scenes - first)
+        SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_write_scene: scenes %u .. %u+%u are not all inside the batch of %u", first, first, count, b->opt.n_scenes);
+    const sb_status cs = check_sizes(b, "sb_batch_write_scene", true, metadata, metadata_bytes, mapping, mapping_bytes, particles, particles_bytes,
+                                     beams, beams_bytes);
+    if (cs != SB_OK) return cs;
+    const uint8_t *md = (const uint8_t *)metadata, *mp = (const uint8_t *)mapping, *pd = (const uint8_t *)particles, *bd = (const uint8_t *)beams;
+    const uint32_t P = rd32(md + 4), B = rd32(md + 24);
+    if (rd32(md + 40) != maxP || rd32(md + 44) != maxB)
+        SBB_FAIL(b, SB_ERR_INVALID, "metadata max_particles/max_beams (%u/%u) differ from the batch's capacity per scene (%u/%u)", rd32(md + 40),
+                 rd32(md + 44), maxP, maxB);
+    if (P > maxP || B > maxB) SBB_FAIL(b, SB_ERR_INVALID, "metadata counts (%u/%u) exceed capacity (%u/%u)", P, B, maxP, maxB);
+
+    const SbBatchView &V = b->V;
+    std::vector<unsigned char> img((size_t)SB_BM_WORDS * 4u + V.cst_bytes + V.st_bytes, 0);
+    uint32_t *meta = (uint32_t *)img.data();
+    unsigned char *cst = img.data() + SB_BM_WORDS * 4u, *st = cst + V.cst_bytes;
+    uint32_t *pmap = (uint32_t *)(cst + V.o_pmap), *bword = (uint32_t *)(cst + V.o_bword), *bmap = (uint32_t *)(st + V.o_bmap);
+    float *bmat = (float *)(cst + V.o_bmat), *bstate = (float *)(st + V.o_bstate);
+    unsigned char *pex = cst + V.o_pex, *bex = cst + V.o_bex, *balive = st + V.o_balive;
+    memcpy(meta, md, SB_METADATA_BYTES);
+    meta[SB_BM_B0] = B;
+    meta[SB_BM_LOADED] = 1u;
+    for (uint32_t s = 0; s < maxP; s++) pmap[s] = map_get(b, mp, s);
+    for (uint32_t s = 0; s < maxB; s++) bmap[s] = map_get(b, mp, (size_t)maxP + s);
+    memcpy(st + V.o_part, pd, (size_t)maxP * SB_PARTICLE_STRIDE);
+    // particles: slot -> data index must be a partial injection
+    std::vector<uint32_t> slot_of(maxP, 0xFFFFFFFFu);
+    for (uint32_t s = 0; s < P; s++) {
+        const uint32_t idx = pmap[s];
+        if (idx >= maxP) SBB_FAIL(b, SB_ERR_INVALID, "particle slot %u maps to data index %u >= max_particles", s, idx);
+        if (slot_of[idx] != 0xFFFFFFFFu) SBB_FAIL(b, SB_ERR_INVALID, "particle data index %u is mapped by two slots (%u and %u)", idx, slot_of[idx], s);
+        slot_of[idx] = s;
+        pex[idx] = 1;
+    }
+    // beams: slot -> record; endpoints must be active particles
+    const size_t foff = b->opt.layout == SB_LAYOUT_V1 ? 4 : 8;
+    for (uint32_t s = 0; s < B; s++) {
+        const uint32_t idx = bmap[s];
+        if (idx >= maxB) SBB_FAIL(b, SB_ERR_INVALID, "beam slot %u maps to data index %u >= max_beams", s, idx);
+        if (bex[idx]) SBB_FAIL(b, SB_ERR_INVALID, "beam data index %u is mapped by two slots", idx);
+        const uint8_t *rec = bd + (size_t)idx * bstride(b);
+        uint32_t a, e;
+        if (b->opt.layout == SB_LAYOUT_V1) { // engineMapping.ts:183-186, compute.wgsl:99-100
+            const uint32_t pair = rd32(rec);
+            a = pair & 0xffffu;
+            e = pair >> 16;
+        } else {
+            a = rd32(rec);
+            e = rd32(rec + 4);
+        }
+        if (a >= maxP || e >= maxP || slot_of[a] == 0xFFFFFFFFu || slot_of[e] == 0xFFFFFFFFu)
+            SBB_FAIL(b, SB_ERR_INVALID, "beam slot %u (data index %u) references particle data index %u/%u that no particle slot maps to", s, idx, a, e);
+        float f[9]; // length, target_length, last_length, spring, damp, yield_strain, strain_break_limit, strain, stress
+        memcpy(f, rec + foff, sizeof f);
+        bex[idx] = balive[idx] = 1;
+        bword[idx] = slot_of[a] | (slot_of[e] << 16);
+        float *m = bmat + (size_t)SB_BATCH_MAT_ROW * idx, *q = bstate + 4u * (size_t)idx;
+        m[0] = f[0], m[1] = f[3], m[2] = f[4], m[3] = f[5], m[4] = f[6];
+        m[5] = 1.0f / f[0]; // one IEEE divide per beam at upload (compute.wgsl:112 pinned as x * (1 / length))
+        q[0] = f[1], q[1] = f[2], q[2] = f[7], q[3] = f[8];
+    }
+    SBB_HIP(b, hipSetDevice(b->device));
+    SBB_HIP(b, hipMemcpyAsync(b->stage, img.data(), img.size(), hipMemcpyHostToDevice, b->stream));
+    k_batch_replicate<<<count, SBB_BLOCK, 0, b->stream>>>(V, (const uint4 *)(b->stage + SB_BM_WORDS * 4u),
+                                                          (const uint4 *)(b->stage + SB_BM_WORDS * 4u + V.cst_bytes), (const uint32_t *)b->stage, first,
+                                                          count);
+    const sb_status ls = check_launch(b, "sb_batch_write_scene");
+    SBB_HIP(b, hipStreamSynchronize(b->stream)); // copy semantics: `img` and the caller's buffers are free again
+    return ls;
+}
+
+sb_status sb_batch_write_user_input(sb_batch *b, const void *bytes32)
+{
+    if (!b) return SB_ERR_INVALID;
+    if (!bytes32) SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_write_user_input: null buffer");
+    SbBatchWords8 w;
+    memcpy(w.w, bytes32, SB_USER_INPUT_BYTES);
+    SBB_HIP(b, hipSetDevice(b->device));
+    const uint32_t n = b->opt.n_scenes;
+    k_batch_meta8<<<cdivb(n * 8u, SBB_BLOCK), SBB_BLOCK, 0, b->stream>>>(b->V, 0u, n, SB_USER_INPUT_OFFSET / 4u, nullptr, w);
+    return check_launch(b, "sb_batch_write_user_input");
+}
+
+sb_status sb_batch_write_user_input_device(sb_batch *b, const void *device_bytes)
+{
+    if (!b) return SB_ERR_INVALID;
+    if (!device_bytes || ((uintptr_t)device_bytes & 3u)) SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_write_user_input_device: null or misaligned device buffer");
+    SBB_HIP(b, hipSetDevice(b->device));
+    const uint32_t n = b->opt.n_scenes;
+    k_batch_meta8<<<cdivb(n * 8u, SBB_BLOCK), SBB_BLOCK, 0, b->stream>>>(b->V, 0u, n, SB_USER_INPUT_OFFSET / 4u, (const uint32_t *)device_bytes,
+                                                                         SbBatchWords8{});
+    return check_launch(b, "sb_batch_write_user_input_device");
+}
+
+sb_status sb_batch_set_physics_constants(sb_batch *b, uint32_t first, uint32_t count, const float c8[8])
+{
+    if (!b) return SB_ERR_INVALID;
+    if (!c8) SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_set_physics_constants: null buffer");
+    if (count == 0 || first >= b->opt.n_scenes || count > b->opt.n_scenes - first)
+        SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_set_physics_constants: scenes %u .. %u+%u are not all inside the batch of %u", first, first, count,
+                 b->opt.n_scenes);
+    SbBatchWords8 w;
+    memcpy(w.w, c8, 32);
+    SBB_HIP(b, hipSetDevice(b->device));
+    k_batch_meta8<<<cdivb(count * 8u, SBB_BLOCK), SBB_BLOCK, 0, b->stream>>>(b->V, first, count, SB_BM_CONSTS, nullptr, w);
+    return check_launch(b, "sb_batch_set_physics_constants");
+}
+
+static sb_status launch_frame(sb_batch *b, uint32_t n_sub, uint32_t do_delete)
+{
+    hipLaunchKernelGGL(sb_batch_frame_kernel(b), dim3(b->opt.n_scenes), dim3(b->threads), b->lds_bytes, b->stream, b->V, b->prm, n_sub, do_delete);
+    return check_launch(b, "sb_batch frame kernel");
+}
+
+sb_status sb_batch_frame(sb_batch *b, uint32_t n_frames)
+{
+    if (!b) return SB_ERR_INVALID;
+    SBB_HIP(b, hipSetDevice(b->device));
+    for (uint32_t f = 0; f < n_frames; f++) { // engineWorker.ts:646-665
+        const sb_status s = launch_frame(b, b->subticks, 1u);
+        if (s != SB_OK) return s;
+        b->frames_done++;
+        b->substeps_done += b->subticks;
+    }
+    return SB_OK;
+}
+
+sb_status sb_batch_step(sb_batch *b, uint32_t n_substeps)
+{
+    if (!b) return SB_ERR_INVALID;
+    if (n_substeps == 0) return SB_OK;
+    SBB_HIP(b, hipSetDevice(b->device));
+    const sb_status s = launch_frame(b, n_substeps, 0u);
+    if (s == SB_OK) b->substeps_done += n_substeps;
+    return s;
+}
+
+sb_status sb_batch_delete_pass(sb_batch *b)
+{
+    if (!b) return SB_ERR_INVALID;
+    SBB_HIP(b, hipSetDevice(b->device));
+    return launch_frame(b, 0u, 1u);
+}
+
+sb_status sb_batch_reset_device(sb_batch *b, const void *device_mask_u8)
+{
+    if (!b) return SB_ERR_INVALID;
+    SBB_HIP(b, hipSetDevice(b->device));
+    k_batch_reset<<<b->opt.n_scenes, SBB_BLOCK, 0, b->stream>>>(b->V, (const unsigned char *)device_mask_u8);
+    return check_launch(b, "sb_batch_reset_device");
+}
+
+sb_status sb_batch_read_state_device(sb_batch *b, void *device_particles, void *device_beams, void *device_beam_alive)
+{
+    if (!b) return SB_ERR_INVALID;
+    if (((uintptr_t)device_particles & 3u) || ((uintptr_t)device_beams & 3u))
+        SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_read_state_device: particle and beam buffers must be 4-byte aligned");
+    if (!device_particles && !device_beams && !device_beam_alive) return SB_OK;
+    SBB_HIP(b, hipSetDevice(b->device));
+    k_batch_export<<<b->opt.n_scenes, SBB_BLOCK, 0, b->stream>>>(b->V, (float *)device_particles, (float *)device_beams, (unsigned char *)device_beam_alive);
+    return check_launch(b, "sb_batch_read_state_device");
+}
+
+sb_status sb_batch_write_particles_device(sb_batch *b, const void *device_particles)
+{
+    if (!b) return SB_ERR_INVALID;
+    if (!device_particles || ((uintptr_t)device_particles & 3u))
+        SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_write_particles_device: null or misaligned device buffer");
+    SBB_HIP(b, hipSetDevice(b->device));
+    k_batch_import<<<b->opt.n_scenes, SBB_BLOCK, 0, b->stream>>>(b->V, (const float *)device_particles);
+    return check_launch(b, "sb_batch_write_particles_device");
+}
+
+sb_status sb_batch_load_scene(sb_batch *b, uint32_t scene, void *metadata, size_t metadata_bytes, void *mapping, size_t mapping_bytes, void *particles,
+                              size_t particles_bytes, void *beams, size_t beams_bytes)
+{
+    if (!b) return SB_ERR_INVALID;
+    if (scene >= b->opt.n_scenes) SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_load_scene: scene %u is not inside the batch of %u", scene, b->opt.n_scenes);
+    const sb_status cs = check_sizes(b, "sb_batch_load_scene", false, metadata, metadata_bytes, mapping, mapping_bytes, particles, particles_bytes, beams,
+                                     beams_bytes);
+    if (cs != SB_OK) return cs;
+    const SbBatchView &V = b->V;
+    const uint32_t maxP = V.maxP, maxB = V.maxB;
+    SBB_HIP(b, hipSetDevice(b->device));
+    SBB_HIP(b, hipStreamSynchronize(b->stream));
+    uint32_t meta[SB_BM_WORDS];
+    std::vector<unsigned char> cst(V.cst_bytes), st(V.st_bytes);
+    SBB_HIP(b, hipMemcpy(meta, V.meta + (size_t)scene * SB_BM_WORDS, sizeof meta, hipMemcpyDeviceToHost));
+    if (meta[SB_BM_LOADED] == 0u) SBB_FAIL(b, SB_ERR_STATE, "sb_batch_load_scene: scene %u was never uploaded", scene);
+    SBB_HIP(b, hipMemcpy(cst.data(), V.cst + (size_t)scene * V.cst_bytes, V.cst_bytes, hipMemcpyDeviceToHost));
+    SBB_HIP(b, hipMemcpy(st.data(), V.st + (size_t)scene * V.st_bytes, V.st_bytes, hipMemcpyDeviceToHost));
+    const uint32_t *pmap = (const uint32_t *)(cst.data() + V.o_pmap), *bword = (const uint32_t *)(cst.data() + V.o_bword);
+    const uint32_t *bmap = (const uint32_t *)(st.data() + V.o_bmap);
+    const float *bmat = (const float *)(cst.data() + V.o_bmat), *bstate = (const float *)(st.data() + V.o_bstate);
+    const unsigned char *bex = cst.data() + V.o_bex;
+    const uint32_t P = meta[SB_BM_P];
+    if (metadata) memcpy(metadata, meta, SB_METADATA_BYTES);
+    if (mapping) {
+        uint8_t *m = (uint8_t *)mapping;
+        for (uint32_t s = 0; s < maxP; s++) map_set(b, m, s, pmap[s]);
+        for (uint32_t s = 0; s < maxB; s++) map_set(b, m, (size_t)maxP + s, bmap[s]);
+    }
+    if (particles)
+        for (uint32_t s = 0; s < P; s++)
+            memcpy((uint8_t *)particles + (size_t)pmap[s] * SB_PARTICLE_STRIDE, st.data() + V.o_part + (size_t)pmap[s] * SB_PARTICLE_STRIDE, SB_PARTICLE_STRIDE);
+    if (beams) {
+        const size_t foff = b->opt.layout == SB_LAYOUT_V1 ? 4 : 8;
+        for (uint32_t idx = 0; idx < maxB; idx++) { // every beam of the upload, removed ones with their last state
+            if (!bex[idx]) continue;
+            uint8_t *rec = (uint8_t *)beams + (size_t)idx * bstride(b);
+            const uint32_t da = pmap[bword[idx] & 0xffffu], db = pmap[bword[idx] >> 16];
+            if (b->opt.layout == SB_LAYOUT_V1) {
+                const uint32_t pair = (da & 0xffffu) | (db << 16);
+                memcpy(rec, &pair, 4);
+            } else {
+                memcpy(rec, &da, 4);
+                memcpy(rec + 4, &db, 4);
+            }
+            const float *m = bmat + (size_t)SB_BATCH_MAT_ROW * idx, *q = bstate + 4u * (size_t)idx;
+            const float f[9] = {m[0], q[0], q[1], m[1], m[2], m[3], m[4], q[2], q[3]};
+            memcpy(rec + foff, f, sizeof f);
+        }
+    }
+    return SB_OK;
+}
+
+sb_status sb_batch_sync(sb_batch *b)
+{
+    if (!b) return SB_ERR_INVALID;
+    SBB_HIP(b, hipSetDevice(b->device));
+    SBB_HIP(b, hipStreamSynchronize(b->stream));
+    return SB_OK;
+}
+
+sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream)
+{
+    if (!b) return SB_ERR_INVALID;
+    if (!hip_stream) SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_get_stream: null argument");
+    *hip_stream = (void *)b->stream;
+    return SB_OK;
+}
+
+sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value)
+{
+    if (!b) return SB_ERR_INVALID;
+    if (!key || !value) SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_get_info: null argument");
+    const std::string k(key);
+    if (k == "n_scenes") *value = b->opt.n_scenes;
+    else if (k == "scene_max_particles") *value = SB_BATCH_MAX_PARTICLES;
+    else if (k == "scene_max_beams") *value = SB_BATCH_MAX_BEAMS;
+    else if (k == "max_particles") *value = b->opt.max_particles;
+    else if (k == "max_beams") *value = b->opt.max_beams;
+    else if (k == "threads_per_scene") *value = b->threads;
+    else if (k == "lds_bytes_per_scene") *value = b->lds_bytes;
+    else if (k == "materials_in_lds") *value = b->mat_lds ? 1u : 0u;
+    else if (k == "scenes_per_cu") *value = (uint64_t)std::max(b->scenes_per_cu, 0);
+    else if (k == "frame_kernel_vgprs") *value = (uint64_t)std::max(b->vgprs, 0);
+    else if (k == "frame_kernel_scratch_bytes") *value = (uint64_t)std::max(b->scratch, 0);
+    else if (k == "frames_done") *value = b->frames_done;
+    else if (k == "substeps_done") *value = b->substeps_done;
+    else SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_get_info: unknown key '%s'", key);
+    return SB_OK;
+}
