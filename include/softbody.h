@@ -40,6 +40,7 @@
  *         hash copies its start state from host memory, which the runtime may do behind the work in flight).
  *       The sb_batch_* group (many small scenes, below): everything only enqueues on the batch's own stream except
  *         sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync, which wait for it.
+ *         sb_batch_render_device only enqueues; sb_batch_render_scene waits for the stream.
  *       A wait POLLS the stream for as long as the work in flight should take (busily for
  *         the first 8 ms, then every ~50 us between short sleeps; 0.2 s at most) before it
  *         parks the thread: being woken costs 0.2 - 0.5 ms on some hosts, more than many
@@ -427,6 +428,7 @@ sb_status sb_write_particles_device(sb_engine *e, const void *device_particles);
  *   When do calls return?  sb_batch_frame / _step / _delete_pass / _reset_device / _write_user_input[_device] /
  *     _set_physics_constants / _read_state_device / _write_particles_device only ENQUEUE on the batch's stream (device buffers
  *     must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
+ *     sb_batch_render_device only ENQUEUES (its device buffer must stay valid likewise); sb_batch_render_scene WAITS.
  *   Errors: every call returns an sb_status; sb_batch_last_error(b) gives the message (b == NULL: the last failed
  *     sb_batch_create of the calling thread).  Options are checked BEFORE a device is looked for. */
 #define SB_BATCH_MAX_PARTICLES 1024
@@ -488,11 +490,38 @@ sb_status sb_batch_write_particles_device(sb_batch *b, const void *device_partic
 sb_status sb_batch_load_scene(sb_batch *b, uint32_t scene, void *metadata, size_t metadata_bytes, void *mapping, size_t mapping_bytes,
                               void *particles, size_t particles_bytes, void *beams, size_t beams_bytes);
 
+/* ---- pictures of a batch: one per scene, all in ONE launch ----
+ * The picture of scene i is host/render.js's renderPPM body of what sb_batch_load_scene(i) would return at that point of the
+ * stream, byte for byte: RGB8, rows top to bottom, no header -- sb_render's rules, including what is drawn for non-finite
+ * coordinates.  A scene never uploaded, or one of zero particles, gives an all-black picture whose bytes ARE written: the output
+ * is fully defined, the caller need not clear it.  A render only reads: frame, render, frame equals frame, frame bit for bit,
+ * pending break flags included.
+ * Zero fields mean: resolution 64; bounds_size and particle_radius those of sb_batch_options; count = every scene from `first` on.
+ * sb_batch_render_device only ENQUEUES on the batch's stream: `count` pictures of resolution^2 * 3 bytes, back to back, into
+ *   DEVICE memory (no alignment asked for), which must stay valid until that work has run.
+ * sb_batch_render_scene WAITS: ONE scene's picture into host memory (debugging, the C user); `first` / `count` are not used.
+ * Errors: SB_ERR_INVALID for a NULL handle, a struct_size that is neither 0 nor the struct's, a resolution above
+ *   SB_BATCH_RENDER_MAX_RESOLUTION, first or first + count (or `scene`) outside the batch, a NULL output, a host buffer smaller than
+ *   the picture -- all checked before anything touches a device; SB_ERR_STATE from sb_batch_render_scene for a scene never
+ *   uploaded, as from sb_batch_load_scene. */
+#define SB_BATCH_RENDER_MAX_RESOLUTION 1024
+typedef struct sb_batch_render_options {
+    uint32_t struct_size;    /* = sizeof(sb_batch_render_options); 0 or a NULL pointer = all defaults */
+    uint32_t resolution;     /* each picture is resolution x resolution pixels; 0 = 64 */
+    double bounds_size;      /* world units across the picture; 0 = sb_batch_options.bounds_size */
+    double particle_radius;  /* disc radius in world units; 0 = sb_batch_options.particle_radius */
+    uint32_t first, count;   /* scenes first .. first+count-1; count 0 = first .. n_scenes-1 */
+    uint32_t reserved[4];
+} sb_batch_render_options;
+sb_status sb_batch_render_device(sb_batch *b, const sb_batch_render_options *opts, void *device_rgb);
+sb_status sb_batch_render_scene(sb_batch *b, uint32_t scene, const sb_batch_render_options *opts, void *rgb, size_t rgb_bytes);
+
 sb_status sb_batch_sync(sb_batch *b);
 sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream);
 /* key = "n_scenes", "scene_max_particles", "scene_max_beams" (the limits), "max_particles", "max_beams" (this batch's capacity),
  * "threads_per_scene", "lds_bytes_per_scene", "materials_in_lds", "scenes_per_cu", "frame_kernel_vgprs",
- * "frame_kernel_scratch_bytes", "frames_done", "substeps_done" */
+ * "frame_kernel_scratch_bytes", "frames_done", "substeps_done", "render_kernel_vgprs", "render_kernel_scratch_bytes",
+ * "render_lds_bytes", "render_bands" (the last two: LDS per workgroup and bands per picture of the most recent render) */
 sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value);
 const char *sb_batch_last_error(const sb_batch *b);
 

@@ -9,6 +9,7 @@ from .engine import COLLIDE_GRID, EngineError, _ptr
 from .layout import LAYOUT_V1, PARTICLE_STRIDE, Buffers
 
 BATCH_MAX_PARTICLES, BATCH_MAX_BEAMS = 1024, 4096     # SB_BATCH_MAX_* (include/softbody.h)
+BATCH_RENDER_MAX_RESOLUTION = 1024                    # SB_BATCH_RENDER_MAX_RESOLUTION
 
 
 class SbBatchOptions(ctypes.Structure):
@@ -16,6 +17,12 @@ class SbBatchOptions(ctypes.Structure):
                 ("particle_radius", ctypes.c_float), ("subticks", ctypes.c_uint32), ("max_particles", ctypes.c_uint32),
                 ("max_beams", ctypes.c_uint32), ("layout", ctypes.c_uint32), ("collision_mode", ctypes.c_uint32),
                 ("device_ordinal", ctypes.c_int32), ("reserved", ctypes.c_uint32 * 6)]
+
+
+class SbBatchRenderOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("resolution", ctypes.c_uint32), ("bounds_size", ctypes.c_double),
+                ("particle_radius", ctypes.c_double), ("first", ctypes.c_uint32), ("count", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 4)]
 
 
 _bound = None
@@ -43,6 +50,8 @@ def load_library():
     L.sb_batch_read_state_device.argtypes = [vp, vp, vp, vp]
     L.sb_batch_write_particles_device.argtypes = [vp, vp]
     L.sb_batch_load_scene.argtypes = [vp, u32, vp, sz, vp, sz, vp, sz, vp, sz]
+    L.sb_batch_render_device.argtypes = [vp, ctypes.POINTER(SbBatchRenderOptions), vp]
+    L.sb_batch_render_scene.argtypes = [vp, u32, ctypes.POINTER(SbBatchRenderOptions), vp, sz]
     L.sb_batch_sync.argtypes = [vp]
     L.sb_batch_get_stream.argtypes = [vp, ctypes.POINTER(vp)]
     L.sb_batch_get_info.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)]
@@ -227,3 +236,46 @@ class BatchEngine:
         a = torch.zeros((self.n_scenes, self.max_beams), dtype=torch.bool, device=dev)
         self.read_state_device(p, b, a)
         return p, b, a
+
+    # ---- pictures (sb_batch_render_device / sb_batch_render_scene)
+    def _render_options(self, resolution, bounds_size, particle_radius, first=0, count=0):
+        o = SbBatchRenderOptions()
+        o.struct_size = ctypes.sizeof(SbBatchRenderOptions)
+        o.resolution = int(resolution)
+        o.bounds_size = 0.0 if bounds_size is None else float(bounds_size)
+        o.particle_radius = 0.0 if particle_radius is None else float(particle_radius)
+        o.first, o.count = first, count
+        return o
+
+    def render(self, resolution=64, bounds_size=None, particle_radius=None, first=0, count=None, out=None):
+        """One picture per scene first .. first+count-1 (count=None: every scene from `first` on), all drawn in one launch: a
+        torch.uint8 tensor [count, resolution, resolution, 3] on the batch's device, each picture host/render.js's renderPPM
+        body (RGB8, rows top to bottom) of what load_scene would return now; scenes never uploaded or empty are black.
+        None = the batch's own bounds / radius.  `out`: a device pointer (int) or a contiguous uint8 torch tensor of at least
+        count * resolution^2 * 3 bytes to draw into.  Only enqueues; torch's current stream is ordered after the render."""
+        import torch
+        res = int(resolution)
+        if not 0 < res <= BATCH_RENDER_MAX_RESOLUTION:
+            raise ValueError("render: resolution %d is not in 1 .. %d" % (res, BATCH_RENDER_MAX_RESOLUTION))
+        first = int(first)
+        count = self.n_scenes - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > self.n_scenes:
+            raise ValueError("render: scenes %d .. %d+%d are not all inside the batch of %d" % (first, first, count, self.n_scenes))
+        if out is None:
+            out = torch.empty((count, res, res, 3), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        ptr, t = self._device_buffer("render: out", out, "uint8", count * res * res * 3)
+        o = self._render_options(res, bounds_size, particle_radius, first, count)
+        self._ordered(t, lambda: load_library().sb_batch_render_device(self._h, ctypes.byref(o), ctypes.c_void_p(ptr)))
+        if t and tuple(out.shape) != (count, res, res, 3):
+            return out.view(-1)[:count * res * res * 3].view(count, res, res, 3)
+        return out
+
+    def render_scene(self, i, resolution=64, bounds_size=None, particle_radius=None):
+        """Scene i's picture as a numpy (resolution, resolution, 3) uint8 array.  Waits for the stream."""
+        res = int(resolution)
+        if not 0 < res <= BATCH_RENDER_MAX_RESOLUTION:
+            raise ValueError("render_scene: resolution %d is not in 1 .. %d" % (res, BATCH_RENDER_MAX_RESOLUTION))
+        out = np.empty((res, res, 3), dtype=np.uint8)
+        o = self._render_options(res, bounds_size, particle_radius)
+        self._check(load_library().sb_batch_render_scene(self._h, int(i), ctypes.byref(o), _ptr(out), out.nbytes))
+        return out

@@ -1,0 +1,90 @@
+// sb_batch.h -- what the files of the sb_batch_* group share: the device memory of a batch and its host object
+// (sb_batch.hip: upload, stepping, state I/O; sb_batch_render.hip: pictures).
+#pragma once
+#include <cstdio>
+#include <string>
+
+#include "../../include/softbody.h"
+#include "sb_physics.h"
+
+// ---------------------------------------------------------------- device memory of a batch
+// Per scene: 32 metadata words (the 112 bytes of the reference's metadata buffer, then SB_BM_B0 / SB_BM_LOADED), a CONSTANT blob
+// (what only an upload writes) and a STATE blob (what stepping changes), the latter twice: current and reset.  Everything a
+// beam or a particle owns is stored at its DATA index, so the state export / import are plain row copies.
+#define SB_BM_WORDS 32u
+#define SB_BM_P 1u       // metadata.particle_i_c
+#define SB_BM_B 6u       // metadata.beam_i_c (live beam slots)
+#define SB_BM_CONSTS 12u // 8 physics constants, 8 user input words
+#define SB_BM_B0 28u     // beam slots at the latest upload
+#define SB_BM_LOADED 29u // 1 once uploaded
+#define SB_BATCH_MAT_ROW 6u // length, spring, damp, yield, limit, 1/length
+
+struct SbBatchView {
+    uint32_t *meta;     // [n_scenes][SB_BM_WORDS]
+    unsigned char *cst; // [n_scenes][cst_bytes]
+    unsigned char *st;  // [n_scenes][st_bytes]  current
+    unsigned char *rst; // [n_scenes][st_bytes]  reset
+    uint32_t cst_bytes, st_bytes; // multiples of 16
+    // constant blob: slot -> data index of every particle slot (all max_particles entries of the uploaded mapping, verbatim),
+    // per beam DATA index (slot of endpoint A) | (slot of endpoint B) << 16 and the material row, per data index "holds a
+    // particle / beam of the upload"
+    uint32_t o_pmap, o_bword, o_bmat, o_pex, o_bex;
+    // state blob: particle records (6 f32) and beam state {target, last, strain, stress} at their data indices, slot -> data
+    // index of every beam slot (verbatim; the delete pass compacts its head in place), pending break flags (one bit per beam
+    // SLOT), per beam data index "not removed by a delete pass"
+    uint32_t o_part, o_bstate, o_bmap, o_bflags, o_balive;
+    uint32_t maxP, maxB, nflagw, n_scenes;
+};
+
+SB_DEV uint32_t sbb_uniform(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
+SB_DEV float sbb_uniform(float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); }
+
+// ---------------------------------------------------------------- host
+struct SbBatchRender; // sb_batch_render.hip
+
+struct sb_batch {
+    sb_batch_options opt{};
+    std::string err;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    SbBatchView V{};
+    SbParams prm{};
+    uint32_t subticks = 0, threads = 0, lds_bytes = 0;
+    bool mat_lds = false, collide = false;
+    unsigned char *stage = nullptr; // device staging of one upload: meta words, constant blob, state blob
+    uint64_t frames_done = 0, substeps_done = 0;
+    int scenes_per_cu = 0, vgprs = 0, scratch = 0;
+    SbBatchRender *render = nullptr; // what the renderer keeps between calls (made at the first render)
+};
+
+extern thread_local std::string g_batch_create_error; // sb_batch.hip
+
+#define SBB_FAIL(b, code, ...)                                         \
+    do {                                                               \
+        char _buf[512];                                                \
+        snprintf(_buf, sizeof _buf, __VA_ARGS__);                      \
+        if (b) (b)->err = _buf; else g_batch_create_error = _buf;      \
+        return (code);                                                 \
+    } while (0)
+#define SBB_HIP(b, call)                                                                                   \
+    do {                                                                                                   \
+        hipError_t _r = (call);                                                                            \
+        if (_r != hipSuccess) {                                                                            \
+            (void)hipGetLastError();                                                                       \
+            SBB_FAIL(b, _r == hipErrorOutOfMemory ? SB_ERR_OOM : SB_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(_r)); \
+        }                                                                                                  \
+    } while (0)
+
+static inline sb_status check_launch(sb_batch *b, const char *what)
+{
+    const hipError_t r = hipGetLastError();
+    if (r != hipSuccess) SBB_FAIL(b, SB_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(r));
+    return SB_OK;
+}
+
+static inline uint32_t up16(uint32_t x) { return (x + 15u) & ~15u; }
+static inline uint32_t cdivb(uint32_t a, uint32_t b) { return (a + b - 1u) / b; }
+
+// sb_batch_render.hip
+void sbb_render_release(sb_batch *b);                                   // sb_batch_destroy
+bool sbb_render_info(sb_batch *b, const char *key, uint64_t *value);    // sb_batch_get_info's render keys; false: not one of them

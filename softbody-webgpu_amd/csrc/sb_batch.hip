@@ -21,40 +21,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/softbody.h"
-#include "sb_physics.h"
-
-// ---------------------------------------------------------------- device memory of a batch
-// Per scene: 32 metadata words (the 112 bytes of the reference's metadata buffer, then SB_BM_B0 / SB_BM_LOADED), a CONSTANT blob
-// (what only an upload writes) and a STATE blob (what stepping changes), the latter twice: current and reset.  Everything a
-// beam or a particle owns is stored at its DATA index, so the state export / import are plain row copies.
-#define SB_BM_WORDS 32u
-#define SB_BM_P 1u       // metadata.particle_i_c
-#define SB_BM_B 6u       // metadata.beam_i_c (live beam slots)
-#define SB_BM_CONSTS 12u // 8 physics constants, 8 user input words
-#define SB_BM_B0 28u     // beam slots at the latest upload
-#define SB_BM_LOADED 29u // 1 once uploaded
-#define SB_BATCH_MAT_ROW 6u // length, spring, damp, yield, limit, 1/length
-
-struct SbBatchView {
-    uint32_t *meta;     // [n_scenes][SB_BM_WORDS]
-    unsigned char *cst; // [n_scenes][cst_bytes]
-    unsigned char *st;  // [n_scenes][st_bytes]  current
-    unsigned char *rst; // [n_scenes][st_bytes]  reset
-    uint32_t cst_bytes, st_bytes; // multiples of 16
-    // constant blob: slot -> data index of every particle slot (all max_particles entries of the uploaded mapping, verbatim),
-    // per beam DATA index (slot of endpoint A) | (slot of endpoint B) << 16 and the material row, per data index "holds a
-    // particle / beam of the upload"
-    uint32_t o_pmap, o_bword, o_bmat, o_pex, o_bex;
-    // state blob: particle records (6 f32) and beam state {target, last, strain, stress} at their data indices, slot -> data
-    // index of every beam slot (verbatim; the delete pass compacts its head in place), pending break flags (one bit per beam
-    // SLOT), per beam data index "not removed by a delete pass"
-    uint32_t o_part, o_bstate, o_bmap, o_bflags, o_balive;
-    uint32_t maxP, maxB, nflagw, n_scenes;
-};
-
-SB_DEV uint32_t sbb_uniform(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
-SB_DEV float sbb_uniform(float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); }
+#include "sb_batch.h"
 
 // ---------------------------------------------------------------- the frame kernel
 // One thread per particle slot (blockDim.x >= max_particles: chosen at create), beams dealt round-robin.
@@ -312,40 +279,8 @@ __global__ __launch_bounds__(SBB_BLOCK) void k_batch_import(SbBatchView V, const
 }
 
 // ---------------------------------------------------------------- host
-struct sb_batch {
-    sb_batch_options opt{};
-    std::string err;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    SbBatchView V{};
-    SbParams prm{};
-    uint32_t subticks = 0, threads = 0, lds_bytes = 0;
-    bool mat_lds = false, collide = false;
-    unsigned char *stage = nullptr; // device staging of one upload: meta words, constant blob, state blob
-    uint64_t frames_done = 0, substeps_done = 0;
-    int scenes_per_cu = 0, vgprs = 0, scratch = 0;
-};
+thread_local std::string g_batch_create_error;
 
-static thread_local std::string g_batch_create_error;
-
-#define SBB_FAIL(b, code, ...)                                         \
-    do {                                                               \
-        char _buf[512];                                                \
-        snprintf(_buf, sizeof _buf, __VA_ARGS__);                      \
-        if (b) (b)->err = _buf; else g_batch_create_error = _buf;      \
-        return (code);                                                 \
-    } while (0)
-#define SBB_HIP(b, call)                                                                                   \
-    do {                                                                                                   \
-        hipError_t _r = (call);                                                                            \
-        if (_r != hipSuccess) {                                                                            \
-            (void)hipGetLastError();                                                                       \
-            SBB_FAIL(b, _r == hipErrorOutOfMemory ? SB_ERR_OOM : SB_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(_r)); \
-        }                                                                                                  \
-    } while (0)
-
-static inline uint32_t up16(uint32_t x) { return (x + 15u) & ~15u; }
-static inline uint32_t cdivb(uint32_t a, uint32_t b) { return (a + b - 1u) / b; }
 
 // threads of a scene's workgroup: one per particle slot of the capacity, and enough that a lane evaluates at most four beams
 // per substep; whole waves, 64 .. 1024
@@ -396,6 +331,7 @@ sb_status sb_batch_destroy(sb_batch *b)
     if (b->V.st) (void)hipFree(b->V.st);
     if (b->V.rst) (void)hipFree(b->V.rst);
     if (b->stage) (void)hipFree(b->stage);
+    sbb_render_release(b);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
     return SB_OK;
@@ -542,13 +478,6 @@ static sb_status check_sizes(sb_batch *b, const char *who, bool need_all, const 
         SBB_FAIL(b, SB_ERR_INVALID, "%s: particle buffer is %zu bytes, need %zu", who, particles_bytes, (size_t)maxP * SB_PARTICLE_STRIDE);
     if (beams && beams_bytes < (size_t)maxB * bstride(b))
         SBB_FAIL(b, SB_ERR_INVALID, "%s: beam buffer is %zu bytes, need %zu", who, beams_bytes, (size_t)maxB * bstride(b));
-    return SB_OK;
-}
-
-static sb_status check_launch(sb_batch *b, const char *what)
-{
-    const hipError_t r = hipGetLastError();
-    if (r != hipSuccess) SBB_FAIL(b, SB_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(r));
     return SB_OK;
 }
 
@@ -817,6 +746,7 @@ sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value)
     else if (k == "frame_kernel_scratch_bytes") *value = (uint64_t)std::max(b->scratch, 0);
     else if (k == "frames_done") *value = b->frames_done;
     else if (k == "substeps_done") *value = b->substeps_done;
+    else if (sbb_render_info(b, key, value)) return SB_OK;
     else SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_get_info: unknown key '%s'", key);
     return SB_OK;
 }
