@@ -21,25 +21,7 @@
 extern "C" sb_status sb_halo_set_layout(sb_engine *e, const uint32_t *, const uint32_t *, const uint32_t *, const uint32_t *);
 
 static thread_local std::string g_create_error;
-void sb_set_create_error(const char *msg) { g_create_error = msg ? msg : ""; } // for sb_partition.cpp
-
-#define SB_FAIL(e, code, ...)                                   \
-    do {                                                        \
-        char _buf[512];                                         \
-        snprintf(_buf, sizeof _buf, __VA_ARGS__);               \
-        if (e) (e)->err = _buf; else g_create_error = _buf;     \
-        return (code);                                          \
-    } while (0)
-
-#define SB_HIP(e, call)                                                                       \
-    do {                                                                                      \
-        hipError_t _r = (call);                                                               \
-        if (_r != hipSuccess) {                                                               \
-            (void)hipGetLastError(); /* reported here: must not resurface in a later launch check */ \
-            SB_FAIL(e, _r == hipErrorOutOfMemory ? SB_ERR_OOM : SB_ERR_HIP, "%s failed: %s",  \
-                    #call, hipGetErrorString(_r));                                            \
-        }                                                                                     \
-    } while (0)
+void sb_set_create_error(const char *msg) { g_create_error = msg ? msg : ""; } // (sb_error.h)
 
 // Device arrays of a scene come from a per-engine pool: an upload that replaces a scene (the reference uploads after every
 // edit, engineWorker.ts:569-601) finds last scene's blocks there instead of paying ~30 hipFree + hipMalloc pairs, each a device
@@ -84,12 +66,6 @@ static void pool_trim(sb_engine *e)
         e->pool_free.erase(e->pool_free.begin() + (ptrdiff_t)big);
     }
 }
-
-#define SB_TRY(x)                          \
-    do {                                   \
-        sb_status _s = (x);                \
-        if (_s != SB_OK) return _s;        \
-    } while (0)
 
 // Waiting for the engine's stream where the wait is SHORT (the end of a call's launches, the looks of the spatial hash, a run of
 // blocked launches under the hash): poll for `spin_us` before falling back on the blocking wait.  hipStreamSynchronize parks the
@@ -207,21 +183,6 @@ static void free_scene(sb_engine *e)
     e->d_guard_status = nullptr;
     if (e->dev_err) *e->dev_err = 0;
 }
-
-static inline uint32_t beam_stride(const sb_engine *e)
-{
-    return e->opt.layout == SB_LAYOUT_V1 ? SB_BEAM_STRIDE_V1 : SB_BEAM_STRIDE_V2;
-}
-static inline void map_set(const sb_engine *e, uint8_t *m, size_t id, uint32_t val)
-{
-    if (e->opt.layout == SB_LAYOUT_V1) {
-        uint16_t v = (uint16_t)val;
-        memcpy(m + 2 * id, &v, 2);
-    } else {
-        memcpy(m + 4 * id, &val, 4);
-    }
-}
-static inline uint32_t rd_u32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
 
 // material dictionary: beams that share (length, spring, damp, yield, limit) share one table row; mode 2 = rows with
 // the rest length, mode 1 = rows without it (arbitrary rest lengths travel per beam), 0 = more rows than `cap`
@@ -725,9 +686,10 @@ static sb_status rewrite_scene_state(sb_engine *e, const uint8_t *md, const uint
 {
     *kept = false;
     static const bool off = [] { const char *v = getenv("SB_KEEP_PLAN"); return v && atoi(v) == 0; }();
-    const uint32_t maxP = e->opt.max_particles, maxB = e->opt.max_beams, bstride = beam_stride(e);
-    const uint32_t P = rd_u32(md + 4), B = rd_u32(md + 24);
-    const size_t map_bytes = (size_t)(maxP + (size_t)maxB) * map_isz(e), isz = map_isz(e);
+    const uint32_t maxP = e->opt.max_particles, maxB = e->opt.max_beams, layout = e->opt.layout, bstride = sbc::beam_stride(layout);
+    const sbc::Header hd(md);
+    const uint32_t P = hd.P, B = hd.B;
+    const size_t map_bytes = sbc::mapping_bytes(layout, maxP, maxB), isz = map_isz(e);
     const uint32_t Bu = e->loaded ? sb_user_beams(e) : 0u; // beams of the upload before this one, in the caller's slots
     if (off || !e->loaded || P != e->P || B > Bu || e->h_beams.size() != e->B || e->h_pidx.size() != P || e->h_mapping.size() != map_bytes)
         return SB_OK;
@@ -751,30 +713,17 @@ static sb_status rewrite_scene_state(sb_engine *e, const uint8_t *md, const uint
             seen[idx] = 1;
         }
     }
-    const bool v1 = e->opt.layout == SB_LAYOUT_V1;
     // one record of the new upload against one beam of the engine: endpoints and static parameters must match what the plan was
     // made for; the state fields are taken over on a match (if the upload turns out not to fit, the full path replaces every
     // record anyway)
     auto take = [&](size_t u, uint32_t s) -> bool {
-        const uint8_t *rec = bd + (size_t)map_get(e, mp, (size_t)maxP + u) * bstride;
         uint32_t a, b;
-        float f[9];
-        if (v1) {
-            const uint32_t pair = rd_u32(rec);
-            a = pair & 0xffffu;
-            b = pair >> 16;
-            memcpy(f, rec + 4, sizeof f);
-        } else {
-            a = rd_u32(rec);
-            b = rd_u32(rec + 4);
-            memcpy(f, rec + 8, sizeof f);
-        }
+        const uint8_t *f9;
+        sbc::decode_beam(layout, bd + (size_t)map_get(e, mp, (size_t)maxP + u) * bstride, a, b, f9);
         SbHostBeam &h = e->h_beams[s];
-        if (a != h.da || b != h.db || memcmp(&f[0], &h.f[0], 4) != 0 || memcmp(&f[3], &h.f[3], 16) != 0) return false;
-        h.f[1] = f[1];
-        h.f[2] = f[2];
-        h.f[7] = f[7];
-        h.f[8] = f[8];
+        if (a != h.da || b != h.db || memcmp(f9, &h.f[0], 4) != 0 || memcmp(f9 + 12, &h.f[3], 16) != 0) return false;
+        memcpy(&h.f[1], f9 + 4, 8);  // target_length, last_length
+        memcpy(&h.f[7], f9 + 28, 8); // strain, stress
         return true;
     };
     std::vector<uint32_t> user_slot; // (stays empty when the caller's slots are the engine's)
@@ -792,8 +741,9 @@ static sb_status rewrite_scene_state(sb_engine *e, const uint8_t *md, const uint
     } else {
         // Beams were removed: the records that are left are a subsequence of the old ones (sb_edit.h)
         auto same_key = [&](size_t u, size_t o) {
-            const uint8_t *rec = bd + (size_t)map_get(e, mp, (size_t)maxP + u) * bstride;
-            const uint32_t a = v1 ? rd_u32(rec) & 0xffffu : rd_u32(rec), b = v1 ? rd_u32(rec) >> 16 : rd_u32(rec + 4);
+            uint32_t a, b;
+            const uint8_t *f9;
+            sbc::decode_beam(layout, bd + (size_t)map_get(e, mp, (size_t)maxP + u) * bstride, a, b, f9);
             const SbHostBeam &h = e->h_beams[sb_user_slot(e, o)];
             return h.da == a && h.db == b;
         };
@@ -934,24 +884,18 @@ static sb_status sb_write_buffers_impl(sb_engine *e, const void *metadata, size_
                            const void *beams, size_t beams_bytes)
 {
     if (!e) return SB_ERR_INVALID;
-    if (!metadata || !mapping || !particles || (!beams && e->opt.max_beams))
-        SB_FAIL(e, SB_ERR_INVALID, "sb_write_buffers: null buffer");
-    const uint32_t maxP = e->opt.max_particles, maxB = e->opt.max_beams;
-    const uint32_t bstride = beam_stride(e);
-    if (metadata_bytes < SB_METADATA_BYTES) SB_FAIL(e, SB_ERR_INVALID, "metadata buffer is %zu bytes, need 112", metadata_bytes);
-    if (mapping_bytes < (size_t)(maxP + (size_t)maxB) * map_isz(e))
-        SB_FAIL(e, SB_ERR_INVALID, "mapping buffer is %zu bytes, need %zu", mapping_bytes, (size_t)(maxP + (size_t)maxB) * map_isz(e));
-    if (particles_bytes < (size_t)maxP * SB_PARTICLE_STRIDE)
-        SB_FAIL(e, SB_ERR_INVALID, "particle buffer is %zu bytes, need %zu", particles_bytes, (size_t)maxP * SB_PARTICLE_STRIDE);
-    if (beams_bytes < (size_t)maxB * bstride)
-        SB_FAIL(e, SB_ERR_INVALID, "beam buffer is %zu bytes, need %zu", beams_bytes, (size_t)maxB * bstride);
+    const uint32_t maxP = e->opt.max_particles, maxB = e->opt.max_beams, layout = e->opt.layout;
+    const sbc::SizeError sz = sbc::check_sizes(layout, maxP, maxB, true, metadata, metadata_bytes, mapping, mapping_bytes, particles, particles_bytes,
+                                               beams, beams_bytes);
+    if (sz.buffer == sbc::BUF_NULL) SB_FAIL(e, SB_ERR_INVALID, "sb_write_buffers: null buffer");
+    if (sz.buffer) SB_FAIL(e, SB_ERR_INVALID, "%s buffer is %zu bytes, need %zu", sbc::buffer_name(sz.buffer), sz.have, sz.need);
     const uint8_t *md = (const uint8_t *)metadata, *mp = (const uint8_t *)mapping;
     const uint8_t *pd = (const uint8_t *)particles, *bd = (const uint8_t *)beams;
-    const uint32_t P = rd_u32(md + 4), B = rd_u32(md + 24);
-    if (rd_u32(md + 40) != maxP || rd_u32(md + 44) != maxB)
-        SB_FAIL(e, SB_ERR_INVALID, "metadata max_particles/max_beams (%u/%u) differ from the engine capacity (%u/%u)",
-                rd_u32(md + 40), rd_u32(md + 44), maxP, maxB);
-    if (P > maxP || B > maxB) SB_FAIL(e, SB_ERR_INVALID, "metadata counts (%u/%u) exceed capacity (%u/%u)", P, B, maxP, maxB);
+    const sbc::Header hd(md);
+    const uint32_t P = hd.P, B = hd.B;
+    if (!hd.capacity_is(maxP, maxB))
+        SB_FAIL(e, SB_ERR_INVALID, "metadata max_particles/max_beams (%u/%u) differ from the engine capacity (%u/%u)", hd.maxP, hd.maxB, maxP, maxB);
+    if (!hd.counts_fit(maxP, maxB)) SB_FAIL(e, SB_ERR_INVALID, "metadata counts (%u/%u) exceed capacity (%u/%u)", P, B, maxP, maxB);
 
     SB_HIP(e, hipSetDevice(e->device));
     SB_HIP(e, hipStreamSynchronize(e->stream));
@@ -970,7 +914,7 @@ static sb_status sb_write_buffers_impl(sb_engine *e, const void *metadata, size_
     SbStageTimer tm;
     // ---- host shadows (copy semantics)
     e->h_metadata.assign(md, md + SB_METADATA_BYTES);
-    e->h_mapping.assign(mp, mp + (size_t)(maxP + (size_t)maxB) * map_isz(e));
+    e->h_mapping.assign(mp, mp + sbc::mapping_bytes(layout, maxP, maxB));
     e->P = P;
     e->B = B;
     e->h_user_slot.clear();
@@ -978,70 +922,26 @@ static sb_status sb_write_buffers_impl(sb_engine *e, const void *metadata, size_
     e->substeps_done = 0;
 
     tm.mark("sync + free + shadows");
-    // ---- particles: slot -> data index, must be a partial injection
-    std::vector<uint32_t> slot_index(P), internal_of_index(maxP, 0xFFFFFFFFu);
-    for (uint32_t s = 0; s < P; s++) {
-        uint32_t idx = map_get(e, mp, s);
-        if (idx >= maxP) SB_FAIL(e, SB_ERR_INVALID, "particle slot %u maps to data index %u >= max_particles", s, idx);
-        if (internal_of_index[idx] != 0xFFFFFFFFu)
-            SB_FAIL(e, SB_ERR_INVALID, "particle data index %u is mapped by two slots (%u and %u)", idx, internal_of_index[idx], s);
-        internal_of_index[idx] = s; // provisional: slot
-        slot_index[s] = idx;
-    }
-    // ---- beams: slot -> record; endpoints must be active particles
+    // ---- validate (sb_scene_codec.h) and take the beam records over in the same walk: a few host threads over the beam slots
+    std::vector<uint32_t> slot_index, internal_of_index; // slot -> data index; data index -> slot (provisional: re-indexed below)
     SbHostBeams hb(B);
     {
-        // a few host threads over the beam slots; the first offence (lowest slot of its chunk) is reported
-        std::vector<uint8_t> seen((size_t)maxB, 0);
-        struct Bad { uint32_t slot = 0xFFFFFFFFu, kind = 0, idx = 0, a = 0, b = 0; };
-        std::vector<Bad> bad(64);
-        std::atomic<uint32_t> nchunk{0};
-        sbt::parallel_ranges(B, 1 << 15, [&](size_t s0, size_t s1) {
-            Bad &mine = bad[nchunk.fetch_add(1) % bad.size()];
-            for (size_t s = s0; s < s1; s++) {
-                const uint32_t idx = map_get(e, mp, (size_t)maxP + s);
-                Bad here;
-                here.slot = (uint32_t)s;
-                here.idx = idx;
-                if (idx >= maxB) here.kind = 1;
-                else if (__atomic_fetch_or(&seen[idx], 1, __ATOMIC_RELAXED)) here.kind = 2;
-                if (!here.kind) {
-                    const uint8_t *rec = bd + (size_t)idx * bstride;
-                    uint32_t a, b;
-                    const uint8_t *f;
-                    if (e->opt.layout == SB_LAYOUT_V1) { // engineMapping.ts:183-186, compute.wgsl:99-100
-                        uint32_t pair = rd_u32(rec);
-                        a = pair & 0xffffu;
-                        b = pair >> 16;
-                        f = rec + 4;
-                    } else {
-                        a = rd_u32(rec);
-                        b = rd_u32(rec + 4);
-                        f = rec + 8;
-                    }
-                    here.a = a;
-                    here.b = b;
-                    if (a >= maxP || b >= maxP || internal_of_index[a] == 0xFFFFFFFFu || internal_of_index[b] == 0xFFFFFFFFu) here.kind = 3;
-                    else {
-                        SbHostBeam &h = hb[s];
-                        h.a = internal_of_index[a]; // slot of endpoint A (re-indexed below)
-                        h.b = internal_of_index[b];
-                        h.da = a;
-                        h.db = b;
-                        memcpy(h.f, f, 9 * sizeof(float));
-                    }
-                }
-                if (here.kind && here.slot < mine.slot) mine = here;
-            }
+        const sbc::Scene sc{layout, maxP, maxB, P, B, mp, bd};
+        const sbc::SceneError bad = sbc::validate_scene(sc, slot_index, internal_of_index, [&](const sbc::BeamSlot &r) {
+            SbHostBeam &h = hb[r.slot];
+            h.a = r.a, h.b = r.b, h.da = r.da, h.db = r.db; // endpoints as slots (re-indexed below) and as data indices
+            memcpy(h.f, r.f9, 9 * sizeof(float));
         });
-        Bad first;
-        for (const Bad &c : bad)
-            if (c.kind && c.slot < first.slot) first = c;
-        if (first.kind == 1) SB_FAIL(e, SB_ERR_INVALID, "beam slot %u maps to data index %u >= max_beams", first.slot, first.idx);
-        if (first.kind == 2) SB_FAIL(e, SB_ERR_INVALID, "beam data index %u is mapped by two slots", first.idx);
-        if (first.kind == 3)
-            SB_FAIL(e, SB_ERR_INVALID, "beam slot %u (data index %u) references particle data index %u/%u that no particle slot maps to",
-                    first.slot, first.idx, first.a, first.b);
+        switch (bad.kind) {
+        case sbc::SCENE_OK: break;
+        case sbc::PARTICLE_RANGE: SB_FAIL(e, SB_ERR_INVALID, "particle slot %u maps to data index %u >= max_particles", bad.slot, bad.idx);
+        case sbc::PARTICLE_TWICE: SB_FAIL(e, SB_ERR_INVALID, "particle data index %u is mapped by two slots (%u and %u)", bad.idx, bad.a, bad.slot);
+        case sbc::BEAM_RANGE: SB_FAIL(e, SB_ERR_INVALID, "beam slot %u maps to data index %u >= max_beams", bad.slot, bad.idx);
+        case sbc::BEAM_TWICE: SB_FAIL(e, SB_ERR_INVALID, "beam data index %u is mapped by two slots", bad.idx);
+        default:
+            SB_FAIL(e, SB_ERR_INVALID, "beam slot %u (data index %u) references particle data index %u/%u that no particle slot maps to", bad.slot,
+                    bad.idx, bad.a, bad.b);
+        }
     }
 
     tm.mark("validate + beam records");
@@ -1888,11 +1788,10 @@ static sb_status sb_load_buffers_impl(sb_engine *e, void *metadata, size_t metad
     if (!e) return SB_ERR_INVALID;
     if (!e->loaded) SB_FAIL(e, SB_ERR_STATE, "sb_load_buffers before sb_write_buffers");
     const uint32_t maxP = e->opt.max_particles, maxB = e->opt.max_beams, P = e->P, B = e->B;
-    const uint32_t bstride = beam_stride(e);
-    if (metadata && metadata_bytes < SB_METADATA_BYTES) SB_FAIL(e, SB_ERR_INVALID, "metadata buffer too small");
-    if (mapping && mapping_bytes < (size_t)(maxP + (size_t)maxB) * map_isz(e)) SB_FAIL(e, SB_ERR_INVALID, "mapping buffer too small");
-    if (particles && particles_bytes < (size_t)maxP * SB_PARTICLE_STRIDE) SB_FAIL(e, SB_ERR_INVALID, "particle buffer too small");
-    if (beams && beams_bytes < (size_t)maxB * bstride) SB_FAIL(e, SB_ERR_INVALID, "beam buffer too small");
+    const uint32_t layout = e->opt.layout, bstride = sbc::beam_stride(layout);
+    const sbc::SizeError sz = sbc::check_sizes(layout, maxP, maxB, false, metadata, metadata_bytes, mapping, mapping_bytes, particles, particles_bytes,
+                                               beams, beams_bytes);
+    if (sz.buffer) SB_FAIL(e, SB_ERR_INVALID, "%s buffer too small", sbc::buffer_name(sz.buffer));
     SB_HIP(e, hipSetDevice(e->device));
     SB_HIP(e, hipStreamSynchronize(e->stream)); // engineWorker.ts:554
     SbStageTimer tm;
@@ -1927,7 +1826,7 @@ static sb_status sb_load_buffers_impl(sb_engine *e, void *metadata, size_t metad
                 for (uint32_t s = 0; s < count; s++)
                     if (dead[orig[s]] != g) {
                         if (w != s) {
-                            map_set(e, m, (size_t)maxP + w, map_get(e, m, (size_t)maxP + s));
+                            sbc::map_set(layout, m, (size_t)maxP + w, map_get(e, m, (size_t)maxP + s));
                             orig[w] = orig[s];
                         }
                         w++;
@@ -1961,27 +1860,17 @@ static sb_status sb_load_buffers_impl(sb_engine *e, void *metadata, size_t metad
         SB_TRY(stage_get_bytes(e, ss.data(), e->beams.stress, (size_t)nc * 4));
         tm.mark("readback: beam state to host");
         uint8_t *out = (uint8_t *)beams;
-        const size_t foff = e->opt.layout == SB_LAYOUT_V1 ? 4 : 8;
         sbt::parallel_ranges(sb_user_beams(e), 1 << 16, [&](size_t s0, size_t s1) {
         for (size_t u = s0; u < s1; u++) {
             // every slot that was active at upload is written, dead ones with their last state
             const uint32_t s = sb_user_slot(e, u);
             uint32_t c = e->h_copy_of_slot[s];
             uint32_t idx = map_get(e, e->h_mapping.data(), (size_t)maxP + u);
-            uint8_t *rec = out + (size_t)idx * bstride, *f = rec + foff;
             const SbHostBeam &h = e->h_beams[s];
-            if (e->opt.layout == SB_LAYOUT_V1) {
-                uint32_t pair = (h.da & 0xffffu) | (h.db << 16);
-                memcpy(rec, &pair, 4);
-            } else {
-                memcpy(rec, &h.da, 4);
-                memcpy(rec + 4, &h.db, 4);
-            }
-            memcpy(f, h.f, 9 * sizeof(float));
-            memcpy(f + 4, &t[c], 4);   // target_length
-            memcpy(f + 8, &l[c], 4);   // last_length
-            memcpy(f + 28, &sn[c], 4); // strain
-            memcpy(f + 32, &ss[c], 4); // stress
+            float f[9];
+            memcpy(f, h.f, sizeof f);
+            f[1] = t[c], f[2] = l[c], f[7] = sn[c], f[8] = ss[c]; // target_length, last_length, strain, stress
+            sbc::encode_beam(layout, out + (size_t)idx * bstride, h.da, h.db, f);
         }
         });
         tm.mark("readback: beam records");

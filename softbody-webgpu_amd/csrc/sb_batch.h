@@ -5,6 +5,7 @@
 #include <string>
 
 #include "../../include/softbody.h"
+#include "sb_error.h"
 #include "sb_physics.h"
 
 // ---------------------------------------------------------------- device memory of a batch
@@ -59,26 +60,12 @@ struct sb_batch {
 
 extern thread_local std::string g_batch_create_error; // sb_batch.hip
 
-#define SBB_FAIL(b, code, ...)                                         \
-    do {                                                               \
-        char _buf[512];                                                \
-        snprintf(_buf, sizeof _buf, __VA_ARGS__);                      \
-        if (b) (b)->err = _buf; else g_batch_create_error = _buf;      \
-        return (code);                                                 \
-    } while (0)
-#define SBB_HIP(b, call)                                                                                   \
-    do {                                                                                                   \
-        hipError_t _r = (call);                                                                            \
-        if (_r != hipSuccess) {                                                                            \
-            (void)hipGetLastError();                                                                       \
-            SBB_FAIL(b, _r == hipErrorOutOfMemory ? SB_ERR_OOM : SB_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(_r)); \
-        }                                                                                                  \
-    } while (0)
+inline void sb_set_error(sb_batch *b, const char *text) { (b ? b->err : g_batch_create_error) = text; } // (sb_error.h)
 
 static inline sb_status check_launch(sb_batch *b, const char *what)
 {
     const hipError_t r = hipGetLastError();
-    if (r != hipSuccess) SBB_FAIL(b, SB_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(r));
+    if (r != hipSuccess) SB_FAIL(b, SB_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(r));
     return SB_OK;
 }
 

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "sb_batch.h"
+#include "sb_scene_codec.h"
 
 // ---------------------------------------------------------------- the frame kernel
 // One thread per particle slot (blockDim.x >= max_particles: chosen at create), beams dealt round-robin.
@@ -340,33 +341,33 @@ sb_status sb_batch_destroy(sb_batch *b)
 sb_status sb_batch_create(const sb_batch_options *opts, sb_batch **out)
 {
     sb_batch *none = nullptr;
-    if (!opts || !out) SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: null argument");
+    if (!opts || !out) SB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: null argument");
     *out = nullptr;
     if (opts->struct_size != sizeof(sb_batch_options))
-        SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: sb_batch_options.struct_size %u != %zu", opts->struct_size, sizeof(sb_batch_options));
-    if (opts->n_scenes == 0) SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: n_scenes is 0");
-    if (opts->layout != SB_LAYOUT_V1 && opts->layout != SB_LAYOUT_V2) SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: unknown layout %u", opts->layout);
+        SB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: sb_batch_options.struct_size %u != %zu", opts->struct_size, sizeof(sb_batch_options));
+    if (opts->n_scenes == 0) SB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: n_scenes is 0");
+    if (opts->layout != SB_LAYOUT_V1 && opts->layout != SB_LAYOUT_V2) SB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: unknown layout %u", opts->layout);
     if (opts->layout == SB_LAYOUT_V1 && (opts->max_particles > 65536 || opts->max_beams > 65536))
-        SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: v1 layout holds at most 65536 particles/beams (u16 indices)");
-    if (opts->max_particles == 0) SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: max_particles is 0");
+        SB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: v1 layout holds at most 65536 particles/beams (u16 indices)");
+    if (opts->max_particles == 0) SB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: max_particles is 0");
     if (opts->max_particles > SB_BATCH_MAX_PARTICLES)
-        SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: max_particles %u per scene is above the limit of %u (what one workgroup holds)",
+        SB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: max_particles %u per scene is above the limit of %u (what one workgroup holds)",
                  opts->max_particles, (unsigned)SB_BATCH_MAX_PARTICLES);
     if (opts->max_beams > SB_BATCH_MAX_BEAMS)
-        SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: max_beams %u per scene is above the limit of %u (what one workgroup holds)",
+        SB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: max_beams %u per scene is above the limit of %u (what one workgroup holds)",
                  opts->max_beams, (unsigned)SB_BATCH_MAX_BEAMS);
-    if (opts->collision_mode > SB_COLLIDE_GRID) SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: unknown collision_mode %u", opts->collision_mode);
+    if (opts->collision_mode > SB_COLLIDE_GRID) SB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: unknown collision_mode %u", opts->collision_mode);
     if (!(opts->particle_radius > 0.f) || !(opts->bounds_size > 0.f) || opts->subticks == 0)
-        SBB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: radius, bounds and subticks must be positive");
+        SB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: radius, bounds and subticks must be positive");
     int ndev = 0;
     hipError_t r = hipGetDeviceCount(&ndev);
     if (r != hipSuccess || ndev <= 0) {
         (void)hipGetLastError();
-        SBB_FAIL(none, SB_ERR_NO_DEVICE, "no HIP device available (%s); a batch has no CPU fallback",
+        SB_FAIL(none, SB_ERR_NO_DEVICE, "no HIP device available (%s); a batch has no CPU fallback",
                  r == hipSuccess ? "device count 0" : hipGetErrorString(r));
     }
     if (opts->device_ordinal < 0 || opts->device_ordinal >= ndev)
-        SBB_FAIL(none, SB_ERR_NO_DEVICE, "device_ordinal %d out of range (%d devices)", opts->device_ordinal, ndev);
+        SB_FAIL(none, SB_ERR_NO_DEVICE, "device_ordinal %d out of range (%d devices)", opts->device_ordinal, ndev);
 
     sb_batch *b = new sb_batch();
     b->opt = *opts;
@@ -444,40 +445,14 @@ sb_status sb_batch_create(const sb_batch_options *opts, sb_batch **out)
     return SB_OK;
 }
 
-static inline uint32_t rd32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
-static inline uint32_t map_isz(const sb_batch *b) { return b->opt.layout == SB_LAYOUT_V1 ? 2u : 4u; }
-static inline uint32_t bstride(const sb_batch *b) { return b->opt.layout == SB_LAYOUT_V1 ? SB_BEAM_STRIDE_V1 : SB_BEAM_STRIDE_V2; }
-static inline uint32_t map_get(const sb_batch *b, const uint8_t *m, size_t id)
-{
-    if (b->opt.layout == SB_LAYOUT_V1) {
-        uint16_t v;
-        memcpy(&v, m + 2 * id, 2);
-        return v;
-    }
-    return rd32(m + 4 * id);
-}
-static inline void map_set(const sb_batch *b, uint8_t *m, size_t id, uint32_t val)
-{
-    if (b->opt.layout == SB_LAYOUT_V1) {
-        const uint16_t v = (uint16_t)val;
-        memcpy(m + 2 * id, &v, 2);
-    } else {
-        memcpy(m + 4 * id, &val, 4);
-    }
-}
-
+// buffer presence and sizes against the batch's capacity per scene (sb_scene_codec.h); need_all: an upload
 static sb_status check_sizes(sb_batch *b, const char *who, bool need_all, const void *metadata, size_t metadata_bytes, const void *mapping,
                              size_t mapping_bytes, const void *particles, size_t particles_bytes, const void *beams, size_t beams_bytes)
 {
-    const uint32_t maxP = b->opt.max_particles, maxB = b->opt.max_beams;
-    if (need_all && (!metadata || !mapping || !particles || (!beams && maxB))) SBB_FAIL(b, SB_ERR_INVALID, "%s: null buffer", who);
-    if (metadata && metadata_bytes < SB_METADATA_BYTES) SBB_FAIL(b, SB_ERR_INVALID, "%s: metadata buffer is %zu bytes, need 112", who, metadata_bytes);
-    if (mapping && mapping_bytes < (size_t)(maxP + (size_t)maxB) * map_isz(b))
-        SBB_FAIL(b, SB_ERR_INVALID, "%s: mapping buffer is %zu bytes, need %zu", who, mapping_bytes, (size_t)(maxP + (size_t)maxB) * map_isz(b));
-    if (particles && particles_bytes < (size_t)maxP * SB_PARTICLE_STRIDE)
-        SBB_FAIL(b, SB_ERR_INVALID, "%s: particle buffer is %zu bytes, need %zu", who, particles_bytes, (size_t)maxP * SB_PARTICLE_STRIDE);
-    if (beams && beams_bytes < (size_t)maxB * bstride(b))
-        SBB_FAIL(b, SB_ERR_INVALID, "%s: beam buffer is %zu bytes, need %zu", who, beams_bytes, (size_t)maxB * bstride(b));
+    const sbc::SizeError sz = sbc::check_sizes(b->opt.layout, b->opt.max_particles, b->opt.max_beams, need_all, metadata, metadata_bytes, mapping,
+                                               mapping_bytes, particles, particles_bytes, beams, beams_bytes);
+    if (sz.buffer == sbc::BUF_NULL) SB_FAIL(b, SB_ERR_INVALID, "%s: null buffer", who);
+    if (sz.buffer) SB_FAIL(b, SB_ERR_INVALID, "%s: %s buffer is %zu bytes, need %zu", who, sbc::buffer_name(sz.buffer), sz.have, sz.need);
     return SB_OK;
 }
 
@@ -485,18 +460,17 @@ sb_status sb_batch_write_scene(sb_batch *b, uint32_t first, uint32_t count, cons
                                size_t mapping_bytes, const void *particles, size_t particles_bytes, const void *beams, size_t beams_bytes)
 {
     if (!b) return SB_ERR_INVALID;
-    const uint32_t maxP = b->opt.max_particles, maxB = b->opt.max_beams;
+    const uint32_t maxP = b->opt.max_particles, maxB = b->opt.max_beams, layout = b->opt.layout;
     if (count == 0 || first >= b->opt.n_scenes || count > b->opt.n_scenes - first)
-        SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_write_scene: scenes %u .. %u+%u are not all inside the batch of %u", first, first, count, b->opt.n_scenes);
-    const sb_status cs = check_sizes(b, "sb_batch_write_scene", true, metadata, metadata_bytes, mapping, mapping_bytes, particles, particles_bytes,
-                                     beams, beams_bytes);
-    if (cs != SB_OK) return cs;
+        SB_FAIL(b, SB_ERR_INVALID, "sb_batch_write_scene: scenes %u .. %u+%u are not all inside the batch of %u", first, first, count, b->opt.n_scenes);
+    SB_TRY(check_sizes(b, "sb_batch_write_scene", true, metadata, metadata_bytes, mapping, mapping_bytes, particles, particles_bytes, beams, beams_bytes));
     const uint8_t *md = (const uint8_t *)metadata, *mp = (const uint8_t *)mapping, *pd = (const uint8_t *)particles, *bd = (const uint8_t *)beams;
-    const uint32_t P = rd32(md + 4), B = rd32(md + 24);
-    if (rd32(md + 40) != maxP || rd32(md + 44) != maxB)
-        SBB_FAIL(b, SB_ERR_INVALID, "metadata max_particles/max_beams (%u/%u) differ from the batch's capacity per scene (%u/%u)", rd32(md + 40),
-                 rd32(md + 44), maxP, maxB);
-    if (P > maxP || B > maxB) SBB_FAIL(b, SB_ERR_INVALID, "metadata counts (%u/%u) exceed capacity (%u/%u)", P, B, maxP, maxB);
+    const sbc::Header hd(md);
+    const uint32_t P = hd.P, B = hd.B;
+    if (!hd.capacity_is(maxP, maxB))
+        SB_FAIL(b, SB_ERR_INVALID, "metadata max_particles/max_beams (%u/%u) differ from the batch's capacity per scene (%u/%u)", hd.maxP, hd.maxB,
+                maxP, maxB);
+    if (!hd.counts_fit(maxP, maxB)) SB_FAIL(b, SB_ERR_INVALID, "metadata counts (%u/%u) exceed capacity (%u/%u)", P, B, maxP, maxB);
 
     const SbBatchView &V = b->V;
     std::vector<unsigned char> img((size_t)SB_BM_WORDS * 4u + V.cst_bytes + V.st_bytes, 0);
@@ -508,62 +482,50 @@ sb_status sb_batch_write_scene(sb_batch *b, uint32_t first, uint32_t count, cons
     memcpy(meta, md, SB_METADATA_BYTES);
     meta[SB_BM_B0] = B;
     meta[SB_BM_LOADED] = 1u;
-    for (uint32_t s = 0; s < maxP; s++) pmap[s] = map_get(b, mp, s);
-    for (uint32_t s = 0; s < maxB; s++) bmap[s] = map_get(b, mp, (size_t)maxP + s);
+    for (uint32_t s = 0; s < maxP; s++) pmap[s] = sbc::map_get(layout, mp, s);
+    for (uint32_t s = 0; s < maxB; s++) bmap[s] = sbc::map_get(layout, mp, (size_t)maxP + s);
     memcpy(st + V.o_part, pd, (size_t)maxP * SB_PARTICLE_STRIDE);
-    // particles: slot -> data index must be a partial injection
-    std::vector<uint32_t> slot_of(maxP, 0xFFFFFFFFu);
-    for (uint32_t s = 0; s < P; s++) {
-        const uint32_t idx = pmap[s];
-        if (idx >= maxP) SBB_FAIL(b, SB_ERR_INVALID, "particle slot %u maps to data index %u >= max_particles", s, idx);
-        if (slot_of[idx] != 0xFFFFFFFFu) SBB_FAIL(b, SB_ERR_INVALID, "particle data index %u is mapped by two slots (%u and %u)", idx, slot_of[idx], s);
-        slot_of[idx] = s;
-        pex[idx] = 1;
-    }
-    // beams: slot -> record; endpoints must be active particles
-    const size_t foff = b->opt.layout == SB_LAYOUT_V1 ? 4 : 8;
-    for (uint32_t s = 0; s < B; s++) {
-        const uint32_t idx = bmap[s];
-        if (idx >= maxB) SBB_FAIL(b, SB_ERR_INVALID, "beam slot %u maps to data index %u >= max_beams", s, idx);
-        if (bex[idx]) SBB_FAIL(b, SB_ERR_INVALID, "beam data index %u is mapped by two slots", idx);
-        const uint8_t *rec = bd + (size_t)idx * bstride(b);
-        uint32_t a, e;
-        if (b->opt.layout == SB_LAYOUT_V1) { // engineMapping.ts:183-186, compute.wgsl:99-100
-            const uint32_t pair = rd32(rec);
-            a = pair & 0xffffu;
-            e = pair >> 16;
-        } else {
-            a = rd32(rec);
-            e = rd32(rec + 4);
-        }
-        if (a >= maxP || e >= maxP || slot_of[a] == 0xFFFFFFFFu || slot_of[e] == 0xFFFFFFFFu)
-            SBB_FAIL(b, SB_ERR_INVALID, "beam slot %u (data index %u) references particle data index %u/%u that no particle slot maps to", s, idx, a, e);
+    // validate (sb_scene_codec.h) and fill the image's beam rows in the same walk
+    std::vector<uint32_t> data_of_slot, slot_of;
+    const sbc::Scene sc{layout, maxP, maxB, P, B, mp, bd};
+    const sbc::SceneError bad = sbc::validate_scene(sc, data_of_slot, slot_of, [&](const sbc::BeamSlot &r) {
         float f[9]; // length, target_length, last_length, spring, damp, yield_strain, strain_break_limit, strain, stress
-        memcpy(f, rec + foff, sizeof f);
-        bex[idx] = balive[idx] = 1;
-        bword[idx] = slot_of[a] | (slot_of[e] << 16);
-        float *m = bmat + (size_t)SB_BATCH_MAT_ROW * idx, *q = bstate + 4u * (size_t)idx;
+        memcpy(f, r.f9, sizeof f);
+        bex[r.idx] = balive[r.idx] = 1;
+        bword[r.idx] = r.a | (r.b << 16);
+        float *m = bmat + (size_t)SB_BATCH_MAT_ROW * r.idx, *q = bstate + 4u * (size_t)r.idx;
         m[0] = f[0], m[1] = f[3], m[2] = f[4], m[3] = f[5], m[4] = f[6];
         m[5] = 1.0f / f[0]; // one IEEE divide per beam at upload (compute.wgsl:112 pinned as x * (1 / length))
         q[0] = f[1], q[1] = f[2], q[2] = f[7], q[3] = f[8];
+    });
+    switch (bad.kind) {
+    case sbc::SCENE_OK: break;
+    case sbc::PARTICLE_RANGE: SB_FAIL(b, SB_ERR_INVALID, "particle slot %u maps to data index %u >= max_particles", bad.slot, bad.idx);
+    case sbc::PARTICLE_TWICE: SB_FAIL(b, SB_ERR_INVALID, "particle data index %u is mapped by two slots (%u and %u)", bad.idx, bad.a, bad.slot);
+    case sbc::BEAM_RANGE: SB_FAIL(b, SB_ERR_INVALID, "beam slot %u maps to data index %u >= max_beams", bad.slot, bad.idx);
+    case sbc::BEAM_TWICE: SB_FAIL(b, SB_ERR_INVALID, "beam data index %u is mapped by two slots", bad.idx);
+    default:
+        SB_FAIL(b, SB_ERR_INVALID, "beam slot %u (data index %u) references particle data index %u/%u that no particle slot maps to", bad.slot, bad.idx,
+                bad.a, bad.b);
     }
-    SBB_HIP(b, hipSetDevice(b->device));
-    SBB_HIP(b, hipMemcpyAsync(b->stage, img.data(), img.size(), hipMemcpyHostToDevice, b->stream));
+    for (uint32_t idx : data_of_slot) pex[idx] = 1;
+    SB_HIP(b, hipSetDevice(b->device));
+    SB_HIP(b, hipMemcpyAsync(b->stage, img.data(), img.size(), hipMemcpyHostToDevice, b->stream));
     k_batch_replicate<<<count, SBB_BLOCK, 0, b->stream>>>(V, (const uint4 *)(b->stage + SB_BM_WORDS * 4u),
                                                           (const uint4 *)(b->stage + SB_BM_WORDS * 4u + V.cst_bytes), (const uint32_t *)b->stage, first,
                                                           count);
     const sb_status ls = check_launch(b, "sb_batch_write_scene");
-    SBB_HIP(b, hipStreamSynchronize(b->stream)); // copy semantics: `img` and the caller's buffers are free again
+    SB_HIP(b, hipStreamSynchronize(b->stream)); // copy semantics: `img` and the caller's buffers are free again
     return ls;
 }
 
 sb_status sb_batch_write_user_input(sb_batch *b, const void *bytes32)
 {
     if (!b) return SB_ERR_INVALID;
-    if (!bytes32) SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_write_user_input: null buffer");
+    if (!bytes32) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_write_user_input: null buffer");
     SbBatchWords8 w;
     memcpy(w.w, bytes32, SB_USER_INPUT_BYTES);
-    SBB_HIP(b, hipSetDevice(b->device));
+    SB_HIP(b, hipSetDevice(b->device));
     const uint32_t n = b->opt.n_scenes;
     k_batch_meta8<<<cdivb(n * 8u, SBB_BLOCK), SBB_BLOCK, 0, b->stream>>>(b->V, 0u, n, SB_USER_INPUT_OFFSET / 4u, nullptr, w);
     return check_launch(b, "sb_batch_write_user_input");
@@ -572,8 +534,8 @@ sb_status sb_batch_write_user_input(sb_batch *b, const void *bytes32)
 sb_status sb_batch_write_user_input_device(sb_batch *b, const void *device_bytes)
 {
     if (!b) return SB_ERR_INVALID;
-    if (!device_bytes || ((uintptr_t)device_bytes & 3u)) SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_write_user_input_device: null or misaligned device buffer");
-    SBB_HIP(b, hipSetDevice(b->device));
+    if (!device_bytes || ((uintptr_t)device_bytes & 3u)) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_write_user_input_device: null or misaligned device buffer");
+    SB_HIP(b, hipSetDevice(b->device));
     const uint32_t n = b->opt.n_scenes;
     k_batch_meta8<<<cdivb(n * 8u, SBB_BLOCK), SBB_BLOCK, 0, b->stream>>>(b->V, 0u, n, SB_USER_INPUT_OFFSET / 4u, (const uint32_t *)device_bytes,
                                                                          SbBatchWords8{});
@@ -583,13 +545,13 @@ sb_status sb_batch_write_user_input_device(sb_batch *b, const void *device_bytes
 sb_status sb_batch_set_physics_constants(sb_batch *b, uint32_t first, uint32_t count, const float c8[8])
 {
     if (!b) return SB_ERR_INVALID;
-    if (!c8) SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_set_physics_constants: null buffer");
+    if (!c8) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_set_physics_constants: null buffer");
     if (count == 0 || first >= b->opt.n_scenes || count > b->opt.n_scenes - first)
-        SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_set_physics_constants: scenes %u .. %u+%u are not all inside the batch of %u", first, first, count,
+        SB_FAIL(b, SB_ERR_INVALID, "sb_batch_set_physics_constants: scenes %u .. %u+%u are not all inside the batch of %u", first, first, count,
                  b->opt.n_scenes);
     SbBatchWords8 w;
     memcpy(w.w, c8, 32);
-    SBB_HIP(b, hipSetDevice(b->device));
+    SB_HIP(b, hipSetDevice(b->device));
     k_batch_meta8<<<cdivb(count * 8u, SBB_BLOCK), SBB_BLOCK, 0, b->stream>>>(b->V, first, count, SB_BM_CONSTS, nullptr, w);
     return check_launch(b, "sb_batch_set_physics_constants");
 }
@@ -603,7 +565,7 @@ static sb_status launch_frame(sb_batch *b, uint32_t n_sub, uint32_t do_delete)
 sb_status sb_batch_frame(sb_batch *b, uint32_t n_frames)
 {
     if (!b) return SB_ERR_INVALID;
-    SBB_HIP(b, hipSetDevice(b->device));
+    SB_HIP(b, hipSetDevice(b->device));
     for (uint32_t f = 0; f < n_frames; f++) { // engineWorker.ts:646-665
         const sb_status s = launch_frame(b, b->subticks, 1u);
         if (s != SB_OK) return s;
@@ -617,7 +579,7 @@ sb_status sb_batch_step(sb_batch *b, uint32_t n_substeps)
 {
     if (!b) return SB_ERR_INVALID;
     if (n_substeps == 0) return SB_OK;
-    SBB_HIP(b, hipSetDevice(b->device));
+    SB_HIP(b, hipSetDevice(b->device));
     const sb_status s = launch_frame(b, n_substeps, 0u);
     if (s == SB_OK) b->substeps_done += n_substeps;
     return s;
@@ -626,14 +588,14 @@ sb_status sb_batch_step(sb_batch *b, uint32_t n_substeps)
 sb_status sb_batch_delete_pass(sb_batch *b)
 {
     if (!b) return SB_ERR_INVALID;
-    SBB_HIP(b, hipSetDevice(b->device));
+    SB_HIP(b, hipSetDevice(b->device));
     return launch_frame(b, 0u, 1u);
 }
 
 sb_status sb_batch_reset_device(sb_batch *b, const void *device_mask_u8)
 {
     if (!b) return SB_ERR_INVALID;
-    SBB_HIP(b, hipSetDevice(b->device));
+    SB_HIP(b, hipSetDevice(b->device));
     k_batch_reset<<<b->opt.n_scenes, SBB_BLOCK, 0, b->stream>>>(b->V, (const unsigned char *)device_mask_u8);
     return check_launch(b, "sb_batch_reset_device");
 }
@@ -642,9 +604,9 @@ sb_status sb_batch_read_state_device(sb_batch *b, void *device_particles, void *
 {
     if (!b) return SB_ERR_INVALID;
     if (((uintptr_t)device_particles & 3u) || ((uintptr_t)device_beams & 3u))
-        SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_read_state_device: particle and beam buffers must be 4-byte aligned");
+        SB_FAIL(b, SB_ERR_INVALID, "sb_batch_read_state_device: particle and beam buffers must be 4-byte aligned");
     if (!device_particles && !device_beams && !device_beam_alive) return SB_OK;
-    SBB_HIP(b, hipSetDevice(b->device));
+    SB_HIP(b, hipSetDevice(b->device));
     k_batch_export<<<b->opt.n_scenes, SBB_BLOCK, 0, b->stream>>>(b->V, (float *)device_particles, (float *)device_beams, (unsigned char *)device_beam_alive);
     return check_launch(b, "sb_batch_read_state_device");
 }
@@ -653,8 +615,8 @@ sb_status sb_batch_write_particles_device(sb_batch *b, const void *device_partic
 {
     if (!b) return SB_ERR_INVALID;
     if (!device_particles || ((uintptr_t)device_particles & 3u))
-        SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_write_particles_device: null or misaligned device buffer");
-    SBB_HIP(b, hipSetDevice(b->device));
+        SB_FAIL(b, SB_ERR_INVALID, "sb_batch_write_particles_device: null or misaligned device buffer");
+    SB_HIP(b, hipSetDevice(b->device));
     k_batch_import<<<b->opt.n_scenes, SBB_BLOCK, 0, b->stream>>>(b->V, (const float *)device_particles);
     return check_launch(b, "sb_batch_write_particles_device");
 }
@@ -663,20 +625,18 @@ sb_status sb_batch_load_scene(sb_batch *b, uint32_t scene, void *metadata, size_
                               size_t particles_bytes, void *beams, size_t beams_bytes)
 {
     if (!b) return SB_ERR_INVALID;
-    if (scene >= b->opt.n_scenes) SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_load_scene: scene %u is not inside the batch of %u", scene, b->opt.n_scenes);
-    const sb_status cs = check_sizes(b, "sb_batch_load_scene", false, metadata, metadata_bytes, mapping, mapping_bytes, particles, particles_bytes, beams,
-                                     beams_bytes);
-    if (cs != SB_OK) return cs;
+    if (scene >= b->opt.n_scenes) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_load_scene: scene %u is not inside the batch of %u", scene, b->opt.n_scenes);
+    SB_TRY(check_sizes(b, "sb_batch_load_scene", false, metadata, metadata_bytes, mapping, mapping_bytes, particles, particles_bytes, beams, beams_bytes));
     const SbBatchView &V = b->V;
     const uint32_t maxP = V.maxP, maxB = V.maxB;
-    SBB_HIP(b, hipSetDevice(b->device));
-    SBB_HIP(b, hipStreamSynchronize(b->stream));
+    SB_HIP(b, hipSetDevice(b->device));
+    SB_HIP(b, hipStreamSynchronize(b->stream));
     uint32_t meta[SB_BM_WORDS];
     std::vector<unsigned char> cst(V.cst_bytes), st(V.st_bytes);
-    SBB_HIP(b, hipMemcpy(meta, V.meta + (size_t)scene * SB_BM_WORDS, sizeof meta, hipMemcpyDeviceToHost));
-    if (meta[SB_BM_LOADED] == 0u) SBB_FAIL(b, SB_ERR_STATE, "sb_batch_load_scene: scene %u was never uploaded", scene);
-    SBB_HIP(b, hipMemcpy(cst.data(), V.cst + (size_t)scene * V.cst_bytes, V.cst_bytes, hipMemcpyDeviceToHost));
-    SBB_HIP(b, hipMemcpy(st.data(), V.st + (size_t)scene * V.st_bytes, V.st_bytes, hipMemcpyDeviceToHost));
+    SB_HIP(b, hipMemcpy(meta, V.meta + (size_t)scene * SB_BM_WORDS, sizeof meta, hipMemcpyDeviceToHost));
+    if (meta[SB_BM_LOADED] == 0u) SB_FAIL(b, SB_ERR_STATE, "sb_batch_load_scene: scene %u was never uploaded", scene);
+    SB_HIP(b, hipMemcpy(cst.data(), V.cst + (size_t)scene * V.cst_bytes, V.cst_bytes, hipMemcpyDeviceToHost));
+    SB_HIP(b, hipMemcpy(st.data(), V.st + (size_t)scene * V.st_bytes, V.st_bytes, hipMemcpyDeviceToHost));
     const uint32_t *pmap = (const uint32_t *)(cst.data() + V.o_pmap), *bword = (const uint32_t *)(cst.data() + V.o_bword);
     const uint32_t *bmap = (const uint32_t *)(st.data() + V.o_bmap);
     const float *bmat = (const float *)(cst.data() + V.o_bmat), *bstate = (const float *)(st.data() + V.o_bstate);
@@ -685,28 +645,20 @@ sb_status sb_batch_load_scene(sb_batch *b, uint32_t scene, void *metadata, size_
     if (metadata) memcpy(metadata, meta, SB_METADATA_BYTES);
     if (mapping) {
         uint8_t *m = (uint8_t *)mapping;
-        for (uint32_t s = 0; s < maxP; s++) map_set(b, m, s, pmap[s]);
-        for (uint32_t s = 0; s < maxB; s++) map_set(b, m, (size_t)maxP + s, bmap[s]);
+        for (uint32_t s = 0; s < maxP; s++) sbc::map_set(b->opt.layout, m, s, pmap[s]);
+        for (uint32_t s = 0; s < maxB; s++) sbc::map_set(b->opt.layout, m, (size_t)maxP + s, bmap[s]);
     }
     if (particles)
         for (uint32_t s = 0; s < P; s++)
             memcpy((uint8_t *)particles + (size_t)pmap[s] * SB_PARTICLE_STRIDE, st.data() + V.o_part + (size_t)pmap[s] * SB_PARTICLE_STRIDE, SB_PARTICLE_STRIDE);
     if (beams) {
-        const size_t foff = b->opt.layout == SB_LAYOUT_V1 ? 4 : 8;
+        const uint32_t stride = sbc::beam_stride(b->opt.layout);
         for (uint32_t idx = 0; idx < maxB; idx++) { // every beam of the upload, removed ones with their last state
             if (!bex[idx]) continue;
-            uint8_t *rec = (uint8_t *)beams + (size_t)idx * bstride(b);
-            const uint32_t da = pmap[bword[idx] & 0xffffu], db = pmap[bword[idx] >> 16];
-            if (b->opt.layout == SB_LAYOUT_V1) {
-                const uint32_t pair = (da & 0xffffu) | (db << 16);
-                memcpy(rec, &pair, 4);
-            } else {
-                memcpy(rec, &da, 4);
-                memcpy(rec + 4, &db, 4);
-            }
+            const uint32_t da = pmap[bword[idx] & 0xffffu], db = pmap[bword[idx] >> 16]; // (the batch's own endpoint word: slots)
             const float *m = bmat + (size_t)SB_BATCH_MAT_ROW * idx, *q = bstate + 4u * (size_t)idx;
             const float f[9] = {m[0], q[0], q[1], m[1], m[2], m[3], m[4], q[2], q[3]};
-            memcpy(rec + foff, f, sizeof f);
+            sbc::encode_beam(b->opt.layout, (uint8_t *)beams + (size_t)idx * stride, da, db, f);
         }
     }
     return SB_OK;
@@ -715,15 +667,15 @@ sb_status sb_batch_load_scene(sb_batch *b, uint32_t scene, void *metadata, size_
 sb_status sb_batch_sync(sb_batch *b)
 {
     if (!b) return SB_ERR_INVALID;
-    SBB_HIP(b, hipSetDevice(b->device));
-    SBB_HIP(b, hipStreamSynchronize(b->stream));
+    SB_HIP(b, hipSetDevice(b->device));
+    SB_HIP(b, hipStreamSynchronize(b->stream));
     return SB_OK;
 }
 
 sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream)
 {
     if (!b) return SB_ERR_INVALID;
-    if (!hip_stream) SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_get_stream: null argument");
+    if (!hip_stream) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_get_stream: null argument");
     *hip_stream = (void *)b->stream;
     return SB_OK;
 }
@@ -731,7 +683,7 @@ sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream)
 sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value)
 {
     if (!b) return SB_ERR_INVALID;
-    if (!key || !value) SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_get_info: null argument");
+    if (!key || !value) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_get_info: null argument");
     const std::string k(key);
     if (k == "n_scenes") *value = b->opt.n_scenes;
     else if (k == "scene_max_particles") *value = SB_BATCH_MAX_PARTICLES;
@@ -747,6 +699,6 @@ sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value)
     else if (k == "frames_done") *value = b->frames_done;
     else if (k == "substeps_done") *value = b->substeps_done;
     else if (sbb_render_info(b, key, value)) return SB_OK;
-    else SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_get_info: unknown key '%s'", key);
+    else SB_FAIL(b, SB_ERR_INVALID, "sb_batch_get_info: unknown key '%s'", key);
     return SB_OK;
 }

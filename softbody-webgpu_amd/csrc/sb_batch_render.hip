@@ -203,16 +203,16 @@ static inline uint32_t sbbr_lds_fixed(uint32_t maxP, uint32_t maxB) { return max
 static sb_status sbbr_options(sb_batch *b, const char *who, const sb_batch_render_options *o, SbrArgs &a, uint32_t &first, uint32_t &count)
 {
     if (o && o->struct_size != 0 && o->struct_size != sizeof(sb_batch_render_options))
-        SBB_FAIL(b, SB_ERR_INVALID, "%s: sb_batch_render_options.struct_size %u != %zu", who, o->struct_size, sizeof(sb_batch_render_options));
+        SB_FAIL(b, SB_ERR_INVALID, "%s: sb_batch_render_options.struct_size %u != %zu", who, o->struct_size, sizeof(sb_batch_render_options));
     const bool given = o && o->struct_size;
     const uint32_t res = given && o->resolution ? o->resolution : 64u;
     if (res > SB_BATCH_RENDER_MAX_RESOLUTION)
-        SBB_FAIL(b, SB_ERR_INVALID, "%s: resolution %u above %u", who, res, (unsigned)SB_BATCH_RENDER_MAX_RESOLUTION);
+        SB_FAIL(b, SB_ERR_INVALID, "%s: resolution %u above %u", who, res, (unsigned)SB_BATCH_RENDER_MAX_RESOLUTION);
     const uint32_t n = b->opt.n_scenes;
     first = given ? o->first : 0u;
     count = given ? o->count : 0u;
     if (first >= n || count > n - first)
-        SBB_FAIL(b, SB_ERR_INVALID, "%s: scenes %u .. %u+%u are not all inside the batch of %u", who, first, first, count, n);
+        SB_FAIL(b, SB_ERR_INVALID, "%s: scenes %u .. %u+%u are not all inside the batch of %u", who, first, first, count, n);
     if (count == 0u) count = n - first;
     a.S = given && o->bounds_size != 0.0 ? o->bounds_size : (double)b->opt.bounds_size;
     a.r = given && o->particle_radius != 0.0 ? o->particle_radius : (double)b->opt.particle_radius;
@@ -232,7 +232,7 @@ static sb_status sbbr_launch(sb_batch *b, const SbrArgs &a, uint32_t first, uint
     budget = std::min(std::max(budget, fixed + row), SBBR_LDS_LIMIT);
     const uint32_t rows = std::min(res, (budget - fixed) / row), bands = cdivb(res, rows), lds = fixed + rows * row;
     if (!r.attr_set) {
-        SBB_HIP(b, hipFuncSetAttribute((const void *)k_batch_render, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SBBR_LDS_LIMIT));
+        SB_HIP(b, hipFuncSetAttribute((const void *)k_batch_render, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SBBR_LDS_LIMIT));
         r.attr_set = true;
     }
     hipLaunchKernelGGL(k_batch_render, dim3(count * bands), dim3(SBBR_THREADS), lds, b->stream, b->V, a, first, bands, rows, d_rgb);
@@ -282,8 +282,8 @@ sb_status sb_batch_render_device(sb_batch *b, const sb_batch_render_options *opt
     uint32_t first, count;
     const sb_status s = sbbr_options(b, "sb_batch_render_device", opts, a, first, count);
     if (s != SB_OK) return s;
-    if (!device_rgb) SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_render_device: null destination");
-    SBB_HIP(b, hipSetDevice(b->device));
+    if (!device_rgb) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_render_device: null destination");
+    SB_HIP(b, hipSetDevice(b->device));
     return sbbr_launch(b, a, first, count, (uint8_t *)device_rgb);
 }
 
@@ -294,27 +294,27 @@ sb_status sb_batch_render_scene(sb_batch *b, uint32_t scene, const sb_batch_rend
     uint32_t first, count; // (of the options: the scene argument decides here)
     const sb_status s = sbbr_options(b, "sb_batch_render_scene", opts, a, first, count);
     if (s != SB_OK) return s;
-    if (scene >= b->opt.n_scenes) SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_render_scene: scene %u is not inside the batch of %u", scene, b->opt.n_scenes);
+    if (scene >= b->opt.n_scenes) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_render_scene: scene %u is not inside the batch of %u", scene, b->opt.n_scenes);
     const size_t bytes = (size_t)a.nres * a.nres * 3u;
-    if (!rgb) SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_render_scene: null destination");
-    if (rgb_bytes < bytes) SBB_FAIL(b, SB_ERR_INVALID, "sb_batch_render_scene: buffer of %zu bytes, the picture needs %zu", rgb_bytes, bytes);
-    SBB_HIP(b, hipSetDevice(b->device));
-    SBB_HIP(b, hipStreamSynchronize(b->stream));
+    if (!rgb) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_render_scene: null destination");
+    if (rgb_bytes < bytes) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_render_scene: buffer of %zu bytes, the picture needs %zu", rgb_bytes, bytes);
+    SB_HIP(b, hipSetDevice(b->device));
+    SB_HIP(b, hipStreamSynchronize(b->stream));
     uint32_t loaded = 0;
-    SBB_HIP(b, hipMemcpy(&loaded, b->V.meta + (size_t)scene * SB_BM_WORDS + SB_BM_LOADED, 4, hipMemcpyDeviceToHost));
-    if (loaded == 0u) SBB_FAIL(b, SB_ERR_STATE, "sb_batch_render_scene: scene %u was never uploaded", scene);
+    SB_HIP(b, hipMemcpy(&loaded, b->V.meta + (size_t)scene * SB_BM_WORDS + SB_BM_LOADED, 4, hipMemcpyDeviceToHost));
+    if (loaded == 0u) SB_FAIL(b, SB_ERR_STATE, "sb_batch_render_scene: scene %u was never uploaded", scene);
     if (!b->render) b->render = new SbBatchRender();
     SbBatchRender &r = *b->render;
     if (r.cap_rgb < bytes) {
-        if (r.d_rgb) SBB_HIP(b, hipFree(r.d_rgb)); // (the stream is idle)
+        if (r.d_rgb) SB_HIP(b, hipFree(r.d_rgb)); // (the stream is idle)
         r.d_rgb = nullptr, r.cap_rgb = 0;
-        SBB_HIP(b, hipMalloc((void **)&r.d_rgb, std::max<size_t>(bytes, 1)));
+        SB_HIP(b, hipMalloc((void **)&r.d_rgb, std::max<size_t>(bytes, 1)));
         r.cap_rgb = bytes;
     }
     const sb_status ls = sbbr_launch(b, a, scene, 1u, r.d_rgb);
     if (ls != SB_OK) return ls;
-    SBB_HIP(b, hipMemcpyAsync(rgb, r.d_rgb, bytes, hipMemcpyDeviceToHost, b->stream));
-    SBB_HIP(b, hipStreamSynchronize(b->stream));
+    SB_HIP(b, hipMemcpyAsync(rgb, r.d_rgb, bytes, hipMemcpyDeviceToHost, b->stream));
+    SB_HIP(b, hipStreamSynchronize(b->stream));
     return SB_OK;
 }
 

@@ -12,6 +12,8 @@
 #include "sb_physics.h"
 #include "sb_tiling.h"
 #include "sb_blocking.h"
+#include "sb_error.h"
+#include "sb_scene_codec.h"
 
 // Device SoA of the beam working set.  One entry per beam COPY: the atomic path keeps one
 // copy per active slot (slot order); the tiled path keeps per-tile slices in which a beam
@@ -253,19 +255,11 @@ struct sb_engine {
     std::vector<std::pair<void *, size_t>> pool_used, pool_free; // device blocks of the scene / kept for the next upload (sb_api.hip dev_alloc)
 };
 
-// mapping entries of the caller's layout (u16 in v1, u32 in v2)
-static inline uint32_t map_isz(const sb_engine *e) { return e->opt.layout == SB_LAYOUT_V1 ? 2 : 4; }
-static inline uint32_t map_get(const sb_engine *e, const uint8_t *m, size_t id)
-{
-    if (e->opt.layout == SB_LAYOUT_V1) {
-        uint16_t v;
-        memcpy(&v, m + 2 * id, 2);
-        return v;
-    }
-    uint32_t v;
-    memcpy(&v, m + 4 * id, 4);
-    return v;
-}
+inline void sb_set_error(sb_engine *e, const char *text) { if (e) e->err = text; else sb_set_create_error(text); } // (sb_error.h)
+
+// mapping entries of the caller's layout (sb_scene_codec.h)
+static inline uint32_t map_isz(const sb_engine *e) { return sbc::map_item_bytes(e->opt.layout); }
+static inline uint32_t map_get(const sb_engine *e, const uint8_t *m, size_t id) { return sbc::map_get(e->opt.layout, m, id); }
 // the caller's beam slots (those of the latest upload) -> the engine's own (h_user_slot above)
 static inline uint32_t sb_user_beams(const sb_engine *e) { return e->h_user_slot.empty() ? e->B : (uint32_t)e->h_user_slot.size(); }
 static inline uint32_t sb_user_slot(const sb_engine *e, size_t u) { return e->h_user_slot.empty() ? (uint32_t)u : e->h_user_slot[u]; }

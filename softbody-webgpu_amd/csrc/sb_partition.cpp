@@ -24,8 +24,8 @@
 #include <vector>
 
 #include "../../include/softbody.h"
-
-void sb_set_create_error(const char *msg); // sb_api.hip: what sb_last_error(NULL) returns
+#include "sb_error.h"
+#include "sb_scene_codec.h"
 
 namespace {
 
@@ -57,16 +57,9 @@ struct sb_partition {
     float reach = 0.0f, longest_beam = 0.0f;
 };
 
-static inline uint32_t rd32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
 static inline float rdf(const uint8_t *p) { float v; memcpy(&v, p, 4); return v; }
 
-#define PFAIL(code, ...)                                 \
-    do {                                                 \
-        char _b[400];                                    \
-        snprintf(_b, sizeof _b, __VA_ARGS__);            \
-        sb_set_create_error(_b);                         \
-        return (code);                                   \
-    } while (0)
+#define PFAIL(code, ...) SB_FAIL(nullptr, code, __VA_ARGS__)
 
 static sb_status partition_create_impl(uint32_t layout, uint32_t maxP, uint32_t maxB, const uint8_t *md, const uint8_t *mp,
                                        const uint8_t *pd, const uint8_t *bd, uint32_t world, uint32_t depth, float reach,
@@ -75,45 +68,31 @@ static sb_status partition_create_impl(uint32_t layout, uint32_t maxP, uint32_t 
     if (layout != SB_LAYOUT_V1 && layout != SB_LAYOUT_V2) PFAIL(SB_ERR_INVALID, "sb_partition_create: unknown layout %u", layout);
     if (!world || world > 4096) PFAIL(SB_ERR_INVALID, "sb_partition_create: world %u", world);
     if (world > 1 && depth == 0) PFAIL(SB_ERR_INVALID, "sb_partition_create: depth 0 (a ghost zone at least one beam hop deep is needed)");
-    const uint32_t P = rd32(md + 4), B = rd32(md + 24);
-    if (P > maxP || B > maxB) PFAIL(SB_ERR_INVALID, "sb_partition_create: counts (%u/%u) exceed capacity (%u/%u)", P, B, maxP, maxB);
-    const uint32_t bstride = layout == SB_LAYOUT_V1 ? SB_BEAM_STRIDE_V1 : SB_BEAM_STRIDE_V2, isz = layout == SB_LAYOUT_V1 ? 2 : 4;
-    auto map_get = [&](size_t id) -> uint32_t {
-        if (isz == 2) { uint16_t v; memcpy(&v, mp + 2 * id, 2); return v; }
-        return rd32(mp + 4 * id);
-    };
+    const sbc::Header hd(md);
+    const uint32_t P = hd.P, B = hd.B;
+    if (!hd.counts_fit(maxP, maxB)) PFAIL(SB_ERR_INVALID, "sb_partition_create: counts (%u/%u) exceed capacity (%u/%u)", P, B, maxP, maxB);
     std::unique_ptr<sb_partition> holder(new sb_partition()); // released to the caller on success only: an exception or an
     sb_partition *pt = holder.get();                          // early return below frees it
     pt->layout = layout; pt->world = world; pt->depth = depth; pt->P = P; pt->B = B; pt->maxP = maxP; pt->maxB = maxB;
     pt->reach = reach;
     pt->metadata.assign(md, md + SB_METADATA_BYTES);
     pt->particles.assign(pd, pd + (size_t)maxP * SB_PARTICLE_STRIDE);
-    pt->beams.assign(bd, bd + (size_t)maxB * bstride);
-    pt->p_data_of_slot.resize(P);
+    pt->beams.assign(bd, bd + (size_t)maxB * sbc::beam_stride(layout));
     pt->b_data_of_slot.resize(B);
-    std::vector<uint32_t> slot_of_data(maxP, 0xFFFFFFFFu);
-    for (uint32_t s = 0; s < P; s++) {
-        const uint32_t idx = map_get(s);
-        if (idx >= maxP || slot_of_data[idx] != 0xFFFFFFFFu) {
-            PFAIL(SB_ERR_INVALID, "sb_partition_create: particle slot %u maps to a bad or doubly mapped data index %u", s, idx);
-        }
-        slot_of_data[idx] = s;
-        pt->p_data_of_slot[s] = idx;
-    }
-    std::vector<uint32_t> ba(B), bb(B); // endpoints as particle SLOTS
-    for (uint32_t s = 0; s < B; s++) {
-        const uint32_t idx = map_get((size_t)maxP + s);
-        if (idx >= maxB) { PFAIL(SB_ERR_INVALID, "sb_partition_create: beam slot %u maps to data index %u >= max_beams", s, idx); }
-        pt->b_data_of_slot[s] = idx;
-        const uint8_t *rec = pt->beams.data() + (size_t)idx * bstride;
-        uint32_t a, b;
-        if (layout == SB_LAYOUT_V1) { const uint32_t pr = rd32(rec); a = pr & 0xffffu; b = pr >> 16; }
-        else { a = rd32(rec); b = rd32(rec + 4); }
-        if (a >= maxP || b >= maxP || slot_of_data[a] == 0xFFFFFFFFu || slot_of_data[b] == 0xFFFFFFFFu) {
-            PFAIL(SB_ERR_INVALID, "sb_partition_create: beam slot %u references particle data index %u/%u that no slot maps to", s, a, b);
-        }
-        ba[s] = slot_of_data[a];
-        bb[s] = slot_of_data[b];
+    std::vector<uint32_t> slot_of_data, ba(B), bb(B); // particle data index -> slot; the beams' endpoints as particle SLOTS
+    const sbc::Scene sc{layout, maxP, maxB, P, B, mp, pt->beams.data()};
+    const sbc::SceneError bad = sbc::validate_scene(sc, pt->p_data_of_slot, slot_of_data, [&](const sbc::BeamSlot &r) {
+        pt->b_data_of_slot[r.slot] = r.idx;
+        ba[r.slot] = r.a;
+        bb[r.slot] = r.b;
+    });
+    switch (bad.kind) {
+    case sbc::SCENE_OK: break;
+    case sbc::PARTICLE_RANGE:
+    case sbc::PARTICLE_TWICE: PFAIL(SB_ERR_INVALID, "sb_partition_create: particle slot %u maps to a bad or doubly mapped data index %u", bad.slot, bad.idx);
+    case sbc::BEAM_RANGE: PFAIL(SB_ERR_INVALID, "sb_partition_create: beam slot %u maps to data index %u >= max_beams", bad.slot, bad.idx);
+    case sbc::BEAM_TWICE: PFAIL(SB_ERR_INVALID, "sb_partition_create: beam slot %u maps to data index %u that another slot maps to", bad.slot, bad.idx);
+    default: PFAIL(SB_ERR_INVALID, "sb_partition_create: beam slot %u references particle data index %u/%u that no slot maps to", bad.slot, bad.a, bad.b);
     }
     // owner of every particle (by slot): equal-population slabs in x order
     std::vector<float> x(P);
@@ -320,17 +299,14 @@ sb_status sb_partition_rank_scene(const sb_partition *p, uint32_t rank, uint32_t
         sb_set_create_error("sb_partition_rank_scene: capacities do not hold the rank's scene");
         return SB_ERR_INVALID;
     }
-    const uint32_t bstride = p->layout == SB_LAYOUT_V1 ? SB_BEAM_STRIDE_V1 : SB_BEAM_STRIDE_V2, isz = p->layout == SB_LAYOUT_V1 ? 2 : 4;
+    const uint32_t bstride = sbc::beam_stride(p->layout);
     uint8_t *md = (uint8_t *)metadata, *mp = (uint8_t *)mapping, *pd = (uint8_t *)particles, *bd = (uint8_t *)beams;
     memcpy(md, p->metadata.data(), SB_METADATA_BYTES);
     memcpy(md + 4, &nP, 4);
     memcpy(md + 24, &nB, 4);
     memcpy(md + 40, &max_particles, 4);
     memcpy(md + 44, &max_beams, 4);
-    auto map_set = [&](size_t id, uint32_t v) {
-        if (isz == 2) { const uint16_t h = (uint16_t)v; memcpy(mp + 2 * id, &h, 2); }
-        else memcpy(mp + 4 * id, &v, 4);
-    };
+    auto map_set = [&](size_t id, uint32_t v) { sbc::map_set(p->layout, mp, id, v); };
     // identity beyond the active slots, as BufferMapper.writeState leaves it (engineMapping.ts:505-516)
     for (uint32_t s = 0; s < max_particles; s++) map_set(s, s);
     for (uint32_t s = 0; s < max_beams; s++) map_set((size_t)max_particles + s, s);
@@ -344,18 +320,10 @@ sb_status sb_partition_rank_scene(const sb_partition *p, uint32_t rank, uint32_t
     std::vector<uint32_t> local_of_global(p->maxP, 0xFFFFFFFFu);
     for (uint32_t i = 0; i < nP; i++) local_of_global[R.p_global_data[i]] = i;
     for (uint32_t i = 0; i < nB; i++) {
-        const uint8_t *src = p->beams.data() + (size_t)R.b_global_data[i] * bstride;
-        uint8_t *dst = bd + (size_t)i * bstride;
-        memcpy(dst, src, bstride);
-        if (p->layout == SB_LAYOUT_V1) {
-            const uint32_t pr = rd32(src), a = local_of_global[pr & 0xffffu], b = local_of_global[pr >> 16];
-            const uint32_t w = (a & 0xffffu) | (b << 16);
-            memcpy(dst, &w, 4);
-        } else {
-            const uint32_t a = local_of_global[rd32(src)], b = local_of_global[rd32(src + 4)];
-            memcpy(dst, &a, 4);
-            memcpy(dst + 4, &b, 4);
-        }
+        uint32_t a, b;
+        const uint8_t *f9;
+        sbc::decode_beam(p->layout, p->beams.data() + (size_t)R.b_global_data[i] * bstride, a, b, f9);
+        sbc::encode_beam(p->layout, bd + (size_t)i * bstride, local_of_global[a], local_of_global[b], f9);
     }
     return SB_OK;
 }

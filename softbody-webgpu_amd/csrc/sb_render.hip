@@ -172,40 +172,18 @@ __global__ __launch_bounds__(SBR_BLOCK) void k_render_resolve(const unsigned lon
 
 // ---------------------------------------------------------------- host side
 
-#define SBR_FAIL(e, code, ...)                            \
-    do {                                                  \
-        char _buf[512];                                   \
-        snprintf(_buf, sizeof _buf, __VA_ARGS__);         \
-        (e)->err = _buf;                                  \
-        return (code);                                    \
-    } while (0)
-#define SBR_HIP(e, call)                                                                                       \
-    do {                                                                                                       \
-        hipError_t _r = (call);                                                                                \
-        if (_r != hipSuccess) {                                                                                \
-            (void)hipGetLastError();                                                                           \
-            SBR_FAIL(e, _r == hipErrorOutOfMemory ? SB_ERR_OOM : SB_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(_r)); \
-        }                                                                                                      \
-    } while (0)
-
-#define SB_TRYR(x)                   \
-    do {                             \
-        sb_status _s = (x);          \
-        if (_s != SB_OK) return _s;  \
-    } while (0)
-
 template <typename T>
 static sb_status sbr_grow(sb_engine *e, T **p, size_t &cap, size_t n)
 {
     n = std::max<size_t>(n, 1);
     if (*p && cap >= n) return SB_OK;
     if (*p) {
-        SBR_HIP(e, hipStreamSynchronize(e->stream)); // a render in flight may still read it
-        SBR_HIP(e, hipFree(*p));
+        SB_HIP(e, hipStreamSynchronize(e->stream)); // a render in flight may still read it
+        SB_HIP(e, hipFree(*p));
         *p = nullptr;
         cap = 0;
     }
-    SBR_HIP(e, hipMalloc((void **)p, n * sizeof(T)));
+    SB_HIP(e, hipMalloc((void **)p, n * sizeof(T)));
     cap = n;
     return SB_OK;
 }
@@ -236,10 +214,10 @@ sb_status sbr_copy_table(sb_engine *e, const uint32_t **copy)
     SbRenderState &r = *e->rs;
     if (!r.copy_valid) {
         const uint32_t B = e->B;
-        if (e->h_copy_of_slot.size() < B) SBR_FAIL(e, SB_ERR_STATE, "host shadows of the scene are inconsistent");
-        SB_TRYR(sbr_grow(e, &r.d_copy, r.cap_copy, B));
-        if (B) SBR_HIP(e, hipMemcpyAsync(r.d_copy, e->h_copy_of_slot.data(), (size_t)B * 4, hipMemcpyHostToDevice, e->stream));
-        SBR_HIP(e, hipStreamSynchronize(e->stream)); // (an upload may rewrite the host array)
+        if (e->h_copy_of_slot.size() < B) SB_FAIL(e, SB_ERR_STATE, "host shadows of the scene are inconsistent");
+        SB_TRY(sbr_grow(e, &r.d_copy, r.cap_copy, B));
+        if (B) SB_HIP(e, hipMemcpyAsync(r.d_copy, e->h_copy_of_slot.data(), (size_t)B * 4, hipMemcpyHostToDevice, e->stream));
+        SB_HIP(e, hipStreamSynchronize(e->stream)); // (an upload may rewrite the host array)
         r.copy_valid = true;
     }
     if (copy) *copy = r.d_copy;
@@ -254,7 +232,7 @@ static sb_status sbr_build_tables(sb_engine *e)
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t P = e->P, B = e->B, maxP = e->opt.max_particles;
     if (e->h_pidx.size() != P || e->h_beams.size() != B || e->h_copy_of_slot.size() < B)
-        SBR_FAIL(e, SB_ERR_STATE, "sb_render: host shadows of the scene are inconsistent");
+        SB_FAIL(e, SB_ERR_STATE, "sb_render: host shadows of the scene are inconsistent");
     std::vector<uint32_t> internal_of_index(maxP, 0xFFFFFFFFu);
     for (uint32_t i = 0; i < P; i++) internal_of_index[e->h_pidx[i]] = i;
     std::vector<uint2> ends(std::max<uint32_t>(B, 1), make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu));
@@ -267,13 +245,13 @@ static sb_status sbr_build_tables(sb_engine *e)
         }
     });
     for (const uint2 &v : ends)
-        if (v.x != 0xFFFFFFFFu && (v.x >= P || v.y >= P)) SBR_FAIL(e, SB_ERR_STATE, "sb_render: beam endpoint outside the scene");
-    SB_TRYR(sbr_grow(e, &r.d_ends, r.cap_ends, B));
-    SB_TRYR(sbr_copy_table(e, nullptr));
-    SBR_HIP(e, hipMemcpyAsync(r.d_ends, ends.data(), (size_t)std::max<uint32_t>(B, 1) * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
-    SB_TRYR(sbr_grow(e, &r.d_wide_p, r.cap_wide_p, P));
-    SB_TRYR(sbr_grow(e, &r.d_wide_b, r.cap_wide_b, B));
-    SBR_HIP(e, hipStreamSynchronize(e->stream)); // (the host vectors go out of scope)
+        if (v.x != 0xFFFFFFFFu && (v.x >= P || v.y >= P)) SB_FAIL(e, SB_ERR_STATE, "sb_render: beam endpoint outside the scene");
+    SB_TRY(sbr_grow(e, &r.d_ends, r.cap_ends, B));
+    SB_TRY(sbr_copy_table(e, nullptr));
+    SB_HIP(e, hipMemcpyAsync(r.d_ends, ends.data(), (size_t)std::max<uint32_t>(B, 1) * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+    SB_TRY(sbr_grow(e, &r.d_wide_p, r.cap_wide_p, P));
+    SB_TRY(sbr_grow(e, &r.d_wide_b, r.cap_wide_b, B));
+    SB_HIP(e, hipStreamSynchronize(e->stream)); // (the host vectors go out of scope)
     r.nbeam_slots = B;
     r.valid = true;
     r.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -285,31 +263,31 @@ static sb_status sbr_enqueue(sb_engine *e, const sb_render_options *o, uint8_t *
 {
     if (!e) return SB_ERR_INVALID;
     if (o && o->struct_size != 0 && o->struct_size != sizeof(sb_render_options))
-        SBR_FAIL(e, SB_ERR_INVALID, "sb_render: sb_render_options.struct_size %u != %zu", o->struct_size, sizeof(sb_render_options));
+        SB_FAIL(e, SB_ERR_INVALID, "sb_render: sb_render_options.struct_size %u != %zu", o->struct_size, sizeof(sb_render_options));
     const bool given = o && o->struct_size;
     const uint32_t res = given && o->resolution ? o->resolution : 512u;
-    if (res > SB_RENDER_MAX_RESOLUTION) SBR_FAIL(e, SB_ERR_INVALID, "sb_render: resolution %u above %u", res, SB_RENDER_MAX_RESOLUTION);
-    if (!e->loaded) SBR_FAIL(e, SB_ERR_STATE, "sb_render before sb_write_buffers");
+    if (res > SB_RENDER_MAX_RESOLUTION) SB_FAIL(e, SB_ERR_INVALID, "sb_render: resolution %u above %u", res, SB_RENDER_MAX_RESOLUTION);
+    if (!e->loaded) SB_FAIL(e, SB_ERR_STATE, "sb_render before sb_write_buffers");
     if (e->n_ghost_p || e->n_send_p || e->n_ghost_b || e->n_send_b)
-        SBR_FAIL(e, SB_ERR_UNSUPPORTED, "sb_render: the engine has ghost zones configured (ranks are not composited)");
+        SB_FAIL(e, SB_ERR_UNSUPPORTED, "sb_render: the engine has ghost zones configured (ranks are not composited)");
     const size_t npix = (size_t)res * res;
     if (host_bytes && bytes_avail < npix * 3)
-        SBR_FAIL(e, SB_ERR_INVALID, "sb_render: buffer of %zu bytes, the picture needs %zu", bytes_avail, npix * 3);
-    if (!d_rgb && !host_bytes) SBR_FAIL(e, SB_ERR_INVALID, "sb_render_device: null destination");
+        SB_FAIL(e, SB_ERR_INVALID, "sb_render: buffer of %zu bytes, the picture needs %zu", bytes_avail, npix * 3);
+    if (!d_rgb && !host_bytes) SB_FAIL(e, SB_ERR_INVALID, "sb_render_device: null destination");
     SbrArgs a;
     a.S = given && o->bounds_size != 0.0 ? o->bounds_size : (double)e->opt.bounds_size;
     a.r = given && o->particle_radius != 0.0 ? o->particle_radius : (double)e->opt.particle_radius;
     a.r08 = a.r * 0.8;
     a.res = (double)res;
     a.nres = res;
-    SBR_HIP(e, hipSetDevice(e->device));
+    SB_HIP(e, hipSetDevice(e->device));
     if (!e->rs) e->rs = new SbRenderState();
     SbRenderState &r = *e->rs;
-    if (!r.valid) SB_TRYR(sbr_build_tables(e));
-    if (!r.d_count) SBR_HIP(e, hipMalloc((void **)&r.d_count, 2 * sizeof(uint32_t)));
-    SB_TRYR(sbr_grow(e, &r.d_keys, r.cap_keys, npix));
-    SBR_HIP(e, hipMemsetAsync(r.d_keys, 0, npix * sizeof(unsigned long long), e->stream));
-    SBR_HIP(e, hipMemsetAsync(r.d_count, 0, 2 * sizeof(uint32_t), e->stream));
+    if (!r.valid) SB_TRY(sbr_build_tables(e));
+    if (!r.d_count) SB_HIP(e, hipMalloc((void **)&r.d_count, 2 * sizeof(uint32_t)));
+    SB_TRY(sbr_grow(e, &r.d_keys, r.cap_keys, npix));
+    SB_HIP(e, hipMemsetAsync(r.d_keys, 0, npix * sizeof(unsigned long long), e->stream));
+    SB_HIP(e, hipMemsetAsync(r.d_count, 0, 2 * sizeof(uint32_t), e->stream));
     const float2 *pos = e->part[e->cur].pos;
     const uint32_t *dead = e->B && e->delete_gen ? e->d_dead_gen : nullptr; // as sb_load_buffers (fetch_dead) sees it
     const uint32_t P = e->P, B = e->B;
@@ -325,7 +303,7 @@ static sb_status sbr_enqueue(sb_engine *e, const sb_render_options *o, uint8_t *
     }
     k_render_resolve<<<(unsigned)((npix + SBR_BLOCK - 1) / SBR_BLOCK), SBR_BLOCK, 0, e->stream>>>(
         r.d_keys, npix, r.d_copy, e->beams.strain, e->beams.stress, d_rgb);
-    SBR_HIP(e, hipGetLastError());
+    SB_HIP(e, hipGetLastError());
     *res_out = res;
     return SB_OK;
 }
@@ -350,18 +328,18 @@ sb_status sb_render(sb_engine *e, const sb_render_options *opts, void *rgb, size
 {
     try {
         if (!e) return SB_ERR_INVALID;
-        if (!rgb) SBR_FAIL(e, SB_ERR_INVALID, "sb_render: null destination");
+        if (!rgb) SB_FAIL(e, SB_ERR_INVALID, "sb_render: null destination");
         // the size check needs the resolution before anything is enqueued: sbr_enqueue checks it against rgb_bytes
         const bool given = opts && opts->struct_size;
         const size_t res = given && opts->resolution ? opts->resolution : 512u;
         if (res <= SB_RENDER_MAX_RESOLUTION && e->loaded) {
             if (!e->rs) e->rs = new SbRenderState();
-            if (rgb_bytes >= res * res * 3) SB_TRYR(sbr_grow(e, &e->rs->d_rgb, e->rs->cap_rgb, res * res * 3));
+            if (rgb_bytes >= res * res * 3) SB_TRY(sbr_grow(e, &e->rs->d_rgb, e->rs->cap_rgb, res * res * 3));
         }
         uint32_t got = 0;
-        SB_TRYR(sbr_enqueue(e, opts, e->rs ? e->rs->d_rgb : nullptr, rgb_bytes, true, &got));
-        SBR_HIP(e, hipMemcpyAsync(rgb, e->rs->d_rgb, (size_t)got * got * 3, hipMemcpyDeviceToHost, e->stream));
-        SBR_HIP(e, hipStreamSynchronize(e->stream));
+        SB_TRY(sbr_enqueue(e, opts, e->rs ? e->rs->d_rgb : nullptr, rgb_bytes, true, &got));
+        SB_HIP(e, hipMemcpyAsync(rgb, e->rs->d_rgb, (size_t)got * got * 3, hipMemcpyDeviceToHost, e->stream));
+        SB_HIP(e, hipStreamSynchronize(e->stream));
         return SB_OK;
     } catch (const std::bad_alloc &) {
         if (e) e->err = "out of host memory";

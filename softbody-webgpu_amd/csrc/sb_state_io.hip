@@ -82,27 +82,6 @@ __global__ __launch_bounds__(SBS_BLOCK) void k_state_import_particles(const floa
 
 // ---------------------------------------------------------------- host side
 
-#define SBS_FAIL(e, code, ...)                            \
-    do {                                                  \
-        char _buf[512];                                   \
-        snprintf(_buf, sizeof _buf, __VA_ARGS__);         \
-        (e)->err = _buf;                                  \
-        return (code);                                    \
-    } while (0)
-#define SBS_HIP(e, call)                                                                                       \
-    do {                                                                                                       \
-        hipError_t _r = (call);                                                                                \
-        if (_r != hipSuccess) {                                                                                \
-            (void)hipGetLastError();                                                                           \
-            SBS_FAIL(e, _r == hipErrorOutOfMemory ? SB_ERR_OOM : SB_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(_r)); \
-        }                                                                                                      \
-    } while (0)
-#define SBS_TRY(x)                   \
-    do {                             \
-        sb_status _s = (x);          \
-        if (_s != SB_OK) return _s;  \
-    } while (0)
-
 void sbs_invalidate(sb_engine *e)
 {
     if (e && e->sio) e->sio->valid = false;
@@ -118,10 +97,10 @@ void sbs_release(sb_engine *e)
 
 static sb_status sbs_check(sb_engine *e, const char *what)
 {
-    if (!e->loaded) SBS_FAIL(e, SB_ERR_STATE, "%s before sb_write_buffers", what);
+    if (!e->loaded) SB_FAIL(e, SB_ERR_STATE, "%s before sb_write_buffers", what);
     if (e->halo_configured || e->n_ghost_p || e->n_send_p || e->n_ghost_b || e->n_send_b || e->n_peers || e->mailbox)
-        SBS_FAIL(e, SB_ERR_UNSUPPORTED, "%s: the engine has ghost zones or peers configured (ranks are not handled)", what);
-    SBS_HIP(e, hipSetDevice(e->device));
+        SB_FAIL(e, SB_ERR_UNSUPPORTED, "%s: the engine has ghost zones or peers configured (ranks are not handled)", what);
+    SB_HIP(e, hipSetDevice(e->device));
     return SB_OK;
 }
 
@@ -137,19 +116,19 @@ static sb_status sbs_build_tables(sb_engine *e)
         for (size_t u = u0; u < u1; u++) slots[u] = make_uint2(sb_user_slot(e, u), map_get(e, e->h_mapping.data(), (size_t)maxP + u));
     });
     for (uint32_t u = 0; u < Bu; u++)
-        if (slots[u].x >= e->B || slots[u].y >= e->opt.max_beams) SBS_FAIL(e, SB_ERR_STATE, "sb_read_state_device: beam slot outside the scene");
+        if (slots[u].x >= e->B || slots[u].y >= e->opt.max_beams) SB_FAIL(e, SB_ERR_STATE, "sb_read_state_device: beam slot outside the scene");
     if (!s.d_slot || s.cap_slot < slots.size()) {
         if (s.d_slot) {
-            SBS_HIP(e, hipStreamSynchronize(e->stream)); // an export in flight may still read it
-            SBS_HIP(e, hipFree(s.d_slot));
+            SB_HIP(e, hipStreamSynchronize(e->stream)); // an export in flight may still read it
+            SB_HIP(e, hipFree(s.d_slot));
             s.d_slot = nullptr;
             s.cap_slot = 0;
         }
-        SBS_HIP(e, hipMalloc((void **)&s.d_slot, slots.size() * sizeof(uint2)));
+        SB_HIP(e, hipMalloc((void **)&s.d_slot, slots.size() * sizeof(uint2)));
         s.cap_slot = slots.size();
     }
-    SBS_HIP(e, hipMemcpyAsync(s.d_slot, slots.data(), slots.size() * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
-    SBS_HIP(e, hipStreamSynchronize(e->stream)); // (the host vector goes out of scope)
+    SB_HIP(e, hipMemcpyAsync(s.d_slot, slots.data(), slots.size() * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+    SB_HIP(e, hipStreamSynchronize(e->stream)); // (the host vector goes out of scope)
     s.nslots = Bu;
     s.valid = true;
     s.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -159,9 +138,9 @@ static sb_status sbs_build_tables(sb_engine *e)
 static sb_status sbs_read(sb_engine *e, void *particles, void *beams, void *alive)
 {
     if (!e) return SB_ERR_INVALID;
-    SBS_TRY(sbs_check(e, "sb_read_state_device"));
+    SB_TRY(sbs_check(e, "sb_read_state_device"));
     if (((uintptr_t)particles & 7u) || ((uintptr_t)beams & 15u))
-        SBS_FAIL(e, SB_ERR_INVALID, "sb_read_state_device: particle records need 8-byte, beam rows 16-byte aligned buffers");
+        SB_FAIL(e, SB_ERR_INVALID, "sb_read_state_device: particle records need 8-byte, beam rows 16-byte aligned buffers");
     const uint32_t P = e->P;
     if (particles && P) {
         const SbParticleArrays &c = e->part[e->cur];
@@ -169,25 +148,25 @@ static sb_status sbs_read(sb_engine *e, void *particles, void *beams, void *aliv
                                                                                               (float2 *)particles);
     }
     if ((beams || alive) && sb_user_beams(e)) {
-        if (!e->sio || !e->sio->valid) SBS_TRY(sbs_build_tables(e));
+        if (!e->sio || !e->sio->valid) SB_TRY(sbs_build_tables(e));
         const uint32_t *copy = nullptr;
-        SBS_TRY(sbr_copy_table(e, &copy));
+        SB_TRY(sbr_copy_table(e, &copy));
         const SbStateIoState &s = *e->sio;
         const uint32_t *dead = e->B && e->delete_gen ? e->d_dead_gen : nullptr; // as sb_load_buffers (fetch_dead) sees it
         k_state_export_beams<<<(s.nslots + SBS_BLOCK - 1) / SBS_BLOCK, SBS_BLOCK, 0, e->stream>>>(
             s.d_slot, s.nslots, copy, e->beams.target, e->beams.last, e->beams.strain, e->beams.stress, dead, (float4 *)beams,
             (uint8_t *)alive);
     }
-    SBS_HIP(e, hipGetLastError());
+    SB_HIP(e, hipGetLastError());
     return SB_OK;
 }
 
 static sb_status sbs_write(sb_engine *e, const void *particles)
 {
     if (!e) return SB_ERR_INVALID;
-    SBS_TRY(sbs_check(e, "sb_write_particles_device"));
-    if (!particles) SBS_FAIL(e, SB_ERR_INVALID, "sb_write_particles_device: null source");
-    if ((uintptr_t)particles & 7u) SBS_FAIL(e, SB_ERR_INVALID, "sb_write_particles_device: particle records need an 8-byte aligned buffer");
+    SB_TRY(sbs_check(e, "sb_write_particles_device"));
+    if (!particles) SB_FAIL(e, SB_ERR_INVALID, "sb_write_particles_device: null source");
+    if ((uintptr_t)particles & 7u) SB_FAIL(e, SB_ERR_INVALID, "sb_write_particles_device: particle records need an 8-byte aligned buffer");
     const uint32_t P = e->P;
     if (P) {
         const SbParticleArrays &c = e->part[e->cur];
@@ -199,12 +178,12 @@ static sb_status sbs_write(sb_engine *e, const void *particles)
         }
         k_state_import_particles<<<(P + SBS_BLOCK - 1) / SBS_BLOCK, SBS_BLOCK, 0, e->stream>>>(
             (const float2 *)particles, e->d_pidx, P, c.pos, c.vel, c.acc, flag, tile_p0, e->ntiles);
-        SBS_HIP(e, hipGetLastError());
+        SB_HIP(e, hipGetLastError());
     }
     // Whatever the engine promised itself about where the particles are holds no more: the hash starts again (as after an upload
     // that keeps the plan), and the hybrid looks at the scene afresh at the start of the next call (hybrid_substeps honours
     // grid_force: single substeps until the new hash has made its lists).
-    SBS_TRY(sb_grid_reset_hash(e));
+    SB_TRY(sb_grid_reset_hash(e));
     e->hy.slow_chunk = e->hy.slow_left = 0;
     return SB_OK;
 }

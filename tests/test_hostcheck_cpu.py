@@ -1,8 +1,8 @@
 """The host side of the C library under sanitizers (`make -C softbody-webgpu_amd/csrc hostcheck`): the scene
 partitioner (csrc/sb_partition.cpp, driven by tests/partition_check.cpp on the reference's default scene, main.ts:188-246, and
 on a 90 000-particle lattice, v1 and v2 layouts) and the two multi-threaded upload planners (sb_tiling.h, sb_blocking.h with the
-check drivers of tests/test_tiling_cpu.py / test_blocking_cpu.py) and the subsequence matcher of edit uploads (sb_edit.h), each built with AddressSanitizer + UBSan and with
-ThreadSanitizer.  CPU only: the GPU pool has no sanitizers."""
+check drivers of tests/test_tiling_cpu.py / test_blocking_cpu.py), the subsequence matcher of edit uploads (sb_edit.h) and the scene codec
+(sb_scene_codec.h), each built with AddressSanitizer + UBSan and with ThreadSanitizer.  CPU only: the GPU pool has no sanitizers."""
 import os
 import subprocess
 import sys
@@ -37,8 +37,7 @@ def run(exe, args, timeout=600):
     return p.stdout
 
 
-@pytest.mark.parametrize("san", ["asan", "tsan"])
-def test_partitioner_under_sanitizers(built, sb, tmp_path, san):
+def check_scenes(sb):
     scenes = {"default_v1": sb.scenes.default_buffers(1, 256, 512), "default_v2": sb.scenes.default_buffers(2, 200, 400),
               "lattice_90k": sb.scenes.lattice_buffers(300, 300, d=30.0, jitter=1.0, layout=2, slack=7)}
     # a scene whose mapping is not the identity (compute_delete permutes it, engineMapping.ts:336-339): slots reversed
@@ -47,7 +46,12 @@ def test_partitioner_under_sanitizers(built, sb, tmp_path, san):
     perm.mapping[:P] = perm.mapping[:P][::-1].copy()
     perm.mapping[perm.max_particles:perm.max_particles + B] = perm.mapping[perm.max_particles:perm.max_particles + B][::-1].copy()
     scenes["default_permuted"] = perm
-    for name, buf in scenes.items():
+    return scenes
+
+
+@pytest.mark.parametrize("san", ["asan", "tsan"])
+def test_partitioner_under_sanitizers(built, sb, tmp_path, san):
+    for name, buf in check_scenes(sb).items():
         path = str(tmp_path / (name + ".bin"))
         dump(buf, path)
         out = run(os.path.join(built, "partition_check_" + san), [path])
@@ -70,3 +74,24 @@ def test_subsequence_matcher_under_sanitizers(built, san):
     records, the new record's state taken over), every spoiled list refused."""
     out = run(os.path.join(built, "edit_check_" + san), ["300"])
     assert "300 lists matched, 0 refused, 300 spoiled lists refused" in out, out
+
+
+@pytest.mark.parametrize("san", ["asan", "tsan"])
+def test_scene_codec_under_sanitizers(built, sb, tmp_path, san):
+    """csrc/sb_scene_codec.h, the one reader and writer of the reference's records: per beam slot it decodes the endpoints and
+    the nine floats that numpy (layout.py) reads from the same buffers, bit for bit, and encoding them gives the record back (default scene
+    v1 / v2, a permuted mapping, a 300 x 300 lattice); each of the five defects of a scene, planted in the first and in a late range
+    of slots, comes back with its kind, slot and indices from the parallel walk and from 1 and 8 threads over explicit ranges; of
+    two defects the one at the lower slot is reported (tests/scene_codec_check.cpp)."""
+    for name, buf in check_scenes(sb).items():
+        P, B, P0 = buf.particle_count, buf.beam_count, buf.max_particles
+        rec = buf.beams[buf.mapping[P0:P0 + B].astype(np.int64)]
+        want = np.zeros((B, 11), "<u4")
+        want[:, 0], want[:, 1] = rec["a"], rec["b"]
+        for k, field in enumerate(sb.layout.BEAM_FLOATS):
+            want[:, 2 + k] = np.ascontiguousarray(rec[field]).view("<u4")
+        path = str(tmp_path / (name + ".bin"))
+        dump(buf, path)
+        want.tofile(path + ".decoded")
+        out = run(os.path.join(built, "scene_codec_check_" + san), [path, path + ".decoded"])
+        assert "SCENE_CODEC_OK %d particles %d beams 17 defects" % (P, B) in out, (name, out)

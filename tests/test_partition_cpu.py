@@ -217,3 +217,14 @@ def test_partition_argument_checks(sb):
     one = sb.halo.partition_scene(buf, 1, 0)
     assert len(one) == 1 and not one[0][1].peers and one[0][0].particle_count == 119
     assert np.array_equal(one[0][0].particles[:119], buf.particles[:119])
+
+
+def test_partition_refuses_two_beam_slots_with_one_data_index(sb):
+    """Two beam slots that map to the same record are no scene (sb_write_buffers refuses them too): the slot that comes second is
+    named."""
+    for layout in (1, 2):
+        bad = sb.scenes.default_buffers(layout, 256, 512)
+        P0 = bad.max_particles
+        bad.mapping[P0 + 200] = bad.mapping[P0 + 17]
+        with pytest.raises(sb.engine.EngineError, match="beam slot 200 maps to data index 17 that another slot maps to"):
+            sb.halo.partition_scene(bad, 2, 2)
