@@ -443,10 +443,18 @@ typedef struct sb_batch_options {
     uint32_t max_particles;  /* capacity PER SCENE, 1 .. SB_BATCH_MAX_PARTICLES */
     uint32_t max_beams;      /* capacity PER SCENE, 0 .. SB_BATCH_MAX_BEAMS */
     uint32_t layout;         /* SB_LAYOUT_* of the host buffers of sb_batch_write_scene / sb_batch_load_scene */
-    uint32_t collision_mode; /* SB_COLLIDE_OFF, or on: SB_COLLIDE_ALLPAIRS and SB_COLLIDE_GRID both mean the reference's loop
-                              * over all slots in ascending order (compute.wgsl:144-170) and give the same bits */
+    uint32_t collision_mode; /* SB_COLLIDE_OFF; SB_COLLIDE_ALLPAIRS: the reference's loop over all slots in ascending order
+                              * (compute.wgsl:144-170); SB_COLLIDE_GRID (the default): scenes of at least grid_min_particles
+                              * particles bin their particles into a uniform cell grid in LDS every substep and test only the
+                              * 3 x 3 cells around each particle, applying the contacts in the same ascending slot order -- the
+                              * same bits as SB_COLLIDE_ALLPAIRS, O(P) instead of O(P^2); smaller scenes, and any substep in which
+                              * a cell holds more than "contact_cell_capacity" particles, run the loop */
     int32_t device_ordinal;
-    uint32_t reserved[6];
+    uint32_t grid_min_particles; /* SB_COLLIDE_GRID: 0 = the build's default (the measured break-even, sb_batch_get_info
+                              * "grid_min_particles"), n = scenes of at least n particles (1 .. SB_BATCH_MAX_PARTICLES) use the
+                              * cells, 0xFFFFFFFF = never.  Anything else is SB_ERR_INVALID.  Ignored by the other modes.
+                              * (carved from `reserved`: zero, as sb_batch_default_options always left it, is the default) */
+    uint32_t reserved[5];
 } sb_batch_options;
 
 /* reference defaults (bounds 1000, radius 10, subticks 64, v1, collisions on, device 0), one scene at the capacity limit */
@@ -521,7 +529,12 @@ sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream);
 /* key = "n_scenes", "scene_max_particles", "scene_max_beams" (the limits), "max_particles", "max_beams" (this batch's capacity),
  * "threads_per_scene", "lds_bytes_per_scene", "materials_in_lds", "scenes_per_cu", "frame_kernel_vgprs",
  * "frame_kernel_scratch_bytes", "frames_done", "substeps_done", "render_kernel_vgprs", "render_kernel_scratch_bytes",
- * "render_lds_bytes", "render_bands" (the last two: LDS per workgroup and bands per picture of the most recent render) */
+ * "render_lds_bytes", "render_bands" (the last two: LDS per workgroup and bands per picture of the most recent render);
+ * the contact cells of SB_COLLIDE_GRID: "contact_cells_per_side" (G of the G x G grid over the bounds; 0 when the whole batch
+ * runs the loop: another mode, a capacity below the threshold, or a radius / bounds whose cell width is no ordinary number),
+ * "contact_cell_capacity" (particles a cell holds), "grid_min_particles" (the resolved threshold), and two counts over all
+ * scenes and launches so far, which WAIT for the stream: "cell_substeps" (substeps of a scene that ran on the cells) and
+ * "cell_overflow_substeps" (substeps of a scene at or above the threshold that ran the loop because a cell was full) */
 sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value);
 const char *sb_batch_last_error(const sb_batch *b);
 

@@ -10,13 +10,14 @@ from .layout import LAYOUT_V1, PARTICLE_STRIDE, Buffers
 
 BATCH_MAX_PARTICLES, BATCH_MAX_BEAMS = 1024, 4096     # SB_BATCH_MAX_* (include/softbody.h)
 BATCH_RENDER_MAX_RESOLUTION = 1024                    # SB_BATCH_RENDER_MAX_RESOLUTION
+GRID_NEVER = 0xFFFFFFFF                               # sb_batch_options.grid_min_particles: no scene takes the cells
 
 
 class SbBatchOptions(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("n_scenes", ctypes.c_uint32), ("bounds_size", ctypes.c_float),
                 ("particle_radius", ctypes.c_float), ("subticks", ctypes.c_uint32), ("max_particles", ctypes.c_uint32),
                 ("max_beams", ctypes.c_uint32), ("layout", ctypes.c_uint32), ("collision_mode", ctypes.c_uint32),
-                ("device_ordinal", ctypes.c_int32), ("reserved", ctypes.c_uint32 * 6)]
+                ("device_ordinal", ctypes.c_int32), ("grid_min_particles", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 5)]
 
 
 class SbBatchRenderOptions(ctypes.Structure):
@@ -66,16 +67,26 @@ def load_library():
 
 class BatchEngine:
     """N independent scenes of at most BATCH_MAX_PARTICLES particles / BATCH_MAX_BEAMS beams each, stepped together.
-    max_particles / max_beams are the capacity PER SCENE (the sizes of the layout.Buffers that write_scene / load_scene take)."""
+    max_particles / max_beams are the capacity PER SCENE (the sizes of the layout.Buffers that write_scene / load_scene take).
+
+    collision_mode: COLLIDE_OFF, COLLIDE_ALLPAIRS (the reference's loop over every slot) or COLLIDE_GRID (the default): scenes
+    of at least `grid_min_particles` particles bin their particles into a cell grid in LDS every substep and test only the
+    3 x 3 cells around each particle -- the same bits as COLLIDE_ALLPAIRS.  grid_min_particles: None / 0 = the build's default
+    (the measured break-even), n = 1 .. BATCH_MAX_PARTICLES, GRID_NEVER = no scene.
+    info() keys of the cells: "contact_cells_per_side" (0: the whole batch runs the loop), "contact_cell_capacity",
+    "grid_min_particles" (resolved), and, waiting for the stream, "cell_substeps" (scene-substeps that ran on the cells) and
+    "cell_overflow_substeps" (scene-substeps that ran the loop because a cell held more than its capacity)."""
 
     def __init__(self, n_scenes=1, bounds_size=1000.0, particle_radius=10.0, subticks=64, layout=LAYOUT_V1,
-                 max_particles=BATCH_MAX_PARTICLES, max_beams=BATCH_MAX_BEAMS, collision_mode=COLLIDE_GRID, device=0):
+                 max_particles=BATCH_MAX_PARTICLES, max_beams=BATCH_MAX_BEAMS, collision_mode=COLLIDE_GRID, device=0,
+                 grid_min_particles=None):
         L = load_library()
         o = SbBatchOptions()
         L.sb_batch_default_options(ctypes.byref(o))
         o.n_scenes, o.bounds_size, o.particle_radius, o.subticks = n_scenes, bounds_size, particle_radius, subticks
         o.max_particles, o.max_beams, o.layout = max_particles, max_beams, layout
         o.collision_mode, o.device_ordinal = collision_mode, device
+        o.grid_min_particles = 0 if grid_min_particles is None else grid_min_particles
         self._h = ctypes.c_void_p()
         st = L.sb_batch_create(ctypes.byref(o), ctypes.byref(self._h))
         if st != 0:

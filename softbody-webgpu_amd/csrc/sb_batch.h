@@ -35,7 +35,21 @@ struct SbBatchView {
     // SLOT), per beam data index "not removed by a delete pass"
     uint32_t o_part, o_bstate, o_bmap, o_bflags, o_balive;
     uint32_t maxP, maxB, nflagw, n_scenes;
+    // contact cells (k_batch_frame<SB_BATCH_CELLS, .>; all zero when the batch walks): G x G cells of side `cell` over
+    // [0, bounds]^2, their LDS arrays cell_off bytes into the workgroup's LDS; scenes of at least cell_min_p particles use them;
+    // cell_stats[0] / [1]: substeps that ran on the cells / that fell back to the walk because a cell was full
+    uint32_t cell_g, cell_off, cell_min_p;
+    float cell;
+    unsigned long long *cell_stats;
 };
+// k_batch_frame's COLLIDE parameter
+#define SB_BATCH_NO_CONTACTS 0
+#define SB_BATCH_WALK 1  // the reference's loop over all slots
+#define SB_BATCH_CELLS 2 // the in-LDS cell grid, with the walk as its fallback
+#define SB_BATCH_CELL_K 4u // slot entries a cell holds
+// LDS behind cell_off: entries u16[G*G][SB_BATCH_CELL_K]; counts, two 16-bit counts to a word, u32[2][(G*G + 1) / 2] (one
+// buffer per substep parity); overflow words u32[2]
+static inline uint32_t sb_batch_cell_lds_bytes(uint32_t g) { return g * g * SB_BATCH_CELL_K * 2u + 2u * ((g * g + 1u) / 2u) * 4u + 8u; }
 
 SB_DEV uint32_t sbb_uniform(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
 SB_DEV float sbb_uniform(float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); }
@@ -51,7 +65,9 @@ struct sb_batch {
     SbBatchView V{};
     SbParams prm{};
     uint32_t subticks = 0, threads = 0, lds_bytes = 0;
-    bool mat_lds = false, collide = false;
+    bool mat_lds = false;
+    int collide = 0; // SB_BATCH_NO_CONTACTS / _WALK / _CELLS
+    uint32_t grid_min_particles = 0; // resolved
     unsigned char *stage = nullptr; // device staging of one upload: meta words, constant blob, state blob
     uint64_t frames_done = 0, substeps_done = 0;
     int scenes_per_cu = 0, vgprs = 0, scratch = 0;

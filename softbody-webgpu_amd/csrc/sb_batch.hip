@@ -10,6 +10,11 @@
 //           flags as bits per beam slot; barrier; particle phase: the reference's loop over slots 0 .. P-1 in ascending order
 //           against the frozen positions / velocities (every lane reads the same LDS word: a broadcast), sb_collide_pair_at,
 //           sb_particle_finish with the consumed and cleared sum, new state into the WRITE half of the ping-pong; barrier
+//   cells   (COLLIDE = SB_BATCH_CELLS, scenes of at least cell_min_p particles) beside the beam phase every particle's thread
+//           puts its slot into the cell of its READ position: G x G fixed-capacity buckets in LDS, placed by ds_add on the cell's
+//           count.  The particle phase then visits the 3 x 3 cells around its own and applies the contacts it finds in ascending
+//           slot order (SB_SELECT_INSERT, the selection of sb_collide_grid): the walk's bits.  A full bucket sets a word that
+//           sends the WHOLE workgroup through the walk for that substep.
 //   delete  flagged beams leave the slot list by forward stable compaction (sbo_delete / SURVEY A7), counts updated, flags cleared
 //   store   once per launch
 //
@@ -26,9 +31,9 @@
 
 // ---------------------------------------------------------------- the frame kernel
 // One thread per particle slot (blockDim.x >= max_particles: chosen at create), beams dealt round-robin.
-// COLLIDE: the collision loop is compiled in.  MAT_LDS: the material rows fit the LDS beside the rest (else they are read from
-// the constant blob every substep: L2 hits).
-template <bool COLLIDE, bool MAT_LDS>
+// COLLIDE: SB_BATCH_NO_CONTACTS, SB_BATCH_WALK (the collision loop) or SB_BATCH_CELLS (the cell grid and the loop).
+// MAT_LDS: the material rows fit the LDS beside the rest (else they are read from the constant blob every substep: L2 hits).
+template <int COLLIDE, bool MAT_LDS>
 __global__ __launch_bounds__(1024) void k_batch_frame(SbBatchView V, SbParams prm, uint32_t n_sub, uint32_t do_delete)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char sbb_lds[];
@@ -50,6 +55,13 @@ __global__ __launch_bounds__(1024) void k_batch_frame(SbBatchView V, SbParams pr
     uint32_t *s_flags = s_bd + maxB;         // [nflagw] break flags
     uint32_t *s_off = s_flags + V.nflagw;    // [nflagw + 1] delete pass: live beams in front of each flag word
     float *s_mat = (float *)(s_off + V.nflagw + 1u); // [maxB][6] (MAT_LDS)
+    // contact cells (sb_batch_cell_lds_bytes mirrors them): the counts are double buffered by substep parity, so a substep
+    // fills one buffer while every thread empties the word it filled in the other: no pass over G^2 words, no barrier of its own
+    const bool cells = COLLIDE == SB_BATCH_CELLS && P >= V.cell_min_p; // workgroup-uniform
+    const uint32_t G = V.cell_g, cntw = (G * G + 1u) >> 1;
+    uint16_t *s_cent = (uint16_t *)(sbb_lds + V.cell_off);               // [G * G][SB_BATCH_CELL_K] slots
+    uint32_t *s_ccnt = (uint32_t *)(s_cent + G * G * SB_BATCH_CELL_K);   // [2][cntw] two 16-bit counts to a word
+    uint32_t *s_covf = s_ccnt + 2u * cntw;                               // [2] "a cell was full"
 
     const unsigned char *cst = V.cst + (size_t)scene * V.cst_bytes;
     unsigned char *st = V.st + (size_t)scene * V.st_bytes;
@@ -100,6 +112,8 @@ __global__ __launch_bounds__(1024) void k_batch_frame(SbBatchView V, SbParams pr
         }
     }
     for (uint32_t w = tid; w < V.nflagw; w += T) s_flags[w] = g_bflags[w];
+    if (COLLIDE == SB_BATCH_CELLS && cells)
+        for (uint32_t w = tid; w < 2u * cntw + 2u; w += T) s_ccnt[w] = 0u; // (once per launch; the overflow words with them)
     __syncthreads();
 
     const float elasticity_coeff = sb_div(c.elasticity + 1.0f, 2.0f); // :143
@@ -113,10 +127,28 @@ __global__ __launch_bounds__(1024) void k_batch_frame(SbBatchView V, SbParams pr
 
     // ---- substeps
     uint32_t cur = 0u;
+    uint32_t my_cx = 0u, my_cy = 0u;        // this particle's cell in the substep at hand
+    uint32_t n_on_cells = 0u, n_fell_back = 0u; // substeps of this launch (uniform)
     for (uint32_t k = 0; k < n_sub; k++) {
         const bool aux = k + 1u == n_sub; // strain / stress are outputs only (:122-123): stored by the last substep of a launch
         const float2 *rp = s_pos + cur * maxP, *rv = s_vel + cur * maxP;
         float2 *wp = s_pos + (cur ^ 1u) * maxP, *wv = s_vel + (cur ^ 1u) * maxP;
+        uint32_t *ccnt = s_ccnt + (k & 1u) * cntw;
+        if (COLLIDE == SB_BATCH_CELLS && cells) {
+            // bin the READ positions (q.p is rp[tid]).  The count word this thread filled in the substep before goes back to 0
+            // first: nobody reads that buffer any more (everybody is past that substep's last barrier), and the buffer filled now
+            // was emptied the same way one substep ago, a barrier in front of the adds below.
+            if (active) {
+                if (k != 0u) s_ccnt[((k & 1u) ^ 1u) * cntw + ((my_cy * G + my_cx) >> 1)] = 0u;
+                my_cx = sb_grid_coord(q.p.x, 0.0f, V.cell, G); // monotone, clamped; NaN and -inf: cell 0, +inf: the last one
+                my_cy = sb_grid_coord(q.p.y, 0.0f, V.cell, G);
+                const uint32_t cell = my_cy * G + my_cx, sh = (cell & 1u) << 4;
+                const uint32_t n = (atomicAdd(&ccnt[cell >> 1], 1u << sh) >> sh) & 0xffffu; // (at most 1024 per cell: no carry)
+                if (n < SB_BATCH_CELL_K) s_cent[cell * SB_BATCH_CELL_K + n] = (uint16_t)tid;
+                else s_covf[k & 1u] = 1u;
+            }
+            if (tid == 0u && k != 0u) s_covf[(k & 1u) ^ 1u] = 0u;
+        }
         // beam phase (compute.wgsl:96-131)
         for (uint32_t j = tid; j < Bc; j += T) {
             const uint32_t word = s_w[j], ia = word & 0xffffu, ib = word >> 16;
@@ -139,10 +171,16 @@ __global__ __launch_bounds__(1024) void k_batch_frame(SbBatchView V, SbParams pr
         }
         __syncthreads();
         // particle phase (compute.wgsl:134-202)
+        bool walk = COLLIDE != SB_BATCH_NO_CONTACTS;
+        if (COLLIDE == SB_BATCH_CELLS && cells) {
+            walk = sbb_uniform(s_covf[k & 1u]) != 0u; // a cell was full: every thread of the workgroup takes the loop
+            n_fell_back += walk ? 1u : 0u;
+            n_on_cells += walk ? 0u : 1u;
+        }
         if (active) {
             SbParticle particle = q;
             const SbParticle self = q; // :141
-            if (COLLIDE) {
+            if (COLLIDE != SB_BATCH_NO_CONTACTS && walk) {
                 for (uint32_t o = 0; o < P; o++) { // :144-170, ascending slot order
                     const float2 op = rp[o];
                     const float dx = op.x - self.p.x, dy = op.y - self.p.y;
@@ -151,6 +189,58 @@ __global__ __launch_bounds__(1024) void k_batch_frame(SbBatchView V, SbParams pr
                     const float dist = sb_sqrt(d2); // sb_length(dx, dy)
                     if (o != tid && (dist == 0.0f || dist < two_r))
                         sb_collide_pair_at(prm, c.friction, elasticity_coeff, particle, self, my_idx, s_pidx[o], dx, dy, dist, rv[o]);
+                }
+            }
+            if (COLLIDE == SB_BATCH_CELLS && !walk) {
+                // The same loop restricted to the slots in the 3 x 3 cells around this particle's.  Cells are at least
+                // 2r (1 + 1/64) wide and the coordinate map is monotone, so whoever the loop above would find in contact
+                // (dist == 0 or dist < 2r) sits in one of them; everybody else is a no-op of that loop.  The contacts are
+                // applied in ascending slot order: a sweep collects the four smallest slots above the last one applied
+                // (the order of the entries inside a cell does not matter), then they are applied; a sweep that comes back
+                // with fewer than four was the last.
+                const uint32_t x0 = my_cx > 0u ? my_cx - 1u : 0u, x1 = my_cx + 1u < G ? my_cx + 1u : G - 1u;
+                const uint32_t y0 = my_cy > 0u ? my_cy - 1u : 0u, y1 = my_cy + 1u < G ? my_cy + 1u : G - 1u;
+                bool have_last = false;
+                uint32_t last = 0u;
+                for (;;) {
+                    uint32_t bs[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, bi[4] = {0u, 0u, 0u, 0u};
+                    for (uint32_t yy = y0; yy <= y1; yy++) {
+                        for (uint32_t xx = x0; xx <= x1; xx++) {
+                            const uint32_t cell = yy * G + xx;
+                            const uint32_t n = (ccnt[cell >> 1] >> ((cell & 1u) << 4)) & 0xffffu; // <= SB_BATCH_CELL_K: no cell was full
+                            const uint2 ent = *(const uint2 *)(s_cent + cell * SB_BATCH_CELL_K);
+#pragma unroll
+                            for (uint32_t j = 0; j < SB_BATCH_CELL_K; j++) {
+                                const uint32_t o = ((j < 2u ? ent.x : ent.y) >> ((j & 1u) << 4)) & 0xffffu;
+                                if (j >= n || o == tid || (have_last && o <= last) || o >= bs[3]) continue;
+                                const float2 op = rp[o];
+                                const float dx = op.x - self.p.x, dy = op.y - self.p.y;
+                                const float d2 = dx * dx + dy * dy;
+                                if (d2 > thr) continue;
+                                const float dist = sb_sqrt(d2);
+                                if (dist == 0.0f || dist < two_r) {
+                                    uint32_t slot = o, id = o; // (internal index == slot here)
+                                    SB_SELECT_INSERT(4, bs, bi, slot, id)
+                                }
+                            }
+                        }
+                    }
+                    bool full = true;
+#pragma unroll
+                    for (int s4 = 0; s4 < 4; s4++) {
+                        if (bs[s4] == 0xFFFFFFFFu) {
+                            full = false;
+                        } else {
+                            const uint32_t o = bi[s4];
+                            const float2 op = rp[o];
+                            const float dx = op.x - self.p.x, dy = op.y - self.p.y;
+                            const float dist = sb_sqrt(dx * dx + dy * dy);
+                            sb_collide_pair_at(prm, c.friction, elasticity_coeff, particle, self, my_idx, s_pidx[o], dx, dy, dist, rv[o]);
+                            last = o;
+                            have_last = true;
+                        }
+                    }
+                    if (!full) break;
                 }
             }
             const int fx = s_f[2u * tid], fy = s_f[2u * tid + 1u];
@@ -166,6 +256,10 @@ __global__ __launch_bounds__(1024) void k_batch_frame(SbBatchView V, SbParams pr
         cur ^= 1u;
     }
 
+    if (COLLIDE == SB_BATCH_CELLS && tid == 0u) { // what the launch ran on, once per launch
+        if (n_on_cells) (void)atomicAdd(&V.cell_stats[0], (unsigned long long)n_on_cells);
+        if (n_fell_back) (void)atomicAdd(&V.cell_stats[1], (unsigned long long)n_fell_back);
+    }
     // ---- store (beam state went out with the last substep)
     if (n_sub != 0u && active) {
         g_part[3u * my_idx] = q.p;
@@ -298,6 +392,32 @@ static uint32_t sb_batch_lds_bytes(uint32_t maxP, uint32_t maxB, bool mats)
 }
 #define SB_BATCH_LDS_LIMIT (160u * 1024u) // one CU of gfx950
 
+// ---- contact cells: geometry
+// Scenes of at least this many particles take the cells when sb_batch_options.grid_min_particles is 0: the smallest size of the
+// measured sweep (replicated lattices of 64 .. 1024 particles, profiles/batch_grid_timing.json) at which the cells win -- at 64
+// and 128 the cap on G makes the cells so coarse that a lattice fills their buckets, and the default scene (119) is 1.96 ms on
+// the walk against 2.45 ms on the cells.
+#define SB_BATCH_GRID_MIN_PARTICLES_DEFAULT 256u
+// the most cells per side a capacity gets: the largest G with G^2 <= 2.5 * max_particles (17 at 128, 25 at 256, 50 at 1024)
+static uint32_t sb_batch_cell_cap(uint32_t maxP)
+{
+    uint32_t g = 1u;
+    while (2u * (g + 1u) * (g + 1u) <= 5u * maxP) g++;
+    return g;
+}
+// cells per side and their width for a radius and bounds: SbGrid's rule, cell >= 2r (1 + 1/64); G = clamp(floor(bounds / that),
+// 1, cap), the cells then as wide as G of them need to cover the bounds (never narrower than the rule: coarser is always right;
+// whatever lies past the last cell is clamped into it).  0: the width is not an ordinary number, the batch walks.
+static uint32_t sb_batch_cell_geometry(float bounds, float radius, uint32_t cap, float *cell)
+{
+    const float two_r = radius * 2.0f, cell_min = two_r * (1.0f + 1.0f / 64.0f);
+    if (!(cell_min >= 0x1p-60f && cell_min <= 0x1p60f) || !(bounds >= 0x1p-60f && bounds <= 0x1p60f)) return 0u;
+    const float per_side = bounds / cell_min; // (ordinary: both are)
+    const uint32_t g = per_side >= (float)cap ? cap : (per_side >= 1.0f ? (uint32_t)per_side : 1u);
+    *cell = std::max(cell_min, bounds / (float)g);
+    return g;
+}
+
 const char *sb_batch_last_error(const sb_batch *b) { return b ? b->err.c_str() : g_batch_create_error.c_str(); }
 
 void sb_batch_default_options(sb_batch_options *o)
@@ -318,8 +438,9 @@ void sb_batch_default_options(sb_batch_options *o)
 typedef void (*sb_batch_kernel)(SbBatchView, SbParams, uint32_t, uint32_t);
 static sb_batch_kernel sb_batch_frame_kernel(const sb_batch *b)
 {
-    if (b->collide) return b->mat_lds ? k_batch_frame<true, true> : k_batch_frame<true, false>;
-    return b->mat_lds ? k_batch_frame<false, true> : k_batch_frame<false, false>;
+    if (b->collide == SB_BATCH_CELLS) return b->mat_lds ? k_batch_frame<SB_BATCH_CELLS, true> : k_batch_frame<SB_BATCH_CELLS, false>;
+    if (b->collide == SB_BATCH_WALK) return b->mat_lds ? k_batch_frame<SB_BATCH_WALK, true> : k_batch_frame<SB_BATCH_WALK, false>;
+    return b->mat_lds ? k_batch_frame<SB_BATCH_NO_CONTACTS, true> : k_batch_frame<SB_BATCH_NO_CONTACTS, false>;
 }
 
 sb_status sb_batch_destroy(sb_batch *b)
@@ -331,6 +452,7 @@ sb_status sb_batch_destroy(sb_batch *b)
     if (b->V.cst) (void)hipFree(b->V.cst);
     if (b->V.st) (void)hipFree(b->V.st);
     if (b->V.rst) (void)hipFree(b->V.rst);
+    if (b->V.cell_stats) (void)hipFree(b->V.cell_stats);
     if (b->stage) (void)hipFree(b->stage);
     sbb_render_release(b);
     if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -359,6 +481,9 @@ sb_status sb_batch_create(const sb_batch_options *opts, sb_batch **out)
     if (opts->collision_mode > SB_COLLIDE_GRID) SB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: unknown collision_mode %u", opts->collision_mode);
     if (!(opts->particle_radius > 0.f) || !(opts->bounds_size > 0.f) || opts->subticks == 0)
         SB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: radius, bounds and subticks must be positive");
+    if (opts->grid_min_particles > SB_BATCH_MAX_PARTICLES && opts->grid_min_particles != 0xFFFFFFFFu)
+        SB_FAIL(none, SB_ERR_INVALID, "sb_batch_create: grid_min_particles %u is neither 0 (the default), 1 .. %u, nor 0xFFFFFFFF (never)",
+                 opts->grid_min_particles, (unsigned)SB_BATCH_MAX_PARTICLES);
     int ndev = 0;
     hipError_t r = hipGetDeviceCount(&ndev);
     if (r != hipSuccess || ndev <= 0) {
@@ -385,13 +510,30 @@ sb_status sb_batch_create(const sb_batch_options *opts, sb_batch **out)
         const bool pow2 = (bits & 0x007fffffu) == 0u && (bits >> 23) > 1u && (bits >> 23) < 253u;
         b->prm.inv_dt2 = pow2 ? 1.0f / dt2 : 0.0f;
     }
-    b->collide = opts->collision_mode != SB_COLLIDE_OFF;
     const uint32_t maxP = opts->max_particles, maxB = opts->max_beams, n = opts->n_scenes;
-    b->threads = sb_batch_threads(maxP, maxB);
-    b->mat_lds = sb_batch_lds_bytes(maxP, maxB, true) <= SB_BATCH_LDS_LIMIT;
-    b->lds_bytes = sb_batch_lds_bytes(maxP, maxB, b->mat_lds);
-
     SbBatchView &V = b->V;
+    // SB_COLLIDE_GRID: the cells, for scenes of at least grid_min_particles particles -- unless no scene of this capacity can
+    // have that many, or the cell width is not an ordinary number: then the batch is the walk's, with the walk's LDS
+    b->collide = opts->collision_mode == SB_COLLIDE_OFF ? SB_BATCH_NO_CONTACTS : SB_BATCH_WALK;
+    b->grid_min_particles = opts->grid_min_particles ? opts->grid_min_particles : SB_BATCH_GRID_MIN_PARTICLES_DEFAULT;
+    uint32_t cell_bytes = 0u;
+    if (opts->collision_mode == SB_COLLIDE_GRID && b->grid_min_particles <= maxP) {
+        float cell = 0.f;
+        const uint32_t g = sb_batch_cell_geometry(opts->bounds_size, opts->particle_radius, sb_batch_cell_cap(maxP), &cell);
+        if (g != 0u) {
+            b->collide = SB_BATCH_CELLS;
+            V.cell_g = g;
+            V.cell = cell;
+            V.cell_min_p = b->grid_min_particles;
+            cell_bytes = up16(sb_batch_cell_lds_bytes(g));
+        }
+    }
+    b->threads = sb_batch_threads(maxP, maxB);
+    // (the material rows give way to the cells: with them in memory the LDS of the limit capacity still holds both)
+    b->mat_lds = sb_batch_lds_bytes(maxP, maxB, true) + cell_bytes <= SB_BATCH_LDS_LIMIT;
+    V.cell_off = sb_batch_lds_bytes(maxP, maxB, b->mat_lds);
+    b->lds_bytes = V.cell_off + cell_bytes;
+
     V.maxP = maxP;
     V.maxB = maxB;
     V.n_scenes = n;
@@ -432,6 +574,10 @@ sb_status sb_batch_create(const sb_batch_options *opts, sb_batch **out)
     SBB_CREATE_HIP(hipMemsetAsync(V.cst, 0, (size_t)n * V.cst_bytes, b->stream));
     SBB_CREATE_HIP(hipMemsetAsync(V.st, 0, (size_t)n * V.st_bytes, b->stream));
     SBB_CREATE_HIP(hipMemsetAsync(V.rst, 0, (size_t)n * V.st_bytes, b->stream));
+    if (b->collide == SB_BATCH_CELLS) {
+        SBB_CREATE_HIP(hipMalloc((void **)&V.cell_stats, 2u * sizeof(unsigned long long)));
+        SBB_CREATE_HIP(hipMemsetAsync(V.cell_stats, 0, 2u * sizeof(unsigned long long), b->stream));
+    }
     const void *fn = (const void *)sb_batch_frame_kernel(b);
     SBB_CREATE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes));
     hipFuncAttributes fa{};
@@ -698,6 +844,18 @@ sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value)
     else if (k == "frame_kernel_scratch_bytes") *value = (uint64_t)std::max(b->scratch, 0);
     else if (k == "frames_done") *value = b->frames_done;
     else if (k == "substeps_done") *value = b->substeps_done;
+    else if (k == "contact_cells_per_side") *value = b->V.cell_g;
+    else if (k == "contact_cell_capacity") *value = SB_BATCH_CELL_K;
+    else if (k == "grid_min_particles") *value = b->grid_min_particles;
+    else if (k == "cell_substeps" || k == "cell_overflow_substeps") {
+        unsigned long long st[2] = {0ull, 0ull};
+        if (b->V.cell_stats) {
+            SB_HIP(b, hipSetDevice(b->device));
+            SB_HIP(b, hipStreamSynchronize(b->stream));
+            SB_HIP(b, hipMemcpy(st, b->V.cell_stats, sizeof st, hipMemcpyDeviceToHost));
+        }
+        *value = st[k == "cell_substeps" ? 0 : 1];
+    }
     else if (sbb_render_info(b, key, value)) return SB_OK;
     else SB_FAIL(b, SB_ERR_INVALID, "sb_batch_get_info: unknown key '%s'", key);
     return SB_OK;

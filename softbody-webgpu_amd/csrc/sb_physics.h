@@ -1010,6 +1010,20 @@ SB_DEV void sb_grid_walk(const SbGrid &g, const SbGridHood &h, uint32_t self, F 
     }
 }
 
+// The selection step the ascending-slot-order loops below (and sb_batch.hip's cell walk) share: bs[] holds the N smallest slots
+// seen so far in ascending order (0xFFFFFFFF: none yet), bi[] what came with each; (slot, id) is inserted in its place and the
+// larger ones are carried down the registers, the largest falling out.  slot and id are the caller's variables and are
+// clobbered.  (A macro: as a function taking the arrays by reference the engine's kernels came out with other registers.)
+#define SB_SELECT_INSERT(N, bs, bi, slot, id)                                  \
+    _Pragma("unroll") for (int sel_q = 0; sel_q < (N); sel_q++) {              \
+        const bool sel_lt = (slot) < (bs)[sel_q];                              \
+        const uint32_t sel_ts = sel_lt ? (bs)[sel_q] : (slot), sel_ti = sel_lt ? (bi)[sel_q] : (id); \
+        (bs)[sel_q] = sel_lt ? (slot) : (bs)[sel_q];                           \
+        (bi)[sel_q] = sel_lt ? (id) : (bi)[sel_q];                             \
+        (slot) = sel_ts;                                                       \
+        (id) = sel_ti;                                                         \
+    }
+
 // The collision loop of compute.wgsl:144-170 restricted to the 3x3 cell neighbourhood, applying
 // contacts in ASCENDING SLOT ORDER exactly like the all-pairs scan does: repeatedly pick the
 // contact with the smallest slot above the last one applied.  Non-contacts are no-ops in the
@@ -1042,15 +1056,7 @@ SB_DEV void sb_collide_grid(const SbGrid &g, const SbGridGeom &m, const SbGridHo
             if (d2 > far2) return;
             const float d = sb_sqrt(d2);
             if (!(d == 0.0f || d < two_r)) return;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; q4++) { // carry the larger one down the four registers
-                const bool lt = slot < bs[q4];
-                const uint32_t ts = lt ? bs[q4] : slot, ti = lt ? bi[q4] : id;
-                bs[q4] = lt ? slot : bs[q4];
-                bi[q4] = lt ? id : bi[q4];
-                slot = ts;
-                id = ti;
-            }
+            SB_SELECT_INSERT(4, bs, bi, slot, id)
         });
         bool full = true;
 #pragma unroll
@@ -1092,15 +1098,7 @@ SB_DEV uint32_t sb_neighbour_list_build(const SbGrid &g, const SbGridGeom &m, ui
             const float dx = rx - p.x, dy = ry - p.y;
             // (one test, no short-circuit branches)
             if ((id == i) | (have_last & (slot <= last)) | (slot >= bs[SB_NL_SEL - 1]) | (dx * dx + dy * dy > reach2)) return;
-#pragma unroll
-            for (int q = 0; q < SB_NL_SEL; q++) { // carry the larger one down the four registers
-                const bool lt = slot < bs[q];
-                const uint32_t ts = lt ? bs[q] : slot, ti = lt ? bi[q] : id;
-                bs[q] = lt ? slot : bs[q];
-                bi[q] = lt ? id : bi[q];
-                slot = ts;
-                id = ti;
-            }
+            SB_SELECT_INSERT(SB_NL_SEL, bs, bi, slot, id)
         });
         bool full = true;
 #pragma unroll
