@@ -426,8 +426,8 @@ sb_status sb_write_particles_device(sb_engine *e, const void *device_particles);
  * An sb_batch never touches an sb_engine.
  *   Limits: per scene at most SB_BATCH_MAX_PARTICLES particles and SB_BATCH_MAX_BEAMS beams (what one workgroup holds).
  *   When do calls return?  sb_batch_frame / _step / _delete_pass / _reset_device / _write_user_input[_device] /
- *     _set_physics_constants / _read_state_device / _write_particles_device only ENQUEUE on the batch's stream (device buffers
- *     must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
+ *     _set_physics_constants / _read_state_device / _write_particles_device / _fork_device / _checkpoint_device /
+ *     _write_beams_device only ENQUEUE on the batch's stream (device buffers must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
  *     sb_batch_render_device only ENQUEUES (its device buffer must stay valid likewise); sb_batch_render_scene WAITS.
  *   Errors: every call returns an sb_status; sb_batch_last_error(b) gives the message (b == NULL: the last failed
  *     sb_batch_create of the calling thread).  Options are checked BEFORE a device is looked for. */
@@ -481,8 +481,9 @@ sb_status sb_batch_frame(sb_batch *b, uint32_t n_frames);
 sb_status sb_batch_step(sb_batch *b, uint32_t n_substeps);
 sb_status sb_batch_delete_pass(sb_batch *b);
 
-/* scenes whose byte in device_mask_u8[n_scenes] is nonzero go back to the state of their latest upload (particles, beam state,
- * beam mapping, counts, pending break flags); user input and physics constants stay.  NULL = all scenes. */
+/* scenes whose byte in device_mask_u8[n_scenes] is nonzero go back to their reset state: that of their latest upload, or of a
+ * later sb_batch_checkpoint_device / sb_batch_fork_device (particles, beam state, beam mapping, counts, pending break flags);
+ * user input and physics constants stay.  NULL = all scenes. */
 sb_status sb_batch_reset_device(sb_batch *b, const void *device_mask_u8);
 
 /* the layouts of sb_read_state_device / sb_write_particles_device with a leading scene dimension: particles
@@ -491,6 +492,51 @@ sb_status sb_batch_reset_device(sb_batch *b, const void *device_mask_u8);
  * are not written (not read).  Any pointer of the export may be NULL.  Pointers must be 4-byte aligned. */
 sb_status sb_batch_read_state_device(sb_batch *b, void *device_particles, void *device_beams, void *device_beam_alive);
 sb_status sb_batch_write_particles_device(sb_batch *b, const void *device_particles);
+
+/* ---- fork, checkpoint, beam import: the planner's and the policy's moves between frames, on the device ----
+ * All three only ENQUEUE on the batch's stream (device buffers must stay valid until that work has run).  Their argument errors
+ * -- a NULL handle, a NULL or misaligned (not 4-byte) pointer where one is required, unknown flag / field bits -- are
+ * SB_ERR_INVALID and are checked before anything touches a device.
+ *
+ * sb_batch_fork_device -- device_src_u32[n_scenes]: scene i becomes a copy of scene src[i].
+ *   Snapshot: every source is read as it was when the call's work began, so a permutation, a swap, or a broadcast from a scene
+ *     that is itself overwritten are well defined.  (Two launches through a staging set of blobs that the first fork allocates
+ *     and the batch keeps: sb_batch_get_info "fork_staging_bytes"; 0 before the first fork.)
+ *   src[i] == i and src[i] == SB_BATCH_FORK_KEEP leave scene i byte for byte as it was.  Any other entry >= n_scenes leaves
+ *     scene i untouched as well, is never used as an index, and is counted in sb_batch_get_info "fork_bad_sources" (all forks
+ *     so far; that key WAITS for the stream).
+ *   Copied: the constant blob (topology, materials, the "holds a particle / beam of the upload" bytes), the current state
+ *     (particle records, beam state, beam mapping, pending break flags, which beams were removed) and the metadata words that
+ *     describe the scene (the reference's counts and indices, words 0 .. 11, and "uploaded").  The destination KEEPS its 8 user
+ *     input words (the action) and, unless SB_BATCH_FORK_CONSTANTS is set, its 8 physics constants, as a reset does.
+ *   "Latest upload" in sb_batch_read_state_device, sb_batch_write_particles_device and sb_batch_write_beams_device means, for
+ *     a forked scene, its SOURCE's upload: the rows those calls touch travel with the constant blob.
+ *   Reset state: a reset image only makes sense beside the constant blob it was made for, so a fork never leaves the
+ *     destination's old one behind.  Without SB_BATCH_FORK_AS_RESET the destination also receives the source's reset state: a
+ *     later reset takes it where a reset would take the source (the source's upload, or its checkpoint).  With
+ *     SB_BATCH_FORK_AS_RESET the forked state itself becomes the destination's reset state.  Either way a later reset is well
+ *     defined and fault-free.  (Scenes the fork leaves untouched keep their reset state under both flags.)
+ *   A source that was never uploaded makes the destination a never-uploaded scene: it steps as a no-op, renders black, and
+ *     sb_batch_load_scene returns SB_ERR_STATE for it. */
+#define SB_BATCH_FORK_KEEP 0xFFFFFFFFu
+#define SB_BATCH_FORK_CONSTANTS 1u /* the source's 8 physics constants come along */
+#define SB_BATCH_FORK_AS_RESET 2u  /* the forked state becomes the destination's reset state */
+sb_status sb_batch_fork_device(sb_batch *b, const void *device_src_u32, uint32_t flags);
+
+/* the inverse of sb_batch_reset_device: scenes whose byte in device_mask_u8[n_scenes] is nonzero (NULL = all scenes) make their
+ * CURRENT state their reset state -- particles, beam state, beam mapping, live-beam count, pending break flags, which beams were
+ * removed.  Scenes never uploaded are skipped.  A later reset returns to exactly these bytes. */
+sb_status sb_batch_checkpoint_device(sb_batch *b, const void *device_mask_u8);
+
+/* the counterpart of sb_batch_write_particles_device for beams: device_beams in sb_batch_read_state_device's beam layout,
+ * [n_scenes][max_beams] x 16 B {target_length, last_length, strain, stress} at DATA indices.  `fields` selects what is written:
+ * SB_BATCH_BEAM_TARGET_LENGTH and / or SB_BATCH_BEAM_LAST_LENGTH (zero or any other bit: SB_ERR_INVALID); strain and stress are
+ * the step's outputs and are never imported.  Only rows of beams of the scene's latest upload are read; a removed beam's row is
+ * written but inert.  Counts, mappings, "removed" bytes and pending break flags are untouched.  Every later result is the one
+ * the batch would compute had those floats been these bytes all along. */
+#define SB_BATCH_BEAM_TARGET_LENGTH 1u
+#define SB_BATCH_BEAM_LAST_LENGTH 2u
+sb_status sb_batch_write_beams_device(sb_batch *b, const void *device_beams, uint32_t fields);
 
 /* scene i back into host buffers exactly as sb_load_buffers returns a single engine in the same state (counts in the metadata,
  * the mapping after the delete passes' stable in-place compactions, beam records with strain / stress; only records reachable
@@ -534,7 +580,11 @@ sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream);
  * runs the loop: another mode, a capacity below the threshold, or a radius / bounds whose cell width is no ordinary number),
  * "contact_cell_capacity" (particles a cell holds), "grid_min_particles" (the resolved threshold), and two counts over all
  * scenes and launches so far, which WAIT for the stream: "cell_substeps" (substeps of a scene that ran on the cells) and
- * "cell_overflow_substeps" (substeps of a scene at or above the threshold that ran the loop because a cell was full) */
+ * "cell_overflow_substeps" (substeps of a scene at or above the threshold that ran the loop because a cell was full);
+ * "constant_blob_bytes" / "state_blob_bytes" (device memory per scene of what only an upload or a fork writes / of what stepping
+ * changes; the latter is kept twice, current and reset); sb_batch_fork_device: "fork_staging_bytes" (device memory of the staging
+ * blobs; 0 before the first fork) and, WAITING for the stream, "fork_bad_sources" (entries >= n_scenes other than
+ * SB_BATCH_FORK_KEEP seen by all forks so far) */
 sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value);
 const char *sb_batch_last_error(const sb_batch *b);
 

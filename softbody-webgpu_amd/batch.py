@@ -10,6 +10,9 @@ from .layout import LAYOUT_V1, PARTICLE_STRIDE, Buffers
 
 BATCH_MAX_PARTICLES, BATCH_MAX_BEAMS = 1024, 4096     # SB_BATCH_MAX_* (include/softbody.h)
 BATCH_RENDER_MAX_RESOLUTION = 1024                    # SB_BATCH_RENDER_MAX_RESOLUTION
+FORK_KEEP = 0xFFFFFFFF                                # SB_BATCH_FORK_KEEP: this entry of fork()'s `src` leaves its scene as it is
+FORK_CONSTANTS, FORK_AS_RESET = 1, 2                  # SB_BATCH_FORK_*
+BEAM_TARGET_LENGTH, BEAM_LAST_LENGTH = 1, 2           # SB_BATCH_BEAM_*
 GRID_NEVER = 0xFFFFFFFF                               # sb_batch_options.grid_min_particles: no scene takes the cells
 
 
@@ -50,6 +53,9 @@ def load_library():
     L.sb_batch_reset_device.argtypes = [vp, vp]
     L.sb_batch_read_state_device.argtypes = [vp, vp, vp, vp]
     L.sb_batch_write_particles_device.argtypes = [vp, vp]
+    L.sb_batch_fork_device.argtypes = [vp, vp, u32]
+    L.sb_batch_checkpoint_device.argtypes = [vp, vp]
+    L.sb_batch_write_beams_device.argtypes = [vp, vp, u32]
     L.sb_batch_load_scene.argtypes = [vp, u32, vp, sz, vp, sz, vp, sz, vp, sz]
     L.sb_batch_render_device.argtypes = [vp, ctypes.POINTER(SbBatchRenderOptions), vp]
     L.sb_batch_render_scene.argtypes = [vp, u32, ctypes.POINTER(SbBatchRenderOptions), vp, sz]
@@ -160,11 +166,36 @@ class BatchEngine:
 
     def reset(self, mask=None):
         """Scenes whose mask entry is nonzero (a uint8 / bool torch tensor of n_scenes entries on the device, or a device
-        pointer) go back to their latest upload; None = all."""
+        pointer) go back to their reset state: their latest upload, or a later checkpoint() / fork(); None = all."""
         if mask is None:
             return self._check(load_library().sb_batch_reset_device(self._h, None))
         ptr, t = self._device_buffer("reset", mask, ("uint8", "bool"), self.n_scenes)
         self._ordered(t, lambda: load_library().sb_batch_reset_device(self._h, ctypes.c_void_p(ptr)))
+
+    def checkpoint(self, mask=None):
+        """The inverse of reset(): scenes whose mask entry is nonzero (as in reset(); None = all) make their CURRENT state their
+        reset state -- particles, beam state, beam mapping, live-beam count, pending break flags, removed beams.  Scenes never
+        uploaded are skipped.  Only enqueues."""
+        if mask is None:
+            return self._check(load_library().sb_batch_checkpoint_device(self._h, None))
+        ptr, t = self._device_buffer("checkpoint", mask, ("uint8", "bool"), self.n_scenes)
+        self._ordered(t, lambda: load_library().sb_batch_checkpoint_device(self._h, ctypes.c_void_p(ptr)))
+
+    def fork(self, src, constants=False, as_reset=False):
+        """Scene i becomes a copy of scene src[i]: `src` is an int32 / uint32 torch tensor of n_scenes entries on the device (or a
+        device pointer to as many 32-bit words).  Every source is read as it was before the call, so permutations, swaps and a
+        broadcast from a scene that is itself overwritten are well defined.  src[i] == i and FORK_KEEP (-1 in an int32 tensor)
+        leave scene i as it is; so does any other entry outside the batch, counted in info("fork_bad_sources").
+        Copied: topology and materials, particles, beam state, beam mapping, counts, pending break flags, removed beams.  The
+        destination keeps its user input and, unless constants=True, its physics constants.  Its reset state becomes the
+        source's (reset() then takes it where it would take the source), or, with as_reset=True, the forked state itself.  A
+        source never uploaded makes the destination a never-uploaded scene.  Only enqueues; the first fork allocates the
+        staging blobs (info("fork_staging_bytes"))."""
+        ptr, t = self._device_buffer("fork", src, ("int32", "uint32"), self.n_scenes * 4)
+        if t and src.numel() != self.n_scenes:
+            raise ValueError("fork: one source per scene is needed (%d), not %d" % (self.n_scenes, src.numel()))
+        flags = (FORK_CONSTANTS if constants else 0) | (FORK_AS_RESET if as_reset else 0)
+        self._ordered(t, lambda: load_library().sb_batch_fork_device(self._h, ctypes.c_void_p(ptr), flags))
 
     def sync(self):
         self._check(load_library().sb_batch_sync(self._h))
@@ -236,6 +267,15 @@ class BatchEngine:
         rows of a scene's particles are read).  Beams, counts, mappings and pending break flags are untouched."""
         ptr, t = self._device_buffer("write_particles_device", src, "float32", self.n_scenes * self.max_particles * PARTICLE_STRIDE)
         self._ordered(t, lambda: load_library().sb_batch_write_particles_device(self._h, ctypes.c_void_p(ptr)))
+
+    def write_beams_device(self, src, target_length=True, last_length=False):
+        """The counterpart of write_particles_device for beams: `src` is float32 [n_scenes, max_beams, 4] on the device in
+        read_state_device's beam layout; target_length / last_length select which of the first two floats of every row are
+        written (strain and stress never are).  Only rows of beams of a scene's latest upload are read; a removed beam's row is
+        written but inert.  Counts, mappings, removed beams and pending break flags are untouched.  Only enqueues."""
+        fields = (BEAM_TARGET_LENGTH if target_length else 0) | (BEAM_LAST_LENGTH if last_length else 0)
+        ptr, t = self._device_buffer("write_beams_device", src, "float32", self.n_scenes * self.max_beams * 16)
+        self._ordered(t, lambda: load_library().sb_batch_write_beams_device(self._h, ctypes.c_void_p(ptr), fields))
 
     def state_tensors(self):
         """(particles [N, maxP, 6] float32, beams [N, maxB, 4] float32, alive [N, maxB] bool) of the current state as new torch

@@ -16,7 +16,7 @@
 #define SB_BM_P 1u       // metadata.particle_i_c
 #define SB_BM_B 6u       // metadata.beam_i_c (live beam slots)
 #define SB_BM_CONSTS 12u // 8 physics constants, 8 user input words
-#define SB_BM_B0 28u     // beam slots at the latest upload
+#define SB_BM_B0 28u     // beam slots of the reset state (the latest upload, checkpoint or fork); k_batch_reset alone reads it
 #define SB_BM_LOADED 29u // 1 once uploaded
 #define SB_BATCH_MAT_ROW 6u // length, spring, damp, yield, limit, 1/length
 
@@ -69,6 +69,11 @@ struct sb_batch {
     int collide = 0; // SB_BATCH_NO_CONTACTS / _WALK / _CELLS
     uint32_t grid_min_particles = 0; // resolved
     unsigned char *stage = nullptr; // device staging of one upload: meta words, constant blob, state blob
+    // sb_batch_fork_device (made at the first fork): per scene the metadata words, the constant blob, the state blob and the reset
+    // blob of its source, and the count of entries that named no scene
+    unsigned char *fork_stage = nullptr;
+    unsigned long long *fork_bad = nullptr;
+    size_t fork_stage_bytes = 0;
     uint64_t frames_done = 0, substeps_done = 0;
     int scenes_per_cu = 0, vgprs = 0, scratch = 0;
     SbBatchRender *render = nullptr; // what the renderer keeps between calls (made at the first render)

@@ -373,6 +373,87 @@ __global__ __launch_bounds__(SBB_BLOCK) void k_batch_import(SbBatchView V, const
         if (pex[i / 6u]) part[i] = particles[(size_t)scene * V.maxP * 6u + i];
 }
 
+// ---------------------------------------------------------------- fork, checkpoint, beam import
+// Blobs are copied by blockIdx.y's share of the workgroups of a scene: the blobs of the limit capacity are 100 KB and more.
+static uint32_t sb_batch_copy_chunks(const SbBatchView &V) { return std::max(1u, cdivb(std::max(V.cst_bytes, V.st_bytes) / 16u, SBB_BLOCK * 4u)); }
+SB_DEV void sbb_copy16(unsigned char *dst, const unsigned char *src, uint32_t bytes)
+{
+    for (uint32_t i = blockIdx.y * SBB_BLOCK + threadIdx.x; i < bytes / 16u; i += gridDim.y * SBB_BLOCK) ((uint4 *)dst)[i] = ((const uint4 *)src)[i];
+}
+// the scene that scene i becomes a copy of; SB_BATCH_FORK_KEEP: scene i stays (KEEP itself, i, or an entry that names no scene)
+SB_DEV uint32_t sbb_fork_source(const uint32_t *__restrict__ src, uint32_t i, uint32_t n)
+{
+    const uint32_t s = src[i];
+    return (s >= n || s == i) ? SB_BATCH_FORK_KEEP : s;
+}
+SB_DEV size_t sbb_fork_stride(const SbBatchView &V) { return (size_t)SB_BM_WORDS * 4u + V.cst_bytes + 2u * (size_t)V.st_bytes; }
+
+// pass 1 only READS the batch: scene i's staging row gets the metadata words and the blobs of its source
+__global__ __launch_bounds__(SBB_BLOCK) void k_batch_fork_gather(SbBatchView V, const uint32_t *__restrict__ src, unsigned char *stage,
+                                                                  unsigned long long *bad, uint32_t flags)
+{
+    const uint32_t scene = blockIdx.x;
+    if (scene >= V.n_scenes) return;
+    const uint32_t raw = src[scene];
+    if (raw >= V.n_scenes && raw != SB_BATCH_FORK_KEEP && blockIdx.y == 0u && threadIdx.x == 0u) (void)atomicAdd(bad, 1ull);
+    const uint32_t s = sbb_fork_source(src, scene, V.n_scenes);
+    if (s == SB_BATCH_FORK_KEEP) return;
+    unsigned char *row = stage + (size_t)scene * sbb_fork_stride(V);
+    if (blockIdx.y == 0u && threadIdx.x < SB_BM_WORDS) ((uint32_t *)row)[threadIdx.x] = V.meta[(size_t)s * SB_BM_WORDS + threadIdx.x];
+    row += SB_BM_WORDS * 4u;
+    sbb_copy16(row, V.cst + (size_t)s * V.cst_bytes, V.cst_bytes);
+    sbb_copy16(row + V.cst_bytes, V.st + (size_t)s * V.st_bytes, V.st_bytes);
+    if (!(flags & SB_BATCH_FORK_AS_RESET)) sbb_copy16(row + V.cst_bytes + V.st_bytes, V.rst + (size_t)s * V.st_bytes, V.st_bytes);
+}
+
+// pass 2 only WRITES it (and reads nothing of it that pass 2 writes): what describes the scene comes from the row, the user
+// input stays, the physics constants stay unless asked for
+__global__ __launch_bounds__(SBB_BLOCK) void k_batch_fork_scatter(SbBatchView V, const uint32_t *__restrict__ src, const unsigned char *stage,
+                                                                   uint32_t flags)
+{
+    const uint32_t scene = blockIdx.x;
+    if (scene >= V.n_scenes) return;
+    if (sbb_fork_source(src, scene, V.n_scenes) == SB_BATCH_FORK_KEEP) return;
+    const unsigned char *row = stage + (size_t)scene * sbb_fork_stride(V);
+    const bool as_reset = (flags & SB_BATCH_FORK_AS_RESET) != 0u;
+    if (blockIdx.y == 0u && threadIdx.x < SB_BM_WORDS) {
+        const uint32_t k = threadIdx.x, *m = (const uint32_t *)row;
+        uint32_t *meta = V.meta + (size_t)scene * SB_BM_WORDS;
+        if (k < SB_BM_CONSTS || k == SB_BM_LOADED || ((flags & SB_BATCH_FORK_CONSTANTS) && k < SB_BM_CONSTS + 8u)) meta[k] = m[k];
+        else if (k == SB_BM_B0) meta[k] = as_reset ? m[SB_BM_B] : m[SB_BM_B0];
+    }
+    row += SB_BM_WORDS * 4u;
+    sbb_copy16(V.cst + (size_t)scene * V.cst_bytes, row, V.cst_bytes);
+    sbb_copy16(V.st + (size_t)scene * V.st_bytes, row + V.cst_bytes, V.st_bytes);
+    sbb_copy16(V.rst + (size_t)scene * V.st_bytes, row + V.cst_bytes + (as_reset ? 0u : V.st_bytes), V.st_bytes);
+}
+
+// k_batch_reset the other way round
+__global__ __launch_bounds__(SBB_BLOCK) void k_batch_checkpoint(SbBatchView V, const unsigned char *__restrict__ mask)
+{
+    const uint32_t scene = blockIdx.x;
+    if (scene >= V.n_scenes) return;
+    if (mask && mask[scene] == 0) return;
+    uint32_t *meta = V.meta + (size_t)scene * SB_BM_WORDS;
+    if (meta[SB_BM_LOADED] == 0u) return;
+    sbb_copy16(V.rst + (size_t)scene * V.st_bytes, V.st + (size_t)scene * V.st_bytes, V.st_bytes);
+    if (blockIdx.y == 0u && threadIdx.x == 0u) meta[SB_BM_B0] = meta[SB_BM_B];
+}
+
+__global__ __launch_bounds__(SBB_BLOCK) void k_batch_import_beams(SbBatchView V, const float *__restrict__ beams, uint32_t fields)
+{
+    const uint32_t scene = blockIdx.x;
+    if (scene >= V.n_scenes) return;
+    const unsigned char *bex = V.cst + (size_t)scene * V.cst_bytes + V.o_bex;
+    float *bstate = (float *)(V.st + (size_t)scene * V.st_bytes + V.o_bstate);
+    const float *in = beams + (size_t)scene * V.maxB * 4u;
+    for (uint32_t i = threadIdx.x; i < V.maxB; i += SBB_BLOCK) {
+        if (!bex[i]) continue;
+        if (fields & SB_BATCH_BEAM_TARGET_LENGTH) bstate[4u * i] = in[4u * i];
+        if (fields & SB_BATCH_BEAM_LAST_LENGTH) bstate[4u * i + 1u] = in[4u * i + 1u];
+    }
+}
+
 // ---------------------------------------------------------------- host
 thread_local std::string g_batch_create_error;
 
@@ -454,6 +535,8 @@ sb_status sb_batch_destroy(sb_batch *b)
     if (b->V.rst) (void)hipFree(b->V.rst);
     if (b->V.cell_stats) (void)hipFree(b->V.cell_stats);
     if (b->stage) (void)hipFree(b->stage);
+    if (b->fork_stage) (void)hipFree(b->fork_stage);
+    if (b->fork_bad) (void)hipFree(b->fork_bad);
     sbb_render_release(b);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
@@ -767,6 +850,56 @@ sb_status sb_batch_write_particles_device(sb_batch *b, const void *device_partic
     return check_launch(b, "sb_batch_write_particles_device");
 }
 
+sb_status sb_batch_fork_device(sb_batch *b, const void *device_src_u32, uint32_t flags)
+{
+    if (!b) return SB_ERR_INVALID;
+    if (!device_src_u32 || ((uintptr_t)device_src_u32 & 3u)) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_fork_device: null or misaligned device buffer");
+    if (flags & ~(SB_BATCH_FORK_CONSTANTS | SB_BATCH_FORK_AS_RESET)) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_fork_device: unknown flags 0x%x", flags);
+    const SbBatchView &V = b->V;
+    const uint32_t n = b->opt.n_scenes;
+    SB_HIP(b, hipSetDevice(b->device));
+    if (!b->fork_stage) { // the staging blobs: once, kept
+        const size_t bytes = (size_t)n * ((size_t)SB_BM_WORDS * 4u + V.cst_bytes + 2u * (size_t)V.st_bytes);
+        unsigned char *stage = nullptr;
+        unsigned long long *bad = nullptr;
+        hipError_t r = hipMalloc((void **)&stage, bytes);
+        if (r == hipSuccess && (r = hipMalloc((void **)&bad, sizeof *bad)) == hipSuccess) r = hipMemsetAsync(bad, 0, sizeof *bad, b->stream);
+        if (r != hipSuccess) {
+            (void)hipGetLastError();
+            if (stage) (void)hipFree(stage);
+            if (bad) (void)hipFree(bad);
+            SB_FAIL(b, r == hipErrorOutOfMemory ? SB_ERR_OOM : SB_ERR_HIP, "sb_batch_fork_device: %zu bytes of staging: %s", bytes, hipGetErrorString(r));
+        }
+        b->fork_stage = stage;
+        b->fork_bad = bad;
+        b->fork_stage_bytes = bytes;
+    }
+    const dim3 grid(n, sb_batch_copy_chunks(V));
+    k_batch_fork_gather<<<grid, SBB_BLOCK, 0, b->stream>>>(V, (const uint32_t *)device_src_u32, b->fork_stage, b->fork_bad, flags);
+    SB_TRY(check_launch(b, "sb_batch_fork_device (gather)"));
+    k_batch_fork_scatter<<<grid, SBB_BLOCK, 0, b->stream>>>(V, (const uint32_t *)device_src_u32, b->fork_stage, flags);
+    return check_launch(b, "sb_batch_fork_device (scatter)");
+}
+
+sb_status sb_batch_checkpoint_device(sb_batch *b, const void *device_mask_u8)
+{
+    if (!b) return SB_ERR_INVALID;
+    SB_HIP(b, hipSetDevice(b->device));
+    k_batch_checkpoint<<<dim3(b->opt.n_scenes, sb_batch_copy_chunks(b->V)), SBB_BLOCK, 0, b->stream>>>(b->V, (const unsigned char *)device_mask_u8);
+    return check_launch(b, "sb_batch_checkpoint_device");
+}
+
+sb_status sb_batch_write_beams_device(sb_batch *b, const void *device_beams, uint32_t fields)
+{
+    if (!b) return SB_ERR_INVALID;
+    if (!device_beams || ((uintptr_t)device_beams & 3u)) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_write_beams_device: null or misaligned device buffer");
+    if (fields == 0u || (fields & ~(SB_BATCH_BEAM_TARGET_LENGTH | SB_BATCH_BEAM_LAST_LENGTH)))
+        SB_FAIL(b, SB_ERR_INVALID, "sb_batch_write_beams_device: fields 0x%x is not a mask of SB_BATCH_BEAM_TARGET_LENGTH / _LAST_LENGTH", fields);
+    SB_HIP(b, hipSetDevice(b->device));
+    k_batch_import_beams<<<b->opt.n_scenes, SBB_BLOCK, 0, b->stream>>>(b->V, (const float *)device_beams, fields);
+    return check_launch(b, "sb_batch_write_beams_device");
+}
+
 sb_status sb_batch_load_scene(sb_batch *b, uint32_t scene, void *metadata, size_t metadata_bytes, void *mapping, size_t mapping_bytes, void *particles,
                               size_t particles_bytes, void *beams, size_t beams_bytes)
 {
@@ -855,6 +988,18 @@ sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value)
             SB_HIP(b, hipMemcpy(st, b->V.cell_stats, sizeof st, hipMemcpyDeviceToHost));
         }
         *value = st[k == "cell_substeps" ? 0 : 1];
+    }
+    else if (k == "constant_blob_bytes") *value = b->V.cst_bytes;
+    else if (k == "state_blob_bytes") *value = b->V.st_bytes;
+    else if (k == "fork_staging_bytes") *value = b->fork_stage_bytes;
+    else if (k == "fork_bad_sources") {
+        unsigned long long bad = 0ull;
+        if (b->fork_bad) {
+            SB_HIP(b, hipSetDevice(b->device));
+            SB_HIP(b, hipStreamSynchronize(b->stream));
+            SB_HIP(b, hipMemcpy(&bad, b->fork_bad, sizeof bad, hipMemcpyDeviceToHost));
+        }
+        *value = bad;
     }
     else if (sbb_render_info(b, key, value)) return SB_OK;
     else SB_FAIL(b, SB_ERR_INVALID, "sb_batch_get_info: unknown key '%s'", key);
