@@ -427,7 +427,7 @@ sb_status sb_write_particles_device(sb_engine *e, const void *device_particles);
  *   Limits: per scene at most SB_BATCH_MAX_PARTICLES particles and SB_BATCH_MAX_BEAMS beams (what one workgroup holds).
  *   When do calls return?  sb_batch_frame / _step / _delete_pass / _reset_device / _write_user_input[_device] /
  *     _set_physics_constants / _read_state_device / _write_particles_device / _fork_device / _checkpoint_device /
- *     _write_beams_device only ENQUEUE on the batch's stream (device buffers must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
+ *     _write_beams_device / _summary_device / _rollout_device only ENQUEUE on the batch's stream (device buffers must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
  *     sb_batch_render_device only ENQUEUES (its device buffer must stay valid likewise); sb_batch_render_scene WAITS.
  *   Errors: every call returns an sb_status; sb_batch_last_error(b) gives the message (b == NULL: the last failed
  *     sb_batch_create of the calling thread).  Options are checked BEFORE a device is looked for. */
@@ -538,6 +538,43 @@ sb_status sb_batch_checkpoint_device(sb_batch *b, const void *device_mask_u8);
 #define SB_BATCH_BEAM_LAST_LENGTH 2u
 sb_status sb_batch_write_beams_device(sb_batch *b, const void *device_beams, uint32_t fields);
 
+/* ---- per-scene summary rows and multi-frame rollouts on the device ----
+ * sb_batch_summary_device -- one row of SB_BATCH_SUMMARY_WORDS floats per scene into device_out_f32[n_scenes][SB_BATCH_SUMMARY_WORDS],
+ * in ONE launch: what a done-test or a score reads of a scene without exporting its state.  It only ENQUEUES and only READS the
+ * batch: frame, summary, frame equals frame, frame bit for bit, pending break flags included.  Every word of every row is
+ * written.  Counts are floats (all <= 4096: exact).  A FINITE PARTICLE is one whose six floats are all finite; a FINITE BEAM is a
+ * live beam (of the scene's upload and not removed) whose strain and stress are both finite.
+ *    0  particles of the scene                      1  live beam slots (metadata.beam_i_c)
+ *    2  beams of the upload that a delete pass has removed
+ *    3  break flags pending (set bits among the live beam slots)
+ *    4  particles that are not finite               5  live beams that are not finite
+ *    6, 7  mean position x, y                       8, 9  mean velocity x, y            (over the finite particles)
+ *   10 .. 13  min x, min y, max x, max y            (over the finite particles)
+ *   14  kinetic energy, the sum of 0.5 (vx^2 + vy^2)   15  max of vx^2 + vy^2           (over the finite particles)
+ *   16, 17, 18  max strain, max stress, min stress  19  mean strain                     (over the finite beams)
+ *   20  1 if the scene was ever uploaded (or forked from one that was), else 0          21 .. 23  0
+ * A statistic over an empty set (means, extremes) is the quiet NaN 0x7FC00000; counts and the energy are 0 then.  A scene never
+ * uploaded gives counts 0, word 20 = 0 and NaN elsewhere.
+ * The arithmetic is pinned, so a row is reproducible bit for bit: sums are taken in double; leaf i of a sum is the value at DATA
+ * index i (+0.0 where no finite particle / beam lives), i = 0 .. W-1, W the smallest power of two >= max_particles (particle sums)
+ * or >= max_beams (beam sums); the reduction is the stride-halving tree, for h = W/2, W/4, .. 1: s[i] += s[i + h] (i < h).  The
+ * energy leaf is 0.5 * ((double)vx * vx + (double)vy * vy), the candidate of word 15 the same without the 0.5; a mean is
+ * (float)(sum / (double)count); energy and word 15 are rounded to float once, at the end (beyond float's range: +inf).  Extremes
+ * are plain comparisons (-0 and +0 compare equal: either may be returned).
+ * Errors: SB_ERR_INVALID for a NULL handle, a NULL output, a pointer that is not 4-byte aligned -- before anything touches a device.
+ *
+ * sb_batch_rollout_device -- n_frames times, in this order: slice t of device_inputs[n_frames][n_scenes][32 B] applied exactly as
+ * sb_batch_write_user_input_device would (NULL: the inputs stay as they are); one frame exactly as sb_batch_frame(b, 1); the
+ * summary of the state after that frame into slice t of device_summaries[n_frames][n_scenes][SB_BATCH_SUMMARY_WORDS] (NULL: none).
+ * A host-side sequence of those launches, enqueued in one call: bit for bit the result of the individual calls; "frames_done" and
+ * "substeps_done" advance as they would; afterwards the scenes hold the inputs of the last slice.  n_frames = 0: SB_OK, nothing
+ * done.  A pointer that is not 4-byte aligned: SB_ERR_INVALID, before anything touches a device. */
+#define SB_BATCH_SUMMARY_WORDS 24u
+sb_status sb_batch_summary_device(sb_batch *b, void *device_out_f32 /* [n_scenes][SB_BATCH_SUMMARY_WORDS] float */);
+sb_status sb_batch_rollout_device(sb_batch *b, uint32_t n_frames,
+                                  const void *device_inputs  /* [n_frames][n_scenes][32 B] or NULL: inputs stay as they are */,
+                                  void *device_summaries     /* [n_frames][n_scenes][SB_BATCH_SUMMARY_WORDS] float or NULL */);
+
 /* scene i back into host buffers exactly as sb_load_buffers returns a single engine in the same state (counts in the metadata,
  * the mapping after the delete passes' stable in-place compactions, beam records with strain / stress; only records reachable
  * through the uploaded mapping are written; any pointer may be NULL).  SB_ERR_STATE for a scene never uploaded. */
@@ -584,7 +621,8 @@ sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream);
  * "constant_blob_bytes" / "state_blob_bytes" (device memory per scene of what only an upload or a fork writes / of what stepping
  * changes; the latter is kept twice, current and reset); sb_batch_fork_device: "fork_staging_bytes" (device memory of the staging
  * blobs; 0 before the first fork) and, WAITING for the stream, "fork_bad_sources" (entries >= n_scenes other than
- * SB_BATCH_FORK_KEEP seen by all forks so far) */
+ * SB_BATCH_FORK_KEEP seen by all forks so far); sb_batch_summary_device: "summary_words" (SB_BATCH_SUMMARY_WORDS),
+ * "summary_kernel_vgprs", "summary_kernel_scratch_bytes" */
 sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value);
 const char *sb_batch_last_error(const sb_batch *b);
 

@@ -14,6 +14,11 @@ FORK_KEEP = 0xFFFFFFFF                                # SB_BATCH_FORK_KEEP: this
 FORK_CONSTANTS, FORK_AS_RESET = 1, 2                  # SB_BATCH_FORK_*
 BEAM_TARGET_LENGTH, BEAM_LAST_LENGTH = 1, 2           # SB_BATCH_BEAM_*
 GRID_NEVER = 0xFFFFFFFF                               # sb_batch_options.grid_min_particles: no scene takes the cells
+SUMMARY_WORDS = 24                                    # SB_BATCH_SUMMARY_WORDS
+# the words of a summary row, in order (include/softbody.h, sb_batch_summary_device): s[:, SUMMARY_FIELDS.index("kinetic_energy")]
+SUMMARY_FIELDS = ("particles", "live_beams", "removed_beams", "pending_breaks", "nonfinite_particles", "nonfinite_beams",
+                  "mean_x", "mean_y", "mean_vx", "mean_vy", "min_x", "min_y", "max_x", "max_y", "kinetic_energy", "max_speed_sq",
+                  "max_strain", "max_stress", "min_stress", "mean_strain", "uploaded", "reserved_21", "reserved_22", "reserved_23")
 
 
 class SbBatchOptions(ctypes.Structure):
@@ -56,6 +61,8 @@ def load_library():
     L.sb_batch_fork_device.argtypes = [vp, vp, u32]
     L.sb_batch_checkpoint_device.argtypes = [vp, vp]
     L.sb_batch_write_beams_device.argtypes = [vp, vp, u32]
+    L.sb_batch_summary_device.argtypes = [vp, vp]
+    L.sb_batch_rollout_device.argtypes = [vp, u32, vp, vp]
     L.sb_batch_load_scene.argtypes = [vp, u32, vp, sz, vp, sz, vp, sz, vp, sz]
     L.sb_batch_render_device.argtypes = [vp, ctypes.POINTER(SbBatchRenderOptions), vp]
     L.sb_batch_render_scene.argtypes = [vp, u32, ctypes.POINTER(SbBatchRenderOptions), vp, sz]
@@ -287,6 +294,59 @@ class BatchEngine:
         a = torch.zeros((self.n_scenes, self.max_beams), dtype=torch.bool, device=dev)
         self.read_state_device(p, b, a)
         return p, b, a
+
+    # ---- per-scene statistics and rollouts (sb_batch_summary_device / sb_batch_rollout_device)
+    def summary(self, out=None):
+        """One row of SUMMARY_WORDS statistics per scene (SUMMARY_FIELDS names the columns) in one launch: a float32 tensor
+        [n_scenes, 24] on the batch's device -- counts, means, extremes and the kinetic energy of the finite particles, strain
+        and stress of the finite live beams; an empty set gives NaN; every word is written.  `out`: a device pointer (int) or a
+        contiguous float32 torch tensor of at least n_scenes * 24 elements to write into.  Only reads the batch, only enqueues;
+        torch's current stream is ordered after it."""
+        import torch
+        n = self.n_scenes
+        if out is None:
+            out = torch.empty((n, SUMMARY_WORDS), dtype=torch.float32, device=torch.device("cuda", self.device))
+        ptr, t = self._device_buffer("summary: out", out, "float32", n * SUMMARY_WORDS * 4)
+        self._ordered(t, lambda: load_library().sb_batch_summary_device(self._h, ctypes.c_void_p(ptr)))
+        if t and tuple(out.shape) != (n, SUMMARY_WORDS):
+            return out.view(-1)[:n * SUMMARY_WORDS].view(n, SUMMARY_WORDS)
+        return out
+
+    def rollout(self, inputs=None, frames=None, summary=True, out=None):
+        """`frames` times: (scene i gets the 32 bytes inputs[t, i] as write_user_input would write them), frame(), (summary()
+        into row t) -- enqueued in one call, bit for bit what the individual calls give.  inputs: a device pointer (int) or a
+        contiguous torch tensor of frames x n_scenes x 32 bytes on the batch's device (any dtype, e.g. float32 [T, N, 8]);
+        None: the inputs stay as they are.  frames: None = inputs.shape[0]; required when `inputs` is None or a pointer.
+        Returns a float32 tensor [frames, n_scenes, 24] (`out`: a pointer or a float32 tensor of at least that many elements to
+        write into), or None with summary=False.  Afterwards the scenes hold the inputs of the last slice."""
+        import torch
+        n = self.n_scenes
+        if frames is None:
+            if not isinstance(inputs, torch.Tensor) or inputs.dim() == 0:
+                raise ValueError("rollout: `frames` is needed when `inputs` is not a tensor with a leading frame dimension")
+            frames = inputs.shape[0]
+        frames = int(frames)
+        if frames < 0:
+            raise ValueError("rollout: frames is %d" % frames)
+        iptr = optr = None
+        tensors = False
+        if inputs is not None:
+            iptr, t = self._device_buffer("rollout: inputs", inputs, None, frames * n * 32)
+            tensors |= t
+        if summary:
+            if out is None:
+                out = torch.empty((frames, n, SUMMARY_WORDS), dtype=torch.float32, device=torch.device("cuda", self.device))
+            optr, t = self._device_buffer("rollout: out", out, "float32", frames * n * SUMMARY_WORDS * 4)
+            tensors |= t
+        elif out is not None:
+            raise ValueError("rollout: `out` is given but summary=False")
+        vp = ctypes.c_void_p
+        self._ordered(tensors, lambda: load_library().sb_batch_rollout_device(self._h, frames, vp(iptr), vp(optr)))
+        if not summary:
+            return None
+        if isinstance(out, torch.Tensor) and tuple(out.shape) != (frames, n, SUMMARY_WORDS):
+            return out.view(-1)[:frames * n * SUMMARY_WORDS].view(frames, n, SUMMARY_WORDS)
+        return out
 
     # ---- pictures (sb_batch_render_device / sb_batch_render_scene; DESIGN.md 5.11)
     def _render_options(self, resolution, bounds_size, particle_radius, first=0, count=0):
