@@ -427,7 +427,7 @@ sb_status sb_write_particles_device(sb_engine *e, const void *device_particles);
  *   Limits: per scene at most SB_BATCH_MAX_PARTICLES particles and SB_BATCH_MAX_BEAMS beams (what one workgroup holds).
  *   When do calls return?  sb_batch_frame / _step / _delete_pass / _reset_device / _write_user_input[_device] /
  *     _set_physics_constants / _read_state_device / _write_particles_device / _fork_device / _checkpoint_device /
- *     _write_beams_device / _summary_device / _rollout_device only ENQUEUE on the batch's stream (device buffers must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
+ *     _write_beams_device / _summary_device / _rollout_device / _bodies_device only ENQUEUE on the batch's stream (device buffers must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
  *     sb_batch_render_device only ENQUEUES (its device buffer must stay valid likewise); sb_batch_render_scene WAITS.
  *   Errors: every call returns an sb_status; sb_batch_last_error(b) gives the message (b == NULL: the last failed
  *     sb_batch_create of the calling thread).  Options are checked BEFORE a device is looked for. */
@@ -575,6 +575,29 @@ sb_status sb_batch_rollout_device(sb_batch *b, uint32_t n_frames,
                                   const void *device_inputs  /* [n_frames][n_scenes][32 B] or NULL: inputs stay as they are */,
                                   void *device_summaries     /* [n_frames][n_scenes][SB_BATCH_SUMMARY_WORDS] float or NULL */);
 
+/* ---- the connected bodies of every scene, labelled on the device ----
+ * sb_batch_bodies_device -- what the breaking of beams did to the bodies, in ONE launch.  A BODY is a connected component of the
+ * graph whose nodes are the scene's particles and whose edges are its LIVE beams (the beam slots 0 .. metadata.beam_i_c - 1).  A
+ * beam whose break flag is pending is still live and still connects; it stops connecting when a delete pass has removed it,
+ * exactly as it stops exerting force.  Every output is indexed by particle DATA index, like sb_batch_read_state_device's rows;
+ * any of the three may be NULL (not written), not all of them; every word of a non-NULL output is written.
+ *   labels[s][i]  the smallest data index among the particles of the body that particle i belongs to; -1 where data index i holds
+ *                 no particle of the scene's upload.  (The definition names no schedule: the bits are the same on every run.)
+ *   sizes[s][i]   {particles, live beams} of the body whose label is i; {0, 0} in every other row.  A beam belongs to the body of
+ *                 its endpoints.
+ *   counts[s]     SB_BATCH_BODY_WORDS words: 0 bodies, 1 particles of the largest body, 2 bodies of exactly one particle,
+ *                 3 label of the largest body (of several that large, the smallest label).  A scene of no particles, or one never
+ *                 uploaded, gives {0, 0, 0, -1} and labels of -1.
+ * labels is what torch.index_add_ needs for a statistic per body; counts[:, 0] is the "still whole" / "torn in two" test.
+ * It only ENQUEUES and only READS the batch: frame, bodies, frame equals frame, frame bit for bit.  Integers only.
+ * Errors: SB_ERR_INVALID for a NULL handle, for three NULL outputs, for a pointer that is not 4-byte aligned -- before anything
+ * touches a device. */
+#define SB_BATCH_BODY_WORDS 4u
+sb_status sb_batch_bodies_device(sb_batch *b,
+                                 void *device_labels_i32  /* [n_scenes][max_particles] int32 or NULL */,
+                                 void *device_sizes_i32   /* [n_scenes][max_particles][2] int32 or NULL */,
+                                 void *device_counts_i32  /* [n_scenes][SB_BATCH_BODY_WORDS] int32 or NULL */);
+
 /* scene i back into host buffers exactly as sb_load_buffers returns a single engine in the same state (counts in the metadata,
  * the mapping after the delete passes' stable in-place compactions, beam records with strain / stress; only records reachable
  * through the uploaded mapping are written; any pointer may be NULL).  SB_ERR_STATE for a scene never uploaded. */
@@ -622,7 +645,8 @@ sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream);
  * changes; the latter is kept twice, current and reset); sb_batch_fork_device: "fork_staging_bytes" (device memory of the staging
  * blobs; 0 before the first fork) and, WAITING for the stream, "fork_bad_sources" (entries >= n_scenes other than
  * SB_BATCH_FORK_KEEP seen by all forks so far); sb_batch_summary_device: "summary_words" (SB_BATCH_SUMMARY_WORDS),
- * "summary_kernel_vgprs", "summary_kernel_scratch_bytes" */
+ * "summary_kernel_vgprs", "summary_kernel_scratch_bytes"; sb_batch_bodies_device: "body_words" (SB_BATCH_BODY_WORDS),
+ * "bodies_kernel_vgprs", "bodies_kernel_scratch_bytes", "bodies_lds_bytes" (LDS of one workgroup at this batch's capacity) */
 sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value);
 const char *sb_batch_last_error(const sb_batch *b);
 

@@ -19,6 +19,9 @@ SUMMARY_WORDS = 24                                    # SB_BATCH_SUMMARY_WORDS
 SUMMARY_FIELDS = ("particles", "live_beams", "removed_beams", "pending_breaks", "nonfinite_particles", "nonfinite_beams",
                   "mean_x", "mean_y", "mean_vx", "mean_vy", "min_x", "min_y", "max_x", "max_y", "kinetic_energy", "max_speed_sq",
                   "max_strain", "max_stress", "min_stress", "mean_strain", "uploaded", "reserved_21", "reserved_22", "reserved_23")
+BODY_WORDS = 4                                        # SB_BATCH_BODY_WORDS
+# the words of a row of bodies()'s counts, in order (include/softbody.h, sb_batch_bodies_device)
+BODY_FIELDS = ("bodies", "largest_particles", "single_particles", "largest_label")
 
 
 class SbBatchOptions(ctypes.Structure):
@@ -63,6 +66,7 @@ def load_library():
     L.sb_batch_write_beams_device.argtypes = [vp, vp, u32]
     L.sb_batch_summary_device.argtypes = [vp, vp]
     L.sb_batch_rollout_device.argtypes = [vp, u32, vp, vp]
+    L.sb_batch_bodies_device.argtypes = [vp, vp, vp, vp]
     L.sb_batch_load_scene.argtypes = [vp, u32, vp, sz, vp, sz, vp, sz, vp, sz]
     L.sb_batch_render_device.argtypes = [vp, ctypes.POINTER(SbBatchRenderOptions), vp]
     L.sb_batch_render_scene.argtypes = [vp, u32, ctypes.POINTER(SbBatchRenderOptions), vp, sz]
@@ -347,6 +351,42 @@ class BatchEngine:
         if isinstance(out, torch.Tensor) and tuple(out.shape) != (frames, n, SUMMARY_WORDS):
             return out.view(-1)[:frames * n * SUMMARY_WORDS].view(frames, n, SUMMARY_WORDS)
         return out
+
+    # ---- connected bodies (sb_batch_bodies_device)
+    def bodies(self, labels=None, sizes=False, counts=None):
+        """The connected bodies of every scene in one launch: particles joined by LIVE beams (a pending break flag still
+        connects, a beam removed by a delete pass does not).  Returns (labels, counts), int32 tensors on the batch's device, or
+        (labels, counts, sizes) with sizes=True or a tensor.  labels [n_scenes, max_particles]: at particle DATA index i (the rows
+        of read_state_device) the smallest data index of i's body, -1 where no particle lives -- what torch.index_add_ takes for a
+        statistic per body.  counts [n_scenes, 4] (BODY_FIELDS names the columns): bodies, particles of the largest, bodies of one
+        particle, label of the largest (the smallest label on a tie; -1 in a scene of no particles or never uploaded).  sizes
+        [n_scenes, max_particles, 2]: {particles, live beams} of the body at its label's row, {0, 0} in every other row.  Every
+        word is written.  labels / counts / sizes: a device pointer (int) or a contiguous int32 torch tensor of at least that
+        many elements to write into.  Only reads the batch, only enqueues; torch's current stream is ordered after it."""
+        import torch
+        n, dev = self.n_scenes, torch.device("cuda", self.device)
+        shapes = ((n, self.max_particles), (n, self.max_particles, 2), (n, BODY_WORDS))
+        outs = [labels, None if sizes is False else sizes, counts]
+        want = (True, sizes is not False, True)
+        for k, what in enumerate(("labels", "sizes", "counts")):   # (what the caller gave is looked at before anything is allocated)
+            if outs[k] is not None and outs[k] is not True:
+                self._device_buffer("bodies: " + what, outs[k], "int32", int(np.prod(shapes[k])) * 4)
+        ptrs, tensors = [], False
+        for k in range(3):
+            if not want[k]:
+                ptrs.append(None)
+                continue
+            if outs[k] is None or outs[k] is True:
+                outs[k] = torch.empty(shapes[k], dtype=torch.int32, device=dev)
+            numel = int(np.prod(shapes[k]))
+            ptr, t = self._device_buffer("bodies", outs[k], "int32", numel * 4)
+            if t and tuple(outs[k].shape) != shapes[k]:
+                outs[k] = outs[k].view(-1)[:numel].view(shapes[k])
+            ptrs.append(ptr)
+            tensors |= t
+        vp = ctypes.c_void_p
+        self._ordered(tensors, lambda: load_library().sb_batch_bodies_device(self._h, vp(ptrs[0]), vp(ptrs[1]), vp(ptrs[2])))
+        return (outs[0], outs[2], outs[1]) if want[1] else (outs[0], outs[2])
 
     # ---- pictures (sb_batch_render_device / sb_batch_render_scene; DESIGN.md 5.11)
     def _render_options(self, resolution, bounds_size, particle_radius, first=0, count=0):

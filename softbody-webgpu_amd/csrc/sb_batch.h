@@ -1,5 +1,6 @@
 // sb_batch.h -- what the files of the sb_batch_* group share: the device memory of a batch and its host object
-// (sb_batch.hip: upload, stepping, state I/O; sb_batch_render.hip: pictures; sb_batch_summary.hip: per-scene statistics, rollouts).
+// (sb_batch.hip: upload, stepping, state I/O; sb_batch_render.hip: pictures; sb_batch_summary.hip: per-scene statistics, rollouts;
+// sb_batch_bodies.hip: connected bodies).
 #pragma once
 #include <cstdio>
 #include <string>
@@ -78,6 +79,7 @@ struct sb_batch {
     int scenes_per_cu = 0, vgprs = 0, scratch = 0;
     SbBatchRender *render = nullptr; // what the renderer keeps between calls (made at the first render)
     int summary_vgprs = -1, summary_scratch = 0; // k_batch_summary's (asked for at the first sb_batch_get_info of them)
+    int bodies_vgprs = -1, bodies_scratch = 0;   // k_batch_bodies' (likewise)
 };
 
 extern thread_local std::string g_batch_create_error; // sb_batch.hip
@@ -99,3 +101,5 @@ void sbb_render_release(sb_batch *b);                                   // sb_ba
 bool sbb_render_info(sb_batch *b, const char *key, uint64_t *value);    // sb_batch_get_info's render keys; false: not one of them
 // sb_batch_summary.hip
 bool sbb_summary_info(sb_batch *b, const char *key, uint64_t *value);   // sb_batch_get_info's summary keys; false: not one of them
+// sb_batch_bodies.hip
+bool sbb_bodies_info(sb_batch *b, const char *key, uint64_t *value);    // sb_batch_get_info's bodies keys; false: not one of them
