@@ -427,7 +427,7 @@ sb_status sb_write_particles_device(sb_engine *e, const void *device_particles);
  *   Limits: per scene at most SB_BATCH_MAX_PARTICLES particles and SB_BATCH_MAX_BEAMS beams (what one workgroup holds).
  *   When do calls return?  sb_batch_frame / _step / _delete_pass / _reset_device / _write_user_input[_device] /
  *     _set_physics_constants / _read_state_device / _write_particles_device / _fork_device / _checkpoint_device /
- *     _write_beams_device / _summary_device / _rollout_device / _bodies_device only ENQUEUE on the batch's stream (device buffers must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
+ *     _write_beams_device / _summary_device / _rollout_device / _bodies_device / _contacts_device only ENQUEUE on the batch's stream (device buffers must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
  *     sb_batch_render_device only ENQUEUES (its device buffer must stay valid likewise); sb_batch_render_scene WAITS.
  *   Errors: every call returns an sb_status; sb_batch_last_error(b) gives the message (b == NULL: the last failed
  *     sb_batch_create of the calling thread).  Options are checked BEFORE a device is looked for. */
@@ -598,6 +598,47 @@ sb_status sb_batch_bodies_device(sb_batch *b,
                                  void *device_sizes_i32   /* [n_scenes][max_particles][2] int32 or NULL */,
                                  void *device_counts_i32  /* [n_scenes][SB_BATCH_BODY_WORDS] int32 or NULL */);
 
+/* ---- particle and wall contacts of every scene, reported on the device ----
+ * sb_batch_contacts_device -- who touches whom, and who touches a wall, in ONE launch.
+ * Particle set: the particles of a scene are its slots 0 .. metadata.particle_i_c - 1, named by their DATA index like the rows of
+ *   sb_batch_read_state_device; their coordinates are the current particle records (what sb_batch_read_state_device would export
+ *   at this point of the stream).
+ * Particle contact: two distinct particles i and j TOUCH iff dist == 0 or dist < particle_radius * 2.0f, where dx = xj - xi,
+ *   dy = yj - yi, dist = sqrt(dx * dx + dy * dy) in the library's arithmetic (binary32, one rounding per operator, correctly
+ *   rounded sqrt): the expressions of the frame kernel's collision loop, so this is exactly the set of pairs the next substep's
+ *   collision loop acts on (compute.wgsl:150-155).  The relation is symmetric.  A NaN or infinite dist is no contact.  The result
+ *   does NOT depend on the batch's collision_mode: with SB_COLLIDE_OFF the same geometric set is reported.
+ * Wall contact: lo = particle_radius, hi = bounds_size - particle_radius in float, as the step computes them; the bits are
+ *   SB_BATCH_WALL_LEFT x <= lo, _RIGHT x >= hi, _LOW y <= lo, _HIGH y >= hi.  A particle the step has clamped sits exactly on lo or
+ *   hi.  A NaN coordinate sets no bit.
+ *   touch[s][i]   SB_BATCH_CONTACT_WORDS words per particle data index: 0 the number of particles touching i, 1 the number of those
+ *                 whose label differs from i's (-1 when device_labels_i32 is NULL), 2 the wall bits, 3 the smallest data index of a
+ *                 particle touching i (-1: none).  A row where no particle lives is {0, labels ? 0 : -1, 0, -1}.
+ *   pairs[s]      one {i, j} per touching pair of the scene, i < j as data indices, in ascending lexicographic order of (i, j) (the
+ *                 definition names no schedule); rows from the number of listed pairs up to max_pairs are {-1, -1}: every word is
+ *                 written.  A scene of more than max_pairs pairs lists the first max_pairs in that order.  With
+ *                 SB_BATCH_CONTACTS_OTHER_BODY only pairs whose labels differ are listed; order and truncation stay the same.
+ *   counts[s]     SB_BATCH_CONTACT_WORDS words: 0 touching pairs (the true number, however small max_pairs is), 1 pairs whose labels
+ *                 differ (-1 without labels), 2 particles with a nonzero wall word, 3 particles that touch at least one other.  A
+ *                 scene with no particles, or one never uploaded, gives {0, 0 or -1, 0, 0}.
+ * Labels ([n_scenes][max_particles] int32, as sb_batch_bodies_device writes them) are only compared for equality with each other
+ * and never used as an index: stale or arbitrary labels cannot fault, they only mean what the caller made them mean.
+ * Any of touch / pairs / counts may be NULL (not written), not all of them.  The call only ENQUEUES and only READS the batch:
+ * frame, contacts, frame equals frame, frame bit for bit.
+ * Errors: SB_ERR_INVALID for a NULL handle, an unknown flag bit, SB_BATCH_CONTACTS_OTHER_BODY without labels, touch, pairs and
+ * counts all NULL, pairs non-NULL with max_pairs == 0, a pointer that is not 4-byte aligned -- before anything touches a device. */
+#define SB_BATCH_CONTACT_WORDS 4u          /* words of a per-particle row and of a per-scene row */
+#define SB_BATCH_CONTACTS_OTHER_BODY 1u    /* the pair list holds only pairs whose particles carry different labels */
+#define SB_BATCH_WALL_LEFT 1u   /* x <= lo */
+#define SB_BATCH_WALL_RIGHT 2u  /* x >= hi */
+#define SB_BATCH_WALL_LOW 4u    /* y <= lo */
+#define SB_BATCH_WALL_HIGH 8u   /* y >= hi */
+sb_status sb_batch_contacts_device(sb_batch *b, uint32_t flags,
+        const void *device_labels_i32 /* [n_scenes][max_particles] as sb_batch_bodies_device writes them, or NULL */,
+        void *device_touch_i32        /* [n_scenes][max_particles][SB_BATCH_CONTACT_WORDS] or NULL */,
+        void *device_pairs_i32        /* [n_scenes][max_pairs][2] or NULL */, uint32_t max_pairs,
+        void *device_counts_i32       /* [n_scenes][SB_BATCH_CONTACT_WORDS] or NULL */);
+
 /* scene i back into host buffers exactly as sb_load_buffers returns a single engine in the same state (counts in the metadata,
  * the mapping after the delete passes' stable in-place compactions, beam records with strain / stress; only records reachable
  * through the uploaded mapping are written; any pointer may be NULL).  SB_ERR_STATE for a scene never uploaded. */
@@ -646,7 +687,10 @@ sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream);
  * blobs; 0 before the first fork) and, WAITING for the stream, "fork_bad_sources" (entries >= n_scenes other than
  * SB_BATCH_FORK_KEEP seen by all forks so far); sb_batch_summary_device: "summary_words" (SB_BATCH_SUMMARY_WORDS),
  * "summary_kernel_vgprs", "summary_kernel_scratch_bytes"; sb_batch_bodies_device: "body_words" (SB_BATCH_BODY_WORDS),
- * "bodies_kernel_vgprs", "bodies_kernel_scratch_bytes", "bodies_lds_bytes" (LDS of one workgroup at this batch's capacity) */
+ * "bodies_kernel_vgprs", "bodies_kernel_scratch_bytes", "bodies_lds_bytes" (LDS of one workgroup at this batch's capacity);
+ * sb_batch_contacts_device: "contact_words" (SB_BATCH_CONTACT_WORDS), "contacts_kernel_vgprs", "contacts_kernel_scratch_bytes",
+ * "contacts_lds_bytes" (likewise), "contacts_cells_per_side" (G of the G x G cells the call bins into: the rule of
+ * "contact_cells_per_side" whatever the collision mode and threshold; 1 where the cell width is no ordinary number) */
 sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value);
 const char *sb_batch_last_error(const sb_batch *b);
 

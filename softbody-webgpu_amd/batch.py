@@ -22,6 +22,12 @@ SUMMARY_FIELDS = ("particles", "live_beams", "removed_beams", "pending_breaks", 
 BODY_WORDS = 4                                        # SB_BATCH_BODY_WORDS
 # the words of a row of bodies()'s counts, in order (include/softbody.h, sb_batch_bodies_device)
 BODY_FIELDS = ("bodies", "largest_particles", "single_particles", "largest_label")
+CONTACT_WORDS = 4                                     # SB_BATCH_CONTACT_WORDS
+# the words of a row of contacts()'s touch and of its counts, in order (include/softbody.h, sb_batch_contacts_device)
+CONTACT_TOUCH_FIELDS = ("touching", "touching_other_body", "walls", "first_partner")
+CONTACT_COUNT_FIELDS = ("pairs", "other_body_pairs", "wall_particles", "touching_particles")
+CONTACTS_OTHER_BODY = 1                               # SB_BATCH_CONTACTS_OTHER_BODY
+WALL_LEFT, WALL_RIGHT, WALL_LOW, WALL_HIGH = 1, 2, 4, 8   # SB_BATCH_WALL_*: the bits of a touch row's "walls"
 
 
 class SbBatchOptions(ctypes.Structure):
@@ -67,6 +73,7 @@ def load_library():
     L.sb_batch_summary_device.argtypes = [vp, vp]
     L.sb_batch_rollout_device.argtypes = [vp, u32, vp, vp]
     L.sb_batch_bodies_device.argtypes = [vp, vp, vp, vp]
+    L.sb_batch_contacts_device.argtypes = [vp, u32, vp, vp, vp, u32, vp]
     L.sb_batch_load_scene.argtypes = [vp, u32, vp, sz, vp, sz, vp, sz, vp, sz]
     L.sb_batch_render_device.argtypes = [vp, ctypes.POINTER(SbBatchRenderOptions), vp]
     L.sb_batch_render_scene.argtypes = [vp, u32, ctypes.POINTER(SbBatchRenderOptions), vp, sz]
@@ -386,6 +393,64 @@ class BatchEngine:
             tensors |= t
         vp = ctypes.c_void_p
         self._ordered(tensors, lambda: load_library().sb_batch_bodies_device(self._h, vp(ptrs[0]), vp(ptrs[1]), vp(ptrs[2])))
+        return (outs[0], outs[2], outs[1]) if want[1] else (outs[0], outs[2])
+
+    # ---- particle and wall contacts (sb_batch_contacts_device)
+    def contacts(self, labels=None, pairs=0, other_body=False, touch=None, counts=None):
+        """Who touches whom, and who touches a wall, in every scene in one launch.  Two particles touch iff the next substep's
+        collision loop would act on them (dist == 0 or dist < 2 * particle_radius in the library's float arithmetic); the answer
+        is the same in every collision_mode, COLLIDE_OFF included.  Returns (touch, counts), int32 tensors on the batch's device,
+        or (touch, counts, pairs) when a pair list is asked for.  touch [n_scenes, max_particles, 4] at particle DATA indices
+        (CONTACT_TOUCH_FIELDS names the columns): particles touching i, those of them whose label differs from i's (-1 without
+        labels), the wall bits (WALL_LEFT x <= r, WALL_RIGHT x >= bounds - r, WALL_LOW y <= r, WALL_HIGH y >= bounds - r), the
+        smallest data index touching i (-1: none); a row where no particle lives is (0, 0 or -1, 0, -1).  counts [n_scenes, 4]
+        (CONTACT_COUNT_FIELDS): touching pairs (the true number, however short the list), pairs of different labels (-1 without
+        labels), particles on a wall, particles touching another.  pairs [n_scenes, n, 2]: the pairs (i, j), i < j, in ascending
+        order of (i, j), the first n of them, (-1, -1) behind the last; with other_body=True only pairs of different labels.
+        labels: None, True (self.bodies() is called first and its labels are used), or an int32 tensor / device pointer of
+        [n_scenes, max_particles] labels of the caller's own, which are only compared with each other.  pairs: 0 / None = no
+        list, n = a new tensor of n pairs per scene, or a contiguous int32 tensor [n_scenes, n, 2] to write into.  touch /
+        counts: a device pointer (int) or a contiguous int32 torch tensor of at least that many elements to write into.  Every
+        word is written.  Only reads the batch, only enqueues; torch's current stream is ordered after it."""
+        import torch
+        n, dev = self.n_scenes, torch.device("cuda", self.device)
+        max_pairs = 0
+        if isinstance(pairs, torch.Tensor):
+            self._device_buffer("contacts: pairs", pairs, "int32", n * 2 * 4)
+            max_pairs = pairs.shape[1] if pairs.dim() == 3 and tuple(pairs.shape[::2]) == (n, 2) else pairs.numel() // (2 * n)
+        elif pairs is not None:
+            if isinstance(pairs, bool) or not isinstance(pairs, (int, np.integer)) or not 0 <= pairs < 2 ** 32:
+                raise ValueError("contacts: pairs is a number of pairs per scene or an int32 torch tensor, not %r" % (pairs,))
+            max_pairs = int(pairs)
+        shapes = ((n, self.max_particles, CONTACT_WORDS), (n, max_pairs, 2), (n, CONTACT_WORDS))
+        outs = [touch, pairs if isinstance(pairs, torch.Tensor) else None, counts]
+        want = (True, max_pairs > 0, True)
+        for k, what in enumerate(("touch", "pairs", "counts")):   # (what the caller gave is looked at before anything is allocated)
+            if outs[k] is not None:
+                self._device_buffer("contacts: " + what, outs[k], "int32", int(np.prod(shapes[k])) * 4)
+        lptr, tensors = None, False
+        if labels is True:
+            labels = self.bodies()[0]
+        if labels is not None:
+            lptr, t = self._device_buffer("contacts: labels", labels, "int32", n * self.max_particles * 4)
+            tensors |= t
+        ptrs = []
+        for k in range(3):
+            if not want[k]:
+                ptrs.append(None)
+                continue
+            if outs[k] is None:
+                outs[k] = torch.empty(shapes[k], dtype=torch.int32, device=dev)
+            numel = int(np.prod(shapes[k]))
+            ptr, t = self._device_buffer("contacts", outs[k], "int32", numel * 4)
+            if t and tuple(outs[k].shape) != shapes[k]:
+                outs[k] = outs[k].view(-1)[:numel].view(shapes[k])
+            ptrs.append(ptr)
+            tensors |= t
+        vp = ctypes.c_void_p
+        flags = CONTACTS_OTHER_BODY if other_body else 0
+        self._ordered(tensors, lambda: load_library().sb_batch_contacts_device(self._h, flags, vp(lptr), vp(ptrs[0]), vp(ptrs[1]), max_pairs,
+                                                                               vp(ptrs[2])))
         return (outs[0], outs[2], outs[1]) if want[1] else (outs[0], outs[2])
 
     # ---- pictures (sb_batch_render_device / sb_batch_render_scene; DESIGN.md 5.11)

@@ -1,7 +1,8 @@
 // sb_batch.h -- what the files of the sb_batch_* group share: the device memory of a batch and its host object
 // (sb_batch.hip: upload, stepping, state I/O; sb_batch_render.hip: pictures; sb_batch_summary.hip: per-scene statistics, rollouts;
-// sb_batch_bodies.hip: connected bodies).
+// sb_batch_bodies.hip: connected bodies; sb_batch_contacts.hip: particle and wall contacts).
 #pragma once
+#include <algorithm>
 #include <cstdio>
 #include <string>
 
@@ -52,6 +53,28 @@ struct SbBatchView {
 // buffer per substep parity); overflow words u32[2]
 static inline uint32_t sb_batch_cell_lds_bytes(uint32_t g) { return g * g * SB_BATCH_CELL_K * 2u + 2u * ((g * g + 1u) / 2u) * 4u + 8u; }
 
+// ---- contact cells: geometry, shared by sb_batch_create (the frame kernel's cells) and sb_batch_contacts_device
+// the most cells per side a capacity gets: the largest G with G^2 <= 2.5 * max_particles (17 at 128, 25 at 256, 50 at 1024)
+static inline uint32_t sb_batch_cell_cap(uint32_t maxP)
+{
+    uint32_t g = 1u;
+    while (2u * (g + 1u) * (g + 1u) <= 5u * maxP) g++;
+    return g;
+}
+// cells per side and their width for a radius and bounds: SbGrid's rule, cell >= 2r (1 + 1/64); G = clamp(floor(bounds / that),
+// 1, cap), the cells then as wide as G of them need to cover the bounds (never narrower than the rule: coarser is always right;
+// whatever lies past the last cell is clamped into it).  0: the width is not an ordinary number (the batch walks,
+// sb_batch_contacts_device tests all pairs).
+static inline uint32_t sb_batch_cell_geometry(float bounds, float radius, uint32_t cap, float *cell)
+{
+    const float two_r = radius * 2.0f, cell_min = two_r * (1.0f + 1.0f / 64.0f);
+    if (!(cell_min >= 0x1p-60f && cell_min <= 0x1p60f) || !(bounds >= 0x1p-60f && bounds <= 0x1p60f)) return 0u;
+    const float per_side = bounds / cell_min; // (ordinary: both are)
+    const uint32_t g = per_side >= (float)cap ? cap : (per_side >= 1.0f ? (uint32_t)per_side : 1u);
+    *cell = std::max(cell_min, bounds / (float)g);
+    return g;
+}
+
 SB_DEV uint32_t sbb_uniform(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
 SB_DEV float sbb_uniform(float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); }
 
@@ -80,6 +103,7 @@ struct sb_batch {
     SbBatchRender *render = nullptr; // what the renderer keeps between calls (made at the first render)
     int summary_vgprs = -1, summary_scratch = 0; // k_batch_summary's (asked for at the first sb_batch_get_info of them)
     int bodies_vgprs = -1, bodies_scratch = 0;   // k_batch_bodies' (likewise)
+    int contacts_vgprs = -1, contacts_scratch = 0; // k_batch_contacts' (likewise)
 };
 
 extern thread_local std::string g_batch_create_error; // sb_batch.hip
@@ -103,3 +127,5 @@ bool sbb_render_info(sb_batch *b, const char *key, uint64_t *value);    // sb_ba
 bool sbb_summary_info(sb_batch *b, const char *key, uint64_t *value);   // sb_batch_get_info's summary keys; false: not one of them
 // sb_batch_bodies.hip
 bool sbb_bodies_info(sb_batch *b, const char *key, uint64_t *value);    // sb_batch_get_info's bodies keys; false: not one of them
+// sb_batch_contacts.hip
+bool sbb_contacts_info(sb_batch *b, const char *key, uint64_t *value);  // sb_batch_get_info's contacts keys; false: not one of them

@@ -479,25 +479,7 @@ static uint32_t sb_batch_lds_bytes(uint32_t maxP, uint32_t maxB, bool mats)
 // and 128 the cap on G makes the cells so coarse that a lattice fills their buckets, and the default scene (119) is 1.96 ms on
 // the walk against 2.45 ms on the cells.
 #define SB_BATCH_GRID_MIN_PARTICLES_DEFAULT 256u
-// the most cells per side a capacity gets: the largest G with G^2 <= 2.5 * max_particles (17 at 128, 25 at 256, 50 at 1024)
-static uint32_t sb_batch_cell_cap(uint32_t maxP)
-{
-    uint32_t g = 1u;
-    while (2u * (g + 1u) * (g + 1u) <= 5u * maxP) g++;
-    return g;
-}
-// cells per side and their width for a radius and bounds: SbGrid's rule, cell >= 2r (1 + 1/64); G = clamp(floor(bounds / that),
-// 1, cap), the cells then as wide as G of them need to cover the bounds (never narrower than the rule: coarser is always right;
-// whatever lies past the last cell is clamped into it).  0: the width is not an ordinary number, the batch walks.
-static uint32_t sb_batch_cell_geometry(float bounds, float radius, uint32_t cap, float *cell)
-{
-    const float two_r = radius * 2.0f, cell_min = two_r * (1.0f + 1.0f / 64.0f);
-    if (!(cell_min >= 0x1p-60f && cell_min <= 0x1p60f) || !(bounds >= 0x1p-60f && bounds <= 0x1p60f)) return 0u;
-    const float per_side = bounds / cell_min; // (ordinary: both are)
-    const uint32_t g = per_side >= (float)cap ? cap : (per_side >= 1.0f ? (uint32_t)per_side : 1u);
-    *cell = std::max(cell_min, bounds / (float)g);
-    return g;
-}
+// (the rule that turns a radius, bounds and a capacity into cells: sb_batch_cell_cap / sb_batch_cell_geometry, sb_batch.h)
 
 const char *sb_batch_last_error(const sb_batch *b) { return b ? b->err.c_str() : g_batch_create_error.c_str(); }
 
@@ -1004,6 +986,7 @@ sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value)
     else if (sbb_render_info(b, key, value)) return SB_OK;
     else if (sbb_summary_info(b, key, value)) return SB_OK;
     else if (sbb_bodies_info(b, key, value)) return SB_OK;
+    else if (sbb_contacts_info(b, key, value)) return SB_OK;
     else SB_FAIL(b, SB_ERR_INVALID, "sb_batch_get_info: unknown key '%s'", key);
     return SB_OK;
 }
