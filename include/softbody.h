@@ -598,6 +598,51 @@ sb_status sb_batch_bodies_device(sb_batch *b,
                                  void *device_sizes_i32   /* [n_scenes][max_particles][2] int32 or NULL */,
                                  void *device_counts_i32  /* [n_scenes][SB_BATCH_BODY_WORDS] int32 or NULL */);
 
+/* ---- statistics per body, reproducible bit for bit ----
+ * sb_batch_body_summary_device -- one row of SB_BATCH_BODY_SUMMARY_WORDS floats per GROUP of particles of every scene, in ONE
+ * launch: "follow the largest fragment", "where did the piece that broke off go", "how fast does each piece move".  It only
+ * ENQUEUES on the batch's stream and only READS the batch: frame, body_summary, frame equals frame, frame bit for bit.
+ * Groups: labels[s][i] is read at every particle DATA index i of scene s (never at a data index that holds no particle).  A value
+ *   g with 0 <= g < max_particles puts particle i into group g; any other value (-1, negative, too large) into no group.  With
+ *   the labels sb_batch_bodies_device writes the groups are the bodies, but any partition will do (limbs, stripes): nothing
+ *   assumes connectivity.  A live beam (beam slots 0 .. metadata.beam_i_c - 1) belongs to group g iff BOTH its endpoints are in g;
+ *   with body labels that is every live beam.
+ * Ranking: the non-empty groups of a scene are ranked by particles descending, then label ascending (the key by which
+ *   sb_batch_bodies_device names the largest body).  rows[s][k] is the group of rank k, k < max_rows; rows behind the last group
+ *   are the EMPTY ROW.  rank[s][i] is the rank of particle i's group, however large -- a value >= max_rows means that its row was
+ *   cut; -1 marks a data index that holds no particle, or a particle in no group.  Every word of a non-NULL output is written.
+ * Row (words 4 .. 18 mean what they mean in a row of sb_batch_summary_device, restricted to the group):
+ *    0  particles of the group (finite or not)       1  live beams of the group
+ *    2  the label (<= 1023: exact as a float)        3  break flags pending among the group's live beam slots
+ *    4  particles of the group that are not finite   5  live beams of the group that are not finite
+ *    6, 7  mean position x, y                        8, 9  mean velocity x, y           (over the group's finite particles)
+ *   10 .. 13  min x, min y, max x, max y             (over the group's finite particles)
+ *   14  kinetic energy, the sum of 0.5 (vx^2 + vy^2)    15  max of vx^2 + vy^2          (over the group's finite particles)
+ *   16, 17, 18  max strain, max stress, min stress   (over the group's finite beams)
+ *   19  angular momentum about the origin, the sum of x vy - y vx                       (over the group's finite particles)
+ *   20 .. 23  0
+ * Over an empty set a mean or an extreme is the quiet NaN 0x7FC00000; counts, word 14 and word 19 are 0.  The EMPTY ROW: words
+ * 0, 1, 3, 4, 5, 14, 19 .. 23 are 0, word 2 is -1, the others NaN.  A scene never uploaded, and a scene without particles, give
+ * empty rows and rank -1.  (The mean strain is deliberately not in the row: it would need a second pinned tree over up to 4096
+ * beam leaves.  The beam words are the order-free ones.)
+ * The sums are pinned, and the pin is sb_batch_summary_device's: the sum of a group is what that call's tree gives for a scene
+ * that holds only the group's finite particles at their data indices -- in double; leaf i is the value at DATA index i if particle
+ * i is finite and in the group, else +0.0; i = 0 .. W-1, W the smallest power of two >= max_particles; for h = W/2 .. 1:
+ * s[i] += s[i + h].  The energy leaf is 0.5 * ((double)vx * vx + (double)vy * vy), the candidate of word 15 the same without the
+ * 0.5; the angular-momentum leaf is (double)x * vy - (double)y * vx (both products are exact in double: one rounding).  A mean is
+ * (float)(sum / (double)finite_count); words 14 and 19 are rounded to float once.  ONE addition to the pin: a sum that is zero is
+ * written as +0.0.  The masked tree gives that in every case but one -- a group that fills all W leaves with -0.0, where the tree
+ * gives -0.0 and this call still writes +0.0.  Extremes are plain comparisons (-0 and +0 compare equal: either may be returned).
+ * Consequence: for a scene that is ONE body, row 0's words 0, 1, 3 .. 18 equal sb_batch_summary_device's words by their bits.
+ * Errors: SB_ERR_INVALID for a NULL handle, NULL labels, rows and rank both NULL, max_rows of 0 or above max_particles (so also
+ * rows non-NULL with max_rows == 0), a pointer that is not 4-byte aligned -- before anything touches a device. */
+#define SB_BATCH_BODY_SUMMARY_WORDS 24u
+sb_status sb_batch_body_summary_device(sb_batch *b,
+        const void *device_labels_i32 /* [n_scenes][max_particles] int32, required */,
+        uint32_t max_rows             /* 1 .. max_particles */,
+        void *device_rows_f32         /* [n_scenes][max_rows][SB_BATCH_BODY_SUMMARY_WORDS] float or NULL */,
+        void *device_rank_i32         /* [n_scenes][max_particles] int32 or NULL */);
+
 /* ---- particle and wall contacts of every scene, reported on the device ----
  * sb_batch_contacts_device -- who touches whom, and who touches a wall, in ONE launch.
  * Particle set: the particles of a scene are its slots 0 .. metadata.particle_i_c - 1, named by their DATA index like the rows of
@@ -690,7 +735,9 @@ sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream);
  * "bodies_kernel_vgprs", "bodies_kernel_scratch_bytes", "bodies_lds_bytes" (LDS of one workgroup at this batch's capacity);
  * sb_batch_contacts_device: "contact_words" (SB_BATCH_CONTACT_WORDS), "contacts_kernel_vgprs", "contacts_kernel_scratch_bytes",
  * "contacts_lds_bytes" (likewise), "contacts_cells_per_side" (G of the G x G cells the call bins into: the rule of
- * "contact_cells_per_side" whatever the collision mode and threshold; 1 where the cell width is no ordinary number) */
+ * "contact_cells_per_side" whatever the collision mode and threshold; 1 where the cell width is no ordinary number);
+ * sb_batch_body_summary_device: "body_summary_words" (SB_BATCH_BODY_SUMMARY_WORDS), "body_summary_kernel_vgprs",
+ * "body_summary_kernel_scratch_bytes", "body_summary_lds_bytes" (LDS of one workgroup at this batch's capacity) */
 sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value);
 const char *sb_batch_last_error(const sb_batch *b);
 

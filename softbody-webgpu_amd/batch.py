@@ -22,6 +22,13 @@ SUMMARY_FIELDS = ("particles", "live_beams", "removed_beams", "pending_breaks", 
 BODY_WORDS = 4                                        # SB_BATCH_BODY_WORDS
 # the words of a row of bodies()'s counts, in order (include/softbody.h, sb_batch_bodies_device)
 BODY_FIELDS = ("bodies", "largest_particles", "single_particles", "largest_label")
+BODY_SUMMARY_WORDS = 24                               # SB_BATCH_BODY_SUMMARY_WORDS
+# the words of a row of body_summary(), in order (include/softbody.h, sb_batch_body_summary_device): SUMMARY_FIELDS' names where the
+# word means the same, restricted to the group
+BODY_SUMMARY_FIELDS = ("particles", "live_beams", "label", "pending_breaks", "nonfinite_particles", "nonfinite_beams",
+                       "mean_x", "mean_y", "mean_vx", "mean_vy", "min_x", "min_y", "max_x", "max_y", "kinetic_energy", "max_speed_sq",
+                       "max_strain", "max_stress", "min_stress", "angular_momentum", "reserved_20", "reserved_21", "reserved_22",
+                       "reserved_23")
 CONTACT_WORDS = 4                                     # SB_BATCH_CONTACT_WORDS
 # the words of a row of contacts()'s touch and of its counts, in order (include/softbody.h, sb_batch_contacts_device)
 CONTACT_TOUCH_FIELDS = ("touching", "touching_other_body", "walls", "first_partner")
@@ -74,6 +81,7 @@ def load_library():
     L.sb_batch_rollout_device.argtypes = [vp, u32, vp, vp]
     L.sb_batch_bodies_device.argtypes = [vp, vp, vp, vp]
     L.sb_batch_contacts_device.argtypes = [vp, u32, vp, vp, vp, u32, vp]
+    L.sb_batch_body_summary_device.argtypes = [vp, vp, u32, vp, vp]
     L.sb_batch_load_scene.argtypes = [vp, u32, vp, sz, vp, sz, vp, sz, vp, sz]
     L.sb_batch_render_device.argtypes = [vp, ctypes.POINTER(SbBatchRenderOptions), vp]
     L.sb_batch_render_scene.argtypes = [vp, u32, ctypes.POINTER(SbBatchRenderOptions), vp, sz]
@@ -394,6 +402,54 @@ class BatchEngine:
         vp = ctypes.c_void_p
         self._ordered(tensors, lambda: load_library().sb_batch_bodies_device(self._h, vp(ptrs[0]), vp(ptrs[1]), vp(ptrs[2])))
         return (outs[0], outs[2], outs[1]) if want[1] else (outs[0], outs[2])
+
+    # ---- statistics per body (sb_batch_body_summary_device)
+    def body_summary(self, labels=None, rows=8, out=None, rank=False):
+        """One row of BODY_SUMMARY_WORDS statistics per GROUP of particles of every scene in one launch (BODY_SUMMARY_FIELDS names
+        the columns): a float32 tensor [n_scenes, rows, 24] on the batch's device, or (that, rank) with rank=True or a tensor.
+        labels: None (self.bodies() is called first, on the same stream, and the groups are the bodies) or an int32 tensor /
+        device pointer of [n_scenes, max_particles] labels of the caller's own at particle DATA indices: a value 0 .. max_particles-1
+        names the particle's group, any other value puts it into none; a live beam belongs to the group that holds both its
+        endpoints.  Row k of a scene is its group of rank k -- particles descending, then label ascending -- and rows behind the
+        last group are empty (label -1, counts 0, NaN elsewhere).  Counts, label, pending breaks, means, extremes, kinetic energy
+        and angular momentum of the group's finite particles, strain and stress extremes of its finite beams; the sums are those
+        of summary()'s pinned tree over the group alone, so a row is reproducible bit for bit, and a scene that is one body gives
+        summary()'s words.  rank int32 [n_scenes, max_particles]: the rank of the group of the particle at that data index (>= rows:
+        its row was cut), -1 where no particle lives or the particle is in no group.  rows: 1 .. max_particles.  out / rank: a
+        device pointer (int) or a contiguous torch tensor (float32 / int32) of at least that many elements to write into.  Every
+        word is written.  Only reads the batch, only enqueues; torch's current stream is ordered after it."""
+        import torch
+        n, dev = self.n_scenes, torch.device("cuda", self.device)
+        if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or not 1 <= rows <= self.max_particles:
+            raise ValueError("body_summary: rows is %r, not a number in 1 .. max_particles (%d)" % (rows, self.max_particles))
+        rows = int(rows)
+        shapes = ((n, rows, BODY_SUMMARY_WORDS), (n, self.max_particles))
+        outs = [out, None if rank is False else rank]
+        want, dtypes = (True, rank is not False), ("float32", "int32")
+        for k, what in enumerate(("out", "rank")):   # (what the caller gave is looked at before anything is allocated or enqueued)
+            if outs[k] is not None and outs[k] is not True:
+                self._device_buffer("body_summary: " + what, outs[k], dtypes[k], int(np.prod(shapes[k])) * 4)
+        if labels is not None:
+            self._device_buffer("body_summary: labels", labels, "int32", n * self.max_particles * 4)
+        else:
+            labels = self.bodies()[0]
+        lptr, tensors = self._device_buffer("body_summary: labels", labels, "int32", n * self.max_particles * 4)
+        ptrs = []
+        for k in range(2):
+            if not want[k]:
+                ptrs.append(None)
+                continue
+            if outs[k] is None or outs[k] is True:
+                outs[k] = torch.empty(shapes[k], dtype=getattr(torch, dtypes[k]), device=dev)
+            numel = int(np.prod(shapes[k]))
+            ptr, t = self._device_buffer("body_summary", outs[k], dtypes[k], numel * 4)
+            if t and tuple(outs[k].shape) != shapes[k]:
+                outs[k] = outs[k].view(-1)[:numel].view(shapes[k])
+            ptrs.append(ptr)
+            tensors |= t
+        vp = ctypes.c_void_p
+        self._ordered(tensors, lambda: load_library().sb_batch_body_summary_device(self._h, vp(lptr), rows, vp(ptrs[0]), vp(ptrs[1])))
+        return (outs[0], outs[1]) if want[1] else outs[0]
 
     # ---- particle and wall contacts (sb_batch_contacts_device; DESIGN.md 5.15)
     def contacts(self, labels=None, pairs=0, other_body=False, touch=None, counts=None):

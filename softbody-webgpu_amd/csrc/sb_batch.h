@@ -1,6 +1,7 @@
 // sb_batch.h -- what the files of the sb_batch_* group share: the device memory of a batch and its host object
 // (sb_batch.hip: upload, stepping, state I/O; sb_batch_render.hip: pictures; sb_batch_summary.hip: per-scene statistics, rollouts;
-// sb_batch_bodies.hip: connected bodies; sb_batch_contacts.hip: particle and wall contacts).
+// sb_batch_bodies.hip: connected bodies; sb_batch_contacts.hip: particle and wall contacts; sb_batch_body_summary.hip: statistics per
+// body).
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -104,6 +105,8 @@ struct sb_batch {
     int summary_vgprs = -1, summary_scratch = 0; // k_batch_summary's (asked for at the first sb_batch_get_info of them)
     int bodies_vgprs = -1, bodies_scratch = 0;   // k_batch_bodies' (likewise)
     int contacts_vgprs = -1, contacts_scratch = 0; // k_batch_contacts' (likewise)
+    int body_summary_vgprs = -1, body_summary_scratch = 0; // k_batch_body_summary's (likewise)
+    bool body_summary_lds_allowed = false; // k_batch_body_summary may be launched with more than 64 KiB of LDS (asked for at the first such launch)
 };
 
 extern thread_local std::string g_batch_create_error; // sb_batch.hip
@@ -129,3 +132,5 @@ bool sbb_summary_info(sb_batch *b, const char *key, uint64_t *value);   // sb_ba
 bool sbb_bodies_info(sb_batch *b, const char *key, uint64_t *value);    // sb_batch_get_info's bodies keys; false: not one of them
 // sb_batch_contacts.hip
 bool sbb_contacts_info(sb_batch *b, const char *key, uint64_t *value);  // sb_batch_get_info's contacts keys; false: not one of them
+// sb_batch_body_summary.hip
+bool sbb_body_summary_info(sb_batch *b, const char *key, uint64_t *value); // sb_batch_get_info's body summary keys; false: not one of them

@@ -1,0 +1,306 @@
+// sb_batch_body_summary.hip -- statistics per GROUP of particles (with sb_batch_bodies_device's labels: per body) of every scene
+// of a batch in ONE launch, reproducible bit for bit (gfx950, wave64).
+//
+// One workgroup per scene reads the caller's labels, the scene's metadata words, its constant blob and its state blob; nothing is
+// written but the rows and the ranks.
+//
+// The sums are PINNED to sb_batch_summary_device's tree: the sum of a group is what that tree gives for a scene holding only the
+// group's finite particles -- double precision, leaf i = the value at DATA index i if particle i is finite and in the group, else
+// +0.0, i = 0 .. W-1, reduced by  for h = W/2 .. 1: s[i] += s[i + h].  That tree is never evaluated per group.  Every partial sum
+// is finite (at most 1024 finite floats, in double), so the +0.0 of an absent leaf changes no partial sum but a zero's sign, and
+// the masked tree is a tree over the members alone.  With r = bitrev(i) over log2 W bits the stride-halving tree is the
+// ADJACENT-PAIR tree in r order (level l adds the block whose r has bit l set onto its left sibling), so
+//   sort     the finite members of all groups by the key  label * W + r  (unique; a bitonic network over W keys in LDS: the order
+//            comes from the keys alone, never from which atomic won)
+//   reduce   log2 W levels, one barrier each: at level l a sorted position is the HEAD of its block iff its predecessor's key
+//            differs in key >> l; a head whose key has bit l set and whose predecessor shares key >> (l + 1) adds its six partial
+//            sums onto the head of the left sibling block (the lower bound of ((key >> l) - 1) << l).  Nobody else touches either
+//            operand at that level; after the last level a group's sums sit at the first sorted position of its label.
+// All groups are reduced at once.  A sum that is zero is written as +0.0 (sbq_canon): the masked tree gives that in every case but
+// a group that fills all W leaves with -0.0.
+// Everything else in a row (counts, extremes) is order-free and goes through LDS atomics on integer keys; the ranking sorts the
+// keys  particles << 10 | (1023 - label)  with the same network.
+#include <algorithm>
+#include <string>
+
+#include "sb_batch.h"
+
+// 256 threads as the sibling kernels: the sort's W / 2 = 512 compare-exchanges of the largest capacity are two per thread, and
+// four waves keep a barrier (there are about 120 in a launch at W = 1024) cheap
+#define SBQ_BLOCK 256u
+#define SBQ_NSUM 6u // x, y, vx, vy, 0.5 (vx^2 + vy^2), x vy - y vx
+#define SBQ_NONE 0xFFFFFFFFu
+#define SBQ_QNAN 0x7FC00000u
+#define SBQ_LDS_DEFAULT_LIMIT (64u * 1024u) // above it a launch needs hipFuncAttributeMaxDynamicSharedMemorySize
+
+// per-label statistics words, each an array of max_particles entries
+enum {
+    SBQ_NP,      // particles | particles that are not finite << 16
+    SBQ_NB,      // live beams | live beams that are not finite << 16
+    SBQ_PENDING, // break flags pending among the group's live beam slots
+    SBQ_MINX, SBQ_MINY, SBQ_MAXX, SBQ_MAXY, SBQ_MAX_V2, SBQ_MAX_STRAIN, SBQ_MAX_STRESS, SBQ_MIN_STRESS, SBQ_NSTAT
+};
+
+static_assert(SB_BATCH_MAX_PARTICLES <= 1024 && SB_BATCH_MAX_BEAMS < 0x10000, "a rank key holds 10 bits of label, a count word 16 bits per count");
+
+static inline uint32_t sbq_pow2_at_least(uint32_t n)
+{
+    uint32_t w = 1u;
+    while (w < n) w <<= 1;
+    return w;
+}
+// LDS of a workgroup: double col[SBQ_NSUM][W]; uint32 key[W], rkey[W], grp[maxP], rank[maxP], stat[SBQ_NSTAT][maxP]
+static inline uint32_t sbq_lds_bytes(uint32_t maxP)
+{
+    const uint32_t W = sbq_pow2_at_least(maxP);
+    return W * (SBQ_NSUM * 8u + 2u * 4u) + maxP * (2u + SBQ_NSTAT) * 4u;
+}
+
+SB_DEV bool sbq_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+// finite floats as unsigned keys of the same order (-0 below +0: either may come back from an extreme)
+SB_DEV uint32_t sbq_fkey(float x)
+{
+    const uint32_t b = __float_as_uint(x);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+SB_DEV float sbq_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+SB_DEV double sbq_canon(double sum) { return sum + 0.0; } // -0.0 -> +0.0, every other value as it is
+
+// ascending bitonic sort of a[0 .. W-1] (W a power of two) by the whole workgroup; ends in a barrier
+SB_DEV void sbq_sort(uint32_t *a, uint32_t W, uint32_t tid)
+{
+    for (uint32_t k = 2u; k <= W; k <<= 1) {
+        for (uint32_t j = k >> 1; j != 0u; j >>= 1) {
+            for (uint32_t t = tid; t < (W >> 1); t += SBQ_BLOCK) {
+                const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), p = i | j;
+                const uint32_t x = a[i], y = a[p];
+                if ((x > y) == ((i & k) == 0u)) a[i] = y, a[p] = x;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V, const int32_t *__restrict__ labels, uint32_t max_rows,
+                                                                  float *__restrict__ rows, int32_t *__restrict__ rank, uint32_t W, uint32_t logW)
+{
+    extern __shared__ __attribute__((aligned(16))) double sbq_lds[];
+    const uint32_t scene = blockIdx.x, tid = threadIdx.x;
+    if (scene >= V.n_scenes) return;
+    const uint32_t maxP = V.maxP, maxB = V.maxB;
+    double *s_col = sbq_lds;                      // [SBQ_NSUM][W] partial sums at sorted positions
+    uint32_t *s_key = (uint32_t *)(s_col + SBQ_NSUM * W); // [W] label * W + bitrev(data index) of the finite members, SBQ_NONE behind them
+    uint32_t *s_rkey = s_key + W;                 // [W] ~(particles << 10 | (1023 - label)) of the non-empty groups, SBQ_NONE behind them
+    uint32_t *s_grp = s_rkey + W;                 // [maxP] per DATA index: its group, SBQ_NONE where there is none
+    uint32_t *s_rank = s_grp + maxP;              // [maxP] per label: its rank
+    uint32_t *s_stat = s_rank + maxP;             // [SBQ_NSTAT][maxP] per label
+
+    const uint32_t *meta = V.meta + (size_t)scene * SB_BM_WORDS;
+    // (metadata words are rewritten between launches by other kernels: read at agent scope, as k_batch_frame does)
+    const uint32_t loaded = sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_LOADED]));
+    const uint32_t P = loaded ? min(sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_P])), maxP) : 0u; // (counts are validated at upload)
+    const uint32_t Bc = loaded ? min(sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_B])), maxB) : 0u; // beam slots >= Bc are stale: never read
+    const unsigned char *cst = V.cst + (size_t)scene * V.cst_bytes, *st = V.st + (size_t)scene * V.st_bytes;
+    const uint32_t *g_pmap = (const uint32_t *)(cst + V.o_pmap), *g_bword = (const uint32_t *)(cst + V.o_bword);
+    const uint32_t *g_bmap = (const uint32_t *)(st + V.o_bmap), *g_flags = (const uint32_t *)(st + V.o_bflags);
+    const float2 *g_part = (const float2 *)(st + V.o_part);
+    const float4 *g_bstate = (const float4 *)(st + V.o_bstate);
+    const int32_t *lrow = labels + (size_t)scene * maxP;
+
+    // ---- clear
+    for (uint32_t q = tid; q < W; q += SBQ_BLOCK) s_key[q] = SBQ_NONE;
+    for (uint32_t d = tid; d < maxP; d += SBQ_BLOCK) {
+        s_grp[d] = SBQ_NONE;
+#pragma unroll
+        for (uint32_t k = 0; k < SBQ_NSTAT; k++)
+            s_stat[k * maxP + d] = (k == SBQ_MINX || k == SBQ_MINY || k == SBQ_MIN_STRESS) ? 0xFFFFFFFFu : 0u;
+    }
+    __syncthreads();
+
+    // ---- particles (an upload is refused unless its data indices are distinct and inside the capacity): group, counts, extremes,
+    // and the sort key of a finite member, parked at its data index
+    for (uint32_t s = tid; s < P; s += SBQ_BLOCK) {
+        const uint32_t d = g_pmap[s];
+        const uint32_t g = (uint32_t)lrow[d]; // (a negative label is a large unsigned one)
+        if (g >= maxP) continue;
+        s_grp[d] = g;
+        const float2 p = g_part[3u * d], v = g_part[3u * d + 1u], a = g_part[3u * d + 2u];
+        if (!(sbq_finite(p.x) && sbq_finite(p.y) && sbq_finite(v.x) && sbq_finite(v.y) && sbq_finite(a.x) && sbq_finite(a.y))) {
+            atomicAdd(&s_stat[SBQ_NP * maxP + g], 0x10001u);
+            continue;
+        }
+        atomicAdd(&s_stat[SBQ_NP * maxP + g], 1u);
+        atomicMin(&s_stat[SBQ_MINX * maxP + g], sbq_fkey(p.x));
+        atomicMin(&s_stat[SBQ_MINY * maxP + g], sbq_fkey(p.y));
+        atomicMax(&s_stat[SBQ_MAXX * maxP + g], sbq_fkey(p.x));
+        atomicMax(&s_stat[SBQ_MAXY * maxP + g], sbq_fkey(p.y));
+        // (rounding to float is monotonic: the largest float is the float of the largest double; >= 0, so its bits order as it does)
+        const double v2 = (double)v.x * (double)v.x + (double)v.y * (double)v.y;
+        atomicMax(&s_stat[SBQ_MAX_V2 * maxP + g], __float_as_uint((float)v2));
+        s_key[d] = g * W + (logW ? __brev(d) >> (32u - logW) : 0u);
+    }
+    __syncthreads();
+
+    // ---- live beams: a beam belongs to group g iff both endpoints do
+    for (uint32_t j = tid; j < Bc; j += SBQ_BLOCK) {
+        const uint32_t bd = g_bmap[j], w = g_bword[bd];
+        const uint32_t g = s_grp[g_pmap[w & 0xffffu]];
+        if (g == SBQ_NONE || g != s_grp[g_pmap[w >> 16]]) continue;
+        const float4 q = g_bstate[bd]; // {target_length, last_length, strain, stress}
+        if ((j >> 5) < V.nflagw && ((g_flags[j >> 5] >> (j & 31u)) & 1u)) atomicAdd(&s_stat[SBQ_PENDING * maxP + g], 1u);
+        if (!(sbq_finite(q.z) && sbq_finite(q.w))) {
+            atomicAdd(&s_stat[SBQ_NB * maxP + g], 0x10001u);
+            continue;
+        }
+        atomicAdd(&s_stat[SBQ_NB * maxP + g], 1u);
+        atomicMax(&s_stat[SBQ_MAX_STRAIN * maxP + g], sbq_fkey(q.z));
+        atomicMax(&s_stat[SBQ_MAX_STRESS * maxP + g], sbq_fkey(q.w));
+        atomicMin(&s_stat[SBQ_MIN_STRESS * maxP + g], sbq_fkey(q.w));
+    }
+    // ---- the ranking: particles descending, then label ascending
+    for (uint32_t q = tid; q < W; q += SBQ_BLOCK) {
+        const uint32_t np = q < maxP ? (s_stat[SBQ_NP * maxP + q] & 0xffffu) : 0u;
+        s_rkey[q] = np ? ~((np << 10) | (1023u - q)) : SBQ_NONE;
+    }
+    __syncthreads();
+    sbq_sort(s_rkey, W, tid);
+    for (uint32_t q = tid; q < W; q += SBQ_BLOCK)
+        if (s_rkey[q] != SBQ_NONE) s_rank[1023u - (~s_rkey[q] & 1023u)] = q;
+
+    // ---- the members in key order, their leaves behind them
+    sbq_sort(s_key, W, tid);
+    for (uint32_t q = tid; q < W; q += SBQ_BLOCK) {
+        const uint32_t key = s_key[q];
+        if (key == SBQ_NONE) continue;
+        const uint32_t r = key & (W - 1u), d = logW ? __brev(r) >> (32u - logW) : 0u;
+        const float2 p = g_part[3u * d], v = g_part[3u * d + 1u];
+        s_col[0u * W + q] = (double)p.x, s_col[1u * W + q] = (double)p.y, s_col[2u * W + q] = (double)v.x, s_col[3u * W + q] = (double)v.y;
+        s_col[4u * W + q] = 0.5 * ((double)v.x * (double)v.x + (double)v.y * (double)v.y); // (the products are exact)
+        s_col[5u * W + q] = (double)p.x * (double)v.y - (double)p.y * (double)v.x;
+    }
+    __syncthreads();
+
+    // ---- the tree over the members alone
+    for (uint32_t l = 0u; l < logW; l++) {
+        for (uint32_t q = tid + (tid == 0u ? SBQ_BLOCK : 0u); q < W; q += SBQ_BLOCK) { // (position 0 never adds)
+            const uint32_t key = s_key[q];
+            if (key == SBQ_NONE) continue;
+            const uint32_t prev = s_key[q - 1u];
+            if ((prev >> l) == (key >> l) || !((key >> l) & 1u) || (prev >> (l + 1u)) != (key >> (l + 1u))) continue;
+            const uint32_t want = ((key >> l) - 1u) << l; // the left sibling block's head: the first position of a key >= want
+            uint32_t lo = 0u, hi = q - 1u;               // (position q - 1 is in that block)
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (s_key[mid] < want) lo = mid + 1u;
+                else hi = mid;
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < SBQ_NSUM; k++) s_col[k * W + lo] = s_col[k * W + lo] + s_col[k * W + q];
+        }
+        __syncthreads();
+    }
+
+    // ---- the rank of every data index
+    if (rank) {
+        int32_t *krow = rank + (size_t)scene * maxP;
+        for (uint32_t d = tid; d < maxP; d += SBQ_BLOCK) {
+            const uint32_t g = s_grp[d];
+            krow[d] = g == SBQ_NONE ? -1 : (int32_t)s_rank[g];
+        }
+    }
+    if (!rows) return; // (uniform)
+    float *out = rows + (size_t)scene * max_rows * SB_BATCH_BODY_SUMMARY_WORDS;
+    const float nan = __uint_as_float(SBQ_QNAN);
+    // ---- the sums, from the first sorted position of every label that has a finite member
+    for (uint32_t q = tid; q < W; q += SBQ_BLOCK) {
+        const uint32_t key = s_key[q];
+        if (key == SBQ_NONE || (q != 0u && (s_key[q - 1u] >> logW) == (key >> logW))) continue;
+        const uint32_t g = key >> logW, r = s_rank[g];
+        if (r >= max_rows) continue;
+        const uint32_t cnt = s_stat[SBQ_NP * maxP + g];
+        const double n = (double)((cnt & 0xffffu) - (cnt >> 16));
+        float *row = out + (size_t)r * SB_BATCH_BODY_SUMMARY_WORDS;
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) row[6u + k] = (float)(sbq_canon(s_col[k * W + q]) / n);
+        row[14] = (float)sbq_canon(s_col[4u * W + q]); // (round to nearest: +inf beyond the range of float)
+        row[19] = (float)sbq_canon(s_col[5u * W + q]);
+    }
+    // ---- everything else, one row per thread
+    for (uint32_t r = tid; r < max_rows; r += SBQ_BLOCK) {
+        float *row = out + (size_t)r * SB_BATCH_BODY_SUMMARY_WORDS;
+        const uint32_t rkey = r < W ? s_rkey[r] : SBQ_NONE;
+        if (rkey == SBQ_NONE) { // behind the last group: the empty row
+#pragma unroll
+            for (uint32_t k = 0; k < SB_BATCH_BODY_SUMMARY_WORDS; k++)
+                row[k] = (k <= 1u || (k >= 3u && k <= 5u) || k == 14u || k >= 19u) ? 0.0f : (k == 2u ? -1.0f : nan);
+            continue;
+        }
+        const uint32_t g = 1023u - (~rkey & 1023u);
+        const uint32_t cp = s_stat[SBQ_NP * maxP + g], cb = s_stat[SBQ_NB * maxP + g];
+        const uint32_t np = (cp & 0xffffu) - (cp >> 16), nb = (cb & 0xffffu) - (cb >> 16);
+        row[0] = (float)(cp & 0xffffu);
+        row[1] = (float)(cb & 0xffffu);
+        row[2] = (float)g;
+        row[3] = (float)s_stat[SBQ_PENDING * maxP + g];
+        row[4] = (float)(cp >> 16);
+        row[5] = (float)(cb >> 16);
+        if (np == 0u) { // no finite member: no sorted position wrote the sums
+            row[6] = row[7] = row[8] = row[9] = nan;
+            row[14] = row[19] = 0.0f;
+        }
+        row[10] = np ? sbq_unkey(s_stat[SBQ_MINX * maxP + g]) : nan;
+        row[11] = np ? sbq_unkey(s_stat[SBQ_MINY * maxP + g]) : nan;
+        row[12] = np ? sbq_unkey(s_stat[SBQ_MAXX * maxP + g]) : nan;
+        row[13] = np ? sbq_unkey(s_stat[SBQ_MAXY * maxP + g]) : nan;
+        row[15] = np ? __uint_as_float(s_stat[SBQ_MAX_V2 * maxP + g]) : nan;
+        row[16] = nb ? sbq_unkey(s_stat[SBQ_MAX_STRAIN * maxP + g]) : nan;
+        row[17] = nb ? sbq_unkey(s_stat[SBQ_MAX_STRESS * maxP + g]) : nan;
+        row[18] = nb ? sbq_unkey(s_stat[SBQ_MIN_STRESS * maxP + g]) : nan;
+        row[20] = row[21] = row[22] = row[23] = 0.0f;
+    }
+}
+
+// ---------------------------------------------------------------- host
+bool sbb_body_summary_info(sb_batch *b, const char *key, uint64_t *value)
+{
+    const std::string k(key);
+    if (k == "body_summary_words") *value = SB_BATCH_BODY_SUMMARY_WORDS;
+    else if (k == "body_summary_lds_bytes") *value = sbq_lds_bytes(b->V.maxP);
+    else if (k == "body_summary_kernel_vgprs" || k == "body_summary_kernel_scratch_bytes") {
+        if (b->body_summary_vgprs < 0) {
+            hipFuncAttributes fa{};
+            if (hipSetDevice(b->device) != hipSuccess || hipFuncGetAttributes(&fa, (const void *)k_batch_body_summary) != hipSuccess) {
+                (void)hipGetLastError();
+                *value = 0;
+                return true;
+            }
+            b->body_summary_vgprs = fa.numRegs;
+            b->body_summary_scratch = (int)fa.localSizeBytes;
+        }
+        *value = (uint64_t)std::max(k == "body_summary_kernel_vgprs" ? b->body_summary_vgprs : b->body_summary_scratch, 0);
+    } else return false;
+    return true;
+}
+
+sb_status sb_batch_body_summary_device(sb_batch *b, const void *device_labels_i32, uint32_t max_rows, void *device_rows_f32, void *device_rank_i32)
+{
+    if (!b) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_body_summary_device: null batch");
+    if (!device_labels_i32) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_body_summary_device: null labels");
+    if (!device_rows_f32 && !device_rank_i32) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_body_summary_device: rows and rank are both null: nothing to write");
+    if (max_rows == 0u || max_rows > b->V.maxP)
+        SB_FAIL(b, SB_ERR_INVALID, "sb_batch_body_summary_device: max_rows %u is not in 1 .. max_particles (%u)", max_rows, b->V.maxP);
+    if (((uintptr_t)device_labels_i32 & 3u) || ((uintptr_t)device_rows_f32 & 3u) || ((uintptr_t)device_rank_i32 & 3u))
+        SB_FAIL(b, SB_ERR_INVALID, "sb_batch_body_summary_device: the device buffers must be 4-byte aligned");
+    SB_HIP(b, hipSetDevice(b->device));
+    const SbBatchView &V = b->V;
+    const uint32_t W = sbq_pow2_at_least(V.maxP), lds = sbq_lds_bytes(V.maxP);
+    uint32_t logW = 0u;
+    while ((1u << logW) < W) logW++;
+    if (lds > SBQ_LDS_DEFAULT_LIMIT && !b->body_summary_lds_allowed) {
+        SB_HIP(b, hipFuncSetAttribute((const void *)k_batch_body_summary, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        b->body_summary_lds_allowed = true;
+    }
+    k_batch_body_summary<<<b->opt.n_scenes, SBQ_BLOCK, lds, b->stream>>>(V, (const int32_t *)device_labels_i32, max_rows, (float *)device_rows_f32,
+                                                                       (int32_t *)device_rank_i32, W, logW);
+    return check_launch(b, "sb_batch_body_summary_device");
+}
