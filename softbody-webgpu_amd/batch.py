@@ -271,6 +271,32 @@ class BatchEngine:
         self._check(call())
         cur.wait_stream(self._ext_stream)
 
+    def _bind(self, call, entries):
+        """The buffers of one report call.  entries: (name, given, wanted, shape, dtype) each; `given` is what the caller passed
+        (a device pointer, a torch tensor, or None: make one), or a function that makes the buffer from the batch (bodies()'s
+        labels).  In this order: everything the caller gave is validated; the functions are called; what is wanted and missing
+        is allocated; a flat tensor becomes a view of `shape`.  Returns (buffers, pointers, "one of them is a tensor"), None
+        where an entry is not wanted.  ValueError before anything is allocated or enqueued."""
+        import torch
+        nbytes = [int(np.prod(shape)) * np.dtype(dtype).itemsize for _, _, _, shape, dtype in entries]
+        for (name, given, _, _, dtype), nb in zip(entries, nbytes):
+            if given is not None and not callable(given):
+                self._device_buffer("%s: %s" % (call, name), given, dtype, nb)
+        made = [given() if callable(given) else given for _, given, _, _, _ in entries]
+        bufs, ptrs, tensors = [], [], False
+        for (name, _, wanted, shape, dtype), x, nb in zip(entries, made, nbytes):
+            ptr = None
+            if wanted:
+                if x is None:
+                    x = torch.empty(shape, dtype=getattr(torch, dtype), device=torch.device("cuda", self.device))
+                ptr, t = self._device_buffer("%s: %s" % (call, name), x, dtype, nb)
+                if t and tuple(x.shape) != tuple(shape):
+                    x = x.view(-1)[:int(np.prod(shape))].view(shape)
+                tensors |= t
+            bufs.append(x if wanted else None)
+            ptrs.append(ptr)
+        return bufs, ptrs, tensors
+
     def read_state_device(self, particles=None, beams=None, beam_alive=None):
         """Engine.read_state_device with a leading scene dimension: particles float32 [n_scenes, max_particles, 6], beams
         float32 [n_scenes, max_beams, 4] {target_length, last_length, strain, stress}, beam_alive uint8 / bool
@@ -321,14 +347,8 @@ class BatchEngine:
         and stress of the finite live beams; an empty set gives NaN; every word is written.  `out`: a device pointer (int) or a
         contiguous float32 torch tensor of at least n_scenes * 24 elements to write into.  Only reads the batch, only enqueues;
         torch's current stream is ordered after it."""
-        import torch
-        n = self.n_scenes
-        if out is None:
-            out = torch.empty((n, SUMMARY_WORDS), dtype=torch.float32, device=torch.device("cuda", self.device))
-        ptr, t = self._device_buffer("summary: out", out, "float32", n * SUMMARY_WORDS * 4)
+        (out,), (ptr,), t = self._bind("summary", [("out", out, True, (self.n_scenes, SUMMARY_WORDS), "float32")])
         self._ordered(t, lambda: load_library().sb_batch_summary_device(self._h, ctypes.c_void_p(ptr)))
-        if t and tuple(out.shape) != (n, SUMMARY_WORDS):
-            return out.view(-1)[:n * SUMMARY_WORDS].view(n, SUMMARY_WORDS)
         return out
 
     def rollout(self, inputs=None, frames=None, summary=True, out=None):
@@ -347,24 +367,14 @@ class BatchEngine:
         frames = int(frames)
         if frames < 0:
             raise ValueError("rollout: frames is %d" % frames)
-        iptr = optr = None
-        tensors = False
+        iptr, tensors = None, False
         if inputs is not None:
-            iptr, t = self._device_buffer("rollout: inputs", inputs, None, frames * n * 32)
-            tensors |= t
-        if summary:
-            if out is None:
-                out = torch.empty((frames, n, SUMMARY_WORDS), dtype=torch.float32, device=torch.device("cuda", self.device))
-            optr, t = self._device_buffer("rollout: out", out, "float32", frames * n * SUMMARY_WORDS * 4)
-            tensors |= t
-        elif out is not None:
+            iptr, tensors = self._device_buffer("rollout: inputs", inputs, None, frames * n * 32)
+        if not summary and out is not None:
             raise ValueError("rollout: `out` is given but summary=False")
+        (out,), (optr,), t = self._bind("rollout", [("out", out, bool(summary), (frames, n, SUMMARY_WORDS), "float32")])
         vp = ctypes.c_void_p
-        self._ordered(tensors, lambda: load_library().sb_batch_rollout_device(self._h, frames, vp(iptr), vp(optr)))
-        if not summary:
-            return None
-        if isinstance(out, torch.Tensor) and tuple(out.shape) != (frames, n, SUMMARY_WORDS):
-            return out.view(-1)[:frames * n * SUMMARY_WORDS].view(frames, n, SUMMARY_WORDS)
+        self._ordered(tensors | t, lambda: load_library().sb_batch_rollout_device(self._h, frames, vp(iptr), vp(optr)))
         return out
 
     # ---- connected bodies (sb_batch_bodies_device)
@@ -378,30 +388,14 @@ class BatchEngine:
         [n_scenes, max_particles, 2]: {particles, live beams} of the body at its label's row, {0, 0} in every other row.  Every
         word is written.  labels / counts / sizes: a device pointer (int) or a contiguous int32 torch tensor of at least that
         many elements to write into.  Only reads the batch, only enqueues; torch's current stream is ordered after it."""
-        import torch
-        n, dev = self.n_scenes, torch.device("cuda", self.device)
-        shapes = ((n, self.max_particles), (n, self.max_particles, 2), (n, BODY_WORDS))
-        outs = [labels, None if sizes is False else sizes, counts]
-        want = (True, sizes is not False, True)
-        for k, what in enumerate(("labels", "sizes", "counts")):   # (what the caller gave is looked at before anything is allocated)
-            if outs[k] is not None and outs[k] is not True:
-                self._device_buffer("bodies: " + what, outs[k], "int32", int(np.prod(shapes[k])) * 4)
-        ptrs, tensors = [], False
-        for k in range(3):
-            if not want[k]:
-                ptrs.append(None)
-                continue
-            if outs[k] is None or outs[k] is True:
-                outs[k] = torch.empty(shapes[k], dtype=torch.int32, device=dev)
-            numel = int(np.prod(shapes[k]))
-            ptr, t = self._device_buffer("bodies", outs[k], "int32", numel * 4)
-            if t and tuple(outs[k].shape) != shapes[k]:
-                outs[k] = outs[k].view(-1)[:numel].view(shapes[k])
-            ptrs.append(ptr)
-            tensors |= t
+        n, maxp = self.n_scenes, self.max_particles
+        given = [None if x is True else x for x in (labels, None if sizes is False else sizes, counts)]   # (True: a new tensor)
+        outs, ptrs, tensors = self._bind("bodies", [("labels", given[0], True, (n, maxp), "int32"),
+                                                    ("sizes", given[1], sizes is not False, (n, maxp, 2), "int32"),
+                                                    ("counts", given[2], True, (n, BODY_WORDS), "int32")])
         vp = ctypes.c_void_p
         self._ordered(tensors, lambda: load_library().sb_batch_bodies_device(self._h, vp(ptrs[0]), vp(ptrs[1]), vp(ptrs[2])))
-        return (outs[0], outs[2], outs[1]) if want[1] else (outs[0], outs[2])
+        return (outs[0], outs[2], outs[1]) if sizes is not False else (outs[0], outs[2])
 
     # ---- statistics per body (sb_batch_body_summary_device; DESIGN.md 5.16)
     def body_summary(self, labels=None, rows=8, out=None, rank=False):
@@ -418,38 +412,17 @@ class BatchEngine:
         its row was cut), -1 where no particle lives or the particle is in no group.  rows: 1 .. max_particles.  out / rank: a
         device pointer (int) or a contiguous torch tensor (float32 / int32) of at least that many elements to write into.  Every
         word is written.  Only reads the batch, only enqueues; torch's current stream is ordered after it."""
-        import torch
-        n, dev = self.n_scenes, torch.device("cuda", self.device)
-        if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or not 1 <= rows <= self.max_particles:
-            raise ValueError("body_summary: rows is %r, not a number in 1 .. max_particles (%d)" % (rows, self.max_particles))
+        n, maxp = self.n_scenes, self.max_particles
+        if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or not 1 <= rows <= maxp:
+            raise ValueError("body_summary: rows is %r, not a number in 1 .. max_particles (%d)" % (rows, maxp))
         rows = int(rows)
-        shapes = ((n, rows, BODY_SUMMARY_WORDS), (n, self.max_particles))
-        outs = [out, None if rank is False else rank]
-        want, dtypes = (True, rank is not False), ("float32", "int32")
-        for k, what in enumerate(("out", "rank")):   # (what the caller gave is looked at before anything is allocated or enqueued)
-            if outs[k] is not None and outs[k] is not True:
-                self._device_buffer("body_summary: " + what, outs[k], dtypes[k], int(np.prod(shapes[k])) * 4)
-        if labels is not None:
-            self._device_buffer("body_summary: labels", labels, "int32", n * self.max_particles * 4)
-        else:
-            labels = self.bodies()[0]
-        lptr, tensors = self._device_buffer("body_summary: labels", labels, "int32", n * self.max_particles * 4)
-        ptrs = []
-        for k in range(2):
-            if not want[k]:
-                ptrs.append(None)
-                continue
-            if outs[k] is None or outs[k] is True:
-                outs[k] = torch.empty(shapes[k], dtype=getattr(torch, dtypes[k]), device=dev)
-            numel = int(np.prod(shapes[k]))
-            ptr, t = self._device_buffer("body_summary", outs[k], dtypes[k], numel * 4)
-            if t and tuple(outs[k].shape) != shapes[k]:
-                outs[k] = outs[k].view(-1)[:numel].view(shapes[k])
-            ptrs.append(ptr)
-            tensors |= t
+        outs, ptrs, tensors = self._bind("body_summary", [
+            ("out", None if out is True else out, True, (n, rows, BODY_SUMMARY_WORDS), "float32"),
+            ("rank", None if rank is True or rank is False else rank, rank is not False, (n, maxp), "int32"),
+            ("labels", (lambda: self.bodies()[0]) if labels is None else labels, True, (n, maxp), "int32")])
         vp = ctypes.c_void_p
-        self._ordered(tensors, lambda: load_library().sb_batch_body_summary_device(self._h, vp(lptr), rows, vp(ptrs[0]), vp(ptrs[1])))
-        return (outs[0], outs[1]) if want[1] else outs[0]
+        self._ordered(tensors, lambda: load_library().sb_batch_body_summary_device(self._h, vp(ptrs[2]), rows, vp(ptrs[0]), vp(ptrs[1])))
+        return (outs[0], outs[1]) if rank is not False else outs[0]
 
     # ---- particle and wall contacts (sb_batch_contacts_device; DESIGN.md 5.15)
     def contacts(self, labels=None, pairs=0, other_body=False, touch=None, counts=None):
@@ -469,7 +442,7 @@ class BatchEngine:
         counts: a device pointer (int) or a contiguous int32 torch tensor of at least that many elements to write into.  Every
         word is written.  Only reads the batch, only enqueues; torch's current stream is ordered after it."""
         import torch
-        n, dev = self.n_scenes, torch.device("cuda", self.device)
+        n, maxp = self.n_scenes, self.max_particles
         max_pairs = 0
         if isinstance(pairs, torch.Tensor):
             self._device_buffer("contacts: pairs", pairs, "int32", n * 2 * 4)
@@ -478,36 +451,16 @@ class BatchEngine:
             if isinstance(pairs, bool) or not isinstance(pairs, (int, np.integer)) or not 0 <= pairs < 2 ** 32:
                 raise ValueError("contacts: pairs is a number of pairs per scene or an int32 torch tensor, not %r" % (pairs,))
             max_pairs = int(pairs)
-        shapes = ((n, self.max_particles, CONTACT_WORDS), (n, max_pairs, 2), (n, CONTACT_WORDS))
-        outs = [touch, pairs if isinstance(pairs, torch.Tensor) else None, counts]
-        want = (True, max_pairs > 0, True)
-        for k, what in enumerate(("touch", "pairs", "counts")):   # (what the caller gave is looked at before anything is allocated)
-            if outs[k] is not None:
-                self._device_buffer("contacts: " + what, outs[k], "int32", int(np.prod(shapes[k])) * 4)
-        lptr, tensors = None, False
-        if labels is True:
-            labels = self.bodies()[0]
-        if labels is not None:
-            lptr, t = self._device_buffer("contacts: labels", labels, "int32", n * self.max_particles * 4)
-            tensors |= t
-        ptrs = []
-        for k in range(3):
-            if not want[k]:
-                ptrs.append(None)
-                continue
-            if outs[k] is None:
-                outs[k] = torch.empty(shapes[k], dtype=torch.int32, device=dev)
-            numel = int(np.prod(shapes[k]))
-            ptr, t = self._device_buffer("contacts", outs[k], "int32", numel * 4)
-            if t and tuple(outs[k].shape) != shapes[k]:
-                outs[k] = outs[k].view(-1)[:numel].view(shapes[k])
-            ptrs.append(ptr)
-            tensors |= t
+        outs, ptrs, tensors = self._bind("contacts", [
+            ("touch", touch, True, (n, maxp, CONTACT_WORDS), "int32"),
+            ("pairs", pairs if isinstance(pairs, torch.Tensor) else None, max_pairs > 0, (n, max_pairs, 2), "int32"),
+            ("counts", counts, True, (n, CONTACT_WORDS), "int32"),
+            ("labels", (lambda: self.bodies()[0]) if labels is True else labels, labels is not None, (n, maxp), "int32")])
         vp = ctypes.c_void_p
         flags = CONTACTS_OTHER_BODY if other_body else 0
-        self._ordered(tensors, lambda: load_library().sb_batch_contacts_device(self._h, flags, vp(lptr), vp(ptrs[0]), vp(ptrs[1]), max_pairs,
+        self._ordered(tensors, lambda: load_library().sb_batch_contacts_device(self._h, flags, vp(ptrs[3]), vp(ptrs[0]), vp(ptrs[1]), max_pairs,
                                                                                vp(ptrs[2])))
-        return (outs[0], outs[2], outs[1]) if want[1] else (outs[0], outs[2])
+        return (outs[0], outs[2], outs[1]) if max_pairs > 0 else (outs[0], outs[2])
 
     # ---- pictures (sb_batch_render_device / sb_batch_render_scene)
     def _render_options(self, resolution, bounds_size, particle_radius, first=0, count=0):
@@ -525,7 +478,6 @@ class BatchEngine:
         body (RGB8, rows top to bottom) of what load_scene would return now; scenes never uploaded or empty are black.
         None = the batch's own bounds / radius.  `out`: a device pointer (int) or a contiguous uint8 torch tensor of at least
         count * resolution^2 * 3 bytes to draw into.  Only enqueues; torch's current stream is ordered after the render."""
-        import torch
         res = int(resolution)
         if not 0 < res <= BATCH_RENDER_MAX_RESOLUTION:
             raise ValueError("render: resolution %d is not in 1 .. %d" % (res, BATCH_RENDER_MAX_RESOLUTION))
@@ -533,13 +485,9 @@ class BatchEngine:
         count = self.n_scenes - first if count is None else int(count)
         if first < 0 or count < 1 or first + count > self.n_scenes:
             raise ValueError("render: scenes %d .. %d+%d are not all inside the batch of %d" % (first, first, count, self.n_scenes))
-        if out is None:
-            out = torch.empty((count, res, res, 3), dtype=torch.uint8, device=torch.device("cuda", self.device))
-        ptr, t = self._device_buffer("render: out", out, "uint8", count * res * res * 3)
+        (out,), (ptr,), t = self._bind("render", [("out", out, True, (count, res, res, 3), "uint8")])
         o = self._render_options(res, bounds_size, particle_radius, first, count)
         self._ordered(t, lambda: load_library().sb_batch_render_device(self._h, ctypes.byref(o), ctypes.c_void_p(ptr)))
-        if t and tuple(out.shape) != (count, res, res, 3):
-            return out.view(-1)[:count * res * res * 3].view(count, res, res, 3)
         return out
 
     def render_scene(self, i, resolution=64, bounds_size=None, particle_radius=None):

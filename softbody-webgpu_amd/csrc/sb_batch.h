@@ -1,10 +1,14 @@
 // sb_batch.h -- what the files of the sb_batch_* group share: the device memory of a batch and its host object
 // (sb_batch.hip: upload, stepping, state I/O; sb_batch_render.hip: pictures; sb_batch_summary.hip: per-scene statistics, rollouts;
 // sb_batch_bodies.hip: connected bodies; sb_batch_contacts.hip: particle and wall contacts; sb_batch_body_summary.hip: statistics per
-// body).
+// body), and what the four report kernels have in common: the scene header each of them opens with (sbb_scene), the float <->
+// ordered-key codec of their extremes (sbb_fkey) and the width of the pinned summation tree (sbb_pow2_at_least); on the host the
+// cache behind the *_kernel_vgprs / *_kernel_scratch_bytes info keys (sbb_kernel_res) and the alignment test of the entry points
+// (sbb_misaligned4).  All of it is inline; what only one kernel uses stays in that kernel's file.
 #pragma once
 #include <algorithm>
 #include <cstdio>
+#include <initializer_list>
 #include <string>
 
 #include "../../include/softbody.h"
@@ -79,8 +83,52 @@ static inline uint32_t sb_batch_cell_geometry(float bounds, float radius, uint32
 SB_DEV uint32_t sbb_uniform(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
 SB_DEV float sbb_uniform(float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); }
 
+// ---------------------------------------------------------------- what the report kernels share (one workgroup per scene)
+// The header of a scene, workgroup-uniform: `loaded` (0: never uploaded), its particle slots P and live beam slots Bc -- 0 in a
+// scene never uploaded, else the metadata's counts, clamped to the capacity (an upload is refused unless they fit; beam slots
+// >= Bc are stale: never read) -- and its constant and state blobs.
+struct SbbScene {
+    uint32_t loaded, P, Bc;
+    const unsigned char *cst, *st;
+};
+SB_DEV SbbScene sbb_scene(const SbBatchView &V, uint32_t scene)
+{
+    const uint32_t *meta = V.meta + (size_t)scene * SB_BM_WORDS;
+    SbbScene s;
+    // (metadata words are rewritten between launches by other kernels: read at agent scope, as k_batch_frame does; all three
+    // loads are issued before the first is looked at -- the words of a scene never uploaded are zero)
+    s.loaded = sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_LOADED]));
+    const uint32_t P = sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_P])), Bc = sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_B]));
+    s.P = s.loaded ? min(P, V.maxP) : 0u;
+    s.Bc = s.loaded ? min(Bc, V.maxB) : 0u;
+    s.cst = V.cst + (size_t)scene * V.cst_bytes, s.st = V.st + (size_t)scene * V.st_bytes;
+    return s;
+}
+
+#define SBB_QNAN 0x7FC00000u // the word of a statistic over an empty set
+SB_DEV bool sbb_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+// finite floats as unsigned keys of the same order (-0 below +0: either may come back from an extreme)
+SB_DEV uint32_t sbb_fkey(float x)
+{
+    const uint32_t b = __float_as_uint(x);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+SB_DEV float sbb_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// the leaves of the pinned summation tree over a capacity: the smallest power of two >= n
+static inline uint32_t sbb_pow2_at_least(uint32_t n)
+{
+    uint32_t w = 1u;
+    while (w < n) w <<= 1;
+    return w;
+}
+
 // ---------------------------------------------------------------- host
 struct SbBatchRender; // sb_batch_render.hip
+// registers and scratch bytes of one kernel as the runtime reports them (asked for at the first sb_batch_get_info of either)
+struct SbbKernelRes {
+    int vgprs = -1, scratch = 0;
+};
 
 struct sb_batch {
     sb_batch_options opt{};
@@ -102,10 +150,7 @@ struct sb_batch {
     uint64_t frames_done = 0, substeps_done = 0;
     int scenes_per_cu = 0, vgprs = 0, scratch = 0;
     SbBatchRender *render = nullptr; // what the renderer keeps between calls (made at the first render)
-    int summary_vgprs = -1, summary_scratch = 0; // k_batch_summary's (asked for at the first sb_batch_get_info of them)
-    int bodies_vgprs = -1, bodies_scratch = 0;   // k_batch_bodies' (likewise)
-    int contacts_vgprs = -1, contacts_scratch = 0; // k_batch_contacts' (likewise)
-    int body_summary_vgprs = -1, body_summary_scratch = 0; // k_batch_body_summary's (likewise)
+    SbbKernelRes render_res, summary_res, bodies_res, contacts_res, body_summary_res; // of k_batch_render, k_batch_summary, ...
     bool body_summary_lds_allowed = false; // k_batch_body_summary may be launched with more than 64 KiB of LDS (asked for at the first such launch)
 };
 
@@ -118,6 +163,30 @@ static inline sb_status check_launch(sb_batch *b, const char *what)
     const hipError_t r = hipGetLastError();
     if (r != hipSuccess) SB_FAIL(b, SB_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(r));
     return SB_OK;
+}
+
+// sb_batch_get_info's "<report>_kernel_vgprs" (want_vgprs) / "<report>_kernel_scratch_bytes" of `kernel`, whose answers `r` keeps;
+// 0 where the runtime does not tell (its error is taken off the record: it must not resurface in a later launch check)
+static inline uint64_t sbb_kernel_res(sb_batch *b, SbbKernelRes &r, const void *kernel, bool want_vgprs)
+{
+    if (r.vgprs < 0) {
+        hipFuncAttributes fa{};
+        if (hipSetDevice(b->device) != hipSuccess || hipFuncGetAttributes(&fa, kernel) != hipSuccess) {
+            (void)hipGetLastError();
+            return 0;
+        }
+        r.vgprs = fa.numRegs;
+        r.scratch = (int)fa.localSizeBytes;
+    }
+    return (uint64_t)std::max(want_vgprs ? r.vgprs : r.scratch, 0);
+}
+
+// "is one of these device pointers not 4-byte aligned?" (null is aligned: an output that is not asked for)
+static inline bool sbb_misaligned4(std::initializer_list<const void *> ptrs)
+{
+    uintptr_t low = 0;
+    for (const void *p : ptrs) low |= (uintptr_t)p;
+    return (low & 3u) != 0;
 }
 
 static inline uint32_t up16(uint32_t x) { return (x + 15u) & ~15u; }

@@ -57,12 +57,9 @@ __global__ __launch_bounds__(SBO_BLOCK) void k_batch_bodies(SbBatchView V, int32
     uint32_t *s_edge = s_nb + maxP;    // [maxB] per live beam SLOT: (slot of endpoint A) | (slot of endpoint B) << 16
     uint32_t *s_red = s_edge + maxB;   // [SBO_NWORDS]
 
-    const uint32_t *meta = V.meta + (size_t)scene * SB_BM_WORDS;
-    // (metadata words are rewritten between launches by other kernels: read at agent scope, as k_batch_frame does)
-    const uint32_t loaded = sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_LOADED]));
-    const uint32_t P = loaded ? min(sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_P])), maxP) : 0u; // (counts are validated at upload)
-    const uint32_t Bc = loaded ? min(sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_B])), maxB) : 0u; // beam slots >= Bc are stale: never read
-    const unsigned char *cst = V.cst + (size_t)scene * V.cst_bytes, *st = V.st + (size_t)scene * V.st_bytes;
+    const SbbScene hd = sbb_scene(V, scene);
+    const uint32_t P = hd.P, Bc = hd.Bc;
+    const unsigned char *cst = hd.cst, *st = hd.st;
     const uint32_t *g_pmap = (const uint32_t *)(cst + V.o_pmap), *g_bword = (const uint32_t *)(cst + V.o_bword);
     const uint32_t *g_bmap = (const uint32_t *)(st + V.o_bmap);
 
@@ -153,19 +150,9 @@ bool sbb_bodies_info(sb_batch *b, const char *key, uint64_t *value)
     const std::string k(key);
     if (k == "body_words") *value = SB_BATCH_BODY_WORDS;
     else if (k == "bodies_lds_bytes") *value = sbo_lds_bytes(b->V.maxP, b->V.maxB);
-    else if (k == "bodies_kernel_vgprs" || k == "bodies_kernel_scratch_bytes") {
-        if (b->bodies_vgprs < 0) {
-            hipFuncAttributes fa{};
-            if (hipSetDevice(b->device) != hipSuccess || hipFuncGetAttributes(&fa, (const void *)k_batch_bodies) != hipSuccess) {
-                (void)hipGetLastError();
-                *value = 0;
-                return true;
-            }
-            b->bodies_vgprs = fa.numRegs;
-            b->bodies_scratch = (int)fa.localSizeBytes;
-        }
-        *value = (uint64_t)std::max(k == "bodies_kernel_vgprs" ? b->bodies_vgprs : b->bodies_scratch, 0);
-    } else return false;
+    else if (k == "bodies_kernel_vgprs" || k == "bodies_kernel_scratch_bytes")
+        *value = sbb_kernel_res(b, b->bodies_res, (const void *)k_batch_bodies, k == "bodies_kernel_vgprs");
+    else return false;
     return true;
 }
 
@@ -174,7 +161,7 @@ sb_status sb_batch_bodies_device(sb_batch *b, void *device_labels_i32, void *dev
     if (!b) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_bodies_device: null batch");
     if (!device_labels_i32 && !device_sizes_i32 && !device_counts_i32)
         SB_FAIL(b, SB_ERR_INVALID, "sb_batch_bodies_device: labels, sizes and counts are all null: nothing to write");
-    if (((uintptr_t)device_labels_i32 & 3u) || ((uintptr_t)device_sizes_i32 & 3u) || ((uintptr_t)device_counts_i32 & 3u))
+    if (sbb_misaligned4({device_labels_i32, device_sizes_i32, device_counts_i32}))
         SB_FAIL(b, SB_ERR_INVALID, "sb_batch_bodies_device: the device buffers must be 4-byte aligned");
     SB_HIP(b, hipSetDevice(b->device));
     const SbBatchView &V = b->V;

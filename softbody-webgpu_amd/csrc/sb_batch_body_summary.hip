@@ -30,7 +30,6 @@
 #define SBQ_BLOCK 256u
 #define SBQ_NSUM 6u // x, y, vx, vy, 0.5 (vx^2 + vy^2), x vy - y vx
 #define SBQ_NONE 0xFFFFFFFFu
-#define SBQ_QNAN 0x7FC00000u
 #define SBQ_LDS_DEFAULT_LIMIT (64u * 1024u) // above it a launch needs hipFuncAttributeMaxDynamicSharedMemorySize
 
 // per-label statistics words, each an array of max_particles entries
@@ -43,27 +42,13 @@ enum {
 
 static_assert(SB_BATCH_MAX_PARTICLES <= 1024 && SB_BATCH_MAX_BEAMS < 0x10000, "a rank key holds 10 bits of label, a count word 16 bits per count");
 
-static inline uint32_t sbq_pow2_at_least(uint32_t n)
-{
-    uint32_t w = 1u;
-    while (w < n) w <<= 1;
-    return w;
-}
 // LDS of a workgroup: double col[SBQ_NSUM][W]; uint32 key[W], rkey[W], grp[maxP], rank[maxP], stat[SBQ_NSTAT][maxP]
 static inline uint32_t sbq_lds_bytes(uint32_t maxP)
 {
-    const uint32_t W = sbq_pow2_at_least(maxP);
+    const uint32_t W = sbb_pow2_at_least(maxP);
     return W * (SBQ_NSUM * 8u + 2u * 4u) + maxP * (2u + SBQ_NSTAT) * 4u;
 }
 
-SB_DEV bool sbq_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-// finite floats as unsigned keys of the same order (-0 below +0: either may come back from an extreme)
-SB_DEV uint32_t sbq_fkey(float x)
-{
-    const uint32_t b = __float_as_uint(x);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-SB_DEV float sbq_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 SB_DEV double sbq_canon(double sum) { return sum + 0.0; } // -0.0 -> +0.0, every other value as it is
 
 // ascending bitonic sort of a[0 .. W-1] (W a power of two) by the whole workgroup; ends in a barrier
@@ -87,7 +72,7 @@ __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V,
     extern __shared__ __attribute__((aligned(16))) double sbq_lds[];
     const uint32_t scene = blockIdx.x, tid = threadIdx.x;
     if (scene >= V.n_scenes) return;
-    const uint32_t maxP = V.maxP, maxB = V.maxB;
+    const uint32_t maxP = V.maxP;
     double *s_col = sbq_lds;                      // [SBQ_NSUM][W] partial sums at sorted positions
     uint32_t *s_key = (uint32_t *)(s_col + SBQ_NSUM * W); // [W] label * W + bitrev(data index) of the finite members, SBQ_NONE behind them
     uint32_t *s_rkey = s_key + W;                 // [W] ~(particles << 10 | (1023 - label)) of the non-empty groups, SBQ_NONE behind them
@@ -95,12 +80,9 @@ __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V,
     uint32_t *s_rank = s_grp + maxP;              // [maxP] per label: its rank
     uint32_t *s_stat = s_rank + maxP;             // [SBQ_NSTAT][maxP] per label
 
-    const uint32_t *meta = V.meta + (size_t)scene * SB_BM_WORDS;
-    // (metadata words are rewritten between launches by other kernels: read at agent scope, as k_batch_frame does)
-    const uint32_t loaded = sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_LOADED]));
-    const uint32_t P = loaded ? min(sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_P])), maxP) : 0u; // (counts are validated at upload)
-    const uint32_t Bc = loaded ? min(sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_B])), maxB) : 0u; // beam slots >= Bc are stale: never read
-    const unsigned char *cst = V.cst + (size_t)scene * V.cst_bytes, *st = V.st + (size_t)scene * V.st_bytes;
+    const SbbScene hd = sbb_scene(V, scene);
+    const uint32_t P = hd.P, Bc = hd.Bc;
+    const unsigned char *cst = hd.cst, *st = hd.st;
     const uint32_t *g_pmap = (const uint32_t *)(cst + V.o_pmap), *g_bword = (const uint32_t *)(cst + V.o_bword);
     const uint32_t *g_bmap = (const uint32_t *)(st + V.o_bmap), *g_flags = (const uint32_t *)(st + V.o_bflags);
     const float2 *g_part = (const float2 *)(st + V.o_part);
@@ -125,15 +107,15 @@ __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V,
         if (g >= maxP) continue;
         s_grp[d] = g;
         const float2 p = g_part[3u * d], v = g_part[3u * d + 1u], a = g_part[3u * d + 2u];
-        if (!(sbq_finite(p.x) && sbq_finite(p.y) && sbq_finite(v.x) && sbq_finite(v.y) && sbq_finite(a.x) && sbq_finite(a.y))) {
+        if (!(sbb_finite(p.x) && sbb_finite(p.y) && sbb_finite(v.x) && sbb_finite(v.y) && sbb_finite(a.x) && sbb_finite(a.y))) {
             atomicAdd(&s_stat[SBQ_NP * maxP + g], 0x10001u);
             continue;
         }
         atomicAdd(&s_stat[SBQ_NP * maxP + g], 1u);
-        atomicMin(&s_stat[SBQ_MINX * maxP + g], sbq_fkey(p.x));
-        atomicMin(&s_stat[SBQ_MINY * maxP + g], sbq_fkey(p.y));
-        atomicMax(&s_stat[SBQ_MAXX * maxP + g], sbq_fkey(p.x));
-        atomicMax(&s_stat[SBQ_MAXY * maxP + g], sbq_fkey(p.y));
+        atomicMin(&s_stat[SBQ_MINX * maxP + g], sbb_fkey(p.x));
+        atomicMin(&s_stat[SBQ_MINY * maxP + g], sbb_fkey(p.y));
+        atomicMax(&s_stat[SBQ_MAXX * maxP + g], sbb_fkey(p.x));
+        atomicMax(&s_stat[SBQ_MAXY * maxP + g], sbb_fkey(p.y));
         // (rounding to float is monotonic: the largest float is the float of the largest double; >= 0, so its bits order as it does)
         const double v2 = (double)v.x * (double)v.x + (double)v.y * (double)v.y;
         atomicMax(&s_stat[SBQ_MAX_V2 * maxP + g], __float_as_uint((float)v2));
@@ -148,14 +130,14 @@ __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V,
         if (g == SBQ_NONE || g != s_grp[g_pmap[w >> 16]]) continue;
         const float4 q = g_bstate[bd]; // {target_length, last_length, strain, stress}
         if ((j >> 5) < V.nflagw && ((g_flags[j >> 5] >> (j & 31u)) & 1u)) atomicAdd(&s_stat[SBQ_PENDING * maxP + g], 1u);
-        if (!(sbq_finite(q.z) && sbq_finite(q.w))) {
+        if (!(sbb_finite(q.z) && sbb_finite(q.w))) {
             atomicAdd(&s_stat[SBQ_NB * maxP + g], 0x10001u);
             continue;
         }
         atomicAdd(&s_stat[SBQ_NB * maxP + g], 1u);
-        atomicMax(&s_stat[SBQ_MAX_STRAIN * maxP + g], sbq_fkey(q.z));
-        atomicMax(&s_stat[SBQ_MAX_STRESS * maxP + g], sbq_fkey(q.w));
-        atomicMin(&s_stat[SBQ_MIN_STRESS * maxP + g], sbq_fkey(q.w));
+        atomicMax(&s_stat[SBQ_MAX_STRAIN * maxP + g], sbb_fkey(q.z));
+        atomicMax(&s_stat[SBQ_MAX_STRESS * maxP + g], sbb_fkey(q.w));
+        atomicMin(&s_stat[SBQ_MIN_STRESS * maxP + g], sbb_fkey(q.w));
     }
     // ---- the ranking: particles descending, then label ascending
     for (uint32_t q = tid; q < W; q += SBQ_BLOCK) {
@@ -210,7 +192,7 @@ __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V,
     }
     if (!rows) return; // (uniform)
     float *out = rows + (size_t)scene * max_rows * SB_BATCH_BODY_SUMMARY_WORDS;
-    const float nan = __uint_as_float(SBQ_QNAN);
+    const float nan = __uint_as_float(SBB_QNAN);
     // ---- the sums, from the first sorted position of every label that has a finite member
     for (uint32_t q = tid; q < W; q += SBQ_BLOCK) {
         const uint32_t key = s_key[q];
@@ -248,14 +230,14 @@ __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V,
             row[6] = row[7] = row[8] = row[9] = nan;
             row[14] = row[19] = 0.0f;
         }
-        row[10] = np ? sbq_unkey(s_stat[SBQ_MINX * maxP + g]) : nan;
-        row[11] = np ? sbq_unkey(s_stat[SBQ_MINY * maxP + g]) : nan;
-        row[12] = np ? sbq_unkey(s_stat[SBQ_MAXX * maxP + g]) : nan;
-        row[13] = np ? sbq_unkey(s_stat[SBQ_MAXY * maxP + g]) : nan;
+        row[10] = np ? sbb_unkey(s_stat[SBQ_MINX * maxP + g]) : nan;
+        row[11] = np ? sbb_unkey(s_stat[SBQ_MINY * maxP + g]) : nan;
+        row[12] = np ? sbb_unkey(s_stat[SBQ_MAXX * maxP + g]) : nan;
+        row[13] = np ? sbb_unkey(s_stat[SBQ_MAXY * maxP + g]) : nan;
         row[15] = np ? __uint_as_float(s_stat[SBQ_MAX_V2 * maxP + g]) : nan;
-        row[16] = nb ? sbq_unkey(s_stat[SBQ_MAX_STRAIN * maxP + g]) : nan;
-        row[17] = nb ? sbq_unkey(s_stat[SBQ_MAX_STRESS * maxP + g]) : nan;
-        row[18] = nb ? sbq_unkey(s_stat[SBQ_MIN_STRESS * maxP + g]) : nan;
+        row[16] = nb ? sbb_unkey(s_stat[SBQ_MAX_STRAIN * maxP + g]) : nan;
+        row[17] = nb ? sbb_unkey(s_stat[SBQ_MAX_STRESS * maxP + g]) : nan;
+        row[18] = nb ? sbb_unkey(s_stat[SBQ_MIN_STRESS * maxP + g]) : nan;
         row[20] = row[21] = row[22] = row[23] = 0.0f;
     }
 }
@@ -266,19 +248,9 @@ bool sbb_body_summary_info(sb_batch *b, const char *key, uint64_t *value)
     const std::string k(key);
     if (k == "body_summary_words") *value = SB_BATCH_BODY_SUMMARY_WORDS;
     else if (k == "body_summary_lds_bytes") *value = sbq_lds_bytes(b->V.maxP);
-    else if (k == "body_summary_kernel_vgprs" || k == "body_summary_kernel_scratch_bytes") {
-        if (b->body_summary_vgprs < 0) {
-            hipFuncAttributes fa{};
-            if (hipSetDevice(b->device) != hipSuccess || hipFuncGetAttributes(&fa, (const void *)k_batch_body_summary) != hipSuccess) {
-                (void)hipGetLastError();
-                *value = 0;
-                return true;
-            }
-            b->body_summary_vgprs = fa.numRegs;
-            b->body_summary_scratch = (int)fa.localSizeBytes;
-        }
-        *value = (uint64_t)std::max(k == "body_summary_kernel_vgprs" ? b->body_summary_vgprs : b->body_summary_scratch, 0);
-    } else return false;
+    else if (k == "body_summary_kernel_vgprs" || k == "body_summary_kernel_scratch_bytes")
+        *value = sbb_kernel_res(b, b->body_summary_res, (const void *)k_batch_body_summary, k == "body_summary_kernel_vgprs");
+    else return false;
     return true;
 }
 
@@ -289,11 +261,11 @@ sb_status sb_batch_body_summary_device(sb_batch *b, const void *device_labels_i3
     if (!device_rows_f32 && !device_rank_i32) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_body_summary_device: rows and rank are both null: nothing to write");
     if (max_rows == 0u || max_rows > b->V.maxP)
         SB_FAIL(b, SB_ERR_INVALID, "sb_batch_body_summary_device: max_rows %u is not in 1 .. max_particles (%u)", max_rows, b->V.maxP);
-    if (((uintptr_t)device_labels_i32 & 3u) || ((uintptr_t)device_rows_f32 & 3u) || ((uintptr_t)device_rank_i32 & 3u))
+    if (sbb_misaligned4({device_labels_i32, device_rows_f32, device_rank_i32}))
         SB_FAIL(b, SB_ERR_INVALID, "sb_batch_body_summary_device: the device buffers must be 4-byte aligned");
     SB_HIP(b, hipSetDevice(b->device));
     const SbBatchView &V = b->V;
-    const uint32_t W = sbq_pow2_at_least(V.maxP), lds = sbq_lds_bytes(V.maxP);
+    const uint32_t W = sbb_pow2_at_least(V.maxP), lds = sbq_lds_bytes(V.maxP);
     uint32_t logW = 0u;
     while ((1u << logW) < W) logW++;
     if (lds > SBQ_LDS_DEFAULT_LIMIT && !b->body_summary_lds_allowed) {

@@ -104,12 +104,10 @@ __global__ __launch_bounds__(SBK_BLOCK) void k_batch_contacts(SbBatchView V, SbP
     uint32_t *s_end = s_above + maxP;             // [ncell + 1] particles per cell, then the end of every cell in s_sorted
     uint32_t *s_red = s_end + ncell + 1u;         // [SBK_NWORDS]
 
-    const uint32_t *meta = V.meta + (size_t)scene * SB_BM_WORDS;
-    // (metadata words are rewritten between launches by other kernels: read at agent scope, as k_batch_frame does)
-    const uint32_t loaded = sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_LOADED]));
-    const uint32_t P = loaded ? min(sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_P])), maxP) : 0u; // (counts are validated at upload)
-    const uint32_t *g_pmap = (const uint32_t *)(V.cst + (size_t)scene * V.cst_bytes + V.o_pmap);
-    const float2 *g_part = (const float2 *)(V.st + (size_t)scene * V.st_bytes + V.o_part);
+    const SbbScene hd = sbb_scene(V, scene);
+    const uint32_t P = hd.P;
+    const uint32_t *g_pmap = (const uint32_t *)(hd.cst + V.o_pmap);
+    const float2 *g_part = (const float2 *)(hd.st + V.o_part);
     const int32_t *lrow = labels ? labels + (size_t)scene * maxP : nullptr;
     int32_t *trow = touch ? touch + (size_t)scene * maxP * SB_BATCH_CONTACT_WORDS : nullptr;
     int32_t *prow = pairs ? pairs + (size_t)scene * max_pairs * 2u : nullptr;
@@ -266,19 +264,9 @@ bool sbb_contacts_info(sb_batch *b, const char *key, uint64_t *value)
     if (k == "contact_words") *value = SB_BATCH_CONTACT_WORDS;
     else if (k == "contacts_cells_per_side") *value = sbk_cells(b, &cell);
     else if (k == "contacts_lds_bytes") *value = sbk_lds_bytes(b->V.maxP, sbk_cells(b, &cell));
-    else if (k == "contacts_kernel_vgprs" || k == "contacts_kernel_scratch_bytes") {
-        if (b->contacts_vgprs < 0) {
-            hipFuncAttributes fa{};
-            if (hipSetDevice(b->device) != hipSuccess || hipFuncGetAttributes(&fa, (const void *)k_batch_contacts) != hipSuccess) {
-                (void)hipGetLastError();
-                *value = 0;
-                return true;
-            }
-            b->contacts_vgprs = fa.numRegs;
-            b->contacts_scratch = (int)fa.localSizeBytes;
-        }
-        *value = (uint64_t)std::max(k == "contacts_kernel_vgprs" ? b->contacts_vgprs : b->contacts_scratch, 0);
-    } else return false;
+    else if (k == "contacts_kernel_vgprs" || k == "contacts_kernel_scratch_bytes")
+        *value = sbb_kernel_res(b, b->contacts_res, (const void *)k_batch_contacts, k == "contacts_kernel_vgprs");
+    else return false;
     return true;
 }
 
@@ -292,8 +280,7 @@ sb_status sb_batch_contacts_device(sb_batch *b, uint32_t flags, const void *devi
     if (!device_touch_i32 && !device_pairs_i32 && !device_counts_i32)
         SB_FAIL(b, SB_ERR_INVALID, "sb_batch_contacts_device: touch, pairs and counts are all null: nothing to write");
     if (device_pairs_i32 && max_pairs == 0u) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_contacts_device: a pair list of max_pairs 0");
-    if (((uintptr_t)device_labels_i32 & 3u) || ((uintptr_t)device_touch_i32 & 3u) || ((uintptr_t)device_pairs_i32 & 3u) ||
-        ((uintptr_t)device_counts_i32 & 3u))
+    if (sbb_misaligned4({device_labels_i32, device_touch_i32, device_pairs_i32, device_counts_i32}))
         SB_FAIL(b, SB_ERR_INVALID, "sb_batch_contacts_device: the device buffers must be 4-byte aligned");
     SB_HIP(b, hipSetDevice(b->device));
     float cell = 0.f;

@@ -36,7 +36,6 @@ struct SbBatchRender {
     uint8_t *d_rgb = nullptr; // sb_batch_render_scene's picture on its way to the host
     size_t cap_rgb = 0;
     bool attr_set = false;    // the kernel may use the whole LDS
-    int vgprs = -1, scratch = -1;
     uint32_t last_lds = 0, last_bands = 0;
 };
 
@@ -255,21 +254,9 @@ bool sbb_render_info(sb_batch *b, const char *key, uint64_t *value)
     const std::string k(key);
     if (k == "render_lds_bytes") *value = b->render ? b->render->last_lds : 0u;
     else if (k == "render_bands") *value = b->render ? b->render->last_bands : 0u;
-    else if (k == "render_kernel_vgprs" || k == "render_kernel_scratch_bytes") {
-        if (!b->render) b->render = new SbBatchRender();
-        SbBatchRender &r = *b->render;
-        if (r.vgprs < 0) {
-            hipFuncAttributes fa{};
-            if (hipSetDevice(b->device) != hipSuccess || hipFuncGetAttributes(&fa, (const void *)k_batch_render) != hipSuccess) {
-                (void)hipGetLastError();
-                *value = 0;
-                return true;
-            }
-            r.vgprs = fa.numRegs;
-            r.scratch = (int)fa.localSizeBytes;
-        }
-        *value = (uint64_t)std::max(k == "render_kernel_vgprs" ? r.vgprs : r.scratch, 0);
-    } else return false;
+    else if (k == "render_kernel_vgprs" || k == "render_kernel_scratch_bytes")
+        *value = sbb_kernel_res(b, b->render_res, (const void *)k_batch_render, k == "render_kernel_vgprs");
+    else return false;
     return true;
 }
 

@@ -21,22 +21,12 @@
 
 #define SBS_BLOCK 256u
 #define SBS_NSUM 6u  // px, py, vx, vy, kinetic energy | strain
-#define SBS_QNAN 0x7FC00000u
 
 // LDS statistics words
 enum {
     SBS_P_FIN, SBS_P_BAD, SBS_B_FIN, SBS_B_BAD, SBS_B_REMOVED, SBS_PENDING,
     SBS_MINX, SBS_MINY, SBS_MAXX, SBS_MAXY, SBS_MAX_STRAIN, SBS_MAX_STRESS, SBS_MIN_STRESS, SBS_NSTAT
 };
-
-SB_DEV bool sbs_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-// finite floats as unsigned keys of the same order (-0 below +0: either may come back from an extreme)
-SB_DEV uint32_t sbs_key(float x)
-{
-    const uint32_t b = __float_as_uint(x);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-SB_DEV float sbs_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 struct SbsScene {
     const unsigned char *pex, *bex, *balive;
@@ -58,7 +48,7 @@ SB_DEV void sbs_particle_leaf(const SbsScene &s, uint32_t i, double (&out)[5], S
     for (int k = 0; k < 5; k++) out[k] = 0.0;
     if (i >= s.maxP || !s.pex[i]) return;
     const float2 p = s.part[3u * i], v = s.part[3u * i + 1u], a = s.part[3u * i + 2u];
-    if (!(sbs_finite(p.x) && sbs_finite(p.y) && sbs_finite(v.x) && sbs_finite(v.y) && sbs_finite(a.x) && sbs_finite(a.y))) {
+    if (!(sbb_finite(p.x) && sbb_finite(p.y) && sbb_finite(v.x) && sbb_finite(v.y) && sbb_finite(a.x) && sbb_finite(a.y))) {
         l.p_bad++;
         return;
     }
@@ -80,7 +70,7 @@ SB_DEV void sbs_beam_leaf(const SbsScene &s, uint32_t i, double (&out)[1], SbsLo
     out[0] = 0.0;
     if (i >= s.maxB || !s.bex[i] || !s.balive[i]) return;
     const float4 q = s.bstate[i]; // {target_length, last_length, strain, stress}
-    if (!(sbs_finite(q.z) && sbs_finite(q.w))) {
+    if (!(sbb_finite(q.z) && sbb_finite(q.w))) {
         l.b_bad++;
         return;
     }
@@ -130,17 +120,14 @@ __global__ __launch_bounds__(SBS_BLOCK) void k_batch_summary(SbBatchView V, floa
     __shared__ uint32_t s_stat[SBS_NSTAT];
     const uint32_t scene = blockIdx.x, tid = threadIdx.x;
     if (scene >= V.n_scenes) return;
-    const uint32_t *meta = V.meta + (size_t)scene * SB_BM_WORDS;
     float *row = rows + (size_t)scene * SB_BATCH_SUMMARY_WORDS;
-    // (metadata words are rewritten between launches by other kernels: read at agent scope, as k_batch_frame does)
-    const uint32_t loaded = sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_LOADED]));
-    if (loaded == 0u) { // never uploaded: counts 0, no statistic
-        if (tid < SB_BATCH_SUMMARY_WORDS) row[tid] = (tid <= 5u || tid == 14u || tid >= 20u) ? 0.0f : __uint_as_float(SBS_QNAN);
+    const SbbScene hd = sbb_scene(V, scene);
+    if (hd.loaded == 0u) { // never uploaded: counts 0, no statistic
+        if (tid < SB_BATCH_SUMMARY_WORDS) row[tid] = (tid <= 5u || tid == 14u || tid >= 20u) ? 0.0f : __uint_as_float(SBB_QNAN);
         return;
     }
-    const uint32_t P = sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_P]));
-    const uint32_t Bc = min(sbb_uniform(SB_AGENT_LOAD(&meta[SB_BM_B])), V.maxB);
-    const unsigned char *cst = V.cst + (size_t)scene * V.cst_bytes, *st = V.st + (size_t)scene * V.st_bytes;
+    const uint32_t P = hd.P, Bc = hd.Bc; // (P: the metadata's own word, an upload is refused unless it fits the capacity)
+    const unsigned char *cst = hd.cst, *st = hd.st;
     SbsScene s;
     s.pex = cst + V.o_pex, s.bex = cst + V.o_bex, s.balive = st + V.o_balive;
     s.part = (const float2 *)(st + V.o_part), s.bstate = (const float4 *)(st + V.o_bstate);
@@ -183,17 +170,17 @@ __global__ __launch_bounds__(SBS_BLOCK) void k_batch_summary(SbBatchView V, floa
     if (l.b_bad) atomicAdd(&s_stat[SBS_B_BAD], l.b_bad);
     if (l.p_fin) {
         atomicAdd(&s_stat[SBS_P_FIN], l.p_fin);
-        atomicMin(&s_stat[SBS_MINX], sbs_key(l.minx));
-        atomicMin(&s_stat[SBS_MINY], sbs_key(l.miny));
-        atomicMax(&s_stat[SBS_MAXX], sbs_key(l.maxx));
-        atomicMax(&s_stat[SBS_MAXY], sbs_key(l.maxy));
+        atomicMin(&s_stat[SBS_MINX], sbb_fkey(l.minx));
+        atomicMin(&s_stat[SBS_MINY], sbb_fkey(l.miny));
+        atomicMax(&s_stat[SBS_MAXX], sbb_fkey(l.maxx));
+        atomicMax(&s_stat[SBS_MAXY], sbb_fkey(l.maxy));
         atomicMax(&s_max_v2, (unsigned long long)__double_as_longlong(l.max_v2)); // (>= 0: its bits order as it does)
     }
     if (l.b_fin) {
         atomicAdd(&s_stat[SBS_B_FIN], l.b_fin);
-        atomicMax(&s_stat[SBS_MAX_STRAIN], sbs_key(l.max_strain));
-        atomicMax(&s_stat[SBS_MAX_STRESS], sbs_key(l.max_stress));
-        atomicMin(&s_stat[SBS_MIN_STRESS], sbs_key(l.min_stress));
+        atomicMax(&s_stat[SBS_MAX_STRAIN], sbb_fkey(l.max_strain));
+        atomicMax(&s_stat[SBS_MAX_STRESS], sbb_fkey(l.max_stress));
+        atomicMin(&s_stat[SBS_MIN_STRESS], sbb_fkey(l.min_stress));
     }
     __syncthreads();
     if (tid >= 64u) return;
@@ -203,7 +190,7 @@ __global__ __launch_bounds__(SBS_BLOCK) void k_batch_summary(SbBatchView V, floa
 #pragma unroll
     for (uint32_t k = 0; k < SBS_NSUM; k++) tot[k] = sbs_tree_tail(s_sum[k], tid, k < 5u ? Wp : Wb);
     if (tid != 0u) return;
-    const float nan = __uint_as_float(SBS_QNAN);
+    const float nan = __uint_as_float(SBB_QNAN);
     const uint32_t np = s_stat[SBS_P_FIN], nb = s_stat[SBS_B_FIN];
     row[0] = (float)P;
     row[1] = (float)Bc;
@@ -213,32 +200,25 @@ __global__ __launch_bounds__(SBS_BLOCK) void k_batch_summary(SbBatchView V, floa
     row[5] = (float)s_stat[SBS_B_BAD];
 #pragma unroll
     for (int k = 0; k < 4; k++) row[6 + k] = np ? (float)(tot[k] / (double)np) : nan;
-    row[10] = np ? sbs_unkey(s_stat[SBS_MINX]) : nan;
-    row[11] = np ? sbs_unkey(s_stat[SBS_MINY]) : nan;
-    row[12] = np ? sbs_unkey(s_stat[SBS_MAXX]) : nan;
-    row[13] = np ? sbs_unkey(s_stat[SBS_MAXY]) : nan;
+    row[10] = np ? sbb_unkey(s_stat[SBS_MINX]) : nan;
+    row[11] = np ? sbb_unkey(s_stat[SBS_MINY]) : nan;
+    row[12] = np ? sbb_unkey(s_stat[SBS_MAXX]) : nan;
+    row[13] = np ? sbb_unkey(s_stat[SBS_MAXY]) : nan;
     row[14] = (float)tot[4]; // (round to nearest: +inf beyond the range of float)
     row[15] = np ? (float)__longlong_as_double((long long)s_max_v2) : nan;
-    row[16] = nb ? sbs_unkey(s_stat[SBS_MAX_STRAIN]) : nan;
-    row[17] = nb ? sbs_unkey(s_stat[SBS_MAX_STRESS]) : nan;
-    row[18] = nb ? sbs_unkey(s_stat[SBS_MIN_STRESS]) : nan;
+    row[16] = nb ? sbb_unkey(s_stat[SBS_MAX_STRAIN]) : nan;
+    row[17] = nb ? sbb_unkey(s_stat[SBS_MAX_STRESS]) : nan;
+    row[18] = nb ? sbb_unkey(s_stat[SBS_MIN_STRESS]) : nan;
     row[19] = nb ? (float)(tot[5] / (double)nb) : nan;
     row[20] = 1.0f;
     row[21] = row[22] = row[23] = 0.0f;
 }
 
 // ---------------------------------------------------------------- host
-static uint32_t sbs_pow2_at_least(uint32_t n)
-{
-    uint32_t w = 1u;
-    while (w < n) w <<= 1;
-    return w;
-}
-
 static sb_status launch_summary(sb_batch *b, float *rows)
 {
     const SbBatchView &V = b->V;
-    k_batch_summary<<<b->opt.n_scenes, SBS_BLOCK, 0, b->stream>>>(V, rows, sbs_pow2_at_least(V.maxP), sbs_pow2_at_least(V.maxB));
+    k_batch_summary<<<b->opt.n_scenes, SBS_BLOCK, 0, b->stream>>>(V, rows, sbb_pow2_at_least(V.maxP), sbb_pow2_at_least(V.maxB));
     return check_launch(b, "sb_batch_summary_device");
 }
 
@@ -246,26 +226,16 @@ bool sbb_summary_info(sb_batch *b, const char *key, uint64_t *value)
 {
     const std::string k(key);
     if (k == "summary_words") *value = SB_BATCH_SUMMARY_WORDS;
-    else if (k == "summary_kernel_vgprs" || k == "summary_kernel_scratch_bytes") {
-        if (b->summary_vgprs < 0) {
-            hipFuncAttributes fa{};
-            if (hipSetDevice(b->device) != hipSuccess || hipFuncGetAttributes(&fa, (const void *)k_batch_summary) != hipSuccess) {
-                (void)hipGetLastError();
-                *value = 0;
-                return true;
-            }
-            b->summary_vgprs = fa.numRegs;
-            b->summary_scratch = (int)fa.localSizeBytes;
-        }
-        *value = (uint64_t)std::max(k == "summary_kernel_vgprs" ? b->summary_vgprs : b->summary_scratch, 0);
-    } else return false;
+    else if (k == "summary_kernel_vgprs" || k == "summary_kernel_scratch_bytes")
+        *value = sbb_kernel_res(b, b->summary_res, (const void *)k_batch_summary, k == "summary_kernel_vgprs");
+    else return false;
     return true;
 }
 
 sb_status sb_batch_summary_device(sb_batch *b, void *device_out_f32)
 {
     if (!b) return SB_ERR_INVALID;
-    if (!device_out_f32 || ((uintptr_t)device_out_f32 & 3u)) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_summary_device: null or misaligned device buffer");
+    if (!device_out_f32 || sbb_misaligned4({device_out_f32})) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_summary_device: null or misaligned device buffer");
     SB_HIP(b, hipSetDevice(b->device));
     return launch_summary(b, (float *)device_out_f32);
 }
@@ -273,7 +243,7 @@ sb_status sb_batch_summary_device(sb_batch *b, void *device_out_f32)
 sb_status sb_batch_rollout_device(sb_batch *b, uint32_t n_frames, const void *device_inputs, void *device_summaries)
 {
     if (!b) return SB_ERR_INVALID;
-    if (((uintptr_t)device_inputs & 3u) || ((uintptr_t)device_summaries & 3u))
+    if (sbb_misaligned4({device_inputs, device_summaries}))
         SB_FAIL(b, SB_ERR_INVALID, "sb_batch_rollout_device: input and summary buffers must be 4-byte aligned");
     const size_t n = b->opt.n_scenes;
     for (uint32_t t = 0; t < n_frames; t++) { // the individual calls, in their order: nothing here that they do not do

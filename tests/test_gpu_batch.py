@@ -9,45 +9,9 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import batch_cases as bc  # noqa: E402
+from batch_harness import apply_to_batch, make_batch, upload_each  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-OFF, ALLPAIRS, GRID = 0, 1, 2
-
-
-def make_batch(sb, case, n=None, mode=None):
-    mode = case["mode"] if mode is None else mode
-    return sb.BatchEngine(n_scenes=n or len(case["bufs"]), layout=case["layout"], max_particles=case["cap"][0],
-                          max_beams=case["cap"][1], collision_mode=GRID if mode else OFF, subticks=case.get("subticks", 64))
-
-
-def upload_each(be, bufs):
-    for i, b in enumerate(bufs):
-        if b is not None:
-            be.write_scene(b, i, 1)
-
-
-def device_bytes(rows):
-    import torch
-    a = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), 32).copy()
-    return torch.from_numpy(a).cuda()
-
-
-def apply_to_batch(be, op):
-    if op[0] == "frame":
-        be.frame(op[1])
-    elif op[0] == "step":
-        be.step(op[1])
-    elif op[0] == "delete":
-        be.delete_pass()
-    elif op[0] == "consts":
-        be.set_physics_constants(op[2], first=op[1], count=1)
-    elif op[0] == "input":
-        be.write_user_input(op[1])
-    elif op[0] == "inputs":
-        be.write_user_input(device_bytes(op[1]))
-    else:
-        raise ValueError(op)
 
 
 def compare_all(be, case, refs, what=""):
@@ -378,3 +342,25 @@ def test_upload_validation_and_call_errors(sb):
     be.sync()
     assert be.info("n_scenes") == 3 and be.info("lds_bytes_per_scene") > 0 and be.info("scenes_per_cu") >= 1
     be.destroy()
+
+
+def test_kernel_resource_info_in_either_order(sb):
+    """*_kernel_vgprs / *_kernel_scratch_bytes of the five kernels that are asked on demand: one batch is asked for the registers
+    first, the other for the scratch bytes first, each key twice; every answer for a key is the same, the registers > 0, the
+    scratch bytes 0.  Nothing is launched."""
+    cap = (8, 8)
+    case = dict(name="two particles twice", layout=1, cap=cap, mode=bc.OFF, bufs=[bc.two_particles(sb, 1, cap)] * 2)
+    a, b = make_batch(sb, case), make_batch(sb, case)
+    for be in (a, b):
+        upload_each(be, case["bufs"])
+    for prefix in ("render", "summary", "bodies", "contacts", "body_summary"):
+        vgprs, scratch = prefix + "_kernel_vgprs", prefix + "_kernel_scratch_bytes"
+        got = {vgprs: [], scratch: []}
+        for be, keys in ((a, (vgprs, scratch)), (b, (scratch, vgprs))):
+            for key in keys + keys:
+                got[key].append(be.info(key))
+        assert len(got[vgprs]) == len(got[scratch]) == 4
+        assert len(set(got[vgprs])) == 1 and got[vgprs][0] > 0, (prefix, got)
+        assert got[scratch] == [0, 0, 0, 0], (prefix, got)
+    a.destroy()
+    b.destroy()

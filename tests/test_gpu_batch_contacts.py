@@ -11,10 +11,11 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import batch_cases as bc  # noqa: E402
+from batch_harness import apply_to_batch, load_all, make_batch, upload_each  # noqa: E402
 import batch_grid_cases as gc  # noqa: E402
 import batch_contacts_cases as cs  # noqa: E402
 import batch_contacts_ref as cr  # noqa: E402
-from test_gpu_batch_bodies import apply_to_batch, assert_scenes_equal, load_all, upload_each  # noqa: E402
+from test_gpu_batch_bodies import assert_scenes_equal  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -23,14 +24,6 @@ NAMES = ("touch", "pairs", "counts")
 SENTINEL = -7
 N_CASES = 20
 _expected = {}
-
-
-def make_batch(sb, case, mode=None, grid_min_particles=None, n=None):
-    radius, bounds = cs.geometry(case)
-    mode = (GRID if case["mode"] else OFF) if mode is None else mode
-    return sb.BatchEngine(n_scenes=n or len(case["bufs"]), bounds_size=bounds, particle_radius=radius, layout=case["layout"],
-                          max_particles=case["cap"][0], max_beams=case["cap"][1], collision_mode=mode, subticks=case.get("subticks", 64),
-                          grid_min_particles=grid_min_particles)
 
 
 def expected(oracle, case):

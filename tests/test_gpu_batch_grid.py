@@ -11,8 +11,8 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import batch_cases as bc  # noqa: E402
+from batch_harness import apply_to_batch, make_batch, upload_each  # noqa: E402
 import batch_grid_cases as gc  # noqa: E402
-from test_gpu_batch import apply_to_batch, upload_each  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -33,12 +33,6 @@ def reference(oracle, case):
     return _reference[case["name"]]
 
 
-def make_batch(sb, case, mode=GRID, grid_min_particles=1):
-    return sb.BatchEngine(n_scenes=len(case["bufs"]), bounds_size=case.get("bounds", 1000.0), particle_radius=case.get("radius", 10.0),
-                          layout=case["layout"], max_particles=case["cap"][0], max_beams=case["cap"][1],
-                          collision_mode=mode, subticks=case.get("subticks", 64), grid_min_particles=grid_min_particles)
-
-
 def compare(be, case, exp_per_scene, what):
     for i, (buf, exp) in enumerate(zip(case["bufs"], exp_per_scene)):
         if exp is None:
@@ -48,10 +42,10 @@ def compare(be, case, exp_per_scene, what):
         bc.assert_same(be.load_scene(i, buf.copy()), exp, "%s %s: scene %d" % (case["name"], what, i))
 
 
-def run(sb, oracle, case, **kw):
+def run(sb, oracle, case, mode=GRID, grid_min_particles=1):
     """The case's program on a batch, compared with the oracle after every op."""
     exp = reference(oracle, case)
-    be = make_batch(sb, case, **kw)
+    be = make_batch(sb, case, mode=mode, grid_min_particles=grid_min_particles)
     upload_each(be, case["bufs"])
     for k, op in enumerate(case["program"]):
         apply_to_batch(be, op)
@@ -156,7 +150,7 @@ def test_cells_follow_positions_changed_outside_the_kernel(sb, oracle):
     import torch
     case = bc.case_break(sb)
     bufs = case["bufs"]
-    be = make_batch(sb, case)
+    be = make_batch(sb, case, mode=GRID, grid_min_particles=1)
     upload_each(be, bufs)
     refs = [bc.make_oracle(oracle, case, b) for b in bufs]
 

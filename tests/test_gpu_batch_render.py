@@ -11,34 +11,13 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import batch_cases as bc  # noqa: E402
+from batch_harness import apply_to_batch, make_batch, upload_each  # noqa: E402
 from render_ref import render_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 OFF, ALLPAIRS, GRID = 0, 1, 2
 S0, R0 = 1000.0, 10.0
-
-
-def make_batch(sb, case, n=None):
-    return sb.BatchEngine(n_scenes=n or len(case["bufs"]), layout=case["layout"], max_particles=case["cap"][0],
-                          max_beams=case["cap"][1], collision_mode=GRID if case["mode"] else OFF, subticks=case.get("subticks", 64))
-
-
-def upload_each(be, bufs):
-    for i, b in enumerate(bufs):
-        if b is not None:
-            be.write_scene(b, i, 1)
-
-
-def apply_to_batch(be, op):
-    if op[0] == "frame":
-        be.frame(op[1])
-    elif op[0] == "step":
-        be.step(op[1])
-    elif op[0] == "consts":
-        be.set_physics_constants(op[2], first=op[1], count=1)
-    else:
-        raise ValueError(op)
 
 
 class Refs:

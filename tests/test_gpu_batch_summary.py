@@ -10,48 +10,11 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import batch_cases as bc  # noqa: E402
+from batch_harness import apply_to_batch, device_bytes, load_all, make_batch, upload_each  # noqa: E402
 import batch_summary_cases as sc  # noqa: E402
 import batch_summary_ref as sr  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-OFF, ALLPAIRS, GRID = 0, 1, 2
-
-
-def make_batch(sb, case, n=None):
-    return sb.BatchEngine(n_scenes=n or len(case["bufs"]), layout=case["layout"], max_particles=case["cap"][0],
-                          max_beams=case["cap"][1], collision_mode=GRID if case["mode"] else OFF, subticks=case.get("subticks", 64))
-
-
-def upload_each(be, bufs):
-    for i, b in enumerate(bufs):
-        if b is not None:
-            be.write_scene(b, i, 1)
-
-
-def device_bytes(rows):
-    import torch
-    a = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), 32).copy()
-    return torch.from_numpy(a).cuda()
-
-
-def apply_to_batch(be, op):
-    if op[0] == "frame":
-        be.frame(op[1])
-    elif op[0] == "step":
-        be.step(op[1])
-    elif op[0] == "consts":
-        be.set_physics_constants(op[2], first=op[1], count=1)
-    elif op[0] == "input":
-        be.write_user_input(op[1])
-    elif op[0] == "inputs":
-        be.write_user_input(device_bytes(op[1]))
-    else:
-        raise ValueError(op)
-
-
-def load_all(be, bufs):
-    return [None if b is None else be.load_scene(i, b.copy()) for i, b in enumerate(bufs)]
 
 
 def assert_scenes_equal(a, b, bufs, what):

@@ -18,55 +18,14 @@ import os
 import statistics
 import subprocess
 import sys
-import time
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from batch_timing_shapes import scene, timed  # noqa: E402
 
 SHAPES = {"default_4096": (4096, 128, 320, 1, "default"), "lattice_32x32_n256": (256, 1024, 4096, 2, "lattice"),
           "shuffled_path_1024_n256": (256, 1024, 4096, 2, "path")}
-
-
-def scene(sb, kind, layout, maxp, maxb):
-    if kind == "default":
-        return sb.scenes.default_buffers(layout, maxp, maxb)
-    buf = sb.Buffers(layout, maxp, maxb)
-    if kind == "lattice":
-        src = sb.scenes.lattice_buffers(32, 32, d=25.0, origin=(100.0, 100.0), spring=50.0, damp=700.0, yield_strain=0.2, strain_limit=0.5,
-                                        jitter=2.0, layout=layout)
-        P, B = src.particle_count, src.beam_count
-        buf.set_scene(src.particles[:P], src.beams[:B].copy())
-        buf.metadata[12:28] = src.metadata[12:28]
-        return buf
-    # the path: particle k at data index D[k] in slot S[k], beam k (k -- k + 1) at data index E[k] in slot T[k]
-    n, rng = maxp, np.random.default_rng(1)
-    D, S, E, T = rng.permutation(maxp)[:n], rng.permutation(n), rng.permutation(maxb)[:n - 1], rng.permutation(n - 1)
-    buf.particles[D, 0] = 20.0 + 30.0 * (D % 32)
-    buf.particles[D, 1] = 20.0 + 30.0 * (D // 32)
-    buf.mapping[S] = D
-    rec = buf.beams[E]
-    rec["a"], rec["b"] = D[:-1], D[1:]
-    for f, v in (("length", 30.0), ("target_length", 30.0), ("last_length", 30.0), ("spring", 50.0), ("damp", 700.0),
-                 ("yield_strain", 0.2), ("strain_break_limit", 0.5)):
-        rec[f] = v
-    buf.beams[E] = rec
-    buf.mapping[maxp + T] = E
-    buf.particle_count, buf.beam_count = n, n - 1
-    return buf
-
-
-def timed(sync, repeats, warmup, call):
-    ms = []
-    for k in range(warmup + repeats):
-        sync()
-        t = time.perf_counter()
-        call()
-        sync()
-        if k >= warmup:
-            ms.append((time.perf_counter() - t) * 1e3)
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "n": len(ms)}
 
 
 def worker(a):

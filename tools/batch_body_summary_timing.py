@@ -23,7 +23,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import batch_bodies_timing as bt  # noqa: E402  (the shapes, the scenes and the timing loop)
+import batch_bodies_timing as bt  # noqa: E402  (the shapes)
+from batch_timing_shapes import scene, timed  # noqa: E402
 
 CASES = ("label_and_score", "body_summary", "frame", "torch_route", "sync_only")
 ROWS = 8
@@ -49,7 +50,7 @@ def worker(a):
     dev = torch.device("cuda", 0)
     out = {}
     for name, (n, maxp, maxb, layout, kind) in bt.SHAPES.items():
-        buf = bt.scene(sb, kind, layout, maxp, maxb)
+        buf = scene(sb, kind, layout, maxp, maxb)
         be = sb.BatchEngine(n_scenes=n, layout=layout, max_particles=maxp, max_beams=maxb)
         be.write_scene(buf)
         if kind != "path":
@@ -65,17 +66,17 @@ def worker(a):
         def both():
             be.bodies(labels, counts=counts)
             be.body_summary(labels, rows=ROWS, out=rows)
-        r = {"sync_only": bt.timed(sync, a.repeats, a.warmup, lambda: None),
-             "label_and_score": bt.timed(sync, a.repeats, a.warmup, both),
-             "body_summary": bt.timed(sync, a.repeats, a.warmup, lambda: be.body_summary(labels, rows=ROWS, out=rows)),
-             "torch_route": bt.timed(sync, a.repeats, a.warmup, lambda: torch_route(be, torch))}
+        r = {"sync_only": timed(sync, a.repeats, a.warmup, lambda: None),
+             "label_and_score": timed(sync, a.repeats, a.warmup, both),
+             "body_summary": timed(sync, a.repeats, a.warmup, lambda: be.body_summary(labels, rows=ROWS, out=rows)),
+             "torch_route": timed(sync, a.repeats, a.warmup, lambda: torch_route(be, torch))}
         sync()
         again = rows.clone()
         both()
         sync()
         r["rows_repeat_bit_for_bit"] = bool(torch.equal(again.view(torch.int32), rows.view(torch.int32)))
         r["row_0_particles"] = rows[0, :, 0].tolist()
-        r["frame"] = bt.timed(sync, a.repeats, a.warmup, lambda: be.frame(1))    # (last: it moves the scenes on)
+        r["frame"] = timed(sync, a.repeats, a.warmup, lambda: be.frame(1))    # (last: it moves the scenes on)
         r["kernel"] = {x: be.info(x) for x in ("body_summary_kernel_vgprs", "body_summary_kernel_scratch_bytes", "body_summary_lds_bytes")}
         r["particles_beams"] = [buf.particle_count, buf.beam_count]
         out[name] = r

@@ -22,22 +22,12 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from batch_timing_shapes import scene  # noqa: E402
 
 SHAPES = {"default_4096": (4096, 128, 320, 1, "default"), "lattice_32x32_4096": (4096, 1024, 4096, 2, "lattice")}
 PAIRS = 256
 CHUNK = 256
-
-
-def scene(sb, kind, layout, maxp, maxb):
-    if kind == "default":
-        return sb.scenes.default_buffers(layout, maxp, maxb)
-    buf = sb.Buffers(layout, maxp, maxb)
-    src = sb.scenes.lattice_buffers(32, 32, d=25.0, origin=(100.0, 100.0), spring=50.0, damp=700.0, yield_strain=0.2, strain_limit=0.5,
-                                    jitter=2.0, layout=layout)
-    P, B = src.particle_count, src.beam_count
-    buf.set_scene(src.particles[:P], src.beams[:B].copy())
-    buf.metadata[12:28] = src.metadata[12:28]
-    return buf
 
 
 def main():

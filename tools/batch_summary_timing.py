@@ -20,10 +20,11 @@ import os
 import statistics
 import subprocess
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from batch_timing_shapes import scene, timed  # noqa: E402
 
 SHAPES = {"default_4096": (4096, 128, 320, 1, "default"), "lattice_32x32_n256": (256, 1024, 4096, 2, "lattice")}
 ROLLOUT_T = 16
@@ -35,18 +36,6 @@ def load_tree(tree):
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod.load_package()
-
-
-def scene(sb, kind, layout, maxp, maxb):
-    if kind == "default":
-        return sb.scenes.default_buffers(layout, maxp, maxb)
-    src = sb.scenes.lattice_buffers(32, 32, d=25.0, origin=(100.0, 100.0), spring=50.0, damp=700.0, yield_strain=0.2, strain_limit=0.5,
-                                    jitter=2.0, layout=layout)
-    P, B = src.particle_count, src.beam_count
-    buf = sb.Buffers(layout, maxp, maxb)
-    buf.set_scene(src.particles[:P], src.beams[:B].copy())
-    buf.metadata[12:28] = src.metadata[12:28]
-    return buf
 
 
 def parent_route(torch, be, p, b, alive, out):
@@ -77,18 +66,6 @@ def parent_route(torch, be, p, b, alive, out):
             torch.where(bsome, torch.where(bfin, stress, inf).amin(dim=1), nan),
             torch.where(bfin, strain, torch.zeros((), device=p.device)).sum(dim=1) / nb, zero, zero, zero, zero]
     torch.stack(cols, dim=1, out=out)
-
-
-def timed(sync, repeats, warmup, call):
-    ms = []
-    for k in range(warmup + repeats):
-        sync()
-        t = time.perf_counter()
-        call()
-        sync()
-        if k >= warmup:
-            ms.append((time.perf_counter() - t) * 1e3)
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "n": len(ms)}
 
 
 def worker(a):
