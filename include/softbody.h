@@ -208,7 +208,10 @@ sb_status sb_get_counts(sb_engine *e, uint32_t *particles, uint32_t *beams);
  * launch has to move with the data layout the engine holds: the launched kernel's own compulsory traffic),
  * "grid_cells", "grid_builds", "grid_wide", "grid_skin_x1000", "material_mode", "materials", "local_index_bits",
  * "render_table_build_us" (host time of sb_render's last draw-table build: the first render after an upload),
- * "halo_guard" (1 while a halo guard is set, sb_halo_guard). */
+ * "halo_guard" (1 while a halo guard is set, sb_halo_guard),
+ * "acc_dirty_tiles" / "plastic_tiles" (tiles whose zero-acceleration / never-yielded promise flag in the CURRENT state
+ * buffer is nonzero; 0 on engines without tiles, "plastic_tiles" 0 without a blocked plan.  Both wait for the stream and
+ * copy one word per tile to the host: for tests, never inside a timed region). */
 sb_status sb_get_info(sb_engine *e, const char *key, uint64_t *value);
 
 /* ---- multi-GPU halo exchange; one engine per rank/GPU, each holding its

@@ -1982,6 +1982,21 @@ sb_status sb_get_info(sb_engine *e, const char *key, uint64_t *value)
             *value = n;
         }
     }
+    else if (k == "acc_dirty_tiles" || k == "plastic_tiles") { // tiles whose promise flag in the CURRENT state buffer is nonzero (DESIGN.md 4.1;
+        *value = 0;                                            // read-only, waits for the stream: for tests, not for timing)
+        const SbBlockedDev &bk = e->bk.K ? e->bk : e->hy; // (the hybrid's plan: what its last run of blocked launches left)
+        const bool acc = k == "acc_dirty_tiles";
+        const uint32_t *d = acc ? e->d_acc_flag[e->cur] : (bk.K ? bk.d_plastic[bk.cur] : nullptr);
+        const size_t T = acc ? e->ntiles : (bk.K ? bk.ntiles : 0u);
+        if (T && d) {
+            std::vector<uint32_t> h(T);
+            SB_HIP(e, hipStreamSynchronize(e->stream));
+            SB_HIP(e, hipMemcpy(h.data(), d, T * 4, hipMemcpyDeviceToHost));
+            uint64_t n = 0;
+            for (uint32_t w : h) n += w != 0u;
+            *value = n;
+        }
+    }
     else if (k.rfind("grid_stamp_", 0) == 0) { // -DSB_STAMPS builds: stamps of one mid-grid workgroup of the last substep launch, 10 ns ticks since its start (diagnostic)
         const int i = atoi(key + 11);
         SB_HIP(e, hipStreamSynchronize(e->stream));

@@ -41,8 +41,10 @@ struct SbBlockedState {
     // "plastic" flags, per tile and per state buffer (like the acceleration flags): 0 = every beam the tile owns still has
     // target_length == length, bit for bit (compute.wgsl:113-116 has never fired for them), in BOTH state buffers -- such a
     // tile neither reads nor writes its targets, and tiles around it do not gather them: 33 of a launch's 147 MB on a
-    // scene that has not yielded (BASELINE config 2).  Set for good when a beam of the tile yields (that launch stores the
-    // tile's targets, every later one reads and stores them), by an upload that holds yielded beams, by a ghost refresh.
+    // scene that has not yielded (BASELINE config 2).  Set when a beam of the tile yields (that launch stores the
+    // tile's targets, every later one reads and stores them), by an upload that holds yielded beams, by a ghost refresh; a
+    // delete pass recomputes it over the beams it leaves (k_plastic_recount), so a tile that loses its only yielded beams is
+    // an unyielded tile again.
     const uint32_t *plastic_r;
     uint32_t *plastic_w;
 };
@@ -728,6 +730,30 @@ __global__ __launch_bounds__(256) void k_delete_blocked(uint32_t *ent_word, cons
     }
 }
 
+// behind k_delete_blocked: the plastic flag of every tile that has one set, as of NOW (the test of k_hybrid_to_blocked, over the
+// beams the pass has left).  0 again = every own beam that is still alive has target == rest length, bit for bit, in BOTH state
+// buffers: the launches that follow neither read nor store those targets, so the buffer they write into must hold them already.
+// A removed beam keeps the state it died with; its owner carries that from buffer to buffer whatever the flag says.
+__global__ __launch_bounds__(256) void k_plastic_recount(const uint32_t *__restrict__ tile_b0, const uint32_t *__restrict__ tile_e0,
+                                                         const uint32_t *__restrict__ ent_word, const float *__restrict__ ent_length,
+                                                         const float *__restrict__ mat_tab, const float *__restrict__ target_a,
+                                                         const float *__restrict__ target_b, uint32_t *plastic_a, uint32_t *plastic_b,
+                                                         uint32_t dummy_word)
+{
+    const uint32_t tile = blockIdx.x;
+    if ((plastic_a[tile] | plastic_b[tile]) == 0u) return; // (uniform; nearly every tile of nearly every pass)
+    const uint32_t b0 = tile_b0[tile], nb = tile_b0[tile + 1] - b0, e0 = tile_e0[tile];
+    bool differs = false;
+    for (uint32_t j = threadIdx.x; j < nb; j += 256u) {
+        const uint32_t wd = ent_word[e0 + j];
+        if (wd == dummy_word) continue;
+        const uint32_t rest = __float_as_uint(ent_length ? ent_length[e0 + j] : mat_tab[6u * (wd >> (2u * SB_BK_LBITS))]);
+        differs |= __float_as_uint(target_a[b0 + j]) != rest || __float_as_uint(target_b[b0 + j]) != rest;
+    }
+    const int any = __syncthreads_or(differs ? 1 : 0);
+    if (threadIdx.x == 0u && !any) plastic_a[tile] = plastic_b[tile] = 0u;
+}
+
 static inline uint32_t cdiv_b(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
 // How a call of n substeps is cut into launches of at most kmax substeps each.  A launch pays a fixed part (its load and
@@ -917,4 +943,8 @@ void sbk_launch_delete_blocked(sb_engine *e)
     k_delete_blocked<<<cdiv_b(nwords, 256), 256, 0, e->stream>>>(e->bk.d_ent_word, e->beams.slot, e->bk.d_slot_e0, e->bk.d_slot_ent,
                                                                  nwords, e->nbeam, e->d_broken, e->d_dead_gen, ++e->delete_gen,
                                                                  e->bk.dummy_word);
+    const SbBlockedDev &bk = e->bk; // a tile whose only yielded beams the pass removed is an unyielded tile again
+    if (bk.ntiles)
+        k_plastic_recount<<<bk.ntiles, 256, 0, e->stream>>>(bk.d_tile_b0, bk.d_tile_e0, bk.d_ent_word, bk.mat_mode == 1 ? bk.d_ent_length : nullptr,
+                                                            bk.d_mat, bk.d_target[0], bk.d_target[1], bk.d_plastic[0], bk.d_plastic[1], bk.dummy_word);
 }
