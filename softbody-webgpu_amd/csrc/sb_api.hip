@@ -10,6 +10,8 @@
 #include <cstdlib>
 #include <cmath>
 #include <cstring>
+#include <memory>
+#include <mutex>
 #include <new>
 #include <numeric>
 #include <stdexcept>
@@ -124,14 +126,32 @@ struct SbStageTimer {
     }
 };
 
-// The plan of an upload lives in a few hundred megabytes of host arrays; handing them back to the kernel (munmap) took 40 ms of
-// a 140 ms upload.  They are moved here and destroyed on a side thread, which the next upload or sb_destroy joins.
-struct SbUploadTrash {
-    std::vector<float> px, py;
+// finite bounding box of a set of positions (the spatial hash's frame is made from it, and kept while a scene stays inside)
+struct SbBox {
+    float minx = INFINITY, maxx = -INFINITY, miny = INFINITY, maxy = -INFINITY;
+    void add(const SbBox &o) { minx = std::min(minx, o.minx), maxx = std::max(maxx, o.maxx), miny = std::min(miny, o.miny), maxy = std::max(maxy, o.maxy); }
+};
+struct SbParticleSoA { std::vector<float2> pos, vel, acc; }; // internal order, as the device keeps them
+
+// What an upload that plans works on, phase by phase (sb_write_buffers_impl).  The plan lives in a few hundred megabytes of host
+// arrays; handing them back to the kernel (munmap) took 40 ms of a 140 ms upload, so the whole struct is destroyed on a side
+// thread, which the next upload or sb_destroy joins.
+struct SbUpload {
+    const uint8_t *md = nullptr, *mp = nullptr, *pd = nullptr, *bd = nullptr; // the caller's four buffers
+    uint32_t P = 0, B = 0;
+    SbStageTimer tm;
+    std::vector<uint32_t> slot_index, internal_of_index; // slot -> data index; data index -> slot
+    SbHostBeams hb;                // validated beam records per slot (behind the final swap: the previous scene's)
+    std::vector<float> px, py;     // positions per slot
     SbTiling tl;
     SbBlocking bl;
-    SbHostBeams hb;
-    std::vector<uint32_t> v[8];
+    uint32_t blockK = 0;           // > 0: the temporally blocked plan is in use (sb_blocking.h)
+    uint32_t plan_target = 0, tile_target = 0; // tile size the plan's bisection was made for, and the single-substep tiling's
+    std::vector<uint32_t> order, internal_of_slot; // internal -> slot and back
+    SbParticleSoA soa;
+    SbBox box;                     // of the uploaded positions
+    std::vector<uint32_t> c_ia, c_ib, c_pair, c_slot; // per beam copy of the tiled / atomic layout
+    std::vector<float> mat_table;
 };
 static void reap_join(sb_engine *e)
 {
@@ -357,26 +377,30 @@ static sb_status dev_upload(sb_engine *e, T **p, const std::vector<T, A> &v)
     return SB_OK;
 }
 
+// One field of the beam records, one float per copy (tiled / atomic layout) or per beam in owner order (blocked plan), gathered
+// straight into the pinned staging chunks: dst[c] = hb[slot_of_copy[c]].f[field], 0 for a padding copy (slot 0xFFFFFFFF).
+static sb_status put_beam_field(sb_engine *e, float *dst, const SbHostBeams &hb, int field, const uint32_t *slot_of_copy, size_t count)
+{
+    return stage_put(e, dst, count * 4, [&](size_t off, size_t len, uint8_t *out) {
+        float *o = (float *)out;
+        const uint32_t *slot = slot_of_copy + off / 4;
+        sbt::parallel_ranges(len / 4, 1 << 16, [&](size_t i0, size_t i1) {
+            for (size_t i = i0; i < i1; i++) o[i] = slot[i] == 0xFFFFFFFFu ? 0.0f : hb[slot[i]].f[field];
+        });
+    });
+}
+static const int SB_BEAM_STATE_FIELD[4] = {1, 2, 7, 8}; // what a run changes of a beam record: target, last, strain, stress
+
 // Beam state of a blocked plan (the engine's, or the one beside a tiled layout), one entry per beam in owner order, from the
 // records of an upload: buffer 0 = uploaded, buffer 1 = the same targets (a tile that never yields never stores its targets:
 // both buffers must hold them) and zeroed lengths; the plastic flags -- a tile starts unyielded when every beam it owns is
-// uploaded with target_length == length, bit for bit.  Gathered straight into the pinned staging chunks.
+// uploaded with target_length == length, bit for bit.
 static sb_status blocked_state_to_device(sb_engine *e, SbBlockedDev &k, const SbHostBeams &hb)
 {
     const uint32_t B = k.nbeams, T = k.ntiles;
     float *dst[4] = {k.d_target[0], k.d_last[0], k.d_strain, k.d_stress};
-    const int field[4] = {1, 2, 7, 8};
     const uint32_t *slot_of = k.h_beam_slot.data();
-    for (int a = 0; a < 4 && B; a++) {
-        const int fld = field[a];
-        SB_TRY(stage_put(e, dst[a], (size_t)B * 4, [&](size_t off, size_t len, uint8_t *out) {
-            float *o = (float *)out;
-            const size_t g_first = off / 4, n = len / 4;
-            sbt::parallel_ranges(n, 1 << 16, [&](size_t i0, size_t i1) {
-                for (size_t i = i0; i < i1; i++) o[i] = hb[slot_of[g_first + i]].f[fld];
-            });
-        }));
-    }
+    for (int a = 0; a < 4; a++) SB_TRY(put_beam_field(e, dst[a], hb, SB_BEAM_STATE_FIELD[a], slot_of, B));
     if (B) SB_HIP(e, hipMemcpyAsync(k.d_target[1], k.d_target[0], (size_t)B * 4, hipMemcpyDeviceToDevice, e->stream));
     SB_HIP(e, hipMemsetAsync(k.d_last[1], 0, std::max<size_t>(B, 1) * 4, e->stream));
     std::vector<uint32_t> pl(std::max<uint32_t>(T, 1), 0u);
@@ -524,9 +548,6 @@ static sb_status upload_blocked(sb_engine *e, const SbBlocking &bl, const SbHost
         SB_HIP(e, hipMemsetAsync(k.d_hslots, 0, 3 * 65 * 16, e->stream));
         SB_HIP(e, hipMemsetAsync(k.d_q, 0, 2 * sizeof(SbHybridCtl), e->stream));
         k.qpar = k.seq = k.run_launches = k.k_prev = 0;
-        k.synced_delete_gen = 0;
-        k.slow_chunk = 0;
-        k.slow_left = 0;
         return SB_OK;
     }
     k.d_broken = nullptr; // (set by the caller once the engine's mask exists)
@@ -534,12 +555,33 @@ static sb_status upload_blocked(sb_engine *e, const SbBlocking &bl, const SbHost
     e->beams.stress = k.d_stress;
     e->beams.target = k.d_target[0];
     e->beams.last = k.d_last[0];
-    // buffer A holds whatever accelerations were uploaded; buffer B is all zeros (engineWorker.ts:593)
-    SB_TRY(dev_alloc(e, &e->d_acc_flag[0], T));
+    SB_TRY(dev_alloc(e, &e->d_acc_flag[0], T)); // (their contents: reset_run_state)
     SB_TRY(dev_alloc(e, &e->d_acc_flag[1], T));
-    SB_HIP(e, hipMemset(e->d_acc_flag[0], 0x01, std::max<size_t>(T, 1) * 4));
-    SB_HIP(e, hipMemset(e->d_acc_flag[1], 0x00, std::max<size_t>(T, 1) * 4));
     return SB_OK;
+}
+
+// The deepest launch a blocked plan made `asked` substeps deep can serve: every tile's region at that depth has to fit the
+// kernel's slots, by class (own and halo items sit in slots of their own, sb_blocked.hip) and its 12-bit local indices.  A
+// launch of k substeps loads the depth-k prefix of the plan only, so a plan that does not fit at full depth is kept and the
+// launches stay shallower: the deepest d in [min_depth, asked) that fits; 0 = none.
+static uint32_t blocked_fit_depth(const SbBlocking &bl, uint32_t asked, uint32_t min_depth)
+{
+    auto fits = [&](uint32_t d) {
+        return bl.max_own <= SB_BK_OWNP * SB_BK_T && bl.halo_at[d] <= SB_BK_HALOP * SB_BK_T && bl.max_ownb <= SB_BK_OWNB * SB_BK_T &&
+               bl.halo_entries_at[d] <= SB_BK_HALOB * SB_BK_T && bl.region_at[d] <= (1u << SB_BK_LBITS) - 2u;
+    };
+    if (fits(asked)) return asked;
+    for (uint32_t d = asked; d-- > min_depth;)
+        if (fits(d)) return d;
+    return 0;
+}
+
+// compute units of the engine's device (the tile sizes are fitted to whole rounds of its workgroup slots)
+static uint64_t cu_count(const sb_engine *e)
+{
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device);
+    return (uint64_t)std::max(cus, 1);
 }
 
 extern "C" {
@@ -656,20 +698,82 @@ static inline uint32_t sb_grid_executed0()
 
 } // extern "C"
 
-// The spatial hash forgets every particle position it holds: no build yet, same frame (an upload that keeps the plan; a particle
-// import, sb_state_io.hip).  Enqueued on the engine's stream; the first substep after it starts with a forced helper launch.
+// The spatial hash forgets every particle position it holds: no build yet, same frame (every upload, through reset_run_state; a
+// particle import, sb_state_io.hip).  The one writer of the hash's initial contents and of the host's counters: the upload that
+// plans only allocates the arrays and fills grid_ctl0 (upload_hash).  Enqueued on the engine's stream; the first substep after
+// it starts with a forced helper launch.
 sb_status sb_grid_reset_hash(sb_engine *e)
 {
     if (!(e->opt.collision_mode == SB_COLLIDE_GRID && e->d_grid_ctl)) return SB_OK;
-    for (int k = 0; k < 2; k++) SB_HIP(e, hipMemsetAsync(e->d_head[k], 0, e->grid_heads * 8, e->stream));
+    for (int k = 0; k < 2; k++) SB_HIP(e, hipMemsetAsync(e->d_head[k], 0, e->grid_heads * 8, e->stream)); // build number 0: "never written" (the first build is number 1)
     SB_HIP(e, hipMemsetAsync(e->d_blk_max, 0, e->grid_slots * 4, e->stream));
     SB_HIP(e, hipMemsetAsync(e->d_grid_outside, 0, 16, e->stream));
     SB_HIP(e, hipMemsetAsync(e->d_nl_count, 0, std::max<size_t>(e->P, 1) * 4, e->stream));
     SB_HIP(e, hipMemcpyAsync(e->d_grid_ctl, e->grid_ctl0, sizeof e->grid_ctl0, hipMemcpyHostToDevice, e->stream));
     e->grid_par = 0;
-    e->grid_force = true;
+    e->grid_force = true; // no hash yet: the first substep starts with a forced helper launch
     e->grid_classic_left = e->grid_classic_chunk = e->grid_calm = 0;
     e->grid_executed = sb_grid_executed0();
+    return SB_OK;
+}
+
+// "Just uploaded" (DESIGN.md 4.2): everything a RUN mutates besides the particle and beam state itself goes back to what a
+// fresh upload starts from.  The one writer of it: the upload that plans calls it once behind its allocations, the upload that
+// keeps the plan calls it in place of planning; a new per-run flag, mask or counter is reset HERE.  Enqueued on the engine's
+// stream (a blocking stream: ordered with the null-stream copies of the upload); the caller synchronises.
+static sb_status reset_run_state(sb_engine *e)
+{
+    const size_t T = std::max<size_t>(e->ntiles, 1), P = std::max<size_t>(e->P, 1), B = std::max<size_t>(e->B, 1);
+    if (e->d_acc_flag[0]) { // buffer A holds whatever accelerations were uploaded; buffer B is all zeros (engineWorker.ts:593)
+        SB_HIP(e, hipMemsetAsync(e->d_acc_flag[0], 0x01, T * 4, e->stream));
+        SB_HIP(e, hipMemsetAsync(e->d_acc_flag[1], 0x00, T * 4, e->stream));
+    }
+    // accumulators and masks, zeroed (engineWorker.ts:591-592)
+    if (e->d_forces) SB_HIP(e, hipMemsetAsync(e->d_forces, 0, P * sizeof(int2), e->stream));
+    SB_HIP(e, hipMemsetAsync(e->d_broken, 0, std::max<size_t>((e->nbeam + 31) / 32, 1) * 4, e->stream));
+    SB_HIP(e, hipMemsetAsync(e->d_dead_gen, 0, B * 4, e->stream));
+    e->cur = e->delete_gen = 0;
+    e->substeps_done = 0;
+    if (e->dev_err) *e->dev_err = 0;
+    e->hy.synced_delete_gen = 0;
+    e->hy.slow_chunk = e->hy.slow_left = 0; // (also while its plan is still on the side thread: that one only depends on the topology)
+    for (int b = 0; b < 2 && e->hy.K; b++) // (what its last run left; every run recomputes them from the state it borrows, info "plastic_tiles" reads them)
+        SB_HIP(e, hipMemsetAsync(e->hy.d_plastic[b], 0, std::max<size_t>(e->hy.ntiles, 1) * 4, e->stream));
+    return sb_grid_reset_hash(e);
+}
+
+// particles of the caller's buffer in internal order, as the three device arrays; the finite bounding box of their positions
+static SbBox deinterleave_particles(const uint8_t *pd, const std::vector<uint32_t> &pidx, SbParticleSoA &out)
+{
+    const size_t P = pidx.size();
+    out.pos.resize(P), out.vel.resize(P), out.acc.resize(P);
+    SbBox all;
+    std::mutex merge;
+    sbt::parallel_ranges(P, 1 << 16, [&](size_t i0, size_t i1) {
+        SbBox bx;
+        for (size_t i = i0; i < i1; i++) {
+            float q[6];
+            memcpy(q, pd + (size_t)pidx[i] * SB_PARTICLE_STRIDE, SB_PARTICLE_STRIDE);
+            out.pos[i] = make_float2(q[0], q[1]);
+            out.vel[i] = make_float2(q[2], q[3]);
+            out.acc[i] = make_float2(q[4], q[5]);
+            if (std::isfinite(q[0]) && std::isfinite(q[1])) bx.add(SbBox{q[0], q[0], q[1], q[1]});
+        }
+        std::lock_guard<std::mutex> lock(merge);
+        all.add(bx);
+    });
+    return all;
+}
+// A = data, B = zero (engineWorker.ts:588,593)
+static sb_status particles_to_device(sb_engine *e, const SbParticleSoA &h)
+{
+    const size_t P = h.pos.size();
+    SB_TRY(stage_put_bytes(e, e->part[0].pos, h.pos.data(), P * sizeof(float2)));
+    SB_TRY(stage_put_bytes(e, e->part[0].vel, h.vel.data(), P * sizeof(float2)));
+    SB_TRY(stage_put_bytes(e, e->part[0].acc, h.acc.data(), P * sizeof(float2)));
+    SB_HIP(e, hipMemsetAsync(e->part[1].pos, 0, std::max<size_t>(P, 1) * sizeof(float2), e->stream));
+    SB_HIP(e, hipMemsetAsync(e->part[1].vel, 0, std::max<size_t>(P, 1) * sizeof(float2), e->stream));
+    SB_HIP(e, hipMemsetAsync(e->part[1].acc, 0, std::max<size_t>(P, 1) * sizeof(float2), e->stream));
     return SB_OK;
 }
 
@@ -754,53 +858,20 @@ static sb_status rewrite_scene_state(sb_engine *e, const uint8_t *md, const uint
         for (uint32_t u = 0; u < B; u++) user_slot[u] = sb_user_slot(e, old_of_new[u]);
     }
     tm.mark("same topology: mapping + beam records");
-    std::vector<float2> hp(P), hv(P), ha(P);
-    {
-        struct Box { float minx = INFINITY, maxx = -INFINITY, miny = INFINITY, maxy = -INFINITY; };
-        std::vector<Box> boxes(256);
-        std::atomic<uint32_t> nbox{0};
-        sbt::parallel_ranges(P, 1 << 16, [&](size_t i0, size_t i1) {
-            Box bx;
-            for (size_t i = i0; i < i1; i++) {
-                float q[6];
-                memcpy(q, pd + (size_t)e->h_pidx[i] * SB_PARTICLE_STRIDE, SB_PARTICLE_STRIDE);
-                hp[i] = make_float2(q[0], q[1]);
-                hv[i] = make_float2(q[2], q[3]);
-                ha[i] = make_float2(q[4], q[5]);
-                if (std::isfinite(q[0]) && std::isfinite(q[1])) {
-                    bx.minx = std::min(bx.minx, q[0]); bx.maxx = std::max(bx.maxx, q[0]);
-                    bx.miny = std::min(bx.miny, q[1]); bx.maxy = std::max(bx.maxy, q[1]);
-                }
-            }
-            boxes[nbox.fetch_add(1) % boxes.size()] = bx; // (P / 65536 ranges: fewer than 256 up to 16 M particles; beyond, a box may be lost
-        });                                              //  -- which only ever keeps a frame that a fresh upload would have moved)
-        if (e->opt.collision_mode == SB_COLLIDE_GRID && e->d_grid_ctl) {
-            Box all;
-            for (const Box &b : boxes) {
-                all.minx = std::min(all.minx, b.minx); all.maxx = std::max(all.maxx, b.maxx);
-                all.miny = std::min(all.miny, b.miny); all.maxy = std::max(all.maxy, b.maxy);
-            }
-            // the hash keeps its frame: fine while the scene is still inside it (outside, particles are clamped into edge
-            // cells -- correct, but slow: plan again)
-            if (all.minx <= all.maxx && !(all.minx >= e->grid.x0 && all.maxx <= e->grid.x0 + e->grid.width && all.miny >= e->grid.y0 &&
-                                          all.maxy <= e->grid.y0 + e->grid.height))
-                return SB_OK;
-        }
-    }
+    SbParticleSoA soa;
+    const SbBox box = deinterleave_particles(pd, e->h_pidx, soa);
+    // the hash keeps its frame: fine while the scene is still inside it (outside, particles are clamped into edge cells --
+    // correct, but slow: plan again)
+    if (e->opt.collision_mode == SB_COLLIDE_GRID && e->d_grid_ctl && box.minx <= box.maxx &&
+        !(box.minx >= e->grid.x0 && box.maxx <= e->grid.x0 + e->grid.width && box.miny >= e->grid.y0 && box.maxy <= e->grid.y0 + e->grid.height))
+        return SB_OK;
     // ---- from here on the scene on the device is rewritten
     e->h_metadata.assign(md, md + SB_METADATA_BYTES);
     if (B != Bu) e->h_mapping.assign(mp, mp + map_bytes);
-    e->cur = 0;
-    e->substeps_done = 0;
-    if (e->dev_err) *e->dev_err = 0;
-    SB_TRY(stage_put_bytes(e, e->part[0].pos, hp.data(), P * sizeof(float2)));
-    SB_TRY(stage_put_bytes(e, e->part[0].vel, hv.data(), P * sizeof(float2)));
-    SB_TRY(stage_put_bytes(e, e->part[0].acc, ha.data(), P * sizeof(float2)));
-    SB_HIP(e, hipMemsetAsync(e->part[1].pos, 0, std::max<size_t>(P, 1) * sizeof(float2), e->stream));
-    SB_HIP(e, hipMemsetAsync(e->part[1].vel, 0, std::max<size_t>(P, 1) * sizeof(float2), e->stream));
-    SB_HIP(e, hipMemsetAsync(e->part[1].acc, 0, std::max<size_t>(P, 1) * sizeof(float2), e->stream));
+    SB_TRY(particles_to_device(e, soa));
     tm.mark("particles to device");
     const uint32_t nc = e->nbeam;
+    // beam state, and what delete passes since the last upload wrote into the plan taken back
     if (e->bk.K) {
         SB_TRY(blocked_state_to_device(e, e->bk, e->h_beams));
         e->beams.target = e->bk.d_target[0];
@@ -809,41 +880,15 @@ static sb_status rewrite_scene_state(sb_engine *e, const uint8_t *md, const uint
             SB_HIP(e, hipMemcpyAsync(e->bk.d_ent_word, e->bk.d_ent_word0, (size_t)e->bk.entries * 4, hipMemcpyDeviceToDevice, e->stream));
     } else {
         float *dst[4] = {e->beams.target, e->beams.last, e->beams.strain, e->beams.stress};
-        const int field[4] = {1, 2, 7, 8};
-        const uint32_t *slot_of = e->h_slot_of_copy.data();
-        for (int a = 0; a < 4 && nc; a++) {
-            const int fld = field[a];
-            SB_TRY(stage_put(e, dst[a], (size_t)nc * 4, [&](size_t off, size_t len, uint8_t *out) {
-                float *o = (float *)out;
-                const size_t c_first = off / 4, n = len / 4;
-                sbt::parallel_ranges(n, 1 << 16, [&](size_t i0, size_t i1) {
-                    for (size_t i = i0; i < i1; i++) {
-                        const uint32_t sl = slot_of[c_first + i];
-                        o[i] = sl == 0xFFFFFFFFu ? 0.0f : e->h_beams[sl].f[fld];
-                    }
-                });
-            }));
-        }
+        for (int a = 0; a < 4; a++) SB_TRY(put_beam_field(e, dst[a], e->h_beams, SB_BEAM_STATE_FIELD[a], e->h_slot_of_copy.data(), nc));
         if (e->delete_gen && e->live_words)
             SB_HIP(e, hipMemcpyAsync(e->path == SB_PATH_TILED ? e->beams.pair : e->beams.ia, e->d_live0, e->live_words * 4,
                                      hipMemcpyDeviceToDevice, e->stream));
     }
-    if (e->hy.K) {
-        SbBlockedDev &h = e->hy; // (its beam state is borrowed from the tiled layout at the start of every run)
-        if (h.synced_delete_gen && h.entries)
-            SB_HIP(e, hipMemcpyAsync(h.d_ent_word, h.d_ent_word0, (size_t)h.entries * 4, hipMemcpyDeviceToDevice, e->stream));
-        h.synced_delete_gen = 0;
-    }
-    e->hy.slow_chunk = e->hy.slow_left = 0; // (also while its plan is still on the side thread: that one only depends on the topology)
+    if (e->hy.K && e->hy.synced_delete_gen && e->hy.entries) // (its beam state is borrowed from the tiled layout at the start of every run)
+        SB_HIP(e, hipMemcpyAsync(e->hy.d_ent_word, e->hy.d_ent_word0, (size_t)e->hy.entries * 4, hipMemcpyDeviceToDevice, e->stream));
     tm.mark("beam state to device");
-    if (e->d_acc_flag[0]) { // buffer A holds whatever accelerations were uploaded; buffer B is all zeros (engineWorker.ts:593)
-        SB_HIP(e, hipMemsetAsync(e->d_acc_flag[0], 0x01, std::max<size_t>(e->ntiles, 1) * 4, e->stream));
-        SB_HIP(e, hipMemsetAsync(e->d_acc_flag[1], 0x00, std::max<size_t>(e->ntiles, 1) * 4, e->stream));
-    }
-    if (e->d_forces) SB_HIP(e, hipMemsetAsync(e->d_forces, 0, std::max<size_t>(P, 1) * sizeof(int2), e->stream));
-    SB_HIP(e, hipMemsetAsync(e->d_broken, 0, std::max<size_t>((nc + 31) / 32, 1) * 4, e->stream));
-    SB_HIP(e, hipMemsetAsync(e->d_dead_gen, 0, std::max<size_t>(e->B, 1) * 4, e->stream));
-    e->delete_gen = 0;
+    SB_TRY(reset_run_state(e));
     // The engine's beams that are not part of the scene any more (removed by this upload or by one before it) die like beams a
     // delete pass removes -- every copy / entry of them, in a pass of its own that is the upload's: generation 1; the passes of
     // the frames that follow count from 2, and none of the caller's slots ever carries 1.
@@ -870,7 +915,6 @@ static sb_status rewrite_scene_state(sb_engine *e, const uint8_t *md, const uint
         e->uploads_edited += B != Bu ? 1u : 0u;
     }
     e->h_user_slot.swap(user_slot);
-    SB_TRY(sb_grid_reset_hash(e));
     memcpy(&e->consts, md + 48, sizeof(SbConsts));
     SB_HIP(e, hipStreamSynchronize(e->stream));
     e->uploads_kept++;
@@ -879,86 +923,50 @@ static sb_status rewrite_scene_state(sb_engine *e, const uint8_t *md, const uint
     return SB_OK;
 }
 
-static sb_status sb_write_buffers_impl(sb_engine *e, const void *metadata, size_t metadata_bytes, const void *mapping,
-                           size_t mapping_bytes, const void *particles, size_t particles_bytes,
-                           const void *beams, size_t beams_bytes)
+// ---- the phases of an upload that plans (sb_write_buffers_impl), over one SbUpload
+
+// host shadows (copy semantics); validate (sb_scene_codec.h) and take the beam records over in the same walk: a few host threads
+// over the beam slots; positions per slot
+static sb_status upload_validate(sb_engine *e, SbUpload &u)
 {
-    if (!e) return SB_ERR_INVALID;
     const uint32_t maxP = e->opt.max_particles, maxB = e->opt.max_beams, layout = e->opt.layout;
-    const sbc::SizeError sz = sbc::check_sizes(layout, maxP, maxB, true, metadata, metadata_bytes, mapping, mapping_bytes, particles, particles_bytes,
-                                               beams, beams_bytes);
-    if (sz.buffer == sbc::BUF_NULL) SB_FAIL(e, SB_ERR_INVALID, "sb_write_buffers: null buffer");
-    if (sz.buffer) SB_FAIL(e, SB_ERR_INVALID, "%s buffer is %zu bytes, need %zu", sbc::buffer_name(sz.buffer), sz.have, sz.need);
-    const uint8_t *md = (const uint8_t *)metadata, *mp = (const uint8_t *)mapping;
-    const uint8_t *pd = (const uint8_t *)particles, *bd = (const uint8_t *)beams;
-    const sbc::Header hd(md);
-    const uint32_t P = hd.P, B = hd.B;
-    if (!hd.capacity_is(maxP, maxB))
-        SB_FAIL(e, SB_ERR_INVALID, "metadata max_particles/max_beams (%u/%u) differ from the engine capacity (%u/%u)", hd.maxP, hd.maxB, maxP, maxB);
-    if (!hd.counts_fit(maxP, maxB)) SB_FAIL(e, SB_ERR_INVALID, "metadata counts (%u/%u) exceed capacity (%u/%u)", P, B, maxP, maxB);
-
-    SB_HIP(e, hipSetDevice(e->device));
-    SB_HIP(e, hipStreamSynchronize(e->stream));
-    reap_join(e);
-    {
-        bool kept = false;
-        const sb_status st = rewrite_scene_state(e, md, mp, pd, bd, &kept);
-        if (st != SB_OK) { // (past its point of no return the device holds half of each scene: nothing may step or read it)
-            e->loaded = false;
-            return st;
-        }
-        if (kept) return SB_OK;
-    }
-    free_scene(e);
-
-    SbStageTimer tm;
-    // ---- host shadows (copy semantics)
-    e->h_metadata.assign(md, md + SB_METADATA_BYTES);
-    e->h_mapping.assign(mp, mp + sbc::mapping_bytes(layout, maxP, maxB));
-    e->P = P;
-    e->B = B;
+    e->h_metadata.assign(u.md, u.md + SB_METADATA_BYTES);
+    e->h_mapping.assign(u.mp, u.mp + sbc::mapping_bytes(layout, maxP, maxB));
+    e->P = u.P, e->B = u.B;
     e->h_user_slot.clear();
-    e->cur = 0;
-    e->substeps_done = 0;
-
-    tm.mark("sync + free + shadows");
-    // ---- validate (sb_scene_codec.h) and take the beam records over in the same walk: a few host threads over the beam slots
-    std::vector<uint32_t> slot_index, internal_of_index; // slot -> data index; data index -> slot (provisional: re-indexed below)
-    SbHostBeams hb(B);
-    {
-        const sbc::Scene sc{layout, maxP, maxB, P, B, mp, bd};
-        const sbc::SceneError bad = sbc::validate_scene(sc, slot_index, internal_of_index, [&](const sbc::BeamSlot &r) {
-            SbHostBeam &h = hb[r.slot];
-            h.a = r.a, h.b = r.b, h.da = r.da, h.db = r.db; // endpoints as slots (re-indexed below) and as data indices
-            memcpy(h.f, r.f9, 9 * sizeof(float));
-        });
-        switch (bad.kind) {
-        case sbc::SCENE_OK: break;
-        case sbc::PARTICLE_RANGE: SB_FAIL(e, SB_ERR_INVALID, "particle slot %u maps to data index %u >= max_particles", bad.slot, bad.idx);
-        case sbc::PARTICLE_TWICE: SB_FAIL(e, SB_ERR_INVALID, "particle data index %u is mapped by two slots (%u and %u)", bad.idx, bad.a, bad.slot);
-        case sbc::BEAM_RANGE: SB_FAIL(e, SB_ERR_INVALID, "beam slot %u maps to data index %u >= max_beams", bad.slot, bad.idx);
-        case sbc::BEAM_TWICE: SB_FAIL(e, SB_ERR_INVALID, "beam data index %u is mapped by two slots", bad.idx);
-        default:
-            SB_FAIL(e, SB_ERR_INVALID, "beam slot %u (data index %u) references particle data index %u/%u that no particle slot maps to", bad.slot,
-                    bad.idx, bad.a, bad.b);
-        }
+    u.tm.mark("sync + free + shadows");
+    u.hb.resize(u.B);
+    const sbc::Scene sc{layout, maxP, maxB, u.P, u.B, u.mp, u.bd};
+    const sbc::SceneError bad = sbc::validate_scene(sc, u.slot_index, u.internal_of_index, [&](const sbc::BeamSlot &r) {
+        SbHostBeam &h = u.hb[r.slot];
+        h.a = r.a, h.b = r.b, h.da = r.da, h.db = r.db; // endpoints as slots (re-indexed below) and as data indices
+        memcpy(h.f, r.f9, 9 * sizeof(float));
+    });
+    switch (bad.kind) {
+    case sbc::SCENE_OK: break;
+    case sbc::PARTICLE_RANGE: SB_FAIL(e, SB_ERR_INVALID, "particle slot %u maps to data index %u >= max_particles", bad.slot, bad.idx);
+    case sbc::PARTICLE_TWICE: SB_FAIL(e, SB_ERR_INVALID, "particle data index %u is mapped by two slots (%u and %u)", bad.idx, bad.a, bad.slot);
+    case sbc::BEAM_RANGE: SB_FAIL(e, SB_ERR_INVALID, "beam slot %u maps to data index %u >= max_beams", bad.slot, bad.idx);
+    case sbc::BEAM_TWICE: SB_FAIL(e, SB_ERR_INVALID, "beam data index %u is mapped by two slots", bad.idx);
+    default:
+        SB_FAIL(e, SB_ERR_INVALID, "beam slot %u (data index %u) references particle data index %u/%u that no particle slot maps to", bad.slot,
+                bad.idx, bad.a, bad.b);
     }
-
-    tm.mark("validate + beam records");
-    // ---- internal particle order
-    std::vector<float> px(P), py(P);
-    sbt::parallel_ranges(P, 1 << 16, [&](size_t s0, size_t s1) {
+    u.tm.mark("validate + beam records");
+    u.px.resize(u.P), u.py.resize(u.P);
+    sbt::parallel_ranges(u.P, 1 << 16, [&](size_t s0, size_t s1) {
         for (size_t s = s0; s < s1; s++) {
-            memcpy(&px[s], pd + (size_t)slot_index[s] * SB_PARTICLE_STRIDE, 4);
-            memcpy(&py[s], pd + (size_t)slot_index[s] * SB_PARTICLE_STRIDE + 4, 4);
+            memcpy(&u.px[s], u.pd + (size_t)u.slot_index[s] * SB_PARTICLE_STRIDE, 4);
+            memcpy(&u.py[s], u.pd + (size_t)u.slot_index[s] * SB_PARTICLE_STRIDE + 4, 4);
         }
     });
-    SbTiling tl;
-    SbBlocking bl;
-    uint32_t blockK = 0; // > 0: the temporally blocked plan is in use (sb_blocking.h)
-    uint32_t plan_target = 0; // tile size the plan's bisection was made for
-    uint32_t tile_target_used = 0; // ... and the single-substep tiling's
-    std::vector<uint32_t> order; // internal -> slot
+    return SB_OK;
+}
+
+// the internal particle order: the blocked plan's, the single-substep tiling's, or the slots' own (atomic path)
+static void upload_plan(sb_engine *e, SbUpload &u)
+{
+    const uint32_t P = u.P, B = u.B;
     if (e->path == SB_PATH_TILED) {
         uint32_t target = e->opt.tile_particles ? e->opt.tile_particles : 1024;
         const bool want_blocked = e->opt.collision_mode == SB_COLLIDE_OFF && e->opt.block_substeps != 1 && P && B;
@@ -967,9 +975,7 @@ static sb_status sb_write_buffers_impl(sb_engine *e, const void *metadata, size_
             // runs in whole rounds of them: 1026 tiles on 512 slots take three rounds where 1024 take two (a slab with its
             // ghost columns ran 27 % slower than the same slab without, for 5 % more particles).  So the tile size follows
             // the scene: the fewest rounds whose tiles stay within ~1100 particles, and then tiles that fill those rounds.
-            int cus = 256;
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device);
-            const uint64_t slots = (uint64_t)std::max(cus, 1) * 2u;
+            const uint64_t slots = cu_count(e) * 2u;
             const uint64_t own_cap = SB_BK_OWNP * SB_BK_T; // (the kernel's own-particle slots)
             const uint64_t rounds = std::max<uint64_t>(1, (P + slots * own_cap - 1) / (slots * own_cap));
             target = (uint32_t)std::min<uint64_t>(own_cap, std::max<uint64_t>(256u, (P + slots * rounds - 1) / (slots * rounds)));
@@ -980,201 +986,179 @@ static sb_status sb_write_buffers_impl(sb_engine *e, const void *metadata, size_
             // region and entry sizes of EVERY smaller depth (they are prefixes) -- and a launch of k substeps only ever loads the
             // depth-k prefix of the plan, so a plan that does not fit at full depth is kept as it is and the launches stay at the
             // deepest depth that does (r02 re-made the plan for that depth: 65 ms per million particles; before that once per candidate)
-            // (by class: the kernel keeps own and halo items in slots of their own, sb_blocked.hip)
-            auto fits = [&](uint32_t d) {
-                return bl.max_own <= SB_BK_OWNP * SB_BK_T && bl.halo_at[d] <= SB_BK_HALOP * SB_BK_T && bl.max_ownb <= SB_BK_OWNB * SB_BK_T &&
-                       bl.halo_entries_at[d] <= SB_BK_HALOB * SB_BK_T && bl.region_at[d] <= (1u << SB_BK_LBITS) - 2u;
-            };
-            blockK = std::min<uint32_t>(e->opt.block_substeps ? e->opt.block_substeps : SB_BK_KPLAN, SB_BK_KMAX);
-            sb_build_blocking(bl, px, py, hb, target, blockK);
-            if (bl.max_own > SB_BK_OWNP * SB_BK_T || bl.max_ownb > SB_BK_OWNB * SB_BK_T) {
+            const uint32_t asked = std::min<uint32_t>(e->opt.block_substeps ? e->opt.block_substeps : SB_BK_KPLAN, SB_BK_KMAX);
+            sb_build_blocking(u.bl, u.px, u.py, u.hb, target, asked);
+            if (u.bl.max_own > SB_BK_OWNP * SB_BK_T || u.bl.max_ownb > SB_BK_OWNB * SB_BK_T) {
                 // the tile size owns more than the kernel's own slots hold (the automatic one on a scene with four or more beams
                 // per particle; an explicit sb_options.tile_particles above 1024 -- it is an upper bound, include/softbody.h:
                 // until r04 such a value silently lost the blocked kernel): smaller tiles, once
-                const double shrink = std::min((double)(SB_BK_OWNP * SB_BK_T) / bl.max_own, (double)(SB_BK_OWNB * SB_BK_T) / std::max(bl.max_ownb, 1u));
+                const double shrink = std::min((double)(SB_BK_OWNP * SB_BK_T) / u.bl.max_own, (double)(SB_BK_OWNB * SB_BK_T) / std::max(u.bl.max_ownb, 1u));
                 target = std::max<uint32_t>(128u, (uint32_t)(target * shrink * 0.97));
-                sb_build_blocking(bl, px, py, hb, target, blockK);
+                sb_build_blocking(u.bl, u.px, u.py, u.hb, target, asked);
             }
-            plan_target = target;
-            if (!fits(blockK)) { // the plan stays (a launch of k substeps loads the depth-k prefix of it): launches just stay shallower
-                uint32_t fit = 0;
-                for (uint32_t d = 1; d < blockK; d++)
-                    if (fits(d)) fit = d;
-                blockK = fit;
-            }
+            u.plan_target = target;
+            u.blockK = blocked_fit_depth(u.bl, asked, 1); // (the blocked layout is the engine's own: one substep a launch is still a plan)
         }
-        if (blockK) {
-            order = bl.order;
+        if (u.blockK) {
+            u.order = u.bl.order;
         } else {
             if (!e->opt.tile_particles) {
                 // the single-substep kernel's own default: 1024 particles, four workgroups per CU.  A scene a few per cent
                 // above a whole number of rounds of those slots (a 1000-column slab with its ghost columns: 1036 tiles) would
                 // run one more, almost empty round -- tiles of up to 1100 particles that fit the rounds instead: 29.6 -> 26.7 us
                 // with the hash on, 20.3 -> 18.9 without (smaller tiles in more rounds measured worse than either)
-                int cus = 256;
-                (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device);
-                const uint64_t slots = (uint64_t)std::max(cus, 1) * 4u, full = ((uint64_t)P + 1023u) / 1024u / slots;
+                const uint64_t slots = cu_count(e) * 4u, full = ((uint64_t)P + 1023u) / 1024u / slots;
                 target = 1024;
                 if (full >= 1 && (uint64_t)P > slots * full * 1024u && (uint64_t)P <= slots * full * 1100u)
                     target = (uint32_t)(((uint64_t)P + slots * full - 1) / (slots * full));
             }
-            sb_build_tiling(tl, px, py, hb, target);
-            tile_target_used = target;
-            order = tl.order;
+            sb_build_tiling(u.tl, u.px, u.py, u.hb, target);
+            u.tile_target = target;
+            u.order = u.tl.order;
         }
     } else {
-        order.resize(P);
-        std::iota(order.begin(), order.end(), 0u);
+        u.order.resize(P);
+        std::iota(u.order.begin(), u.order.end(), 0u);
     }
-    std::vector<uint32_t> internal_of_slot(P);
-    e->h_pslot = order;
+    u.internal_of_slot.resize(P);
+    e->h_pslot = u.order;
     e->h_pidx.resize(P);
     sbt::parallel_ranges(P, 1 << 16, [&](size_t i0, size_t i1) {
         for (size_t i = i0; i < i1; i++) {
-            internal_of_slot[order[i]] = (uint32_t)i;
-            e->h_pidx[i] = slot_index[order[i]];
+            u.internal_of_slot[u.order[i]] = (uint32_t)i;
+            e->h_pidx[i] = u.slot_index[u.order[i]];
         }
     });
+    u.tm.mark("tiling / blocking plan");
+}
 
-    tm.mark("tiling / blocking plan");
-    // ---- upload particles (A = data, B = zero: engineWorker.ts:588,593)
-    {
-        std::vector<float2> hp(P), hv(P), ha(P);
-        sbt::parallel_ranges(P, 1 << 16, [&](size_t i0, size_t i1) {
-            for (size_t i = i0; i < i1; i++) {
-                float q[6];
-                memcpy(q, pd + (size_t)e->h_pidx[i] * SB_PARTICLE_STRIDE, SB_PARTICLE_STRIDE);
-                hp[i] = make_float2(q[0], q[1]);
-                hv[i] = make_float2(q[2], q[3]);
-                ha[i] = make_float2(q[4], q[5]);
-            }
-        });
-        for (int k = 0; k < 2; k++) {
-            SB_TRY(dev_alloc(e, &e->part[k].pos, P));
-            SB_TRY(dev_alloc(e, &e->part[k].vel, P));
-            SB_TRY(dev_alloc(e, &e->part[k].acc, P));
-        }
-        SB_TRY(stage_put_bytes(e, e->part[0].pos, hp.data(), P * sizeof(float2)));
-        SB_TRY(stage_put_bytes(e, e->part[0].vel, hv.data(), P * sizeof(float2)));
-        SB_TRY(stage_put_bytes(e, e->part[0].acc, ha.data(), P * sizeof(float2)));
-        SB_HIP(e, hipMemset(e->part[1].pos, 0, std::max<size_t>(P, 1) * sizeof(float2)));
-        SB_HIP(e, hipMemset(e->part[1].vel, 0, std::max<size_t>(P, 1) * sizeof(float2)));
-        SB_HIP(e, hipMemset(e->part[1].acc, 0, std::max<size_t>(P, 1) * sizeof(float2)));
-        SB_TRY(dev_alloc(e, &e->d_pidx, P));
-        SB_TRY(dev_alloc(e, &e->d_pslot, P));
-        SB_TRY(stage_put_bytes(e, e->d_pidx, e->h_pidx.data(), (size_t)P * 4));
-        SB_TRY(stage_put_bytes(e, e->d_pslot, e->h_pslot.data(), (size_t)P * 4));
-        e->d_islot = nullptr;
-        if (e->opt.collision_mode == SB_COLLIDE_GRID && e->path == SB_PATH_TILED) { // (active slots are 0 .. P - 1)
-            SB_TRY(dev_alloc(e, &e->d_islot, P));
-            SB_TRY(stage_put(e, e->d_islot, (size_t)P * 4, [&](size_t off, size_t len, uint8_t *out) {
-                uint32_t *o = (uint32_t *)out;
-                const size_t first = off / 4, n = len / 4;
-                sbt::parallel_ranges(n, 1 << 16, [&](size_t i0, size_t i1) {
-                    for (size_t i = i0; i < i1; i++) o[i] = internal_of_slot[first + i];
-                });
-            }));
-        }
+static sb_status upload_particles(sb_engine *e, SbUpload &u)
+{
+    const uint32_t P = u.P;
+    u.box = deinterleave_particles(u.pd, e->h_pidx, u.soa);
+    for (int k = 0; k < 2; k++) {
+        SB_TRY(dev_alloc(e, &e->part[k].pos, P));
+        SB_TRY(dev_alloc(e, &e->part[k].vel, P));
+        SB_TRY(dev_alloc(e, &e->part[k].acc, P));
     }
+    SB_TRY(particles_to_device(e, u.soa));
+    SB_TRY(dev_alloc(e, &e->d_pidx, P));
+    SB_TRY(dev_alloc(e, &e->d_pslot, P));
+    SB_TRY(stage_put_bytes(e, e->d_pidx, e->h_pidx.data(), (size_t)P * 4));
+    SB_TRY(stage_put_bytes(e, e->d_pslot, e->h_pslot.data(), (size_t)P * 4));
+    e->d_islot = nullptr;
+    if (e->opt.collision_mode == SB_COLLIDE_GRID && e->path == SB_PATH_TILED) { // (active slots are 0 .. P - 1)
+        SB_TRY(dev_alloc(e, &e->d_islot, P));
+        SB_TRY(stage_put_bytes(e, e->d_islot, u.internal_of_slot.data(), (size_t)P * 4));
+    }
+    u.tm.mark("particles to device");
+    return SB_OK;
+}
 
-    tm.mark("particles to device");
-    // ---- beam copies
-    std::vector<uint32_t> c_ia, c_ib, c_pair, c_slot;
-    std::vector<float> mat_table;
-    e->h_copy_of_slot.assign(B, 0);
-    e->bk = SbBlockedDev{};
-    e->beams = SbBeamArrays{};
-    if (blockK) {
-        SB_TRY(upload_blocked(e, bl, hb, blockK, tm));
-        if (!blockK) // no dictionary: the single-substep tiling after all, on the SAME bisection (the particles are already on
-            sb_build_tiling(tl, px, py, hb, plan_target); // the device in the blocked plan's order, which follows its tile size)
-        if (!blockK) tile_target_used = plan_target;
+// ---- beam layout, one function per kernel family.  Blocked: the plan goes to the device whole (upload_blocked); u.blockK = 0
+// on return: no dictionary, the single-substep tiling after all, on the SAME bisection (the particles are already on the device
+// in the blocked plan's order, which follows its tile size)
+static sb_status layout_blocked(sb_engine *e, SbUpload &u)
+{
+    SB_TRY(upload_blocked(e, u.bl, u.hb, u.blockK, u.tm));
+    if (!u.blockK) {
+        sb_build_tiling(u.tl, u.px, u.py, u.hb, u.plan_target);
+        u.tile_target = u.plan_target;
     }
-    if (blockK) {
-    } else if (e->path == SB_PATH_TILED) {
-        e->ntiles = tl.ntiles;
-        e->nhalo = (uint32_t)tl.halo_idx.size();
-        c_slot = tl.copy_slot;
-        e->h_copy_of_slot = tl.copy_of_slot;
-        e->tile_cap_own = tl.max_own;
-        e->tile_cap_all = tl.max_all;
-        SB_TRY(dev_alloc(e, &e->d_tile_p0, tl.tile_p0.size()));
-        SB_TRY(dev_alloc(e, &e->d_tile_b0, tl.tile_b0.size()));
-        SB_TRY(dev_alloc(e, &e->d_tile_h0, tl.tile_h0.size()));
-        SB_TRY(dev_alloc(e, &e->d_halo_idx, tl.halo_idx.size()));
-        SB_HIP(e, hipMemcpy(e->d_tile_p0, tl.tile_p0.data(), tl.tile_p0.size() * 4, hipMemcpyHostToDevice));
-        SB_HIP(e, hipMemcpy(e->d_tile_b0, tl.tile_b0.data(), tl.tile_b0.size() * 4, hipMemcpyHostToDevice));
-        SB_HIP(e, hipMemcpy(e->d_tile_h0, tl.tile_h0.data(), tl.tile_h0.size() * 4, hipMemcpyHostToDevice));
-        // buffer A holds whatever accelerations were uploaded; buffer B is all zeros (engineWorker.ts:593)
-        SB_TRY(dev_alloc(e, &e->d_acc_flag[0], tl.ntiles));
-        SB_TRY(dev_alloc(e, &e->d_acc_flag[1], tl.ntiles));
-        SB_HIP(e, hipMemset(e->d_acc_flag[0], 0x01, std::max<size_t>(tl.ntiles, 1) * 4));
-        SB_HIP(e, hipMemset(e->d_acc_flag[1], 0x00, std::max<size_t>(tl.ntiles, 1) * 4));
-        if (!tl.halo_idx.empty())
-            SB_HIP(e, hipMemcpy(e->d_halo_idx, tl.halo_idx.data(), tl.halo_idx.size() * 4, hipMemcpyHostToDevice));
-        if (tl.max_all > 65535)
-            SB_FAIL(e, SB_ERR_UNSUPPORTED, "a tile addresses %u particles (> 65535, 16-bit local indices): lower tile_particles", tl.max_all);
-        // ---- material dictionary: beams that share (length, spring, damp, yield, limit) share one
-        // table row, and the row number rides in the spare bits of the endpoint word.  Lossless;
-        // falls back to (spring, damp, yield, limit) rows + per-copy length, then to per-copy arrays.
-        uint32_t lbits = 1;
-        while ((1u << lbits) <= tl.max_all) lbits++; // all-ones local index stays free for the dead marker
-        const uint32_t mbits = lbits >= 16 ? 0 : 32 - 2 * lbits;
-        const uint32_t mat_cap = mbits == 0 ? 0 : std::min<uint32_t>(1u << std::min(mbits, 12u), 2048u);
-        SbMatDict mdict;
-        build_material_dictionary(mdict, hb, mat_cap);
-        e->mat_mode = mdict.mode;
-        mat_table.swap(mdict.table);
-        if (e->mat_mode == 0) lbits = 16;
-        e->lbits = lbits;
-        e->nmat = (uint32_t)(mat_table.size() / 6);
-        c_pair.resize(tl.copy_la.size());
-        sbt::parallel_ranges(c_pair.size(), 1 << 16, [&](size_t c0, size_t c1) {
-            for (size_t c = c0; c < c1; c++) {
-                uint32_t w = 0xFFFFFFFFu;
-                if (tl.copy_slot[c] != 0xFFFFFFFFu) {
-                    w = tl.copy_la[c] | (tl.copy_lb[c] << lbits);
-                    if (e->mat_mode) w |= mdict.of_slot[tl.copy_slot[c]] << (2 * lbits);
-                }
-                c_pair[c] = w;
+    return SB_OK;
+}
+
+static sb_status layout_tiled(sb_engine *e, SbUpload &u)
+{
+    const SbTiling &tl = u.tl;
+    e->ntiles = tl.ntiles;
+    e->nhalo = (uint32_t)tl.halo_idx.size();
+    u.c_slot = tl.copy_slot;
+    e->h_copy_of_slot = tl.copy_of_slot;
+    e->tile_cap_own = tl.max_own;
+    e->tile_cap_all = tl.max_all;
+    SB_TRY(dev_alloc(e, &e->d_tile_p0, tl.tile_p0.size()));
+    SB_TRY(dev_alloc(e, &e->d_tile_b0, tl.tile_b0.size()));
+    SB_TRY(dev_alloc(e, &e->d_tile_h0, tl.tile_h0.size()));
+    SB_TRY(dev_alloc(e, &e->d_halo_idx, tl.halo_idx.size()));
+    SB_HIP(e, hipMemcpy(e->d_tile_p0, tl.tile_p0.data(), tl.tile_p0.size() * 4, hipMemcpyHostToDevice));
+    SB_HIP(e, hipMemcpy(e->d_tile_b0, tl.tile_b0.data(), tl.tile_b0.size() * 4, hipMemcpyHostToDevice));
+    SB_HIP(e, hipMemcpy(e->d_tile_h0, tl.tile_h0.data(), tl.tile_h0.size() * 4, hipMemcpyHostToDevice));
+    SB_TRY(dev_alloc(e, &e->d_acc_flag[0], tl.ntiles));
+    SB_TRY(dev_alloc(e, &e->d_acc_flag[1], tl.ntiles));
+    if (!tl.halo_idx.empty())
+        SB_HIP(e, hipMemcpy(e->d_halo_idx, tl.halo_idx.data(), tl.halo_idx.size() * 4, hipMemcpyHostToDevice));
+    if (tl.max_all > 65535)
+        SB_FAIL(e, SB_ERR_UNSUPPORTED, "a tile addresses %u particles (> 65535, 16-bit local indices): lower tile_particles", tl.max_all);
+    // ---- material dictionary: beams that share (length, spring, damp, yield, limit) share one
+    // table row, and the row number rides in the spare bits of the endpoint word.  Lossless;
+    // falls back to (spring, damp, yield, limit) rows + per-copy length, then to per-copy arrays.
+    uint32_t lbits = 1;
+    while ((1u << lbits) <= tl.max_all) lbits++; // all-ones local index stays free for the dead marker
+    const uint32_t mbits = lbits >= 16 ? 0 : 32 - 2 * lbits;
+    const uint32_t mat_cap = mbits == 0 ? 0 : std::min<uint32_t>(1u << std::min(mbits, 12u), 2048u);
+    SbMatDict mdict;
+    build_material_dictionary(mdict, u.hb, mat_cap);
+    e->mat_mode = mdict.mode;
+    u.mat_table.swap(mdict.table);
+    if (e->mat_mode == 0) lbits = 16;
+    e->lbits = lbits;
+    e->nmat = (uint32_t)(u.mat_table.size() / 6);
+    u.c_pair.resize(tl.copy_la.size());
+    sbt::parallel_ranges(u.c_pair.size(), 1 << 16, [&](size_t c0, size_t c1) {
+        for (size_t c = c0; c < c1; c++) {
+            uint32_t w = 0xFFFFFFFFu;
+            if (tl.copy_slot[c] != 0xFFFFFFFFu) {
+                w = tl.copy_la[c] | (tl.copy_lb[c] << lbits);
+                if (e->mat_mode) w |= mdict.of_slot[tl.copy_slot[c]] << (2 * lbits);
             }
-        });
-        e->lds_bytes = (size_t)tl.max_all * sizeof(float2) + (size_t)tl.max_all * sizeof(int2) + (size_t)e->nmat * 6 * sizeof(float);
-        if (e->lds_bytes > 160 * 1024)
-            SB_FAIL(e, SB_ERR_UNSUPPORTED, "tile needs %zu bytes of LDS (> 160 KiB): lower tile_particles or use SB_PATH_ATOMIC", e->lds_bytes);
-        // SB_COLLIDE_GRID: what is left of a quarter of the CU's LDS (four workgroups per CU) behind the kernel's own arrays is
-        // the area the workgroup makes its tile's neighbour lists in (sb_lists_cooperative: 12 bytes per record and cell)
-        e->lds_coop_off = e->lds_coop = 0;
-        if (e->opt.collision_mode == SB_COLLIDE_GRID) {
-            static const bool coop_off = [] { const char *v = getenv("SB_GRID_COOP"); return v && atoi(v) == 0; }();
-            const size_t quarter = 160 * 1024 / (SB_GRID_WAVES / 2), fixed = 1024 /* the kernel's static LDS */ + 512 /* allocation granule */;
-            const size_t off = (e->lds_bytes + 15) & ~(size_t)15;
-            if (!coop_off && off + fixed + 8 * 1024 <= quarter) {
-                e->lds_coop_off = (uint32_t)off;
-                e->lds_coop = (uint32_t)((quarter - fixed - off) & ~(size_t)15);
-            }
+            u.c_pair[c] = w;
         }
-    } else {
-        c_ia.resize(B);
-        c_ib.resize(B);
-        c_slot.resize(B);
-        for (uint32_t s = 0; s < B; s++) {
-            c_ia[s] = internal_of_slot[hb[s].a];
-            c_ib[s] = internal_of_slot[hb[s].b];
-            c_slot[s] = s;
-            e->h_copy_of_slot[s] = s;
+    });
+    e->lds_bytes = (size_t)tl.max_all * sizeof(float2) + (size_t)tl.max_all * sizeof(int2) + (size_t)e->nmat * 6 * sizeof(float);
+    if (e->lds_bytes > 160 * 1024)
+        SB_FAIL(e, SB_ERR_UNSUPPORTED, "tile needs %zu bytes of LDS (> 160 KiB): lower tile_particles or use SB_PATH_ATOMIC", e->lds_bytes);
+    // SB_COLLIDE_GRID: what is left of a quarter of the CU's LDS (four workgroups per CU) behind the kernel's own arrays is
+    // the area the workgroup makes its tile's neighbour lists in (sb_lists_cooperative: 12 bytes per record and cell)
+    e->lds_coop_off = e->lds_coop = 0;
+    if (e->opt.collision_mode == SB_COLLIDE_GRID) {
+        static const bool coop_off = [] { const char *v = getenv("SB_GRID_COOP"); return v && atoi(v) == 0; }();
+        const size_t quarter = 160 * 1024 / (SB_GRID_WAVES / 2), fixed = 1024 /* the kernel's static LDS */ + 512 /* allocation granule */;
+        const size_t off = (e->lds_bytes + 15) & ~(size_t)15;
+        if (!coop_off && off + fixed + 8 * 1024 <= quarter) {
+            e->lds_coop_off = (uint32_t)off;
+            e->lds_coop = (uint32_t)((quarter - fixed - off) & ~(size_t)15);
         }
     }
-    const uint32_t nc = blockK ? e->nbeam : (uint32_t)c_slot.size();
+    return SB_OK;
+}
+
+static void layout_atomic(sb_engine *e, SbUpload &u)
+{
+    const uint32_t B = u.B;
+    u.c_ia.resize(B);
+    u.c_ib.resize(B);
+    u.c_slot.resize(B);
+    for (uint32_t s = 0; s < B; s++) {
+        u.c_ia[s] = u.internal_of_slot[u.hb[s].a];
+        u.c_ib[s] = u.internal_of_slot[u.hb[s].b];
+        u.c_slot[s] = s;
+        e->h_copy_of_slot[s] = s;
+    }
+}
+
+// the per-copy arrays of the tiled and the atomic layout (a blocked plan brought its own: upload_blocked)
+static sb_status upload_beam_arrays(sb_engine *e, SbUpload &u)
+{
+    const uint32_t nc = u.blockK ? e->nbeam : (uint32_t)u.c_slot.size();
     e->nbeam = nc;
-    e->h_slot_of_copy = c_slot; // (empty with a blocked plan, which keeps its own maps: SbBlockedDev::h_beam_slot)
+    e->h_slot_of_copy = u.c_slot; // (empty with a blocked plan, which keeps its own maps: SbBlockedDev::h_beam_slot)
     e->d_live0 = nullptr;
     e->live_words = 0;
-    if (!blockK) {
+    if (!u.blockK) {
         float *SbBeamArrays::*fields[9] = {&SbBeamArrays::length, &SbBeamArrays::target, &SbBeamArrays::last,
                                            &SbBeamArrays::spring, &SbBeamArrays::damp,   &SbBeamArrays::yield,
                                            &SbBeamArrays::limit,  &SbBeamArrays::strain, &SbBeamArrays::stress};
-        sbt::uvec<float> tmp(nc);
         for (int k = 0; k < 9; k++) {
             // the material table replaces the static parameter arrays (and the length array in mode 2)
             const bool is_static = k == 0 || (k >= 3 && k <= 6);
@@ -1182,25 +1166,22 @@ static sb_status sb_write_buffers_impl(sb_engine *e, const void *metadata, size_
                 e->beams.*fields[k] = nullptr;
                 continue;
             }
-            sbt::parallel_ranges(nc, 1 << 16, [&](size_t c0, size_t c1) {
-                for (size_t c = c0; c < c1; c++) tmp[c] = c_slot[c] == 0xFFFFFFFFu ? 0.0f : hb[c_slot[c]].f[k];
-            });
             SB_TRY(dev_alloc(e, &(e->beams.*fields[k]), nc));
-            if (nc) SB_TRY(stage_put_bytes(e, e->beams.*fields[k], tmp.data(), (size_t)nc * 4));
+            SB_TRY(put_beam_field(e, e->beams.*fields[k], u.hb, k, u.c_slot.data(), nc));
         }
         SB_TRY(dev_alloc(e, &e->beams.slot, nc));
-        if (nc) SB_TRY(stage_put_bytes(e, e->beams.slot, c_slot.data(), (size_t)nc * 4));
+        if (nc) SB_TRY(stage_put_bytes(e, e->beams.slot, u.c_slot.data(), (size_t)nc * 4));
         if (e->path == SB_PATH_TILED) {
             SB_TRY(dev_alloc(e, &e->beams.pair, nc));
-            if (nc) SB_TRY(stage_put_bytes(e, e->beams.pair, c_pair.data(), (size_t)nc * 4));
-            SB_TRY(dev_alloc(e, &e->d_mat, mat_table.size()));
-            if (!mat_table.empty())
-                SB_HIP(e, hipMemcpy(e->d_mat, mat_table.data(), mat_table.size() * 4, hipMemcpyHostToDevice));
+            if (nc) SB_TRY(stage_put_bytes(e, e->beams.pair, u.c_pair.data(), (size_t)nc * 4));
+            SB_TRY(dev_alloc(e, &e->d_mat, u.mat_table.size()));
+            if (!u.mat_table.empty())
+                SB_HIP(e, hipMemcpy(e->d_mat, u.mat_table.data(), u.mat_table.size() * 4, hipMemcpyHostToDevice));
         } else {
             SB_TRY(dev_alloc(e, &e->beams.ia, nc));
             SB_TRY(dev_alloc(e, &e->beams.ib, nc));
-            if (nc) SB_TRY(stage_put_bytes(e, e->beams.ia, c_ia.data(), (size_t)nc * 4));
-            if (nc) SB_TRY(stage_put_bytes(e, e->beams.ib, c_ib.data(), (size_t)nc * 4));
+            if (nc) SB_TRY(stage_put_bytes(e, e->beams.ia, u.c_ia.data(), (size_t)nc * 4));
+            if (nc) SB_TRY(stage_put_bytes(e, e->beams.ib, u.c_ib.data(), (size_t)nc * 4));
         }
         // the one array delete passes write into, as uploaded (rewrite_scene_state puts it back)
         uint32_t *live = e->path == SB_PATH_TILED ? e->beams.pair : e->beams.ia;
@@ -1208,19 +1189,21 @@ static sb_status sb_write_buffers_impl(sb_engine *e, const void *metadata, size_
         if (nc) SB_HIP(e, hipMemcpyAsync(e->d_live0, live, (size_t)nc * 4, hipMemcpyDeviceToDevice, e->stream));
         e->live_words = nc;
     }
-    tm.mark("beams to device");
-    // ---- spatial hash: covers the uploaded bounding box plus a margin; particles that later
-    // leave it are clamped into edge cells (still a superset of the contacts, sb_physics.h)
+    u.tm.mark("beams to device");
+    return SB_OK;
+}
+
+// spatial hash: the geometry, the arrays and the decision state a run starts from (grid_ctl0); their contents and the host's
+// counters are sb_grid_reset_hash's.  Covers the uploaded bounding box plus a margin; particles that later leave it are clamped
+// into edge cells (still a superset of the contacts, sb_physics.h)
+static sb_status upload_hash(sb_engine *e, SbUpload &u)
+{
+    const uint32_t P = u.P;
     e->grid = SbGrid{};
     e->ncell = 0;
     e->d_grid_ctl = nullptr;
     if (e->opt.collision_mode == SB_COLLIDE_GRID) {
-        float minx = INFINITY, maxx = -INFINITY, miny = INFINITY, maxy = -INFINITY;
-        for (uint32_t s = 0; s < P; s++) {
-            if (!std::isfinite(px[s]) || !std::isfinite(py[s])) continue;
-            minx = std::min(minx, px[s]); maxx = std::max(maxx, px[s]);
-            miny = std::min(miny, py[s]); maxy = std::max(maxy, py[s]);
-        }
+        float minx = u.box.minx, maxx = u.box.maxx, miny = u.box.miny, maxy = u.box.maxy;
         if (!(minx <= maxx)) minx = maxx = miny = maxy = 0.f;
         // skin: how far a particle may drift before the hash is rebuilt (SbGridCtl, sb_physics.h)
         const float skin = e->opt.grid_skin < 0.f ? 0.f : (e->opt.grid_skin > 0.f ? e->opt.grid_skin : 0.4f * e->prm.particle_radius);
@@ -1248,107 +1231,126 @@ static sb_status sb_write_buffers_impl(sb_engine *e, const void *metadata, size_
         e->ncell = e->grid.nx_cap * e->grid.ny_cap; // capacity: the skin only ever makes cells larger than cell_min
         e->grid.bounds = S;
         e->grid.wide_side = std::max(1u, (uint32_t)std::floor(std::sqrt((double)e->ncell)));
-        const size_t n1 = (size_t)e->ncell + 1;
+        e->grid_heads = (size_t)e->ncell + 1;
+        e->grid_slots = 3 * SB_GRID_SLOTS * 4; // float4[3][SB_GRID_SLOTS]: max | sample dx | sample dy | -
         for (int k = 0; k < 2; k++) { // two hash buffers (SbGrid: the lagged schedule pushes the next one while the current one is still scanned)
-            SB_TRY(dev_alloc(e, &e->d_head[k], n1));
-            SB_HIP(e, hipMemset(e->d_head[k], 0, n1 * 8)); // build number 0: "never written" (the first build is number 1)
+            SB_TRY(dev_alloc(e, &e->d_head[k], e->grid_heads));
             SB_TRY(dev_alloc(e, &e->d_rec[k], P));
             SB_TRY(dev_alloc(e, &e->d_cell_of[k], P));
         }
         SB_TRY(dev_alloc(e, &e->d_grid_ctl, 2));
-        SB_TRY(dev_alloc(e, &e->d_blk_max, 3 * SB_GRID_SLOTS * 4)); // float4[3][SB_GRID_SLOTS]: max | sample dx | sample dy | -
-        SB_HIP(e, hipMemset(e->d_blk_max, 0, 3 * SB_GRID_SLOTS * 16));
+        SB_TRY(dev_alloc(e, &e->d_blk_max, e->grid_slots));
         SB_TRY(dev_alloc(e, &e->d_grid_outside, 4));
-        SB_HIP(e, hipMemset(e->d_grid_outside, 0, 16));
         SB_TRY(dev_alloc(e, &e->d_grid_nonempty, 1 + 1024)); // (the hybrid look's answer and the per-workgroup minima behind it)
-        SbGridCtl ctl[2] = {};
-        for (int k = 0; k < 2; k++) {
-            ctl[k].skin_min = skin;
-            // grid_skin given explicitly: that skin, fixed.  Default: adaptive between 0.4 r and 1.6 r (SbGridCtl).
-            ctl[k].skin_max = e->opt.grid_skin > 0.f ? skin : 4.0f * skin;
-            ctl[k].geo.skin = skin;
-            ctl[k].geo.cell = cell;
-            ctl[k].geo.nx = e->grid.nx_cap;
-            ctl[k].geo.ny = e->grid.ny_cap;
-            ctl[k].geo.x0 = x0;
-            ctl[k].geo.y0 = y0;
-            ctl[k].geo.wide = 0;
-            const float reach = e->grid.two_r + 2.0f * skin;
-            ctl[k].geo.reach2 = reach * reach * 1.001f;
-            ctl[k].pgeo = ctl[k].geo;
-            ctl[k].since = 1000; // "the hash before the first one lasted long": start lean
-            ctl[k].executed = sb_grid_executed0();
-        }
-        SB_HIP(e, hipMemcpy(e->d_grid_ctl, ctl, sizeof ctl, hipMemcpyHostToDevice));
-        memcpy(e->grid_ctl0, ctl, sizeof ctl);
-        e->grid_heads = n1;
-        e->grid_slots = 3 * SB_GRID_SLOTS * 4;
-        e->grid_par = 0;
-        e->grid_force = true; // no hash yet: the first substep starts with a forced helper launch
-        e->grid_classic_left = e->grid_classic_chunk = e->grid_calm = 0;
-        e->grid_executed = sb_grid_executed0();
-        e->grid.head = e->d_head[0];
-        e->grid.rec = e->d_rec[0];
-        e->grid.cell_of = e->d_cell_of[0];
-        e->grid.head1 = e->d_head[1];
-        e->grid.rec1 = e->d_rec[1];
-        e->grid.cell_of1 = e->d_cell_of[1];
         SB_TRY(dev_alloc(e, &e->d_nl_count, P));
         SB_TRY(dev_alloc(e, &e->d_nl, (size_t)SB_NL_CAP * std::max<size_t>(P, 1)));
-        SB_HIP(e, hipMemset(e->d_nl_count, 0, std::max<size_t>(P, 1) * 4));
-        e->grid.nl_count = e->d_nl_count;
-        e->grid.nl = e->d_nl;
-        e->grid.nl_stride = P;
+        for (SbGridCtl &c : e->grid_ctl0) {
+            c = SbGridCtl{};
+            c.skin_min = skin;
+            // grid_skin given explicitly: that skin, fixed.  Default: adaptive between 0.4 r and 1.6 r (SbGridCtl).
+            c.skin_max = e->opt.grid_skin > 0.f ? skin : 4.0f * skin;
+            c.geo.skin = skin;
+            c.geo.cell = cell;
+            c.geo.nx = e->grid.nx_cap;
+            c.geo.ny = e->grid.ny_cap;
+            c.geo.x0 = x0;
+            c.geo.y0 = y0;
+            c.geo.wide = 0;
+            const float reach = e->grid.two_r + 2.0f * skin;
+            c.geo.reach2 = reach * reach * 1.001f;
+            c.pgeo = c.geo;
+            c.since = 1000; // "the hash before the first one lasted long": start lean
+            c.executed = sb_grid_executed0();
+        }
+        e->grid.head = e->d_head[0], e->grid.rec = e->d_rec[0], e->grid.cell_of = e->d_cell_of[0];
+        e->grid.head1 = e->d_head[1], e->grid.rec1 = e->d_rec[1], e->grid.cell_of1 = e->d_cell_of[1];
+        e->grid.nl_count = e->d_nl_count, e->grid.nl = e->d_nl, e->grid.nl_stride = P;
     }
-    tm.mark("spatial hash arrays");
-    // ---- accumulators and masks, zeroed (engineWorker.ts:591-592)
-    if (e->path == SB_PATH_ATOMIC) {
-        SB_TRY(dev_alloc(e, &e->d_forces, P));
-        SB_HIP(e, hipMemset(e->d_forces, 0, std::max<size_t>(P, 1) * sizeof(int2)));
+    u.tm.mark("spatial hash arrays");
+    return SB_OK;
+}
+
+// SB_COLLIDE_GRID: a blocked plan BESIDE the tiled layout, on the same bisection, for the stretches of a run in which
+// nothing is within reach of anything (every neighbour list empty: the collision loop of compute.wgsl:142-170, which the
+// reference always runs, is then a no-op and K substeps can go out of LDS and registers as with collisions off).
+// hybrid_substeps below decides substep run by substep run; every other entry point only ever sees the tiled layout.
+// The upload only starts the plan (SbHybridPending).
+static void start_hybrid_plan(sb_engine *e, const SbUpload &u)
+{
+    static const bool hybrid_off = [] { const char *v = getenv("SB_HYBRID"); return v && atoi(v) == 0; }();
+    if (hybrid_off || e->path != SB_PATH_TILED || e->opt.collision_mode != SB_COLLIDE_GRID || e->opt.block_substeps == 1 || !u.P || !u.B || !u.tl.ntiles)
+        return;
+    auto *p = new SbHybridPending;
+    p->px = u.px;
+    p->py = u.py;
+    p->target = u.tile_target;
+    p->depth = std::min<uint32_t>(e->opt.block_substeps ? e->opt.block_substeps : SB_BK_KPLAN, SB_BK_KMAX);
+    const SbHostBeams *beams = &e->h_beams;
+    p->th = std::thread([p, beams] { sb_build_blocking(p->bl, p->px, p->py, *beams, p->target, p->depth); });
+    e->hy_pending = p;
+}
+
+static sb_status sb_write_buffers_impl(sb_engine *e, const void *metadata, size_t metadata_bytes, const void *mapping,
+                           size_t mapping_bytes, const void *particles, size_t particles_bytes,
+                           const void *beams, size_t beams_bytes)
+{
+    if (!e) return SB_ERR_INVALID;
+    const uint32_t maxP = e->opt.max_particles, maxB = e->opt.max_beams, layout = e->opt.layout;
+    const sbc::SizeError sz = sbc::check_sizes(layout, maxP, maxB, true, metadata, metadata_bytes, mapping, mapping_bytes, particles, particles_bytes,
+                                               beams, beams_bytes);
+    if (sz.buffer == sbc::BUF_NULL) SB_FAIL(e, SB_ERR_INVALID, "sb_write_buffers: null buffer");
+    if (sz.buffer) SB_FAIL(e, SB_ERR_INVALID, "%s buffer is %zu bytes, need %zu", sbc::buffer_name(sz.buffer), sz.have, sz.need);
+    const uint8_t *md = (const uint8_t *)metadata, *mp = (const uint8_t *)mapping;
+    const uint8_t *pd = (const uint8_t *)particles, *bd = (const uint8_t *)beams;
+    const sbc::Header hd(md);
+    if (!hd.capacity_is(maxP, maxB))
+        SB_FAIL(e, SB_ERR_INVALID, "metadata max_particles/max_beams (%u/%u) differ from the engine capacity (%u/%u)", hd.maxP, hd.maxB, maxP, maxB);
+    if (!hd.counts_fit(maxP, maxB)) SB_FAIL(e, SB_ERR_INVALID, "metadata counts (%u/%u) exceed capacity (%u/%u)", hd.P, hd.B, maxP, maxB);
+
+    SB_HIP(e, hipSetDevice(e->device));
+    SB_HIP(e, hipStreamSynchronize(e->stream));
+    reap_join(e);
+    {
+        bool kept = false;
+        const sb_status st = rewrite_scene_state(e, md, mp, pd, bd, &kept);
+        if (st != SB_OK) { // (past its point of no return the device holds half of each scene: nothing may step or read it)
+            e->loaded = false;
+            return st;
+        }
+        if (kept) return SB_OK;
     }
-    SB_TRY(dev_alloc(e, &e->d_broken, (nc + 31) / 32));
-    SB_HIP(e, hipMemset(e->d_broken, 0, std::max<size_t>((nc + 31) / 32, 1) * 4));
-    if (e->bk.K) e->bk.d_broken = e->d_broken;
-    // ---- SB_COLLIDE_GRID: a blocked plan BESIDE the tiled layout, on the same bisection, for the stretches of a run in which
-    // nothing is within reach of anything (every neighbour list empty: the collision loop of compute.wgsl:142-170, which the
-    // reference always runs, is then a no-op and K substeps can go out of LDS and registers as with collisions off).
-    // hybrid_substeps below decides substep run by substep run; every other entry point only ever sees the tiled layout.
+    free_scene(e);
+
+    std::unique_ptr<SbUpload> up(new SbUpload); // (a failure destroys it here, success on the side thread)
+    SbUpload &u = *up;
+    u.md = md, u.mp = mp, u.pd = pd, u.bd = bd, u.P = hd.P, u.B = hd.B;
+    SB_TRY(upload_validate(e, u));
+    upload_plan(e, u);
+    SB_TRY(upload_particles(e, u));
+    e->h_copy_of_slot.assign(u.B, 0);
+    e->bk = SbBlockedDev{};
     e->hy = SbBlockedDev{};
-    e->h_tile_p0.assign(tl.tile_p0.begin(), tl.tile_p0.end());
-    SB_TRY(dev_alloc(e, &e->d_dead_gen, B));
-    SB_HIP(e, hipMemset(e->d_dead_gen, 0, std::max<size_t>(B, 1) * 4));
-    e->delete_gen = 0;
+    e->beams = SbBeamArrays{};
+    if (u.blockK) SB_TRY(layout_blocked(e, u)); // (may give the blocked plan up: u.blockK = 0)
+    if (!u.blockK && e->path == SB_PATH_TILED) SB_TRY(layout_tiled(e, u));
+    if (e->path != SB_PATH_TILED) layout_atomic(e, u);
+    SB_TRY(upload_beam_arrays(e, u));
+    SB_TRY(upload_hash(e, u));
+    // ---- what a run mutates: allocated here, put to "just uploaded" by the one function that does
+    if (e->path == SB_PATH_ATOMIC) SB_TRY(dev_alloc(e, &e->d_forces, u.P));
+    SB_TRY(dev_alloc(e, &e->d_broken, (e->nbeam + 31) / 32));
+    if (e->bk.K) e->bk.d_broken = e->d_broken;
+    SB_TRY(dev_alloc(e, &e->d_dead_gen, u.B));
+    e->h_tile_p0.assign(u.tl.tile_p0.begin(), u.tl.tile_p0.end());
+    SB_TRY(reset_run_state(e));
     memcpy(&e->consts, md + 48, sizeof(SbConsts));
     SB_HIP(e, hipDeviceSynchronize());
-    e->h_beams.swap(hb);
+    e->h_beams.swap(u.hb); // (u.hb: the previous scene's records from here on)
     e->loaded = true;
     pool_trim(e);
-    tm.mark("masks + final sync");
-    {
-        static const bool hybrid_off = [] { const char *v = getenv("SB_HYBRID"); return v && atoi(v) == 0; }();
-        if (!hybrid_off && e->path == SB_PATH_TILED && e->opt.collision_mode == SB_COLLIDE_GRID && e->opt.block_substeps != 1 && P && B &&
-            tl.ntiles) {
-            auto *p = new SbHybridPending;
-            p->px = px;
-            p->py = py;
-            p->target = tile_target_used;
-            p->depth = std::min<uint32_t>(e->opt.block_substeps ? e->opt.block_substeps : SB_BK_KPLAN, SB_BK_KMAX);
-            const SbHostBeams *beams = &e->h_beams;
-            p->th = std::thread([p, beams] { sb_build_blocking(p->bl, p->px, p->py, *beams, p->target, p->depth); });
-            e->hy_pending = p;
-        }
-    }
-    {
-        auto *trash = new SbUploadTrash;
-        trash->px.swap(px);
-        trash->py.swap(py);
-        std::swap(trash->tl, tl);
-        std::swap(trash->bl, bl);
-        trash->hb.swap(hb); // (the previous scene's records)
-        std::vector<uint32_t> *big[8] = {&slot_index, &internal_of_index, &order, &internal_of_slot, &c_ia, &c_ib, &c_pair, &c_slot};
-        for (int k = 0; k < 8; k++) trash->v[k].swap(*big[k]);
-        e->reaper = std::thread([trash] { delete trash; });
-    }
+    u.tm.mark("masks + final sync");
+    start_hybrid_plan(e, u);
+    e->reaper = std::thread([trash = up.release()] { delete trash; });
     return SB_OK;
 }
 
@@ -1482,17 +1484,7 @@ static sb_status hybrid_materialise(sb_engine *e)
     if (!p) return SB_OK;
     if (p->th.joinable()) p->th.join();
     const SbBlocking &hbl = p->bl;
-    uint32_t hk = p->depth;
-    auto fits = [&](uint32_t d) {
-        return hbl.max_own <= SB_BK_OWNP * SB_BK_T && hbl.halo_at[d] <= SB_BK_HALOP * SB_BK_T && hbl.max_ownb <= SB_BK_OWNB * SB_BK_T &&
-               hbl.halo_entries_at[d] <= SB_BK_HALOB * SB_BK_T && hbl.region_at[d] <= (1u << SB_BK_LBITS) - 2u;
-    };
-    if (!fits(hk)) { // (launches of k substeps load the depth-k prefix of the plan: they just stay shallower)
-        uint32_t fit = 0;
-        for (uint32_t d = 2; d < hk; d++)
-            if (fits(d)) fit = d;
-        hk = fit;
-    }
+    uint32_t hk = blocked_fit_depth(hbl, p->depth, 2); // (one substep a launch is what the tiled kernel beside it already does)
     sb_status st = SB_OK;
     // the two plans must agree on the particle order and on the tiles (same bisection of the same positions)
     if (hk && hbl.order == e->h_pslot && hbl.tile_p0 == e->h_tile_p0) {

@@ -245,7 +245,7 @@ struct sb_engine {
     hipEvent_t stage_done[2] = {nullptr, nullptr};
     bool stage_busy[2] = {false, false};
     int stage_cur = 0;
-    std::thread reaper;               // frees the host arrays of the last upload (sb_api.hip: SbUploadTrash)
+    std::thread reaper;               // frees the host arrays of the last upload (sb_api.hip: SbUpload)
 
     struct SbRenderState *rs = nullptr; // sb_render.hip: draw tables (rebuilt at the first render after an upload) + key image
     struct SbStateIoState *sio = nullptr; // sb_state_io.hip: export tables (rebuilt at the first export after an upload)
@@ -292,4 +292,4 @@ sb_status sbr_copy_table(sb_engine *e, const uint32_t **copy); // per engine bea
 void sbs_invalidate(sb_engine *e);      // an upload replaced the scene: the next export builds its tables again
 void sbs_release(sb_engine *e);         // everything sb_state_io allocated (sb_destroy)
 // sb_api.hip
-sb_status sb_grid_reset_hash(sb_engine *e); // the spatial hash forgets every position it holds (plan-keeping upload, particle import)
+sb_status sb_grid_reset_hash(sb_engine *e); // the spatial hash forgets every position it holds (every upload, through reset_run_state; particle import)
