@@ -209,6 +209,9 @@ sb_status sb_get_counts(sb_engine *e, uint32_t *particles, uint32_t *beams);
  * "grid_cells", "grid_builds", "grid_wide", "grid_skin_x1000", "material_mode", "materials", "local_index_bits",
  * "render_table_build_us" (host time of sb_render's last draw-table build: the first render after an upload),
  * "halo_guard" (1 while a halo guard is set, sb_halo_guard),
+ * "summary_partials" (sb_summary: the partials the last call used), "summary_table_build_us" (host time of its last table build:
+ * the first summary after an upload), "summary_kernel_vgprs" / "summary_kernel_scratch_bytes" (the most registers / scratch
+ * bytes per lane over every kernel a summary may launch, as the runtime reports them; scratch must be 0),
  * "acc_dirty_tiles" / "plastic_tiles" (tiles whose zero-acceleration / never-yielded promise flag in the CURRENT state
  * buffer is nonzero; 0 on engines without tiles, "plastic_tiles" 0 without a blocked plan.  Both wait for the stream and
  * copy one word per tile to the host: for tests, never inside a timed region). */
@@ -420,6 +423,48 @@ sb_status sb_read_state_device(sb_engine *e, void *device_particles, void *devic
  * planning upload: the hash keeps the frame fitted at that upload (particles outside are clamped into its edge cells), and the
  * tiles stay those bisected from the upload's positions. */
 sb_status sb_write_particles_device(sb_engine *e, const void *device_particles);
+
+/* ---- one summary row of the whole scene, reduced on the device ----
+ * What a driver asks of a big scene between steps -- is everything still finite, did it leave the box, how much energy is left,
+ * did anything break -- without exporting the state.  The row is SB_SUMMARY_WORDS = 24 floats with the meaning of a row of
+ * sb_batch_summary_device (below), word for word: counts in words 0 .. 5, means, extremes, the kinetic energy, word 20 = 1
+ * ("uploaded"), words 21 .. 23 = 0; a statistic over an empty set is the quiet NaN 0x7FC00000, counts and the energy are 0 then;
+ * a FINITE PARTICLE is one whose six floats are finite, a FINITE BEAM a live beam whose strain and stress are finite.
+ * counts (optional, NULL = none): 8 x uint64 -- particles, live beam slots, beams removed by a delete pass (or by a plan-keeping
+ * upload), break flags pending among the live beam slots, non-finite particles, non-finite live beams, 1 ("uploaded"), 0.  These
+ * are exact whatever the size of the scene; row words 0 .. 5 are (float) of the same integers.  "Pending" is one per beam SLOT
+ * flagged since the last delete pass (the bits of the reference's delete mask at this point of the stream), not one per copy
+ * the engine's layout keeps of a beam.
+ * The arithmetic is sb_batch_summary_device's pin, for any capacity: sums in double; leaf i is the value at DATA index i (+0.0
+ * where no finite particle / beam lives), i = 0 .. W-1, W the smallest power of two >= max_particles (particle sums) or
+ * >= max_beams (the mean strain); the reduction is the stride-halving tree, for h = W/2 .. 1: s[i] += s[i + h] (i < h); the energy
+ * leaf is 0.5 * ((double)vx * vx + (double)vy * vy), word 15 the largest such value without the 0.5; a mean is
+ * (float)(sum / (double)finite count); energy and word 15 are rounded to float once.  Extremes compare -0.0 below +0.0 at every
+ * stage, so which zero they return does not depend on the cut either.  So a row is the same bits on every run, for
+ * every way the reduction is cut into launches, and for a scene that also fits an sb_batch it is that batch's row.
+ * sb_summary_options.partials moves the cut (how many partial sums per column the launches pass through): 0 = the engine's
+ * choice for its capacity, else a power of two in [256, SB_SUMMARY_MAX_PARTIALS] (the scratch buffer is then at most
+ * 48 B * max(partials, W / 16): 12 MiB at the cap for capacities up to 2^22).  The result does not depend on it; it exists for tests
+ * and timing.  sb_get_info "summary_partials" reports the one the last call used (the particle tree's, when chosen by the engine).
+ * sb_summary_device only ENQUEUES on the engine's stream and writes device memory, which must stay valid until that work has
+ * run; sb_summary WAITS and copies to the host.  The first summary after an upload builds its tables (data index -> the engine's
+ * own order) on the host and waits for the stream once, as the first export does; later ones only enqueue.  Nothing is read
+ * back to the host to form the row.  A summary only reads: positions, the spatial hash, the per-tile flags, the hybrid's
+ * schedule and the blocked plan stay as they were, and every later result is the one without the call.
+ * Errors: SB_ERR_INVALID for a NULL handle, a NULL row, a row that is not 4-byte or counts that are not 8-byte aligned, a
+ * struct_size that is neither 0 nor the struct's, partials that is not such a power of two, a nonzero reserved word, a capacity
+ * above 2^31 -- all before anything touches a device; SB_ERR_STATE before an upload; SB_ERR_UNSUPPORTED on an engine with ghost
+ * zones or peers configured (per-rank rows are not handled). */
+#define SB_SUMMARY_WORDS 24u
+#define SB_SUMMARY_MAX_PARTIALS 262144u
+typedef struct sb_summary_options {
+    uint32_t struct_size;    /* = sizeof(sb_summary_options); 0 or a NULL pointer = all defaults */
+    uint32_t partials;       /* partial sums per column at the cut; 0 = the engine's choice */
+    uint32_t reserved[6];    /* zero */
+} sb_summary_options;
+sb_status sb_summary_device(sb_engine *e, const sb_summary_options *opts, void *device_row_f32 /* [SB_SUMMARY_WORDS] float */,
+                            void *device_counts_u64 /* [8] uint64 or NULL */);
+sb_status sb_summary(sb_engine *e, const sb_summary_options *opts, float *row /* [SB_SUMMARY_WORDS] */, uint64_t *counts /* [8] or NULL */);
 
 /* ---- batched small scenes: N independent scenes, one workgroup per scene, one launch per frame ----
  * A second object beside sb_engine, for the user who steps thousands of copies of a SMALL scene (a controller, an RL loop):

@@ -255,6 +255,26 @@ struct sb_engine {
     std::vector<std::pair<void *, size_t>> pool_used, pool_free; // device blocks of the scene / kept for the next upload (sb_api.hip dev_alloc)
 };
 
+// what sb_state_io.hip and sb_summary.hip keep between calls (sb_engine sio): tables of the scene of the latest upload, built at
+// the first export / the first summary after it (sb_write_buffers drops both through sbs_invalidate)
+struct SbStateIoState {
+    bool valid = false;
+    uint32_t nslots = 0;       // the caller's beam slots of the latest upload
+    uint2 *d_slot = nullptr;   // per caller slot u: {engine slot, data index of its record}; the copy is sbr_copy_table's
+    size_t cap_slot = 0;
+    double build_ms = 0.0;     // host time of the last table build
+    // sb_summary.hip: the summation tree runs over DATA indices
+    bool sum_valid = false;
+    uint32_t *d_sum_pinv = nullptr; // per particle data index < sum_np: its internal particle (0xFFFFFFFF: none)
+    uint2 *d_sum_bleaf = nullptr;   // per beam data index < sum_nb: {engine slot (0xFFFFFFFF: none), the copy read back for it}
+    uint32_t sum_np = 0, sum_nb = 0, sum_nslots = 0; // highest data index in use + 1 (particles, beams); the caller's beam slots (table size only)
+    double *d_sum_part = nullptr;   // partial sums of a call: 5 particle columns, then the strain column
+    unsigned long long *d_sum_stat = nullptr, *d_sum_out = nullptr; // the order-free statistics of a call; sb_summary's device-side result
+    size_t cap_sum_pinv = 0, cap_sum_bleaf = 0, cap_sum_part = 0, cap_sum_stat = 0, cap_sum_out = 0;
+    uint32_t sum_partials = 0;      // sb_summary_options.partials as the last call resolved it ("summary_partials")
+    double sum_build_ms = 0.0;
+};
+
 inline void sb_set_error(sb_engine *e, const char *text) { if (e) e->err = text; else sb_set_create_error(text); } // (sb_error.h)
 
 // mapping entries of the caller's layout (sb_scene_codec.h)
@@ -291,5 +311,7 @@ sb_status sbr_copy_table(sb_engine *e, const uint32_t **copy); // per engine bea
 // sb_state_io.hip
 void sbs_invalidate(sb_engine *e);      // an upload replaced the scene: the next export builds its tables again
 void sbs_release(sb_engine *e);         // everything sb_state_io allocated (sb_destroy)
+// sb_summary.hip
+bool sbm_info(sb_engine *e, const char *key, uint64_t *value); // its sb_get_info keys (false: not one of them)
 // sb_api.hip
 sb_status sb_grid_reset_hash(sb_engine *e); // the spatial hash forgets every position it holds (every upload, through reset_run_state; particle import)

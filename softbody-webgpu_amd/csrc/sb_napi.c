@@ -77,6 +77,7 @@ static struct {
     sb_status (*peer_exchange)(sb_engine *);
     sb_status (*get_stream)(sb_engine *, void **);
     sb_status (*render)(sb_engine *, const sb_render_options *, void *, size_t);
+    sb_status (*summary)(sb_engine *, const sb_summary_options *, float *, uint64_t *);
     sb_status (*partition_create)(uint32_t, uint32_t, uint32_t, const void *, const void *, const void *, const void *, uint32_t,
                                   uint32_t, float, sb_partition **);
     sb_status (*partition_destroy)(sb_partition *);
@@ -176,6 +177,7 @@ static napi_value js_load(napi_env env, napi_callback_info info)
     SYM(peer_exchange, "sb_peer_exchange");
     SYM(get_stream, "sb_get_stream");
     SYM(render, "sb_render");
+    SYM(summary, "sb_summary");
     SYM(partition_create, "sb_partition_create");
     SYM(partition_destroy, "sb_partition_destroy");
     SYM(partition_rank_counts, "sb_partition_rank_counts");
@@ -1080,6 +1082,45 @@ static napi_value js_render(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* summary(handle, {partials}) -> {row: Float32Array(24), counts: Float64Array(8)}: the summary row of the whole scene and its exact
+ * integer counts (as numbers: all below 2^53), reduced on the GPU by sb_summary (which waits for the stream). */
+static napi_value js_summary(napi_env env, napi_callback_info info)
+{
+    if (!need_lib(env)) return NULL;
+    size_t argc = 2;
+    napi_value argv[2];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    sb_engine *e = argc >= 1 ? get_engine(env, argv[0]) : NULL;
+    if (!e) return NULL;
+    sb_summary_options o;
+    memset(&o, 0, sizeof o);
+    o.struct_size = sizeof o;
+    double partials = 0.0;
+    if (argc >= 2) {
+        napi_valuetype t;
+        CHECK_NAPI(napi_typeof(env, argv[1], &t));
+        if (t == napi_object) (void)opt_number(env, argv[1], "partials", &partials);
+    }
+    if (!(partials >= 0.0 && partials <= 4294967295.0) || partials != (double)(uint32_t)partials) {
+        napi_throw_range_error(env, NULL, "summary: partials must be a non-negative integer");
+        return NULL;
+    }
+    o.partials = (uint32_t)partials;
+    void *row = NULL, *cnt = NULL;
+    napi_value vrow = make_typed(env, napi_float32_array, SB_SUMMARY_WORDS, 4, &row);
+    napi_value vcnt = make_typed(env, napi_float64_array, 8, 8, &cnt);
+    if (!vrow || !vcnt) return NULL;
+    uint64_t counts[8];
+    sb_status st = sb.summary(e, &o, (float *)row, counts);
+    if (st != SB_OK) return throw_status(env, e, st, "sb_summary");
+    for (int i = 0; i < 8; i++) ((double *)cnt)[i] = (double)counts[i];
+    napi_value obj;
+    CHECK_NAPI(napi_create_object(env, &obj));
+    CHECK_NAPI(napi_set_named_property(env, obj, "row", vrow));
+    CHECK_NAPI(napi_set_named_property(env, obj, "counts", vcnt));
+    return obj;
+}
+
 static napi_value init(napi_env env, napi_value exports)
 {
     static const struct { const char *name; napi_callback fn; } fns[] = {
@@ -1096,6 +1137,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"partitionCreate", js_partition_create}, {"partitionDestroy", js_partition_destroy},
         {"partitionRankCounts", js_partition_rank_counts}, {"partitionRankScene", js_partition_rank_scene},
         {"partitionRankIds", js_partition_rank_ids}, {"partitionPeer", js_partition_peer}, {"render", js_render},
+        {"summary", js_summary},
         {"partitionRankGuard", js_partition_rank_guard}, {"haloGuard", js_halo_guard}, {"haloGuardStatus", js_halo_guard_status},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

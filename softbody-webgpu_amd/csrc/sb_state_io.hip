@@ -19,16 +19,6 @@
 
 #define SBS_BLOCK 256
 
-// what sb_state_io keeps between calls (sb_engine.h sio): the export tables of the scene of the latest upload, built at the
-// first export after it (sb_write_buffers drops them through sbs_invalidate)
-struct SbStateIoState {
-    bool valid = false;
-    uint32_t nslots = 0;       // the caller's beam slots of the latest upload
-    uint2 *d_slot = nullptr;   // per caller slot u: {engine slot, data index of its record}; the copy is sbr_copy_table's
-    size_t cap_slot = 0;
-    double build_ms = 0.0;     // host time of the last table build
-};
-
 // ---------------------------------------------------------------- kernels
 
 // particle export: a lane per internal index, the 24-byte record at its data index (reads coalesce; writes scatter by the tile
@@ -84,13 +74,15 @@ __global__ __launch_bounds__(SBS_BLOCK) void k_state_import_particles(const floa
 
 void sbs_invalidate(sb_engine *e)
 {
-    if (e && e->sio) e->sio->valid = false;
+    if (e && e->sio) e->sio->valid = e->sio->sum_valid = false;
 }
 
 void sbs_release(sb_engine *e)
 {
     if (!e || !e->sio) return;
-    if (e->sio->d_slot) (void)hipFree(e->sio->d_slot);
+    void *ps[] = {e->sio->d_slot, e->sio->d_sum_pinv, e->sio->d_sum_bleaf, e->sio->d_sum_part, e->sio->d_sum_stat, e->sio->d_sum_out};
+    for (void *p : ps)
+        if (p) (void)hipFree(p);
     delete e->sio;
     e->sio = nullptr;
 }

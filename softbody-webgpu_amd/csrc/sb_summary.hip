@@ -1,0 +1,482 @@
+// sb_summary.hip -- one row of SB_SUMMARY_WORDS statistics of the whole scene of an sb_engine, reduced on the device (sb_summary /
+// sb_summary_device of include/softbody.h; gfx950, wave64).
+//
+// The row is sb_batch_summary_device's, word for word, and so is its pin: sums in double, leaf i = the value at DATA index i (+0.0
+// where no finite particle / beam lives), i = 0 .. W-1 with W the smallest power of two >= the capacity, reduced by the
+// stride-halving tree  for h = W/2 .. 1: s[i] += s[i + h] (i < h).  An engine holds millions of leaves, so the tree is cut into
+// launches.  What makes that possible: after all levels h >= n, element g < n holds the tree-sum of the leaves g + n k
+// (k < W / n), and the tree over those W / n values is again stride-halving: tree(e_0 .. e_K-1) = tree(even e) + tree(odd e)
+// (sbm_tree<K>, the batch kernel's recursion).  So
+//   k_summary_particles<R> / k_summary_beams<R>   n = W / R threads; thread g tree-sums its own R leaves g + n k and writes one
+//                                                 partial per column (x, y, vx, vy, energy | strain); neighbouring threads read
+//                                                 neighbouring data indices
+//   k_summary_fold<R>                             the same step on a column of partials, in place, n -> n / R
+//   k_summary_row                                 one workgroup, at most 256 partials a column: levels 128 and 64 through LDS, the
+//                                                 rest by the xor butterfly of wave 0 (sbm_tree_tail); forms the row
+// Every launch performs exactly the additions of its levels on exactly the tree's operands, so the bits do not depend on where
+// the cuts are (sb_summary_options.partials moves them).  A leaf above the highest data index in use is +0.0 WITHOUT a load:
+// the addition stays (x + +0.0 turns a -0.0 into +0.0, as the tree does), the read goes.  Levels h >= W do not exist: with
+// W < 256 the row kernel starts its butterfly below W.
+// Counts and extremes do not depend on an order: per thread, then LDS atomics, then global atomics on integer keys (SbmStat).
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <new>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "sb_engine.h"
+#include "sb_batch.h" // sbb_finite, sbb_fkey / sbb_unkey, SBB_QNAN, sbb_pow2_at_least: the batch row's own helpers
+
+#define SBM_BLOCK 256u
+#define SBM_RMAX 64u      // partials a thread of a fold tree-sums, at most
+#define SBM_RMAX_LEAF 16u // leaves a thread of a leaf launch tree-sums, at most (all its loads are in flight at once: 179 VGPRs)
+
+// statistics words (unsigned long long each; extremes as ordered keys, so that the neutral values below never win)
+enum {
+    SBM_P_FIN, SBM_P_BAD, SBM_B_FIN, SBM_B_BAD, SBM_B_REMOVED, SBM_PENDING, SBM_MAX_V2, SBM_MAXX, SBM_MAXY, SBM_MAX_STRAIN,
+    SBM_MAX_STRESS, SBM_MINX, SBM_MINY, SBM_MIN_STRESS, SBM_NSTAT
+};
+SB_DEV unsigned long long sbm_neutral(uint32_t k) { return k >= SBM_MINX ? ~0ull : 0ull; }
+
+struct SbmParticles {
+    const uint32_t *inv; // data index -> internal particle (0xFFFFFFFF: none), n_leaf entries
+    const float2 *pos, *vel, *acc;
+    uint32_t n_leaf;
+};
+struct SbmBeams {
+    const uint2 *leaf;   // data index -> {engine slot (0xFFFFFFFF: none), copy read back for it}, n_leaf entries
+    const uint32_t *dead, *broken; // per engine slot: delete pass that removed it (NULL: none has run); bit per copy
+    const float *strain, *stress;
+    uint32_t n_leaf;
+};
+// (extremes as sbb_fkey keys from the first comparison on: -0.0 orders below +0.0 inside a thread exactly as it does between
+// threads and workgroups, so which zero an extreme returns does not depend on which leaves share a thread; 0xFFFFFFFF and 0 are
+// below / above the key of every finite float)
+struct SbmLocal {
+    uint32_t p_fin = 0u, p_bad = 0u, b_fin = 0u, b_bad = 0u, removed = 0u, pending = 0u;
+    uint32_t minx = 0xFFFFFFFFu, miny = 0xFFFFFFFFu, maxx = 0u, maxy = 0u, max_strain = 0u, max_stress = 0u, min_stress = 0xFFFFFFFFu;
+    double max_v2 = 0.0;
+};
+
+// the particle leaves of data index d: {px, py, vx, vy, 0.5 (vx^2 + vy^2)}
+struct SbmParticleLeaf {
+    const SbmParticles &s;
+    SbmLocal &l;
+    uint32_t g, n;
+    SB_DEV void operator()(uint32_t k, double (&out)[5]) const
+    {
+#pragma unroll
+        for (int c = 0; c < 5; c++) out[c] = 0.0;
+        const uint64_t d = (uint64_t)g + (uint64_t)n * k;
+        if (d >= s.n_leaf) return;
+        const uint32_t i = s.inv[d];
+        if (i == 0xFFFFFFFFu) return;
+        const float2 p = s.pos[i], v = s.vel[i], a = s.acc[i];
+        if (!(sbb_finite(p.x) && sbb_finite(p.y) && sbb_finite(v.x) && sbb_finite(v.y) && sbb_finite(a.x) && sbb_finite(a.y))) {
+            l.p_bad++;
+            return;
+        }
+        const double v2 = (double)v.x * (double)v.x + (double)v.y * (double)v.y; // (the products are exact)
+        out[0] = (double)p.x, out[1] = (double)p.y, out[2] = (double)v.x, out[3] = (double)v.y, out[4] = 0.5 * v2;
+        const uint32_t kx = sbb_fkey(p.x), ky = sbb_fkey(p.y);
+        l.minx = min(l.minx, kx), l.maxx = max(l.maxx, kx);
+        l.miny = min(l.miny, ky), l.maxy = max(l.maxy, ky);
+        l.max_v2 = v2 > l.max_v2 ? v2 : l.max_v2; // (a sum of squares: never below +0.0)
+        l.p_fin++;
+    }
+};
+
+// the beam leaf of data index d: strain
+struct SbmBeamLeaf {
+    const SbmBeams &s;
+    SbmLocal &l;
+    uint32_t g, n;
+    SB_DEV void operator()(uint32_t k, double (&out)[1]) const
+    {
+        out[0] = 0.0;
+        const uint64_t d = (uint64_t)g + (uint64_t)n * k;
+        if (d >= s.n_leaf) return;
+        const uint2 t = s.leaf[d];
+        if (t.x == 0xFFFFFFFFu) return;
+        if (s.dead && s.dead[t.x] != 0u) {
+            l.removed++;
+            return;
+        }
+        l.pending += (s.broken[t.y >> 5] >> (t.y & 31u)) & 1u;
+        const float strain = s.strain[t.y], stress = s.stress[t.y];
+        if (!(sbb_finite(strain) && sbb_finite(stress))) {
+            l.b_bad++;
+            return;
+        }
+        out[0] = (double)strain;
+        const uint32_t kn = sbb_fkey(strain), ks = sbb_fkey(stress);
+        l.max_strain = max(l.max_strain, kn);
+        l.max_stress = max(l.max_stress, ks), l.min_stress = min(l.min_stress, ks);
+        l.b_fin++;
+    }
+};
+
+// a column of partials: element g + n k
+struct SbmPartialLeaf {
+    const double *col;
+    uint32_t g, n;
+    SB_DEV void operator()(uint32_t k, double (&out)[1]) const { out[0] = col[(size_t)g + (size_t)n * k]; }
+};
+
+// the stride-halving tree over K values e_j = leaf(base + j step), j < K
+template <int K, int N, class Leaf>
+SB_DEV void sbm_tree(const Leaf &leaf, uint32_t base, uint32_t step, double (&out)[N])
+{
+    if constexpr (K == 1) {
+        leaf(base, out);
+    } else {
+        double even[N], odd[N];
+        sbm_tree<K / 2, N>(leaf, base, 2u * step, even);
+        sbm_tree<K / 2, N>(leaf, base + step, 2u * step, odd);
+#pragma unroll
+        for (int c = 0; c < N; c++) out[c] = even[c] + odd[c];
+    }
+}
+
+// a workgroup's share of the order-free statistics: LDS first, then one global atomic per word that is not neutral
+SB_DEV void sbm_push_stats(const SbmLocal &l, unsigned long long *s_stat, unsigned long long *stat, uint32_t tid)
+{
+    if (tid < SBM_NSTAT) s_stat[tid] = sbm_neutral(tid);
+    __syncthreads();
+    if (l.p_bad) atomicAdd(&s_stat[SBM_P_BAD], (unsigned long long)l.p_bad);
+    if (l.b_bad) atomicAdd(&s_stat[SBM_B_BAD], (unsigned long long)l.b_bad);
+    if (l.removed) atomicAdd(&s_stat[SBM_B_REMOVED], (unsigned long long)l.removed);
+    if (l.pending) atomicAdd(&s_stat[SBM_PENDING], (unsigned long long)l.pending);
+    if (l.p_fin) {
+        atomicAdd(&s_stat[SBM_P_FIN], (unsigned long long)l.p_fin);
+        atomicMin(&s_stat[SBM_MINX], (unsigned long long)l.minx);
+        atomicMin(&s_stat[SBM_MINY], (unsigned long long)l.miny);
+        atomicMax(&s_stat[SBM_MAXX], (unsigned long long)l.maxx);
+        atomicMax(&s_stat[SBM_MAXY], (unsigned long long)l.maxy);
+        atomicMax(&s_stat[SBM_MAX_V2], (unsigned long long)__double_as_longlong(l.max_v2)); // (>= 0: its bits order as it does)
+    }
+    if (l.b_fin) {
+        atomicAdd(&s_stat[SBM_B_FIN], (unsigned long long)l.b_fin);
+        atomicMax(&s_stat[SBM_MAX_STRAIN], (unsigned long long)l.max_strain);
+        atomicMax(&s_stat[SBM_MAX_STRESS], (unsigned long long)l.max_stress);
+        atomicMin(&s_stat[SBM_MIN_STRESS], (unsigned long long)l.min_stress);
+    }
+    __syncthreads();
+    if (tid < SBM_NSTAT) {
+        const unsigned long long v = s_stat[tid];
+        if (v != sbm_neutral(tid)) {
+            if (tid <= SBM_PENDING) atomicAdd(&stat[tid], v);
+            else if (tid < SBM_MINX) atomicMax(&stat[tid], v);
+            else atomicMin(&stat[tid], v);
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_summary_init(unsigned long long *stat)
+{
+    if (threadIdx.x < SBM_NSTAT) stat[threadIdx.x] = sbm_neutral(threadIdx.x);
+}
+
+// n threads; thread g: the tree over its R particle leaves g + n k, one partial per column into part[c * n + g]
+template <int R>
+__global__ __launch_bounds__(SBM_BLOCK) void k_summary_particles(SbmParticles s, uint32_t n, double *part, unsigned long long *stat)
+{
+    __shared__ unsigned long long s_stat[SBM_NSTAT];
+    const uint32_t tid = threadIdx.x, g = blockIdx.x * SBM_BLOCK + tid;
+    SbmLocal l;
+    if (g < n) {
+        double out[5];
+        sbm_tree<R, 5>(SbmParticleLeaf{s, l, g, n}, 0u, 1u, out);
+#pragma unroll
+        for (int c = 0; c < 5; c++) part[(size_t)c * n + g] = out[c];
+    }
+    sbm_push_stats(l, s_stat, stat, tid);
+}
+
+template <int R>
+__global__ __launch_bounds__(SBM_BLOCK) void k_summary_beams(SbmBeams s, uint32_t n, double *part, unsigned long long *stat)
+{
+    __shared__ unsigned long long s_stat[SBM_NSTAT];
+    const uint32_t tid = threadIdx.x, g = blockIdx.x * SBM_BLOCK + tid;
+    SbmLocal l;
+    if (g < n) {
+        double out[1];
+        sbm_tree<R, 1>(SbmBeamLeaf{s, l, g, n}, 0u, 1u, out);
+        part[g] = out[0];
+    }
+    sbm_push_stats(l, s_stat, stat, tid);
+}
+
+// column blockIdx.y of `part` (columns `stride` apart), in place: element g < n_out becomes the tree over the elements g + n_out k,
+// k < R.  Thread g alone reads element g, and nobody writes an element >= n_out, so in place is safe.
+template <int R>
+__global__ __launch_bounds__(SBM_BLOCK) void k_summary_fold(double *part, uint32_t stride, uint32_t n_out)
+{
+    const uint32_t g = blockIdx.x * SBM_BLOCK + threadIdx.x;
+    if (g >= n_out) return;
+    double *col = part + (size_t)blockIdx.y * stride;
+    double out[1];
+    sbm_tree<R, 1>(SbmPartialLeaf{col, g, n_out}, 0u, 1u, out);
+    col[g] = out[0];
+}
+
+// levels h = 128 .. 1 of a tree whose upper levels left w <= 256 partials in s_col[0 .. w-1]; the sum is lane 0's
+SB_DEV double sbm_tree_tail(const double *s_col, uint32_t lane, uint32_t w)
+{
+    double v = s_col[lane];
+    if (w >= 256u) v = (v + s_col[lane + 128u]) + (s_col[lane + 64u] + s_col[lane + 192u]);
+    else if (w == 128u) v = v + s_col[lane + 64u];
+#pragma unroll
+    for (uint32_t h = 32u; h != 0u; h >>= 1)
+        if (h < w) v = v + __shfl_xor(v, (int)h);
+    return v;
+}
+
+// one workgroup: wp <= 256 partials of each particle column (columns stride_p apart), wb <= 256 of the strain column
+__global__ __launch_bounds__(SBM_BLOCK) void k_summary_row(const double *__restrict__ pcol, uint32_t stride_p, uint32_t wp,
+                                                           const double *__restrict__ bcol, uint32_t wb,
+                                                           const unsigned long long *__restrict__ stat,
+                                                           float *row, unsigned long long *counts)
+{
+    __shared__ double s_sum[6][SBM_BLOCK];
+    const uint32_t tid = threadIdx.x;
+#pragma unroll
+    for (uint32_t c = 0; c < 5u; c++) s_sum[c][tid] = tid < wp ? pcol[(size_t)c * stride_p + tid] : 0.0;
+    s_sum[5][tid] = tid < wb ? bcol[tid] : 0.0;
+    __syncthreads();
+    if (tid >= 64u) return;
+    double tot[6];
+#pragma unroll
+    for (uint32_t c = 0; c < 6u; c++) tot[c] = sbm_tree_tail(s_sum[c], tid, c < 5u ? wp : wb);
+    if (tid != 0u) return;
+    const float nan = __uint_as_float(SBB_QNAN);
+    const unsigned long long np = stat[SBM_P_FIN], nb = stat[SBM_B_FIN], removed = stat[SBM_B_REMOVED];
+    // (the engine keeps no metadata buffer on the device: particle_i_c is the particles the leaf launches met, beam_i_c the beams
+    // they met alive -- counted on the device, no host shadow enters the row)
+    const unsigned long long c8[8] = {np + stat[SBM_P_BAD], nb + stat[SBM_B_BAD], removed, stat[SBM_PENDING], stat[SBM_P_BAD], stat[SBM_B_BAD], 1ull, 0ull};
+#pragma unroll
+    for (int k = 0; k < 6; k++) row[k] = (float)c8[k];
+#pragma unroll
+    for (int k = 0; k < 4; k++) row[6 + k] = np ? (float)(tot[k] / (double)np) : nan;
+    row[10] = np ? sbb_unkey((uint32_t)stat[SBM_MINX]) : nan;
+    row[11] = np ? sbb_unkey((uint32_t)stat[SBM_MINY]) : nan;
+    row[12] = np ? sbb_unkey((uint32_t)stat[SBM_MAXX]) : nan;
+    row[13] = np ? sbb_unkey((uint32_t)stat[SBM_MAXY]) : nan;
+    row[14] = (float)tot[4]; // (round to nearest: +inf beyond the range of float)
+    row[15] = np ? (float)__longlong_as_double((long long)stat[SBM_MAX_V2]) : nan;
+    row[16] = nb ? sbb_unkey((uint32_t)stat[SBM_MAX_STRAIN]) : nan;
+    row[17] = nb ? sbb_unkey((uint32_t)stat[SBM_MAX_STRESS]) : nan;
+    row[18] = nb ? sbb_unkey((uint32_t)stat[SBM_MIN_STRESS]) : nan;
+    row[19] = nb ? (float)(tot[5] / (double)nb) : nan;
+    row[20] = 1.0f;
+    row[21] = row[22] = row[23] = 0.0f;
+    if (counts) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) counts[k] = c8[k];
+    }
+}
+
+// ---------------------------------------------------------------- host side
+
+template <class T>
+static sb_status sbm_grow(sb_engine *e, T **p, size_t &cap, size_t n)
+{
+    n = std::max<size_t>(n, 1);
+    if (*p && cap >= n) return SB_OK;
+    if (*p) {
+        SB_HIP(e, hipStreamSynchronize(e->stream)); // a summary in flight may still read it
+        SB_HIP(e, hipFree(*p));
+        *p = nullptr;
+        cap = 0;
+    }
+    SB_HIP(e, hipMalloc((void **)p, n * sizeof(T)));
+    cap = n;
+    return SB_OK;
+}
+
+// The tree is over DATA indices, the engine's arrays are in its own order: per particle data index the internal particle
+// (e->h_pidx inverted), per beam data index the engine slot and the copy sb_load_buffers reads back for it (its beam loop; the
+// caller's slots of the latest upload).  Both end at the highest data index in use: a capacity far above the scene costs no reads.
+static sb_status sbm_build_tables(sb_engine *e)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!e->sio) e->sio = new SbStateIoState();
+    SbStateIoState &s = *e->sio;
+    const uint32_t P = e->P, maxP = e->opt.max_particles, maxB = e->opt.max_beams, Bu = sb_user_beams(e);
+    if (e->h_pidx.size() != P || e->h_copy_of_slot.size() < e->B) SB_FAIL(e, SB_ERR_STATE, "sb_summary: host shadows of the scene are inconsistent");
+    uint32_t np = 0, nb = 0;
+    for (uint32_t i = 0; i < P; i++) np = std::max(np, e->h_pidx[i] + 1u);
+    if (np > maxP) SB_FAIL(e, SB_ERR_STATE, "sb_summary: particle data index outside the scene");
+    std::vector<uint32_t> inv(std::max<uint32_t>(np, 1), 0xFFFFFFFFu);
+    for (uint32_t i = 0; i < P; i++) inv[e->h_pidx[i]] = i;
+    std::vector<uint2> slots(std::max<uint32_t>(Bu, 1));
+    sbt::parallel_ranges(Bu, 1 << 16, [&](size_t u0, size_t u1) {
+        for (size_t u = u0; u < u1; u++) slots[u] = make_uint2(sb_user_slot(e, u), map_get(e, e->h_mapping.data(), (size_t)maxP + u));
+    });
+    for (uint32_t u = 0; u < Bu; u++) {
+        if (slots[u].x >= e->B || slots[u].y >= maxB) SB_FAIL(e, SB_ERR_STATE, "sb_summary: beam slot outside the scene");
+        nb = std::max(nb, slots[u].y + 1u);
+    }
+    std::vector<uint2> leaf(std::max<uint32_t>(nb, 1), make_uint2(0xFFFFFFFFu, 0u));
+    for (uint32_t u = 0; u < Bu; u++) leaf[slots[u].y] = make_uint2(slots[u].x, e->h_copy_of_slot[slots[u].x]);
+    for (uint32_t u = 0; u < Bu; u++)
+        if (leaf[slots[u].y].y >= e->nbeam) SB_FAIL(e, SB_ERR_STATE, "sb_summary: beam copy outside the scene");
+    SB_TRY(sbm_grow(e, &s.d_sum_pinv, s.cap_sum_pinv, inv.size()));
+    SB_TRY(sbm_grow(e, &s.d_sum_bleaf, s.cap_sum_bleaf, leaf.size()));
+    SB_HIP(e, hipMemcpyAsync(s.d_sum_pinv, inv.data(), inv.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    SB_HIP(e, hipMemcpyAsync(s.d_sum_bleaf, leaf.data(), leaf.size() * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+    SB_HIP(e, hipStreamSynchronize(e->stream)); // (the host vectors go out of scope)
+    s.sum_np = np;
+    s.sum_nb = nb;
+    s.sum_nslots = Bu;
+    s.sum_valid = true;
+    s.sum_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SB_OK;
+}
+
+// the widths a tree over W leaves is cut at with `m` partials asked for: the leaf launch writes first() partials a column
+// (a thread sums at most SBM_RMAX_LEAF leaves), folds go on to m and then to at most 256, each by at most SBM_RMAX
+struct SbmCut {
+    uint32_t W, m;
+    uint32_t first() const { return W <= m ? W : std::max(m, W / SBM_RMAX_LEAF); }
+    uint32_t next(uint32_t n) const { return n > m ? std::max(m, n / SBM_RMAX) : std::max(std::min(n, SBM_BLOCK), n / SBM_RMAX); }
+};
+static uint32_t sbm_default_partials(uint32_t W) { return std::min(std::max(W / 4u, SBM_BLOCK), (uint32_t)SB_SUMMARY_MAX_PARTIALS); }
+
+#define SBM_SWITCH_LEAF(R, CALL)                                \
+    switch (R) {                                                \
+    case 1u: { constexpr int R_ = 1; CALL; } break;             \
+    case 2u: { constexpr int R_ = 2; CALL; } break;             \
+    case 4u: { constexpr int R_ = 4; CALL; } break;             \
+    case 8u: { constexpr int R_ = 8; CALL; } break;             \
+    case 16u: { constexpr int R_ = 16; CALL; } break;           \
+    default: SB_FAIL(e, SB_ERR_STATE, "sb_summary: no kernel sums %u values a thread", (unsigned)(R)); \
+    }
+#define SBM_SWITCH_FOLD(R, CALL)                                \
+    switch (R) {                                                \
+    case 32u: { constexpr int R_ = 32; CALL; } break;           \
+    case 64u: { constexpr int R_ = 64; CALL; } break;           \
+    default: SBM_SWITCH_LEAF(R, CALL)                           \
+    }
+
+static sb_status sbm_fold(sb_engine *e, const SbmCut &cut, double *part, uint32_t stride, uint32_t ncols, uint32_t *width)
+{
+    uint32_t n = *width;
+    while (n > SBM_BLOCK) {
+        const uint32_t n_out = cut.next(n), R = n / n_out;
+        const dim3 grid((n_out + SBM_BLOCK - 1) / SBM_BLOCK, ncols);
+        SBM_SWITCH_FOLD(R, (k_summary_fold<R_><<<grid, SBM_BLOCK, 0, e->stream>>>(part, stride, n_out)));
+        n = n_out;
+    }
+    *width = n;
+    return SB_OK;
+}
+
+static sb_status sbm_enqueue(sb_engine *e, const sb_summary_options *o, void *row, void *counts, bool host)
+{
+    if (!e) return SB_ERR_INVALID;
+    const char *what = host ? "sb_summary" : "sb_summary_device";
+    if (!row || ((uintptr_t)row & 3u)) SB_FAIL(e, SB_ERR_INVALID, "%s: null or misaligned row", what);
+    if ((uintptr_t)counts & 7u) SB_FAIL(e, SB_ERR_INVALID, "%s: counts must be 8-byte aligned", what);
+    if (o && o->struct_size != 0 && o->struct_size != sizeof(sb_summary_options))
+        SB_FAIL(e, SB_ERR_INVALID, "%s: sb_summary_options.struct_size %u != %zu", what, o->struct_size, sizeof(sb_summary_options));
+    const uint32_t m_asked = o && o->struct_size ? o->partials : 0u;
+    if (m_asked && (m_asked < SBM_BLOCK || (m_asked & (m_asked - 1u)) || m_asked > SB_SUMMARY_MAX_PARTIALS))
+        SB_FAIL(e, SB_ERR_INVALID, "%s: partials %u is not a power of two in [256, %u]", what, m_asked, (unsigned)SB_SUMMARY_MAX_PARTIALS);
+    if (o && o->struct_size)
+        for (uint32_t r : o->reserved)
+            if (r) SB_FAIL(e, SB_ERR_INVALID, "%s: reserved option words must be zero", what);
+    if (e->opt.max_particles > 0x80000000u || e->opt.max_beams > 0x80000000u)
+        SB_FAIL(e, SB_ERR_INVALID, "%s: capacities above 2^31 are not summed", what);
+    if (!e->loaded) SB_FAIL(e, SB_ERR_STATE, "%s before sb_write_buffers", what);
+    if (e->halo_configured || e->n_ghost_p || e->n_send_p || e->n_ghost_b || e->n_send_b || e->n_peers || e->mailbox)
+        SB_FAIL(e, SB_ERR_UNSUPPORTED, "%s: the engine has ghost zones or peers configured (per-rank rows are not handled)", what);
+    SB_HIP(e, hipSetDevice(e->device));
+    if (!e->sio || !e->sio->sum_valid) SB_TRY(sbm_build_tables(e));
+    SbStateIoState &s = *e->sio;
+
+    const SbmCut cp{sbb_pow2_at_least(e->opt.max_particles), m_asked ? m_asked : sbm_default_partials(sbb_pow2_at_least(e->opt.max_particles))};
+    const SbmCut cb{sbb_pow2_at_least(e->opt.max_beams), m_asked ? m_asked : sbm_default_partials(sbb_pow2_at_least(e->opt.max_beams))};
+    uint32_t np = cp.first(), nb = cb.first();
+    const uint32_t stride_p = np;
+    SB_TRY(sbm_grow(e, &s.d_sum_part, s.cap_sum_part, (size_t)5 * np + nb));
+    SB_TRY(sbm_grow(e, &s.d_sum_stat, s.cap_sum_stat, (size_t)SBM_NSTAT));
+    if (host) SB_TRY(sbm_grow(e, &s.d_sum_out, s.cap_sum_out, (size_t)8 + SB_SUMMARY_WORDS / 2)); // 8 counts, then the row
+    double *pcol = s.d_sum_part, *bcol = s.d_sum_part + (size_t)5 * np;
+    unsigned long long *d_counts = host ? s.d_sum_out : (unsigned long long *)counts;
+    float *d_row = host ? (float *)(s.d_sum_out + 8) : (float *)row;
+
+    k_summary_init<<<1, 64, 0, e->stream>>>(s.d_sum_stat);
+    const SbParticleArrays &c = e->part[e->cur];
+    const SbmParticles sp{s.d_sum_pinv, c.pos, c.vel, c.acc, s.sum_np};
+    const SbmBeams sbm{s.d_sum_bleaf, e->B && e->delete_gen ? e->d_dead_gen : nullptr /* as sb_load_buffers (fetch_dead) sees it */,
+                       e->d_broken, e->beams.strain, e->beams.stress, s.sum_nb};
+    SBM_SWITCH_LEAF(cp.W / np, (k_summary_particles<R_><<<(np + SBM_BLOCK - 1) / SBM_BLOCK, SBM_BLOCK, 0, e->stream>>>(sp, np, pcol, s.d_sum_stat)));
+    SBM_SWITCH_LEAF(cb.W / nb, (k_summary_beams<R_><<<(nb + SBM_BLOCK - 1) / SBM_BLOCK, SBM_BLOCK, 0, e->stream>>>(sbm, nb, bcol, s.d_sum_stat)));
+    SB_TRY(sbm_fold(e, cp, pcol, stride_p, 5u, &np));
+    SB_TRY(sbm_fold(e, cb, bcol, nb, 1u, &nb));
+    k_summary_row<<<1, SBM_BLOCK, 0, e->stream>>>(pcol, stride_p, np, bcol, nb, s.d_sum_stat, d_row,
+                                                  host || counts ? d_counts : nullptr);
+    SB_HIP(e, hipGetLastError());
+    s.sum_partials = cp.m;
+    if (host) {
+        SB_HIP(e, hipMemcpyAsync(row, d_row, SB_SUMMARY_WORDS * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+        if (counts) SB_HIP(e, hipMemcpyAsync(counts, d_counts, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+        SB_HIP(e, hipStreamSynchronize(e->stream));
+    }
+    return SB_OK;
+}
+
+// what sb_get_info reads ("summary_partials", "summary_table_build_us", "summary_kernel_vgprs", "summary_kernel_scratch_bytes")
+bool sbm_info(sb_engine *e, const char *key, uint64_t *value)
+{
+    const std::string k(key);
+    if (k == "summary_partials") *value = e->sio ? e->sio->sum_partials : 0u;
+    else if (k == "summary_table_build_us") *value = e->sio ? (uint64_t)(e->sio->sum_build_ms * 1000.0 + 0.5) : 0u;
+    else if (k == "summary_kernel_vgprs" || k == "summary_kernel_scratch_bytes") { // the most over every kernel a call may launch
+#define SBM_LEAVES(K) (const void *)K<1>, (const void *)K<2>, (const void *)K<4>, (const void *)K<8>, (const void *)K<16>
+        const void *ks[] = {SBM_LEAVES(k_summary_particles), SBM_LEAVES(k_summary_beams), SBM_LEAVES(k_summary_fold),
+                            (const void *)k_summary_fold<32>, (const void *)k_summary_fold<64>, (const void *)k_summary_row,
+                            (const void *)k_summary_init};
+#undef SBM_LEAVES
+        uint64_t most = 0;
+        for (const void *f : ks) {
+            hipFuncAttributes fa{};
+            if (hipSetDevice(e->device) != hipSuccess || hipFuncGetAttributes(&fa, f) != hipSuccess) {
+                (void)hipGetLastError();
+                return false;
+            }
+            most = std::max<uint64_t>(most, k == "summary_kernel_vgprs" ? (uint64_t)fa.numRegs : (uint64_t)fa.localSizeBytes);
+        }
+        *value = most;
+    }
+    else return false;
+    return true;
+}
+
+#define SBM_GUARDED(e, call)                                                   \
+    try {                                                                      \
+        return (call);                                                         \
+    } catch (const std::bad_alloc &) {                                         \
+        if (e) (e)->err = "out of host memory";                                \
+        return SB_ERR_OOM;                                                     \
+    } catch (const std::exception &ex) {                                       \
+        if (e) (e)->err = std::string("internal error: ") + ex.what();         \
+        return SB_ERR_INVALID;                                                 \
+    }
+
+extern "C" {
+
+sb_status sb_summary_device(sb_engine *e, const sb_summary_options *opts, void *device_row_f32, void *device_counts_u64)
+{
+    SBM_GUARDED(e, sbm_enqueue(e, opts, device_row_f32, device_counts_u64, false))
+}
+
+sb_status sb_summary(sb_engine *e, const sb_summary_options *opts, float *row, uint64_t *counts)
+{
+    SBM_GUARDED(e, sbm_enqueue(e, opts, row, counts, true))
+}
+
+} // extern "C"

@@ -39,6 +39,24 @@ class SbOptions(ctypes.Structure):
                 ("block_substeps", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
 
 
+class SbSummaryOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("partials", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 6)]
+
+
+SUMMARY_WORDS = 24           # SB_SUMMARY_WORDS
+SUMMARY_COUNT_WORDS = 8      # the uint64 counts beside the row
+# the counts, in order (include/softbody.h, sb_summary_device); the row's words are batch.SUMMARY_FIELDS (engine.SUMMARY_FIELDS)
+SUMMARY_COUNT_FIELDS = ("particles", "live_beams", "removed_beams", "pending_breaks", "nonfinite_particles", "nonfinite_beams",
+                        "uploaded", "reserved_7")
+
+
+def __getattr__(name):
+    if name == "SUMMARY_FIELDS":  # the batch's row, word for word: its names are not copied (batch.py imports this module)
+        from .batch import SUMMARY_FIELDS
+        return SUMMARY_FIELDS
+    raise AttributeError(name)
+
+
 class SbRenderOptions(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("resolution", ctypes.c_uint32), ("bounds_size", ctypes.c_double),
                 ("particle_radius", ctypes.c_double), ("reserved", ctypes.c_uint32 * 4)]
@@ -150,6 +168,8 @@ def load_library():
     L.sb_render_device.argtypes = [vp, ctypes.POINTER(SbRenderOptions), vp]
     L.sb_read_state_device.argtypes = [vp, vp, vp, vp]
     L.sb_write_particles_device.argtypes = [vp, vp]
+    L.sb_summary_device.argtypes = [vp, ctypes.POINTER(SbSummaryOptions), vp, vp]
+    L.sb_summary.argtypes = [vp, ctypes.POINTER(SbSummaryOptions), vp, vp]
     f32 = ctypes.c_float
     L.sb_partition_create.argtypes = [u32, u32, u32, vp, vp, vp, vp, u32, u32, f32, ctypes.POINTER(vp)]
     L.sb_partition_destroy.argtypes = [vp]
@@ -463,6 +483,44 @@ class Engine:
         Only enqueues; with a tensor, the import waits for torch's current stream and torch's current stream for the import."""
         ptr, t = self._device_buffer("write_particles_device", src, "float32", self.max_particles * PARTICLE_STRIDE)
         self._ordered(t, lambda: load_library().sb_write_particles_device(self._h, ctypes.c_void_p(ptr)))
+
+    # ---- one summary row of the whole scene (sb_summary_device / sb_summary; DESIGN.md 5.18)
+
+    @staticmethod
+    def _summary_options(partials):
+        o = SbSummaryOptions()
+        o.struct_size = ctypes.sizeof(SbSummaryOptions)
+        o.partials = int(partials)
+        return o
+
+    def summary(self, out=None, counts=None, partials=0):
+        """One row of 24 statistics of the whole scene (SUMMARY_FIELDS names the words; the row of BatchEngine.summary(), bit for
+        bit the same arithmetic), reduced on the GPU: a float32 tensor [24] on the engine's device.  `out`: a device pointer
+        (int) or a contiguous float32 torch tensor of at least 24 elements to write into.  counts=True or an int64 tensor of at
+        least 8 elements (or a device pointer): the exact integer counts too (SUMMARY_COUNT_FIELDS), returned as (row, counts).
+        partials: where the reduction is cut (0: the engine's choice; the result does not depend on it).  Only reads the
+        engine, only enqueues; torch's current stream is ordered after it."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty(SUMMARY_WORDS, dtype=torch.float32, device=dev)
+        want_counts = counts is not None and counts is not False
+        if counts is True:
+            counts = torch.empty(SUMMARY_COUNT_WORDS, dtype=torch.int64, device=dev)
+        ptr, t = self._device_buffer("summary: out", out, "float32", SUMMARY_WORDS * 4)
+        cptr, ct = (self._device_buffer("summary: counts", counts, "int64", SUMMARY_COUNT_WORDS * 8) if want_counts else (None, False))
+        o = self._summary_options(partials)
+        vp = ctypes.c_void_p
+        self._ordered(t or ct, lambda: load_library().sb_summary_device(self._h, ctypes.byref(o), vp(ptr), vp(cptr)))
+        return (out, counts) if want_counts else out
+
+    def summary_host(self, partials=0):
+        """The same row without torch: (float32 [24], uint64 [8]) numpy arrays.  Waits for the stream."""
+        row = np.empty(SUMMARY_WORDS, dtype=np.float32)
+        counts = np.empty(SUMMARY_COUNT_WORDS, dtype=np.uint64)
+        o = self._summary_options(partials)
+        self._check(load_library().sb_summary(self._h, ctypes.byref(o), _ptr(row), _ptr(counts)))
+        return row, counts
 
     def state_tensors(self):
         """New torch tensors of the current state: {"particles": (max_particles, 6) float32, "beams": (max_beams, 4) float32,

@@ -71,6 +71,8 @@ class WGPUSoftbodyEngine {
     async frame() { await this.worker.frame(); }
     /** the picture of the current state: the PPM Buffer renderPPM returns, drawn on the GPU (engineWorker.js render) */
     async render(opts) { return this.worker.render(opts); }
+    /** 24 statistics of the whole scene and their integer counts, reduced on the GPU (engineWorker.js summary) */
+    async summary(opts) { return this.worker.summary(opts); }
     /** n frames back to back */
     async run(frames) { for (let i = 0; i < frames && this.running; i++) await this.frame(); }
 

@@ -117,6 +117,20 @@ class WGPUSoftbodyEngineWorker {
         });
     }
 
+    /**
+     * One row of 24 statistics of the whole scene (counts, means, extremes, kinetic energy: the words of sb_summary in
+     * include/softbody.h), reduced on the GPU (sb_summary): no state travels to the host.
+     * @param opts {partials} -- where the reduction is cut (the result does not depend on it)
+     * @returns {row: Float32Array(24), counts: Float64Array(8)}
+     */
+    async summary(opts) {
+        const o = opts || {};
+        return this.lock.run(() => {
+            if (!this.uploaded) throw new Error('summary before writeBuffers');
+            return this.addon.summary(this.handle, { partials: o.partials || 0 });
+        });
+    }
+
     /** benchmark granularity: n substeps, no delete pass; returns device milliseconds */
     async step(n) {
         return this.lock.run(() => this.addon.stepTimed(this.handle, n));

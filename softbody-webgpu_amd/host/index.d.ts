@@ -175,10 +175,18 @@ export class WGPUSoftbodyEngine {
     frame(): Promise<void>;
     /** renderPPM's picture of the current state ("P6" header included), drawn on the GPU (sb_render) */
     render(opts?: RenderOptions): Promise<Buffer>;
+    /** 24 statistics of the whole scene (sb_summary's row) and its exact counts, reduced on the GPU */
+    summary(opts?: SummaryOptions): Promise<SceneSummary>;
     run(frames: number): Promise<void>;
     destroy(): Promise<void>;
     readonly destroyed: boolean;
 }
+
+/** where sb_summary cuts its reduction (a power of two >= 256; the result does not depend on it) */
+export interface SummaryOptions { partials?: number }
+/** row: the 24 words of sb_summary (include/softbody.h); counts: particles, live beams, removed beams, pending breaks, non-finite
+ *  particles, non-finite beams, 1, 0 */
+export interface SceneSummary { row: Float32Array, counts: Float64Array }
 
 export class WGPUSoftbodyEngineWorker {
     static create(canvas: unknown | null, opts?: NativeEngineOptions, post?: (m: { type: number, data?: unknown }) => void): WGPUSoftbodyEngineWorker;
@@ -195,6 +203,8 @@ export class WGPUSoftbodyEngineWorker {
     /** renderPPM(bufferMapper after loadBuffers(), opts) byte for byte, drawn on the GPU without a read-back; the engine's own
      *  boundsSize / particleRadius unless given */
     render(opts?: RenderOptions): Promise<Buffer>;
+    /** sb_summary: the row of 24 statistics of the whole scene and its 8 integer counts, reduced on the GPU without a read-back */
+    summary(opts?: SummaryOptions): Promise<SceneSummary>;
     onMessage(msg: { type: WGPUSoftbodyEngineMessageTypes, data?: unknown }): Promise<void>;
     destroy(): Promise<void>;
 }

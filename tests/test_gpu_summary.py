@@ -1,0 +1,221 @@
+"""Engine.summary() (sb_summary_device) against tests/batch_summary_ref.py on an oracle that ran the same program:
+sums, means and counts by their bits, on every path; the same bytes however the reduction is cut; the batch's row for a scene
+that fits a batch; reading changes nothing; torch's stream is ordered behind it."""
+import json
+
+import numpy as np
+import pytest
+
+import batch_cases as bc
+import batch_harness as bh
+import batch_summary_ref as sr
+import summary_cases as sc
+from test_node_host import needs_node, run_node
+from test_gpu_parity import ATOMIC, GRID, OFF, TILED, ALLPAIRS, assert_same
+
+pytestmark = pytest.mark.gpu
+
+
+def engine(sb, case, **kw):
+    buf = case["buf"]
+    eng = sb.Engine(bounds_size=case["bounds"], layout=buf.layout, max_particles=buf.max_particles, max_beams=buf.max_beams, **kw)
+    eng.write_buffers(buf)
+    return eng
+
+
+def check_now(eng, exp, what, partials=0):
+    row, counts = eng.summary(counts=True, partials=partials)
+    row, counts = row.cpu().numpy(), counts.cpu().numpy().astype(np.uint64)   # (torch's stream waits for the summary: no sync)
+    print(what, "row", row.tolist(), "counts", counts.tolist())
+    sr.assert_rows_equal(row, exp[0], what)
+    assert np.array_equal(counts, exp[1]), "%s: counts %s, expected %s" % (what, counts, exp[1])
+    return row
+
+
+def run_case(sb, oracle, case, what, **kw):
+    exp, _ = sc.expected(oracle, case)
+    eng = engine(sb, case, **kw)
+    if -1 in exp:
+        check_now(eng, exp[-1], what + ", uploaded")
+    for k, op in enumerate(case["program"]):
+        sc.apply_to_engine(eng, op)
+        if k in exp:
+            check_now(eng, exp[k], "%s, after op %d %s" % (what, k, op[0]))
+    eng.destroy()
+
+
+# (every pair of collision mode and path the engine accepts: sb_create refuses SB_COLLIDE_ALLPAIRS on SB_PATH_TILED)
+@pytest.mark.parametrize("mode,path", [(OFF, ATOMIC), (ALLPAIRS, ATOMIC), (GRID, ATOMIC), (OFF, TILED), (GRID, TILED)])
+def test_default_scene(sb, oracle, mode, path):
+    run_case(sb, oracle, sc.case_default(sb, sc.OFF if mode == OFF else sc.ALLPAIRS), "default, mode %d path %d" % (mode, path),
+             collision_mode=mode, path=path)
+
+
+def test_cut_independence(sb, oracle):
+    case = sc.case_cut(sb)
+    exp, _ = sc.expected(oracle, case)
+    eng = engine(sb, case, collision_mode=OFF)
+    for k in (-1, 0):
+        if k == 0:
+            sc.apply_to_engine(eng, case["program"][0])
+        rows = [check_now(eng, exp[k], "cut %d, partials %d" % (k, m), partials=m) for m in (256, 1024, 16384, 0)]
+        assert len({r.tobytes() for r in rows}) == 1
+        assert eng.info("summary_partials") == 4096    # the engine's choice at W = 16384
+    eng.destroy()
+
+
+def test_capacity_far_above_the_scene(sb, oracle):
+    run_case(sb, oracle, sc.case_capacity(sb), "capacity", collision_mode=OFF)
+
+
+@pytest.mark.parametrize("i", [0, 1, 2])
+def test_tree_order_witness(sb, oracle, i):
+    case = sc.witness_cases(sb)[i]
+    run_case(sb, oracle, case, case["name"], collision_mode=OFF, path=ATOMIC)
+
+
+def test_nonfinite(sb, oracle):
+    run_case(sb, oracle, sc.case_nonfinite(sb), "non-finite", collision_mode=OFF, path=TILED)
+
+
+@pytest.mark.parametrize("what,kw", [("tiled", dict(path=TILED, block_substeps=1)), ("blocked", dict(path=TILED)), ("atomic", dict(path=ATOMIC))])
+def test_breaking_lattice(sb, oracle, what, kw):
+    run_case(sb, oracle, sc.case_break(sb), "breaking, " + what, collision_mode=OFF, **kw)
+
+
+def test_equals_the_batch(sb):
+    """the heterogeneous scenes that fit a batch: same buffers, same constants, 2 frames each; words 0 .. 20 by their bits"""
+    hc = bc.case_hetero(sb)
+    consts = {op[1]: op[2] for op in hc["program"] if op[0] == "consts"}
+    for i, buf in enumerate(hc["bufs"]):
+        if buf is None:
+            continue
+        one = dict(hc, bufs=[buf])
+        be = bh.make_batch(sb, one)
+        bh.upload_each(be, [buf])
+        bh.apply_to_batch(be, ("consts", 0, consts[i]))
+        be.frame(2)
+        brow = be.summary().cpu().numpy()[0]
+        be.destroy()
+        eng = sb.Engine(bounds_size=1000.0, layout=buf.layout, max_particles=buf.max_particles, max_beams=buf.max_beams,
+                        collision_mode=GRID)
+        eng.write_buffers(buf)
+        eng.set_physics_constants(consts[i])
+        eng.frame()
+        eng.frame()
+        erow = eng.summary().cpu().numpy()
+        eng.destroy()
+        print("scene", i, "engine", erow.tolist(), "batch", brow.tolist())
+        assert erow[:21].tobytes() == brow[:21].tobytes(), "scene %d: engine %s, batch %s" % (i, erow, brow)
+
+
+READ_ONLY = [("tiled grid", lambda sb: sc.case_break(sb), dict(collision_mode=GRID, path=TILED, tile_particles=256)),
+             ("blocked", lambda sb: sc.case_break(sb), dict(collision_mode=OFF, path=TILED)),
+             ("hybrid", None, dict(collision_mode=GRID))]
+
+
+@pytest.mark.parametrize("what,mk,kw", READ_ONLY, ids=[r[0] for r in READ_ONLY])
+def test_read_only(sb, what, mk, kw):
+    """frame, summary, frame == frame, frame: the read-back byte for byte, and the promise flags and the schedule"""
+    if mk is None:   # a quiet lattice: the hybrid runs blocked launches under SB_COLLIDE_GRID
+        buf = sb.scenes.lattice_buffers(128, 96, d=30.0, origin=(300.0, 900.0), jitter=1.0, layout=2, velocity=(0.4, -1.0))
+        case = dict(buf=buf, bounds=6000.0)
+    else:
+        case = mk(sb)
+    out = {}
+    for k in ("plain", "read"):
+        eng = engine(sb, case, **kw)
+        eng.frame()
+        if k == "read":
+            eng.summary(counts=True)
+            eng.summary(partials=256)
+        eng.frame()
+        out[k] = (eng.load_buffers(case["buf"].copy()), [eng.info(x) for x in ("acc_dirty_tiles", "plastic_tiles", "grid_schedule", "substeps_done")])
+        if what == "hybrid":
+            assert eng.info("hybrid_launches") > 0
+        eng.destroy()
+    assert_same(out["read"][0], out["plain"][0], what)
+    assert out["read"][1] == out["plain"][1], (what, out["read"][1], out["plain"][1])
+
+
+def test_ordering_and_host_variant(sb, oracle):
+    """frame(), summary(), a torch reduction on another torch stream, no sync in between; summary_host() gives the same bytes"""
+    import torch
+    case = sc.case_default(sb)
+    exp, _ = sc.expected(oracle, dict(case, program=[("frame", 1)], compare_after=[0]))
+    eng = engine(sb, case, collision_mode=GRID)
+    side = torch.cuda.Stream(device=torch.device("cuda", eng.device))
+    with torch.cuda.stream(side):
+        eng.frame()
+        row = eng.summary()
+        k = torch.argmax(row[10:14])
+        got = row.clone()
+    side.synchronize()
+    sr.assert_rows_equal(got.cpu().numpy(), exp[0][0], "ordering")
+    assert int(k) == int(np.argmax(exp[0][0][10:14]))
+    hrow, hcounts = eng.summary_host()
+    assert hrow.tobytes() == got.cpu().numpy().tobytes() and np.array_equal(hcounts, exp[0][1])
+    eng.destroy()
+
+
+def test_errors_on_a_live_engine(sb):
+    import torch
+    case = sc.case_default(sb)
+    buf = case["buf"]
+    eng = sb.Engine(bounds_size=1000.0, layout=buf.layout, max_particles=buf.max_particles, max_beams=buf.max_beams, collision_mode=OFF)
+    with pytest.raises(sb.EngineError) as e:
+        eng.summary()
+    assert e.value.status == 5          # SB_ERR_STATE
+    eng.write_buffers(buf)
+    for bad in (1, 255, 257, 300, 1 << 19):
+        with pytest.raises(sb.EngineError) as e:
+            eng.summary(partials=bad)
+        assert e.value.status == 1      # SB_ERR_INVALID
+    row = torch.empty(32, dtype=torch.float32, device="cuda")
+    with pytest.raises(sb.EngineError) as e:
+        eng.summary(out=row.data_ptr() + 2)
+    assert e.value.status == 1
+    with pytest.raises(sb.EngineError) as e:
+        eng.summary(out=row, counts=row.data_ptr() + 4)
+    assert e.value.status == 1
+    import ctypes
+    L, vp = sb.engine.load_library(), ctypes.c_void_p
+    o = sb.engine.SbSummaryOptions()
+    for size, reserved in ((ctypes.sizeof(o) - 4, 0), (ctypes.sizeof(o) + 8, 0), (ctypes.sizeof(o), 7)):
+        o.struct_size, o.partials, o.reserved[5] = size, 0, reserved
+        assert L.sb_summary_device(eng._h, ctypes.byref(o), vp(row.data_ptr()), None) == 1, (size, reserved)
+        assert L.sb_summary(eng._h, ctypes.byref(o), vp(row.data_ptr()), None) == 1, (size, reserved)
+    assert L.sb_summary_device(eng._h, None, None, None) == 1                      # a NULL row
+    eng.summary(out=row)                # ... and the engine still works
+    eng.halo_configure([0, 1], [2, 3])
+    with pytest.raises(sb.EngineError) as e:
+        eng.summary()
+    assert e.value.status == 6          # SB_ERR_UNSUPPORTED
+    eng.destroy()
+
+
+def test_kernels_use_no_scratch(sb):
+    """0 spilled registers means no scratch; 256 VGPRs is where a kernel of 256 threads drops to one wave per SIMD (the deepest leaf
+    kernel, 16 leaves a thread with all their loads in flight, has 184)"""
+    case = sc.case_default(sb)
+    eng = engine(sb, case, collision_mode=OFF)
+    assert eng.info("summary_kernel_scratch_bytes") == 0
+    assert 0 < eng.info("summary_kernel_vgprs") <= 256
+    eng.summary()
+    assert eng.info("summary_table_build_us") > 0 and eng.info("summary_partials") == 256
+    eng.destroy()
+
+
+@needs_node
+def test_node_summary_equals_pythons(sb):
+    r = run_node("summary.gpu.test.js")
+    assert r["ok"], r
+    buf = sb.scenes.default_buffers(1, 128, 320)
+    eng = sb.Engine(bounds_size=1000.0, particle_radius=10.0, subticks=64, layout=1, max_particles=128, max_beams=320,
+                    collision_mode=OFF)
+    eng.write_buffers(buf)
+    eng.frame()
+    row, counts = eng.summary_host()
+    eng.destroy()
+    assert r["row"] == row.view(np.uint32).tolist(), json.dumps(r)
+    assert r["counts"] == [int(c) for c in counts] == r["workerCounts"]
