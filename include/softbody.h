@@ -212,6 +212,8 @@ sb_status sb_get_counts(sb_engine *e, uint32_t *particles, uint32_t *beams);
  * "summary_partials" (sb_summary: the partials the last call used), "summary_table_build_us" (host time of its last table build:
  * the first summary after an upload), "summary_kernel_vgprs" / "summary_kernel_scratch_bytes" (the most registers / scratch
  * bytes per lane over every kernel a summary may launch, as the runtime reports them; scratch must be 0),
+ * "bodies_table_build_us" (sb_bodies: host time of its last table build: the first call after an upload), "bodies_kernel_vgprs" /
+ * "bodies_kernel_scratch_bytes" (the same two figures over every kernel sb_bodies may launch; scratch must be 0),
  * "acc_dirty_tiles" / "plastic_tiles" (tiles whose zero-acceleration / never-yielded promise flag in the CURRENT state
  * buffer is nonzero; 0 on engines without tiles, "plastic_tiles" 0 without a blocked plan.  Both wait for the stream and
  * copy one word per tile to the host: for tests, never inside a timed region). */
@@ -465,6 +467,40 @@ typedef struct sb_summary_options {
 sb_status sb_summary_device(sb_engine *e, const sb_summary_options *opts, void *device_row_f32 /* [SB_SUMMARY_WORDS] float */,
                             void *device_counts_u64 /* [8] uint64 or NULL */);
 sb_status sb_summary(sb_engine *e, const sb_summary_options *opts, float *row /* [SB_SUMMARY_WORDS] */, uint64_t *counts /* [8] or NULL */);
+
+/* ---- the connected bodies of the whole scene, labelled on the device ----
+ * Is it still one piece, how many fragments, which is the largest -- without reading the scene back for a union-find on the host.
+ * The definition is sb_batch_bodies_device's (below), word for word: a BODY is a connected component of the graph whose nodes are
+ * the scene's particles and whose edges are its LIVE beams -- the caller's beam slots of the latest upload that neither a delete
+ * pass nor a plan-keeping upload that removed beams has removed (the "removed" of sb_load_buffers and of sb_summary's counts).
+ * A beam whose break flag is pending still connects.  Everything is indexed by particle DATA index (the rows of
+ * sb_read_state_device):
+ * labels [max_particles] int32: at index i the smallest data index of the body of particle i, -1 where no particle lives --
+ *     for every index up to max_particles; what torch.index_add_ takes for any statistic per body;
+ * sizes  [max_particles][2] int32: {particles, live beams} of the body labelled l in row l, {0, 0} in every other row;
+ * counts [SB_BODY_WORDS] int64 (like sb_summary's exact counts): bodies, particles of the largest body, bodies of one particle,
+ *     label of the largest body (among bodies of equal size the smallest label); a scene of no particles gives {0, 0, 0, -1}.
+ * Each output may be NULL (not all three); every word of a non-NULL output is written.  The outputs are integers and the
+ * definition names no schedule: they are identical on every run.
+ * sb_bodies_device only ENQUEUES on the engine's stream and writes device memory, which must stay valid until that work has
+ * run; nothing is read back to the host to decide anything (a lock-free union-find in global memory: no cooperative launch, no
+ * grid-wide barrier, no workgroup waits for another).  sb_bodies WAITS and copies to the host.  The first call after an upload
+ * builds its tables on the host and waits for the stream once, as the first summary does; later ones only enqueue.  Which
+ * beams are live is read on the device at the call's place in the stream.  The call only reads the engine: positions, the
+ * spatial hash, the per-tile flags, the hybrid's schedule, the blocked plan and the pending break flags stay as they were.
+ * Errors: SB_ERR_INVALID for a NULL handle, three NULL outputs, labels or sizes that are not 4-byte or counts that are not
+ * 8-byte aligned, a struct_size that is neither 0 nor the struct's, a nonzero reserved word, a capacity above 2^31 -- all
+ * before anything touches a device; SB_ERR_STATE before an upload; SB_ERR_UNSUPPORTED on an engine with ghost zones or peers
+ * configured (bodies across ranks are not handled). */
+#define SB_BODY_WORDS 4u
+typedef struct sb_bodies_options {
+    uint32_t struct_size;    /* = sizeof(sb_bodies_options); 0 or a NULL pointer = all defaults */
+    uint32_t reserved[7];    /* zero */
+} sb_bodies_options;
+sb_status sb_bodies_device(sb_engine *e, const sb_bodies_options *opts, void *device_labels_i32 /* [max_particles] int32 or NULL */,
+                           void *device_sizes_i32 /* [max_particles][2] int32 or NULL */,
+                           void *device_counts_i64 /* [SB_BODY_WORDS] int64 or NULL */);
+sb_status sb_bodies(sb_engine *e, const sb_bodies_options *opts, int32_t *labels, int32_t *sizes, int64_t *counts);
 
 /* ---- batched small scenes: N independent scenes, one workgroup per scene, one launch per frame ----
  * A second object beside sb_engine, for the user who steps thousands of copies of a SMALL scene (a controller, an RL loop):

@@ -255,8 +255,8 @@ struct sb_engine {
     std::vector<std::pair<void *, size_t>> pool_used, pool_free; // device blocks of the scene / kept for the next upload (sb_api.hip dev_alloc)
 };
 
-// what sb_state_io.hip and sb_summary.hip keep between calls (sb_engine sio): tables of the scene of the latest upload, built at
-// the first export / the first summary after it (sb_write_buffers drops both through sbs_invalidate)
+// what sb_state_io.hip, sb_summary.hip and sb_bodies.hip keep between calls (sb_engine sio): tables of the scene of the latest
+// upload, built at the first export / summary / bodies call after it (sb_write_buffers drops them all through sbs_invalidate)
 struct SbStateIoState {
     bool valid = false;
     uint32_t nslots = 0;       // the caller's beam slots of the latest upload
@@ -273,6 +273,15 @@ struct SbStateIoState {
     size_t cap_sum_pinv = 0, cap_sum_bleaf = 0, cap_sum_part = 0, cap_sum_stat = 0, cap_sum_out = 0;
     uint32_t sum_partials = 0;      // sb_summary_options.partials as the last call resolved it ("summary_partials")
     double sum_build_ms = 0.0;
+    // sb_bodies.hip: the component search runs over particle DATA indices and the caller's beam slots
+    bool bod_valid = false;
+    uint32_t *d_bod_pinv = nullptr; // per particle data index < bod_np: its internal particle (0xFFFFFFFF: none)
+    uint32_t *d_bod_tab = nullptr;  // [3][bod_nslots]: per caller beam slot the data index of A, of B, the engine slot
+    uint32_t bod_np = 0, bod_nslots = 0; // highest particle data index in use + 1; the caller's beam slots
+    int32_t *d_bod_parent = nullptr, *d_bod_sizes = nullptr; // a call's parent words / sizes where the caller gave no device memory for them
+    unsigned long long *d_bod_acc = nullptr; // a call's accumulators (bodies, single bodies, key of the largest), then sb_bodies' counts
+    size_t cap_bod_pinv = 0, cap_bod_tab = 0, cap_bod_parent = 0, cap_bod_sizes = 0, cap_bod_acc = 0;
+    double bod_build_ms = 0.0;
 };
 
 inline void sb_set_error(sb_engine *e, const char *text) { if (e) e->err = text; else sb_set_create_error(text); } // (sb_error.h)
@@ -313,5 +322,7 @@ void sbs_invalidate(sb_engine *e);      // an upload replaced the scene: the nex
 void sbs_release(sb_engine *e);         // everything sb_state_io allocated (sb_destroy)
 // sb_summary.hip
 bool sbm_info(sb_engine *e, const char *key, uint64_t *value); // its sb_get_info keys (false: not one of them)
+// sb_bodies.hip
+bool sbd_info(sb_engine *e, const char *key, uint64_t *value); // its sb_get_info keys (false: not one of them)
 // sb_api.hip
 sb_status sb_grid_reset_hash(sb_engine *e); // the spatial hash forgets every position it holds (every upload, through reset_run_state; particle import)

@@ -78,6 +78,7 @@ static struct {
     sb_status (*get_stream)(sb_engine *, void **);
     sb_status (*render)(sb_engine *, const sb_render_options *, void *, size_t);
     sb_status (*summary)(sb_engine *, const sb_summary_options *, float *, uint64_t *);
+    sb_status (*bodies)(sb_engine *, const sb_bodies_options *, int32_t *, int32_t *, int64_t *);
     sb_status (*partition_create)(uint32_t, uint32_t, uint32_t, const void *, const void *, const void *, const void *, uint32_t,
                                   uint32_t, float, sb_partition **);
     sb_status (*partition_destroy)(sb_partition *);
@@ -178,6 +179,7 @@ static napi_value js_load(napi_env env, napi_callback_info info)
     SYM(get_stream, "sb_get_stream");
     SYM(render, "sb_render");
     SYM(summary, "sb_summary");
+    SYM(bodies, "sb_bodies");
     SYM(partition_create, "sb_partition_create");
     SYM(partition_destroy, "sb_partition_destroy");
     SYM(partition_rank_counts, "sb_partition_rank_counts");
@@ -1121,6 +1123,43 @@ static napi_value js_summary(napi_env env, napi_callback_info info)
     return obj;
 }
 
+/* bodies(handle, maxParticles) -> {labels: Int32Array(maxParticles), counts: [4 numbers]}: the connected bodies of the whole scene
+ * at particle data indices and the four count words (bodies, particles of the largest, bodies of one particle, label of the
+ * largest), labelled on the GPU by sb_bodies (which waits for the stream).  maxParticles: the capacity the engine was created with. */
+static napi_value js_bodies(napi_env env, napi_callback_info info)
+{
+    if (!need_lib(env)) return NULL;
+    size_t argc = 2;
+    napi_value argv[2];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    sb_engine *e = argc >= 1 ? get_engine(env, argv[0]) : NULL;
+    if (!e) return NULL;
+    double cap = -1.0;
+    if (argc >= 2) (void)napi_get_value_double(env, argv[1], &cap);
+    if (!(cap >= 0.0 && cap <= 2147483648.0) || cap != (double)(uint32_t)cap) {
+        napi_throw_range_error(env, NULL, "bodies: maxParticles must be the engine's particle capacity");
+        return NULL;
+    }
+    void *lab = NULL;
+    napi_value vlab = make_typed(env, napi_int32_array, (size_t)cap, 4, &lab);
+    if (!vlab) return NULL;
+    int32_t none = 0; /* (a capacity of 0: no array to write into, and sb_bodies refuses three NULL outputs) */
+    int64_t counts[SB_BODY_WORDS];
+    sb_status st = sb.bodies(e, NULL, cap > 0.0 ? (int32_t *)lab : &none, NULL, counts);
+    if (st != SB_OK) return throw_status(env, e, st, "sb_bodies");
+    napi_value obj, vcnt;
+    CHECK_NAPI(napi_create_object(env, &obj));
+    CHECK_NAPI(napi_create_array_with_length(env, SB_BODY_WORDS, &vcnt));
+    for (uint32_t i = 0; i < SB_BODY_WORDS; i++) {
+        napi_value v;
+        CHECK_NAPI(napi_create_double(env, (double)counts[i], &v));
+        CHECK_NAPI(napi_set_element(env, vcnt, i, v));
+    }
+    CHECK_NAPI(napi_set_named_property(env, obj, "labels", vlab));
+    CHECK_NAPI(napi_set_named_property(env, obj, "counts", vcnt));
+    return obj;
+}
+
 static napi_value init(napi_env env, napi_value exports)
 {
     static const struct { const char *name; napi_callback fn; } fns[] = {
@@ -1137,7 +1176,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"partitionCreate", js_partition_create}, {"partitionDestroy", js_partition_destroy},
         {"partitionRankCounts", js_partition_rank_counts}, {"partitionRankScene", js_partition_rank_scene},
         {"partitionRankIds", js_partition_rank_ids}, {"partitionPeer", js_partition_peer}, {"render", js_render},
-        {"summary", js_summary},
+        {"summary", js_summary}, {"bodies", js_bodies},
         {"partitionRankGuard", js_partition_rank_guard}, {"haloGuard", js_halo_guard}, {"haloGuardStatus", js_halo_guard_status},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

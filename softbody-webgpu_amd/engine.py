@@ -50,10 +50,17 @@ SUMMARY_COUNT_FIELDS = ("particles", "live_beams", "removed_beams", "pending_bre
                         "uploaded", "reserved_7")
 
 
+class SbBodiesOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 7)]
+
+
+BODY_WORDS = 4               # SB_BODY_WORDS: the int64 counts of bodies(); batch.BODY_FIELDS (engine.BODY_FIELDS) names them
+
+
 def __getattr__(name):
-    if name == "SUMMARY_FIELDS":  # the batch's row, word for word: its names are not copied (batch.py imports this module)
-        from .batch import SUMMARY_FIELDS
-        return SUMMARY_FIELDS
+    if name in ("SUMMARY_FIELDS", "BODY_FIELDS"):  # the batch's words: its names are not copied (batch.py imports this module)
+        from . import batch
+        return getattr(batch, name)
     raise AttributeError(name)
 
 
@@ -170,6 +177,8 @@ def load_library():
     L.sb_write_particles_device.argtypes = [vp, vp]
     L.sb_summary_device.argtypes = [vp, ctypes.POINTER(SbSummaryOptions), vp, vp]
     L.sb_summary.argtypes = [vp, ctypes.POINTER(SbSummaryOptions), vp, vp]
+    L.sb_bodies_device.argtypes = [vp, ctypes.POINTER(SbBodiesOptions), vp, vp, vp]
+    L.sb_bodies.argtypes = [vp, ctypes.POINTER(SbBodiesOptions), vp, vp, vp]
     f32 = ctypes.c_float
     L.sb_partition_create.argtypes = [u32, u32, u32, vp, vp, vp, vp, u32, u32, f32, ctypes.POINTER(vp)]
     L.sb_partition_destroy.argtypes = [vp]
@@ -521,6 +530,49 @@ class Engine:
         o = self._summary_options(partials)
         self._check(load_library().sb_summary(self._h, ctypes.byref(o), _ptr(row), _ptr(counts)))
         return row, counts
+
+    # ---- the connected bodies of the whole scene (sb_bodies_device / sb_bodies)
+
+    def bodies(self, labels=None, sizes=False, counts=True):
+        """The connected bodies of the scene: particles joined by LIVE beams (a pending break flag still connects; a beam removed
+        by a delete pass, or by a plan-keeping upload that removed beams, does not), labelled on the GPU.  Returns
+        (labels, counts), or (labels, counts, sizes) when sizes is asked for: torch tensors on the engine's device.  labels int32
+        [max_particles]: at particle DATA index i (the rows of state_tensors()["particles"]) the smallest data index of i's body, -1
+        where no particle lives -- what torch.index_add_ takes for a statistic per body.  counts int64 [4] (BODY_FIELDS names the
+        words): bodies, particles of the largest, bodies of one particle, label of the largest (the smallest label on a tie;
+        {0, 0, 0, -1} in a scene of no particles).  sizes int32 [max_particles, 2]: {particles, live beams} of the body at its
+        label's row, {0, 0} in every other row.  Each argument: None or True -- a new tensor; False -- left out (None is
+        returned in its place; not all three); a device pointer (int) or a contiguous torch tensor of that dtype and at least
+        that many elements to write into.  Every word of an output is written.  Only reads the engine, only enqueues; torch's
+        current stream is ordered after it."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        shapes = (("labels", labels, (self.max_particles,), "int32"), ("sizes", sizes, (self.max_particles, 2), "int32"),
+                  ("counts", counts, (BODY_WORDS,), "int64"))
+        outs, ptrs, tensors = [], [], False
+        for what, x, shape, dtype in shapes:
+            if x is False:
+                outs.append(None)
+                ptrs.append(None)
+                continue
+            if x is None or x is True:
+                x = torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
+            ptr, t = self._device_buffer("bodies: " + what, x, dtype, int(np.prod(shape)) * (8 if dtype == "int64" else 4))
+            outs.append(x)
+            ptrs.append(ptr)
+            tensors |= t
+        vp = ctypes.c_void_p
+        self._ordered(tensors, lambda: load_library().sb_bodies_device(self._h, None, vp(ptrs[0]), vp(ptrs[1]), vp(ptrs[2])))
+        return (outs[0], outs[2], outs[1]) if sizes is not False else (outs[0], outs[2])
+
+    def bodies_host(self):
+        """The same without torch: (labels int32 [max_particles], sizes int32 [max_particles, 2], counts int64 [4]) numpy arrays.
+        Waits for the stream."""
+        labels = np.empty(self.max_particles, dtype=np.int32)
+        sizes = np.empty((self.max_particles, 2), dtype=np.int32)
+        counts = np.empty(BODY_WORDS, dtype=np.int64)
+        self._check(load_library().sb_bodies(self._h, None, _ptr(labels), _ptr(sizes), _ptr(counts)))
+        return labels, sizes, counts
 
     def state_tensors(self):
         """New torch tensors of the current state: {"particles": (max_particles, 6) float32, "beams": (max_beams, 4) float32,

@@ -73,6 +73,8 @@ class WGPUSoftbodyEngine {
     async render(opts) { return this.worker.render(opts); }
     /** 24 statistics of the whole scene and their integer counts, reduced on the GPU (engineWorker.js summary) */
     async summary(opts) { return this.worker.summary(opts); }
+    /** the connected bodies of the whole scene: labels per particle data index and the four counts (engineWorker.js bodies) */
+    async bodies() { return this.worker.bodies(); }
     /** n frames back to back */
     async run(frames) { for (let i = 0; i < frames && this.running; i++) await this.frame(); }
 

@@ -131,6 +131,19 @@ class WGPUSoftbodyEngineWorker {
         });
     }
 
+    /**
+     * The connected bodies of the whole scene -- particles joined by live beams; a pending break flag still connects, a beam a
+     * delete pass removed does not -- labelled on the GPU (sb_bodies): no state travels to the host.
+     * @returns {labels: Int32Array(maxParticles), counts: [bodies, particles of the largest, bodies of one particle, label of the
+     *          largest]}; labels[i] is the smallest data index of the body of the particle at data index i, -1 where none lives
+     */
+    async bodies() {
+        return this.lock.run(() => {
+            if (!this.uploaded) throw new Error('bodies before writeBuffers');
+            return this.addon.bodies(this.handle, this.bufferMapper.maxParticles);
+        });
+    }
+
     /** benchmark granularity: n substeps, no delete pass; returns device milliseconds */
     async step(n) {
         return this.lock.run(() => this.addon.stepTimed(this.handle, n));

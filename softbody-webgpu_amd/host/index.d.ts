@@ -177,6 +177,8 @@ export class WGPUSoftbodyEngine {
     render(opts?: RenderOptions): Promise<Buffer>;
     /** 24 statistics of the whole scene (sb_summary's row) and its exact counts, reduced on the GPU */
     summary(opts?: SummaryOptions): Promise<SceneSummary>;
+    /** the connected bodies of the whole scene (sb_bodies), labelled on the GPU */
+    bodies(): Promise<SceneBodies>;
     run(frames: number): Promise<void>;
     destroy(): Promise<void>;
     readonly destroyed: boolean;
@@ -187,6 +189,9 @@ export interface SummaryOptions { partials?: number }
 /** row: the 24 words of sb_summary (include/softbody.h); counts: particles, live beams, removed beams, pending breaks, non-finite
  *  particles, non-finite beams, 1, 0 */
 export interface SceneSummary { row: Float32Array, counts: Float64Array }
+/** labels: per particle data index the smallest data index of its body, -1 where no particle lives; counts: bodies, particles of
+ *  the largest body, bodies of one particle, label of the largest body (-1 in a scene of no particles) */
+export interface SceneBodies { labels: Int32Array, counts: [number, number, number, number] }
 
 export class WGPUSoftbodyEngineWorker {
     static create(canvas: unknown | null, opts?: NativeEngineOptions, post?: (m: { type: number, data?: unknown }) => void): WGPUSoftbodyEngineWorker;
@@ -205,6 +210,8 @@ export class WGPUSoftbodyEngineWorker {
     render(opts?: RenderOptions): Promise<Buffer>;
     /** sb_summary: the row of 24 statistics of the whole scene and its 8 integer counts, reduced on the GPU without a read-back */
     summary(opts?: SummaryOptions): Promise<SceneSummary>;
+    /** sb_bodies: labels of the connected bodies per particle data index and the four counts, without a read-back of the scene */
+    bodies(): Promise<SceneBodies>;
     onMessage(msg: { type: WGPUSoftbodyEngineMessageTypes, data?: unknown }): Promise<void>;
     destroy(): Promise<void>;
 }
