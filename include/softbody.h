@@ -214,6 +214,9 @@ sb_status sb_get_counts(sb_engine *e, uint32_t *particles, uint32_t *beams);
  * bytes per lane over every kernel a summary may launch, as the runtime reports them; scratch must be 0),
  * "bodies_table_build_us" (sb_bodies: host time of its last table build: the first call after an upload), "bodies_kernel_vgprs" /
  * "bodies_kernel_scratch_bytes" (the same two figures over every kernel sb_bodies may launch; scratch must be 0),
+ * "contacts_table_build_us" (sb_contacts: host time of its last table build: the first call after an upload),
+ * "contacts_cells_per_side" (the cells per side its counting sort uses for the scene as it is now; 1: the all-pairs test),
+ * "contacts_kernel_vgprs" / "contacts_kernel_scratch_bytes" (the same two figures over every kernel sb_contacts may launch),
  * "acc_dirty_tiles" / "plastic_tiles" (tiles whose zero-acceleration / never-yielded promise flag in the CURRENT state
  * buffer is nonzero; 0 on engines without tiles, "plastic_tiles" 0 without a blocked plan.  Both wait for the stream and
  * copy one word per tile to the host: for tests, never inside a timed region). */
@@ -501,6 +504,51 @@ sb_status sb_bodies_device(sb_engine *e, const sb_bodies_options *opts, void *de
                            void *device_sizes_i32 /* [max_particles][2] int32 or NULL */,
                            void *device_counts_i64 /* [SB_BODY_WORDS] int64 or NULL */);
 sb_status sb_bodies(sb_engine *e, const sb_bodies_options *opts, int32_t *labels, int32_t *sizes, int64_t *counts);
+
+/* ---- particle and wall contacts of the whole scene, found on the device ----
+ * Who touches whom, and who touches a wall -- without reading the scene back for a grid on the host.  The definition is
+ * sb_batch_contacts_device's (below), word for word, for the one scene: particles are named by DATA index (the rows of
+ * sb_read_state_device), coordinates are the current particle records at the call's place in the stream, and two distinct
+ * particles i, j TOUCH iff dist == 0 or dist < particle_radius * 2, dist = length(xj - xi, yj - yi) in float -- the step's own
+ * test, so a pair exactly 2r apart is absent and one an ulp closer is present; a NaN or infinite distance is no contact.  The
+ * result depends on the positions alone: not on collision_mode, not on the path.  Wall bits are SB_BATCH_WALL_LEFT / _RIGHT /
+ * _LOW / _HIGH with lo = particle_radius, hi = bounds_size - particle_radius in float, compared with <= / >=; a NaN sets none.
+ * labels [max_particles] int32 or NULL: any partition of the particles (sb_bodies_device's labels, say); only ever compared.
+ * touch  [max_particles][SB_CONTACT_WORDS] int32: per data index {partners, partners of another label (-1 without labels), wall
+ *     bits, smallest partner (-1: none)}; {0, 0 or -1, 0, -1} where no particle lives, for every index up to max_particles;
+ * pairs  [max_pairs][2] int32: the touching pairs {i, j}, i < j, in ascending (i, j) order, the first max_pairs of them, {-1, -1}
+ *     behind the last; with SB_CONTACTS_OTHER_BODY only pairs whose labels differ, order and truncation the same;
+ * counts [SB_CONTACT_COUNT_WORDS] int64 (a dense scene exceeds 2^31 pairs): touching pairs (the true number, whatever max_pairs
+ *     is), pairs of different labels (-1 without labels), particles on a wall, particles that touch another.
+ * Each output may be NULL (not all three); every word of a non-NULL output is written.  Everything behind the float test is
+ * integers: the outputs are identical on every run.
+ * sb_contacts_device only ENQUEUES on the engine's stream and reads / writes device memory, which must stay valid until that
+ * work has run; nothing is read back to decide anything, and no workgroup waits for another (a counting sort by cell in global
+ * memory).  sb_contacts WAITS and copies to / from the host.  The first call after an upload builds its table on the host and
+ * waits for the stream once; later ones only enqueue.  The call only reads the engine: positions, the spatial hash and its
+ * decision state, the per-tile flags, the hybrid's schedule and the blocked plan stay as they were.  Cost: the sum over the
+ * particles of the population of their 3 x 3 cells (cells at least 2r (1 + 1/64) wide over [0, bounds]^2, at most about eight a
+ * particle); a scene crowded into one cell is quadratic, as it is in the step.
+ * Errors: SB_ERR_INVALID for a NULL handle, a struct_size that is neither 0 nor the struct's, an unknown flag bit, a nonzero
+ * reserved word, SB_CONTACTS_OTHER_BODY without labels, three NULL outputs, max_pairs > 0 with NULL pairs, labels, touch or pairs
+ * that are not 4-byte or counts that are not 8-byte aligned, max_pairs above 2^31 -- all before anything touches a device;
+ * SB_ERR_STATE before an upload; SB_ERR_UNSUPPORTED on an engine with ghost zones or peers configured, and where the cell side
+ * is no ordinary number (a radius or bounds that are zero, NaN, infinite, beyond 2^+-60) in a scene of more than 4096 particles
+ * (at or below 4096 every pair is tested, as the batch does). */
+#define SB_CONTACT_WORDS 4u            /* words of a touch row (SB_BATCH_CONTACT_WORDS) */
+#define SB_CONTACT_COUNT_WORDS 4u      /* int64 words of counts */
+#define SB_CONTACTS_OTHER_BODY 1u      /* the pair list holds only pairs whose particles carry different labels */
+typedef struct sb_contacts_options {
+    uint32_t struct_size;    /* = sizeof(sb_contacts_options); 0 or a NULL pointer = all defaults: no flags, max_pairs 0 */
+    uint32_t flags;          /* SB_CONTACTS_OTHER_BODY */
+    uint64_t max_pairs;      /* rows of `pairs`; 0: no list */
+    uint32_t reserved[4];    /* zero */
+} sb_contacts_options;
+sb_status sb_contacts_device(sb_engine *e, const sb_contacts_options *opts, const void *device_labels_i32 /* [max_particles] or NULL */,
+                             void *device_touch_i32 /* [max_particles][SB_CONTACT_WORDS] or NULL */,
+                             void *device_pairs_i32 /* [max_pairs][2] or NULL */,
+                             void *device_counts_i64 /* [SB_CONTACT_COUNT_WORDS] or NULL */);
+sb_status sb_contacts(sb_engine *e, const sb_contacts_options *opts, const int32_t *labels, int32_t *touch, int32_t *pairs, int64_t *counts);
 
 /* ---- batched small scenes: N independent scenes, one workgroup per scene, one launch per frame ----
  * A second object beside sb_engine, for the user who steps thousands of copies of a SMALL scene (a controller, an RL loop):

@@ -255,8 +255,10 @@ struct sb_engine {
     std::vector<std::pair<void *, size_t>> pool_used, pool_free; // device blocks of the scene / kept for the next upload (sb_api.hip dev_alloc)
 };
 
-// what sb_state_io.hip, sb_summary.hip and sb_bodies.hip keep between calls (sb_engine sio): tables of the scene of the latest
-// upload, built at the first export / summary / bodies call after it (sb_write_buffers drops them all through sbs_invalidate)
+// what sb_state_io.hip, sb_summary.hip, sb_bodies.hip and sb_contacts.hip keep between calls (sb_engine sio): tables of the scene
+// of the latest upload, built at the first export / summary / bodies / contacts call after it (sb_write_buffers drops them all
+// through sbs_invalidate)
+#define SB_CONTACTS_BUFFERS 10
 struct SbStateIoState {
     bool valid = false;
     uint32_t nslots = 0;       // the caller's beam slots of the latest upload
@@ -282,6 +284,12 @@ struct SbStateIoState {
     unsigned long long *d_bod_acc = nullptr; // a call's accumulators (bodies, single bodies, key of the largest), then sb_bodies' counts
     size_t cap_bod_pinv = 0, cap_bod_tab = 0, cap_bod_parent = 0, cap_bod_sizes = 0, cap_bod_acc = 0;
     double bod_build_ms = 0.0;
+    // sb_contacts.hip: its own data index -> internal particle table, and the scratch of a call, by use (its SBC_M_* enum)
+    bool con_valid = false;
+    uint32_t con_np = 0, con_P = 0; // highest particle data index in use + 1; particles
+    void *d_con[SB_CONTACTS_BUFFERS] = {};
+    size_t cap_con[SB_CONTACTS_BUFFERS] = {}; // bytes
+    double con_build_ms = 0.0;
 };
 
 inline void sb_set_error(sb_engine *e, const char *text) { if (e) e->err = text; else sb_set_create_error(text); } // (sb_error.h)
@@ -324,5 +332,7 @@ void sbs_release(sb_engine *e);         // everything sb_state_io allocated (sb_
 bool sbm_info(sb_engine *e, const char *key, uint64_t *value); // its sb_get_info keys (false: not one of them)
 // sb_bodies.hip
 bool sbd_info(sb_engine *e, const char *key, uint64_t *value); // its sb_get_info keys (false: not one of them)
+// sb_contacts.hip
+bool sbc_info(sb_engine *e, const char *key, uint64_t *value); // its sb_get_info keys (false: not one of them)
 // sb_api.hip
 sb_status sb_grid_reset_hash(sb_engine *e); // the spatial hash forgets every position it holds (every upload, through reset_run_state; particle import)

@@ -79,6 +79,7 @@ static struct {
     sb_status (*render)(sb_engine *, const sb_render_options *, void *, size_t);
     sb_status (*summary)(sb_engine *, const sb_summary_options *, float *, uint64_t *);
     sb_status (*bodies)(sb_engine *, const sb_bodies_options *, int32_t *, int32_t *, int64_t *);
+    sb_status (*contacts)(sb_engine *, const sb_contacts_options *, const int32_t *, int32_t *, int32_t *, int64_t *);
     sb_status (*partition_create)(uint32_t, uint32_t, uint32_t, const void *, const void *, const void *, const void *, uint32_t,
                                   uint32_t, float, sb_partition **);
     sb_status (*partition_destroy)(sb_partition *);
@@ -180,6 +181,7 @@ static napi_value js_load(napi_env env, napi_callback_info info)
     SYM(render, "sb_render");
     SYM(summary, "sb_summary");
     SYM(bodies, "sb_bodies");
+    SYM(contacts, "sb_contacts");
     SYM(partition_create, "sb_partition_create");
     SYM(partition_destroy, "sb_partition_destroy");
     SYM(partition_rank_counts, "sb_partition_rank_counts");
@@ -1160,6 +1162,54 @@ static napi_value js_bodies(napi_env env, napi_callback_info info)
     return obj;
 }
 
+/* contacts(handle, maxParticles, maxPairs) -> {touch: Int32Array(4 * maxParticles), counts: [4 numbers], pairs: Int32Array(2 *
+ * maxPairs)}: per particle data index {partners, -1 (no labels), wall bits, smallest partner}, the four count words (touching
+ * pairs, -1, particles on a wall, particles touching another) and the first maxPairs pairs {i, j}, i < j, ascending, {-1, -1} behind
+ * the last, found on the GPU by sb_contacts (which waits for the stream).  maxParticles: the capacity the engine was created with. */
+static napi_value js_contacts(napi_env env, napi_callback_info info)
+{
+    if (!need_lib(env)) return NULL;
+    size_t argc = 3;
+    napi_value argv[3];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    sb_engine *e = argc >= 1 ? get_engine(env, argv[0]) : NULL;
+    if (!e) return NULL;
+    double cap = -1.0, want = 0.0;
+    if (argc >= 2) (void)napi_get_value_double(env, argv[1], &cap);
+    if (argc >= 3) (void)napi_get_value_double(env, argv[2], &want);
+    if (!(cap >= 0.0 && cap <= 2147483648.0) || cap != (double)(uint32_t)cap) {
+        napi_throw_range_error(env, NULL, "contacts: maxParticles must be the engine's particle capacity");
+        return NULL;
+    }
+    if (!(want >= 0.0 && want <= 268435456.0) || want != (double)(uint32_t)want) {
+        napi_throw_range_error(env, NULL, "contacts: pairs must be a whole number of pairs, at most 2^28");
+        return NULL;
+    }
+    void *touch = NULL, *pairs = NULL;
+    napi_value vtouch = make_typed(env, napi_int32_array, (size_t)cap * SB_CONTACT_WORDS, 4, &touch);
+    napi_value vpairs = make_typed(env, napi_int32_array, (size_t)want * 2, 4, &pairs);
+    if (!vtouch || !vpairs) return NULL;
+    sb_contacts_options o;
+    memset(&o, 0, sizeof o);
+    o.struct_size = (uint32_t)sizeof o;
+    o.max_pairs = (uint64_t)want;
+    int64_t counts[SB_CONTACT_COUNT_WORDS];
+    sb_status st = sb.contacts(e, &o, NULL, cap > 0.0 ? (int32_t *)touch : NULL, want > 0.0 ? (int32_t *)pairs : NULL, counts);
+    if (st != SB_OK) return throw_status(env, e, st, "sb_contacts");
+    napi_value obj, vcnt;
+    CHECK_NAPI(napi_create_object(env, &obj));
+    CHECK_NAPI(napi_create_array_with_length(env, SB_CONTACT_COUNT_WORDS, &vcnt));
+    for (uint32_t i = 0; i < SB_CONTACT_COUNT_WORDS; i++) {
+        napi_value v;
+        CHECK_NAPI(napi_create_double(env, (double)counts[i], &v));
+        CHECK_NAPI(napi_set_element(env, vcnt, i, v));
+    }
+    CHECK_NAPI(napi_set_named_property(env, obj, "touch", vtouch));
+    CHECK_NAPI(napi_set_named_property(env, obj, "counts", vcnt));
+    CHECK_NAPI(napi_set_named_property(env, obj, "pairs", vpairs));
+    return obj;
+}
+
 static napi_value init(napi_env env, napi_value exports)
 {
     static const struct { const char *name; napi_callback fn; } fns[] = {
@@ -1176,7 +1226,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"partitionCreate", js_partition_create}, {"partitionDestroy", js_partition_destroy},
         {"partitionRankCounts", js_partition_rank_counts}, {"partitionRankScene", js_partition_rank_scene},
         {"partitionRankIds", js_partition_rank_ids}, {"partitionPeer", js_partition_peer}, {"render", js_render},
-        {"summary", js_summary}, {"bodies", js_bodies},
+        {"summary", js_summary}, {"bodies", js_bodies}, {"contacts", js_contacts},
         {"partitionRankGuard", js_partition_rank_guard}, {"haloGuard", js_halo_guard}, {"haloGuardStatus", js_halo_guard_status},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

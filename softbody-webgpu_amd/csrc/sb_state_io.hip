@@ -74,7 +74,7 @@ __global__ __launch_bounds__(SBS_BLOCK) void k_state_import_particles(const floa
 
 void sbs_invalidate(sb_engine *e)
 {
-    if (e && e->sio) e->sio->valid = e->sio->sum_valid = e->sio->bod_valid = false;
+    if (e && e->sio) e->sio->valid = e->sio->sum_valid = e->sio->bod_valid = e->sio->con_valid = false;
 }
 
 void sbs_release(sb_engine *e)
@@ -83,6 +83,8 @@ void sbs_release(sb_engine *e)
     void *ps[] = {e->sio->d_slot, e->sio->d_sum_pinv, e->sio->d_sum_bleaf, e->sio->d_sum_part, e->sio->d_sum_stat, e->sio->d_sum_out,
                   e->sio->d_bod_pinv, e->sio->d_bod_tab, e->sio->d_bod_parent, e->sio->d_bod_sizes, e->sio->d_bod_acc};
     for (void *p : ps)
+        if (p) (void)hipFree(p);
+    for (void *p : e->sio->d_con)
         if (p) (void)hipFree(p);
     delete e->sio;
     e->sio = nullptr;

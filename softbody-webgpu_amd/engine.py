@@ -57,8 +57,19 @@ class SbBodiesOptions(ctypes.Structure):
 BODY_WORDS = 4               # SB_BODY_WORDS: the int64 counts of bodies(); batch.BODY_FIELDS (engine.BODY_FIELDS) names them
 
 
+class SbContactsOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("max_pairs", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint32 * 4)]
+
+
+CONTACT_WORDS = 4            # SB_CONTACT_WORDS: the int32 words of a touch row; batch.CONTACT_TOUCH_FIELDS names them
+CONTACT_COUNT_WORDS = 4      # SB_CONTACT_COUNT_WORDS: the int64 counts of contacts(); batch.CONTACT_COUNT_FIELDS names them
+CONTACTS_OTHER_BODY = 1      # SB_CONTACTS_OTHER_BODY
+
+
 def __getattr__(name):
-    if name in ("SUMMARY_FIELDS", "BODY_FIELDS"):  # the batch's words: its names are not copied (batch.py imports this module)
+    if name in ("SUMMARY_FIELDS", "BODY_FIELDS", "CONTACT_TOUCH_FIELDS", "CONTACT_COUNT_FIELDS", "WALL_LEFT", "WALL_RIGHT", "WALL_LOW",
+                "WALL_HIGH"):  # the batch's words: its names are not copied (batch.py imports this module)
         from . import batch
         return getattr(batch, name)
     raise AttributeError(name)
@@ -179,6 +190,8 @@ def load_library():
     L.sb_summary.argtypes = [vp, ctypes.POINTER(SbSummaryOptions), vp, vp]
     L.sb_bodies_device.argtypes = [vp, ctypes.POINTER(SbBodiesOptions), vp, vp, vp]
     L.sb_bodies.argtypes = [vp, ctypes.POINTER(SbBodiesOptions), vp, vp, vp]
+    L.sb_contacts_device.argtypes = [vp, ctypes.POINTER(SbContactsOptions), vp, vp, vp, vp]
+    L.sb_contacts.argtypes = [vp, ctypes.POINTER(SbContactsOptions), vp, vp, vp, vp]
     f32 = ctypes.c_float
     L.sb_partition_create.argtypes = [u32, u32, u32, vp, vp, vp, vp, u32, u32, f32, ctypes.POINTER(vp)]
     L.sb_partition_destroy.argtypes = [vp]
@@ -573,6 +586,92 @@ class Engine:
         counts = np.empty(BODY_WORDS, dtype=np.int64)
         self._check(load_library().sb_bodies(self._h, None, _ptr(labels), _ptr(sizes), _ptr(counts)))
         return labels, sizes, counts
+
+    # ---- particle and wall contacts of the whole scene (sb_contacts_device / sb_contacts)
+
+    @staticmethod
+    def _contacts_options(max_pairs, other_body):
+        o = SbContactsOptions()
+        o.struct_size = ctypes.sizeof(SbContactsOptions)
+        o.flags = CONTACTS_OTHER_BODY if other_body else 0
+        o.max_pairs = int(max_pairs)
+        return o
+
+    def contacts(self, labels=None, pairs=0, other_body=False, touch=True, counts=True, out=None):
+        """Who touches whom, and who touches a wall, in the whole scene, found on the GPU.  Two particles touch iff the next
+        substep's collision loop would act on them (dist == 0 or dist < 2 * particle_radius in the library's float arithmetic); the
+        answer is the same in every collision_mode and on every path.  Returns (touch, counts), or (touch, counts, pairs) when a
+        pair list is asked for: torch tensors on the engine's device.  touch int32 [max_particles, 4] at particle DATA indices
+        (CONTACT_TOUCH_FIELDS names the columns): particles touching i, those of them whose label differs from i's (-1 without
+        labels), the wall bits (WALL_LEFT x <= r, WALL_RIGHT x >= bounds - r, WALL_LOW y <= r, WALL_HIGH y >= bounds - r), the
+        smallest data index touching i (-1: none); a row where no particle lives is (0, 0 or -1, 0, -1).  counts int64 [4]
+        (CONTACT_COUNT_FIELDS): touching pairs (the true number, however short the list), pairs of different labels (-1 without
+        labels), particles on a wall, particles touching another.  pairs int32 [n, 2]: the pairs (i, j), i < j, in ascending
+        order of (i, j), the first n of them, (-1, -1) behind the last; with other_body=True only pairs of different labels.
+        labels: None, True (self.bodies() is called first, on the same stream, and its labels are used), or an int32 tensor /
+        device pointer of [max_particles] labels of the caller's own, which are only compared with each other.  pairs: 0 / None
+        = no list; n = a list of n pairs (a new tensor, or `out`: a device pointer or a contiguous int32 tensor of at least
+        2 n elements to write into); or such a tensor itself, n = its pairs.  touch / counts: None or True -- a new tensor;
+        False -- left out (None is returned in its place); a device pointer (int) or a contiguous torch tensor of that dtype
+        and at least that many elements to write into.  Every word of an output is written.  Only reads the engine, only
+        enqueues; torch's current stream is ordered after it."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        maxp = self.max_particles
+        if isinstance(pairs, torch.Tensor):
+            if out is not None:
+                raise ValueError("contacts: pairs is a tensor to write into, and so is out")
+            out, pairs = pairs, pairs.numel() // 2
+        elif pairs is None:
+            pairs = 0
+        if isinstance(pairs, bool) or not isinstance(pairs, (int, np.integer)) or pairs < 0:
+            raise ValueError("contacts: pairs is a number of pairs or an int32 torch tensor, not %r" % (pairs,))
+        max_pairs = int(pairs)
+        if out is not None and max_pairs == 0:
+            raise ValueError("contacts: out needs a pair list (pairs > 0)")
+        if labels is True:
+            labels = self.bodies(counts=False)[0]
+        elif labels is False:
+            labels = None
+        shapes = (("touch", touch, (maxp, CONTACT_WORDS), "int32"), ("counts", counts, (CONTACT_COUNT_WORDS,), "int64"),
+                  ("pairs", out if max_pairs else False, (max_pairs, 2), "int32"))
+        outs, ptrs, tensors = [], [], False
+        for what, x, shape, dtype in shapes:
+            if x is False:
+                outs.append(None)
+                ptrs.append(None)
+                continue
+            if x is None or x is True:
+                x = torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
+            ptr, t = self._device_buffer("contacts: " + what, x, dtype, int(np.prod(shape)) * (8 if dtype == "int64" else 4))
+            outs.append(x)
+            ptrs.append(ptr)
+            tensors |= t
+        lab = None
+        if labels is not None:
+            lab, t = self._device_buffer("contacts: labels", labels, "int32", maxp * 4)
+            tensors |= t
+        o = self._contacts_options(max_pairs, other_body)
+        vp = ctypes.c_void_p
+        self._ordered(tensors, lambda: load_library().sb_contacts_device(self._h, ctypes.byref(o), vp(lab), vp(ptrs[0]), vp(ptrs[2]),
+                                                                         vp(ptrs[1])))
+        return (outs[0], outs[1], outs[2]) if max_pairs > 0 else (outs[0], outs[1])
+
+    def contacts_host(self, labels=None, pairs=0, other_body=False):
+        """The same without torch: (touch int32 [max_particles, 4], counts int64 [4], pairs int32 [pairs, 2]) numpy arrays; labels:
+        None or an int32 array of [max_particles] labels.  Waits for the stream."""
+        touch = np.empty((self.max_particles, CONTACT_WORDS), dtype=np.int32)
+        counts = np.empty(CONTACT_COUNT_WORDS, dtype=np.int64)
+        plist = np.empty((int(pairs), 2), dtype=np.int32)
+        lab = None
+        if labels is not None:
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.size < self.max_particles:
+                raise ValueError("contacts_host: labels needs max_particles entries")
+        o = self._contacts_options(pairs, other_body)
+        self._check(load_library().sb_contacts(self._h, ctypes.byref(o), None if lab is None else _ptr(lab), _ptr(touch),
+                                               _ptr(plist) if int(pairs) else None, _ptr(counts)))
+        return touch, counts, plist
 
     def state_tensors(self):
         """New torch tensors of the current state: {"particles": (max_particles, 6) float32, "beams": (max_beams, 4) float32,

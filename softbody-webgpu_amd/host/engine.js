@@ -75,6 +75,8 @@ class WGPUSoftbodyEngine {
     async summary(opts) { return this.worker.summary(opts); }
     /** the connected bodies of the whole scene: labels per particle data index and the four counts (engineWorker.js bodies) */
     async bodies() { return this.worker.bodies(); }
+    /** who touches whom and who touches a wall in the whole scene: touch rows, counts, optional pair list (engineWorker.js contacts) */
+    async contacts(opts) { return this.worker.contacts(opts); }
     /** n frames back to back */
     async run(frames) { for (let i = 0; i < frames && this.running; i++) await this.frame(); }
 

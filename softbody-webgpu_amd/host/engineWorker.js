@@ -144,6 +144,21 @@ class WGPUSoftbodyEngineWorker {
         });
     }
 
+    /**
+     * Who touches whom, and who touches a wall, in the whole scene -- two particles touch iff the next substep's collision loop
+     * would act on them -- found on the GPU (sb_contacts): no state travels to the host.
+     * @param opts {pairs: rows of the pair list to return (default 0: none)}
+     * @returns {touch: Int32Array(4 * maxParticles), counts: [pairs, -1, particles on a wall, particles touching another],
+     *          pairs: Int32Array(2 * opts.pairs)}; touch holds per particle data index {partners, -1, wall bits, smallest
+     *          partner or -1}; pairs the first opts.pairs pairs {i, j}, i < j, ascending, {-1, -1} behind the last
+     */
+    async contacts(opts) {
+        return this.lock.run(() => {
+            if (!this.uploaded) throw new Error('contacts before writeBuffers');
+            return this.addon.contacts(this.handle, this.bufferMapper.maxParticles, (opts && opts.pairs) || 0);
+        });
+    }
+
     /** benchmark granularity: n substeps, no delete pass; returns device milliseconds */
     async step(n) {
         return this.lock.run(() => this.addon.stepTimed(this.handle, n));

@@ -179,6 +179,8 @@ export class WGPUSoftbodyEngine {
     summary(opts?: SummaryOptions): Promise<SceneSummary>;
     /** the connected bodies of the whole scene (sb_bodies), labelled on the GPU */
     bodies(): Promise<SceneBodies>;
+    /** particle and wall contacts of the whole scene (sb_contacts), found on the GPU */
+    contacts(opts?: ContactsOptions): Promise<SceneContacts>;
     run(frames: number): Promise<void>;
     destroy(): Promise<void>;
     readonly destroyed: boolean;
@@ -192,6 +194,10 @@ export interface SceneSummary { row: Float32Array, counts: Float64Array }
 /** labels: per particle data index the smallest data index of its body, -1 where no particle lives; counts: bodies, particles of
  *  the largest body, bodies of one particle, label of the largest body (-1 in a scene of no particles) */
 export interface SceneBodies { labels: Int32Array, counts: [number, number, number, number] }
+export interface ContactsOptions { pairs?: number }
+/** touch: per particle data index {partners, -1, wall bits, smallest partner or -1}; counts: touching pairs, -1 (no labels), particles
+ *  on a wall, particles touching another; pairs: the first `pairs` pairs {i, j}, i < j, ascending, {-1, -1} behind the last */
+export interface SceneContacts { touch: Int32Array, counts: [number, number, number, number], pairs: Int32Array }
 
 export class WGPUSoftbodyEngineWorker {
     static create(canvas: unknown | null, opts?: NativeEngineOptions, post?: (m: { type: number, data?: unknown }) => void): WGPUSoftbodyEngineWorker;
@@ -212,6 +218,8 @@ export class WGPUSoftbodyEngineWorker {
     summary(opts?: SummaryOptions): Promise<SceneSummary>;
     /** sb_bodies: labels of the connected bodies per particle data index and the four counts, without a read-back of the scene */
     bodies(): Promise<SceneBodies>;
+    /** sb_contacts: touch rows per particle data index, the four counts and an optional pair list, without a read-back of the scene */
+    contacts(opts?: ContactsOptions): Promise<SceneContacts>;
     onMessage(msg: { type: WGPUSoftbodyEngineMessageTypes, data?: unknown }): Promise<void>;
     destroy(): Promise<void>;
 }
