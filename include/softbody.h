@@ -217,6 +217,10 @@ sb_status sb_get_counts(sb_engine *e, uint32_t *particles, uint32_t *beams);
  * "contacts_table_build_us" (sb_contacts: host time of its last table build: the first call after an upload),
  * "contacts_cells_per_side" (the cells per side its counting sort uses for the scene as it is now; 1: the all-pairs test),
  * "contacts_kernel_vgprs" / "contacts_kernel_scratch_bytes" (the same two figures over every kernel sb_contacts may launch),
+ * "body_summary_table_build_us" (sb_body_summary: host time of its last table build: the first call after an upload),
+ * "body_summary_scratch_bytes" (device bytes its calls hold so far: scratch, labels, its two tables, sb_body_summary's result),
+ * "body_summary_kernel_vgprs" /
+ * "body_summary_kernel_scratch_bytes" (the same two figures over every kernel sb_body_summary may launch; scratch must be 0),
  * "acc_dirty_tiles" / "plastic_tiles" (tiles whose zero-acceleration / never-yielded promise flag in the CURRENT state
  * buffer is nonzero; 0 on engines without tiles, "plastic_tiles" 0 without a blocked plan.  Both wait for the stream and
  * copy one word per tile to the host: for tests, never inside a timed region). */
@@ -549,6 +553,79 @@ sb_status sb_contacts_device(sb_engine *e, const sb_contacts_options *opts, cons
                              void *device_pairs_i32 /* [max_pairs][2] or NULL */,
                              void *device_counts_i64 /* [SB_CONTACT_COUNT_WORDS] or NULL */);
 sb_status sb_contacts(sb_engine *e, const sb_contacts_options *opts, const int32_t *labels, int32_t *touch, int32_t *pairs, int64_t *counts);
+
+/* ---- statistics per body of the whole scene, reproducible bit for bit, on the device ----
+ * "Follow the largest fragment", "where did the piece that broke off go", "how fast does each piece move" -- one row of
+ * SB_BODY_SUMMARY_WORDS floats per GROUP of particles, without exporting the state.  The definition is
+ * sb_batch_body_summary_device's (below), word for word, for the one scene:
+ * Groups: labels[i] is read at every particle DATA index i at which a particle lives (never elsewhere).  A value g with
+ *   0 <= g < max_particles puts particle i into group g; any other value (-1, negative, too large) into no group.  labels == NULL
+ *   means the engine's own bodies: the call first runs sb_bodies_device's labelling into memory of the engine's, on the same stream,
+ *   and nothing waits.  Any partition will do (limbs, stripes): nothing assumes connectivity.  A LIVE beam -- sb_bodies' sense: a
+ *   caller's beam slot of the latest upload that neither a delete pass nor a plan-keeping upload removed -- belongs to group g iff
+ *   BOTH its endpoints are in g; with body labels that is every live beam.  Pending flags (one per beam SLOT flagged since the last
+ *   delete pass) and FINITE (a particle whose six floats are finite, a live beam whose strain and stress are) are sb_summary's.
+ * Ranking: the non-empty groups are ranked by particles descending, then label ascending (the key by which sb_bodies names the
+ *   largest body).  rows[k] is the group of rank k, k < max_rows; rows behind the last group are the EMPTY ROW.  rank[i] is the
+ *   rank of particle i's group, however large -- a value >= max_rows means that its row was cut; -1 marks a data index that holds
+ *   no particle, or a particle in no group, for every index up to max_particles.  Every word of a non-NULL output is written.
+ * Row (words 4 .. 18 mean what they mean in a row of sb_summary_device, restricted to the group):
+ *    0  particles of the group (finite or not)       1  live beams of the group
+ *    2  the label                                    3  break flags pending among the group's live beam slots
+ *    4  particles of the group that are not finite   5  live beams of the group that are not finite
+ *    6, 7  mean position x, y                        8, 9  mean velocity x, y           (over the group's finite particles)
+ *   10 .. 13  min x, min y, max x, max y             (over the group's finite particles)
+ *   14  kinetic energy, the sum of 0.5 (vx^2 + vy^2)    15  max of vx^2 + vy^2          (over the group's finite particles)
+ *   16, 17, 18  max strain, max stress, min stress   (over the group's finite beams)
+ *   19  angular momentum about the origin, the sum of x vy - y vx                       (over the group's finite particles)
+ *   20 .. 23  0
+ * Over an empty set a mean or an extreme is the quiet NaN 0x7FC00000; counts, word 14 and word 19 are 0.  The EMPTY ROW: words
+ * 0, 1, 3, 4, 5, 14, 19 .. 23 are 0, word 2 is -1, the others NaN.  A scene without particles gives empty rows and rank -1.
+ * Words 0 .. 5 are (float) of integers, and an engine can exceed 2^24: rows_i64[k] holds them exactly, SB_BODY_SUMMARY_COUNT_WORDS
+ * int64 per row -- particles, live beams, label, pending flags, non-finite particles, non-finite beams, finite particles, 0; the
+ * empty row is {0, 0, -1, 0, 0, 0, 0, 0}.
+ * The sums are pinned, and the pin is sb_summary's: the sum of a group is what that call's tree gives for a scene that holds only
+ * the group's finite particles at their data indices -- in double; leaf i is the value at DATA index i if particle i is finite and
+ * in the group, else +0.0; i = 0 .. W-1, W the smallest power of two >= max_particles; for h = W/2 .. 1: s[i] += s[i + h].  The
+ * energy leaf is 0.5 * ((double)vx * vx + (double)vy * vy), the candidate of word 15 the same without the 0.5; the
+ * angular-momentum leaf is (double)x * vy - (double)y * vx (both products are exact in double: one rounding).  A mean is
+ * (float)(sum / (double)finite_count); words 14 and 19 are rounded to float once.  ONE addition to the pin: a sum that is zero is
+ * written as +0.0 (the masked tree gives that in every case but a group that fills all W leaves with -0.0).  Extremes compare
+ * sb_summary's ordered integer keys from the first comparison on: -0.0 sorts below +0.0, and which zero comes back does not
+ * depend on the schedule.  So a row is the same bits on every run.
+ * Consequences: for a scene that is ONE body, row 0's words 0, 1, 3 .. 18 equal sb_summary_device's words by their bits; for a
+ * scene that also fits an sb_batch the rows are sb_batch_body_summary_device's (counts and sums by their bits, extremes by value:
+ * the batch may return either zero).
+ * sb_body_summary_device only ENQUEUES on the engine's stream and reads / writes device memory, which must stay valid until that
+ * work has run; nothing is read back to decide anything and no workgroup waits for another (a stable radix sort of the members
+ * by label and a segmented tree in global memory, one launch per stage and level; the number of groups is read on the device).
+ * sb_body_summary WAITS and copies to / from the host.  The first call after an upload builds its tables on the host and waits
+ * for the stream once; later ones only enqueue.  Which beams are live is read on the device at the call's place in the stream.
+ * The call only reads the engine.  Scratch grows on demand: 137 bytes per data index up to the highest in use, rounded up to a
+ * power of two, and 4 bytes per particle of capacity where the labels are the engine's own (sb_get_info
+ * "body_summary_scratch_bytes": what the calls so far hold on the device, with the call's two tables: 4 bytes per data index
+ * in use and 16 bytes per caller beam slot).
+ * sb_body_summary_options.max_rows: 1 .. max_particles; a NULL pointer or struct_size 0 = SB_BODY_SUMMARY_DEFAULT_ROWS rows (at
+ * most max_particles).
+ * Errors: SB_ERR_INVALID for a NULL handle, three NULL outputs, max_rows of 0 or above max_particles (so also rows non-NULL with
+ * max_rows == 0), labels, rows or rank that are not 4-byte or rows_i64 that is not 8-byte aligned, a struct_size that is neither 0
+ * nor the struct's, a nonzero reserved word, a capacity above 2^31 -- all before anything touches a device; SB_ERR_STATE before
+ * an upload; SB_ERR_UNSUPPORTED on an engine with ghost zones or peers configured (bodies across ranks are not handled). */
+#define SB_BODY_SUMMARY_WORDS 24u          /* floats of a row (SB_BATCH_BODY_SUMMARY_WORDS) */
+#define SB_BODY_SUMMARY_COUNT_WORDS 8u     /* int64 words of a row of rows_i64 */
+#define SB_BODY_SUMMARY_DEFAULT_ROWS 8u
+typedef struct sb_body_summary_options {
+    uint32_t struct_size;    /* = sizeof(sb_body_summary_options); 0 or a NULL pointer = all defaults */
+    uint32_t reserved[5];    /* zero */
+    uint64_t max_rows;       /* rows of `rows` and `rows_i64`: 1 .. max_particles */
+} sb_body_summary_options;
+sb_status sb_body_summary_device(sb_engine *e, const sb_body_summary_options *opts,
+        const void *device_labels_i32 /* [max_particles] or NULL */,
+        void *device_rows_f32         /* [max_rows][SB_BODY_SUMMARY_WORDS] float or NULL */,
+        void *device_rows_i64         /* [max_rows][SB_BODY_SUMMARY_COUNT_WORDS] int64 or NULL */,
+        void *device_rank_i32         /* [max_particles] int32 or NULL */);
+sb_status sb_body_summary(sb_engine *e, const sb_body_summary_options *opts, const int32_t *labels, float *rows, int64_t *rows_i64,
+                          int32_t *rank);
 
 /* ---- batched small scenes: N independent scenes, one workgroup per scene, one launch per frame ----
  * A second object beside sb_engine, for the user who steps thousands of copies of a SMALL scene (a controller, an RL loop):

@@ -255,8 +255,8 @@ struct sb_engine {
     std::vector<std::pair<void *, size_t>> pool_used, pool_free; // device blocks of the scene / kept for the next upload (sb_api.hip dev_alloc)
 };
 
-// what sb_state_io.hip, sb_summary.hip, sb_bodies.hip and sb_contacts.hip keep between calls (sb_engine sio): tables of the scene
-// of the latest upload, built at the first export / summary / bodies / contacts call after it (sb_write_buffers drops them all
+// what sb_state_io.hip, sb_summary.hip, sb_bodies.hip, sb_contacts.hip and sb_body_summary.hip keep between calls (sb_engine sio):
+// tables of the scene of the latest upload, built at the first export / summary / bodies / contacts / body_summary call after it (sb_write_buffers drops them all
 // through sbs_invalidate)
 #define SB_CONTACTS_BUFFERS 10
 struct SbStateIoState {
@@ -290,6 +290,14 @@ struct SbStateIoState {
     void *d_con[SB_CONTACTS_BUFFERS] = {};
     size_t cap_con[SB_CONTACTS_BUFFERS] = {}; // bytes
     double con_build_ms = 0.0;
+    // sb_body_summary.hip: its own tables, the scratch of a call (one allocation, carved by use), the engine's own labels
+    bool bsm_valid = false;
+    void *d_bsm_pinv = nullptr;     // per particle data index < bsm_np: its internal particle (0xFFFFFFFF: none)
+    void *d_bsm_tab = nullptr;      // [4][bsm_nslots]: per caller beam slot the data index of A, of B, the engine slot, the copy read back
+    uint32_t bsm_np = 0, bsm_nslots = 0; // highest particle data index in use + 1; the caller's beam slots
+    void *d_bsm = nullptr, *d_bsm_labels = nullptr, *d_bsm_out = nullptr; // scratch; sb_bodies_device's labels / the host's; sb_body_summary's device-side result
+    size_t cap_bsm_pinv = 0, cap_bsm_tab = 0, cap_bsm = 0, cap_bsm_labels = 0, cap_bsm_out = 0; // bytes
+    double bsm_build_ms = 0.0;
 };
 
 inline void sb_set_error(sb_engine *e, const char *text) { if (e) e->err = text; else sb_set_create_error(text); } // (sb_error.h)
@@ -334,5 +342,7 @@ bool sbm_info(sb_engine *e, const char *key, uint64_t *value); // its sb_get_inf
 bool sbd_info(sb_engine *e, const char *key, uint64_t *value); // its sb_get_info keys (false: not one of them)
 // sb_contacts.hip
 bool sbc_info(sb_engine *e, const char *key, uint64_t *value); // its sb_get_info keys (false: not one of them)
+// sb_body_summary.hip
+bool sby_info(sb_engine *e, const char *key, uint64_t *value); // its sb_get_info keys (false: not one of them)
 // sb_api.hip
 sb_status sb_grid_reset_hash(sb_engine *e); // the spatial hash forgets every position it holds (every upload, through reset_run_state; particle import)

@@ -80,6 +80,7 @@ static struct {
     sb_status (*summary)(sb_engine *, const sb_summary_options *, float *, uint64_t *);
     sb_status (*bodies)(sb_engine *, const sb_bodies_options *, int32_t *, int32_t *, int64_t *);
     sb_status (*contacts)(sb_engine *, const sb_contacts_options *, const int32_t *, int32_t *, int32_t *, int64_t *);
+    sb_status (*body_summary)(sb_engine *, const sb_body_summary_options *, const int32_t *, float *, int64_t *, int32_t *);
     sb_status (*partition_create)(uint32_t, uint32_t, uint32_t, const void *, const void *, const void *, const void *, uint32_t,
                                   uint32_t, float, sb_partition **);
     sb_status (*partition_destroy)(sb_partition *);
@@ -182,6 +183,7 @@ static napi_value js_load(napi_env env, napi_callback_info info)
     SYM(summary, "sb_summary");
     SYM(bodies, "sb_bodies");
     SYM(contacts, "sb_contacts");
+    SYM(body_summary, "sb_body_summary");
     SYM(partition_create, "sb_partition_create");
     SYM(partition_destroy, "sb_partition_destroy");
     SYM(partition_rank_counts, "sb_partition_rank_counts");
@@ -1210,6 +1212,58 @@ static napi_value js_contacts(napi_env env, napi_callback_info info)
     return obj;
 }
 
+/* bodySummary(handle, maxParticles, rows) -> {rows: Float32Array(24 * rows), counts: Float64Array(8 * rows), rank:
+ * Int32Array(maxParticles)}: one row of SB_BODY_SUMMARY_WORDS statistics per body of the whole scene (the engine's own bodies: no
+ * labels go through Node), ranked by particles descending, then label ascending; the exact integers of every row (particles, live
+ * beams, label, pending flags, non-finite particles, non-finite beams, finite particles, 0; whole numbers below 2^31, exact in
+ * a double); the rank at every particle data index (-1: none lives there).  Found on the GPU by sb_body_summary (which waits for
+ * the stream).  maxParticles: the capacity the engine was created with; rows: 1 .. maxParticles. */
+static napi_value js_body_summary(napi_env env, napi_callback_info info)
+{
+    if (!need_lib(env)) return NULL;
+    size_t argc = 3;
+    napi_value argv[3];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    sb_engine *e = argc >= 1 ? get_engine(env, argv[0]) : NULL;
+    if (!e) return NULL;
+    double cap = -1.0, want = 0.0;
+    if (argc >= 2) (void)napi_get_value_double(env, argv[1], &cap);
+    if (argc >= 3) (void)napi_get_value_double(env, argv[2], &want);
+    if (!(cap >= 1.0 && cap <= 2147483648.0) || cap != (double)(uint32_t)cap) {
+        napi_throw_range_error(env, NULL, "bodySummary: maxParticles must be the engine's particle capacity");
+        return NULL;
+    }
+    if (!(want >= 1.0 && want <= cap) || want != (double)(uint32_t)want) {
+        napi_throw_range_error(env, NULL, "bodySummary: rows must be a whole number in 1 .. maxParticles");
+        return NULL;
+    }
+    void *rows = NULL, *cnt = NULL, *rank = NULL;
+    napi_value vrows = make_typed(env, napi_float32_array, (size_t)want * SB_BODY_SUMMARY_WORDS, 4, &rows);
+    napi_value vcnt = make_typed(env, napi_float64_array, (size_t)want * SB_BODY_SUMMARY_COUNT_WORDS, 8, &cnt);
+    napi_value vrank = make_typed(env, napi_int32_array, (size_t)cap, 4, &rank);
+    if (!vrows || !vcnt || !vrank) return NULL;
+    sb_body_summary_options o;
+    memset(&o, 0, sizeof o);
+    o.struct_size = (uint32_t)sizeof o;
+    o.max_rows = (uint64_t)want;
+    /* (the int64 words land in the Float64Array's memory and are converted in place: both are 8 bytes a word) */
+    sb_status st = sb.body_summary(e, &o, NULL, (float *)rows, (int64_t *)cnt, (int32_t *)rank);
+    if (st != SB_OK) return throw_status(env, e, st, "sb_body_summary");
+    const size_t n = (size_t)want * SB_BODY_SUMMARY_COUNT_WORDS;
+    for (size_t i = 0; i < n; i++) {
+        int64_t v;
+        memcpy(&v, (char *)cnt + 8 * i, 8);
+        const double d = (double)v;
+        memcpy((char *)cnt + 8 * i, &d, 8);
+    }
+    napi_value obj;
+    CHECK_NAPI(napi_create_object(env, &obj));
+    CHECK_NAPI(napi_set_named_property(env, obj, "rows", vrows));
+    CHECK_NAPI(napi_set_named_property(env, obj, "counts", vcnt));
+    CHECK_NAPI(napi_set_named_property(env, obj, "rank", vrank));
+    return obj;
+}
+
 static napi_value init(napi_env env, napi_value exports)
 {
     static const struct { const char *name; napi_callback fn; } fns[] = {
@@ -1226,7 +1280,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"partitionCreate", js_partition_create}, {"partitionDestroy", js_partition_destroy},
         {"partitionRankCounts", js_partition_rank_counts}, {"partitionRankScene", js_partition_rank_scene},
         {"partitionRankIds", js_partition_rank_ids}, {"partitionPeer", js_partition_peer}, {"render", js_render},
-        {"summary", js_summary}, {"bodies", js_bodies}, {"contacts", js_contacts},
+        {"summary", js_summary}, {"bodies", js_bodies}, {"contacts", js_contacts}, {"bodySummary", js_body_summary},
         {"partitionRankGuard", js_partition_rank_guard}, {"haloGuard", js_halo_guard}, {"haloGuardStatus", js_halo_guard_status},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

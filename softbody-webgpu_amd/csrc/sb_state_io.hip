@@ -74,14 +74,15 @@ __global__ __launch_bounds__(SBS_BLOCK) void k_state_import_particles(const floa
 
 void sbs_invalidate(sb_engine *e)
 {
-    if (e && e->sio) e->sio->valid = e->sio->sum_valid = e->sio->bod_valid = e->sio->con_valid = false;
+    if (e && e->sio) e->sio->valid = e->sio->sum_valid = e->sio->bod_valid = e->sio->con_valid = e->sio->bsm_valid = false;
 }
 
 void sbs_release(sb_engine *e)
 {
     if (!e || !e->sio) return;
     void *ps[] = {e->sio->d_slot, e->sio->d_sum_pinv, e->sio->d_sum_bleaf, e->sio->d_sum_part, e->sio->d_sum_stat, e->sio->d_sum_out,
-                  e->sio->d_bod_pinv, e->sio->d_bod_tab, e->sio->d_bod_parent, e->sio->d_bod_sizes, e->sio->d_bod_acc};
+                  e->sio->d_bod_pinv, e->sio->d_bod_tab, e->sio->d_bod_parent, e->sio->d_bod_sizes, e->sio->d_bod_acc,
+                  e->sio->d_bsm_pinv, e->sio->d_bsm_tab, e->sio->d_bsm, e->sio->d_bsm_labels, e->sio->d_bsm_out};
     for (void *p : ps)
         if (p) (void)hipFree(p);
     for (void *p : e->sio->d_con)

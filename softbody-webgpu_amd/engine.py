@@ -67,8 +67,19 @@ CONTACT_COUNT_WORDS = 4      # SB_CONTACT_COUNT_WORDS: the int64 counts of conta
 CONTACTS_OTHER_BODY = 1      # SB_CONTACTS_OTHER_BODY
 
 
+class SbBodySummaryOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 5), ("max_rows", ctypes.c_uint64)]
+
+
+BODY_SUMMARY_WORDS = 24          # SB_BODY_SUMMARY_WORDS: the floats of a row of body_summary(); batch.BODY_SUMMARY_FIELDS names them
+BODY_SUMMARY_COUNT_WORDS = 8     # SB_BODY_SUMMARY_COUNT_WORDS: the exact int64 words beside a row
+# the int64 words of a row of body_summary()'s counts, in order (include/softbody.h, sb_body_summary_device)
+BODY_SUMMARY_COUNT_FIELDS = ("particles", "live_beams", "label", "pending_breaks", "nonfinite_particles", "nonfinite_beams",
+                             "finite_particles", "reserved_7")
+
+
 def __getattr__(name):
-    if name in ("SUMMARY_FIELDS", "BODY_FIELDS", "CONTACT_TOUCH_FIELDS", "CONTACT_COUNT_FIELDS", "WALL_LEFT", "WALL_RIGHT", "WALL_LOW",
+    if name in ("SUMMARY_FIELDS", "BODY_FIELDS", "BODY_SUMMARY_FIELDS", "CONTACT_TOUCH_FIELDS", "CONTACT_COUNT_FIELDS", "WALL_LEFT", "WALL_RIGHT", "WALL_LOW",
                 "WALL_HIGH"):  # the batch's words: its names are not copied (batch.py imports this module)
         from . import batch
         return getattr(batch, name)
@@ -192,6 +203,8 @@ def load_library():
     L.sb_bodies.argtypes = [vp, ctypes.POINTER(SbBodiesOptions), vp, vp, vp]
     L.sb_contacts_device.argtypes = [vp, ctypes.POINTER(SbContactsOptions), vp, vp, vp, vp]
     L.sb_contacts.argtypes = [vp, ctypes.POINTER(SbContactsOptions), vp, vp, vp, vp]
+    L.sb_body_summary_device.argtypes = [vp, ctypes.POINTER(SbBodySummaryOptions), vp, vp, vp, vp]
+    L.sb_body_summary.argtypes = [vp, ctypes.POINTER(SbBodySummaryOptions), vp, vp, vp, vp]
     f32 = ctypes.c_float
     L.sb_partition_create.argtypes = [u32, u32, u32, vp, vp, vp, vp, u32, u32, f32, ctypes.POINTER(vp)]
     L.sb_partition_destroy.argtypes = [vp]
@@ -672,6 +685,78 @@ class Engine:
         self._check(load_library().sb_contacts(self._h, ctypes.byref(o), None if lab is None else _ptr(lab), _ptr(touch),
                                                _ptr(plist) if int(pairs) else None, _ptr(counts)))
         return touch, counts, plist
+
+    # ---- statistics per body of the whole scene (sb_body_summary_device / sb_body_summary)
+
+    def _body_summary_options(self, what, rows):
+        if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or not 1 <= rows <= self.max_particles:
+            raise ValueError("%s: rows is %r, not a number in 1 .. max_particles (%d)" % (what, rows, self.max_particles))
+        o = SbBodySummaryOptions()
+        o.struct_size = ctypes.sizeof(SbBodySummaryOptions)
+        o.max_rows = int(rows)
+        return o
+
+    def body_summary(self, labels=None, rows=8, out=None, counts=False, rank=False):
+        """One row of 24 statistics per GROUP of particles of the whole scene (BODY_SUMMARY_FIELDS names the columns; the row of
+        BatchEngine.body_summary(), the same definition): a float32 tensor [rows, 24] on the engine's device -- alone, or followed
+        by counts and / or rank, in that order, where they are asked for.  labels: None or True (self.bodies()' labelling runs
+        first, on the same stream, and the groups are the bodies) or an int32 tensor / device pointer of [max_particles] labels of
+        the caller's own at particle DATA indices: a value 0 .. max_particles-1 names the particle's group, any other value puts it
+        into none; a live beam belongs to the group that holds both its endpoints.  Row k is the group of rank k -- particles
+        descending, then label ascending -- and rows behind the last group are empty (label -1, counts 0, NaN elsewhere).  Counts,
+        label, pending breaks, means, extremes, kinetic energy and angular momentum of the group's finite particles, strain and
+        stress extremes of its finite beams; the sums are those of summary()'s pinned tree over the group alone, so a row is the
+        same bits on every run, and a scene that is one body gives summary()'s words.  counts int64 [rows, 8]
+        (BODY_SUMMARY_COUNT_FIELDS): the integers of a row exactly, whatever the size of the scene.  rank int32 [max_particles]:
+        the rank of the group of the particle at that data index (>= rows: its row was cut), -1 where no particle lives or the
+        particle is in no group.  rows: 1 .. max_particles.  out: None or True -- a new tensor; False -- left out (None in its
+        place; not all three); counts / rank: False -- left out; None or True -- a new tensor; each also a device pointer (int)
+        or a contiguous torch tensor of that dtype and at least that many elements to write into.  Every word of an output is
+        written.  Only reads the engine, only enqueues; torch's current stream is ordered after it."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        o = self._body_summary_options("body_summary", rows)
+        rows = int(rows)
+        want_counts, want_rank = counts is not False, rank is not False
+        shapes = (("out", out, (rows, BODY_SUMMARY_WORDS), "float32"),
+                  ("counts", counts, (rows, BODY_SUMMARY_COUNT_WORDS), "int64"), ("rank", rank, (self.max_particles,), "int32"))
+        outs, ptrs, tensors = [], [], False
+        for what, x, shape, dtype in shapes:
+            if x is False:
+                outs.append(None)
+                ptrs.append(None)
+                continue
+            if x is None or x is True:
+                x = torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
+            ptr, t = self._device_buffer("body_summary: " + what, x, dtype, int(np.prod(shape)) * (8 if dtype == "int64" else 4))
+            outs.append(x)
+            ptrs.append(ptr)
+            tensors |= t
+        lab = None
+        if labels is not None and labels is not True:
+            lab, t = self._device_buffer("body_summary: labels", labels, "int32", self.max_particles * 4)
+            tensors |= t
+        vp = ctypes.c_void_p
+        self._ordered(tensors, lambda: load_library().sb_body_summary_device(self._h, ctypes.byref(o), vp(lab), vp(ptrs[0]), vp(ptrs[1]),
+                                                                             vp(ptrs[2])))
+        res = [outs[0]] + ([outs[1]] if want_counts else []) + ([outs[2]] if want_rank else [])
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def body_summary_host(self, labels=None, rows=8):
+        """The same without torch: (rows float32 [rows, 24], counts int64 [rows, 8], rank int32 [max_particles]) numpy arrays;
+        labels: None (the engine's bodies) or an int32 array of [max_particles] labels.  Waits for the stream."""
+        o = self._body_summary_options("body_summary_host", rows)
+        out = np.empty((int(rows), BODY_SUMMARY_WORDS), dtype=np.float32)
+        counts = np.empty((int(rows), BODY_SUMMARY_COUNT_WORDS), dtype=np.int64)
+        rank = np.empty(self.max_particles, dtype=np.int32)
+        lab = None
+        if labels is not None:
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.size < self.max_particles:
+                raise ValueError("body_summary_host: labels needs max_particles entries")
+        self._check(load_library().sb_body_summary(self._h, ctypes.byref(o), None if lab is None else _ptr(lab), _ptr(out), _ptr(counts),
+                                                   _ptr(rank)))
+        return out, counts, rank
 
     def state_tensors(self):
         """New torch tensors of the current state: {"particles": (max_particles, 6) float32, "beams": (max_beams, 4) float32,

@@ -77,6 +77,8 @@ class WGPUSoftbodyEngine {
     async bodies() { return this.worker.bodies(); }
     /** who touches whom and who touches a wall in the whole scene: touch rows, counts, optional pair list (engineWorker.js contacts) */
     async contacts(opts) { return this.worker.contacts(opts); }
+    /** one row of 24 statistics per body of the whole scene, ranked by size, exact counts and ranks (engineWorker.js bodySummary) */
+    async bodySummary(opts) { return this.worker.bodySummary(opts); }
     /** n frames back to back */
     async run(frames) { for (let i = 0; i < frames && this.running; i++) await this.frame(); }
 

@@ -159,6 +159,24 @@ class WGPUSoftbodyEngineWorker {
         });
     }
 
+    /**
+     * Statistics per body of the whole scene, the same bits on every run -- found on the GPU (sb_body_summary) with the engine's
+     * own bodies as the groups: no state travels to the host and no labels go through Node.
+     * @param opts {rows: rows to return, 1 .. maxParticles (default 8, at most maxParticles)}
+     * @returns {rows: Float32Array(24 * rows), counts: Float64Array(8 * rows), rank: Int32Array(maxParticles)}; row k is the body
+     *          of rank k (particles descending, then label ascending; the empty row behind the last: label -1, counts 0, NaN
+     *          elsewhere); counts holds per row the exact {particles, live beams, label, pending breaks, non-finite particles,
+     *          non-finite beams, finite particles, 0}; rank[i] is the rank of the body of the particle at data index i, -1 where
+     *          none lives
+     */
+    async bodySummary(opts) {
+        return this.lock.run(() => {
+            if (!this.uploaded) throw new Error('bodySummary before writeBuffers');
+            const cap = this.bufferMapper.maxParticles;
+            return this.addon.bodySummary(this.handle, cap, (opts && opts.rows) || Math.min(8, cap));
+        });
+    }
+
     /** benchmark granularity: n substeps, no delete pass; returns device milliseconds */
     async step(n) {
         return this.lock.run(() => this.addon.stepTimed(this.handle, n));

@@ -181,6 +181,8 @@ export class WGPUSoftbodyEngine {
     bodies(): Promise<SceneBodies>;
     /** particle and wall contacts of the whole scene (sb_contacts), found on the GPU */
     contacts(opts?: ContactsOptions): Promise<SceneContacts>;
+    /** statistics per body of the whole scene (sb_body_summary), the same bits on every run, found on the GPU */
+    bodySummary(opts?: BodySummaryOptions): Promise<SceneBodySummary>;
     run(frames: number): Promise<void>;
     destroy(): Promise<void>;
     readonly destroyed: boolean;
@@ -197,6 +199,12 @@ export interface SceneBodies { labels: Int32Array, counts: [number, number, numb
 export interface ContactsOptions { pairs?: number }
 /** touch: per particle data index {partners, -1, wall bits, smallest partner or -1}; counts: touching pairs, -1 (no labels), particles
  *  on a wall, particles touching another; pairs: the first `pairs` pairs {i, j}, i < j, ascending, {-1, -1} behind the last */
+/** rows to return: 1 .. maxParticles (default 8) */
+export interface BodySummaryOptions { rows?: number }
+/** rows: 24 floats per row (the words of sb_body_summary, include/softbody.h), row k the body of rank k (particles descending, then
+ *  label ascending), the empty row behind the last; counts: 8 exact integers per row (particles, live beams, label, pending breaks,
+ *  non-finite particles, non-finite beams, finite particles, 0); rank: per particle data index the rank of its body, -1 where none lives */
+export interface SceneBodySummary { rows: Float32Array, counts: Float64Array, rank: Int32Array }
 export interface SceneContacts { touch: Int32Array, counts: [number, number, number, number], pairs: Int32Array }
 
 export class WGPUSoftbodyEngineWorker {
@@ -220,6 +228,8 @@ export class WGPUSoftbodyEngineWorker {
     bodies(): Promise<SceneBodies>;
     /** sb_contacts: touch rows per particle data index, the four counts and an optional pair list, without a read-back of the scene */
     contacts(opts?: ContactsOptions): Promise<SceneContacts>;
+    /** sb_body_summary: one row of 24 statistics per body, ranked by size, with exact counts and ranks, without a read-back of the scene */
+    bodySummary(opts?: BodySummaryOptions): Promise<SceneBodySummary>;
     onMessage(msg: { type: WGPUSoftbodyEngineMessageTypes, data?: unknown }): Promise<void>;
     destroy(): Promise<void>;
 }

@@ -1,0 +1,260 @@
+"""Engine.body_summary() (sb_body_summary / sb_body_summary_device) without a GPU: the header declares the calls,
+the library exports them, engine.py binds them with a structure of the C struct's size, every argument error that is raised before a
+device is touched, the dense reference on the hand-worked scene of DESIGN 5.16 and against the batch's reference, the kernel's
+sparse route replayed sequentially against the dense trees, the -0.0 rule, the one-body identity with summary_ref, what the scenes
+of tests/test_gpu_body_summary.py must show, and no kernel of the call spills or uses scratch."""
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import batch_body_summary_ref as qr  # noqa: E402
+import batch_summary_ref as sr  # noqa: E402
+import bodies_cases as bc  # noqa: E402
+import body_summary_cases as yc  # noqa: E402
+import body_summary_ref as yr  # noqa: E402
+import summary_cases as sc  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SYMBOLS = ["sb_body_summary", "sb_body_summary_device"]
+KERNELS = ("k_bsum_stage", "k_bsum_hist", "k_bsum_scatter", "k_bsum_scan_reduce", "k_bsum_scan_sums", "k_bsum_scan_add", "k_bsum_leaves",
+           "k_bsum_level", "k_bsum_beams", "k_bsum_groups", "k_bsum_rank_of", "k_bsum_rows", "k_bsum_rank")
+
+
+def test_header_declares_and_library_exports_the_calls(sb):
+    names = sb.engine.declared_symbols()
+    L = sb.engine.load_library()
+    for s in SYMBOLS:
+        assert s in names, s
+        assert hasattr(L, s), s
+    assert L.sb_abi_version() == 1   # additions only
+    vp, po = ctypes.c_void_p, ctypes.POINTER(sb.engine.SbBodySummaryOptions)
+    assert L.sb_body_summary_device.argtypes == [vp, po, vp, vp, vp, vp] and L.sb_body_summary.argtypes == [vp, po, vp, vp, vp, vp]
+    assert callable(sb.Engine.body_summary) and callable(sb.Engine.body_summary_host)
+
+
+def test_options_structure_and_words_are_the_c_headers(sb, tmp_path):
+    src = tmp_path / "size.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "softbody.h"\n'
+                   'int main(void) { printf("%zu %zu %zu %u %u %u %u\\n", sizeof(sb_body_summary_options), offsetof(sb_body_summary_options, reserved), '
+                   'offsetof(sb_body_summary_options, max_rows), SB_BODY_SUMMARY_WORDS, SB_BODY_SUMMARY_COUNT_WORDS, '
+                   'SB_BATCH_BODY_SUMMARY_WORDS, SB_BODY_SUMMARY_DEFAULT_ROWS); return 0; }\n')
+    exe = str(tmp_path / "size")
+    p = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe],
+                       capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr
+    size, o_res, o_rows, words, cwords, bwords, default = (int(x) for x in subprocess.run([exe], capture_output=True, text=True).stdout.split())
+    O = sb.engine.SbBodySummaryOptions
+    assert ctypes.sizeof(O) == size == 32 and (O.reserved.offset, O.max_rows.offset) == (o_res, o_rows) == (4, 24)
+    assert words == bwords == 24 == sb.engine.BODY_SUMMARY_WORDS == len(sb.BODY_SUMMARY_FIELDS) == yr.WORDS
+    assert cwords == 8 == sb.engine.BODY_SUMMARY_COUNT_WORDS == len(sb.BODY_SUMMARY_COUNT_FIELDS) == yr.COUNT_WORDS and default == 8
+    assert sb.BODY_SUMMARY_FIELDS is sb.batch.BODY_SUMMARY_FIELDS       # the batch's names, not a copy
+    assert sb.BODY_SUMMARY_COUNT_FIELDS[:6] == sb.BODY_SUMMARY_FIELDS[:6]
+
+
+def test_null_handle_is_invalid_before_anything_touches_a_device(sb):
+    """A NULL handle is all that can be refused without a device here: sb_create itself needs one, so the errors that need a live
+    handle (three NULL outputs, max_rows of 0 or above the capacity, misalignment, a bad struct_size, a nonzero reserved word) are in
+    tests/test_gpu_body_summary.py::test_errors_on_a_live_engine, which also shows that the engine still works after each.  A
+    capacity above 2^31 is tested nowhere: no machine creates such an engine."""
+    L, vp = sb.engine.load_library(), ctypes.c_void_p
+    rows, rows64, rank = (ctypes.c_float * 64)(), (ctypes.c_int64 * 16)(), (ctypes.c_int32 * 16)()
+    o = sb.engine.SbBodySummaryOptions()
+    o.struct_size, o.max_rows = ctypes.sizeof(o), 2
+    for f in (L.sb_body_summary, L.sb_body_summary_device):
+        assert f(None, None, None, None, None, None) == 1
+        assert f(None, ctypes.byref(o), None, ctypes.cast(rows, vp), ctypes.cast(rows64, vp), ctypes.cast(rank, vp)) == 1
+
+
+def test_python_refuses_rows_outside_the_capacity_without_a_call(sb):
+    class Fake(sb.Engine):
+        def __init__(self):
+            self.max_particles, self._h = 8, None
+    for rows in (0, 9, True, 2.0, None):
+        with pytest.raises(ValueError):
+            Fake()._body_summary_options("body_summary", rows)
+    assert Fake()._body_summary_options("body_summary", 8).max_rows == 8
+
+
+def hand_scene(sb):
+    """DESIGN 5.16's: x = 2^60, 1, -2^60 at data indices 0, 1, 4 (group 0), a second group (label 2) interleaved at 2, 3, 5; W = 8"""
+    buf = sb.Buffers(2, 8, 4)
+    big = float(2.0 ** 60)
+    pts = np.zeros((6, 6), "f4")
+    pts[:, 0] = [big, 1.0, 3.0, 5.0, -big, 7.0]
+    pts[:, 1] = 500.0
+    buf.set_scene(pts, np.zeros(0, sb.layout.BEAM_DTYPE[2]))
+    return buf, np.array([0, 0, 2, 2, 0, 2, -1, -1], np.int32)
+
+
+def test_hand_worked_scene_the_tree_gives_one_and_index_order_zero(sb):
+    buf, labels = hand_scene(sb)
+    rows, counts, rank = yr.body_summary_ref(buf, labels, 3)
+    # the tree: s[0] += s[4] first (2^60 - 2^60 = 0), then + 1: the sum is 1 and the mean 1/3; index order gives (2^60 + 1) - 2^60 = 0
+    assert rows[0, 6] == np.float32(1.0 / 3.0) and counts[0].tolist() == [3, 0, 0, 0, 0, 0, 3, 0]
+    assert float(np.float64(2.0 ** 60) + 1.0 - 2.0 ** 60) == 0.0
+    assert rows[1, 6] == np.float32(15.0 / 3.0) and counts[1, 2] == 2 and counts[2].tolist() == list(yr.EMPTY_COUNTS)
+    assert rank.tolist() == [0, 0, 1, 1, 0, 1, -1, -1]
+    b = qr.body_summary_ref(buf, labels, 3)
+    qr.assert_equal((rows, rank), b, "against the batch's reference")
+
+
+@pytest.mark.parametrize("W", [8, 128, 8192])
+def test_sparse_route_equals_the_dense_trees(W):
+    """the kernel's route (members sorted by label * W + bitrev, a head adds onto its left sibling's head, level by level) replayed
+    one addition at a time against the masked trees; random groupings, magnitudes spread over 2^40"""
+    rng = np.random.default_rng(W)
+    differs = 0
+    for trial in range({8: 64, 128: 4, 8192: 1}[W]):      # (a tree of 8 leaves rarely rounds: many small draws)
+        n = W - W // 5
+        grp = rng.integers(0, max(2, W // 16), n)
+        member = rng.random(n) < 0.9
+        leaves = (rng.standard_normal(n) * np.exp2(rng.integers(-20, 20, n))).astype(np.float32).astype(np.float64)
+        route = qr.replay_route(grp, member, leaves, W)
+        for g in sorted(set(grp[member].tolist())):
+            mask = np.zeros(W)
+            idx = np.nonzero(member & (grp == g))[0]
+            mask[idx] = leaves[idx]
+            dense = sr.tree_sum(mask) + 0.0
+            assert np.float64(route[g]).tobytes() == np.float64(dense).tobytes(), (W, trial, g)
+            seq = np.float64(0.0)
+            for i in idx:
+                seq = seq + leaves[i]
+            differs += seq.tobytes() != np.float64(dense).tobytes()
+    assert differs >= 1      # index-order summation gives other bits in at least one group: the case bites
+
+
+def test_the_minus_zero_rule(sb):
+    """a zero sum is +0.0; the extremes order -0.0 below +0.0 (the batch's reference may return either)"""
+    buf = sc.free_particles(sb, 4, [-0.0, 0.0, -0.0, 0.0])
+    buf.particles[:4, 0] = np.array([0.0, -0.0, 0.0, -0.0], "f4")
+    rows, counts, rank = yr.body_summary_ref(buf, np.zeros(4, np.int32), 1)
+    bits = rows.view(np.uint32)[0]
+    assert bits[8] == 0 and bits[14] == 0 and bits[19] == 0 and bits[6] == 0          # +0.0
+    assert bits[10] == 0x80000000 and bits[12] == 0                                   # min x = -0.0, max x = +0.0
+    allneg = sc.free_particles(sb, 4, [-0.0] * 4)
+    assert yr.body_summary_ref(allneg, np.zeros(4, np.int32), 1)[0].view(np.uint32)[0, 8] == 0    # where the tree itself gives -0.0
+
+
+def test_one_body_is_summary_refs_row(sb, oracle):
+    case = sc.case_break(sb)
+    ref = sc.make_oracle(oracle, case)
+    sc.apply_to_oracle(ref, case["program"][0])
+    now = ref.load_buffers(case["buf"].copy())
+    row = sr.summary_ref(now, case["buf"], sr.pending_of(ref))
+    rows, counts, rank = yr.body_summary_ref(now, yc.body_labels(now), 2, qr.pending_slots_of(ref, case["buf"]))
+    w = list(yr.SUMMARY_SHARED_WORDS)
+    assert counts[0, 0] == 144 and counts[1, 2] == -1 and counts[0, 3] == sr.pending_of(ref) > 0
+    assert rows[0, w].tobytes() == row[w].tobytes()
+
+
+def test_reference_equals_the_batchs_on_scenes_that_fit_a_batch(sb):
+    for name in ("path 8 in 8/8", "two pairs in 65/64", "path 65 in 65/64", "two particles", "no particles", "512 pairs"):
+        buf = yc.scene(sb, name)
+        for labels in (yc.body_labels(buf), yc.caller_labels(buf, "stripes"), yc.caller_labels(buf, "outside")):
+            for m in (1, buf.max_particles if buf.max_particles <= 65 else 16):
+                a = yr.body_summary_ref(buf, labels, m)
+                qr.assert_equal((a[0], a[2]), qr.body_summary_ref(buf, labels, m), name)
+                assert np.array_equal(a[1][:, :6].astype(np.float32), a[0][:, :6])
+
+
+# name: (groups, particles of the first three rows) -- what the construction says, on the reference alone
+FIGURES = {"path 4097": (1, [4097, 0, 0]), "16 pieces of 256": (16, [256, 256, 256]), "512 pairs": (512, [2, 2, 2]),
+           "star 1024": (1, [1024, 0, 0]), "shuffled 65536, many bodies": (21846, [3, 3, 3]),
+           "1023 singles": (1023, [1, 1, 1]), "1024 singles": (1024, [1, 1, 1]), "1025 singles": (1025, [1, 1, 1])}
+
+
+@pytest.mark.parametrize("name", list(FIGURES))
+def test_scene_is_what_its_construction_says(sb, name):
+    buf = yc.scene(sb, name)
+    rows, counts, rank = yr.body_summary_ref(buf, yc.body_labels(buf), 3)
+    groups, first = FIGURES[name]
+    assert rank.max() + 1 == groups and counts[:, 0].tolist() == first
+    P = buf.particle_count
+    assert not np.array_equal(np.sort(buf.mapping[:P]), buf.mapping[:P])      # the mapping is shuffled
+    if groups > 1:
+        assert counts[0, 2] < counts[1, 2]      # equal sizes: the label decides
+    # the pinned sum is not the sum in index order: the scene bites
+    grp = yr.groups_of(buf, yc.body_labels(buf))
+    sums, fin, _ = yr.group_sums(buf, grp, int(counts[0, 2]))
+    if len(fin) > 64:
+        seq = np.float64(0.0)
+        for v in buf.particles[fin, 2].astype(np.float64):
+            seq = seq + v
+        assert seq.tobytes() != np.float64(sums[2]).tobytes()
+
+
+# ---- the programs of tests/test_gpu_body_summary.py on the oracle, with the figures they give there
+def test_breaking_lattice_apart_on_the_oracle(sb, oracle):
+    case = bc.case_break_apart(sb)
+    buf = case["buf"]
+    ref = sc.make_oracle(oracle, case)
+    sc.apply_to_oracle(ref, case["program"][0])
+    now = ref.load_buffers(buf.copy())
+    rows, counts, rank = yr.body_summary_ref(now, yc.body_labels(now), 8, qr.pending_slots_of(ref, buf))
+    assert counts[:2].tolist() == [[144, 385, 0, 34, 0, 0, 144, 0], list(yr.EMPTY_COUNTS)]       # one body, 34 flags pending
+    sc.apply_to_oracle(ref, case["program"][1])
+    now = ref.load_buffers(buf.copy())
+    rows, counts, rank = yr.body_summary_ref(now, yc.body_labels(now), 8)
+    assert counts[:5, :4].tolist() == [[141, 351, 1, 0], [1, 0, 0, 0], [1, 0, 12, 0], [1, 0, 13, 0], [0, 0, -1, 0]]
+    assert (rank >= 0).sum() == 144 and rank.max() == 3
+
+
+def test_cut_lattice_figures(sb):
+    whole, cut = bc.cut_lattice(sb)
+    assert yr.body_summary_ref(whole, yc.body_labels(whole), 4)[1][:2, :3].tolist() == [[288, 793, 0], [0, 0, -1]]
+    assert yr.body_summary_ref(cut, yc.body_labels(cut), 4)[1][:3, :3].tolist() == [[144, 385, 0], [144, 385, 144], [0, 0, -1]]
+
+
+def test_nonfinite_scene_on_the_oracle(sb, oracle):
+    """the default scene after a frame with a NaN coordinate at data index 7 and an infinite velocity at 40: 9 bodies, two of
+    them with a particle that is not finite, which stays in its body's counts and leaves its sums"""
+    case = dict(sc.case_default(sb, sc.OFF), program=[("frame", 1), ("poke", [(7, 0, np.nan), (40, 3, np.inf)])])
+    ref = sc.make_oracle(oracle, case)
+    for op in case["program"]:
+        sc.apply_to_oracle(ref, op)
+    now = ref.load_buffers(case["buf"].copy())
+    rows, counts, rank = yr.body_summary_ref(now, yc.body_labels(now), case["buf"].max_particles)
+    assert rank.max() + 1 == 9 and counts[:9, 0].tolist() == [40, 36, 25, 4, 4, 4, 4, 1, 1] and counts[9, 2] == -1
+    assert counts[:, 4].sum() == 2 and counts[1].tolist() == [36, 107, 8, 0, 1, 0, 35, 0] and counts[0, :3].tolist() == [40, 96, 46]
+    assert np.isfinite(rows[:9, 6:10]).all()
+    assert np.array_equal(np.bincount(rank[rank >= 0], minlength=9), counts[:9, 0])
+
+
+def test_callers_labels_figures(sb):
+    buf = yc.scene(sb, "path 4097")
+    got = {w: yr.body_summary_ref(buf, yc.caller_labels(buf, w), 8) for w in ("stripes", "outside", "split")}
+    assert got["stripes"][1][:3, :3].tolist() == [[831, 154, 2000], [829, 177, 4000], [828, 167, 0]] and got["stripes"][1][5, 2] == -1
+    assert got["outside"][1][:2, :3].tolist() == [[1783, 796, 4999], [0, 0, -1]] and (got["outside"][2] == -1).sum() == 5000 - 1783
+    assert got["split"][1][:3, :3].tolist() == [[2063, 1058, 0], [2034, 1029, 3], [0, 0, -1]]
+    assert got["split"][1][:2, 1].sum() < buf.beam_count == 4096
+
+
+def test_block_sizes_are_the_kernels(sb):
+    src = open(os.path.join(ROOT, "softbody-webgpu_amd", "csrc", "sb_body_summary.hip")).read()
+    assert "#define SBY_BLOCK 256u" in src and "#define SBY_PER 4u" in src
+    assert yc.SORT_KEYS == yc.SCAN_WORDS == 256 * 4 and yc.SCAN_SUMS_BLOCK == 256
+
+
+def test_sparse_capacity_scene_skips_levels(sb):
+    wide, tight = yc.sparse_in_big_capacity(sb)
+    top = int(wide.mapping[:wide.particle_count].max())
+    assert wide.max_particles == 1 << 20 and top < 2048 and wide.particle_count == 992 == tight.particle_count
+    a, b = yr.body_summary_ref(wide, yc.body_labels(wide), 2), yr.body_summary_ref(tight, yc.body_labels(tight), 2)
+    assert np.array_equal(a[1], b[1]) and a[1][0, 0] == 992
+
+
+def test_no_kernel_of_the_call_spills_or_uses_scratch():
+    """the compiler's own report (tools/kernel_resources.py) for every kernel of sb_body_summary.hip, and the committed table is that report"""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"),
+                        os.path.join(ROOT, "softbody-webgpu_amd", "csrc", "sb_body_summary.hip"), "k_bsum"], capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr
+    rows = [ln.split() for ln in p.stdout.splitlines() if "k_bsum" in ln]
+    assert sorted(r[0] for r in rows) == sorted(KERNELS)
+    for r in rows:
+        assert r[r.index("spill") + 1] == "0" and r[r.index("scratch") + 1] == "0", r
+    assert p.stdout == open(os.path.join(ROOT, "profiles", "body_summary_kernel_resources.txt")).read()
