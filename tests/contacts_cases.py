@@ -8,6 +8,8 @@ import batch_contacts_cases as bcc
 import contacts_ref as cref
 
 SCAN_BLOCK = 1024       # SBC_SCAN of sb_contacts.hip: the words a workgroup of the cell scan owns
+SCAN_SUMS = 256         # SBC_BLOCK: the block sums one trip of k_contacts_scan_sums' loop takes
+SECOND_TRIP = SCAN_BLOCK * SCAN_SUMS     # the first word whose block sum the SECOND trip of that loop owns: 2^18
 
 
 def cells_per_side(bounds, radius, particles):
@@ -22,12 +24,45 @@ def cells_per_side(bounds, radius, particles):
     return int(min(cap, max(1, int(per_side))))
 
 
-def free_scene(sb, cap, pts, seed, max_beams=4):
-    """len(pts) free particles: number k at data index D[k] in slot S[k].  Returns (Buffers, D)."""
+def cell_words(scene):
+    """(G, cell [P]): the cells per side and the count word y * G + x of every particle NUMBER, by sb_contacts.hip's rule in
+    float32 (sb_batch_cell_geometry's side, sb_grid_coord's division and clamp); finite positions"""
+    f = np.float32
+    buf, D = scene["buf"], scene["D"]
+    G = cells_per_side(scene["bounds"], scene["radius"], buf.particle_count)
+    side = max(f(scene["radius"]) * f(2.0) * (f(1.0) + f(1.0) / f(64.0)), f(scene["bounds"]) / f(G))
+    q = (buf.particles[D, :2].astype(f) / f(side)).astype(f)
+    c = np.where(q > 0, np.minimum(q, f(G - 1)), f(0)).astype(np.int64)       # (truncation; q >= G clamps to G - 1)
+    return G, c[:, 1] * G + c[:, 0]
+
+
+def scan_model(words, carry=True):
+    """The exclusive scan of `words` the way the three launches of sbc_scan / sby_scan take it, in integers: a sum per block of
+    SCAN_BLOCK words; the block sums scanned SCAN_SUMS at a time with a running carry between the trips; added back inside every
+    block.  carry=False is the loop with its carry LEFT OUT: what a test scene must tell from the right answer.  (out, total)"""
+    w = np.asarray(words, dtype=np.int64)
+    nb = (len(w) + SCAN_BLOCK - 1) // SCAN_BLOCK
+    blocks = np.zeros(nb * SCAN_BLOCK, np.int64)
+    blocks[:len(w)] = w
+    blocks = blocks.reshape(nb, SCAN_BLOCK)
+    bsum = blocks.sum(axis=1)
+    base, run = np.zeros(nb, np.int64), 0
+    for at in range(0, nb, SCAN_SUMS):
+        part = bsum[at:at + SCAN_SUMS]
+        base[at:at + SCAN_SUMS] = (run if carry else 0) + np.cumsum(part) - part
+        run += int(part.sum())
+    out = base[:, None] + np.cumsum(blocks, axis=1) - blocks
+    return out.reshape(-1)[:len(w)], run
+
+
+def free_scene(sb, cap, pts, seed, max_beams=4, among=None):
+    """len(pts) free particles: number k at data index D[k] in slot S[k].  among: the data indices to draw from (all of the
+    capacity's where None).  Returns (Buffers, D)."""
     pts = np.asarray(pts, "f4")
     n = len(pts)
     rng = np.random.default_rng(seed)
-    D, S = rng.permutation(cap)[:n], rng.permutation(n)
+    D = rng.permutation(cap)[:n] if among is None else np.asarray(among, np.int64)[rng.permutation(len(among))[:n]]
+    S = rng.permutation(n)
     buf = sb.Buffers(2, cap, max_beams)
     buf.particles[D, :2] = pts[:, :2]
     buf.mapping[S] = D
@@ -85,14 +120,41 @@ def crowd_600(sb):
     return _scene("crowd 600", buf, 1000.0, D=D)
 
 
+def cells_544(sb):
+    """40 000 particles over a box of 11 060: 544 cells per side, 295 937 count words = 290 blocks of the cell scan, so the SECOND
+    trip of the loop over the block sums owns the cells from word 2^18 = row 481, column 480 on.  Three jittered patches -- the
+    low rows, twenty rows across that word (whose own row the patch spans from x = 500 to 10 500), the last rows up to the last
+    cell -- and 15 000 particles scattered over the whole box"""
+    bounds = 11060.0
+    rng = np.random.default_rng(61)
+    pts = np.concatenate([jittered_grid(10000, 200, (100.0, 100.0), seed=62),
+                          jittered_grid(10000, 500, (500.0, 9600.0), seed=63),
+                          jittered_grid(5000, 100, (bounds - 1990.0, bounds - 990.0), seed=64),
+                          rng.uniform(5.0, bounds - 5.0, (15000, 2)).astype("f4")])
+    buf, D = free_scene(sb, 40100, pts, seed=65)
+    return _scene("544 cells per side", buf, bounds, D=D, cells=544, prune=True)
+
+
+def indices_past_2_18(sb):
+    """6000 particles on a jittered grid at capacity 2^18 + 4096: 260 blocks of the 64-bit scan over the data indices.  The data
+    indices are drawn from every 64th index below 2^18 and every index from 2^18 on, so about half of the particles -- and of the
+    pairs, which are listed under their smaller index -- lie in the second trip's four blocks"""
+    cap = SECOND_TRIP + 4096
+    among = np.concatenate([np.arange(0, SECOND_TRIP, 64), np.arange(SECOND_TRIP, cap)])
+    buf, D = free_scene(sb, cap, jittered_grid(6000, 80, (40.0, 40.0), seed=66), seed=67, among=among)
+    return _scene("indices past 2^18", buf, 1700.0, D=D)
+
+
 BIG = {"pile 4097 in 5000": pile_4097, "box 16384": box_16384, "32 cells per side": lambda sb: scan_edge(sb, 32),
        "64 cells per side": lambda sb: scan_edge(sb, 64), "crowd 600": crowd_600}
+# scenes that reach the second trip of the loop over the block sums (more than SCAN_SUMS blocks): tests of their own
+PAST = {"544 cells per side": cells_544, "indices past 2^18": indices_past_2_18}
 _cache = {}
 
 
 def big_scene(sb, name):
     if name not in _cache:
-        _cache[name] = BIG[name](sb)
+        _cache[name] = (BIG[name] if name in BIG else PAST[name])(sb)
     return _cache[name]
 
 
@@ -132,6 +194,22 @@ def striped_labels(max_particles, width=3):
     return (np.arange(max_particles) // width % 5 - 2).astype(np.int32)     # (negative labels too: only ever compared)
 
 
+def pairs_above(scene):
+    """(above [np], total): per data index up to the highest in use the pairs listed under it (its partners of a larger data
+    index) -- the words of the 64-bit scan that places the pair list -- from the reference's whole list"""
+    total = int(expected(scene, None, 0, key="plain")[2][0])
+    pairs = expected(scene, None, total, key="all")[1]
+    return np.bincount(pairs[:, 0], minlength=int(scene["D"].max()) + 1), total
+
+
+def cut_of(scene):
+    """a max_pairs that truncates the list: half way through the pairs listed under data indices from SECOND_TRIP on where the
+    scene has such (the cut then lies behind the carry of the scan over the data indices), else half of the list"""
+    above, total = pairs_above(scene)
+    first = int(above[:SECOND_TRIP].sum())
+    return first + (total - first) // 2 if first < total else total // 2
+
+
 _ref_cache = {}
 
 
@@ -139,7 +217,7 @@ def expected(scene, labels=None, max_pairs=0, other_body=False, key=None):
     """contacts_ref of the scene as uploaded, computed once per (scene, key) and shared; the arrays are not to be written to"""
     k = (scene["name"], key, max_pairs, other_body)
     if key is None or k not in _ref_cache:
-        out = cref.contacts_ref(scene["buf"], scene["radius"], scene["bounds"], labels, max_pairs, other_body)
+        out = cref.contacts_ref(scene["buf"], scene["radius"], scene["bounds"], labels, max_pairs, other_body, prune=scene.get("prune", False))
         for a in out:
             a.setflags(write=False)
         if key is None:

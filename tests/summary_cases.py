@@ -58,6 +58,26 @@ def case_capacity(sb):
                 program=[("frame", 1)], compare_after=[-1, 0])
 
 
+CLAMP_CAPACITY = (1 << 20) + 1
+
+
+def case_clamp(sb):
+    """The same lattice, permuted, at capacity 2^20 + 1 / 2^20 + 1: W = 2^21 for both trees, where the engine's own cut, W / 4
+    clamped to SB_SUMMARY_MAX_PARTIALS = 262 144, is the clamp and no longer W / 4.  Every particle a velocity of its own, spread
+    over forty binary orders (case_cut's), so the sums round."""
+    lat = sb.scenes.lattice_buffers(8, 6, d=30.0, origin=(200.0, 300.0), strain_limit=0.5, layout=2, velocity=(3.0, -2.0))
+    buf = permuted(sb, lat, CLAMP_CAPACITY, CLAMP_CAPACITY, 50, 100)
+    rng = np.random.default_rng(12)
+    idx = buf.mapping[:buf.particle_count].astype(np.int64)
+    buf.particles[idx, 2:4] = ((rng.standard_normal((len(idx), 2)) * 3.0 + (0.7, -1.3)) * np.exp2(-rng.integers(0, 40, (len(idx), 2)))).astype("f4")
+    return dict(name="8x6 in 2^20+1/2^20+1", buf=buf, bounds=1000.0, mode=OFF, program=[("frame", 1)], compare_after=[-1, 0])
+
+
+def default_partials(W):
+    """sbm_default_partials of sb_summary.hip: W / 4, at least 256, at most SB_SUMMARY_MAX_PARTIALS"""
+    return min(max(W // 4, 256), 262144)
+
+
 def free_particles(sb, cap, vx):
     """len(vx) free particles at data indices 0 .. in capacity cap / 4, x velocities vx"""
     buf = sb.Buffers(2, cap, 4)
@@ -95,7 +115,8 @@ def case_break(sb):
 
 
 def all_cases(sb):
-    return [case_default(sb), case_default(sb, OFF), case_cut(sb), case_capacity(sb)] + witness_cases(sb) + [case_nonfinite(sb), case_break(sb)]
+    return ([case_default(sb), case_default(sb, OFF), case_cut(sb), case_capacity(sb)] + witness_cases(sb) + [case_nonfinite(sb), case_break(sb)] +
+            [case_clamp(sb)])
 
 
 def make_oracle(orc, case):

@@ -1,8 +1,10 @@
 """Engine.body_summary() (sb_body_summary / sb_body_summary_device) without a GPU: the header declares the calls,
 the library exports them, engine.py binds them with a structure of the C struct's size, every argument error that is raised before a
 device is touched, the dense reference on the hand-worked scene of DESIGN 5.16 and against the batch's reference, the kernel's
-sparse route replayed sequentially against the dense trees, the -0.0 rule, the one-body identity with summary_ref, what the scenes
-of tests/test_gpu_body_summary.py must show, and no kernel of the call spills or uses scratch."""
+sparse route replayed sequentially against the dense trees, the reference's direct route for groups of at most two against them,
+the -0.0 rule, the one-body identity with summary_ref, what the scenes of tests/test_gpu_body_summary.py must show -- those past
+256 scan blocks against a model of the scan whose loop over the block sums drops its carry --, and no kernel of the call spills or
+uses scratch."""
 import ctypes
 import os
 import subprocess
@@ -17,6 +19,7 @@ import batch_summary_ref as sr  # noqa: E402
 import bodies_cases as bc  # noqa: E402
 import body_summary_cases as yc  # noqa: E402
 import body_summary_ref as yr  # noqa: E402
+from contacts_cases import SECOND_TRIP, scan_model  # noqa: E402
 import summary_cases as sc  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -238,6 +241,108 @@ def test_block_sizes_are_the_kernels(sb):
     src = open(os.path.join(ROOT, "softbody-webgpu_amd", "csrc", "sb_body_summary.hip")).read()
     assert "#define SBY_BLOCK 256u" in src and "#define SBY_PER 4u" in src
     assert yc.SORT_KEYS == yc.SCAN_WORDS == 256 * 4 and yc.SCAN_SUMS_BLOCK == 256
+
+
+def test_direct_route_equals_the_dense_trees_bit_for_bit(sb):
+    """body_summary_ref's route for groups of one or two members against its masked trees, every row, count and rank"""
+    small = 0
+    for name in ("512 pairs", "1023 singles", "1024 singles", "1025 singles", "two particles", "two pairs in 65/64", "16 pieces of 256"):
+        buf = yc.scene(sb, name)
+        for labels in (yc.body_labels(buf), yc.caller_labels(buf, "outside"), yc.caller_labels(buf, "stripes")):
+            m = min(buf.max_particles, 1100)
+            a, b = yr.body_summary_ref(buf, labels, m), yr.body_summary_ref(buf, labels, m, direct=False)
+            yr.assert_equal(a, b, name)
+            small += int(((a[1][:, 0] > 0) & (a[1][:, 0] <= 2)).sum())
+    assert small > 3000
+    # what is not finite, -0.0, and a pair whose sum rounds: one member not finite, both, a lone -0.0, a pair of -0.0
+    buf = sc.free_particles(sb, 12, [np.nan, 1.0, np.inf, -np.inf, -0.0, -0.0, -0.0, 2.0 ** 60, 1.0, 0.1, 0.2])
+    buf.particles[5, 0] = buf.particles[6, 0] = -0.0
+    labels = np.array([0, 0, 1, 1, 2, 3, 3, 4, 4, 5, 5, -1], np.int32)
+    a, b = yr.body_summary_ref(buf, labels, 12), yr.body_summary_ref(buf, labels, 12, direct=False)
+    yr.assert_equal(a, b, "edge pairs")
+    assert a[1][:6, 4].tolist() == [1, 2, 0, 0, 0, 0] and a[1][6, 2] == -1
+
+
+PAST_RUNS = [("sparse up to index 2^20+", None), ("sparse up to index 2^20+", "stripes"), ("sparse up to index 2^20+", "uneven"),
+             ("sparse in capacity 2^21 + 1", "stripes"), ("2^18 + 1025 particles, pairs and singles", None),
+             ("2^18 + 1025 particles, pairs and singles", "bodies, some outside")]      # tests/test_gpu_body_summary.py's
+
+
+def without_carry(words):
+    """(right, wrong, carry): the scan of `words`, the scan whose loop over the block sums leaves its carry out, what is left out"""
+    right, total = scan_model(words)
+    assert total == words.sum() and np.array_equal(right, np.cumsum(words) - words)
+    return right, scan_model(words, carry=False)[0], int(words[:SECOND_TRIP].sum())
+
+
+@pytest.mark.parametrize("name,which", PAST_RUNS, ids=["%s, %s" % r for r in PAST_RUNS])
+def test_scene_reaches_the_second_iteration_of_the_scan_of_the_block_sums(sb, name, which):
+    buf = yc.scene(sb, name)
+    labels = yc.body_labels(buf) if which is None else yc.caller_labels(buf, which)
+    wn = yc.position_count(buf)
+    g, d, none = yc.sorted_positions(buf, labels, which is None)
+    member = g != none
+    head = np.ones(wn, bool)
+    head[1:] = g[1:] != g[:-1]
+    rows, counts, rank = yr.body_summary_ref(buf, labels, 8)
+    groups = int((head & member).sum())
+    assert groups == rank.max() + 1 and member.sum() == (rank >= 0).sum()
+    hist_blocks, flag_blocks = yc.scan_blocks(wn)
+    assert (hist_blocks, flag_blocks) == (wn // 4096, wn // 1024)
+    if name.startswith("sparse"):
+        assert int(buf.mapping[:buf.particle_count].max()) >= 1 << 20 and wn == 1 << 21 and hist_blocks == 512 > yc.SCAN_SUMS_BLOCK
+        assert groups == {None: 17, "stripes": 5, "uneven": 3}[which]
+        # the member sort: the digits of its passes; `none` is the populous run, and not the only populous digit
+        bits = yc.bits_for(none)
+        bites, staged = [], _stage_order(g, d, wn)
+        for p in range(len(yc.digit_plan(bits))):
+            words = yc.hist_words(staged, wn, bits, p)
+            right, wrong, carry = without_carry(words)
+            bites.append(bool(((wrong != right) & (words > 0)).any()))
+        # the rank sort: `groups` keys (~particles), 22 bits, digits of 8, 8 and 6
+        sizes = np.bincount(rank[rank >= 0])
+        cnt = np.diff(np.append(np.flatnonzero(head & member), member.sum()))
+        cbits = (wn.bit_length() - 1) + 1
+        rkeys = ~cnt & ((1 << cbits) - 1)
+        assert [w for _, w in yc.digit_plan(cbits)] == [8, 8, 6] and sorted(cnt.tolist(), reverse=True) == sizes.tolist()
+        for p in range(3):
+            words = yc.hist_words(rkeys, wn, cbits, p)
+            right, wrong, carry = without_carry(words)
+            bites.append(bool(((wrong != right) & (words > 0)).any()))
+        if name == "sparse in capacity 2^21 + 1":
+            assert which == "stripes" and none == buf.max_particles and [w for _, w in yc.digit_plan(bits)] == [8, 8, 6]
+            assert bites[0] and bites[1]        # a member sort without the carry scatters keys to other places
+        else:
+            assert [w for _, w in yc.digit_plan(bits)] == [7, 7, 7] and not any(bites[:3])     # digits below 128: those words are not read
+            assert any(bites[3:]) == (which == "uneven")     # sizes 200 | 300, 3597: low bytes on both sides of 128
+    else:
+        assert buf.particle_count == yc.N_PAST and buf.max_particles == (1 << 18) + 2048 and wn == 1 << 19
+        assert flag_blocks == 512 > yc.SCAN_SUMS_BLOCK >= hist_blocks
+        assert (head & member)[SECOND_TRIP:].sum() > 300 and member[SECOND_TRIP:].sum() > 300
+        assert sorted(set(counts[:, 0].tolist())) == [2] and (rank == groups - 1).sum() == 1       # groups of both sizes
+        if which is None:
+            assert groups == yc.N_PAST - yc.PAIRED // 2 > 1 << 18
+        else:
+            assert 600 < (rank == -1).sum() - (buf.max_particles - buf.particle_count) < 1024     # the members still pass 2^18
+        right, wrong, carry = without_carry(head.astype(np.int64))
+        heads = np.flatnonzero(head & member)
+        assert 0 < carry and np.array_equal(right[heads], np.arange(groups))       # the group numbers
+        bad = heads[wrong[heads] != right[heads]]
+        assert bad.size > 300 and bad.min() >= SECOND_TRIP and (wrong[bad] == right[bad] - carry).all()
+        rank_of = rank[d[heads]]                                                   # by group number
+        assert (rank_of[wrong[bad]] != rank_of[right[bad]]).sum() > 300            # ... and the ranks read through them
+        assert not np.array_equal(rank_of, np.arange(groups))                      # the rank order is not the label order
+
+
+def _stage_order(g, d, wn):
+    """the keys as k_bsum_stage writes them: position t holds the data index bitrev(t)"""
+    out = np.empty(wn, np.int64)
+    logw = wn.bit_length() - 1
+    t = np.zeros(wn, np.int64)
+    for k in range(logw):
+        t |= ((d >> k) & 1) << (logw - 1 - k)
+    out[t] = g
+    return out
 
 
 def test_sparse_capacity_scene_skips_levels(sb):

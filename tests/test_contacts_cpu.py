@@ -1,7 +1,9 @@
 """Engine.contacts() (sb_contacts / sb_contacts_device) without a GPU: the header declares the calls, the library
 exports them, engine.py binds them with a structure of the C struct's size, a NULL handle is refused before anything touches a
 device, the row-chunked reference equals the batch's on every scene of the batch's cases and a scene worked out by hand, every
-scene of tests/test_gpu_contacts.py BITES on the reference alone, and no kernel of the call spills or uses scratch."""
+scene of tests/test_gpu_contacts.py BITES on the reference alone -- the two scenes past 256 scan blocks against a model of the scan
+whose loop over the block sums drops its carry --, the reference's pruning changes no output, and no kernel of the call spills or
+uses scratch."""
 import ctypes
 import os
 import subprocess
@@ -134,6 +136,94 @@ def test_scene_is_what_its_construction_says(sb, name):
         assert len(np.unique((x / cell).astype(int), axis=0)) == 1 and touch[:, 0].max() > 500
         above = np.bincount(pairs[:, 0], minlength=maxP)
         assert above.max() > 400         # far more than the four partners a list sweep keeps
+
+
+def test_scan_model_is_the_exclusive_scan():
+    rng = np.random.default_rng(3)
+    for n in (1, 1023, 1024, 1025, cc.SECOND_TRIP, cc.SECOND_TRIP + 1, cc.SECOND_TRIP + 2 * cc.SCAN_BLOCK + 7):
+        w = rng.integers(0, 5, n)
+        out, total = cc.scan_model(w)
+        assert np.array_equal(out, np.cumsum(w) - w) and total == w.sum(), n
+        wrong = cc.scan_model(w, carry=False)[0]
+        assert np.array_equal(wrong[:cc.SECOND_TRIP], out[:cc.SECOND_TRIP])
+        assert n <= cc.SECOND_TRIP or np.array_equal(wrong[cc.SECOND_TRIP:], out[cc.SECOND_TRIP:] - w[:cc.SECOND_TRIP].sum())
+
+
+def test_pruned_reference_equals_the_unpruned_on_every_existing_scene(sb):
+    """contacts_ref(prune=True) is what only the scene of 40 000 particles is compared with; here against prune=False, every output"""
+    def same(a, b, what):
+        for x, y in zip(a, b):
+            assert x.dtype == y.dtype and np.array_equal(x, y), what
+    scenes = cc.batch_scenes(sb)
+    assert sum(not s["finite"] for s in scenes) >= 2        # coordinates that are not finite among them
+    for s in scenes:
+        lab = cc.striped_labels(s["buf"].max_particles)
+        for labels, m, other in ((None, 0, False), (None, 40, False), (lab, 40, False), (lab, 40, True)):
+            same(cref.contacts_ref(s["buf"], s["radius"], s["bounds"], labels, m, other, prune=True),
+                 cref.contacts_ref(s["buf"], s["radius"], s["bounds"], labels, m, other), (s["name"], m, other))
+    for name in cc.BIG:
+        s = cc.big_scene(sb, name)
+        assert not s.get("prune")
+        lab = cc.striped_labels(s["buf"].max_particles)
+        total = int(cc.expected(s, lab, key="striped")[2][0])
+        same(cref.contacts_ref(s["buf"], s["radius"], s["bounds"], lab, prune=True), cc.expected(s, lab, key="striped"), name)
+        same(cref.contacts_ref(s["buf"], s["radius"], s["bounds"], None, total, prune=True), cc.expected(s, None, total, key="all"), name)
+        same(cref.contacts_ref(s["buf"], s["radius"], s["bounds"], lab, 50, True, prune=True),
+             cc.expected(s, lab, 50, True, key="other 50"), name)
+
+
+# name: (cells per side, blocks of the cell scan, blocks of the scan over the data indices, counts with striped labels)
+PAST_FIGURES = {"544 cells per side": (544, 290, 40, (29338, 23426, 99, 27549)), "indices past 2^18": (83, 7, 260, (5904, 4721, 0, 5805))}
+
+
+@pytest.mark.parametrize("name", list(cc.PAST))
+def test_scene_reaches_the_second_trip_of_the_scan_of_the_block_sums(sb, name):
+    """From the reference and the constants alone: more than 256 scan blocks, a nonzero carry into the second trip, touching pairs
+    on both sides of it, and a scan that leaves the carry out is wrong at words the outputs are read through."""
+    s = cc.big_scene(sb, name)
+    buf, D = s["buf"], s["D"]
+    P, maxP, edge = buf.particle_count, buf.max_particles, cc.SECOND_TRIP
+    cells, cell_blocks, index_blocks, exp = PAST_FIGURES[name]
+    touch, _, counts = cc.expected(s, cc.striped_labels(maxP), key="striped")
+    G, word = cc.cell_words(s)
+    blocks = lambda n: (n + cc.SCAN_BLOCK - 1) // cc.SCAN_BLOCK
+    assert tuple(counts.tolist()) == exp and G == cells == cc.cells_per_side(s["bounds"], s["radius"], P)
+    assert (blocks(G * G + 1), blocks(int(D.max()) + 1)) == (cell_blocks, index_blocks)
+    assert not np.array_equal(D, np.arange(P)) and not np.array_equal(np.sort(buf.mapping[:P]), buf.mapping[:P])
+    assert (touch[:, 0] > 0).sum() == counts[3] and touch[:, 0].sum() == 2 * counts[0] and 0 < counts[1] < counts[0]
+    above, total = cc.pairs_above(s)
+    pairs = cc.expected(s, None, total, key="all")[1]
+    assert total == counts[0] == above.sum()
+    if name.startswith("544"):
+        assert s["prune"] and P == 40000 and G >= 530 and G * G <= 8 * P and cell_blocks > cc.SCAN_SUMS >= index_blocks
+        words = np.bincount(word, minlength=G * G + 1)          # what k_contacts_bin leaves: a count per cell, and the word behind
+        carry = int(words[:edge].sum())
+        assert 0 < carry < P and carry == (word < edge).sum()
+        assert word.min() < G and word.max() == G * G - 1 and words[-1] == 0       # the first row and the last cell are lived in
+        at = np.zeros(maxP, np.int64)
+        at[D] = word
+        a, b = at[pairs[:, 0]], at[pairs[:, 1]]
+        assert ((a < edge) & (b < edge)).any() and ((a >= edge) & (b >= edge)).any() and ((a < edge) != (b < edge)).sum() > 100
+        used = words > 0        # a cell's start is read for every cell somebody lives in (and its end is the next start)
+    else:
+        assert maxP == edge + 4096 and index_blocks > cc.SCAN_SUMS >= cell_blocks
+        words = above                                           # what k_contacts_visit leaves: pairs listed under every data index
+        carry = int(words[:edge].sum())
+        assert 0 < carry < total
+        assert (pairs[:, 0] < edge).sum() > 1000 and (pairs[:, 0] >= edge).sum() > 1000
+        assert ((pairs[:, 0] < edge) & (pairs[:, 1] >= edge)).any()
+        used = words > 0        # a particle reads its place iff pairs are listed under it
+    cut = cc.cut_of(s)                                          # the truncating max_pairs of the GPU test
+    if name.startswith("544"):
+        assert 0 < cut < total
+    else:                                                       # ... behind the carry: the last pair kept is the second trip's
+        assert carry < cut < total and pairs[cut - 1, 0] >= edge
+    right, sum_ = cc.scan_model(words)
+    wrong, _ = cc.scan_model(words, carry=False)
+    assert sum_ == words.sum() and np.array_equal(right, np.cumsum(words) - words)
+    bad = np.flatnonzero((wrong != right) & used)
+    assert bad.size > 100 and bad.min() >= edge and np.array_equal(wrong[:edge], right[:edge])
+    assert (wrong[bad] == right[bad] - carry).all()
 
 
 def test_no_kernel_of_the_contacts_spills_or_uses_scratch():

@@ -92,6 +92,27 @@ def test_group_counts_at_the_block_edges(sb, name):
     eng.destroy()
 
 
+# 3b (tests/test_body_summary_cpu.py shows, on the CPU, what each run reaches and that a scan without its carry gives other words)
+PAST_RUNS = [("sparse up to index 2^20+", None), ("sparse up to index 2^20+", "stripes"), ("sparse up to index 2^20+", "uneven"),
+             ("sparse in capacity 2^21 + 1", "stripes"), ("2^18 + 1025 particles, pairs and singles", None),
+             ("2^18 + 1025 particles, pairs and singles", "bodies, some outside")]
+
+
+@pytest.mark.parametrize("name,which", PAST_RUNS, ids=["%s, %s" % r for r in PAST_RUNS])
+def test_past_256_scan_blocks(sb, name, which):
+    """more than 256 blocks in the scan of a sort's digit counts (Wn = 2^21) and in the scan of the head flags (Wn = 2^19): the
+    second iteration of the loop over the block sums, with its carry"""
+    buf = yc.scene(sb, name)
+    labels = None if which is None else yc.caller_labels(buf, which)
+    eng = engine(sb, buf, path=ATOMIC)
+    for m in (1, 8, buf.max_particles):
+        got = check(eng, buf, m, labels, what="%s, %s, %d rows" % (name, which, m))
+    assert (got[2] >= 0).sum() == got[1][:, 0].sum() <= buf.particle_count
+    again = call(eng, buf.max_particles, labels)
+    assert tuple(g.tobytes() for g in again) == tuple(g.tobytes() for g in got)     # two calls in a row: identical bytes
+    eng.destroy()
+
+
 # 4
 def test_capacity_far_above_the_scene_and_the_same_scene_tight(sb):
     wide, tight = yc.sparse_in_big_capacity(sb)

@@ -102,6 +102,25 @@ def test_beyond_one_workgroup_and_one_scan_block(sb, name, path):
     eng.destroy()
 
 
+# 2b (tests/test_contacts_cpu.py: what the two scenes reach, and that a scan without its carry gives other words there)
+@pytest.mark.parametrize("name", list(cc.PAST))
+def test_past_256_scan_blocks(sb, name):
+    """more than 256 blocks in the scan of the cell counts ("544 cells per side") and in the 64-bit scan over the data indices
+    that places the pair list ("indices past 2^18"): the second trip of the loop over the block sums, with its carry"""
+    s = cc.big_scene(sb, name)
+    lab = cc.striped_labels(s["buf"].max_particles)
+    eng = engine(sb, s)
+    assert eng.info("contacts_cells_per_side") == cc.cells_per_side(s["bounds"], s["radius"], s["buf"].particle_count)
+    exp = cc.expected(s, None, 0, key="plain")
+    assert_contacts(call(eng), exp, name + ", no labels")
+    total, cut = int(exp[2][0]), cc.cut_of(s)
+    assert 0 < cut < total
+    assert_contacts(call(eng, lab, total + 5), cc.expected(s, lab, total + 5, key="striped, every pair"), name + ", every pair")
+    assert_contacts(call(eng, lab, total, True), cc.expected(s, lab, total, True, key="other body"), name + ", other_body")
+    assert_contacts(call(eng, None, cut), cc.expected(s, None, cut, key="cut"), name + ", max_pairs %d" % cut)
+    eng.destroy()
+
+
 # 3
 def test_pair_list_truncation_and_other_body(sb):
     import torch

@@ -68,6 +68,20 @@ def test_capacity_far_above_the_scene(sb, oracle):
     run_case(sb, oracle, sc.case_capacity(sb), "capacity", collision_mode=OFF)
 
 
+def test_where_the_default_cut_is_the_clamp(sb, oracle):
+    """W = 2^21 for both trees: the engine's own cut is SB_SUMMARY_MAX_PARTIALS, not W / 4; that cut asked for, and the narrowest"""
+    case = sc.case_clamp(sb)
+    exp, _ = sc.expected(oracle, case)
+    eng = engine(sb, case, collision_mode=OFF)
+    for k in (-1, 0):
+        if k == 0:
+            sc.apply_to_engine(eng, case["program"][0])
+        rows = [check_now(eng, exp[k], "clamp %d, partials %d" % (k, m), partials=m) for m in (262144, 256, 0)]
+        assert len({r.tobytes() for r in rows}) == 1
+        assert eng.info("summary_partials") == 262144 != sr.pow2_at_least(case["buf"].max_particles) // 4     # the default, run last
+    eng.destroy()
+
+
 @pytest.mark.parametrize("i", [0, 1, 2])
 def test_tree_order_witness(sb, oracle, i):
     case = sc.witness_cases(sb)[i]

@@ -130,6 +130,35 @@ def test_permuted_case_is_not_the_identity(runs):
     assert buf.mapping[:P].max() < 200 and buf.mapping[maxP:maxP + B].max() < 400   # far below the capacity
 
 
+def test_clamp_case_is_where_the_default_cut_is_the_clamp(runs):
+    """W = 2^21 for both trees: the default cut is SB_SUMMARY_MAX_PARTIALS (asserted to be 262 144 above) and not W / 4; at every
+    capacity of the other cases it is W / 4 or the floor of 256.  The sums round, so the order of the additions shows."""
+    c, exp, _ = runs["8x6 in 2^20+1/2^20+1 mode 0"]
+    buf = c["buf"]
+    for cap in (buf.max_particles, buf.max_beams):
+        W = sr.pow2_at_least(cap)
+        assert cap == sc.CLAMP_CAPACITY and W == 1 << 21 and sc.default_partials(W) == 262144 != W // 4
+    for name, (other, _, _) in runs.items():
+        if other is not c:
+            for cap in (other["buf"].max_particles, other["buf"].max_beams):
+                W = sr.pow2_at_least(cap)
+                assert W <= 131072 and sc.default_partials(W) == max(W // 4, 256), name
+    P, B, maxP = buf.particle_count, buf.beam_count, buf.max_particles
+    assert P == 48 and B > 100
+    assert not np.array_equal(np.sort(buf.mapping[:P]), buf.mapping[:P]) and buf.mapping[:P].max() < 200
+    idx = np.sort(buf.mapping[:P].astype(np.int64))
+    differs = 0
+    for col in (2, 3):
+        leaves = np.zeros(1 << 21)
+        leaves[idx] = buf.particles[idx, col].astype(np.float64)
+        serial = 0.0
+        for v in leaves[idx]:
+            serial += v
+        differs += sr.tree_sum(leaves) != serial
+    assert differs > 0
+    assert sorted(exp) == [-1, 0] and exp[-1][0].tobytes() != exp[0][0].tobytes()
+
+
 def test_multi_leaf_case_tree_sum_differs_from_a_flat_sum(runs):
     buf = runs["96x96 lattice mode 0"][0]["buf"]   # (as uploaded: the first comparison of the case)
     P = buf.particle_count
