@@ -408,7 +408,7 @@ sb_status sb_render(sb_engine *e, const sb_render_options *opts, void *rgb, size
 sb_status sb_render_device(sb_engine *e, const sb_render_options *opts, void *device_rgb);
 
 /* ---- the state in device memory (no host round trip) ----
- * Both calls only ENQUEUE on the engine's stream; the device buffers must stay valid until that work has run.  The first export
+ * These calls only ENQUEUE on the engine's stream; the device buffers must stay valid until that work has run.  The first export
  * after an upload builds its beam tables and waits for the stream once, as the first render does; later calls only enqueue.
  * Errors: SB_ERR_STATE before an upload; SB_ERR_UNSUPPORTED on an engine with ghost zones or peers configured (ranks are not
  * handled here); SB_ERR_INVALID for a NULL source to sb_write_particles_device, or a particle buffer that is not 8-byte / a beam
@@ -432,6 +432,35 @@ sb_status sb_read_state_device(sb_engine *e, void *device_particles, void *devic
  * planning upload: the hash keeps the frame fitted at that upload (particles outside are clamped into its edge cells), and the
  * tiles stay those bisected from the upload's positions. */
 sb_status sb_write_particles_device(sb_engine *e, const void *device_particles);
+
+/* sb_write_beams_device -- overwrites target_length and / or last_length of every beam of the latest upload from a device buffer
+ * in sb_read_state_device's beam layout (max_beams * 16 B, { target_length, last_length, strain, stress } at beam DATA indices; only
+ * the rows of the latest upload's beams are read, through the latest mapping -- also after an upload that cut beams).  fields:
+ * SB_BEAM_TARGET_LENGTH and / or SB_BEAM_LAST_LENGTH (zero or any other bit: SB_ERR_INVALID); strain and stress are never
+ * imported.  Every copy the engine keeps of a beam is written.  A removed beam's row is written but inert: a later export shows the
+ * imported floats, nothing else changes.  Counts, the mapping, pending break flags, the substep count and the particles are
+ * untouched; the spatial hash and the hybrid schedule stay as they are (beams do not move particles).  Every later result is the one
+ * the engine would compute had those floats been these bytes all along; values move bit for bit (NaN payloads, -0.0).  Only
+ * enqueues; the first call after an upload builds a table and waits for the stream once.  Errors as above; SB_ERR_INVALID also for
+ * a NULL source or a buffer that is not 16-byte aligned (checked, like `fields`, before anything touches a device). */
+#define SB_BEAM_TARGET_LENGTH 1u
+#define SB_BEAM_LAST_LENGTH   2u
+sb_status sb_write_beams_device(sb_engine *e, const void *device_beams, uint32_t fields);
+
+/* sb_checkpoint_device / sb_restore_device -- going back without the host.  A checkpoint is a copy of everything a run mutates
+ * (particles, beam state, per-tile promise flags, pending break flags, the beams delete passes removed, the substep count), held in
+ * device memory of the engine's: one per engine, a later one replaces it; every sb_write_buffers (plan-keeping or not),
+ * sb_halo_configure and sb_destroy drop it.  After sb_restore_device, sb_load_buffers, sb_get_counts, sb_read_state_device, every
+ * report (summary, bodies, contacts, body_summary, render), sb_get_info "substeps_done" and every later step / frame / delete pass
+ * give the bits the engine gave -- or would have given -- at and after the checkpoint, on every path and collision mode: also for a
+ * checkpoint taken mid-frame with break flags pending, and across delete passes that removed beams since.  Physics constants and
+ * user input are NOT part of it: they stay as they are now.  The spatial hash starts again and the hybrid schedule looks at the
+ * scene afresh, as after sb_write_particles_device.  Several restores from one checkpoint are allowed; sb_restore_device without a
+ * checkpoint is SB_ERR_STATE.  The first checkpoint after an upload allocates (SB_ERR_OOM: the engine is unchanged and there is no
+ * checkpoint) and may wait for the stream once; later checkpoints, and every restore, only enqueue.  sb_get_info:
+ * "checkpoint_bytes" (device bytes the checkpoint holds; 0: none), "checkpoints" and "restores" (calls since sb_create). */
+sb_status sb_checkpoint_device(sb_engine *e);
+sb_status sb_restore_device(sb_engine *e);
 
 /* ---- one summary row of the whole scene, reduced on the device ----
  * What a driver asks of a big scene between steps -- is everything still finite, did it leave the box, how much energy is left,

@@ -719,7 +719,8 @@ sb_status sb_grid_reset_hash(sb_engine *e)
 
 // "Just uploaded" (DESIGN.md 4.2): everything a RUN mutates besides the particle and beam state itself goes back to what a
 // fresh upload starts from.  The one writer of it: the upload that plans calls it once behind its allocations, the upload that
-// keeps the plan calls it in place of planning; a new per-run flag, mask or counter is reset HERE.  Enqueued on the engine's
+// keeps the plan calls it in place of planning; a new per-run flag, mask or counter is reset HERE -- and gets a row in
+// sbs_walk_run_state's table (sb_state_io.hip: restored / reset / not part of a checkpoint).  Enqueued on the engine's
 // stream (a blocking stream: ordered with the null-stream copies of the upload); the caller synchronises.
 static sb_status reset_run_state(sb_engine *e)
 {
@@ -2017,6 +2018,7 @@ sb_status sb_get_info(sb_engine *e, const char *key, uint64_t *value)
     else if (k == "material_mode") *value = e->mat_mode;
     else if (k == "materials") *value = e->nmat;
     else if (k == "local_index_bits") *value = e->lbits;
+    else if (sbs_info(e, key, value)) {} // sb_state_io.hip: "checkpoint_bytes", "checkpoints", "restores"
     else if (sbm_info(e, key, value)) {} // sb_summary.hip: "summary_partials", ...
     else if (sbd_info(e, key, value)) {} // sb_bodies.hip: "bodies_table_build_us", ...
     else if (sbc_info(e, key, value)) {} // sb_contacts.hip: "contacts_table_build_us", ...
@@ -2437,6 +2439,7 @@ sb_status sb_write_buffers(sb_engine *e, const void *metadata, size_t metadata_b
 {
     sbr_invalidate(e);
     sbs_invalidate(e);
+    sbs_drop_checkpoint(e);
     if (e) e->halo_configured = e->guard_on = false; // (also when the upload keeps the plan: a new scene has no halo, no guard)
     SB_GUARDED(e, sb_write_buffers_impl(e, metadata, metadata_bytes, mapping, mapping_bytes, particles, particles_bytes,
                                         beams, beams_bytes))
@@ -2453,6 +2456,7 @@ sb_status sb_halo_configure(sb_engine *e, const uint32_t *ghost_particles, uint3
                             const uint32_t *send_particles, uint32_t n_sp, const uint32_t *ghost_beams,
                             uint32_t n_gb, const uint32_t *send_beams, uint32_t n_sb)
 {
+    sbs_drop_checkpoint(e); // (ghost zones: the three calls of the state in device memory refuse such an engine)
     SB_GUARDED(e, sb_halo_configure_impl(e, ghost_particles, n_gp, send_particles, n_sp, ghost_beams, n_gb, send_beams, n_sb))
 }
 

@@ -298,6 +298,19 @@ struct SbStateIoState {
     void *d_bsm = nullptr, *d_bsm_labels = nullptr, *d_bsm_out = nullptr; // scratch; sb_bodies_device's labels / the host's; sb_body_summary's device-side result
     size_t cap_bsm_pinv = 0, cap_bsm_tab = 0, cap_bsm = 0, cap_bsm_labels = 0, cap_bsm_out = 0; // bytes
     double bsm_build_ms = 0.0;
+    // sb_write_beams_device: per ENGINE beam slot the data index of its record in the latest upload (0xFFFFFFFF: a beam an upload
+    // removed); on the blocked layout also the rest length of every blocked beam, in owner order (the plastic promise's rule)
+    bool imp_valid = false;
+    uint32_t *d_imp_row = nullptr;
+    float *d_imp_rest = nullptr;
+    size_t cap_imp_row = 0, cap_imp_rest = 0;
+    double imp_build_ms = 0.0;
+    // sb_checkpoint_device: one block holding a copy of everything a run mutates (sbs_walk_run_state), and the host's words of it
+    void *d_ckpt = nullptr;
+    size_t cap_ckpt = 0, ckpt_bytes = 0;      // ckpt_bytes == 0: no checkpoint
+    uint32_t ck_cur = 0, ck_bcur = 0, ck_delete_gen = 0;
+    uint64_t ck_substeps_done = 0;
+    uint64_t checkpoints = 0, restores = 0;   // calls since sb_create
 };
 
 inline void sb_set_error(sb_engine *e, const char *text) { if (e) e->err = text; else sb_set_create_error(text); } // (sb_error.h)
@@ -336,6 +349,8 @@ sb_status sbr_copy_table(sb_engine *e, const uint32_t **copy); // per engine bea
 // sb_state_io.hip
 void sbs_invalidate(sb_engine *e);      // an upload replaced the scene: the next export builds its tables again
 void sbs_release(sb_engine *e);         // everything sb_state_io allocated (sb_destroy)
+void sbs_drop_checkpoint(sb_engine *e); // sb_write_buffers, sb_halo_configure: the checkpoint is of a scene that is no more
+bool sbs_info(sb_engine *e, const char *key, uint64_t *value); // its sb_get_info keys (false: not one of them)
 // sb_summary.hip
 bool sbm_info(sb_engine *e, const char *key, uint64_t *value); // its sb_get_info keys (false: not one of them)
 // sb_bodies.hip

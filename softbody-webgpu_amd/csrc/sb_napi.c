@@ -60,6 +60,8 @@ static struct {
     sb_status (*delete_pass)(sb_engine *);
     sb_status (*halo_delete_ghosts)(sb_engine *);
     sb_status (*sync)(sb_engine *);
+    sb_status (*checkpoint_device)(sb_engine *);
+    sb_status (*restore_device)(sb_engine *);
     sb_status (*step_timed)(sb_engine *, uint32_t, float *);
     sb_status (*mark)(sb_engine *, uint32_t);
     sb_status (*mark_elapsed)(sb_engine *, uint32_t, uint32_t, float *);
@@ -165,6 +167,8 @@ static napi_value js_load(napi_env env, napi_callback_info info)
     SYM(delete_pass, "sb_delete_pass");
     SYM(halo_delete_ghosts, "sb_halo_delete_ghosts");
     SYM(sync, "sb_sync");
+    SYM(checkpoint_device, "sb_checkpoint_device");
+    SYM(restore_device, "sb_restore_device");
     SYM(step_timed, "sb_step_timed");
     SYM(mark, "sb_mark");
     SYM(mark_elapsed, "sb_mark_elapsed");
@@ -407,7 +411,7 @@ static napi_value js_simple(napi_env env, napi_callback_info info, int which, co
     CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     sb_engine *e = argc >= 1 ? get_engine(env, argv[0]) : NULL;
     if (!e) return NULL;
-    simple_fn f = which == 0 ? sb.frame : which == 1 ? sb.delete_pass : which == 2 ? sb.sync : which == 4 ? sb.peer_exchange : which == 5 ? sb.halo_delete_ghosts : sb.destroy;
+    simple_fn f = which == 0 ? sb.frame : which == 1 ? sb.delete_pass : which == 2 ? sb.sync : which == 4 ? sb.peer_exchange : which == 5 ? sb.halo_delete_ghosts : which == 6 ? sb.checkpoint_device : which == 7 ? sb.restore_device : sb.destroy;
     if (which == 3) get_box(env, argv[0])->e = NULL; /* whatever sb_destroy says, the pointer is gone */
     sb_status st = f(e);
     if (st != SB_OK) return throw_status(env, which == 3 ? NULL : e, st, name);
@@ -419,6 +423,9 @@ static napi_value js_sync(napi_env env, napi_callback_info info) { return js_sim
 static napi_value js_destroy(napi_env env, napi_callback_info info) { return js_simple(env, info, 3, "sb_destroy"); }
 static napi_value js_peer_exchange(napi_env env, napi_callback_info info) { return js_simple(env, info, 4, "sb_peer_exchange"); }
 static napi_value js_halo_delete_ghosts(napi_env env, napi_callback_info info) { return js_simple(env, info, 5, "sb_halo_delete_ghosts"); }
+/* checkpoint(handle) / restore(handle): the run state kept in, and put back from, device memory (sb_checkpoint_device / sb_restore_device) */
+static napi_value js_checkpoint(napi_env env, napi_callback_info info) { return js_simple(env, info, 6, "sb_checkpoint_device"); }
+static napi_value js_restore(napi_env env, napi_callback_info info) { return js_simple(env, info, 7, "sb_restore_device"); }
 
 static napi_value js_step(napi_env env, napi_callback_info info, int timed)
 {
@@ -1281,6 +1288,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"partitionRankCounts", js_partition_rank_counts}, {"partitionRankScene", js_partition_rank_scene},
         {"partitionRankIds", js_partition_rank_ids}, {"partitionPeer", js_partition_peer}, {"render", js_render},
         {"summary", js_summary}, {"bodies", js_bodies}, {"contacts", js_contacts}, {"bodySummary", js_body_summary},
+        {"checkpoint", js_checkpoint}, {"restore", js_restore},
         {"partitionRankGuard", js_partition_rank_guard}, {"haloGuard", js_halo_guard}, {"haloGuardStatus", js_halo_guard_status},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -92,6 +92,7 @@ class SbRenderOptions(ctypes.Structure):
 
 
 RENDER_MAX_RESOLUTION = 16384
+BEAM_TARGET_LENGTH, BEAM_LAST_LENGTH = 1, 2          # SB_BEAM_* (sb_write_beams_device)
 
 GUARD_SLAB, GUARD_BAND, GUARD_BEAM, GUARD_MOTION = 1, 2, 4, 8     # SB_GUARD_* (include/softbody.h sb_halo_guard)
 GUARD_KIND_NAMES = {GUARD_SLAB: "A", GUARD_BAND: "B", GUARD_BEAM: "C", GUARD_MOTION: "D"}
@@ -197,6 +198,9 @@ def load_library():
     L.sb_render_device.argtypes = [vp, ctypes.POINTER(SbRenderOptions), vp]
     L.sb_read_state_device.argtypes = [vp, vp, vp, vp]
     L.sb_write_particles_device.argtypes = [vp, vp]
+    L.sb_write_beams_device.argtypes = [vp, vp, u32]
+    L.sb_checkpoint_device.argtypes = [vp]
+    L.sb_restore_device.argtypes = [vp]
     L.sb_summary_device.argtypes = [vp, ctypes.POINTER(SbSummaryOptions), vp, vp]
     L.sb_summary.argtypes = [vp, ctypes.POINTER(SbSummaryOptions), vp, vp]
     L.sb_bodies_device.argtypes = [vp, ctypes.POINTER(SbBodiesOptions), vp, vp, vp]
@@ -518,6 +522,29 @@ class Engine:
         Only enqueues; with a tensor, the import waits for torch's current stream and torch's current stream for the import."""
         ptr, t = self._device_buffer("write_particles_device", src, "float32", self.max_particles * PARTICLE_STRIDE)
         self._ordered(t, lambda: load_library().sb_write_particles_device(self._h, ctypes.c_void_p(ptr)))
+
+    def write_beams_device(self, src, target_length=True, last_length=False):
+        """Overwrite target_length and / or last_length of every beam of the latest upload from beam rows on the GPU (the layout of
+        read_state_device's `beams`: {target_length, last_length, strain, stress} at beam data indices; strain and stress are never
+        imported): a device pointer (int) or a contiguous float32 torch tensor of at least max_beams * 16 bytes on the engine's
+        device.  Every copy the engine keeps of a beam is written, bit for bit; a removed beam's row is written but inert.  Only
+        enqueues; with a tensor, the import waits for torch's current stream and torch's current stream for the import."""
+        fields = (BEAM_TARGET_LENGTH if target_length else 0) | (BEAM_LAST_LENGTH if last_length else 0)
+        if not fields:
+            raise ValueError("write_beams_device: neither target_length nor last_length is asked for")
+        ptr, t = self._device_buffer("write_beams_device", src, "float32", self.max_beams * 16)
+        self._ordered(t, lambda: load_library().sb_write_beams_device(self._h, ctypes.c_void_p(ptr), fields))
+
+    def checkpoint(self):
+        """Keep a copy of everything a run mutates in device memory of the engine's (one per engine: a later checkpoint replaces it;
+        every write_buffers and halo_configure drops it).  Only enqueues (the first one after an upload allocates)."""
+        self._check(load_library().sb_checkpoint_device(self._h))
+
+    def restore(self):
+        """Back to the checkpoint: every read-back, report and later step gives the bits the engine gave, or would have given, at
+        and after checkpoint() -- also mid-frame and across delete passes.  Physics constants and user input stay as they are now.
+        Only enqueues; EngineError (SB_ERR_STATE) without a checkpoint."""
+        self._check(load_library().sb_restore_device(self._h))
 
     # ---- one summary row of the whole scene (sb_summary_device / sb_summary; DESIGN.md 5.18)
 

@@ -79,6 +79,10 @@ class WGPUSoftbodyEngine {
     async contacts(opts) { return this.worker.contacts(opts); }
     /** one row of 24 statistics per body of the whole scene, ranked by size, exact counts and ranks (engineWorker.js bodySummary) */
     async bodySummary(opts) { return this.worker.bodySummary(opts); }
+    /** keep the run state in device memory (engineWorker.js checkpoint) */
+    async checkpoint() { return this.worker.checkpoint(); }
+    /** back to the checkpoint; rejects with the engine's message when there is none (engineWorker.js restore) */
+    async restore() { return this.worker.restore(); }
     /** n frames back to back */
     async run(frames) { for (let i = 0; i < frames && this.running; i++) await this.frame(); }
 

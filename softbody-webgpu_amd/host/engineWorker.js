@@ -177,6 +177,29 @@ class WGPUSoftbodyEngineWorker {
         });
     }
 
+    /**
+     * Keep a copy of everything a run mutates in device memory of the engine's (sb_checkpoint_device): one per engine, a later one
+     * replaces it, every writeBuffers drops it.  No state travels to the host.
+     */
+    async checkpoint() {
+        await this.lock.run(() => {
+            if (!this.uploaded) throw new Error('checkpoint before writeBuffers');
+            this.addon.checkpoint(this.handle);
+        });
+    }
+
+    /**
+     * Back to the checkpoint (sb_restore_device): every later frame, read-back and report gives the bits the engine gave, or would
+     * have given, at and after checkpoint().  Physics constants and user input stay as they are now.  Rejects with the engine's
+     * message when there is no checkpoint.
+     */
+    async restore() {
+        await this.lock.run(() => {
+            if (!this.uploaded) throw new Error('restore before writeBuffers');
+            this.addon.restore(this.handle);
+        });
+    }
+
     /** benchmark granularity: n substeps, no delete pass; returns device milliseconds */
     async step(n) {
         return this.lock.run(() => this.addon.stepTimed(this.handle, n));

@@ -183,6 +183,11 @@ export class WGPUSoftbodyEngine {
     contacts(opts?: ContactsOptions): Promise<SceneContacts>;
     /** statistics per body of the whole scene (sb_body_summary), the same bits on every run, found on the GPU */
     bodySummary(opts?: BodySummaryOptions): Promise<SceneBodySummary>;
+    /** keep a copy of everything a run mutates in device memory (sb_checkpoint_device): one per engine, dropped by every upload */
+    checkpoint(): Promise<void>;
+    /** back to the checkpoint (sb_restore_device): later frames and read-backs give the bits they gave, or would have given, after
+     *  checkpoint(); rejects with the engine's message when there is none */
+    restore(): Promise<void>;
     run(frames: number): Promise<void>;
     destroy(): Promise<void>;
     readonly destroyed: boolean;
@@ -230,6 +235,10 @@ export class WGPUSoftbodyEngineWorker {
     contacts(opts?: ContactsOptions): Promise<SceneContacts>;
     /** sb_body_summary: one row of 24 statistics per body, ranked by size, with exact counts and ranks, without a read-back of the scene */
     bodySummary(opts?: BodySummaryOptions): Promise<SceneBodySummary>;
+    /** sb_checkpoint_device: the run state kept in device memory of the engine's; no state travels to the host */
+    checkpoint(): Promise<void>;
+    /** sb_restore_device: the run state put back from the checkpoint; rejects with the engine's message when there is none */
+    restore(): Promise<void>;
     onMessage(msg: { type: WGPUSoftbodyEngineMessageTypes, data?: unknown }): Promise<void>;
     destroy(): Promise<void>;
 }
