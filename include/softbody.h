@@ -223,7 +223,10 @@ sb_status sb_get_counts(sb_engine *e, uint32_t *particles, uint32_t *beams);
  * "body_summary_kernel_scratch_bytes" (the same two figures over every kernel sb_body_summary may launch; scratch must be 0),
  * "acc_dirty_tiles" / "plastic_tiles" (tiles whose zero-acceleration / never-yielded promise flag in the CURRENT state
  * buffer is nonzero; 0 on engines without tiles, "plastic_tiles" 0 without a blocked plan.  Both wait for the stream and
- * copy one word per tile to the host: for tests, never inside a timed region). */
+ * copy one word per tile to the host: for tests, never inside a timed region),
+ * "state_half" (0 / 1: the particle buffer, and with it the row of acceleration flags, that is current; every substep launch
+ * flips it), "beam_state_half" (0 / 1: the current half of the blocked layout's target / last-length / plastic double buffers;
+ * 0 without a blocked plan).  Both read host words only: tests assert the half an import, checkpoint or restore ran on. */
 sb_status sb_get_info(sb_engine *e, const char *key, uint64_t *value);
 
 /* ---- multi-GPU halo exchange; one engine per rank/GPU, each holding its

@@ -1990,6 +1990,8 @@ sb_status sb_get_info(sb_engine *e, const char *key, uint64_t *value)
             *value = n;
         }
     }
+    else if (k == "state_half") *value = e->cur;                       // the particle buffer (and acceleration-flag row) that is current: flips per launch
+    else if (k == "beam_state_half") *value = e->bk.K ? e->bk.cur : 0; // the blocked layout's current half of target / last / plastic (0: no blocked plan)
     else if (k.rfind("grid_stamp_", 0) == 0) { // -DSB_STAMPS builds: stamps of one mid-grid workgroup of the last substep launch, 10 ns ticks since its start (diagnostic)
         const int i = atoi(key + 11);
         SB_HIP(e, hipStreamSynchronize(e->stream));

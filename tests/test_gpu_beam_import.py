@@ -90,7 +90,8 @@ def test_import_equals_host_edit(sb, oracle, what, mode, path, kw):
     """1: an edit imported through write_beams_device (A) == the same buffers uploaded (B) == the oracle given them, two frames
     later, bit for bit.  What each case is there for: the tiled-grid case cuts many beams (every COPY of a beam must be written,
     asserted through "beam_copies"); the blocked case needs the second target half and the plastic flag (a tile that is not flagged
-    never reads its targets).  The check against libraries with one of these left out has NOT been made yet."""
+    never reads its targets).  Which of these writes which test notices, and on which half of the double buffers, is worked out
+    over a model of the store in tests/test_state_io_model_cpu.py; tests/test_gpu_state_io_halves.py runs the import on each half."""
     buf = quiet_lattice(sb)
     A = engine(sb, buf, 6000.0, collision_mode=mode, path=path, **kw)
     for _ in range(3):
