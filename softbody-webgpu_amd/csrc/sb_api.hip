@@ -452,6 +452,8 @@ static sb_status upload_blocked(sb_engine *e, const SbBlocking &bl, const SbHost
     k.halo_entries = bl.ent_state.size();
     k.halo_particles = bl.halo_idx.size();
     k.fixed_depth = e->opt.block_substeps != 0;
+    k.odd_offsets = 0;
+    for (uint32_t t = 0; t < T; t++) k.odd_offsets |= (bl.tile_b0[t] & 1u) | ((bl.tile_e0[t] & 1u) << 1) | ((bl.tile_s0[t] & 1u) << 2);
     {
         uint32_t first = 0, n_first = 0; // what a long call's launches look like (sbk_split_call prices the candidates)
         sbk_split_call(960u, blockK, k.fixed_depth, &first, &n_first);
@@ -1914,6 +1916,7 @@ sb_status sb_get_info(sb_engine *e, const char *key, uint64_t *value)
     else if (k == "substep_hbm_bytes") *value = substep_bytes_model(e);
     else if (k == "substeps_per_launch") *value = e->bk.K ? e->bk.k_long : 1; // of a long call (sbk_split_call)
     else if (k == "plan_depth") *value = e->bk.K ? e->bk.K : 1;
+    else if (k == "plan_odd_offsets") *value = e->bk.K ? e->bk.odd_offsets : 0; // (SbBlockedDev::odd_offsets: where a tile's ranges of the plan arrays start)
     else if (k.rfind("block_redundancy_x1000_", 0) == 0) { // beam evaluations per beam and substep of a launch of <k> substeps, in thousandths (ring redundancy of the blocked plan)
         const int d = atoi(key + 23);
         const SbBlockedDev &bk = e->bk.K ? e->bk : e->hy;

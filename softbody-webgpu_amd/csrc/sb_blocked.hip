@@ -64,6 +64,25 @@ struct SbBlockedState {
 #define SB_LANDED(x) asm volatile("" : "+v"(x)) /* a use: the compiler's wait for x goes HERE (inside a rare branch, not at its join) */
 #define SB_BK_DUMMY_A (SB_BK_MAXP * SB_BK_T)      // (what the host packs into dummy_word, sb_api.hip upload_blocked)
 #define SB_BK_DUMMY_B (SB_BK_MAXP * SB_BK_T + 1u)
+// ENTRY SLOTS -> ENTRIES.  The beam phase walks a thread's entry slots in groups of SB_BK_G = 2 and runs a group when the entry
+// behind its FIRST slot is inside the substep's prefix; the second rides along.  A WAVE's group covers 128 consecutive
+// entries of the tile's ring-sorted list: group g of a class holds entries g 2T .. g 2T + 2T - 1 (counted from the class's
+// first entry: 0 for own slots, n_ownb for halo slots), wave w of the workgroup the 128 from g 2T + 128 w on -- its first slot
+// the first 64 of them, lane by lane, its second slot the other 64.  So a wave skips a group as soon as the prefix ends in
+// front of those 128 entries, and a thread's second slot is at most 64 entries past its first.  (Until this mapping slot i
+// held entry tid + i T: a group's second slot lay a whole 512 entries behind its first and a prefix was cut at 512 to 1024
+// entries -- on BASELINE config 2, 8.8 % of the entries a launch of 6 evaluated were past their prefix or padding, 7.8 % of
+// the wave-groups it issued: profiles/blocked_prefix_waste.txt, tools/blocked_prefix_waste.cpp.)
+// Consecutive LANES keep consecutive entries in every slot, as before: the plan sorts a tile's entries so that a wave's
+// endpoint gathers and force sums fall into distinct LDS banks (sb_blocking.h), and its loads and stores of beam state are
+// whole cache lines.  Pairs per THREAD (entries 2 tid, 2 tid + 1: the prefix cut to one entry per thread, the same 128 per
+// wave) put a wave's lanes two particles apart -- two-way bank conflicts on every gather and every ds_add: measured 0.7 %
+// SLOWER than the old mapping where this one is 2 % faster (profiles/blocked_prefix_before_after.json).
+// The LISTS keep their order -- ent_word, ent_state and the owned state arrays are what they were, and so is every kernel
+// that walks them in list order (delete pass, plastic recount, the hybrid copies); only this kernel's view changes.
+// SB_ENT_L(t, il): class-relative list index behind slot `il` of the class for thread t.
+#define SB_ENT_L(t, il) (((uint32_t)(il) >> 1) * (2u * SB_BK_T) + (t) + ((t) & ~63u) + ((uint32_t)(il) & 1u) * 64u)
+static_assert(SB_BK_G == 2 && SB_BK_OWNB % 2u == 0u && SB_BK_HALOB % 2u == 0u, "entry slots pair up inside their class");
 #define SB_BK_ROW 8u // LDS material row: length, 1/length, spring, damp, yield, yield*length, length*limit, limit
 
 #ifndef SB_BK_WAVES_AUX
@@ -220,6 +239,8 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
     // Every request below is UNCONDITIONAL -- a lane with nothing to fetch reads element 0 of the array and discards it: a
     // conditional load is a branch, and behind a dozen exec-mask branches the compiler's bookkeeping of what is in flight
     // degrades to "wait for everything" at the first use of the first index.
+    // list index (inside the tile) of entry slot i: own slots count from 0, halo slots from the tile's own beams
+#define SB_ENT_J(i) ((i) < (int)SB_BK_OWNB ? SB_ENT_L(tid, (i)) : n_ownb + SB_ENT_L(tid, (i) - (int)SB_BK_OWNB))
     const uint32_t nh_load = np_load - n_own, nh_move = np_move - n_own, nhe = ne_load - min(n_ownb, ne_load);
     uint32_t hidx[SB_BK_HALOP], sidx[SB_BK_HALOB];
 #pragma unroll
@@ -229,7 +250,7 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
     }
 #pragma unroll
     for (int i = 0; i < SB_BK_HALOB; i++) {
-        const uint32_t j = tid + (uint32_t)i * SB_BK_T;
+        const uint32_t j = SB_ENT_L(tid, i);
         sidx[i] = bp.ent_state[j < nhe ? s0 + j : 0u];
     }
     float2 pp[SB_BK_MAXP], pv[SB_BK_MAXP], pa[SB_BK_MAXP];
@@ -243,13 +264,13 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
     float tg[SB_BK_MAXB], ls[SB_BK_MAXB], ln[SB_BK_MAXB];
 #pragma unroll
     for (int i = 0; i < SB_BK_OWNB; i++) {
-        const uint32_t j = tid + (uint32_t)i * SB_BK_T;
+        const uint32_t j = SB_ENT_L(tid, i);
         ls[i] = bs.last_r[j < n_ownb ? b0 + j : 0u];
     }
     uint32_t word[SB_BK_MAXB];
 #pragma unroll
     for (int i = 0; i < SB_BK_MAXB; i++) {
-        const uint32_t j = i < (int)SB_BK_OWNB ? tid + (uint32_t)i * SB_BK_T : n_ownb + tid + (uint32_t)(i - (int)SB_BK_OWNB) * SB_BK_T;
+        const uint32_t j = SB_ENT_J(i);
         const bool have = i < (int)SB_BK_OWNB ? j < n_ownb : j < ne_load;
         word[i] = bp.ent_word[have ? e0 + j : 0u];
         ln[i] = MAT == 1 ? bp.ent_length[have ? e0 + j : 0u] : 1.0f;
@@ -258,7 +279,7 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
     // round, because the address waits for the tile's flag
 #pragma unroll
     for (int i = 0; i < SB_BK_OWNB; i++) {
-        const uint32_t j = tid + (uint32_t)i * SB_BK_T;
+        const uint32_t j = SB_ENT_L(tid, i);
         tg[i] = bs.target_r[(own_plastic && j < n_ownb) ? b0 + j : 0u];
     }
     // MAT == 1 (rest lengths that do not fit the dictionary: every scene built the way the reference's editor builds beams):
@@ -276,7 +297,7 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
     }
 #pragma unroll
     for (int i = 0; i < SB_BK_HALOB; i++) {
-        const uint32_t j = tid + (uint32_t)i * SB_BK_T;
+        const uint32_t j = SB_ENT_L(tid, i);
         const uint32_t at = j < nhe ? sidx[i] : 0u;
         tg[SB_BK_OWNB + i] = bs.target_r[nb_plastic ? at : 0u]; // (no tile around has yielded: nothing to gather)
         ls[SB_BK_OWNB + i] = bs.last_r[at];
@@ -285,7 +306,7 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
     const uint32_t pad_word = (SB_BK_PAD0 + 2u * (tid & 63u)) | ((SB_BK_PAD0 + 2u * (tid & 63u) + 1u) << SB_BK_LBITS);
 #pragma unroll
     for (int i = 0; i < SB_BK_MAXB; i++) {
-        const uint32_t j = i < (int)SB_BK_OWNB ? tid + (uint32_t)i * SB_BK_T : n_ownb + tid + (uint32_t)(i - (int)SB_BK_OWNB) * SB_BK_T;
+        const uint32_t j = SB_ENT_J(i);
         const bool have = i < (int)SB_BK_OWNB ? j < n_ownb : j < ne_load;
         word[i] = have ? word[i] : pad_word;
         tg[i] = have ? tg[i] : 1.0f;
@@ -358,7 +379,7 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
 #pragma unroll
         for (int i = 0; i < SB_BK_MAXB; i++) {
             const bool own = i < (int)SB_BK_OWNB;
-            const uint32_t j = own ? tid + (uint32_t)i * SB_BK_T : n_ownb + tid + (uint32_t)(i - (int)SB_BK_OWNB) * SB_BK_T;
+            const uint32_t j = SB_ENT_J(i);
             const bool have = own ? j < n_ownb : j < ne_load;
             if (have && !(own ? own_plastic : nb_plastic))
                 tg[i] = MAT == 2 ? s_mat[SB_BK_ROW * (word[i] >> (2u * SB_BK_LBITS))] : s_len[tid + (uint32_t)i * SB_BK_T];
@@ -391,7 +412,7 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
             const uint32_t dump = bp.tile_b0[bp.ntiles] + tid;
 #pragma unroll
             for (int i = 0; i < (int)SB_BK_OWNB; i++) {
-                uint32_t j = tid + (uint32_t)i * SB_BK_T;
+                uint32_t j = SB_ENT_L(tid, i);
                 asm volatile("" : "+v"(j)); // (or the store addresses of a thread are hoisted out of the substep loop: 48 VGPRs)
                 uint32_t wd = word[i];
                 asm volatile("" : "+v"(wd));
@@ -415,11 +436,12 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
         }
         // ---- beam phase: groups of SB_BK_G entries in straight-line code.  An entry past the prefix (its inputs
         // are no longer the true state) may ride along in a group: its force lands on particles that are not
-        // integrated any more and its state is never stored (owned entries are always inside the prefix).
+        // integrated any more and its state is never stored (owned entries are always inside the prefix).  A group's two
+        // slots are 64 entries apart in the ring-sorted list (SB_ENT_L): a wave stops 128 entries behind the prefix at most.
 #pragma unroll
         for (int i0 = 0; i0 < SB_BK_MAXB; i0 += SB_BK_G) {
             // (the entry number of the group's first slot: own slots count from 0, halo slots from the tile's own beams)
-            const uint32_t j0 = i0 < (int)SB_BK_OWNB ? tid + (uint32_t)i0 * SB_BK_T : n_ownb + tid + (uint32_t)(i0 - (int)SB_BK_OWNB) * SB_BK_T;
+            const uint32_t j0 = SB_ENT_J(i0);
             if ((i0 < (int)SB_BK_OWNB ? j0 < n_ownb : j0 < nbl) && !((SB_BK_ABLATE & 1) && prm.time_step >= 0.0f)) {
                 float2 qa[SB_BK_G], qb[SB_BK_G];
                 SbBeamMat mt[SB_BK_G];
@@ -554,7 +576,7 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
     if (!own_plastic) {
 #pragma unroll
         for (int i = 0; i < SB_BK_OWNB; i++) {
-            const uint32_t j = tid_s + (uint32_t)i * SB_BK_T;
+            const uint32_t j = SB_ENT_L(tid_s, i);
             const float len_i = MAT == 2 ? s_mat[SB_BK_ROW * (word[i] >> (2u * SB_BK_LBITS))] : s_len[tid + (uint32_t)i * SB_BK_T];
             yielded |= j < n_ownb && word[i] != bp.dummy_word && __float_as_uint(tg[i]) != __float_as_uint(len_i);
         }
@@ -563,7 +585,7 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
     if (tid == 0) bs.plastic_w[tile] = plastic_w ? 1u : 0u;
 #pragma unroll
     for (int i = 0; i < SB_BK_OWNB; i++) {
-        const uint32_t j = tid_s + (uint32_t)i * SB_BK_T;
+        const uint32_t j = SB_ENT_L(tid_s, i);
         if (j < n_ownb) {
             if (__builtin_expect(word[i] != bp.dummy_word, 1)) {
                 if (plastic_w) sb_store_wt(&bs.target_w[b0 + j], tg[i]);

@@ -104,6 +104,7 @@ struct SbBlockedDev {
     uint32_t k_long = 0;      // substeps per launch of a long call (what the traffic model prices)
     bool fixed_depth = false; // the caller named the depth (sb_options.block_substeps): every call runs in the fewest launches
     uint64_t entries = 0, halo_entries = 0, halo_particles = 0; // totals of the whole plan (depth K)
+    uint32_t odd_offsets = 0; // bit 0 / 1 / 2: some tile's first own beam (tile_b0) / first entry (tile_e0) / first halo state index (tile_s0) is odd
     uint64_t entries_at[SB_BK_KMAX + 1] = {}, region_at[SB_BK_KMAX + 1] = {}; // totals over the tiles of what a launch of depth k loads
 };
 
