@@ -208,6 +208,9 @@ sb_status sb_get_counts(sb_engine *e, uint32_t *particles, uint32_t *beams);
  * launch has to move with the data layout the engine holds: the launched kernel's own compulsory traffic),
  * "grid_cells", "grid_builds", "grid_wide", "grid_skin_x1000", "material_mode", "materials", "local_index_bits",
  * "render_table_build_us" (host time of sb_render's last draw-table build: the first render after an upload),
+ * "render_wide_particles" / "render_wide_beams" (how many particles / beams the latest sb_render or sb_render_device drew with a
+ * wave each rather than in their own thread: a clipped box of more than 64 pixels, more than 32 clipped points; 0 before the
+ * first render.  Both wait for the stream and copy two words to the host: for tests, never inside a timed region),
  * "halo_guard" (1 while a halo guard is set, sb_halo_guard),
  * "summary_partials" (sb_summary: the partials the last call used), "summary_table_build_us" (host time of its last table build:
  * the first summary after an upload), "summary_kernel_vgprs" / "summary_kernel_scratch_bytes" (the most registers / scratch

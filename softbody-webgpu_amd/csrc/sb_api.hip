@@ -1993,6 +1993,11 @@ sb_status sb_get_info(sb_engine *e, const char *key, uint64_t *value)
             *value = n;
         }
     }
+    else if (k == "render_wide_particles" || k == "render_wide_beams") { // primitives the latest sb_render / sb_render_device drew a wave each (read-only, waits for the stream: for tests)
+        uint32_t c[2];
+        SB_TRY(sbr_wide_counts(e, c));
+        *value = c[k == "render_wide_beams"];
+    }
     else if (k == "state_half") *value = e->cur;                       // the particle buffer (and acceleration-flag row) that is current: flips per launch
     else if (k == "beam_state_half") *value = e->bk.K ? e->bk.cur : 0; // the blocked layout's current half of target / last / plastic (0: no blocked plan)
     else if (k.rfind("grid_stamp_", 0) == 0) { // -DSB_STAMPS builds: stamps of one mid-grid workgroup of the last substep launch, 10 ns ticks since its start (diagnostic)

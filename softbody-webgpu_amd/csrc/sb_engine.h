@@ -346,6 +346,7 @@ void sbk_hybrid_launch(sb_engine *e, const uint32_t *ks, uint32_t count, bool au
 void sbr_invalidate(sb_engine *e);      // an upload replaced the scene: the next render builds its draw tables again
 void sbr_release(sb_engine *e);         // everything sb_render allocated (sb_destroy)
 double sbr_last_build_ms(const sb_engine *e);
+sb_status sbr_wide_counts(sb_engine *e, uint32_t counts[2]); // lengths of the latest render's two wave lists (waits for the stream)
 sb_status sbr_copy_table(sb_engine *e, const uint32_t **copy); // per engine beam slot: the copy read back for it (device; built on first use)
 // sb_state_io.hip
 void sbs_invalidate(sb_engine *e);      // an upload replaced the scene: the next export builds its tables again

@@ -206,6 +206,16 @@ void sbr_release(sb_engine *e)
 
 double sbr_last_build_ms(const sb_engine *e) { return e && e->rs ? e->rs->build_ms : 0.0; }
 
+// the lengths of the two wave lists of the latest render: {particles, beams} (0, 0 before the first); waits for the stream
+sb_status sbr_wide_counts(sb_engine *e, uint32_t counts[2])
+{
+    counts[0] = counts[1] = 0u;
+    if (!e->rs || !e->rs->d_count) return SB_OK;
+    SB_HIP(e, hipStreamSynchronize(e->stream));
+    SB_HIP(e, hipMemcpy(counts, e->rs->d_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return SB_OK;
+}
+
 // per engine beam slot: the copy whose state sb_load_buffers reads back for it (h_copy_of_slot on the device), built at the first
 // use after an upload; the draw tables and sb_state_io.hip's beam export share it (copy may be NULL: build only)
 sb_status sbr_copy_table(sb_engine *e, const uint32_t **copy)

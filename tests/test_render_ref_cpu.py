@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from render_cases import CASES, custom, shuffled  # noqa: F401  (tests/test_gpu_render.py imports shuffled from here)
 from render_ref import ppm, render_ref, v8_hypot
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,38 +56,6 @@ def check(tmp_path, buf, resolution=512, bounds_size=None, particle_radius=None)
     return np.frombuffer(got, np.uint8)
 
 
-def custom(sbp, layout, points, beams):
-    """points: [(x, y)]; beams: [(a, b, strain, stress)] (data indices = slots)."""
-    from softbody_webgpu_amd.layout import BEAM_DTYPE, Buffers
-    buf = Buffers(layout, max(len(points), 1) + 3, max(len(beams), 1) + 3)
-    b = np.zeros(len(beams), dtype=BEAM_DTYPE[layout])
-    for i, (a, c, sn, ss) in enumerate(beams):
-        b[i]["a"], b[i]["b"], b[i]["strain"], b[i]["stress"] = a, c, sn, ss
-        b[i]["length"] = b[i]["target_length"] = 1.0
-    buf.set_scene(np.asarray(points, dtype="<f4"), b)
-    return buf
-
-
-def shuffled(buf, seed):
-    """Slots != data indices: particles and beams moved to permuted data indices, both mappings permuted."""
-    out = buf.copy()
-    rng = np.random.default_rng(seed)
-    P, B, maxP = buf.particle_count, buf.beam_count, buf.max_particles
-    pp = rng.permutation(buf.max_particles)[:P]
-    bp = rng.permutation(buf.max_beams)[:B]
-    out.particles[:] = 0
-    out.particles[pp] = buf.particles[:P]
-    bb = buf.beams[:B].copy()
-    bb["a"] = pp[bb["a"]]
-    bb["b"] = pp[bb["b"]]
-    out.beams[:] = 0
-    out.beams[bp] = bb
-    sp, sbm = rng.permutation(P), rng.permutation(B)
-    out.mapping[:P] = pp[sp]
-    out.mapping[maxP:maxP + B] = bp[sbm]
-    return out
-
-
 # ---------------------------------------------------------------- V8's Math.hypot
 
 @needs_node
@@ -131,54 +100,38 @@ def test_bounds_and_radius(sbp, tmp_path):
     check(tmp_path, buf, 257, bounds_size=700.0, particle_radius=3.0)
 
 
+def check_case(sbp, tmp_path, name, layout=None):
+    """Every picture the case names, against render.js."""
+    case = CASES[name]
+    buf = case.buffers(sbp, layout)
+    return [check(tmp_path, buf, res, bounds_size=S, particle_radius=r) for res, S, r in case.renders]
+
+
 @needs_node
 @pytest.mark.parametrize("layout", [1, 2])
 def test_edges(sbp, tmp_path, layout):
     """Discs cut by every edge and corner, beams that enter, leave and cross the image on every side."""
-    pts = [(-5.0, 500.0), (1005.0, 500.0), (500.0, -4.0), (500.0, 1006.0), (2.0, 3.0), (998.0, 997.0), (-8.0, 1007.0), (1009.0, -9.0),
-           (-300.0, 200.0), (1300.0, 800.0), (200.0, -400.0), (800.0, 1500.0), (-50.0, -70.0), (1100.0, 1200.0), (400.0, 400.0),
-           (-2000.0, 500.5), (3000.0, 499.5)]
-    bms = [(8, 9, 0.1, 0.3), (10, 11, -0.2, -0.4), (12, 13, 0.5, 0.9), (14, 8, 0.0, 0.0), (14, 11, 1.5, -1.5), (15, 16, 0.25, 0.25),
-           (0, 1, 0.3, 0.6), (2, 3, 0.7, -0.7), (6, 7, 0.05, 0.1), (9, 8, 0.2, 0.2)]
-    buf = custom(sbp, layout, pts, bms)
-    check(tmp_path, buf, 128)
-    check(tmp_path, buf, 97, particle_radius=33.0)
+    check_case(sbp, tmp_path, "edges", layout)
 
 
 @needs_node
 def test_slot_order_decides(sbp, tmp_path):
     """Crossing beams of different stress and overlapping discs: the later slot is on top, inner versus ring included."""
-    pts = [(500.0, 500.0), (507.0, 503.0), (512.0, 498.0), (100.0, 100.0), (900.0, 900.0), (100.0, 900.0), (900.0, 100.0),
-           (300.0, 300.0), (300.0, 700.0)]
-    bms = [(3, 4, 0.1, -0.9), (5, 6, 0.6, 0.9), (7, 8, 0.0, 0.3), (8, 7, 0.9, -0.3)]
-    buf = custom(sbp, 1, pts, bms)
-    a = check(tmp_path, buf, 200)
+    a, = check_case(sbp, tmp_path, "slot_order", 1)
     # the same with the slots reversed gives another picture
-    rev = buf.copy()
-    P, B, maxP = buf.particle_count, buf.beam_count, buf.max_particles
-    rev.mapping[:P] = buf.mapping[:P][::-1]
-    rev.mapping[maxP:maxP + B] = buf.mapping[maxP:maxP + B][::-1]
-    b = check(tmp_path, rev, 200)
+    b, = check_case(sbp, tmp_path, "slot_order_reversed", 1)
     assert not np.array_equal(a, b)
 
 
 @needs_node
 def test_nonfinite_strain_stress(sbp, tmp_path):
-    nan, inf = float("nan"), float("inf")
-    pts = [(100.0 + 80.0 * i, 100.0 + 60.0 * (i % 3)) for i in range(12)] + [(100.0 + 80.0 * i, 800.0) for i in range(12)]
-    vals = [(nan, 0.0), (0.0, nan), (inf, 0.0), (-inf, 0.0), (0.0, inf), (0.0, -inf), (nan, nan), (inf, -inf), (1e30, -1e30),
-            (-0.0, -0.0), (0.5, 1e-8), (-3.0, -2.0)]
-    bms = [(i, 12 + i, sn, ss) for i, (sn, ss) in enumerate(vals)]
-    check(tmp_path, custom(sbp, 2, pts, bms), 160)
+    check_case(sbp, tmp_path, "nonfinite_colours", 2)
 
 
 @needs_node
 @pytest.mark.parametrize("layout", [1, 2])
 def test_shuffled_mapping(sbp, tmp_path, layout):
-    buf = sbp.scenes.default_buffers(layout, 256, 512)
-    buf.beams["strain"][:buf.beam_count] = np.linspace(-1.5, 1.5, buf.beam_count, dtype="f4")
-    buf.beams["stress"][:buf.beam_count] = np.linspace(1.2, -1.2, buf.beam_count, dtype="f4")
-    check(tmp_path, shuffled(buf, 9), 400)
+    check_case(sbp, tmp_path, "shuffled_mapping", layout)
 
 
 @needs_node
