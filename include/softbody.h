@@ -212,16 +212,16 @@ sb_status sb_get_counts(sb_engine *e, uint32_t *particles, uint32_t *beams);
  * wave each rather than in their own thread: a clipped box of more than 64 pixels, more than 32 clipped points; 0 before the
  * first render.  Both wait for the stream and copy two words to the host: for tests, never inside a timed region),
  * "halo_guard" (1 while a halo guard is set, sb_halo_guard),
- * "summary_partials" (sb_summary: the partials the last call used), "summary_table_build_us" (host time of its last table build:
- * the first summary after an upload), "summary_kernel_vgprs" / "summary_kernel_scratch_bytes" (the most registers / scratch
+ * "summary_partials" (sb_summary: the partials the last call used), "summary_table_build_us" (host time of the last build of the tables
+ * its latest call read: the scene tables the reports share and its own; 0 before its first call), "summary_kernel_vgprs" / "summary_kernel_scratch_bytes" (the most registers / scratch
  * bytes per lane over every kernel a summary may launch, as the runtime reports them; scratch must be 0),
- * "bodies_table_build_us" (sb_bodies: host time of its last table build: the first call after an upload), "bodies_kernel_vgprs" /
+ * "bodies_table_build_us" (sb_bodies: host time of the last build of the shared scene tables its latest call read; 0 before its first call), "bodies_kernel_vgprs" /
  * "bodies_kernel_scratch_bytes" (the same two figures over every kernel sb_bodies may launch; scratch must be 0),
- * "contacts_table_build_us" (sb_contacts: host time of its last table build: the first call after an upload),
+ * "contacts_table_build_us" (sb_contacts: host time of the last build of the shared scene table its latest call read; 0 before its first call),
  * "contacts_cells_per_side" (the cells per side its counting sort uses for the scene as it is now; 1: the all-pairs test),
  * "contacts_kernel_vgprs" / "contacts_kernel_scratch_bytes" (the same two figures over every kernel sb_contacts may launch),
- * "body_summary_table_build_us" (sb_body_summary: host time of its last table build: the first call after an upload),
- * "body_summary_scratch_bytes" (device bytes its calls hold so far: scratch, labels, its two tables, sb_body_summary's result),
+ * "body_summary_table_build_us" (sb_body_summary: host time of the last build of the shared scene tables its latest call read; 0 before its first call),
+ * "body_summary_scratch_bytes" (device bytes its calls hold so far: scratch, labels, the two scene tables it reads, sb_body_summary's result),
  * "body_summary_kernel_vgprs" /
  * "body_summary_kernel_scratch_bytes" (the same two figures over every kernel sb_body_summary may launch; scratch must be 0),
  * "acc_dirty_tiles" / "plastic_tiles" (tiles whose zero-acceleration / never-yielded promise flag in the CURRENT state

@@ -2430,19 +2430,6 @@ sb_status sb_get_stream(sb_engine *e, void **hip_stream)
     return SB_OK;
 }
 
-// C++ exceptions must not cross the C boundary: the entry points that allocate host memory run
-// their bodies under a catch-all that turns std::bad_alloc (and anything else) into a status.
-#define SB_GUARDED(e, call)                                                                   \
-    try {                                                                                     \
-        return (call);                                                                        \
-    } catch (const std::bad_alloc &) {                                                        \
-        if (e) (e)->err = "out of host memory";                                               \
-        return SB_ERR_OOM;                                                                    \
-    } catch (const std::exception &ex) {                                                      \
-        if (e) (e)->err = std::string("internal error: ") + ex.what();                        \
-        return SB_ERR_INVALID;                                                                \
-    }
-
 sb_status sb_write_buffers(sb_engine *e, const void *metadata, size_t metadata_bytes, const void *mapping,
                            size_t mapping_bytes, const void *particles, size_t particles_bytes,
                            const void *beams, size_t beams_bytes)

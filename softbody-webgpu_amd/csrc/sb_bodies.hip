@@ -27,15 +27,13 @@
 // as their left neighbour are added by the first lane of their run (sbd_add_runs): neighbouring data indices mostly share a body.
 // Integers only: the outputs do not depend on the order in which anything above happens.
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cstring>
 #include <new>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
-#include "sb_engine.h"
+#include "sb_report.h"
 
 #define SBD_BLOCK 256u
 #define SBD_NONE 0xFFFFFFFFu
@@ -59,15 +57,8 @@ SB_DEV int32_t sbd_find_halving(int32_t *parent, int32_t x)
 // the wave calls it (l = -1: nothing to add).
 SB_DEV void sbd_add_runs(int32_t *sizes, int32_t l, uint32_t col)
 {
-    const uint32_t lane = __lane_id();
-    const int32_t left = __shfl_up(l, 1);
-    const bool head = lane == 0u || left != l;
-    const unsigned long long heads = __ballot(head);
-    if (head && l >= 0) {
-        const unsigned long long rest = lane == 63u ? 0ull : heads >> (lane + 1u);
-        const uint32_t run = rest ? (uint32_t)__ffsll(rest) : 64u - lane; // up to the next head, or to the end of the wave
-        atomicAdd(&sizes[2u * (size_t)l + col], (int)run);
-    }
+    const uint32_t run = sbq_run_length((uint32_t)l, l >= 0);
+    if (run) atomicAdd(&sizes[2u * (size_t)l + col], (int)run);
 }
 
 // grid over max(n_parent, n_sizes): parent over n_parent words (a particle lives at d: pinv[d] != none, d < np), sizes over
@@ -160,69 +151,6 @@ __global__ __launch_bounds__(64) void k_bodies_counts(const unsigned long long *
 
 // ---------------------------------------------------------------- host side
 
-template <class T>
-static sb_status sbd_grow(sb_engine *e, T **p, size_t &cap, size_t n)
-{
-    n = std::max<size_t>(n, 1);
-    if (*p && cap >= n) return SB_OK;
-    if (*p) {
-        SB_HIP(e, hipStreamSynchronize(e->stream)); // a call in flight may still use it
-        SB_HIP(e, hipFree(*p));
-        *p = nullptr;
-        cap = 0;
-    }
-    SB_HIP(e, hipMalloc((void **)p, n * sizeof(T)));
-    cap = n;
-    return SB_OK;
-}
-
-// data index -> internal particle (e->h_pidx inverted) up to the highest data index in use, and per caller beam slot of the latest
-// upload {data index of A, data index of B, engine slot} as three planes.  Every endpoint is checked here to name a data index
-// at which a particle lives: the kernels index parent[] with it.
-static sb_status sbd_build_tables(sb_engine *e)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!e->sio) e->sio = new SbStateIoState();
-    SbStateIoState &s = *e->sio;
-    const uint32_t P = e->P, maxP = e->opt.max_particles, Bu = sb_user_beams(e);
-    if (e->h_pidx.size() != P || e->h_beams.size() != e->B) SB_FAIL(e, SB_ERR_STATE, "sb_bodies: host shadows of the scene are inconsistent");
-    uint32_t np = 0;
-    for (uint32_t i = 0; i < P; i++) np = std::max(np, e->h_pidx[i] + 1u);
-    if (np > maxP) SB_FAIL(e, SB_ERR_STATE, "sb_bodies: particle data index outside the scene");
-    std::vector<uint32_t> inv(std::max<uint32_t>(np, 1), SBD_NONE);
-    for (uint32_t i = 0; i < P; i++) inv[e->h_pidx[i]] = i;
-    const size_t n = std::max<uint32_t>(Bu, 1);
-    std::vector<uint32_t> tab(3 * n, 0u);
-    std::atomic<uint32_t> bad{0u};
-    const uint32_t B = e->B;
-    sbt::parallel_ranges(Bu, 1 << 16, [&](size_t u0, size_t u1) {
-        for (size_t u = u0; u < u1; u++) {
-            const uint32_t slot = sb_user_slot(e, u);
-            if (slot >= B) {
-                bad.store(1u, std::memory_order_relaxed);
-                continue;
-            }
-            const SbHostBeam &h = e->h_beams[slot];
-            if (h.da >= np || h.db >= np || inv[h.da] == SBD_NONE || inv[h.db] == SBD_NONE) {
-                bad.store(1u, std::memory_order_relaxed);
-                continue;
-            }
-            tab[u] = h.da, tab[n + u] = h.db, tab[2 * n + u] = slot;
-        }
-    });
-    if (bad.load()) SB_FAIL(e, SB_ERR_STATE, "sb_bodies: beam slot or endpoint outside the scene");
-    SB_TRY(sbd_grow(e, &s.d_bod_pinv, s.cap_bod_pinv, inv.size()));
-    SB_TRY(sbd_grow(e, &s.d_bod_tab, s.cap_bod_tab, tab.size()));
-    SB_HIP(e, hipMemcpyAsync(s.d_bod_pinv, inv.data(), inv.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    SB_HIP(e, hipMemcpyAsync(s.d_bod_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    SB_HIP(e, hipStreamSynchronize(e->stream)); // (the host vectors go out of scope)
-    s.bod_np = np;
-    s.bod_nslots = Bu;
-    s.bod_valid = true;
-    s.bod_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SB_OK;
-}
-
 static sb_status sbd_enqueue(sb_engine *e, const sb_bodies_options *o, void *labels, void *sizes, void *counts, bool host)
 {
     if (!e) return SB_ERR_INVALID;
@@ -230,51 +158,44 @@ static sb_status sbd_enqueue(sb_engine *e, const sb_bodies_options *o, void *lab
     if (!labels && !sizes && !counts) SB_FAIL(e, SB_ERR_INVALID, "%s: no output asked for", what);
     if (((uintptr_t)labels & 3u) || ((uintptr_t)sizes & 3u)) SB_FAIL(e, SB_ERR_INVALID, "%s: labels and sizes must be 4-byte aligned", what);
     if ((uintptr_t)counts & 7u) SB_FAIL(e, SB_ERR_INVALID, "%s: counts must be 8-byte aligned", what);
-    if (o && o->struct_size != 0 && o->struct_size != sizeof(sb_bodies_options))
-        SB_FAIL(e, SB_ERR_INVALID, "%s: sb_bodies_options.struct_size %u != %zu", what, o->struct_size, sizeof(sb_bodies_options));
-    if (o && o->struct_size)
-        for (uint32_t r : o->reserved)
-            if (r) SB_FAIL(e, SB_ERR_INVALID, "%s: reserved option words must be zero", what);
-    if (e->opt.max_particles > 0x80000000u || e->opt.max_beams > 0x80000000u)
-        SB_FAIL(e, SB_ERR_INVALID, "%s: capacities above 2^31 are not labelled", what);
-    if (!e->loaded) SB_FAIL(e, SB_ERR_STATE, "%s before sb_write_buffers", what);
-    if (e->halo_configured || e->n_ghost_p || e->n_send_p || e->n_ghost_b || e->n_send_b || e->n_peers || e->mailbox)
-        SB_FAIL(e, SB_ERR_UNSUPPORTED, "%s: the engine has ghost zones or peers configured (bodies across ranks are not handled)", what);
-    SB_HIP(e, hipSetDevice(e->device));
-    if (!e->sio || !e->sio->bod_valid) SB_TRY(sbd_build_tables(e));
+    SB_TRY(sbq_preflight(e, what, o, "labelled", "bodies across ranks are not handled"));
+    SB_TRY(sbq_need(e, "sb_bodies", SBQ_PARTICLES | SBQ_BEAMS));
     SbStateIoState &s = *e->sio;
+    s.bod_build_ms = s.part_ms + s.beam_ms;
 
     // where the launches write: the caller's device memory, or the engine's own (what the caller did not ask for but a later
     // stage needs: up to the highest data index in use; sb_bodies: whole outputs, copied to the host below)
-    const uint32_t maxP = e->opt.max_particles, np = s.bod_np, n = s.bod_nslots;
+    const uint32_t maxP = e->opt.max_particles, np = s.np, n = s.nslots;
     const bool want_sizes = sizes || counts;
     const uint32_t n_parent = labels ? maxP : np, n_sizes = !want_sizes ? 0u : sizes ? maxP : np;
     int32_t *d_parent = (int32_t *)labels, *d_sizes = (int32_t *)sizes;
     long long *d_counts = (long long *)counts;
     if (host || !labels) {
-        SB_TRY(sbd_grow(e, &s.d_bod_parent, s.cap_bod_parent, (size_t)n_parent));
-        d_parent = s.d_bod_parent;
+        SB_TRY(s.buf[SBD_B_PARENT].grow(e, (size_t)n_parent * sizeof(int32_t)));
+        d_parent = s.buf[SBD_B_PARENT].as<int32_t>();
     }
     if (want_sizes && (host || !sizes)) {
-        SB_TRY(sbd_grow(e, &s.d_bod_sizes, s.cap_bod_sizes, (size_t)2 * n_sizes));
-        d_sizes = s.d_bod_sizes;
+        SB_TRY(s.buf[SBD_B_SIZES].grow(e, (size_t)2 * n_sizes * sizeof(int32_t)));
+        d_sizes = s.buf[SBD_B_SIZES].as<int32_t>();
     }
+    unsigned long long *d_acc = nullptr;
     if (counts) {
-        SB_TRY(sbd_grow(e, &s.d_bod_acc, s.cap_bod_acc, (size_t)SBD_COUNTS + SB_BODY_WORDS));
-        if (host) d_counts = (long long *)(s.d_bod_acc + SBD_COUNTS);
+        SB_TRY(s.buf[SBD_B_ACC].grow(e, ((size_t)SBD_COUNTS + SB_BODY_WORDS) * sizeof(unsigned long long)));
+        d_acc = s.buf[SBD_B_ACC].as<unsigned long long>();
+        if (host) d_counts = (long long *)(d_acc + SBD_COUNTS);
     }
-    unsigned long long *d_acc = counts ? s.d_bod_acc : nullptr;
+    const uint32_t *d_pinv = s.buf[SBQ_B_PINV].as<uint32_t>(), *d_tab = s.buf[SBQ_B_TAB].as<uint32_t>(); // (three planes of the four are read)
     const uint32_t *dead = e->B && e->delete_gen ? e->d_dead_gen : nullptr; // as sb_load_buffers (fetch_dead) sees it
     auto blocks = [](uint32_t k) { return (k + SBD_BLOCK - 1u) / SBD_BLOCK; };
 
-    k_bodies_init<<<std::max(blocks(std::max(n_parent, n_sizes)), 1u), SBD_BLOCK, 0, e->stream>>>(s.d_bod_pinv, np, d_parent, n_parent,
+    k_bodies_init<<<std::max(blocks(std::max(n_parent, n_sizes)), 1u), SBD_BLOCK, 0, e->stream>>>(d_pinv, np, d_parent, n_parent,
                                                                                                   want_sizes ? d_sizes : nullptr, n_sizes, d_acc);
-    if (n) k_bodies_union<<<blocks(n), SBD_BLOCK, 0, e->stream>>>(s.d_bod_tab, n, dead, d_parent);
+    if (n) k_bodies_union<<<blocks(n), SBD_BLOCK, 0, e->stream>>>(d_tab, n, dead, d_parent);
     if (np) {
         if (want_sizes) k_bodies_flatten<true><<<blocks(np), SBD_BLOCK, 0, e->stream>>>(d_parent, np, d_sizes);
         else k_bodies_flatten<false><<<blocks(np), SBD_BLOCK, 0, e->stream>>>(d_parent, np, nullptr);
     }
-    if (want_sizes && n) k_bodies_beams<<<blocks(n), SBD_BLOCK, 0, e->stream>>>(s.d_bod_tab, n, dead, d_parent, d_sizes);
+    if (want_sizes && n) k_bodies_beams<<<blocks(n), SBD_BLOCK, 0, e->stream>>>(d_tab, n, dead, d_parent, d_sizes);
     if (counts) {
         if (np) k_bodies_roots<<<blocks(np), SBD_BLOCK, 0, e->stream>>>(d_parent, d_sizes, np, d_acc);
         k_bodies_counts<<<1, 64, 0, e->stream>>>(d_acc, d_counts);
@@ -295,46 +216,26 @@ bool sbd_info(sb_engine *e, const char *key, uint64_t *value)
     const std::string k(key);
     if (k == "bodies_table_build_us") *value = e->sio ? (uint64_t)(e->sio->bod_build_ms * 1000.0 + 0.5) : 0u;
     else if (k == "bodies_kernel_vgprs" || k == "bodies_kernel_scratch_bytes") { // the most over every kernel a call may launch
-        const void *ks[] = {(const void *)k_bodies_init, (const void *)k_bodies_union, (const void *)k_bodies_flatten<true>,
+        const std::vector<const void *> ks = {(const void *)k_bodies_init, (const void *)k_bodies_union, (const void *)k_bodies_flatten<true>,
                             (const void *)k_bodies_flatten<false>, (const void *)k_bodies_beams, (const void *)k_bodies_roots,
                             (const void *)k_bodies_counts};
-        uint64_t most = 0;
-        for (const void *f : ks) {
-            hipFuncAttributes fa{};
-            if (hipSetDevice(e->device) != hipSuccess || hipFuncGetAttributes(&fa, f) != hipSuccess) {
-                (void)hipGetLastError();
-                return false;
-            }
-            most = std::max<uint64_t>(most, k == "bodies_kernel_vgprs" ? (uint64_t)fa.numRegs : (uint64_t)fa.localSizeBytes);
-        }
-        *value = most;
+        return sbq_kernel_most(e, ks, k == "bodies_kernel_vgprs", value);
     }
     else return false;
     return true;
 }
-
-#define SBD_GUARDED(e, call)                                                   \
-    try {                                                                      \
-        return (call);                                                         \
-    } catch (const std::bad_alloc &) {                                         \
-        if (e) (e)->err = "out of host memory";                                \
-        return SB_ERR_OOM;                                                     \
-    } catch (const std::exception &ex) {                                       \
-        if (e) (e)->err = std::string("internal error: ") + ex.what();         \
-        return SB_ERR_INVALID;                                                 \
-    }
 
 extern "C" {
 
 sb_status sb_bodies_device(sb_engine *e, const sb_bodies_options *opts, void *device_labels_i32, void *device_sizes_i32,
                            void *device_counts_i64)
 {
-    SBD_GUARDED(e, sbd_enqueue(e, opts, device_labels_i32, device_sizes_i32, device_counts_i64, false))
+    SB_GUARDED(e, sbd_enqueue(e, opts, device_labels_i32, device_sizes_i32, device_counts_i64, false))
 }
 
 sb_status sb_bodies(sb_engine *e, const sb_bodies_options *opts, int32_t *labels, int32_t *sizes, int64_t *counts)
 {
-    SBD_GUARDED(e, sbd_enqueue(e, opts, labels, sizes, counts, true))
+    SB_GUARDED(e, sbd_enqueue(e, opts, labels, sizes, counts, true))
 }
 
 } // extern "C"

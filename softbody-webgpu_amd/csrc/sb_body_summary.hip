@@ -8,13 +8,12 @@
 // k_batch_body_summary sorts a scene in the LDS of one workgroup; here the members lie in HBM, a scene holds a million bodies or
 // one, and the call may only enqueue: nothing loops on a host read-back and no workgroup waits for another.  One launch a stage:
 //   k_bsum_stage     a thread per t < Wn (Wn the smallest power of two >= the highest data index in use + 1): the data index
-//                    d = bitrev(t), its group g (through the call's own data index -> internal particle table; `none` where no
+//                    d = bitrev(t), its group g (through the shared data index -> internal particle table, sb_report.hip; `none` where no
 //                    particle lives or the label names no group), the key  g << 32 | bitrev32(d).  bitrev32(d) is r = bitrev(d)
 //                    over log2 W bits, left-aligned: the order of  label * W + r, and t ascending IS r ascending
 //   sort             a stable LSD radix sort of the keys by their label bits alone (the input is in r order, so that is the
 //                    order by the whole key; the keys are unique): per pass k_bsum_hist (digit counts per block of SBY_SORT keys),
-//                    an exclusive scan of the counts (a sum per scan block, the block sums scanned by ONE workgroup that loops
-//                    with a running carry, added back), k_bsum_scatter (the rank of a key inside its block by wave ballots and a
+//                    an exclusive scan of the counts (sbq_scan, sb_report.hip), k_bsum_scatter (the rank of a key inside its block by wave ballots and a
 //                    count per wave and round in LDS: the order comes from the keys' places alone, never from which atomic won)
 //   k_bsum_leaves    a thread per sorted position: the six leaves of its particle (+0.0 for one that is not finite: such a leaf
 //                    changes no partial sum but a zero's sign, and a zero sum is written as +0.0), its order-free particle words,
@@ -36,22 +35,19 @@
 // Everything that reaches an output is either a double sum whose operands and order the keys fix, or an integer (count, minimum,
 // maximum of ordered keys): no schedule can change a bit.  The file only READS the engine.
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cstring>
 #include <new>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
-#include "sb_engine.h"
+#include "sb_report.h"
 #include "sb_batch.h" // sbb_finite, sbb_fkey / sbb_unkey, SBB_QNAN, sbb_pow2_at_least: the batch row's own helpers
 
 #define SBY_BLOCK 256u
 #define SBY_WAVES (SBY_BLOCK / 64u)
-#define SBY_PER 4u                        // keys (sort) / words (scan) / beam slots a thread owns
+#define SBY_PER 4u                        // keys (sort) / beam slots a thread owns
 #define SBY_SORT (SBY_BLOCK * SBY_PER)    // keys of a sort block: 1024
-#define SBY_SCAN (SBY_BLOCK * SBY_PER)    // words of a scan block: 1024
 #define SBY_RADIX_BITS 8u
 #define SBY_RADIX 256u                    // = SBY_BLOCK: a thread per digit where the counts are scanned
 #define SBY_GROUPS (SBY_PER * SBY_WAVES)  // (round, wave) pairs of a sort block, in key order
@@ -164,77 +160,6 @@ __global__ __launch_bounds__(SBY_BLOCK) void k_bsum_scatter(const unsigned long 
         const uint32_t dig = (uint32_t)(key[q] >> shift) & mask;
         const uint32_t at = s_base[dig] + s_cnt[q * SBY_WAVES + wave][dig] + below[q];
         if (at < n) out[at] = key[q]; // (always: the counts add up to n)
-    }
-}
-
-// ---- exclusive scan of n 32-bit words in place: bsum[b] = the sum of scan block b; bsum scanned by one workgroup (its total to
-// *total); word k = bsum[block of k] + the words of the block before k
-SB_DEV uint32_t sby_block_sum(uint32_t v, uint32_t *s_wave, uint32_t *before)
-{
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (uint32_t off = 1u; off < 64u; off <<= 1) {
-        const uint32_t u = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += u;
-    }
-    if (lane == 63u) s_wave[wave] = inc;
-    __syncthreads();
-    uint32_t base = inc - v, total = 0u;
-#pragma unroll
-    for (uint32_t w = 0; w < SBY_WAVES; w++) {
-        const uint32_t t = s_wave[w];
-        base += w < wave ? t : 0u;
-        total += t;
-    }
-    __syncthreads(); // (s_wave may be written again)
-    *before = base;
-    return total;
-}
-
-__global__ __launch_bounds__(SBY_BLOCK) void k_bsum_scan_reduce(const uint32_t *__restrict__ in, uint64_t n, uint32_t *__restrict__ bsum)
-{
-    __shared__ uint32_t s_wave[SBY_WAVES];
-    const uint64_t k0 = (uint64_t)blockIdx.x * SBY_SCAN + threadIdx.x * SBY_PER;
-    uint32_t v = 0u, before;
-#pragma unroll
-    for (uint32_t q = 0; q < SBY_PER; q++)
-        if (k0 + q < n) v += in[k0 + q];
-    const uint32_t total = sby_block_sum(v, s_wave, &before);
-    if (threadIdx.x == 0u) bsum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(SBY_BLOCK) void k_bsum_scan_sums(uint32_t *bsum, uint32_t nb, uint32_t *total)
-{
-    __shared__ uint32_t s_wave[SBY_WAVES];
-    uint32_t carry = 0u;
-    for (uint32_t at = 0; at < nb; at += SBY_BLOCK) { // (uniform)
-        const uint32_t k = at + threadIdx.x;
-        const uint32_t v = k < nb ? bsum[k] : 0u;
-        uint32_t before;
-        const uint32_t sum = sby_block_sum(v, s_wave, &before);
-        if (k < nb) bsum[k] = carry + before;
-        carry += sum;
-    }
-    if (total && threadIdx.x == 0u) *total = carry;
-}
-
-__global__ __launch_bounds__(SBY_BLOCK) void k_bsum_scan_add(uint32_t *data, uint64_t n, const uint32_t *__restrict__ bsum)
-{
-    __shared__ uint32_t s_wave[SBY_WAVES];
-    const uint64_t k0 = (uint64_t)blockIdx.x * SBY_SCAN + threadIdx.x * SBY_PER;
-    uint32_t w[SBY_PER], v = 0u, before;
-#pragma unroll
-    for (uint32_t q = 0; q < SBY_PER; q++) {
-        w[q] = k0 + q < n ? data[k0 + q] : 0u;
-        v += w[q];
-    }
-    (void)sby_block_sum(v, s_wave, &before);
-    uint32_t at = bsum[blockIdx.x] + before;
-#pragma unroll
-    for (uint32_t q = 0; q < SBY_PER; q++) {
-        if (k0 + q < n) data[k0 + q] = at;
-        at += w[q];
     }
 }
 
@@ -511,68 +436,6 @@ __global__ __launch_bounds__(SBY_BLOCK) void k_bsum_rank(const unsigned long lon
 
 // ---------------------------------------------------------------- host side
 
-static sb_status sby_grow(sb_engine *e, void **p, size_t &cap, size_t bytes)
-{
-    bytes = std::max<size_t>(bytes, 16);
-    if (*p && cap >= bytes) return SB_OK;
-    if (*p) {
-        SB_HIP(e, hipStreamSynchronize(e->stream)); // a call in flight may still use it
-        SB_HIP(e, hipFree(*p));
-        *p = nullptr;
-        cap = 0;
-    }
-    SB_HIP(e, hipMalloc(p, bytes));
-    cap = bytes;
-    return SB_OK;
-}
-
-// data index -> internal particle (e->h_pidx inverted) up to the highest data index in use, and per caller beam slot of the
-// latest upload {data index of A, data index of B, engine slot, the copy read back for it} as four planes.  Every endpoint is
-// checked here to name a data index at which a particle lives, every copy to lie inside the beam arrays: the kernels index with them.
-static sb_status sby_build_tables(sb_engine *e)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    SbStateIoState &s = *e->sio;
-    const uint32_t P = e->P, maxP = e->opt.max_particles, Bu = sb_user_beams(e), B = e->B, nbeam = e->nbeam;
-    if (e->h_pidx.size() != P || e->h_beams.size() != B || e->h_copy_of_slot.size() < B)
-        SB_FAIL(e, SB_ERR_STATE, "sb_body_summary: host shadows of the scene are inconsistent");
-    uint32_t np = 0;
-    for (uint32_t i = 0; i < P; i++) np = std::max(np, e->h_pidx[i] + 1u);
-    if (np > maxP) SB_FAIL(e, SB_ERR_STATE, "sb_body_summary: particle data index outside the scene");
-    std::vector<uint32_t> inv(std::max<uint32_t>(np, 1), SBY_NONE);
-    for (uint32_t i = 0; i < P; i++) inv[e->h_pidx[i]] = i;
-    const size_t n = std::max<uint32_t>(Bu, 1);
-    std::vector<uint32_t> tab(4 * n, 0u);
-    std::atomic<uint32_t> bad{0u};
-    sbt::parallel_ranges(Bu, 1 << 16, [&](size_t u0, size_t u1) {
-        for (size_t u = u0; u < u1; u++) {
-            const uint32_t slot = sb_user_slot(e, u);
-            if (slot >= B) {
-                bad.store(1u, std::memory_order_relaxed);
-                continue;
-            }
-            const SbHostBeam &h = e->h_beams[slot];
-            const uint32_t copy = e->h_copy_of_slot[slot];
-            if (h.da >= np || h.db >= np || inv[h.da] == SBY_NONE || inv[h.db] == SBY_NONE || copy >= nbeam) {
-                bad.store(1u, std::memory_order_relaxed);
-                continue;
-            }
-            tab[u] = h.da, tab[n + u] = h.db, tab[2 * n + u] = slot, tab[3 * n + u] = copy;
-        }
-    });
-    if (bad.load()) SB_FAIL(e, SB_ERR_STATE, "sb_body_summary: beam slot, endpoint or copy outside the scene");
-    SB_TRY(sby_grow(e, (void **)&s.d_bsm_pinv, s.cap_bsm_pinv, inv.size() * sizeof(uint32_t)));
-    SB_TRY(sby_grow(e, (void **)&s.d_bsm_tab, s.cap_bsm_tab, tab.size() * sizeof(uint32_t)));
-    SB_HIP(e, hipMemcpyAsync(s.d_bsm_pinv, inv.data(), inv.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    SB_HIP(e, hipMemcpyAsync(s.d_bsm_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    SB_HIP(e, hipStreamSynchronize(e->stream)); // (the host vectors go out of scope)
-    s.bsm_np = np;
-    s.bsm_nslots = Bu;
-    s.bsm_valid = true;
-    s.bsm_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SB_OK;
-}
-
 static uint32_t sby_bits(uint64_t most) // bits that hold every value 0 .. most
 {
     uint32_t b = 1u;
@@ -581,15 +444,6 @@ static uint32_t sby_bits(uint64_t most) // bits that hold every value 0 .. most
 }
 
 static uint32_t sby_blocks(uint64_t k, uint32_t per) { return (uint32_t)((k + per - 1u) / per); }
-
-// exclusive scan of data[0 .. n) in place, the sum to *total (may be NULL)
-static void sby_scan(sb_engine *e, uint32_t *data, uint64_t n, uint32_t *bsum, uint32_t *total)
-{
-    const uint32_t nb = sby_blocks(n, SBY_SCAN);
-    k_bsum_scan_reduce<<<nb, SBY_BLOCK, 0, e->stream>>>(data, n, bsum);
-    k_bsum_scan_sums<<<1, SBY_BLOCK, 0, e->stream>>>(bsum, nb, total);
-    k_bsum_scan_add<<<nb, SBY_BLOCK, 0, e->stream>>>(data, n, bsum);
-}
 
 // Stable sort of at most n_max keys (the number on the device where n_dev is given) by their bits 32 .. 32 + bits - 1, between
 // the buffers a and b; returns the one that holds the result.  hist: SBY_RADIX words per sort block; bsum: a word per scan block.
@@ -601,7 +455,7 @@ static unsigned long long *sby_sort(sb_engine *e, unsigned long long *a, unsigne
     for (uint32_t p = 0, at = 0; p < passes; p++, at += per) {
         const uint32_t width = std::min(per, bits - at), shift = 32u + at, mask = (1u << width) - 1u;
         k_bsum_hist<<<nb, SBY_BLOCK, 0, e->stream>>>(a, n_max, n_dev, shift, mask, hist, nb);
-        sby_scan(e, hist, (uint64_t)SBY_RADIX * nb, bsum, nullptr);
+        sbq_scan<uint32_t>(e, hist, (uint64_t)SBY_RADIX * nb, bsum, hist, nullptr);
         k_bsum_scatter<<<nb, SBY_BLOCK, 0, e->stream>>>(a, b, n_max, n_dev, shift, mask, hist, nb);
         std::swap(a, b);
     }
@@ -623,30 +477,21 @@ static sb_status sby_enqueue(sb_engine *e, const sb_body_summary_options *o, con
 {
     if (!e) return SB_ERR_INVALID;
     const char *what = host ? "sb_body_summary" : "sb_body_summary_device";
-    if (o && o->struct_size != 0 && o->struct_size != sizeof(sb_body_summary_options))
-        SB_FAIL(e, SB_ERR_INVALID, "%s: sb_body_summary_options.struct_size %u != %zu", what, o->struct_size, sizeof(sb_body_summary_options));
-    const bool given = o && o->struct_size;
+    const bool given = o && o->struct_size == sizeof(sb_body_summary_options);
     const uint32_t maxP = e->opt.max_particles;
     const uint64_t max_rows = given ? o->max_rows : std::min<uint64_t>(SB_BODY_SUMMARY_DEFAULT_ROWS, maxP);
-    if (given)
-        for (uint32_t r : o->reserved)
-            if (r) SB_FAIL(e, SB_ERR_INVALID, "%s: reserved option words must be zero", what);
     if (!rows && !rows64 && !rank) SB_FAIL(e, SB_ERR_INVALID, "%s: no output asked for", what);
     if (max_rows == 0 || max_rows > maxP)
         SB_FAIL(e, SB_ERR_INVALID, "%s: max_rows %llu is not in 1 .. max_particles (%u)", what, (unsigned long long)max_rows, maxP);
     if (((uintptr_t)labels & 3u) || ((uintptr_t)rows & 3u) || ((uintptr_t)rank & 3u))
         SB_FAIL(e, SB_ERR_INVALID, "%s: labels, rows and rank must be 4-byte aligned", what);
     if ((uintptr_t)rows64 & 7u) SB_FAIL(e, SB_ERR_INVALID, "%s: rows_i64 must be 8-byte aligned", what);
-    if (maxP > 0x80000000u || e->opt.max_beams > 0x80000000u) SB_FAIL(e, SB_ERR_INVALID, "%s: capacities above 2^31 are not handled", what);
-    if (!e->loaded) SB_FAIL(e, SB_ERR_STATE, "%s before sb_write_buffers", what);
-    if (e->halo_configured || e->n_ghost_p || e->n_send_p || e->n_ghost_b || e->n_send_b || e->n_peers || e->mailbox)
-        SB_FAIL(e, SB_ERR_UNSUPPORTED, "%s: the engine has ghost zones or peers configured (bodies across ranks are not handled)", what);
-    SB_HIP(e, hipSetDevice(e->device));
-    if (!e->sio) e->sio = new SbStateIoState();
-    if (!e->sio->bsm_valid) SB_TRY(sby_build_tables(e));
+    SB_TRY(sbq_preflight(e, what, o, "handled", "bodies across ranks are not handled"));
+    SB_TRY(sbq_need(e, "sb_body_summary", SBQ_PARTICLES | SBQ_BEAMS | SBQ_COPIES));
     SbStateIoState &s = *e->sio;
+    s.bsm_build_ms = s.part_ms + s.beam_ms + s.copy_ms;
 
-    const uint32_t np = s.bsm_np, n = s.bsm_nslots, Wn = sbb_pow2_at_least(std::max(np, 1u));
+    const uint32_t np = s.np, n = s.nslots, Wn = sbb_pow2_at_least(std::max(np, 1u));
     uint32_t logWn = 0u;
     while ((1u << logWn) < Wn) logWn++;
     // the word of "no group" in a key: above every label that names a group (the engine's own labels are data indices in use)
@@ -658,10 +503,10 @@ static sb_status sby_enqueue(sb_engine *e, const sb_body_summary_options *o, con
     const size_t o_keys_a = cv.take((size_t)Wn * 8), o_keys_b = cv.take((size_t)Wn * 8), o_rkeys = cv.take((size_t)Wn * 8);
     const size_t o_col = cv.take((size_t)Wn * 8 * SBY_NSUM), o_pst = cv.take((size_t)Wn * 4 * SBY_NPST), o_bst = cv.take((size_t)Wn * 4 * SBY_NBST);
     const size_t o_ord = cv.take((size_t)Wn * 4), o_ghead = cv.take((size_t)Wn * 4), o_gcnt = cv.take((size_t)Wn * 4), o_rank_of = cv.take((size_t)Wn * 4);
-    const size_t o_hist = cv.take((size_t)hist_words * 4), o_bsum = cv.take((size_t)sby_blocks(std::max<uint64_t>(hist_words, Wn), SBY_SCAN) * 4);
+    const size_t o_hist = cv.take((size_t)hist_words * 4), o_bsum = cv.take((size_t)sby_blocks(std::max<uint64_t>(hist_words, Wn), SBQ_SCAN) * 4);
     const size_t o_ctl = cv.take(SBY_NCTL * 4);
-    SB_TRY(sby_grow(e, &s.d_bsm, s.cap_bsm, cv.at));
-    char *m = (char *)s.d_bsm;
+    SB_TRY(s.buf[SBY_B_SCRATCH].grow(e, cv.at));
+    char *m = s.buf[SBY_B_SCRATCH].as<char>();
     unsigned long long *keys_a = (unsigned long long *)(m + o_keys_a), *keys_b = (unsigned long long *)(m + o_keys_b);
     unsigned long long *rkeys = (unsigned long long *)(m + o_rkeys);
     double *col = (double *)(m + o_col);
@@ -675,29 +520,29 @@ static sb_status sby_enqueue(sb_engine *e, const sb_body_summary_options *o, con
     long long *d_rows64 = (long long *)rows64;
     int32_t *d_rank = (int32_t *)rank;
     const size_t b_rows = (size_t)max_rows * SB_BODY_SUMMARY_WORDS * sizeof(float), b_rows64 = (size_t)max_rows * SB_BODY_SUMMARY_COUNT_WORDS * sizeof(int64_t);
-    if (host || !labels) SB_TRY(sby_grow(e, &s.d_bsm_labels, s.cap_bsm_labels, (size_t)maxP * sizeof(int32_t)));
+    if (host || !labels) SB_TRY(s.buf[SBY_B_LABELS].grow(e, (size_t)maxP * sizeof(int32_t)));
     if (host) {
         SbyCarve out;
         const size_t o_r64 = out.take(rows64 ? b_rows64 : 0), o_r = out.take(rows ? b_rows : 0), o_k = out.take(rank ? (size_t)maxP * 4 : 0);
-        SB_TRY(sby_grow(e, &s.d_bsm_out, s.cap_bsm_out, out.at));
-        char *w = (char *)s.d_bsm_out;
+        SB_TRY(s.buf[SBY_B_OUT].grow(e, out.at));
+        char *w = s.buf[SBY_B_OUT].as<char>();
         if (rows64) d_rows64 = (long long *)(w + o_r64);
         if (rows) d_rows = (float *)(w + o_r);
         if (rank) d_rank = (int32_t *)(w + o_k);
         if (labels) {
-            SB_HIP(e, hipMemcpyAsync(s.d_bsm_labels, labels, (size_t)maxP * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-            d_labels = (const int32_t *)s.d_bsm_labels;
+            SB_HIP(e, hipMemcpyAsync(s.buf[SBY_B_LABELS].p, labels, (size_t)maxP * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+            d_labels = s.buf[SBY_B_LABELS].as<int32_t>();
         }
     }
     if (!labels) { // the engine's own bodies: sb_bodies_device's labelling, on the same stream, nothing waits
-        const sb_status st = sb_bodies_device(e, nullptr, s.d_bsm_labels, nullptr, nullptr);
+        const sb_status st = sb_bodies_device(e, nullptr, s.buf[SBY_B_LABELS].p, nullptr, nullptr);
         if (st != SB_OK) return st;
-        d_labels = (const int32_t *)s.d_bsm_labels;
+        d_labels = s.buf[SBY_B_LABELS].as<int32_t>();
     }
 
     const SbParticleArrays &c = e->part[e->cur];
     const uint32_t *dead = e->B && e->delete_gen ? e->d_dead_gen : nullptr; // as sb_load_buffers (fetch_dead) sees it
-    const uint32_t *pinv = (const uint32_t *)s.d_bsm_pinv, *tab = (const uint32_t *)s.d_bsm_tab;
+    const uint32_t *pinv = s.buf[SBQ_B_PINV].as<uint32_t>(), *tab = s.buf[SBQ_B_TAB].as<uint32_t>();
     const uint32_t grid_w = sby_blocks(Wn, SBY_BLOCK);
 
     k_bsum_stage<<<grid_w, SBY_BLOCK, 0, e->stream>>>(pinv, np, d_labels, none, Wn, logWn, keys_a);
@@ -709,7 +554,7 @@ static sb_status sby_enqueue(sb_engine *e, const sb_body_summary_options *o, con
     if (n)
         k_bsum_beams<<<sby_blocks(n, SBY_PER * SBY_BLOCK), SBY_BLOCK, 0, e->stream>>>(tab, n, dead, e->d_broken, e->beams.strain, e->beams.stress,
                                                                                       d_labels, none, keys, Wn, bst);
-    sby_scan(e, ord, Wn, bsum, ctl + SBY_C_HEADS);
+    sbq_scan<uint32_t>(e, ord, Wn, bsum, ord, ctl + SBY_C_HEADS);
     const uint32_t cbits = logWn + 1u, cmask = (uint32_t)((1ull << cbits) - 1ull); // a group holds at most Wn particles
     k_bsum_groups<<<grid_w, SBY_BLOCK, 0, e->stream>>>(keys, Wn, none, ord, cmask, ghead, gcnt, rkeys, ctl);
     const unsigned long long *sorted = sby_sort(e, rkeys, spare, Wn, ctl + SBY_C_GROUPS, cbits, hist, bsum);
@@ -736,49 +581,32 @@ bool sby_info(sb_engine *e, const char *key, uint64_t *value)
 {
     const std::string k(key);
     if (k == "body_summary_table_build_us") *value = e->sio ? (uint64_t)(e->sio->bsm_build_ms * 1000.0 + 0.5) : 0u;
-    else if (k == "body_summary_scratch_bytes") *value = e->sio ? (uint64_t)(e->sio->cap_bsm + e->sio->cap_bsm_labels + e->sio->cap_bsm_pinv + e->sio->cap_bsm_tab + e->sio->cap_bsm_out) : 0u; // everything the calls so far hold on the device: scratch, labels, the two tables, sb_body_summary's result
+    else if (k == "body_summary_scratch_bytes") { // everything its calls so far hold on the device: scratch, labels, the two tables they read, sb_body_summary's result
+        const SbStateIoState *s = e->sio;
+        *value = s && s->buf[SBY_B_SCRATCH].cap ? (uint64_t)(s->buf[SBY_B_SCRATCH].cap + s->buf[SBY_B_LABELS].cap + s->buf[SBQ_B_PINV].cap + s->buf[SBQ_B_TAB].cap + s->buf[SBY_B_OUT].cap) : 0u;
+    }
     else if (k == "body_summary_kernel_vgprs" || k == "body_summary_kernel_scratch_bytes") { // the most over every kernel a call may launch
-        const void *ks[] = {(const void *)k_bsum_stage, (const void *)k_bsum_hist, (const void *)k_bsum_scatter, (const void *)k_bsum_scan_reduce,
-                            (const void *)k_bsum_scan_sums, (const void *)k_bsum_scan_add, (const void *)k_bsum_leaves, (const void *)k_bsum_level,
-                            (const void *)k_bsum_beams, (const void *)k_bsum_groups, (const void *)k_bsum_rank_of, (const void *)k_bsum_rows,
-                            (const void *)k_bsum_rank};
-        uint64_t most = 0;
-        for (const void *f : ks) {
-            hipFuncAttributes fa{};
-            if (hipSetDevice(e->device) != hipSuccess || hipFuncGetAttributes(&fa, f) != hipSuccess) {
-                (void)hipGetLastError();
-                return false;
-            }
-            most = std::max<uint64_t>(most, k == "body_summary_kernel_vgprs" ? (uint64_t)fa.numRegs : (uint64_t)fa.localSizeBytes);
-        }
-        *value = most;
+        std::vector<const void *> ks = {(const void *)k_bsum_stage, (const void *)k_bsum_hist, (const void *)k_bsum_scatter, (const void *)k_bsum_leaves,
+                                        (const void *)k_bsum_level, (const void *)k_bsum_beams, (const void *)k_bsum_groups, (const void *)k_bsum_rank_of,
+                                        (const void *)k_bsum_rows, (const void *)k_bsum_rank};
+        for (const void *f : sbq_scan_kernels(false)) ks.push_back(f); // (32-bit words only)
+        return sbq_kernel_most(e, ks, k == "body_summary_kernel_vgprs", value);
     }
     else return false;
     return true;
 }
-
-#define SBY_GUARDED(e, call)                                                   \
-    try {                                                                      \
-        return (call);                                                         \
-    } catch (const std::bad_alloc &) {                                         \
-        if (e) (e)->err = "out of host memory";                                \
-        return SB_ERR_OOM;                                                     \
-    } catch (const std::exception &ex) {                                       \
-        if (e) (e)->err = std::string("internal error: ") + ex.what();         \
-        return SB_ERR_INVALID;                                                 \
-    }
 
 extern "C" {
 
 sb_status sb_body_summary_device(sb_engine *e, const sb_body_summary_options *opts, const void *device_labels_i32, void *device_rows_f32,
                                  void *device_rows_i64, void *device_rank_i32)
 {
-    SBY_GUARDED(e, sby_enqueue(e, opts, device_labels_i32, device_rows_f32, device_rows_i64, device_rank_i32, false))
+    SB_GUARDED(e, sby_enqueue(e, opts, device_labels_i32, device_rows_f32, device_rows_i64, device_rank_i32, false))
 }
 
 sb_status sb_body_summary(sb_engine *e, const sb_body_summary_options *opts, const int32_t *labels, float *rows, int64_t *rows_i64, int32_t *rank)
 {
-    SBY_GUARDED(e, sby_enqueue(e, opts, labels, rows, rows_i64, rank, true))
+    SB_GUARDED(e, sby_enqueue(e, opts, labels, rows, rows_i64, rank, true))
 }
 
 } // extern "C"

@@ -6,14 +6,12 @@
 // sb_batch_contacts.hip, expression for expression, compiled with the same flags), everything named by particle DATA index.
 // k_batch_contacts holds a scene in the LDS of one workgroup; here the scene lies in HBM, and the call may only enqueue: nothing
 // loops on a host read-back and no workgroup waits for another.  A counting sort by cell in global memory, one launch per stage:
-//   k_contacts_bin      a thread per data index: the position (through the call's own data index -> internal particle table, in
+//   k_contacts_bin      a thread per data index: the position (through the shared data index -> internal particle table, sb_report.hip, in
 //                       the CURRENT particle arrays, as sb_summary.hip's leaf kernel finds it), its cell (sb_grid_coord over
 //                       [0, bounds]^2: out-of-range and NaN coordinates clamp into edge cells), ONE atomicAdd on that cell's
 //                       count per run of lanes with the same cell (sbc_count_runs); the defined row of every data index at which
 //                       no particle lives, up to max_particles (the "fill" stage, fused: it depends on nothing)
-//   k_contacts_reduce / k_contacts_scan_sums / k_contacts_scan_add
-//                       exclusive scan of the G^2 + 1 counts: a sum per block of SBC_SCAN words, the block sums scanned by ONE
-//                       workgroup (which loops over them, carrying the running total: no recursion, no other workgroup), added back
+//   sbq_scan            exclusive scan of the G^2 + 1 counts (sb_report.hip: three launches, no recursion, no workgroup waits)
 //   k_contacts_scatter  sorted[atomicAdd(&start[cell], 1)] = {x, y, d}: every cell's END is left in its word; the order inside a
 //                       cell is the one thing the atomics decide, and nothing below observes it
 //   k_contacts_visit    a thread per sorted record (neighbouring lanes share cells: the nine cell runs hit in L2): the three rows
@@ -29,20 +27,16 @@
 // decision state.  Cost: the sum over particles of the population of their 3 x 3 cells; a scene crowded into one cell is quadratic
 // here, as it is in the step.
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <new>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
-#include "sb_engine.h"
+#include "sb_report.h"
 #include "sb_batch.h" // sb_batch_cell_geometry: the cells' rule
 
 #define SBC_BLOCK 256u
-#define SBC_WAVES (SBC_BLOCK / 64u)
-#define SBC_PER 4u                      // words a thread of a scan block owns
-#define SBC_SCAN (SBC_BLOCK * SBC_PER)  // words of a scan block
 #define SBC_NONE 0xFFFFFFFFu
 #define SBC_MAX_CELLS_PER_SIDE 8192u    // 2^26 cells: 256 MiB of counts
 #define SBC_ALL_PAIRS_MAX 4096u         // particles up to which a degenerate geometry is answered by the all-pairs test
@@ -76,15 +70,8 @@ SB_DEV bool sbc_touch(float mx, float my, float ox, float oy, float thr, float t
 // form: neighbouring data indices mostly lie in neighbouring places).  Every lane of the wave calls it.
 SB_DEV void sbc_count_runs(uint32_t *count, uint32_t c)
 {
-    const uint32_t lane = __lane_id();
-    const uint32_t left = __shfl_up(c, 1);
-    const bool head = lane == 0u || left != c;
-    const unsigned long long heads = __ballot(head);
-    if (head && c != SBC_NONE) {
-        const unsigned long long rest = lane == 63u ? 0ull : heads >> (lane + 1u);
-        const uint32_t run = rest ? (uint32_t)__ffsll(rest) : 64u - lane;
-        atomicAdd(&count[c], run);
-    }
+    const uint32_t run = sbq_run_length(c, c != SBC_NONE);
+    if (run) atomicAdd(&count[c], run);
 }
 
 // grid over max(np, n_rows): bin (d < np where a particle lives) and fill (every other d < n_rows; n_rows = max_particles with
@@ -107,83 +94,6 @@ __global__ __launch_bounds__(SBC_BLOCK) void k_contacts_bin(const uint32_t *__re
     if (c == SBC_NONE && d < n_rows) {
         int32_t *t = touch + (size_t)d * SB_CONTACT_WORDS;
         t[0] = 0, t[1] = no_label, t[2] = 0, t[3] = -1;
-    }
-}
-
-// ---- exclusive scan of n 32-bit words into T words: bsum[b] = the sum of block b; bsum scanned in place by one workgroup (its
-// total to *total); out[k] = bsum[block of k] + the words of the block before k.  `out` may be `in` (T = uint32_t): a thread
-// reads its SBC_PER words before it writes them and nobody else touches them.
-template <class T>
-SB_DEV T sbc_block_sum(T v, T *s_wave, T *before)
-{
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    T inc = v;
-#pragma unroll
-    for (uint32_t off = 1u; off < 64u; off <<= 1) {
-        const T u = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += u;
-    }
-    if (lane == 63u) s_wave[wave] = inc;
-    __syncthreads();
-    T base = inc - v, total = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < SBC_WAVES; w++) {
-        const T t = s_wave[w];
-        base += w < wave ? t : (T)0;
-        total += t;
-    }
-    __syncthreads(); // (s_wave may be written again)
-    *before = base;
-    return total;
-}
-
-template <class T>
-__global__ __launch_bounds__(SBC_BLOCK) void k_contacts_reduce(const uint32_t *__restrict__ in, uint64_t n, T *__restrict__ bsum)
-{
-    __shared__ T s_wave[SBC_WAVES];
-    const uint64_t k0 = (uint64_t)blockIdx.x * SBC_SCAN + threadIdx.x * SBC_PER;
-    T v = 0, before;
-#pragma unroll
-    for (uint32_t q = 0; q < SBC_PER; q++)
-        if (k0 + q < n) v += (T)in[k0 + q];
-    const T total = sbc_block_sum(v, s_wave, &before);
-    if (threadIdx.x == 0u) bsum[blockIdx.x] = total;
-}
-
-template <class T>
-__global__ __launch_bounds__(SBC_BLOCK) void k_contacts_scan_sums(T *bsum, uint32_t nb, unsigned long long *total)
-{
-    __shared__ T s_wave[SBC_WAVES];
-    T carry = 0;
-    for (uint32_t at = 0; at < nb; at += SBC_BLOCK) { // (uniform)
-        const uint32_t k = at + threadIdx.x;
-        const T v = k < nb ? bsum[k] : (T)0;
-        T before;
-        const T sum = sbc_block_sum(v, s_wave, &before);
-        if (k < nb) bsum[k] = carry + before;
-        carry += sum;
-    }
-    if (total && threadIdx.x == 0u) *total = (unsigned long long)carry;
-}
-
-template <class T>
-__global__ __launch_bounds__(SBC_BLOCK) void k_contacts_scan_add(const uint32_t *in, uint64_t n, const T *__restrict__ bsum, T *out)
-{
-    __shared__ T s_wave[SBC_WAVES];
-    const uint64_t k0 = (uint64_t)blockIdx.x * SBC_SCAN + threadIdx.x * SBC_PER;
-    uint32_t w[SBC_PER];
-    T v = 0, before;
-#pragma unroll
-    for (uint32_t q = 0; q < SBC_PER; q++) {
-        w[q] = k0 + q < n ? in[k0 + q] : 0u;
-        v += (T)w[q];
-    }
-    (void)sbc_block_sum(v, s_wave, &before);
-    T at = bsum[blockIdx.x] + before;
-#pragma unroll
-    for (uint32_t q = 0; q < SBC_PER; q++) {
-        if (k0 + q < n) out[k0 + q] = at;
-        at += (T)w[q];
     }
 }
 
@@ -339,28 +249,6 @@ __global__ __launch_bounds__(64) void k_contacts_counts(const unsigned long long
 
 // ---------------------------------------------------------------- host side
 
-// device memory of the call, by use (SbStateIoState::d_con)
-enum { SBC_M_PINV, SBC_M_CELLS, SBC_M_BSUM, SBC_M_SORTED, SBC_M_ABOVE, SBC_M_PLACE, SBC_M_ACC, SBC_M_LABELS, SBC_M_TOUCH, SBC_M_PAIRS, SBC_M_N };
-static_assert(SBC_M_N == SB_CONTACTS_BUFFERS, "SbStateIoState::d_con holds one pointer per use");
-
-static sb_status sbc_grow(sb_engine *e, uint32_t which, size_t bytes, void **out)
-{
-    SbStateIoState &s = *e->sio;
-    bytes = std::max<size_t>(bytes, 16);
-    if (!s.d_con[which] || s.cap_con[which] < bytes) {
-        if (s.d_con[which]) {
-            SB_HIP(e, hipStreamSynchronize(e->stream)); // a call in flight may still use it
-            SB_HIP(e, hipFree(s.d_con[which]));
-            s.d_con[which] = nullptr;
-            s.cap_con[which] = 0;
-        }
-        SB_HIP(e, hipMalloc(&s.d_con[which], bytes));
-        s.cap_con[which] = bytes;
-    }
-    *out = s.d_con[which];
-    return SB_OK;
-}
-
 // The most cells per side for P particles: the largest G with G^2 <= 8 P (at least 1, at most SBC_MAX_CELLS_PER_SIDE).  Eight
 // cells a particle keep the counts a small multiple of the records (4 bytes a cell against 12 a record) while a scene spread
 // over its bounds gets cells of the narrowest width the rule allows; coarser is always right.
@@ -382,52 +270,14 @@ static bool sbc_geometry(const sb_engine *e, SbcGeo *geo)
     return g != 0u;
 }
 
-// data index -> internal particle (e->h_pidx inverted) up to the highest data index in use: the call's own table
-static sb_status sbc_build_tables(sb_engine *e)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    SbStateIoState &s = *e->sio;
-    const uint32_t P = e->P, maxP = e->opt.max_particles;
-    if (e->h_pidx.size() != P) SB_FAIL(e, SB_ERR_STATE, "sb_contacts: host shadows of the scene are inconsistent");
-    uint32_t np = 0;
-    for (uint32_t i = 0; i < P; i++) np = std::max(np, e->h_pidx[i] + 1u);
-    if (np > maxP) SB_FAIL(e, SB_ERR_STATE, "sb_contacts: particle data index outside the scene");
-    std::vector<uint32_t> inv(std::max<uint32_t>(np, 1), SBC_NONE);
-    for (uint32_t i = 0; i < P; i++) inv[e->h_pidx[i]] = i;
-    void *d_pinv = nullptr;
-    SB_TRY(sbc_grow(e, SBC_M_PINV, inv.size() * sizeof(uint32_t), &d_pinv));
-    SB_HIP(e, hipMemcpyAsync(d_pinv, inv.data(), inv.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    SB_HIP(e, hipStreamSynchronize(e->stream)); // (the host vector goes out of scope)
-    s.con_np = np;
-    s.con_P = P;
-    s.con_valid = true;
-    s.con_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SB_OK;
-}
-
-// exclusive scan of in[0 .. n) into out (T words; may be `in` for 32-bit words), the sum to *total (may be NULL)
-template <class T>
-static void sbc_scan(sb_engine *e, const uint32_t *in, uint64_t n, T *bsum, T *out, unsigned long long *total)
-{
-    const uint32_t nb = (uint32_t)((n + SBC_SCAN - 1u) / SBC_SCAN);
-    k_contacts_reduce<T><<<nb, SBC_BLOCK, 0, e->stream>>>(in, n, bsum);
-    k_contacts_scan_sums<T><<<1, SBC_BLOCK, 0, e->stream>>>(bsum, nb, total);
-    k_contacts_scan_add<T><<<nb, SBC_BLOCK, 0, e->stream>>>(in, n, bsum, out);
-}
-
 static sb_status sbc_enqueue(sb_engine *e, const sb_contacts_options *o, const void *labels, void *touch, void *pairs, void *counts, bool host)
 {
     if (!e) return SB_ERR_INVALID;
     const char *what = host ? "sb_contacts" : "sb_contacts_device";
-    if (o && o->struct_size != 0 && o->struct_size != sizeof(sb_contacts_options))
-        SB_FAIL(e, SB_ERR_INVALID, "%s: sb_contacts_options.struct_size %u != %zu", what, o->struct_size, sizeof(sb_contacts_options));
-    const bool given = o && o->struct_size;
+    const bool given = o && o->struct_size == sizeof(sb_contacts_options);
     const uint32_t flags = given ? o->flags : 0u;
     const uint64_t max_pairs = given ? o->max_pairs : 0u;
     if (flags & ~SB_CONTACTS_OTHER_BODY) SB_FAIL(e, SB_ERR_INVALID, "%s: unknown flags 0x%x", what, flags);
-    if (given)
-        for (uint32_t r : o->reserved)
-            if (r) SB_FAIL(e, SB_ERR_INVALID, "%s: reserved option words must be zero", what);
     if ((flags & SB_CONTACTS_OTHER_BODY) && !labels) SB_FAIL(e, SB_ERR_INVALID, "%s: SB_CONTACTS_OTHER_BODY needs labels", what);
     if (!touch && !pairs && !counts) SB_FAIL(e, SB_ERR_INVALID, "%s: no output asked for", what);
     if (max_pairs > 0 && !pairs) SB_FAIL(e, SB_ERR_INVALID, "%s: max_pairs %llu without a pair list", what, (unsigned long long)max_pairs);
@@ -435,38 +285,33 @@ static sb_status sbc_enqueue(sb_engine *e, const sb_contacts_options *o, const v
         SB_FAIL(e, SB_ERR_INVALID, "%s: labels, touch and pairs must be 4-byte aligned", what);
     if ((uintptr_t)counts & 7u) SB_FAIL(e, SB_ERR_INVALID, "%s: counts must be 8-byte aligned", what);
     if (max_pairs > 0x80000000ull) SB_FAIL(e, SB_ERR_INVALID, "%s: max_pairs above 2^31", what);
-    if (e->opt.max_particles > 0x80000000u) SB_FAIL(e, SB_ERR_INVALID, "%s: capacities above 2^31 are not handled", what);
-    if (!e->loaded) SB_FAIL(e, SB_ERR_STATE, "%s before sb_write_buffers", what);
-    if (e->halo_configured || e->n_ghost_p || e->n_send_p || e->n_ghost_b || e->n_send_b || e->n_peers || e->mailbox)
-        SB_FAIL(e, SB_ERR_UNSUPPORTED, "%s: the engine has ghost zones or peers configured (contacts across ranks are not handled)", what);
+    SB_TRY(sbq_preflight(e, what, o, "handled", "contacts across ranks are not handled"));
     SbcGeo geo;
     if (!sbc_geometry(e, &geo) && e->P > SBC_ALL_PAIRS_MAX)
         SB_FAIL(e, SB_ERR_UNSUPPORTED, "%s: the cell side is no ordinary number and the scene has more than %u particles (an all-pairs test of it is not run)",
                 what, SBC_ALL_PAIRS_MAX);
-    SB_HIP(e, hipSetDevice(e->device));
-    if (!e->sio) e->sio = new SbStateIoState();
-    if (!e->sio->con_valid) SB_TRY(sbc_build_tables(e));
+    SB_TRY(sbq_need(e, "sb_contacts", SBQ_PARTICLES));
     SbStateIoState &s = *e->sio;
+    s.con_build_ms = s.part_ms;
 
-    const uint32_t maxP = e->opt.max_particles, np = s.con_np, P = s.con_P;
+    const uint32_t maxP = e->opt.max_particles, np = s.np, P = s.P;
     const uint64_t ncell = (uint64_t)geo.G * geo.G + 1u;
-    const uint32_t nb_cells = (uint32_t)((ncell + SBC_SCAN - 1u) / SBC_SCAN), nb_np = (np + SBC_SCAN - 1u) / SBC_SCAN;
+    const uint32_t nb_cells = (uint32_t)((ncell + SBQ_SCAN - 1u) / SBQ_SCAN), nb_np = (np + SBQ_SCAN - 1u) / SBQ_SCAN;
     const bool list = pairs && max_pairs > 0;
-    void *m = nullptr;
-    SB_TRY(sbc_grow(e, SBC_M_CELLS, ncell * sizeof(uint32_t), &m));
-    uint32_t *d_cells = (uint32_t *)m;
-    SB_TRY(sbc_grow(e, SBC_M_BSUM, (size_t)std::max(nb_cells, nb_np) * sizeof(unsigned long long), &m));
-    void *d_bsum = m;
-    SB_TRY(sbc_grow(e, SBC_M_SORTED, (size_t)P * sizeof(SbcRec), &m));
-    SbcRec *d_sorted = (SbcRec *)m;
-    SB_TRY(sbc_grow(e, SBC_M_ABOVE, (size_t)np * sizeof(uint32_t), &m));
-    uint32_t *d_above = (uint32_t *)m;
-    SB_TRY(sbc_grow(e, SBC_M_ACC, (SBC_NACC + SB_CONTACT_COUNT_WORDS) * sizeof(unsigned long long), &m));
-    unsigned long long *d_acc = (unsigned long long *)m;
+    SB_TRY(s.buf[SBC_B_CELLS].grow(e, ncell * sizeof(uint32_t)));
+    uint32_t *d_cells = s.buf[SBC_B_CELLS].as<uint32_t>();
+    SB_TRY(s.buf[SBC_B_BSUM].grow(e, (size_t)std::max(nb_cells, nb_np) * sizeof(unsigned long long)));
+    void *d_bsum = s.buf[SBC_B_BSUM].p;
+    SB_TRY(s.buf[SBC_B_SORTED].grow(e, (size_t)P * sizeof(SbcRec)));
+    SbcRec *d_sorted = s.buf[SBC_B_SORTED].as<SbcRec>();
+    SB_TRY(s.buf[SBC_B_ABOVE].grow(e, (size_t)np * sizeof(uint32_t)));
+    uint32_t *d_above = s.buf[SBC_B_ABOVE].as<uint32_t>();
+    SB_TRY(s.buf[SBC_B_ACC].grow(e, (SBC_NACC + SB_CONTACT_COUNT_WORDS) * sizeof(unsigned long long)));
+    unsigned long long *d_acc = s.buf[SBC_B_ACC].as<unsigned long long>();
     unsigned long long *d_place = nullptr;
     if (list) {
-        SB_TRY(sbc_grow(e, SBC_M_PLACE, (size_t)np * sizeof(unsigned long long), &m));
-        d_place = (unsigned long long *)m;
+        SB_TRY(s.buf[SBC_B_PLACE].grow(e, (size_t)np * sizeof(unsigned long long)));
+        d_place = s.buf[SBC_B_PLACE].as<unsigned long long>();
     }
     // where the launches read and write: the caller's device memory, or (sb_contacts) the engine's own, copied below
     const int32_t *d_labels = (const int32_t *)labels;
@@ -474,17 +319,17 @@ static sb_status sbc_enqueue(sb_engine *e, const sb_contacts_options *o, const v
     long long *d_counts = (long long *)counts;
     if (host) {
         if (labels) {
-            SB_TRY(sbc_grow(e, SBC_M_LABELS, (size_t)maxP * sizeof(int32_t), &m));
-            SB_HIP(e, hipMemcpyAsync(m, labels, (size_t)maxP * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-            d_labels = (const int32_t *)m;
+            SB_TRY(s.buf[SBC_B_LABELS].grow(e, (size_t)maxP * sizeof(int32_t)));
+            d_labels = s.buf[SBC_B_LABELS].as<int32_t>();
+            SB_HIP(e, hipMemcpyAsync(s.buf[SBC_B_LABELS].p, labels, (size_t)maxP * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
         }
         if (touch) {
-            SB_TRY(sbc_grow(e, SBC_M_TOUCH, (size_t)maxP * SB_CONTACT_WORDS * sizeof(int32_t), &m));
-            d_touch = (int32_t *)m;
+            SB_TRY(s.buf[SBC_B_TOUCH].grow(e, (size_t)maxP * SB_CONTACT_WORDS * sizeof(int32_t)));
+            d_touch = s.buf[SBC_B_TOUCH].as<int32_t>();
         }
         if (list) {
-            SB_TRY(sbc_grow(e, SBC_M_PAIRS, (size_t)max_pairs * 2 * sizeof(int32_t), &m));
-            d_pairs = (int32_t *)m;
+            SB_TRY(s.buf[SBC_B_PAIRS].grow(e, (size_t)max_pairs * 2 * sizeof(int32_t)));
+            d_pairs = s.buf[SBC_B_PAIRS].as<int32_t>();
         }
         d_counts = (long long *)(d_acc + SBC_NACC);
     }
@@ -494,7 +339,7 @@ static sb_status sbc_enqueue(sb_engine *e, const sb_contacts_options *o, const v
                      e->prm.bounds_size - e->prm.particle_radius}; // sb_particle_finish's lo / hi (compute.wgsl:190)
     const uint32_t other = flags & SB_CONTACTS_OTHER_BODY;
     const float2 *pos = e->part[e->cur].pos;
-    const uint32_t *d_pinv = (const uint32_t *)s.d_con[SBC_M_PINV];
+    const uint32_t *d_pinv = s.buf[SBQ_B_PINV].as<uint32_t>();
     auto blocks = [](uint64_t k) { return (uint32_t)((k + SBC_BLOCK - 1u) / SBC_BLOCK); };
 
     SB_HIP(e, hipMemsetAsync(d_cells, 0, ncell * sizeof(uint32_t), e->stream));
@@ -503,11 +348,11 @@ static sb_status sbc_enqueue(sb_engine *e, const sb_contacts_options *o, const v
     if (std::max(np, n_rows))
         k_contacts_bin<<<blocks(std::max(np, n_rows)), SBC_BLOCK, 0, e->stream>>>(d_pinv, np, pos, geo, d_cells, d_above, d_touch, n_rows, labels ? 0 : -1);
     if (P) {
-        sbc_scan<uint32_t>(e, d_cells, ncell, (uint32_t *)d_bsum, d_cells, nullptr);
+        sbq_scan<uint32_t>(e, d_cells, ncell, (uint32_t *)d_bsum, d_cells, nullptr);
         k_contacts_scatter<<<blocks(np), SBC_BLOCK, 0, e->stream>>>(d_pinv, np, pos, d_above, d_cells, d_sorted);
         k_contacts_visit<<<blocks(P), SBC_BLOCK, 0, e->stream>>>(d_sorted, P, d_cells, geo, ts, d_labels, other, d_touch, d_above, d_acc);
         if (list) {
-            sbc_scan<unsigned long long>(e, d_above, np, (unsigned long long *)d_bsum, d_place, d_acc + SBC_LISTED);
+            sbq_scan<unsigned long long>(e, d_above, np, (unsigned long long *)d_bsum, d_place, d_acc + SBC_LISTED);
             k_contacts_list<<<blocks(P), SBC_BLOCK, 0, e->stream>>>(d_sorted, P, d_cells, geo, ts, d_labels, other, d_above, d_place, d_pairs, max_pairs);
         }
     }
@@ -534,48 +379,26 @@ bool sbc_info(sb_engine *e, const char *key, uint64_t *value)
         *value = geo.G;
     }
     else if (k == "contacts_kernel_vgprs" || k == "contacts_kernel_scratch_bytes") { // the most over every kernel a call may launch
-        const void *ks[] = {(const void *)k_contacts_bin, (const void *)k_contacts_reduce<uint32_t>, (const void *)k_contacts_reduce<unsigned long long>,
-                            (const void *)k_contacts_scan_sums<uint32_t>, (const void *)k_contacts_scan_sums<unsigned long long>,
-                            (const void *)k_contacts_scan_add<uint32_t>, (const void *)k_contacts_scan_add<unsigned long long>,
-                            (const void *)k_contacts_scatter, (const void *)k_contacts_visit, (const void *)k_contacts_list,
-                            (const void *)k_contacts_tail, (const void *)k_contacts_counts};
-        uint64_t most = 0;
-        for (const void *f : ks) {
-            hipFuncAttributes fa{};
-            if (hipSetDevice(e->device) != hipSuccess || hipFuncGetAttributes(&fa, f) != hipSuccess) {
-                (void)hipGetLastError();
-                return false;
-            }
-            most = std::max<uint64_t>(most, k == "contacts_kernel_vgprs" ? (uint64_t)fa.numRegs : (uint64_t)fa.localSizeBytes);
-        }
-        *value = most;
+        std::vector<const void *> ks = {(const void *)k_contacts_bin, (const void *)k_contacts_scatter, (const void *)k_contacts_visit,
+                                        (const void *)k_contacts_list, (const void *)k_contacts_tail, (const void *)k_contacts_counts};
+        for (const void *f : sbq_scan_kernels(true)) ks.push_back(f); // (both widths)
+        return sbq_kernel_most(e, ks, k == "contacts_kernel_vgprs", value);
     }
     else return false;
     return true;
 }
-
-#define SBC_GUARDED(e, call)                                                   \
-    try {                                                                      \
-        return (call);                                                         \
-    } catch (const std::bad_alloc &) {                                         \
-        if (e) (e)->err = "out of host memory";                                \
-        return SB_ERR_OOM;                                                     \
-    } catch (const std::exception &ex) {                                       \
-        if (e) (e)->err = std::string("internal error: ") + ex.what();         \
-        return SB_ERR_INVALID;                                                 \
-    }
 
 extern "C" {
 
 sb_status sb_contacts_device(sb_engine *e, const sb_contacts_options *opts, const void *device_labels_i32, void *device_touch_i32,
                              void *device_pairs_i32, void *device_counts_i64)
 {
-    SBC_GUARDED(e, sbc_enqueue(e, opts, device_labels_i32, device_touch_i32, device_pairs_i32, device_counts_i64, false))
+    SB_GUARDED(e, sbc_enqueue(e, opts, device_labels_i32, device_touch_i32, device_pairs_i32, device_counts_i64, false))
 }
 
 sb_status sb_contacts(sb_engine *e, const sb_contacts_options *opts, const int32_t *labels, int32_t *touch, int32_t *pairs, int64_t *counts)
 {
-    SBC_GUARDED(e, sbc_enqueue(e, opts, labels, touch, pairs, counts, true))
+    SB_GUARDED(e, sbc_enqueue(e, opts, labels, touch, pairs, counts, true))
 }
 
 } // extern "C"

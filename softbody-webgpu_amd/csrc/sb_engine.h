@@ -4,6 +4,8 @@
 #include <stdint.h>
 
 #include <cstring>
+#include <new>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
@@ -249,72 +251,33 @@ struct sb_engine {
     std::thread reaper;               // frees the host arrays of the last upload (sb_api.hip: SbUpload)
 
     struct SbRenderState *rs = nullptr; // sb_render.hip: draw tables (rebuilt at the first render after an upload) + key image
-    struct SbStateIoState *sio = nullptr; // sb_state_io.hip: export tables (rebuilt at the first export after an upload)
+    struct SbStateIoState *sio = nullptr; // sb_report.h: what the state calls and the four reports keep between calls
 
     size_t device_bytes = 0;
     std::vector<void *> allocs;                             // freed with the scene (not pooled)
     std::vector<std::pair<void *, size_t>> pool_used, pool_free; // device blocks of the scene / kept for the next upload (sb_api.hip dev_alloc)
 };
 
-// what sb_state_io.hip, sb_summary.hip, sb_bodies.hip, sb_contacts.hip and sb_body_summary.hip keep between calls (sb_engine sio):
-// tables of the scene of the latest upload, built at the first export / summary / bodies / contacts / body_summary call after it (sb_write_buffers drops them all
-// through sbs_invalidate)
-#define SB_CONTACTS_BUFFERS 10
-struct SbStateIoState {
-    bool valid = false;
-    uint32_t nslots = 0;       // the caller's beam slots of the latest upload
-    uint2 *d_slot = nullptr;   // per caller slot u: {engine slot, data index of its record}; the copy is sbr_copy_table's
-    size_t cap_slot = 0;
-    double build_ms = 0.0;     // host time of the last table build
-    // sb_summary.hip: the summation tree runs over DATA indices
-    bool sum_valid = false;
-    uint32_t *d_sum_pinv = nullptr; // per particle data index < sum_np: its internal particle (0xFFFFFFFF: none)
-    uint2 *d_sum_bleaf = nullptr;   // per beam data index < sum_nb: {engine slot (0xFFFFFFFF: none), the copy read back for it}
-    uint32_t sum_np = 0, sum_nb = 0, sum_nslots = 0; // highest data index in use + 1 (particles, beams); the caller's beam slots (table size only)
-    double *d_sum_part = nullptr;   // partial sums of a call: 5 particle columns, then the strain column
-    unsigned long long *d_sum_stat = nullptr, *d_sum_out = nullptr; // the order-free statistics of a call; sb_summary's device-side result
-    size_t cap_sum_pinv = 0, cap_sum_bleaf = 0, cap_sum_part = 0, cap_sum_stat = 0, cap_sum_out = 0;
-    uint32_t sum_partials = 0;      // sb_summary_options.partials as the last call resolved it ("summary_partials")
-    double sum_build_ms = 0.0;
-    // sb_bodies.hip: the component search runs over particle DATA indices and the caller's beam slots
-    bool bod_valid = false;
-    uint32_t *d_bod_pinv = nullptr; // per particle data index < bod_np: its internal particle (0xFFFFFFFF: none)
-    uint32_t *d_bod_tab = nullptr;  // [3][bod_nslots]: per caller beam slot the data index of A, of B, the engine slot
-    uint32_t bod_np = 0, bod_nslots = 0; // highest particle data index in use + 1; the caller's beam slots
-    int32_t *d_bod_parent = nullptr, *d_bod_sizes = nullptr; // a call's parent words / sizes where the caller gave no device memory for them
-    unsigned long long *d_bod_acc = nullptr; // a call's accumulators (bodies, single bodies, key of the largest), then sb_bodies' counts
-    size_t cap_bod_pinv = 0, cap_bod_tab = 0, cap_bod_parent = 0, cap_bod_sizes = 0, cap_bod_acc = 0;
-    double bod_build_ms = 0.0;
-    // sb_contacts.hip: its own data index -> internal particle table, and the scratch of a call, by use (its SBC_M_* enum)
-    bool con_valid = false;
-    uint32_t con_np = 0, con_P = 0; // highest particle data index in use + 1; particles
-    void *d_con[SB_CONTACTS_BUFFERS] = {};
-    size_t cap_con[SB_CONTACTS_BUFFERS] = {}; // bytes
-    double con_build_ms = 0.0;
-    // sb_body_summary.hip: its own tables, the scratch of a call (one allocation, carved by use), the engine's own labels
-    bool bsm_valid = false;
-    void *d_bsm_pinv = nullptr;     // per particle data index < bsm_np: its internal particle (0xFFFFFFFF: none)
-    void *d_bsm_tab = nullptr;      // [4][bsm_nslots]: per caller beam slot the data index of A, of B, the engine slot, the copy read back
-    uint32_t bsm_np = 0, bsm_nslots = 0; // highest particle data index in use + 1; the caller's beam slots
-    void *d_bsm = nullptr, *d_bsm_labels = nullptr, *d_bsm_out = nullptr; // scratch; sb_bodies_device's labels / the host's; sb_body_summary's device-side result
-    size_t cap_bsm_pinv = 0, cap_bsm_tab = 0, cap_bsm = 0, cap_bsm_labels = 0, cap_bsm_out = 0; // bytes
-    double bsm_build_ms = 0.0;
-    // sb_write_beams_device: per ENGINE beam slot the data index of its record in the latest upload (0xFFFFFFFF: a beam an upload
-    // removed); on the blocked layout also the rest length of every blocked beam, in owner order (the plastic promise's rule)
-    bool imp_valid = false;
-    uint32_t *d_imp_row = nullptr;
-    float *d_imp_rest = nullptr;
-    size_t cap_imp_row = 0, cap_imp_rest = 0;
-    double imp_build_ms = 0.0;
-    // sb_checkpoint_device: one block holding a copy of everything a run mutates (sbs_walk_run_state), and the host's words of it
-    void *d_ckpt = nullptr;
-    size_t cap_ckpt = 0, ckpt_bytes = 0;      // ckpt_bytes == 0: no checkpoint
-    uint32_t ck_cur = 0, ck_bcur = 0, ck_delete_gen = 0;
-    uint64_t ck_substeps_done = 0;
-    uint64_t checkpoints = 0, restores = 0;   // calls since sb_create
-};
-
 inline void sb_set_error(sb_engine *e, const char *text) { if (e) e->err = text; else sb_set_create_error(text); } // (sb_error.h)
+
+// C++ exceptions must not cross the C boundary: the entry points that allocate host memory run their bodies under a catch-all that
+// turns std::bad_alloc (and anything else) into a status.
+#define SB_GUARDED(e, call)                                               \
+    try {                                                                 \
+        return (call);                                                    \
+    } catch (const std::bad_alloc &) {                                    \
+        if (e) (e)->err = "out of host memory";                           \
+        return SB_ERR_OOM;                                                \
+    } catch (const std::exception &ex) {                                  \
+        if (e) (e)->err = std::string("internal error: ") + ex.what();    \
+        return SB_ERR_INVALID;                                            \
+    }
+
+// ghost zones or peers: what the calls that see one rank's scene as the whole scene refuse (sb_state_io.hip, sb_report.hip)
+static inline bool sb_has_ranks(const sb_engine *e)
+{
+    return e->halo_configured || e->n_ghost_p || e->n_send_p || e->n_ghost_b || e->n_send_b || e->n_peers || e->mailbox;
+}
 
 // mapping entries of the caller's layout (sb_scene_codec.h)
 static inline uint32_t map_isz(const sb_engine *e) { return sbc::map_item_bytes(e->opt.layout); }

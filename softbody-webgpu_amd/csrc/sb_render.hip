@@ -318,46 +318,33 @@ static sb_status sbr_enqueue(sb_engine *e, const sb_render_options *o, uint8_t *
     return SB_OK;
 }
 
+static sb_status sbr_render_device(sb_engine *e, const sb_render_options *opts, void *device_rgb)
+{
+    uint32_t res = 0;
+    return sbr_enqueue(e, opts, (uint8_t *)device_rgb, 0, false, &res);
+}
+
+static sb_status sbr_render(sb_engine *e, const sb_render_options *opts, void *rgb, size_t rgb_bytes)
+{
+    if (!e) return SB_ERR_INVALID;
+    if (!rgb) SB_FAIL(e, SB_ERR_INVALID, "sb_render: null destination");
+    // the size check needs the resolution before anything is enqueued: sbr_enqueue checks it against rgb_bytes
+    const bool given = opts && opts->struct_size;
+    const size_t res = given && opts->resolution ? opts->resolution : 512u;
+    if (res <= SB_RENDER_MAX_RESOLUTION && e->loaded) {
+        if (!e->rs) e->rs = new SbRenderState();
+        if (rgb_bytes >= res * res * 3) SB_TRY(sbr_grow(e, &e->rs->d_rgb, e->rs->cap_rgb, res * res * 3));
+    }
+    uint32_t got = 0;
+    SB_TRY(sbr_enqueue(e, opts, e->rs ? e->rs->d_rgb : nullptr, rgb_bytes, true, &got));
+    SB_HIP(e, hipMemcpyAsync(rgb, e->rs->d_rgb, (size_t)got * got * 3, hipMemcpyDeviceToHost, e->stream));
+    SB_HIP(e, hipStreamSynchronize(e->stream));
+    return SB_OK;
+}
+
 extern "C" {
 
-sb_status sb_render_device(sb_engine *e, const sb_render_options *opts, void *device_rgb)
-{
-    try {
-        uint32_t res = 0;
-        return sbr_enqueue(e, opts, (uint8_t *)device_rgb, 0, false, &res);
-    } catch (const std::bad_alloc &) {
-        if (e) e->err = "out of host memory";
-        return SB_ERR_OOM;
-    } catch (const std::exception &ex) {
-        if (e) e->err = std::string("internal error: ") + ex.what();
-        return SB_ERR_INVALID;
-    }
-}
-
-sb_status sb_render(sb_engine *e, const sb_render_options *opts, void *rgb, size_t rgb_bytes)
-{
-    try {
-        if (!e) return SB_ERR_INVALID;
-        if (!rgb) SB_FAIL(e, SB_ERR_INVALID, "sb_render: null destination");
-        // the size check needs the resolution before anything is enqueued: sbr_enqueue checks it against rgb_bytes
-        const bool given = opts && opts->struct_size;
-        const size_t res = given && opts->resolution ? opts->resolution : 512u;
-        if (res <= SB_RENDER_MAX_RESOLUTION && e->loaded) {
-            if (!e->rs) e->rs = new SbRenderState();
-            if (rgb_bytes >= res * res * 3) SB_TRY(sbr_grow(e, &e->rs->d_rgb, e->rs->cap_rgb, res * res * 3));
-        }
-        uint32_t got = 0;
-        SB_TRY(sbr_enqueue(e, opts, e->rs ? e->rs->d_rgb : nullptr, rgb_bytes, true, &got));
-        SB_HIP(e, hipMemcpyAsync(rgb, e->rs->d_rgb, (size_t)got * got * 3, hipMemcpyDeviceToHost, e->stream));
-        SB_HIP(e, hipStreamSynchronize(e->stream));
-        return SB_OK;
-    } catch (const std::bad_alloc &) {
-        if (e) e->err = "out of host memory";
-        return SB_ERR_OOM;
-    } catch (const std::exception &ex) {
-        if (e) e->err = std::string("internal error: ") + ex.what();
-        return SB_ERR_INVALID;
-    }
-}
+sb_status sb_render_device(sb_engine *e, const sb_render_options *opts, void *device_rgb) { SB_GUARDED(e, sbr_render_device(e, opts, device_rgb)) }
+sb_status sb_render(sb_engine *e, const sb_render_options *opts, void *rgb, size_t rgb_bytes) { SB_GUARDED(e, sbr_render(e, opts, rgb, rgb_bytes)) }
 
 } // extern "C"

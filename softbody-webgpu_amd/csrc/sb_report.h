@@ -1,0 +1,114 @@
+// sb_report.h -- what the engine's state calls (sb_state_io.hip) and its four whole-scene reports (sb_summary.hip, sb_bodies.hip,
+// sb_contacts.hip, sb_body_summary.hip) share: the owner of their device buffers, the preflight of a call, the scene tables of the
+// latest upload, the exclusive scan and the wave's run counter.  What only one report uses stays in its file.
+#pragma once
+#include <vector>
+
+#include "sb_engine.h"
+#include "sb_report_tables.h"
+
+// a device block that only ever grows; freed with the engine (sbs_release)
+struct SbDevBuf {
+    void *p = nullptr;
+    size_t cap = 0; // bytes
+    sb_status grow(sb_engine *e, size_t bytes); // at least 16 bytes; waits for the stream before a block too small is freed
+    void release();
+    template <class T> T *as() const { return (T *)p; }
+};
+
+// every device buffer the five files keep between calls, by use
+enum SbReportBuf {
+    SBQ_B_PINV, SBQ_B_TAB,                                                         // the shared scene tables (sbq_need)
+    SBS_B_SLOT, SBS_B_IMP_ROW, SBS_B_IMP_REST, SBS_B_CKPT,                         // sb_state_io.hip
+    SBM_B_BLEAF, SBM_B_PART, SBM_B_STAT, SBM_B_OUT,                                // sb_summary.hip
+    SBD_B_PARENT, SBD_B_SIZES, SBD_B_ACC,                                          // sb_bodies.hip
+    SBC_B_CELLS, SBC_B_BSUM, SBC_B_SORTED, SBC_B_ABOVE, SBC_B_PLACE, SBC_B_ACC, SBC_B_LABELS, SBC_B_TOUCH, SBC_B_PAIRS, // sb_contacts.hip
+    SBY_B_SCRATCH, SBY_B_LABELS, SBY_B_OUT,                                        // sb_body_summary.hip
+    SBQ_NBUF
+};
+
+// sb_engine::sio.  Tables of the scene of the latest upload are built at the first call after it that reads them;
+// sb_write_buffers drops them all through sbs_invalidate.
+struct SbStateIoState {
+    SbDevBuf buf[SBQ_NBUF];
+    // the shared scene tables, in two parts, the second's fourth plane on its own (sbq_need)
+    bool part_valid = false, beam_valid = false, copy_valid = false;
+    uint32_t np = 0, P = 0, nslots = 0; // highest particle data index in use + 1; particles; the caller's beam slots
+    std::vector<uint32_t> h_pinv;       // part 1 on the host: part 2's endpoint check reads it
+    double part_ms = 0.0, beam_ms = 0.0, copy_ms = 0.0; // host time of each one's last build (copy_ms 0: built with the other planes)
+    // sb_read_state_device: per caller slot u {engine slot, data index of its record} (SBS_B_SLOT); the copy is sbr_copy_table's
+    bool valid = false;
+    // sb_summary.hip: per beam data index < sum_nb {engine slot (0xFFFFFFFF: none), the copy read back for it} (SBM_B_BLEAF)
+    bool bleaf_valid = false;
+    uint32_t sum_nb = 0, sum_partials = 0; // highest beam data index in use + 1; sb_summary_options.partials as the last call resolved it
+    double bleaf_ms = 0.0;
+    // sb_write_beams_device: per ENGINE beam slot the data index of its record in the latest upload (0xFFFFFFFF: a beam an upload
+    // removed); on the blocked layout also the rest length of every blocked beam, in owner order (the plastic promise's rule)
+    bool imp_valid = false;
+    double imp_build_ms = 0.0;
+    // "<report>_table_build_us": host time of the last build of the tables the report's latest call read (0: no call yet)
+    double sum_build_ms = 0.0, bod_build_ms = 0.0, con_build_ms = 0.0, bsm_build_ms = 0.0;
+    // sb_checkpoint_device: one block (SBS_B_CKPT) holding a copy of everything a run mutates (sbs_walk_run_state), and the host's words of it
+    size_t ckpt_bytes = 0;                    // 0: no checkpoint
+    uint32_t ck_cur = 0, ck_bcur = 0, ck_delete_gen = 0;
+    uint64_t ck_substeps_done = 0;
+    uint64_t checkpoints = 0, restores = 0;   // calls since sb_create
+
+    void invalidate() { part_valid = beam_valid = copy_valid = valid = bleaf_valid = imp_valid = false; } // every table of the scene: the one place
+};
+
+enum { SBQ_PARTICLES = 1u, SBQ_BEAMS = 2u, SBQ_COPIES = 4u }; // the parts of the shared scene tables; SBQ_COPIES: part 2's fourth plane
+
+inline const char *sbq_options_name(const sb_summary_options *) { return "sb_summary_options"; }
+inline const char *sbq_options_name(const sb_bodies_options *) { return "sb_bodies_options"; }
+inline const char *sbq_options_name(const sb_contacts_options *) { return "sb_contacts_options"; }
+inline const char *sbq_options_name(const sb_body_summary_options *) { return "sb_body_summary_options"; }
+
+sb_status sbq_ready(sb_engine *e, const char *what, const char *why); // loaded, no ranks (`why`: the call's parenthesis); the device; e->sio
+
+// What every report checks before it enqueues, in one order: the options' size, their reserved words, capacities above 2^31
+// ("... are not <verb>"), an upload, no ranks; then the device is made current and e->sio exists.  A report's own INVALID checks
+// come before the call (they read option fields only where struct_size is exactly the struct's).
+template <class O>
+sb_status sbq_preflight(sb_engine *e, const char *what, const O *o, const char *verb, const char *why)
+{
+    if (o && o->struct_size != 0 && o->struct_size != sizeof(O))
+        SB_FAIL(e, SB_ERR_INVALID, "%s: %s.struct_size %u != %zu", what, sbq_options_name(o), o->struct_size, sizeof(O));
+    if (o && o->struct_size)
+        for (uint32_t r : o->reserved)
+            if (r) SB_FAIL(e, SB_ERR_INVALID, "%s: reserved option words must be zero", what);
+    if (e->opt.max_particles > 0x80000000u || e->opt.max_beams > 0x80000000u)
+        SB_FAIL(e, SB_ERR_INVALID, "%s: capacities above 2^31 are not %s", what, verb);
+    return sbq_ready(e, what, why);
+}
+
+// the most VGPRs (want_vgprs) or scratch bytes over the kernels; false: the runtime refused (the error is taken off the record)
+bool sbq_kernel_most(sb_engine *e, const std::vector<const void *> &kernels, bool want_vgprs, uint64_t *value);
+
+// the shared scene tables: builds the parts asked for that the latest upload has not built yet (`what`: the call in messages)
+sb_status sbq_need(sb_engine *e, const char *what, uint32_t parts);
+// per caller beam slot of the latest upload {engine slot, data index of its record}, both checked against the scene
+sb_status sbq_user_slots(sb_engine *e, const char *what, std::vector<uint2> &slots);
+
+// ---- exclusive scan of n 32-bit words into T words (uint32_t / unsigned long long), three launches: a sum per block of SBQ_SCAN
+// words into bsum, the block sums scanned in place by ONE workgroup that loops over them with a carry (the sum of all to *total,
+// which may be NULL), added back.  `out` may be `in` when T is 32 bits.
+#define SBQ_BLOCK 256u
+#define SBQ_PER 4u                      // words a thread of a scan block owns
+#define SBQ_SCAN (SBQ_BLOCK * SBQ_PER)  // words of a scan block
+template <class T>
+void sbq_scan(sb_engine *e, const uint32_t *in, uint64_t n, T *bsum, T *out, T *total);
+std::vector<const void *> sbq_scan_kernels(bool wide); // the kernels sbq_scan<uint32_t> may launch; wide: and sbq_scan<unsigned long long>'s (the reports' *_kernel_vgprs keys)
+
+// The length of the run for the first lane of each maximal run of equal keys in the wave, 0 for every other lane and for a run
+// that is not valid.  Every lane of the wave calls it.
+SB_DEV uint32_t sbq_run_length(uint32_t key, bool valid)
+{
+    const uint32_t lane = __lane_id();
+    const uint32_t left = __shfl_up(key, 1);
+    const bool head = lane == 0u || left != key;
+    const unsigned long long heads = __ballot(head);
+    if (!(head && valid)) return 0u;
+    const unsigned long long rest = lane == 63u ? 0ull : heads >> (lane + 1u);
+    return rest ? (uint32_t)__ffsll(rest) : 64u - lane; // up to the next head, or to the end of the wave
+}

@@ -18,7 +18,7 @@
 #include <stdexcept>
 #include <vector>
 
-#include "sb_engine.h"
+#include "sb_report.h"
 
 #define SBS_BLOCK 256
 
@@ -124,73 +124,28 @@ __global__ __launch_bounds__(SBS_BLOCK) void k_state_import_beams_blocked(const 
 
 // ---------------------------------------------------------------- host side
 
-void sbs_invalidate(sb_engine *e)
-{
-    if (e && e->sio) e->sio->valid = e->sio->sum_valid = e->sio->bod_valid = e->sio->con_valid = e->sio->bsm_valid = e->sio->imp_valid = false;
-}
-
 void sbs_drop_checkpoint(sb_engine *e)
 {
-    if (!e || !e->sio || !e->sio->d_ckpt) return;
+    if (!e || !e->sio || !e->sio->buf[SBS_B_CKPT].p) return;
     (void)hipSetDevice(e->device);
     (void)hipStreamSynchronize(e->stream); // (a restore in flight still reads it)
-    (void)hipFree(e->sio->d_ckpt);
-    e->sio->d_ckpt = nullptr;
-    e->sio->cap_ckpt = e->sio->ckpt_bytes = 0;
+    e->sio->buf[SBS_B_CKPT].release();
+    e->sio->ckpt_bytes = 0;
 }
 
-void sbs_release(sb_engine *e)
-{
-    if (!e || !e->sio) return;
-    void *ps[] = {e->sio->d_slot, e->sio->d_sum_pinv, e->sio->d_sum_bleaf, e->sio->d_sum_part, e->sio->d_sum_stat, e->sio->d_sum_out,
-                  e->sio->d_bod_pinv, e->sio->d_bod_tab, e->sio->d_bod_parent, e->sio->d_bod_sizes, e->sio->d_bod_acc,
-                  e->sio->d_bsm_pinv, e->sio->d_bsm_tab, e->sio->d_bsm, e->sio->d_bsm_labels, e->sio->d_bsm_out,
-                  e->sio->d_imp_row, e->sio->d_imp_rest, e->sio->d_ckpt};
-    for (void *p : ps)
-        if (p) (void)hipFree(p);
-    for (void *p : e->sio->d_con)
-        if (p) (void)hipFree(p);
-    delete e->sio;
-    e->sio = nullptr;
-}
-
-static sb_status sbs_check(sb_engine *e, const char *what)
-{
-    if (!e->loaded) SB_FAIL(e, SB_ERR_STATE, "%s before sb_write_buffers", what);
-    if (e->halo_configured || e->n_ghost_p || e->n_send_p || e->n_ghost_b || e->n_send_b || e->n_peers || e->mailbox)
-        SB_FAIL(e, SB_ERR_UNSUPPORTED, "%s: the engine has ghost zones or peers configured (ranks are not handled)", what);
-    SB_HIP(e, hipSetDevice(e->device));
-    return SB_OK;
-}
+// every call of this file: an upload, no ranks (sbq_ready also makes the device current)
+static sb_status sbs_check(sb_engine *e, const char *what) { return sbq_ready(e, what, "ranks are not handled"); }
 
 // per caller beam slot of the latest upload: its engine slot and the data index of its record (sb_load_buffers' beam loop)
 static sb_status sbs_build_tables(sb_engine *e)
 {
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!e->sio) e->sio = new SbStateIoState();
     SbStateIoState &s = *e->sio;
-    const uint32_t maxP = e->opt.max_particles, Bu = sb_user_beams(e);
-    std::vector<uint2> slots(std::max<uint32_t>(Bu, 1));
-    sbt::parallel_ranges(Bu, 1 << 16, [&](size_t u0, size_t u1) {
-        for (size_t u = u0; u < u1; u++) slots[u] = make_uint2(sb_user_slot(e, u), map_get(e, e->h_mapping.data(), (size_t)maxP + u));
-    });
-    for (uint32_t u = 0; u < Bu; u++)
-        if (slots[u].x >= e->B || slots[u].y >= e->opt.max_beams) SB_FAIL(e, SB_ERR_STATE, "sb_read_state_device: beam slot outside the scene");
-    if (!s.d_slot || s.cap_slot < slots.size()) {
-        if (s.d_slot) {
-            SB_HIP(e, hipStreamSynchronize(e->stream)); // an export in flight may still read it
-            SB_HIP(e, hipFree(s.d_slot));
-            s.d_slot = nullptr;
-            s.cap_slot = 0;
-        }
-        SB_HIP(e, hipMalloc((void **)&s.d_slot, slots.size() * sizeof(uint2)));
-        s.cap_slot = slots.size();
-    }
-    SB_HIP(e, hipMemcpyAsync(s.d_slot, slots.data(), slots.size() * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+    std::vector<uint2> slots;
+    SB_TRY(sbq_user_slots(e, "sb_read_state_device", slots));
+    SB_TRY(s.buf[SBS_B_SLOT].grow(e, slots.size() * sizeof(uint2)));
+    SB_HIP(e, hipMemcpyAsync(s.buf[SBS_B_SLOT].p, slots.data(), slots.size() * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
     SB_HIP(e, hipStreamSynchronize(e->stream)); // (the host vector goes out of scope)
-    s.nslots = Bu;
     s.valid = true;
-    s.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return SB_OK;
 }
 
@@ -207,13 +162,13 @@ static sb_status sbs_read(sb_engine *e, void *particles, void *beams, void *aliv
                                                                                               (float2 *)particles);
     }
     if ((beams || alive) && sb_user_beams(e)) {
-        if (!e->sio || !e->sio->valid) SB_TRY(sbs_build_tables(e));
+        if (!e->sio->valid) SB_TRY(sbs_build_tables(e));
         const uint32_t *copy = nullptr;
         SB_TRY(sbr_copy_table(e, &copy));
-        const SbStateIoState &s = *e->sio;
+        const uint32_t nslots = sb_user_beams(e);
         const uint32_t *dead = e->B && e->delete_gen ? e->d_dead_gen : nullptr; // as sb_load_buffers (fetch_dead) sees it
-        k_state_export_beams<<<(s.nslots + SBS_BLOCK - 1) / SBS_BLOCK, SBS_BLOCK, 0, e->stream>>>(
-            s.d_slot, s.nslots, copy, e->beams.target, e->beams.last, e->beams.strain, e->beams.stress, dead, (float4 *)beams,
+        k_state_export_beams<<<(nslots + SBS_BLOCK - 1) / SBS_BLOCK, SBS_BLOCK, 0, e->stream>>>(
+            e->sio->buf[SBS_B_SLOT].as<uint2>(), nslots, copy, e->beams.target, e->beams.last, e->beams.strain, e->beams.stress, dead, (float4 *)beams,
             (uint8_t *)alive);
     }
     SB_HIP(e, hipGetLastError());
@@ -255,15 +210,12 @@ static sb_status sbs_write(sb_engine *e, const void *particles)
 static sb_status sbs_build_import_tables(sb_engine *e)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    if (!e->sio) e->sio = new SbStateIoState();
     SbStateIoState &s = *e->sio;
-    const uint32_t maxP = e->opt.max_particles, Bu = sb_user_beams(e), B = e->B;
-    std::vector<uint32_t> row(std::max<uint32_t>(B, 1), 0xFFFFFFFFu);
-    for (uint32_t u = 0; u < Bu; u++) {
-        const uint32_t sl = sb_user_slot(e, u), idx = map_get(e, e->h_mapping.data(), (size_t)maxP + u);
-        if (sl >= B || idx >= e->opt.max_beams) SB_FAIL(e, SB_ERR_STATE, "sb_write_beams_device: beam slot outside the scene");
-        row[sl] = idx;
-    }
+    const uint32_t Bu = sb_user_beams(e);
+    std::vector<uint2> slots;
+    SB_TRY(sbq_user_slots(e, "sb_write_beams_device", slots));
+    std::vector<uint32_t> row(std::max<uint32_t>(e->B, 1), 0xFFFFFFFFu);
+    for (uint32_t u = 0; u < Bu; u++) row[slots[u].x] = slots[u].y;
     std::vector<float> rest;
     if (e->bk.K) {
         if (e->bk.h_beam_slot.size() != e->nbeam) SB_FAIL(e, SB_ERR_STATE, "sb_write_beams_device: %zu beams in the host map, %u on the device", e->bk.h_beam_slot.size(), e->nbeam);
@@ -272,23 +224,11 @@ static sb_status sbs_build_import_tables(sb_engine *e)
             for (size_t g = g0; g < g1; g++) rest[g] = e->h_beams[e->bk.h_beam_slot[g]].f[0];
         });
     }
-    auto fit = [&](void **p, size_t *cap, size_t bytes) -> sb_status {
-        if (*p && *cap >= bytes) return SB_OK;
-        if (*p) {
-            SB_HIP(e, hipStreamSynchronize(e->stream)); // an import in flight may still read it
-            SB_HIP(e, hipFree(*p));
-            *p = nullptr;
-            *cap = 0;
-        }
-        SB_HIP(e, hipMalloc(p, bytes));
-        *cap = bytes;
-        return SB_OK;
-    };
-    SB_TRY(fit((void **)&s.d_imp_row, &s.cap_imp_row, row.size() * 4));
-    SB_HIP(e, hipMemcpyAsync(s.d_imp_row, row.data(), row.size() * 4, hipMemcpyHostToDevice, e->stream));
+    SB_TRY(s.buf[SBS_B_IMP_ROW].grow(e, row.size() * 4));
+    SB_HIP(e, hipMemcpyAsync(s.buf[SBS_B_IMP_ROW].p, row.data(), row.size() * 4, hipMemcpyHostToDevice, e->stream));
     if (!rest.empty()) {
-        SB_TRY(fit((void **)&s.d_imp_rest, &s.cap_imp_rest, rest.size() * 4));
-        SB_HIP(e, hipMemcpyAsync(s.d_imp_rest, rest.data(), rest.size() * 4, hipMemcpyHostToDevice, e->stream));
+        SB_TRY(s.buf[SBS_B_IMP_REST].grow(e, rest.size() * 4));
+        SB_HIP(e, hipMemcpyAsync(s.buf[SBS_B_IMP_REST].p, rest.data(), rest.size() * 4, hipMemcpyHostToDevice, e->stream));
     }
     SB_HIP(e, hipStreamSynchronize(e->stream)); // (the host vectors go out of scope)
     s.imp_valid = true;
@@ -306,19 +246,19 @@ static sb_status sbs_write_beams(sb_engine *e, const void *beams, uint32_t field
     SB_TRY(sbs_check(e, "sb_write_beams_device"));
     const uint32_t nc = e->nbeam;
     if (!nc || !sb_user_beams(e)) return SB_OK;
-    if (!e->sio || !e->sio->imp_valid) SB_TRY(sbs_build_import_tables(e));
+    if (!e->sio->imp_valid) SB_TRY(sbs_build_import_tables(e));
     const SbStateIoState &s = *e->sio;
     const uint32_t blocks = (nc + SBS_BLOCK - 1) / SBS_BLOCK;
     if (e->bk.K) {
         const SbBlockedDev &k = e->bk;
         k_state_import_beams_blocked<<<blocks, SBS_BLOCK, 0, e->stream>>>(
-            (const uint2 *)beams, e->beams.slot, s.d_imp_row, (const uint32_t *)s.d_imp_rest, nc, e->B, e->opt.max_beams, fields,
+            (const uint2 *)beams, e->beams.slot, s.buf[SBS_B_IMP_ROW].as<uint32_t>(), s.buf[SBS_B_IMP_REST].as<uint32_t>(), nc, e->B, e->opt.max_beams, fields,
             (uint32_t *)k.d_target[0], (uint32_t *)k.d_target[1], (uint32_t *)k.d_last[k.cur], k.d_plastic[0], k.d_plastic[1], k.d_tile_b0,
             k.ntiles);
     } else {
         // (SB_COLLIDE_GRID with a blocked plan beside the tiling: that plan borrows target / last from these arrays and recomputes its
         // plastic flags at the start of every run -- k_hybrid_to_blocked, sb_blocked.hip:676 -- so the tiled layout is all there is to write)
-        k_state_import_beams<<<blocks, SBS_BLOCK, 0, e->stream>>>((const uint2 *)beams, e->beams.slot, s.d_imp_row, nc, e->B,
+        k_state_import_beams<<<blocks, SBS_BLOCK, 0, e->stream>>>((const uint2 *)beams, e->beams.slot, s.buf[SBS_B_IMP_ROW].as<uint32_t>(), nc, e->B,
                                                                   e->opt.max_beams, fields, (uint32_t *)e->beams.target,
                                                                   (uint32_t *)e->beams.last);
     }
@@ -400,26 +340,26 @@ static sb_status sbs_checkpoint(sb_engine *e)
 {
     if (!e) return SB_ERR_INVALID;
     SB_TRY(sbs_check(e, "sb_checkpoint_device"));
-    if (!e->sio) e->sio = new SbStateIoState();
     SbStateIoState &s = *e->sio;
+    SbDevBuf &ck = s.buf[SBS_B_CKPT];
     std::vector<SbRunItem> items;
     sbs_walk_run_state(e, e->cur, e->bk.cur, items);
     size_t total = 0;
     for (const SbRunItem &it : items) total += sbs_item_stride(it.bytes);
     total = std::max<size_t>(total, 256);
-    if (!s.d_ckpt || s.cap_ckpt < total) { // (the first checkpoint after an upload: every later one finds the block)
+    if (!ck.p || ck.cap < total) { // (the first checkpoint after an upload: every later one finds the block)
         sbs_drop_checkpoint(e);
         void *blk = nullptr;
         if (hipMalloc(&blk, total) != hipSuccess) {
             (void)hipGetLastError();
             SB_FAIL(e, SB_ERR_OOM, "sb_checkpoint_device: no device memory for %zu bytes (the engine is unchanged; there is no checkpoint)", total);
         }
-        s.d_ckpt = blk;
-        s.cap_ckpt = total;
+        ck.p = blk;
+        ck.cap = total;
     }
     size_t off = 0;
     for (const SbRunItem &it : items) {
-        SB_HIP(e, hipMemcpyAsync((uint8_t *)s.d_ckpt + off, it.p, it.bytes, hipMemcpyDeviceToDevice, e->stream));
+        SB_HIP(e, hipMemcpyAsync(ck.as<uint8_t>() + off, it.p, it.bytes, hipMemcpyDeviceToDevice, e->stream));
         off += sbs_item_stride(it.bytes);
     }
     s.ck_cur = e->cur;
@@ -435,13 +375,13 @@ static sb_status sbs_restore(sb_engine *e)
 {
     if (!e) return SB_ERR_INVALID;
     SB_TRY(sbs_check(e, "sb_restore_device"));
-    if (!e->sio || !e->sio->d_ckpt || !e->sio->ckpt_bytes) SB_FAIL(e, SB_ERR_STATE, "sb_restore_device without a checkpoint (sb_checkpoint_device; every upload drops it)");
+    if (!e->sio->buf[SBS_B_CKPT].p || !e->sio->ckpt_bytes) SB_FAIL(e, SB_ERR_STATE, "sb_restore_device without a checkpoint (sb_checkpoint_device; every upload drops it)");
     SbStateIoState &s = *e->sio;
     std::vector<SbRunItem> items;
     sbs_walk_run_state(e, s.ck_cur, s.ck_bcur, items);
     size_t off = 0;
     for (const SbRunItem &it : items) {
-        SB_HIP(e, hipMemcpyAsync(it.p, (const uint8_t *)s.d_ckpt + off, it.bytes, hipMemcpyDeviceToDevice, e->stream));
+        SB_HIP(e, hipMemcpyAsync(it.p, s.buf[SBS_B_CKPT].as<const uint8_t>() + off, it.bytes, hipMemcpyDeviceToDevice, e->stream));
         off += sbs_item_stride(it.bytes);
     }
     if (off > s.ckpt_bytes) SB_FAIL(e, SB_ERR_STATE, "sb_restore_device: the checkpoint holds %zu bytes, the scene's run state %zu", s.ckpt_bytes, off);
@@ -479,47 +419,16 @@ bool sbs_info(sb_engine *e, const char *key, uint64_t *value)
     return true;
 }
 
-#define SBS_GUARDED(e, call)                                              \
-    try {                                                                 \
-        return (call);                                                    \
-    } catch (const std::bad_alloc &) {                                    \
-        if (e) (e)->err = "out of host memory";                           \
-        return SB_ERR_OOM;                                                \
-    } catch (const std::exception &ex) {                                  \
-        if (e) (e)->err = std::string("internal error: ") + ex.what();    \
-        return SB_ERR_INVALID;                                            \
-    }
-
 extern "C" {
 
-sb_status sb_write_beams_device(sb_engine *e, const void *device_beams, uint32_t fields) { SBS_GUARDED(e, sbs_write_beams(e, device_beams, fields)) }
-sb_status sb_checkpoint_device(sb_engine *e) { SBS_GUARDED(e, sbs_checkpoint(e)) }
-sb_status sb_restore_device(sb_engine *e) { SBS_GUARDED(e, sbs_restore(e)) }
+sb_status sb_write_beams_device(sb_engine *e, const void *device_beams, uint32_t fields) { SB_GUARDED(e, sbs_write_beams(e, device_beams, fields)) }
+sb_status sb_checkpoint_device(sb_engine *e) { SB_GUARDED(e, sbs_checkpoint(e)) }
+sb_status sb_restore_device(sb_engine *e) { SB_GUARDED(e, sbs_restore(e)) }
 
 sb_status sb_read_state_device(sb_engine *e, void *device_particles, void *device_beams, void *device_beam_alive)
 {
-    try {
-        return sbs_read(e, device_particles, device_beams, device_beam_alive);
-    } catch (const std::bad_alloc &) {
-        if (e) e->err = "out of host memory";
-        return SB_ERR_OOM;
-    } catch (const std::exception &ex) {
-        if (e) e->err = std::string("internal error: ") + ex.what();
-        return SB_ERR_INVALID;
-    }
+    SB_GUARDED(e, sbs_read(e, device_particles, device_beams, device_beam_alive))
 }
-
-sb_status sb_write_particles_device(sb_engine *e, const void *device_particles)
-{
-    try {
-        return sbs_write(e, device_particles);
-    } catch (const std::bad_alloc &) {
-        if (e) e->err = "out of host memory";
-        return SB_ERR_OOM;
-    } catch (const std::exception &ex) {
-        if (e) e->err = std::string("internal error: ") + ex.what();
-        return SB_ERR_INVALID;
-    }
-}
+sb_status sb_write_particles_device(sb_engine *e, const void *device_particles) { SB_GUARDED(e, sbs_write(e, device_particles)) }
 
 } // extern "C"

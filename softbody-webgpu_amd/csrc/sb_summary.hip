@@ -26,7 +26,7 @@
 #include <string>
 #include <vector>
 
-#include "sb_engine.h"
+#include "sb_report.h"
 #include "sb_batch.h" // sbb_finite, sbb_fkey / sbb_unkey, SBB_QNAN, sbb_pow2_at_least: the batch row's own helpers
 
 #define SBM_BLOCK 256u
@@ -280,59 +280,30 @@ __global__ __launch_bounds__(SBM_BLOCK) void k_summary_row(const double *__restr
 
 // ---------------------------------------------------------------- host side
 
-template <class T>
-static sb_status sbm_grow(sb_engine *e, T **p, size_t &cap, size_t n)
-{
-    n = std::max<size_t>(n, 1);
-    if (*p && cap >= n) return SB_OK;
-    if (*p) {
-        SB_HIP(e, hipStreamSynchronize(e->stream)); // a summary in flight may still read it
-        SB_HIP(e, hipFree(*p));
-        *p = nullptr;
-        cap = 0;
-    }
-    SB_HIP(e, hipMalloc((void **)p, n * sizeof(T)));
-    cap = n;
-    return SB_OK;
-}
-
-// The tree is over DATA indices, the engine's arrays are in its own order: per particle data index the internal particle
-// (e->h_pidx inverted), per beam data index the engine slot and the copy sb_load_buffers reads back for it (its beam loop; the
-// caller's slots of the latest upload).  Both end at the highest data index in use: a capacity far above the scene costs no reads.
-static sb_status sbm_build_tables(sb_engine *e)
+// The tree is over DATA indices, the engine's arrays are in its own order.  Particles: the shared table data index -> internal
+// particle (sbq_need).  Beams, this file's own: per beam data index the engine slot and the copy sb_load_buffers reads back for it
+// (its beam loop; the caller's slots of the latest upload).  Both end at the highest data index in use: a capacity far above the
+// scene costs no reads.
+static sb_status sbm_build_bleaf(sb_engine *e)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    if (!e->sio) e->sio = new SbStateIoState();
     SbStateIoState &s = *e->sio;
-    const uint32_t P = e->P, maxP = e->opt.max_particles, maxB = e->opt.max_beams, Bu = sb_user_beams(e);
-    if (e->h_pidx.size() != P || e->h_copy_of_slot.size() < e->B) SB_FAIL(e, SB_ERR_STATE, "sb_summary: host shadows of the scene are inconsistent");
-    uint32_t np = 0, nb = 0;
-    for (uint32_t i = 0; i < P; i++) np = std::max(np, e->h_pidx[i] + 1u);
-    if (np > maxP) SB_FAIL(e, SB_ERR_STATE, "sb_summary: particle data index outside the scene");
-    std::vector<uint32_t> inv(std::max<uint32_t>(np, 1), 0xFFFFFFFFu);
-    for (uint32_t i = 0; i < P; i++) inv[e->h_pidx[i]] = i;
-    std::vector<uint2> slots(std::max<uint32_t>(Bu, 1));
-    sbt::parallel_ranges(Bu, 1 << 16, [&](size_t u0, size_t u1) {
-        for (size_t u = u0; u < u1; u++) slots[u] = make_uint2(sb_user_slot(e, u), map_get(e, e->h_mapping.data(), (size_t)maxP + u));
-    });
-    for (uint32_t u = 0; u < Bu; u++) {
-        if (slots[u].x >= e->B || slots[u].y >= maxB) SB_FAIL(e, SB_ERR_STATE, "sb_summary: beam slot outside the scene");
-        nb = std::max(nb, slots[u].y + 1u);
-    }
+    const uint32_t Bu = sb_user_beams(e);
+    if (e->h_copy_of_slot.size() < e->B) SB_FAIL(e, SB_ERR_STATE, "sb_summary: host shadows of the scene are inconsistent");
+    std::vector<uint2> slots;
+    SB_TRY(sbq_user_slots(e, "sb_summary", slots));
+    uint32_t nb = 0;
+    for (uint32_t u = 0; u < Bu; u++) nb = std::max(nb, slots[u].y + 1u);
     std::vector<uint2> leaf(std::max<uint32_t>(nb, 1), make_uint2(0xFFFFFFFFu, 0u));
     for (uint32_t u = 0; u < Bu; u++) leaf[slots[u].y] = make_uint2(slots[u].x, e->h_copy_of_slot[slots[u].x]);
     for (uint32_t u = 0; u < Bu; u++)
         if (leaf[slots[u].y].y >= e->nbeam) SB_FAIL(e, SB_ERR_STATE, "sb_summary: beam copy outside the scene");
-    SB_TRY(sbm_grow(e, &s.d_sum_pinv, s.cap_sum_pinv, inv.size()));
-    SB_TRY(sbm_grow(e, &s.d_sum_bleaf, s.cap_sum_bleaf, leaf.size()));
-    SB_HIP(e, hipMemcpyAsync(s.d_sum_pinv, inv.data(), inv.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    SB_HIP(e, hipMemcpyAsync(s.d_sum_bleaf, leaf.data(), leaf.size() * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+    SB_TRY(s.buf[SBM_B_BLEAF].grow(e, leaf.size() * sizeof(uint2)));
+    SB_HIP(e, hipMemcpyAsync(s.buf[SBM_B_BLEAF].p, leaf.data(), leaf.size() * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
     SB_HIP(e, hipStreamSynchronize(e->stream)); // (the host vectors go out of scope)
-    s.sum_np = np;
     s.sum_nb = nb;
-    s.sum_nslots = Bu;
-    s.sum_valid = true;
-    s.sum_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    s.bleaf_valid = true;
+    s.bleaf_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return SB_OK;
 }
 
@@ -380,44 +351,37 @@ static sb_status sbm_enqueue(sb_engine *e, const sb_summary_options *o, void *ro
     const char *what = host ? "sb_summary" : "sb_summary_device";
     if (!row || ((uintptr_t)row & 3u)) SB_FAIL(e, SB_ERR_INVALID, "%s: null or misaligned row", what);
     if ((uintptr_t)counts & 7u) SB_FAIL(e, SB_ERR_INVALID, "%s: counts must be 8-byte aligned", what);
-    if (o && o->struct_size != 0 && o->struct_size != sizeof(sb_summary_options))
-        SB_FAIL(e, SB_ERR_INVALID, "%s: sb_summary_options.struct_size %u != %zu", what, o->struct_size, sizeof(sb_summary_options));
-    const uint32_t m_asked = o && o->struct_size ? o->partials : 0u;
+    const uint32_t m_asked = o && o->struct_size == sizeof(sb_summary_options) ? o->partials : 0u;
     if (m_asked && (m_asked < SBM_BLOCK || (m_asked & (m_asked - 1u)) || m_asked > SB_SUMMARY_MAX_PARTIALS))
         SB_FAIL(e, SB_ERR_INVALID, "%s: partials %u is not a power of two in [256, %u]", what, m_asked, (unsigned)SB_SUMMARY_MAX_PARTIALS);
-    if (o && o->struct_size)
-        for (uint32_t r : o->reserved)
-            if (r) SB_FAIL(e, SB_ERR_INVALID, "%s: reserved option words must be zero", what);
-    if (e->opt.max_particles > 0x80000000u || e->opt.max_beams > 0x80000000u)
-        SB_FAIL(e, SB_ERR_INVALID, "%s: capacities above 2^31 are not summed", what);
-    if (!e->loaded) SB_FAIL(e, SB_ERR_STATE, "%s before sb_write_buffers", what);
-    if (e->halo_configured || e->n_ghost_p || e->n_send_p || e->n_ghost_b || e->n_send_b || e->n_peers || e->mailbox)
-        SB_FAIL(e, SB_ERR_UNSUPPORTED, "%s: the engine has ghost zones or peers configured (per-rank rows are not handled)", what);
-    SB_HIP(e, hipSetDevice(e->device));
-    if (!e->sio || !e->sio->sum_valid) SB_TRY(sbm_build_tables(e));
+    SB_TRY(sbq_preflight(e, what, o, "summed", "per-rank rows are not handled"));
+    SB_TRY(sbq_need(e, "sb_summary", SBQ_PARTICLES));
     SbStateIoState &s = *e->sio;
+    if (!s.bleaf_valid) SB_TRY(sbm_build_bleaf(e));
+    s.sum_build_ms = s.part_ms + s.bleaf_ms;
 
     const SbmCut cp{sbb_pow2_at_least(e->opt.max_particles), m_asked ? m_asked : sbm_default_partials(sbb_pow2_at_least(e->opt.max_particles))};
     const SbmCut cb{sbb_pow2_at_least(e->opt.max_beams), m_asked ? m_asked : sbm_default_partials(sbb_pow2_at_least(e->opt.max_beams))};
     uint32_t np = cp.first(), nb = cb.first();
     const uint32_t stride_p = np;
-    SB_TRY(sbm_grow(e, &s.d_sum_part, s.cap_sum_part, (size_t)5 * np + nb));
-    SB_TRY(sbm_grow(e, &s.d_sum_stat, s.cap_sum_stat, (size_t)SBM_NSTAT));
-    if (host) SB_TRY(sbm_grow(e, &s.d_sum_out, s.cap_sum_out, (size_t)8 + SB_SUMMARY_WORDS / 2)); // 8 counts, then the row
-    double *pcol = s.d_sum_part, *bcol = s.d_sum_part + (size_t)5 * np;
-    unsigned long long *d_counts = host ? s.d_sum_out : (unsigned long long *)counts;
-    float *d_row = host ? (float *)(s.d_sum_out + 8) : (float *)row;
+    SB_TRY(s.buf[SBM_B_PART].grow(e, ((size_t)5 * np + nb) * sizeof(double)));
+    SB_TRY(s.buf[SBM_B_STAT].grow(e, (size_t)SBM_NSTAT * sizeof(unsigned long long)));
+    if (host) SB_TRY(s.buf[SBM_B_OUT].grow(e, ((size_t)8 + SB_SUMMARY_WORDS / 2) * sizeof(unsigned long long))); // 8 counts, then the row
+    double *pcol = s.buf[SBM_B_PART].as<double>(), *bcol = pcol + (size_t)5 * np;
+    unsigned long long *d_stat = s.buf[SBM_B_STAT].as<unsigned long long>(), *d_out = s.buf[SBM_B_OUT].as<unsigned long long>();
+    unsigned long long *d_counts = host ? d_out : (unsigned long long *)counts;
+    float *d_row = host ? (float *)(d_out + 8) : (float *)row;
 
-    k_summary_init<<<1, 64, 0, e->stream>>>(s.d_sum_stat);
+    k_summary_init<<<1, 64, 0, e->stream>>>(d_stat);
     const SbParticleArrays &c = e->part[e->cur];
-    const SbmParticles sp{s.d_sum_pinv, c.pos, c.vel, c.acc, s.sum_np};
-    const SbmBeams sbm{s.d_sum_bleaf, e->B && e->delete_gen ? e->d_dead_gen : nullptr /* as sb_load_buffers (fetch_dead) sees it */,
+    const SbmParticles sp{s.buf[SBQ_B_PINV].as<uint32_t>(), c.pos, c.vel, c.acc, s.np};
+    const SbmBeams sbm{s.buf[SBM_B_BLEAF].as<uint2>(), e->B && e->delete_gen ? e->d_dead_gen : nullptr /* as sb_load_buffers (fetch_dead) sees it */,
                        e->d_broken, e->beams.strain, e->beams.stress, s.sum_nb};
-    SBM_SWITCH_LEAF(cp.W / np, (k_summary_particles<R_><<<(np + SBM_BLOCK - 1) / SBM_BLOCK, SBM_BLOCK, 0, e->stream>>>(sp, np, pcol, s.d_sum_stat)));
-    SBM_SWITCH_LEAF(cb.W / nb, (k_summary_beams<R_><<<(nb + SBM_BLOCK - 1) / SBM_BLOCK, SBM_BLOCK, 0, e->stream>>>(sbm, nb, bcol, s.d_sum_stat)));
+    SBM_SWITCH_LEAF(cp.W / np, (k_summary_particles<R_><<<(np + SBM_BLOCK - 1) / SBM_BLOCK, SBM_BLOCK, 0, e->stream>>>(sp, np, pcol, d_stat)));
+    SBM_SWITCH_LEAF(cb.W / nb, (k_summary_beams<R_><<<(nb + SBM_BLOCK - 1) / SBM_BLOCK, SBM_BLOCK, 0, e->stream>>>(sbm, nb, bcol, d_stat)));
     SB_TRY(sbm_fold(e, cp, pcol, stride_p, 5u, &np));
     SB_TRY(sbm_fold(e, cb, bcol, nb, 1u, &nb));
-    k_summary_row<<<1, SBM_BLOCK, 0, e->stream>>>(pcol, stride_p, np, bcol, nb, s.d_sum_stat, d_row,
+    k_summary_row<<<1, SBM_BLOCK, 0, e->stream>>>(pcol, stride_p, np, bcol, nb, d_stat, d_row,
                                                   host || counts ? d_counts : nullptr);
     SB_HIP(e, hipGetLastError());
     s.sum_partials = cp.m;
@@ -437,46 +401,26 @@ bool sbm_info(sb_engine *e, const char *key, uint64_t *value)
     else if (k == "summary_table_build_us") *value = e->sio ? (uint64_t)(e->sio->sum_build_ms * 1000.0 + 0.5) : 0u;
     else if (k == "summary_kernel_vgprs" || k == "summary_kernel_scratch_bytes") { // the most over every kernel a call may launch
 #define SBM_LEAVES(K) (const void *)K<1>, (const void *)K<2>, (const void *)K<4>, (const void *)K<8>, (const void *)K<16>
-        const void *ks[] = {SBM_LEAVES(k_summary_particles), SBM_LEAVES(k_summary_beams), SBM_LEAVES(k_summary_fold),
+        const std::vector<const void *> ks = {SBM_LEAVES(k_summary_particles), SBM_LEAVES(k_summary_beams), SBM_LEAVES(k_summary_fold),
                             (const void *)k_summary_fold<32>, (const void *)k_summary_fold<64>, (const void *)k_summary_row,
                             (const void *)k_summary_init};
 #undef SBM_LEAVES
-        uint64_t most = 0;
-        for (const void *f : ks) {
-            hipFuncAttributes fa{};
-            if (hipSetDevice(e->device) != hipSuccess || hipFuncGetAttributes(&fa, f) != hipSuccess) {
-                (void)hipGetLastError();
-                return false;
-            }
-            most = std::max<uint64_t>(most, k == "summary_kernel_vgprs" ? (uint64_t)fa.numRegs : (uint64_t)fa.localSizeBytes);
-        }
-        *value = most;
+        return sbq_kernel_most(e, ks, k == "summary_kernel_vgprs", value);
     }
     else return false;
     return true;
 }
 
-#define SBM_GUARDED(e, call)                                                   \
-    try {                                                                      \
-        return (call);                                                         \
-    } catch (const std::bad_alloc &) {                                         \
-        if (e) (e)->err = "out of host memory";                                \
-        return SB_ERR_OOM;                                                     \
-    } catch (const std::exception &ex) {                                       \
-        if (e) (e)->err = std::string("internal error: ") + ex.what();         \
-        return SB_ERR_INVALID;                                                 \
-    }
-
 extern "C" {
 
 sb_status sb_summary_device(sb_engine *e, const sb_summary_options *opts, void *device_row_f32, void *device_counts_u64)
 {
-    SBM_GUARDED(e, sbm_enqueue(e, opts, device_row_f32, device_counts_u64, false))
+    SB_GUARDED(e, sbm_enqueue(e, opts, device_row_f32, device_counts_u64, false))
 }
 
 sb_status sb_summary(sb_engine *e, const sb_summary_options *opts, float *row, uint64_t *counts)
 {
-    SBM_GUARDED(e, sbm_enqueue(e, opts, row, counts, true))
+    SB_GUARDED(e, sbm_enqueue(e, opts, row, counts, true))
 }
 
 } // extern "C"

@@ -14,8 +14,8 @@ import summary_cases as sc
 from batch_bodies_cases import path_edges
 
 SORT_KEYS = 1024        # SBY_SORT
-SCAN_WORDS = 1024       # SBY_SCAN
-SCAN_SUMS_BLOCK = 256   # SBY_BLOCK
+SCAN_WORDS = 1024       # SBQ_SCAN (sb_report.h)
+SCAN_SUMS_BLOCK = 256   # SBQ_BLOCK
 INT32_MIN = -2 ** 31
 
 

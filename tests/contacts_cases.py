@@ -7,8 +7,8 @@ import numpy as np
 import batch_contacts_cases as bcc
 import contacts_ref as cref
 
-SCAN_BLOCK = 1024       # SBC_SCAN of sb_contacts.hip: the words a workgroup of the cell scan owns
-SCAN_SUMS = 256         # SBC_BLOCK: the block sums one trip of k_contacts_scan_sums' loop takes
+SCAN_BLOCK = 1024       # SBQ_SCAN of sb_report.h: the words a workgroup of the scan owns
+SCAN_SUMS = 256         # SBQ_BLOCK: the block sums one trip of k_report_scan_sums' loop takes
 SECOND_TRIP = SCAN_BLOCK * SCAN_SUMS     # the first word whose block sum the SECOND trip of that loop owns: 2^18
 
 

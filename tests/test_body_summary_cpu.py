@@ -24,8 +24,7 @@ import summary_cases as sc  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["sb_body_summary", "sb_body_summary_device"]
-KERNELS = ("k_bsum_stage", "k_bsum_hist", "k_bsum_scatter", "k_bsum_scan_reduce", "k_bsum_scan_sums", "k_bsum_scan_add", "k_bsum_leaves",
-           "k_bsum_level", "k_bsum_beams", "k_bsum_groups", "k_bsum_rank_of", "k_bsum_rows", "k_bsum_rank")
+KERNELS = ("k_bsum_stage", "k_bsum_hist", "k_bsum_scatter", "k_bsum_leaves", "k_bsum_level", "k_bsum_beams", "k_bsum_groups", "k_bsum_rank_of", "k_bsum_rows", "k_bsum_rank")
 
 
 def test_header_declares_and_library_exports_the_calls(sb):
@@ -238,8 +237,10 @@ def test_callers_labels_figures(sb):
 
 
 def test_block_sizes_are_the_kernels(sb):
-    src = open(os.path.join(ROOT, "softbody-webgpu_amd", "csrc", "sb_body_summary.hip")).read()
-    assert "#define SBY_BLOCK 256u" in src and "#define SBY_PER 4u" in src
+    csrc = os.path.join(ROOT, "softbody-webgpu_amd", "csrc")
+    src, scan = open(os.path.join(csrc, "sb_body_summary.hip")).read(), open(os.path.join(csrc, "sb_report.h")).read()
+    assert "#define SBY_BLOCK 256u" in src and "#define SBY_PER 4u" in src       # the sort
+    assert "#define SBQ_BLOCK 256u" in scan and "#define SBQ_PER 4u" in scan     # the scan (sb_report.hip)
     assert yc.SORT_KEYS == yc.SCAN_WORDS == 256 * 4 and yc.SCAN_SUMS_BLOCK == 256
 
 
@@ -354,12 +355,17 @@ def test_sparse_capacity_scene_skips_levels(sb):
 
 
 def test_no_kernel_of_the_call_spills_or_uses_scratch():
-    """the compiler's own report (tools/kernel_resources.py) for every kernel of sb_body_summary.hip, and the committed table is that report"""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"),
-                        os.path.join(ROOT, "softbody-webgpu_amd", "csrc", "sb_body_summary.hip"), "k_bsum"], capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr
-    rows = [ln.split() for ln in p.stdout.splitlines() if "k_bsum" in ln]
-    assert sorted(r[0] for r in rows) == sorted(KERNELS)
-    for r in rows:
-        assert r[r.index("spill") + 1] == "0" and r[r.index("scratch") + 1] == "0", r
-    assert p.stdout == open(os.path.join(ROOT, "profiles", "body_summary_kernel_resources.txt")).read()
+    """the compiler's own report (tools/kernel_resources.py) for every kernel of sb_body_summary.hip and for the scan it launches
+    (sb_report.hip), and the committed tables are that report"""
+    csrc = os.path.join(ROOT, "softbody-webgpu_amd", "csrc")
+    scan = tuple("k_report_scan_%s<unsigned %s>" % (k, t) for k in ("reduce", "sums", "add") for t in ("int", "long long"))
+    for src, prefix, table, kernels in (("sb_body_summary.hip", "k_bsum", "body_summary_kernel_resources.txt", KERNELS),
+                                        ("sb_report.hip", "k_report", "report_kernel_resources.txt", scan)):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), os.path.join(csrc, src), prefix],
+                           capture_output=True, text=True)
+        assert p.returncode == 0, p.stderr
+        rows = [ln.split() for ln in p.stdout.splitlines() if prefix in ln]
+        assert sorted(" ".join(r[:r.index("VGPR")]).replace("void ", "") for r in rows) == sorted(kernels)
+        for r in rows:
+            assert r[r.index("spill") + 1] == "0" and r[r.index("scratch") + 1] == "0", r
+        assert p.stdout == open(os.path.join(ROOT, "profiles", table)).read()

@@ -227,17 +227,23 @@ def test_scene_reaches_the_second_trip_of_the_scan_of_the_block_sums(sb, name):
 
 
 def test_no_kernel_of_the_contacts_spills_or_uses_scratch():
-    """the compiler's own report (tools/kernel_resources.py) for every kernel of sb_contacts.hip, and the committed table is that report"""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"),
-                        os.path.join(ROOT, "softbody-webgpu_amd", "csrc", "sb_contacts.hip"), "k_contacts"], capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr
-    rows = [ln.split() for ln in p.stdout.splitlines() if "k_contacts" in ln]
-    names = " ".join(" ".join(r) for r in rows)
-    for k in ("k_contacts_bin", "k_contacts_scatter", "k_contacts_visit", "k_contacts_list", "k_contacts_tail", "k_contacts_counts",
-              "k_contacts_reduce<unsigned int>", "k_contacts_reduce<unsigned long long>", "k_contacts_scan_sums<unsigned int>",
-              "k_contacts_scan_sums<unsigned long long>", "k_contacts_scan_add<unsigned int>", "k_contacts_scan_add<unsigned long long>"):
-        assert k in names, k
-    assert len(rows) == 12
-    for r in rows:
-        assert r[r.index("spill") + 1] == "0" and r[r.index("scratch") + 1] == "0", r
-    assert p.stdout == open(os.path.join(ROOT, "profiles", "contacts_kernel_resources.txt")).read()
+    """the compiler's own report (tools/kernel_resources.py) for every kernel of sb_contacts.hip and for the scan it launches
+    (sb_report.hip), and the committed tables are that report"""
+    csrc = os.path.join(ROOT, "softbody-webgpu_amd", "csrc")
+    for src, prefix, table, kernels in (
+            ("sb_contacts.hip", "k_contacts", "contacts_kernel_resources.txt",
+             ("k_contacts_bin", "k_contacts_scatter", "k_contacts_visit", "k_contacts_list", "k_contacts_tail", "k_contacts_counts")),
+            ("sb_report.hip", "k_report", "report_kernel_resources.txt",
+             ("k_report_scan_reduce<unsigned int>", "k_report_scan_reduce<unsigned long long>", "k_report_scan_sums<unsigned int>",
+              "k_report_scan_sums<unsigned long long>", "k_report_scan_add<unsigned int>", "k_report_scan_add<unsigned long long>"))):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), os.path.join(csrc, src), prefix],
+                           capture_output=True, text=True)
+        assert p.returncode == 0, p.stderr
+        rows = [ln.split() for ln in p.stdout.splitlines() if prefix in ln]
+        names = " ".join(" ".join(r) for r in rows)
+        for k in kernels:
+            assert k in names, k
+        assert len(rows) == len(kernels) == 6
+        for r in rows:
+            assert r[r.index("spill") + 1] == "0" and r[r.index("scratch") + 1] == "0", r
+        assert p.stdout == open(os.path.join(ROOT, "profiles", table)).read()

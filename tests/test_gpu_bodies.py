@@ -12,6 +12,7 @@ import batch_bodies_ref as br
 import batch_cases as bcs
 import batch_harness as bh
 import bodies_cases as bc
+import report_harness as rh
 import summary_cases as sc
 from test_gpu_parity import ATOMIC, GRID, OFF, TILED, ALLPAIRS, assert_same
 from test_gpu_summary import READ_ONLY
@@ -21,10 +22,7 @@ pytestmark = pytest.mark.gpu
 
 
 def engine(sb, case, **kw):
-    buf = case["buf"]
-    eng = sb.Engine(bounds_size=case["bounds"], layout=buf.layout, max_particles=buf.max_particles, max_beams=buf.max_beams, **kw)
-    eng.write_buffers(buf)
-    return eng
+    return rh.engine(sb, case["buf"], case["bounds"], **kw)
 
 
 def brief(counts):
@@ -209,28 +207,11 @@ def test_equals_the_batch(sb, which):
 @pytest.mark.parametrize("what,mk,kw", READ_ONLY, ids=[r[0] for r in READ_ONLY])
 def test_read_only(sb, what, mk, kw):
     """frame, bodies, frame == frame, frame: the read-back byte for byte, the summary row, the promise flags and the schedule"""
-    if mk is None:   # a quiet lattice: the hybrid runs blocked launches under SB_COLLIDE_GRID
-        buf = sb.scenes.lattice_buffers(128, 96, d=30.0, origin=(300.0, 900.0), jitter=1.0, layout=2, velocity=(0.4, -1.0))
-        case = dict(buf=buf, bounds=6000.0)
-    else:
-        case = mk(sb)
-    out = {}
-    for k in ("plain", "read"):
-        eng = engine(sb, case, **kw)
-        eng.frame()
-        if k == "read":
-            eng.bodies(sizes=True)
-            eng.bodies(labels=False)
-            eng.bodies_host()
-        eng.frame()
-        row, counts = eng.summary(counts=True)
-        out[k] = (eng.load_buffers(case["buf"].copy()), row.cpu().numpy().tobytes(), counts.cpu().numpy().tolist(),
-                  [eng.info(x) for x in ("acc_dirty_tiles", "plastic_tiles", "grid_schedule", "substeps_done")])
-        if what == "hybrid":
-            assert eng.info("hybrid_launches") > 0
-        eng.destroy()
-    assert_same(out["read"][0], out["plain"][0], what)
-    assert out["read"][1:] == out["plain"][1:], (what, out["read"][2:], out["plain"][2:])
+    def calls(eng, case):
+        eng.bodies(sizes=True)
+        eng.bodies(labels=False)
+        eng.bodies_host()
+    rh.read_only(sb, what, mk, kw, engine, calls)
 
 
 # 10

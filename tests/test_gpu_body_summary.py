@@ -13,6 +13,7 @@ import batch_harness as bh
 import bodies_cases as bc
 import body_summary_cases as yc
 import body_summary_ref as yr
+import report_harness as rh
 import summary_cases as sc
 from test_gpu_parity import ATOMIC, GRID, OFF, TILED, assert_same
 from test_gpu_summary import READ_ONLY
@@ -25,10 +26,7 @@ SENTINEL = -77
 
 def engine(sb, buf, bounds=None, **kw):
     kw.setdefault("collision_mode", OFF)
-    eng = sb.Engine(bounds_size=bounds or bc.bounds_of(max(buf.particle_count, 1)), layout=buf.layout, max_particles=buf.max_particles,
-                    max_beams=buf.max_beams, **kw)
-    eng.write_buffers(buf)
-    return eng
+    return rh.engine(sb, buf, bounds or bc.bounds_of(max(buf.particle_count, 1)), **kw)
 
 
 def call(eng, rows, labels=None):
@@ -283,28 +281,12 @@ def test_every_combination_of_outputs_and_two_calls_in_a_row(sb):
 def test_read_only(sb, what, mk, kw):
     """frame, body_summary, frame == frame, frame: the read-back byte for byte, the summary row, the promise flags and the schedule"""
     import torch
-    if mk is None:   # a quiet lattice: the hybrid runs blocked launches under SB_COLLIDE_GRID
-        buf = sb.scenes.lattice_buffers(128, 96, d=30.0, origin=(300.0, 900.0), jitter=1.0, layout=2, velocity=(0.4, -1.0))
-        case = dict(buf=buf, bounds=6000.0)
-    else:
-        case = mk(sb)
-    out = {}
-    for k in ("plain", "read"):
-        eng = engine(sb, case["buf"], bounds=case["bounds"], **kw)
-        eng.frame()
-        if k == "read":
-            eng.body_summary(counts=True, rank=True)
-            eng.body_summary(torch.from_numpy(yc.caller_labels(case["buf"], "stripes")).cuda(), rows=3)
-            eng.body_summary_host()
-        eng.frame()
-        row, counts = eng.summary(counts=True)
-        out[k] = (eng.load_buffers(case["buf"].copy()), row.cpu().numpy().tobytes(), counts.cpu().numpy().tolist(),
-                  [eng.info(x) for x in ("acc_dirty_tiles", "plastic_tiles", "grid_schedule", "substeps_done")])
-        if what == "hybrid":
-            assert eng.info("hybrid_launches") > 0
-        eng.destroy()
-    assert_same(out["read"][0], out["plain"][0], what)
-    assert out["read"][1:] == out["plain"][1:], (what, out["read"][2:], out["plain"][2:])
+
+    def calls(eng, case):
+        eng.body_summary(counts=True, rank=True)
+        eng.body_summary(torch.from_numpy(yc.caller_labels(case["buf"], "stripes")).cuda(), rows=3)
+        eng.body_summary_host()
+    rh.read_only(sb, what, mk, kw, lambda sb, case, **k: engine(sb, case["buf"], bounds=case["bounds"], **k), calls)
 
 
 # 13

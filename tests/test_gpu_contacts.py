@@ -11,6 +11,7 @@ import pytest
 import batch_harness as bh
 import contacts_cases as cc
 import contacts_ref as cref
+import report_harness as rh
 import summary_cases as sc
 from test_gpu_parity import ATOMIC, GRID, OFF, TILED, ALLPAIRS, assert_same
 from test_gpu_summary import READ_ONLY
@@ -20,12 +21,8 @@ pytestmark = pytest.mark.gpu
 
 
 def engine(sb, scene, **kw):
-    buf = cc.for_engine(sb, scene["buf"])
     kw.setdefault("collision_mode", OFF)
-    eng = sb.Engine(bounds_size=scene["bounds"], particle_radius=scene.get("radius", 10.0), layout=buf.layout, max_particles=buf.max_particles,
-                    max_beams=buf.max_beams, **kw)
-    eng.write_buffers(buf)
-    return eng
+    return rh.engine(sb, cc.for_engine(sb, scene["buf"]), scene["bounds"], particle_radius=scene.get("radius", 10.0), **kw)
 
 
 def brief(counts):
@@ -204,33 +201,18 @@ def test_read_only(sb, what, mk, kw):
     """frame, contacts, frame == frame, frame: the read-back byte for byte, the summary row, the promise flags, the schedule and
     the hash's counters; on the hybrid (a quiet lattice under SB_COLLIDE_GRID, blocked launches) the answer is the reference's on
     the engine's own read-back"""
-    if mk is None:
-        buf = sb.scenes.lattice_buffers(128, 96, d=30.0, origin=(300.0, 900.0), jitter=1.0, layout=2, velocity=(0.4, -1.0))
-        case = dict(buf=buf, bounds=6000.0)
-    else:
-        case = mk(sb)
-    out = {}
-    for k in ("plain", "read"):
-        eng = engine(sb, case, **kw)
-        eng.frame()
-        if k == "read":
-            got = eng.contacts(pairs=64)
-            eng.contacts(labels=True, touch=False)
-            eng.contacts_host(pairs=3)
-            if what == "hybrid":
-                exp = cref.contacts_ref(eng.load_buffers(case["buf"].copy()), 10.0, case["bounds"], None, 64)
-                assert_contacts((got[0].cpu().numpy(), got[2].cpu().numpy(), got[1].cpu().numpy()), exp, "hybrid")
-        eng.frame()
-        row, counts = eng.summary(counts=True)
-        out[k] = (eng.load_buffers(case["buf"].copy()), row.cpu().numpy().tobytes(), counts.cpu().numpy().tolist(),
-                  [eng.info(x) for x in ("acc_dirty_tiles", "plastic_tiles", "grid_schedule", "substeps_done", "grid_builds", "grid_cells", "grid_wide")])
+    def calls(eng, case):
+        got = eng.contacts(pairs=64)
+        eng.contacts(labels=True, touch=False)
+        eng.contacts_host(pairs=3)
         if what == "hybrid":
-            assert eng.info("hybrid_launches") > 0
+            exp = cref.contacts_ref(eng.load_buffers(case["buf"].copy()), 10.0, case["bounds"], None, 64)
+            assert_contacts((got[0].cpu().numpy(), got[2].cpu().numpy(), got[1].cpu().numpy()), exp, "hybrid")
+
+    def after(eng, case):
         if what == "tiled grid":
             assert eng.info("grid_builds") > 1      # across a rebuild of the hash
-        eng.destroy()
-    assert_same(out["read"][0], out["plain"][0], what)
-    assert out["read"][1:] == out["plain"][1:], (what, out["read"][2:], out["plain"][2:])
+    rh.read_only(sb, what, mk, kw, engine, calls, keys=("grid_builds", "grid_cells", "grid_wide"), after=after)
 
 
 # 6

@@ -9,6 +9,7 @@ import pytest
 import batch_cases as bc
 import batch_harness as bh
 import batch_summary_ref as sr
+import report_harness as rh
 import summary_cases as sc
 from test_node_host import needs_node, run_node
 from test_gpu_parity import ATOMIC, GRID, OFF, TILED, ALLPAIRS, assert_same
@@ -17,10 +18,7 @@ pytestmark = pytest.mark.gpu
 
 
 def engine(sb, case, **kw):
-    buf = case["buf"]
-    eng = sb.Engine(bounds_size=case["bounds"], layout=buf.layout, max_particles=buf.max_particles, max_beams=buf.max_beams, **kw)
-    eng.write_buffers(buf)
-    return eng
+    return rh.engine(sb, case["buf"], case["bounds"], **kw)
 
 
 def check_now(eng, exp, what, partials=0):
@@ -131,25 +129,10 @@ READ_ONLY = [("tiled grid", lambda sb: sc.case_break(sb), dict(collision_mode=GR
 @pytest.mark.parametrize("what,mk,kw", READ_ONLY, ids=[r[0] for r in READ_ONLY])
 def test_read_only(sb, what, mk, kw):
     """frame, summary, frame == frame, frame: the read-back byte for byte, and the promise flags and the schedule"""
-    if mk is None:   # a quiet lattice: the hybrid runs blocked launches under SB_COLLIDE_GRID
-        buf = sb.scenes.lattice_buffers(128, 96, d=30.0, origin=(300.0, 900.0), jitter=1.0, layout=2, velocity=(0.4, -1.0))
-        case = dict(buf=buf, bounds=6000.0)
-    else:
-        case = mk(sb)
-    out = {}
-    for k in ("plain", "read"):
-        eng = engine(sb, case, **kw)
-        eng.frame()
-        if k == "read":
-            eng.summary(counts=True)
-            eng.summary(partials=256)
-        eng.frame()
-        out[k] = (eng.load_buffers(case["buf"].copy()), [eng.info(x) for x in ("acc_dirty_tiles", "plastic_tiles", "grid_schedule", "substeps_done")])
-        if what == "hybrid":
-            assert eng.info("hybrid_launches") > 0
-        eng.destroy()
-    assert_same(out["read"][0], out["plain"][0], what)
-    assert out["read"][1] == out["plain"][1], (what, out["read"][1], out["plain"][1])
+    def calls(eng, case):
+        eng.summary(counts=True)
+        eng.summary(partials=256)
+    rh.read_only(sb, what, mk, kw, engine, calls)
 
 
 def test_ordering_and_host_variant(sb, oracle):

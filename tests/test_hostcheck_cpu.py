@@ -1,8 +1,8 @@
 """The host side of the C library under sanitizers (`make -C softbody-webgpu_amd/csrc hostcheck`): the scene
 partitioner (csrc/sb_partition.cpp, driven by tests/partition_check.cpp on the reference's default scene, main.ts:188-246, and
 on a 90 000-particle lattice, v1 and v2 layouts) and the two multi-threaded upload planners (sb_tiling.h, sb_blocking.h with the
-check drivers of tests/test_tiling_cpu.py / test_blocking_cpu.py), the subsequence matcher of edit uploads (sb_edit.h) and the scene codec
-(sb_scene_codec.h), each built with AddressSanitizer + UBSan and with ThreadSanitizer.  CPU only: the GPU pool has no sanitizers."""
+check drivers of tests/test_tiling_cpu.py / test_blocking_cpu.py), the subsequence matcher of edit uploads (sb_edit.h), the scene codec
+(sb_scene_codec.h) and the table builder of the engine's reports (sb_report_tables.h), each built with AddressSanitizer + UBSan and with ThreadSanitizer.  CPU only: the GPU pool has no sanitizers."""
 import os
 import subprocess
 import sys
@@ -95,3 +95,17 @@ def test_scene_codec_under_sanitizers(built, sb, tmp_path, san):
         want.tofile(path + ".decoded")
         out = run(os.path.join(built, "scene_codec_check_" + san), [path, path + ".decoded"])
         assert "SCENE_CODEC_OK %d particles %d beams 17 defects" % (P, B) in out, (name, out)
+
+
+@pytest.mark.parametrize("san", ["asan", "tsan"])
+def test_report_tables_under_sanitizers(built, sb, tmp_path, san):
+    """csrc/sb_report_tables.h, the scene tables the engine's whole-scene reports share: for every scene, with the identity map of
+    the caller's beam slots and with a strictly increasing subset that drops every 7th slot, the parallel build equals a naive serial
+    one, pinv[h_pidx[i]] == i and every other entry is "none"; each of the five defects (a slot >= B, an endpoint where no particle
+    lives, an endpoint >= np, a copy >= nbeam, a data index >= max_particles), planted in the first and in a late range, is refused
+    (tests/report_tables_check.cpp)."""
+    for name, buf in check_scenes(sb).items():
+        path = str(tmp_path / (name + ".bin"))
+        dump(buf, path)
+        out = run(os.path.join(built, "report_tables_check_" + san), [path])
+        assert "REPORT_TABLES_OK %d particles %d beams 10 defects" % (buf.particle_count, buf.beam_count) in out, (name, out)

@@ -24,17 +24,11 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from engine_timing_shapes import config2, load_tree, timed  # noqa: E402
 
 SHAPES = ("config2", "config2_cut")
 WARM_SUBSTEPS = 64
-
-
-def load_tree(tree):
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("sb_entry_of_tree", os.path.join(tree, "__graft_entry__.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod.load_package()
 
 
 def without(buf, keep):
@@ -51,27 +45,13 @@ def without(buf, keep):
 
 def make_engine(sb, shape):
     import numpy as np
-    buf = sb.scenes.lattice_buffers(1000, 1000, d=30.0, origin=(1000.0, 1000.0), jitter=1.0, layout=2)
-    eng = sb.Engine(bounds_size=32000.0, layout=2, max_particles=buf.max_particles, max_beams=buf.max_beams, collision_mode=0)
-    eng.write_buffers(buf)
+    eng, buf = config2(sb)
     if shape == "config2_cut":
         buf = without(buf, np.random.default_rng(1).random(buf.beam_count) >= 0.01)
         eng.write_buffers(buf)
         if eng.info("uploads_edited") != 1:
             sys.exit("the cut upload did not keep the plan")
     return eng, buf
-
-
-def timed(eng, repeats, warmup, call):
-    ms = []
-    for k in range(warmup + repeats):
-        eng.sync()
-        t = time.perf_counter()
-        call()
-        eng.sync()
-        if k >= warmup:
-            ms.append((time.perf_counter() - t) * 1e3)
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "n": len(ms)}
 
 
 def worker(a):

@@ -27,18 +27,12 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from engine_timing_shapes import config2, config3, load_tree, timed  # noqa: E402
 
 SHAPES = ("config2", "config3", "config2cut")
 WARM_SUBSTEPS = 64
 ROWS = 8
-
-
-def load_tree(tree):
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("sb_entry_of_tree", os.path.join(tree, "__graft_entry__.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod.load_package()
 
 
 def without_a_hundredth(buf):
@@ -56,34 +50,16 @@ def without_a_hundredth(buf):
 
 def make_engine(sb, shape):
     if shape in ("config2", "config2cut"):
-        buf = sb.scenes.lattice_buffers(1000, 1000, d=30.0, origin=(1000.0, 1000.0), jitter=1.0, layout=2)
-        eng = sb.Engine(bounds_size=32000.0, layout=2, max_particles=buf.max_particles, max_beams=buf.max_beams, collision_mode=0)
-        eng.write_buffers(buf)
+        eng, buf = config2(sb)
         if shape == "config2cut":
             buf = without_a_hundredth(buf)
             eng.write_buffers(buf)
             assert eng.info("uploads_edited") == 1, "the upload did not keep the plan"
         eng.step(WARM_SUBSTEPS)
     else:
-        buf, bounds = sb.scenes.config3_buffers()
-        eng = sb.Engine(bounds_size=float(bounds), layout=2, max_particles=buf.max_particles, max_beams=buf.max_beams, collision_mode=2)
-        eng.write_buffers(buf)
-        for _ in range(sb.scenes.CONFIG3_SETTLE_FRAMES):
-            eng.frame()
+        eng, buf = config3(sb)
     eng.sync()
     return eng, buf
-
-
-def timed(eng, repeats, warmup, call):
-    ms = []
-    for k in range(warmup + repeats):
-        eng.sync()
-        t = time.perf_counter()
-        call()
-        eng.sync()
-        if k >= warmup:
-            ms.append((time.perf_counter() - t) * 1e3)
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "n": len(ms)}
 
 
 def worker(a):

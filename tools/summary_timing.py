@@ -30,45 +30,24 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from engine_timing_shapes import config2, load_tree, timed  # noqa: E402
 
 SHAPES = ("config2", "lattice_32x32")
 WARM_SUBSTEPS = 64
 
 
-def load_tree(tree):
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("sb_entry_of_tree", os.path.join(tree, "__graft_entry__.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod.load_package()
-
-
 def make_engine(sb, shape):
     if shape == "config2":
-        buf = sb.scenes.lattice_buffers(1000, 1000, d=30.0, origin=(1000.0, 1000.0), jitter=1.0, layout=2)
-        bounds = 32000.0
-    else:
-        lat = sb.scenes.lattice_buffers(32, 32, d=25.0, origin=(100.0, 100.0), spring=50.0, damp=700.0, yield_strain=0.2, strain_limit=0.5,
-                                        jitter=2.0, layout=2)
-        buf = sb.Buffers(2, 1024, 4096)
-        buf.set_scene(lat.particles[:lat.particle_count], lat.beams[:lat.beam_count].copy())
-        buf.metadata[12:28] = lat.metadata[12:28]
-        bounds = 1000.0
-    eng = sb.Engine(bounds_size=bounds, layout=2, max_particles=buf.max_particles, max_beams=buf.max_beams, collision_mode=0)
+        return config2(sb)
+    lat = sb.scenes.lattice_buffers(32, 32, d=25.0, origin=(100.0, 100.0), spring=50.0, damp=700.0, yield_strain=0.2, strain_limit=0.5,
+                                    jitter=2.0, layout=2)
+    buf = sb.Buffers(2, 1024, 4096)
+    buf.set_scene(lat.particles[:lat.particle_count], lat.beams[:lat.beam_count].copy())
+    buf.metadata[12:28] = lat.metadata[12:28]
+    eng = sb.Engine(bounds_size=1000.0, layout=2, max_particles=buf.max_particles, max_beams=buf.max_beams, collision_mode=0)
     eng.write_buffers(buf)
     return eng, buf
-
-
-def timed(eng, repeats, warmup, call):
-    ms = []
-    for k in range(warmup + repeats):
-        eng.sync()
-        t = time.perf_counter()
-        call()
-        eng.sync()
-        if k >= warmup:
-            ms.append((time.perf_counter() - t) * 1e3)
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "n": len(ms)}
 
 
 def pow2_at_least(n):
