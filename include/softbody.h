@@ -468,6 +468,70 @@ sb_status sb_write_beams_device(sb_engine *e, const void *device_beams, uint32_t
 sb_status sb_checkpoint_device(sb_engine *e);
 sb_status sb_restore_device(sb_engine *e);
 
+/* ---- cutting beams on the device: knife strokes and eraser discs ----
+ * "Cut what this stroke crosses", "erase what lies under this disc" -- without reading the scene back, removing beams on the host
+ * and uploading again.  A cut raises, for every beam it hits, the break flag the substep would have raised had the beam broken:
+ * from then on the beam is in exactly the state of one that broke in the last substep.  It still acts until the next delete pass
+ * (sb_frame's own, or sb_delete_pass), which removes it; until then it shows in sb_get_info "beams_flagged", in the pending counts
+ * of the summaries, and in a checkpoint.
+ *
+ * A SHAPE is 8 words, sb_cut_shape: { kind, x0, y0, x1, y1, 0, 0, 0 }; kind is an integer word, the coordinates are floats.
+ *   SB_CUT_NONE     ignored
+ *   SB_CUT_SEGMENT  a knife from P = (x0, y0) to Q = (x1, y1)
+ *   SB_CUT_DISC     an eraser with centre C = (x0, y0) and radius r = x1; y1 must be 0
+ * THE PREDICATE (csrc/sb_cut_math.h), float32, one rounding per operator, in the order written; A, B are the positions of the
+ * beam's endpoints in the particle state at the call's place in the stream.
+ *   Segment: orient(u, v, w) = (v.x - u.x) * (w.y - u.y) - (v.y - u.y) * (w.x - u.x); d1 = orient(P, Q, A), d2 = orient(P, Q, B),
+ *     d3 = orient(A, B, P), d4 = orient(A, B, Q); inbox(u, v, w): min(u.x, v.x) <= w.x <= max(u.x, v.x), and the same in y.  A hit iff
+ *       ((d1 > 0 && d2 < 0) || (d1 < 0 && d2 > 0)) && ((d3 > 0 && d4 < 0) || (d3 < 0 && d4 > 0)), or
+ *       d1 == 0 && inbox(P, Q, A), or d2 == 0 && inbox(P, Q, B), or d3 == 0 && inbox(A, B, P), or d4 == 0 && inbox(A, B, Q).
+ *   Disc: d = B - A, w = C - A, L2 = d.x * d.x + d.y * d.y, t = w.x * d.x + w.y * d.y, r2 = r * r.  Never a hit unless r >= 0;
+ *     if !(t > 0): a hit iff w.x * w.x + w.y * w.y <= r2; else if t >= L2: with u = C - B, iff u.x * u.x + u.y * u.y <= r2;
+ *     else with c = d.x * w.y - d.y * w.x, iff c * c <= r2 * L2.
+ *   No division, no square root.  Every comparison with a NaN is false, so a NaN in a beam or in a shape hits nothing.  An
+ *   infinity follows the operators like any other number (Inf - Inf and 0 * Inf are NaN, the rest compares): an infinite radius
+ *   over a finite beam is a hit.
+ * A beam is HIT when any shape of the call hits it.  Only LIVE beams of the latest upload are tested: the caller's beam slots that
+ * neither a delete pass nor a plan-keeping upload has removed (a beam whose flag is already pending is live).
+ *
+ * Outputs, each may be NULL:
+ *   hit    [max_beams] bytes: 1 / 0 per beam DATA index of the latest upload's beams (0 for a removed beam); indices that hold no
+ *          beam of the latest upload are NOT written, as in sb_read_state_device.
+ *   counts [SB_CUT_COUNT_WORDS] int64, exact: tested (live beams tested), hit, flagged (hit beams whose flag this call raised;
+ *          0 in a dry run), already_flagged (hit beams whose flag was pending before the call).
+ * flags: SB_CUT_DRY_RUN reports and raises no flag.  Every copy the engine's layout keeps of a hit beam gets its bit.  Particles,
+ * beam floats, the spatial hash and the hybrid schedule are untouched, exactly as sb_write_beams_device leaves them.
+ * sb_cut_device only ENQUEUES on the engine's stream: shapes and outputs are device memory, which must stay valid until that
+ * work has run.  The first call after an upload builds its tables on the host and waits for the stream once; no host copy of
+ * positions is read.  sb_cut takes host memory, WAITS and copies back.
+ * Errors, all before anything touches a device: SB_ERR_INVALID for a NULL handle, a struct_size that is neither 0 nor the
+ * struct's, a nonzero reserved word, unknown flag bits, n_shapes > SB_CUT_MAX_SHAPES, NULL shapes with n_shapes > 0, shapes that
+ * are not 4-byte or counts that are not 8-byte aligned, a capacity above 2^31; sb_cut also for a kind outside { 0, 1, 2 } and a disc
+ * with y1 != 0 (sb_cut_device cannot see the shapes: such a shape hits nothing).  SB_ERR_STATE before an upload;
+ * SB_ERR_UNSUPPORTED on an engine with ghost zones or peers configured.  n_shapes == 0 is a valid call: nothing is hit, `tested`
+ * is still reported.  sb_get_info: "cuts" (calls since sb_create), "cut_table_build_us", "cut_kernel_vgprs". */
+#define SB_CUT_NONE 0u
+#define SB_CUT_SEGMENT 1u
+#define SB_CUT_DISC 2u
+#define SB_CUT_MAX_SHAPES 64u
+#define SB_CUT_COUNT_WORDS 4u
+#define SB_CUT_DRY_RUN 1u
+typedef struct sb_cut_shape {
+    uint32_t kind;           /* SB_CUT_NONE / SB_CUT_SEGMENT / SB_CUT_DISC */
+    float x0, y0, x1, y1;    /* segment: P, Q; disc: centre, radius, 0 */
+    uint32_t reserved[3];    /* zero */
+} sb_cut_shape;
+typedef struct sb_cut_options {
+    uint32_t struct_size;    /* = sizeof(sb_cut_options); 0 or a NULL pointer = all defaults */
+    uint32_t flags;          /* SB_CUT_DRY_RUN */
+    uint32_t reserved[6];    /* zero */
+} sb_cut_options;
+sb_status sb_cut_device(sb_engine *e, const sb_cut_options *opts, const void *device_shapes /* [n_shapes] sb_cut_shape */,
+                        uint32_t n_shapes, void *device_hit_u8 /* [max_beams] or NULL */,
+                        void *device_counts_i64 /* [SB_CUT_COUNT_WORDS] int64 or NULL */);
+sb_status sb_cut(sb_engine *e, const sb_cut_options *opts, const sb_cut_shape *shapes, uint32_t n_shapes, uint8_t *hit /* [max_beams] or NULL */,
+                 int64_t *counts /* [SB_CUT_COUNT_WORDS] or NULL */);
+
 /* ---- one summary row of the whole scene, reduced on the device ----
  * What a driver asks of a big scene between steps -- is everything still finite, did it leave the box, how much energy is left,
  * did anything break -- without exporting the state.  The row is SB_SUMMARY_WORDS = 24 floats with the meaning of a row of
@@ -781,6 +845,20 @@ sb_status sb_batch_checkpoint_device(sb_batch *b, const void *device_mask_u8);
 #define SB_BATCH_BEAM_TARGET_LENGTH 1u
 #define SB_BATCH_BEAM_LAST_LENGTH 2u
 sb_status sb_batch_write_beams_device(sb_batch *b, const void *device_beams, uint32_t fields);
+
+/* sb_batch_cut_device -- the planner's "tear it here": sb_cut_device (above) for every scene in ONE launch.  device_shapes is
+ * [n_scenes][k] sb_cut_shape, k <= SB_CUT_MAX_SHAPES: scene i is cut by its own k shapes.  The predicate, "hit", "live" (the
+ * scene's live beam slots) and the four counts are sb_cut_device's, word for word; the counts are int32 here,
+ * device_counts_i32 [n_scenes][SB_CUT_COUNT_WORDS].  device_hit_u8 [n_scenes][max_beams]: 1 / 0 at beam DATA indices, zero-filled
+ * over max_beams for every scene.  flags: SB_CUT_DRY_RUN.  A hit beam's pending break flag is raised: the scene's next frame (or
+ * rollout) removes it in its delete pass, a reset undoes it, a fork copies it, a checkpoint keeps it.  A scene whose k shapes are
+ * all SB_CUT_NONE, or that was never uploaded, is left untouched bit for bit; its counts row and its hit row are still written.
+ * Only ENQUEUES on the batch's stream.  Either output may be NULL.  Errors, before anything touches a device: SB_ERR_INVALID for
+ * a NULL handle, unknown flag bits, k > SB_CUT_MAX_SHAPES, NULL shapes with k > 0, a shape or counts pointer that is not
+ * 4-byte aligned.  sb_batch_get_info: "cut_kernel_vgprs", "cut_kernel_scratch_bytes". */
+sb_status sb_batch_cut_device(sb_batch *b, uint32_t flags, const void *device_shapes /* [n_scenes][k] sb_cut_shape */, uint32_t k,
+                              void *device_hit_u8 /* [n_scenes][max_beams] or NULL */,
+                              void *device_counts_i32 /* [n_scenes][SB_CUT_COUNT_WORDS] int32 or NULL */);
 
 /* ---- per-scene summary rows and multi-frame rollouts on the device ----
  * sb_batch_summary_device -- one row of SB_BATCH_SUMMARY_WORDS floats per scene into device_out_f32[n_scenes][SB_BATCH_SUMMARY_WORDS],

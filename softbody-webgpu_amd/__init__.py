@@ -19,7 +19,8 @@ def __getattr__(name):
         import importlib
         mod = importlib.import_module({"halo": ".halo", "batch": ".batch", "BatchEngine": ".batch"}.get(name, ".engine"), __name__)
         return mod if name in ("engine", "halo", "batch") else getattr(mod, name)
-    if name in ("BODY_SUMMARY_FIELDS", "BODY_SUMMARY_COUNT_FIELDS"):  # the words of Engine.body_summary()'s rows and counts
+    if name in ("BODY_SUMMARY_FIELDS", "BODY_SUMMARY_COUNT_FIELDS",  # the words of Engine.body_summary()'s rows and counts
+                "CUT_NONE", "CUT_SEGMENT", "CUT_DISC", "CUT_COUNT_FIELDS", "cut_shapes"):  # Engine.cut() / BatchEngine.cut()
         from . import engine
         return getattr(engine, name)
     raise AttributeError(name)

@@ -77,6 +77,7 @@ def load_library():
     L.sb_batch_fork_device.argtypes = [vp, vp, u32]
     L.sb_batch_checkpoint_device.argtypes = [vp, vp]
     L.sb_batch_write_beams_device.argtypes = [vp, vp, u32]
+    L.sb_batch_cut_device.argtypes = [vp, u32, vp, u32, vp, vp]
     L.sb_batch_summary_device.argtypes = [vp, vp]
     L.sb_batch_rollout_device.argtypes = [vp, u32, vp, vp]
     L.sb_batch_bodies_device.argtypes = [vp, vp, vp, vp]
@@ -396,6 +397,32 @@ class BatchEngine:
         vp = ctypes.c_void_p
         self._ordered(tensors, lambda: load_library().sb_batch_bodies_device(self._h, vp(ptrs[0]), vp(ptrs[1]), vp(ptrs[2])))
         return (outs[0], outs[2], outs[1]) if sizes is not False else (outs[0], outs[2])
+
+    # ---- cutting beams (sb_batch_cut_device)
+    def cut(self, shapes, dry_run=False, hit=False, counts=None):
+        """Cut every scene with its own k shapes in one launch: `shapes` is [n_scenes, k, 8] (engine.cut_shapes packs rows:
+        {kind, x0, y0, x1, y1, 0, 0, 0}; CUT_SEGMENT: a knife from (x0, y0) to (x1, y1); CUT_DISC: an eraser at (x0, y0) of radius
+        x1; CUT_NONE: ignored), k <= 64 -- an int32 torch tensor on the batch's device (the coordinates as float bits), a float32
+        tensor (the kind as a number: converted on the device), or a numpy array / nested list, which is uploaded.  Every live
+        beam a shape hits (include/softbody.h states the predicate) gets its pending break flag raised: the next frame's delete
+        pass removes it; reset() undoes it, fork() copies it, checkpoint() keeps it.  dry_run: report only.  Returns (hit, counts):
+        hit uint8 [n_scenes, max_beams], 1 at the DATA index of a hit beam, else 0 (hit=True or a tensor / pointer; None
+        otherwise); counts int32 [n_scenes, 4] (CUT_COUNT_FIELDS: tested, hit, flagged, already_flagged; counts=False: None).
+        A scene never uploaded, or whose shapes are all CUT_NONE, is untouched.  Only enqueues."""
+        from .engine import CUT_DRY_RUN, CUT_MAX_SHAPES, CUT_COUNT_FIELDS, device_shapes
+        import torch
+        n = self.n_scenes
+        words = device_shapes(shapes, torch.device("cuda", self.device), 3)
+        if words.shape[0] != n or words.shape[1] > CUT_MAX_SHAPES:
+            raise ValueError("cut: shapes must be [n_scenes = %d, k <= %d, 8], not %s" % (n, CUT_MAX_SHAPES, tuple(words.shape)))
+        k = int(words.shape[1])
+        given = [None if isinstance(x, bool) else x for x in (hit, counts)]   # (True: a new tensor)
+        outs, ptrs, tensors = self._bind("cut", [("hit", given[0], hit is not False, (n, self.max_beams), "uint8"),
+                                                 ("counts", given[1], counts is not False, (n, len(CUT_COUNT_FIELDS)), "int32")])
+        vp = ctypes.c_void_p
+        self._ordered(True, lambda: load_library().sb_batch_cut_device(self._h, CUT_DRY_RUN if dry_run else 0, vp(words.data_ptr() if k else None),
+                                                                       k, vp(ptrs[0]), vp(ptrs[1])))
+        return outs[0], outs[1]
 
     # ---- statistics per body (sb_batch_body_summary_device; DESIGN.md 5.16)
     def body_summary(self, labels=None, rows=8, out=None, rank=False):

@@ -150,7 +150,7 @@ struct sb_batch {
     uint64_t frames_done = 0, substeps_done = 0;
     int scenes_per_cu = 0, vgprs = 0, scratch = 0;
     SbBatchRender *render = nullptr; // what the renderer keeps between calls (made at the first render)
-    SbbKernelRes render_res, summary_res, bodies_res, contacts_res, body_summary_res; // of k_batch_render, k_batch_summary, ...
+    SbbKernelRes render_res, summary_res, bodies_res, contacts_res, body_summary_res, cut_res; // of k_batch_render, k_batch_summary, ...
     bool body_summary_lds_allowed = false; // k_batch_body_summary may be launched with more than 64 KiB of LDS (asked for at the first such launch)
 };
 
@@ -203,3 +203,5 @@ bool sbb_bodies_info(sb_batch *b, const char *key, uint64_t *value);    // sb_ba
 bool sbb_contacts_info(sb_batch *b, const char *key, uint64_t *value);  // sb_batch_get_info's contacts keys; false: not one of them
 // sb_batch_body_summary.hip
 bool sbb_body_summary_info(sb_batch *b, const char *key, uint64_t *value); // sb_batch_get_info's body summary keys; false: not one of them
+// sb_batch_cut.hip
+bool sbb_cut_info(sb_batch *b, const char *key, uint64_t *value);       // sb_batch_get_info's cut keys; false: not one of them

@@ -62,6 +62,7 @@ static struct {
     sb_status (*sync)(sb_engine *);
     sb_status (*checkpoint_device)(sb_engine *);
     sb_status (*restore_device)(sb_engine *);
+    sb_status (*cut)(sb_engine *, const sb_cut_options *, const sb_cut_shape *, uint32_t, uint8_t *, int64_t *);
     sb_status (*step_timed)(sb_engine *, uint32_t, float *);
     sb_status (*mark)(sb_engine *, uint32_t);
     sb_status (*mark_elapsed)(sb_engine *, uint32_t, uint32_t, float *);
@@ -169,6 +170,7 @@ static napi_value js_load(napi_env env, napi_callback_info info)
     SYM(sync, "sb_sync");
     SYM(checkpoint_device, "sb_checkpoint_device");
     SYM(restore_device, "sb_restore_device");
+    SYM(cut, "sb_cut");
     SYM(step_timed, "sb_step_timed");
     SYM(mark, "sb_mark");
     SYM(mark_elapsed, "sb_mark_elapsed");
@@ -1171,6 +1173,56 @@ static napi_value js_bodies(napi_env env, napi_callback_info info)
     return obj;
 }
 
+/* cut(handle, maxBeams, shapes, dryRun, wantHit) -> {counts: Float64Array(4), hit?: Uint8Array(maxBeams)}: every live beam that one
+ * of the shapes hits gets its pending break flag raised on the GPU by sb_cut (which waits for the stream); counts: tested, hit,
+ * flagged, already flagged; hit: 1 / 0 per beam data index (0 where no beam lives).  shapes: a Uint32Array of 8 words per shape,
+ * sb_cut_shape's layout (the kind as an integer, the coordinates as float32 bits); maxBeams: the capacity the engine was created with. */
+static napi_value js_cut(napi_env env, napi_callback_info info)
+{
+    if (!need_lib(env)) return NULL;
+    size_t argc = 5;
+    napi_value argv[5];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    sb_engine *e = argc >= 1 ? get_engine(env, argv[0]) : NULL;
+    if (!e) return NULL;
+    double cap = -1.0;
+    if (argc >= 2) (void)napi_get_value_double(env, argv[1], &cap);
+    if (!(cap >= 0.0 && cap <= 2147483648.0) || cap != (double)(uint32_t)cap) {
+        napi_throw_range_error(env, NULL, "cut: maxBeams must be the engine's beam capacity");
+        return NULL;
+    }
+    const void *words = NULL;
+    uint32_t n_words = 0;
+    if (argc < 3 || !get_typed(env, argv[2], napi_uint32_array, &words, &n_words) || n_words % 8u != 0u) {
+        napi_throw_type_error(env, NULL, "cut: shapes must be a Uint32Array of 8 words per shape");
+        return NULL;
+    }
+    bool dry = false, want_hit = false;
+    if (argc >= 4) (void)napi_get_value_bool(env, argv[3], &dry);
+    if (argc >= 5) (void)napi_get_value_bool(env, argv[4], &want_hit);
+    sb_cut_options o;
+    memset(&o, 0, sizeof o);
+    o.struct_size = (uint32_t)sizeof o;
+    o.flags = dry ? SB_CUT_DRY_RUN : 0u;
+    void *hit = NULL, *cnt = NULL;
+    napi_value vhit = NULL, vcnt = make_typed(env, napi_float64_array, SB_CUT_COUNT_WORDS, 8, &cnt);
+    if (!vcnt) return NULL;
+    if (want_hit) {
+        vhit = make_typed(env, napi_uint8_array, (size_t)cap, 1, &hit);
+        if (!vhit) return NULL;
+        if (cap > 0.0) memset(hit, 0, (size_t)cap);
+    }
+    int64_t counts[SB_CUT_COUNT_WORDS];
+    sb_status st = sb.cut(e, &o, (const sb_cut_shape *)words, n_words / 8u, cap > 0.0 ? (uint8_t *)hit : NULL, counts);
+    if (st != SB_OK) return throw_status(env, e, st, "sb_cut");
+    for (uint32_t i = 0; i < SB_CUT_COUNT_WORDS; i++) ((double *)cnt)[i] = (double)counts[i];
+    napi_value obj;
+    CHECK_NAPI(napi_create_object(env, &obj));
+    CHECK_NAPI(napi_set_named_property(env, obj, "counts", vcnt));
+    if (vhit) CHECK_NAPI(napi_set_named_property(env, obj, "hit", vhit));
+    return obj;
+}
+
 /* contacts(handle, maxParticles, maxPairs) -> {touch: Int32Array(4 * maxParticles), counts: [4 numbers], pairs: Int32Array(2 *
  * maxPairs)}: per particle data index {partners, -1 (no labels), wall bits, smallest partner}, the four count words (touching
  * pairs, -1, particles on a wall, particles touching another) and the first maxPairs pairs {i, j}, i < j, ascending, {-1, -1} behind
@@ -1288,7 +1340,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"partitionRankCounts", js_partition_rank_counts}, {"partitionRankScene", js_partition_rank_scene},
         {"partitionRankIds", js_partition_rank_ids}, {"partitionPeer", js_partition_peer}, {"render", js_render},
         {"summary", js_summary}, {"bodies", js_bodies}, {"contacts", js_contacts}, {"bodySummary", js_body_summary},
-        {"checkpoint", js_checkpoint}, {"restore", js_restore},
+        {"checkpoint", js_checkpoint}, {"restore", js_restore}, {"cut", js_cut},
         {"partitionRankGuard", js_partition_rank_guard}, {"haloGuard", js_halo_guard}, {"haloGuardStatus", js_halo_guard_status},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

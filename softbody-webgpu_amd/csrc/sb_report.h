@@ -1,6 +1,7 @@
-// sb_report.h -- what the engine's state calls (sb_state_io.hip) and its four whole-scene reports (sb_summary.hip, sb_bodies.hip,
-// sb_contacts.hip, sb_body_summary.hip) share: the owner of their device buffers, the preflight of a call, the scene tables of the
-// latest upload, the exclusive scan and the wave's run counter.  What only one report uses stays in its file.
+// sb_report.h -- what the engine's state calls (sb_state_io.hip), its four whole-scene reports (sb_summary.hip, sb_bodies.hip,
+// sb_contacts.hip, sb_body_summary.hip) and the cut (sb_cut.hip) share: the owner of their device buffers, the preflight of a
+// call, the scene tables of the latest upload, the exclusive scan and the wave's run counter.  What only one
+// report uses stays in its file.
 #pragma once
 #include <vector>
 
@@ -24,6 +25,7 @@ enum SbReportBuf {
     SBD_B_PARENT, SBD_B_SIZES, SBD_B_ACC,                                          // sb_bodies.hip
     SBC_B_CELLS, SBC_B_BSUM, SBC_B_SORTED, SBC_B_ABOVE, SBC_B_PLACE, SBC_B_ACC, SBC_B_LABELS, SBC_B_TOUCH, SBC_B_PAIRS, // sb_contacts.hip
     SBY_B_SCRATCH, SBY_B_LABELS, SBY_B_OUT,                                        // sb_body_summary.hip
+    SBX_B_ROW, SBX_B_MARK, SBX_B_ACC, SBX_B_SHAPES, SBX_B_HIT,                     // sb_cut.hip
     SBQ_NBUF
 };
 
@@ -53,8 +55,12 @@ struct SbStateIoState {
     uint32_t ck_cur = 0, ck_bcur = 0, ck_delete_gen = 0;
     uint64_t ck_substeps_done = 0;
     uint64_t checkpoints = 0, restores = 0;   // calls since sb_create
+    // sb_cut_device: per caller slot the data index of its beam record (SBX_B_ROW), beside the shared scene tables
+    bool cut_valid = false;
+    double cut_row_ms = 0.0, cut_build_ms = 0.0;
+    uint64_t cuts = 0;                        // calls since sb_create
 
-    void invalidate() { part_valid = beam_valid = copy_valid = valid = bleaf_valid = imp_valid = false; } // every table of the scene: the one place
+    void invalidate() { part_valid = beam_valid = copy_valid = valid = bleaf_valid = imp_valid = cut_valid = false; } // every table of the scene: the one place
 };
 
 enum { SBQ_PARTICLES = 1u, SBQ_BEAMS = 2u, SBQ_COPIES = 4u }; // the parts of the shared scene tables; SBQ_COPIES: part 2's fourth plane
@@ -63,6 +69,7 @@ inline const char *sbq_options_name(const sb_summary_options *) { return "sb_sum
 inline const char *sbq_options_name(const sb_bodies_options *) { return "sb_bodies_options"; }
 inline const char *sbq_options_name(const sb_contacts_options *) { return "sb_contacts_options"; }
 inline const char *sbq_options_name(const sb_body_summary_options *) { return "sb_body_summary_options"; }
+inline const char *sbq_options_name(const sb_cut_options *) { return "sb_cut_options"; }
 
 sb_status sbq_ready(sb_engine *e, const char *what, const char *why); // loaded, no ranks (`why`: the call's parenthesis); the device; e->sio
 

@@ -78,6 +78,71 @@ BODY_SUMMARY_COUNT_FIELDS = ("particles", "live_beams", "label", "pending_breaks
                              "finite_particles", "reserved_7")
 
 
+class SbCutOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 6)]
+
+
+CUT_NONE, CUT_SEGMENT, CUT_DISC = 0, 1, 2     # SB_CUT_*: the kind word of a shape
+CUT_MAX_SHAPES = 64                           # SB_CUT_MAX_SHAPES
+CUT_SHAPE_WORDS = 8                           # a shape: {kind, x0, y0, x1, y1, 0, 0, 0}
+CUT_DRY_RUN = 1                               # SB_CUT_DRY_RUN
+CUT_COUNT_FIELDS = ("tested", "hit", "flagged", "already_flagged")   # the counts of cut(), in order (SB_CUT_COUNT_WORDS of them)
+
+
+def cut_shapes(segments=(), discs=()):
+    """Rows of shapes for Engine.cut() / BatchEngine.cut(): segments (x0, y0, x1, y1) -- a knife from (x0, y0) to (x1, y1) --
+    then discs (x, y, r) -- an eraser at (x, y) of radius r -- as a uint32 numpy array [n, 8] in sb_cut_shape's layout (the kind
+    as an integer word, the coordinates as float32 bits)."""
+    seg = np.asarray(segments, dtype=np.float32).reshape(-1, 4)
+    dsc = np.asarray(discs, dtype=np.float32).reshape(-1, 3)
+    rows = np.zeros((len(seg) + len(dsc), CUT_SHAPE_WORDS), dtype=np.uint32)
+    rows[:len(seg), 0] = CUT_SEGMENT
+    rows[:len(seg), 1:5] = seg.view(np.uint32)
+    rows[len(seg):, 0] = CUT_DISC
+    rows[len(seg):, 1:4] = dsc.view(np.uint32)
+    return rows
+
+
+def host_shapes(shapes, ndim=2):
+    """`shapes` as a uint32 numpy array [..., 8] in sb_cut_shape's layout.  An int32 / uint32 array is taken as the words
+    themselves (cut_shapes() makes one); any other array or a nested list holds numbers (the kind too), in rows of 5
+    (kind, x0, y0, x1, y1) or 8."""
+    a = np.asarray(shapes)
+    if a.size == 0:
+        a = a.reshape((0,) * (ndim - 1) + (CUT_SHAPE_WORDS,)) if a.ndim < ndim else a
+    if a.ndim != ndim or a.shape[-1] not in (5, CUT_SHAPE_WORDS):
+        raise ValueError("cut: shapes must be %d-dimensional with rows of 5 or 8 words, not %s" % (ndim, a.shape))
+    if a.dtype in (np.dtype(np.int32), np.dtype(np.uint32)):
+        w = np.ascontiguousarray(a).view(np.uint32)
+    else:
+        f = a.astype(np.float32)
+        kind = f[..., 0]
+        if not np.all(np.isin(kind, (CUT_NONE, CUT_SEGMENT, CUT_DISC))):
+            raise ValueError("cut: a shape's kind must be CUT_NONE, CUT_SEGMENT or CUT_DISC")
+        w = np.ascontiguousarray(f).view(np.uint32).copy()
+        w[..., 0] = kind.astype(np.uint32)
+    out = np.zeros(w.shape[:-1] + (CUT_SHAPE_WORDS,), dtype=np.uint32)
+    out[..., :w.shape[-1]] = w
+    return out
+
+
+def device_shapes(shapes, dev, ndim=2):
+    """`shapes` as a contiguous int32 torch tensor [..., 8] on `dev` in sb_cut_shape's layout: an int32 tensor as it is, a float32
+    tensor with its kind column converted on the device, anything else through host_shapes()."""
+    import torch
+    if isinstance(shapes, torch.Tensor):
+        if shapes.dim() != ndim or shapes.shape[-1] != CUT_SHAPE_WORDS or shapes.dtype not in (torch.int32, torch.float32):
+            raise ValueError("cut: a tensor of shapes must be float32 / int32 with %d dimensions and rows of 8 words" % ndim)
+        if shapes.device != dev and not (shapes.device.type == dev.type and shapes.device.index in (None, dev.index)):
+            raise ValueError("cut: the shapes are on %s, not on %s" % (shapes.device, dev))
+        if shapes.dtype == torch.int32:
+            return shapes.contiguous()
+        words = shapes.contiguous().view(torch.int32).clone()
+        words[..., 0] = shapes[..., 0].to(torch.int32)
+        return words
+    return torch.from_numpy(host_shapes(shapes, ndim).view(np.int32)).to(dev)
+
+
 def __getattr__(name):
     if name in ("SUMMARY_FIELDS", "BODY_FIELDS", "BODY_SUMMARY_FIELDS", "CONTACT_TOUCH_FIELDS", "CONTACT_COUNT_FIELDS", "WALL_LEFT", "WALL_RIGHT", "WALL_LOW",
                 "WALL_HIGH"):  # the batch's words: its names are not copied (batch.py imports this module)
@@ -201,6 +266,8 @@ def load_library():
     L.sb_write_beams_device.argtypes = [vp, vp, u32]
     L.sb_checkpoint_device.argtypes = [vp]
     L.sb_restore_device.argtypes = [vp]
+    L.sb_cut_device.argtypes = [vp, ctypes.POINTER(SbCutOptions), vp, u32, vp, vp]
+    L.sb_cut.argtypes = [vp, ctypes.POINTER(SbCutOptions), vp, u32, vp, vp]
     L.sb_summary_device.argtypes = [vp, ctypes.POINTER(SbSummaryOptions), vp, vp]
     L.sb_summary.argtypes = [vp, ctypes.POINTER(SbSummaryOptions), vp, vp]
     L.sb_bodies_device.argtypes = [vp, ctypes.POINTER(SbBodiesOptions), vp, vp, vp]
@@ -545,6 +612,57 @@ class Engine:
         and after checkpoint() -- also mid-frame and across delete passes.  Physics constants and user input stay as they are now.
         Only enqueues; EngineError (SB_ERR_STATE) without a checkpoint."""
         self._check(load_library().sb_restore_device(self._h))
+
+    # ---- cutting beams on the device (sb_cut_device / sb_cut; DESIGN.md 5.23)
+
+    @staticmethod
+    def _cut_options(dry_run):
+        o = SbCutOptions()
+        o.struct_size = ctypes.sizeof(SbCutOptions)
+        o.flags = CUT_DRY_RUN if dry_run else 0
+        return o
+
+    def cut(self, shapes, dry_run=False, hit=False, counts=True):
+        """Cut the scene: every live beam that a shape hits (include/softbody.h states the predicate, on the positions at this
+        point of the stream) gets its pending break flag raised, as if it had broken in the last substep -- it still acts until
+        the next delete pass (frame()'s own, or delete_pass()), which removes it.  shapes: [n, 8] rows {kind, x0, y0, x1, y1, 0,
+        0, 0}, n <= 64 (CUT_SEGMENT: a knife from (x0, y0) to (x1, y1); CUT_DISC: an eraser at (x0, y0) of radius x1; CUT_NONE:
+        ignored) -- an int32 torch tensor on the engine's device (the coordinates as float bits; cut_shapes() packs such rows), a
+        float32 tensor (the kind as a number: converted on the device), or a numpy array / list of (kind, x0, y0, x1, y1), which
+        goes through sb_cut's checks on the host (that path waits for the stream).  dry_run: report, raise no flag.  Returns
+        (hit, counts): hit uint8 [max_beams], 1 / 0 at the DATA index of every beam of the latest upload, indices of no beam not
+        written (hit=True: a new zeroed tensor; a tensor / pointer: written into; False: None); counts int64 [4]
+        (CUT_COUNT_FIELDS: tested, hit, flagged, already_flagged; False: None).  Tensors with device shapes, numpy arrays with
+        host shapes.  Particles, beam floats, the spatial hash and the schedule are untouched."""
+        o = self._cut_options(dry_run)
+        vp = ctypes.c_void_p
+        try:
+            import torch
+            on_device = isinstance(shapes, torch.Tensor)
+        except ImportError:
+            on_device = False
+        if not on_device:
+            rows = host_shapes(shapes)
+            h = None
+            if hit is not False:
+                h = np.zeros(self.max_beams, dtype=np.uint8) if hit is True else hit
+                if not (isinstance(h, np.ndarray) and h.dtype == np.uint8 and h.flags.c_contiguous and h.size >= self.max_beams):
+                    raise ValueError("cut: with host shapes, hit is True or a contiguous uint8 numpy array of max_beams bytes")
+            c = np.zeros(len(CUT_COUNT_FIELDS), dtype=np.int64) if counts is not False else None
+            self._check(load_library().sb_cut(self._h, ctypes.byref(o), _ptr(rows) if len(rows) else None, len(rows), _ptr(h), _ptr(c)))
+            return h, c
+        dev = torch.device("cuda", self.device)
+        words = device_shapes(shapes, dev)
+        n = int(words.shape[0])
+        if hit is True:
+            hit = torch.zeros(self.max_beams, dtype=torch.uint8, device=dev)
+        if counts is True:
+            counts = torch.empty(len(CUT_COUNT_FIELDS), dtype=torch.int64, device=dev)
+        hptr = self._device_buffer("cut: hit", hit, "uint8", self.max_beams)[0] if hit is not False else None
+        cptr = self._device_buffer("cut: counts", counts, "int64", len(CUT_COUNT_FIELDS) * 8)[0] if counts is not False else None
+        self._ordered(True, lambda: load_library().sb_cut_device(self._h, ctypes.byref(o), vp(words.data_ptr() if n else None), n,
+                                                                 vp(hptr), vp(cptr)))
+        return (None if hit is False else hit), (None if counts is False else counts)
 
     # ---- one summary row of the whole scene (sb_summary_device / sb_summary; DESIGN.md 5.18)
 

@@ -79,6 +79,8 @@ class WGPUSoftbodyEngine {
     async contacts(opts) { return this.worker.contacts(opts); }
     /** one row of 24 statistics per body of the whole scene, ranked by size, exact counts and ranks (engineWorker.js bodySummary) */
     async bodySummary(opts) { return this.worker.bodySummary(opts); }
+    /** cut the beams that knife strokes cross and eraser discs cover, on the GPU: counts and optional hit bytes (engineWorker.js cut) */
+    async cut(opts) { return this.worker.cut(opts); }
     /** keep the run state in device memory (engineWorker.js checkpoint) */
     async checkpoint() { return this.worker.checkpoint(); }
     /** back to the checkpoint; rejects with the engine's message when there is none (engineWorker.js restore) */

@@ -14,6 +14,24 @@ const { BufferMapper, Vector2D } = require('./engineMapping');
 const { AsyncLock } = require('./lock');
 const { native, COLLIDE, PATH } = require('./native');
 
+/** segments [[x0, y0, x1, y1], ...] then discs [[x, y, r], ...] as sb_cut_shape words: 8 per shape, kind 1 / 2, float32 bits */
+function packCutShapes(segments, discs) {
+    const n = segments.length + discs.length;
+    const words = new Uint32Array(8 * n), floats = new Float32Array(words.buffer);
+    segments.forEach((s, i) => {
+        if (s.length !== 4) throw new RangeError('cut: a segment is [x0, y0, x1, y1]');
+        words[8 * i] = 1;
+        floats.set(s, 8 * i + 1);
+    });
+    discs.forEach((d, j) => {
+        if (d.length !== 3) throw new RangeError('cut: a disc is [x, y, r]');
+        const i = segments.length + j;
+        words[8 * i] = 2;
+        floats.set(d, 8 * i + 1);
+    });
+    return words;
+}
+
 class WGPUSoftbodyEngineWorker {
     static create(canvas, opts, post) {
         WGPUSoftbodyEngineWorker.sInstance = new WGPUSoftbodyEngineWorker(canvas, opts, post);
@@ -174,6 +192,24 @@ class WGPUSoftbodyEngineWorker {
             if (!this.uploaded) throw new Error('bodySummary before writeBuffers');
             const cap = this.bufferMapper.maxParticles;
             return this.addon.bodySummary(this.handle, cap, (opts && opts.rows) || Math.min(8, cap));
+        });
+    }
+
+    /**
+     * Cut the scene on the GPU (sb_cut): every live beam that a knife stroke crosses or an eraser disc covers -- the predicate of
+     * include/softbody.h on the positions as they are now -- gets its pending break flag raised, as if it had broken in the last
+     * substep; the next frame's delete pass removes it.  No state travels to the host.
+     * @param opts {segments: [[x0, y0, x1, y1], ...], discs: [[x, y, r], ...] (at most 64 shapes together), dryRun: report only,
+     *        hit: also return the hit bytes}
+     * @returns {counts: Float64Array(4) [tested, hit, flagged, already flagged], hit?: Uint8Array(maxBeams)}; hit[d] is 1 where
+     *          the beam at data index d was hit
+     */
+    async cut(opts) {
+        const o = opts || {};
+        const shapes = packCutShapes(o.segments || [], o.discs || []);
+        return this.lock.run(() => {
+            if (!this.uploaded) throw new Error('cut before writeBuffers');
+            return this.addon.cut(this.handle, this.bufferMapper.maxBeams, shapes, !!o.dryRun, !!o.hit);
         });
     }
 

@@ -183,6 +183,8 @@ export class WGPUSoftbodyEngine {
     contacts(opts?: ContactsOptions): Promise<SceneContacts>;
     /** statistics per body of the whole scene (sb_body_summary), the same bits on every run, found on the GPU */
     bodySummary(opts?: BodySummaryOptions): Promise<SceneBodySummary>;
+    /** cut the scene on the GPU (sb_cut): the beams hit get their pending break flag raised and go with the next delete pass */
+    cut(opts?: CutOptions): Promise<SceneCut>;
     /** keep a copy of everything a run mutates in device memory (sb_checkpoint_device): one per engine, dropped by every upload */
     checkpoint(): Promise<void>;
     /** back to the checkpoint (sb_restore_device): later frames and read-backs give the bits they gave, or would have given, after
@@ -211,6 +213,12 @@ export interface BodySummaryOptions { rows?: number }
  *  non-finite particles, non-finite beams, finite particles, 0); rank: per particle data index the rank of its body, -1 where none lives */
 export interface SceneBodySummary { rows: Float32Array, counts: Float64Array, rank: Int32Array }
 export interface SceneContacts { touch: Int32Array, counts: [number, number, number, number], pairs: Int32Array }
+/** segments: knife strokes [x0, y0, x1, y1]; discs: erasers [x, y, r]; at most 64 shapes together; dryRun: report, raise no flag;
+ *  hit: also return the hit bytes */
+export interface CutOptions { segments?: number[][], discs?: number[][], dryRun?: boolean, hit?: boolean }
+/** counts: live beams tested, beams hit, flags this call raised, hit beams whose flag was pending already; hit: 1 / 0 per beam data
+ *  index (include/softbody.h, sb_cut, states the predicate) */
+export interface SceneCut { counts: Float64Array, hit?: Uint8Array }
 
 export class WGPUSoftbodyEngineWorker {
     static create(canvas: unknown | null, opts?: NativeEngineOptions, post?: (m: { type: number, data?: unknown }) => void): WGPUSoftbodyEngineWorker;
@@ -235,6 +243,8 @@ export class WGPUSoftbodyEngineWorker {
     contacts(opts?: ContactsOptions): Promise<SceneContacts>;
     /** sb_body_summary: one row of 24 statistics per body, ranked by size, with exact counts and ranks, without a read-back of the scene */
     bodySummary(opts?: BodySummaryOptions): Promise<SceneBodySummary>;
+    /** sb_cut: knife strokes and eraser discs against every live beam on the GPU; the beams hit go with the next delete pass */
+    cut(opts?: CutOptions): Promise<SceneCut>;
     /** sb_checkpoint_device: the run state kept in device memory of the engine's; no state travels to the host */
     checkpoint(): Promise<void>;
     /** sb_restore_device: the run state put back from the checkpoint; rejects with the engine's message when there is none */
