@@ -693,8 +693,7 @@ sb_status sb_contacts(sb_engine *e, const sb_contacts_options *opts, const int32
  * sb_summary's ordered integer keys from the first comparison on: -0.0 sorts below +0.0, and which zero comes back does not
  * depend on the schedule.  So a row is the same bits on every run.
  * Consequences: for a scene that is ONE body, row 0's words 0, 1, 3 .. 18 equal sb_summary_device's words by their bits; for a
- * scene that also fits an sb_batch the rows are sb_batch_body_summary_device's (counts and sums by their bits, extremes by value:
- * the batch may return either zero).
+ * scene that also fits an sb_batch the rows are sb_batch_body_summary_device's, every word by its bits.
  * sb_body_summary_device only ENQUEUES on the engine's stream and reads / writes device memory, which must stay valid until that
  * work has run; nothing is read back to decide anything and no workgroup waits for another (a stable radix sort of the members
  * by label and a segmented tree in global memory, one launch per stage and level; the number of groups is read on the device).
@@ -882,7 +881,7 @@ sb_status sb_batch_cut_device(sb_batch *b, uint32_t flags, const void *device_sh
  * or >= max_beams (beam sums); the reduction is the stride-halving tree, for h = W/2, W/4, .. 1: s[i] += s[i + h] (i < h).  The
  * energy leaf is 0.5 * ((double)vx * vx + (double)vy * vy), the candidate of word 15 the same without the 0.5; a mean is
  * (float)(sum / (double)count); energy and word 15 are rounded to float once, at the end (beyond float's range: +inf).  Extremes
- * are plain comparisons (-0 and +0 compare equal: either may be returned).
+ * are taken in the order of the floats' keys, in which -0.0 lies below +0.0: over both zeros a minimum is -0.0, a maximum +0.0.
  * Errors: SB_ERR_INVALID for a NULL handle, a NULL output, a pointer that is not 4-byte aligned -- before anything touches a device.
  *
  * sb_batch_rollout_device -- n_frames times, in this order: slice t of device_inputs[n_frames][n_scenes][32 B] applied exactly as
@@ -954,7 +953,7 @@ sb_status sb_batch_bodies_device(sb_batch *b,
  * 0.5; the angular-momentum leaf is (double)x * vy - (double)y * vx (both products are exact in double: one rounding).  A mean is
  * (float)(sum / (double)finite_count); words 14 and 19 are rounded to float once.  ONE addition to the pin: a sum that is zero is
  * written as +0.0.  The masked tree gives that in every case but one -- a group that fills all W leaves with -0.0, where the tree
- * gives -0.0 and this call still writes +0.0.  Extremes are plain comparisons (-0 and +0 compare equal: either may be returned).
+ * gives -0.0 and this call still writes +0.0.  Extremes as in sb_batch_summary_device's row (-0.0 below +0.0).
  * Consequence: for a scene that is ONE body, row 0's words 0, 1, 3 .. 18 equal sb_batch_summary_device's words by their bits.
  * Errors: SB_ERR_INVALID for a NULL handle, NULL labels, rows and rank both NULL, max_rows of 0 or above max_particles (so also
  * rows non-NULL with max_rows == 0), a pointer that is not 4-byte aligned -- before anything touches a device. */

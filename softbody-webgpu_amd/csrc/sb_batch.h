@@ -2,7 +2,7 @@
 // (sb_batch.hip: upload, stepping, state I/O; sb_batch_render.hip: pictures; sb_batch_summary.hip: per-scene statistics, rollouts;
 // sb_batch_bodies.hip: connected bodies; sb_batch_contacts.hip: particle and wall contacts; sb_batch_body_summary.hip: statistics per
 // body), and what the four report kernels have in common: the scene header each of them opens with (sbb_scene), the float <->
-// ordered-key codec of their extremes (sbb_fkey) and the width of the pinned summation tree (sbb_pow2_at_least); on the host the
+// ordered-key codec of their extremes and the width of the pinned summation tree (sb_summary_math.h), the contact test (sb_touch); on the host the
 // cache behind the *_kernel_vgprs / *_kernel_scratch_bytes info keys (sbb_kernel_res) and the alignment test of the entry points
 // (sbb_misaligned4).  All of it is inline; what only one kernel uses stays in that kernel's file.
 #pragma once
@@ -14,6 +14,7 @@
 #include "../../include/softbody.h"
 #include "sb_error.h"
 #include "sb_physics.h"
+#include "sb_summary_math.h" // sbb_finite, sbb_fkey / sbb_unkey, SBB_QNAN, sbb_pow2_at_least: the codec of the report rows
 
 // ---------------------------------------------------------------- device memory of a batch
 // Per scene: 32 metadata words (the 112 bytes of the reference's metadata buffer, then SB_BM_B0 / SB_BM_LOADED), a CONSTANT blob
@@ -80,6 +81,18 @@ static inline uint32_t sb_batch_cell_geometry(float bounds, float radius, uint32
     return g;
 }
 
+// The contact test of the step's collision loop on two positions (both contacts reports).  The root is only taken where d2 <= thr =
+// (2r)^2 * 1.001 (beyond it sqrt(d2) > 2r * 1.0004: no contact, and d2 > 0); thr is +inf where that product is no ordinary number, a
+// NaN d2 fails `d2 > thr` and then every comparison: a NaN or infinite distance is no contact.
+SB_DEV bool sb_touch(float2 me, float2 other, float thr, float two_r)
+{
+    const float dx = other.x - me.x, dy = other.y - me.y;
+    const float d2 = dx * dx + dy * dy;
+    if (d2 > thr) return false;
+    const float dist = sb_sqrt(d2); // sb_length(dx, dy)
+    return dist == 0.0f || dist < two_r;
+}
+
 SB_DEV uint32_t sbb_uniform(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
 SB_DEV float sbb_uniform(float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); }
 
@@ -103,24 +116,6 @@ SB_DEV SbbScene sbb_scene(const SbBatchView &V, uint32_t scene)
     s.Bc = s.loaded ? min(Bc, V.maxB) : 0u;
     s.cst = V.cst + (size_t)scene * V.cst_bytes, s.st = V.st + (size_t)scene * V.st_bytes;
     return s;
-}
-
-#define SBB_QNAN 0x7FC00000u // the word of a statistic over an empty set
-SB_DEV bool sbb_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-// finite floats as unsigned keys of the same order (-0 below +0: either may come back from an extreme)
-SB_DEV uint32_t sbb_fkey(float x)
-{
-    const uint32_t b = __float_as_uint(x);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-SB_DEV float sbb_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-// the leaves of the pinned summation tree over a capacity: the smallest power of two >= n
-static inline uint32_t sbb_pow2_at_least(uint32_t n)
-{
-    uint32_t w = 1u;
-    while (w < n) w <<= 1;
-    return w;
 }
 
 // ---------------------------------------------------------------- host

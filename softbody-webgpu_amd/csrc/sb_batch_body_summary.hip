@@ -4,7 +4,7 @@
 // One workgroup per scene reads the caller's labels, the scene's metadata words, its constant blob and its state blob; nothing is
 // written but the rows and the ranks.
 //
-// The sums are PINNED to sb_batch_summary_device's tree: the sum of a group is what that tree gives for a scene holding only the
+// The sums are PINNED to sb_batch_summary_device's tree (sb_summary_math.h): the sum of a group is what that tree gives for a scene holding only the
 // group's finite particles -- double precision, leaf i = the value at DATA index i if particle i is finite and in the group, else
 // +0.0, i = 0 .. W-1, reduced by  for h = W/2 .. 1: s[i] += s[i + h].  That tree is never evaluated per group.  Every partial sum
 // is finite (at most 1024 finite floats, in double), so the +0.0 of an absent leaf changes no partial sum but a zero's sign, and
@@ -16,7 +16,7 @@
 //            differs in key >> l; a head whose key has bit l set and whose predecessor shares key >> (l + 1) adds its six partial
 //            sums onto the head of the left sibling block (the lower bound of ((key >> l) - 1) << l).  Nobody else touches either
 //            operand at that level; after the last level a group's sums sit at the first sorted position of its label.
-// All groups are reduced at once.  A sum that is zero is written as +0.0 (sbq_canon): the masked tree gives that in every case but
+// All groups are reduced at once.  A sum that is zero is written as +0.0 (sbu_canon): the masked tree gives that in every case but
 // a group that fills all W leaves with -0.0.
 // Everything else in a row (counts, extremes) is order-free and goes through LDS atomics on integer keys; the ranking sorts the
 // keys  particles << 10 | (1023 - label)  with the same network.
@@ -48,8 +48,6 @@ static inline uint32_t sbq_lds_bytes(uint32_t maxP)
     const uint32_t W = sbb_pow2_at_least(maxP);
     return W * (SBQ_NSUM * 8u + 2u * 4u) + maxP * (2u + SBQ_NSTAT) * 4u;
 }
-
-SB_DEV double sbq_canon(double sum) { return sum + 0.0; } // -0.0 -> +0.0, every other value as it is
 
 // ascending bitonic sort of a[0 .. W-1] (W a power of two) by the whole workgroup; ends in a barrier
 SB_DEV void sbq_sort(uint32_t *a, uint32_t W, uint32_t tid)
@@ -95,7 +93,7 @@ __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V,
         s_grp[d] = SBQ_NONE;
 #pragma unroll
         for (uint32_t k = 0; k < SBQ_NSTAT; k++)
-            s_stat[k * maxP + d] = (k == SBQ_MINX || k == SBQ_MINY || k == SBQ_MIN_STRESS) ? 0xFFFFFFFFu : 0u;
+            s_stat[k * maxP + d] = (k == SBQ_MINX || k == SBQ_MINY || k == SBQ_MIN_STRESS) ? SBB_KEY_MOST : 0u;
     }
     __syncthreads();
 
@@ -106,19 +104,19 @@ __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V,
         const uint32_t g = (uint32_t)lrow[d]; // (a negative label is a large unsigned one)
         if (g >= maxP) continue;
         s_grp[d] = g;
-        const float2 p = g_part[3u * d], v = g_part[3u * d + 1u], a = g_part[3u * d + 2u];
-        if (!(sbb_finite(p.x) && sbb_finite(p.y) && sbb_finite(v.x) && sbb_finite(v.y) && sbb_finite(a.x) && sbb_finite(a.y))) {
+        const float2 p = g_part[3u * d], v = g_part[3u * d + 1u];
+        if (!sbu_particle_finite(p, v, g_part[3u * d + 2u])) {
             atomicAdd(&s_stat[SBQ_NP * maxP + g], 0x10001u);
             continue;
         }
+        const SbuParticleKeys k = sbu_particle_keys(p, v); // (the leaves are taken once the members are sorted)
         atomicAdd(&s_stat[SBQ_NP * maxP + g], 1u);
-        atomicMin(&s_stat[SBQ_MINX * maxP + g], sbb_fkey(p.x));
-        atomicMin(&s_stat[SBQ_MINY * maxP + g], sbb_fkey(p.y));
-        atomicMax(&s_stat[SBQ_MAXX * maxP + g], sbb_fkey(p.x));
-        atomicMax(&s_stat[SBQ_MAXY * maxP + g], sbb_fkey(p.y));
+        atomicMin(&s_stat[SBQ_MINX * maxP + g], k.x);
+        atomicMin(&s_stat[SBQ_MINY * maxP + g], k.y);
+        atomicMax(&s_stat[SBQ_MAXX * maxP + g], k.x);
+        atomicMax(&s_stat[SBQ_MAXY * maxP + g], k.y);
         // (rounding to float is monotonic: the largest float is the float of the largest double; >= 0, so its bits order as it does)
-        const double v2 = (double)v.x * (double)v.x + (double)v.y * (double)v.y;
-        atomicMax(&s_stat[SBQ_MAX_V2 * maxP + g], __float_as_uint((float)v2));
+        atomicMax(&s_stat[SBQ_MAX_V2 * maxP + g], __float_as_uint((float)k.v2));
         s_key[d] = g * W + (logW ? __brev(d) >> (32u - logW) : 0u);
     }
     __syncthreads();
@@ -130,14 +128,16 @@ __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V,
         if (g == SBQ_NONE || g != s_grp[g_pmap[w >> 16]]) continue;
         const float4 q = g_bstate[bd]; // {target_length, last_length, strain, stress}
         if ((j >> 5) < V.nflagw && ((g_flags[j >> 5] >> (j & 31u)) & 1u)) atomicAdd(&s_stat[SBQ_PENDING * maxP + g], 1u);
-        if (!(sbb_finite(q.z) && sbb_finite(q.w))) {
+        double strain;
+        uint32_t k[2];
+        if (!sbu_beam_leaf(q.z, q.w, strain, k)) {
             atomicAdd(&s_stat[SBQ_NB * maxP + g], 0x10001u);
             continue;
         }
         atomicAdd(&s_stat[SBQ_NB * maxP + g], 1u);
-        atomicMax(&s_stat[SBQ_MAX_STRAIN * maxP + g], sbb_fkey(q.z));
-        atomicMax(&s_stat[SBQ_MAX_STRESS * maxP + g], sbb_fkey(q.w));
-        atomicMin(&s_stat[SBQ_MIN_STRESS * maxP + g], sbb_fkey(q.w));
+        atomicMax(&s_stat[SBQ_MAX_STRAIN * maxP + g], k[0]);
+        atomicMax(&s_stat[SBQ_MAX_STRESS * maxP + g], k[1]);
+        atomicMin(&s_stat[SBQ_MIN_STRESS * maxP + g], k[1]);
     }
     // ---- the ranking: particles descending, then label ascending
     for (uint32_t q = tid; q < W; q += SBQ_BLOCK) {
@@ -155,27 +155,20 @@ __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V,
         const uint32_t key = s_key[q];
         if (key == SBQ_NONE) continue;
         const uint32_t r = key & (W - 1u), d = logW ? __brev(r) >> (32u - logW) : 0u;
-        const float2 p = g_part[3u * d], v = g_part[3u * d + 1u];
-        s_col[0u * W + q] = (double)p.x, s_col[1u * W + q] = (double)p.y, s_col[2u * W + q] = (double)v.x, s_col[3u * W + q] = (double)v.y;
-        s_col[4u * W + q] = 0.5 * ((double)v.x * (double)v.x + (double)v.y * (double)v.y); // (the products are exact)
-        s_col[5u * W + q] = (double)p.x * (double)v.y - (double)p.y * (double)v.x;
+        double leaf[SBQ_NSUM];
+        SbuParticleKeys k;
+        sbu_particle_values(g_part[3u * d], g_part[3u * d + 1u], leaf, k); // (a member: finite)
+#pragma unroll
+        for (uint32_t c = 0; c < SBQ_NSUM; c++) s_col[c * W + q] = leaf[c];
     }
     __syncthreads();
 
     // ---- the tree over the members alone
     for (uint32_t l = 0u; l < logW; l++) {
         for (uint32_t q = tid + (tid == 0u ? SBQ_BLOCK : 0u); q < W; q += SBQ_BLOCK) { // (position 0 never adds)
-            const uint32_t key = s_key[q];
-            if (key == SBQ_NONE) continue;
-            const uint32_t prev = s_key[q - 1u];
-            if ((prev >> l) == (key >> l) || !((key >> l) & 1u) || (prev >> (l + 1u)) != (key >> (l + 1u))) continue;
-            const uint32_t want = ((key >> l) - 1u) << l; // the left sibling block's head: the first position of a key >= want
-            uint32_t lo = 0u, hi = q - 1u;               // (position q - 1 is in that block)
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (s_key[mid] < want) lo = mid + 1u;
-                else hi = mid;
-            }
+            if (s_key[q] == SBQ_NONE) continue;
+            const uint32_t lo = sbu_sparse_step(s_key, q, l, 0u);
+            if (lo == SBU_NO_ADD) continue;
 #pragma unroll
             for (uint32_t k = 0; k < SBQ_NSUM; k++) s_col[k * W + lo] = s_col[k * W + lo] + s_col[k * W + q];
         }
@@ -192,7 +185,6 @@ __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V,
     }
     if (!rows) return; // (uniform)
     float *out = rows + (size_t)scene * max_rows * SB_BATCH_BODY_SUMMARY_WORDS;
-    const float nan = __uint_as_float(SBB_QNAN);
     // ---- the sums, from the first sorted position of every label that has a finite member
     for (uint32_t q = tid; q < W; q += SBQ_BLOCK) {
         const uint32_t key = s_key[q];
@@ -200,12 +192,12 @@ __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V,
         const uint32_t g = key >> logW, r = s_rank[g];
         if (r >= max_rows) continue;
         const uint32_t cnt = s_stat[SBQ_NP * maxP + g];
-        const double n = (double)((cnt & 0xffffu) - (cnt >> 16));
         float *row = out + (size_t)r * SB_BATCH_BODY_SUMMARY_WORDS;
+        double tot[SBQ_NSUM];
 #pragma unroll
-        for (uint32_t k = 0; k < 4u; k++) row[6u + k] = (float)(sbq_canon(s_col[k * W + q]) / n);
-        row[14] = (float)sbq_canon(s_col[4u * W + q]); // (round to nearest: +inf beyond the range of float)
-        row[19] = (float)sbq_canon(s_col[5u * W + q]);
+        for (uint32_t k = 0; k < SBQ_NSUM; k++) tot[k] = sbu_canon(s_col[k * W + q]);
+        sbu_row_sums(row, (cnt & 0xffffu) - (cnt >> 16), tot);
+        row[19] = (float)tot[5];
     }
     // ---- everything else, one row per thread
     for (uint32_t r = tid; r < max_rows; r += SBQ_BLOCK) {
@@ -214,7 +206,7 @@ __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V,
         if (rkey == SBQ_NONE) { // behind the last group: the empty row
 #pragma unroll
             for (uint32_t k = 0; k < SB_BATCH_BODY_SUMMARY_WORDS; k++)
-                row[k] = (k <= 1u || (k >= 3u && k <= 5u) || k == 14u || k >= 19u) ? 0.0f : (k == 2u ? -1.0f : nan);
+                row[k] = sbu_empty_body_word(k);
             continue;
         }
         const uint32_t g = 1023u - (~rkey & 1023u);
@@ -227,17 +219,13 @@ __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V,
         row[4] = (float)(cp >> 16);
         row[5] = (float)(cb >> 16);
         if (np == 0u) { // no finite member: no sorted position wrote the sums
-            row[6] = row[7] = row[8] = row[9] = nan;
+            row[6] = row[7] = row[8] = row[9] = __uint_as_float(SBB_QNAN);
             row[14] = row[19] = 0.0f;
         }
-        row[10] = np ? sbb_unkey(s_stat[SBQ_MINX * maxP + g]) : nan;
-        row[11] = np ? sbb_unkey(s_stat[SBQ_MINY * maxP + g]) : nan;
-        row[12] = np ? sbb_unkey(s_stat[SBQ_MAXX * maxP + g]) : nan;
-        row[13] = np ? sbb_unkey(s_stat[SBQ_MAXY * maxP + g]) : nan;
-        row[15] = np ? __uint_as_float(s_stat[SBQ_MAX_V2 * maxP + g]) : nan;
-        row[16] = nb ? sbb_unkey(s_stat[SBQ_MAX_STRAIN * maxP + g]) : nan;
-        row[17] = nb ? sbb_unkey(s_stat[SBQ_MAX_STRESS * maxP + g]) : nan;
-        row[18] = nb ? sbb_unkey(s_stat[SBQ_MIN_STRESS * maxP + g]) : nan;
+        sbu_row_extremes(row, np, nb, SbuRowKeys{s_stat[SBQ_MINX * maxP + g], s_stat[SBQ_MINY * maxP + g], s_stat[SBQ_MAXX * maxP + g],
+                                                 s_stat[SBQ_MAXY * maxP + g], __uint_as_float(s_stat[SBQ_MAX_V2 * maxP + g]),
+                                                 s_stat[SBQ_MAX_STRAIN * maxP + g], s_stat[SBQ_MAX_STRESS * maxP + g],
+                                                 s_stat[SBQ_MIN_STRESS * maxP + g]});
         row[20] = row[21] = row[22] = row[23] = 0.0f;
     }
 }

@@ -76,18 +76,6 @@ SB_DEV uint32_t sbk_scan(uint32_t *a, uint32_t n, uint32_t *s_wave)
     return total;
 }
 
-// The contact test of k_batch_frame's collision loop on two positions.  The root is only taken where d2 <= thr = (2r)^2 * 1.001
-// (beyond it sqrt(d2) > 2r * 1.0004: no contact, and d2 > 0); thr is +inf where that product is no ordinary number, a NaN d2 fails
-// `d2 > thr` and then every comparison: a NaN or infinite distance is no contact.
-SB_DEV bool sbk_touch(float2 me, float2 other, float thr, float two_r)
-{
-    const float dx = other.x - me.x, dy = other.y - me.y;
-    const float d2 = dx * dx + dy * dy;
-    if (d2 > thr) return false;
-    const float dist = sb_sqrt(d2); // sb_length(dx, dy)
-    return dist == 0.0f || dist < two_r;
-}
-
 __global__ __launch_bounds__(SBK_BLOCK) void k_batch_contacts(SbBatchView V, SbParams prm, uint32_t G, float cell, uint32_t other_body,
                                                               const int32_t *__restrict__ labels, int32_t *__restrict__ touch,
                                                               int32_t *__restrict__ pairs, uint32_t max_pairs, int32_t *__restrict__ counts)
@@ -174,7 +162,7 @@ __global__ __launch_bounds__(SBK_BLOCK) void k_batch_contacts(SbBatchView V, SbP
                 const uint32_t from = r0 ? s_end[r0 - 1u] : 0u, to = s_end[r1];
                 for (uint32_t k = from; k < to; k++) {
                     const uint32_t o = s_sorted[k];
-                    if (o == d || !sbk_touch(me, s_pos[o], thr, two_r)) continue;
+                    if (o == d || !sb_touch(me, s_pos[o], thr, two_r)) continue;
                     const uint32_t differs = s_lab[o] != my_lab ? 1u : 0u, up = o > d ? 1u : 0u;
                     n++;
                     cross += differs;
@@ -232,7 +220,7 @@ __global__ __launch_bounds__(SBK_BLOCK) void k_batch_contacts(SbBatchView V, SbP
                 const uint32_t from = r0 ? s_end[r0 - 1u] : 0u, to = s_end[r1];
                 for (uint32_t k = from; k < to; k++) {
                     uint32_t o = s_sorted[k];
-                    if (o <= last || o >= bs[3] || (other_body && s_lab[o] == my_lab) || !sbk_touch(me, s_pos[o], thr, two_r)) continue;
+                    if (o <= last || o >= bs[3] || (other_body && s_lab[o] == my_lab) || !sb_touch(me, s_pos[o], thr, two_r)) continue;
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
                         const uint32_t small = min(o, bs[q]);

@@ -2,7 +2,7 @@
 // sb_engine, reproducible bit for bit, on the device (sb_body_summary / sb_body_summary_device of include/softbody.h; gfx950,
 // wave64).
 //
-// The definition is sb_batch_body_summary_device's, word for word, for the one scene, and so is its pin: the sum of a group is
+// The definition is sb_batch_body_summary_device's, word for word (both files call sb_summary_math.h), and so is its pin: the sum of a group is
 // what sb_summary's tree gives for a scene holding only the group's finite particles -- double precision, leaf i = the value at
 // DATA index i if the particle is finite and in the group, else +0.0, i = 0 .. W-1, reduced by  for h = W/2 .. 1: s[i] += s[i + h].
 // k_batch_body_summary sorts a scene in the LDS of one workgroup; here the members lie in HBM, a scene holds a million bodies or
@@ -42,7 +42,7 @@
 #include <vector>
 
 #include "sb_report.h"
-#include "sb_batch.h" // sbb_finite, sbb_fkey / sbb_unkey, SBB_QNAN, sbb_pow2_at_least: the batch row's own helpers
+#include "sb_batch.h" // (sb_summary_math.h: the row's arithmetic, shared with the batch)
 
 #define SBY_BLOCK 256u
 #define SBY_WAVES (SBY_BLOCK / 64u)
@@ -62,7 +62,6 @@ enum { SBY_C_HEADS, SBY_C_GROUPS, SBY_NCTL }; // device control words: runs of e
 
 SB_DEV uint32_t sby_label(unsigned long long key) { return (uint32_t)(key >> 32); }
 SB_DEV uint32_t sby_data_index(unsigned long long key) { return __brev((uint32_t)key); }
-SB_DEV double sby_canon(double sum) { return sum + 0.0; } // -0.0 -> +0.0, every other value as it is
 
 // the number of keys of a sort: the host's bound, or the device's word where that is smaller
 SB_DEV uint32_t sby_count(uint32_t n_max, const uint32_t *__restrict__ n_dev) { return n_dev ? min(*n_dev, n_max) : n_max; }
@@ -177,19 +176,15 @@ __global__ __launch_bounds__(SBY_BLOCK) void k_bsum_leaves(const unsigned long l
     flag[q] = head ? 1u : 0u;
     if (g == none) return;
     const uint32_t i = pinv[sby_data_index(key)]; // (a member: a particle lives there)
-    const float2 p = pos[i], v = vel[i], a = acc[i];
     double leaf[SBY_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    uint32_t st[SBY_NPST] = {1u, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
-    if (sbb_finite(p.x) && sbb_finite(p.y) && sbb_finite(v.x) && sbb_finite(v.y) && sbb_finite(a.x) && sbb_finite(a.y)) {
-        const double v2 = (double)v.x * (double)v.x + (double)v.y * (double)v.y; // (the products are exact)
-        leaf[0] = (double)p.x, leaf[1] = (double)p.y, leaf[2] = (double)v.x, leaf[3] = (double)v.y;
-        leaf[4] = 0.5 * v2;
-        leaf[5] = (double)p.x * (double)v.y - (double)p.y * (double)v.x;
+    uint32_t st[SBY_NPST] = {1u, SBB_KEY_MOST, SBB_KEY_MOST, SBB_KEY_LEAST, SBB_KEY_LEAST, 0u};
+    SbuParticleKeys pk;
+    if (sbu_particle_leaf(pos[i], vel[i], acc[i], leaf, pk)) {
         st[SBY_P_BAD] = 0u;
-        st[SBY_P_MINX] = st[SBY_P_MAXX] = sbb_fkey(p.x);
-        st[SBY_P_MINY] = st[SBY_P_MAXY] = sbb_fkey(p.y);
+        st[SBY_P_MINX] = st[SBY_P_MAXX] = pk.x;
+        st[SBY_P_MINY] = st[SBY_P_MAXY] = pk.y;
         // (rounding to float is monotonic: the largest float is the float of the largest double; >= 0, so its bits order as it does)
-        st[SBY_P_MAXV2] = __float_as_uint((float)v2);
+        st[SBY_P_MAXV2] = __float_as_uint((float)pk.v2);
     }
 #pragma unroll
     for (uint32_t k = 0; k < SBY_NSUM; k++) col[(size_t)k * Wn + q] = leaf[k];
@@ -197,7 +192,7 @@ __global__ __launch_bounds__(SBY_BLOCK) void k_bsum_leaves(const unsigned long l
     for (uint32_t k = 0; k < SBY_NPST; k++) pst[(size_t)k * Wn + q] = st[k];
     if (head) {
 #pragma unroll
-        for (uint32_t k = 0; k < SBY_NBST; k++) bst[(size_t)k * Wn + q] = k == SBY_B_MINSTRESS ? 0xFFFFFFFFu : 0u;
+        for (uint32_t k = 0; k < SBY_NBST; k++) bst[(size_t)k * Wn + q] = k == SBY_B_MINSTRESS ? SBB_KEY_MOST : 0u;
     }
 }
 
@@ -207,17 +202,9 @@ __global__ __launch_bounds__(SBY_BLOCK) void k_bsum_level(const unsigned long lo
 {
     const uint32_t q = blockIdx.x * SBY_BLOCK + threadIdx.x;
     if (q == 0u || q >= Wn) return; // (position 0 never adds)
-    const unsigned long long key = keys[q];
-    if (sby_label(key) == none) return;
-    const unsigned long long prev = keys[q - 1u];
-    if ((prev >> bit) == (key >> bit) || !((key >> bit) & 1ull) || (prev >> (bit + 1u)) != (key >> (bit + 1u))) return;
-    const unsigned long long want = ((key >> bit) - 1ull) << bit; // the left sibling block's head: the first position of a key >= want
-    uint32_t lo = q > span ? q - span : 0u, hi = q - 1u;          // (position q - 1 is in that block, which holds at most span keys)
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < want) lo = mid + 1u;
-        else hi = mid;
-    }
+    if (sby_label(keys[q]) == none) return;
+    const uint32_t lo = sbu_sparse_step(keys, q, bit, q > span ? q - span : 0u); // (the sibling block holds at most span keys)
+    if (lo == SBU_NO_ADD) return;
 #pragma unroll
     for (uint32_t k = 0; k < SBY_NSUM; k++) col[(size_t)k * Wn + lo] = col[(size_t)k * Wn + lo] + col[(size_t)k * Wn + q];
     pst[(size_t)SBY_P_BAD * Wn + lo] += pst[(size_t)SBY_P_BAD * Wn + q];
@@ -256,7 +243,7 @@ SB_DEV void sby_beam_push(T *row, size_t stride, const uint32_t (&v)[SBY_NBST])
     if (v[SBY_B_BAD]) atomicAdd(&row[SBY_B_BAD * stride], v[SBY_B_BAD]);
     if (v[SBY_B_MAXSTRAIN]) atomicMax(&row[SBY_B_MAXSTRAIN * stride], v[SBY_B_MAXSTRAIN]);
     if (v[SBY_B_MAXSTRESS]) atomicMax(&row[SBY_B_MAXSTRESS * stride], v[SBY_B_MAXSTRESS]);
-    if (v[SBY_B_MINSTRESS] != 0xFFFFFFFFu) atomicMin(&row[SBY_B_MINSTRESS * stride], v[SBY_B_MINSTRESS]);
+    if (v[SBY_B_MINSTRESS] != SBB_KEY_MOST) atomicMin(&row[SBY_B_MINSTRESS * stride], v[SBY_B_MINSTRESS]);
 }
 
 // tab: [4][n] = data index of A, data index of B, engine slot, the copy read back for it, per caller beam slot.  A workgroup owns
@@ -270,7 +257,7 @@ __global__ __launch_bounds__(SBY_BLOCK) void k_bsum_beams(const uint32_t *__rest
     __shared__ uint32_t s_acc[SBY_NBST];
     __shared__ uint32_t s_first;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    if (tid < SBY_NBST) s_acc[tid] = tid == SBY_B_MINSTRESS ? 0xFFFFFFFFu : 0u;
+    if (tid < SBY_NBST) s_acc[tid] = tid == SBY_B_MINSTRESS ? SBB_KEY_MOST : 0u;
     if (tid == 0u) { // the group of the A end of the first slot, whether or not that beam counts
         const uint32_t u0 = blockIdx.x * (SBY_PER * SBY_BLOCK);
         const uint32_t lab = u0 < n ? (uint32_t)labels[tab[u0]] : none;
@@ -281,18 +268,19 @@ __global__ __launch_bounds__(SBY_BLOCK) void k_bsum_beams(const uint32_t *__rest
     for (uint32_t j = 0; j < SBY_PER; j++) { // (uniform)
         const uint32_t u = blockIdx.x * (SBY_PER * SBY_BLOCK) + j * SBY_BLOCK + tid;
         uint32_t g = none;
-        uint32_t v[SBY_NBST] = {0u, 0u, 0u, 0u, 0u, 0xFFFFFFFFu};
+        uint32_t v[SBY_NBST] = {0u, 0u, 0u, SBB_KEY_LEAST, SBB_KEY_LEAST, SBB_KEY_MOST};
         if (u < n && !(dead && dead[tab[2u * (size_t)n + u]] != 0u)) {
             const uint32_t la = (uint32_t)labels[tab[u]], lb = (uint32_t)labels[tab[(size_t)n + u]];
             if (la < none && la == lb) {
                 g = la;
                 const uint32_t c = tab[3u * (size_t)n + u];
-                const float sn = strain[c], ss = stress[c];
                 v[SBY_B_LIVE] = 1u;
                 v[SBY_B_PENDING] = (broken[c >> 5] >> (c & 31u)) & 1u;
-                if (sbb_finite(sn) && sbb_finite(ss)) {
-                    v[SBY_B_MAXSTRAIN] = sbb_fkey(sn);
-                    v[SBY_B_MAXSTRESS] = v[SBY_B_MINSTRESS] = sbb_fkey(ss);
+                double leaf;
+                uint32_t bk[2];
+                if (sbu_beam_leaf(strain[c], stress[c], leaf, bk)) {
+                    v[SBY_B_MAXSTRAIN] = bk[0];
+                    v[SBY_B_MAXSTRESS] = v[SBY_B_MINSTRESS] = bk[1];
                 } else v[SBY_B_BAD] = 1u;
             }
         }
@@ -370,13 +358,12 @@ __global__ __launch_bounds__(SBY_BLOCK) void k_bsum_rows(const unsigned long lon
 {
     const uint64_t k = (uint64_t)blockIdx.x * SBY_BLOCK + threadIdx.x;
     if (k >= max_rows) return;
-    const float nan = __uint_as_float(SBB_QNAN);
     float row[SB_BODY_SUMMARY_WORDS];
     long long c8[SB_BODY_SUMMARY_COUNT_WORDS] = {0, 0, -1, 0, 0, 0, 0, 0};
     if (k >= min(ctl[SBY_C_GROUPS], Wn)) { // behind the last group: the empty row
 #pragma unroll
         for (uint32_t w = 0; w < SB_BODY_SUMMARY_WORDS; w++)
-            row[w] = (w <= 1u || (w >= 3u && w <= 5u) || w == 14u || w >= 19u) ? 0.0f : (w == 2u ? -1.0f : nan);
+            row[w] = sbu_empty_body_word(w);
     } else {
         const uint32_t j = (uint32_t)sorted[k], h = ghead[j], cnt = gcnt[j];
         uint32_t p[SBY_NPST], b[SBY_NBST];
@@ -389,18 +376,13 @@ __global__ __launch_bounds__(SBY_BLOCK) void k_bsum_rows(const unsigned long lon
         c8[6] = np;
 #pragma unroll
         for (uint32_t w = 0; w < 6u; w++) row[w] = (float)c8[w];
+        double tot[SBY_NSUM]; // (a zero sum as +0.0)
 #pragma unroll
-        for (uint32_t w = 0; w < 4u; w++) row[6u + w] = np ? (float)(sby_canon(col[(size_t)w * Wn + h]) / (double)np) : nan;
-        row[10] = np ? sbb_unkey(p[SBY_P_MINX]) : nan;
-        row[11] = np ? sbb_unkey(p[SBY_P_MINY]) : nan;
-        row[12] = np ? sbb_unkey(p[SBY_P_MAXX]) : nan;
-        row[13] = np ? sbb_unkey(p[SBY_P_MAXY]) : nan;
-        row[14] = (float)sby_canon(col[(size_t)4u * Wn + h]); // (round to nearest: +inf beyond the range of float)
-        row[15] = np ? __uint_as_float(p[SBY_P_MAXV2]) : nan;
-        row[16] = nb ? sbb_unkey(b[SBY_B_MAXSTRAIN]) : nan;
-        row[17] = nb ? sbb_unkey(b[SBY_B_MAXSTRESS]) : nan;
-        row[18] = nb ? sbb_unkey(b[SBY_B_MINSTRESS]) : nan;
-        row[19] = (float)sby_canon(col[(size_t)5u * Wn + h]);
+        for (uint32_t w = 0; w < SBY_NSUM; w++) tot[w] = sbu_canon(col[(size_t)w * Wn + h]);
+        sbu_row_sums(row, np, tot);
+        sbu_row_extremes(row, np, nb, SbuRowKeys{p[SBY_P_MINX], p[SBY_P_MINY], p[SBY_P_MAXX], p[SBY_P_MAXY], __uint_as_float(p[SBY_P_MAXV2]),
+                                                 b[SBY_B_MAXSTRAIN], b[SBY_B_MAXSTRESS], b[SBY_B_MINSTRESS]});
+        row[19] = (float)tot[5];
         row[20] = row[21] = row[22] = row[23] = 0.0f;
     }
     if (rows) {

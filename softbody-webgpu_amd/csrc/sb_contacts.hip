@@ -2,8 +2,8 @@
 // sb_contacts_device of include/softbody.h; gfx950, wave64).
 //
 // The definition is sb_batch_contacts_device's, word for word: two distinct particles i, j TOUCH iff dist == 0 or
-// dist < particle_radius * 2, dist = sb_length(xj - xi, yj - yi) of the current particle records (sbc_touch below is sbk_touch of
-// sb_batch_contacts.hip, expression for expression, compiled with the same flags), everything named by particle DATA index.
+// dist < particle_radius * 2, dist = sb_length(xj - xi, yj - yi) of the current particle records (sb_touch of sb_batch.h, the one test both
+// files call), everything named by particle DATA index.
 // k_batch_contacts holds a scene in the LDS of one workgroup; here the scene lies in HBM, and the call may only enqueue: nothing
 // loops on a host read-back and no workgroup waits for another.  A counting sort by cell in global memory, one launch per stage:
 //   k_contacts_bin      a thread per data index: the position (through the shared data index -> internal particle table, sb_report.hip, in
@@ -34,7 +34,7 @@
 #include <vector>
 
 #include "sb_report.h"
-#include "sb_batch.h" // sb_batch_cell_geometry: the cells' rule
+#include "sb_batch.h" // sb_batch_cell_geometry: the cells' rule; sb_touch: the contact test
 
 #define SBC_BLOCK 256u
 #define SBC_NONE 0xFFFFFFFFu
@@ -54,17 +54,6 @@ struct SbcGeo {
 };
 
 SB_DEV uint32_t sbc_cell(float x, float y, SbcGeo g) { return sb_grid_coord(y, 0.0f, g.cell, g.G) * g.G + sb_grid_coord(x, 0.0f, g.cell, g.G); }
-
-// sbk_touch (sb_batch_contacts.hip): the contact test of the step's collision loop on two positions.  The root is only taken
-// where d2 <= thr = (2r)^2 * 1.001; a NaN d2 fails `d2 > thr` and then every comparison: a NaN or infinite distance is no contact.
-SB_DEV bool sbc_touch(float mx, float my, float ox, float oy, float thr, float two_r)
-{
-    const float dx = ox - mx, dy = oy - my;
-    const float d2 = dx * dx + dy * dy;
-    if (d2 > thr) return false;
-    const float dist = sb_sqrt(d2); // sb_length(dx, dy)
-    return dist == 0.0f || dist < two_r;
-}
 
 // Add each maximal run of lanes with the same cell c != SBC_NONE to count[c] with one atomic of its first lane (sbd_add_runs'
 // form: neighbouring data indices mostly lie in neighbouring places).  Every lane of the wave calls it.
@@ -154,7 +143,7 @@ __global__ __launch_bounds__(SBC_BLOCK) void k_contacts_visit(const SbcRec *__re
             w.row(end, yy, &from, &to);
             for (uint32_t q = from; q < to; q++) {
                 const SbcRec o = sorted[q];
-                if (o.d == me.d || !sbc_touch(me.x, me.y, o.x, o.y, ts.thr, ts.two_r)) continue;
+                if (o.d == me.d || !sb_touch(make_float2(me.x, me.y), make_float2(o.x, o.y), ts.thr, ts.two_r)) continue;
                 const uint32_t differs = labels && labels[o.d] != my_lab ? 1u : 0u, up = o.d > me.d ? 1u : 0u;
                 n++;
                 cross += differs;
@@ -209,7 +198,7 @@ __global__ __launch_bounds__(SBC_BLOCK) void k_contacts_list(const SbcRec *__res
             for (uint32_t q = from; q < to; q++) {
                 const SbcRec r = sorted[q];
                 uint32_t o = r.d;
-                if (o <= last || o >= bs[3] || !sbc_touch(me.x, me.y, r.x, r.y, ts.thr, ts.two_r) || (other_body && labels[o] == my_lab)) continue;
+                if (o <= last || o >= bs[3] || !sb_touch(make_float2(me.x, me.y), make_float2(r.x, r.y), ts.thr, ts.two_r) || (other_body && labels[o] == my_lab)) continue;
 #pragma unroll
                 for (int s = 0; s < 4; s++) {
                     const uint32_t small = min(o, bs[s]);

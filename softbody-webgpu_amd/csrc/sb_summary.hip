@@ -1,18 +1,19 @@
 // sb_summary.hip -- one row of SB_SUMMARY_WORDS statistics of the whole scene of an sb_engine, reduced on the device (sb_summary /
 // sb_summary_device of include/softbody.h; gfx950, wave64).
 //
-// The row is sb_batch_summary_device's, word for word, and so is its pin: sums in double, leaf i = the value at DATA index i (+0.0
+// The row is sb_batch_summary_device's, word for word (both files call sb_summary_math.h; tests/test_gpu_summary.py compares the two
+// rows bit for bit), and so is its pin: sums in double, leaf i = the value at DATA index i (+0.0
 // where no finite particle / beam lives), i = 0 .. W-1 with W the smallest power of two >= the capacity, reduced by the
 // stride-halving tree  for h = W/2 .. 1: s[i] += s[i + h] (i < h).  An engine holds millions of leaves, so the tree is cut into
 // launches.  What makes that possible: after all levels h >= n, element g < n holds the tree-sum of the leaves g + n k
 // (k < W / n), and the tree over those W / n values is again stride-halving: tree(e_0 .. e_K-1) = tree(even e) + tree(odd e)
-// (sbm_tree<K>, the batch kernel's recursion).  So
+// (sbu_tree<K>, the batch kernel's recursion).  So
 //   k_summary_particles<R> / k_summary_beams<R>   n = W / R threads; thread g tree-sums its own R leaves g + n k and writes one
 //                                                 partial per column (x, y, vx, vy, energy | strain); neighbouring threads read
 //                                                 neighbouring data indices
 //   k_summary_fold<R>                             the same step on a column of partials, in place, n -> n / R
 //   k_summary_row                                 one workgroup, at most 256 partials a column: levels 128 and 64 through LDS, the
-//                                                 rest by the xor butterfly of wave 0 (sbm_tree_tail); forms the row
+//                                                 rest by the xor butterfly of wave 0 (sbu_tree_tail); forms the row
 // Every launch performs exactly the additions of its levels on exactly the tree's operands, so the bits do not depend on where
 // the cuts are (sb_summary_options.partials moves them).  A leaf above the highest data index in use is +0.0 WITHOUT a load:
 // the addition stays (x + +0.0 turns a -0.0 into +0.0, as the tree does), the read goes.  Levels h >= W do not exist: with
@@ -27,7 +28,7 @@
 #include <vector>
 
 #include "sb_report.h"
-#include "sb_batch.h" // sbb_finite, sbb_fkey / sbb_unkey, SBB_QNAN, sbb_pow2_at_least: the batch row's own helpers
+#include "sb_batch.h" // (sb_summary_math.h: the row's arithmetic, shared with the batch)
 
 #define SBM_BLOCK 256u
 #define SBM_RMAX 64u      // partials a thread of a fold tree-sums, at most
@@ -51,13 +52,8 @@ struct SbmBeams {
     const float *strain, *stress;
     uint32_t n_leaf;
 };
-// (extremes as sbb_fkey keys from the first comparison on: -0.0 orders below +0.0 inside a thread exactly as it does between
-// threads and workgroups, so which zero an extreme returns does not depend on which leaves share a thread; 0xFFFFFFFF and 0 are
-// below / above the key of every finite float)
-struct SbmLocal {
-    uint32_t p_fin = 0u, p_bad = 0u, b_fin = 0u, b_bad = 0u, removed = 0u, pending = 0u;
-    uint32_t minx = 0xFFFFFFFFu, miny = 0xFFFFFFFFu, maxx = 0u, maxy = 0u, max_strain = 0u, max_stress = 0u, min_stress = 0xFFFFFFFFu;
-    double max_v2 = 0.0;
+struct SbmLocal : SbuLocal {
+    uint32_t removed = 0u, pending = 0u;
 };
 
 // the particle leaves of data index d: {px, py, vx, vy, 0.5 (vx^2 + vy^2)}
@@ -73,18 +69,7 @@ struct SbmParticleLeaf {
         if (d >= s.n_leaf) return;
         const uint32_t i = s.inv[d];
         if (i == 0xFFFFFFFFu) return;
-        const float2 p = s.pos[i], v = s.vel[i], a = s.acc[i];
-        if (!(sbb_finite(p.x) && sbb_finite(p.y) && sbb_finite(v.x) && sbb_finite(v.y) && sbb_finite(a.x) && sbb_finite(a.y))) {
-            l.p_bad++;
-            return;
-        }
-        const double v2 = (double)v.x * (double)v.x + (double)v.y * (double)v.y; // (the products are exact)
-        out[0] = (double)p.x, out[1] = (double)p.y, out[2] = (double)v.x, out[3] = (double)v.y, out[4] = 0.5 * v2;
-        const uint32_t kx = sbb_fkey(p.x), ky = sbb_fkey(p.y);
-        l.minx = min(l.minx, kx), l.maxx = max(l.maxx, kx);
-        l.miny = min(l.miny, ky), l.maxy = max(l.maxy, ky);
-        l.max_v2 = v2 > l.max_v2 ? v2 : l.max_v2; // (a sum of squares: never below +0.0)
-        l.p_fin++;
+        sbu_local_particle(l, s.pos[i], s.vel[i], s.acc[i], out);
     }
 };
 
@@ -105,16 +90,7 @@ struct SbmBeamLeaf {
             return;
         }
         l.pending += (s.broken[t.y >> 5] >> (t.y & 31u)) & 1u;
-        const float strain = s.strain[t.y], stress = s.stress[t.y];
-        if (!(sbb_finite(strain) && sbb_finite(stress))) {
-            l.b_bad++;
-            return;
-        }
-        out[0] = (double)strain;
-        const uint32_t kn = sbb_fkey(strain), ks = sbb_fkey(stress);
-        l.max_strain = max(l.max_strain, kn);
-        l.max_stress = max(l.max_stress, ks), l.min_stress = min(l.min_stress, ks);
-        l.b_fin++;
+        sbu_local_beam(l, s.strain[t.y], s.stress[t.y], out);
     }
 };
 
@@ -124,21 +100,6 @@ struct SbmPartialLeaf {
     uint32_t g, n;
     SB_DEV void operator()(uint32_t k, double (&out)[1]) const { out[0] = col[(size_t)g + (size_t)n * k]; }
 };
-
-// the stride-halving tree over K values e_j = leaf(base + j step), j < K
-template <int K, int N, class Leaf>
-SB_DEV void sbm_tree(const Leaf &leaf, uint32_t base, uint32_t step, double (&out)[N])
-{
-    if constexpr (K == 1) {
-        leaf(base, out);
-    } else {
-        double even[N], odd[N];
-        sbm_tree<K / 2, N>(leaf, base, 2u * step, even);
-        sbm_tree<K / 2, N>(leaf, base + step, 2u * step, odd);
-#pragma unroll
-        for (int c = 0; c < N; c++) out[c] = even[c] + odd[c];
-    }
-}
 
 // a workgroup's share of the order-free statistics: LDS first, then one global atomic per word that is not neutral
 SB_DEV void sbm_push_stats(const SbmLocal &l, unsigned long long *s_stat, unsigned long long *stat, uint32_t tid)
@@ -188,7 +149,7 @@ __global__ __launch_bounds__(SBM_BLOCK) void k_summary_particles(SbmParticles s,
     SbmLocal l;
     if (g < n) {
         double out[5];
-        sbm_tree<R, 5>(SbmParticleLeaf{s, l, g, n}, 0u, 1u, out);
+        sbu_tree<R, 5>(SbmParticleLeaf{s, l, g, n}, 0u, 1u, out);
 #pragma unroll
         for (int c = 0; c < 5; c++) part[(size_t)c * n + g] = out[c];
     }
@@ -203,7 +164,7 @@ __global__ __launch_bounds__(SBM_BLOCK) void k_summary_beams(SbmBeams s, uint32_
     SbmLocal l;
     if (g < n) {
         double out[1];
-        sbm_tree<R, 1>(SbmBeamLeaf{s, l, g, n}, 0u, 1u, out);
+        sbu_tree<R, 1>(SbmBeamLeaf{s, l, g, n}, 0u, 1u, out);
         part[g] = out[0];
     }
     sbm_push_stats(l, s_stat, stat, tid);
@@ -218,20 +179,8 @@ __global__ __launch_bounds__(SBM_BLOCK) void k_summary_fold(double *part, uint32
     if (g >= n_out) return;
     double *col = part + (size_t)blockIdx.y * stride;
     double out[1];
-    sbm_tree<R, 1>(SbmPartialLeaf{col, g, n_out}, 0u, 1u, out);
+    sbu_tree<R, 1>(SbmPartialLeaf{col, g, n_out}, 0u, 1u, out);
     col[g] = out[0];
-}
-
-// levels h = 128 .. 1 of a tree whose upper levels left w <= 256 partials in s_col[0 .. w-1]; the sum is lane 0's
-SB_DEV double sbm_tree_tail(const double *s_col, uint32_t lane, uint32_t w)
-{
-    double v = s_col[lane];
-    if (w >= 256u) v = (v + s_col[lane + 128u]) + (s_col[lane + 64u] + s_col[lane + 192u]);
-    else if (w == 128u) v = v + s_col[lane + 64u];
-#pragma unroll
-    for (uint32_t h = 32u; h != 0u; h >>= 1)
-        if (h < w) v = v + __shfl_xor(v, (int)h);
-    return v;
 }
 
 // one workgroup: wp <= 256 partials of each particle column (columns stride_p apart), wb <= 256 of the strain column
@@ -249,27 +198,19 @@ __global__ __launch_bounds__(SBM_BLOCK) void k_summary_row(const double *__restr
     if (tid >= 64u) return;
     double tot[6];
 #pragma unroll
-    for (uint32_t c = 0; c < 6u; c++) tot[c] = sbm_tree_tail(s_sum[c], tid, c < 5u ? wp : wb);
+    for (uint32_t c = 0; c < 6u; c++) tot[c] = sbu_tree_tail(s_sum[c], tid, c < 5u ? wp : wb);
     if (tid != 0u) return;
-    const float nan = __uint_as_float(SBB_QNAN);
     const unsigned long long np = stat[SBM_P_FIN], nb = stat[SBM_B_FIN], removed = stat[SBM_B_REMOVED];
     // (the engine keeps no metadata buffer on the device: particle_i_c is the particles the leaf launches met, beam_i_c the beams
     // they met alive -- counted on the device, no host shadow enters the row)
     const unsigned long long c8[8] = {np + stat[SBM_P_BAD], nb + stat[SBM_B_BAD], removed, stat[SBM_PENDING], stat[SBM_P_BAD], stat[SBM_B_BAD], 1ull, 0ull};
 #pragma unroll
     for (int k = 0; k < 6; k++) row[k] = (float)c8[k];
-#pragma unroll
-    for (int k = 0; k < 4; k++) row[6 + k] = np ? (float)(tot[k] / (double)np) : nan;
-    row[10] = np ? sbb_unkey((uint32_t)stat[SBM_MINX]) : nan;
-    row[11] = np ? sbb_unkey((uint32_t)stat[SBM_MINY]) : nan;
-    row[12] = np ? sbb_unkey((uint32_t)stat[SBM_MAXX]) : nan;
-    row[13] = np ? sbb_unkey((uint32_t)stat[SBM_MAXY]) : nan;
-    row[14] = (float)tot[4]; // (round to nearest: +inf beyond the range of float)
-    row[15] = np ? (float)__longlong_as_double((long long)stat[SBM_MAX_V2]) : nan;
-    row[16] = nb ? sbb_unkey((uint32_t)stat[SBM_MAX_STRAIN]) : nan;
-    row[17] = nb ? sbb_unkey((uint32_t)stat[SBM_MAX_STRESS]) : nan;
-    row[18] = nb ? sbb_unkey((uint32_t)stat[SBM_MIN_STRESS]) : nan;
-    row[19] = nb ? (float)(tot[5] / (double)nb) : nan;
+    sbu_row_sums(row, np, tot);
+    sbu_row_extremes(row, np, nb, SbuRowKeys{(uint32_t)stat[SBM_MINX], (uint32_t)stat[SBM_MINY], (uint32_t)stat[SBM_MAXX], (uint32_t)stat[SBM_MAXY],
+                                             (float)__longlong_as_double((long long)stat[SBM_MAX_V2]), (uint32_t)stat[SBM_MAX_STRAIN],
+                                             (uint32_t)stat[SBM_MAX_STRESS], (uint32_t)stat[SBM_MIN_STRESS]});
+    row[19] = nb ? (float)(tot[5] / (double)nb) : __uint_as_float(SBB_QNAN);
     row[20] = 1.0f;
     row[21] = row[22] = row[23] = 0.0f;
     if (counts) {

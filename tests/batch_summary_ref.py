@@ -2,12 +2,14 @@
 tests/test_gpu_batch_summary.py and, on the oracle alone, of tests/test_batch_summary_cpu.py.
 
 The sums are the pinned ones: float64, leaf i = the value at DATA index i (+0.0 where no finite particle / beam lives),
-i = 0 .. W-1 with W the smallest power of two >= the capacity, reduced by the stride-halving tree."""
+i = 0 .. W-1 with W the smallest power of two >= the capacity, reduced by the stride-halving tree.  The extremes are taken in the
+order of the floats' keys: -0.0 below +0.0 (tests/float_keys.py)."""
 import numpy as np
+
+from float_keys import key_max, key_min
 
 WORDS = 24
 QNAN = np.uint32(0x7FC00000).view(np.float32)
-COUNT_WORDS, MEAN_SUM_WORDS, EXTREME_WORDS = (0, 1, 2, 3, 4, 5, 20, 21, 22, 23), (6, 7, 8, 9, 14, 19), (10, 11, 12, 13, 15, 16, 17, 18)
 
 
 def pow2_at_least(n):
@@ -71,8 +73,8 @@ def summary_ref(buf, uploaded_exists, pending):
         if n:
             for k in range(4):
                 row[6 + k] = np.float32(tree_sum(leaf[k]) / np.float64(n))
-            row[10], row[11] = rec[fin][:, 0].min(), rec[fin][:, 1].min()
-            row[12], row[13] = rec[fin][:, 0].max(), rec[fin][:, 1].max()
+            row[10], row[11] = key_min(rec[fin][:, 0]), key_min(rec[fin][:, 1])
+            row[12], row[13] = key_max(rec[fin][:, 0]), key_max(rec[fin][:, 1])
             row[15] = np.float32(v2.max())
         row[14] = np.float32(tree_sum(leaf[4]))
         strain, stress = buf.beams["strain"][live], buf.beams["stress"][live]
@@ -83,7 +85,7 @@ def summary_ref(buf, uploaded_exists, pending):
         if nb:
             bl = np.zeros(Wb, dtype=np.float64)
             bl[live[bfin]] = strain[bfin].astype(np.float64)
-            row[16], row[17], row[18] = strain[bfin].max(), stress[bfin].max(), stress[bfin].min()
+            row[16], row[17], row[18] = key_max(strain[bfin]), key_max(stress[bfin]), key_min(stress[bfin])
             row[19] = np.float32(tree_sum(bl) / np.float64(nb))
         row[20] = 1.0
     return row
@@ -98,7 +100,8 @@ def rows_of(refs, bufs):
 
 
 def assert_rows_equal(got, exp, what=""):
-    """Sums, means and counts by their bits; extremes by value (-0 == +0); NaN words as `is NaN`."""
+    """Every word by its bits -- sums, means, counts and extremes (a zero extreme has the sign the keys' order gives it); NaN words
+    as `is NaN`."""
     got, exp = np.asarray(got, dtype=np.float32), np.asarray(exp, dtype=np.float32)
     assert got.shape == exp.shape and got.shape[-1] == WORDS, (what, got.shape, exp.shape)
     g2, e2 = got.reshape(-1, WORDS), exp.reshape(-1, WORDS)
@@ -108,7 +111,5 @@ def assert_rows_equal(got, exp, what=""):
             where = "%s: row %d word %d: got %r, expected %r" % (what, r, w, g, e)
             if np.isnan(e):
                 assert np.isnan(g), where
-            elif w in EXTREME_WORDS:
-                assert g == e, where
             else:
                 assert g.view(np.uint32) == e.view(np.uint32), where

@@ -1,8 +1,8 @@
 """The rows, exact counts and ranks of sb_body_summary_device (include/softbody.h), restated in numpy the dense
 way: per group a masked tree of W float64 leaves (leaf i = the value at DATA index i if particle i is finite and in the group, else
 +0.0) reduced by tests/batch_summary_ref.py's tree_sum, a zero sum +0.0; int64 counts; extremes by the ORDERED KEYS of the floats
-(-0.0 below +0.0).  On a scene that also fits a batch it gives tests/batch_body_summary_ref.py's rows (that one compares floats:
-its extremes agree by value).  Only the rows that are asked for are summed, so a scene of thousands of groups costs max_rows trees.
+(-0.0 below +0.0; tests/float_keys.py).  On a scene that also fits a batch it gives tests/batch_body_summary_ref.py's rows, bit
+for bit.  Only the rows that are asked for are summed, so a scene of thousands of groups costs max_rows trees.
 
 A group of at most two members needs no tree (direct=True, the default): by the pin's own rules a lone leaf among +0.0s comes out
 as itself (-0.0 as +0.0), and two leaves meet in exactly ONE addition of the tree -- each of them x + 0.0 + .. = x before it -- and
@@ -13,30 +13,12 @@ import numpy as np
 
 import batch_body_summary_ref as qr
 import batch_summary_ref as sr
+from float_keys import fkey, key_max, key_min, unkey  # noqa: F401 (the ordered keys, -0.0 below +0.0)
 
 WORDS, COUNT_WORDS = 24, 8
 QNAN = sr.QNAN
 SUMMARY_SHARED_WORDS = qr.SUMMARY_SHARED_WORDS
 EMPTY_COUNTS = (0, 0, -1, 0, 0, 0, 0, 0)
-
-
-def fkey(x):
-    """finite float32 values as uint32 keys of the same order, -0.0 below +0.0 (sbb_fkey)"""
-    b = np.asarray(x, dtype=np.float32).view(np.uint32)
-    return np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint32)
-
-
-def unkey(k):
-    k = np.asarray(k, dtype=np.uint32)
-    return np.where(k & np.uint32(0x80000000), k & np.uint32(0x7FFFFFFF), ~k).astype(np.uint32).view(np.float32)
-
-
-def key_min(x):
-    return unkey(fkey(x).min())
-
-
-def key_max(x):
-    return unkey(fkey(x).max())
 
 
 def groups_of(buf, labels):

@@ -96,6 +96,23 @@ def witness_cases(sb):
     return [mk("tree order", [big, 1.0, -big]), mk("all -0.0", [-0.0] * 4), mk("-0.0 beside empty leaves", [-0.0, -0.0])]
 
 
+def zero_sign_scenes(sb, cap=(1024, 0)):
+    """Two scenes of two free particles at data indices 0 and 256 -- at capacity 1024 both leaves of thread 0 of the batch's kernel,
+    which the tree visits in that order -- whose x, y, vx, vy are all zeros: A holds +0.0 at index 0 and -0.0 at index 256, B the
+    signs swapped.  Either way a minimum is -0.0 and a maximum +0.0: the keys order -0.0 below +0.0."""
+    out = []
+    for first in (0.0, -0.0):
+        buf = sb.Buffers(2, *cap)
+        pts = np.zeros((2, 6), "f4")
+        pts[0, :4], pts[1, :4] = first, -first
+        buf.set_scene(pts, np.zeros(0, sb.layout.BEAM_DTYPE[2]))
+        buf.particles[256], buf.particles[1] = buf.particles[1].copy(), 0.0
+        buf.mapping[1] = 256
+        out.append(dict(name="zeros %s first" % ("+0.0" if first == 0.0 and not np.signbit(first) else "-0.0"), buf=buf, bounds=1000.0,
+                        mode=OFF, program=[], compare_after=[-1]))
+    return out
+
+
 def case_nonfinite(sb):
     """After a frame a NaN coordinate in one particle and an infinite velocity in another; one substep later the beams on them
     are not finite either."""

@@ -4,6 +4,7 @@ tests/test_gpu_batch_summary.py: free of warnings, and biting where the GPU test
 non-finite state)."""
 import ctypes
 import os
+import subprocess
 import sys
 import warnings
 
@@ -14,8 +15,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import batch_cases as bc  # noqa: E402
 import batch_summary_cases as sc  # noqa: E402
 import batch_summary_ref as sr  # noqa: E402
+import summary_cases as ec  # noqa: E402
 
 F = np.float32
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "softbody-webgpu_amd", "csrc")
 
 
 def test_header_declares_and_library_exports_both_calls(sb):
@@ -111,6 +114,49 @@ def test_summary_ref_on_a_scene_worked_out_by_hand(sb):
         warnings.simplefilter("error")
         row = sr.summary_ref(now, buf, 0)
     assert row[14] == np.inf and row[15] == np.inf and np.isfinite(row[8])
+
+
+def dump_scene(buf, path, removed, pending):
+    """the input of tests/summary_math_check.cpp: the finite-or-not records of a scene at their data indices"""
+    P, B, maxP = buf.particle_count, buf.beam_count, buf.max_particles
+    pidx, bidx = buf.mapping[:P].astype(np.int64), buf.mapping[maxP:maxP + B].astype(np.int64)
+    with open(path, "wb") as f:
+        np.array([maxP, buf.max_beams, P, B, removed, pending], "<u4").tofile(f)
+        rec = np.zeros((P, 7), "<u4")
+        rec[:, 0], rec[:, 1:] = pidx, np.ascontiguousarray(buf.particles[pidx], "<f4").view("<u4")
+        rec.tofile(f)
+        rec = np.zeros((B, 3), "<u4")
+        rec[:, 0] = bidx
+        rec[:, 1], rec[:, 2] = (np.ascontiguousarray(buf.beams[k][bidx], "<f4").view("<u4") for k in ("strain", "stress"))
+        rec.tofile(f)
+
+
+@pytest.mark.parametrize("san", ["asan", "tsan"])
+def test_the_header_builds_the_references_row_on_the_host(sb, tmp_path, san):
+    """csrc/sb_summary_math.h -- the leaves, the tree over all W leaves, the row former the four kernels call -- compiled for the
+    host under sanitizers (tests/summary_math_check.cpp) gives summary_ref's 24 words bit for bit: on the tree-order witnesses, on
+    the two scenes of zeros of both signs (min -0.0, max +0.0 in both), and on the hand-made scene with beams, also where a
+    particle and a beam are not finite."""
+    exe = os.path.join("hostcheck_build", "summary_math_check_" + san)
+    p = subprocess.run(["make", "-C", CSRC, exe], capture_output=True, text=True)
+    assert p.returncode == 0, p.stdout + p.stderr
+    hand, _ = hand_scene(sb)
+    bad = hand.copy()
+    bad.particles[0, 5] = np.inf
+    bad.beams[1]["stress"] = np.nan
+    scenes = [(c["name"], c["buf"], 0) for c in ec.witness_cases(sb) + ec.zero_sign_scenes(sb)] + [("hand", hand, 1), ("hand, not finite", bad, 0)]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1",
+               TSAN_OPTIONS="halt_on_error=1")
+    for name, buf, pending in scenes:
+        path = str(tmp_path / "scene.bin")
+        dump_scene(buf, path, 0, pending)
+        r = subprocess.run([os.path.join(CSRC, exe), path], capture_output=True, text=True, timeout=120, env=env)
+        assert r.returncode == 0 and "Sanitizer" not in r.stderr, (name, r.stdout, r.stderr[-2000:])
+        got = np.array([int(w, 16) for w in r.stdout.split()], "<u4").view("f4")
+        sr.assert_rows_equal(got, sr.summary_ref(buf, buf, pending), name)
+    for c in ec.zero_sign_scenes(sb):
+        bits = sr.summary_ref(c["buf"], c["buf"], 0).view(np.uint32)
+        assert bits[10] == bits[11] == 0x80000000 and bits[12] == bits[13] == 0, c["name"]
 
 
 def test_tree_sum_is_the_stride_halving_tree():

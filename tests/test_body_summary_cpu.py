@@ -131,7 +131,8 @@ def test_sparse_route_equals_the_dense_trees(W):
 
 
 def test_the_minus_zero_rule(sb):
-    """a zero sum is +0.0; the extremes order -0.0 below +0.0 (the batch's reference may return either)"""
+    """a zero sum is +0.0; the extremes order -0.0 below +0.0 (as every reference of a row does: tests/batch_summary_ref.py and
+    tests/batch_body_summary_ref.py take their extremes through this file's keys)"""
     buf = sc.free_particles(sb, 4, [-0.0, 0.0, -0.0, 0.0])
     buf.particles[:4, 0] = np.array([0.0, -0.0, 0.0, -0.0], "f4")
     rows, counts, rank = yr.body_summary_ref(buf, np.zeros(4, np.int32), 1)

@@ -1,5 +1,5 @@
 """BatchEngine.summary / rollout (sb_batch_summary_device, sb_batch_rollout_device) against tests/batch_summary_ref.py
-on one oracle.OracleEngine per scene.  Sums, means and counts are compared by their bits, extremes by value, NaN words as NaN.
+on one oracle.OracleEngine per scene.  Every word is compared by its bits, NaN words as NaN.
 Scenes and programs live in tests/batch_summary_cases.py; tests/test_batch_summary_cpu.py shows on the CPU that they bite."""
 import ctypes
 import os
@@ -13,6 +13,7 @@ import batch_cases as bc  # noqa: E402
 from batch_harness import apply_to_batch, device_bytes, load_all, make_batch, upload_each  # noqa: E402
 import batch_summary_cases as sc  # noqa: E402
 import batch_summary_ref as sr  # noqa: E402
+import summary_cases as ec  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -74,6 +75,23 @@ def test_summary_against_the_oracle(sb, oracle, which):
     if which == "pile":
         assert be.info("cell_substeps") > 0
     be.destroy()
+
+
+def test_a_zero_extreme_does_not_depend_on_which_leaves_share_a_thread(sb):
+    """Capacity 1024 / 0: data indices 0 and 256 are leaves of thread 0.  Zeros of both signs in x, y, vx, vy, in either order:
+    the minimum is -0.0 and the maximum +0.0 (the keys' order), as where the two meet in different threads."""
+    scenes = ec.zero_sign_scenes(sb)
+    bufs = [c["buf"] for c in scenes]
+    be = make_batch(sb, dict(layout=2, cap=(1024, 0), mode=0, bufs=bufs))
+    upload_each(be, bufs)
+    rows = be.summary().cpu().numpy()
+    be.destroy()
+    print("rows", rows.view(np.uint32).tolist())
+    for i, c in enumerate(scenes):
+        bits = rows[i].view(np.uint32)
+        assert bits[10] == 0x80000000 and bits[12] == 0, (c["name"], hex(bits[10]), hex(bits[12]))   # min_x, max_x
+        assert bits[11] == 0x80000000 and bits[13] == 0, (c["name"], hex(bits[11]), hex(bits[13]))   # min_y, max_y
+        sr.assert_rows_equal(rows[i], sr.summary_ref(c["buf"], c["buf"], 0), c["name"])
 
 
 def test_summary_only_reads(sb):

@@ -146,8 +146,37 @@ def test_equals_the_batch_after_two_frames(sb, which):
     for m in (1, 16):
         brow, brank = be.body_summary(rows=m, rank=True)
         got = call(eng, m)
-        qr.assert_equal((got[0], got[2]), (brow.cpu().numpy()[0], brank.cpu().numpy()[0]), "%s, %d rows" % (which, m))   # (extremes by value)
+        qr.assert_equal((got[0], got[2]), (brow.cpu().numpy()[0], brank.cpu().numpy()[0]), "%s, %d rows" % (which, m))
         assert np.array_equal(got[1][:, :6].astype(np.float32), got[0][:, :6])
+    be.destroy()
+    eng.destroy()
+
+
+@pytest.mark.parametrize("which", ["default", "zeros"])
+def test_rows_and_ranks_are_the_batchs_word_for_word(sb, which):
+    """the same upload and the same labels, not stepped, in an Engine and in a BatchEngine of one scene: every word of the rows
+    (NaN as NaN) and every rank by its bits -- the default scene at the batch's capacity with its own bodies, and the zeros of
+    both signs at data indices 0 and 256 as one group (min -0.0, max +0.0)"""
+    if which == "default":
+        buf = bcs.fit(sb, bc.case_default(sb)["buf"], 1024, 4096)
+        labels = yc.body_labels(buf)
+    else:
+        buf = sc.zero_sign_scenes(sb)[0]["buf"]
+        labels = np.zeros(buf.max_particles, np.int32)
+    labels = np.ascontiguousarray(labels, np.int32)
+    be = bh.make_batch(sb, dict(layout=buf.layout, cap=(buf.max_particles, buf.max_beams), mode=0, bufs=[buf]))
+    bh.upload_each(be, [buf])
+    eng = engine(sb, buf, bounds=1000.0)
+    import torch
+    for m in (1, 16):
+        brow, brank = be.body_summary(torch.from_numpy(labels[None, :].copy()).cuda(), rows=m, rank=True)
+        got = call(eng, m, labels)
+        brow, brank = brow.cpu().numpy()[0], brank.cpu().numpy()[0]
+        print(which, m, "engine", got[0][0].view(np.uint32).tolist(), "batch", brow[0].view(np.uint32).tolist())
+        qr.assert_equal((got[0], got[2]), (brow, brank), "%s, %d rows" % (which, m))
+    if which == "zeros":
+        bits = got[0][0].view(np.uint32)
+        assert got[1][0, 0] == 2 and bits[10] == bits[11] == 0x80000000 and bits[12] == bits[13] == 0
     be.destroy()
     eng.destroy()
 

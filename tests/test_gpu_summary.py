@@ -121,6 +121,38 @@ def test_equals_the_batch(sb):
         assert erow[:21].tobytes() == brow[:21].tobytes(), "scene %d: engine %s, batch %s" % (i, erow, brow)
 
 
+def word_for_word_scenes(sb):
+    """(name, upload, pokes): the two scenes of zeros of both signs, the default scene at the batch's largest capacity, and the
+    non-finite case's pokes on its scene as uploaded"""
+    nf = sc.case_nonfinite(sb)
+    return ([(c["name"], c["buf"], []) for c in sc.zero_sign_scenes(sb)] +
+            [("default in 1024/4096", bc.fit(sb, sc.case_default(sb)["buf"], 1024, 4096), []), ("non-finite", nf["buf"], nf["program"][1][1])])
+
+
+@pytest.mark.parametrize("i", [0, 1, 2, 3])
+def test_row_is_the_batchs_word_for_word(sb, i):
+    """the same upload, not stepped, in an Engine and in a BatchEngine of one scene: all 24 words by their bits, NaN as NaN"""
+    name, buf, pokes = word_for_word_scenes(sb)[i]
+    be = bh.make_batch(sb, dict(layout=buf.layout, cap=(buf.max_particles, buf.max_beams), mode=0, bufs=[buf]))
+    bh.upload_each(be, [buf])
+    eng = sb.Engine(bounds_size=1000.0, layout=buf.layout, max_particles=buf.max_particles, max_beams=buf.max_beams, collision_mode=OFF)
+    eng.write_buffers(buf)
+    if pokes:
+        sc.apply_to_engine(eng, ("poke", pokes))
+        p = be.state_tensors()[0]
+        for d, col, v in pokes:
+            p[0, d, col] = float(v)
+        be.write_particles_device(p)
+    brow, erow = be.summary().cpu().numpy()[0], eng.summary().cpu().numpy()
+    be.destroy()
+    eng.destroy()
+    print(name, "engine", erow.view(np.uint32).tolist(), "batch", brow.view(np.uint32).tolist())
+    assert erow[20] == 1.0 and erow[0] == buf.particle_count
+    if pokes:
+        assert erow[4] == 2                  # the poked particles are counted and left out
+    sr.assert_rows_equal(erow, brow, name)
+
+
 READ_ONLY = [("tiled grid", lambda sb: sc.case_break(sb), dict(collision_mode=GRID, path=TILED, tile_particles=256)),
              ("blocked", lambda sb: sc.case_break(sb), dict(collision_mode=OFF, path=TILED)),
              ("hybrid", None, dict(collision_mode=GRID))]
