@@ -859,6 +859,65 @@ sb_status sb_batch_cut_device(sb_batch *b, uint32_t flags, const void *device_sh
                               void *device_hit_u8 /* [n_scenes][max_beams] or NULL */,
                               void *device_counts_i32 /* [n_scenes][SB_CUT_COUNT_WORDS] int32 or NULL */);
 
+/* ---- adding beams on the device ("welds"), the inverse of a cut ----
+ * sb_batch_add_beams_device -- the planner's "glue these two": every scene gets its own k rows of new beams in ONE launch.
+ * device_rows is [n_scenes][k] sb_batch_new_beam, k <= SB_BATCH_ADD_MAX; contacts' pair list holds exactly the (a, b) a row wants.
+ *
+ * DEFINITION.  Scene i processes its k rows in row order.  Row j is decided in four steps.
+ * 1. Empty.  a < 0 gives EMPTY.  The row is not counted.
+ * 2. Invalid.  The row is INVALID if any of these hold: the scene was never uploaded; a or b is >= max_particles; a == b;
+ *    either endpoint is not the data index of a particle slot < P; reserved != 0; the resolved length is not a finite number
+ *    > 0.  The length is resolved as follows.  The current distance is sb_length(pb.x - pa.x, pb.y - pa.y) on the current
+ *    particle records; these are the beam phase's own expressions.  With LENGTH_CURRENT the resolved length is the current
+ *    distance.  Otherwise it is the row's length.  A distance of 0 or NaN under LENGTH_CURRENT is therefore INVALID.  spring,
+ *    damp, yield_strain and strain_break_limit are taken verbatim, as an upload takes them.
+ * 3. Joined.  This step applies only with SKIP_JOINED.  The row is JOINED in either of these cases: a live beam slot
+ *    (< beam_i_c; a pending break flag still joins) connects the unordered pair {a, b}; an earlier row of this call, not EMPTY,
+ *    INVALID or JOINED, names the same unordered pair.
+ * 4. Room.  The rows that survive are the candidates.  Their rank r is the number of candidates before them.  A candidate is
+ *    added when beam_i_c + r < max_beams and there is an r-th free beam data index.  Otherwise it is FULL.  Room is first come,
+ *    first served, so the duplicate rule above cannot depend on it.
+ * Free data index.  A beam data index d is free when balive[d] == 0 in the CURRENT state blob AND in the RESET state blob
+ * (balive[d] == 1 iff a live slot of that state's beam mapping names d: DESIGN.md 5.24).  No live slot of either state's mapping
+ * names such an index, so its constant rows may be rewritten without corrupting a later reset.  An index a delete pass freed
+ * becomes reusable once a checkpoint has made that removal part of the reset state.  An addition that a reset undoes frees its
+ * index again: episodes of weld, reset, weld do not leak capacity.
+ * What the r-th added beam writes.  It takes the r-th smallest free data index d and beam slot beam_i_c + r.  Constant blob:
+ * endpoint SLOTS of a and b (through the inverse of the particle mapping), the material row {length, spring, damp, yield, limit,
+ * 1 / length} with one IEEE divide, the upload's own, and "holds a beam of the upload" = 1.  State blob: the beam's state
+ * {target_length = length, last_length = current distance, strain 0, stress 0}, beam mapping [slot] = d, alive [d] = 1, the slot's
+ * pending break bit CLEARED.  After all rows metadata.beam_i_c += added.  The reset state and its beam count are untouched.
+ * Outputs.  result[j] is d for an added row, else the code.  counts = {added, invalid, joined, full}.  With DRY_RUN, result and
+ * counts are the real call's and nothing else is written.
+ *
+ * CONSEQUENCES.  Every later launch sees the beam as if it had been uploaded: frame, reports, render, read_state_device,
+ * write_beams_device, load_scene, cut and fork.  checkpoint keeps it and reset removes it.  After such a reset the index reads
+ * "of the upload" = 1, alive = 0: sb_batch_summary_device's word 2 counts it as "removed", like a beam a delete pass removed;
+ * reusing an index lowers that word by one.  A scene with no candidate row (or none that finds room) is left bit for bit as it was.
+ *
+ * Only ENQUEUES on the batch's stream.  Either output may be NULL.  Errors, before anything touches a device: SB_ERR_INVALID for a
+ * NULL handle, unknown flag bits, k > SB_BATCH_ADD_MAX, NULL rows with k > 0, a pointer that is not 4-byte aligned.  k == 0 is
+ * SB_OK: the counts rows are still written, as zeros.  sb_batch_get_info: "add_beams_kernel_vgprs",
+ * "add_beams_kernel_scratch_bytes". */
+typedef struct sb_batch_new_beam { /* 32 bytes */
+    int32_t a, b;            /* particle DATA indices (what state_tensors / contacts use); a < 0: empty row */
+    float length;            /* rest length; see SB_BATCH_ADD_LENGTH_CURRENT */
+    float spring, damp, yield_strain, strain_break_limit;
+    uint32_t reserved;       /* 0 */
+} sb_batch_new_beam;
+#define SB_BATCH_ADD_MAX 64u            /* rows per scene and call */
+#define SB_BATCH_ADD_DRY_RUN 1u
+#define SB_BATCH_ADD_LENGTH_CURRENT 2u  /* length := the endpoints' current distance */
+#define SB_BATCH_ADD_SKIP_JOINED 4u
+#define SB_BATCH_ADD_EMPTY (-1)
+#define SB_BATCH_ADD_INVALID (-2)
+#define SB_BATCH_ADD_JOINED (-3)
+#define SB_BATCH_ADD_FULL (-4)
+#define SB_BATCH_ADD_COUNT_WORDS 4u     /* added, invalid, joined, full */
+sb_status sb_batch_add_beams_device(sb_batch *b, uint32_t flags, const void *device_rows /* [n_scenes][k] sb_batch_new_beam */, uint32_t k,
+                                    void *device_result_i32 /* [n_scenes][k] int32 or NULL */,
+                                    void *device_counts_i32 /* [n_scenes][SB_BATCH_ADD_COUNT_WORDS] int32 or NULL */);
+
 /* ---- per-scene summary rows and multi-frame rollouts on the device ----
  * sb_batch_summary_device -- one row of SB_BATCH_SUMMARY_WORDS floats per scene into device_out_f32[n_scenes][SB_BATCH_SUMMARY_WORDS],
  * in ONE launch: what a done-test or a score reads of a scene without exporting its state.  It only ENQUEUES and only READS the

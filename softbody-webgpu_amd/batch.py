@@ -35,6 +35,28 @@ CONTACT_TOUCH_FIELDS = ("touching", "touching_other_body", "walls", "first_partn
 CONTACT_COUNT_FIELDS = ("pairs", "other_body_pairs", "wall_particles", "touching_particles")
 CONTACTS_OTHER_BODY = 1                               # SB_BATCH_CONTACTS_OTHER_BODY
 WALL_LEFT, WALL_RIGHT, WALL_LOW, WALL_HIGH = 1, 2, 4, 8   # SB_BATCH_WALL_*: the bits of a touch row's "walls"
+ADD_MAX = 64                                          # SB_BATCH_ADD_MAX: rows per scene and call of add_beams()
+ADD_ROW_WORDS = 8                                     # sb_batch_new_beam: {a, b, length, spring, damp, yield_strain, strain_break_limit, 0}
+ADD_DRY_RUN, ADD_LENGTH_CURRENT, ADD_SKIP_JOINED = 1, 2, 4   # SB_BATCH_ADD_*: the flags
+ADD_EMPTY, ADD_INVALID, ADD_JOINED, ADD_FULL = -1, -2, -3, -4   # SB_BATCH_ADD_*: what add_beams()'s result holds where no beam was added
+ADD_COUNT_FIELDS = ("added", "invalid", "joined", "full")     # the counts of add_beams(), in order (SB_BATCH_ADD_COUNT_WORDS of them)
+
+
+def new_beam_rows(pairs, spring, damp, yield_strain, strain_break_limit, length=None):
+    """Rows for BatchEngine.add_beams() from an int32 torch tensor [N, k, 2] of particle DATA index pairs -- contacts()'s `pairs`
+    as it is: a row whose first index is negative stays an empty row -- packed with torch ops on the pairs' device: an int32
+    tensor [N, k, 8] in sb_batch_new_beam's layout (the floats as their bits).  spring, damp, yield_strain, strain_break_limit
+    and length: a number, or a tensor that broadcasts to [N, k]; length=None fills 0 and is meant for length_current=True."""
+    import torch
+    if not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int32 or pairs.dim() != 3 or pairs.shape[2] != 2:
+        raise ValueError("new_beam_rows: pairs must be an int32 torch tensor [N, k, 2]")
+    n, k = pairs.shape[0], pairs.shape[1]
+    rows = torch.zeros((n, k, ADD_ROW_WORDS), dtype=torch.int32, device=pairs.device)
+    rows[:, :, 0:2] = pairs
+    for col, x in ((2, 0.0 if length is None else length), (3, spring), (4, damp), (5, yield_strain), (6, strain_break_limit)):
+        f = torch.as_tensor(x, dtype=torch.float32, device=pairs.device).expand(n, k).contiguous()
+        rows[:, :, col] = f.view(torch.int32)
+    return rows
 
 
 class SbBatchOptions(ctypes.Structure):
@@ -78,6 +100,7 @@ def load_library():
     L.sb_batch_checkpoint_device.argtypes = [vp, vp]
     L.sb_batch_write_beams_device.argtypes = [vp, vp, u32]
     L.sb_batch_cut_device.argtypes = [vp, u32, vp, u32, vp, vp]
+    L.sb_batch_add_beams_device.argtypes = [vp, u32, vp, u32, vp, vp]
     L.sb_batch_summary_device.argtypes = [vp, vp]
     L.sb_batch_rollout_device.argtypes = [vp, u32, vp, vp]
     L.sb_batch_bodies_device.argtypes = [vp, vp, vp, vp]
@@ -422,6 +445,41 @@ class BatchEngine:
         vp = ctypes.c_void_p
         self._ordered(True, lambda: load_library().sb_batch_cut_device(self._h, CUT_DRY_RUN if dry_run else 0, vp(words.data_ptr() if k else None),
                                                                        k, vp(ptrs[0]), vp(ptrs[1])))
+        return outs[0], outs[1]
+
+    # ---- adding beams (sb_batch_add_beams_device)
+    def add_beams(self, rows, *, length_current=False, skip_joined=False, dry_run=False, result=None, counts=None):
+        """The inverse of cut(): every scene gets its own k new beams ("welds") in one launch.  `rows` is [n_scenes, k, 8],
+        k <= ADD_MAX, in sb_batch_new_beam's layout {a, b, length, spring, damp, yield_strain, strain_break_limit, 0} -- a and b
+        particle DATA indices as integers, the five floats as their bits: an int32 or float32 (bits) torch tensor on the batch's
+        device (new_beam_rows() packs one from contacts()'s pairs), or a tuple (device pointer, k).
+        include/softbody.h states the rule row by row: a < 0 is an empty row; a row that names no two particles of the scene, has
+        a nonzero last word or a length that is no finite number > 0 is ADD_INVALID; with skip_joined a pair that a live beam or
+        an earlier row of the call already joins is ADD_JOINED; a row that finds no free beam slot or data index is ADD_FULL.
+        length_current: the rest length is the endpoints' current distance.  dry_run: report only.  Returns (result, counts):
+        result int32 [n_scenes, k], the new beam's DATA index or the code; counts int32 [n_scenes, 4] (ADD_COUNT_FIELDS).  An
+        added beam is from then on a beam of the scene as if uploaded; checkpoint() keeps it, reset() removes it, fork() copies
+        it.  result / counts: a device pointer (int) or a contiguous int32 torch tensor to write into.  Only enqueues."""
+        import torch
+        n = self.n_scenes
+        if isinstance(rows, tuple):
+            ptr, k = int(rows[0]), int(rows[1])
+            is_tensor = False
+        else:
+            if not isinstance(rows, torch.Tensor) or rows.dtype not in (torch.int32, torch.float32):
+                raise ValueError("add_beams: rows must be an int32 / float32 torch tensor [n_scenes, k, 8] or (device pointer, k)")
+            if rows.dim() != 3 or rows.shape[0] != n or rows.shape[2] != ADD_ROW_WORDS or rows.shape[1] > ADD_MAX:
+                raise ValueError("add_beams: rows must be [n_scenes = %d, k <= %d, 8], not %s" % (n, ADD_MAX, tuple(rows.shape)))
+            k = int(rows.shape[1])
+            ptr, is_tensor = self._device_buffer("add_beams: rows", rows, None, n * k * ADD_ROW_WORDS * 4)
+        if not 0 <= k <= ADD_MAX:
+            raise ValueError("add_beams: k is %d, not in 0 .. %d" % (k, ADD_MAX))
+        outs, ptrs, tensors = self._bind("add_beams", [("result", result, True, (n, k), "int32"),
+                                                       ("counts", counts, True, (n, len(ADD_COUNT_FIELDS)), "int32")])
+        flags = (ADD_DRY_RUN if dry_run else 0) | (ADD_LENGTH_CURRENT if length_current else 0) | (ADD_SKIP_JOINED if skip_joined else 0)
+        vp = ctypes.c_void_p
+        self._ordered(tensors or is_tensor, lambda: load_library().sb_batch_add_beams_device(self._h, flags, vp(ptr if k else None), k,
+                                                                                             vp(ptrs[0]), vp(ptrs[1])))
         return outs[0], outs[1]
 
     # ---- statistics per body (sb_batch_body_summary_device; DESIGN.md 5.16)

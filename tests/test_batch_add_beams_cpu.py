@@ -1,0 +1,210 @@
+"""sb_batch_add_beams_device without a GPU: softbody.h declares it and the library exports it, batch.py binds it, the row struct is
+32 bytes and the SB_BATCH_ADD_* constants agree between the header and Python, the argument checks come before any device call;
+tests/batch_add_beams_ref.py on every case of tests/batch_add_beams_cases.py: the codes are the ones the case is built for, the
+edited buffers load into the oracle, stay finite over two frames and keep the welded beams alive; csrc/sb_batch_add_math.h (built
+on the host, under sanitizers) agrees with the restatement's row verdict."""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import batch_add_beams_cases as cases
+import batch_add_beams_ref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "softbody-webgpu_amd", "csrc")
+ERR_INVALID = 1
+SYMBOL = "sb_batch_add_beams_device"
+
+
+def test_header_declares_and_library_exports(sb):
+    assert SYMBOL in sb.engine.declared_symbols()
+    L = sb.engine.load_library()
+    assert hasattr(L, SYMBOL) and L.sb_abi_version() == 1
+    B = sb.batch.load_library()
+    vp, u32 = ctypes.c_void_p, ctypes.c_uint32
+    assert B.sb_batch_add_beams_device.argtypes == [vp, u32, vp, u32, vp, vp] and B.sb_batch_add_beams_device.restype is ctypes.c_int
+    assert callable(sb.BatchEngine.add_beams) and callable(sb.batch.new_beam_rows)
+
+
+def test_struct_and_constants(sb):
+    src = open(sb.engine.HEADER_PATH).read()
+    assert "#define SB_ABI_VERSION 1\n" in src
+    m = re.search(r"typedef struct sb_batch_new_beam \{(.*?)\} sb_batch_new_beam;", src, re.S)
+    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
+    fields = []
+    for ctype, names in re.findall(r"(int32_t|uint32_t|float)\s+([^;]+);", body):
+        fields += [(ctype, n.strip()) for n in names.split(",")]
+    assert fields == [("int32_t", "a"), ("int32_t", "b"), ("float", "length"), ("float", "spring"), ("float", "damp"), ("float", "yield_strain"),
+                      ("float", "strain_break_limit"), ("uint32_t", "reserved")]
+    assert 4 * len(fields) == 32 == 4 * sb.batch.ADD_ROW_WORDS == 4 * ref.ROW_WORDS
+    got = dict(re.findall(r"#define SB_BATCH_ADD_(\w+)\s+\(?(-?\d+)u?\)?", src))
+    b = sb.batch
+    assert {k: int(v) for k, v in got.items()} == {
+        "MAX": b.ADD_MAX, "DRY_RUN": b.ADD_DRY_RUN, "LENGTH_CURRENT": b.ADD_LENGTH_CURRENT, "SKIP_JOINED": b.ADD_SKIP_JOINED,
+        "EMPTY": b.ADD_EMPTY, "INVALID": b.ADD_INVALID, "JOINED": b.ADD_JOINED, "FULL": b.ADD_FULL, "COUNT_WORDS": len(b.ADD_COUNT_FIELDS)}
+    assert (b.ADD_MAX, b.ADD_DRY_RUN, b.ADD_LENGTH_CURRENT, b.ADD_SKIP_JOINED) == (64, 1, 2, 4)
+    assert (b.ADD_EMPTY, b.ADD_INVALID, b.ADD_JOINED, b.ADD_FULL) == (-1, -2, -3, -4) == (ref.EMPTY, ref.INVALID, ref.JOINED, ref.FULL)
+    assert b.ADD_COUNT_FIELDS == ("added", "invalid", "joined", "full")
+    assert (ref.DRY_RUN, ref.LENGTH_CURRENT, ref.SKIP_JOINED) == (b.ADD_DRY_RUN, b.ADD_LENGTH_CURRENT, b.ADD_SKIP_JOINED)
+    for needle in ("add_beams_kernel_vgprs", "add_beams_kernel_scratch_bytes"):
+        assert needle in src, needle
+
+
+def test_null_handle_is_refused_without_a_device(sb):
+    """every INVALID case of the header on a NULL handle: nothing may touch a device on the way"""
+    L = sb.batch.load_library()
+    p = ctypes.c_void_p(4096)
+    for flags, rows, k, result, counts in ((0, p, 1, None, None), (8, p, 1, None, None), (0, p, 65, None, None), (0, None, 1, None, None),
+                                           (0, ctypes.c_void_p(4097), 1, None, None), (0, p, 1, ctypes.c_void_p(4098), None),
+                                           (0, p, 1, None, ctypes.c_void_p(4099)), (0, None, 0, None, None)):
+        assert L.sb_batch_add_beams_device(None, flags, rows, k, result, counts) == ERR_INVALID
+
+
+# ---------------------------------------------------------------- the restatement on the cases
+
+def oracle_run(oracle, buf, frames=2, mode=1):
+    r = oracle.OracleEngine(1000.0, 10.0, 64, buf.layout, mode, threads=2)
+    r.write_buffers(buf)
+    for _ in range(frames):
+        r.frame()
+    out = r.load_buffers(buf.copy())
+    assert np.isfinite(out.particles[buf.mapping[:buf.particle_count].astype(np.int64)]).all()
+    return out
+
+
+def check_case(oracle, case, flags, breaking=None):
+    total = 0
+    for i, (edited, result, counts) in enumerate(cases.expected(case, flags)):
+        if edited is None:
+            continue
+        added = [int(d) for d in result if d >= 0]
+        assert len(added) == counts[0] and edited.beam_count == case["bufs"][i].beam_count + counts[0]
+        assert sum(counts) == int((case["rows"][i][:, 0] >= 0).sum())
+        out = oracle_run(oracle, edited)
+        alive = ref.alive_set(out)
+        for j, d in enumerate(result):
+            if d >= 0:
+                assert alive[d] == ((i, j) != breaking), (i, j, d)
+        total += counts[0]
+    return total
+
+
+@pytest.mark.parametrize("flags", [0, ref.LENGTH_CURRENT | ref.SKIP_JOINED])
+def test_default_case(sb, oracle, flags):
+    case = cases.default_case(sb)
+    assert check_case(oracle, case, flags, None if flags else case["breaking"]) >= 40
+    exp = cases.expected(case, flags)
+    assert all(r[1][i % cases.K] == ref.EMPTY and r[1][(i + 3) % cases.K] == ref.INVALID for i, r in enumerate(exp))
+    assert len({r[1].tobytes() for r in exp}) == len(exp), "every scene its own rows"
+
+
+def test_codes_case(sb, oracle):
+    case, _ = cases.codes_case(sb)
+    E, I, J = ref.EMPTY, ref.INVALID, ref.JOINED
+    (_, res, counts), = cases.expected(case, ref.SKIP_JOINED)
+    assert res.tolist() == [I, I, I, I, I, I, I, I, I, 299, J, J, 300, J, E, I] and counts == [2, 10, 3, 0]
+    (_, res, counts), = cases.expected(case, 0)
+    assert res.tolist() == [I, I, I, I, I, I, I, I, I, 299, 300, 301, 302, 303, E, I] and counts == [5, 10, 0, 0]
+    (_, res, counts), = cases.expected(case, ref.SKIP_JOINED | ref.LENGTH_CURRENT)
+    assert res.tolist() == [I, I, I, I, I, 299, 300, 301, 302, I, J, J, 303, J, E, I] and counts == [5, 7, 3, 0]
+    assert check_case(oracle, case, ref.SKIP_JOINED, breaking=(0, 9)) == 2   # (a beam of rest length 25 between coincident ends breaks at once)
+
+
+def test_room_and_sparse_cases(sb, oracle):
+    case = cases.room_case(sb)
+    exp = cases.expected(case, 0)
+    F_ = ref.FULL
+    assert exp[0][1].tolist() == [36, 37, 38, 39, F_, F_, F_, F_] and exp[0][2] == [4, 0, 0, 4]
+    assert exp[1][1].tolist() == [F_] * 8 and exp[1][2] == [0, 0, 0, 8]
+    assert exp[2][0] is None and exp[2][1].tolist() == [ref.INVALID] * 8 and exp[2][2] == [0, 8, 0, 0]
+    assert check_case(oracle, case, 0) == 4
+    case = cases.sparse_case(sb)
+    (edited, res, counts), = cases.expected(case, 0)
+    used = set(((7 * np.arange(30) + 3) % 64).tolist())
+    free = [d for d in range(64) if d not in used]
+    assert res.tolist() == free[:5] == [4, 5, 6, 11, 12] and counts == [5, 0, 0, 0]
+    assert edited.mapping[32 + 30:32 + 35].tolist() == res.tolist()
+    assert check_case(oracle, case, 0) == 5
+    # an index alive in the reset state only is not free
+    ra = ref.alive_set(case["bufs"][0])
+    ra[[4, 6]] = True
+    assert ref.add_ref(case["bufs"][0], case["rows"][0], 0, ra)[1].tolist() == [5, 11, 12, 13, 18]
+
+
+def test_touching_case_welds_into_one_body(sb, oracle):
+    case = cases.touching_case(sb)
+    buf = case["bufs"][0]
+    rows = ref.pack([(2, 4, 0.0) + cases.MAT, (3, 5, 0.0) + cases.MAT, (-1, -1, 0.0) + cases.MAT])
+    edited, res, counts = ref.add_ref(buf, rows, ref.LENGTH_CURRENT | ref.SKIP_JOINED, ref.alive_set(buf))
+    assert res.tolist() == [12, 13, ref.EMPTY] and counts == [2, 0, 0, 0]
+    assert edited.beams["length"][12:14].tolist() == [15.0, 15.0] == edited.beams["last_length"][12:14].tolist()
+    again = ref.add_ref(edited, rows, ref.LENGTH_CURRENT | ref.SKIP_JOINED, ref.alive_set(buf))
+    assert again[1].tolist() == [ref.JOINED, ref.JOINED, ref.EMPTY] and again[2] == [0, 0, 2, 0]
+    oracle_run(oracle, edited)
+
+
+# ---------------------------------------------------------------- the row verdict: header == restatement
+
+@pytest.mark.parametrize("san", ["asan", "tsan"])
+def test_header_equals_the_restatement_under_sanitizers(sb, tmp_path, san):
+    """csrc/sb_batch_add_math.h on the host (tests/batch_add_check.cpp, `make hostcheck`) == batch_add_beams_ref.row_verdict and
+    .distance on the rows of the codes case under every flag, and on random rows with special lengths and positions"""
+    exe = os.path.join(CSRC, "hostcheck_build", "batch_add_check_" + san)
+    p = subprocess.run(["make", "-C", CSRC, os.path.join("hostcheck_build", "batch_add_check_" + san)], capture_output=True, text=True)
+    assert p.returncode == 0, p.stdout + p.stderr
+    rng = np.random.default_rng(11)
+    case, _ = cases.codes_case(sb)
+    buf = case["bufs"][0]
+    maxP = buf.max_particles
+    holds = np.zeros(maxP, dtype=bool)
+    holds[buf.mapping[:buf.particle_count].astype(np.int64)] = True
+    recs = []
+    for flags in (0, 2, 4, 6, 3):
+        for row in case["rows"][0]:
+            a, b = int(row[0]), int(row[1])
+            pa = buf.particles[a, :2] if 0 <= a < maxP else np.zeros(2, "f4")
+            pb = buf.particles[b, :2] if 0 <= b < maxP else np.zeros(2, "f4")
+            recs.append((row, flags, maxP, 1, int(0 <= a < maxP and holds[a]), int(0 <= b < maxP and holds[b]), pa, pb))
+    special = np.asarray([0.0, -0.0, np.nan, np.inf, -np.inf, 1e-45, 3.4028235e38, -1.0, 1.0], "f4")
+    for _ in range(3000):
+        row = np.zeros(8, np.int32)
+        row[0:2] = rng.integers(-2, 12, size=2)
+        row[2] = (special[rng.integers(len(special))] if rng.random() < 0.5 else np.float32(rng.normal() * 10)).view(np.int32)
+        row[7] = int(rng.random() < 0.1)
+        pa, pb = (rng.normal(size=2) * (1e20 if rng.random() < 0.1 else 30)).astype("f4"), (rng.normal(size=2) * 30).astype("f4")
+        if rng.random() < 0.15:
+            pb = pa.copy()
+        if rng.random() < 0.05:
+            pb[0] = np.nan
+        recs.append((row, int(rng.integers(0, 8)), 10, int(rng.random() < 0.9), int(rng.random() < 0.9), int(rng.random() < 0.9), pa, pb))
+    words = np.zeros((len(recs), 17), "<u4")
+    want = []
+    for i, (row, flags, mp, loaded, ha, hb, pa, pb) in enumerate(recs):
+        words[i, :8] = row.view(np.uint32)
+        words[i, 8:13] = (flags, mp, loaded, ha, hb)
+        words[i, 13:15], words[i, 15:17] = np.asarray(pa, "f4").view(np.uint32), np.asarray(pb, "f4").view(np.uint32)
+        current = ref.distance(pa, pb)
+        h = np.zeros(max(mp, 1), dtype=bool)
+        a, b = int(row[0]), int(row[1])
+        if 0 <= a < mp:
+            h[a] = bool(ha)
+        if 0 <= b < mp and b != a:
+            h[b] = bool(hb)
+        code, length = ref.row_verdict(row, flags, mp, bool(loaded), h, current)
+        want.append("%d %d %d" % (code, int(np.float32(length).view(np.uint32)), int(np.float32(current).view(np.uint32))))
+    path = str(tmp_path / "records.bin")
+    words.tofile(path)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1",
+               TSAN_OPTIONS="halt_on_error=1")
+    r = subprocess.run([exe, path], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0 and "Sanitizer" not in r.stderr, r.stderr[-4000:]
+    got = r.stdout.split("\n")[:-1]
+    assert len(got) == len(want)
+    bad = [i for i, (g, w) in enumerate(zip(got, want)) if g != w]
+    assert not bad, [(i, got[i], want[i]) for i in bad[:5]]
+    codes = [int(w.split()[0]) for w in want]
+    assert min(codes.count(c) for c in (0, ref.EMPTY, ref.INVALID)) > 100
