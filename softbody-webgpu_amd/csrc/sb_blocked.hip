@@ -531,7 +531,13 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
                 s_fx[q] = 0;
                 s_fy[q] = 0;
                 const float2 p_old = particle.p;
-                if (!((SB_BK_ABLATE & 2) && prm.time_step >= 0.0f)) sb_particle_finish<PLAIN>(prm, c, particle, fx, fy);
+                if (!((SB_BK_ABLATE & 2) && prm.time_step >= 0.0f)) {
+                    // sb_particle_finish with the walls behind one question per wave: has any lane left [lo, hi] (a NaN
+                    // coordinate counts)?  Almost never -- and then two clamps, two compares and two exec-mask regions per slot
+                    // are skipped, a quarter of the slot's vector instructions; a wave that says yes runs them as they are.
+                    sb_particle_integrate<PLAIN>(prm, c, particle, fx, fy);
+                    if (!sb_wave_all(sb_inside_walls(prm, particle))) sb_particle_walls(prm, c, particle);
+                }
                 if (TRACK && i < (int)SB_BK_OWNP) { // (as sb_substep_tiled measures it: sqrt(2) x the larger component)
                     const float ddx = particle.p.x - p_old.x, ddy = particle.p.y - p_old.y;
                     const float m = fmaxf(sb_abs(ddx - track_cx), sb_abs(ddy - track_cy)) * 1.4142137f;

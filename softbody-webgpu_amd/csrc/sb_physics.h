@@ -1385,35 +1385,38 @@ SB_DEV void sb_collide_slow(const SbGrid &g, bool fresh, const SbParams &prm, fl
     }
 }
 
-// everything after the collision loop, compute.wgsl:171-199; fx,fy are the complete fixed-point
-// beam force sums for this particle (the atomicExchange results of :184-185).
-// PLAIN (compile time; the host launches that variant when the constants of the call say so): drag_exp == 2 and no mouse
-// grab -- the reference's defaults (engineMapping.ts:271; mouse_active is 0 unless a button is down).  The general form
-// dispatches pow() over five cases and tests the mouse per particle: all uniform, all scalar branches, about a dozen of them
-// per particle in a kernel whose scalar instructions were a quarter of its vector ones (r02 counters).  Same bits: the case
-// pow() takes for y == 2 is x * x.
-template <bool PLAIN = false>
-SB_DEV void sb_particle_finish(const SbParams &prm, const SbConsts &c, SbParticle &particle,
-                               int32_t fx, int32_t fy)
+// the drag term, compute.wgsl:174-176, for a particle whose speed vl is > 0 (inv_vl = 1 / vl)
+template <bool PLAIN>
+SB_DEV void sb_particle_drag(const SbConsts &c, SbParticle &particle, float inv_vl)
 {
-    const float particle_force_scale = 65536.0f;
+    float nx = particle.v.x * inv_vl, ny = particle.v.y * inv_vl;
+    float px = PLAIN ? particle.v.x * particle.v.x : sb_pow(sb_abs(particle.v.x), c.drag_exp); // (|x| * |x| == x * x, bit for bit)
+    float py = PLAIN ? particle.v.y * particle.v.y : sb_pow(sb_abs(particle.v.y), c.drag_exp);
+    particle.a.x -= c.drag_coeff * px * nx;
+    particle.a.y -= c.drag_coeff * py * ny;
+}
+
+// compute.wgsl:171-188: forces, velocity, position; leaves the acceleration zero and the position unclamped.
+// sb_particle_walls (below) is the rest of the particle's substep; sb_particle_finish is the two in a row.
+template <bool PLAIN = false>
+SB_DEV void sb_particle_integrate(const SbParams &prm, const SbConsts &c, SbParticle &particle,
+                                  int32_t fx, int32_t fy)
+{
+    constexpr float particle_force_scale = 65536.0f;
     particle.a.x += c.gravity_x; // :172
     particle.a.y += c.gravity_y;
     const float v2 = particle.v.x * particle.v.x + particle.v.y * particle.v.y;
-    float vl, inv_vl = 0.0f;
-    if (sb_wave_all(sb_in_sqrt_gate(v2) || v2 == 0.0f)) { // (a particle at rest has no drag: nothing to take a root of)
-        vl = v2 == 0.0f ? 0.0f : sb_sqrt_gated(v2);
-        inv_vl = sb_rcp_gated(vl); // unused (infinite) at rest
+    if (__builtin_expect(sb_wave_all(sb_in_sqrt_gate(v2) || v2 == 0.0f), 1)) { // (a particle at rest has no drag: nothing to take a root of)
+        // In here a lane is at rest or inside the gate, where the root is at least 2^-45: "vl > 0" (:174) IS "v2 != 0", the
+        // compare the gate has already made.  So the at-rest lanes are simply masked out of the whole chain -- no select to
+        // keep their rsq(0) = inf out of vl, no second compare on the root.
+        if (v2 != 0.0f) {
+            const float vl = sb_sqrt_gated(v2);
+            sb_particle_drag<PLAIN>(c, particle, sb_rcp_gated(vl));
+        }
     } else {
-        vl = sb_sqrt(v2);
-        if (vl > 0.0f) inv_vl = sb_div(1.0f, vl);
-    }
-    if (vl > 0.0f) { // :174-176
-        float nx = particle.v.x * inv_vl, ny = particle.v.y * inv_vl;
-        float px = PLAIN ? particle.v.x * particle.v.x : sb_pow(sb_abs(particle.v.x), c.drag_exp); // (|x| * |x| == x * x, bit for bit)
-        float py = PLAIN ? particle.v.y * particle.v.y : sb_pow(sb_abs(particle.v.y), c.drag_exp);
-        particle.a.x -= c.drag_coeff * px * nx;
-        particle.a.y -= c.drag_coeff * py * ny;
+        const float vl = sb_sqrt(v2);
+        if (vl > 0.0f) sb_particle_drag<PLAIN>(c, particle, sb_div(1.0f, vl)); // :174-176
     }
     particle.a.x += c.applied_force_x * c.user_strength; // :178
     particle.a.y += c.applied_force_y * c.user_strength;
@@ -1424,14 +1427,33 @@ SB_DEV void sb_particle_finish(const SbParams &prm, const SbConsts &c, SbParticl
             particle.a.y += (c.mouse_vel_y - particle.v.y) * c.user_strength - c.gravity_y;
         }
     }
-    particle.a.x += sb_div((float)fx, particle_force_scale); // :184-185
-    particle.a.y += sb_div((float)fy, particle_force_scale);
+    // :184-185 divide by the force scale 65536.  (float)fx is zero or at least 1 in magnitude and 2^-16 is exact, so the product
+    // below is exact (no rounding, never subnormal): the IEEE quotient, bit for bit, in one multiplication -- which is also
+    // what the compiler made of the division (profiles/particle_phase_isa.txt); spelled out so that it does not rest on that.
+    static_assert(particle_force_scale * 0x1p-16f == 1.0f, "the reciprocal of the force scale");
+    particle.a.x += (float)fx * 0x1p-16f;
+    particle.a.y += (float)fy * 0x1p-16f;
     particle.v.x += particle.a.x * prm.time_step; // :186
     particle.v.y += particle.a.y * prm.time_step;
     particle.p.x += particle.v.x * prm.time_step; // :187
     particle.p.y += particle.v.y * prm.time_step;
     particle.a.x = 0.0f; // :188
     particle.a.y = 0.0f;
+}
+
+// true when the walls (sb_particle_walls) leave this particle as it is: both coordinates inside [lo, hi], where
+// sb_clamp returns its argument itself and neither branch of :191-198 is taken.  False for a NaN coordinate, which
+// compares unequal to its clamp and takes both.  (May be false for a particle the walls leave alone when lo > hi: the
+// test only ever sends too many particles through the walls, never too few.)
+SB_DEV bool sb_inside_walls(const SbParams &prm, const SbParticle &particle)
+{
+    const float lo = prm.particle_radius, hi = prm.bounds_size - prm.particle_radius;
+    return particle.p.x >= lo && particle.p.x <= hi && particle.p.y >= lo && particle.p.y <= hi;
+}
+
+// compute.wgsl:190-199: the walls, for a particle sb_particle_integrate has just moved
+SB_DEV void sb_particle_walls(const SbParams &prm, const SbConsts &c, SbParticle &particle)
+{
     float lo = prm.particle_radius, hi = prm.bounds_size - prm.particle_radius; // :190
     float cx = sb_clamp(particle.p.x, lo, hi), cy = sb_clamp(particle.p.y, lo, hi);
     if (particle.p.x != cx) { // :191-194
@@ -1446,4 +1468,19 @@ SB_DEV void sb_particle_finish(const SbParams &prm, const SbConsts &c, SbParticl
     }
     particle.p.x = cx; // :199
     particle.p.y = cy;
+}
+
+// everything after the collision loop, compute.wgsl:171-199; fx,fy are the complete fixed-point
+// beam force sums for this particle (the atomicExchange results of :184-185).
+// PLAIN (compile time; the host launches that variant when the constants of the call say so): drag_exp == 2 and no mouse
+// grab -- the reference's defaults (engineMapping.ts:271; mouse_active is 0 unless a button is down).  The general form
+// dispatches pow() over five cases and tests the mouse per particle: all uniform, all scalar branches, about a dozen of them
+// per particle in a kernel whose scalar instructions were a quarter of its vector ones (r02 counters).  Same bits: the case
+// pow() takes for y == 2 is x * x.
+template <bool PLAIN = false>
+SB_DEV void sb_particle_finish(const SbParams &prm, const SbConsts &c, SbParticle &particle,
+                               int32_t fx, int32_t fy)
+{
+    sb_particle_integrate<PLAIN>(prm, c, particle, fx, fy);
+    sb_particle_walls(prm, c, particle);
 }
