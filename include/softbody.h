@@ -532,6 +532,44 @@ sb_status sb_cut_device(sb_engine *e, const sb_cut_options *opts, const void *de
 sb_status sb_cut(sb_engine *e, const sb_cut_options *opts, const sb_cut_shape *shapes, uint32_t n_shapes, uint8_t *hit /* [max_beams] or NULL */,
                  int64_t *counts /* [SB_CUT_COUNT_WORDS] or NULL */);
 
+/* ---- the beam graph of the whole scene: edge list and CSR adjacency on the device ----
+ * After a cut on the device, or frames in which beams broke, which beams are left and who hangs on whom -- without reading three
+ * million beams back.  The definition is sb_batch_graph_device's (below), word for word, on what sb_load_buffers would return at
+ * that point of the stream: nodes are the particles at particle DATA indices, edges the LISTED beams at beam DATA indices.  A beam
+ * is LIVE by sb_bodies' rule: a caller beam slot of the latest upload that neither a delete pass nor a plan-keeping upload has
+ * removed; a pending break flag still connects.  A live beam is listed unless SB_GRAPH_SKIP_PENDING is set and its pending break
+ * flag is raised (what the next delete pass will leave).  Half-edges, sides and degrees as there.
+ *   ends[d]     int32 {a, b}, the particle data indices of the record's particle_pair, at beam data index d < max_beams; {-1, -1}
+ *               where d is not a listed beam.  (The caller holds the upload: materials are not exported.)
+ *   row_ptr     int64 [max_particles + 1]: the exclusive prefix sum of the degrees over particle data indices; always complete.
+ *   nbr         int32 [max_half_edges][2]: {neighbour, beam data index} by particle, inside a particle by ascending beam data
+ *               index (a beam from p to p: side 0, then side 1): a unique order, the same bits on every run.  The first
+ *               max_half_edges rows of that list are written, {-1, -1} behind the last half-edge; rows at or behind
+ *               max_half_edges are not written.  nbr without row_ptr, or with max_half_edges == 0: SB_ERR_INVALID.
+ *   counts      int64 [SB_GRAPH_COUNT_WORDS]: 0 listed beams, 1 particles of degree >= 1, 2 the largest degree, 3 the smallest
+ *               data index of a particle of that degree (-1: no beam listed).
+ * Each output may be NULL; every element of one that is passed is written.  sb_graph_device only ENQUEUES on the engine's stream,
+ * reads nothing back and waits for nothing but the one table build after an upload (the shared scene tables of DESIGN.md 5.22 and
+ * sb_cut_device's caller-slot rows); it only READS the engine: frame, graph, frame equals frame, frame bit for bit.  sb_graph is
+ * the host-copy convenience: the same launches into buffers of the engine's own, copied back; it waits.
+ * Errors, before anything touches a device: SB_ERR_INVALID for a NULL handle, a struct_size that is neither 0 nor the struct's,
+ * nonzero reserved words, unknown flag bits, ends / nbr not 4-byte or row_ptr / counts not 8-byte aligned, nbr without row_ptr or
+ * with max_half_edges == 0, a scene whose beam data indices reach 2^31; SB_ERR_STATE before an upload; SB_ERR_UNSUPPORTED with
+ * ranks.  sb_get_info: "graph_kernel_vgprs", "graph_kernel_scratch_bytes", "graph_table_build_us". */
+#define SB_GRAPH_SKIP_PENDING 1u             /* a live beam whose break flag is pending is not listed */
+#define SB_GRAPH_COUNT_WORDS 4u
+typedef struct sb_graph_options {
+    uint32_t struct_size;    /* = sizeof(sb_graph_options); 0 or a NULL pointer = all defaults */
+    uint32_t flags;          /* SB_GRAPH_SKIP_PENDING */
+    uint64_t max_half_edges; /* rows of nbr; 0 with nbr NULL */
+    uint32_t reserved[4];
+} sb_graph_options;
+sb_status sb_graph_device(sb_engine *e, const sb_graph_options *opts, void *device_ends_i32 /* [max_beams][2] or NULL */,
+                          void *device_row_ptr_i64 /* [max_particles + 1] or NULL */,
+                          void *device_nbr_i32 /* [max_half_edges][2] or NULL; needs row_ptr */,
+                          void *device_counts_i64 /* [SB_GRAPH_COUNT_WORDS] or NULL */);
+sb_status sb_graph(sb_engine *e, const sb_graph_options *opts, int32_t *ends, int64_t *row_ptr, int32_t *nbr, int64_t *counts);
+
 /* ---- one summary row of the whole scene, reduced on the device ----
  * What a driver asks of a big scene between steps -- is everything still finite, did it leave the box, how much energy is left,
  * did anything break -- without exporting the state.  The row is SB_SUMMARY_WORDS = 24 floats with the meaning of a row of
@@ -1064,6 +1102,47 @@ sb_status sb_batch_contacts_device(sb_batch *b, uint32_t flags,
         void *device_pairs_i32        /* [n_scenes][max_pairs][2] or NULL */, uint32_t max_pairs,
         void *device_counts_i32       /* [n_scenes][SB_BATCH_CONTACT_WORDS] or NULL */);
 
+/* ---- the beam graph of every scene: edge list, materials and a sorted adjacency on the device ----
+ * sb_batch_graph_device -- which two particles every beam joins, with what material, and who hangs on whom, in ONE launch: the
+ * beam half of a graph network's edge list (sb_batch_contacts_device's pair list is the contact half).
+ *
+ * DEFINITION.  The graph of a scene is defined on what sb_batch_load_scene would return at that point of the stream.
+ * Nodes are the scene's particles, at particle DATA indices: the rows of sb_batch_read_state_device and of the contacts report.
+ * Edges are its LISTED beams, at beam DATA indices.  A beam is LIVE by sb_batch_bodies_device's rule, word for word: a beam slot
+ * < metadata.beam_i_c names its data index; a pending break flag still connects.  A live beam is LISTED unless
+ * SB_GRAPH_SKIP_PENDING is set and its pending break flag is raised: with that flag the graph is what the next delete pass will
+ * leave.  A listed beam d whose record's particle_pair is (a, b) -- low half, high half -- has two HALF-EDGES: side 0 at a with
+ * neighbour b, side 1 at b with neighbour a.  The DEGREE of a particle is the number of half-edges at it (parallel beams count
+ * each); a data index that holds no particle has degree 0.
+ *
+ * OUTPUTS.  Each may be NULL (not wanted); int32 unless said; every element of an output that is passed is written.
+ *   ends[s][d]      {a, b}, particle data indices, at beam data index d; {-1, -1} where d is not a listed beam.  Row d lines up
+ *                   with row d of sb_batch_read_state_device's beams: beam state becomes edge features by plain indexing.
+ *   material[s][d]  float32 {length, spring, damp, yield_strain, strain_break_limit} of the beam's material row, verbatim bits;
+ *                   zeros where d is not listed.  (After sb_batch_add_beams_device the caller holds no host copy of these.)
+ *   row_ptr[s]      max_particles + 1 words: the exclusive prefix sum of the degrees over particle data indices;
+ *                   row_ptr[s][max_particles] is the number of half-edges, twice the listed beams.
+ *   nbr[s]          2 * max_beams rows {neighbour, beam data index}: the half-edges at particle p are rows row_ptr[p] ..
+ *                   row_ptr[p + 1] - 1, in ascending order of beam data index (a beam from p to p: side 0, then side 1).  That order
+ *                   is unique, so the array is the same bits on every run.  {-1, -1} behind the last half-edge.
+ *   counts[s]       SB_BATCH_GRAPH_COUNT_WORDS words: 0 listed beams, 1 particles of degree >= 1, 2 the largest degree, 3 the
+ *                   smallest data index of a particle of that degree (-1: no beam listed).
+ * A scene never uploaded gives ends and nbr of -1, zero materials and row_ptr, counts {0, 0, 0, -1}.
+ * It only ENQUEUES on the batch's stream and only READS the batch: frame, graph, frame equals frame, frame bit for bit.  Integers
+ * only.  Errors, before anything touches a device: SB_ERR_INVALID for a NULL handle, unknown flag bits, a pointer that is not
+ * 4-byte aligned, nbr without row_ptr.  With every output NULL the call is SB_OK and enqueues nothing.
+ * sb_batch_get_info: "graph_count_words", "graph_material_words", "graph_lds_bytes" (LDS of one workgroup at this batch's
+ * capacity), "graph_kernel_vgprs", "graph_kernel_scratch_bytes". */
+/* flags: SB_GRAPH_SKIP_PENDING (above, with sb_graph_device) */
+#define SB_BATCH_GRAPH_COUNT_WORDS 4u
+#define SB_BATCH_GRAPH_MATERIAL_WORDS 5u
+sb_status sb_batch_graph_device(sb_batch *b, uint32_t flags,
+        void *device_ends_i32     /* [n_scenes][max_beams][2] or NULL */,
+        void *device_material_f32 /* [n_scenes][max_beams][SB_BATCH_GRAPH_MATERIAL_WORDS] float or NULL */,
+        void *device_row_ptr_i32  /* [n_scenes][max_particles + 1] or NULL */,
+        void *device_nbr_i32      /* [n_scenes][2 * max_beams][2] or NULL; needs row_ptr */,
+        void *device_counts_i32   /* [n_scenes][SB_BATCH_GRAPH_COUNT_WORDS] or NULL */);
+
 /* scene i back into host buffers exactly as sb_load_buffers returns a single engine in the same state (counts in the metadata,
  * the mapping after the delete passes' stable in-place compactions, beam records with strain / stress; only records reachable
  * through the uploaded mapping are written; any pointer may be NULL).  SB_ERR_STATE for a scene never uploaded. */
@@ -1117,7 +1196,9 @@ sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream);
  * "contacts_lds_bytes" (likewise), "contacts_cells_per_side" (G of the G x G cells the call bins into: the rule of
  * "contact_cells_per_side" whatever the collision mode and threshold; 1 where the cell width is no ordinary number);
  * sb_batch_body_summary_device: "body_summary_words" (SB_BATCH_BODY_SUMMARY_WORDS), "body_summary_kernel_vgprs",
- * "body_summary_kernel_scratch_bytes", "body_summary_lds_bytes" (LDS of one workgroup at this batch's capacity) */
+ * "body_summary_kernel_scratch_bytes", "body_summary_lds_bytes" (LDS of one workgroup at this batch's capacity);
+ * sb_batch_graph_device: "graph_count_words", "graph_material_words", "graph_kernel_vgprs", "graph_kernel_scratch_bytes",
+ * "graph_lds_bytes" (likewise) */
 sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value);
 const char *sb_batch_last_error(const sb_batch *b);
 

@@ -1,5 +1,6 @@
 """ctypes binding of the sb_batch_* group of include/softbody.h: N independent small scenes, one workgroup per scene,
 one launch per frame.  Like engine.py this only marshals buffers; there is no CPU fallback."""
+import collections
 import ctypes
 
 import numpy as np
@@ -40,6 +41,13 @@ ADD_ROW_WORDS = 8                                     # sb_batch_new_beam: {a, b
 ADD_DRY_RUN, ADD_LENGTH_CURRENT, ADD_SKIP_JOINED = 1, 2, 4   # SB_BATCH_ADD_*: the flags
 ADD_EMPTY, ADD_INVALID, ADD_JOINED, ADD_FULL = -1, -2, -3, -4   # SB_BATCH_ADD_*: what add_beams()'s result holds where no beam was added
 ADD_COUNT_FIELDS = ("added", "invalid", "joined", "full")     # the counts of add_beams(), in order (SB_BATCH_ADD_COUNT_WORDS of them)
+GRAPH_SKIP_PENDING = 1                                # SB_GRAPH_SKIP_PENDING
+GRAPH_COUNT_WORDS, GRAPH_MATERIAL_WORDS = 4, 5        # SB_BATCH_GRAPH_COUNT_WORDS, SB_BATCH_GRAPH_MATERIAL_WORDS
+# the words of a row of graph()'s counts and of its material, in order (include/softbody.h, sb_batch_graph_device)
+GRAPH_COUNT_FIELDS = ("beams", "connected_particles", "max_degree", "max_degree_particle")
+GRAPH_MATERIAL_FIELDS = ("length", "spring", "damp", "yield_strain", "strain_break_limit")
+# what graph() returns; None where an output was not asked for
+Graph = collections.namedtuple("Graph", ("ends", "material", "row_ptr", "nbr", "counts"))
 
 
 def new_beam_rows(pairs, spring, damp, yield_strain, strain_break_limit, length=None):
@@ -105,6 +113,7 @@ def load_library():
     L.sb_batch_rollout_device.argtypes = [vp, u32, vp, vp]
     L.sb_batch_bodies_device.argtypes = [vp, vp, vp, vp]
     L.sb_batch_contacts_device.argtypes = [vp, u32, vp, vp, vp, u32, vp]
+    L.sb_batch_graph_device.argtypes = [vp, u32, vp, vp, vp, vp, vp]
     L.sb_batch_body_summary_device.argtypes = [vp, vp, u32, vp, vp]
     L.sb_batch_load_scene.argtypes = [vp, u32, vp, sz, vp, sz, vp, sz, vp, sz]
     L.sb_batch_render_device.argtypes = [vp, ctypes.POINTER(SbBatchRenderOptions), vp]
@@ -546,6 +555,49 @@ class BatchEngine:
         self._ordered(tensors, lambda: load_library().sb_batch_contacts_device(self._h, flags, vp(ptrs[3]), vp(ptrs[0]), vp(ptrs[1]), max_pairs,
                                                                                vp(ptrs[2])))
         return (outs[0], outs[2], outs[1]) if max_pairs > 0 else (outs[0], outs[2])
+
+    # ---- the beam graph (sb_batch_graph_device)
+    def graph(self, ends=True, material=False, adjacency=False, skip_pending=False, counts=None):
+        """Which particles every beam joins, with what material, and who hangs on whom, in every scene in one launch: the beam
+        half of a graph network's edge list (contacts(pairs=n) is the contact half).  Nodes are the particles at particle DATA
+        indices (the rows of state_tensors() and contacts()), edges the LISTED beams at beam DATA indices: the live beams, by
+        bodies()' rule -- a pending break flag still connects -- or, with skip_pending=True, the live beams without a pending
+        flag: what the next delete pass will leave.  Returns a Graph named tuple of tensors on the batch's device (None where
+        not asked for), int32 unless said:
+        ends [n_scenes, max_beams, 2]: at beam data index d the particle data indices {a, b} of the beam's record, (-1, -1) where
+        d is not a listed beam; row d lines up with row d of state_tensors()'s beams.
+        material [n_scenes, max_beams, 5] float32 (GRAPH_MATERIAL_FIELDS): length, spring, damp, yield_strain,
+        strain_break_limit, verbatim bits; zeros where d is not listed.
+        row_ptr [n_scenes, max_particles + 1] and nbr [n_scenes, 2 * max_beams, 2] (adjacency=True), a CSR adjacency: the rows
+        row_ptr[p] .. row_ptr[p + 1] - 1 of nbr are {other endpoint, beam data index} of the listed beams at particle p, in
+        ascending order of beam data index; (-1, -1) behind the last.  The same bits on every run.
+        counts [n_scenes, 4] (GRAPH_COUNT_FIELDS): listed beams, particles of degree >= 1, the largest degree, the smallest data
+        index of a particle of that degree (-1: no beam listed).  counts=None: made whenever something else is; False: not.
+        A scene never uploaded gives -1 / 0 rows.  ends / material / counts: True, False, a device pointer (int) or a contiguous
+        torch tensor to write into; adjacency: True, False or a pair (row_ptr, nbr) of those.  Every word of what is asked for
+        is written.  Only reads the batch, only enqueues; torch's current stream is ordered after it."""
+        n, maxp, maxb = self.n_scenes, self.max_particles, self.max_beams
+        if isinstance(adjacency, (tuple, list)):
+            if len(adjacency) != 2:
+                raise ValueError("graph: adjacency is True, False or a pair (row_ptr, nbr)")
+            row_ptr, nbr = adjacency
+        else:
+            row_ptr = nbr = bool(adjacency)
+        if nbr is not False and nbr is not None and (row_ptr is False or row_ptr is None):
+            raise ValueError("graph: nbr without row_ptr")
+        if counts is None:
+            counts = True
+        wanted = [x is not False and x is not None for x in (ends, material, row_ptr, nbr, counts)]
+        given = [None if isinstance(x, bool) else x for x in (ends, material, row_ptr, nbr, counts)]   # (True: a new tensor)
+        outs, ptrs, tensors = self._bind("graph", [("ends", given[0], wanted[0], (n, maxb, 2), "int32"),
+                                                   ("material", given[1], wanted[1], (n, maxb, GRAPH_MATERIAL_WORDS), "float32"),
+                                                   ("row_ptr", given[2], wanted[2], (n, maxp + 1), "int32"),
+                                                   ("nbr", given[3], wanted[3], (n, 2 * maxb, 2), "int32"),
+                                                   ("counts", given[4], wanted[4], (n, GRAPH_COUNT_WORDS), "int32")])
+        vp = ctypes.c_void_p
+        self._ordered(tensors, lambda: load_library().sb_batch_graph_device(self._h, GRAPH_SKIP_PENDING if skip_pending else 0,
+                                                                            *[vp(p) for p in ptrs]))
+        return Graph(*outs)
 
     # ---- pictures (sb_batch_render_device / sb_batch_render_scene; DESIGN.md 5.11)
     def _render_options(self, resolution, bounds_size, particle_radius, first=0, count=0):

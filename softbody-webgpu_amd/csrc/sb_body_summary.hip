@@ -55,6 +55,7 @@
 #define SBY_NONE 0xFFFFFFFFu
 
 static_assert(SBY_RADIX == SBY_BLOCK, "k_bsum_hist / k_bsum_scatter: one thread per digit");
+static_assert(SBY_RADIX == SBQ_RADIX && SBY_SORT == SBQ_SORT, "what sb_report.h tells sbq_sort's callers about its buffers");
 
 enum { SBY_P_BAD, SBY_P_MINX, SBY_P_MINY, SBY_P_MAXX, SBY_P_MAXY, SBY_P_MAXV2, SBY_NPST }; // particle words per sorted position
 enum { SBY_B_LIVE, SBY_B_PENDING, SBY_B_BAD, SBY_B_MAXSTRAIN, SBY_B_MAXSTRESS, SBY_B_MINSTRESS, SBY_NBST }; // beam words per head
@@ -429,8 +430,9 @@ static uint32_t sby_blocks(uint64_t k, uint32_t per) { return (uint32_t)((k + pe
 
 // Stable sort of at most n_max keys (the number on the device where n_dev is given) by their bits 32 .. 32 + bits - 1, between
 // the buffers a and b; returns the one that holds the result.  hist: SBY_RADIX words per sort block; bsum: a word per scan block.
-static unsigned long long *sby_sort(sb_engine *e, unsigned long long *a, unsigned long long *b, uint32_t n_max, const uint32_t *n_dev,
-                                    uint32_t bits, uint32_t *hist, uint32_t *bsum)
+// (sbq_sort of sb_report.h: sb_graph.hip orders its half-edges with the same launches)
+unsigned long long *sbq_sort(sb_engine *e, unsigned long long *a, unsigned long long *b, uint32_t n_max, const uint32_t *n_dev, uint32_t bits,
+                             uint32_t *hist, uint32_t *bsum)
 {
     const uint32_t nb = sby_blocks(n_max, SBY_SORT), passes = (bits + SBY_RADIX_BITS - 1u) / SBY_RADIX_BITS;
     const uint32_t per = (bits + passes - 1u) / passes; // digits of equal width: 21 bits are three passes of 7
@@ -443,6 +445,8 @@ static unsigned long long *sby_sort(sb_engine *e, unsigned long long *a, unsigne
     }
     return a;
 }
+
+std::vector<const void *> sbq_sort_kernels() { return {(const void *)k_bsum_hist, (const void *)k_bsum_scatter}; }
 
 // the call's scratch, carved out of one allocation: bytes per position of Wn (sb_get_info "body_summary_scratch_bytes")
 struct SbyCarve {
@@ -528,7 +532,7 @@ static sb_status sby_enqueue(sb_engine *e, const sb_body_summary_options *o, con
     const uint32_t grid_w = sby_blocks(Wn, SBY_BLOCK);
 
     k_bsum_stage<<<grid_w, SBY_BLOCK, 0, e->stream>>>(pinv, np, d_labels, none, Wn, logWn, keys_a);
-    unsigned long long *keys = sby_sort(e, keys_a, keys_b, Wn, nullptr, sby_bits(none), hist, bsum);
+    unsigned long long *keys = sbq_sort(e, keys_a, keys_b, Wn, nullptr, sby_bits(none), hist, bsum);
     unsigned long long *spare = keys == keys_a ? keys_b : keys_a;
     k_bsum_leaves<<<grid_w, SBY_BLOCK, 0, e->stream>>>(keys, Wn, none, pinv, c.pos, c.vel, c.acc, col, pst, bst, ord);
     for (uint32_t l = 0; l < logWn; l++) // (no key has a bit below 32 - log2 Wn set: those levels add nothing)
@@ -539,7 +543,7 @@ static sb_status sby_enqueue(sb_engine *e, const sb_body_summary_options *o, con
     sbq_scan<uint32_t>(e, ord, Wn, bsum, ord, ctl + SBY_C_HEADS);
     const uint32_t cbits = logWn + 1u, cmask = (uint32_t)((1ull << cbits) - 1ull); // a group holds at most Wn particles
     k_bsum_groups<<<grid_w, SBY_BLOCK, 0, e->stream>>>(keys, Wn, none, ord, cmask, ghead, gcnt, rkeys, ctl);
-    const unsigned long long *sorted = sby_sort(e, rkeys, spare, Wn, ctl + SBY_C_GROUPS, cbits, hist, bsum);
+    const unsigned long long *sorted = sbq_sort(e, rkeys, spare, Wn, ctl + SBY_C_GROUPS, cbits, hist, bsum);
     if (rows || rows64)
         k_bsum_rows<<<sby_blocks(max_rows, SBY_BLOCK), SBY_BLOCK, 0, e->stream>>>(sorted, Wn, ctl, keys, ghead, gcnt, col, pst, bst, max_rows,
                                                                                  d_rows, d_rows64);

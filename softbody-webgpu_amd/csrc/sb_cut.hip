@@ -85,7 +85,7 @@ __global__ __launch_bounds__(SBX_BLOCK) void k_cut_apply(const uint32_t *__restr
 // ---------------------------------------------------------------- host side
 
 // per caller beam slot of the latest upload the data index of its record (sb_load_buffers' beam loop)
-static sb_status sbx_build_rows(sb_engine *e, const char *what)
+sb_status sbx_build_rows(sb_engine *e, const char *what) // (sb_report.h: sb_graph.hip reads the same rows)
 {
     const auto t0 = std::chrono::steady_clock::now();
     SbStateIoState &s = *e->sio;
@@ -93,6 +93,8 @@ static sb_status sbx_build_rows(sb_engine *e, const char *what)
     SB_TRY(sbq_user_slots(e, what, slots));
     std::vector<uint32_t> row(slots.size());
     for (size_t u = 0; u < slots.size(); u++) row[u] = slots[u].y;
+    s.cut_nd = 0;
+    for (uint32_t u = 0; u < sb_user_beams(e); u++) s.cut_nd = std::max(s.cut_nd, row[u] + 1u);
     SB_TRY(s.buf[SBX_B_ROW].grow(e, row.size() * 4));
     SB_HIP(e, hipMemcpyAsync(s.buf[SBX_B_ROW].p, row.data(), row.size() * 4, hipMemcpyHostToDevice, e->stream));
     SB_HIP(e, hipStreamSynchronize(e->stream)); // (the host vector goes out of scope)

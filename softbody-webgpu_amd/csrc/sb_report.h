@@ -25,7 +25,8 @@ enum SbReportBuf {
     SBD_B_PARENT, SBD_B_SIZES, SBD_B_ACC,                                          // sb_bodies.hip
     SBC_B_CELLS, SBC_B_BSUM, SBC_B_SORTED, SBC_B_ABOVE, SBC_B_PLACE, SBC_B_ACC, SBC_B_LABELS, SBC_B_TOUCH, SBC_B_PAIRS, // sb_contacts.hip
     SBY_B_SCRATCH, SBY_B_LABELS, SBY_B_OUT,                                        // sb_body_summary.hip
-    SBX_B_ROW, SBX_B_MARK, SBX_B_ACC, SBX_B_SHAPES, SBX_B_HIT,                     // sb_cut.hip
+    SBX_B_ROW, SBX_B_MARK, SBX_B_ACC, SBX_B_SHAPES, SBX_B_HIT,                     // sb_cut.hip (SBX_B_ROW: also sb_graph.hip)
+    SBG_B_SCRATCH, SBG_B_ENDS, SBG_B_ROWPTR, SBG_B_NBR, SBG_B_COUNTS,              // sb_graph.hip
     SBQ_NBUF
 };
 
@@ -59,6 +60,8 @@ struct SbStateIoState {
     bool cut_valid = false;
     double cut_row_ms = 0.0, cut_build_ms = 0.0;
     uint64_t cuts = 0;                        // calls since sb_create
+    uint32_t cut_nd = 0;                      // highest beam data index among the rows + 1 (sb_graph.hip)
+    double graph_build_ms = 0.0;              // "graph_table_build_us"
 
     void invalidate() { part_valid = beam_valid = copy_valid = valid = bleaf_valid = imp_valid = cut_valid = false; } // every table of the scene: the one place
 };
@@ -70,6 +73,7 @@ inline const char *sbq_options_name(const sb_bodies_options *) { return "sb_bodi
 inline const char *sbq_options_name(const sb_contacts_options *) { return "sb_contacts_options"; }
 inline const char *sbq_options_name(const sb_body_summary_options *) { return "sb_body_summary_options"; }
 inline const char *sbq_options_name(const sb_cut_options *) { return "sb_cut_options"; }
+inline const char *sbq_options_name(const sb_graph_options *) { return "sb_graph_options"; }
 
 sb_status sbq_ready(sb_engine *e, const char *what, const char *why); // loaded, no ranks (`why`: the call's parenthesis); the device; e->sio
 
@@ -97,6 +101,9 @@ sb_status sbq_need(sb_engine *e, const char *what, uint32_t parts);
 // per caller beam slot of the latest upload {engine slot, data index of its record}, both checked against the scene
 sb_status sbq_user_slots(sb_engine *e, const char *what, std::vector<uint2> &slots);
 
+// sb_cut.hip: per caller beam slot of the latest upload the data index of its record, on the device (SBX_B_ROW; cut_valid, cut_nd)
+sb_status sbx_build_rows(sb_engine *e, const char *what);
+
 // ---- exclusive scan of n 32-bit words into T words (uint32_t / unsigned long long), three launches: a sum per block of SBQ_SCAN
 // words into bsum, the block sums scanned in place by ONE workgroup that loops over them with a carry (the sum of all to *total,
 // which may be NULL), added back.  `out` may be `in` when T is 32 bits.
@@ -106,6 +113,16 @@ sb_status sbq_user_slots(sb_engine *e, const char *what, std::vector<uint2> &slo
 template <class T>
 void sbq_scan(sb_engine *e, const uint32_t *in, uint64_t n, T *bsum, T *out, T *total);
 std::vector<const void *> sbq_scan_kernels(bool wide); // the kernels sbq_scan<uint32_t> may launch; wide: and sbq_scan<unsigned long long>'s (the reports' *_kernel_vgprs keys)
+
+// ---- stable LSD radix sort of at most n_max 64-bit keys (the number on the device where n_dev is given) by their bits 32 ..
+// 32 + bits - 1, between the buffers a and b; returns the one that holds the result.  It is the body summary's sort
+// (sb_body_summary.hip, where its two kernels k_bsum_hist / k_bsum_scatter live), shared with sb_graph.hip.  hist: SBQ_RADIX words per
+// block of SBQ_SORT keys; bsum: a word per scan block of hist.
+#define SBQ_SORT 1024u
+#define SBQ_RADIX 256u
+unsigned long long *sbq_sort(sb_engine *e, unsigned long long *a, unsigned long long *b, uint32_t n_max, const uint32_t *n_dev, uint32_t bits,
+                             uint32_t *hist, uint32_t *bsum);
+std::vector<const void *> sbq_sort_kernels();
 
 // The length of the run for the first lane of each maximal run of equal keys in the wave, 0 for every other lane and for a run
 // that is not valid.  Every lane of the wave calls it.

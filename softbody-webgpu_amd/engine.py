@@ -50,6 +50,17 @@ SUMMARY_COUNT_FIELDS = ("particles", "live_beams", "removed_beams", "pending_bre
                         "uploaded", "reserved_7")
 
 
+class SbGraphOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("max_half_edges", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint32 * 4)]
+
+
+GRAPH_SKIP_PENDING = 1                                # SB_GRAPH_SKIP_PENDING
+GRAPH_COUNT_WORDS = 4                                 # SB_GRAPH_COUNT_WORDS
+# the words of graph()'s counts, in order (include/softbody.h, sb_graph_device)
+GRAPH_COUNT_FIELDS = ("beams", "connected_particles", "max_degree", "max_degree_particle")
+
+
 class SbBodiesOptions(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 7)]
 
@@ -270,6 +281,8 @@ def load_library():
     L.sb_cut.argtypes = [vp, ctypes.POINTER(SbCutOptions), vp, u32, vp, vp]
     L.sb_summary_device.argtypes = [vp, ctypes.POINTER(SbSummaryOptions), vp, vp]
     L.sb_summary.argtypes = [vp, ctypes.POINTER(SbSummaryOptions), vp, vp]
+    L.sb_graph_device.argtypes = [vp, ctypes.POINTER(SbGraphOptions), vp, vp, vp, vp]
+    L.sb_graph.argtypes = [vp, ctypes.POINTER(SbGraphOptions), vp, vp, vp, vp]
     L.sb_bodies_device.argtypes = [vp, ctypes.POINTER(SbBodiesOptions), vp, vp, vp]
     L.sb_bodies.argtypes = [vp, ctypes.POINTER(SbBodiesOptions), vp, vp, vp]
     L.sb_contacts_device.argtypes = [vp, ctypes.POINTER(SbContactsOptions), vp, vp, vp, vp]
@@ -744,6 +757,71 @@ class Engine:
         counts = np.empty(BODY_WORDS, dtype=np.int64)
         self._check(load_library().sb_bodies(self._h, None, _ptr(labels), _ptr(sizes), _ptr(counts)))
         return labels, sizes, counts
+
+    # ---- the beam graph of the whole scene (sb_graph_device / sb_graph)
+
+    @staticmethod
+    def _graph_options(max_half_edges, skip_pending):
+        o = SbGraphOptions()
+        o.struct_size = ctypes.sizeof(SbGraphOptions)
+        o.flags = GRAPH_SKIP_PENDING if skip_pending else 0
+        o.max_half_edges = int(max_half_edges)
+        return o
+
+    def graph(self, ends=True, adjacency=False, max_half_edges=None, skip_pending=False, counts=True):
+        """The beam graph of the scene in the caller's index space, written on the GPU: (ends, row_ptr, nbr, counts), torch tensors
+        on the engine's device, None where not asked for.  Nodes are the particles at particle DATA indices, edges the LISTED
+        beams at beam DATA indices: the live beams by bodies()' rule (a pending break flag still connects), or with
+        skip_pending=True those without a pending flag -- what the next delete pass will leave.  ends int32 [max_beams, 2]: {a, b} of
+        the beam's record at its data index, (-1, -1) where no listed beam lives.  adjacency=True: row_ptr int64
+        [max_particles + 1], the exclusive prefix sum of the degrees, always complete, and nbr int32 [max_half_edges, 2], the rows
+        row_ptr[p] .. row_ptr[p + 1] - 1 being {other endpoint, beam data index} of the listed beams at p in ascending beam data
+        index, (-1, -1) behind the last; max_half_edges=None: 2 * max_beams; 0: row_ptr alone.  counts int64 [4]
+        (GRAPH_COUNT_FIELDS).  ends / counts: True, False, a device pointer (int) or a contiguous torch tensor to write into;
+        adjacency: True, False or a pair (row_ptr, nbr) of those (then max_half_edges is nbr's rows).  Only reads the engine, only
+        enqueues; torch's current stream is ordered after it."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(adjacency, (tuple, list)):
+            row_ptr, nbr = adjacency
+        else:
+            row_ptr = nbr = bool(adjacency)
+        H = 2 * self.max_beams if max_half_edges is None else int(max_half_edges)
+        if isinstance(nbr, torch.Tensor) and max_half_edges is None:
+            H = nbr.numel() // 2
+        if H == 0:
+            nbr = False
+        if nbr is not False and nbr is not None and (row_ptr is False or row_ptr is None):
+            raise ValueError("graph: nbr without row_ptr")
+        shapes = (("ends", ends, (self.max_beams, 2), "int32"), ("row_ptr", row_ptr, (self.max_particles + 1,), "int64"),
+                  ("nbr", nbr, (H, 2), "int32"), ("counts", counts, (GRAPH_COUNT_WORDS,), "int64"))
+        outs, ptrs, tensors = [], [], False
+        for what, x, shape, dtype in shapes:
+            if x is False or x is None:
+                outs.append(None)
+                ptrs.append(None)
+                continue
+            if x is True:
+                x = torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
+            ptr, t = self._device_buffer("graph: " + what, x, dtype, int(np.prod(shape)) * (8 if dtype == "int64" else 4))
+            outs.append(x)
+            ptrs.append(ptr)
+            tensors |= t
+        o = self._graph_options(H if ptrs[2] else 0, skip_pending)
+        vp = ctypes.c_void_p
+        self._ordered(tensors, lambda: load_library().sb_graph_device(self._h, ctypes.byref(o), vp(ptrs[0]), vp(ptrs[1]), vp(ptrs[2]), vp(ptrs[3])))
+        return tuple(outs)
+
+    def graph_host(self, max_half_edges=None, skip_pending=False):
+        """The same without torch: (ends, row_ptr, nbr, counts) numpy arrays (nbr None with max_half_edges=0).  Waits for the stream."""
+        H = 2 * self.max_beams if max_half_edges is None else int(max_half_edges)
+        ends = np.empty((self.max_beams, 2), dtype=np.int32)
+        row_ptr = np.empty(self.max_particles + 1, dtype=np.int64)
+        nbr = np.empty((H, 2), dtype=np.int32) if H else None
+        counts = np.empty(GRAPH_COUNT_WORDS, dtype=np.int64)
+        o = self._graph_options(H, skip_pending)
+        self._check(load_library().sb_graph(self._h, ctypes.byref(o), _ptr(ends), _ptr(row_ptr), _ptr(nbr), _ptr(counts)))
+        return ends, row_ptr, nbr, counts
 
     # ---- particle and wall contacts of the whole scene (sb_contacts_device / sb_contacts; DESIGN.md 5.20)
 
