@@ -7,6 +7,7 @@ The directory name carries a hyphen (it is the reference's name), so load it wit
   scenes.py   synthetic scene generators (generalised main.ts:addRectangle)
   engine.py   ctypes binding of the C ABI in include/softbody.h (libsoftbody_hip.so)
   batch.py    BatchEngine: the sb_batch_* group (N small scenes, one workgroup each, one launch per frame)
+  device_binding.py   what Engine and BatchEngine share for device memory: buffer check, stream ordering, output binder
   csrc/       HIP kernels + the C ABI + the N-API addon
   host/       JavaScript/TypeScript host mirror of engine.ts / engineMapping.ts / engineWorker.ts
 """

@@ -6,6 +6,7 @@ import ctypes
 import numpy as np
 
 from . import engine as _engine
+from .device_binding import DeviceBinding
 from .engine import COLLIDE_GRID, EngineError, _ptr
 from .layout import LAYOUT_V1, PARTICLE_STRIDE, Buffers
 
@@ -130,7 +131,7 @@ def load_library():
     return L
 
 
-class BatchEngine:
+class BatchEngine(DeviceBinding):
     """N independent scenes of at most BATCH_MAX_PARTICLES particles / BATCH_MAX_BEAMS beams each, stepped together.
     max_particles / max_beams are the capacity PER SCENE (the sizes of the layout.Buffers that write_scene / load_scene take).
 
@@ -141,6 +142,8 @@ class BatchEngine:
     info() keys of the cells: "contact_cells_per_side" (0: the whole batch runs the loop), "contact_cell_capacity",
     "grid_min_particles" (resolved), and, waiting for the stream, "cell_substeps" (scene-substeps that ran on the cells) and
     "cell_overflow_substeps" (scene-substeps that ran the loop because a cell held more than its capacity)."""
+
+    _owner = "batch"
 
     def __init__(self, n_scenes=1, bounds_size=1000.0, particle_radius=10.0, subticks=64, layout=LAYOUT_V1,
                  max_particles=BATCH_MAX_PARTICLES, max_beams=BATCH_MAX_BEAMS, collision_mode=COLLIDE_GRID, device=0,
@@ -270,66 +273,6 @@ class BatchEngine:
         return s.value
 
     # ---- the state in device memory
-    def _device_buffer(self, what, x, dtypes, nbytes):
-        """A device pointer (int, passed as is) or a contiguous torch tensor on the batch's device, of one of `dtypes` (None:
-        any) and at least `nbytes` bytes: (pointer, is_tensor).  ValueError otherwise."""
-        if isinstance(x, int) and not isinstance(x, bool):
-            return x, False
-        import torch
-        if not isinstance(x, torch.Tensor):
-            raise ValueError("%s: a device pointer (int) or a torch tensor is needed, not %s" % (what, type(x).__name__))
-        if x.device.type != "cuda" or (x.device.index if x.device.index is not None else torch.cuda.current_device()) != self.device:
-            raise ValueError("%s: the tensor is on %s, the batch on cuda:%d" % (what, x.device, self.device))
-        if dtypes is not None:
-            dtypes = (dtypes,) if isinstance(dtypes, str) else dtypes
-            if x.dtype not in [getattr(torch, d) for d in dtypes]:
-                raise ValueError("%s: a %s tensor is needed, not %s" % (what, " / ".join(dtypes), x.dtype))
-        if not x.is_contiguous():
-            raise ValueError("%s: the tensor must be contiguous" % what)
-        if x.element_size() * x.numel() < nbytes:
-            raise ValueError("%s: a tensor of at least %d bytes is needed, this one has %d" % (what, nbytes, x.element_size() * x.numel()))
-        return x.data_ptr(), True
-
-    def _ordered(self, tensors, call):
-        """call() enqueues on the batch's stream; with tensors, that work is ordered behind torch's current stream and torch's
-        current stream behind it (as Engine._ordered does for one engine)."""
-        if not tensors:
-            return self._check(call())
-        import torch
-        dev = torch.device("cuda", self.device)
-        if self._ext_stream is None:
-            self._ext_stream = torch.cuda.ExternalStream(self.stream(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        self._ext_stream.wait_stream(cur)
-        self._check(call())
-        cur.wait_stream(self._ext_stream)
-
-    def _bind(self, call, entries):
-        """The buffers of one report call.  entries: (name, given, wanted, shape, dtype) each; `given` is what the caller passed
-        (a device pointer, a torch tensor, or None: make one), or a function that makes the buffer from the batch (bodies()'s
-        labels).  In this order: everything the caller gave is validated; the functions are called; what is wanted and missing
-        is allocated; a flat tensor becomes a view of `shape`.  Returns (buffers, pointers, "one of them is a tensor"), None
-        where an entry is not wanted.  ValueError before anything is allocated or enqueued."""
-        import torch
-        nbytes = [int(np.prod(shape)) * np.dtype(dtype).itemsize for _, _, _, shape, dtype in entries]
-        for (name, given, _, _, dtype), nb in zip(entries, nbytes):
-            if given is not None and not callable(given):
-                self._device_buffer("%s: %s" % (call, name), given, dtype, nb)
-        made = [given() if callable(given) else given for _, given, _, _, _ in entries]
-        bufs, ptrs, tensors = [], [], False
-        for (name, _, wanted, shape, dtype), x, nb in zip(entries, made, nbytes):
-            ptr = None
-            if wanted:
-                if x is None:
-                    x = torch.empty(shape, dtype=getattr(torch, dtype), device=torch.device("cuda", self.device))
-                ptr, t = self._device_buffer("%s: %s" % (call, name), x, dtype, nb)
-                if t and tuple(x.shape) != tuple(shape):
-                    x = x.view(-1)[:int(np.prod(shape))].view(shape)
-                tensors |= t
-            bufs.append(x if wanted else None)
-            ptrs.append(ptr)
-        return bufs, ptrs, tensors
-
     def read_state_device(self, particles=None, beams=None, beam_alive=None):
         """Engine.read_state_device with a leading scene dimension: particles float32 [n_scenes, max_particles, 6], beams
         float32 [n_scenes, max_beams, 4] {target_length, last_length, strain, stress}, beam_alive uint8 / bool

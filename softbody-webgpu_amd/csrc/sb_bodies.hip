@@ -164,28 +164,31 @@ static sb_status sbd_enqueue(sb_engine *e, const sb_bodies_options *o, void *lab
     s.bod_build_ms = s.part_ms + s.beam_ms;
 
     // where the launches write: the caller's device memory, or the engine's own (what the caller did not ask for but a later
-    // stage needs: up to the highest data index in use; sb_bodies: whole outputs, copied to the host below)
+    // stage needs: up to the highest data index in use; sb_bodies: whole outputs, copied to the host by the mirror)
     const uint32_t maxP = e->opt.max_particles, np = s.np, n = s.nslots;
     const bool want_sizes = sizes || counts;
     const uint32_t n_parent = labels ? maxP : np, n_sizes = !want_sizes ? 0u : sizes ? maxP : np;
-    int32_t *d_parent = (int32_t *)labels, *d_sizes = (int32_t *)sizes;
-    long long *d_counts = (long long *)counts;
-    if (host || !labels) {
+    SbqMirror mir(e, host);
+    int32_t *d_parent = mir.out<int32_t>(SBD_B_PARENT, labels, (size_t)maxP * sizeof(int32_t));
+    int32_t *d_sizes = mir.out<int32_t>(SBD_B_SIZES, sizes, (size_t)2 * maxP * sizeof(int32_t));
+    if (!labels) {
         SB_TRY(s.buf[SBD_B_PARENT].grow(e, (size_t)n_parent * sizeof(int32_t)));
         d_parent = s.buf[SBD_B_PARENT].as<int32_t>();
     }
-    if (want_sizes && (host || !sizes)) {
+    if (want_sizes && !sizes) {
         SB_TRY(s.buf[SBD_B_SIZES].grow(e, (size_t)2 * n_sizes * sizeof(int32_t)));
         d_sizes = s.buf[SBD_B_SIZES].as<int32_t>();
     }
     unsigned long long *d_acc = nullptr;
+    long long *d_counts = nullptr;
     if (counts) {
         SB_TRY(s.buf[SBD_B_ACC].grow(e, ((size_t)SBD_COUNTS + SB_BODY_WORDS) * sizeof(unsigned long long)));
         d_acc = s.buf[SBD_B_ACC].as<unsigned long long>();
-        if (host) d_counts = (long long *)(d_acc + SBD_COUNTS);
+        d_counts = mir.out_at<long long>(counts, d_acc, SBD_COUNTS * sizeof(unsigned long long), SB_BODY_WORDS * sizeof(int64_t));
     }
+    SB_TRY(mir.st);
     const uint32_t *d_pinv = s.buf[SBQ_B_PINV].as<uint32_t>(), *d_tab = s.buf[SBQ_B_TAB].as<uint32_t>(); // (three planes of the four are read)
-    const uint32_t *dead = e->B && e->delete_gen ? e->d_dead_gen : nullptr; // as sb_load_buffers (fetch_dead) sees it
+    const uint32_t *dead = sbq_dead(e);
     auto blocks = [](uint32_t k) { return (k + SBD_BLOCK - 1u) / SBD_BLOCK; };
 
     k_bodies_init<<<std::max(blocks(std::max(n_parent, n_sizes)), 1u), SBD_BLOCK, 0, e->stream>>>(d_pinv, np, d_parent, n_parent,
@@ -201,13 +204,7 @@ static sb_status sbd_enqueue(sb_engine *e, const sb_bodies_options *o, void *lab
         k_bodies_counts<<<1, 64, 0, e->stream>>>(d_acc, d_counts);
     }
     SB_HIP(e, hipGetLastError());
-    if (host) {
-        if (labels) SB_HIP(e, hipMemcpyAsync(labels, d_parent, (size_t)maxP * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-        if (sizes) SB_HIP(e, hipMemcpyAsync(sizes, d_sizes, (size_t)maxP * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-        if (counts) SB_HIP(e, hipMemcpyAsync(counts, d_counts, SB_BODY_WORDS * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
-        SB_HIP(e, hipStreamSynchronize(e->stream));
-    }
-    return SB_OK;
+    return mir.finish();
 }
 
 // what sb_get_info reads ("bodies_table_build_us", "bodies_kernel_vgprs", "bodies_kernel_scratch_bytes")

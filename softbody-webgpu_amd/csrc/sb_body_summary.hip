@@ -501,33 +501,28 @@ static sb_status sby_enqueue(sb_engine *e, const sb_body_summary_options *o, con
     uint32_t *bsum = (uint32_t *)(m + o_bsum), *ctl = (uint32_t *)(m + o_ctl);
 
     // where the launches read and write: the caller's device memory, or (sb_body_summary) the engine's own, copied below
-    const int32_t *d_labels = (const int32_t *)labels;
-    float *d_rows = (float *)rows;
-    long long *d_rows64 = (long long *)rows64;
-    int32_t *d_rank = (int32_t *)rank;
-    const size_t b_rows = (size_t)max_rows * SB_BODY_SUMMARY_WORDS * sizeof(float), b_rows64 = (size_t)max_rows * SB_BODY_SUMMARY_COUNT_WORDS * sizeof(int64_t);
-    if (host || !labels) SB_TRY(s.buf[SBY_B_LABELS].grow(e, (size_t)maxP * sizeof(int32_t)));
-    if (host) {
-        SbyCarve out;
-        const size_t o_r64 = out.take(rows64 ? b_rows64 : 0), o_r = out.take(rows ? b_rows : 0), o_k = out.take(rank ? (size_t)maxP * 4 : 0);
-        SB_TRY(s.buf[SBY_B_OUT].grow(e, out.at));
-        char *w = s.buf[SBY_B_OUT].as<char>();
-        if (rows64) d_rows64 = (long long *)(w + o_r64);
-        if (rows) d_rows = (float *)(w + o_r);
-        if (rank) d_rank = (int32_t *)(w + o_k);
-        if (labels) {
-            SB_HIP(e, hipMemcpyAsync(s.buf[SBY_B_LABELS].p, labels, (size_t)maxP * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-            d_labels = s.buf[SBY_B_LABELS].as<int32_t>();
-        }
-    }
+    // (the outputs of sb_body_summary lie in one block, SBY_B_OUT: "body_summary_scratch_bytes" counts it)
+    const size_t b_labels = (size_t)maxP * sizeof(int32_t), b_rows = (size_t)max_rows * SB_BODY_SUMMARY_WORDS * sizeof(float),
+                 b_rows64 = (size_t)max_rows * SB_BODY_SUMMARY_COUNT_WORDS * sizeof(int64_t), b_rank = (size_t)maxP * sizeof(int32_t);
+    SbqMirror mir(e, host);
+    const int32_t *d_labels = mir.in<int32_t>(SBY_B_LABELS, labels, b_labels, b_labels);
+    SbyCarve out;
+    const size_t o_r64 = out.take(rows64 ? b_rows64 : 0), o_r = out.take(rows ? b_rows : 0), o_k = out.take(rank ? b_rank : 0);
+    if (host) SB_TRY(s.buf[SBY_B_OUT].grow(e, out.at));
+    void *w = s.buf[SBY_B_OUT].p;
+    long long *d_rows64 = mir.out_at<long long>(rows64, w, o_r64, b_rows64);
+    float *d_rows = mir.out_at<float>(rows, w, o_r, b_rows);
+    int32_t *d_rank = mir.out_at<int32_t>(rank, w, o_k, b_rank);
+    SB_TRY(mir.st);
     if (!labels) { // the engine's own bodies: sb_bodies_device's labelling, on the same stream, nothing waits
+        SB_TRY(s.buf[SBY_B_LABELS].grow(e, b_labels));
         const sb_status st = sb_bodies_device(e, nullptr, s.buf[SBY_B_LABELS].p, nullptr, nullptr);
         if (st != SB_OK) return st;
         d_labels = s.buf[SBY_B_LABELS].as<int32_t>();
     }
 
     const SbParticleArrays &c = e->part[e->cur];
-    const uint32_t *dead = e->B && e->delete_gen ? e->d_dead_gen : nullptr; // as sb_load_buffers (fetch_dead) sees it
+    const uint32_t *dead = sbq_dead(e);
     const uint32_t *pinv = s.buf[SBQ_B_PINV].as<uint32_t>(), *tab = s.buf[SBQ_B_TAB].as<uint32_t>();
     const uint32_t grid_w = sby_blocks(Wn, SBY_BLOCK);
 
@@ -552,13 +547,7 @@ static sb_status sby_enqueue(sb_engine *e, const sb_body_summary_options *o, con
         k_bsum_rank<<<sby_blocks(std::max(Wn, maxP), SBY_BLOCK), SBY_BLOCK, 0, e->stream>>>(keys, Wn, none, ord, rank_of, maxP, d_rank);
     }
     SB_HIP(e, hipGetLastError());
-    if (host) {
-        if (rows) SB_HIP(e, hipMemcpyAsync(rows, d_rows, b_rows, hipMemcpyDeviceToHost, e->stream));
-        if (rows64) SB_HIP(e, hipMemcpyAsync(rows64, d_rows64, b_rows64, hipMemcpyDeviceToHost, e->stream));
-        if (rank) SB_HIP(e, hipMemcpyAsync(rank, d_rank, (size_t)maxP * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-        SB_HIP(e, hipStreamSynchronize(e->stream));
-    }
-    return SB_OK;
+    return mir.finish();
 }
 
 // what sb_get_info reads ("body_summary_table_build_us", "body_summary_scratch_bytes", "body_summary_kernel_vgprs",

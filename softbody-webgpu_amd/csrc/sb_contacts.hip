@@ -303,25 +303,13 @@ static sb_status sbc_enqueue(sb_engine *e, const sb_contacts_options *o, const v
         d_place = s.buf[SBC_B_PLACE].as<unsigned long long>();
     }
     // where the launches read and write: the caller's device memory, or (sb_contacts) the engine's own, copied below
-    const int32_t *d_labels = (const int32_t *)labels;
-    int32_t *d_touch = (int32_t *)touch, *d_pairs = (int32_t *)pairs;
-    long long *d_counts = (long long *)counts;
-    if (host) {
-        if (labels) {
-            SB_TRY(s.buf[SBC_B_LABELS].grow(e, (size_t)maxP * sizeof(int32_t)));
-            d_labels = s.buf[SBC_B_LABELS].as<int32_t>();
-            SB_HIP(e, hipMemcpyAsync(s.buf[SBC_B_LABELS].p, labels, (size_t)maxP * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-        }
-        if (touch) {
-            SB_TRY(s.buf[SBC_B_TOUCH].grow(e, (size_t)maxP * SB_CONTACT_WORDS * sizeof(int32_t)));
-            d_touch = s.buf[SBC_B_TOUCH].as<int32_t>();
-        }
-        if (list) {
-            SB_TRY(s.buf[SBC_B_PAIRS].grow(e, (size_t)max_pairs * 2 * sizeof(int32_t)));
-            d_pairs = s.buf[SBC_B_PAIRS].as<int32_t>();
-        }
-        d_counts = (long long *)(d_acc + SBC_NACC);
-    }
+    SbqMirror mir(e, host);
+    const size_t b_labels = (size_t)maxP * sizeof(int32_t);
+    const int32_t *d_labels = mir.in<int32_t>(SBC_B_LABELS, labels, b_labels, b_labels);
+    int32_t *d_touch = mir.out<int32_t>(SBC_B_TOUCH, touch, (size_t)maxP * SB_CONTACT_WORDS * sizeof(int32_t));
+    int32_t *d_pairs = mir.out<int32_t>(SBC_B_PAIRS, list ? pairs : nullptr, (size_t)max_pairs * 2 * sizeof(int32_t));
+    long long *d_counts = mir.out_at<long long>(counts, d_acc, SBC_NACC * sizeof(unsigned long long), SB_CONTACT_COUNT_WORDS * sizeof(int64_t));
+    SB_TRY(mir.st);
 
     const float two_r = e->prm.particle_radius * 2.0f, thr0 = two_r * two_r * 1.001f;
     const SbcTest ts{two_r, (thr0 >= 0x1p-100f && thr0 <= 0x1p100f) ? thr0 : __builtin_inff(), e->prm.particle_radius,
@@ -348,13 +336,7 @@ static sb_status sbc_enqueue(sb_engine *e, const sb_contacts_options *o, const v
     if (list) k_contacts_tail<<<blocks(max_pairs), SBC_BLOCK, 0, e->stream>>>(d_acc, d_pairs, max_pairs);
     if (counts) k_contacts_counts<<<1, 64, 0, e->stream>>>(d_acc, d_counts, labels ? 1u : 0u);
     SB_HIP(e, hipGetLastError());
-    if (host) {
-        if (touch) SB_HIP(e, hipMemcpyAsync(touch, d_touch, (size_t)maxP * SB_CONTACT_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-        if (list) SB_HIP(e, hipMemcpyAsync(pairs, d_pairs, (size_t)max_pairs * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-        if (counts) SB_HIP(e, hipMemcpyAsync(counts, d_counts, SB_CONTACT_COUNT_WORDS * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
-        SB_HIP(e, hipStreamSynchronize(e->stream));
-    }
-    return SB_OK;
+    return mir.finish();
 }
 
 // what sb_get_info reads ("contacts_table_build_us", "contacts_cells_per_side", "contacts_kernel_vgprs", "contacts_kernel_scratch_bytes")

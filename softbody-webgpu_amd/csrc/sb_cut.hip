@@ -131,25 +131,12 @@ static sb_status sbx_enqueue(sb_engine *e, const sb_cut_options *o, const void *
 
     const uint32_t n = s.nslots, maxB = e->opt.max_beams;
     const bool dry = (flags & SB_CUT_DRY_RUN) != 0u;
-    const uint32_t *d_shapes = (const uint32_t *)shapes;
-    uint8_t *d_hit = (uint8_t *)hit;
-    unsigned long long *d_counts = (unsigned long long *)counts;
-    if (host) { // the same launches on the engine's own copies of the caller's memory
-        if (n_shapes) {
-            SB_TRY(s.buf[SBX_B_SHAPES].grow(e, (size_t)SB_CUT_MAX_SHAPES * sizeof(sb_cut_shape)));
-            SB_HIP(e, hipMemcpyAsync(s.buf[SBX_B_SHAPES].p, shapes, (size_t)n_shapes * sizeof(sb_cut_shape), hipMemcpyHostToDevice, e->stream));
-            d_shapes = s.buf[SBX_B_SHAPES].as<uint32_t>();
-        }
-        if (hit) { // (bytes at indices that hold no beam stay the caller's: they travel there and back)
-            SB_TRY(s.buf[SBX_B_HIT].grow(e, maxB));
-            SB_HIP(e, hipMemcpyAsync(s.buf[SBX_B_HIT].p, hit, maxB, hipMemcpyHostToDevice, e->stream));
-            d_hit = s.buf[SBX_B_HIT].as<uint8_t>();
-        }
-        if (counts) {
-            SB_TRY(s.buf[SBX_B_ACC].grow(e, SB_CUT_COUNT_WORDS * sizeof(unsigned long long)));
-            d_counts = s.buf[SBX_B_ACC].as<unsigned long long>();
-        }
-    }
+    SbqMirror mir(e, host); // (sb_cut: the same launches on the engine's own copies of the caller's memory)
+    const uint32_t *d_shapes = mir.in<uint32_t>(SBX_B_SHAPES, n_shapes ? shapes : nullptr, (size_t)n_shapes * sizeof(sb_cut_shape),
+                                                (size_t)SB_CUT_MAX_SHAPES * sizeof(sb_cut_shape));
+    uint8_t *d_hit = mir.inout<uint8_t>(SBX_B_HIT, hit, maxB); // (bytes at indices that hold no beam stay the caller's: they travel there and back)
+    unsigned long long *d_counts = mir.out<unsigned long long>(SBX_B_ACC, counts, SB_CUT_COUNT_WORDS * sizeof(unsigned long long));
+    SB_TRY(mir.st);
     if (d_counts) SB_HIP(e, hipMemsetAsync(d_counts, 0, SB_CUT_COUNT_WORDS * sizeof(unsigned long long), e->stream));
     if (n) {
         uint8_t *d_mark = nullptr;
@@ -158,21 +145,15 @@ static sb_status sbx_enqueue(sb_engine *e, const sb_cut_options *o, const void *
             d_mark = s.buf[SBX_B_MARK].as<uint8_t>();
             SB_HIP(e, hipMemsetAsync(d_mark, 0, e->B, e->stream));
         }
-        const uint32_t *dead = e->B && e->delete_gen ? e->d_dead_gen : nullptr; // as sb_load_buffers (fetch_dead) sees it
         auto blocks = [](uint32_t k) { return (k + SBX_BLOCK - 1u) / SBX_BLOCK; };
         k_cut_decide<<<blocks(n), SBX_BLOCK, 0, e->stream>>>(s.buf[SBQ_B_TAB].as<uint32_t>(), n, s.buf[SBX_B_ROW].as<uint32_t>(),
-                                                             s.buf[SBQ_B_PINV].as<uint32_t>(), e->part[e->cur].pos, dead, e->d_broken, d_shapes,
+                                                             s.buf[SBQ_B_PINV].as<uint32_t>(), e->part[e->cur].pos, sbq_dead(e), e->d_broken, d_shapes,
                                                              n_shapes, dry ? 1u : 0u, d_hit, d_mark, d_counts);
         if (!dry && n_shapes && e->nbeam)
             k_cut_apply<<<blocks(e->nbeam), SBX_BLOCK, 0, e->stream>>>(e->beams.slot, e->nbeam, e->B, d_mark, e->d_broken);
         SB_HIP(e, hipGetLastError());
     }
-    if (host) {
-        if (hit) SB_HIP(e, hipMemcpyAsync(hit, d_hit, maxB, hipMemcpyDeviceToHost, e->stream));
-        if (counts) SB_HIP(e, hipMemcpyAsync(counts, d_counts, SB_CUT_COUNT_WORDS * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
-        SB_HIP(e, hipStreamSynchronize(e->stream));
-    }
-    return SB_OK;
+    return mir.finish();
 }
 
 // what sb_get_info reads ("cuts", "cut_table_build_us", "cut_kernel_vgprs")

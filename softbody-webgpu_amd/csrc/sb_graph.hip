@@ -154,35 +154,18 @@ static sb_status sbg_enqueue(sb_engine *e, const sb_graph_options *o, void *ends
     unsigned long long *ka = n2 ? (unsigned long long *)(base + o_ka) : nullptr, *kb = (unsigned long long *)(base + o_kb);
     uint32_t *other = (uint32_t *)(base + o_other), *hist = (uint32_t *)(base + o_hist), *hsum = (uint32_t *)(base + o_hsum);
 
-    int32_t *d_ends = (int32_t *)ends, *d_nbr = (int32_t *)nbr;
-    unsigned long long *d_rp = (unsigned long long *)row_ptr;
-    long long *d_counts = (long long *)counts;
-    if (host) { // the same launches into the engine's own buffers
-        if (ends) {
-            SB_TRY(s.buf[SBG_B_ENDS].grow(e, (size_t)maxB * 8));
-            d_ends = s.buf[SBG_B_ENDS].as<int32_t>();
-        }
-        if (row_ptr) {
-            SB_TRY(s.buf[SBG_B_ROWPTR].grow(e, (size_t)nscan * 8));
-            d_rp = s.buf[SBG_B_ROWPTR].as<unsigned long long>();
-        }
-        if (nbr) {
-            SB_TRY(s.buf[SBG_B_NBR].grow(e, (size_t)H * 8));
-            d_nbr = s.buf[SBG_B_NBR].as<int32_t>();
-        }
-        if (counts) {
-            SB_TRY(s.buf[SBG_B_COUNTS].grow(e, SB_GRAPH_COUNT_WORDS * 8));
-            d_counts = s.buf[SBG_B_COUNTS].as<long long>();
-        }
-    }
+    SbqMirror mir(e, host);
+    int32_t *d_ends = mir.out<int32_t>(SBG_B_ENDS, ends, (size_t)maxB * 8), *d_nbr = mir.out<int32_t>(SBG_B_NBR, nbr, (size_t)H * 8);
+    unsigned long long *d_rp = mir.out<unsigned long long>(SBG_B_ROWPTR, row_ptr, (size_t)nscan * 8);
+    long long *d_counts = mir.out<long long>(SBG_B_COUNTS, counts, SB_GRAPH_COUNT_WORDS * 8);
+    SB_TRY(mir.st);
     auto blocks = [](uint64_t k) { return (uint32_t)((k + SBG_BLOCK - 1u) / SBG_BLOCK); };
     SB_HIP(e, hipMemsetAsync(acc, 0, SBG_NACC * 8, e->stream));
     if (d_ends && maxB) SB_HIP(e, hipMemsetAsync(d_ends, 0xFF, (size_t)maxB * 8, e->stream)); // {-1, -1}
     if (deg) SB_HIP(e, hipMemsetAsync(deg, 0, nscan * 4, e->stream));
     if (n2) k_graph_fill<<<blocks(n2), SBG_BLOCK, 0, e->stream>>>(ka, n2, none);
     if (n) {
-        const uint32_t *dead = e->B && e->delete_gen ? e->d_dead_gen : nullptr; // as sb_load_buffers (fetch_dead) sees it
-        k_graph_edges<<<blocks(n), SBG_BLOCK, 0, e->stream>>>(s.buf[SBQ_B_TAB].as<uint32_t>(), n, s.buf[SBX_B_ROW].as<uint32_t>(), dead, e->d_broken,
+        k_graph_edges<<<blocks(n), SBG_BLOCK, 0, e->stream>>>(s.buf[SBQ_B_TAB].as<uint32_t>(), n, s.buf[SBX_B_ROW].as<uint32_t>(), sbq_dead(e), e->d_broken,
                                                               (flags & SB_GRAPH_SKIP_PENDING) ? 1u : 0u, maxB, maxP, d_ends, deg, ka, other, nd, acc);
     }
     if (d_rp) sbq_scan<unsigned long long>(e, deg, nscan, bsum, d_rp, nullptr);
@@ -195,14 +178,7 @@ static sb_status sbg_enqueue(sb_engine *e, const sb_graph_options *o, void *ends
         k_graph_counts<<<1, 64, 0, e->stream>>>(acc, d_counts);
     }
     SB_HIP(e, hipGetLastError());
-    if (host) {
-        if (ends) SB_HIP(e, hipMemcpyAsync(ends, d_ends, (size_t)maxB * 8, hipMemcpyDeviceToHost, e->stream));
-        if (row_ptr) SB_HIP(e, hipMemcpyAsync(row_ptr, d_rp, (size_t)nscan * 8, hipMemcpyDeviceToHost, e->stream));
-        if (nbr) SB_HIP(e, hipMemcpyAsync(nbr, d_nbr, (size_t)H * 8, hipMemcpyDeviceToHost, e->stream));
-        if (counts) SB_HIP(e, hipMemcpyAsync(counts, d_counts, SB_GRAPH_COUNT_WORDS * 8, hipMemcpyDeviceToHost, e->stream));
-        SB_HIP(e, hipStreamSynchronize(e->stream));
-    }
-    return SB_OK;
+    return mir.finish();
 }
 
 // what sb_get_info reads ("graph_kernel_vgprs", "graph_kernel_scratch_bytes", "graph_table_build_us")

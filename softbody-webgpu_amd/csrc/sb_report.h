@@ -1,7 +1,7 @@
 // sb_report.h -- what the engine's state calls (sb_state_io.hip), its four whole-scene reports (sb_summary.hip, sb_bodies.hip,
-// sb_contacts.hip, sb_body_summary.hip) and the cut (sb_cut.hip) share: the owner of their device buffers, the preflight of a
-// call, the scene tables of the latest upload, the exclusive scan and the wave's run counter.  What only one
-// report uses stays in its file.
+// sb_contacts.hip, sb_body_summary.hip), the cut (sb_cut.hip) and the graph (sb_graph.hip) share: the owner of their device
+// buffers, the preflight of a call, the host mirror of a report, the scene tables of the latest upload, the exclusive scan and
+// the wave's run counter.  What only one report uses stays in its file.
 #pragma once
 #include <vector>
 
@@ -92,6 +92,44 @@ sb_status sbq_preflight(sb_engine *e, const char *what, const O *o, const char *
         SB_FAIL(e, SB_ERR_INVALID, "%s: capacities above 2^31 are not %s", what, verb);
     return sbq_ready(e, what, why);
 }
+
+// the mask of beams removed by a delete pass as sb_load_buffers (fetch_dead) sees it: NULL while no pass has removed any
+inline const uint32_t *sbq_dead(const sb_engine *e) { return e->B && e->delete_gen ? e->d_dead_gen : nullptr; }
+
+// The host mirror of a report.  One *_enqueue serves both exports of a report: the _device one launches into the caller's device
+// memory, the host one into blocks of the engine's, copied to the caller after the launches.  The function names each buffer
+// once, through the mirror, and launches into what it gets back; with host == false every operation hands the caller's pointer
+// through and finish() does nothing.  A NULL caller pointer is "not wanted" and yields NULL.  out / in / inout record their first
+// failure in `st`: check it once, behind the last of them.
+struct SbqMirror {
+    SbqMirror(sb_engine *e, bool host) : e(e), host(host) {}
+    sb_status st = SB_OK;
+    // an output of `bytes` bytes in s.buf[buf] (grown to hold it)
+    template <class T> T *out(SbReportBuf buf, void *caller, size_t bytes) { return (T *)bind(buf, caller, bytes, bytes, false, true); }
+    // an output that lives `offset` bytes into a block the report owns anyway (the counts behind its accumulators)
+    template <class T> T *out_at(void *caller, void *block, size_t offset, size_t bytes)
+    {
+        if (!host || !caller) return (T *)caller;
+        back.push_back({caller, (char *)block + offset, bytes});
+        return (T *)back.back().dev;
+    }
+    // an input of `bytes` bytes, uploaded into s.buf[buf] (grown to cap_bytes >= bytes); inout: and copied back with the outputs
+    template <class T> const T *in(SbReportBuf buf, const void *caller, size_t bytes, size_t cap_bytes)
+    {
+        return (const T *)bind(buf, const_cast<void *>(caller), bytes, cap_bytes, true, false);
+    }
+    template <class T> T *inout(SbReportBuf buf, void *caller, size_t bytes) { return (T *)bind(buf, caller, bytes, bytes, true, true); }
+    // behind the launches: the outputs to the caller on e->stream, then the call's one hipStreamSynchronize
+    sb_status finish();
+
+private:
+    struct Copy { void *caller, *dev; size_t bytes; };
+    void *bind(SbReportBuf buf, void *caller, size_t bytes, size_t cap_bytes, bool upload, bool download);
+    sb_status stage(SbReportBuf buf, const void *caller, size_t bytes, size_t cap_bytes, bool upload);
+    sb_engine *e;
+    bool host;
+    std::vector<Copy> back;
+};
 
 // the most VGPRs (want_vgprs) or scratch bytes over the kernels; false: the runtime refused (the error is taken off the record)
 bool sbq_kernel_most(sb_engine *e, const std::vector<const void *> &kernels, bool want_vgprs, uint64_t *value);

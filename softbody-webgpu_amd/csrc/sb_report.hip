@@ -41,6 +41,34 @@ void sbs_release(sb_engine *e)
     e->sio = nullptr;
 }
 
+// ---------------------------------------------------------------- the host mirror
+
+sb_status SbqMirror::stage(SbReportBuf buf, const void *caller, size_t bytes, size_t cap_bytes, bool upload)
+{
+    SbDevBuf &b = e->sio->buf[buf];
+    SB_TRY(b.grow(e, cap_bytes));
+    if (upload) SB_HIP(e, hipMemcpyAsync(b.p, caller, bytes, hipMemcpyHostToDevice, e->stream));
+    return SB_OK;
+}
+
+void *SbqMirror::bind(SbReportBuf buf, void *caller, size_t bytes, size_t cap_bytes, bool upload, bool download)
+{
+    if (!host || !caller) return caller;
+    if (st == SB_OK) st = stage(buf, caller, bytes, cap_bytes, upload);
+    if (st != SB_OK) return nullptr;
+    void *dev = e->sio->buf[buf].p;
+    if (download) back.push_back({caller, dev, bytes});
+    return dev;
+}
+
+sb_status SbqMirror::finish()
+{
+    if (!host) return SB_OK;
+    for (const Copy &c : back) SB_HIP(e, hipMemcpyAsync(c.caller, c.dev, c.bytes, hipMemcpyDeviceToHost, e->stream));
+    SB_HIP(e, hipStreamSynchronize(e->stream));
+    return SB_OK;
+}
+
 // ---------------------------------------------------------------- preflight, kernel resources
 
 sb_status sbq_ready(sb_engine *e, const char *what, const char *why)

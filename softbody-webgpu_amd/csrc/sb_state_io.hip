@@ -166,7 +166,7 @@ static sb_status sbs_read(sb_engine *e, void *particles, void *beams, void *aliv
         const uint32_t *copy = nullptr;
         SB_TRY(sbr_copy_table(e, &copy));
         const uint32_t nslots = sb_user_beams(e);
-        const uint32_t *dead = e->B && e->delete_gen ? e->d_dead_gen : nullptr; // as sb_load_buffers (fetch_dead) sees it
+        const uint32_t *dead = sbq_dead(e);
         k_state_export_beams<<<(nslots + SBS_BLOCK - 1) / SBS_BLOCK, SBS_BLOCK, 0, e->stream>>>(
             e->sio->buf[SBS_B_SLOT].as<uint2>(), nslots, copy, e->beams.target, e->beams.last, e->beams.strain, e->beams.stress, dead, (float4 *)beams,
             (uint8_t *)alive);

@@ -310,28 +310,23 @@ static sb_status sbm_enqueue(sb_engine *e, const sb_summary_options *o, void *ro
     if (host) SB_TRY(s.buf[SBM_B_OUT].grow(e, ((size_t)8 + SB_SUMMARY_WORDS / 2) * sizeof(unsigned long long))); // 8 counts, then the row
     double *pcol = s.buf[SBM_B_PART].as<double>(), *bcol = pcol + (size_t)5 * np;
     unsigned long long *d_stat = s.buf[SBM_B_STAT].as<unsigned long long>(), *d_out = s.buf[SBM_B_OUT].as<unsigned long long>();
-    unsigned long long *d_counts = host ? d_out : (unsigned long long *)counts;
-    float *d_row = host ? (float *)(d_out + 8) : (float *)row;
+    SbqMirror mir(e, host);
+    unsigned long long *d_counts = mir.out_at<unsigned long long>(counts, d_out, 0, 8 * sizeof(uint64_t));
+    float *d_row = mir.out_at<float>(row, d_out, 8 * sizeof(uint64_t), SB_SUMMARY_WORDS * sizeof(float));
 
     k_summary_init<<<1, 64, 0, e->stream>>>(d_stat);
     const SbParticleArrays &c = e->part[e->cur];
     const SbmParticles sp{s.buf[SBQ_B_PINV].as<uint32_t>(), c.pos, c.vel, c.acc, s.np};
-    const SbmBeams sbm{s.buf[SBM_B_BLEAF].as<uint2>(), e->B && e->delete_gen ? e->d_dead_gen : nullptr /* as sb_load_buffers (fetch_dead) sees it */,
+    const SbmBeams sbm{s.buf[SBM_B_BLEAF].as<uint2>(), sbq_dead(e),
                        e->d_broken, e->beams.strain, e->beams.stress, s.sum_nb};
     SBM_SWITCH_LEAF(cp.W / np, (k_summary_particles<R_><<<(np + SBM_BLOCK - 1) / SBM_BLOCK, SBM_BLOCK, 0, e->stream>>>(sp, np, pcol, d_stat)));
     SBM_SWITCH_LEAF(cb.W / nb, (k_summary_beams<R_><<<(nb + SBM_BLOCK - 1) / SBM_BLOCK, SBM_BLOCK, 0, e->stream>>>(sbm, nb, bcol, d_stat)));
     SB_TRY(sbm_fold(e, cp, pcol, stride_p, 5u, &np));
     SB_TRY(sbm_fold(e, cb, bcol, nb, 1u, &nb));
-    k_summary_row<<<1, SBM_BLOCK, 0, e->stream>>>(pcol, stride_p, np, bcol, nb, d_stat, d_row,
-                                                  host || counts ? d_counts : nullptr);
+    k_summary_row<<<1, SBM_BLOCK, 0, e->stream>>>(pcol, stride_p, np, bcol, nb, d_stat, d_row, d_counts);
     SB_HIP(e, hipGetLastError());
     s.sum_partials = cp.m;
-    if (host) {
-        SB_HIP(e, hipMemcpyAsync(row, d_row, SB_SUMMARY_WORDS * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-        if (counts) SB_HIP(e, hipMemcpyAsync(counts, d_counts, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
-        SB_HIP(e, hipStreamSynchronize(e->stream));
-    }
-    return SB_OK;
+    return mir.finish();
 }
 
 // what sb_get_info reads ("summary_partials", "summary_table_build_us", "summary_kernel_vgprs", "summary_kernel_scratch_bytes")

@@ -10,6 +10,7 @@ import re
 
 import numpy as np
 
+from .device_binding import DeviceBinding
 from .layout import BEAM_STRIDE, LAYOUT_V1, METADATA_BYTES, PARTICLE_STRIDE, Buffers
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -314,9 +315,14 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
-class Engine:
+class Engine(DeviceBinding):
     """Host-side handle of one engine; method names follow engineWorker.ts
-    (writeBuffers / loadBuffers / frame) and the C ABI."""
+    (writeBuffers / loadBuffers / frame) and the C ABI.
+
+    Where a method takes device memory, device_binding.DeviceBinding checks it, orders the streams and binds a report's outputs,
+    as it does for BatchEngine.  A bool is never a device pointer: ValueError, unless the method gives True / False a meaning of
+    its own.  A tensor handed in with another shape than the documented one -- a flat one, say -- comes back as a view of the
+    documented shape over the same storage; one that has the shape comes back as the same object."""
 
     def __init__(self, bounds_size=1000.0, particle_radius=10.0, subticks=64, layout=LAYOUT_V1,
                  max_particles=65536, max_beams=65536, collision_mode=COLLIDE_GRID,
@@ -540,43 +546,6 @@ class Engine:
 
     # ---- the state in device memory (sb_read_state_device / sb_write_particles_device)
 
-    def _device_buffer(self, what, x, dtype, nbytes):
-        """A device pointer (int, passed as is) or a contiguous torch tensor on the engine's device with dtype `dtype` and at
-        least `nbytes` bytes: (pointer, is_tensor).  ValueError otherwise."""
-        if isinstance(x, int):
-            return x, False
-        import torch
-        if not isinstance(x, torch.Tensor):
-            raise ValueError("%s: a device pointer (int) or a torch tensor is needed, not %s" % (what, type(x).__name__))
-        dev = torch.device("cuda", self.device)
-        if x.device.type != "cuda" or (x.device.index if x.device.index is not None else torch.cuda.current_device()) != self.device:
-            raise ValueError("%s: the tensor is on %s, the engine on %s" % (what, x.device, dev))
-        if x.dtype != getattr(torch, dtype):
-            raise ValueError("%s: a %s tensor is needed, not %s" % (what, dtype, x.dtype))
-        if not x.is_contiguous():
-            raise ValueError("%s: the tensor must be contiguous" % what)
-        if x.element_size() * x.numel() < nbytes:
-            raise ValueError("%s: a tensor of at least %d bytes is needed, this one has %d" % (what, nbytes, x.element_size() * x.numel()))
-        return x.data_ptr(), True
-
-    def _streams(self):
-        """(torch's current stream, the engine's stream as a torch stream) on the engine's device."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        if self._ext_stream is None:
-            self._ext_stream = torch.cuda.ExternalStream(self.stream(), device=dev)
-        return torch.cuda.current_stream(dev), self._ext_stream
-
-    def _ordered(self, tensors, call):
-        """call() enqueues on the engine's stream; with tensors, that work is ordered behind torch's current stream and torch's
-        current stream behind it (no explicit sync needed on either side)."""
-        if not tensors:
-            return self._check(call())
-        cur, eng = self._streams()
-        eng.wait_stream(cur)
-        self._check(call())
-        cur.wait_stream(eng)
-
     def read_state_device(self, particles=None, beams=None, beam_alive=None):
         """The state sb_load_buffers would read back now, gathered on the GPU: particle records (6 f32: p.xy, v.xy, a.xy) at each
         particle's data index into `particles` (float32, max_particles * 24 bytes), {target_length, last_length, strain, stress}
@@ -667,15 +636,15 @@ class Engine:
         dev = torch.device("cuda", self.device)
         words = device_shapes(shapes, dev)
         n = int(words.shape[0])
-        if hit is True:
-            hit = torch.zeros(self.max_beams, dtype=torch.uint8, device=dev)
-        if counts is True:
-            counts = torch.empty(len(CUT_COUNT_FIELDS), dtype=torch.int64, device=dev)
-        hptr = self._device_buffer("cut: hit", hit, "uint8", self.max_beams)[0] if hit is not False else None
-        cptr = self._device_buffer("cut: counts", counts, "int64", len(CUT_COUNT_FIELDS) * 8)[0] if counts is not False else None
+        if hit is None or counts is None:
+            raise ValueError("cut: hit and counts are True, False, a device pointer (int) or a torch tensor, not None")
+        zeroed = lambda: torch.zeros(self.max_beams, dtype=torch.uint8, device=dev)   # (indices of no beam are not written)
+        outs, ptrs, _ = self._bind("cut", [
+            ("hit", zeroed if hit is True else None if hit is False else hit, hit is not False, (self.max_beams,), "uint8"),
+            ("counts", None if isinstance(counts, bool) else counts, counts is not False, (len(CUT_COUNT_FIELDS),), "int64")])
         self._ordered(True, lambda: load_library().sb_cut_device(self._h, ctypes.byref(o), vp(words.data_ptr() if n else None), n,
-                                                                 vp(hptr), vp(cptr)))
-        return (None if hit is False else hit), (None if counts is False else counts)
+                                                                 vp(ptrs[0]), vp(ptrs[1])))
+        return outs[0], outs[1]
 
     # ---- one summary row of the whole scene (sb_summary_device / sb_summary)
 
@@ -693,18 +662,13 @@ class Engine:
         least 8 elements (or a device pointer): the exact integer counts too (SUMMARY_COUNT_FIELDS), returned as (row, counts).
         partials: where the reduction is cut (0: the engine's choice; the result does not depend on it).  Only reads the
         engine, only enqueues; torch's current stream is ordered after it."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        if out is None:
-            out = torch.empty(SUMMARY_WORDS, dtype=torch.float32, device=dev)
         want_counts = counts is not None and counts is not False
-        if counts is True:
-            counts = torch.empty(SUMMARY_COUNT_WORDS, dtype=torch.int64, device=dev)
-        ptr, t = self._device_buffer("summary: out", out, "float32", SUMMARY_WORDS * 4)
-        cptr, ct = (self._device_buffer("summary: counts", counts, "int64", SUMMARY_COUNT_WORDS * 8) if want_counts else (None, False))
+        (out, counts), (ptr, cptr), t = self._bind("summary", [
+            ("out", out, True, (SUMMARY_WORDS,), "float32"),
+            ("counts", None if isinstance(counts, bool) else counts, want_counts, (SUMMARY_COUNT_WORDS,), "int64")])
         o = self._summary_options(partials)
         vp = ctypes.c_void_p
-        self._ordered(t or ct, lambda: load_library().sb_summary_device(self._h, ctypes.byref(o), vp(ptr), vp(cptr)))
+        self._ordered(t, lambda: load_library().sb_summary_device(self._h, ctypes.byref(o), vp(ptr), vp(cptr)))
         return (out, counts) if want_counts else out
 
     def summary_host(self, partials=0):
@@ -729,22 +693,10 @@ class Engine:
         returned in its place; not all three); a device pointer (int) or a contiguous torch tensor of that dtype and at least
         that many elements to write into.  Every word of an output is written.  Only reads the engine, only enqueues; torch's
         current stream is ordered after it."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        shapes = (("labels", labels, (self.max_particles,), "int32"), ("sizes", sizes, (self.max_particles, 2), "int32"),
-                  ("counts", counts, (BODY_WORDS,), "int64"))
-        outs, ptrs, tensors = [], [], False
-        for what, x, shape, dtype in shapes:
-            if x is False:
-                outs.append(None)
-                ptrs.append(None)
-                continue
-            if x is None or x is True:
-                x = torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
-            ptr, t = self._device_buffer("bodies: " + what, x, dtype, int(np.prod(shape)) * (8 if dtype == "int64" else 4))
-            outs.append(x)
-            ptrs.append(ptr)
-            tensors |= t
+        outs, ptrs, tensors = self._bind("bodies", [
+            (name, None if isinstance(x, bool) else x, x is not False, shape, dtype)   # (None / True: a new tensor)
+            for name, x, shape, dtype in (("labels", labels, (self.max_particles,), "int32"), ("sizes", sizes, (self.max_particles, 2), "int32"),
+                                          ("counts", counts, (BODY_WORDS,), "int64"))])
         vp = ctypes.c_void_p
         self._ordered(tensors, lambda: load_library().sb_bodies_device(self._h, None, vp(ptrs[0]), vp(ptrs[1]), vp(ptrs[2])))
         return (outs[0], outs[2], outs[1]) if sizes is not False else (outs[0], outs[2])
@@ -781,7 +733,6 @@ class Engine:
         adjacency: True, False or a pair (row_ptr, nbr) of those (then max_half_edges is nbr's rows).  Only reads the engine, only
         enqueues; torch's current stream is ordered after it."""
         import torch
-        dev = torch.device("cuda", self.device)
         if isinstance(adjacency, (tuple, list)):
             row_ptr, nbr = adjacency
         else:
@@ -793,20 +744,10 @@ class Engine:
             nbr = False
         if nbr is not False and nbr is not None and (row_ptr is False or row_ptr is None):
             raise ValueError("graph: nbr without row_ptr")
-        shapes = (("ends", ends, (self.max_beams, 2), "int32"), ("row_ptr", row_ptr, (self.max_particles + 1,), "int64"),
-                  ("nbr", nbr, (H, 2), "int32"), ("counts", counts, (GRAPH_COUNT_WORDS,), "int64"))
-        outs, ptrs, tensors = [], [], False
-        for what, x, shape, dtype in shapes:
-            if x is False or x is None:
-                outs.append(None)
-                ptrs.append(None)
-                continue
-            if x is True:
-                x = torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
-            ptr, t = self._device_buffer("graph: " + what, x, dtype, int(np.prod(shape)) * (8 if dtype == "int64" else 4))
-            outs.append(x)
-            ptrs.append(ptr)
-            tensors |= t
+        outs, ptrs, tensors = self._bind("graph", [
+            (name, None if isinstance(x, bool) else x, x is not False and x is not None, shape, dtype)   # (True: a new tensor)
+            for name, x, shape, dtype in (("ends", ends, (self.max_beams, 2), "int32"), ("row_ptr", row_ptr, (self.max_particles + 1,), "int64"),
+                                          ("nbr", nbr, (H, 2), "int32"), ("counts", counts, (GRAPH_COUNT_WORDS,), "int64"))])
         o = self._graph_options(H if ptrs[2] else 0, skip_pending)
         vp = ctypes.c_void_p
         self._ordered(tensors, lambda: load_library().sb_graph_device(self._h, ctypes.byref(o), vp(ptrs[0]), vp(ptrs[1]), vp(ptrs[2]), vp(ptrs[3])))
@@ -852,7 +793,6 @@ class Engine:
         and at least that many elements to write into.  Every word of an output is written.  Only reads the engine, only
         enqueues; torch's current stream is ordered after it."""
         import torch
-        dev = torch.device("cuda", self.device)
         maxp = self.max_particles
         if isinstance(pairs, torch.Tensor):
             if out is not None:
@@ -865,31 +805,15 @@ class Engine:
         max_pairs = int(pairs)
         if out is not None and max_pairs == 0:
             raise ValueError("contacts: out needs a pair list (pairs > 0)")
-        if labels is True:
-            labels = self.bodies(counts=False)[0]
-        elif labels is False:
-            labels = None
-        shapes = (("touch", touch, (maxp, CONTACT_WORDS), "int32"), ("counts", counts, (CONTACT_COUNT_WORDS,), "int64"),
-                  ("pairs", out if max_pairs else False, (max_pairs, 2), "int32"))
-        outs, ptrs, tensors = [], [], False
-        for what, x, shape, dtype in shapes:
-            if x is False:
-                outs.append(None)
-                ptrs.append(None)
-                continue
-            if x is None or x is True:
-                x = torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
-            ptr, t = self._device_buffer("contacts: " + what, x, dtype, int(np.prod(shape)) * (8 if dtype == "int64" else 4))
-            outs.append(x)
-            ptrs.append(ptr)
-            tensors |= t
-        lab = None
-        if labels is not None:
-            lab, t = self._device_buffer("contacts: labels", labels, "int32", maxp * 4)
-            tensors |= t
+        outs, ptrs, tensors = self._bind("contacts", [
+            ("touch", None if isinstance(touch, bool) else touch, touch is not False, (maxp, CONTACT_WORDS), "int32"),
+            ("counts", None if isinstance(counts, bool) else counts, counts is not False, (CONTACT_COUNT_WORDS,), "int64"),
+            ("pairs", out, max_pairs > 0, (max_pairs, 2), "int32"),
+            ("labels", (lambda: self.bodies(counts=False)[0]) if labels is True else None if labels is False else labels,
+             labels is not None and labels is not False, (maxp,), "int32")])
         o = self._contacts_options(max_pairs, other_body)
         vp = ctypes.c_void_p
-        self._ordered(tensors, lambda: load_library().sb_contacts_device(self._h, ctypes.byref(o), vp(lab), vp(ptrs[0]), vp(ptrs[2]),
+        self._ordered(tensors, lambda: load_library().sb_contacts_device(self._h, ctypes.byref(o), vp(ptrs[3]), vp(ptrs[0]), vp(ptrs[2]),
                                                                          vp(ptrs[1])))
         return (outs[0], outs[1], outs[2]) if max_pairs > 0 else (outs[0], outs[1])
 
@@ -936,31 +860,18 @@ class Engine:
         place; not all three); counts / rank: False -- left out; None or True -- a new tensor; each also a device pointer (int)
         or a contiguous torch tensor of that dtype and at least that many elements to write into.  Every word of an output is
         written.  Only reads the engine, only enqueues; torch's current stream is ordered after it."""
-        import torch
-        dev = torch.device("cuda", self.device)
         o = self._body_summary_options("body_summary", rows)
         rows = int(rows)
         want_counts, want_rank = counts is not False, rank is not False
-        shapes = (("out", out, (rows, BODY_SUMMARY_WORDS), "float32"),
-                  ("counts", counts, (rows, BODY_SUMMARY_COUNT_WORDS), "int64"), ("rank", rank, (self.max_particles,), "int32"))
-        outs, ptrs, tensors = [], [], False
-        for what, x, shape, dtype in shapes:
-            if x is False:
-                outs.append(None)
-                ptrs.append(None)
-                continue
-            if x is None or x is True:
-                x = torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
-            ptr, t = self._device_buffer("body_summary: " + what, x, dtype, int(np.prod(shape)) * (8 if dtype == "int64" else 4))
-            outs.append(x)
-            ptrs.append(ptr)
-            tensors |= t
-        lab = None
-        if labels is not None and labels is not True:
-            lab, t = self._device_buffer("body_summary: labels", labels, "int32", self.max_particles * 4)
-            tensors |= t
+        own = labels is not None and labels is not True   # (the engine's bodies are labelled inside the call: no buffer of the caller's)
+        outs, ptrs, tensors = self._bind("body_summary", [
+            (name, None if isinstance(x, bool) else x, x is not False, shape, dtype)   # (None / True: a new tensor)
+            for name, x, shape, dtype in (("out", out, (rows, BODY_SUMMARY_WORDS), "float32"),
+                                          ("counts", counts, (rows, BODY_SUMMARY_COUNT_WORDS), "int64"),
+                                          ("rank", rank, (self.max_particles,), "int32"))]
+            + [("labels", labels if own else None, own, (self.max_particles,), "int32")])
         vp = ctypes.c_void_p
-        self._ordered(tensors, lambda: load_library().sb_body_summary_device(self._h, ctypes.byref(o), vp(lab), vp(ptrs[0]), vp(ptrs[1]),
+        self._ordered(tensors, lambda: load_library().sb_body_summary_device(self._h, ctypes.byref(o), vp(ptrs[3]), vp(ptrs[0]), vp(ptrs[1]),
                                                                              vp(ptrs[2])))
         res = [outs[0]] + ([outs[1]] if want_counts else []) + ([outs[2]] if want_rank else [])
         return res[0] if len(res) == 1 else tuple(res)

@@ -12,6 +12,14 @@ def engine(sb, buf, bounds, **kw):
     return eng
 
 
+def in_place(got, given, shape):
+    """`got` is what a report returns for the tensor `given` that it wrote into: `given` itself where it has the documented
+    `shape`, else a view of that shape over the same storage"""
+    if tuple(given.shape) == tuple(shape):
+        return got is given
+    return tuple(got.shape) == tuple(shape) and got.data_ptr() == given.data_ptr() and got.untyped_storage().data_ptr() == given.untyped_storage().data_ptr()
+
+
 def read_only(sb, what, mk, kw, make, calls, keys=(), after=None):
     """frame, the report calls, frame == frame, frame: the read-back byte for byte, the summary row and its counts, the promise
     flags, the schedule and the info keys `keys`.  make(sb, case, **kw): the file's engine; calls(eng, case): the report calls;

@@ -135,7 +135,7 @@ def test_pair_list_truncation_and_other_body(sb):
             continue
         sentinel = torch.full((m + 3, 2), -77, dtype=torch.int32, device="cuda")
         touch, counts, pairs = eng.contacts(pairs=m, out=sentinel)
-        assert pairs is sentinel and (sentinel[m:] == -77).all()        # nothing at or behind max_pairs
+        assert rh.in_place(pairs, sentinel, (m, 2)) and (sentinel[m:] == -77).all()        # nothing at or behind max_pairs
         assert_contacts((touch.cpu().numpy(), sentinel[:m].cpu().numpy(), counts.cpu().numpy()), exp, "max_pairs %d" % m)
         if m == total + 7:
             assert (sentinel[total:m] == -1).all() and (sentinel[total - 1] >= 0).all()
@@ -253,11 +253,13 @@ def test_every_combination_of_outputs_and_labels_true(sb):
         pairs = torch.full((m + 2, 2), -77, dtype=torch.int32, device="cuda") if mask & 2 else None
         counts = torch.full((6,), -77, dtype=torch.int64, device="cuda") if mask & 4 else False
         got = eng.contacts(labels=bl, touch=touch, counts=counts, pairs=m if mask & 2 else 0, out=pairs)
-        assert got[0] is (touch if mask & 1 else None) and got[1] is (counts if mask & 4 else None) and len(got) == (3 if mask & 2 else 2)
+        assert got[0] is None if touch is False else rh.in_place(got[0], touch, (maxp, 4)), mask
+        assert got[1] is None if counts is False else rh.in_place(got[1], counts, (4,)), mask
+        assert len(got) == (3 if mask & 2 else 2)
         if mask & 1:
             assert np.array_equal(touch[:maxp].cpu().numpy(), exp[0]) and (touch[maxp:] == -77).all(), mask
         if mask & 2:
-            assert got[2] is pairs and np.array_equal(pairs[:m].cpu().numpy(), exp[1]) and (pairs[m:] == -77).all(), mask
+            assert rh.in_place(got[2], pairs, (m, 2)) and np.array_equal(pairs[:m].cpu().numpy(), exp[1]) and (pairs[m:] == -77).all(), mask
         if mask & 4:
             assert brief(counts[:4].cpu().numpy()) == brief(exp[2]) and (counts[4:] == -77).all(), mask
     # labels=True is bodies() first, on the same stream; torch's stream is ordered behind the call with no sync

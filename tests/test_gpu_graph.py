@@ -44,8 +44,8 @@ def device_graph(eng, H=None, **kw):
     nbr = torch.full((rows + 8, 2), -1515870811, dtype=torch.int32, device="cuda")
     counts = torch.full((4,), -77, dtype=torch.int64, device="cuda")
     out = eng.graph(ends=ends, adjacency=(row_ptr, nbr), max_half_edges=rows, counts=counts, **kw)
-    assert out[0] is ends and out[2] is nbr
-    got = [x.cpu().numpy() for x in out]
+    assert out[0] is ends and out[1] is row_ptr and out[3] is counts and rh.in_place(out[2], nbr, (rows, 2))
+    got = [x.cpu().numpy() for x in (ends, row_ptr, nbr, counts)]
     assert (got[2][rows:] == -1515870811).all(), "rows at or behind max_half_edges are not written"
     got[2] = got[2][:rows]
     return tuple(got)
