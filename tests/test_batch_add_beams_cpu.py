@@ -208,3 +208,122 @@ def test_header_equals_the_restatement_under_sanitizers(sb, tmp_path, san):
     assert not bad, [(i, got[i], want[i]) for i in bad[:5]]
     codes = [int(w.split()[0]) for w in want]
     assert min(codes.count(c) for c in (0, ref.EMPTY, ref.INVALID)) > 100
+
+
+# ---------------------------------------------------------------- the cases at full width and capacity: what each is named for
+
+def flagged_slots(buf, shapes):
+    import cut_ref
+    _, A, B = cut_ref.beam_ends(buf)
+    return np.flatnonzero(cut_ref.hits(shapes, A, B)).tolist()
+
+
+def with_bits(oracle, buf, slots, frames=1, mode=1):
+    """the oracle from `buf` with the delete bits of `slots` raised, `frames` frames on"""
+    r = oracle.OracleEngine(1000.0, 10.0, 64, buf.layout, mode, threads=2)
+    r.write_buffers(buf)
+    for s in slots:
+        bit = buf.max_particles + int(s)
+        r.delete[bit >> 5] |= np.uint32(1 << (bit & 31))
+    for _ in range(frames):
+        r.frame()
+    out = r.load_buffers(buf.copy())
+    assert np.isfinite(out.particles[buf.mapping[:buf.particle_count].astype(np.int64)]).all()
+    return out
+
+
+@pytest.mark.parametrize("name", list(cases.FLAG_WORD_CASES))
+def test_flag_words_case(sb, oracle, name):
+    case = cases.flag_words_case(sb, name)
+    bc, k = cases.FLAG_WORD_CASES[name]
+    buf = case["bufs"][0]
+    assert buf.beam_count == bc and bc % 32 == {"three-words": 30, "one-whole-word": 0, "two-words-one-bit-each": 31}[name]
+    assert flagged_slots(buf, case["cut"][0]) == case["cut_slots"] == [bc - 2, bc - 1], "the cut hits exactly the two slots in front of the new ones"
+    (edited, res, counts), = cases.expected(case, case["flags"])
+    assert counts == [k, 0, 0, 0] and (res >= 0).all() and len(set(res.tolist())) == k, "every row finds room"
+    words = sorted({s >> 5 for s in range(bc, bc + k)})
+    assert words == {"three-words": [0, 1, 2], "one-whole-word": [1], "two-words-one-bit-each": [0, 1]}[name]
+    assert edited.mapping[32 + bc:32 + bc + k].tolist() == res.tolist()
+    out = with_bits(oracle, edited, case["cut_slots"])
+    assert out.beam_count == bc + k - 2 and ref.alive_set(out)[res].all() and not ref.alive_set(out)[buf.mapping[32 + bc - 2:32 + bc].astype(int)].any()
+
+
+def test_upper_half_case(sb, oracle):
+    case = cases.upper_half_case(sb)
+    E, I, J = ref.EMPTY, ref.INVALID, ref.JOINED
+    exp = cases.expected(case, case["flags"])
+    assert case["joined_rows"][0] == [33, 40, 47, 62, 63] and case["joined_rows"][1] == case["joined_rows"][2] == [33, 40, 47, 61, 62]
+    ranks = []
+    for s, (edited, res, counts) in enumerate(exp):
+        inv, emp = cases.UPPER_SPECIAL[s], cases.UPPER_SPECIAL[(s + 1) % 3]
+        assert case["rows"][s].shape == (64, 8)
+        assert res[inv] == I and res[emp] == E and [j for j in range(64) if res[j] == J] == case["joined_rows"][s], s
+        assert counts == [57, 1, 5, 0] and (np.delete(res, [inv, emp] + case["joined_rows"][s]) >= 0).all()
+        ranks.append([int((res[:j] >= 0).sum()) for j in (31, 32, 33, 63)])
+        oracle_run(oracle, edited, frames=1)
+    assert len({tuple(r) for r in ranks}) == 3, "the ranks at the half boundary differ between the scenes"
+    # without the flag every one of those rows is added: the codes above come from SKIP_JOINED alone
+    assert all(c == [62, 1, 0, 0] for _, _, c in cases.expected(case, 0))
+
+
+def test_big_case(sb):
+    import graph_ref
+    case = cases.big_case(sb)
+    a, b, c = case["bufs"]
+    assert (a.beam_count, b.beam_count, c.beam_count) == (4056, 4096, 700)
+    assert sorted(np.flatnonzero(~ref.alive_set(a)).tolist()) == cases.BIG_FREE and min(cases.BIG_FREE) > 4000
+    per_word = np.bincount(np.asarray(cases.BIG_FREE) >> 5, minlength=128)
+    assert per_word.max() >= 5 and per_word[127] > 0 and cases.BIG_FREE[-1] == 4095, "several in one word; the last word; the last index"
+    for buf in case["bufs"]:
+        slots = buf.mapping[1024:1024 + buf.beam_count].astype(np.int64)
+        assert not np.array_equal(slots, np.sort(slots)) and not np.array_equal(buf.mapping[:1024], np.arange(1024)), "shuffled mappings"
+    (ea, ra, ca), (eb, rb, cb), (ec, rc, cc) = cases.expected(case, case["flags"])
+    F_ = ref.FULL
+    assert ra.tolist() == cases.BIG_FREE + [F_] * 24 and ca == [40, 0, 0, 24], "40 in ascending free order, then FULL"
+    assert rb.tolist() == [F_] * 64 and cb == [0, 0, 0, 64] and eb.beams.tobytes() == b.beams.tobytes() and np.array_equal(eb.mapping, b.mapping)
+    joined = [j for j in range(64) if rc[j] == ref.JOINED]
+    assert joined == case["joined_rows"] and cc == [48, 0, 16, 0]
+    lo, hi, step = case["late_slots"]
+    assert lo > 512 and c.beam_count >= 600
+    late = {frozenset((int(c.beams["a"][d]), int(c.beams["b"][d]))) for d in c.mapping[1024 + lo:1024 + hi:step].astype(int)}
+    early = {frozenset((int(c.beams["a"][d]), int(c.beams["b"][d]))) for d in c.mapping[1024:1024 + lo].astype(int)}
+    named = {frozenset((int(r[0]), int(r[1]))) for r in case["rows"][2][joined]}
+    assert named <= late and not (named & early), "only beams in slots above 512 join those pairs"
+    free_c = np.flatnonzero(~ref.alive_set(c))
+    assert [int(d) for d in rc if d >= 0] == free_c[:48].tolist()
+    for e in (ea, ec):
+        graph_ref.graph_ref(e)
+
+
+def test_no_index_case(sb, oracle):
+    case = cases.no_index_case(sb)
+    buf = case["bufs"][0]
+    assert buf.beam_count == buf.max_beams == 40
+    assert flagged_slots(buf, case["cut"][0]) == case["cut_slots"] and len(case["cut_slots"]) == 3
+    after = with_bits(oracle, buf, case["cut_slots"])
+    assert after.beam_count == 37
+    upload_alive = ref.alive_set(buf)
+    free = [d for d in range(40) if not ref.alive_set(after)[d] and not upload_alive[d]]
+    assert after.beam_count + 0 < after.max_beams and free == [], "room for a slot, no free index: the `added < len(free)` half refuses"
+    _, res, counts = ref.add_ref(after, case["rows"][0], 0, upload_alive)
+    assert res.tolist() == [ref.FULL] * 3 and counts == [0, 0, 0, 3]
+    edited, res, counts = ref.add_ref(after, case["rows"][0], 0, ref.alive_set(after))      # after a checkpoint
+    assert res.tolist() == sorted(case["cut_slots"]) and counts == [3, 0, 0, 0]
+    oracle_run(oracle, edited, frames=1)
+
+
+@pytest.mark.parametrize("cap", cases.ODD_CAPS)
+def test_odd_case(sb, oracle, cap):
+    case = cases.odd_case(sb, cap)
+    maxP, maxB = cap
+    buf = case["bufs"][1]
+    assert maxP % 2 == 1 and maxB % 4 != 0 and maxB % 32 != 0
+    assert maxP - 1 in buf.mapping[:buf.particle_count].tolist() and not ref.alive_set(buf)[maxB - 1]
+    exp = cases.expected(case, case["flags"])
+    edited, res, counts = exp[1]
+    rows = case["rows"][1]
+    assert all(maxP - 1 in (int(r[0]), int(r[1])) for r in rows) and len(rows) == cases.ODD_FREE + 2
+    free = np.flatnonzero(~ref.alive_set(buf)).tolist()
+    assert res.tolist() == free + [ref.FULL] * 2 and free[-1] == maxB - 1 and counts == [cases.ODD_FREE, 0, 0, 2]
+    assert exp[0][2] == exp[2][2] == [0, 0, 0, 0] and exp[0][1].tolist() == [ref.EMPTY] * len(rows)
+    oracle_run(oracle, edited, frames=1)
