@@ -772,7 +772,7 @@ sb_status sb_body_summary(sb_engine *e, const sb_body_summary_options *opts, con
  *   Limits: per scene at most SB_BATCH_MAX_PARTICLES particles and SB_BATCH_MAX_BEAMS beams (what one workgroup holds).
  *   When do calls return?  sb_batch_frame / _step / _delete_pass / _reset_device / _write_user_input[_device] /
  *     _set_physics_constants / _read_state_device / _write_particles_device / _fork_device / _checkpoint_device /
- *     _write_beams_device / _summary_device / _rollout_device / _bodies_device / _contacts_device only ENQUEUE on the batch's stream (device buffers must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
+ *     _write_beams_device / _add_beams_device / _add_particles_device / _summary_device / _rollout_device / _bodies_device / _contacts_device only ENQUEUE on the batch's stream (device buffers must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
  *     sb_batch_render_device only ENQUEUES (its device buffer must stay valid likewise); sb_batch_render_scene WAITS.
  *   Errors: every call returns an sb_status; sb_batch_last_error(b) gives the message (b == NULL: the last failed
  *     sb_batch_create of the calling thread).  Options are checked BEFORE a device is looked for. */
@@ -955,6 +955,61 @@ typedef struct sb_batch_new_beam { /* 32 bytes */
 sb_status sb_batch_add_beams_device(sb_batch *b, uint32_t flags, const void *device_rows /* [n_scenes][k] sb_batch_new_beam */, uint32_t k,
                                     void *device_result_i32 /* [n_scenes][k] int32 or NULL */,
                                     void *device_counts_i32 /* [n_scenes][SB_BATCH_ADD_COUNT_WORDS] int32 or NULL */);
+
+/* ---- adding particles on the device ("spawns"), undone by a reset ----
+ * sb_batch_add_particles_device -- the planner's "throw a ball at it": every scene gets its own k rows of new particles in ONE
+ * launch.  device_rows is [n_scenes][k] sb_batch_new_particle, k <= SB_BATCH_ADD_MAX.  The result names the DATA indices the new
+ * particles got: what a row of sb_batch_add_beams_device wants as a or b, so spawn -> weld makes a whole body in two launches.
+ *
+ * DEFINITION.  Scene i processes its k rows in row order.  P is metadata.particle_i_c as the call finds it.  Row j is decided in
+ * four steps.
+ * 1. Empty.  tag < 0 gives EMPTY.  The row is not counted.  (tag >= 0 is the caller's own: it is not stored.)
+ * 2. Invalid.  The row is INVALID if any of these hold: the scene was never uploaded; reserved != 0; x or y is not finite.
+ *    vx, vy, ax and ay are taken verbatim, non-finite values included, as an upload takes them.  A position outside the box is
+ *    legal: the step clamps it.
+ * 3. Blocked.  This step applies only with SKIP_TOUCHING.  "Touches" is the contact test of the step and of
+ *    sb_batch_contacts_device, in the same float expressions, with the batch's particle_radius: dist = sqrt(dx * dx + dy * dy),
+ *    touching when dist == 0 or dist < 2 * radius.  Let E(j) mean: row j touches the current position of a particle slot < P.
+ *    Row j is BLOCKED if E(j) holds.  Row j is also BLOCKED if it touches an earlier row i that is not EMPTY, not INVALID and not
+ *    E(i) -- whether or not row i was itself blocked by a still earlier row, or found no room.  The rule needs no serial pass and
+ *    does not depend on room; it is deliberately conservative.
+ * 4. Room.  The rows that survive are the candidates.  Their rank r is the number of candidates before them.  A candidate is
+ *    added when P + r < max_particles and there is an r-th free particle data index.  Otherwise it is FULL.
+ * Free data index.  A particle data index d is free when "holds a particle" [d] == 0 in the constant blob ("holds a particle" [d]
+ * == 1 iff a slot < P of the scene's particle mapping names d: DESIGN.md 5.26).
+ * What the r-th added particle writes.  It takes the r-th smallest free data index d and particle slot P + r.  Constant blob:
+ * particle mapping [P + r] = d, "holds a particle" [d] = 1.  Current state blob: the particle record at d = {x, y, vx, vy, ax, ay}.
+ * After all rows metadata.particle_i_c += added.  The reset state and its particle count are untouched, and so is every other
+ * metadata word (word 0, particle_v_c, is the constant 3 of the reference's record: nothing the batch reads depends on it).
+ * Outputs.  result[j] is d for an added row, else the code.  counts = {added, invalid, blocked, full}.  With DRY_RUN, result and
+ * counts are the real call's and nothing else is written.
+ *
+ * CONSEQUENCES.  Every later launch sees the particle as if it had been uploaded: frame, reports, render, read_state_device,
+ * write_particles_device, load_scene, add_beams and fork.  sb_batch_checkpoint_device keeps it (the reset particle count becomes
+ * P).  sb_batch_reset_device removes it: the slots from the reset particle count on give their data indices back, and with them
+ * goes every beam welded onto them, since such a beam is younger than the reset state.  Episodes of spawn, reset, spawn do not
+ * leak capacity.  sb_batch_fork_device copies it, with the source's reset particle count (SB_BATCH_FORK_AS_RESET: the source's P).
+ * A scene with no added row is left bit for bit as it was.
+ *
+ * Only ENQUEUES on the batch's stream.  Either output may be NULL.  Errors, before anything touches a device: SB_ERR_INVALID for a
+ * NULL handle, unknown flag bits, k > SB_BATCH_ADD_MAX, NULL rows with k > 0, a pointer that is not 4-byte aligned.  k == 0 is
+ * SB_OK: the counts rows are still written, as zeros.  sb_batch_get_info: "add_particles_kernel_vgprs",
+ * "add_particles_kernel_scratch_bytes". */
+typedef struct sb_batch_new_particle { /* 32 bytes */
+    int32_t tag;             /* < 0: empty row */
+    float x, y, vx, vy, ax, ay; /* the six floats of a particle record, taken verbatim as an upload takes them */
+    uint32_t reserved;       /* 0 */
+} sb_batch_new_particle;
+#define SB_BATCH_SPAWN_DRY_RUN 1u
+#define SB_BATCH_SPAWN_SKIP_TOUCHING 2u
+#define SB_BATCH_SPAWN_EMPTY (-1)
+#define SB_BATCH_SPAWN_INVALID (-2)
+#define SB_BATCH_SPAWN_BLOCKED (-3)
+#define SB_BATCH_SPAWN_FULL (-4)
+#define SB_BATCH_SPAWN_COUNT_WORDS 4u   /* added, invalid, blocked, full */
+sb_status sb_batch_add_particles_device(sb_batch *b, uint32_t flags, const void *device_rows /* [n_scenes][k] sb_batch_new_particle */,
+                                        uint32_t k, void *device_result_i32 /* [n_scenes][k] int32 or NULL */,
+                                        void *device_counts_i32 /* [n_scenes][SB_BATCH_SPAWN_COUNT_WORDS] int32 or NULL */);
 
 /* ---- per-scene summary rows and multi-frame rollouts on the device ----
  * sb_batch_summary_device -- one row of SB_BATCH_SUMMARY_WORDS floats per scene into device_out_f32[n_scenes][SB_BATCH_SUMMARY_WORDS],
@@ -1198,7 +1253,8 @@ sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream);
  * sb_batch_body_summary_device: "body_summary_words" (SB_BATCH_BODY_SUMMARY_WORDS), "body_summary_kernel_vgprs",
  * "body_summary_kernel_scratch_bytes", "body_summary_lds_bytes" (LDS of one workgroup at this batch's capacity);
  * sb_batch_graph_device: "graph_count_words", "graph_material_words", "graph_kernel_vgprs", "graph_kernel_scratch_bytes",
- * "graph_lds_bytes" (likewise) */
+ * "graph_lds_bytes" (likewise); sb_batch_add_particles_device: "add_particles_kernel_vgprs",
+ * "add_particles_kernel_scratch_bytes" */
 sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value);
 const char *sb_batch_last_error(const sb_batch *b);
 

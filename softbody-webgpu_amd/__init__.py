@@ -24,7 +24,8 @@ def __getattr__(name):
                 "CUT_NONE", "CUT_SEGMENT", "CUT_DISC", "CUT_COUNT_FIELDS", "cut_shapes"):  # Engine.cut() / BatchEngine.cut()
         from . import engine
         return getattr(engine, name)
-    if name in ("GRAPH_COUNT_FIELDS", "GRAPH_MATERIAL_FIELDS"):  # the words of BatchEngine.graph()'s counts and material rows
+    if name in ("GRAPH_COUNT_FIELDS", "GRAPH_MATERIAL_FIELDS",  # the words of BatchEngine.graph()'s counts and material rows
+                "SPAWN_EMPTY", "SPAWN_INVALID", "SPAWN_BLOCKED", "SPAWN_FULL", "SPAWN_COUNT_FIELDS"):  # BatchEngine.add_particles()
         from . import batch
         return getattr(batch, name)
     raise AttributeError(name)

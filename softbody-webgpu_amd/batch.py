@@ -42,6 +42,10 @@ ADD_ROW_WORDS = 8                                     # sb_batch_new_beam: {a, b
 ADD_DRY_RUN, ADD_LENGTH_CURRENT, ADD_SKIP_JOINED = 1, 2, 4   # SB_BATCH_ADD_*: the flags
 ADD_EMPTY, ADD_INVALID, ADD_JOINED, ADD_FULL = -1, -2, -3, -4   # SB_BATCH_ADD_*: what add_beams()'s result holds where no beam was added
 ADD_COUNT_FIELDS = ("added", "invalid", "joined", "full")     # the counts of add_beams(), in order (SB_BATCH_ADD_COUNT_WORDS of them)
+SPAWN_ROW_WORDS = 8                                   # sb_batch_new_particle: {tag, x, y, vx, vy, ax, ay, 0}
+SPAWN_DRY_RUN, SPAWN_SKIP_TOUCHING = 1, 2             # SB_BATCH_SPAWN_*: the flags
+SPAWN_EMPTY, SPAWN_INVALID, SPAWN_BLOCKED, SPAWN_FULL = -1, -2, -3, -4   # SB_BATCH_SPAWN_*: add_particles()'s result where no particle was added
+SPAWN_COUNT_FIELDS = ("added", "invalid", "blocked", "full")   # the counts of add_particles(), in order (SB_BATCH_SPAWN_COUNT_WORDS of them)
 GRAPH_SKIP_PENDING = 1                                # SB_GRAPH_SKIP_PENDING
 GRAPH_COUNT_WORDS, GRAPH_MATERIAL_WORDS = 4, 5        # SB_BATCH_GRAPH_COUNT_WORDS, SB_BATCH_GRAPH_MATERIAL_WORDS
 # the words of a row of graph()'s counts and of its material, in order (include/softbody.h, sb_batch_graph_device)
@@ -66,6 +70,55 @@ def new_beam_rows(pairs, spring, damp, yield_strain, strain_break_limit, length=
         f = torch.as_tensor(x, dtype=torch.float32, device=pairs.device).expand(n, k).contiguous()
         rows[:, :, col] = f.view(torch.int32)
     return rows
+
+
+def new_particle_rows(pos, vel=None, acc=None, valid=None):
+    """Rows for BatchEngine.add_particles() from a float32 torch tensor [N, k, 2] of positions, packed with torch ops on its
+    device: an int32 tensor [N, k, 8] in sb_batch_new_particle's layout (the floats as their bits).  vel, acc: float32 tensors that
+    broadcast to [N, k, 2], or None for zeros.  valid: a bool tensor that broadcasts to [N, k], False where the row is to be an
+    empty one (tag -1); None: every row counts (tag 0)."""
+    import torch
+    if not isinstance(pos, torch.Tensor) or pos.dtype != torch.float32 or pos.dim() != 3 or pos.shape[2] != 2:
+        raise ValueError("new_particle_rows: pos must be a float32 torch tensor [N, k, 2]")
+    n, k = pos.shape[0], pos.shape[1]
+    rows = torch.zeros((n, k, SPAWN_ROW_WORDS), dtype=torch.int32, device=pos.device)
+    for col, x in ((1, pos), (3, vel), (5, acc)):
+        if x is not None:
+            f = torch.as_tensor(x, dtype=torch.float32, device=pos.device).expand(n, k, 2).contiguous()
+            rows[:, :, col:col + 2] = f.view(torch.int32)
+    if valid is not None:
+        ok = torch.as_tensor(valid, dtype=torch.bool, device=pos.device).expand(n, k)
+        rows[:, :, 0] = torch.where(ok, 0, -1).to(torch.int32)
+    return rows
+
+
+def body_beam_rows(result, edges, length, spring, damp, yield_strain, strain_break_limit):
+    """Rows for BatchEngine.add_beams() that join the particles one add_particles() call made into a body: `result` is that
+    call's int32 [N, k] (data indices, or negative codes), `edges` an integer tensor [m, 2] of indices into its k rows -- the
+    template of the body, the same for every scene.  Returns new_beam_rows()'s format, int32 [N, m, 8], on result's device; a row
+    is an empty one wherever either endpoint's result is negative.  length and the material: numbers, or tensors that broadcast
+    to [N, m].  Nothing is read back: add_particles -> body_beam_rows -> add_beams spawns a body."""
+    import torch
+    if not isinstance(result, torch.Tensor) or result.dtype != torch.int32 or result.dim() != 2:
+        raise ValueError("body_beam_rows: result must be add_particles()'s int32 torch tensor [N, k]")
+    k = result.shape[1]
+    on_device = isinstance(edges, torch.Tensor) and edges.is_cuda
+    if on_device:
+        e = edges
+    else:
+        host = edges.numpy() if isinstance(edges, torch.Tensor) else edges
+        e = torch.as_tensor(np.asarray(host, dtype=np.int64))
+    if e.dim() != 2 or e.shape[1] != 2:
+        raise ValueError("body_beam_rows: edges must be [m, 2] indices into the %d rows of the spawn call" % k)
+    if not on_device and e.numel() and (int(e.min()) < 0 or int(e.max()) >= k):     # (host values: checked here, no read-back)
+        raise ValueError("body_beam_rows: edges must be [m, 2] indices into the %d rows of the spawn call" % k)
+    e = e.to(device=result.device, dtype=torch.int64)
+    # (edges already on the device are not read back: an index outside 0 .. k - 1 makes its row an empty one instead of wrapping)
+    outside = ((e < 0) | (e >= k)).any(dim=1)                          # [m]
+    pairs = result[:, e.clamp(0, max(k - 1, 0))]                      # [N, m, 2]
+    bad = (pairs < 0).any(dim=2, keepdim=True) | outside[None, :, None]
+    pairs = torch.where(bad, torch.full_like(pairs, -1), pairs)
+    return new_beam_rows(pairs.contiguous(), spring, damp, yield_strain, strain_break_limit, length=length)
 
 
 class SbBatchOptions(ctypes.Structure):
@@ -110,6 +163,7 @@ def load_library():
     L.sb_batch_write_beams_device.argtypes = [vp, vp, u32]
     L.sb_batch_cut_device.argtypes = [vp, u32, vp, u32, vp, vp]
     L.sb_batch_add_beams_device.argtypes = [vp, u32, vp, u32, vp, vp]
+    L.sb_batch_add_particles_device.argtypes = [vp, u32, vp, u32, vp, vp]
     L.sb_batch_summary_device.argtypes = [vp, vp]
     L.sb_batch_rollout_device.argtypes = [vp, u32, vp, vp]
     L.sb_batch_bodies_device.argtypes = [vp, vp, vp, vp]
@@ -432,6 +486,41 @@ class BatchEngine(DeviceBinding):
         vp = ctypes.c_void_p
         self._ordered(tensors or is_tensor, lambda: load_library().sb_batch_add_beams_device(self._h, flags, vp(ptr if k else None), k,
                                                                                              vp(ptrs[0]), vp(ptrs[1])))
+        return outs[0], outs[1]
+
+    # ---- adding particles (sb_batch_add_particles_device)
+    def add_particles(self, rows, *, skip_touching=False, dry_run=False, result=None, counts=None):
+        """Every scene gets its own k new particles ("spawns") in one launch.  `rows` is [n_scenes, k, 8], k <= ADD_MAX, in
+        sb_batch_new_particle's layout {tag, x, y, vx, vy, ax, ay, 0} -- the tag an integer, the six floats as their bits: an int32
+        or float32 (bits) torch tensor on the batch's device (new_particle_rows() packs one), or a tuple (device pointer, k).
+        include/softbody.h states the rule row by row: tag < 0 is an empty row; a row with a nonzero last word, or whose x or y
+        is not finite, or in a scene never uploaded, is SPAWN_INVALID; with skip_touching a row that touches a particle of the
+        scene (contacts()'s test), or an earlier row of the call that itself touches none, is SPAWN_BLOCKED; a row that finds no
+        free particle slot or data index is SPAWN_FULL.  dry_run: report only.  Returns (result, counts): result int32
+        [n_scenes, k], the new particle's DATA index -- what a row of add_beams() names -- or the code; counts int32 [n_scenes, 4]
+        (SPAWN_COUNT_FIELDS).  An added particle is from then on a particle of the scene as if uploaded; checkpoint() keeps it,
+        reset() removes it together with every beam welded onto it, fork() copies it.  result / counts: a device pointer (int)
+        or a contiguous int32 torch tensor to write into.  Only enqueues."""
+        import torch
+        n = self.n_scenes
+        if isinstance(rows, tuple):
+            ptr, k = int(rows[0]), int(rows[1])
+            is_tensor = False
+        else:
+            if not isinstance(rows, torch.Tensor) or rows.dtype not in (torch.int32, torch.float32):
+                raise ValueError("add_particles: rows must be an int32 / float32 torch tensor [n_scenes, k, 8] or (device pointer, k)")
+            if rows.dim() != 3 or rows.shape[0] != n or rows.shape[2] != SPAWN_ROW_WORDS or rows.shape[1] > ADD_MAX:
+                raise ValueError("add_particles: rows must be [n_scenes = %d, k <= %d, 8], not %s" % (n, ADD_MAX, tuple(rows.shape)))
+            k = int(rows.shape[1])
+            ptr, is_tensor = self._device_buffer("add_particles: rows", rows, None, n * k * SPAWN_ROW_WORDS * 4)
+        if not 0 <= k <= ADD_MAX:
+            raise ValueError("add_particles: k is %d, not in 0 .. %d" % (k, ADD_MAX))
+        outs, ptrs, tensors = self._bind("add_particles", [("result", result, True, (n, k), "int32"),
+                                                           ("counts", counts, True, (n, len(SPAWN_COUNT_FIELDS)), "int32")])
+        flags = (SPAWN_DRY_RUN if dry_run else 0) | (SPAWN_SKIP_TOUCHING if skip_touching else 0)
+        vp = ctypes.c_void_p
+        self._ordered(tensors or is_tensor, lambda: load_library().sb_batch_add_particles_device(self._h, flags, vp(ptr if k else None), k,
+                                                                                                 vp(ptrs[0]), vp(ptrs[1])))
         return outs[0], outs[1]
 
     # ---- statistics per body (sb_batch_body_summary_device; DESIGN.md 5.16)

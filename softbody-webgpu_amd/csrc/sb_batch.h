@@ -1,7 +1,7 @@
 // sb_batch.h -- what the files of the sb_batch_* group share: the device memory of a batch and its host object
 // (sb_batch.hip: upload, stepping, state I/O; sb_batch_render.hip: pictures; sb_batch_summary.hip: per-scene statistics, rollouts;
 // sb_batch_bodies.hip: connected bodies; sb_batch_contacts.hip: particle and wall contacts; sb_batch_body_summary.hip: statistics per
-// body; sb_batch_cut.hip / sb_batch_add.hip: cuts and welds; sb_batch_graph.hip: the beam graph), and what the four report kernels have in common: the scene header each of them opens with (sbb_scene), the float <->
+// body; sb_batch_cut.hip / sb_batch_add.hip / sb_batch_spawn.hip: cuts, welds and spawned particles; sb_batch_graph.hip: the beam graph), and what the four report kernels have in common: the scene header each of them opens with (sbb_scene), the float <->
 // ordered-key codec of their extremes and the width of the pinned summation tree (sb_summary_math.h), the contact test (sb_touch); on the host the
 // cache behind the *_kernel_vgprs / *_kernel_scratch_bytes info keys (sbb_kernel_res) and the alignment test of the entry points
 // (sbb_misaligned4).  All of it is inline; what only one kernel uses stays in that kernel's file.
@@ -17,8 +17,8 @@
 #include "sb_summary_math.h" // sbb_finite, sbb_fkey / sbb_unkey, SBB_QNAN, sbb_pow2_at_least: the codec of the report rows
 
 // ---------------------------------------------------------------- device memory of a batch
-// Per scene: 32 metadata words (the 112 bytes of the reference's metadata buffer, then SB_BM_B0 / SB_BM_LOADED), a CONSTANT blob
-// (what only an upload writes) and a STATE blob (what stepping changes), the latter twice: current and reset.  Everything a
+// Per scene: 32 metadata words (the 112 bytes of the reference's metadata buffer, then SB_BM_B0 / SB_BM_LOADED / SB_BM_P0), a CONSTANT blob
+// (what only an upload or an added beam / particle writes) and a STATE blob (what stepping changes), the latter twice: current and reset.  Everything a
 // beam or a particle owns is stored at its DATA index, so the state export / import are plain row copies.
 #define SB_BM_WORDS 32u
 #define SB_BM_P 1u       // metadata.particle_i_c
@@ -26,6 +26,7 @@
 #define SB_BM_CONSTS 12u // 8 physics constants, 8 user input words
 #define SB_BM_B0 28u     // beam slots of the reset state (the latest upload, checkpoint or fork); k_batch_reset alone reads it
 #define SB_BM_LOADED 29u // 1 once uploaded
+#define SB_BM_P0 30u     // particle slots of the reset state; k_batch_reset alone reads it (P0 <= P: only sb_batch_add_particles_device raises P)
 #define SB_BATCH_MAT_ROW 6u // length, spring, damp, yield, limit, 1/length
 
 struct SbBatchView {
@@ -145,7 +146,7 @@ struct sb_batch {
     uint64_t frames_done = 0, substeps_done = 0;
     int scenes_per_cu = 0, vgprs = 0, scratch = 0;
     SbBatchRender *render = nullptr; // what the renderer keeps between calls (made at the first render)
-    SbbKernelRes render_res, summary_res, bodies_res, contacts_res, body_summary_res, cut_res, add_res, graph_res; // of k_batch_render, k_batch_summary, ...
+    SbbKernelRes render_res, summary_res, bodies_res, contacts_res, body_summary_res, cut_res, add_res, graph_res, spawn_res; // of k_batch_render, k_batch_summary, ...
     bool body_summary_lds_allowed = false; // k_batch_body_summary may be launched with more than 64 KiB of LDS (asked for at the first such launch)
 };
 
@@ -202,5 +203,7 @@ bool sbb_body_summary_info(sb_batch *b, const char *key, uint64_t *value); // sb
 bool sbb_cut_info(sb_batch *b, const char *key, uint64_t *value);       // sb_batch_get_info's cut keys; false: not one of them
 // sb_batch_add.hip
 bool sbb_add_info(sb_batch *b, const char *key, uint64_t *value);       // sb_batch_get_info's add_beams keys; false: not one of them
+// sb_batch_spawn.hip
+bool sbb_spawn_info(sb_batch *b, const char *key, uint64_t *value);     // sb_batch_get_info's add_particles keys; false: not one of them
 // sb_batch_graph.hip
 bool sbb_graph_info(sb_batch *b, const char *key, uint64_t *value);     // sb_batch_get_info's graph keys; false: not one of them

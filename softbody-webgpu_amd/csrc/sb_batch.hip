@@ -327,10 +327,25 @@ __global__ __launch_bounds__(SBB_BLOCK) void k_batch_reset(SbBatchView V, const 
     if (mask && mask[scene] == 0) return;
     uint32_t *meta = V.meta + (size_t)scene * SB_BM_WORDS;
     if (meta[SB_BM_LOADED] == 0u) return;
+    // particles added since the reset state was made (sb_batch_add_particles_device) give their data indices back: the slots
+    // P0 .. P - 1.  (Every thread has read P before thread 0 writes it: the barrier.)
+    const uint32_t P = min(SB_AGENT_LOAD(&meta[SB_BM_P]), V.maxP), P0 = SB_AGENT_LOAD(&meta[SB_BM_P0]);
+    __syncthreads();
+    if (P > P0) {
+        unsigned char *cst = V.cst + (size_t)scene * V.cst_bytes;
+        const uint32_t *pmap = (const uint32_t *)(cst + V.o_pmap);
+        for (uint32_t slot = P0 + threadIdx.x; slot < P; slot += SBB_BLOCK) {
+            const uint32_t d = pmap[slot];
+            if (d < V.maxP) (cst + V.o_pex)[d] = 0;
+        }
+    }
     uint4 *s = (uint4 *)(V.st + (size_t)scene * V.st_bytes);
     const uint4 *r = (const uint4 *)(V.rst + (size_t)scene * V.st_bytes);
     for (uint32_t i = threadIdx.x; i < V.st_bytes / 16u; i += SBB_BLOCK) s[i] = r[i];
-    if (threadIdx.x == 0u) meta[SB_BM_B] = meta[SB_BM_B0];
+    if (threadIdx.x == 0u) {
+        meta[SB_BM_B] = meta[SB_BM_B0];
+        if (P > P0) SB_AGENT_STORE(&meta[SB_BM_P], P0);
+    }
 }
 
 struct SbBatchWords8 {
@@ -421,6 +436,7 @@ __global__ __launch_bounds__(SBB_BLOCK) void k_batch_fork_scatter(SbBatchView V,
         uint32_t *meta = V.meta + (size_t)scene * SB_BM_WORDS;
         if (k < SB_BM_CONSTS || k == SB_BM_LOADED || ((flags & SB_BATCH_FORK_CONSTANTS) && k < SB_BM_CONSTS + 8u)) meta[k] = m[k];
         else if (k == SB_BM_B0) meta[k] = as_reset ? m[SB_BM_B] : m[SB_BM_B0];
+        else if (k == SB_BM_P0) meta[k] = as_reset ? m[SB_BM_P] : m[SB_BM_P0];
     }
     row += SB_BM_WORDS * 4u;
     sbb_copy16(V.cst + (size_t)scene * V.cst_bytes, row, V.cst_bytes);
@@ -437,7 +453,7 @@ __global__ __launch_bounds__(SBB_BLOCK) void k_batch_checkpoint(SbBatchView V, c
     uint32_t *meta = V.meta + (size_t)scene * SB_BM_WORDS;
     if (meta[SB_BM_LOADED] == 0u) return;
     sbb_copy16(V.rst + (size_t)scene * V.st_bytes, V.st + (size_t)scene * V.st_bytes, V.st_bytes);
-    if (blockIdx.y == 0u && threadIdx.x == 0u) meta[SB_BM_B0] = meta[SB_BM_B];
+    if (blockIdx.y == 0u && threadIdx.x == 0u) meta[SB_BM_B0] = meta[SB_BM_B], meta[SB_BM_P0] = meta[SB_BM_P];
 }
 
 __global__ __launch_bounds__(SBB_BLOCK) void k_batch_import_beams(SbBatchView V, const float *__restrict__ beams, uint32_t fields)
@@ -692,6 +708,7 @@ sb_status sb_batch_write_scene(sb_batch *b, uint32_t first, uint32_t count, cons
     unsigned char *pex = cst + V.o_pex, *bex = cst + V.o_bex, *balive = st + V.o_balive;
     memcpy(meta, md, SB_METADATA_BYTES);
     meta[SB_BM_B0] = B;
+    meta[SB_BM_P0] = P;
     meta[SB_BM_LOADED] = 1u;
     for (uint32_t s = 0; s < maxP; s++) pmap[s] = sbc::map_get(layout, mp, s);
     for (uint32_t s = 0; s < maxB; s++) bmap[s] = sbc::map_get(layout, mp, (size_t)maxP + s);
@@ -990,6 +1007,7 @@ sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value)
     else if (sbb_body_summary_info(b, key, value)) return SB_OK;
     else if (sbb_cut_info(b, key, value)) return SB_OK;
     else if (sbb_add_info(b, key, value)) return SB_OK;
+    else if (sbb_spawn_info(b, key, value)) return SB_OK;
     else if (sbb_graph_info(b, key, value)) return SB_OK;
     else SB_FAIL(b, SB_ERR_INVALID, "sb_batch_get_info: unknown key '%s'", key);
     return SB_OK;
