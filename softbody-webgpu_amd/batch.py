@@ -466,27 +466,8 @@ class BatchEngine(DeviceBinding):
         result int32 [n_scenes, k], the new beam's DATA index or the code; counts int32 [n_scenes, 4] (ADD_COUNT_FIELDS).  An
         added beam is from then on a beam of the scene as if uploaded; checkpoint() keeps it, reset() removes it, fork() copies
         it.  result / counts: a device pointer (int) or a contiguous int32 torch tensor to write into.  Only enqueues."""
-        import torch
-        n = self.n_scenes
-        if isinstance(rows, tuple):
-            ptr, k = int(rows[0]), int(rows[1])
-            is_tensor = False
-        else:
-            if not isinstance(rows, torch.Tensor) or rows.dtype not in (torch.int32, torch.float32):
-                raise ValueError("add_beams: rows must be an int32 / float32 torch tensor [n_scenes, k, 8] or (device pointer, k)")
-            if rows.dim() != 3 or rows.shape[0] != n or rows.shape[2] != ADD_ROW_WORDS or rows.shape[1] > ADD_MAX:
-                raise ValueError("add_beams: rows must be [n_scenes = %d, k <= %d, 8], not %s" % (n, ADD_MAX, tuple(rows.shape)))
-            k = int(rows.shape[1])
-            ptr, is_tensor = self._device_buffer("add_beams: rows", rows, None, n * k * ADD_ROW_WORDS * 4)
-        if not 0 <= k <= ADD_MAX:
-            raise ValueError("add_beams: k is %d, not in 0 .. %d" % (k, ADD_MAX))
-        outs, ptrs, tensors = self._bind("add_beams", [("result", result, True, (n, k), "int32"),
-                                                       ("counts", counts, True, (n, len(ADD_COUNT_FIELDS)), "int32")])
         flags = (ADD_DRY_RUN if dry_run else 0) | (ADD_LENGTH_CURRENT if length_current else 0) | (ADD_SKIP_JOINED if skip_joined else 0)
-        vp = ctypes.c_void_p
-        self._ordered(tensors or is_tensor, lambda: load_library().sb_batch_add_beams_device(self._h, flags, vp(ptr if k else None), k,
-                                                                                             vp(ptrs[0]), vp(ptrs[1])))
-        return outs[0], outs[1]
+        return self._add_rows("add_beams", load_library().sb_batch_add_beams_device, rows, ADD_ROW_WORDS, flags, result, counts, ADD_COUNT_FIELDS)
 
     # ---- adding particles (sb_batch_add_particles_device; DESIGN.md 5.26)
     def add_particles(self, rows, *, skip_touching=False, dry_run=False, result=None, counts=None):
@@ -501,6 +482,13 @@ class BatchEngine(DeviceBinding):
         (SPAWN_COUNT_FIELDS).  An added particle is from then on a particle of the scene as if uploaded; checkpoint() keeps it,
         reset() removes it together with every beam welded onto it, fork() copies it.  result / counts: a device pointer (int)
         or a contiguous int32 torch tensor to write into.  Only enqueues."""
+        flags = (SPAWN_DRY_RUN if dry_run else 0) | (SPAWN_SKIP_TOUCHING if skip_touching else 0)
+        return self._add_rows("add_particles", load_library().sb_batch_add_particles_device, rows, SPAWN_ROW_WORDS, flags, result, counts,
+                              SPAWN_COUNT_FIELDS)
+
+    def _add_rows(self, what, entry, rows, row_words, flags, result, counts, count_fields):
+        """add_beams() / add_particles() (`what`: the name in the messages, `entry`: its function of the library): k rows of
+        row_words words per scene in, (result [n_scenes, k], counts [n_scenes, len(count_fields)]) out"""
         import torch
         n = self.n_scenes
         if isinstance(rows, tuple):
@@ -508,19 +496,17 @@ class BatchEngine(DeviceBinding):
             is_tensor = False
         else:
             if not isinstance(rows, torch.Tensor) or rows.dtype not in (torch.int32, torch.float32):
-                raise ValueError("add_particles: rows must be an int32 / float32 torch tensor [n_scenes, k, 8] or (device pointer, k)")
-            if rows.dim() != 3 or rows.shape[0] != n or rows.shape[2] != SPAWN_ROW_WORDS or rows.shape[1] > ADD_MAX:
-                raise ValueError("add_particles: rows must be [n_scenes = %d, k <= %d, 8], not %s" % (n, ADD_MAX, tuple(rows.shape)))
+                raise ValueError("%s: rows must be an int32 / float32 torch tensor [n_scenes, k, 8] or (device pointer, k)" % what)
+            if rows.dim() != 3 or rows.shape[0] != n or rows.shape[2] != row_words or rows.shape[1] > ADD_MAX:
+                raise ValueError("%s: rows must be [n_scenes = %d, k <= %d, 8], not %s" % (what, n, ADD_MAX, tuple(rows.shape)))
             k = int(rows.shape[1])
-            ptr, is_tensor = self._device_buffer("add_particles: rows", rows, None, n * k * SPAWN_ROW_WORDS * 4)
+            ptr, is_tensor = self._device_buffer(what + ": rows", rows, None, n * k * row_words * 4)
         if not 0 <= k <= ADD_MAX:
-            raise ValueError("add_particles: k is %d, not in 0 .. %d" % (k, ADD_MAX))
-        outs, ptrs, tensors = self._bind("add_particles", [("result", result, True, (n, k), "int32"),
-                                                           ("counts", counts, True, (n, len(SPAWN_COUNT_FIELDS)), "int32")])
-        flags = (SPAWN_DRY_RUN if dry_run else 0) | (SPAWN_SKIP_TOUCHING if skip_touching else 0)
+            raise ValueError("%s: k is %d, not in 0 .. %d" % (what, k, ADD_MAX))
+        outs, ptrs, tensors = self._bind(what, [("result", result, True, (n, k), "int32"),
+                                                ("counts", counts, True, (n, len(count_fields)), "int32")])
         vp = ctypes.c_void_p
-        self._ordered(tensors or is_tensor, lambda: load_library().sb_batch_add_particles_device(self._h, flags, vp(ptr if k else None), k,
-                                                                                                 vp(ptrs[0]), vp(ptrs[1])))
+        self._ordered(tensors or is_tensor, lambda: entry(self._h, flags, vp(ptr if k else None), k, vp(ptrs[0]), vp(ptrs[1])))
         return outs[0], outs[1]
 
     # ---- statistics per body (sb_batch_body_summary_device)

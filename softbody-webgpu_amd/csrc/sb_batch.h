@@ -1,10 +1,11 @@
 // sb_batch.h -- what the files of the sb_batch_* group share: the device memory of a batch and its host object
 // (sb_batch.hip: upload, stepping, state I/O; sb_batch_render.hip: pictures; sb_batch_summary.hip: per-scene statistics, rollouts;
 // sb_batch_bodies.hip: connected bodies; sb_batch_contacts.hip: particle and wall contacts; sb_batch_body_summary.hip: statistics per
-// body; sb_batch_cut.hip / sb_batch_add.hip / sb_batch_spawn.hip: cuts, welds and spawned particles; sb_batch_graph.hip: the beam graph), and what the four report kernels have in common: the scene header each of them opens with (sbb_scene), the float <->
+// body; sb_batch_cut.hip / sb_batch_add.hip / sb_batch_spawn.hip: cuts, welds and spawned particles, the latter two on
+// sb_batch_alloc.h, the allocator of their data indices; sb_batch_graph.hip: the beam graph), and what the four report kernels have in common: the scene header each of them opens with (sbb_scene), the float <->
 // ordered-key codec of their extremes and the width of the pinned summation tree (sb_summary_math.h), the contact test (sb_touch); on the host the
-// cache behind the *_kernel_vgprs / *_kernel_scratch_bytes info keys (sbb_kernel_res) and the alignment test of the entry points
-// (sbb_misaligned4).  All of it is inline; what only one kernel uses stays in that kernel's file.
+// *_kernel_vgprs / *_kernel_scratch_bytes info keys (sbb_kernel_info), the alignment test of the entry points (sbb_misaligned4)
+// and the opening checks of the editing calls (sbb_edit_entry).  All of it is inline; what only one kernel uses stays in that kernel's file.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -161,20 +162,21 @@ static inline sb_status check_launch(sb_batch *b, const char *what)
     return SB_OK;
 }
 
-// sb_batch_get_info's "<report>_kernel_vgprs" (want_vgprs) / "<report>_kernel_scratch_bytes" of `kernel`, whose answers `r` keeps;
-// 0 where the runtime does not tell (its error is taken off the record: it must not resurface in a later launch check)
-static inline uint64_t sbb_kernel_res(sb_batch *b, SbbKernelRes &r, const void *kernel, bool want_vgprs)
+// sb_batch_get_info's "<name>_kernel_vgprs" / "<name>_kernel_scratch_bytes" of `kernel`: its registers and scratch bytes as the
+// runtime reports them, which `r` keeps; 0 where the runtime does not tell (its error is taken off the record: it must not resurface
+// in a later launch check).  false: `key` is neither of the two.
+static inline bool sbb_kernel_info(sb_batch *b, const char *name, const void *kernel, SbbKernelRes &r, const char *key, uint64_t *value)
 {
+    const std::string k(key), n(name);
+    const bool want_vgprs = k == n + "_kernel_vgprs";
+    if (!want_vgprs && k != n + "_kernel_scratch_bytes") return false;
     if (r.vgprs < 0) {
         hipFuncAttributes fa{};
-        if (hipSetDevice(b->device) != hipSuccess || hipFuncGetAttributes(&fa, kernel) != hipSuccess) {
-            (void)hipGetLastError();
-            return 0;
-        }
-        r.vgprs = fa.numRegs;
-        r.scratch = (int)fa.localSizeBytes;
+        if (hipSetDevice(b->device) == hipSuccess && hipFuncGetAttributes(&fa, kernel) == hipSuccess) r.vgprs = fa.numRegs, r.scratch = (int)fa.localSizeBytes;
+        else (void)hipGetLastError();
     }
-    return (uint64_t)std::max(want_vgprs ? r.vgprs : r.scratch, 0);
+    *value = (uint64_t)std::max(want_vgprs ? r.vgprs : r.scratch, 0);
+    return true;
 }
 
 // "is one of these device pointers not 4-byte aligned?" (null is aligned: an output that is not asked for)
@@ -185,25 +187,34 @@ static inline bool sbb_misaligned4(std::initializer_list<const void *> ptrs)
     return (low & 3u) != 0;
 }
 
+// The opening checks of an editing call (sb_batch_cut_device, sb_batch_add_beams_device, sb_batch_add_particles_device; `call`:
+// its name in the messages), then the batch's device is selected: a null batch, flag bits outside `known` (known_text: the
+// message's list of them), more than k_max `items` ("rows", "shapes") per scene, null items with k > 0, a pointer of `aligned`
+// that is not 4-byte aligned (aligned_text: their names).
+static inline sb_status sbb_edit_entry(sb_batch *b, const char *call, uint32_t flags, uint32_t known, const char *known_text, uint32_t k,
+                                       uint32_t k_max, const char *items, const void *device_items, std::initializer_list<const void *> aligned,
+                                       const char *aligned_text)
+{
+    if (!b) SB_FAIL(b, SB_ERR_INVALID, "%s: null batch", call);
+    if (flags & ~known) SB_FAIL(b, SB_ERR_INVALID, "%s: flags 0x%x: only %s known", call, flags, known_text);
+    if (k > k_max) SB_FAIL(b, SB_ERR_INVALID, "%s: %u %s per scene, at most %u", call, k, items, k_max);
+    if (k && !device_items) SB_FAIL(b, SB_ERR_INVALID, "%s: null %s", call, items);
+    if (sbb_misaligned4(aligned)) SB_FAIL(b, SB_ERR_INVALID, "%s: %s must be 4-byte aligned", call, aligned_text);
+    SB_HIP(b, hipSetDevice(b->device));
+    return SB_OK;
+}
+
 static inline uint32_t up16(uint32_t x) { return (x + 15u) & ~15u; }
 static inline uint32_t cdivb(uint32_t a, uint32_t b) { return (a + b - 1u) / b; }
 
-// sb_batch_render.hip
-void sbb_render_release(sb_batch *b);                                   // sb_batch_destroy
-bool sbb_render_info(sb_batch *b, const char *key, uint64_t *value);    // sb_batch_get_info's render keys; false: not one of them
-// sb_batch_summary.hip
-bool sbb_summary_info(sb_batch *b, const char *key, uint64_t *value);   // sb_batch_get_info's summary keys; false: not one of them
-// sb_batch_bodies.hip
-bool sbb_bodies_info(sb_batch *b, const char *key, uint64_t *value);    // sb_batch_get_info's bodies keys; false: not one of them
-// sb_batch_contacts.hip
-bool sbb_contacts_info(sb_batch *b, const char *key, uint64_t *value);  // sb_batch_get_info's contacts keys; false: not one of them
-// sb_batch_body_summary.hip
-bool sbb_body_summary_info(sb_batch *b, const char *key, uint64_t *value); // sb_batch_get_info's body summary keys; false: not one of them
-// sb_batch_cut.hip
-bool sbb_cut_info(sb_batch *b, const char *key, uint64_t *value);       // sb_batch_get_info's cut keys; false: not one of them
-// sb_batch_add.hip
-bool sbb_add_info(sb_batch *b, const char *key, uint64_t *value);       // sb_batch_get_info's add_beams keys; false: not one of them
-// sb_batch_spawn.hip
-bool sbb_spawn_info(sb_batch *b, const char *key, uint64_t *value);     // sb_batch_get_info's add_particles keys; false: not one of them
-// sb_batch_graph.hip
-bool sbb_graph_info(sb_batch *b, const char *key, uint64_t *value);     // sb_batch_get_info's graph keys; false: not one of them
+void sbb_render_release(sb_batch *b); // sb_batch_render.hip, for sb_batch_destroy
+// sb_batch_get_info's keys of one file each (sb_batch_render.hip, sb_batch_summary.hip, ...); false: not one of them
+bool sbb_render_info(sb_batch *b, const char *key, uint64_t *value);
+bool sbb_summary_info(sb_batch *b, const char *key, uint64_t *value);
+bool sbb_bodies_info(sb_batch *b, const char *key, uint64_t *value);
+bool sbb_contacts_info(sb_batch *b, const char *key, uint64_t *value);
+bool sbb_body_summary_info(sb_batch *b, const char *key, uint64_t *value);
+bool sbb_cut_info(sb_batch *b, const char *key, uint64_t *value);
+bool sbb_add_info(sb_batch *b, const char *key, uint64_t *value);   // sb_batch_add.hip: add_beams
+bool sbb_spawn_info(sb_batch *b, const char *key, uint64_t *value); // sb_batch_spawn.hip: add_particles
+bool sbb_graph_info(sb_batch *b, const char *key, uint64_t *value);

@@ -1,38 +1,35 @@
 // sb_batch_add.hip -- adding beams ("welds") in every scene of a batch in ONE launch, the inverse of a cut
 // (sb_batch_add_beams_device of include/softbody.h; gfx950, wave64).
 //
-// One workgroup per scene.  All lanes build, in LDS, the data -> slot inverse of the particle mapping and a bitmap of the FREE beam
-// data indices (balive == 0 in the current AND in the reset state blob), with a popcount prefix over its words.  A lane per row
+// One workgroup per scene.  All lanes build, in LDS, the data -> slot inverse of the particle mapping and the bitmap of the FREE beam
+// data indices (balive == 0 in the current AND in the reset state blob) with its prefix (sb_batch_alloc.h).  A lane per row
 // takes the row's verdict (sb_batch_add_math.h) and its endpoint slots; with SB_BATCH_ADD_SKIP_JOINED all lanes then sweep the live
-// beam slots against the rows' unordered slot pairs.  Wave 0 finishes: in-call duplicates, ranks from one ballot, the r-th free
-// index from the prefix, the rows of the constant and the state blob, the pending bits of the new slots, the count.  Everything
-// behind the float length is integers; every store is a plain vector store of this workgroup into its own scene.
-#include <string>
-
+// beam slots against the rows' unordered slot pairs.  Wave 0 finishes: in-call duplicates, the allocator's finish (rank, room, the
+// r-th free index, result and counts), the rows of the constant and the state blob, the pending bits of the new slots, the count.
+// Everything behind the float length is integers; every store is a plain vector store of this workgroup into its own scene.
 #include "sb_batch.h"
 #include "sb_batch_add_math.h"
 
 #define SBW_BLOCK 256u
-enum { SBW_ADDED, SBW_N_INVALID, SBW_N_JOINED, SBW_N_FULL, SBW_NWORDS };
 
-static_assert(SBW_NWORDS == SB_BATCH_ADD_COUNT_WORDS, "the count words of sb_batch_add_beams_device");
+static_assert(SBA_COUNT_WORDS == SB_BATCH_ADD_COUNT_WORDS, "the count words of sb_batch_add_beams_device: added, invalid, joined, full");
 static_assert(SB_BATCH_ADD_MAX == 64u, "a lane of wave 0 per row, one ballot for the ranks");
-static_assert(sizeof(sb_batch_new_beam) == SBW_ROW_WORDS * 4u, "a row is 8 words");
-static_assert(sbw::SBW_EMPTY == SB_BATCH_ADD_EMPTY && sbw::SBW_INVALID == SB_BATCH_ADD_INVALID && sbw::SBW_JOINED == SB_BATCH_ADD_JOINED &&
-                  sbw::SBW_FULL == SB_BATCH_ADD_FULL,
+static_assert(sizeof(sb_batch_new_beam) == SBA_ROW_WORDS * 4u, "a row is 8 words");
+static_assert(sba::EMPTY == SB_BATCH_ADD_EMPTY && sba::INVALID == SB_BATCH_ADD_INVALID && sbw::SBW_JOINED == SB_BATCH_ADD_JOINED &&
+                  sba::FULL == SB_BATCH_ADD_FULL,
               "the row codes");
 static_assert(sbw::SBW_DRY_RUN == SB_BATCH_ADD_DRY_RUN && sbw::SBW_LENGTH_CURRENT == SB_BATCH_ADD_LENGTH_CURRENT &&
                   sbw::SBW_SKIP_JOINED == SB_BATCH_ADD_SKIP_JOINED,
               "the flags");
 static_assert(SB_BATCH_MAX_PARTICLES <= 0xFFFFu, "the inverse holds slots in 16 bits, 0xFFFF: no slot");
+static_assert(SB_BATCH_MAX_BEAMS <= 32u * SBA_MAX_WORDS, "the free bitmap of the beam data indices");
 
 #define SBW_NO_SLOT 0xFFFFu
 // words of the fixed part of a workgroup's LDS: rows, per row {verdict, length, current distance, endpoint slots, unordered key},
-// the rows a live beam joins (two words), the free count
-#define SBW_FIXED_WORDS (SB_BATCH_ADD_MAX * SBW_ROW_WORDS + 5u * SB_BATCH_ADD_MAX + 2u + 1u)
-static __host__ __device__ inline uint32_t sbw_bitmap_words(uint32_t maxB) { return (maxB + 31u) >> 5; }
+// the rows a live beam joins (two words)
+#define SBW_FIXED_WORDS (SB_BATCH_ADD_MAX * SBA_ROW_WORDS + 5u * SB_BATCH_ADD_MAX + 2u)
 // LDS of a workgroup: the fixed part, the bitmap and its prefix (one word more), the inverse (16 bits per particle data index)
-static inline uint32_t sbw_lds_bytes(uint32_t maxP, uint32_t maxB) { return (SBW_FIXED_WORDS + 2u * sbw_bitmap_words(maxB) + 1u + ((maxP + 1u) >> 1)) * 4u; }
+static inline uint32_t sbw_lds_bytes(uint32_t maxP, uint32_t maxB) { return (SBW_FIXED_WORDS + 2u * sba::bitmap_words(maxB) + 1u + ((maxP + 1u) >> 1)) * 4u; }
 
 __global__ __launch_bounds__(SBW_BLOCK) void k_batch_add_beams(SbBatchView V, const uint32_t *__restrict__ rows, uint32_t k, uint32_t flags,
                                                                int32_t *__restrict__ result, int32_t *__restrict__ counts)
@@ -40,17 +37,16 @@ __global__ __launch_bounds__(SBW_BLOCK) void k_batch_add_beams(SbBatchView V, co
     extern __shared__ __attribute__((aligned(16))) uint32_t sbw_lds[];
     const uint32_t scene = blockIdx.x, tid = threadIdx.x;
     if (scene >= V.n_scenes) return;
-    const uint32_t maxP = V.maxP, maxB = V.maxB, nbw = sbw_bitmap_words(maxB), inv_words = (maxP + 1u) >> 1;
+    const uint32_t maxP = V.maxP, maxB = V.maxB, nbw = sba::bitmap_words(maxB), inv_words = (maxP + 1u) >> 1;
     uint32_t *s_row = sbw_lds;                                    // [64][8]
-    int32_t *s_verd = (int32_t *)(s_row + SB_BATCH_ADD_MAX * SBW_ROW_WORDS); // [64]
+    int32_t *s_verd = (int32_t *)(s_row + SB_BATCH_ADD_MAX * SBA_ROW_WORDS); // [64]
     float *s_len = (float *)(s_verd + SB_BATCH_ADD_MAX);          // [64] resolved length
     float *s_cur = s_len + SB_BATCH_ADD_MAX;                      // [64] current distance
     uint32_t *s_ends = (uint32_t *)(s_cur + SB_BATCH_ADD_MAX);    // [64] slot(a) | slot(b) << 16
     uint32_t *s_key = s_ends + SB_BATCH_ADD_MAX;                  // [64] min slot | max slot << 16
     uint32_t *s_joined = s_key + SB_BATCH_ADD_MAX;                // [2] rows a live beam joins
-    uint32_t *s_nfree = s_joined + 2u;                            // [1]
-    uint32_t *s_free = s_nfree + 1u;                              // [nbw] bit d: beam data index d is free
-    uint32_t *s_pref = s_free + nbw;                              // [nbw + 1] free indices in front of each word
+    uint32_t *s_free = s_joined + 2u;                             // [nbw] bit d: beam data index d is free
+    uint32_t *s_pref = s_free + nbw;                              // [nbw + 1] free indices in front of each word; [nbw]: all
     uint16_t *s_inv = (uint16_t *)(s_pref + nbw + 1u);            // [maxP] data index -> slot
 
     const SbbScene hd = sbb_scene(V, scene);
@@ -63,43 +59,20 @@ __global__ __launch_bounds__(SBW_BLOCK) void k_batch_add_beams(SbBatchView V, co
     const bool dry = (flags & SB_BATCH_ADD_DRY_RUN) != 0u, skip_joined = (flags & SB_BATCH_ADD_SKIP_JOINED) != 0u;
 
     // ---- rows, the inverse (empty), the free bitmap
-    for (uint32_t i = tid; i < k * SBW_ROW_WORDS; i += SBW_BLOCK) s_row[i] = rows[(size_t)scene * k * SBW_ROW_WORDS + i];
+    for (uint32_t i = tid; i < k * SBA_ROW_WORDS; i += SBW_BLOCK) s_row[i] = rows[(size_t)scene * k * SBA_ROW_WORDS + i];
     for (uint32_t i = tid; i < inv_words; i += SBW_BLOCK) ((uint32_t *)s_inv)[i] = 0xFFFFFFFFu;
     if (tid < 2u) s_joined[tid] = 0u;
-    {
-        // (the alive bytes, four to a load: a state blob's row of them is padded to 16 bytes; bytes at and past maxB are not indices)
-        const uint32_t *cur4 = (const uint32_t *)(st + V.o_balive), *rst4 = (const uint32_t *)(rst + V.o_balive);
-        for (uint32_t w = tid; w < nbw; w += SBW_BLOCK) {
-            uint32_t bits = 0u;
-            for (uint32_t q = 0; q < 8u; q++) {
-                const uint32_t d0 = 32u * w + 4u * q;
-                if (d0 >= maxB) break;
-                const uint32_t live = cur4[d0 >> 2] | rst4[d0 >> 2];
-                for (uint32_t e = 0; e < 4u; e++)
-                    if (d0 + e < maxB && ((live >> (8u * e)) & 0xffu) == 0u) bits |= 1u << (4u * q + e);
-            }
-            s_free[w] = hd.loaded ? bits : 0u;
-        }
-    }
-    __syncthreads();
+    // (the alive bytes of the current and of the reset state: a state blob's row of them is padded to 16 bytes)
+    sba::fill_free(s_free, s_pref, nbw, (const uint32_t *)(st + V.o_balive), (const uint32_t *)(rst + V.o_balive), maxB, hd.loaded != 0u, tid, SBW_BLOCK);
     for (uint32_t s = tid; s < P; s += SBW_BLOCK) {
         const uint32_t d = g_pmap[s];
         if (d < maxP) s_inv[d] = (uint16_t)s; // (an upload is refused unless its particle data indices are inside the capacity, each once)
-    }
-    if (tid == 0u) {
-        uint32_t run = 0u;
-        for (uint32_t w = 0; w < nbw; w++) {
-            s_pref[w] = run;
-            run += __popc(s_free[w]);
-        }
-        s_pref[nbw] = run;
-        s_nfree[0] = run;
     }
     __syncthreads();
 
     // ---- the verdict of each row, a lane per row
     if (tid < k) {
-        const uint32_t *w = s_row + tid * SBW_ROW_WORDS;
+        const uint32_t *w = s_row + tid * SBA_ROW_WORDS;
         const int32_t a = (int32_t)w[0], b = (int32_t)w[1];
         uint32_t sa = SBW_NO_SLOT, sb = SBW_NO_SLOT;
         float cur = 0.0f, len = 0.0f;
@@ -125,7 +98,7 @@ __global__ __launch_bounds__(SBW_BLOCK) void k_batch_add_beams(SbBatchView V, co
             if (d >= maxB) continue; // (an upload is refused unless its beam data indices are inside the capacity)
             const uint32_t w = g_bword[d], x = w & 0xffffu, y = w >> 16, key = x < y ? x | (y << 16) : y | (x << 16);
             for (uint32_t q = 0; q < k; q++)
-                if (s_verd[q] == sbw::SBW_CANDIDATE && s_key[q] == key) atomicOr(&s_joined[q >> 5], 1u << (q & 31u));
+                if (s_verd[q] == sba::CANDIDATE && s_key[q] == key) atomicOr(&s_joined[q >> 5], 1u << (q & 31u));
         }
         __syncthreads();
     }
@@ -133,40 +106,20 @@ __global__ __launch_bounds__(SBW_BLOCK) void k_batch_add_beams(SbBatchView V, co
 
     // ---- duplicates inside the call, room, the r-th free index
     const bool row = tid < k;
-    int32_t verd = row ? s_verd[tid] : (int32_t)sbw::SBW_EMPTY;
-    if (skip_joined && verd == sbw::SBW_CANDIDATE) {
+    int32_t verd = row ? s_verd[tid] : (int32_t)sba::EMPTY;
+    if (skip_joined && verd == sba::CANDIDATE) {
         bool joined = ((s_joined[tid >> 5] >> (tid & 31u)) & 1u) != 0u;
         // (an earlier candidate row of the same pair: were it joined itself, by a beam or by a row before it, so would this one be)
-        for (uint32_t i = 0; i < tid && !joined; i++) joined = s_verd[i] == sbw::SBW_CANDIDATE && s_key[i] == s_key[tid];
+        for (uint32_t i = 0; i < tid && !joined; i++) joined = s_verd[i] == sba::CANDIDATE && s_key[i] == s_key[tid];
         if (joined) verd = sbw::SBW_JOINED;
     }
-    const unsigned long long m_cand = __ballot(verd == sbw::SBW_CANDIDATE);
-    const uint32_t r = (uint32_t)__popcll(m_cand & ((1ull << tid) - 1ull)), n_free = s_nfree[0];
-    uint32_t d = 0u;
-    if (verd == sbw::SBW_CANDIDATE) {
-        if (Bc + r < maxB && r < n_free) {
-            uint32_t lo = 0u, hi = nbw; // the word w with s_pref[w] <= r < s_pref[w + 1]
-            while (hi - lo > 1u) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (s_pref[mid] <= r) lo = mid;
-                else hi = mid;
-            }
-            uint32_t bits = s_free[lo];
-            for (uint32_t t = r - s_pref[lo]; t != 0u; t--) bits &= bits - 1u;
-            d = 32u * lo + (uint32_t)__builtin_ctz(bits);
-        } else {
-            verd = sbw::SBW_FULL;
-        }
-    }
-    const bool add = verd == sbw::SBW_CANDIDATE;
-    const unsigned long long m_add = __ballot(add), m_inv = __ballot(verd == sbw::SBW_INVALID), m_join = __ballot(verd == sbw::SBW_JOINED),
-                             m_full = __ballot(verd == sbw::SBW_FULL);
-    const uint32_t n_add = (uint32_t)__popcll(m_add);
+    const sba::Finish f = sba::finish(verd, tid, Bc, maxB, s_free, s_pref, nbw);
+    const uint32_t d = f.index, n_add = f.n_added;
 
     if (!dry && n_add != 0u) {
-        if (add && d < maxB) {
-            const uint32_t slot = Bc + r;
-            const uint32_t *w = s_row + tid * SBW_ROW_WORDS;
+        if (f.add && d < maxB) {
+            const uint32_t slot = Bc + f.rank;
+            const uint32_t *w = s_row + tid * SBA_ROW_WORDS;
             const float len = s_len[tid];
             float *m = (float *)(cst + V.o_bmat) + (size_t)SB_BATCH_MAT_ROW * d;
             g_bword[d] = s_ends[tid];
@@ -187,36 +140,20 @@ __global__ __launch_bounds__(SBW_BLOCK) void k_batch_add_beams(SbBatchView V, co
         }
         if (tid == 0u) V.meta[(size_t)scene * SB_BM_WORDS + SB_BM_B] = Bc + n_add;
     }
-    if (result && row) result[(size_t)scene * k + tid] = add ? (int32_t)d : verd;
-    if (counts && tid == 0u) {
-        int32_t *c = counts + (size_t)scene * SBW_NWORDS;
-        c[SBW_ADDED] = (int32_t)n_add;
-        c[SBW_N_INVALID] = __popcll(m_inv);
-        c[SBW_N_JOINED] = __popcll(m_join);
-        c[SBW_N_FULL] = __popcll(m_full);
-    }
+    sba::report(f, row, tid, scene, k, result, counts);
 }
 
 // ---------------------------------------------------------------- host
 bool sbb_add_info(sb_batch *b, const char *key, uint64_t *value)
 {
-    const std::string k(key);
-    if (k == "add_beams_kernel_vgprs" || k == "add_beams_kernel_scratch_bytes")
-        *value = sbb_kernel_res(b, b->add_res, (const void *)k_batch_add_beams, k == "add_beams_kernel_vgprs");
-    else return false;
-    return true;
+    return sbb_kernel_info(b, "add_beams", (const void *)k_batch_add_beams, b->add_res, key, value);
 }
 
 sb_status sb_batch_add_beams_device(sb_batch *b, uint32_t flags, const void *device_rows, uint32_t k, void *device_result_i32, void *device_counts_i32)
 {
-    if (!b) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_add_beams_device: null batch");
-    if (flags & ~(SB_BATCH_ADD_DRY_RUN | SB_BATCH_ADD_LENGTH_CURRENT | SB_BATCH_ADD_SKIP_JOINED))
-        SB_FAIL(b, SB_ERR_INVALID, "sb_batch_add_beams_device: flags 0x%x: only SB_BATCH_ADD_DRY_RUN, _LENGTH_CURRENT and _SKIP_JOINED are known", flags);
-    if (k > SB_BATCH_ADD_MAX) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_add_beams_device: %u rows per scene, at most %u", k, SB_BATCH_ADD_MAX);
-    if (k && !device_rows) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_add_beams_device: null rows");
-    if (sbb_misaligned4({device_rows, device_result_i32, device_counts_i32}))
-        SB_FAIL(b, SB_ERR_INVALID, "sb_batch_add_beams_device: rows, result and counts must be 4-byte aligned");
-    SB_HIP(b, hipSetDevice(b->device));
+    SB_TRY(sbb_edit_entry(b, "sb_batch_add_beams_device", flags, SB_BATCH_ADD_DRY_RUN | SB_BATCH_ADD_LENGTH_CURRENT | SB_BATCH_ADD_SKIP_JOINED,
+                          "SB_BATCH_ADD_DRY_RUN, _LENGTH_CURRENT and _SKIP_JOINED are", k, SB_BATCH_ADD_MAX, "rows", device_rows,
+                          {device_rows, device_result_i32, device_counts_i32}, "rows, result and counts"));
     k_batch_add_beams<<<b->opt.n_scenes, SBW_BLOCK, sbw_lds_bytes(b->V.maxP, b->V.maxB), b->stream>>>(
         b->V, (const uint32_t *)device_rows, k, flags, (int32_t *)device_result_i32, (int32_t *)device_counts_i32);
     return check_launch(b, "sb_batch_add_beams_device");

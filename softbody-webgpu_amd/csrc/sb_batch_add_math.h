@@ -3,31 +3,18 @@
 // range, self, the reserved word, the length's resolution and "a finite number > 0".  Host and device: integers and comparisons
 // plus, on the host, the current distance as the beam phase takes it -- float32, one rounding per operator in the order written
 // (the library builds with -ffp-contract=off; tests/batch_add_check.cpp builds it the same way), the square root IEEE.  Every
-// comparison with a NaN is false, so a NaN length is no length.  Header-only and HIP-free on the host.
+// comparison with a NaN is false, so a NaN length is no length.  Header-only and HIP-free on the host.  The row's width, the
+// codes every adding call shares and word_as_float are sb_batch_alloc.h's.
 #pragma once
-#include <stdint.h>
-#include <string.h>
+#include "sb_batch_alloc.h"
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define SBW_HD __host__ __device__ inline
-#else
-#define SBW_HD inline
-#endif
-
-#define SBW_ROW_WORDS 8u // {a, b, length, spring, damp, yield_strain, strain_break_limit, reserved}: sb_batch_new_beam
-
+// (a row: {a, b, length, spring, damp, yield_strain, strain_break_limit, reserved}, sb_batch_new_beam)
 namespace sbw {
 
-// a row's verdict: SBW_CANDIDATE (it goes on to the joined test and to the room) or SB_BATCH_ADD_EMPTY / _INVALID
-enum { SBW_CANDIDATE = 0, SBW_EMPTY = -1, SBW_INVALID = -2, SBW_JOINED = -3, SBW_FULL = -4 };
+using sba::word_as_float;
+// a row's verdict: sba::CANDIDATE (it goes on to the joined test and to the room) or SB_BATCH_ADD_EMPTY / _INVALID
+enum { SBW_JOINED = sba::OWN };
 enum { SBW_DRY_RUN = 1u, SBW_LENGTH_CURRENT = 2u, SBW_SKIP_JOINED = 4u };
-
-SBW_HD float word_as_float(uint32_t w)
-{
-    float f;
-    memcpy(&f, &w, sizeof f);
-    return f;
-}
 
 // the current distance of two particle records: sb_length(pb.x - pa.x, pb.y - pa.y), the beam phase's own expression (the
 // kernel calls sb_length itself; this is the host's restatement of it for the check program)
@@ -38,28 +25,28 @@ inline float distance(float ax, float ay, float bx, float by)
 }
 
 // "a finite number > 0" (NaN fails the first comparison, +inf the second)
-SBW_HD bool length_ok(float x) { return x > 0.0f && x <= 3.4028234663852886e38f; }
+SBA_HD bool length_ok(float x) { return x > 0.0f && x <= 3.4028234663852886e38f; }
 
 // range and self: the endpoints are two different data indices inside the capacity (a negative b is above it as unsigned)
-SBW_HD bool ends_in_range(int32_t a, int32_t b, uint32_t max_particles)
+SBA_HD bool ends_in_range(int32_t a, int32_t b, uint32_t max_particles)
 {
     return a >= 0 && (uint32_t)a < max_particles && (uint32_t)b < max_particles && a != b;
 }
 
-// The verdict of row `w` (SBW_ROW_WORDS words).  loaded: the scene was uploaded; holds_a / holds_b: the endpoint is the data index
+// The verdict of row `w` (SBA_ROW_WORDS words).  loaded: the scene was uploaded; holds_a / holds_b: the endpoint is the data index
 // of a particle slot < P (only looked at when the ends are in range); current: their current distance (only looked at when both
 // hold a particle).  *length: the resolved rest length of a candidate.
-SBW_HD int row_verdict(const uint32_t *w, uint32_t flags, uint32_t max_particles, bool loaded, bool holds_a, bool holds_b, float current,
+SBA_HD int row_verdict(const uint32_t *w, uint32_t flags, uint32_t max_particles, bool loaded, bool holds_a, bool holds_b, float current,
                        float *length)
 {
     const int32_t a = (int32_t)w[0], b = (int32_t)w[1];
     *length = 0.0f;
-    if (a < 0) return SBW_EMPTY;
-    if (!loaded || !ends_in_range(a, b, max_particles) || !holds_a || !holds_b || w[7] != 0u) return SBW_INVALID;
+    if (a < 0) return sba::EMPTY;
+    if (!loaded || !ends_in_range(a, b, max_particles) || !holds_a || !holds_b || w[7] != 0u) return sba::INVALID;
     const float len = (flags & SBW_LENGTH_CURRENT) ? current : word_as_float(w[2]);
-    if (!length_ok(len)) return SBW_INVALID;
+    if (!length_ok(len)) return sba::INVALID;
     *length = len;
-    return SBW_CANDIDATE;
+    return sba::CANDIDATE;
 }
 
 } // namespace sbw

@@ -150,9 +150,7 @@ bool sbb_bodies_info(sb_batch *b, const char *key, uint64_t *value)
     const std::string k(key);
     if (k == "body_words") *value = SB_BATCH_BODY_WORDS;
     else if (k == "bodies_lds_bytes") *value = sbo_lds_bytes(b->V.maxP, b->V.maxB);
-    else if (k == "bodies_kernel_vgprs" || k == "bodies_kernel_scratch_bytes")
-        *value = sbb_kernel_res(b, b->bodies_res, (const void *)k_batch_bodies, k == "bodies_kernel_vgprs");
-    else return false;
+    else return sbb_kernel_info(b, "bodies", (const void *)k_batch_bodies, b->bodies_res, key, value);
     return true;
 }
 

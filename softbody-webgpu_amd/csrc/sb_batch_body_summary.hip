@@ -236,9 +236,7 @@ bool sbb_body_summary_info(sb_batch *b, const char *key, uint64_t *value)
     const std::string k(key);
     if (k == "body_summary_words") *value = SB_BATCH_BODY_SUMMARY_WORDS;
     else if (k == "body_summary_lds_bytes") *value = sbq_lds_bytes(b->V.maxP);
-    else if (k == "body_summary_kernel_vgprs" || k == "body_summary_kernel_scratch_bytes")
-        *value = sbb_kernel_res(b, b->body_summary_res, (const void *)k_batch_body_summary, k == "body_summary_kernel_vgprs");
-    else return false;
+    else return sbb_kernel_info(b, "body_summary", (const void *)k_batch_body_summary, b->body_summary_res, key, value);
     return true;
 }
 

@@ -252,9 +252,7 @@ bool sbb_contacts_info(sb_batch *b, const char *key, uint64_t *value)
     if (k == "contact_words") *value = SB_BATCH_CONTACT_WORDS;
     else if (k == "contacts_cells_per_side") *value = sbk_cells(b, &cell);
     else if (k == "contacts_lds_bytes") *value = sbk_lds_bytes(b->V.maxP, sbk_cells(b, &cell));
-    else if (k == "contacts_kernel_vgprs" || k == "contacts_kernel_scratch_bytes")
-        *value = sbb_kernel_res(b, b->contacts_res, (const void *)k_batch_contacts, k == "contacts_kernel_vgprs");
-    else return false;
+    else return sbb_kernel_info(b, "contacts", (const void *)k_batch_contacts, b->contacts_res, key, value);
     return true;
 }
 

@@ -6,8 +6,6 @@
 // the predicate of sb_cut_math.h -- sb_cut_device's definition word for word.  A hit raises the slot's bit in the scene's pending
 // break flags (one bit per beam SLOT: what k_batch_frame's delete pass reads), with a vector atomic.  The hit bytes are staged in
 // LDS so that the row is zero-filled and written once.  A scene that is hit nowhere is not written at all.
-#include <string>
-
 #include "sb_batch.h"
 #include "sb_cut_math.h"
 
@@ -79,22 +77,13 @@ __global__ __launch_bounds__(SBU_BLOCK) void k_batch_cut(SbBatchView V, const ui
 // ---------------------------------------------------------------- host
 bool sbb_cut_info(sb_batch *b, const char *key, uint64_t *value)
 {
-    const std::string k(key);
-    if (k == "cut_kernel_vgprs" || k == "cut_kernel_scratch_bytes")
-        *value = sbb_kernel_res(b, b->cut_res, (const void *)k_batch_cut, k == "cut_kernel_vgprs");
-    else return false;
-    return true;
+    return sbb_kernel_info(b, "cut", (const void *)k_batch_cut, b->cut_res, key, value);
 }
 
 sb_status sb_batch_cut_device(sb_batch *b, uint32_t flags, const void *device_shapes, uint32_t k, void *device_hit_u8, void *device_counts_i32)
 {
-    if (!b) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_cut_device: null batch");
-    if (flags & ~SB_CUT_DRY_RUN) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_cut_device: flags 0x%x: only SB_CUT_DRY_RUN is known", flags);
-    if (k > SB_CUT_MAX_SHAPES) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_cut_device: %u shapes per scene, at most %u", k, SB_CUT_MAX_SHAPES);
-    if (k && !device_shapes) SB_FAIL(b, SB_ERR_INVALID, "sb_batch_cut_device: null shapes");
-    if (sbb_misaligned4({device_shapes, device_counts_i32}))
-        SB_FAIL(b, SB_ERR_INVALID, "sb_batch_cut_device: shapes and counts must be 4-byte aligned");
-    SB_HIP(b, hipSetDevice(b->device));
+    SB_TRY(sbb_edit_entry(b, "sb_batch_cut_device", flags, SB_CUT_DRY_RUN, "SB_CUT_DRY_RUN is", k, SB_CUT_MAX_SHAPES, "shapes", device_shapes,
+                          {device_shapes, device_counts_i32}, "shapes and counts"));
     k_batch_cut<<<b->opt.n_scenes, SBU_BLOCK, sbu_lds_bytes(b->V.maxB), b->stream>>>(b->V, (const uint32_t *)device_shapes, k,
                                                                                    (flags & SB_CUT_DRY_RUN) ? 1u : 0u, (uint8_t *)device_hit_u8,
                                                                                    (int32_t *)device_counts_i32);

@@ -177,9 +177,7 @@ bool sbb_graph_info(sb_batch *b, const char *key, uint64_t *value)
     if (k == "graph_count_words") *value = SB_BATCH_GRAPH_COUNT_WORDS;
     else if (k == "graph_material_words") *value = SB_BATCH_GRAPH_MATERIAL_WORDS;
     else if (k == "graph_lds_bytes") *value = sbh_lds_bytes(b->V.maxP, b->V.maxB);
-    else if (k == "graph_kernel_vgprs" || k == "graph_kernel_scratch_bytes")
-        *value = sbb_kernel_res(b, b->graph_res, (const void *)k_batch_graph, k == "graph_kernel_vgprs");
-    else return false;
+    else return sbb_kernel_info(b, "graph", (const void *)k_batch_graph, b->graph_res, key, value);
     return true;
 }
 

@@ -254,9 +254,7 @@ bool sbb_render_info(sb_batch *b, const char *key, uint64_t *value)
     const std::string k(key);
     if (k == "render_lds_bytes") *value = b->render ? b->render->last_lds : 0u;
     else if (k == "render_bands") *value = b->render ? b->render->last_bands : 0u;
-    else if (k == "render_kernel_vgprs" || k == "render_kernel_scratch_bytes")
-        *value = sbb_kernel_res(b, b->render_res, (const void *)k_batch_render, k == "render_kernel_vgprs");
-    else return false;
+    else return sbb_kernel_info(b, "render", (const void *)k_batch_render, b->render_res, key, value);
     return true;
 }
 

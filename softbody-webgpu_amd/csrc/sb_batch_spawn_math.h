@@ -4,46 +4,32 @@
 // rows of one call.  Host and device: integers and comparisons plus, on the host, the contact test as sb_touch (sb_batch.h) takes
 // it -- float32, one rounding per operator in the order written (the library builds with -ffp-contract=off;
 // tests/batch_spawn_check.cpp builds it the same way), the square root IEEE.  Every comparison with a NaN is false.  Header-only
-// and HIP-free on the host.
+// and HIP-free on the host.  The row's width, the codes every adding call shares and word_as_float are sb_batch_alloc.h's.
 #pragma once
-#include <stdint.h>
-#include <string.h>
+#include "sb_batch_alloc.h"
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define SBS_HD __host__ __device__ inline
-#else
-#define SBS_HD inline
-#endif
-
-#define SBS_ROW_WORDS 8u // {tag, x, y, vx, vy, ax, ay, reserved}: sb_batch_new_particle
-
+// (a row: {tag, x, y, vx, vy, ax, ay, reserved}, sb_batch_new_particle)
 namespace sbs {
 
-// a row's verdict: SBS_CANDIDATE (it goes on to the blocked test and to the room) or SB_BATCH_SPAWN_EMPTY / _INVALID
-enum { SBS_CANDIDATE = 0, SBS_EMPTY = -1, SBS_INVALID = -2, SBS_BLOCKED = -3, SBS_FULL = -4 };
+using sba::word_as_float;
+// a row's verdict: sba::CANDIDATE (it goes on to the blocked test and to the room) or SB_BATCH_SPAWN_EMPTY / _INVALID
+enum { SBS_CANDIDATE = sba::CANDIDATE, SBS_BLOCKED = sba::OWN }; // (SBS_CANDIDATE: the check program's name for it)
 enum { SBS_DRY_RUN = 1u, SBS_SKIP_TOUCHING = 2u };
 
-SBS_HD float word_as_float(uint32_t w)
-{
-    float f;
-    memcpy(&f, &w, sizeof f);
-    return f;
-}
-
 // "a finite number" by its bits (neither infinity nor NaN: the exponent is not all ones)
-SBS_HD bool finite_bits(uint32_t w) { return (w & 0x7f800000u) != 0x7f800000u; }
+SBA_HD bool finite_bits(uint32_t w) { return (w & 0x7f800000u) != 0x7f800000u; }
 
-// steps 1 and 2 of the definition on row `w` (SBS_ROW_WORDS words).  loaded: the scene was uploaded.
-SBS_HD int row_verdict(const uint32_t *w, bool loaded)
+// steps 1 and 2 of the definition on row `w` (SBA_ROW_WORDS words).  loaded: the scene was uploaded.
+SBA_HD int row_verdict(const uint32_t *w, bool loaded)
 {
-    if ((int32_t)w[0] < 0) return SBS_EMPTY;
-    if (!loaded || w[7] != 0u || !finite_bits(w[1]) || !finite_bits(w[2])) return SBS_INVALID;
-    return SBS_CANDIDATE;
+    if ((int32_t)w[0] < 0) return sba::EMPTY;
+    if (!loaded || w[7] != 0u || !finite_bits(w[1]) || !finite_bits(w[2])) return sba::INVALID;
+    return sba::CANDIDATE;
 }
 
 // the threshold under which sb_touch takes the root: (2r)^2 * 1.001, +inf where that product is no ordinary number
 // (k_batch_frame's and the contacts report's expression)
-SBS_HD float touch_threshold(float radius, float *two_r)
+SBA_HD float touch_threshold(float radius, float *two_r)
 {
     *two_r = radius * 2.0f;
     const float thr0 = *two_r * *two_r * 1.001f;
@@ -63,11 +49,11 @@ inline bool touch(float mx, float my, float ox, float oy, float thr, float two_r
 // Step 3 for row j from what is known of the rows before it: verd[i] (steps 1 and 2), E[i] ("touches a particle slot < P"),
 // hit[i] ("row j touches row i").  Row j itself: a candidate.
 template <class Verd, class Bit, class Hit>
-SBS_HD bool blocked(uint32_t j, bool e_j, Verd verd, Bit e, Hit hit)
+SBA_HD bool blocked(uint32_t j, bool e_j, Verd verd, Bit e, Hit hit)
 {
     if (e_j) return true;
     for (uint32_t i = 0; i < j; i++)
-        if (verd(i) == SBS_CANDIDATE && !e(i) && hit(i)) return true;
+        if (verd(i) == sba::CANDIDATE && !e(i) && hit(i)) return true;
     return false;
 }
 

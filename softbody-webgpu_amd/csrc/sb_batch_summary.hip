@@ -169,9 +169,7 @@ bool sbb_summary_info(sb_batch *b, const char *key, uint64_t *value)
 {
     const std::string k(key);
     if (k == "summary_words") *value = SB_BATCH_SUMMARY_WORDS;
-    else if (k == "summary_kernel_vgprs" || k == "summary_kernel_scratch_bytes")
-        *value = sbb_kernel_res(b, b->summary_res, (const void *)k_batch_summary, k == "summary_kernel_vgprs");
-    else return false;
+    else return sbb_kernel_info(b, "summary", (const void *)k_batch_summary, b->summary_res, key, value);
     return true;
 }
 
