@@ -207,6 +207,7 @@ sb_status sb_get_counts(sb_engine *e, uint32_t *particles, uint32_t *beams);
  * "device_bytes", "substeps_done", "kernels_per_substep", "substep_hbm_bytes" (the HBM bytes one substep
  * launch has to move with the data layout the engine holds: the launched kernel's own compulsory traffic),
  * "grid_cells", "grid_builds", "grid_wide", "grid_skin_x1000", "material_mode", "materials", "local_index_bits",
+ * "blocked_word_format" (how the blocked kernel holds the plan's entry words: 0 wide, as in memory; 1 narrow, repacked per launch),
  * "render_table_build_us" (host time of sb_render's last draw-table build: the first render after an upload),
  * "render_wide_particles" / "render_wide_beams" (how many particles / beams the latest sb_render or sb_render_device drew with a
  * wave each rather than in their own thread: a clipped box of more than 64 pixels, more than 32 clipped points; 0 before the

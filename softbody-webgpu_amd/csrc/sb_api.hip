@@ -2028,6 +2028,10 @@ sb_status sb_get_info(sb_engine *e, const char *key, uint64_t *value)
     else if (k == "material_mode") *value = e->mat_mode;
     else if (k == "materials") *value = e->nmat;
     else if (k == "local_index_bits") *value = e->lbits;
+    else if (k == "blocked_word_format") { // 0 wide, 1 narrow: the blocked plan's entry words inside the kernel (the hybrid's plan where that is the one)
+        const SbBlockedDev &bk = e->bk.K ? e->bk : e->hy;
+        *value = bk.K ? sbk_word_format(bk) : 0;
+    }
     else if (sbs_info(e, key, value)) {} // sb_state_io.hip: "checkpoint_bytes", "checkpoints", "restores"
     else if (sbm_info(e, key, value)) {} // sb_summary.hip: "summary_partials", ...
     else if (sbd_info(e, key, value)) {} // sb_bodies.hip: "bodies_table_build_us", ...

@@ -12,6 +12,9 @@
 // refresh of the multi-GPU path see what they always saw.  Collisions are not blocked (their reach is spatial,
 // not along beams): SB_COLLIDE_GRID keeps the single-substep kernels of sb_kernels.hip.
 #include "sb_engine.h"
+#include "sb_blocked_word.h"
+
+#include <type_traits>
 
 #ifndef SB_BK_WAVES
 #define SB_BK_WAVES 4 // waves per SIMD the register budget is sized for (2 tiles per CU at 512 threads per tile)
@@ -84,6 +87,50 @@ struct SbBlockedState {
 #define SB_ENT_L(t, il) (((uint32_t)(il) >> 1) * (2u * SB_BK_T) + (t) + ((t) & ~63u) + ((uint32_t)(il) & 1u) * 64u)
 static_assert(SB_BK_G == 2 && SB_BK_OWNB % 2u == 0u && SB_BK_HALOB % 2u == 0u, "entry slots pair up inside their class");
 #define SB_BK_ROW 8u // LDS material row: length, 1/length, spring, damp, yield, yield*length, length*limit, limit
+static_assert(SBW_LBITS == SB_BK_LBITS && SBW_CAP == SB_BK_CAP && SBW_MAT_ROW_BYTES == 4u * SB_BK_ROW, "sb_blocked_word.h restates these");
+// The static LDS of a workgroup: positions and fixed-point force sums of the region's records, in one of two layouts behind the
+// same few operations.  A record is named by a HANDLE -- whatever the layout adds its constants to -- made from a region index
+// (rec) or taken from an entry word (end_a, end_b), and kept in a register by the beam phase from the gather to the force sums.
+//   SbLdsPlanes   four planes of 4-byte words, px, py, fx, fy (sb_blocked_word.h); the handle is the byte offset 4 q, every plane
+//                 is that plus an immediate, and a position or a pair of sums is one ds_read2st64_b32 / ds_write2st64_b32.
+//                 NARROW keeps the material rows (at most 16) here too: the dynamic part starts at an address the compiler
+//                 does not fold into an instruction, and behind the planes a row is 32 row plus an immediate like everything else.
+//   SbLdsRecords  float2 positions and two arrays of sums; the handle is the index q, scaled by 8 and by 4 where it is used.
+//                 For the tracked mode-1 variants, which have no register to spare: on the planes they spill 4 to 14 registers
+//                 in the load phase where they spill 0 or 1 on this layout (profiles/blocked_kernel_resources.txt).
+template <bool NARROW> struct alignas(16) SbLdsPlanes {
+    uint32_t pl[4u * SBW_PLANE];
+    float mat[NARROW ? SBW_NARROW_ROWS * SB_BK_ROW : 4u]; // NARROW: [nmat <= 16][SB_BK_ROW] (launch_one picks NARROW for such plans only)
+    SB_DEV static uint32_t rec(uint32_t q) { return 4u * q; }
+    SB_DEV static uint32_t end_a(uint32_t w) { return sbw::a4<NARROW>(w); }
+    SB_DEV static uint32_t end_b(uint32_t w) { return sbw::b4<NARROW>(w); }
+    template <int PL> SB_DEV uint32_t *at(uint32_t h) { return (uint32_t *)((char *)pl + h + sbw::plane_bytes(PL)); }
+    SB_DEV float2 pos(uint32_t h) { return make_float2(__uint_as_float(*at<SBW_PX>(h)), __uint_as_float(*at<SBW_PY>(h))); }
+    SB_DEV void set_pos(uint32_t h, float2 p)
+    {
+        *at<SBW_PX>(h) = __float_as_uint(p.x);
+        *at<SBW_PY>(h) = __float_as_uint(p.y);
+    }
+    SB_DEV uint32_t *fx(uint32_t h) { return at<SBW_FX>(h); }
+    SB_DEV uint32_t *fy(uint32_t h) { return at<SBW_FY>(h); }
+    SB_DEV void zero_sums(uint32_t h) { *fx(h) = *fy(h) = 0u; }
+};
+static_assert(sizeof(SbLdsPlanes<true>) + 16u < (1u << 16), "a material row's two 16-byte reads are inside the 16-bit offset");
+struct alignas(16) SbLdsRecords {
+    float2 p[SB_BK_CAP];
+    uint32_t sx[SB_BK_CAP], sy[SB_BK_CAP]; // (x and y apart: consecutive particles, consecutive banks)
+    float mat[4];                          // (not used: the rows are in the dynamic part)
+    SB_DEV static uint32_t rec(uint32_t q) { return q; }
+    SB_DEV static uint32_t end_a(uint32_t w) { return sbw::index_a(w); }
+    SB_DEV static uint32_t end_b(uint32_t w) { return sbw::index_b(w); }
+    SB_DEV float2 pos(uint32_t h) { return p[h]; }
+    SB_DEV void set_pos(uint32_t h, float2 v) { p[h] = v; }
+    SB_DEV uint32_t *fx(uint32_t h) { return &sx[h]; }
+    SB_DEV uint32_t *fy(uint32_t h) { return &sy[h]; }
+    SB_DEV void zero_sums(uint32_t h) { sx[h] = sy[h] = 0u; }
+};
+// length, the first float of LDS material row `row32 / 32`
+SB_DEV float sbl_row_length(const float *mat, uint32_t row32) { return *(const float *)((const char *)mat + row32); }
 
 #ifndef SB_BK_WAVES_AUX
 #define SB_BK_WAVES_AUX SB_BK_WAVES
@@ -111,7 +158,7 @@ struct SbTrack {
     uint32_t *broken_ok;
 };
 #define SB_HY_SLOTS 64u  // (slot 0's fourth word: the launch flagged a beam)
-template <int MAT, bool AUX, bool PLAIN, bool TRACK>
+template <int MAT, bool AUX, bool PLAIN, bool TRACK, bool NARROW>
 __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? SB_BK_WAVES_AUX : SB_BK_WAVES, AUX ? SB_BK_WAVES_AUX : SB_BK_WAVES))) void k_substep_blocked(
     SbParticleArrays r, SbParticleArrays w, SbBlockedPlan bp, SbBlockedState bs, uint32_t k_run, const SbConsts c, SbParams prm,
     const uint32_t *__restrict__ acc_flag_r, uint32_t *acc_flag_w, SbTrack tr)
@@ -135,9 +182,12 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
         if (tr.slots_prev) hy_sl = tr.slots_prev[lane];
     }
     // static LDS layout: every address below is a register plus an immediate offset
-    __shared__ float2 s_pos[SB_BK_CAP];
-    __shared__ int s_fx[SB_BK_CAP], s_fy[SB_BK_CAP]; // fixed-point force sums (x and y apart: consecutive particles, consecutive banks)
-    extern __shared__ __attribute__((aligned(16))) float s_mat[]; // [nmat][SB_BK_ROW]
+    constexpr bool PLANES = !(MAT == 1 && TRACK); // (the tracked mode-1 variants: SbLdsRecords)
+    static_assert(PLANES || !NARROW, "a narrow word's fields are byte offsets into the planes");
+    using Lds = typename std::conditional<PLANES, SbLdsPlanes<NARROW>, SbLdsRecords>::type;
+    __shared__ Lds s_lds;
+    extern __shared__ __attribute__((aligned(16))) float s_dyn[]; // [nmat][SB_BK_ROW] (wide: the material rows), then MAT == 1: s_len
+    float *const s_mat = NARROW ? s_lds.mat : s_dyn; // [nmat][SB_BK_ROW]
 
     const uint32_t tile = sbb_tile_of_block(blockIdx.x, bp.ntiles), tid = threadIdx.x, K = bp.K;
     const uint32_t p0 = bp.tile_p0[tile], n_own = bp.tile_p0[tile + 1] - p0, h0 = bp.tile_h0[tile];
@@ -146,7 +196,8 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
     const uint32_t np_load = rc[k_run];       // ring <= k_run: everything this launch reads
     const uint32_t np_move = rc[k_run - 1];   // ring <= k_run - 1: everything it integrates at least once
     const uint32_t ne_load = lc[k_run - 1];
-    const uint32_t lmask = (1u << SB_BK_LBITS) - 1u;
+    // what a dead entry's word reads as in the form this variant holds its words in (NARROW: repacked behind the loads)
+    const uint32_t dummy_held = sbw::held<NARROW>(bp.dummy_word);
 
     // acceleration flags (DESIGN.md 4.1 "zero accelerations"): own tile, and the tiles that own the halo
     const bool acc_r = __hip_atomic_load(&acc_flag_r[tile], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
@@ -285,7 +336,7 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
     // MAT == 1 (rest lengths that do not fit the dictionary: every scene built the way the reference's editor builds beams):
     // the rest length of every entry is staged in LDS behind the material rows and read per evaluation; its reciprocal is
     // recomputed there (the short exact form).  Until r03 both sat in registers, 24 of the 128, and the variant spilled 34-47.
-    float *s_len = s_mat + SB_BK_ROW * bp.nmat;
+    float *s_len = s_dyn + SB_BK_ROW * bp.nmat;
     // (2) the gathers
 #pragma unroll
     for (int i = 0; i < SB_BK_HALOP; i++) {
@@ -308,7 +359,7 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
     for (int i = 0; i < SB_BK_MAXB; i++) {
         const uint32_t j = SB_ENT_J(i);
         const bool have = i < (int)SB_BK_OWNB ? j < n_ownb : j < ne_load;
-        word[i] = have ? word[i] : pad_word;
+        word[i] = sbw::held<NARROW>(have ? word[i] : pad_word);
         tg[i] = have ? tg[i] : 1.0f;
         ls[i] = have ? ls[i] : 1.0f;
         if (MAT == 1) ln[i] = have ? ln[i] : 1.0f;
@@ -344,9 +395,8 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
         const uint32_t q = SB_SLOT_Q(i);
         const bool have = i < (int)SB_BK_OWNP ? q < n_own : q < np_load;
         if (have) {
-            s_pos[q] = pp[i];
-            s_fx[q] = 0;
-            s_fy[q] = 0;
+            s_lds.set_pos(Lds::rec(q), pp[i]);
+            s_lds.zero_sums(Lds::rec(q));
         }
     }
     if (MAT == 1) {
@@ -355,11 +405,14 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
     }
     if (tid < 65u) { // the endpoints of dead entries and of every lane's padding entries: unit beams nobody owns
         const uint32_t a = tid == 64u ? SB_BK_DUMMY_A : SB_BK_PAD0 + 2u * tid;
-        s_pos[a] = make_float2(0.f, 0.f);
-        s_pos[a + 1u] = make_float2(1.f, 0.f);
-        s_fx[a] = s_fy[a] = s_fx[a + 1u] = s_fy[a + 1u] = 0;
+        s_lds.set_pos(Lds::rec(a), make_float2(0.f, 0.f));
+        s_lds.set_pos(Lds::rec(a + 1u), make_float2(1.f, 0.f));
+        s_lds.zero_sums(Lds::rec(a));
+        s_lds.zero_sums(Lds::rec(a + 1u));
     }
-    for (uint32_t i = tid; i < bp.nmat; i += SB_BK_T) { // host row: length, spring, damp, yield, limit, 1/length
+    // (NARROW: s_mat is the static array of SBW_NARROW_ROWS rows -- a plan with more never gets this variant, and is not let past it)
+    const uint32_t nrows = NARROW ? min(bp.nmat, SBW_NARROW_ROWS) : bp.nmat;
+    for (uint32_t i = tid; i < nrows; i += SB_BK_T) { // host row: length, spring, damp, yield, limit, 1/length
         const float *h = bp.mat_tab + 6u * i;
         float *d = s_mat + SB_BK_ROW * i;
         d[0] = h[0];
@@ -382,7 +435,7 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
             const uint32_t j = SB_ENT_J(i);
             const bool have = own ? j < n_ownb : j < ne_load;
             if (have && !(own ? own_plastic : nb_plastic))
-                tg[i] = MAT == 2 ? s_mat[SB_BK_ROW * (word[i] >> (2u * SB_BK_LBITS))] : s_len[tid + (uint32_t)i * SB_BK_T];
+                tg[i] = MAT == 2 ? sbl_row_length(s_mat, sbw::row32<NARROW>(word[i])) : s_len[tid + (uint32_t)i * SB_BK_T];
         }
     }
 
@@ -416,9 +469,9 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
                 asm volatile("" : "+v"(j)); // (or the store addresses of a thread are hoisted out of the substep loop: 48 VGPRs)
                 uint32_t wd = word[i];
                 asm volatile("" : "+v"(wd));
-                const uint32_t at = (j < n_ownb && wd != bp.dummy_word) ? b0 + j : dump;
-                const float4 *row = (const float4 *)(s_mat + SB_BK_ROW * (wd >> (2u * SB_BK_LBITS)));
-                const float2 qa = s_pos[wd & lmask], qb = s_pos[(wd >> SB_BK_LBITS) & lmask];
+                const uint32_t at = (j < n_ownb && wd != dummy_held) ? b0 + j : dump;
+                const float4 *row = (const float4 *)((const char *)s_mat + sbw::row32<NARROW>(wd));
+                const float2 qa = s_lds.pos(Lds::end_a(wd)), qb = s_lds.pos(Lds::end_b(wd));
                 const float4 r0 = row[0]; // length, 1/length, spring', damp' (times the force scale: the scaling is exact)
                 const float yield_strain = row[1].x;
                 float inv_length = r0.y;
@@ -454,12 +507,12 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
                 for (int u = 0; u < SB_BK_G; u++) {
                     const int i = i0 + u;
                     asm volatile("" : "+v"(word[i])); // keep the unpacking inside the loop: hoisted it is 3 registers per entry
-                    la[u] = word[i] & lmask;
-                    lb[u] = (word[i] >> SB_BK_LBITS) & lmask;
+                    la[u] = Lds::end_a(word[i]); // handles (planes: byte offsets, every plane is this plus an immediate)
+                    lb[u] = Lds::end_b(word[i]);
                     // the material row as two 16-byte reads (ds_read_b128: 4 LDS cycles each; the 12-byte form costs 8)
-                    const float4 *row = (const float4 *)(s_mat + SB_BK_ROW * (word[i] >> (2u * SB_BK_LBITS)));
-                    qa[u] = s_pos[la[u]];
-                    qb[u] = s_pos[lb[u]];
+                    const float4 *row = (const float4 *)((const char *)s_mat + sbw::row32<NARROW>(word[i]));
+                    qa[u] = s_lds.pos(la[u]);
+                    qb[u] = s_lds.pos(lb[u]);
                     const float4 r0 = row[0], r1 = row[1]; // length, 1/length, spring', damp' | yield, yield*length, length*limit, limit
                     mt[u].sd = sb_v2{r0.z, r0.w};
                     spring_s[u] = r0.z;
@@ -500,18 +553,18 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
                 } else if (__builtin_expect(mirrored, 1)) { // A's share is minus B's: ds_sub of the same integers (sb_beam_group)
 #pragma unroll
                     for (int u = 0; u < SB_BK_G; u++) {
-                        __hip_atomic_fetch_sub(&s_fx[la[u]], fb[u][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        __hip_atomic_fetch_sub(&s_fy[la[u]], fb[u][1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        __hip_atomic_fetch_add(&s_fx[lb[u]], fb[u][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        __hip_atomic_fetch_add(&s_fy[lb[u]], fb[u][1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        __hip_atomic_fetch_sub(s_lds.fx(la[u]), (uint32_t)fb[u][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        __hip_atomic_fetch_sub(s_lds.fy(la[u]), (uint32_t)fb[u][1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        __hip_atomic_fetch_add(s_lds.fx(lb[u]), (uint32_t)fb[u][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        __hip_atomic_fetch_add(s_lds.fy(lb[u]), (uint32_t)fb[u][1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     }
                 } else {
 #pragma unroll
                     for (int u = 0; u < SB_BK_G; u++) {
-                        atomicAdd(&s_fx[la[u]], fa[u][0]);
-                        atomicAdd(&s_fy[la[u]], fa[u][1]);
-                        atomicAdd(&s_fx[lb[u]], fb[u][0]);
-                        atomicAdd(&s_fy[lb[u]], fb[u][1]);
+                        atomicAdd(s_lds.fx(la[u]), (uint32_t)fa[u][0]);
+                        atomicAdd(s_lds.fy(la[u]), (uint32_t)fa[u][1]);
+                        atomicAdd(s_lds.fx(lb[u]), (uint32_t)fb[u][0]);
+                        atomicAdd(s_lds.fy(lb[u]), (uint32_t)fb[u][1]);
                     }
                 }
             }
@@ -524,12 +577,11 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
             const uint32_t q = SB_SLOT_Q(i);
             if (i < (int)SB_BK_OWNP ? q < n_own : q < npr) { // (own particles are inside every prefix)
                 SbParticle particle;
-                particle.p = s_pos[q];
+                particle.p = s_lds.pos(Lds::rec(q));
                 particle.v = pv[i];
                 particle.a = pa[i];
-                const int fx = s_fx[q], fy = s_fy[q];
-                s_fx[q] = 0;
-                s_fy[q] = 0;
+                const int fx = (int)*s_lds.fx(Lds::rec(q)), fy = (int)*s_lds.fy(Lds::rec(q));
+                s_lds.zero_sums(Lds::rec(q));
                 const float2 p_old = particle.p;
                 if (!((SB_BK_ABLATE & 2) && prm.time_step >= 0.0f)) {
                     // sb_particle_finish with the walls behind one question per wave: has any lane left [lo, hi] (a NaN
@@ -549,7 +601,7 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
                         }
                     }
                 }
-                s_pos[q] = particle.p;
+                s_lds.set_pos(Lds::rec(q), particle.p);
                 pv[i] = particle.v;
                 pa[i] = particle.a;
             }
@@ -570,7 +622,7 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
     for (int i = 0; i < SB_BK_OWNP; i++) {
         const uint32_t q = tid_s + (uint32_t)i * SB_BK_T;
         if (q < n_own) {
-            sb_store_wt(&w.pos[p0 + q], s_pos[q]); // (write-through: sb_physics.h; config 2 at 1 M: 8.15 -> 8.32e10)
+            sb_store_wt(&w.pos[p0 + q], s_lds.pos(Lds::rec(q))); // (write-through: sb_physics.h; config 2 at 1 M: 8.15 -> 8.32e10)
             sb_store_wt(&w.vel[p0 + q], pv[i]);
             const bool nz = (__float_as_uint(pa[i].x) | __float_as_uint(pa[i].y)) != 0u; // -0.0 counts
             any_acc |= nz;
@@ -583,8 +635,8 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
 #pragma unroll
         for (int i = 0; i < SB_BK_OWNB; i++) {
             const uint32_t j = SB_ENT_L(tid_s, i);
-            const float len_i = MAT == 2 ? s_mat[SB_BK_ROW * (word[i] >> (2u * SB_BK_LBITS))] : s_len[tid + (uint32_t)i * SB_BK_T];
-            yielded |= j < n_ownb && word[i] != bp.dummy_word && __float_as_uint(tg[i]) != __float_as_uint(len_i);
+            const float len_i = MAT == 2 ? sbl_row_length(s_mat, sbw::row32<NARROW>(word[i])) : s_len[tid + (uint32_t)i * SB_BK_T];
+            yielded |= j < n_ownb && word[i] != dummy_held && __float_as_uint(tg[i]) != __float_as_uint(len_i);
         }
     }
     const bool plastic_w = own_plastic || __syncthreads_or(yielded ? 1 : 0) != 0;
@@ -593,7 +645,7 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
     for (int i = 0; i < SB_BK_OWNB; i++) {
         const uint32_t j = SB_ENT_L(tid_s, i);
         if (j < n_ownb) {
-            if (__builtin_expect(word[i] != bp.dummy_word, 1)) {
+            if (__builtin_expect(word[i] != dummy_held, 1)) {
                 if (plastic_w) sb_store_wt(&bs.target_w[b0 + j], tg[i]);
                 sb_store_wt(&bs.last_w[b0 + j], ls[i]);
                 if ((brk >> i) & 1u) {
@@ -812,6 +864,15 @@ uint32_t sbk_split_call(uint32_t n, uint32_t kmax, bool fewest, uint32_t *first,
     return best_L;
 }
 
+// SB_BK_NARROW (diagnostic builds: 0 keeps every scene on wide words, to measure the narrow form against)
+#ifndef SB_BK_NARROW
+#define SB_BK_NARROW 1
+#endif
+// the form the kernel holds this plan's entry words in: 1 = narrow (sb_blocked_word.h), 0 = wide, as they lie in HBM.  Narrow
+// wants at most 16 material rows and material mode 2: the mode-1 variants have no register to spare, and their narrow forms spill
+// where the wide ones do not (profiles/blocked_kernel_resources.txt).
+uint32_t sbk_word_format(const SbBlockedDev &bk) { return (SB_BK_NARROW && bk.mat_mode == 2 && bk.nmat <= SBW_NARROW_ROWS) ? 1u : 0u; }
+
 // the mode-1 variants keep one float per entry in dynamic LDS: with the static part that is more than the 64 KB a launch may
 // take without saying so (gfx950 has 160 KB per CU: two such workgroups still fit)
 static void allow_large_lds(int device)
@@ -820,7 +881,7 @@ static void allow_large_lds(int device)
     if (device < 0 || device >= 64 || done[device]) return;
     done[device] = true;
     const int bytes = 100 * 1024;
-#define SB_ALLOW(A, PL, TR) (void)hipFuncSetAttribute((const void *)k_substep_blocked<1, A, PL, TR>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)
+#define SB_ALLOW(A, PL, TR) (void)hipFuncSetAttribute((const void *)k_substep_blocked<1, A, PL, TR, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)
     SB_ALLOW(false, false, false); SB_ALLOW(false, true, false); SB_ALLOW(true, false, false); SB_ALLOW(true, true, false);
     SB_ALLOW(false, false, true); SB_ALLOW(false, true, true); SB_ALLOW(true, false, true); SB_ALLOW(true, true, true);
 #undef SB_ALLOW
@@ -855,18 +916,20 @@ static void launch_one(sb_engine *e, SbBlockedDev &bk, uint32_t k, bool aux, boo
         bk.run_launches++;
         bk.k_prev = k;
     }
-#define SB_LAUNCH_B(M, A, PL, TR)                                                                                            \
-    k_substep_blocked<M, A, PL, TR><<<bk.ntiles, SB_BK_T, bk.lds_bytes, e->stream>>>(r, w, bp, bs, k, e->consts, e->prm,        \
-                                                                                    e->d_acc_flag[e->cur], e->d_acc_flag[e->cur ^ 1], tr)
-#define SB_LAUNCH_BT(M, A, PL) do { if (track) SB_LAUNCH_B(M, A, PL, true); else SB_LAUNCH_B(M, A, PL, false); } while (0)
-#define SB_LAUNCH_BA(M, PL) do { if (aux) SB_LAUNCH_BT(M, true, PL); else SB_LAUNCH_BT(M, false, PL); } while (0)
+#define SB_LAUNCH_B(M, A, PL, TR, NW)                                                                                         \
+    k_substep_blocked<M, A, PL, TR, NW><<<bk.ntiles, SB_BK_T, NW ? 0 : bk.lds_bytes, e->stream>>>(r, w, bp, bs, k, e->consts, e->prm,     \
+                                                                                        e->d_acc_flag[e->cur], e->d_acc_flag[e->cur ^ 1], tr)
+#define SB_LAUNCH_BT(M, A, PL, NW) do { if (track) SB_LAUNCH_B(M, A, PL, true, NW); else SB_LAUNCH_B(M, A, PL, false, NW); } while (0)
+#define SB_LAUNCH_BA(M, PL, NW) do { if (aux) SB_LAUNCH_BT(M, true, PL, NW); else SB_LAUNCH_BT(M, false, PL, NW); } while (0)
     // the constants of THIS launch (they ride in its kernarg): the reference's defaults take the plain particle phase
     const bool plain = e->consts.drag_exp == 2.0f && e->consts.mouse_active == 0u;
     if (bk.ntiles) {
-        if (bk.mat_mode == 2) {
-            if (plain) SB_LAUNCH_BA(2, true); else SB_LAUNCH_BA(2, false);
+        if (sbk_word_format(bk)) { // (mode 2, at most 16 material rows: the words are repacked into byte offsets)
+            if (plain) SB_LAUNCH_BA(2, true, true); else SB_LAUNCH_BA(2, false, true);
+        } else if (bk.mat_mode == 2) {
+            if (plain) SB_LAUNCH_BA(2, true, false); else SB_LAUNCH_BA(2, false, false);
         } else {
-            if (plain) SB_LAUNCH_BA(1, true); else SB_LAUNCH_BA(1, false);
+            if (plain) SB_LAUNCH_BA(1, true, false); else SB_LAUNCH_BA(1, false, false);
         }
     }
 #undef SB_LAUNCH_BA
@@ -884,23 +947,24 @@ static void launch_one(sb_engine *e, SbBlockedDev &bk, uint32_t k, bool aux, boo
 void sbk_preload_blocked(const SbBlockedDev &bk, bool tracked)
 {
     hipFuncAttributes a;
-#define SB_TOUCH(M, A, PL, TR) (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_substep_blocked<M, A, PL, TR>))
-#define SB_TOUCH_M(M)                                      \
+#define SB_TOUCH(M, A, PL, TR, NW) (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_substep_blocked<M, A, PL, TR, NW>))
+#define SB_TOUCH_M(M, NW)                                  \
     do {                                                   \
         if (tracked) {                                     \
-            SB_TOUCH(M, false, false, true);               \
-            SB_TOUCH(M, false, true, true);                \
-            SB_TOUCH(M, true, false, true);                \
-            SB_TOUCH(M, true, true, true);                 \
+            SB_TOUCH(M, false, false, true, NW);           \
+            SB_TOUCH(M, false, true, true, NW);            \
+            SB_TOUCH(M, true, false, true, NW);            \
+            SB_TOUCH(M, true, true, true, NW);             \
         } else {                                           \
-            SB_TOUCH(M, false, false, false);              \
-            SB_TOUCH(M, false, true, false);               \
-            SB_TOUCH(M, true, false, false);               \
-            SB_TOUCH(M, true, true, false);                \
+            SB_TOUCH(M, false, false, false, NW);          \
+            SB_TOUCH(M, false, true, false, NW);           \
+            SB_TOUCH(M, true, false, false, NW);           \
+            SB_TOUCH(M, true, true, false, NW);            \
         }                                                  \
     } while (0)
-    if (bk.mat_mode == 2) SB_TOUCH_M(2);
-    else SB_TOUCH_M(1);
+    if (sbk_word_format(bk)) SB_TOUCH_M(2, true);
+    else if (bk.mat_mode == 2) SB_TOUCH_M(2, false);
+    else SB_TOUCH_M(1, false);
 #undef SB_TOUCH_M
 #undef SB_TOUCH
     (void)hipGetLastError();

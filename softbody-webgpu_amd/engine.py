@@ -422,6 +422,8 @@ class Engine(DeviceBinding):
         return p.value, b.value
 
     def info(self, key):
+        """sb_get_info: one counter or property of the engine by name (include/softbody.h lists them), e.g. "substeps_per_launch",
+        "materials", "blocked_word_format" (0 wide, 1 narrow: how the blocked kernel holds the plan's entry words)."""
         v = ctypes.c_uint64()
         self._check(load_library().sb_get_info(self._h, key.encode(), ctypes.byref(v)))
         return v.value

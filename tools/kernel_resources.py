@@ -1,8 +1,10 @@
 """Register / scratch / occupancy table of every kernel in a HIP source (hipcc -Rpass-analysis=kernel-resource-usage).
-Usage: python tools/kernel_resources.py softbody-webgpu_amd/csrc/sb_kernels.hip [filter]"""
+Usage: python tools/kernel_resources.py softbody-webgpu_amd/csrc/sb_kernels.hip [filter [name-width]]
+(names are cut at name-width characters, 48 unless given: k_substep_blocked's five template arguments want 56)"""
 import re, subprocess, sys, tempfile, os
 src = sys.argv[1]
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
+width = int(sys.argv[3]) if len(sys.argv) > 3 else 48
 flags = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -fno-slp-vectorize".split()
 with tempfile.TemporaryDirectory() as d:
     p = subprocess.run(["/opt/rocm/bin/hipcc", *flags, *os.environ.get("EXTRA", "").split(), "-c", src, "-o", os.path.join(d, "k.o"),
@@ -19,5 +21,5 @@ for line in p.stderr.splitlines():
 for r in rows:
     name = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip().split("(")[0]
     if flt and flt not in name: continue
-    print("%-48s VGPR %3s  spill %3s  scratch %4s  SGPR %3s  occ %s  LDS %s" % (name[:48], r.get("VGPRs"), r.get("VGPRs Spill", r.get("VGPR Spill")),
+    print("%-*s VGPR %3s  spill %3s  scratch %4s  SGPR %3s  occ %s  LDS %s" % (width, name[:width], r.get("VGPRs"), r.get("VGPRs Spill", r.get("VGPR Spill")),
           r.get("ScratchSize [bytes/lane]"), r.get("TotalSGPRs"), r.get("Occupancy [waves/SIMD]"), r.get("LDS Size [bytes/block]")))

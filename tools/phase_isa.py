@@ -7,7 +7,7 @@ The counts are STATIC: both sides of a branch count where the compiler laid them
 instruction across a marker (a comment is no barrier), so a slot's figure is good to a few instructions; the phase totals,
 which end at barriers, are exact.  Nothing in the tree is changed.
 
-Usage: python tools/phase_isa.py [--variant "2, false, true, false"] [--keep file.s] [--dump-slot N]"""
+Usage: python tools/phase_isa.py [--variant "2, false, true, false, true"] [--keep file.s] [--dump-slot N]"""
 import argparse, collections, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -123,7 +123,7 @@ def account(body):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--variant", default="2, false, true, false")
+    ap.add_argument("--variant", default="2, false, true, false, true")
     ap.add_argument("--keep")
     ap.add_argument("--dump-slot", type=int, default=-1, help="print the instructions of this particle slot")
     a = ap.parse_args()
