@@ -773,7 +773,7 @@ sb_status sb_body_summary(sb_engine *e, const sb_body_summary_options *opts, con
  *   Limits: per scene at most SB_BATCH_MAX_PARTICLES particles and SB_BATCH_MAX_BEAMS beams (what one workgroup holds).
  *   When do calls return?  sb_batch_frame / _step / _delete_pass / _reset_device / _write_user_input[_device] /
  *     _set_physics_constants / _read_state_device / _write_particles_device / _fork_device / _checkpoint_device /
- *     _write_beams_device / _add_beams_device / _add_particles_device / _summary_device / _rollout_device / _bodies_device / _contacts_device only ENQUEUE on the batch's stream (device buffers must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
+ *     _write_beams_device / _add_beams_device / _add_particles_device / _summary_device / _rollout_device / _bodies_device / _contacts_device / _graph_device / _raycast_device only ENQUEUE on the batch's stream (device buffers must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
  *     sb_batch_render_device only ENQUEUES (its device buffer must stay valid likewise); sb_batch_render_scene WAITS.
  *   Errors: every call returns an sb_status; sb_batch_last_error(b) gives the message (b == NULL: the last failed
  *     sb_batch_create of the calling thread).  Options are checked BEFORE a device is looked for. */
@@ -1199,6 +1199,80 @@ sb_status sb_batch_graph_device(sb_batch *b, uint32_t flags,
         void *device_nbr_i32      /* [n_scenes][2 * max_beams][2] or NULL; needs row_ptr */,
         void *device_counts_i32   /* [n_scenes][SB_BATCH_GRAPH_COUNT_WORDS] or NULL */);
 
+/* ---- range sensors: ray casts per scene on the device, bit for bit ----
+ * sb_batch_raycast_device -- "how far is the nearest thing in this direction, and what is it?": every scene gets its own k rays,
+ * k <= SB_BATCH_RAY_MAX, in ONE launch; for every ray the answer is the nearest hit among the scene's particles (discs), its live
+ * beams (segments) and the four walls.  device_rays is [n_scenes][k] sb_batch_ray.
+ *
+ * DEFINITION.  The arithmetic is the library's: binary32, one rounding per operator in the order written, correctly rounded / and
+ * sqrt.  A comparison with a NaN is false.  Infinities follow the operators.
+ * Ray row.  The ray is O + t D, O = (ox, oy), D = (dx, dy), for 0 <= t <= tmax.  D is not normalised: t is in units of |D| (pass a
+ *   unit vector to get distances).  mask == 0 is an EMPTY row.  Otherwise the row is INVALID when an unknown mask bit is set; or
+ *   ox, oy, dx or dy is not finite; or tmax is not >= 0 (a NaN fails; +inf is legal); or reserved != 0; or skip_label != -1 while
+ *   device_labels_i32 is NULL.
+ * Geometry: what sb_batch_load_scene would see at this point of the stream.
+ *   Particles (SB_RAY_PARTICLES): the slots < metadata.particle_i_c at their current positions, named by DATA index; the radius is
+ *     sb_batch_options.particle_radius, r2 = r * r computed once.
+ *   Beams (SB_RAY_BEAMS): the live beam slots < metadata.beam_i_c, named by data index -- a pending break flag still counts, as for
+ *     sb_batch_bodies_device --, each the segment between the current positions of its two endpoint particles; no thickness.
+ *   Walls (SB_RAY_WALLS): the lines x = 0, x = bounds_size, y = 0, y = bounds_size.
+ *   A scene never uploaded has no particles and no beams; its walls are still there.
+ * Disc at (cx, cy).  wx = cx - ox, wy = cy - oy, a = dx*dx + dy*dy, b = wx*dx + wy*dy, c = (wx*wx + wy*wy) - r2.  c <= 0 (the
+ *   origin is inside): t = 0.  Otherwise a hit only if b > 0 and q = b*b - a*c satisfies q >= 0; then t = (b - sqrt(q)) / a.  A
+ *   zero D therefore hits only discs that contain O.
+ * Segment A -> B.  ex = bx - ax, ey = by - ay, wx = ax - ox, wy = ay - oy, den = dx*ey - dy*ex, tn = wx*ey - wy*ex,
+ *   un = wx*dy - wy*dx.  den == 0 (parallel or degenerate): no hit.  den < 0: negate all three.  A hit iff 0 <= un && un <= den &&
+ *   0 <= tn; then t = tn / den.
+ * Walls.  dx < 0: t = (0 - ox) / dx, SB_BATCH_WALL_LEFT; dx > 0: t = (bounds_size - ox) / dx, SB_BATCH_WALL_RIGHT; likewise in y
+ *   with SB_BATCH_WALL_LOW and SB_BATCH_WALL_HIGH.  The other coordinate is not tested: from inside the box the nearest of the at
+ *   most two candidates is the exit point; from outside the expressions still define the answer.
+ * Every candidate.  t = t + 0.0f (so -0 becomes +0); it is kept iff t >= 0 && t <= tmax.
+ * Skipping.  A particle whose label equals the row's skip_label is ignored, and so is a beam whose endpoint A (the low half of its
+ *   record's particle_pair) carries that label; -1 ignores nothing.  Labels are [n_scenes][max_particles] int32 at particle data
+ *   indices, as sb_batch_bodies_device writes them; they are only compared and never used as an index, so stale or arbitrary
+ *   labels cannot fault.  A sensor that rides on a body sees past its own body this way.
+ * Winner.  The smallest (t, kind, index): t by its bit pattern (non-negative, so the bits order as the floats do); kind particle 1
+ *   < beam 2 < wall 3; index the particle data index, the beam data index or the wall word.  It is the minimum of the 64-bit keys
+ *   (bits(t) << 32) | (kind << 16) | index: an integer minimum, the same bits whatever the schedule.
+ *
+ * OUTPUTS.  Each may be NULL, not all of them; every word of an output that is passed is written.
+ *   t[s][j]       float32: the hit's t; on a miss the row's tmax bits, verbatim; 0 for an empty or invalid row.
+ *   hit[s][j]     SB_BATCH_RAY_HIT_WORDS int32 {kind, index, label}.  kind: 0 miss, 1 particle, 2 beam, 3 wall, -1 empty row, -2
+ *                 invalid row.  index: -1 where there is no hit.  label: the label of the hit particle, or of the hit beam's
+ *                 endpoint A; -1 for walls, for misses and without labels.
+ *   counts[s]     SB_BATCH_RAY_COUNT_WORDS int32: 0 valid rows (neither empty nor invalid), 1 hits on particles, 2 hits on beams,
+ *                 3 hits on walls.
+ * It only ENQUEUES on the batch's stream and only READS the batch: frame, raycast, frame equals frame, frame bit for bit.
+ * Errors, before anything touches a device: SB_ERR_INVALID for a NULL handle, an unknown flag bit (no flag is defined yet: flags
+ * must be 0), k > SB_BATCH_RAY_MAX, NULL rows with k > 0, all outputs NULL, a pointer that is not 4-byte aligned.  k == 0 is SB_OK
+ * and enqueues nothing.  sb_batch_get_info: "ray_max", "ray_hit_words", "ray_count_words", "raycast_lds_bytes" (LDS of one
+ * workgroup at this batch's capacity), "raycast_kernel_vgprs", "raycast_kernel_scratch_bytes". */
+typedef struct sb_batch_ray { /* 32 bytes */
+    uint32_t mask;           /* SB_RAY_*; 0: empty row */
+    float ox, oy, dx, dy;    /* origin and direction */
+    float tmax;              /* >= 0; +inf: no limit */
+    int32_t skip_label;      /* -1: nothing is skipped */
+    uint32_t reserved;       /* 0 */
+} sb_batch_ray;
+#define SB_BATCH_RAY_MAX 256u           /* rows per scene and call */
+#define SB_RAY_PARTICLES 1u
+#define SB_RAY_BEAMS 2u
+#define SB_RAY_WALLS 4u
+#define SB_BATCH_RAY_HIT_WORDS 3u
+#define SB_BATCH_RAY_COUNT_WORDS 4u
+#define SB_BATCH_RAY_MISS 0             /* hit[0] */
+#define SB_BATCH_RAY_PARTICLE 1
+#define SB_BATCH_RAY_BEAM 2
+#define SB_BATCH_RAY_WALL 3
+#define SB_BATCH_RAY_EMPTY (-1)
+#define SB_BATCH_RAY_INVALID (-2)
+sb_status sb_batch_raycast_device(sb_batch *b, uint32_t flags,
+        const void *device_rays       /* [n_scenes][k] sb_batch_ray */, uint32_t k,
+        const void *device_labels_i32 /* [n_scenes][max_particles] as sb_batch_bodies_device writes them, or NULL */,
+        void *device_t_f32            /* [n_scenes][k] float or NULL */,
+        void *device_hit_i32          /* [n_scenes][k][SB_BATCH_RAY_HIT_WORDS] or NULL */,
+        void *device_counts_i32       /* [n_scenes][SB_BATCH_RAY_COUNT_WORDS] or NULL */);
+
 /* scene i back into host buffers exactly as sb_load_buffers returns a single engine in the same state (counts in the metadata,
  * the mapping after the delete passes' stable in-place compactions, beam records with strain / stress; only records reachable
  * through the uploaded mapping are written; any pointer may be NULL).  SB_ERR_STATE for a scene never uploaded. */
@@ -1255,7 +1329,8 @@ sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream);
  * "body_summary_kernel_scratch_bytes", "body_summary_lds_bytes" (LDS of one workgroup at this batch's capacity);
  * sb_batch_graph_device: "graph_count_words", "graph_material_words", "graph_kernel_vgprs", "graph_kernel_scratch_bytes",
  * "graph_lds_bytes" (likewise); sb_batch_add_particles_device: "add_particles_kernel_vgprs",
- * "add_particles_kernel_scratch_bytes" */
+ * "add_particles_kernel_scratch_bytes"; sb_batch_raycast_device: "ray_max", "ray_hit_words", "ray_count_words",
+ * "raycast_lds_bytes" (likewise), "raycast_kernel_vgprs", "raycast_kernel_scratch_bytes" */
 sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value);
 const char *sb_batch_last_error(const sb_batch *b);
 

@@ -53,6 +53,16 @@ GRAPH_COUNT_FIELDS = ("beams", "connected_particles", "max_degree", "max_degree_
 GRAPH_MATERIAL_FIELDS = ("length", "spring", "damp", "yield_strain", "strain_break_limit")
 # what graph() returns; None where an output was not asked for
 Graph = collections.namedtuple("Graph", ("ends", "material", "row_ptr", "nbr", "counts"))
+RAY_MAX = 256                                         # SB_BATCH_RAY_MAX: rays per scene and call of raycast()
+RAY_ROW_WORDS = 8                                     # sb_batch_ray: {mask, ox, oy, dx, dy, tmax, skip_label, 0}
+RAY_PARTICLES, RAY_BEAMS, RAY_WALLS = 1, 2, 4         # SB_RAY_*: the bits of a row's mask
+RAY_MISS, RAY_PARTICLE, RAY_BEAM, RAY_WALL, RAY_EMPTY, RAY_INVALID = 0, 1, 2, 3, -1, -2   # SB_BATCH_RAY_*: the kind of a hit row
+RAY_HIT_WORDS, RAY_COUNT_WORDS = 3, 4                 # SB_BATCH_RAY_HIT_WORDS, SB_BATCH_RAY_COUNT_WORDS
+# the words of a row of raycast()'s hit and of its counts, in order (include/softbody.h, sb_batch_raycast_device)
+RAY_HIT_FIELDS = ("kind", "index", "label")
+RAY_COUNT_FIELDS = ("valid", "particles", "beams", "walls")
+# what raycast() returns; None where an output was not asked for
+RayCast = collections.namedtuple("RayCast", ("t", "hit", "counts"))
 
 
 def new_beam_rows(pairs, spring, damp, yield_strain, strain_break_limit, length=None):
@@ -89,6 +99,27 @@ def new_particle_rows(pos, vel=None, acc=None, valid=None):
     if valid is not None:
         ok = torch.as_tensor(valid, dtype=torch.bool, device=pos.device).expand(n, k)
         rows[:, :, 0] = torch.where(ok, 0, -1).to(torch.int32)
+    return rows
+
+
+def ray_rows(origin, direction, tmax, mask=RAY_PARTICLES | RAY_BEAMS | RAY_WALLS, skip_label=None):
+    """Rows for BatchEngine.raycast() from a float32 torch tensor [N, k, 2] of origins, packed with torch ops on its device: an
+    int32 tensor [N, k, 8] in sb_batch_ray's layout (the floats as their bits).  direction: a float32 tensor that broadcasts to
+    [N, k, 2] (not normalised: t comes back in units of its length).  tmax: a number, or a tensor that broadcasts to [N, k];
+    float("inf") is no limit.  mask: RAY_* bits, a number or an integer tensor that broadcasts to [N, k]; 0 makes the row an
+    empty one.  skip_label: None (nothing is skipped: -1), a number, or an integer tensor that broadcasts to [N, k] -- a column
+    of bodies()'s labels, say."""
+    import torch
+    if not isinstance(origin, torch.Tensor) or origin.dtype != torch.float32 or origin.dim() != 3 or origin.shape[2] != 2:
+        raise ValueError("ray_rows: origin must be a float32 torch tensor [N, k, 2]")
+    n, k = origin.shape[0], origin.shape[1]
+    rows = torch.zeros((n, k, RAY_ROW_WORDS), dtype=torch.int32, device=origin.device)
+    for col, x in ((1, origin), (3, direction)):
+        f = torch.as_tensor(x, dtype=torch.float32, device=origin.device).expand(n, k, 2).contiguous()
+        rows[:, :, col:col + 2] = f.view(torch.int32)
+    rows[:, :, 5] = torch.as_tensor(tmax, dtype=torch.float32, device=origin.device).expand(n, k).contiguous().view(torch.int32)
+    for col, x in ((0, mask), (6, -1 if skip_label is None else skip_label)):
+        rows[:, :, col] = torch.as_tensor(x, device=origin.device).to(torch.int32).expand(n, k)
     return rows
 
 
@@ -169,6 +200,7 @@ def load_library():
     L.sb_batch_bodies_device.argtypes = [vp, vp, vp, vp]
     L.sb_batch_contacts_device.argtypes = [vp, u32, vp, vp, vp, u32, vp]
     L.sb_batch_graph_device.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+    L.sb_batch_raycast_device.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp]
     L.sb_batch_body_summary_device.argtypes = [vp, vp, u32, vp, vp]
     L.sb_batch_load_scene.argtypes = [vp, u32, vp, sz, vp, sz, vp, sz, vp, sz]
     L.sb_batch_render_device.argtypes = [vp, ctypes.POINTER(SbBatchRenderOptions), vp]
@@ -616,6 +648,63 @@ class BatchEngine(DeviceBinding):
         self._ordered(tensors, lambda: load_library().sb_batch_graph_device(self._h, GRAPH_SKIP_PENDING if skip_pending else 0,
                                                                             *[vp(p) for p in ptrs]))
         return Graph(*outs)
+
+    # ---- range sensors (sb_batch_raycast_device)
+    def raycast(self, rays, labels=None, t=True, hit=True, counts=None):
+        """"How far is the nearest thing in this direction, and what is it?": every scene casts its own k rays in one launch.
+        `rays` is [n_scenes, k, 8], k <= RAY_MAX, in sb_batch_ray's layout {mask, ox, oy, dx, dy, tmax, skip_label, 0} -- mask and
+        skip_label integers, the five floats as their bits: an int32 or float32 (bits) torch tensor on the batch's device
+        (ray_rows() packs one), or a tuple (device pointer, k).  A ray is origin + t * direction for 0 <= t <= tmax; it meets the
+        scene's particles as discs of the batch's particle_radius (RAY_PARTICLES), its live beams as segments (RAY_BEAMS; a
+        pending break flag still counts, as for bodies()) and the four walls (RAY_WALLS); include/softbody.h states every test.
+        The nearest meeting wins; on equal t a particle beats a beam beats a wall, then the smaller index.  Returns a RayCast
+        named tuple of tensors on the batch's device (None where not asked for):
+        t [n_scenes, k] float32: the hit's t (a distance when the direction is a unit vector), the row's tmax on a miss, 0 for
+        an empty (mask 0) or invalid row.
+        hit [n_scenes, k, 3] int32 (RAY_HIT_FIELDS): kind (RAY_MISS, RAY_PARTICLE, RAY_BEAM, RAY_WALL, RAY_EMPTY, RAY_INVALID),
+        index (the particle's or beam's DATA index, the WALL_* word, -1 where nothing was hit), label (of the hit particle or of
+        the hit beam's endpoint a; -1 for walls, misses and without labels).
+        counts [n_scenes, 4] int32 (RAY_COUNT_FIELDS): valid rows, hits on particles, on beams, on walls.  counts=None: made
+        whenever something else is; False: not.
+        labels: None, True (self.bodies() is called first, on the same stream, and its labels are used), or an int32 tensor /
+        device pointer of [n_scenes, max_particles] labels of the caller's own at particle data indices, which are only compared:
+        a row whose skip_label is not -1 ignores the particles of that label and the beams whose endpoint a carries it, so a
+        sensor that rides on a body sees past it.  t / hit / counts: True, False, a device pointer (int) or a contiguous torch
+        tensor to write into.  Every word of what is asked for is written, the same bits on every run (k == 0: counts are
+        zeros).  Only reads the batch, only enqueues; torch's current stream is ordered after it."""
+        import torch
+        n = self.n_scenes
+        if isinstance(rays, tuple):
+            rptr, k = int(rays[0]), int(rays[1])
+            is_tensor = False
+        else:
+            if not isinstance(rays, torch.Tensor) or rays.dtype not in (torch.int32, torch.float32):
+                raise ValueError("raycast: rays must be an int32 / float32 torch tensor [n_scenes, k, 8] or (device pointer, k)")
+            if rays.dim() != 3 or rays.shape[0] != n or rays.shape[2] != RAY_ROW_WORDS or rays.shape[1] > RAY_MAX:
+                raise ValueError("raycast: rays must be [n_scenes = %d, k <= %d, 8], not %s" % (n, RAY_MAX, tuple(rays.shape)))
+            k = int(rays.shape[1])
+            rptr, is_tensor = self._device_buffer("raycast: rays", rays, None, n * k * RAY_ROW_WORDS * 4)
+        if not 0 <= k <= RAY_MAX:
+            raise ValueError("raycast: k is %d, not in 0 .. %d" % (k, RAY_MAX))
+        if counts is None:
+            counts = True
+        wanted = [x is not False and x is not None for x in (t, hit, counts)]
+        if not any(wanted):
+            raise ValueError("raycast: t, hit and counts are all False: nothing to write")
+        given = [None if isinstance(x, bool) else x for x in (t, hit, counts)]   # (True: a new tensor)
+        outs, ptrs, tensors = self._bind("raycast", [
+            ("t", given[0], wanted[0], (n, k), "float32"),
+            ("hit", given[1], wanted[1], (n, k, RAY_HIT_WORDS), "int32"),
+            ("counts", given[2], wanted[2], (n, RAY_COUNT_WORDS), "int32"),
+            ("labels", (lambda: self.bodies()[0]) if labels is True else labels, labels is not None, (n, self.max_particles), "int32")])
+        if k == 0:   # (the library enqueues nothing for no rays: the counts of no rays are zeros)
+            if isinstance(outs[2], torch.Tensor):
+                outs[2].zero_()
+            return RayCast(*outs[:3])
+        vp = ctypes.c_void_p
+        self._ordered(tensors or is_tensor, lambda: load_library().sb_batch_raycast_device(self._h, 0, vp(rptr), k, vp(ptrs[3]), vp(ptrs[0]),
+                                                                                           vp(ptrs[1]), vp(ptrs[2])))
+        return RayCast(*outs[:3])
 
     # ---- pictures (sb_batch_render_device / sb_batch_render_scene; DESIGN.md 5.11)
     def _render_options(self, resolution, bounds_size, particle_radius, first=0, count=0):

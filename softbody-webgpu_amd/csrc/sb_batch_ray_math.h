@@ -1,0 +1,128 @@
+// sb_batch_ray_math.h -- "where does this ray meet this disc, this segment, these walls, and which meeting wins?", the arithmetic
+// behind sb_batch_raycast_device (sb_batch_raycast.hip); include/softbody.h states it row by row.  Host and
+// device: float32, one rounding per operator in the order written (the library builds with -ffp-contract=off;
+// tests/batch_ray_check.cpp builds it the same way), the division and the square root IEEE.  Every comparison with a NaN is false,
+// so a NaN meets nothing; an infinity follows the operators like any other number.  The winner is a minimum over 64-bit integer
+// keys: no schedule can change a bit of it.  Header-only and HIP-free on the host.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define SBR_HD __host__ __device__ inline
+#else
+#define SBR_HD inline
+#endif
+
+#define SBR_ROW_WORDS 8u // {mask, ox, oy, dx, dy, tmax, skip_label, 0}: sb_batch_ray
+#define SBR_HIT_WORDS 3u // {kind, index, label}
+#define SBR_NO_KEY 0xFFFFFFFFFFFFFFFFull // above every key: no candidate yet (a key's kind field is never all ones)
+
+namespace sbr {
+
+// the kind word of a hit row; the three hits are also the kind field of a key, so that on equal t a particle beats a beam beats a wall
+enum { MISS = 0, PARTICLE = 1, BEAM = 2, WALL = 3, EMPTY = -1, INVALID = -2 };
+enum { MASK_PARTICLES = 1u, MASK_BEAMS = 2u, MASK_WALLS = 4u, MASK_KNOWN = 7u };
+enum { WALL_LEFT = 1u, WALL_RIGHT = 2u, WALL_LOW = 4u, WALL_HIGH = 8u }; // SB_BATCH_WALL_*: the index of a wall hit
+
+struct Ray {
+    uint32_t mask;
+    float ox, oy, dx, dy, tmax;
+    int32_t skip;
+    float a; // dx * dx + dy * dy, once per row
+};
+
+SBR_HD float word_as_float(uint32_t w)
+{
+    float f;
+    memcpy(&f, &w, sizeof f);
+    return f;
+}
+SBR_HD uint32_t float_as_word(float f)
+{
+    uint32_t w;
+    memcpy(&w, &f, sizeof w);
+    return w;
+}
+// "a finite number" by its bits (neither infinity nor NaN: the exponent is not all ones)
+SBR_HD bool finite_bits(uint32_t w) { return (w & 0x7f800000u) != 0x7f800000u; }
+
+// a row's verdict: MISS (it is cast), EMPTY or INVALID.  labels: the call has labels.
+SBR_HD int row_verdict(const uint32_t *w, bool labels)
+{
+    if (w[0] == 0u) return EMPTY;
+    if (w[0] & ~(uint32_t)MASK_KNOWN) return INVALID;
+    if (!finite_bits(w[1]) || !finite_bits(w[2]) || !finite_bits(w[3]) || !finite_bits(w[4])) return INVALID;
+    if (!(word_as_float(w[5]) >= 0.0f)) return INVALID; // (a NaN fails; +inf is legal)
+    if (w[7] != 0u) return INVALID;
+    if ((int32_t)w[6] != -1 && !labels) return INVALID;
+    return MISS;
+}
+
+SBR_HD Ray ray_of(const uint32_t *w)
+{
+    Ray r{w[0], word_as_float(w[1]), word_as_float(w[2]), word_as_float(w[3]), word_as_float(w[4]), word_as_float(w[5]), (int32_t)w[6], 0.0f};
+    r.a = r.dx * r.dx + r.dy * r.dy;
+    return r;
+}
+
+// "is a primitive of this label ignored by this row?" (-1 ignores nothing; without labels every label passed here is -1)
+SBR_HD bool skipped(const Ray &r, int32_t label) { return r.skip != -1 && label == r.skip; }
+
+// every candidate: -0 becomes +0; kept iff 0 <= t <= tmax.  The key orders by (t, kind, index): t is non-negative, so its bits order
+// as the floats do.
+SBR_HD uint64_t candidate(const Ray &r, float t, uint32_t kind, uint32_t index)
+{
+    t = t + 0.0f;
+    if (!(t >= 0.0f && t <= r.tmax)) return SBR_NO_KEY;
+    return ((uint64_t)float_as_word(t) << 32) | ((uint64_t)kind << 16) | (uint64_t)index;
+}
+SBR_HD uint64_t nearer(uint64_t x, uint64_t y) { return x < y ? x : y; }
+
+// the disc of centre (cx, cy) and squared radius r2, data index `index`
+SBR_HD uint64_t disc(const Ray &r, float cx, float cy, float r2, uint32_t index)
+{
+    const float wx = cx - r.ox, wy = cy - r.oy;
+    const float b = wx * r.dx + wy * r.dy, c = (wx * wx + wy * wy) - r2;
+    if (c <= 0.0f) return candidate(r, 0.0f, PARTICLE, index); // the origin is inside
+    if (!(b > 0.0f)) return SBR_NO_KEY;
+    const float q = b * b - r.a * c;
+    if (!(q >= 0.0f)) return SBR_NO_KEY;
+    return candidate(r, (b - __builtin_sqrtf(q)) / r.a, PARTICLE, index);
+}
+
+// the segment from (ax, ay) to (bx, by), data index `index`: no division before a candidate is found
+SBR_HD uint64_t segment(const Ray &r, float ax, float ay, float bx, float by, uint32_t index)
+{
+    const float ex = bx - ax, ey = by - ay, wx = ax - r.ox, wy = ay - r.oy;
+    float den = r.dx * ey - r.dy * ex, tn = wx * ey - wy * ex, un = wx * r.dy - wy * r.dx;
+    if (den == 0.0f) return SBR_NO_KEY; // parallel or degenerate
+    if (den < 0.0f) den = -den, tn = -tn, un = -un;
+    if (!(0.0f <= un && un <= den && 0.0f <= tn)) return SBR_NO_KEY; // (a NaN den fails here)
+    return candidate(r, tn / den, BEAM, index);
+}
+
+// the four lines x = 0, x = bounds, y = 0, y = bounds: at most two candidates; the other coordinate is not tested
+SBR_HD uint64_t walls(const Ray &r, float bounds)
+{
+    uint64_t key = SBR_NO_KEY;
+    if (r.dx < 0.0f) key = nearer(key, candidate(r, (0.0f - r.ox) / r.dx, WALL, WALL_LEFT));
+    if (r.dx > 0.0f) key = nearer(key, candidate(r, (bounds - r.ox) / r.dx, WALL, WALL_RIGHT));
+    if (r.dy < 0.0f) key = nearer(key, candidate(r, (0.0f - r.oy) / r.dy, WALL, WALL_LOW));
+    if (r.dy > 0.0f) key = nearer(key, candidate(r, (bounds - r.oy) / r.dy, WALL, WALL_HIGH));
+    return key;
+}
+
+// ---- a row's answer from its verdict and its smallest key
+SBR_HD uint32_t key_kind(uint64_t key) { return (uint32_t)(key >> 16) & 0xffffu; }
+SBR_HD uint32_t key_index(uint64_t key) { return (uint32_t)key & 0xffffu; }
+// the t word: the hit's t, the row's tmax bits verbatim on a miss, 0 for an empty or invalid row
+SBR_HD uint32_t out_t(int verdict, uint64_t key, uint32_t tmax_bits)
+{
+    if (verdict != MISS) return 0u;
+    return key == SBR_NO_KEY ? tmax_bits : (uint32_t)(key >> 32);
+}
+SBR_HD int32_t out_kind(int verdict, uint64_t key) { return verdict != MISS ? verdict : (key == SBR_NO_KEY ? (int32_t)MISS : (int32_t)key_kind(key)); }
+SBR_HD int32_t out_index(int verdict, uint64_t key) { return verdict != MISS || key == SBR_NO_KEY ? -1 : (int32_t)key_index(key); }
+
+} // namespace sbr
