@@ -1273,6 +1273,58 @@ sb_status sb_batch_raycast_device(sb_batch *b, uint32_t flags,
         void *device_hit_i32          /* [n_scenes][k][SB_BATCH_RAY_HIT_WORDS] or NULL */,
         void *device_counts_i32       /* [n_scenes][SB_BATCH_RAY_COUNT_WORDS] or NULL */);
 
+/* ---- range sensors over the whole scene of ONE engine: ray casts on the device, bit for bit ----
+ * sb_raycast_device / sb_raycast -- sb_batch_raycast_device's question asked of an sb_engine: n_rays rows of sb_batch_ray (the same
+ * 32 bytes, masks and verdicts), for each the nearest hit among the scene's particles, live beams and walls.  The DEFINITION is the
+ * one above, word for word: the disc, segment and wall tests, t + 0.0f, 0 <= t <= tmax, skipping by the label of the particle or of
+ * the beam's endpoint A, the winner the smallest (t bits, kind, index).  The geometry is what sb_load_buffers would return at this
+ * point of the stream: particles at DATA indices at their current positions; beams LIVE by sb_bodies' rule (a caller slot of the
+ * latest upload that neither a delete pass nor a plan-keeping upload has removed; a pending break flag still counts), named by beam
+ * data index; radius and bounds are sb_options'.  A scene that fits a batch gives exactly the batch's t and hit rows.
+ * The key is wider: (bits(t) << 32) | (kind << 30) | index -- the same order, so the same winners, with room for the indices of an
+ * engine; max_particles or max_beams above 2^30: SB_ERR_UNSUPPORTED.
+ *   labels   int32 [max_particles] at particle data indices (sb_bodies' labels, or the caller's own), or NULL; only compared.
+ *   t        float32 [n_rays]: the hit's t; the row's tmax bits on a miss; 0 for an empty or invalid row.
+ *   hit      int32 [n_rays][SB_BATCH_RAY_HIT_WORDS] {kind, index, label} as above.
+ *   counts   int64 [SB_RAYCAST_COUNT_WORDS]: 0 valid rows, 1 hits on particles, 2 on beams, 3 on walls; then three COST words,
+ *            pure functions of the rows' bits, the positions and the cells: 4 rows answered by the sweep, 5 particles outside the
+ *            grid, 6 long beams; 7 is 0.
+ * Each output may be NULL, not all of them; every word of one that is passed is written.
+ * COST.  The primitives are sorted into G x G cells over [0, bounds]^2, cell = max(2 r (1 + 1/64), bounds / G): by default the
+ * largest G with G * G <= particles / 2 (at least 1, at most 8192) that keeps the cell that wide; cells_per_side != 0 replaces
+ * particles / 2's G as the cap (one cell where the radius or the bounds lie outside [2^-20, 2^30]).  A particle is IN-GRID iff both
+ * coordinates are finite and in [0, bounds]; a live beam is SHORT iff both endpoints are in-grid and their cells (x / cell, y / cell in
+ * float32, truncated, at most G - 1) differ by at most one per axis.  A row is WALKABLE iff ox and oy lie in [-bounds, 2 bounds] and
+ * a = dx*dx + dy*dy (float32) lies in [2^-40, 2^40]; it looks only into the cells along its line (csrc/sb_ray_walk.h derives which
+ * ones from the rounding of the tests; a row with SB_RAY_BEAMS walks the whole line, a row without stops once nothing further on
+ * can win; a row with neither walks nothing).  So a row with SB_RAY_BEAMS -- mask 7 among them -- costs O(G) columns of a few cells
+ * each whatever its tmax: a sensor that only needs particles and walls should say so in its mask.  Word 4 counts the valid rows that are not walkable: each is tested against every primitive.  Word 5 counts the
+ * particles that are not in-grid, word 6 the live beams that are not short: EVERY valid row is tested against each of them, so a
+ * scene full of them stays correct and gets slow.  The outputs never depend on G.
+ * sb_raycast_device only ENQUEUES on the engine's stream, reads nothing back and waits for nothing but the one table build after
+ * an upload (the shared scene tables, sb_cut_device's rows); it only READS the engine: frame, raycast, frame equals frame, frame
+ * bit for bit.  sb_raycast is the host-copy convenience: rows and labels from host memory, the same launches, the outputs copied
+ * back; it waits.
+ * Errors, before anything touches a device: SB_ERR_INVALID for a NULL handle, a struct_size that is neither 0 nor the struct's, an
+ * unknown flag (none is defined: flags must be 0), a nonzero reserved word, NULL rows with n_rays > 0, all outputs NULL, rows /
+ * labels / t / hit not 4-byte or counts not 8-byte aligned, n_rays above 2^24, cells_per_side above 8192; SB_ERR_STATE before an
+ * upload; SB_ERR_UNSUPPORTED with ranks or ghost zones, or capacities above 2^30.  n_rays == 0 is SB_OK and enqueues nothing.
+ * sb_get_info: "raycast_cells_per_side" (the default rule on the scene as it is), "raycast_kernel_vgprs",
+ * "raycast_kernel_scratch_bytes", "raycast_table_build_us". */
+#define SB_RAYCAST_COUNT_WORDS 8u
+typedef struct sb_raycast_options {
+    uint32_t struct_size;    /* = sizeof(sb_raycast_options); 0 or a NULL pointer = all defaults */
+    uint32_t flags;          /* none defined: 0 */
+    uint32_t cells_per_side; /* 0: the default rule */
+    uint32_t reserved[5];    /* zero */
+} sb_raycast_options;
+sb_status sb_raycast_device(sb_engine *e, const sb_raycast_options *opts, const void *device_rays /* [n_rays] sb_batch_ray */, uint32_t n_rays,
+                            const void *device_labels_i32 /* [max_particles] or NULL */, void *device_t_f32 /* [n_rays] or NULL */,
+                            void *device_hit_i32 /* [n_rays][SB_BATCH_RAY_HIT_WORDS] or NULL */,
+                            void *device_counts_i64 /* [SB_RAYCAST_COUNT_WORDS] or NULL */);
+sb_status sb_raycast(sb_engine *e, const sb_raycast_options *opts, const sb_batch_ray *rays, uint32_t n_rays, const int32_t *labels, float *t,
+                     int32_t *hit, int64_t *counts);
+
 /* scene i back into host buffers exactly as sb_load_buffers returns a single engine in the same state (counts in the metadata,
  * the mapping after the delete passes' stable in-place compactions, beam records with strain / stress; only records reachable
  * through the uploaded mapping are written; any pointer may be NULL).  SB_ERR_STATE for a scene never uploaded. */

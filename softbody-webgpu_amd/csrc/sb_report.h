@@ -1,5 +1,5 @@
 // sb_report.h -- what the engine's state calls (sb_state_io.hip), its four whole-scene reports (sb_summary.hip, sb_bodies.hip,
-// sb_contacts.hip, sb_body_summary.hip), the cut (sb_cut.hip) and the graph (sb_graph.hip) share: the owner of their device
+// sb_contacts.hip, sb_body_summary.hip), the cut (sb_cut.hip), the graph (sb_graph.hip) and the ray casts (sb_raycast.hip) share: the owner of their device
 // buffers, the preflight of a call, the host mirror of a report, the scene tables of the latest upload, the exclusive scan and
 // the wave's run counter.  What only one report uses stays in its file.
 #pragma once
@@ -27,6 +27,7 @@ enum SbReportBuf {
     SBY_B_SCRATCH, SBY_B_LABELS, SBY_B_OUT,                                        // sb_body_summary.hip
     SBX_B_ROW, SBX_B_MARK, SBX_B_ACC, SBX_B_SHAPES, SBX_B_HIT,                     // sb_cut.hip (SBX_B_ROW: also sb_graph.hip)
     SBG_B_SCRATCH, SBG_B_ENDS, SBG_B_ROWPTR, SBG_B_NBR, SBG_B_COUNTS,              // sb_graph.hip
+    SBW_B_SCRATCH, SBW_B_RAYS, SBW_B_LABELS, SBW_B_T, SBW_B_HIT, SBW_B_COUNTS,      // sb_raycast.hip
     SBQ_NBUF
 };
 
@@ -62,6 +63,7 @@ struct SbStateIoState {
     uint64_t cuts = 0;                        // calls since sb_create
     uint32_t cut_nd = 0;                      // highest beam data index among the rows + 1 (sb_graph.hip)
     double graph_build_ms = 0.0;              // "graph_table_build_us"
+    double ray_build_ms = 0.0;                // "raycast_table_build_us"
 
     void invalidate() { part_valid = beam_valid = copy_valid = valid = bleaf_valid = imp_valid = cut_valid = false; } // every table of the scene: the one place
 };
@@ -74,6 +76,7 @@ inline const char *sbq_options_name(const sb_contacts_options *) { return "sb_co
 inline const char *sbq_options_name(const sb_body_summary_options *) { return "sb_body_summary_options"; }
 inline const char *sbq_options_name(const sb_cut_options *) { return "sb_cut_options"; }
 inline const char *sbq_options_name(const sb_graph_options *) { return "sb_graph_options"; }
+inline const char *sbq_options_name(const sb_raycast_options *) { return "sb_raycast_options"; }
 
 sb_status sbq_ready(sb_engine *e, const char *what, const char *why); // loaded, no ranks (`why`: the call's parenthesis); the device; e->sio
 

@@ -4,6 +4,7 @@ The HIP library is the product; this module only marshals numpy buffers into it.
 no CPU fallback: if the library is missing, lacks a declared symbol, or finds no GPU, the
 calls raise.
 """
+import collections
 import ctypes
 import os
 import re
@@ -60,6 +61,28 @@ GRAPH_SKIP_PENDING = 1                                # SB_GRAPH_SKIP_PENDING
 GRAPH_COUNT_WORDS = 4                                 # SB_GRAPH_COUNT_WORDS
 # the words of graph()'s counts, in order (include/softbody.h, sb_graph_device)
 GRAPH_COUNT_FIELDS = ("beams", "connected_particles", "max_degree", "max_degree_particle")
+
+
+class SbRaycastOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("cells_per_side", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 5)]
+
+
+RAYCAST_COUNT_WORDS = 8                               # SB_RAYCAST_COUNT_WORDS
+RAYCAST_MAX_RAYS = 1 << 24                            # rows of one call
+# the words of raycast()'s counts, in order (include/softbody.h, sb_raycast_device): four of the definition, three of the cost
+RAYCAST_COUNT_FIELDS = ("valid", "particles", "beams", "walls", "swept_rows", "particles_outside_grid", "long_beams", "reserved_7")
+RayCast = collections.namedtuple("RayCast", ("t", "hit", "counts"))
+
+
+def ray_rows(origin, direction, tmax, mask=7, skip_label=None):
+    """Rows for Engine.raycast() from a float32 torch tensor [n, 2] of origins: batch.ray_rows() on one scene of n rows, an int32
+    tensor [n, 8] in sb_batch_ray's layout.  direction, tmax, mask, skip_label: as there, broadcasting to [n, 2] / [n]."""
+    import torch
+    from . import batch
+    if not isinstance(origin, torch.Tensor) or origin.dim() != 2:
+        raise ValueError("ray_rows: origin must be a float32 torch tensor [n, 2]")
+    return batch.ray_rows(origin[None], direction, tmax, mask=mask, skip_label=skip_label)[0]
 
 
 class SbBodiesOptions(ctypes.Structure):
@@ -284,6 +307,8 @@ def load_library():
     L.sb_summary.argtypes = [vp, ctypes.POINTER(SbSummaryOptions), vp, vp]
     L.sb_graph_device.argtypes = [vp, ctypes.POINTER(SbGraphOptions), vp, vp, vp, vp]
     L.sb_graph.argtypes = [vp, ctypes.POINTER(SbGraphOptions), vp, vp, vp, vp]
+    L.sb_raycast_device.argtypes = [vp, ctypes.POINTER(SbRaycastOptions), vp, u32, vp, vp, vp, vp]
+    L.sb_raycast.argtypes = [vp, ctypes.POINTER(SbRaycastOptions), vp, u32, vp, vp, vp, vp]
     L.sb_bodies_device.argtypes = [vp, ctypes.POINTER(SbBodiesOptions), vp, vp, vp]
     L.sb_bodies.argtypes = [vp, ctypes.POINTER(SbBodiesOptions), vp, vp, vp]
     L.sb_contacts_device.argtypes = [vp, ctypes.POINTER(SbContactsOptions), vp, vp, vp, vp]
@@ -765,6 +790,77 @@ class Engine(DeviceBinding):
         o = self._graph_options(H, skip_pending)
         self._check(load_library().sb_graph(self._h, ctypes.byref(o), _ptr(ends), _ptr(row_ptr), _ptr(nbr), _ptr(counts)))
         return ends, row_ptr, nbr, counts
+
+    # ---- range sensors over the whole scene (sb_raycast_device / sb_raycast)
+
+    @staticmethod
+    def _raycast_options(cells_per_side):
+        o = SbRaycastOptions()
+        o.struct_size = ctypes.sizeof(SbRaycastOptions)
+        o.cells_per_side = int(cells_per_side)
+        return o
+
+    def raycast(self, rays, labels=None, t=None, hit=None, counts=None, cells_per_side=0):
+        """"How far is the nearest thing in this direction, and what is it?" asked of the whole scene, on the GPU: BatchEngine.raycast()'s
+        definition, bit for bit, on what load_buffers() would return now.  `rays` is [n, 8], n <= 2^24, in sb_batch_ray's layout
+        {mask, ox, oy, dx, dy, tmax, skip_label, 0}: an int32 or float32 (bits) torch tensor on the engine's device (ray_rows() packs
+        one), or a tuple (device pointer, n).  Returns a RayCast named tuple of tensors on the engine's device: t [n] float32; hit
+        [n, 3] int32 (batch.RAY_HIT_FIELDS: kind, particle / beam DATA index or WALL_* word, label); counts [8] int64
+        (RAYCAST_COUNT_FIELDS: valid rows, hits on particles, beams and walls, then the cost words -- rows answered by the sweep over
+        every primitive, particles outside the grid, long beams: every ray is tested against each of the last two).  labels: None,
+        True (self.bodies() runs first, on the same stream, and its labels are used), or an int32 tensor / device pointer of
+        [max_particles] labels of the caller's own, only compared.  t / hit / counts: None or True -- a new tensor; False -- left out
+        (None in its place; not all three); a device pointer (int) or a contiguous torch tensor to write into.  cells_per_side: 0 =
+        the engine's rule (info("raycast_cells_per_side")); the outputs do not depend on it.  Only reads the engine, only
+        enqueues; torch's current stream is ordered after it."""
+        import torch
+        if isinstance(rays, tuple):
+            rptr, n = int(rays[0]), int(rays[1])
+            is_tensor = False
+        else:
+            if not isinstance(rays, torch.Tensor) or rays.dtype not in (torch.int32, torch.float32) or rays.dim() != 2 or rays.shape[1] != 8:
+                raise ValueError("raycast: rays must be an int32 / float32 torch tensor [n, 8] or (device pointer, n)")
+            n = int(rays.shape[0])
+            rptr, is_tensor = self._device_buffer("raycast: rays", rays, None, n * 32)
+        if not 0 <= n <= RAYCAST_MAX_RAYS:
+            raise ValueError("raycast: %d rays, not in 0 .. 2^24" % n)
+        wanted = [x is not False for x in (t, hit, counts)]
+        if not any(wanted):
+            raise ValueError("raycast: t, hit and counts are all False: nothing to write")
+        given = [None if isinstance(x, bool) else x for x in (t, hit, counts)]   # (None / True: a new tensor)
+        outs, ptrs, tensors = self._bind("raycast", [
+            ("t", given[0], wanted[0], (n,), "float32"),
+            ("hit", given[1], wanted[1], (n, 3), "int32"),
+            ("counts", given[2], wanted[2], (RAYCAST_COUNT_WORDS,), "int64"),
+            ("labels", (lambda: self.bodies(counts=False)[0]) if labels is True else None if labels is False else labels,
+             labels is not None and labels is not False, (self.max_particles,), "int32")])
+        if n == 0:   # (the library enqueues nothing for no rays: the counts of no rays are zeros)
+            if isinstance(outs[2], torch.Tensor):
+                outs[2].zero_()
+            return RayCast(*outs[:3])
+        o = self._raycast_options(cells_per_side)
+        vp = ctypes.c_void_p
+        self._ordered(tensors or is_tensor, lambda: load_library().sb_raycast_device(self._h, ctypes.byref(o), vp(rptr), n, vp(ptrs[3]), vp(ptrs[0]),
+                                                                                     vp(ptrs[1]), vp(ptrs[2])))
+        return RayCast(*outs[:3])
+
+    def raycast_host(self, rays, labels=None, cells_per_side=0):
+        """The same without torch: rays a uint32 / int32 / float32 (bits) numpy array [n, 8], labels None or int32 [max_particles];
+        returns RayCast(t float32 [n], hit int32 [n, 3], counts int64 [8]) numpy arrays.  Waits for the stream."""
+        rows = np.ascontiguousarray(rays)
+        if rows.dtype not in (np.dtype(np.uint32), np.dtype(np.int32), np.dtype(np.float32)) or rows.ndim != 2 or rows.shape[1] != 8:
+            raise ValueError("raycast_host: rays must be a uint32 / int32 / float32 array [n, 8]")
+        n = rows.shape[0]
+        t, hit, counts = np.zeros(n, dtype=np.float32), np.zeros((n, 3), dtype=np.int32), np.zeros(RAYCAST_COUNT_WORDS, dtype=np.int64)
+        lab = None
+        if labels is not None:
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.size < self.max_particles:
+                raise ValueError("raycast_host: labels needs max_particles entries")
+        o = self._raycast_options(cells_per_side)
+        self._check(load_library().sb_raycast(self._h, ctypes.byref(o), _ptr(rows) if n else None, n, None if lab is None else _ptr(lab), _ptr(t),
+                                              _ptr(hit), _ptr(counts)))
+        return RayCast(t, hit, counts)
 
     # ---- particle and wall contacts of the whole scene (sb_contacts_device / sb_contacts; DESIGN.md 5.20)
 
