@@ -773,7 +773,7 @@ sb_status sb_body_summary(sb_engine *e, const sb_body_summary_options *opts, con
  *   Limits: per scene at most SB_BATCH_MAX_PARTICLES particles and SB_BATCH_MAX_BEAMS beams (what one workgroup holds).
  *   When do calls return?  sb_batch_frame / _step / _delete_pass / _reset_device / _write_user_input[_device] /
  *     _set_physics_constants / _read_state_device / _write_particles_device / _fork_device / _checkpoint_device /
- *     _write_beams_device / _add_beams_device / _add_particles_device / _summary_device / _rollout_device / _bodies_device / _contacts_device / _graph_device / _raycast_device only ENQUEUE on the batch's stream (device buffers must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
+ *     _write_beams_device / _add_beams_device / _add_particles_device / _summary_device / _rollout_device / _bodies_device / _contacts_device / _graph_device / _raycast_device / _nearest_device only ENQUEUE on the batch's stream (device buffers must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
  *     sb_batch_render_device only ENQUEUES (its device buffer must stay valid likewise); sb_batch_render_scene WAITS.
  *   Errors: every call returns an sb_status; sb_batch_last_error(b) gives the message (b == NULL: the last failed
  *     sb_batch_create of the calling thread).  Options are checked BEFORE a device is looked for. */
@@ -1273,6 +1273,89 @@ sb_status sb_batch_raycast_device(sb_batch *b, uint32_t flags,
         void *device_hit_i32          /* [n_scenes][k][SB_BATCH_RAY_HIT_WORDS] or NULL */,
         void *device_counts_i32       /* [n_scenes][SB_BATCH_RAY_COUNT_WORDS] or NULL */);
 
+/* ---- proximity queries: nearest particle, beam or wall per point on the device, bit for bit ----
+ * sb_batch_nearest_device -- "what is nearest to this point, how far is it, and how much is within reach?": every scene gets its own
+ * k points, k <= SB_BATCH_NEAR_MAX, in ONE launch; for every point the answer is the nearest among the scene's particles (their
+ * centres), its live beams (segments) and the four walls, the closest point on it, and how many particles and beams lie within
+ * rmax.  device_points is [n_scenes][k] sb_batch_near_point.
+ *
+ * DEFINITION.  The arithmetic is the library's: binary32, one rounding per operator in the order written, correctly rounded / and
+ * sqrt.  A comparison with a NaN is false.  Infinities follow the operators.
+ * Row.  The query point is (px, py), the reach rmax; rmax2 = rmax * rmax, computed once.  mask == 0 is an EMPTY row.  Otherwise the
+ *   row is INVALID when an unknown mask bit is set; or px or py is not finite; or rmax is not >= 0 (a NaN fails; +inf is legal); or
+ *   a reserved word is not 0; or skip_label != -1 while device_labels_i32 is NULL.
+ * Geometry: sb_batch_raycast_device's, what sb_batch_load_scene would see at this point of the stream.
+ *   Particles (SB_NEAR_PARTICLES): the slots < metadata.particle_i_c at their current positions, named by DATA index.
+ *   Beams (SB_NEAR_BEAMS): the live beam slots < metadata.beam_i_c, named by data index -- a pending break flag still counts --, each
+ *     the segment between the current positions of its two endpoint particles; no thickness.
+ *   Walls (SB_NEAR_WALLS): the lines x = 0, x = bounds_size, y = 0, y = bounds_size.
+ *   A scene never uploaded has no particles and no beams; its walls are still there.
+ * Every primitive has a closest point Q and the squared distance d2 to it.
+ * Particle at C = (cx, cy).  Q = C (centres, as an editor's hover test measures, not disc surfaces): vx = cx - px, vy = cy - py,
+ *   d2 = vx*vx + vy*vy.
+ * Segment A -> B.  ex = bx - ax, ey = by - ay, wx = px - ax, wy = py - ay, ee = ex*ex + ey*ey, we = wx*ex + wy*ey.  If !(we > 0):
+ *   Q = A (a degenerate beam has ee = 0, so we = 0: it answers as its endpoint A and nothing is divided).  Else if !(we < ee): Q = B.
+ *   Else u = we / ee and Q = (ax + u*ex, ay + u*ey).  Then vx = qx - px, vy = qy - py, d2 = vx*vx + vy*vy: at a clamped end this is
+ *   the particle's expression on that endpoint, bit for bit.
+ * Walls.  Left: vx = 0 - px, d2 = vx*vx, Q = (0, py), index SB_BATCH_WALL_LEFT.  Right: vx = bounds_size - px, Q = (bounds_size, py),
+ *   SB_BATCH_WALL_RIGHT.  Low: vy = 0 - py, d2 = vy*vy, Q = (px, 0), SB_BATCH_WALL_LOW.  High: vy = bounds_size - py,
+ *   Q = (px, bounds_size), SB_BATCH_WALL_HIGH.
+ * Kept.  A primitive is kept iff d2 <= rmax2.  A NaN d2 (a NaN coordinate) is never kept.  A d2 of +inf (an infinite coordinate, or
+ *   an overflow) is kept only when rmax2 is +inf too, that is under rmax = +inf or an rmax whose square overflows: the operators
+ *   decide, nothing is special-cased.
+ * Skipping.  The ray cast's rule: a particle whose label equals the row's skip_label is ignored, and so is a beam whose endpoint A
+ *   (the low half of its record's particle_pair) carries that label; -1 ignores nothing.  Labels are [n_scenes][max_particles]
+ *   int32 at particle data indices; they are only compared and never used as an index, so stale or arbitrary labels cannot fault.
+ * Winner.  Among the kept, the smallest (d2, kind, index): the minimum of the 64-bit keys (bits(d2) << 32) | (kind << 16) | index,
+ *   kind particle 1 < beam 2 < wall 3, index the particle data index, the beam data index or the wall word.  d2 is a sum of squares
+ *   and never -0, so its bits order as the floats do.  A particle therefore beats the beams that end in it, and between equals the
+ *   smaller data index wins.  It is an integer minimum: the same bits whatever the schedule.
+ *
+ * OUTPUTS.  Each may be NULL, not all of them; every word of an output that is passed is written.
+ *   d[s][j]       float32: sqrt(d2) of the winner; on a miss (nothing kept) the row's rmax bits, verbatim; 0 for an empty or invalid
+ *                 row.
+ *   hit[s][j]     SB_BATCH_NEAR_HIT_WORDS int32 {kind, index, label}, the ray cast's: kind 0 miss, 1 particle, 2 beam, 3 wall, -1
+ *                 empty row, -2 invalid row; index -1 where there is no winner; label the label of the winning particle, or of the
+ *                 winning beam's endpoint A; -1 for walls, for misses and without labels.
+ *   point[s][j]   2 float32: the winner's closest point Q, computed again from the winner by the expressions above -- where a grab
+ *                 attaches.  On a miss the query point's bits; 0, 0 for an empty or invalid row.
+ *   within[s][j]  2 int32: how many particles that are not skipped, and how many live beams that are not skipped, were kept
+ *                 (d2 <= rmax2).  A class whose mask bit is off gives 0; an empty or invalid row gives 0, 0.  Walls are not counted.
+ *   counts[s]     SB_BATCH_NEAR_COUNT_WORDS int32: 0 valid rows (neither empty nor invalid), 1 rows whose nearest is a particle, 2 a
+ *                 beam, 3 a wall.
+ * It only ENQUEUES on the batch's stream and only READS the batch: frame, nearest, frame equals frame, frame bit for bit.
+ * Errors, before anything touches a device: SB_ERR_INVALID for a NULL handle, an unknown flag bit (no flag is defined yet: flags
+ * must be 0), k > SB_BATCH_NEAR_MAX, NULL rows with k > 0, all outputs NULL, a pointer that is not 4-byte aligned.  k == 0 is SB_OK
+ * and enqueues nothing.  sb_batch_get_info: "near_max", "near_hit_words", "near_count_words", "nearest_lds_bytes" (LDS of one
+ * workgroup at this batch's capacity), "nearest_kernel_vgprs", "nearest_kernel_scratch_bytes". */
+typedef struct sb_batch_near_point { /* 32 bytes */
+    uint32_t mask;           /* SB_NEAR_*; 0: empty row */
+    float px, py;            /* the query point */
+    float rmax;              /* >= 0; +inf: no limit */
+    int32_t skip_label;      /* -1: nothing is skipped */
+    uint32_t reserved[3];    /* 0 */
+} sb_batch_near_point;
+#define SB_BATCH_NEAR_MAX 256u          /* rows per scene and call */
+#define SB_NEAR_PARTICLES 1u
+#define SB_NEAR_BEAMS 2u
+#define SB_NEAR_WALLS 4u
+#define SB_BATCH_NEAR_HIT_WORDS 3u
+#define SB_BATCH_NEAR_COUNT_WORDS 4u
+#define SB_BATCH_NEAR_MISS 0            /* hit[0] */
+#define SB_BATCH_NEAR_PARTICLE 1
+#define SB_BATCH_NEAR_BEAM 2
+#define SB_BATCH_NEAR_WALL 3
+#define SB_BATCH_NEAR_EMPTY (-1)
+#define SB_BATCH_NEAR_INVALID (-2)
+sb_status sb_batch_nearest_device(sb_batch *b, uint32_t flags,
+        const void *device_points     /* [n_scenes][k] sb_batch_near_point */, uint32_t k,
+        const void *device_labels_i32 /* [n_scenes][max_particles] as sb_batch_bodies_device writes them, or NULL */,
+        void *device_d_f32            /* [n_scenes][k] float or NULL */,
+        void *device_hit_i32          /* [n_scenes][k][SB_BATCH_NEAR_HIT_WORDS] or NULL */,
+        void *device_point_f32        /* [n_scenes][k][2] float or NULL */,
+        void *device_within_i32       /* [n_scenes][k][2] or NULL */,
+        void *device_counts_i32       /* [n_scenes][SB_BATCH_NEAR_COUNT_WORDS] or NULL */);
+
 /* ---- range sensors over the whole scene of ONE engine: ray casts on the device, bit for bit ----
  * sb_raycast_device / sb_raycast -- sb_batch_raycast_device's question asked of an sb_engine: n_rays rows of sb_batch_ray (the same
  * 32 bytes, masks and verdicts), for each the nearest hit among the scene's particles, live beams and walls.  The DEFINITION is the
@@ -1382,7 +1465,8 @@ sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream);
  * sb_batch_graph_device: "graph_count_words", "graph_material_words", "graph_kernel_vgprs", "graph_kernel_scratch_bytes",
  * "graph_lds_bytes" (likewise); sb_batch_add_particles_device: "add_particles_kernel_vgprs",
  * "add_particles_kernel_scratch_bytes"; sb_batch_raycast_device: "ray_max", "ray_hit_words", "ray_count_words",
- * "raycast_lds_bytes" (likewise), "raycast_kernel_vgprs", "raycast_kernel_scratch_bytes" */
+ * "raycast_lds_bytes" (likewise), "raycast_kernel_vgprs", "raycast_kernel_scratch_bytes"; sb_batch_nearest_device: "near_max",
+ * "near_hit_words", "near_count_words", "nearest_lds_bytes" (likewise), "nearest_kernel_vgprs", "nearest_kernel_scratch_bytes" */
 sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value);
 const char *sb_batch_last_error(const sb_batch *b);
 

@@ -63,6 +63,17 @@ RAY_HIT_FIELDS = ("kind", "index", "label")
 RAY_COUNT_FIELDS = ("valid", "particles", "beams", "walls")
 # what raycast() returns; None where an output was not asked for
 RayCast = collections.namedtuple("RayCast", ("t", "hit", "counts"))
+NEAR_MAX = 256                                        # SB_BATCH_NEAR_MAX: points per scene and call of nearest()
+NEAR_ROW_WORDS = 8                                    # sb_batch_near_point: {mask, px, py, rmax, skip_label, 0, 0, 0}
+NEAR_PARTICLES, NEAR_BEAMS, NEAR_WALLS = 1, 2, 4      # SB_NEAR_*: the bits of a row's mask
+NEAR_MISS, NEAR_PARTICLE, NEAR_BEAM, NEAR_WALL, NEAR_EMPTY, NEAR_INVALID = 0, 1, 2, 3, -1, -2   # SB_BATCH_NEAR_*: the kind of a hit row
+NEAR_HIT_WORDS, NEAR_COUNT_WORDS = 3, 4               # SB_BATCH_NEAR_HIT_WORDS, SB_BATCH_NEAR_COUNT_WORDS
+# the words of a row of nearest()'s hit, of its within and of its counts, in order (include/softbody.h, sb_batch_nearest_device)
+NEAR_HIT_FIELDS = ("kind", "index", "label")
+NEAR_WITHIN_FIELDS = ("particles", "beams")
+NEAR_COUNT_FIELDS = ("valid", "particles", "beams", "walls")
+# what nearest() returns; None where an output was not asked for
+Nearest = collections.namedtuple("Nearest", ("d", "hit", "point", "within", "counts"))
 
 
 def new_beam_rows(pairs, spring, damp, yield_strain, strain_break_limit, length=None):
@@ -120,6 +131,24 @@ def ray_rows(origin, direction, tmax, mask=RAY_PARTICLES | RAY_BEAMS | RAY_WALLS
     rows[:, :, 5] = torch.as_tensor(tmax, dtype=torch.float32, device=origin.device).expand(n, k).contiguous().view(torch.int32)
     for col, x in ((0, mask), (6, -1 if skip_label is None else skip_label)):
         rows[:, :, col] = torch.as_tensor(x, device=origin.device).to(torch.int32).expand(n, k)
+    return rows
+
+
+def point_rows(point, rmax, mask=NEAR_PARTICLES | NEAR_BEAMS | NEAR_WALLS, skip_label=None):
+    """Rows for BatchEngine.nearest() from a float32 torch tensor [N, k, 2] of query points, packed with torch ops on its device: an
+    int32 tensor [N, k, 8] in sb_batch_near_point's layout (the floats as their bits).  rmax: the reach, a number or a tensor that
+    broadcasts to [N, k]; float("inf") is no limit.  mask: NEAR_* bits, a number or an integer tensor that broadcasts to [N, k]; 0
+    makes the row an empty one.  skip_label: None (nothing is skipped: -1), a number, or an integer tensor that broadcasts to
+    [N, k] -- a column of bodies()'s labels, say."""
+    import torch
+    if not isinstance(point, torch.Tensor) or point.dtype != torch.float32 or point.dim() != 3 or point.shape[2] != 2:
+        raise ValueError("point_rows: point must be a float32 torch tensor [N, k, 2]")
+    n, k = point.shape[0], point.shape[1]
+    rows = torch.zeros((n, k, NEAR_ROW_WORDS), dtype=torch.int32, device=point.device)
+    rows[:, :, 1:3] = point.contiguous().view(torch.int32)
+    rows[:, :, 3] = torch.as_tensor(rmax, dtype=torch.float32, device=point.device).expand(n, k).contiguous().view(torch.int32)
+    for col, x in ((0, mask), (4, -1 if skip_label is None else skip_label)):
+        rows[:, :, col] = torch.as_tensor(x, device=point.device).to(torch.int32).expand(n, k)
     return rows
 
 
@@ -201,6 +230,7 @@ def load_library():
     L.sb_batch_contacts_device.argtypes = [vp, u32, vp, vp, vp, u32, vp]
     L.sb_batch_graph_device.argtypes = [vp, u32, vp, vp, vp, vp, vp]
     L.sb_batch_raycast_device.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp]
+    L.sb_batch_nearest_device.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp, vp, vp]
     L.sb_batch_body_summary_device.argtypes = [vp, vp, u32, vp, vp]
     L.sb_batch_load_scene.argtypes = [vp, u32, vp, sz, vp, sz, vp, sz, vp, sz]
     L.sb_batch_render_device.argtypes = [vp, ctypes.POINTER(SbBatchRenderOptions), vp]
@@ -705,6 +735,75 @@ class BatchEngine(DeviceBinding):
         self._ordered(tensors or is_tensor, lambda: load_library().sb_batch_raycast_device(self._h, 0, vp(rptr), k, vp(ptrs[3]), vp(ptrs[0]),
                                                                                            vp(ptrs[1]), vp(ptrs[2])))
         return RayCast(*outs[:3])
+
+    # ---- proximity queries (sb_batch_nearest_device)
+    def nearest(self, points, labels=None, d=True, hit=True, point=None, within=None, counts=None):
+        """"What is nearest to this point, how far is it, and how much is within reach?": every scene asks about its own k points
+        in one launch.  `points` is [n_scenes, k, 8], k <= NEAR_MAX, in sb_batch_near_point's layout {mask, px, py, rmax,
+        skip_label, 0, 0, 0} -- mask and skip_label integers, the three floats as their bits: an int32 or float32 (bits) torch
+        tensor on the batch's device (point_rows() packs one), or a tuple (device pointer, k).  A point is measured against the
+        scene's particles (their centres, NEAR_PARTICLES), its live beams as segments (NEAR_BEAMS; a pending break flag still
+        counts, as for bodies()) and the four walls (NEAR_WALLS); whatever lies farther than rmax is not kept;
+        include/softbody.h states every expression.  The nearest kept wins; on equal distance a particle beats a beam beats a
+        wall, then the smaller index.  Returns a Nearest named tuple of tensors on the batch's device (None where not asked for):
+        d [n_scenes, k] float32: the distance to the winner, the row's rmax on a miss, 0 for an empty (mask 0) or invalid row.
+        hit [n_scenes, k, 3] int32 (NEAR_HIT_FIELDS): kind (NEAR_MISS, NEAR_PARTICLE, NEAR_BEAM, NEAR_WALL, NEAR_EMPTY,
+        NEAR_INVALID), index (the particle's or beam's DATA index, the WALL_* word, -1 where there is no winner), label (of the
+        winning particle or of the winning beam's endpoint a; -1 for walls, misses and without labels).
+        point [n_scenes, k, 2] float32: the closest point on the winner -- where a grab attaches; the query point on a miss.
+        within [n_scenes, k, 2] int32 (NEAR_WITHIN_FIELDS): how many particles and how many live beams lie within rmax (0 for a
+        class the mask leaves out).
+        counts [n_scenes, 4] int32 (NEAR_COUNT_FIELDS): valid rows, rows whose nearest is a particle, a beam, a wall.
+        point / within / counts = None: made whenever d or hit is; False: not.
+        labels: None, True (self.bodies() is called first, on the same stream, and its labels are used), or an int32 tensor /
+        device pointer of [n_scenes, max_particles] labels of the caller's own at particle data indices, which are only compared:
+        a row whose skip_label is not -1 ignores the particles of that label and the beams whose endpoint a carries it.
+        d / hit / point / within / counts: True, False, a device pointer (int) or a contiguous torch tensor to write into.  Every
+        word of what is asked for is written, the same bits on every run (k == 0: counts are zeros).  Only reads the batch, only
+        enqueues; torch's current stream is ordered after it.
+
+        Grasping -- weld each scene's hand particle (data index `hand` [n_scenes]) to whatever particle is within reach:
+            near = be.nearest(point_rows(hand_pos[:, None, :], reach, mask=NEAR_PARTICLES, skip_label=hand_label[:, None]), labels=True)
+            partner = torch.where(near.hit[..., 0] == NEAR_PARTICLE, near.hit[..., 1], -1)
+            pairs = torch.stack((partner, hand[:, None].expand_as(partner)), -1)
+            be.add_beams(new_beam_rows(pairs, spring, damp, yield_strain, strain_break_limit), length_current=True, skip_joined=True)
+        A row whose partner is -1 is an empty row of add_beams (ADD_EMPTY); nothing is read back."""
+        import torch
+        n = self.n_scenes
+        if isinstance(points, tuple):
+            rptr, k = int(points[0]), int(points[1])
+            is_tensor = False
+        else:
+            if not isinstance(points, torch.Tensor) or points.dtype not in (torch.int32, torch.float32):
+                raise ValueError("nearest: points must be an int32 / float32 torch tensor [n_scenes, k, 8] or (device pointer, k)")
+            if points.dim() != 3 or points.shape[0] != n or points.shape[2] != NEAR_ROW_WORDS or points.shape[1] > NEAR_MAX:
+                raise ValueError("nearest: points must be [n_scenes = %d, k <= %d, 8], not %s" % (n, NEAR_MAX, tuple(points.shape)))
+            k = int(points.shape[1])
+            rptr, is_tensor = self._device_buffer("nearest: points", points, None, n * k * NEAR_ROW_WORDS * 4)
+        if not 0 <= k <= NEAR_MAX:
+            raise ValueError("nearest: k is %d, not in 0 .. %d" % (k, NEAR_MAX))
+        asked = [d, hit, point, within, counts]
+        some = any(x is not False and x is not None for x in asked[:2])
+        asked = [asked[0], asked[1]] + [some if x is None else x for x in asked[2:]]
+        wanted = [x is not False and x is not None for x in asked]
+        if not any(wanted):
+            raise ValueError("nearest: d, hit, point, within and counts are all False: nothing to write")
+        given = [None if isinstance(x, bool) else x for x in asked]   # (True: a new tensor)
+        outs, ptrs, tensors = self._bind("nearest", [
+            ("d", given[0], wanted[0], (n, k), "float32"),
+            ("hit", given[1], wanted[1], (n, k, NEAR_HIT_WORDS), "int32"),
+            ("point", given[2], wanted[2], (n, k, 2), "float32"),
+            ("within", given[3], wanted[3], (n, k, 2), "int32"),
+            ("counts", given[4], wanted[4], (n, NEAR_COUNT_WORDS), "int32"),
+            ("labels", (lambda: self.bodies()[0]) if labels is True else labels, labels is not None, (n, self.max_particles), "int32")])
+        if k == 0:   # (the library enqueues nothing for no points: the counts of no points are zeros)
+            if isinstance(outs[4], torch.Tensor):
+                outs[4].zero_()
+            return Nearest(*outs[:5])
+        vp = ctypes.c_void_p
+        self._ordered(tensors or is_tensor, lambda: load_library().sb_batch_nearest_device(self._h, 0, vp(rptr), k, vp(ptrs[5]), vp(ptrs[0]), vp(ptrs[1]),
+                                                                                           vp(ptrs[2]), vp(ptrs[3]), vp(ptrs[4])))
+        return Nearest(*outs[:5])
 
     # ---- pictures (sb_batch_render_device / sb_batch_render_scene; DESIGN.md 5.11)
     def _render_options(self, resolution, bounds_size, particle_radius, first=0, count=0):
