@@ -113,6 +113,25 @@ def new_particle_rows(pos, vel=None, acc=None, valid=None):
     return rows
 
 
+def _query_rows(what, first, pairs, floats, ints):
+    """The rows of a query (ray_rows, point_rows), packed with torch ops: an int32 tensor [N, k, 8] on the device of `first`, the
+    float32 tensor [N, k, 2] that sets N and k (`what`: its name in the error).  pairs: (column, x) with x float32, broadcast to
+    [N, k, 2], into two columns as their bits; floats: (column, x) broadcast to [N, k], as their bits; ints: (column, x) integers
+    broadcast to [N, k].  The other columns are 0."""
+    import torch
+    if not isinstance(first, torch.Tensor) or first.dtype != torch.float32 or first.dim() != 3 or first.shape[2] != 2:
+        raise ValueError("%s must be a float32 torch tensor [N, k, 2]" % what)
+    n, k = first.shape[0], first.shape[1]
+    rows = torch.zeros((n, k, RAY_ROW_WORDS), dtype=torch.int32, device=first.device)   # (NEAR_ROW_WORDS is the same 8)
+    for col, x in pairs:
+        rows[:, :, col:col + 2] = torch.as_tensor(x, dtype=torch.float32, device=first.device).expand(n, k, 2).contiguous().view(torch.int32)
+    for col, x in floats:
+        rows[:, :, col] = torch.as_tensor(x, dtype=torch.float32, device=first.device).expand(n, k).contiguous().view(torch.int32)
+    for col, x in ints:
+        rows[:, :, col] = torch.as_tensor(x, device=first.device).to(torch.int32).expand(n, k)
+    return rows
+
+
 def ray_rows(origin, direction, tmax, mask=RAY_PARTICLES | RAY_BEAMS | RAY_WALLS, skip_label=None):
     """Rows for BatchEngine.raycast() from a float32 torch tensor [N, k, 2] of origins, packed with torch ops on its device: an
     int32 tensor [N, k, 8] in sb_batch_ray's layout (the floats as their bits).  direction: a float32 tensor that broadcasts to
@@ -120,18 +139,7 @@ def ray_rows(origin, direction, tmax, mask=RAY_PARTICLES | RAY_BEAMS | RAY_WALLS
     float("inf") is no limit.  mask: RAY_* bits, a number or an integer tensor that broadcasts to [N, k]; 0 makes the row an
     empty one.  skip_label: None (nothing is skipped: -1), a number, or an integer tensor that broadcasts to [N, k] -- a column
     of bodies()'s labels, say."""
-    import torch
-    if not isinstance(origin, torch.Tensor) or origin.dtype != torch.float32 or origin.dim() != 3 or origin.shape[2] != 2:
-        raise ValueError("ray_rows: origin must be a float32 torch tensor [N, k, 2]")
-    n, k = origin.shape[0], origin.shape[1]
-    rows = torch.zeros((n, k, RAY_ROW_WORDS), dtype=torch.int32, device=origin.device)
-    for col, x in ((1, origin), (3, direction)):
-        f = torch.as_tensor(x, dtype=torch.float32, device=origin.device).expand(n, k, 2).contiguous()
-        rows[:, :, col:col + 2] = f.view(torch.int32)
-    rows[:, :, 5] = torch.as_tensor(tmax, dtype=torch.float32, device=origin.device).expand(n, k).contiguous().view(torch.int32)
-    for col, x in ((0, mask), (6, -1 if skip_label is None else skip_label)):
-        rows[:, :, col] = torch.as_tensor(x, device=origin.device).to(torch.int32).expand(n, k)
-    return rows
+    return _query_rows("ray_rows: origin", origin, ((1, origin), (3, direction)), ((5, tmax),), ((0, mask), (6, -1 if skip_label is None else skip_label)))
 
 
 def point_rows(point, rmax, mask=NEAR_PARTICLES | NEAR_BEAMS | NEAR_WALLS, skip_label=None):
@@ -140,16 +148,7 @@ def point_rows(point, rmax, mask=NEAR_PARTICLES | NEAR_BEAMS | NEAR_WALLS, skip_
     broadcasts to [N, k]; float("inf") is no limit.  mask: NEAR_* bits, a number or an integer tensor that broadcasts to [N, k]; 0
     makes the row an empty one.  skip_label: None (nothing is skipped: -1), a number, or an integer tensor that broadcasts to
     [N, k] -- a column of bodies()'s labels, say."""
-    import torch
-    if not isinstance(point, torch.Tensor) or point.dtype != torch.float32 or point.dim() != 3 or point.shape[2] != 2:
-        raise ValueError("point_rows: point must be a float32 torch tensor [N, k, 2]")
-    n, k = point.shape[0], point.shape[1]
-    rows = torch.zeros((n, k, NEAR_ROW_WORDS), dtype=torch.int32, device=point.device)
-    rows[:, :, 1:3] = point.contiguous().view(torch.int32)
-    rows[:, :, 3] = torch.as_tensor(rmax, dtype=torch.float32, device=point.device).expand(n, k).contiguous().view(torch.int32)
-    for col, x in ((0, mask), (4, -1 if skip_label is None else skip_label)):
-        rows[:, :, col] = torch.as_tensor(x, device=point.device).to(torch.int32).expand(n, k)
-    return rows
+    return _query_rows("point_rows: point", point, ((1, point),), ((3, rmax),), ((0, mask), (4, -1 if skip_label is None else skip_label)))
 
 
 def body_beam_rows(result, edges, length, spring, damp, yield_strain, strain_break_limit):
@@ -679,6 +678,48 @@ class BatchEngine(DeviceBinding):
                                                                             *[vp(p) for p in ptrs]))
         return Graph(*outs)
 
+    # ---- what the two queries share (csrc/sb_batch_query.h)
+    def _query(self, call, items, result, rows, labels, rest, outs):
+        """raycast() and nearest() behind their output lists: `rows` is [n_scenes, k, 8], an int32 / float32 torch tensor or
+        (device pointer, k), `items` its name in the errors.  outs: (name, what the caller passed, shape after [n_scenes, k],
+        dtype) in the C call's order, the counts last (shape None: [n_scenes, 4]); the first two are never None, a None among the
+        others means `rest`, or with rest=None "whenever one of the first two is made".  Binds the outputs and the labels
+        (labels=True: bodies()'s), zeroes the counts of k == 0, makes the ordered call sb_batch_<call>_device and returns
+        result(*outputs)."""
+        import torch
+        n, k_max = self.n_scenes, RAY_MAX   # (NEAR_MAX, NEAR_ROW_WORDS and NEAR_COUNT_WORDS are the same numbers: one plan)
+        if isinstance(rows, tuple):
+            rptr, k, is_tensor = int(rows[0]), int(rows[1]), False
+        else:
+            if not isinstance(rows, torch.Tensor) or rows.dtype not in (torch.int32, torch.float32):
+                raise ValueError("%s: %s must be an int32 / float32 torch tensor [n_scenes, k, 8] or (device pointer, k)" % (call, items))
+            if rows.dim() != 3 or rows.shape[0] != n or rows.shape[2] != RAY_ROW_WORDS or rows.shape[1] > k_max:
+                raise ValueError("%s: %s must be [n_scenes = %d, k <= %d, 8], not %s" % (call, items, n, k_max, tuple(rows.shape)))
+            k = int(rows.shape[1])
+            rptr, is_tensor = self._device_buffer("%s: %s" % (call, items), rows, None, n * k * RAY_ROW_WORDS * 4)
+        if not 0 <= k <= k_max:
+            raise ValueError("%s: k is %d, not in 0 .. %d" % (call, k, k_max))
+        asked = [x for _, x, _, _ in outs]
+        if rest is None:
+            rest = any(x is not False and x is not None for x in asked[:2])
+        asked = asked[:2] + [rest if x is None else x for x in asked[2:]]
+        wanted = [x is not False and x is not None for x in asked]
+        names = [name for name, _, _, _ in outs]
+        if not any(wanted):
+            raise ValueError("%s: %s and %s are all False: nothing to write" % (call, ", ".join(names[:-1]), names[-1]))
+        bufs, ptrs, tensors = self._bind(call, [
+            (name, None if isinstance(x, bool) else x, w, (n, RAY_COUNT_WORDS) if tail is None else (n, k) + tail, dtype)   # (True: a new tensor)
+            for (name, _, tail, dtype), x, w in zip(outs, asked, wanted)] + [
+            ("labels", (lambda: self.bodies()[0]) if labels is True else labels, labels is not None, (n, self.max_particles), "int32")])
+        if k == 0:   # (the library enqueues nothing for no rows: the counts of no rows are zeros)
+            if isinstance(bufs[-2], torch.Tensor):
+                bufs[-2].zero_()
+            return result(*bufs[:-1])
+        vp = ctypes.c_void_p
+        fn = getattr(load_library(), "sb_batch_%s_device" % call)
+        self._ordered(tensors or is_tensor, lambda: fn(self._h, 0, vp(rptr), k, vp(ptrs[-1]), *[vp(p) for p in ptrs[:-1]]))
+        return result(*bufs[:-1])
+
     # ---- range sensors (sb_batch_raycast_device; DESIGN.md 5.27)
     def raycast(self, rays, labels=None, t=True, hit=True, counts=None):
         """"How far is the nearest thing in this direction, and what is it?": every scene casts its own k rays in one launch.
@@ -702,39 +743,8 @@ class BatchEngine(DeviceBinding):
         sensor that rides on a body sees past it.  t / hit / counts: True, False, a device pointer (int) or a contiguous torch
         tensor to write into.  Every word of what is asked for is written, the same bits on every run (k == 0: counts are
         zeros).  Only reads the batch, only enqueues; torch's current stream is ordered after it."""
-        import torch
-        n = self.n_scenes
-        if isinstance(rays, tuple):
-            rptr, k = int(rays[0]), int(rays[1])
-            is_tensor = False
-        else:
-            if not isinstance(rays, torch.Tensor) or rays.dtype not in (torch.int32, torch.float32):
-                raise ValueError("raycast: rays must be an int32 / float32 torch tensor [n_scenes, k, 8] or (device pointer, k)")
-            if rays.dim() != 3 or rays.shape[0] != n or rays.shape[2] != RAY_ROW_WORDS or rays.shape[1] > RAY_MAX:
-                raise ValueError("raycast: rays must be [n_scenes = %d, k <= %d, 8], not %s" % (n, RAY_MAX, tuple(rays.shape)))
-            k = int(rays.shape[1])
-            rptr, is_tensor = self._device_buffer("raycast: rays", rays, None, n * k * RAY_ROW_WORDS * 4)
-        if not 0 <= k <= RAY_MAX:
-            raise ValueError("raycast: k is %d, not in 0 .. %d" % (k, RAY_MAX))
-        if counts is None:
-            counts = True
-        wanted = [x is not False and x is not None for x in (t, hit, counts)]
-        if not any(wanted):
-            raise ValueError("raycast: t, hit and counts are all False: nothing to write")
-        given = [None if isinstance(x, bool) else x for x in (t, hit, counts)]   # (True: a new tensor)
-        outs, ptrs, tensors = self._bind("raycast", [
-            ("t", given[0], wanted[0], (n, k), "float32"),
-            ("hit", given[1], wanted[1], (n, k, RAY_HIT_WORDS), "int32"),
-            ("counts", given[2], wanted[2], (n, RAY_COUNT_WORDS), "int32"),
-            ("labels", (lambda: self.bodies()[0]) if labels is True else labels, labels is not None, (n, self.max_particles), "int32")])
-        if k == 0:   # (the library enqueues nothing for no rays: the counts of no rays are zeros)
-            if isinstance(outs[2], torch.Tensor):
-                outs[2].zero_()
-            return RayCast(*outs[:3])
-        vp = ctypes.c_void_p
-        self._ordered(tensors or is_tensor, lambda: load_library().sb_batch_raycast_device(self._h, 0, vp(rptr), k, vp(ptrs[3]), vp(ptrs[0]),
-                                                                                           vp(ptrs[1]), vp(ptrs[2])))
-        return RayCast(*outs[:3])
+        return self._query("raycast", "rays", RayCast, rays, labels, True,
+                           [("t", t, (), "float32"), ("hit", hit, (RAY_HIT_WORDS,), "int32"), ("counts", counts, None, "int32")])
 
     # ---- proximity queries (sb_batch_nearest_device; DESIGN.md 5.29)
     def nearest(self, points, labels=None, d=True, hit=True, point=None, within=None, counts=None):
@@ -768,42 +778,9 @@ class BatchEngine(DeviceBinding):
             pairs = torch.stack((partner, hand[:, None].expand_as(partner)), -1)
             be.add_beams(new_beam_rows(pairs, spring, damp, yield_strain, strain_break_limit), length_current=True, skip_joined=True)
         A row whose partner is -1 is an empty row of add_beams (ADD_EMPTY); nothing is read back."""
-        import torch
-        n = self.n_scenes
-        if isinstance(points, tuple):
-            rptr, k = int(points[0]), int(points[1])
-            is_tensor = False
-        else:
-            if not isinstance(points, torch.Tensor) or points.dtype not in (torch.int32, torch.float32):
-                raise ValueError("nearest: points must be an int32 / float32 torch tensor [n_scenes, k, 8] or (device pointer, k)")
-            if points.dim() != 3 or points.shape[0] != n or points.shape[2] != NEAR_ROW_WORDS or points.shape[1] > NEAR_MAX:
-                raise ValueError("nearest: points must be [n_scenes = %d, k <= %d, 8], not %s" % (n, NEAR_MAX, tuple(points.shape)))
-            k = int(points.shape[1])
-            rptr, is_tensor = self._device_buffer("nearest: points", points, None, n * k * NEAR_ROW_WORDS * 4)
-        if not 0 <= k <= NEAR_MAX:
-            raise ValueError("nearest: k is %d, not in 0 .. %d" % (k, NEAR_MAX))
-        asked = [d, hit, point, within, counts]
-        some = any(x is not False and x is not None for x in asked[:2])
-        asked = [asked[0], asked[1]] + [some if x is None else x for x in asked[2:]]
-        wanted = [x is not False and x is not None for x in asked]
-        if not any(wanted):
-            raise ValueError("nearest: d, hit, point, within and counts are all False: nothing to write")
-        given = [None if isinstance(x, bool) else x for x in asked]   # (True: a new tensor)
-        outs, ptrs, tensors = self._bind("nearest", [
-            ("d", given[0], wanted[0], (n, k), "float32"),
-            ("hit", given[1], wanted[1], (n, k, NEAR_HIT_WORDS), "int32"),
-            ("point", given[2], wanted[2], (n, k, 2), "float32"),
-            ("within", given[3], wanted[3], (n, k, 2), "int32"),
-            ("counts", given[4], wanted[4], (n, NEAR_COUNT_WORDS), "int32"),
-            ("labels", (lambda: self.bodies()[0]) if labels is True else labels, labels is not None, (n, self.max_particles), "int32")])
-        if k == 0:   # (the library enqueues nothing for no points: the counts of no points are zeros)
-            if isinstance(outs[4], torch.Tensor):
-                outs[4].zero_()
-            return Nearest(*outs[:5])
-        vp = ctypes.c_void_p
-        self._ordered(tensors or is_tensor, lambda: load_library().sb_batch_nearest_device(self._h, 0, vp(rptr), k, vp(ptrs[5]), vp(ptrs[0]), vp(ptrs[1]),
-                                                                                           vp(ptrs[2]), vp(ptrs[3]), vp(ptrs[4])))
-        return Nearest(*outs[:5])
+        return self._query("nearest", "points", Nearest, points, labels, None,
+                           [("d", d, (), "float32"), ("hit", hit, (NEAR_HIT_WORDS,), "int32"), ("point", point, (2,), "float32"),
+                            ("within", within, (2,), "int32"), ("counts", counts, None, "int32")])
 
     # ---- pictures (sb_batch_render_device / sb_batch_render_scene; DESIGN.md 5.11)
     def _render_options(self, resolution, bounds_size, particle_radius, first=0, count=0):

@@ -2,10 +2,13 @@
 // (sb_batch.hip: upload, stepping, state I/O; sb_batch_render.hip: pictures; sb_batch_summary.hip: per-scene statistics, rollouts;
 // sb_batch_bodies.hip: connected bodies; sb_batch_contacts.hip: particle and wall contacts; sb_batch_body_summary.hip: statistics per
 // body; sb_batch_cut.hip / sb_batch_add.hip / sb_batch_spawn.hip: cuts, welds and spawned particles, the latter two on
-// sb_batch_alloc.h, the allocator of their data indices; sb_batch_graph.hip: the beam graph; sb_batch_raycast.hip: range sensors; sb_batch_nearest.hip: proximity queries), and what the four report kernels have in common: the scene header each of them opens with (sbb_scene), the float <->
-// ordered-key codec of their extremes and the width of the pinned summation tree (sb_summary_math.h), the contact test (sb_touch); on the host the
-// *_kernel_vgprs / *_kernel_scratch_bytes info keys (sbb_kernel_info), the alignment test of the entry points (sbb_misaligned4)
-// and the opening checks of the editing calls (sbb_edit_entry).  All of it is inline; what only one kernel uses stays in that kernel's file.
+// sb_batch_alloc.h, the allocator of their data indices; sb_batch_graph.hip: the beam graph; sb_batch_raycast.hip /
+// sb_batch_nearest.hip: range sensors and proximity queries, both on sb_batch_query.h, the plan of a query kernel), and what the
+// one-workgroup-per-scene kernels that only read a batch have in common: the scene header each of them opens with (sbb_scene), the
+// float <-> ordered-key codec of the reports' extremes and the width of their pinned summation tree (sb_summary_math.h), the
+// contact test (sb_touch); on the host the *_kernel_vgprs / *_kernel_scratch_bytes info keys (sbb_kernel_info), the alignment test
+// of the entry points (sbb_misaligned4) and the opening checks of the editing and query calls (sbb_edit_entry).  All of it is
+// inline; what only one kernel uses stays in that kernel's file.
 #pragma once
 #include <algorithm>
 #include <cstdio>

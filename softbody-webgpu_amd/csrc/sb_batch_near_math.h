@@ -5,26 +5,16 @@
 // so a NaN distance is never kept; an infinity follows the operators like any other number.  The winner is a minimum over 64-bit
 // integer keys: no schedule can change a bit of it.  Header-only and HIP-free on the host.
 #pragma once
-#include <stdint.h>
-#include <string.h>
+#include "sb_query_key.h" // the kind, mask and wall words, the key and its decoding: shared with sb_batch_ray_math.h
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define SBN_HD __host__ __device__ inline
-#else
-#define SBN_HD inline
-#endif
-
-#define SBN_ROW_WORDS 8u // {mask, px, py, rmax, skip_label, 0, 0, 0}: sb_batch_near_point
-#define SBN_HIT_WORDS 3u // {kind, index, label}
-#define SBN_NO_KEY 0xFFFFFFFFFFFFFFFFull // above every key: nothing kept yet (a key's kind field is never all ones)
+#define SBN_HD SBQ_HD
+#define SBN_ROW_WORDS SBQ_ROW_WORDS // {mask, px, py, rmax, skip_label, 0, 0, 0}: sb_batch_near_point
+#define SBN_HIT_WORDS SBQ_HIT_WORDS
+#define SBN_NO_KEY SBQ_NO_KEY
 
 namespace sbn {
-
-// the kind word of a hit row (the ray cast's codes); the three winners are also the kind field of a key, so that on equal d2 a
-// particle beats a beam beats a wall
-enum { MISS = 0, PARTICLE = 1, BEAM = 2, WALL = 3, EMPTY = -1, INVALID = -2 };
-enum { MASK_PARTICLES = 1u, MASK_BEAMS = 2u, MASK_WALLS = 4u, MASK_KNOWN = 7u };
-enum { WALL_LEFT = 1u, WALL_RIGHT = 2u, WALL_LOW = 4u, WALL_HIGH = 8u }; // SB_BATCH_WALL_*: the index of a wall
+using namespace sbq; // (re-exported: MISS .. INVALID, MASK_*, WALL_*, word_as_float, float_as_word, finite_bits, skipped, pack, nearer,
+                     // key_kind, key_index, out_kind, out_index)
 enum { AT_A = 0, AT_B = 1, INSIDE = 2 }; // where on a segment its closest point lies
 
 struct Probe {
@@ -33,21 +23,6 @@ struct Probe {
     int32_t skip;
     float rmax2; // rmax * rmax, once per row
 };
-
-SBN_HD float word_as_float(uint32_t w)
-{
-    float f;
-    memcpy(&f, &w, sizeof f);
-    return f;
-}
-SBN_HD uint32_t float_as_word(float f)
-{
-    uint32_t w;
-    memcpy(&w, &f, sizeof w);
-    return w;
-}
-// "a finite number" by its bits (neither infinity nor NaN: the exponent is not all ones)
-SBN_HD bool finite_bits(uint32_t w) { return (w & 0x7f800000u) != 0x7f800000u; }
 
 // a row's verdict: MISS (it is asked), EMPTY or INVALID.  labels: the call has labels.
 SBN_HD int row_verdict(const uint32_t *w, bool labels)
@@ -67,9 +42,6 @@ SBN_HD Probe probe_of(const uint32_t *w)
     p.rmax2 = p.rmax * p.rmax;
     return p;
 }
-
-// "is a primitive of this label ignored by this row?" (-1 ignores nothing; without labels every label passed here is -1)
-SBN_HD bool skipped(const Probe &p, int32_t label) { return p.skip != -1 && label == p.skip; }
 
 // ---- the three distance tests: the squared distance from the probe to the closest point Q of a primitive
 SBN_HD float d2_to(const Probe &p, float qx, float qy)
@@ -116,9 +88,7 @@ SBN_HD float wall_d2(const Probe &p, float bounds, uint32_t wall)
 
 // ---- keys: kept iff d2 <= rmax2 (a NaN drops out; +inf is kept only under rmax = +inf).  d2 is a sum of squares, never -0: its
 // bits order as the floats do.
-SBN_HD uint64_t pack(float d2, uint32_t kind, uint32_t index) { return ((uint64_t)float_as_word(d2) << 32) | ((uint64_t)kind << 16) | (uint64_t)index; }
 SBN_HD uint64_t candidate(const Probe &p, float d2, uint32_t kind, uint32_t index) { return d2 <= p.rmax2 ? pack(d2, kind, index) : SBN_NO_KEY; }
-SBN_HD uint64_t nearer(uint64_t x, uint64_t y) { return x < y ? x : y; }
 SBN_HD uint64_t particle(const Probe &p, float cx, float cy, uint32_t index) { return candidate(p, d2_to(p, cx, cy), PARTICLE, index); }
 SBN_HD uint64_t segment(const Probe &p, float ax, float ay, float bx, float by, uint32_t index) { return candidate(p, segment_d2(p, ax, ay, bx, by), BEAM, index); }
 SBN_HD uint64_t walls(const Probe &p, float bounds)
@@ -128,9 +98,7 @@ SBN_HD uint64_t walls(const Probe &p, float bounds)
     return key;
 }
 
-// ---- a row's answer from its verdict and its smallest key
-SBN_HD uint32_t key_kind(uint64_t key) { return (uint32_t)(key >> 16) & 0xffffu; }
-SBN_HD uint32_t key_index(uint64_t key) { return (uint32_t)key & 0xffffu; }
+// ---- a row's answer from its verdict and its smallest key (its kind and index: sb_query_key.h)
 SBN_HD uint32_t key_d2(uint64_t key) { return (uint32_t)(key >> 32); }
 // the d word: sqrt(d2) of the winner, the row's rmax bits verbatim on a miss, 0 for an empty or invalid row
 SBN_HD uint32_t out_d(int verdict, uint64_t key, uint32_t rmax_bits)
@@ -138,7 +106,5 @@ SBN_HD uint32_t out_d(int verdict, uint64_t key, uint32_t rmax_bits)
     if (verdict != MISS) return 0u;
     return key == SBN_NO_KEY ? rmax_bits : float_as_word(__builtin_sqrtf(word_as_float(key_d2(key))));
 }
-SBN_HD int32_t out_kind(int verdict, uint64_t key) { return verdict != MISS ? verdict : (key == SBN_NO_KEY ? (int32_t)MISS : (int32_t)key_kind(key)); }
-SBN_HD int32_t out_index(int verdict, uint64_t key) { return verdict != MISS || key == SBN_NO_KEY ? -1 : (int32_t)key_index(key); }
 
 } // namespace sbn

@@ -5,25 +5,16 @@
 // so a NaN meets nothing; an infinity follows the operators like any other number.  The winner is a minimum over 64-bit integer
 // keys: no schedule can change a bit of it.  Header-only and HIP-free on the host.
 #pragma once
-#include <stdint.h>
-#include <string.h>
+#include "sb_query_key.h" // the kind, mask and wall words, the key and its decoding: shared with sb_batch_near_math.h
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define SBR_HD __host__ __device__ inline
-#else
-#define SBR_HD inline
-#endif
-
-#define SBR_ROW_WORDS 8u // {mask, ox, oy, dx, dy, tmax, skip_label, 0}: sb_batch_ray
-#define SBR_HIT_WORDS 3u // {kind, index, label}
-#define SBR_NO_KEY 0xFFFFFFFFFFFFFFFFull // above every key: no candidate yet (a key's kind field is never all ones)
+#define SBR_HD SBQ_HD
+#define SBR_ROW_WORDS SBQ_ROW_WORDS // {mask, ox, oy, dx, dy, tmax, skip_label, 0}: sb_batch_ray
+#define SBR_HIT_WORDS SBQ_HIT_WORDS
+#define SBR_NO_KEY SBQ_NO_KEY
 
 namespace sbr {
-
-// the kind word of a hit row; the three hits are also the kind field of a key, so that on equal t a particle beats a beam beats a wall
-enum { MISS = 0, PARTICLE = 1, BEAM = 2, WALL = 3, EMPTY = -1, INVALID = -2 };
-enum { MASK_PARTICLES = 1u, MASK_BEAMS = 2u, MASK_WALLS = 4u, MASK_KNOWN = 7u };
-enum { WALL_LEFT = 1u, WALL_RIGHT = 2u, WALL_LOW = 4u, WALL_HIGH = 8u }; // SB_BATCH_WALL_*: the index of a wall hit
+using namespace sbq; // (re-exported: MISS .. INVALID, MASK_*, WALL_*, word_as_float, float_as_word, finite_bits, skipped, pack, nearer,
+                     // key_kind, key_index, out_kind, out_index)
 
 struct Ray {
     uint32_t mask;
@@ -31,21 +22,6 @@ struct Ray {
     int32_t skip;
     float a; // dx * dx + dy * dy, once per row
 };
-
-SBR_HD float word_as_float(uint32_t w)
-{
-    float f;
-    memcpy(&f, &w, sizeof f);
-    return f;
-}
-SBR_HD uint32_t float_as_word(float f)
-{
-    uint32_t w;
-    memcpy(&w, &f, sizeof w);
-    return w;
-}
-// "a finite number" by its bits (neither infinity nor NaN: the exponent is not all ones)
-SBR_HD bool finite_bits(uint32_t w) { return (w & 0x7f800000u) != 0x7f800000u; }
 
 // a row's verdict: MISS (it is cast), EMPTY or INVALID.  labels: the call has labels.
 SBR_HD int row_verdict(const uint32_t *w, bool labels)
@@ -66,9 +42,6 @@ SBR_HD Ray ray_of(const uint32_t *w)
     return r;
 }
 
-// "is a primitive of this label ignored by this row?" (-1 ignores nothing; without labels every label passed here is -1)
-SBR_HD bool skipped(const Ray &r, int32_t label) { return r.skip != -1 && label == r.skip; }
-
 // every candidate: -0 becomes +0; kept iff 0 <= t <= tmax (*t: the kept t).  A key orders by (t, kind, index): t is non-negative, so
 // its bits order as the floats do.  Two packings of one order: the batch's (16 bits of index) and the engine's (30 bits, sb_raycast.hip).
 SBR_HD bool kept_t(const Ray &r, float t, float *out)
@@ -78,10 +51,8 @@ SBR_HD bool kept_t(const Ray &r, float t, float *out)
     *out = t;
     return true;
 }
-SBR_HD uint64_t pack(float t, uint32_t kind, uint32_t index) { return ((uint64_t)float_as_word(t) << 32) | ((uint64_t)kind << 16) | (uint64_t)index; }
 SBR_HD uint64_t pack_wide(float t, uint32_t kind, uint32_t index) { return ((uint64_t)float_as_word(t) << 32) | ((uint64_t)kind << 30) | (uint64_t)index; }
 SBR_HD uint64_t candidate(const Ray &r, float t, uint32_t kind, uint32_t index) { return kept_t(r, t, &t) ? pack(t, kind, index) : SBR_NO_KEY; }
-SBR_HD uint64_t nearer(uint64_t x, uint64_t y) { return x < y ? x : y; }
 
 // "the t of this meeting, or none": the disc of centre (cx, cy) and squared radius r2
 SBR_HD bool disc_t(const Ray &r, float cx, float cy, float r2, float *t)
@@ -148,17 +119,13 @@ SBR_HD uint64_t segment_wide(const Ray &r, float ax, float ay, float bx, float b
 }
 SBR_HD uint64_t walls_wide(const Ray &r, float bounds) { return walls_as<true>(r, bounds); }
 
-// ---- a row's answer from its verdict and its smallest key
-SBR_HD uint32_t key_kind(uint64_t key) { return (uint32_t)(key >> 16) & 0xffffu; }
-SBR_HD uint32_t key_index(uint64_t key) { return (uint32_t)key & 0xffffu; }
+// ---- a row's answer from its verdict and its smallest key (its kind and index: sb_query_key.h)
 // the t word: the hit's t, the row's tmax bits verbatim on a miss, 0 for an empty or invalid row
 SBR_HD uint32_t out_t(int verdict, uint64_t key, uint32_t tmax_bits)
 {
     if (verdict != MISS) return 0u;
     return key == SBR_NO_KEY ? tmax_bits : (uint32_t)(key >> 32);
 }
-SBR_HD int32_t out_kind(int verdict, uint64_t key) { return verdict != MISS ? verdict : (key == SBR_NO_KEY ? (int32_t)MISS : (int32_t)key_kind(key)); }
-SBR_HD int32_t out_index(int verdict, uint64_t key) { return verdict != MISS || key == SBR_NO_KEY ? -1 : (int32_t)key_index(key); }
 
 // ---- the same answers from a wide key (index: 30 bits)
 #define SBR_WIDE_INDEX_BITS 30u

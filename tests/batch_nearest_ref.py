@@ -2,28 +2,21 @@
 tests/test_gpu_batch_nearest*.py and, against csrc/sb_batch_near_math.h on the host, of tests/test_batch_nearest_cpu.py.
 
 Everything is float32 with one rounding per operator, in the order the definition writes them: numpy's float32 +, -, *, / and sqrt
-are correctly rounded, and no expression here is fused.  The geometry of a scene is the ray cast's (batch_raycast_ref.geometry), on
-what load_scene returns: the particle slots 0 .. particle_count-1 of the mapping at their records' positions, the beam slots
-0 .. beam_count-1 whatever their break flags say (`drop`: data indices the caller wants left out -- the WRONG model that forgets
-that a pending beam still counts).  The winner is the smallest 64-bit key (bits(d2) << 32) | (kind << 16) | index; model="first" is
-the other WRONG model, which takes the first kept primitive in slot order (particles, beams, walls) instead of the nearest."""
+are correctly rounded, and no expression here is fused.  The geometry of a scene, the key (bits(d2) << 32) | (kind << 16) | index
+whose minimum wins, the loop over the rows and the two WRONG models (`drop`, model="first") are tests/batch_query_ref.py's; this file
+holds the row, the distances of a point, its `within` counts, its d word and its closest point."""
 import collections
 
 import numpy as np
 
-from batch_raycast_ref import bodies_labels, geometry  # noqa: F401  (the same geometry and labels as the ray cast's)
+import batch_query_ref as query
+from batch_query_ref import (BEAM, BEAMS, COUNT_FIELDS, COUNT_WORDS, EMPTY, F, HIT_FIELDS, HIT_WORDS, INF, INVALID, MISS, NO_KEY,  # noqa: F401
+                             PARTICLE, PARTICLES, ROW_WORDS, WALL, WALLS, WALL_HIGH, WALL_LEFT, WALL_LOW, WALL_RIGHT, bodies_labels,
+                             geometry)
 
-F = np.float32
-ROW_WORDS, HIT_WORDS, COUNT_WORDS, NEAR_MAX = 8, 3, 4, 256
-PARTICLES, BEAMS, WALLS = 1, 2, 4
-MISS, PARTICLE, BEAM, WALL, EMPTY, INVALID = 0, 1, 2, 3, -1, -2
-WALL_LEFT, WALL_RIGHT, WALL_LOW, WALL_HIGH = 1, 2, 4, 8
+NEAR_MAX = query.ROWS_MAX
 AT_A, AT_B, INSIDE = 0, 1, 2
-HIT_FIELDS = ("kind", "index", "label")
 WITHIN_FIELDS = ("particles", "beams")
-COUNT_FIELDS = ("valid", "particles", "beams", "walls")
-NO_KEY = np.uint64(0xFFFFFFFFFFFFFFFF)
-INF = float("inf")
 
 Nearest = collections.namedtuple("Nearest", "d hit point within counts")
 
@@ -42,22 +35,13 @@ def pack(rows):
 
 def verdict(w, has_labels):
     """MISS (the row is asked), EMPTY or INVALID, from the row's eight words"""
-    w = np.asarray(w, np.uint32)
-    if w[0] == 0:
-        return EMPTY
-    f = w.view(F)
-    if w[0] & ~np.uint32(7) or not np.isfinite(f[1:3]).all() or not f[3] >= 0 or w[5:8].any():
-        return INVALID
-    if w.view(np.int32)[4] != -1 and not has_labels:
-        return INVALID
-    return MISS
+    return query.row_verdict(w, has_labels, slice(1, 3), 3, 4, slice(5, 8))
 
 
 def keys(d2, rmax2, kind, index):
     """the keys of squared distances d2 (float32 array), NO_KEY where one is not kept"""
     d2 = np.asarray(d2, F)
-    k = (d2.view(np.uint32).astype(np.uint64) << np.uint64(32)) | np.uint64(kind << 16) | np.asarray(index, np.uint64)
-    return np.where(d2 <= rmax2, k, NO_KEY)
+    return query.keys(d2, d2 <= rmax2, kind, index)
 
 
 def d2_to(qx, qy, px, py):
@@ -122,67 +106,44 @@ def nearest_ref(buf, rows, bounds=1000.0, labels=None, model="nearest", drop=(),
     rows: uint32 [k, 8].  ties: a list that gets, per row with a winner, the number of kept primitives that share its d2 bits;
     d2_bits: a list that gets, per row, the winner's d2 bits (0 where there is none)."""
     rows = np.ascontiguousarray(rows, np.uint32).reshape(-1, ROW_WORDS)
-    g = geometry(buf, labels, drop)
-    lab = None if labels is None else np.asarray(labels, np.int64)
     n = len(rows)
-    d, hit, point = np.zeros(n, np.uint32), np.zeros((n, HIT_WORDS), np.int32), np.zeros((n, 2), np.uint32)
-    within, counts = np.zeros((n, 2), np.int32), np.zeros(COUNT_WORDS, np.int32)
+    d, point, within = np.zeros(n, np.uint32), np.zeros((n, 2), np.uint32), np.zeros((n, 2), np.int32)
     pos = None if buf is None else buf.particles.astype(F)
-    for j, w in enumerate(rows):
-        v = verdict(w, labels is not None)
-        if d2_bits is not None:
-            d2_bits.append(0)
-        if v != MISS:
-            hit[j] = (v, -1, -1)
-            continue
-        counts[0] += 1
+
+    def kept(g, w, j):
         k, within[j, 0], within[j, 1] = candidates(g, w, bounds, branches)
-        kept = k[k != NO_KEY]
-        if kept.size == 0:
-            d[j], hit[j], point[j] = w[3], (MISS, -1, -1), w[1:3]
-            continue
-        best = kept[0] if model == "first" else kept.min()
-        if ties is not None:
-            ties.append(int(((kept >> np.uint64(32)) == (best >> np.uint64(32))).sum()))
-        kind, index = int(best >> np.uint64(16)) & 0xFFFF, int(best) & 0xFFFF
+        return k
+
+    def answer(j, w, best, kind, index):
         if d2_bits is not None:
-            d2_bits[-1] = int(best >> np.uint64(32))
+            d2_bits.append(0 if best is None else int(best >> np.uint64(32)))
+        if best is None:
+            if kind == MISS:
+                d[j], point[j] = w[3], w[1:3]
+            return
         px, py = w.view(F)[1], w.view(F)[2]
-        label = -1
         with np.errstate(all="ignore"):
             if kind == PARTICLE:
                 q = pos[index, :2]
-                label = -1 if lab is None else int(lab[index])
             elif kind == BEAM:
                 a, b = int(buf.beams["a"][index]), int(buf.beams["b"][index])
                 qx, qy, _ = segment_q(*(np.asarray([x], F) for x in (pos[a, 0], pos[a, 1], pos[b, 0], pos[b, 1])), px, py)
                 q = np.asarray([qx[0], qy[0]], F)
-                label = -1 if lab is None else int(lab[a])
             else:
                 q = np.asarray(wall_q(px, py, bounds)[index][:2], F)
             d[j] = np.sqrt(np.asarray([int(best >> np.uint64(32))], np.uint32).view(F))[0].view(np.uint32)
-        hit[j], point[j] = (kind, index, label), np.asarray(q, F).view(np.uint32)
-        counts[kind] += 1
+        point[j] = np.asarray(q, F).view(np.uint32)
+    hit, counts = query.answers(buf, rows, labels, verdict, kept, answer, model, drop, ties)
     return d, hit, point, within, counts
 
 
 def nearest_of(bufs_now, rows, bounds=1000.0, labels=None, **kw):
     """The five arrays of a batch, stacked (d and point as float32), from one Buffers per scene (None: never uploaded), rows uint32
     [N, k, 8] and labels int32 [N, max_particles] or None."""
-    got = [nearest_ref(b, rows[i], bounds, None if labels is None else labels[i], **kw) for i, b in enumerate(bufs_now)]
-    s = lambda i: np.stack([x[i] for x in got])
-    return Nearest(s(0).view(F), s(1), s(2).view(F), s(3), s(4))
+    return query.stacked(Nearest, ("d", "point"), [nearest_ref(b, rows[i], bounds, None if labels is None else labels[i], **kw)
+                                                  for i, b in enumerate(bufs_now)])
 
 
 def same(got, want):
     """the names of the arrays of two Nearests that differ, by their bits"""
-    bad = []
-    for name, x, y in zip(Nearest._fields, got, want):
-        if x is None:
-            continue
-        x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
-        if x.dtype == F:
-            x, y = x.view(np.uint32), y.view(np.uint32)
-        if x.shape != y.shape or not np.array_equal(x, y):
-            bad.append(name)
-    return bad
+    return query.same(Nearest._fields, got, want)

@@ -13,46 +13,17 @@ import batch_add_beams_cases as add_cases
 import batch_add_beams_ref as add_ref
 import batch_nearest_cases as cases
 import batch_nearest_ref as ref
-from batch_harness import load_all, make_batch, upload_each
+from batch_harness import load_all
+from batch_query_rig import GRID, OFF, batch, dev, query, raw
 from test_gpu_parity import assert_same
 
 pytestmark = pytest.mark.gpu
 
-OFF, GRID = 0, 2
 F = np.float32
 INF = ref.INF
 
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).cuda()
-
-
-def batch(sb, bufs, mode=OFF, cap=cases.CAP, layout=cases.LAYOUT):
-    be = make_batch(sb, dict(layout=layout, cap=cap, bufs=bufs, mode=mode), mode=mode)
-    upload_each(be, bufs)
-    return be
-
-
-def ask(be, rows, labels=None):
-    """the five outputs as numpy, written into tensors the test filled with a pattern first: every word is written"""
-    import torch
-    n, k = be.n_scenes, rows.shape[1]
-    fill = lambda shape, dt: torch.full(shape, -1515870811 if dt == torch.int32 else -7.25, dtype=dt, device="cuda")   # 0xA5A5A5A5
-    got = be.nearest(dev(rows), labels=labels if labels is None or labels is True else dev(labels), d=fill((n, k), torch.float32),
-                     hit=fill((n, k, 3), torch.int32), point=fill((n, k, 2), torch.float32), within=fill((n, k, 2), torch.int32),
-                     counts=fill((n, 4), torch.int32))
-    return ref.Nearest(*(x.cpu().numpy() for x in got))
-
-
-def check(be, bufs, rows, labels=None, what=""):
-    """nearest() == the restatement on what load_scene returns now; returns (the scenes as read back, the result)"""
-    now = load_all(be, bufs)
-    want = ref.nearest_of(now, rows, labels=labels)
-    got = ask(be, rows, labels)
-    print(what, "counts", got.counts[:12].tolist(), "want", want.counts[:12].tolist())
-    assert ref.same(got, want) == [], what
-    return now, got
+ask, check = query("nearest", ref.nearest_of, ref.Nearest, ref.same, (("d", (), "float32"), ("hit", (3,), "int32"), ("point", (2,), "float32"),
+                                                                      ("within", (2,), "int32"), ("counts", None, "int32")))
 
 
 def on_beams(buf, ds):
@@ -62,12 +33,6 @@ def on_beams(buf, ds):
         pa, pb = (buf.particles[int(buf.beams[e][d]), :2].astype(np.float64) for e in ("a", "b"))
         rows.append((ref.BEAMS, *(0.75 * pa + 0.25 * pb), 2.0))
     return rows
-
-
-def raw(be):
-    """every byte the other reports can see: state rows, summary, bodies"""
-    p, b, a = be.state_tensors()
-    return [x.cpu().numpy().tobytes() for x in (p, b, a, be.summary(), *be.bodies())]
 
 
 @pytest.mark.parametrize("mode", [OFF, GRID])

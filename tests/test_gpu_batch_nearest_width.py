@@ -10,7 +10,8 @@ import batch_add_beams_cases as add_cases
 import batch_nearest_cases as cases
 import batch_nearest_ref as ref
 from batch_harness import make_batch
-from test_gpu_batch_nearest import batch, check
+from batch_query_rig import batch
+from test_gpu_batch_nearest import check
 
 pytestmark = pytest.mark.gpu
 

@@ -11,45 +11,16 @@ import pytest
 import batch_add_beams_cases as add_cases
 import batch_raycast_cases as cases
 import batch_raycast_ref as ref
-from batch_harness import load_all, make_batch, upload_each
+from batch_harness import load_all
+from batch_query_rig import GRID, OFF, batch, dev, query, raw
 from test_gpu_parity import assert_same
 
 pytestmark = pytest.mark.gpu
 
-OFF, GRID = 0, 2
 F = np.float32
 INF = ref.INF
 
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).cuda()
-
-
-def batch(sb, bufs, mode=OFF, cap=cases.CAP, layout=cases.LAYOUT):
-    be = make_batch(sb, dict(layout=layout, cap=cap, bufs=bufs, mode=mode), mode=mode)
-    upload_each(be, bufs)
-    return be
-
-
-def cast(be, rows, labels=None):
-    """the three outputs as numpy, written into tensors the test filled with a pattern first: every word is written"""
-    import torch
-    n, k = be.n_scenes, rows.shape[1]
-    fill = lambda shape, dt: torch.full(shape, -1515870811 if dt == torch.int32 else -7.25, dtype=dt, device="cuda")   # 0xA5A5A5A5
-    got = be.raycast(dev(rows), labels=labels if labels is None or labels is True else dev(labels), t=fill((n, k), torch.float32),
-                     hit=fill((n, k, 3), torch.int32), counts=fill((n, 4), torch.int32))
-    return ref.RayCast(*(x.cpu().numpy() for x in got))
-
-
-def check(be, bufs, rows, labels=None, what=""):
-    """raycast() == the restatement on what load_scene returns now; returns (the scenes as read back, the result)"""
-    now = load_all(be, bufs)
-    want = ref.raycast_of(now, rows, labels=labels)
-    got = cast(be, rows, labels)
-    print(what, "counts", got.counts[:12].tolist(), "want", want.counts[:12].tolist())
-    assert ref.same(got, want) == [], what
-    return now, got
+cast, check = query("raycast", ref.raycast_of, ref.RayCast, ref.same, (("t", (), "float32"), ("hit", (3,), "int32"), ("counts", None, "int32")))
 
 
 def at_beams(buf, ds, off=4.0):
@@ -61,12 +32,6 @@ def at_beams(buf, ds, off=4.0):
         n = np.array([-e[1], e[0]])
         rows.append((ref.BEAMS, *(mid + off * n + 1.5 * e), *(-n), 2.0 * off))
     return rows
-
-
-def raw(be):
-    """every byte the other reports can see: state rows, summary, bodies"""
-    p, b, a = be.state_tensors()
-    return [x.cpu().numpy().tobytes() for x in (p, b, a, be.summary(), *be.bodies())]
 
 
 @pytest.mark.parametrize("mode", [OFF, GRID])
@@ -247,5 +212,5 @@ def test_kernel_resources(sb):
     be = sb.BatchEngine(n_scenes=1, max_particles=1024, max_beams=4096)
     assert be.info("raycast_kernel_scratch_bytes") == 0 and 0 < be.info("raycast_kernel_vgprs") <= 128
     assert (be.info("ray_max"), be.info("ray_hit_words"), be.info("ray_count_words")) == (256, 3, 4)
-    assert be.info("raycast_lds_bytes") == (2 * 256 + 4 * 1024 + 4096 + 8 * 256) * 4 <= 65536
+    assert be.info("raycast_lds_bytes") == (2 * 256 + 4 * 1024 + 4096 + 8 * 256 + 4) * 4 <= 65536
     be.destroy()

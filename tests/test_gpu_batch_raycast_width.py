@@ -9,7 +9,8 @@ import batch_add_beams_cases as add_cases
 import batch_raycast_cases as cases
 import batch_raycast_ref as ref
 from batch_harness import make_batch
-from test_gpu_batch_raycast import batch, check
+from batch_query_rig import batch
+from test_gpu_batch_raycast import check
 
 pytestmark = pytest.mark.gpu
 
