@@ -1408,6 +1408,59 @@ sb_status sb_raycast_device(sb_engine *e, const sb_raycast_options *opts, const 
 sb_status sb_raycast(sb_engine *e, const sb_raycast_options *opts, const sb_batch_ray *rays, uint32_t n_rays, const int32_t *labels, float *t,
                      int32_t *hit, int64_t *counts);
 
+/* ---- proximity queries over the whole scene of ONE engine, on the device, bit for bit ----
+ * sb_nearest_device / sb_nearest -- sb_batch_nearest_device's question asked of an sb_engine: n_points rows of sb_batch_near_point
+ * (the same 32 bytes, masks and verdicts), for each the nearest among the scene's particles (centres), live beams (segments) and the
+ * four walls, the closest point on it, and how many particles and beams lie within rmax.  The DEFINITION is the one above, word for
+ * word: particle centres, the clamped projection on a beam, the walls; rmax2 = rmax * rmax computed once, kept iff d2 <= rmax2;
+ * skipping by the label of the particle or of the beam's endpoint A; the winner the smallest (d2 bits, kind, index).  The geometry is
+ * sb_raycast_device's: what sb_load_buffers would return at this point of the stream, beams LIVE by sb_bodies' rule (a pending break
+ * flag still counts), radius and bounds sb_options'.  A scene that fits a batch gives exactly the batch's d, hit, point and within
+ * rows.  The key is the wide one, (bits(d2) << 32) | (kind << 30) | index: the same order, room for an engine's indices;
+ * max_particles or max_beams above 2^30: SB_ERR_UNSUPPORTED.
+ *   labels   int32 [max_particles] at particle data indices (sb_bodies' labels, or the caller's own), or NULL; only compared.
+ *   d        float32 [n_points]: sqrt(d2) of the winner; the row's rmax bits on a miss; 0 for an empty or invalid row.
+ *   hit      int32 [n_points][SB_BATCH_NEAR_HIT_WORDS] {kind, index, label} as above.
+ *   point    float32 [n_points][2]: the winner's closest point, computed again from the winner by the definition's expressions; the
+ *            query point's bits on a miss; 0, 0 for an empty or invalid row.
+ *   within   int32 [n_points][2]: particles and beams kept, not skipped, mask bit on; 0, 0 for an empty or invalid row.
+ *   counts   int64 [SB_NEAREST_COUNT_WORDS]: 0 valid rows, 1 winners that are particles, 2 beams, 3 walls; then three COST words,
+ *            pure functions of the rows' bits, the positions, the cells and max_rings: 4 rows answered by the sweep, 5 particles
+ *            outside the grid, 6 long beams; 7 is 0.
+ * Each output may be NULL, not all of them; every word of one that is passed is written.
+ * COST.  The grid is the ray casts': the same cells, the same sort, the same cells_per_side rule and cap.  A row is LOCAL iff px and py
+ * lie in [-bounds, 2 bounds].  A local row looks into the cells round its point ring by ring (csrc/sb_near_walk.h derives which, and
+ * when it may stop, from the rounding of the distances): it stops once nothing further on can be kept (rmax), or -- where within is
+ * NULL -- once nothing further on can win.  A row whose walk has not stopped after max_rings rings (0: the default,
+ * "nearest_max_rings"; rings that lie wholly outside the grid are not counted), and every row that is not local, is tested against
+ * every primitive by the sweep: word 4.  So rmax = +inf with within costs a pass over the scene per row unless the rings cover the
+ * grid -- the count of everything is a sum over everything; rmax = +inf without within stops at the winner.  Words 5 and 6 are the
+ * ray casts': every row is tested against those leftovers.  The outputs never depend on cells_per_side or max_rings.
+ * sb_nearest_device only ENQUEUES on the engine's stream, reads nothing back and waits for nothing but the one table build after an
+ * upload; it only READS the engine: frame, nearest, frame equals frame, frame bit for bit.  sb_nearest is the host-copy convenience:
+ * rows and labels from host memory, the same launches, the outputs copied back; it waits.
+ * Errors, before anything touches a device: SB_ERR_INVALID for a NULL handle, a struct_size that is neither 0 nor the struct's, an
+ * unknown flag (none is defined: flags must be 0), a nonzero reserved word, NULL rows with n_points > 0, all outputs NULL, rows /
+ * labels / d / hit / point / within not 4-byte or counts not 8-byte aligned, n_points above 2^24, cells_per_side or max_rings above
+ * 8192; SB_ERR_STATE before an upload; SB_ERR_UNSUPPORTED with ranks or ghost zones, or capacities above 2^30.  n_points == 0 is SB_OK
+ * and enqueues nothing.  sb_get_info: "nearest_cells_per_side" (the default rule on the scene as it is), "nearest_max_rings" (the
+ * default), "nearest_kernel_vgprs", "nearest_kernel_scratch_bytes". */
+#define SB_NEAREST_COUNT_WORDS 8u
+typedef struct sb_nearest_options {
+    uint32_t struct_size;    /* = sizeof(sb_nearest_options); 0 or a NULL pointer = all defaults */
+    uint32_t flags;          /* none defined: 0 */
+    uint32_t cells_per_side; /* 0: the default rule (sb_raycast_options') */
+    uint32_t max_rings;      /* 0: the default; at most 8192 */
+    uint32_t reserved[4];    /* zero */
+} sb_nearest_options;
+sb_status sb_nearest_device(sb_engine *e, const sb_nearest_options *opts, const void *device_points /* [n_points] sb_batch_near_point */,
+                            uint32_t n_points, const void *device_labels_i32 /* [max_particles] or NULL */,
+                            void *device_d_f32 /* [n_points] or NULL */, void *device_hit_i32 /* [n_points][SB_BATCH_NEAR_HIT_WORDS] or NULL */,
+                            void *device_point_f32 /* [n_points][2] or NULL */, void *device_within_i32 /* [n_points][2] or NULL */,
+                            void *device_counts_i64 /* [SB_NEAREST_COUNT_WORDS] or NULL */);
+sb_status sb_nearest(sb_engine *e, const sb_nearest_options *opts, const sb_batch_near_point *points, uint32_t n_points, const int32_t *labels,
+                     float *d, int32_t *hit, float *point, int32_t *within, int64_t *counts);
+
 /* scene i back into host buffers exactly as sb_load_buffers returns a single engine in the same state (counts in the metadata,
  * the mapping after the delete passes' stable in-place compactions, beam records with strain / stress; only records reachable
  * through the uploaded mapping are written; any pointer may be NULL).  SB_ERR_STATE for a scene never uploaded. */

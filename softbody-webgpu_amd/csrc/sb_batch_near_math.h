@@ -88,15 +88,29 @@ SBN_HD float wall_d2(const Probe &p, float bounds, uint32_t wall)
 
 // ---- keys: kept iff d2 <= rmax2 (a NaN drops out; +inf is kept only under rmax = +inf).  d2 is a sum of squares, never -0: its
 // bits order as the floats do.
-SBN_HD uint64_t candidate(const Probe &p, float d2, uint32_t kind, uint32_t index) { return d2 <= p.rmax2 ? pack(d2, kind, index) : SBN_NO_KEY; }
-SBN_HD uint64_t particle(const Probe &p, float cx, float cy, uint32_t index) { return candidate(p, d2_to(p, cx, cy), PARTICLE, index); }
-SBN_HD uint64_t segment(const Probe &p, float ax, float ay, float bx, float by, uint32_t index) { return candidate(p, segment_d2(p, ax, ay, bx, by), BEAM, index); }
-SBN_HD uint64_t walls(const Probe &p, float bounds)
+// Two packings of one order: the batch's (16 bits of index) and the engine's (WIDE: 30 bits, sb_nearest.hip); one copy of the arithmetic.
+SBN_HD uint64_t pack_wide(float d2, uint32_t kind, uint32_t index) { return ((uint64_t)float_as_word(d2) << 32) | ((uint64_t)kind << 30) | (uint64_t)index; }
+template <bool WIDE>
+SBN_HD uint64_t candidate_as(const Probe &p, float d2, uint32_t kind, uint32_t index)
+{
+    if (!(d2 <= p.rmax2)) return SBN_NO_KEY;
+    return WIDE ? pack_wide(d2, kind, index) : pack(d2, kind, index);
+}
+template <bool WIDE>
+SBN_HD uint64_t walls_as(const Probe &p, float bounds)
 {
     uint64_t key = SBN_NO_KEY;
-    for (uint32_t wall = WALL_LEFT; wall <= WALL_HIGH; wall <<= 1) key = nearer(key, candidate(p, wall_d2(p, bounds, wall), WALL, wall));
+    for (uint32_t wall = WALL_LEFT; wall <= WALL_HIGH; wall <<= 1) key = nearer(key, candidate_as<WIDE>(p, wall_d2(p, bounds, wall), WALL, wall));
     return key;
 }
+SBN_HD uint64_t candidate(const Probe &p, float d2, uint32_t kind, uint32_t index) { return candidate_as<false>(p, d2, kind, index); }
+SBN_HD uint64_t particle(const Probe &p, float cx, float cy, uint32_t index) { return candidate(p, d2_to(p, cx, cy), PARTICLE, index); }
+SBN_HD uint64_t segment(const Probe &p, float ax, float ay, float bx, float by, uint32_t index) { return candidate(p, segment_d2(p, ax, ay, bx, by), BEAM, index); }
+SBN_HD uint64_t walls(const Probe &p, float bounds) { return walls_as<false>(p, bounds); }
+// the engine's packing of the same three distances (SBN_NO_KEY is above every wide key too: a wide key's kind is never 3 with an index of all ones)
+SBN_HD uint64_t particle_wide(const Probe &p, float cx, float cy, uint32_t index) { return candidate_as<true>(p, d2_to(p, cx, cy), PARTICLE, index); }
+SBN_HD uint64_t segment_wide(const Probe &p, float ax, float ay, float bx, float by, uint32_t index) { return candidate_as<true>(p, segment_d2(p, ax, ay, bx, by), BEAM, index); }
+SBN_HD uint64_t walls_wide(const Probe &p, float bounds) { return walls_as<true>(p, bounds); }
 
 // ---- a row's answer from its verdict and its smallest key (its kind and index: sb_query_key.h)
 SBN_HD uint32_t key_d2(uint64_t key) { return (uint32_t)(key >> 32); }
@@ -106,5 +120,12 @@ SBN_HD uint32_t out_d(int verdict, uint64_t key, uint32_t rmax_bits)
     if (verdict != MISS) return 0u;
     return key == SBN_NO_KEY ? rmax_bits : float_as_word(__builtin_sqrtf(word_as_float(key_d2(key))));
 }
+
+// ---- the same answers from a wide key (index: 30 bits; key_d2 and out_d read the high word, which both packings share)
+#define SBN_WIDE_INDEX_BITS 30u
+SBN_HD uint32_t wide_kind(uint64_t key) { return (uint32_t)(key >> SBN_WIDE_INDEX_BITS) & 3u; }
+SBN_HD uint32_t wide_index(uint64_t key) { return (uint32_t)key & ((1u << SBN_WIDE_INDEX_BITS) - 1u); }
+SBN_HD int32_t out_kind_wide(int verdict, uint64_t key) { return verdict != MISS ? verdict : (key == SBN_NO_KEY ? (int32_t)MISS : (int32_t)wide_kind(key)); }
+SBN_HD int32_t out_index_wide(int verdict, uint64_t key) { return verdict != MISS || key == SBN_NO_KEY ? -1 : (int32_t)wide_index(key); }
 
 } // namespace sbn

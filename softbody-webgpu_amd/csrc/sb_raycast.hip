@@ -37,12 +37,6 @@ enum { SBW_A_VALID, SBW_A_PART, SBW_A_BEAM, SBW_A_WALL, SBW_A_SWEPT, SBW_A_OUTSI
 static_assert(SB_RAYCAST_COUNT_WORDS == SBW_NACC, "an accumulator per count word");
 static_assert(sizeof(sb_batch_ray) == SBR_ROW_WORDS * 4u && sizeof(srw::Rec) == 24u, "the row and the record");
 
-SB_DEV void sbw_count(unsigned long long *acc, uint32_t word, bool mine)
-{
-    const unsigned long long m = __ballot(mine);
-    if (m && __lane_id() == (uint32_t)__ffsll((long long)m) - 1u) atomicAdd(&acc[word], (unsigned long long)__popcll(m));
-}
-
 // threads [0, np): particle data indices; [np, np + n): caller beam slots.  tab: [4][n] = data index of A, of B, engine slot, copy.
 // scatter == 0: count the bins; 1: place the records (the same bins: nothing moves between the two launches).
 __global__ __launch_bounds__(SBW_BLOCK) void k_ray_bin(const uint32_t *__restrict__ pinv, uint32_t np, const float2 *__restrict__ pos,
@@ -228,7 +222,7 @@ __global__ __launch_bounds__(64) void k_ray_counts(const unsigned long long *__r
 
 // The grid of a call: the largest G <= cap (cells_per_side, or the default rule's) whose cells are at least 2r (1 + 1/64) wide
 // (sb_batch_cell_geometry); one cell where radius or bounds are no numbers sb_ray_walk.h's derivation covers.
-static srw::Grid sbw_grid(const sb_engine *e, uint32_t cells_per_side)
+srw::Grid sbw_grid(const sb_engine *e, uint32_t cells_per_side)
 {
     srw::Grid g{1u, 1.0f, e->prm.bounds_size, e->prm.particle_radius};
     float cell = 1.0f;
@@ -240,6 +234,44 @@ static srw::Grid sbw_grid(const sb_engine *e, uint32_t cells_per_side)
 }
 
 static size_t sbw_up(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
+
+SbwSortPlan sbw_sort_plan(const sb_engine *e, uint32_t G)
+{
+    const SbStateIoState &s = *e->sio;
+    SbwSortPlan p;
+    p.nbin = (uint64_t)G * G + 2u, p.nb_scan = (p.nbin + SBQ_SCAN - 1u) / SBQ_SCAN, p.items = (uint64_t)s.np + s.nslots;
+    return p;
+}
+
+// The counting sort of the scene into the cells of g, enqueued on the engine's stream (sb_report.h; sb_nearest.hip calls it too):
+// the accumulators (acc_bytes: the count words and what the caller keeps behind them), the bins and a_of cleared, k_ray_bin,
+// sbq_scan, k_ray_bin again.  It needs the shared scene tables and sbx_build_rows' rows.
+sb_status sbw_sort(sb_engine *e, const srw::Grid &g, unsigned long long *acc, size_t acc_bytes, uint32_t *d_cells, uint32_t *bsum, srw::Rec *sorted,
+                   uint32_t *a_of, uint32_t *total)
+{
+    SbStateIoState &s = *e->sio;
+    const uint32_t np = s.np, n = s.nslots, maxB = e->opt.max_beams, nd = s.cut_nd;
+    const SbwSortPlan plan = sbw_sort_plan(e, g.G);
+    const uint32_t *d_pinv = s.buf[SBQ_B_PINV].as<uint32_t>(), *d_tab = s.buf[SBQ_B_TAB].as<uint32_t>(), *d_row = s.buf[SBX_B_ROW].as<uint32_t>();
+    const float2 *pos = e->part[e->cur].pos;
+    const uint32_t blocks = (uint32_t)((plan.items + SBW_BLOCK - 1u) / SBW_BLOCK);
+    SB_HIP(e, hipMemsetAsync(acc, 0, acc_bytes, e->stream));
+    SB_HIP(e, hipMemsetAsync(d_cells, 0, plan.nbin * 4, e->stream));
+    if (a_of && nd) SB_HIP(e, hipMemsetAsync(a_of, 0xFF, (size_t)nd * 4, e->stream));
+    if (plan.items)
+        k_ray_bin<<<blocks, SBW_BLOCK, 0, e->stream>>>(d_pinv, np, pos, d_tab, n, d_row, sbq_dead(e), maxB, g, 0u, d_cells, sorted, a_of, nd, acc);
+    sbq_scan<uint32_t>(e, d_cells, plan.nbin, bsum, d_cells, total);
+    if (plan.items)
+        k_ray_bin<<<blocks, SBW_BLOCK, 0, e->stream>>>(d_pinv, np, pos, d_tab, n, d_row, sbq_dead(e), maxB, g, 1u, d_cells, sorted, nullptr, nd, acc);
+    return SB_OK;
+}
+
+std::vector<const void *> sbw_sort_kernels()
+{
+    std::vector<const void *> ks = {(const void *)k_ray_bin};
+    for (const void *f : sbq_scan_kernels(false)) ks.push_back(f);
+    return ks;
+}
 
 static sb_status sbw_enqueue(sb_engine *e, const sb_raycast_options *o, const void *rays, uint32_t n_rays, const void *labels, void *t, void *hit,
                              void *counts, bool host)
@@ -268,16 +300,15 @@ static sb_status sbw_enqueue(sb_engine *e, const sb_raycast_options *o, const vo
     s.ray_build_ms = s.part_ms + s.beam_ms + s.copy_ms + s.cut_row_ms;
 
     const srw::Grid g = sbw_grid(e, cells_per_side);
-    const uint32_t np = s.np, n = s.nslots, maxP = e->opt.max_particles, maxB = e->opt.max_beams, nd = s.cut_nd;
-    const uint32_t cells = g.G * g.G;
-    const uint64_t nbin = (uint64_t)cells + 2u, nb_scan = (nbin + SBQ_SCAN - 1u) / SBQ_SCAN, items = (uint64_t)np + n;
+    const uint32_t maxP = e->opt.max_particles, nd = s.cut_nd, cells = g.G * g.G;
+    const SbwSortPlan plan = sbw_sort_plan(e, g.G);
     const bool want_a = labels && hit;
     // the call's scratch, one block: the accumulators, the sweep's row count and the scan's total, the bins, the scan's block sums,
     // the records, the keys, the sweep's rows, per beam data index its endpoint A
     size_t at = 0;
     auto take = [&at](size_t bytes) { const size_t o0 = at; at += sbw_up(bytes); return o0; };
-    const size_t o_acc = take(SBW_NACC * 8 + 8), o_cells = take(nbin * 4), o_bsum = take(nb_scan * 4),
-                 o_sorted = take(items * sizeof(srw::Rec)), o_keys = take((size_t)n_rays * 8), o_list = take((size_t)n_rays * 4),
+    const size_t o_acc = take(SBW_NACC * 8 + 8), o_cells = take(plan.nbin * 4), o_bsum = take(plan.nb_scan * 4),
+                 o_sorted = take(plan.items * sizeof(srw::Rec)), o_keys = take((size_t)n_rays * 8), o_list = take((size_t)n_rays * 4),
                  o_aof = take(want_a ? (size_t)nd * 4 : 0);
     SB_TRY(s.buf[SBW_B_SCRATCH].grow(e, at));
     unsigned char *base = s.buf[SBW_B_SCRATCH].as<unsigned char>();
@@ -295,17 +326,8 @@ static sb_status sbw_enqueue(sb_engine *e, const sb_raycast_options *o, const vo
     SB_TRY(mir.st);
 
     auto blocks = [](uint64_t k) { return (uint32_t)((k + SBW_BLOCK - 1u) / SBW_BLOCK); };
-    const uint32_t *d_pinv = s.buf[SBQ_B_PINV].as<uint32_t>(), *d_tab = s.buf[SBQ_B_TAB].as<uint32_t>(), *d_row = s.buf[SBX_B_ROW].as<uint32_t>();
-    const float2 *pos = e->part[e->cur].pos;
-    SB_HIP(e, hipMemsetAsync(acc, 0, SBW_NACC * 8 + 8, e->stream));
-    SB_HIP(e, hipMemsetAsync(d_cells, 0, nbin * 4, e->stream));
+    SB_TRY(sbw_sort(e, g, acc, SBW_NACC * 8 + 8, d_cells, bsum, sorted, a_of, total));
     SB_HIP(e, hipMemsetAsync(keys, 0xFF, (size_t)n_rays * 8, e->stream)); // SBR_NO_KEY
-    if (a_of && nd) SB_HIP(e, hipMemsetAsync(a_of, 0xFF, (size_t)nd * 4, e->stream));
-    if (items)
-        k_ray_bin<<<blocks(items), SBW_BLOCK, 0, e->stream>>>(d_pinv, np, pos, d_tab, n, d_row, sbq_dead(e), maxB, g, 0u, d_cells, sorted, a_of, nd, acc);
-    sbq_scan<uint32_t>(e, d_cells, nbin, bsum, d_cells, total);
-    if (items)
-        k_ray_bin<<<blocks(items), SBW_BLOCK, 0, e->stream>>>(d_pinv, np, pos, d_tab, n, d_row, sbq_dead(e), maxB, g, 1u, d_cells, sorted, nullptr, nd, acc);
     k_ray_walk<<<blocks(n_rays), SBW_BLOCK, 0, e->stream>>>(d_rays, n_rays, d_labels, sorted, d_cells, g, keys, list, n_list, acc);
     k_ray_sweep<<<SBW_SWEEP_BLOCKS, SBW_BLOCK, 0, e->stream>>>(d_rays, d_labels, sorted, total, g.radius, list, n_list, keys);
     k_ray_leftover<<<blocks(n_rays), SBW_BLOCK, 0, e->stream>>>(d_rays, n_rays, d_labels, sorted, d_cells, cells, g.bounds, g.radius, keys);
@@ -322,9 +344,9 @@ bool sbw_info(sb_engine *e, const char *key, uint64_t *value)
     if (k == "raycast_cells_per_side") *value = sbw_grid(e, 0u).G; // the default rule on the scene as it is now
     else if (k == "raycast_table_build_us") *value = e->sio ? (uint64_t)(e->sio->ray_build_ms * 1000.0 + 0.5) : 0u;
     else if (k == "raycast_kernel_vgprs" || k == "raycast_kernel_scratch_bytes") {
-        std::vector<const void *> ks = {(const void *)k_ray_bin, (const void *)k_ray_walk, (const void *)k_ray_sweep, (const void *)k_ray_leftover,
-                                        (const void *)k_ray_finish, (const void *)k_ray_counts};
-        for (const void *f : sbq_scan_kernels(false)) ks.push_back(f);
+        std::vector<const void *> ks = {(const void *)k_ray_walk, (const void *)k_ray_sweep, (const void *)k_ray_leftover, (const void *)k_ray_finish,
+                                        (const void *)k_ray_counts};
+        for (const void *f : sbw_sort_kernels()) ks.push_back(f);
         return sbq_kernel_most(e, ks, k == "raycast_kernel_vgprs", value);
     }
     else return false;

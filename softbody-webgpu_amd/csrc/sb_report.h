@@ -1,5 +1,5 @@
 // sb_report.h -- what the engine's state calls (sb_state_io.hip), its four whole-scene reports (sb_summary.hip, sb_bodies.hip,
-// sb_contacts.hip, sb_body_summary.hip), the cut (sb_cut.hip), the graph (sb_graph.hip) and the ray casts (sb_raycast.hip) share: the owner of their device
+// sb_contacts.hip, sb_body_summary.hip), the cut (sb_cut.hip), the graph (sb_graph.hip), the ray casts (sb_raycast.hip) and the proximity queries (sb_nearest.hip) share: the owner of their device
 // buffers, the preflight of a call, the host mirror of a report, the scene tables of the latest upload, the exclusive scan and
 // the wave's run counter.  What only one report uses stays in its file.
 #pragma once
@@ -28,6 +28,7 @@ enum SbReportBuf {
     SBX_B_ROW, SBX_B_MARK, SBX_B_ACC, SBX_B_SHAPES, SBX_B_HIT,                     // sb_cut.hip (SBX_B_ROW: also sb_graph.hip)
     SBG_B_SCRATCH, SBG_B_ENDS, SBG_B_ROWPTR, SBG_B_NBR, SBG_B_COUNTS,              // sb_graph.hip
     SBW_B_SCRATCH, SBW_B_RAYS, SBW_B_LABELS, SBW_B_T, SBW_B_HIT, SBW_B_COUNTS,      // sb_raycast.hip
+    SBV_B_SCRATCH, SBV_B_POINTS, SBV_B_LABELS, SBV_B_D, SBV_B_HIT, SBV_B_POINT, SBV_B_WITHIN, SBV_B_COUNTS, // sb_nearest.hip
     SBQ_NBUF
 };
 
@@ -77,6 +78,7 @@ inline const char *sbq_options_name(const sb_body_summary_options *) { return "s
 inline const char *sbq_options_name(const sb_cut_options *) { return "sb_cut_options"; }
 inline const char *sbq_options_name(const sb_graph_options *) { return "sb_graph_options"; }
 inline const char *sbq_options_name(const sb_raycast_options *) { return "sb_raycast_options"; }
+inline const char *sbq_options_name(const sb_nearest_options *) { return "sb_nearest_options"; }
 
 sb_status sbq_ready(sb_engine *e, const char *what, const char *why); // loaded, no ranks (`why`: the call's parenthesis); the device; e->sio
 
@@ -177,3 +179,29 @@ SB_DEV uint32_t sbq_run_length(uint32_t key, bool valid)
     const unsigned long long rest = lane == 63u ? 0ull : heads >> (lane + 1u);
     return rest ? (uint32_t)__ffsll(rest) : 64u - lane; // up to the next head, or to the end of the wave
 }
+
+// one atomicAdd per wave on a count word: how many of its lanes say `mine`.  Every lane of the wave calls it.
+SB_DEV void sbw_count(unsigned long long *acc, uint32_t word, bool mine)
+{
+    const unsigned long long m = __ballot(mine);
+    if (m && __lane_id() == (uint32_t)__ffsll((long long)m) - 1u) atomicAdd(&acc[word], (unsigned long long)__popcll(m));
+}
+
+// ---- the uniform grid of the whole scene (sb_raycast.hip; csrc/sb_ray_walk.h states the cells' rule and what is recorded where),
+// shared by the ray casts and the proximity queries: the grid of a call, and the counting sort of particles, short beams and the
+// leftover list into it -- memsets, k_ray_bin, sbq_scan, k_ray_bin -- enqueued on the engine's stream.
+namespace srw {
+struct Grid;
+struct Rec;
+}
+struct SbwSortPlan {
+    uint64_t nbin, nb_scan, items; // words of the bins (G * G cells, the leftover list, one behind), blocks of their scan, records at most
+};
+srw::Grid sbw_grid(const sb_engine *e, uint32_t cells_per_side); // cells_per_side 0: the default rule
+SbwSortPlan sbw_sort_plan(const sb_engine *e, uint32_t G);
+// acc: the eight count words (k_ray_bin takes words 5 and 6) and whatever lies behind them, acc_bytes in all, cleared; d_cells [nbin]:
+// afterwards per bin the END of its records; bsum [nb_scan]; sorted [items]; a_of: per beam data index < cut_nd its endpoint A, or NULL;
+// *total: the number of records
+sb_status sbw_sort(sb_engine *e, const srw::Grid &g, unsigned long long *acc, size_t acc_bytes, uint32_t *d_cells, uint32_t *bsum, srw::Rec *sorted,
+                   uint32_t *a_of, uint32_t *total);
+std::vector<const void *> sbw_sort_kernels(); // what sbw_sort launches (the *_kernel_vgprs keys)

@@ -85,6 +85,18 @@ def ray_rows(origin, direction, tmax, mask=7, skip_label=None):
     return batch.ray_rows(origin[None], direction, tmax, mask=mask, skip_label=skip_label)[0]
 
 
+class SbNearestOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("cells_per_side", ctypes.c_uint32),
+                ("max_rings", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 4)]
+
+
+NEAREST_COUNT_WORDS = 8                               # SB_NEAREST_COUNT_WORDS
+NEAREST_MAX_POINTS = 1 << 24                          # rows of one call
+# the words of nearest()'s counts, in order (include/softbody.h, sb_nearest_device): four of the definition, three of the cost
+NEAREST_COUNT_FIELDS = ("valid", "particles", "beams", "walls", "swept_rows", "particles_outside_grid", "long_beams", "reserved_7")
+Nearest = collections.namedtuple("Nearest", ("d", "hit", "point", "within", "counts"))
+
+
 class SbBodiesOptions(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 7)]
 
@@ -309,6 +321,8 @@ def load_library():
     L.sb_graph.argtypes = [vp, ctypes.POINTER(SbGraphOptions), vp, vp, vp, vp]
     L.sb_raycast_device.argtypes = [vp, ctypes.POINTER(SbRaycastOptions), vp, u32, vp, vp, vp, vp]
     L.sb_raycast.argtypes = [vp, ctypes.POINTER(SbRaycastOptions), vp, u32, vp, vp, vp, vp]
+    L.sb_nearest_device.argtypes = [vp, ctypes.POINTER(SbNearestOptions), vp, u32, vp, vp, vp, vp, vp, vp]
+    L.sb_nearest.argtypes = [vp, ctypes.POINTER(SbNearestOptions), vp, u32, vp, vp, vp, vp, vp, vp]
     L.sb_bodies_device.argtypes = [vp, ctypes.POINTER(SbBodiesOptions), vp, vp, vp]
     L.sb_bodies.argtypes = [vp, ctypes.POINTER(SbBodiesOptions), vp, vp, vp]
     L.sb_contacts_device.argtypes = [vp, ctypes.POINTER(SbContactsOptions), vp, vp, vp, vp]
@@ -861,6 +875,93 @@ class Engine(DeviceBinding):
         self._check(load_library().sb_raycast(self._h, ctypes.byref(o), _ptr(rows) if n else None, n, None if lab is None else _ptr(lab), _ptr(t),
                                               _ptr(hit), _ptr(counts)))
         return RayCast(t, hit, counts)
+
+    # ---- proximity queries over the whole scene (sb_nearest_device / sb_nearest)
+
+    @staticmethod
+    def _nearest_options(cells_per_side, max_rings):
+        o = SbNearestOptions()
+        o.struct_size = ctypes.sizeof(SbNearestOptions)
+        o.cells_per_side, o.max_rings = int(cells_per_side), int(max_rings)
+        return o
+
+    def nearest(self, points, labels=None, d=None, hit=None, point=None, within=None, counts=None, cells_per_side=0, max_rings=0):
+        """"What is nearest to this point, how far is it, and how much is within reach?" asked of the whole scene, on the GPU:
+        BatchEngine.nearest()'s definition, bit for bit, on what load_buffers() would return now.  `points` is [n, 8], n <= 2^24, in
+        sb_batch_near_point's layout {mask, px, py, rmax, skip_label, 0, 0, 0}: an int32 or float32 (bits) torch tensor on the
+        engine's device, or a tuple (device pointer, n).  batch.point_rows() already packs such rows on the device: give it [1, n, 2]
+        points and take [0].  Returns a Nearest named tuple of tensors on the engine's device: d [n] float32; hit [n, 3] int32
+        (batch.NEAR_HIT_FIELDS: kind, particle / beam DATA index or WALL_* word, label); point [n, 2] float32, the closest point on
+        the winner; within [n, 2] int32, particles and beams within rmax; counts [8] int64 (NEAREST_COUNT_FIELDS: valid rows, winners
+        that are particles, beams and walls, then the cost words -- rows answered by the sweep over every primitive, particles
+        outside the grid, long beams).  labels: None, True (self.bodies() runs first, on the same stream), or an int32 tensor / device
+        pointer of [max_particles] labels of the caller's own, only compared.  d / hit / point / within / counts: None or True -- a
+        new tensor; False -- left out (None in its place; not all five); a device pointer (int) or a contiguous torch tensor to
+        write into.  Leaving `within` out lets a row stop at its winner: with rmax = inf it is the difference between a few cells
+        and a pass over the scene.  cells_per_side: 0 = the engine's rule (info("nearest_cells_per_side")); max_rings: 0 = the
+        default (info("nearest_max_rings")); the outputs depend on neither.  Only reads the engine, only enqueues; torch's current
+        stream is ordered after it.
+
+        Hover, then grab, without leaving the device:
+            rows = batch.point_rows(cursor[None], rmax=3 * radius, mask=batch.NEAR_PARTICLES)[0]    # cursor: [n, 2] on the device
+            near = eng.nearest(rows, within=False, counts=False)
+            st = eng.state_tensors()["particles"]                                                  # [max_particles, ...] at data indices
+            grabbed = near.hit[:, 0] == 1
+            st[near.hit[grabbed, 1].long(), :2] = cursor[grabbed]
+            eng.write_particles_device(st)"""
+        import torch
+        if isinstance(points, tuple):
+            rptr, n = int(points[0]), int(points[1])
+            is_tensor = False
+        else:
+            if not isinstance(points, torch.Tensor) or points.dtype not in (torch.int32, torch.float32) or points.dim() != 2 or points.shape[1] != 8:
+                raise ValueError("nearest: points must be an int32 / float32 torch tensor [n, 8] or (device pointer, n)")
+            n = int(points.shape[0])
+            rptr, is_tensor = self._device_buffer("nearest: points", points, None, n * 32)
+        if not 0 <= n <= NEAREST_MAX_POINTS:
+            raise ValueError("nearest: %d points, not in 0 .. 2^24" % n)
+        asked = (d, hit, point, within, counts)
+        wanted = [x is not False for x in asked]
+        if not any(wanted):
+            raise ValueError("nearest: d, hit, point, within and counts are all False: nothing to write")
+        given = [None if isinstance(x, bool) else x for x in asked]   # (None / True: a new tensor)
+        outs, ptrs, tensors = self._bind("nearest", [
+            ("d", given[0], wanted[0], (n,), "float32"),
+            ("hit", given[1], wanted[1], (n, 3), "int32"),
+            ("point", given[2], wanted[2], (n, 2), "float32"),
+            ("within", given[3], wanted[3], (n, 2), "int32"),
+            ("counts", given[4], wanted[4], (NEAREST_COUNT_WORDS,), "int64"),
+            ("labels", (lambda: self.bodies(counts=False)[0]) if labels is True else None if labels is False else labels,
+             labels is not None and labels is not False, (self.max_particles,), "int32")])
+        if n == 0:   # (the library enqueues nothing for no points: the counts of no points are zeros)
+            if isinstance(outs[4], torch.Tensor):
+                outs[4].zero_()
+            return Nearest(*outs[:5])
+        o = self._nearest_options(cells_per_side, max_rings)
+        vp = ctypes.c_void_p
+        self._ordered(tensors or is_tensor, lambda: load_library().sb_nearest_device(self._h, ctypes.byref(o), vp(rptr), n, vp(ptrs[5]), vp(ptrs[0]),
+                                                                                     vp(ptrs[1]), vp(ptrs[2]), vp(ptrs[3]), vp(ptrs[4])))
+        return Nearest(*outs[:5])
+
+    def nearest_host(self, points, labels=None, cells_per_side=0, max_rings=0):
+        """The same without torch: points a uint32 / int32 / float32 (bits) numpy array [n, 8], labels None or int32 [max_particles];
+        returns Nearest(d float32 [n], hit int32 [n, 3], point float32 [n, 2], within int32 [n, 2], counts int64 [8]) numpy arrays.
+        Waits for the stream."""
+        rows = np.ascontiguousarray(points)
+        if rows.dtype not in (np.dtype(np.uint32), np.dtype(np.int32), np.dtype(np.float32)) or rows.ndim != 2 or rows.shape[1] != 8:
+            raise ValueError("nearest_host: points must be a uint32 / int32 / float32 array [n, 8]")
+        n = rows.shape[0]
+        out = Nearest(np.zeros(n, dtype=np.float32), np.zeros((n, 3), dtype=np.int32), np.zeros((n, 2), dtype=np.float32),
+                      np.zeros((n, 2), dtype=np.int32), np.zeros(NEAREST_COUNT_WORDS, dtype=np.int64))
+        lab = None
+        if labels is not None:
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.size < self.max_particles:
+                raise ValueError("nearest_host: labels needs max_particles entries")
+        o = self._nearest_options(cells_per_side, max_rings)
+        self._check(load_library().sb_nearest(self._h, ctypes.byref(o), _ptr(rows) if n else None, n, None if lab is None else _ptr(lab),
+                                              *(_ptr(x) for x in out)))
+        return out
 
     # ---- particle and wall contacts of the whole scene (sb_contacts_device / sb_contacts; DESIGN.md 5.20)
 
