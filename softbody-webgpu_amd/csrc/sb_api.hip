@@ -527,7 +527,7 @@ static sb_status upload_blocked(sb_engine *e, const SbBlocking &bl, const SbHost
     for (int b = 0; b < 2; b++) SB_TRY(dev_alloc(e, &k.d_plastic[b], T));
     SB_TRY(blocked_state_to_device(e, k, hb));
     tm.mark("  beam state to device");
-    sbk_preload_blocked(k, hybrid); // (or the first launch of each kernel variant resolves it inside somebody's timed call)
+    sbk_preload_blocked(e, k, hybrid); // (or the first launch of each kernel variant resolves it inside somebody's timed call)
     tm.mark("  kernels resolved");
     if (hybrid) {
         // break flags of its own (merged into the tiled layout's on the way back), the maps between the two layouts, the
@@ -2031,6 +2031,10 @@ sb_status sb_get_info(sb_engine *e, const char *key, uint64_t *value)
     else if (k == "blocked_word_format") { // 0 wide, 1 narrow: the blocked plan's entry words inside the kernel (the hybrid's plan where that is the one)
         const SbBlockedDev &bk = e->bk.K ? e->bk : e->hy;
         *value = bk.K ? sbk_word_format(bk) : 0;
+    }
+    else if (k == "blocked_addressing") { // 0 flat, 1 buffer: how the blocked kernel's load and store phases address the plan's arrays
+        const SbBlockedDev &bk = e->bk.K ? e->bk : e->hy;
+        *value = bk.K ? sbk_addressing(e, bk) : 0;
     }
     else if (sbs_info(e, key, value)) {} // sb_state_io.hip: "checkpoint_bytes", "checkpoints", "restores"
     else if (sbm_info(e, key, value)) {} // sb_summary.hip: "summary_partials", ...

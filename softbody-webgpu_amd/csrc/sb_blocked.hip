@@ -13,6 +13,7 @@
 // not along beams): SB_COLLIDE_GRID keeps the single-substep kernels of sb_kernels.hip.
 #include "sb_engine.h"
 #include "sb_blocked_word.h"
+#include "sb_blocked_addr.h"
 
 #include <type_traits>
 
@@ -35,6 +36,9 @@ struct SbBlockedPlan {
     const float *ent_length; // MAT == 1: rest length per entry
     const float *mat_tab;    // [nmat][SB_MAT_ROW]
     uint32_t ntiles, K, cap, nmat, dummy_word;
+    // byte lengths, for the descriptors of the buffer form (SbMem<true>): halo_idx; ent_state; ent_word and ent_length; each of
+    // the six particle arrays the launch reads and writes
+    uint32_t halo_bytes, state_idx_bytes, ent_bytes, part_bytes;
 };
 
 struct SbBlockedState {
@@ -50,6 +54,7 @@ struct SbBlockedState {
     // an unyielded tile again.
     const uint32_t *plastic_r;
     uint32_t *plastic_w;
+    uint32_t state_bytes, aux_bytes; // byte lengths: target_* and last_*; strain and stress (with their dump elements)
 };
 
 #define SB_BK_CAP (SB_BK_MAXP * SB_BK_T + 2u + 128u) // LDS records: a full region, the two dummy endpoints, 64 more dummy pairs
@@ -132,6 +137,68 @@ struct alignas(16) SbLdsRecords {
 // length, the first float of LDS material row `row32 / 32`
 SB_DEV float sbl_row_length(const float *mat, uint32_t row32) { return *(const float *)((const char *)mat + row32); }
 
+// The arrays of the load and store phases, in one of two forms behind the same few operations (sb_blocked_addr.h).  A slot's
+// place in an array is an `at`, made once per slot from (have, index) and shared by the arrays the slot indexes alike:
+//   SbMem<false>  flat: at = the element index, 0 for a lane that has nothing; a load reads element 0 and discards it, a store
+//                 sits in an exec-mask region.  64-bit address arithmetic per request.
+//   SbMem<true>   buffer: at = the 32-bit byte offset, SBA_OUT for a lane that has nothing; the descriptor (base and byte length
+//                 in four scalar registers, wave-uniform: kernel arguments only) has the hardware return 0 for such a load and
+//                 drop such a store.  No select of an index, no scale-and-add of an address, no exec-mask region.
+// Either way every request is unconditional and issued in program order (the slot classes above rest on that).
+static_assert(SBA_T == SB_BK_T && SBA_OWNP == SB_BK_OWNP && SBA_OWNB == SB_BK_OWNB, "sb_blocked_addr.h restates these");
+#define SB_BUF_SC1 16 /* aux of a buffer store: sc1, what an agent-scope store carries (sb_physics.h sb_store_wt) */
+template <typename T> struct SbBufOps;
+template <> struct SbBufOps<uint32_t> {
+    SB_DEV static uint32_t ld(__amdgpu_buffer_rsrc_t r, uint32_t o) { return __builtin_amdgcn_raw_buffer_load_b32(r, (int)o, 0, 0); }
+    template <int AUX> SB_DEV static void st(__amdgpu_buffer_rsrc_t r, uint32_t o, uint32_t v) { __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)o, 0, AUX); }
+};
+template <> struct SbBufOps<float> {
+    SB_DEV static float ld(__amdgpu_buffer_rsrc_t r, uint32_t o) { return __uint_as_float(SbBufOps<uint32_t>::ld(r, o)); }
+    template <int AUX> SB_DEV static void st(__amdgpu_buffer_rsrc_t r, uint32_t o, float v) { SbBufOps<uint32_t>::st<AUX>(r, o, __float_as_uint(v)); }
+};
+template <> struct SbBufOps<float2> {
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    SB_DEV static float2 ld(__amdgpu_buffer_rsrc_t r, uint32_t o)
+    {
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)o, 0, 0);
+        return make_float2(__uint_as_float(v.x), __uint_as_float(v.y));
+    }
+    template <int AUX> SB_DEV static void st(__amdgpu_buffer_rsrc_t r, uint32_t o, float2 v)
+    {
+        u32x2 d;
+        d.x = __float_as_uint(v.x);
+        d.y = __float_as_uint(v.y);
+        __builtin_amdgcn_raw_buffer_store_b64(d, r, (int)o, 0, AUX);
+    }
+};
+template <bool BUF> struct SbMem;
+template <> struct SbMem<false> {
+    template <uint32_t SIZE> SB_DEV static uint32_t at(bool have, uint32_t idx) { return have ? idx : 0u; }
+    template <typename T> struct Arr {
+        T *p;
+        SB_DEV Arr(const T *ptr, uint32_t) : p(const_cast<T *>(ptr)) {}
+        SB_DEV T ld(uint32_t a) const { return p[a]; }
+        SB_DEV void st(bool have, uint32_t idx, T v) const // plain store
+        {
+            if (have) p[idx] = v;
+        }
+        SB_DEV void st_wt(bool have, uint32_t idx, T v) const // write-through store (sb_physics.h)
+        {
+            if (have) sb_store_wt(&p[idx], v);
+        }
+    };
+};
+template <> struct SbMem<true> {
+    template <uint32_t SIZE> SB_DEV static uint32_t at(bool have, uint32_t idx) { return sba::off(have, idx, SIZE); }
+    template <typename T> struct Arr {
+        __amdgpu_buffer_rsrc_t r;
+        SB_DEV Arr(const T *ptr, uint32_t bytes) : r(__builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(ptr), 0, (int)bytes, 0x00020000)) {}
+        SB_DEV T ld(uint32_t a) const { return SbBufOps<T>::ld(r, a); }
+        SB_DEV void st(bool have, uint32_t idx, T v) const { SbBufOps<T>::template st<0>(r, sba::off(have, idx, (uint32_t)sizeof(T)), v); }
+        SB_DEV void st_wt(bool have, uint32_t idx, T v) const { SbBufOps<T>::template st<SB_BUF_SC1>(r, sba::off(have, idx, (uint32_t)sizeof(T)), v); }
+    };
+};
+
 #ifndef SB_BK_WAVES_AUX
 #define SB_BK_WAVES_AUX SB_BK_WAVES
 #endif
@@ -158,7 +225,7 @@ struct SbTrack {
     uint32_t *broken_ok;
 };
 #define SB_HY_SLOTS 64u  // (slot 0's fourth word: the launch flagged a beam)
-template <int MAT, bool AUX, bool PLAIN, bool TRACK, bool NARROW>
+template <int MAT, bool AUX, bool PLAIN, bool TRACK, bool NARROW, bool BUF>
 __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? SB_BK_WAVES_AUX : SB_BK_WAVES, AUX ? SB_BK_WAVES_AUX : SB_BK_WAVES))) void k_substep_blocked(
     SbParticleArrays r, SbParticleArrays w, SbBlockedPlan bp, SbBlockedState bs, uint32_t k_run, const SbConsts c, SbParams prm,
     const uint32_t *__restrict__ acc_flag_r, uint32_t *acc_flag_w, SbTrack tr)
@@ -293,45 +360,58 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
     // list index (inside the tile) of entry slot i: own slots count from 0, halo slots from the tile's own beams
 #define SB_ENT_J(i) ((i) < (int)SB_BK_OWNB ? SB_ENT_L(tid, (i)) : n_ownb + SB_ENT_L(tid, (i) - (int)SB_BK_OWNB))
     const uint32_t nh_load = np_load - n_own, nh_move = np_move - n_own, nhe = ne_load - min(n_ownb, ne_load);
+    // the arrays of the two phases (SbMem): a descriptor each in the buffer form, the pointer itself in the flat one
+    using Mem = SbMem<BUF>;
+    const typename Mem::template Arr<uint32_t> m_halo_idx(bp.halo_idx, bp.halo_bytes), m_ent_state(bp.ent_state, bp.state_idx_bytes),
+        m_ent_word(bp.ent_word, bp.ent_bytes);
+    const typename Mem::template Arr<float> m_ent_length(bp.ent_length, MAT == 1 ? bp.ent_bytes : 0u), m_target_r(bs.target_r, bs.state_bytes),
+        m_last_r(bs.last_r, bs.state_bytes), m_target_w(bs.target_w, bs.state_bytes), m_last_w(bs.last_w, bs.state_bytes),
+        m_strain(bs.strain, bs.aux_bytes), m_stress(bs.stress, bs.aux_bytes);
+    const typename Mem::template Arr<float2> m_pos_r(r.pos, bp.part_bytes), m_vel_r(r.vel, bp.part_bytes), m_pos_w(w.pos, bp.part_bytes),
+        m_vel_w(w.vel, bp.part_bytes);
     uint32_t hidx[SB_BK_HALOP], sidx[SB_BK_HALOB];
 #pragma unroll
     for (int i = 0; i < SB_BK_HALOP; i++) {
-        const uint32_t h = tid + (uint32_t)i * SB_BK_T;
-        hidx[i] = bp.halo_idx[h < nh_load ? h0 + h : 0u];
+        const sba::Slot sl = sba::halo_index(tid, (uint32_t)i, h0, nh_load);
+        hidx[i] = m_halo_idx.ld(Mem::template at<4>(sl.have, sl.idx));
     }
 #pragma unroll
     for (int i = 0; i < SB_BK_HALOB; i++) {
-        const uint32_t j = SB_ENT_L(tid, i);
-        sidx[i] = bp.ent_state[j < nhe ? s0 + j : 0u];
+        const sba::Slot sl = sba::halo_state(tid, (uint32_t)i, s0, nhe);
+        sidx[i] = m_ent_state.ld(Mem::template at<4>(sl.have, sl.idx));
     }
     float2 pp[SB_BK_MAXP], pv[SB_BK_MAXP], pa[SB_BK_MAXP];
 #pragma unroll
     for (int i = 0; i < SB_BK_OWNP; i++) {
-        const uint32_t q = tid + (uint32_t)i * SB_BK_T;
-        pp[i] = r.pos[q < n_own ? p0 + q : 0u];
-        pv[i] = r.vel[q < n_own ? p0 + q : 0u];
+        const sba::Slot sl = sba::own_particle(tid, (uint32_t)i, p0, n_own);
+        const uint32_t at = Mem::template at<8>(sl.have, sl.idx);
+        pp[i] = m_pos_r.ld(at);
+        pv[i] = m_vel_r.ld(at);
         pa[i] = make_float2(0.f, 0.f);
     }
     float tg[SB_BK_MAXB], ls[SB_BK_MAXB], ln[SB_BK_MAXB];
 #pragma unroll
     for (int i = 0; i < SB_BK_OWNB; i++) {
-        const uint32_t j = SB_ENT_L(tid, i);
-        ls[i] = bs.last_r[j < n_ownb ? b0 + j : 0u];
+        const sba::Slot sl = sba::own_beam(tid, (uint32_t)i, b0, n_ownb);
+        ls[i] = m_last_r.ld(Mem::template at<4>(sl.have, sl.idx));
     }
+    // (a slot's `have`: formed here, once, for the fix-ups behind the loads and the rest-length targets behind the barrier)
     uint32_t word[SB_BK_MAXB];
+    bool have_e[SB_BK_MAXB];
 #pragma unroll
     for (int i = 0; i < SB_BK_MAXB; i++) {
-        const uint32_t j = SB_ENT_J(i);
-        const bool have = i < (int)SB_BK_OWNB ? j < n_ownb : j < ne_load;
-        word[i] = bp.ent_word[have ? e0 + j : 0u];
-        ln[i] = MAT == 1 ? bp.ent_length[have ? e0 + j : 0u] : 1.0f;
+        const sba::Slot sl = sba::entry(tid, (uint32_t)i, e0, n_ownb, nhe);
+        const uint32_t at = Mem::template at<4>(sl.have, sl.idx);
+        have_e[i] = sl.have;
+        word[i] = m_ent_word.ld(at);
+        ln[i] = MAT == 1 ? m_ent_length.ld(at) : 1.0f;
     }
-    // own targets: only a tile that has yielded fetches them (the others all read element 0: one cache line); last of this
-    // round, because the address waits for the tile's flag
+    // own targets: only a tile that has yielded fetches them (flat: the others all read element 0, one cache line; buffer: they
+    // are out of range); last of this round, because the address waits for the tile's flag
 #pragma unroll
     for (int i = 0; i < SB_BK_OWNB; i++) {
-        const uint32_t j = SB_ENT_L(tid, i);
-        tg[i] = bs.target_r[(own_plastic && j < n_ownb) ? b0 + j : 0u];
+        const sba::Slot sl = sba::own_beam(tid, (uint32_t)i, b0, n_ownb);
+        tg[i] = m_target_r.ld(Mem::template at<4>(own_plastic && sl.have, sl.idx));
     }
     // MAT == 1 (rest lengths that do not fit the dictionary: every scene built the way the reference's editor builds beams):
     // the rest length of every entry is staged in LDS behind the material rows and read per evaluation; its reciprocal is
@@ -341,24 +421,21 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
 #pragma unroll
     for (int i = 0; i < SB_BK_HALOP; i++) {
         const uint32_t h = tid + (uint32_t)i * SB_BK_T;
-        const uint32_t at = h < nh_load ? hidx[i] : 0u;
-        pp[SB_BK_OWNP + i] = r.pos[at];
-        pv[SB_BK_OWNP + i] = r.vel[h < nh_move ? at : 0u];
+        pp[SB_BK_OWNP + i] = m_pos_r.ld(Mem::template at<8>(h < nh_load, hidx[i]));
+        pv[SB_BK_OWNP + i] = m_vel_r.ld(Mem::template at<8>(h < nh_move, hidx[i])); // (nh_move <= nh_load)
         pa[SB_BK_OWNP + i] = make_float2(0.f, 0.f);
     }
 #pragma unroll
     for (int i = 0; i < SB_BK_HALOB; i++) {
-        const uint32_t j = SB_ENT_L(tid, i);
-        const uint32_t at = j < nhe ? sidx[i] : 0u;
-        tg[SB_BK_OWNB + i] = bs.target_r[nb_plastic ? at : 0u]; // (no tile around has yielded: nothing to gather)
-        ls[SB_BK_OWNB + i] = bs.last_r[at];
+        const bool have = have_e[SB_BK_OWNB + i];
+        tg[SB_BK_OWNB + i] = m_target_r.ld(Mem::template at<4>(nb_plastic && have, sidx[i])); // (no tile around has yielded: nothing to gather)
+        ls[SB_BK_OWNB + i] = m_last_r.ld(Mem::template at<4>(have, sidx[i]));
     }
     // (what the lanes with nothing to fetch hold instead: a unit beam between this lane's own pair of dummy records)
     const uint32_t pad_word = (SB_BK_PAD0 + 2u * (tid & 63u)) | ((SB_BK_PAD0 + 2u * (tid & 63u) + 1u) << SB_BK_LBITS);
 #pragma unroll
     for (int i = 0; i < SB_BK_MAXB; i++) {
-        const uint32_t j = SB_ENT_J(i);
-        const bool have = i < (int)SB_BK_OWNB ? j < n_ownb : j < ne_load;
+        const bool have = have_e[i];
         word[i] = sbw::held<NARROW>(have ? word[i] : pad_word);
         tg[i] = have ? tg[i] : 1.0f;
         ls[i] = have ? ls[i] : 1.0f;
@@ -432,9 +509,7 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
 #pragma unroll
         for (int i = 0; i < SB_BK_MAXB; i++) {
             const bool own = i < (int)SB_BK_OWNB;
-            const uint32_t j = SB_ENT_J(i);
-            const bool have = own ? j < n_ownb : j < ne_load;
-            if (have && !(own ? own_plastic : nb_plastic))
+            if (have_e[i] && !(own ? own_plastic : nb_plastic))
                 tg[i] = MAT == 2 ? sbl_row_length(s_mat, sbw::row32<NARROW>(word[i])) : s_len[tid + (uint32_t)i * SB_BK_T];
         }
     }
@@ -469,7 +544,9 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
                 asm volatile("" : "+v"(j)); // (or the store addresses of a thread are hoisted out of the substep loop: 48 VGPRs)
                 uint32_t wd = word[i];
                 asm volatile("" : "+v"(wd));
-                const uint32_t at = (j < n_ownb && wd != dummy_held) ? b0 + j : dump;
+                // (flat: the dump element; buffer: out of range, the store is dropped -- the descriptor covers the dump elements all the same)
+                const bool live = j < n_ownb && wd != dummy_held;
+                const uint32_t at = BUF ? b0 + j : (live ? b0 + j : dump);
                 const float4 *row = (const float4 *)((const char *)s_mat + sbw::row32<NARROW>(wd));
                 const float2 qa = s_lds.pos(Lds::end_a(wd)), qb = s_lds.pos(Lds::end_b(wd));
                 const float4 r0 = row[0]; // length, 1/length, spring', damp' (times the force scale: the scaling is exact)
@@ -482,8 +559,8 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
                 const float len = sb_beam_length(qa, qb);
                 const float force_mag = (tg[i] - len) * (r0.z * 0x1p-16f) + (ls[i] - len) * (r0.w * 0x1p-16f); // :110
                 const float strain_v = (len - tg[i]) * inv_length;                                           // :112
-                bs.stress[at] = force_mag * (1.0f / 20.0f);                                                  // :122
-                bs.strain[at] = sb_div(sb_abs(strain_v), yield_strain);                                      // :123
+                m_stress.st(BUF ? live : true, at, force_mag * (1.0f / 20.0f));                              // :122
+                m_strain.st(BUF ? live : true, at, sb_div(sb_abs(strain_v), yield_strain));                  // :123
                 asm volatile("" ::: "memory"); // one slot at a time: six interleaved evaluations do not fit beside the substep loop's registers
             }
         }
@@ -621,7 +698,15 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
 #pragma unroll
     for (int i = 0; i < SB_BK_OWNP; i++) {
         const uint32_t q = tid_s + (uint32_t)i * SB_BK_T;
-        if (q < n_own) {
+        if (BUF) {
+            // range-checked: a lane past the tile's own particles stores nowhere (its LDS record is somebody's halo, or stale)
+            const bool have = q < n_own;
+            m_pos_w.st_wt(have, p0 + q, s_lds.pos(Lds::rec(q)));
+            m_vel_w.st_wt(have, p0 + q, pv[i]);
+            const bool nz = have && (__float_as_uint(pa[i].x) | __float_as_uint(pa[i].y)) != 0u;
+            any_acc |= nz;
+            if (nz || (have && acc_w_dirty)) w.acc[p0 + q] = pa[i]; // (rare: flat)
+        } else if (q < n_own) {
             sb_store_wt(&w.pos[p0 + q], s_lds.pos(Lds::rec(q))); // (write-through: sb_physics.h; config 2 at 1 M: 8.15 -> 8.32e10)
             sb_store_wt(&w.vel[p0 + q], pv[i]);
             const bool nz = (__float_as_uint(pa[i].x) | __float_as_uint(pa[i].y)) != 0u; // -0.0 counts
@@ -644,7 +729,23 @@ __global__ __launch_bounds__(SB_BK_T) __attribute__((amdgpu_waves_per_eu(AUX ? S
 #pragma unroll
     for (int i = 0; i < SB_BK_OWNB; i++) {
         const uint32_t j = SB_ENT_L(tid_s, i);
-        if (j < n_ownb) {
+        if (BUF) {
+            // range-checked: padding slots and dead beams store nowhere; the two rare cases behind keep their branches
+            const bool own = j < n_ownb, live = own && word[i] != dummy_held;
+            m_target_w.st_wt(live && plastic_w, b0 + j, tg[i]);
+            m_last_w.st_wt(live, b0 + j, ls[i]);
+            if (__builtin_expect(live && ((brk >> i) & 1u), 0)) {
+                atomicOr(&bs.broken[(b0 + j) >> 5], 1u << ((b0 + j) & 31u));
+                if (TRACK) __hip_atomic_store((uint32_t *)&tr.slots_out[0].w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if (__builtin_expect(own && !live, 0)) { // (a beam removed by a delete pass: below)
+                float keep_t = bs.target_r[b0 + j], keep_l = bs.last_r[b0 + j];
+                SB_LANDED(keep_t);
+                SB_LANDED(keep_l);
+                bs.target_w[b0 + j] = keep_t;
+                bs.last_w[b0 + j] = keep_l;
+            }
+        } else if (j < n_ownb) {
             if (__builtin_expect(word[i] != dummy_held, 1)) {
                 if (plastic_w) sb_store_wt(&bs.target_w[b0 + j], tg[i]);
                 sb_store_wt(&bs.last_w[b0 + j], ls[i]);
@@ -864,6 +965,28 @@ uint32_t sbk_split_call(uint32_t n, uint32_t kmax, bool fewest, uint32_t *first,
     return best_L;
 }
 
+// SB_BK_BUFFER: 1 builds the buffer form of the load and store phases (SbMem<true>) and runs it wherever the plan allows.  The
+// library ships 0, flat: measured against the parent the buffer form executes 3.2 % fewer VALU instructions and its launches are
+// 1.1 % shorter, but the default line did not clear the parent's own spread (profiles/blocked_addressing_before_after.json),
+// and what is not built is not instantiated.
+#ifndef SB_BK_BUFFER
+#define SB_BK_BUFFER 0
+#endif
+// how the load and store phases address this plan's arrays: 1 = range-checked buffer instructions (SbMem<true>), 0 = flat.  The
+// buffer form wants every array it makes a descriptor for below 4 GiB (sb_blocked_addr.h sba::fits): 32-bit byte offsets.
+// One variant keeps the flat form whatever the plan: <2, true, false, true, *> (mode 2, strain / stress, the general particle
+// phase, tracked) spills a register in the buffer form where it spills none flat (profiles/blocked_kernel_resources.txt), and its
+// buffer form is not instantiated.
+constexpr bool sbk_variant_buffer(int mat, bool aux, bool plain, bool track) { return !(mat == 2 && aux && !plain && track); }
+uint32_t sbk_addressing(const sb_engine *e, const SbBlockedDev &bk)
+{
+    const uint64_t bytes[] = {bk.halo_particles * 4u, bk.halo_entries * 4u, bk.entries * 4u, (uint64_t)e->P * sizeof(float2),
+                              ((uint64_t)bk.nbeams + SB_BK_T) * 4u};
+    bool fits = SB_BK_BUFFER != 0;
+    for (uint64_t b : bytes) fits = fits && sba::fits(b);
+    return fits ? 1u : 0u;
+}
+
 // SB_BK_NARROW (diagnostic builds: 0 keeps every scene on wide words, to measure the narrow form against)
 #ifndef SB_BK_NARROW
 #define SB_BK_NARROW 1
@@ -881,7 +1004,9 @@ static void allow_large_lds(int device)
     if (device < 0 || device >= 64 || done[device]) return;
     done[device] = true;
     const int bytes = 100 * 1024;
-#define SB_ALLOW(A, PL, TR) (void)hipFuncSetAttribute((const void *)k_substep_blocked<1, A, PL, TR, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)
+#define SB_ALLOW(A, PL, TR)                                                                                                                      \
+    (void)hipFuncSetAttribute((const void *)k_substep_blocked<1, A, PL, TR, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), \
+        (void)(SB_BK_BUFFER ? hipFuncSetAttribute((const void *)k_substep_blocked<1, A, PL, TR, false, SB_BK_BUFFER != 0>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) : hipSuccess)
     SB_ALLOW(false, false, false); SB_ALLOW(false, true, false); SB_ALLOW(true, false, false); SB_ALLOW(true, true, false);
     SB_ALLOW(false, false, true); SB_ALLOW(false, true, true); SB_ALLOW(true, false, true); SB_ALLOW(true, true, true);
 #undef SB_ALLOW
@@ -892,11 +1017,16 @@ static void allow_large_lds(int device)
 // its tiled layout); flips the particle and beam-state buffers
 static void launch_one(sb_engine *e, SbBlockedDev &bk, uint32_t k, bool aux, bool track)
 {
+    // (the byte lengths: what upload_blocked and upload_particles allocated, sb_api.hip; the buffer form reads them only, and only
+    // when every one of them fits a descriptor -- sbk_addressing -- so the casts lose nothing it uses)
+    const bool buf = sbk_addressing(e, bk) != 0u;
     SbBlockedPlan bp{bk.d_tile_p0, bk.d_tile_h0, bk.d_halo_idx, bk.d_ring_cnt, bk.d_tile_b0, bk.d_tile_e0, bk.d_tile_s0, bk.d_ent_word,
                      bk.d_ent_state, bk.d_lvl_cnt, bk.d_tile_n0, bk.d_tile_nb, bk.d_ent_length, bk.d_mat, bk.ntiles, bk.plan_K, bk.cap,
-                     bk.nmat, bk.dummy_word};
+                     bk.nmat, bk.dummy_word, (uint32_t)(bk.halo_particles * 4u), (uint32_t)(bk.halo_entries * 4u), (uint32_t)(bk.entries * 4u),
+                     (uint32_t)((uint64_t)e->P * sizeof(float2))};
     SbBlockedState bs{bk.d_target[bk.cur], bk.d_last[bk.cur], bk.d_target[bk.cur ^ 1u], bk.d_last[bk.cur ^ 1u], bk.d_strain, bk.d_stress,
-                      bk.d_broken, bk.d_plastic[bk.cur], bk.d_plastic[bk.cur ^ 1u]};
+                      bk.d_broken, bk.d_plastic[bk.cur], bk.d_plastic[bk.cur ^ 1u], (uint32_t)((uint64_t)bk.nbeams * 4u),
+                      (uint32_t)(((uint64_t)bk.nbeams + SB_BK_T) * 4u)};
     SbParticleArrays r = e->part[e->cur], w = e->part[e->cur ^ 1];
     SbTrack tr{};
     if (track) { // (launch number bk.seq: its slots, the block it reads and the one it writes, its own mask of break flags)
@@ -916,9 +1046,19 @@ static void launch_one(sb_engine *e, SbBlockedDev &bk, uint32_t k, bool aux, boo
         bk.run_launches++;
         bk.k_prev = k;
     }
-#define SB_LAUNCH_B(M, A, PL, TR, NW)                                                                                         \
-    k_substep_blocked<M, A, PL, TR, NW><<<bk.ntiles, SB_BK_T, NW ? 0 : bk.lds_bytes, e->stream>>>(r, w, bp, bs, k, e->consts, e->prm,     \
+#define SB_LAUNCH_BF(M, A, PL, TR, NW, BF)                                                                                    \
+    k_substep_blocked<M, A, PL, TR, NW, BF><<<bk.ntiles, SB_BK_T, NW ? 0 : bk.lds_bytes, e->stream>>>(r, w, bp, bs, k, e->consts, e->prm, \
                                                                                         e->d_acc_flag[e->cur], e->d_acc_flag[e->cur ^ 1], tr)
+#define SB_LAUNCH_B(M, A, PL, TR, NW)                                 \
+    do {                                                              \
+        if constexpr (SB_BK_BUFFER != 0 && sbk_variant_buffer(M, A, PL, TR)) {             \
+            if (buf) {                                                \
+                SB_LAUNCH_BF(M, A, PL, TR, NW, true);                 \
+                break;                                                \
+            }                                                         \
+        }                                                             \
+        SB_LAUNCH_BF(M, A, PL, TR, NW, false);                        \
+    } while (0)
 #define SB_LAUNCH_BT(M, A, PL, NW) do { if (track) SB_LAUNCH_B(M, A, PL, true, NW); else SB_LAUNCH_B(M, A, PL, false, NW); } while (0)
 #define SB_LAUNCH_BA(M, PL, NW) do { if (aux) SB_LAUNCH_BT(M, true, PL, NW); else SB_LAUNCH_BT(M, false, PL, NW); } while (0)
     // the constants of THIS launch (they ride in its kernarg): the reference's defaults take the plain particle phase
@@ -935,6 +1075,7 @@ static void launch_one(sb_engine *e, SbBlockedDev &bk, uint32_t k, bool aux, boo
 #undef SB_LAUNCH_BA
 #undef SB_LAUNCH_BT
 #undef SB_LAUNCH_B
+#undef SB_LAUNCH_BF
     e->cur ^= 1;
     bk.cur ^= 1u;
     e->substeps_done += k;
@@ -944,10 +1085,20 @@ static void launch_one(sb_engine *e, SbBlockedDev &bk, uint32_t k, bool aux, boo
 // the strain / stress variant and runs the lean one before it, so a short first call -- the five warm-up substeps of the bench
 // protocol are ONE launch -- leaves the lean variant to be resolved inside the next, timed, call.  Called at upload for the
 // plan's material mode: every variant a call may launch.
-void sbk_preload_blocked(const SbBlockedDev &bk, bool tracked)
+void sbk_preload_blocked(const sb_engine *e, const SbBlockedDev &bk, bool tracked)
 {
     hipFuncAttributes a;
-#define SB_TOUCH(M, A, PL, TR, NW) (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_substep_blocked<M, A, PL, TR, NW>))
+    const bool buf = sbk_addressing(e, bk) != 0u;
+#define SB_TOUCH(M, A, PL, TR, NW)                                                                                             \
+    do {                                                                                                                       \
+        if constexpr (SB_BK_BUFFER != 0 && sbk_variant_buffer(M, A, PL, TR)) {                                                                      \
+            if (buf) {                                                                                                         \
+                (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_substep_blocked<M, A, PL, TR, NW, true>));     \
+                break;                                                                                                         \
+            }                                                                                                                  \
+        }                                                                                                                      \
+        (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_substep_blocked<M, A, PL, TR, NW, false>));            \
+    } while (0)
 #define SB_TOUCH_M(M, NW)                                  \
     do {                                                   \
         if (tracked) {                                     \

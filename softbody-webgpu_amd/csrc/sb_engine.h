@@ -299,8 +299,9 @@ void sbk_launch_peer_exchange(sb_engine *e);
 void sbk_launch_halo_guard(sb_engine *e, bool init); // init: record x only (sb_halo_guard)
 // sb_blocked.hip
 void sbk_launch_blocked(sb_engine *e, uint32_t n, bool write_aux);
+uint32_t sbk_addressing(const sb_engine *e, const SbBlockedDev &bk); // 0 flat, 1 buffer: how k_substep_blocked's load and store phases address this plan's arrays (sb_blocked_addr.h)
 uint32_t sbk_word_format(const SbBlockedDev &bk); // 0 wide, 1 narrow: how k_substep_blocked holds this plan's entry words (sb_blocked_word.h)
-void sbk_preload_blocked(const SbBlockedDev &bk, bool tracked); // resolve every kernel variant a call on this plan may launch (upload time)
+void sbk_preload_blocked(const sb_engine *e, const SbBlockedDev &bk, bool tracked); // resolve every kernel variant a call on this plan may launch (upload time)
 uint32_t sbk_split_call(uint32_t n, uint32_t kmax, bool fewest, uint32_t *first, uint32_t *n_first); // launches: n_first of depth first, the rest first - 1
 void sbk_launch_delete_blocked(sb_engine *e);
 void sbk_hybrid_to_blocked(sb_engine *e);

@@ -1,4 +1,5 @@
-"""Static instruction account of k_substep_blocked's substep loop, phase by phase, from hipcc's assembly.
+"""Static instruction account of k_substep_blocked, phase by phase, from hipcc's assembly: the substep loop (beam phase, particle
+phase) and what runs once per launch around it (prologue, the two rounds of requests, fix-ups and LDS fill, store phase).
 
 A scratch copy of sb_blocked.hip gets empty `asm volatile` comment markers around the beam phase (and in front of every entry
 group) and around the particle phase (and in front of every particle slot); it is compiled for gfx950 with the library's flags
@@ -7,10 +8,18 @@ The counts are STATIC: both sides of a branch count where the compiler laid them
 instruction across a marker (a comment is no barrier), so a slot's figure is good to a few instructions; the phase totals,
 which end at barriers, are exact.  Nothing in the tree is changed.
 
-Usage: python tools/phase_isa.py [--variant "2, false, true, false, true"] [--keep file.s] [--dump-slot N]"""
+The once-per-launch regions are cut where the source's phases begin; `fixup_fill` ends at the barrier in front of the loop, and what
+lies between that barrier and the loop's first marker (rest-length targets, the first prefixes) is `loop_head`.
+--root names another checkout of the repository to account (the parent commit's, to set two tables side by side): the anchors are
+text both have.  The default variant is the headline's, with the addressing argument where the source has one: flat, or the buffer
+form under EXTRA=-DSB_BK_BUFFER=1 (the library instantiates it only then).
+
+Usage: python tools/phase_isa.py [--root DIR] [--variant "2, false, true, false, true, true"] [--keep file.s] [--dump-slot N]"""
 import argparse, collections, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--root" in sys.argv:
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--root") + 1])
 CSRC = os.path.join(ROOT, "softbody-webgpu_amd", "csrc")
 def library_flags():
     """HIPFLAGS of csrc/Makefile, the flags the library is built with (continuation lines joined, $(ARCH) filled in)."""
@@ -25,6 +34,12 @@ FLAGS = library_flags()
 MARK = 'asm volatile("; SBMARK %s");'
 # (anchor text in sb_blocked.hip, marker, before or after the anchor)
 ANCHORS = [
+    ("    float moved_sum = 0.0f; // TRACK", "prologue", "before"),
+    ("    const uint32_t nh_load = np_load - n_own, nh_move = np_move - n_own,", "request1", "before"),
+    ("    // (2) the gathers\n", "request2", "before"),
+    ("    // (what the lanes with nothing to fetch hold instead", "fixup_fill", "before"),
+    ("    // targets nobody fetched (tiles that have never yielded", "loop_head", "before"),
+    ("    uint32_t tid_s = tid;\n", "store", "before"),
     ("#pragma unroll\n        for (int i0 = 0; i0 < SB_BK_MAXB; i0 += SB_BK_G) {", "beam_begin", "before"),
     ("            const uint32_t j0 = SB_ENT_J(i0);\n", "beam_group", "before"),
     ("        if (!(SB_BK_ABLATE & 32)) __syncthreads();\n        // ---- particle phase", "beam_end", "before"),
@@ -95,6 +110,8 @@ def classify(l):
             k.append("vcmp")
     if op.startswith("ds_"):
         k.append("lds")
+    if op.startswith(("buffer_", "global_", "flat_", "scratch_")):
+        k.append("vmem")
     if op.startswith("s_waitcnt"):
         k.append("waitcnt")
     if op in ("s_cbranch_execz", "s_cbranch_execnz") or op.startswith(("s_and_saveexec", "s_or_saveexec", "s_xor_saveexec")):
@@ -123,17 +140,20 @@ def account(body):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--variant", default="2, false, true, false, true")
+    ap.add_argument("--root", help="another checkout of the repository (read at import)")
+    ap.add_argument("--variant", default="2, false, true, false, true" + ((", true" if "SB_BK_BUFFER=1" in os.environ.get("EXTRA", "") else ", false")
+                                                                        if "bool BUF" in open(os.path.join(CSRC, "sb_blocked.hip")).read() else ""))
     ap.add_argument("--keep")
     ap.add_argument("--dump-slot", type=int, default=-1, help="print the instructions of this particle slot")
     a = ap.parse_args()
     regions = account(kernel_body(compile_asm(a.keep), a.variant))
-    cols = ["all", "valu", "quarter", "vcmp", "lds", "waitcnt", "saveexec", "exec_branch", "uniform_branch", "salu"]
+    cols = ["all", "valu", "quarter", "vcmp", "lds", "vmem", "waitcnt", "saveexec", "exec_branch", "uniform_branch", "salu"]
+    ONCE = ("prologue", "request1", "request2", "fixup_fill", "loop_head", "store")
     print("k_substep_blocked<%s>: static instructions of one substep iteration, by marker region" % a.variant)
     print("%-18s" % "region" + "".join("%9s" % c[:8] for c in cols))
     tot = collections.defaultdict(collections.Counter)
     for r in regions:
-        if r["name"] in ("beam_end", "particle_end"):
+        if r["name"] in ("beam_end", "particle_end") or r["name"] in ONCE:
             continue  # (what follows these is the barrier and the loop's tail)
         c = collections.Counter(k for l in r["lines"] for k in classify(l))
         phase = "beam" if r["name"].startswith("beam") else "particle"
@@ -143,6 +163,16 @@ def main():
         print("%-18s" % (ph + " phase") + "".join("%9d" % tot[ph][k] for k in cols))
     v = tot["beam"]["valu"] + tot["particle"]["valu"]
     print("particle phase: %.1f %% of the loop's static VALU instructions (%d of %d)" % (100.0 * tot["particle"]["valu"] / v, tot["particle"]["valu"], v))
+    print()
+    print("k_substep_blocked<%s>: static instructions per thread that run once per launch, by marker region" % a.variant)
+    print("%-18s" % "region" + "".join("%9s" % c[:8] for c in cols))
+    once = collections.Counter()
+    for r in regions:
+        if r["name"] in ONCE:
+            c = collections.Counter(k for l in r["lines"] for k in classify(l))
+            once.update(c)
+            print("%-18s" % r["name"] + "".join("%9d" % c[k] for k in cols))
+    print("%-18s" % "once per launch" + "".join("%9d" % once[k] for k in cols))
     if a.dump_slot >= 0:
         for r in regions:
             if r["name"] == "particle_slot[%d]" % a.dump_slot:
