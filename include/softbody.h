@@ -773,7 +773,7 @@ sb_status sb_body_summary(sb_engine *e, const sb_body_summary_options *opts, con
  *   Limits: per scene at most SB_BATCH_MAX_PARTICLES particles and SB_BATCH_MAX_BEAMS beams (what one workgroup holds).
  *   When do calls return?  sb_batch_frame / _step / _delete_pass / _reset_device / _write_user_input[_device] /
  *     _set_physics_constants / _read_state_device / _write_particles_device / _fork_device / _checkpoint_device /
- *     _write_beams_device / _add_beams_device / _add_particles_device / _summary_device / _rollout_device / _bodies_device / _contacts_device / _graph_device / _raycast_device / _nearest_device only ENQUEUE on the batch's stream (device buffers must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
+ *     _write_beams_device / _add_beams_device / _add_particles_device / _summary_device / _rollout_device / _bodies_device / _contacts_device / _graph_device / _raycast_device / _nearest_device / _forces_device only ENQUEUE on the batch's stream (device buffers must stay valid until that work has run); sb_batch_write_scene, sb_batch_load_scene and sb_batch_sync WAIT for it.
  *     sb_batch_render_device only ENQUEUES (its device buffer must stay valid likewise); sb_batch_render_scene WAITS.
  *   Errors: every call returns an sb_status; sb_batch_last_error(b) gives the message (b == NULL: the last failed
  *     sb_batch_create of the calling thread).  Options are checked BEFORE a device is looked for. */
@@ -1356,6 +1356,65 @@ sb_status sb_batch_nearest_device(sb_batch *b, uint32_t flags,
         void *device_within_i32       /* [n_scenes][k][2] or NULL */,
         void *device_counts_i32       /* [n_scenes][SB_BATCH_NEAR_COUNT_WORDS] or NULL */);
 
+/* ---- beam and contact forces per particle of every scene, reported on the device, bit for bit ----
+ * sb_batch_forces_device -- how hard does every beam pull and every contact push?  For every scene, in ONE launch that only reads
+ * the batch and only enqueues, the forces the NEXT substep would compute from the CURRENT state.  Nothing is applied: no yield, no
+ * last_length update, no break flag, no particle moved.
+ *
+ * Let P be the scene's particle slots and Bc its live beam slots (metadata.particle_i_c / beam_i_c, clamped to the capacity; 0 in
+ * a scene never uploaded).  All float expressions are the step's: binary32, one rounding per operator (no contraction), IEEE sqrt
+ * and divide.
+ *
+ * Beam part.  It covers every beam slot j < Bc: exactly the set the frame kernel's beam phase evaluates.  A pending break flag
+ *   still counts.  A beam removed by a delete pass does not.  Each beam is evaluated as the step evaluates it (compute.wgsl:103-130)
+ *   from the current positions of its endpoints, its current {target_length, last_length} and its material row: diff = pb - pa,
+ *   len = length(diff) -- a beam of length zero takes diff = (0, -1e-10) and its length, the guard of :104-107 --
+ *   force_mag = (target_length - len) * spring + (last_length - len) * damp, n = diff * (1 / len), f = force_mag * n, and the four
+ *   i32 contributions ax = i32(-(f.x * 65536)), ay = i32(-(f.y * 65536)), bx = i32(f.x * 65536), by = i32(f.y * 65536).  The
+ *   conversion is v_cvt_i32_f32's: truncate toward zero, saturate at INT_MIN / INT_MAX, NaN -> 0.
+ *   Per particle these contributions are summed with wrapping 32-bit adds: beam_i32[s][i] = {sum x, sum y} at particle DATA index
+ *   i, the words the particle's integration would receive as fx, fy.  Being integers, they do not depend on summation order.
+ *   tension[s][d], float at beam DATA index d, is the beam's force_mag; 0 where no evaluated beam lives.  It is signed, with the
+ *   reference's sign: positive where the beam is shorter than its target and pushes its endpoints apart, negative where it is
+ *   stretched and pulls them together.
+ * Contact part.  For particle slot s, take the partners o != s in ASCENDING SLOT ORDER.  A partner satisfies dist == 0 ||
+ *   dist < 2r, with dx = xo - xs, dy = yo - ys, dist = sqrt(dx * dx + dy * dy), 2r = particle_radius * 2.0f: the contact test of
+ *   sb_batch_contacts_device; the batch's collision_mode does not matter.  Both sums start at +0 and accumulate exactly the terms
+ *   the step's collision loop (compute.wgsl:156-168) would subtract from the particle's acceleration and velocity:
+ *     push    -= (n * overlap * 0.5) * inv_dt2     n = (dx, dy) * (1 / dist), overlap = 2r - dist; where dt^2 = time_step^2 is no
+ *                                                  power of two the product with inv_dt2 is the division by dt^2
+ *     impulse -= impulse_normal * n + impulse_tangent * t
+ *                                                  t = (-n.y, n.x), u = v_s - v_o, impulse_normal = elasticity_coeff * dot(u, n),
+ *                                                  elasticity_coeff = (elasticity + 1) / 2, max_friction = impulse_normal *
+ *                                                  friction, impulse_tangent = clamp(dot(u, t), -max_friction, max_friction)
+ *   with the scene's current physics constants.  A dist == 0 partner counts as a partner with depth 2r and adds nothing to push
+ *   or impulse (the step only shifts p.y there).  depth is the largest 2r - dist over the partners, 0 with no partner.
+ *   With SB_BATCH_FORCES_OTHER_BODY and a labels tensor only partners whose label differs from s's are taken (labels: [n_scenes]
+ *   [max_particles] int32 at particle data indices, as sb_batch_bodies_device writes them; only compared with each other, never
+ *   used as an index).  Without the flag the labels are not looked at.
+ *   rows[s][i]    SB_BATCH_FORCE_WORDS floats at particle DATA index i: 0, 1 beam_x, beam_y = (float)beam_i32 * 2^-16 (the exact
+ *                 product of the particle's integration); 2, 3 push_x, push_y; 4, 5 impulse_x, impulse_y; 6 depth; 7 partners,
+ *                 the number of partners taken as an exact float.  A row where no particle lives is eight +0 words: data indices
+ *                 that hold no particle, scenes never uploaded, empty scenes.  (beam_i32 is {0, 0} there.)
+ *   counts[s]     SB_BATCH_FORCE_COUNT_WORDS int32: 0 particles P, 1 beam slots evaluated (Bc; 0 where P is 0), 2 particles with
+ *                 at least one partner taken, 3 beams whose force_mag is not finite.
+ * Every word of every output that is passed is written; any of them may be NULL (all of them: SB_OK, nothing is enqueued).  The
+ * call only ENQUEUES on the batch's stream and only READS the batch: frame, forces, frame equals frame, frame bit for bit; two
+ * calls give the same bits.
+ * Errors, before anything touches a device: SB_ERR_INVALID for a NULL handle, an unknown flag bit, SB_BATCH_FORCES_OTHER_BODY
+ * without labels, a pointer that is not 4-byte aligned.  sb_batch_get_info: "force_words", "force_count_words",
+ * "forces_kernel_vgprs", "forces_kernel_scratch_bytes", "forces_lds_bytes" (LDS of one workgroup at this batch's capacity),
+ * "forces_cells_per_side" (G of the G x G cells scenes of at least "grid_min_particles" particles are binned into; 0: none). */
+#define SB_BATCH_FORCE_WORDS 8u            /* floats of a per-particle row */
+#define SB_BATCH_FORCE_COUNT_WORDS 4u      /* words of a per-scene row */
+#define SB_BATCH_FORCES_OTHER_BODY 1u      /* only partners whose label differs from the particle's are taken */
+sb_status sb_batch_forces_device(sb_batch *b, uint32_t flags,
+        const void *device_labels_i32 /* [n_scenes][max_particles] as sb_batch_bodies_device writes them, or NULL */,
+        void *device_rows_f32         /* [n_scenes][max_particles][SB_BATCH_FORCE_WORDS] float or NULL */,
+        void *device_beam_i32         /* [n_scenes][max_particles][2] or NULL */,
+        void *device_tension_f32      /* [n_scenes][max_beams] float or NULL */,
+        void *device_counts_i32       /* [n_scenes][SB_BATCH_FORCE_COUNT_WORDS] or NULL */);
+
 /* ---- range sensors over the whole scene of ONE engine: ray casts on the device, bit for bit ----
  * sb_raycast_device / sb_raycast -- sb_batch_raycast_device's question asked of an sb_engine: n_rays rows of sb_batch_ray (the same
  * 32 bytes, masks and verdicts), for each the nearest hit among the scene's particles, live beams and walls.  The DEFINITION is the
@@ -1519,7 +1578,9 @@ sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream);
  * "graph_lds_bytes" (likewise); sb_batch_add_particles_device: "add_particles_kernel_vgprs",
  * "add_particles_kernel_scratch_bytes"; sb_batch_raycast_device: "ray_max", "ray_hit_words", "ray_count_words",
  * "raycast_lds_bytes" (likewise), "raycast_kernel_vgprs", "raycast_kernel_scratch_bytes"; sb_batch_nearest_device: "near_max",
- * "near_hit_words", "near_count_words", "nearest_lds_bytes" (likewise), "nearest_kernel_vgprs", "nearest_kernel_scratch_bytes" */
+ *  "near_hit_words", "near_count_words", "nearest_lds_bytes" (likewise), "nearest_kernel_vgprs", "nearest_kernel_scratch_bytes";
+ * sb_batch_forces_device: "force_words", "force_count_words", "forces_lds_bytes" (likewise), "forces_cells_per_side",
+ * "forces_kernel_vgprs", "forces_kernel_scratch_bytes" */
 sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value);
 const char *sb_batch_last_error(const sb_batch *b);
 

@@ -74,6 +74,13 @@ NEAR_WITHIN_FIELDS = ("particles", "beams")
 NEAR_COUNT_FIELDS = ("valid", "particles", "beams", "walls")
 # what nearest() returns; None where an output was not asked for
 Nearest = collections.namedtuple("Nearest", ("d", "hit", "point", "within", "counts"))
+FORCE_WORDS = 8                                       # SB_BATCH_FORCE_WORDS
+# the columns of a row of forces(), in order
+FORCE_FIELDS = ("beam_x", "beam_y", "push_x", "push_y", "impulse_x", "impulse_y", "depth", "partners")
+FORCE_COUNT_FIELDS = ("particles", "beams", "touching_particles", "nonfinite_beams")   # SB_BATCH_FORCE_COUNT_WORDS of them
+FORCES_OTHER_BODY = 1                                 # SB_BATCH_FORCES_OTHER_BODY
+# what forces() returns; None where an output was not asked for
+Forces = collections.namedtuple("Forces", ("rows", "beam_i32", "tension", "counts"))
 
 
 def new_beam_rows(pairs, spring, damp, yield_strain, strain_break_limit, length=None):
@@ -230,6 +237,7 @@ def load_library():
     L.sb_batch_graph_device.argtypes = [vp, u32, vp, vp, vp, vp, vp]
     L.sb_batch_raycast_device.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp]
     L.sb_batch_nearest_device.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp, vp, vp]
+    L.sb_batch_forces_device.argtypes = [vp, u32, vp, vp, vp, vp, vp]
     L.sb_batch_body_summary_device.argtypes = [vp, vp, u32, vp, vp]
     L.sb_batch_load_scene.argtypes = [vp, u32, vp, sz, vp, sz, vp, sz, vp, sz]
     L.sb_batch_render_device.argtypes = [vp, ctypes.POINTER(SbBatchRenderOptions), vp]
@@ -781,6 +789,50 @@ class BatchEngine(DeviceBinding):
         return self._query("nearest", "points", Nearest, points, labels, None,
                            [("d", d, (), "float32"), ("hit", hit, (NEAR_HIT_WORDS,), "int32"), ("point", point, (2,), "float32"),
                             ("within", within, (2,), "int32"), ("counts", counts, None, "int32")])
+
+    # ---- beam and contact forces per particle (sb_batch_forces_device)
+    def forces(self, labels=None, other_body=False, rows=True, beam_i32=None, tension=None, counts=None):
+        """How hard every beam pulls and every contact pushes, in every scene in one launch: the forces the NEXT substep would
+        compute from the CURRENT state, in the step's own arithmetic, bit for bit (include/softbody.h states the definition).
+        Nothing is applied: no yield, no last_length update, no break flag, no particle moved.  Returns a Forces named tuple of
+        tensors on the batch's device (None where not asked for):
+        rows [n_scenes, max_particles, 8] float32 at particle DATA indices (FORCE_FIELDS names the columns): beam_x, beam_y, the
+        sum of the beam forces on the particle (the fixed-point sum times 2^-16, what the integration adds to the acceleration);
+        push_x, push_y, what the contacts add to the acceleration; impulse_x, impulse_y, what they add to the velocity; depth, the
+        largest overlap 2r - dist among the partners; partners, their number.  Eight zeros where no particle lives.
+        beam_i32 [n_scenes, max_particles, 2] int32: the fixed-point beam force sums themselves (wrapping, saturating).
+        tension [n_scenes, max_beams] float32 at beam DATA indices: the beam's force_mag, the reference's sign: positive when the beam
+        is compressed and pushes its endpoints apart, negative when it is stretched and pulls; 0 where no live beam is.  A beam with a pending break flag still pulls.
+        counts [n_scenes, 4] int32 (FORCE_COUNT_FIELDS): particles, beams evaluated, particles with a partner, beams whose
+        tension is not finite.
+        labels: None, True (self.bodies() is called first, on the same stream, and its labels are used), or an int32 tensor /
+        device pointer of [n_scenes, max_particles] labels of the caller's own; with other_body=True only partners whose label
+        differs from the particle's are taken: what another body does to this one.  rows / beam_i32 / tension / counts: True (a
+        new tensor), None / False (not wanted), a device pointer (int) or a contiguous torch tensor to write into; every word of
+        what is asked for is written.  Only reads the batch, only enqueues; torch's current stream is ordered after it.
+        Grip force on body L, per scene -- the contacts' push on its particles from everybody else, summed:
+            f = be.forces(labels=True, other_body=True)
+            labels = be.bodies()[0]                                        # [n, max_particles], -1 where no particle lives
+            grip = torch.zeros(n, max_particles, 2, device=f.rows.device)
+            flat = (labels + max_particles * torch.arange(n, device=labels.device)[:, None]).clamp_min(0).view(-1)
+            grip.view(-1, 2).index_add_(0, flat.long(), f.rows[..., 2:4].reshape(-1, 2))   # (rows of no particle add zeros)
+            grip[s, L] is then the push on the body labelled L of scene s.
+        Muscle force -- the force the beams of a muscle carry, at the rows of state_tensors()'s beams:
+            tension = be.forces(rows=None, tension=True).tension           # [n, max_beams], row d == row d of state_tensors()[1]
+            muscle_force = tension[:, muscle_beam_indices]"""
+        n, maxp, maxb = self.n_scenes, self.max_particles, self.max_beams
+        wanted = [x is not False and x is not None for x in (rows, beam_i32, tension, counts)]
+        given = [None if isinstance(x, bool) else x for x in (rows, beam_i32, tension, counts)]   # (True: a new tensor)
+        outs, ptrs, tensors = self._bind("forces", [
+            ("rows", given[0], wanted[0], (n, maxp, FORCE_WORDS), "float32"),
+            ("beam_i32", given[1], wanted[1], (n, maxp, 2), "int32"),
+            ("tension", given[2], wanted[2], (n, maxb), "float32"),
+            ("counts", given[3], wanted[3], (n, len(FORCE_COUNT_FIELDS)), "int32"),
+            ("labels", (lambda: self.bodies()[0]) if labels is True else labels, labels is not None, (n, maxp), "int32")])
+        vp = ctypes.c_void_p
+        flags = FORCES_OTHER_BODY if other_body else 0
+        self._ordered(tensors, lambda: load_library().sb_batch_forces_device(self._h, flags, vp(ptrs[4]), *[vp(p) for p in ptrs[:4]]))
+        return Forces(*outs[:4])
 
     # ---- pictures (sb_batch_render_device / sb_batch_render_scene; DESIGN.md 5.11)
     def _render_options(self, resolution, bounds_size, particle_radius, first=0, count=0):

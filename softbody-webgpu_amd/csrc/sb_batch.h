@@ -3,7 +3,8 @@
 // sb_batch_bodies.hip: connected bodies; sb_batch_contacts.hip: particle and wall contacts; sb_batch_body_summary.hip: statistics per
 // body; sb_batch_cut.hip / sb_batch_add.hip / sb_batch_spawn.hip: cuts, welds and spawned particles, the latter two on
 // sb_batch_alloc.h, the allocator of their data indices; sb_batch_graph.hip: the beam graph; sb_batch_raycast.hip /
-// sb_batch_nearest.hip: range sensors and proximity queries, both on sb_batch_query.h, the plan of a query kernel), and what the
+// sb_batch_nearest.hip: range sensors and proximity queries, both on sb_batch_query.h, the plan of a query kernel;
+// sb_batch_forces.hip: the next substep's beam and contact forces), and what the
 // one-workgroup-per-scene kernels that only read a batch have in common: the scene header each of them opens with (sbb_scene), the
 // float <-> ordered-key codec of the reports' extremes and the width of their pinned summation tree (sb_summary_math.h), the
 // contact test (sb_touch); on the host the *_kernel_vgprs / *_kernel_scratch_bytes info keys (sbb_kernel_info), the alignment test
@@ -150,7 +151,7 @@ struct sb_batch {
     uint64_t frames_done = 0, substeps_done = 0;
     int scenes_per_cu = 0, vgprs = 0, scratch = 0;
     SbBatchRender *render = nullptr; // what the renderer keeps between calls (made at the first render)
-    SbbKernelRes render_res, summary_res, bodies_res, contacts_res, body_summary_res, cut_res, add_res, graph_res, spawn_res, raycast_res, nearest_res; // of k_batch_render, k_batch_summary, ...
+    SbbKernelRes render_res, summary_res, bodies_res, contacts_res, body_summary_res, cut_res, add_res, graph_res, spawn_res, raycast_res, nearest_res, forces_res; // of k_batch_render, k_batch_summary, ...
     bool body_summary_lds_allowed = false; // k_batch_body_summary may be launched with more than 64 KiB of LDS (asked for at the first such launch)
 };
 
@@ -223,3 +224,4 @@ bool sbb_spawn_info(sb_batch *b, const char *key, uint64_t *value); // sb_batch_
 bool sbb_graph_info(sb_batch *b, const char *key, uint64_t *value);
 bool sbb_raycast_info(sb_batch *b, const char *key, uint64_t *value);
 bool sbb_nearest_info(sb_batch *b, const char *key, uint64_t *value);
+bool sbb_forces_info(sb_batch *b, const char *key, uint64_t *value); // sb_batch_forces.hip
