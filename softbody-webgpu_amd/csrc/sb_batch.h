@@ -7,8 +7,8 @@
 // sb_batch_forces.hip: the next substep's beam and contact forces), and what the
 // one-workgroup-per-scene kernels that only read a batch have in common: the scene header each of them opens with (sbb_scene), the
 // float <-> ordered-key codec of the reports' extremes and the width of their pinned summation tree (sb_summary_math.h), the
-// contact test (sb_touch); on the host the *_kernel_vgprs / *_kernel_scratch_bytes info keys (sbb_kernel_info), the alignment test
-// of the entry points (sbb_misaligned4) and the opening checks of the editing and query calls (sbb_edit_entry).  All of it is
+// contact neighbourhood (sb_contact_cells.h, included here: the contact test, the cells' rule, window, selection and buckets); on
+// the host the *_kernel_vgprs / *_kernel_scratch_bytes info keys (sbb_kernel_info), the alignment test of the entry points (sbb_misaligned4) and the opening checks of the editing and query calls (sbb_edit_entry).  All of it is
 // inline; what only one kernel uses stays in that kernel's file.
 #pragma once
 #include <algorithm>
@@ -19,6 +19,7 @@
 #include "../../include/softbody.h"
 #include "sb_error.h"
 #include "sb_physics.h"
+#include "sb_contact_cells.h" // sb_touch, sb_batch_cell_geometry, SbCellWindow, sb_select_ascending, the sb_bucket_* of the LDS cells
 #include "sb_summary_math.h" // sbb_finite, sbb_fkey / sbb_unkey, SBB_QNAN, sbb_pow2_at_least: the codec of the report rows
 
 // ---------------------------------------------------------------- device memory of a batch
@@ -60,44 +61,8 @@ struct SbBatchView {
 #define SB_BATCH_NO_CONTACTS 0
 #define SB_BATCH_WALK 1  // the reference's loop over all slots
 #define SB_BATCH_CELLS 2 // the in-LDS cell grid, with the walk as its fallback
-#define SB_BATCH_CELL_K 4u // slot entries a cell holds
-// LDS behind cell_off: entries u16[G*G][SB_BATCH_CELL_K]; counts, two 16-bit counts to a word, u32[2][(G*G + 1) / 2] (one
-// buffer per substep parity); overflow words u32[2]
-static inline uint32_t sb_batch_cell_lds_bytes(uint32_t g) { return g * g * SB_BATCH_CELL_K * 2u + 2u * ((g * g + 1u) / 2u) * 4u + 8u; }
-
-// ---- contact cells: geometry, shared by sb_batch_create (the frame kernel's cells) and sb_batch_contacts_device
-// the most cells per side a capacity gets: the largest G with G^2 <= 2.5 * max_particles (17 at 128, 25 at 256, 50 at 1024)
-static inline uint32_t sb_batch_cell_cap(uint32_t maxP)
-{
-    uint32_t g = 1u;
-    while (2u * (g + 1u) * (g + 1u) <= 5u * maxP) g++;
-    return g;
-}
-// cells per side and their width for a radius and bounds: SbGrid's rule, cell >= 2r (1 + 1/64); G = clamp(floor(bounds / that),
-// 1, cap), the cells then as wide as G of them need to cover the bounds (never narrower than the rule: coarser is always right;
-// whatever lies past the last cell is clamped into it).  0: the width is not an ordinary number (the batch walks,
-// sb_batch_contacts_device tests all pairs).
-static inline uint32_t sb_batch_cell_geometry(float bounds, float radius, uint32_t cap, float *cell)
-{
-    const float two_r = radius * 2.0f, cell_min = two_r * (1.0f + 1.0f / 64.0f);
-    if (!(cell_min >= 0x1p-60f && cell_min <= 0x1p60f) || !(bounds >= 0x1p-60f && bounds <= 0x1p60f)) return 0u;
-    const float per_side = bounds / cell_min; // (ordinary: both are)
-    const uint32_t g = per_side >= (float)cap ? cap : (per_side >= 1.0f ? (uint32_t)per_side : 1u);
-    *cell = std::max(cell_min, bounds / (float)g);
-    return g;
-}
-
-// The contact test of the step's collision loop on two positions (both contacts reports).  The root is only taken where d2 <= thr =
-// (2r)^2 * 1.001 (beyond it sqrt(d2) > 2r * 1.0004: no contact, and d2 > 0); thr is +inf where that product is no ordinary number, a
-// NaN d2 fails `d2 > thr` and then every comparison: a NaN or infinite distance is no contact.
-SB_DEV bool sb_touch(float2 me, float2 other, float thr, float two_r)
-{
-    const float dx = other.x - me.x, dy = other.y - me.y;
-    const float d2 = dx * dx + dy * dy;
-    if (d2 > thr) return false;
-    const float dist = sb_sqrt(d2); // sb_length(dx, dy)
-    return dist == 0.0f || dist < two_r;
-}
+// LDS behind cell_off: the buckets of sb_contact_cells.h with their counts twice (one array per substep parity), overflow words u32[2]
+static inline uint32_t sb_batch_cell_lds_bytes(uint32_t g) { return (sb_bucket_entry_words(g) + 2u * sb_bucket_count_words(g) + 2u) * 4u; }
 
 SB_DEV uint32_t sbb_uniform(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
 SB_DEV float sbb_uniform(float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); }

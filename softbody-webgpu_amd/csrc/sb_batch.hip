@@ -58,7 +58,7 @@ __global__ __launch_bounds__(1024) void k_batch_frame(SbBatchView V, SbParams pr
     // contact cells (sb_batch_cell_lds_bytes mirrors them): the counts are double buffered by substep parity, so a substep
     // fills one buffer while every thread empties the word it filled in the other: no pass over G^2 words, no barrier of its own
     const bool cells = COLLIDE == SB_BATCH_CELLS && P >= V.cell_min_p; // workgroup-uniform
-    const uint32_t G = V.cell_g, cntw = (G * G + 1u) >> 1;
+    const uint32_t G = V.cell_g, cntw = sb_bucket_count_words(G);
     uint16_t *s_cent = (uint16_t *)(sbb_lds + V.cell_off);               // [G * G][SB_BATCH_CELL_K] slots
     uint32_t *s_ccnt = (uint32_t *)(s_cent + G * G * SB_BATCH_CELL_K);   // [2][cntw] two 16-bit counts to a word
     uint32_t *s_covf = s_ccnt + 2u * cntw;                               // [2] "a cell was full"
@@ -117,13 +117,10 @@ __global__ __launch_bounds__(1024) void k_batch_frame(SbBatchView V, SbParams pr
     __syncthreads();
 
     const float elasticity_coeff = sb_div(c.elasticity + 1.0f, 2.0f); // :143
-    // Contact test of k_particles<SB_COLLIDE_ALLPAIRS>: dist = sqrt(d2) (IEEE), contact when dist == 0 or dist < 2r.  The root is
-    // only taken where d2 <= thr = (2r)^2 * 1.001: beyond it sqrt(d2) > 2r * 1.0004, which no rounding brings back under 2r
-    // (and d2 > 0).  A threshold that is not an ordinary number (tiny, huge or NaN radius) turns the shortcut off; a NaN d2
-    // fails `d2 > thr` and takes the exact test.
-    const float two_r = prm.particle_radius * 2.0f;
-    const float thr0 = two_r * two_r * 1.001f;
-    const float thr = (thr0 >= 0x1p-100f && thr0 <= 0x1p100f) ? thr0 : __uint_as_float(0x7f800000u);
+    // Contact test of k_particles<SB_COLLIDE_ALLPAIRS>: dist = sqrt(d2) (IEEE), contact when dist == 0 or dist < 2r, the root
+    // only taken under sb_touch_test's threshold (sb_contact_cells.h; the loops below keep dx, dy and dist for the pair)
+    const SbTouchTest tt = sb_touch_test(prm.particle_radius);
+    const float two_r = tt.two_r, thr = tt.thr;
 
     // ---- substeps
     uint32_t cur = 0u;
@@ -142,6 +139,8 @@ __global__ __launch_bounds__(1024) void k_batch_frame(SbBatchView V, SbParams pr
                 if (k != 0u) s_ccnt[((k & 1u) ^ 1u) * cntw + ((my_cy * G + my_cx) >> 1)] = 0u;
                 my_cx = sb_grid_coord(q.p.x, 0.0f, V.cell, G); // monotone, clamped; NaN and -inf: cell 0, +inf: the last one
                 my_cy = sb_grid_coord(q.p.y, 0.0f, V.cell, G);
+                // (sb_bucket_push in this kernel's own words: through the helper the two arms of the branch change places; this way
+                // the kernel's instructions are unchanged)
                 const uint32_t cell = my_cy * G + my_cx, sh = (cell & 1u) << 4;
                 const uint32_t n = (atomicAdd(&ccnt[cell >> 1], 1u << sh) >> sh) & 0xffffu; // (at most 1024 per cell: no carry)
                 if (n < SB_BATCH_CELL_K) s_cent[cell * SB_BATCH_CELL_K + n] = (uint16_t)tid;
@@ -198,20 +197,19 @@ __global__ __launch_bounds__(1024) void k_batch_frame(SbBatchView V, SbParams pr
                 // applied in ascending slot order: a sweep collects the four smallest slots above the last one applied
                 // (the order of the entries inside a cell does not matter), then they are applied; a sweep that comes back
                 // with fewer than four was the last.
-                const uint32_t x0 = my_cx > 0u ? my_cx - 1u : 0u, x1 = my_cx + 1u < G ? my_cx + 1u : G - 1u;
-                const uint32_t y0 = my_cy > 0u ? my_cy - 1u : 0u, y1 = my_cy + 1u < G ? my_cy + 1u : G - 1u;
+                const SbCellWindow win(my_cx, my_cy, G);
                 bool have_last = false;
                 uint32_t last = 0u;
                 for (;;) {
                     uint32_t bs[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, bi[4] = {0u, 0u, 0u, 0u};
-                    for (uint32_t yy = y0; yy <= y1; yy++) {
-                        for (uint32_t xx = x0; xx <= x1; xx++) {
+                    for (uint32_t yy = win.y0; yy <= win.y1; yy++) {
+                        for (uint32_t xx = win.x0; xx <= win.x1; xx++) {
                             const uint32_t cell = yy * G + xx;
-                            const uint32_t n = (ccnt[cell >> 1] >> ((cell & 1u) << 4)) & 0xffffu; // <= SB_BATCH_CELL_K: no cell was full
-                            const uint2 ent = *(const uint2 *)(s_cent + cell * SB_BATCH_CELL_K);
+                            const uint32_t n = sb_bucket_count(ccnt, cell); // <= SB_BATCH_CELL_K: no cell was full
+                            const SbBucketWords ent = sb_bucket_load(s_cent, cell);
 #pragma unroll
                             for (uint32_t j = 0; j < SB_BATCH_CELL_K; j++) {
-                                const uint32_t o = ((j < 2u ? ent.x : ent.y) >> ((j & 1u) << 4)) & 0xffffu;
+                                const uint32_t o = sb_bucket_entry(ent, j);
                                 if (j >= n || o == tid || (have_last && o <= last) || o >= bs[3]) continue;
                                 const float2 op = rp[o];
                                 const float dx = op.x - self.p.x, dy = op.y - self.p.y;

@@ -15,8 +15,8 @@
 //            wider than 2r and the coordinate map is monotone) and counts: partners, partners of another label, the smallest
 //            partner, partners above it (the pairs it will list)
 //   list     exclusive scan of "pairs I list" over the data indices; particle i then writes its pairs {i, j}, j ascending, by
-//            repeated selection of the four smallest partners above the last one written; positions >= max_pairs are not
-//            written, the tail behind the last pair is filled with -1
+//            repeated selection of the four smallest partners above the last one written (sb_select_ascending); positions
+//            >= max_pairs are not written, the tail behind the last pair is filled with -1
 // Everything behind the float test is integers: counts, minima, sums (LDS integer atomics) and a list whose order is defined by
 // the indices -- neither the order inside a cell nor the schedule can change a bit of the output.
 #include <algorithm>
@@ -141,9 +141,7 @@ __global__ __launch_bounds__(SBK_BLOCK) void k_batch_contacts(SbBatchView V, SbP
     __syncthreads();
 
     // ---- visit
-    const float two_r = prm.particle_radius * 2.0f;
-    const float thr0 = two_r * two_r * 1.001f;
-    const float thr = (thr0 >= 0x1p-100f && thr0 <= 0x1p100f) ? thr0 : __uint_as_float(0x7f800000u);
+    const SbTouchTest tt = sb_touch_test(prm.particle_radius);
     const float lo = prm.particle_radius, hi = prm.bounds_size - prm.particle_radius; // sb_particle_finish's (compute.wgsl:190)
     const bool wide = ((uintptr_t)touch & 15u) == 0u; // (rows are 16 bytes: whole-row stores where the buffer allows them)
     uint32_t n_pairs = 0u, n_cross = 0u, n_walled = 0u, n_touching = 0u;
@@ -153,16 +151,14 @@ __global__ __launch_bounds__(SBK_BLOCK) void k_batch_contacts(SbBatchView V, SbP
         if (c != SBK_NONE) {
             const uint32_t cx = c & 0xffffu, cy = c >> 16, my_lab = s_lab[d];
             const float2 me = s_pos[d];
-            const uint32_t x0 = cx > 0u ? cx - 1u : 0u, x1 = cx + 1u < G ? cx + 1u : G - 1u;
-            const uint32_t y0 = cy > 0u ? cy - 1u : 0u, y1 = cy + 1u < G ? cy + 1u : G - 1u;
+            const SbCellWindow win(cx, cy, G);
             uint32_t n = 0u, cross = 0u, above = 0u, above_cross = 0u, first = SBK_NONE;
-            for (uint32_t yy = y0; yy <= y1; yy++) {
-                // (the cells x0 .. x1 of a row are neighbours in s_sorted: one run)
-                const uint32_t r0 = yy * G + x0, r1 = yy * G + x1;
-                const uint32_t from = r0 ? s_end[r0 - 1u] : 0u, to = s_end[r1];
+            for (uint32_t yy = win.y0; yy <= win.y1; yy++) {
+                uint32_t from, to;
+                win.run(s_end, yy, &from, &to);
                 for (uint32_t k = from; k < to; k++) {
                     const uint32_t o = s_sorted[k];
-                    if (o == d || !sb_touch(me, s_pos[o], thr, two_r)) continue;
+                    if (o == d || !sb_touch(me, s_pos[o], tt.thr, tt.two_r)) continue;
                     const uint32_t differs = s_lab[o] != my_lab ? 1u : 0u, up = o > d ? 1u : 0u;
                     n++;
                     cross += differs;
@@ -209,37 +205,21 @@ __global__ __launch_bounds__(SBK_BLOCK) void k_batch_contacts(SbBatchView V, SbP
         if (c == SBK_NONE || at >= stop) continue;
         const uint32_t cx = c & 0xffffu, cy = c >> 16, my_lab = s_lab[d];
         const float2 me = s_pos[d];
-        const uint32_t x0 = cx > 0u ? cx - 1u : 0u, x1 = cx + 1u < G ? cx + 1u : G - 1u;
-        const uint32_t y0 = cy > 0u ? cy - 1u : 0u, y1 = cy + 1u < G ? cy + 1u : G - 1u;
-        uint32_t last = d; // (a listed partner is above d)
-        while (at < stop) {
-            // one sweep keeps the four smallest partners above `last`, ascending (SB_SELECT_INSERT's carry, on one array)
-            uint32_t bs[4] = {SBK_NONE, SBK_NONE, SBK_NONE, SBK_NONE};
-            for (uint32_t yy = y0; yy <= y1; yy++) {
-                const uint32_t r0 = yy * G + x0, r1 = yy * G + x1;
-                const uint32_t from = r0 ? s_end[r0 - 1u] : 0u, to = s_end[r1];
-                for (uint32_t k = from; k < to; k++) {
-                    uint32_t o = s_sorted[k];
-                    if (o <= last || o >= bs[3] || (other_body && s_lab[o] == my_lab) || !sb_touch(me, s_pos[o], thr, two_r)) continue;
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const uint32_t small = min(o, bs[q]);
-                        o = max(o, bs[q]);
-                        bs[q] = small;
+        const SbCellWindow win(cx, cy, G);
+        sb_select_ascending(true, d, [&](SbSelect4 &sel) { // (a listed partner is above d)
+                for (uint32_t yy = win.y0; yy <= win.y1; yy++) {
+                    uint32_t from, to;
+                    win.run(s_end, yy, &from, &to);
+                    for (uint32_t k = from; k < to; k++) {
+                        const uint32_t o = s_sorted[k];
+                        if (sel.wants(o) && !(other_body && s_lab[o] == my_lab) && sb_touch(me, s_pos[o], tt.thr, tt.two_r)) sel.insert(o);
                     }
                 }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                if (bs[q] != SBK_NONE && at < stop) {
-                    prow[2ull * at] = (int32_t)d;
-                    prow[2ull * at + 1ull] = (int32_t)bs[q];
-                    last = bs[q];
-                    at++;
-                }
-            }
-            if (bs[3] == SBK_NONE) break; // (fewer than four were left; `at` has reached `stop` with them)
-        }
+            },
+            [&](uint32_t o) {
+                prow[2ull * at] = (int32_t)d, prow[2ull * at + 1ull] = (int32_t)o;
+                return ++at < stop;
+            });
     }
     for (unsigned long long k = 2ull * min(listed, max_pairs) + tid; k < 2ull * max_pairs; k += SBK_BLOCK) prow[k] = -1;
 }

@@ -12,10 +12,9 @@
 //            position: the frame kernel's G x G buckets of SB_BATCH_CELL_K slots (sb_batch_cell_geometry).  A full bucket
 //            sends the whole workgroup through the loop over all slots.
 //   contacts a lane per particle slot: its partners in ASCENDING SLOT ORDER -- the loop over all slots, or selection sweeps over
-//            the 3 x 3 cells around its own, four smallest slots above the last one applied per sweep (whoever is a partner sits
-//            there: the cells are wider than 2r, the coordinate map is monotone) -- each through sbf_contact_add: the terms
-//            sb_collide_pair_at would subtract from particle.a and particle.v.  The float sums depend on the order alone, and
-//            the order is the slots': both paths give the same bits.
+//            the 3 x 3 cells around its own (sb_contact_cells.h: window, buckets, sb_select_ascending) -- each through
+//            sbf_contact_add: the terms sb_collide_pair_at would subtract from particle.a and particle.v.  The float sums depend
+//            on the order alone, and the order is the slots': both paths give the same bits.
 //   rows     the lane of a particle writes its row and its two force words at the particle's data index; rows of data indices
 //            where nobody lives are written as zeros by whoever comes by: every word is written exactly once.
 #include <algorithm>
@@ -25,7 +24,6 @@
 #include "sb_batch_forces_math.h"
 
 #define SBF_BLOCK 256u
-#define SBF_NONE 0xFFFFFFFFu
 enum { SBF_TOUCHING, SBF_NONFINITE, SBF_OVERFLOW, SBF_NWORDS = 4 }; // LDS words behind the arrays (the fourth keeps what follows 8-byte aligned)
 
 // cells per side of sb_batch_forces_device and their width: sb_batch_create's rule, whatever the batch's collision_mode; 0: no
@@ -37,10 +35,10 @@ static uint32_t sbf_cells(const sb_batch *b, float *cell)
 }
 // LDS words in front of the cells: pos, vel, f (2 words each), label per slot; the two bitmaps; SBF_NWORDS; made even
 static __host__ __device__ inline uint32_t sbf_cell_off_words(uint32_t maxP, uint32_t maxB) { return (7u * maxP + (maxP + 31u) / 32u + (maxB + 31u) / 32u + SBF_NWORDS + 1u) & ~1u; }
-// the cells: entries u16[G * G][SB_BATCH_CELL_K], then counts, two 16-bit counts to a word
+// the cells behind them: the buckets of sb_contact_cells.h, then their counts
 static inline uint32_t sbf_lds_bytes(uint32_t maxP, uint32_t maxB, uint32_t g)
 {
-    return (sbf_cell_off_words(maxP, maxB) + g * g * SB_BATCH_CELL_K / 2u + (g * g + 1u) / 2u) * 4u;
+    return (sbf_cell_off_words(maxP, maxB) + sb_bucket_entry_words(g) + sb_bucket_count_words(g)) * 4u;
 }
 
 __global__ __launch_bounds__(SBF_BLOCK) void k_batch_forces(SbBatchView V, SbParams prm, uint32_t G, float cell, uint32_t cell_min_p,
@@ -60,7 +58,7 @@ __global__ __launch_bounds__(SBF_BLOCK) void k_batch_forces(SbBatchView V, SbPar
     uint32_t *s_bbits = s_pbits + pw;            // [bw] per beam DATA index: an evaluated beam lives here
     uint32_t *s_red = s_bbits + bw;              // [SBF_NWORDS]
     uint16_t *s_cent = (uint16_t *)(sbf_lds + sbf_cell_off_words(maxP, maxB)); // [ncell][SB_BATCH_CELL_K] slots
-    uint32_t *s_ccnt = (uint32_t *)(s_cent + ncell * SB_BATCH_CELL_K);          // [(ncell + 1) / 2]
+    uint32_t *s_ccnt = (uint32_t *)(s_cent + ncell * SB_BATCH_CELL_K);          // [sb_bucket_count_words(G)]
 
     const SbbScene hd = sbb_scene(V, scene);
     const uint32_t P = hd.P, Bc = hd.Bc;
@@ -103,7 +101,7 @@ __global__ __launch_bounds__(SBF_BLOCK) void k_batch_forces(SbBatchView V, SbPar
     // a blob that is not what an upload leaves from reaching past the caller's buffers all the same)
     for (uint32_t w = tid; w < pw + bw + SBF_NWORDS; w += SBF_BLOCK) s_pbits[w] = 0u; // (the three arrays are neighbours)
     if (cells)
-        for (uint32_t w = tid; w < (ncell + 1u) >> 1; w += SBF_BLOCK) s_ccnt[w] = 0u;
+        for (uint32_t w = tid; w < sb_bucket_count_words(G); w += SBF_BLOCK) s_ccnt[w] = 0u;
     __syncthreads();
     for (uint32_t s = tid; s < P; s += SBF_BLOCK) {
         const uint32_t d = g_pmap[s];
@@ -121,10 +119,7 @@ __global__ __launch_bounds__(SBF_BLOCK) void k_batch_forces(SbBatchView V, SbPar
         if (in) atomicOr(&s_pbits[d >> 5], 1u << (d & 31u));
         if (cells) { // bin (the counts were zeroed a barrier ago)
             const uint32_t cx = sb_grid_coord(p.x, 0.0f, cell, G), cy = sb_grid_coord(p.y, 0.0f, cell, G); // monotone, clamped; NaN: cell 0
-            const uint32_t c = cy * G + cx, sh = (c & 1u) << 4;
-            const uint32_t n = (atomicAdd(&s_ccnt[c >> 1], 1u << sh) >> sh) & 0xffffu; // (at most 1024 per cell: no carry)
-            if (n < SB_BATCH_CELL_K) s_cent[c * SB_BATCH_CELL_K + n] = (uint16_t)s;
-            else s_red[SBF_OVERFLOW] = 1u;
+            if (sb_bucket_push(s_cent, s_ccnt, cy * G + cx, s)) s_red[SBF_OVERFLOW] = 1u;
         }
     }
     __syncthreads();
@@ -153,9 +148,8 @@ __global__ __launch_bounds__(SBF_BLOCK) void k_batch_forces(SbBatchView V, SbPar
 
     // ---- contact phase and the rows of the particles
     const float elasticity_coeff = sb_div(elasticity + 1.0f, 2.0f); // :143
-    const float two_r = prm.particle_radius * 2.0f;
-    const float thr0 = two_r * two_r * 1.001f;
-    const float thr = (thr0 >= 0x1p-100f && thr0 <= 0x1p100f) ? thr0 : __uint_as_float(0x7f800000u); // sb_touch's shortcut
+    const SbTouchTest tt = sb_touch_test(prm.particle_radius);
+    const float two_r = tt.two_r, thr = tt.thr;
     const float dt2 = prm.time_step * prm.time_step;
     const bool walk = !cells || sbb_uniform(s_red[SBF_OVERFLOW]) != 0u; // a cell was full: every thread takes the loop
     uint32_t n_touching = 0u;
@@ -173,45 +167,18 @@ __global__ __launch_bounds__(SBF_BLOCK) void k_batch_forces(SbBatchView V, SbPar
             }
         } else {
             const uint32_t cx = sb_grid_coord(me.x, 0.0f, cell, G), cy = sb_grid_coord(me.y, 0.0f, cell, G);
-            const uint32_t x0 = cx > 0u ? cx - 1u : 0u, x1 = cx + 1u < G ? cx + 1u : G - 1u;
-            const uint32_t y0 = cy > 0u ? cy - 1u : 0u, y1 = cy + 1u < G ? cy + 1u : G - 1u;
-            bool have_last = false;
-            uint32_t last = 0u;
-            for (;;) {
-                // one sweep keeps the four smallest partner slots above `last`, ascending (the carry of SB_SELECT_INSERT, on one array)
-                uint32_t bs[4] = {SBF_NONE, SBF_NONE, SBF_NONE, SBF_NONE};
-                for (uint32_t yy = y0; yy <= y1; yy++) {
-                    for (uint32_t xx = x0; xx <= x1; xx++) {
-                        const uint32_t cc = yy * G + xx;
-                        const uint32_t n = (s_ccnt[cc >> 1] >> ((cc & 1u) << 4)) & 0xffffu; // <= SB_BATCH_CELL_K: no cell was full
-                        const uint2 ent = *(const uint2 *)(s_cent + cc * SB_BATCH_CELL_K);
-#pragma unroll
-                        for (uint32_t j = 0; j < SB_BATCH_CELL_K; j++) {
-                            uint32_t o = ((j < 2u ? ent.x : ent.y) >> ((j & 1u) << 4)) & 0xffffu;
-                            if (j >= n || o == s || (have_last && o <= last) || o >= bs[3]) continue;
-                            if ((other_body && s_lab[o] == my_lab) || !sb_touch(me, s_pos[o], thr, two_r)) continue;
-#pragma unroll
-                            for (int q = 0; q < 4; q++) {
-                                const uint32_t small = min(o, bs[q]);
-                                o = max(o, bs[q]);
-                                bs[q] = small;
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    if (bs[q] != SBF_NONE) {
-                        const uint32_t o = bs[q];
-                        const float2 op = s_pos[o], ov = s_vel[o];
-                        const float dx = op.x - me.x, dy = op.y - me.y;
-                        sbf_contact_add(c, dx, dy, sb_sqrt(dx * dx + dy * dy), mv.x - ov.x, mv.y - ov.y, two_r, friction, elasticity_coeff, prm.inv_dt2, dt2);
-                        last = o;
-                        have_last = true;
-                    }
-                }
-                if (bs[3] == SBF_NONE) break; // (fewer than four were left)
-            }
+            const SbCellWindow win(cx, cy, G);
+            sb_select_ascending(false, 0u, [&](SbSelect4 &sel) {
+                    sb_bucket_for_window(win, s_cent, s_ccnt, [&](uint32_t o) {
+                        if (o != s && sel.wants(o) && !(other_body && s_lab[o] == my_lab) && sb_touch(me, s_pos[o], thr, two_r)) sel.insert(o);
+                    });
+                },
+                [&](uint32_t o) {
+                    const float2 op = s_pos[o], ov = s_vel[o];
+                    const float dx = op.x - me.x, dy = op.y - me.y;
+                    sbf_contact_add(c, dx, dy, sb_sqrt(dx * dx + dy * dy), mv.x - ov.x, mv.y - ov.y, two_r, friction, elasticity_coeff, prm.inv_dt2, dt2);
+                    return true;
+                });
         }
         n_touching += c.partners ? 1u : 0u;
         const uint32_t d = g_pmap[s];

@@ -52,8 +52,7 @@ __global__ __launch_bounds__(SBS_BLOCK) void k_batch_add_particles(SbBatchView V
     __syncthreads();
 
     // ---- touching a particle of the scene: every slot's current position against the candidate rows
-    float two_r;
-    const float thr = sbs::touch_threshold(radius, &two_r);
+    const SbTouchTest tt = sb_touch_test(radius);
     if (skip_touching) {
         for (uint32_t s = tid; s < P; s += SBS_BLOCK) {
             const uint32_t d = g_pmap[s];
@@ -61,7 +60,7 @@ __global__ __launch_bounds__(SBS_BLOCK) void k_batch_add_particles(SbBatchView V
             const float2 other = g_part[3u * d];
             for (uint32_t q = 0; q < k; q++) {
                 const float2 me = make_float2(__uint_as_float(s_row[q * SBA_ROW_WORDS + 1u]), __uint_as_float(s_row[q * SBA_ROW_WORDS + 2u]));
-                if (s_verd[q] == sba::CANDIDATE && sb_touch(me, other, thr, two_r)) atomicOr(&s_hit[q >> 5], 1u << (q & 31u));
+                if (s_verd[q] == sba::CANDIDATE && sb_touch(me, other, tt.thr, tt.two_r)) atomicOr(&s_hit[q >> 5], 1u << (q & 31u));
             }
         }
         __syncthreads();
@@ -78,7 +77,7 @@ __global__ __launch_bounds__(SBS_BLOCK) void k_batch_add_particles(SbBatchView V
             tid, ((s_hit[tid >> 5] >> (tid & 31u)) & 1u) != 0u, [&](uint32_t i) { return s_verd[i]; },
             [&](uint32_t i) { return ((s_hit[i >> 5] >> (i & 31u)) & 1u) != 0u; },
             [&](uint32_t i) {
-                return sb_touch(me, make_float2(__uint_as_float(s_row[i * SBA_ROW_WORDS + 1u]), __uint_as_float(s_row[i * SBA_ROW_WORDS + 2u])), thr, two_r);
+                return sb_touch(me, make_float2(__uint_as_float(s_row[i * SBA_ROW_WORDS + 1u]), __uint_as_float(s_row[i * SBA_ROW_WORDS + 2u])), tt.thr, tt.two_r);
             });
         if (blocked) verd = sbs::SBS_BLOCKED;
     }

@@ -1,10 +1,9 @@
 // sb_batch_spawn_math.h -- "may this row become a particle, and does it touch that one?", the verdict of one
 // sb_batch_new_particle row before the scene's room is looked at (sb_batch_add_particles_device, sb_batch_spawn.hip;
 // include/softbody.h states it): empty, the reserved word, "x and y are finite", and the blocked rule over the
-// rows of one call.  Host and device: integers and comparisons plus, on the host, the contact test as sb_touch (sb_batch.h) takes
-// it -- float32, one rounding per operator in the order written (the library builds with -ffp-contract=off;
-// tests/batch_spawn_check.cpp builds it the same way), the square root IEEE.  Every comparison with a NaN is false.  Header-only
-// and HIP-free on the host.  The row's width, the codes every adding call shares and word_as_float are sb_batch_alloc.h's.
+// rows of one call.  Host and device: integers and comparisons; the contact test the blocked rule is asked with is
+// sb_contact_cells.h's (sb_touch_test, sb_touch / sb_touch_xy), which tests/batch_spawn_check.cpp calls too.  Header-only and
+// HIP-free on the host.  The row's width, the codes every adding call shares and word_as_float are sb_batch_alloc.h's.
 #pragma once
 #include "sb_batch_alloc.h"
 
@@ -25,25 +24,6 @@ SBA_HD int row_verdict(const uint32_t *w, bool loaded)
     if ((int32_t)w[0] < 0) return sba::EMPTY;
     if (!loaded || w[7] != 0u || !finite_bits(w[1]) || !finite_bits(w[2])) return sba::INVALID;
     return sba::CANDIDATE;
-}
-
-// the threshold under which sb_touch takes the root: (2r)^2 * 1.001, +inf where that product is no ordinary number
-// (k_batch_frame's and the contacts report's expression)
-SBA_HD float touch_threshold(float radius, float *two_r)
-{
-    *two_r = radius * 2.0f;
-    const float thr0 = *two_r * *two_r * 1.001f;
-    return (thr0 >= 0x1p-100f && thr0 <= 0x1p100f) ? thr0 : word_as_float(0x7f800000u);
-}
-
-// sb_touch(me, other, thr, two_r) on the host (the kernel calls sb_touch itself; this is its restatement for the check program)
-inline bool touch(float mx, float my, float ox, float oy, float thr, float two_r)
-{
-    const float dx = ox - mx, dy = oy - my;
-    const float d2 = dx * dx + dy * dy;
-    if (d2 > thr) return false;
-    const float dist = __builtin_sqrtf(d2);
-    return dist == 0.0f || dist < two_r;
 }
 
 // Step 3 for row j from what is known of the rows before it: verd[i] (steps 1 and 2), E[i] ("touches a particle slot < P"),

@@ -2,8 +2,8 @@
 // sb_contacts_device of include/softbody.h; gfx950, wave64).
 //
 // The definition is sb_batch_contacts_device's, word for word: two distinct particles i, j TOUCH iff dist == 0 or
-// dist < particle_radius * 2, dist = sb_length(xj - xi, yj - yi) of the current particle records (sb_touch of sb_batch.h, the one test both
-// files call), everything named by particle DATA index.
+// dist < particle_radius * 2, dist = sb_length(xj - xi, yj - yi) of the current particle records (sb_touch of sb_contact_cells.h, the one
+// test both files call), everything named by particle DATA index.
 // k_batch_contacts holds a scene in the LDS of one workgroup; here the scene lies in HBM, and the call may only enqueue: nothing
 // loops on a host read-back and no workgroup waits for another.  A counting sort by cell in global memory, one launch per stage:
 //   k_contacts_bin      a thread per data index: the position (through the shared data index -> internal particle table, sb_report.hip, in
@@ -34,7 +34,7 @@
 #include <vector>
 
 #include "sb_report.h"
-#include "sb_batch.h" // sb_batch_cell_geometry: the cells' rule; sb_touch: the contact test
+#include "sb_batch.h" // sb_contact_cells.h: the cells' rule, the contact test, the window and the selection
 
 #define SBC_BLOCK 256u
 #define SBC_NONE 0xFFFFFFFFu
@@ -103,22 +103,8 @@ __global__ __launch_bounds__(SBC_BLOCK) void k_contacts_scatter(const uint32_t *
     sorted[atomicAdd(&start[c], 1u)] = r;
 }
 
-// the runs of a record's 3 x 3 cells: row yy of them is sorted[from .. to)
-struct SbcWalk {
-    uint32_t x0, x1, y0, y1, G;
-    SB_DEV SbcWalk(float x, float y, SbcGeo g) : G(g.G)
-    {
-        const uint32_t cx = sb_grid_coord(x, 0.0f, g.cell, g.G), cy = sb_grid_coord(y, 0.0f, g.cell, g.G);
-        x0 = cx > 0u ? cx - 1u : 0u, x1 = cx + 1u < G ? cx + 1u : G - 1u;
-        y0 = cy > 0u ? cy - 1u : 0u, y1 = cy + 1u < G ? cy + 1u : G - 1u;
-    }
-    SB_DEV void row(const uint32_t *__restrict__ end, uint32_t yy, uint32_t *from, uint32_t *to) const
-    {
-        const uint32_t r0 = yy * G + x0, r1 = yy * G + x1;
-        *from = r0 ? end[r0 - 1u] : 0u;
-        *to = end[r1];
-    }
-};
+// the window of a record's 3 x 3 cells (sb_contact_cells.h): row yy of them is sorted[from .. to), SbCellWindow::run
+SB_DEV SbCellWindow sbc_window(float x, float y, SbcGeo g) { return SbCellWindow(sb_grid_coord(x, 0.0f, g.cell, g.G), sb_grid_coord(y, 0.0f, g.cell, g.G), g.G); }
 
 struct SbcTest {
     float two_r, thr, lo, hi;
@@ -136,11 +122,11 @@ __global__ __launch_bounds__(SBC_BLOCK) void k_contacts_visit(const SbcRec *__re
     if (k < P) {
         const SbcRec me = sorted[k];
         const int32_t my_lab = labels ? labels[me.d] : 0;
-        const SbcWalk w(me.x, me.y, geo);
+        const SbCellWindow w = sbc_window(me.x, me.y, geo);
         uint32_t first = SBC_NONE;
         for (uint32_t yy = w.y0; yy <= w.y1; yy++) {
             uint32_t from, to;
-            w.row(end, yy, &from, &to);
+            w.run(end, yy, &from, &to);
             for (uint32_t q = from; q < to; q++) {
                 const SbcRec o = sorted[q];
                 if (o.d == me.d || !sb_touch(make_float2(me.x, me.y), make_float2(o.x, o.y), ts.thr, ts.two_r)) continue;
@@ -187,37 +173,22 @@ __global__ __launch_bounds__(SBC_BLOCK) void k_contacts_list(const SbcRec *__res
     const unsigned long long stop = min(at + (unsigned long long)above_of[me.d], max_pairs);
     if (at >= stop) return;
     const int32_t my_lab = other_body ? labels[me.d] : 0;
-    const SbcWalk w(me.x, me.y, geo);
-    uint32_t last = me.d; // (a listed partner is above d)
-    while (at < stop) {
-        // one sweep keeps the four smallest partners above `last`, ascending
-        uint32_t bs[4] = {SBC_NONE, SBC_NONE, SBC_NONE, SBC_NONE};
-        for (uint32_t yy = w.y0; yy <= w.y1; yy++) {
-            uint32_t from, to;
-            w.row(end, yy, &from, &to);
-            for (uint32_t q = from; q < to; q++) {
-                const SbcRec r = sorted[q];
-                uint32_t o = r.d;
-                if (o <= last || o >= bs[3] || !sb_touch(make_float2(me.x, me.y), make_float2(r.x, r.y), ts.thr, ts.two_r) || (other_body && labels[o] == my_lab)) continue;
-#pragma unroll
-                for (int s = 0; s < 4; s++) {
-                    const uint32_t small = min(o, bs[s]);
-                    o = max(o, bs[s]);
-                    bs[s] = small;
+    const SbCellWindow w = sbc_window(me.x, me.y, geo);
+    sb_select_ascending(true, me.d, [&](SbSelect4 &sel) { // (a listed partner is above d)
+            for (uint32_t yy = w.y0; yy <= w.y1; yy++) {
+                uint32_t from, to;
+                w.run(end, yy, &from, &to);
+                for (uint32_t q = from; q < to; q++) {
+                    const SbcRec r = sorted[q];
+                    if (sel.wants(r.d) && sb_touch(make_float2(me.x, me.y), make_float2(r.x, r.y), ts.thr, ts.two_r) && !(other_body && labels[r.d] == my_lab))
+                        sel.insert(r.d);
                 }
             }
-        }
-#pragma unroll
-        for (int s = 0; s < 4; s++) {
-            if (bs[s] != SBC_NONE && at < stop) {
-                pairs[2ull * at] = (int32_t)me.d;
-                pairs[2ull * at + 1ull] = (int32_t)bs[s];
-                last = bs[s];
-                at++;
-            }
-        }
-        if (bs[3] == SBC_NONE) break; // (fewer than four were left; `at` has reached `stop` with them)
-    }
+        },
+        [&](uint32_t o) {
+            pairs[2ull * at] = (int32_t)me.d, pairs[2ull * at + 1ull] = (int32_t)o;
+            return ++at < stop;
+        });
 }
 
 // rows [listed, max_pairs) of the pair list
@@ -311,9 +282,8 @@ static sb_status sbc_enqueue(sb_engine *e, const sb_contacts_options *o, const v
     long long *d_counts = mir.out_at<long long>(counts, d_acc, SBC_NACC * sizeof(unsigned long long), SB_CONTACT_COUNT_WORDS * sizeof(int64_t));
     SB_TRY(mir.st);
 
-    const float two_r = e->prm.particle_radius * 2.0f, thr0 = two_r * two_r * 1.001f;
-    const SbcTest ts{two_r, (thr0 >= 0x1p-100f && thr0 <= 0x1p100f) ? thr0 : __builtin_inff(), e->prm.particle_radius,
-                     e->prm.bounds_size - e->prm.particle_radius}; // sb_particle_finish's lo / hi (compute.wgsl:190)
+    const SbTouchTest tt = sb_touch_test(e->prm.particle_radius);
+    const SbcTest ts{tt.two_r, tt.thr, e->prm.particle_radius, e->prm.bounds_size - e->prm.particle_radius}; // sb_particle_finish's lo / hi (compute.wgsl:190)
     const uint32_t other = flags & SB_CONTACTS_OTHER_BODY;
     const float2 *pos = e->part[e->cur].pos;
     const uint32_t *d_pinv = s.buf[SBQ_B_PINV].as<uint32_t>();

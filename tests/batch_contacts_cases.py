@@ -139,6 +139,11 @@ def case_mixed(sb):
     return _with(gc.case_mixed(sb), 4096)
 
 
+def case_rings(sb):
+    """batch_grid_cases' rings: a centre with 0, 1, 3, 4, 5, 7, 8 and 9 partners; at most 9 spokes and 9 pairs along a ring."""
+    return _with(gc.case_rings(sb), 32)
+
+
 def case_mapping(sb):
     """batch_cases' permuted default scene and its `coincident` scene (particles on one spot: dist == 0)."""
     return _with(bc.case_mapping(sb), 1024)
@@ -159,7 +164,7 @@ def case_saturation(sb):
 
 
 def grid_cases(sb):
-    return [case_pile(sb), case_edges(sb), case_out_of_range(sb), case_mixed(sb)] + [case_geometry(sb, b, r) for b, r in gc.GEOMETRIES]
+    return [case_pile(sb), case_edges(sb), case_out_of_range(sb), case_mixed(sb), case_rings(sb)] + [case_geometry(sb, b, r) for b, r in gc.GEOMETRIES]
 
 
 def batch_cases(sb):

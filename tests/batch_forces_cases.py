@@ -5,6 +5,7 @@ import numpy as np
 
 import batch_cases as bc
 import batch_contacts_cases as cs
+import batch_grid_cases as gc
 
 F = np.float32
 L = 2                            # layout of every scene here
@@ -154,6 +155,12 @@ def case_contacts(sb, subticks=64):
     bufs = [contact_zoo(sb), contact_zoo(sb, -1), contact_zoo(sb, 4), crowded_cell(sb),
             contact_zoo(sb, 2, consts=dict(friction=0.7, elasticity=0.9))]
     return case("contact zoo, subticks %d" % subticks, CONTACT_CAP, bufs, subticks=subticks, grid_min_particles=GRID_MIN)
+
+
+def case_rings(sb):
+    """tests/batch_grid_cases.py's rings, every scene on the cells: a centre with 0, 1, 3, 4, 5, 7, 8 and 9 partners spread over
+    four cells, and the fullest ring once more inside one cell (the fallback)."""
+    return dict(gc.case_rings(sb), grid_min_particles=1)
 
 
 def case_two_bodies(sb):

@@ -161,12 +161,46 @@ def case_mixed(sb):
     return dict(name="mixed sizes", layout=L, cap=cap, mode=bc.ALLPAIRS, bufs=bufs, program=[("frame", 1), ("step", 7)])
 
 
+# ---------------------------------------------------------------- rings
+RING_CAP = (64, 0)               # 12 cells per side, 83.3 wide, at bounds 1000 / radius 10: a whole ring fits into one
+RING_PARTNERS = (0, 1, 3, 4, 5, 7, 8, 9)         # around 4 and 8: where a selection sweep that comes back full was the last
+RING_RADIUS = 19.9               # just inside 2r
+
+
+def ring_points(k, crowded=False, seed=0):
+    """(points, slot of the centre): a centre with k partners RING_RADIUS away, evenly around it from 0.35 rad on.  The centre sits
+    one unit beside the corner of four cells, so the ring spreads over them and none holds more than four; crowded: in the middle
+    of a cell, which then holds all k + 1.  Slots are shuffled: the partners' order in a cell is not their indices'."""
+    cell = cell_geometry(1000.0, 10.0, RING_CAP[0])[1]
+    c = float(cell) * (4.5 if crowded else 4.0) + (0.0 if crowded else 1.0)
+    ang = 0.35 + 2.0 * np.pi * np.arange(k) / max(k, 1)
+    pts = np.array([(c, c)] + [(c + RING_RADIUS * np.cos(a), c + RING_RADIUS * np.sin(a)) for a in ang], "f4")
+    order = np.random.default_rng(40 + seed).permutation(k + 1)
+    return pts[order], int(np.nonzero(order == 0)[0][0])
+
+
+def ring_scenes():
+    """[(k, crowded)] of case_rings' scenes, in order."""
+    return [(k, False) for k in RING_PARTNERS] + [(max(RING_PARTNERS), True)]
+
+
+def case_rings(sb):
+    """Eight scenes of a centre with 0 .. 9 partners spread over four cells (the cells' path), and the fullest ring once more
+    inside one cell (the overflow's); tests/test_batch_grid_cpu.py asserts the counts and the cells' load."""
+    bufs = []
+    for n, (k, crowded) in enumerate(ring_scenes()):
+        pts6 = np.zeros((k + 1, 6), "f4")
+        pts6[:, :2] = ring_points(k, crowded, n)[0]
+        bufs.append(free_particles(sb, 2, RING_CAP, pts6, np.random.default_rng(60 + n).permutation(RING_CAP[0])[:k + 1]))
+    return dict(name="rings", layout=2, cap=RING_CAP, mode=bc.ALLPAIRS, bufs=bufs, program=[("step", 1), ("step", 3)])
+
+
 def substeps_of(program, subticks=64):
     return sum(op[1] * subticks if op[0] == "frame" else op[1] if op[0] == "step" else 0 for op in program)
 
 
 def finite_cases(sb):
-    return [case_pile(sb), case_edges(sb), case_rest(sb), case_mixed(sb)] + [case_geometry(sb, b, r) for b, r in GEOMETRIES]
+    return [case_pile(sb), case_edges(sb), case_rest(sb), case_mixed(sb), case_rings(sb)] + [case_geometry(sb, b, r) for b, r in GEOMETRIES]
 
 
 def make_oracle(orc, case, buf):

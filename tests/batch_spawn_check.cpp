@@ -1,4 +1,4 @@
-// batch_spawn_check.cpp -- csrc/sb_batch_spawn_math.h on the host (`make hostcheck`, under AddressSanitizer + UBSan and under
+// batch_spawn_check.cpp -- csrc/sb_batch_spawn_math.h and the contact test of csrc/sb_contact_cells.h on the host (`make hostcheck`, under AddressSanitizer + UBSan and under
 // ThreadSanitizer): the verdict of new-particle rows and the contact test of the blocked rule, read from a file of records and
 // printed one line per record for tests/test_batch_add_particles_cpu.py to compare with tests/batch_add_particles_ref.py.
 // Stand-alone: nothing here is loaded into Python.
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "sb_batch_spawn_math.h"
+#include "sb_contact_cells.h" // the contact test of the blocked rule
 
 #define REC_WORDS 12u
 
@@ -38,10 +39,9 @@ int main(int argc, char **argv)
     auto run = [&](size_t lo, size_t hi) {
         for (size_t i = lo; i < hi; i++) {
             const uint32_t *r = &rec[i * REC_WORDS];
-            float two_r;
-            const float thr = sbs::touch_threshold(sbs::word_as_float(r[9]), &two_r);
+            const SbTouchTest t = sb_touch_test(sbs::word_as_float(r[9]));
             verdict[i] = sbs::row_verdict(r, r[8] != 0u);
-            touches[i] = sbs::touch(sbs::word_as_float(r[1]), sbs::word_as_float(r[2]), sbs::word_as_float(r[10]), sbs::word_as_float(r[11]), thr, two_r);
+            touches[i] = sb_touch_xy(sbs::word_as_float(r[1]), sbs::word_as_float(r[2]), sbs::word_as_float(r[10]), sbs::word_as_float(r[11]), t.thr, t.two_r);
         }
     };
     std::thread t0(run, 0, n / 2), t1(run, n / 2, n);
@@ -50,16 +50,15 @@ int main(int argc, char **argv)
     for (size_t i = 0; i < n; i++) printf("%d %d\n", verdict[i], touches[i]);
     for (size_t j = 0; j < group; j++) {
         const uint32_t *rj = &rec[j * REC_WORDS];
-        float two_r;
-        const float thr = sbs::touch_threshold(sbs::word_as_float(rj[9]), &two_r);
+        const SbTouchTest t = sb_touch_test(sbs::word_as_float(rj[9]));
         const bool e_j = verdict[j] == sbs::SBS_CANDIDATE && touches[j] != 0;
         const bool b = verdict[j] == sbs::SBS_CANDIDATE &&
                        sbs::blocked(
                            (uint32_t)j, e_j, [&](uint32_t i) { return verdict[i]; }, [&](uint32_t i) { return touches[i] != 0; },
                            [&](uint32_t i) {
                                const uint32_t *ri = &rec[i * REC_WORDS];
-                               return sbs::touch(sbs::word_as_float(rj[1]), sbs::word_as_float(rj[2]), sbs::word_as_float(ri[1]), sbs::word_as_float(ri[2]), thr,
-                                                 two_r);
+                               return sb_touch_xy(sbs::word_as_float(rj[1]), sbs::word_as_float(rj[2]), sbs::word_as_float(ri[1]), sbs::word_as_float(ri[2]), t.thr,
+                                                  t.two_r);
                            });
         printf("%d%s", b ? 1 : 0, j + 1 == group ? "\n" : " ");
     }

@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "../softbody-webgpu_amd/csrc/sb_contact_cells.h" // sb_batch_cell_geometry: the cell side's rule
 #include "../softbody-webgpu_amd/csrc/sb_ray_walk.h"
 
 // The wrong walks, kept here and out of the library.  NoPad: no margin at all.  Tight: the exit bound of EXACT arithmetic,
@@ -58,24 +59,13 @@ struct Stats {
     uint64_t beam_beats_later_disc = 0, border_rows = 0, failures = 0;
 };
 
-// sb_batch_cell_geometry's rule (csrc/sb_batch.h needs HIP), restated
-static uint32_t cell_geometry(float bounds, float radius, uint32_t cap, float *cell)
-{
-    const float two_r = radius * 2.0f, cell_min = two_r * (1.0f + 1.0f / 64.0f);
-    if (!(cell_min >= 0x1p-60f && cell_min <= 0x1p60f) || !(bounds >= 0x1p-60f && bounds <= 0x1p60f)) return 0u;
-    const float per_side = bounds / cell_min;
-    const uint32_t g = per_side >= (float)cap ? cap : (per_side >= 1.0f ? (uint32_t)per_side : 1u);
-    *cell = std::max(cell_min, bounds / (float)g);
-    return g;
-}
-
 static Binned bin(const Scene &s, uint32_t cells_per_side)
 {
     Binned b;
     uint32_t particles = 0;
     for (const srw::Rec &c : s.recs) particles += !(c.index & SRW_KIND_BIT);
     float cell = 1.0f;
-    const uint32_t G = srw::ordinary(s.bounds, s.radius) ? cell_geometry(s.bounds, s.radius, cells_per_side ? cells_per_side : srw::default_cap(particles), &cell) : 0u;
+    const uint32_t G = srw::ordinary(s.bounds, s.radius) ? sb_batch_cell_geometry(s.bounds, s.radius, cells_per_side ? cells_per_side : srw::default_cap(particles), &cell) : 0u;
     b.g = srw::Grid{G ? G : 1u, G ? cell : s.bounds, s.bounds, s.radius};
     b.bins.resize((size_t)b.g.G * b.g.G + 1u);
     for (uint32_t i = 0; i < s.recs.size(); i++) {

@@ -93,7 +93,7 @@ def expected(sb, oracle):
 def test_every_case_runs_and_its_pair_list_holds_every_pair(expected):
     """max_pairs of every case is large enough at every point of its program; the lists are strictly ascending, the tails -1; the
     relation is symmetric: the per-particle counts sum to twice the pair counts."""
-    assert len(expected) == 20
+    assert len(expected) == 21
     for name, (case, exp) in expected.items():
         n, maxP, M = len(case["bufs"]), case["cap"][0], case["max_pairs"]
         assert sorted(exp) == list(range(-1, len(case["program"]))), name

@@ -120,3 +120,26 @@ def test_the_pile_bites(sb, oracle):
     assert most_contacts >= 5, most_contacts                   # more than the four one selection sweep takes
     assert fullest > gc.CELL_K, fullest                        # a bucket overflows: the fallback is due
     assert touched.mean() >= 0.30, touched.mean()
+
+
+def test_the_rings_are_what_they_say(sb):
+    """On the numpy reference of the contacts tests alone: the centre of scene n has exactly its k partners, and before the
+    first substep no cell of an uncrowded scene holds more than a bucket does, while the crowded scene's cell holds all ten."""
+    import batch_contacts_ref as cr
+    case = gc.case_rings(sb)
+    g, cell = gc.cell_geometry(1000.0, 10.0, gc.RING_CAP[0])
+    assert g == 12 and gc.CELL_K == 4 and len(case["bufs"]) == 9
+    assert [k for k, _ in gc.ring_scenes()] == [0, 1, 3, 4, 5, 7, 8, 9, 9]
+    for n, ((k, crowded), buf) in enumerate(zip(gc.ring_scenes(), case["bufs"])):
+        centre = gc.ring_points(k, crowded, n)[1]
+        idx, touch = cr.touching(buf, 10.0)
+        assert buf.particle_count == k + 1 and int(touch[centre].sum()) == k, (n, k, touch.sum(1))
+        assert not np.array_equal(np.argsort(idx), np.arange(k + 1)) or k < 2          # data indices are not in slot order
+        p = buf.particles[idx, :2]
+        cx, cy = (np.clip(np.floor(p[:, a] / cell), 0, g - 1).astype(int) for a in (0, 1))
+        assert np.abs(p / cell - np.round(p / cell)).min() * cell > 0.25, n          # nobody close enough to a border to be binned otherwise
+        load = np.bincount(cy * g + cx)
+        if crowded:
+            assert load.max() == k + 1 > gc.CELL_K
+        else:
+            assert load.max() <= gc.CELL_K and (k < 3 or np.count_nonzero(load) >= 3), (n, load[load > 0])

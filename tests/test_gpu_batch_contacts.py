@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 OFF, ALLPAIRS, GRID = 0, 1, 2
 NAMES = ("touch", "pairs", "counts")
 SENTINEL = -7
-N_CASES = 20
+N_CASES = 21
 _expected = {}
 
 

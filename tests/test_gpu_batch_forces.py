@@ -125,6 +125,16 @@ def test_contact_cases(sb, subticks):
     assert rows[0, d[14]].tolist()[2:] == [0, 0, 0, 0, 20.0, 1.0]                             # on one spot
 
 
+def test_rings_of_zero_to_nine_partners(sb):
+    import batch_grid_cases as gc
+    case = fc.case_rings(sb)
+    rows = check(sb, case)[0]
+    for n, ((k, crowded), buf) in enumerate(zip(gc.ring_scenes(), case["bufs"])):
+        assert rows[n, int(buf.mapping[gc.ring_points(k, crowded, n)[1]]), 7] == k, (n, k)
+    walked = check(sb, case, grid_min_particles=0xFFFFFFFF)[0]
+    assert np.array_equal(fr.words(walked), fr.words(rows))
+
+
 def test_every_collision_mode_and_threshold_gives_the_same_words(sb):
     case = fc.case_contacts(sb)
     outs = []

@@ -84,6 +84,16 @@ def test_lattice_at_rest_never_overflows(sb, oracle):
     be.destroy()
 
 
+def test_rings_take_the_cells_and_the_crowded_one_the_fallback(sb, oracle):
+    """A centre with 0, 1, 3, 4, 5, 7, 8 and 9 partners, spread over four cells; the ninth scene's ring in one cell."""
+    case = gc.case_rings(sb)
+    be = run(sb, oracle, case)
+    assert be.info("max_particles") == 64 and be.info("grid_min_particles") == 1 and be.info("contact_cells_per_side") == 12
+    assert be.info("cell_substeps") > 0 and be.info("cell_overflow_substeps") > 0
+    assert be.info("cell_substeps") + be.info("cell_overflow_substeps") == len(case["bufs"]) * gc.substeps_of(case["program"])
+    be.destroy()
+
+
 def test_cell_edges(sb, oracle):
     be = run(sb, oracle, gc.case_edges(sb))
     assert be.info("contact_cells_per_side") == 49 and be.info("cell_substeps") > 0
