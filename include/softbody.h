@@ -1520,6 +1520,62 @@ sb_status sb_nearest_device(sb_engine *e, const sb_nearest_options *opts, const 
 sb_status sb_nearest(sb_engine *e, const sb_nearest_options *opts, const sb_batch_near_point *points, uint32_t n_points, const int32_t *labels,
                      float *d, int32_t *hit, float *point, int32_t *within, int64_t *counts);
 
+/* ---- beam and contact forces of the whole scene of ONE engine, on the device, bit for bit ----
+ * sb_forces_device / sb_forces -- sb_batch_forces_device's question asked of an sb_engine: the forces the NEXT substep would compute
+ * from the CURRENT state, in the step's own float arithmetic (binary32, one rounding per operator, IEEE sqrt and divide), with nothing
+ * applied: no yield, no last_length update, no break flag, no particle moved.  The DEFINITION is the one above, word for word, for
+ * the one scene; what an engine adds is said here.
+ * Beam part.  It covers every caller beam slot of the latest upload that no delete pass has removed.  A pending break flag still
+ *   counts.  A beam removed by a delete pass or by a plan-keeping upload does not.  Each beam is evaluated as the step evaluates it
+ *   (compute.wgsl:103-130; sb_beam_eval) from the current positions of its endpoints, its current {target_length, last_length} --
+ *   the floats sb_read_state_device exports at this point of the stream -- and its {spring, damp} as uploaded.  tension[d], float at
+ *   beam DATA index d, is the beam's force_mag = (target_length - len) * spring + (last_length - len) * damp (the reference's sign:
+ *   positive pushes the endpoints apart); 0 where no evaluated beam lives, up to max_beams.  The four i32 contributions
+ *   (v_cvt_i32_f32: truncate, saturate, NaN -> 0) are summed per particle DATA index with wrapping 32-bit adds: beam_i32[i] =
+ *   {sum x, sum y}; {0, 0} where no particle lives, up to max_particles.  Integers: no summation order.
+ * Contact part.  For each particle, its partners (dist == 0 || dist < 2r: sb_contacts_device's test, whatever collision_mode is) are
+ *   taken in ASCENDING MAPPING-SLOT ORDER, the order of the step's collision loop, and summed from +0 by the batch's expressions
+ *   with the engine's current constants: friction, elasticity_coeff = (elasticity + 1) / 2 (sb_set_physics_constants or the
+ *   upload's metadata, as the next substep would take them), and inv_dt2 / dt^2 of sb_options.subticks (the product where dt^2 is a
+ *   power of two, the division where it is not).  With SB_FORCES_OTHER_BODY and labels only partners whose label differs from the
+ *   particle's are taken (labels: int32 [max_particles] at particle data indices, sb_bodies_device's or the caller's own; only
+ *   compared).  Without the flag the labels are not looked at.
+ *   rows[i]   SB_FORCE_WORDS floats at particle DATA index i, the batch's columns: 0, 1 beam_x, beam_y = (float)beam_i32 * 2^-16;
+ *             2, 3 push_x, push_y; 4, 5 impulse_x, impulse_y; 6 depth; 7 partners.  Eight +0 words where no particle lives, up to
+ *             max_particles.
+ *   counts    SB_FORCE_COUNT_WORDS int64: 0 particles, 1 beams evaluated, 2 particles with at least one partner taken, 3 beams
+ *             whose force_mag is not finite.
+ * A scene that fits a batch gives exactly the batch's rows, beam_i32 and tension for that scene.  With gravity 0, drag 0 and everything
+ * at rest, forces then one substep: v == (push + beam) * time_step and stress == tension / 20, bit for bit.
+ * Each output may be NULL, not all of them; every word of one that is passed is written.
+ * sb_forces_device only ENQUEUES on the engine's stream -- two clears, a launch over the beams, sb_contacts_device's counting sort by
+ * cell with records keyed by mapping slot, a launch over the sorted records, the rows where nobody lives, the counts -- reads nothing
+ * back, no workgroup waits for another, and it waits for nothing but the one table build after an upload (the shared scene tables
+ * with two more planes: mapping slot -> particle, {spring, damp} per beam slot; sb_cut_device's rows).  It only READS the engine:
+ * frame, forces, frame equals frame, frame bit for bit; two calls give the same bits.  It works on every path, layout and collision
+ * mode.  sb_forces is the host-copy convenience: labels from host memory, the same launches, the outputs copied back; it waits.
+ * Errors, before anything touches a device: SB_ERR_INVALID for a NULL handle, a struct_size that is neither 0 nor the struct's, an
+ * unknown flag bit, a nonzero reserved word, SB_FORCES_OTHER_BODY without labels, all outputs NULL, labels / rows / beam_i32 / tension
+ * not 4-byte or counts not 8-byte aligned; SB_ERR_STATE before an upload; SB_ERR_UNSUPPORTED on an engine with ghost zones or peers
+ * configured, and where the cell side is no ordinary number in a scene of more than 4096 particles (sb_contacts_device's rule; at or
+ * below 4096 every pair is tested).  sb_get_info: "forces_cells_per_side" (of the scene as it is; 1: all pairs),
+ * "forces_table_build_us" (host time of the last build of the tables the latest call read), "forces_kernel_vgprs",
+ * "forces_kernel_scratch_bytes". */
+#define SB_FORCE_WORDS 8u              /* floats of a per-particle row (SB_BATCH_FORCE_WORDS) */
+#define SB_FORCE_COUNT_WORDS 4u        /* int64 words of counts */
+#define SB_FORCES_OTHER_BODY 1u        /* only partners whose label differs from the particle's are taken */
+typedef struct sb_forces_options {
+    uint32_t struct_size;    /* = sizeof(sb_forces_options); 0 or a NULL pointer = all defaults: no flags */
+    uint32_t flags;          /* SB_FORCES_OTHER_BODY */
+    uint32_t reserved[6];    /* zero */
+} sb_forces_options;
+sb_status sb_forces_device(sb_engine *e, const sb_forces_options *opts, const void *device_labels_i32 /* [max_particles] or NULL */,
+                           void *device_rows_f32 /* [max_particles][SB_FORCE_WORDS] float or NULL */,
+                           void *device_beam_i32 /* [max_particles][2] or NULL */, void *device_tension_f32 /* [max_beams] float or NULL */,
+                           void *device_counts_i64 /* [SB_FORCE_COUNT_WORDS] or NULL */);
+sb_status sb_forces(sb_engine *e, const sb_forces_options *opts, const int32_t *labels, float *rows, int32_t *beam_i32, float *tension,
+                    int64_t *counts);
+
 /* scene i back into host buffers exactly as sb_load_buffers returns a single engine in the same state (counts in the metadata,
  * the mapping after the delete passes' stable in-place compactions, beam records with strain / stress; only records reachable
  * through the uploaded mapping are written; any pointer may be NULL).  SB_ERR_STATE for a scene never uploaded. */

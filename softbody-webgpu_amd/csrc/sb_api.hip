@@ -2045,6 +2045,7 @@ sb_status sb_get_info(sb_engine *e, const char *key, uint64_t *value)
     else if (sbg_info(e, key, value)) {} // sb_graph.hip: "graph_kernel_vgprs", "graph_kernel_scratch_bytes", "graph_table_build_us"
     else if (sbw_info(e, key, value)) {} // sb_raycast.hip: "raycast_cells_per_side", "raycast_kernel_vgprs", "raycast_kernel_scratch_bytes", "raycast_table_build_us"
     else if (sbv_info(e, key, value)) {} // sb_nearest.hip: "nearest_cells_per_side", "nearest_max_rings", "nearest_kernel_vgprs", "nearest_kernel_scratch_bytes"
+    else if (sbfe_info(e, key, value)) {} // sb_forces.hip: "forces_cells_per_side", "forces_table_build_us", "forces_kernel_vgprs", "forces_kernel_scratch_bytes"
     else SB_FAIL(e, SB_ERR_INVALID, "sb_get_info: unknown key '%s'", key);
     return SB_OK;
 }

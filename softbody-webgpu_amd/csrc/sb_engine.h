@@ -334,5 +334,7 @@ bool sbg_info(sb_engine *e, const char *key, uint64_t *value); // its sb_get_inf
 bool sbw_info(sb_engine *e, const char *key, uint64_t *value); // its sb_get_info keys (false: not one of them)
 // sb_nearest.hip
 bool sbv_info(sb_engine *e, const char *key, uint64_t *value); // its sb_get_info keys (false: not one of them)
+// sb_forces.hip
+bool sbfe_info(sb_engine *e, const char *key, uint64_t *value); // its sb_get_info keys (false: not one of them)
 // sb_api.hip
 sb_status sb_grid_reset_hash(sb_engine *e); // the spatial hash forgets every position it holds (every upload, through reset_run_state; particle import)

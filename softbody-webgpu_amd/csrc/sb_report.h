@@ -1,5 +1,5 @@
 // sb_report.h -- what the engine's state calls (sb_state_io.hip), its four whole-scene reports (sb_summary.hip, sb_bodies.hip,
-// sb_contacts.hip, sb_body_summary.hip), the cut (sb_cut.hip), the graph (sb_graph.hip), the ray casts (sb_raycast.hip) and the proximity queries (sb_nearest.hip) share: the owner of their device
+// sb_contacts.hip, sb_body_summary.hip), the cut (sb_cut.hip), the graph (sb_graph.hip), the ray casts (sb_raycast.hip), the proximity queries (sb_nearest.hip) and the forces (sb_forces.hip) share: the owner of their device
 // buffers, the preflight of a call, the host mirror of a report, the scene tables of the latest upload, the exclusive scan and
 // the wave's run counter.  What only one report uses stays in its file.
 #pragma once
@@ -19,7 +19,7 @@ struct SbDevBuf {
 
 // every device buffer the five files keep between calls, by use
 enum SbReportBuf {
-    SBQ_B_PINV, SBQ_B_TAB,                                                         // the shared scene tables (sbq_need)
+    SBQ_B_PINV, SBQ_B_TAB, SBQ_B_ISLOT, SBQ_B_MAT,                                 // the shared scene tables (sbq_need)
     SBS_B_SLOT, SBS_B_IMP_ROW, SBS_B_IMP_REST, SBS_B_CKPT,                         // sb_state_io.hip
     SBM_B_BLEAF, SBM_B_PART, SBM_B_STAT, SBM_B_OUT,                                // sb_summary.hip
     SBD_B_PARENT, SBD_B_SIZES, SBD_B_ACC,                                          // sb_bodies.hip
@@ -29,6 +29,7 @@ enum SbReportBuf {
     SBG_B_SCRATCH, SBG_B_ENDS, SBG_B_ROWPTR, SBG_B_NBR, SBG_B_COUNTS,              // sb_graph.hip
     SBW_B_SCRATCH, SBW_B_RAYS, SBW_B_LABELS, SBW_B_T, SBW_B_HIT, SBW_B_COUNTS,      // sb_raycast.hip
     SBV_B_SCRATCH, SBV_B_POINTS, SBV_B_LABELS, SBV_B_D, SBV_B_HIT, SBV_B_POINT, SBV_B_WITHIN, SBV_B_COUNTS, // sb_nearest.hip
+    SBF_B_CELLS, SBF_B_BSUM, SBF_B_SORTED, SBF_B_CELL_OF, SBF_B_BEAM, SBF_B_ACC, SBF_B_LABELS, SBF_B_ROWS, SBF_B_BEAM_OUT, SBF_B_TENSION, // sb_forces.hip
     SBQ_NBUF
 };
 
@@ -38,6 +39,8 @@ struct SbStateIoState {
     SbDevBuf buf[SBQ_NBUF];
     // the shared scene tables, in two parts, the second's fourth plane on its own (sbq_need)
     bool part_valid = false, beam_valid = false, copy_valid = false;
+    bool islot_valid = false, mat_valid = false; // sb_forces.hip's two planes: per particle mapping slot the internal particle (SBQ_B_ISLOT); per caller beam slot {spring, damp} (SBQ_B_MAT)
+    double islot_ms = 0.0, mat_ms = 0.0;
     uint32_t np = 0, P = 0, nslots = 0; // highest particle data index in use + 1; particles; the caller's beam slots
     std::vector<uint32_t> h_pinv;       // part 1 on the host: part 2's endpoint check reads it
     double part_ms = 0.0, beam_ms = 0.0, copy_ms = 0.0; // host time of each one's last build (copy_ms 0: built with the other planes)
@@ -65,11 +68,12 @@ struct SbStateIoState {
     uint32_t cut_nd = 0;                      // highest beam data index among the rows + 1 (sb_graph.hip)
     double graph_build_ms = 0.0;              // "graph_table_build_us"
     double ray_build_ms = 0.0;                // "raycast_table_build_us"
+    double for_build_ms = 0.0;                // "forces_table_build_us"
 
-    void invalidate() { part_valid = beam_valid = copy_valid = valid = bleaf_valid = imp_valid = cut_valid = false; } // every table of the scene: the one place
+    void invalidate() { part_valid = beam_valid = copy_valid = islot_valid = mat_valid = valid = bleaf_valid = imp_valid = cut_valid = false; } // every table of the scene: the one place
 };
 
-enum { SBQ_PARTICLES = 1u, SBQ_BEAMS = 2u, SBQ_COPIES = 4u }; // the parts of the shared scene tables; SBQ_COPIES: part 2's fourth plane
+enum { SBQ_PARTICLES = 1u, SBQ_BEAMS = 2u, SBQ_COPIES = 4u, SBQ_SLOTS = 8u, SBQ_MATERIALS = 16u }; // the parts of the shared scene tables; SBQ_COPIES: part 2's fourth plane; SBQ_SLOTS, SBQ_MATERIALS: sb_forces.hip's planes
 
 inline const char *sbq_options_name(const sb_summary_options *) { return "sb_summary_options"; }
 inline const char *sbq_options_name(const sb_bodies_options *) { return "sb_bodies_options"; }
@@ -79,6 +83,7 @@ inline const char *sbq_options_name(const sb_cut_options *) { return "sb_cut_opt
 inline const char *sbq_options_name(const sb_graph_options *) { return "sb_graph_options"; }
 inline const char *sbq_options_name(const sb_raycast_options *) { return "sb_raycast_options"; }
 inline const char *sbq_options_name(const sb_nearest_options *) { return "sb_nearest_options"; }
+inline const char *sbq_options_name(const sb_forces_options *) { return "sb_forces_options"; }
 
 sb_status sbq_ready(sb_engine *e, const char *what, const char *why); // loaded, no ranks (`why`: the call's parenthesis); the device; e->sio
 

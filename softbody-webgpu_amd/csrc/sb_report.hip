@@ -141,6 +141,30 @@ sb_status sbq_need(sb_engine *e, const char *what, uint32_t parts)
         if (planes & sbq::COPY) s.copy_valid = true, s.copy_ms = (planes & sbq::ENDS) ? 0.0 : sbq_ms_since(t0);
         if (planes & sbq::ENDS) s.beam_valid = true, s.beam_ms = sbq_ms_since(t0);
     }
+    if ((parts & SBQ_SLOTS) && !s.islot_valid) { // sb_forces.hip: mapping slot -> internal particle, the sibling of part 1
+        const auto t0 = std::chrono::steady_clock::now();
+        if (e->h_pslot.size() != e->P) SB_FAIL(e, SB_ERR_STATE, "%s: host shadows of the scene are inconsistent", what);
+        std::vector<uint32_t> islot;
+        const sbq::Defect d = sbq::invert_slots(e->h_pslot.data(), e->P, islot);
+        if (d != sbq::OK) SB_FAIL(e, SB_ERR_STATE, "%s: %s", what, sbq::defect_text(d));
+        SB_TRY(s.buf[SBQ_B_ISLOT].grow(e, islot.size() * sizeof(uint32_t)));
+        SB_HIP(e, hipMemcpyAsync(s.buf[SBQ_B_ISLOT].p, islot.data(), islot.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+        SB_HIP(e, hipStreamSynchronize(e->stream)); // (the host vector goes out of scope)
+        s.islot_valid = true;
+        s.islot_ms = sbq_ms_since(t0);
+    }
+    if ((parts & SBQ_MATERIALS) && !s.mat_valid) { // sb_forces.hip: {spring, damp} per caller beam slot
+        const auto t0 = std::chrono::steady_clock::now();
+        if (e->h_beams.size() != e->B) SB_FAIL(e, SB_ERR_STATE, "%s: host shadows of the scene are inconsistent", what);
+        std::vector<float> mat;
+        const sbq::Defect d = sbq::beam_materials(e->h_user_slot.empty() ? nullptr : e->h_user_slot.data(), sb_user_beams(e), e->h_beams.data(), e->B, mat);
+        if (d != sbq::OK) SB_FAIL(e, SB_ERR_STATE, "%s: %s", what, sbq::defect_text(d));
+        SB_TRY(s.buf[SBQ_B_MAT].grow(e, mat.size() * sizeof(float)));
+        SB_HIP(e, hipMemcpyAsync(s.buf[SBQ_B_MAT].p, mat.data(), mat.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
+        SB_HIP(e, hipStreamSynchronize(e->stream)); // (the host vector goes out of scope)
+        s.mat_valid = true;
+        s.mat_ms = sbq_ms_since(t0);
+    }
     return SB_OK;
 }
 

@@ -1,7 +1,8 @@
 // sb_report_tables.h -- the scene tables of the latest upload that the engine's whole-scene reports read (sb_report.hip uploads
 // what these return).  Part 1: per particle DATA index below np (the highest in use + 1) the internal particle
 // holding it (h_pidx inverted; SBQ_NONE where none lives).  Part 2: per caller beam slot of the latest upload the four planes
-// {data index of A, data index of B, engine slot, the copy read back for it}; the fourth only once a report asks for it.  Everything a kernel will index with is checked here,
+// {data index of A, data index of B, engine slot, the copy read back for it}; the fourth only once a report asks for it.  Two more planes for sb_forces.hip, each on first use: per particle mapping SLOT the
+// internal particle holding it (h_pslot inverted), and per caller beam slot its {spring, damp} as uploaded.  Everything a kernel will index with is checked here,
 // once: a defect names the first kind of fault found.  Header-only and HIP-free: tests/report_tables_check.cpp runs it under
 // AddressSanitizer / ThreadSanitizer.
 #pragma once
@@ -17,7 +18,7 @@
 
 namespace sbq {
 
-enum Defect { OK = 0, BAD_PARTICLE_INDEX, BAD_BEAM_SLOT, BAD_ENDPOINT, BAD_COPY };
+enum Defect { OK = 0, BAD_PARTICLE_INDEX, BAD_BEAM_SLOT, BAD_ENDPOINT, BAD_COPY, BAD_PARTICLE_SLOT };
 
 inline const char *defect_text(Defect d)
 {
@@ -26,6 +27,7 @@ inline const char *defect_text(Defect d)
     case BAD_BEAM_SLOT: return "beam slot outside the scene";
     case BAD_ENDPOINT: return "beam endpoint outside the scene";
     case BAD_COPY: return "beam copy outside the scene";
+    case BAD_PARTICLE_SLOT: return "particle mapping slot outside the scene";
     default: return "";
     }
 }
@@ -83,6 +85,41 @@ inline Defect beam_planes(unsigned planes, const uint32_t *user_slot, size_t nsl
             }
             if (ends) t[u] = h.da, t[n + u] = h.db, t[2 * n + u] = slot;
             if (copy) tc[u] = copy_of_slot[slot];
+        }
+    });
+    return (Defect)bad.load();
+}
+
+// islot[s] = the internal particle i with pslot[i] == s, s < P (the sibling of invert_particles' table: the particle mapping slots of
+// an upload are 0 .. P - 1, each once; one entry of SBQ_NONE for an empty scene).  A slot outside 0 .. P - 1, or one that two
+// particles claim, is a defect: sb_forces_device fetches the partners of a particle through this table.
+inline Defect invert_slots(const uint32_t *pslot, size_t P, std::vector<uint32_t> &islot)
+{
+    islot.assign(std::max<size_t>(P, 1), SBQ_NONE);
+    uint32_t *const to = islot.data();
+    for (size_t i = 0; i < P; i++) {
+        const uint32_t s = pslot[i];
+        if (s >= P || to[s] != SBQ_NONE) return BAD_PARTICLE_SLOT;
+        to[s] = (uint32_t)i;
+    }
+    return OK;
+}
+
+// mat[2 u], mat[2 u + 1] = {spring, damp} of caller beam slot u < nslots as uploaded (SbHostBeam::f[3], f[4]: materials never change
+// between uploads), n = max(nslots, 1) pairs; user_slot as in beam_planes.  Checked: the slot is < B.
+inline Defect beam_materials(const uint32_t *user_slot, size_t nslots, const SbHostBeam *beams, uint32_t B, std::vector<float> &mat)
+{
+    mat.assign(2 * std::max<size_t>(nslots, 1), 0.0f);
+    float *const m = mat.data();
+    std::atomic<uint32_t> bad{OK};
+    sbt::parallel_ranges(nslots, 1 << 16, [&](size_t u0, size_t u1) {
+        for (size_t u = u0; u < u1; u++) {
+            const uint32_t slot = user_slot ? user_slot[u] : (uint32_t)u;
+            if (slot >= B) {
+                note(bad, BAD_BEAM_SLOT);
+                continue;
+            }
+            m[2 * u] = beams[slot].f[3], m[2 * u + 1] = beams[slot].f[4];
         }
     });
     return (Defect)bad.load();

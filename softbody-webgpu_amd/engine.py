@@ -114,6 +114,15 @@ CONTACT_COUNT_WORDS = 4      # SB_CONTACT_COUNT_WORDS: the int64 counts of conta
 CONTACTS_OTHER_BODY = 1      # SB_CONTACTS_OTHER_BODY
 
 
+class SbForcesOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 6)]
+
+
+FORCE_WORDS = 8              # SB_FORCE_WORDS: the floats of a row of forces(); batch.FORCE_FIELDS names them
+FORCE_COUNT_WORDS = 4        # SB_FORCE_COUNT_WORDS: the int64 counts of forces(); batch.FORCE_COUNT_FIELDS names them
+FORCES_OTHER_BODY = 1        # SB_FORCES_OTHER_BODY
+
+
 class SbBodySummaryOptions(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 5), ("max_rows", ctypes.c_uint64)]
 
@@ -191,7 +200,7 @@ def device_shapes(shapes, dev, ndim=2):
 
 
 def __getattr__(name):
-    if name in ("SUMMARY_FIELDS", "BODY_FIELDS", "BODY_SUMMARY_FIELDS", "CONTACT_TOUCH_FIELDS", "CONTACT_COUNT_FIELDS", "WALL_LEFT", "WALL_RIGHT", "WALL_LOW",
+    if name in ("SUMMARY_FIELDS", "BODY_FIELDS", "BODY_SUMMARY_FIELDS", "CONTACT_TOUCH_FIELDS", "CONTACT_COUNT_FIELDS", "FORCE_FIELDS", "FORCE_COUNT_FIELDS", "Forces", "WALL_LEFT", "WALL_RIGHT", "WALL_LOW",
                 "WALL_HIGH"):  # the batch's words: its names are not copied (batch.py imports this module)
         from . import batch
         return getattr(batch, name)
@@ -327,6 +336,8 @@ def load_library():
     L.sb_bodies.argtypes = [vp, ctypes.POINTER(SbBodiesOptions), vp, vp, vp]
     L.sb_contacts_device.argtypes = [vp, ctypes.POINTER(SbContactsOptions), vp, vp, vp, vp]
     L.sb_contacts.argtypes = [vp, ctypes.POINTER(SbContactsOptions), vp, vp, vp, vp]
+    L.sb_forces_device.argtypes = [vp, ctypes.POINTER(SbForcesOptions), vp, vp, vp, vp, vp]
+    L.sb_forces.argtypes = [vp, ctypes.POINTER(SbForcesOptions), vp, vp, vp, vp, vp]
     L.sb_body_summary_device.argtypes = [vp, ctypes.POINTER(SbBodySummaryOptions), vp, vp, vp, vp]
     L.sb_body_summary.argtypes = [vp, ctypes.POINTER(SbBodySummaryOptions), vp, vp, vp, vp]
     f32 = ctypes.c_float
@@ -1031,6 +1042,69 @@ class Engine(DeviceBinding):
         self._check(load_library().sb_contacts(self._h, ctypes.byref(o), None if lab is None else _ptr(lab), _ptr(touch),
                                                _ptr(plist) if int(pairs) else None, _ptr(counts)))
         return touch, counts, plist
+
+    # ---- beam and contact forces of the whole scene (sb_forces_device / sb_forces)
+
+    @staticmethod
+    def _forces_options(other_body):
+        o = SbForcesOptions()
+        o.struct_size = ctypes.sizeof(SbForcesOptions)
+        o.flags = FORCES_OTHER_BODY if other_body else 0
+        return o
+
+    def forces(self, labels=None, other_body=False, rows=True, beam_i32=None, tension=None, counts=None):
+        """How hard every beam pulls and every contact pushes in the whole scene, found on the GPU: the forces the NEXT substep
+        would compute from the CURRENT state, in the step's own arithmetic, bit for bit (include/softbody.h states the definition:
+        BatchEngine.forces()' for one scene).  Nothing is applied: no yield, no last_length update, no break flag, no particle moved.
+        Returns batch.Forces, a named tuple of tensors on the engine's device (None where not asked for):
+        rows [max_particles, 8] float32 at particle DATA indices (FORCE_FIELDS names the columns): beam_x, beam_y, the sum of the beam
+        forces on the particle (the fixed-point sum times 2^-16, what the integration adds to the acceleration); push_x, push_y, what
+        the contacts add to the acceleration; impulse_x, impulse_y, what they add to the velocity; depth, the largest overlap 2r -
+        dist among the partners; partners, their number.  Eight zeros where no particle lives.
+        beam_i32 [max_particles, 2] int32: the fixed-point beam force sums themselves (wrapping, saturating).
+        tension [max_beams] float32 at beam DATA indices (the rows of state_tensors()'s beams): the beam's force_mag, positive when the
+        beam is compressed and pushes its endpoints apart, negative when it is stretched and pulls; 0 where no live beam is.  A beam
+        with a pending break flag still pulls; one a delete pass or an upload removed does not.
+        counts [4] int64 (FORCE_COUNT_FIELDS): particles, beams evaluated, particles with a partner, beams whose tension is not finite.
+        labels: None, True (self.bodies() is called first, on the same stream, and its labels are used), or an int32 tensor / device
+        pointer of [max_particles] labels of the caller's own; with other_body=True only partners whose label differs from the
+        particle's are taken: what another body does to this one.  rows / beam_i32 / tension / counts: True (a new tensor), None /
+        False (not wanted), a device pointer (int) or a contiguous torch tensor to write into; every word of what is asked for is
+        written.  Only reads the engine, only enqueues; torch's current stream is ordered after it."""
+        from .batch import Forces
+        maxp, maxb = self.max_particles, self.max_beams
+        wanted = [x is not False and x is not None for x in (rows, beam_i32, tension, counts)]
+        given = [None if isinstance(x, bool) else x for x in (rows, beam_i32, tension, counts)]   # (True: a new tensor)
+        outs, ptrs, tensors = self._bind("forces", [
+            ("rows", given[0], wanted[0], (maxp, FORCE_WORDS), "float32"),
+            ("beam_i32", given[1], wanted[1], (maxp, 2), "int32"),
+            ("tension", given[2], wanted[2], (maxb,), "float32"),
+            ("counts", given[3], wanted[3], (FORCE_COUNT_WORDS,), "int64"),
+            ("labels", (lambda: self.bodies(counts=False)[0]) if labels is True else None if labels is False else labels,
+             labels is not None and labels is not False, (maxp,), "int32")])
+        o = self._forces_options(other_body)
+        vp = ctypes.c_void_p
+        self._ordered(tensors, lambda: load_library().sb_forces_device(self._h, ctypes.byref(o), vp(ptrs[4]), *[vp(p) for p in ptrs[:4]]))
+        return Forces(*outs[:4])
+
+    def forces_host(self, labels=None, other_body=False):
+        """The same without torch: batch.Forces of numpy arrays (rows float32 [max_particles, 8], beam_i32 int32 [max_particles, 2],
+        tension float32 [max_beams], counts int64 [4]); labels: None or an int32 array of [max_particles] labels.  Waits for the
+        stream."""
+        from .batch import Forces
+        rows = np.empty((self.max_particles, FORCE_WORDS), dtype=np.float32)
+        beam_i32 = np.empty((self.max_particles, 2), dtype=np.int32)
+        tension = np.empty(self.max_beams, dtype=np.float32)
+        counts = np.empty(FORCE_COUNT_WORDS, dtype=np.int64)
+        lab = None
+        if labels is not None:
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.size < self.max_particles:
+                raise ValueError("forces_host: labels needs max_particles entries")
+        o = self._forces_options(other_body)
+        self._check(load_library().sb_forces(self._h, ctypes.byref(o), None if lab is None else _ptr(lab), _ptr(rows), _ptr(beam_i32),
+                                             _ptr(tension), _ptr(counts)))
+        return Forces(rows, beam_i32, tension, counts)
 
     # ---- statistics per body of the whole scene (sb_body_summary_device / sb_body_summary; DESIGN.md 5.21)
 
