@@ -1117,6 +1117,66 @@ sb_status sb_batch_body_summary_device(sb_batch *b,
         void *device_rows_f32         /* [n_scenes][max_rows][SB_BATCH_BODY_SUMMARY_WORDS] float or NULL */,
         void *device_rank_i32         /* [n_scenes][max_particles] int32 or NULL */);
 
+/* ---- the pose of every body against a reference shape, reproducible bit for bit ----
+ * sb_batch_pose_device -- how is every GROUP of particles of every scene turned, how fast does it spin, how far is it bent out of
+ * shape?  One row of SB_BATCH_POSE_WORDS floats and one of SB_BATCH_POSE_MOMENT_WORDS doubles per group, in ONE launch: the
+ * centroids and the moments of the 2-D shape-matching fit of the group's current positions against a REFERENCE configuration.  It
+ * only ENQUEUES on the batch's stream and only READS the batch: frame, pose, frame equals frame, frame bit for bit.
+ * Groups, ranking, rank, empty rows: sb_batch_body_summary_device's, word for word.  labels[s][i] is read at every particle DATA
+ *   index i of scene s (never at a data index that holds no particle); a value g with 0 <= g < max_particles puts particle i into
+ *   group g, any other value into no group.  The non-empty groups of a scene are ranked by particles descending, then label
+ *   ascending: rows[s][k] and moments[s][k] belong to the group of rank k -- the group of row k of sb_batch_body_summary_device
+ *   for the same labels --, rows behind the last group are the EMPTY ROW; rank[s][i] is the rank of particle i's group, however
+ *   large, -1 at a data index that holds no particle or a particle in no group.  Every word of a non-NULL output is written.
+ * Reference: with device_ref_f32, the reference position {X, Y} of particle i is ref[s][i], at its DATA index.  With NULL it is the
+ *   x and y of particle i's record in the scene's RESET state (its latest upload, sb_batch_checkpoint_device or
+ *   sb_batch_fork_device), and only a particle that the reset state holds has one: a particle added by
+ *   sb_batch_add_particles_device since then has no reference until a checkpoint.  Right after a checkpoint or a reset, before any
+ *   step, every reference equals the current position.
+ * Matched members: a member of a group is FINITE when all six floats of its record are (position, velocity, acceleration: the
+ *   rule of sb_batch_summary_device's word 4).  It is MATCHED when it is finite and has a reference whose two floats are finite.
+ *   Everything below word 4 of a row counts all members; every sum is over the matched members alone.
+ * Sums: eleven, in double, each pinned as sb_batch_summary_device pins its sums, restricted to the group's matched members: leaf i
+ *   is the value at DATA index i if particle i is a matched member of the group, else +0.0; i = 0 .. W-1, W the smallest power of
+ *   two >= max_particles; for h = W/2 .. 1: s[i] += s[i + h]; a sum that is zero is written as +0.0.  With every float cast to
+ *   double first (so every product is exact and a leaf has one rounding) the leaves of a particle at (x, y) with velocity
+ *   (vx, vy) and reference (X, Y) are
+ *     x, y, X, Y, vx, vy,   D = x*X + y*Y,   C = X*y - Y*x,   Q = x*x + y*y,   Q0 = X*X + Y*Y,   L = x*vy - y*vx
+ *   and their sums are written Sx, Sy, SX, SY, Svx, Svy, D, C, Q, Q0, L below.
+ * Derived, in double, one rounding per operator, exactly these expressions, n the number of matched members as a double:
+ *     a  = D  - (Sx*SX + Sy*SY) / n        b  = C - (SX*Sy - SY*Sx) / n
+ *     I  = Q  - (Sx*Sx + Sy*Sy) / n        I0 = Q0 - (SX*SX + SY*SY) / n
+ *     Lc = L  - (Sx*Svy - Sy*Svx) / n
+ *   a and b are the dot and cross moments about the two centroids: the rotation that best carries the reference onto the current
+ *   shape is atan2(b, a).  I and I0 are the moments of inertia (unit masses) of the current and the reference shape about their
+ *   centroids, Lc the angular momentum about the current centroid.  The call takes no square root and no arc tangent.
+ * moments[s][k] = {a, b, I, I0, Lc, n, 0, 0}.  With n == 0 -- the empty row included -- words 0 .. 4 are the quiet NaN
+ *   0x7FF8000000000000, n and the padding 0.
+ * rows[s][k], every float rounded once from its double:
+ *    0  particles of the group (finite or not)       1  the label (<= 1023: exact as a float)
+ *    2  matched members n                            3  members that are not matched (word 0 - word 2)
+ *    4, 5  Sx / n, Sy / n: the current centroid      6, 7  SX / n, SY / n: the reference's centroid
+ *    8, 9  Svx / n, Svy / n: the mean velocity      10, 11  a, b
+ *   12, 13  I, I0                                   14  Lc
+ *   15  Lc / I if I > 0, else NaN: the angular velocity
+ *   16  I / I0 if I0 > 0, else NaN: the squared stretch
+ *   17 .. 23  0
+ *   With n == 0 words 4 .. 16 are the quiet NaN 0x7FC00000.  The EMPTY ROW: words 0, 2, 3 and 17 .. 23 are 0, word 1 is -1, words
+ *   4 .. 16 NaN.  A scene never uploaded, and a scene without particles, give empty rows and rank -1.
+ * Consequence: where every finite member of a group is matched, words 4, 5, 8, 9 equal words 6 .. 9 of the same row of
+ * sb_batch_body_summary_device by their bits.
+ * Errors: SB_ERR_INVALID for a NULL handle, NULL labels, rows, moments and rank all NULL, max_rows of 0 or above max_particles, a
+ * pointer that is not 4-byte aligned, moments that is not 8-byte aligned -- before anything touches a device. */
+#define SB_BATCH_POSE_WORDS 24u
+#define SB_BATCH_POSE_MOMENT_WORDS 8u
+sb_status sb_batch_pose_device(sb_batch *b,
+        const void *device_labels_i32 /* [n_scenes][max_particles] int32, required */,
+        const void *device_ref_f32    /* [n_scenes][max_particles][2] float {X, Y} at particle DATA indices, or NULL: the reset state */,
+        uint32_t max_rows             /* 1 .. max_particles */,
+        void *device_rows_f32         /* [n_scenes][max_rows][SB_BATCH_POSE_WORDS] float or NULL */,
+        void *device_moments_f64      /* [n_scenes][max_rows][SB_BATCH_POSE_MOMENT_WORDS] double or NULL; 8-byte aligned */,
+        void *device_rank_i32         /* [n_scenes][max_particles] int32 or NULL */);
+
 /* ---- particle and wall contacts of every scene, reported on the device ----
  * sb_batch_contacts_device -- who touches whom, and who touches a wall, in ONE launch.
  * Particle set: the particles of a scene are its slots 0 .. metadata.particle_i_c - 1, named by their DATA index like the rows of
@@ -1636,7 +1696,8 @@ sb_status sb_batch_get_stream(sb_batch *b, void **hip_stream);
  * "raycast_lds_bytes" (likewise), "raycast_kernel_vgprs", "raycast_kernel_scratch_bytes"; sb_batch_nearest_device: "near_max",
  *  "near_hit_words", "near_count_words", "nearest_lds_bytes" (likewise), "nearest_kernel_vgprs", "nearest_kernel_scratch_bytes";
  * sb_batch_forces_device: "force_words", "force_count_words", "forces_lds_bytes" (likewise), "forces_cells_per_side",
- * "forces_kernel_vgprs", "forces_kernel_scratch_bytes" */
+ * "forces_kernel_vgprs", "forces_kernel_scratch_bytes"; sb_batch_pose_device: "pose_words" (SB_BATCH_POSE_WORDS),
+ * "pose_moment_words" (SB_BATCH_POSE_MOMENT_WORDS), "pose_lds_bytes" (likewise), "pose_kernel_vgprs", "pose_kernel_scratch_bytes" */
 sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value);
 const char *sb_batch_last_error(const sb_batch *b);
 

@@ -27,7 +27,8 @@ def __getattr__(name):
     if name in ("GRAPH_COUNT_FIELDS", "GRAPH_MATERIAL_FIELDS",  # the words of BatchEngine.graph()'s counts and material rows
                 "RAY_HIT_FIELDS", "RAY_COUNT_FIELDS", "ray_rows",  # BatchEngine.raycast()
                 "NEAR_HIT_FIELDS", "NEAR_WITHIN_FIELDS", "NEAR_COUNT_FIELDS", "point_rows",  # BatchEngine.nearest()
-                "SPAWN_EMPTY", "SPAWN_INVALID", "SPAWN_BLOCKED", "SPAWN_FULL", "SPAWN_COUNT_FIELDS"):  # BatchEngine.add_particles()
+                "SPAWN_EMPTY", "SPAWN_INVALID", "SPAWN_BLOCKED", "SPAWN_FULL", "SPAWN_COUNT_FIELDS",  # BatchEngine.add_particles()
+                "POSE_FIELDS", "POSE_MOMENT_FIELDS", "pose_fit"):  # BatchEngine.pose()
         from . import batch
         return getattr(batch, name)
     raise AttributeError(name)

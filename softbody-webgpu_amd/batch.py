@@ -31,6 +31,16 @@ BODY_SUMMARY_FIELDS = ("particles", "live_beams", "label", "pending_breaks", "no
                        "mean_x", "mean_y", "mean_vx", "mean_vy", "min_x", "min_y", "max_x", "max_y", "kinetic_energy", "max_speed_sq",
                        "max_strain", "max_stress", "min_stress", "angular_momentum", "reserved_20", "reserved_21", "reserved_22",
                        "reserved_23")
+POSE_WORDS, POSE_MOMENT_WORDS = 24, 8                 # SB_BATCH_POSE_WORDS, SB_BATCH_POSE_MOMENT_WORDS
+# the words of a row of pose() and of its moments, in order (include/softbody.h, sb_batch_pose_device)
+POSE_FIELDS = ("particles", "label", "matched", "unmatched", "mean_x", "mean_y", "ref_mean_x", "ref_mean_y", "mean_vx", "mean_vy",
+               "fit_a", "fit_b", "inertia", "ref_inertia", "spin", "angular_velocity", "stretch_sq", "reserved_17", "reserved_18",
+               "reserved_19", "reserved_20", "reserved_21", "reserved_22", "reserved_23")
+POSE_MOMENT_FIELDS = ("fit_a", "fit_b", "inertia", "ref_inertia", "spin", "matched", "reserved_6", "reserved_7")
+# what pose() returns when moments or rank are asked for; None where an output was not asked for
+Pose = collections.namedtuple("Pose", ("rows", "moments", "rank"))
+# what pose_fit() returns
+PoseFit = collections.namedtuple("PoseFit", ("theta", "omega", "rms"))
 CONTACT_WORDS = 4                                     # SB_BATCH_CONTACT_WORDS
 # the words of a row of contacts()'s touch and of its counts, in order (include/softbody.h, sb_batch_contacts_device)
 CONTACT_TOUCH_FIELDS = ("touching", "touching_other_body", "walls", "first_partner")
@@ -187,6 +197,22 @@ def body_beam_rows(result, edges, length, spring, damp, yield_strain, strain_bre
     return new_beam_rows(pairs.contiguous(), spring, damp, yield_strain, strain_break_limit, length=length)
 
 
+def pose_fit(moments):
+    """Angle, angular velocity and misfit from BatchEngine.pose()'s `moments` (float64 [..., POSE_MOMENT_WORDS]): a PoseFit of
+    float64 tensors [...] on the moments' device --
+      theta = atan2(b, a)      the rotation that best carries the reference onto the current shape,
+      omega = Lc / I           the angular velocity,
+      rms   = sqrt(max(I + I0 - 2 sqrt(a^2 + b^2), 0) / n)   the root-mean-square distance left after the best rigid fit.
+    Plain torch float64: unlike the moments these are NOT pinned bit for bit (sqrt and atan2 are the device library's).  A row
+    without a matched member gives NaN."""
+    import torch
+    if not isinstance(moments, torch.Tensor) or moments.dtype != torch.float64 or moments.shape[-1] != POSE_MOMENT_WORDS:
+        raise ValueError("pose_fit: moments must be pose()'s float64 torch tensor [..., %d]" % POSE_MOMENT_WORDS)
+    a, b, inertia, ref_inertia, spin, n = (moments[..., k] for k in range(6))
+    rest = torch.clamp(inertia + ref_inertia - 2.0 * torch.sqrt(a * a + b * b), min=0.0)
+    return PoseFit(torch.atan2(b, a), spin / inertia, torch.sqrt(rest / n))
+
+
 class SbBatchOptions(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("n_scenes", ctypes.c_uint32), ("bounds_size", ctypes.c_float),
                 ("particle_radius", ctypes.c_float), ("subticks", ctypes.c_uint32), ("max_particles", ctypes.c_uint32),
@@ -239,6 +265,7 @@ def load_library():
     L.sb_batch_nearest_device.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp, vp, vp]
     L.sb_batch_forces_device.argtypes = [vp, u32, vp, vp, vp, vp, vp]
     L.sb_batch_body_summary_device.argtypes = [vp, vp, u32, vp, vp]
+    L.sb_batch_pose_device.argtypes = [vp, vp, vp, u32, vp, vp, vp]
     L.sb_batch_load_scene.argtypes = [vp, u32, vp, sz, vp, sz, vp, sz, vp, sz]
     L.sb_batch_render_device.argtypes = [vp, ctypes.POINTER(SbBatchRenderOptions), vp]
     L.sb_batch_render_scene.argtypes = [vp, u32, ctypes.POINTER(SbBatchRenderOptions), vp, sz]
@@ -604,6 +631,48 @@ class BatchEngine(DeviceBinding):
         vp = ctypes.c_void_p
         self._ordered(tensors, lambda: load_library().sb_batch_body_summary_device(self._h, vp(ptrs[2]), rows, vp(ptrs[0]), vp(ptrs[1])))
         return (outs[0], outs[1]) if rank is not False else outs[0]
+
+    # ---- pose per body against a reference shape (sb_batch_pose_device)
+    def pose(self, labels=None, ref=None, rows=8, out=None, moments=False, rank=False):
+        """How every GROUP of particles of every scene is turned, how fast it spins and how far it is bent out of shape, in one
+        launch: a float32 tensor [n_scenes, rows, POSE_WORDS] on the batch's device (POSE_FIELDS names the columns), or, with
+        moments or rank asked for, a Pose (rows, moments, rank) with None where an output was not.  labels, rows, rank and the
+        ranking are body_summary()'s: labels=None calls self.bodies() first, on the same stream, and the groups are the bodies;
+        row k is the group of rank k -- the group of body_summary()'s row k.  ref: None -- every particle is compared with its
+        position in the scene's RESET state (the latest write_scene / checkpoint / fork; it never leaves the device), and a
+        particle spawned since then has no reference until a checkpoint() -- or a float32 tensor / device pointer
+        [n_scenes, max_particles, 2] of reference positions {X, Y} at particle DATA indices (a NaN row: no reference).  A member is
+        matched when its record is finite and it has a finite reference; a row holds particles, label, matched, unmatched, then
+        over the matched members the current centroid, the reference's centroid, the mean velocity, the fit's a and b (the rotation
+        from the reference to the current shape is atan2(b, a)), the moments of inertia of the current and of the reference shape
+        about their centroids, the spin (angular momentum about the centroid), the angular velocity spin / inertia and the squared
+        stretch inertia / ref_inertia; NaN where nothing is matched.  moments (True or a tensor / pointer): float64
+        [n_scenes, rows, POSE_MOMENT_WORDS] {a, b, I, I0, Lc, n, 0, 0} (POSE_MOMENT_FIELDS), what pose_fit() takes.  The sums are
+        those of summary()'s pinned tree over the matched members, in double, and what derives from them uses + - * / alone, so
+        rows and moments are reproducible bit for bit: an argmin over them does not flip.  out / moments / rank: a device
+        pointer (int) or a contiguous torch tensor (float32 / float64 / int32) of at least that many elements to write into.
+        Every word is written.  Only reads the batch, only enqueues; torch's current stream is ordered after it.
+
+        Upright reward, nothing exported:
+            r = be.pose()                                        # against the reset state, per body
+            upright = torch.cos(torch.atan2(r[:, 0, 11], r[:, 0, 10]))
+        Match this target shape (target: float32 [n_scenes, max_particles, 2] at data indices):
+            p = be.pose(ref=target, moments=True)
+            cost = pose_fit(p.moments).rms[:, 0]                # 0 where the largest body is the target, turned and shifted"""
+        n, maxp = self.n_scenes, self.max_particles
+        if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or not 1 <= rows <= maxp:
+            raise ValueError("pose: rows is %r, not a number in 1 .. max_particles (%d)" % (rows, maxp))
+        rows = int(rows)
+        outs, ptrs, tensors = self._bind("pose", [
+            ("out", None if out is True else out, True, (n, rows, POSE_WORDS), "float32"),
+            ("moments", None if moments is True or moments is False else moments, moments is not False, (n, rows, POSE_MOMENT_WORDS), "float64"),
+            ("rank", None if rank is True or rank is False else rank, rank is not False, (n, maxp), "int32"),
+            ("ref", ref, ref is not None, (n, maxp, 2), "float32"),
+            ("labels", (lambda: self.bodies()[0]) if labels is None else labels, True, (n, maxp), "int32")])
+        vp = ctypes.c_void_p
+        self._ordered(tensors, lambda: load_library().sb_batch_pose_device(self._h, vp(ptrs[4]), vp(ptrs[3]), rows, vp(ptrs[0]), vp(ptrs[1]),
+                                                                           vp(ptrs[2])))
+        return Pose(outs[0], outs[1], outs[2]) if moments is not False or rank is not False else outs[0]
 
     # ---- particle and wall contacts (sb_batch_contacts_device)
     def contacts(self, labels=None, pairs=0, other_body=False, touch=None, counts=None):

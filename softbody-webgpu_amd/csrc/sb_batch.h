@@ -4,7 +4,8 @@
 // body; sb_batch_cut.hip / sb_batch_add.hip / sb_batch_spawn.hip: cuts, welds and spawned particles, the latter two on
 // sb_batch_alloc.h, the allocator of their data indices; sb_batch_graph.hip: the beam graph; sb_batch_raycast.hip /
 // sb_batch_nearest.hip: range sensors and proximity queries, both on sb_batch_query.h, the plan of a query kernel;
-// sb_batch_forces.hip: the next substep's beam and contact forces), and what the
+// sb_batch_forces.hip: the next substep's beam and contact forces; sb_batch_pose.hip: the pose of every body against a reference
+// shape, on sb_batch_group_sort.h, the sort and ranking it shares with sb_batch_body_summary.hip), and what the
 // one-workgroup-per-scene kernels that only read a batch have in common: the scene header each of them opens with (sbb_scene), the
 // float <-> ordered-key codec of the reports' extremes and the width of their pinned summation tree (sb_summary_math.h), the
 // contact neighbourhood (sb_contact_cells.h, included here: the contact test, the cells' rule, window, selection and buckets); on
@@ -116,8 +117,9 @@ struct sb_batch {
     uint64_t frames_done = 0, substeps_done = 0;
     int scenes_per_cu = 0, vgprs = 0, scratch = 0;
     SbBatchRender *render = nullptr; // what the renderer keeps between calls (made at the first render)
-    SbbKernelRes render_res, summary_res, bodies_res, contacts_res, body_summary_res, cut_res, add_res, graph_res, spawn_res, raycast_res, nearest_res, forces_res; // of k_batch_render, k_batch_summary, ...
+    SbbKernelRes render_res, summary_res, bodies_res, contacts_res, body_summary_res, cut_res, add_res, graph_res, spawn_res, raycast_res, nearest_res, forces_res, pose_res; // of k_batch_render, k_batch_summary, ...
     bool body_summary_lds_allowed = false; // k_batch_body_summary may be launched with more than 64 KiB of LDS (asked for at the first such launch)
+    bool pose_lds_allowed = false;         // likewise k_batch_pose
 };
 
 extern thread_local std::string g_batch_create_error; // sb_batch.hip
@@ -190,3 +192,4 @@ bool sbb_graph_info(sb_batch *b, const char *key, uint64_t *value);
 bool sbb_raycast_info(sb_batch *b, const char *key, uint64_t *value);
 bool sbb_nearest_info(sb_batch *b, const char *key, uint64_t *value);
 bool sbb_forces_info(sb_batch *b, const char *key, uint64_t *value); // sb_batch_forces.hip
+bool sbb_pose_info(sb_batch *b, const char *key, uint64_t *value);   // sb_batch_pose.hip

@@ -1010,6 +1010,7 @@ sb_status sb_batch_get_info(sb_batch *b, const char *key, uint64_t *value)
     else if (sbb_raycast_info(b, key, value)) return SB_OK;
     else if (sbb_nearest_info(b, key, value)) return SB_OK;
     else if (sbb_forces_info(b, key, value)) return SB_OK;
+    else if (sbb_pose_info(b, key, value)) return SB_OK;
     else SB_FAIL(b, SB_ERR_INVALID, "sb_batch_get_info: unknown key '%s'", key);
     return SB_OK;
 }

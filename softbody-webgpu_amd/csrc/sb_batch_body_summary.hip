@@ -23,14 +23,9 @@
 #include <algorithm>
 #include <string>
 
-#include "sb_batch.h"
+#include "sb_batch_group_sort.h" // SBQ_BLOCK, sbq_sort, the rank key
 
-// 256 threads as the sibling kernels: the sort's W / 2 = 512 compare-exchanges of the largest capacity are two per thread, and
-// four waves keep a barrier (there are about 120 in a launch at W = 1024) cheap
-#define SBQ_BLOCK 256u
 #define SBQ_NSUM 6u // x, y, vx, vy, 0.5 (vx^2 + vy^2), x vy - y vx
-#define SBQ_NONE 0xFFFFFFFFu
-#define SBQ_LDS_DEFAULT_LIMIT (64u * 1024u) // above it a launch needs hipFuncAttributeMaxDynamicSharedMemorySize
 
 // per-label statistics words, each an array of max_particles entries
 enum {
@@ -40,28 +35,11 @@ enum {
     SBQ_MINX, SBQ_MINY, SBQ_MAXX, SBQ_MAXY, SBQ_MAX_V2, SBQ_MAX_STRAIN, SBQ_MAX_STRESS, SBQ_MIN_STRESS, SBQ_NSTAT
 };
 
-static_assert(SB_BATCH_MAX_PARTICLES <= 1024 && SB_BATCH_MAX_BEAMS < 0x10000, "a rank key holds 10 bits of label, a count word 16 bits per count");
-
 // LDS of a workgroup: double col[SBQ_NSUM][W]; uint32 key[W], rkey[W], grp[maxP], rank[maxP], stat[SBQ_NSTAT][maxP]
 static inline uint32_t sbq_lds_bytes(uint32_t maxP)
 {
     const uint32_t W = sbb_pow2_at_least(maxP);
     return W * (SBQ_NSUM * 8u + 2u * 4u) + maxP * (2u + SBQ_NSTAT) * 4u;
-}
-
-// ascending bitonic sort of a[0 .. W-1] (W a power of two) by the whole workgroup; ends in a barrier
-SB_DEV void sbq_sort(uint32_t *a, uint32_t W, uint32_t tid)
-{
-    for (uint32_t k = 2u; k <= W; k <<= 1) {
-        for (uint32_t j = k >> 1; j != 0u; j >>= 1) {
-            for (uint32_t t = tid; t < (W >> 1); t += SBQ_BLOCK) {
-                const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), p = i | j;
-                const uint32_t x = a[i], y = a[p];
-                if ((x > y) == ((i & k) == 0u)) a[i] = y, a[p] = x;
-            }
-            __syncthreads();
-        }
-    }
 }
 
 __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V, const int32_t *__restrict__ labels, uint32_t max_rows,
@@ -142,12 +120,12 @@ __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V,
     // ---- the ranking: particles descending, then label ascending
     for (uint32_t q = tid; q < W; q += SBQ_BLOCK) {
         const uint32_t np = q < maxP ? (s_stat[SBQ_NP * maxP + q] & 0xffffu) : 0u;
-        s_rkey[q] = np ? ~((np << 10) | (1023u - q)) : SBQ_NONE;
+        s_rkey[q] = sbq_rank_key(np, q);
     }
     __syncthreads();
     sbq_sort(s_rkey, W, tid);
     for (uint32_t q = tid; q < W; q += SBQ_BLOCK)
-        if (s_rkey[q] != SBQ_NONE) s_rank[1023u - (~s_rkey[q] & 1023u)] = q;
+        if (s_rkey[q] != SBQ_NONE) s_rank[sbq_rank_label(s_rkey[q])] = q;
 
     // ---- the members in key order, their leaves behind them
     sbq_sort(s_key, W, tid);
@@ -209,7 +187,7 @@ __global__ __launch_bounds__(SBQ_BLOCK) void k_batch_body_summary(SbBatchView V,
                 row[k] = sbu_empty_body_word(k);
             continue;
         }
-        const uint32_t g = 1023u - (~rkey & 1023u);
+        const uint32_t g = sbq_rank_label(rkey);
         const uint32_t cp = s_stat[SBQ_NP * maxP + g], cb = s_stat[SBQ_NB * maxP + g];
         const uint32_t np = (cp & 0xffffu) - (cp >> 16), nb = (cb & 0xffffu) - (cb >> 16);
         row[0] = (float)(cp & 0xffffu);
